@@ -56,6 +56,9 @@ other cards idle): rank 0's is the same-run single-shard reference.  The line th
 the MAX over ranks of the wall-clock block): `value_device` (sum over ranks of E*A / the rank's median kernel time: immune to host
 jitter), `scaling_efficiency` = value / (N x the single-shard reference) and `scaling_efficiency_device`, `per_rank` (every rank's
 medians, min / median / max), `process_group`, `rccl_version`.  R: --repeats, else 5, else 25 when a block is shorter than 2 ms.
+--dump-outputs DIR: the headline's results for output-for-output comparison of two builds.  The warm-up ramp and R depend on the
+clock, so the timed blocks do not start from a fixed state; after them the env is rewound to its state before the warm-up (after
+the stagger, which is fixed) and ONE more K-step block runs through the same path, untimed; what its last step returned goes to DIR.
 """
 import argparse
 import json
@@ -337,7 +340,36 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-on-device0", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (implies --backend gloo; at most 6 ranks may share the card)")
     ap.add_argument("--digest-dir", default=None, help="every rank writes a digest of its shard's final state here (cross-process shard check)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed blocks, rewind the headline env to its state before the warm-up, run ONE more K-step block through "
+                         "the same timed path and write what its last step returned (rank 0's shard) as DIR/obs.npy, rew.npy, done.npy "
+                         "(float32; a seeded sample of the games, listed in DIR/games.npy, when they would exceed 64 MB): the same "
+                         "arguments give the same inputs, so two builds can be compared output for output")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, obs, rew, done):
+    """obs [E, A, D], rew [E, A], done [E, A] of one step -> d/*.npy as float32; above DUMP_LIMIT_BYTES a fixed, seeded sample
+    of the games (the same games for the same E) is written instead, and its game indices go to d/games.npy (float64)."""
+    import numpy as np
+    import torch
+    arrays = {"obs": obs, "rew": rew, "done": done}
+    E = obs.shape[0]
+    per_game = sum(a[0].numel() for a in arrays.values()) * 4
+    if E * per_game > DUMP_LIMIT_BYTES:
+        m = (DUMP_LIMIT_BYTES - 4096) // (per_game + 8)     # (4096: room for the .npy headers)
+        games = np.sort(np.random.default_rng(1234).choice(E, m, replace=False))
+        idx = torch.as_tensor(games, device=obs.device)
+        arrays = {k: a.index_select(0, idx) for k, a in arrays.items()}
+        arrays["games"] = torch.as_tensor(games.astype(np.float64))
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        a = a.detach().cpu()
+        np.save(os.path.join(d, f"{k}.npy"), a.numpy() if a.dtype == torch.float64 else a.to(torch.float32).numpy())
+    return sorted(f"{k}.npy" for k in arrays)
 
 
 def self_launch(args):
@@ -538,8 +570,10 @@ def main():
         turn = torch.where(hy * (600 - px) - hx * (400 - py) > 0, 2, 3)
         return torch.where(out | near_base, turn, torch.ones_like(turn)).to(torch.int32)
 
-    def measure(n, E, K, W, mode, graph_len, mix="uniform", continuous=False, R=None, do_stagger=True, chains=1, tag=None):
-        """K timed step() calls of E games x n-v-n on this rank, R times -> dict(env, walls, kms, G, live)."""
+    def measure(n, E, K, W, mode, graph_len, mix="uniform", continuous=False, R=None, do_stagger=True, chains=1, tag=None, dump=False):
+        """K timed step() calls of E games x n-v-n on this rank, R times -> dict(env, walls, kms, G, live, outputs).
+        dump: afterwards one more K-step block from the state before the warm-up (its length depends on the clock); outputs = the
+        (obs, rew, done) its last step returned."""
         A = 2 * n
         R = R or args.repeats
         env = sharding.make_shard(E * world, rank, world, n_agents=n, device=dev, seed=1234, auto_reset=True,
@@ -597,9 +631,11 @@ def main():
         if mix != "dense" and do_stagger and not args.no_stagger:
             stagger(env, lambda k: env.step_batch(actions[k % TT]))
         run_b, Kb = None, None
+        last = [None]                                       # the (obs, rew, done) a caller of the timed path received from its last step
         if mode == "graph":
-            graphs = [env.capture_steps(actions[i * G:(i + 1) * G], chains=chains)[0] for i in range(NG)]
-            graph = graphs[0]
+            caps = [env.capture_steps(actions[i * G:(i + 1) * G], chains=chains) for i in range(NG)]
+            graphs = [g for g, _ in caps]
+            last[0] = caps[0][1]                            # every replay and every plain call writes the env-owned tensors
 
             def run(steps):
                 for _ in range(steps // G):
@@ -627,11 +663,13 @@ def main():
                 r = steps % G
                 if r:
                     env.step_many(actions[:r], store=True, out=tuple(o[:r] for o in outs))
+                last[0] = tuple(o[(r or G) - 1] for o in outs)
         else:
             def run(steps):
                 for t in range(steps):
-                    env.step_batch(actions[pos[0] % TT])
+                    last[0] = env.step_batch(actions[pos[0] % TT])
                     pos[0] += 1
+        snap0 = env.state_dict() if dump and not restore else None
         if not restore:
             run(W)
             ramp(run, args.ramp_ms, K)
@@ -655,7 +693,18 @@ def main():
         walls, kms = timed_blocks(run, K, R, restore, run_b, Kb, tag)
         if live is None and E * A <= (1 << 22):
             live = round(float(env.export_state(("bl_live",))["bl_live"].float().sum()) / (E * A), 3)
-        return dict(env=env, walls=walls, kms=kms, G=G, live=live, Kb=Kb or K, solo=solo)
+        outputs = None
+        if dump:                                            # untimed: the warm-up's length depends on the clock, this block's start does not
+            if restore:
+                restore()
+            else:
+                env.load_state_dict(snap0)
+                pos[0] = 0
+            run(K)
+            torch.cuda.synchronize(dev)
+            outputs = tuple(t.clone() for t in last[0])
+            del snap0
+        return dict(env=env, walls=walls, kms=kms, G=G, live=live, Kb=Kb or K, solo=solo, outputs=outputs)
 
     def two_wave(n, continuous, many, E):
         """csrc split_applies(): 1v1 launches run as a two-wave kernel (bsx_step_split.h) -- discrete multi-tick launches of up to 65 536
@@ -725,8 +774,13 @@ def main():
         fd, dense_tmp = tempfile.mkstemp(prefix="bsx_dense_", suffix=".pt", dir="/tmp")
         os.close(fd)
         args.dense_record = dense_tmp
-    head = measure(n, E, K, W, args.mode, args.graph_len, mix=args.action_mix, continuous=args.continuous, chains=args.chains, tag="head_")
+    head = measure(n, E, K, W, args.mode, args.graph_len, mix=args.action_mix, continuous=args.continuous, chains=args.chains, tag="head_",
+                   dump=bool(args.dump_outputs))
     env = head["env"]
+    if args.dump_outputs and rank == 0:
+        files = dump_outputs(os.path.abspath(args.dump_outputs), *head["outputs"])
+        print(f"bench: wrote {', '.join(files)} to {args.dump_outputs}", file=sys.stderr, flush=True)
+    head["outputs"] = None
     games = sharding.reduce_counters(sharding.local_counter_sums(env).to(red_dev), group=tgroup)   # logging only, after the timed region
     if args.digest_dir:
         # cross-process shard check (tests/test_hip_sharding.py): what this rank's games look like after the run

@@ -180,6 +180,33 @@ def test_bench_bullet_heavy_workload_really_holds_many_bullets():
     assert "keep-shooting" in d["config"]["workload"] and d["config"]["graph_len"] == 150
 
 
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the last step's obs / rew / done of the timed path as float32 .npy files.  Two runs with the same
+    arguments write the same bits although their clock-driven warm-ups differ, and the eager path writes what the graph path
+    wrote; `--steps` is the number of steps of a timed block and the line's ms_per_step is per one of them."""
+    import json, os, statistics, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    E, K = 65536, 30
+    got = {}
+    for name, mode in (("a", "graph"), ("b", "graph"), ("c", "eager")):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(K), "--warmup", "5", "--repeats", "2", "--mode", mode,
+                              "--no-cpu-baseline", "--no-other-workloads", "--no-live-traffic", "--dump-outputs", str(tmp_path / name)],
+                             capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == K and abs(d["ms_per_step"] - statistics.median(d["timing"]["ms_per_step_samples"])) < 2e-6
+        assert abs(d["value"] - E * 2 * K / (d["ms_per_step"] * 1e-3 * K)) / d["value"] < 1e-3
+        assert sorted(os.listdir(tmp_path / name)) == ["done.npy", "obs.npy", "rew.npy"]
+        got[name] = {k: np.load(tmp_path / name / f"{k}.npy") for k in ("obs", "rew", "done")}
+    a = got["a"]
+    assert a["obs"].shape == (E, 2, 5) and a["rew"].shape == (E, 2) and a["done"].shape == (E, 2)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert set(np.unique(a["done"])) <= {0.0, 1.0} and a["rew"].any()
+    for other in ("b", "c"):
+        for k in a:
+            assert np.array_equal(a[k], got[other][k]), (other, k)
+
+
 def test_dropin_io_lives_in_pinned_host_memory_and_custom_rows_still_reach_the_device():
     """Drop-in mode: the kernels read the action / random() block from and write obs / rewards / dones to pinned host memory
     (no staging copies); a tensor that is neither device nor pinned memory must never be handed to a kernel -- the scripted

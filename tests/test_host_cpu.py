@@ -343,6 +343,29 @@ def test_bench_action_table_is_shard_invariant_and_uniform():
     assert float(f.min()) >= -1.0 and float(f.max()) < 1.0 and abs(float(f.mean())) < 0.02
 
 
+def test_bench_dump_outputs_stays_under_64_mb_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one step's obs / rew / done as float32 .npy files; a batch whose files would pass 64 MB is
+    written as the same seeded sample of its games every time, with the sampled game indices beside it."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    E = 1000
+    obs, rew, done = torch.randn(E, 2, 5), torch.randn(E, 2), torch.rand(E, 2) < 0.5
+    assert bench.dump_outputs(str(tmp_path / "small"), obs, rew, done) == ["done.npy", "obs.npy", "rew.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "obs.npy"), obs.numpy())
+    assert np.array_equal(np.load(tmp_path / "small" / "done.npy"), done.numpy().astype(np.float32))
+    E = 3 << 20                                                 # 3 M games of 1v1: 168 MB of outputs
+    obs, rew, done = torch.randn(E, 2, 5), torch.randn(E, 2), torch.zeros(E, 2, dtype=torch.bool)
+    for d in ("big1", "big2"):
+        files = bench.dump_outputs(str(tmp_path / d), obs, rew, done)
+        assert files == ["done.npy", "games.npy", "obs.npy", "rew.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+    g = np.load(tmp_path / "big1" / "games.npy")
+    assert g.dtype == np.float64 and np.array_equal(g, np.load(tmp_path / "big2" / "games.npy")) and np.all(np.diff(g) > 0)
+    o = np.load(tmp_path / "big1" / "obs.npy")
+    assert o.dtype == np.float32 and np.array_equal(o, obs.numpy()[g.astype(np.int64)])
+
+
 def test_bench_multi_gpu_launch_without_gpus_fails_loudly():
     """`python bench.py --gpus 2` launched plainly starts its own ranks; on a box with fewer cards it must say so, not hang."""
     import torch
