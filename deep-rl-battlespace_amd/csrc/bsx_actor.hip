@@ -27,6 +27,7 @@
 
 #include "battlespace_hip.h"
 #include "bsx_actor_core.h"
+#include "bsx_args.h"
 
 namespace {
 
@@ -187,8 +188,6 @@ __global__ __launch_bounds__(TPB) void bsx_actor_kernel(const ActorArgs p) {
     }
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -202,9 +201,9 @@ int bsx_actor_blob_floats(int obs_len, int* floats_per_agent) {
 int bsx_actor_forward(const float* weights, const float* obs, float* scores, int64_t E, int n, int precision,
                       const BsxActorNoise* noise, uint64_t seed, uint64_t seq, const uint64_t* seq_base, int64_t env_offset,
                       void* stream) {
-    if (!weights || !obs || !scores || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
-    if (precision != BSX_ACTOR_F32 && precision != BSX_ACTOR_BF16X3 && precision != BSX_ACTOR_BF16X6) return BSX_E_ARG;
-    if (!aligned(weights, 16) || !aligned(scores, 16) || !aligned(obs, 4)) return BSX_E_ALIGN;
+    if (!obs || !scores || (precision != BSX_ACTOR_F32 && precision != BSX_ACTOR_BF16X3 && precision != BSX_ACTOR_BF16X6)) return BSX_E_ARG;
+    if (const int rc = check_games(weights, E, n, 16)) return rc;
+    if (!aligned(scores, 16) || !aligned(obs, 4)) return BSX_E_ALIGN;
     BsxActorNoise nz = {};
     if (noise) nz = *noise;
     if (nz.ou_scale > 0.f && (!nz.ou_state || !aligned(nz.ou_state, 16))) return nz.ou_state ? BSX_E_ALIGN : BSX_E_ARG;

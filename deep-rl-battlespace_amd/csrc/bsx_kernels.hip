@@ -31,10 +31,12 @@
 // Build: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off   (no FMA contraction: positions are float64 add-then-
 // truncate in the reference, sprites.py:130-131,332-333, and must round exactly as CPython rounds them).
 
+#include <array>
 #include <mutex>
 #include <unordered_map>
 
 #include "bsx_config.h"
+#include "bsx_args.h"
 #include "bsx_state.h"
 #include "bsx_rng.h"
 #include "bsx_geometry.h"
@@ -242,8 +244,6 @@ __global__ __launch_bounds__(TPB) void bsx_instinct_kernel(const InstinctArgs p)
     instinct_continuous_action(td, ta, r0, n0, n1, n2, out[0], out[1], out[2]);
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // Which action family has advanced a state block (ABI 14: the discrete kernels keep headings as whole degrees in the plane record, the
 // continuous ones as float64 beside it -- a parallel_env has one mode for its life, battle_env.py:73).  Kept on the HOST, per state
 // address: nothing on the step path reads or writes device memory for it.  bsx_state_init and a bsx_reset of ALL games forget the
@@ -266,16 +266,6 @@ inline int grid_for(int64_t E, int n, int tpb = TPB) {
     return int((E + epb - 1) / epb);
 }
 
-template <bool CONT, bool MULTI, bool LG, bool OFF32>
-void launch_for_n_w(int n, dim3 grid, dim3 block, hipStream_t s, const StepArgs& a, int64_t bound) {
-    switch (n) {
-        case 1: hipLaunchKernelGGL((bsx_step_kernel<1, CONT, MULTI, false, LG, OFF32>), grid, block, 0, s, bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-        case 2: hipLaunchKernelGGL((bsx_step_kernel<2, CONT, MULTI, false, LG, OFF32>), grid, block, 0, s, bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-        case 3: hipLaunchKernelGGL((bsx_step_kernel<3, CONT, MULTI, false, LG, OFF32>), grid, block, 0, s, bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-        case 4: hipLaunchKernelGGL((bsx_step_kernel<4, CONT, MULTI, false, LG, OFF32>), grid, block, 0, s, bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-        default: hipLaunchKernelGGL((bsx_step_kernel<0, CONT, MULTI, false, LG, OFF32>), grid, block, 0, s, bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-    }
-}
 // 32-bit offsets when every array of the job stays below 4 GB: an observation row is at most 4 (3 * 16 + 2) = 200 bytes per agent,
 // the widest state rows are the exact-path step ring's (12 x 16 bytes per agent, allocated but all but never touched).
 inline bool narrow_offsets_ok(int64_t E, int n, uint32_t flags) {
@@ -302,71 +292,104 @@ inline bool split_applies(int n, const StepArgs& a, int64_t bound) {
     if (CONT) return !MULTI && bound <= SPLIT_CONT_MAX_GAMES;   // (continuous actions: the per-call form only)
     return bound <= (MULTI ? SPLIT_MANY_MAX_GAMES : SPLIT_MAX_GAMES);
 }
-template <bool LG, bool OFF32, int MANY, bool CONT = false, bool DRAW = false>
-void launch_split(dim3 grid, hipStream_t s, const StepArgs& a, int64_t bound) {
-    hipLaunchKernelGGL((bsx_step_split_kernel<LG, OFF32, MANY, CONT, DRAW>), grid, dim3(2 * SPB), 0, s, bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a);
-}
-template <bool CONT, bool MULTI, bool LG>
-void launch_for_n(int n, dim3 grid, dim3 block, hipStream_t s, const StepArgs& a, int64_t bound) {
-    if constexpr (!CONT) {
-        if (split_applies<CONT, MULTI>(n, a, bound)) {   // (the grid is the same: one workgroup per 64 agents, of two waves instead of one)
-            const bool narrow = narrow_offsets_ok(a.E, n, a.flags);
-            if constexpr (!MULTI) {
-                if (bound <= SPLIT_DRAW_MAX_GAMES) {
-                    if (narrow) launch_split<LG, true, 0, false, true>(grid, s, a, bound); else launch_split<LG, false, 0, false, true>(grid, s, a, bound);
-                } else {                                     // seven waves per SIMD: no room beside the first waves for the geometry wave's draw
-                    if (narrow) launch_split<LG, true, 0>(grid, s, a, bound); else launch_split<LG, false, 0>(grid, s, a, bound);
-                }
-            } else if (bound > SPLIT_MANY_FORM2_FROM) {    // two workgroups on some SIMD: the outputs wave that repeats no game logic (form 2)
-                if (narrow) launch_split<LG, true, 2>(grid, s, a, bound); else launch_split<LG, false, 2>(grid, s, a, bound);
-            } else {                                         // one workgroup per SIMD at most: the outputs wave that carries the state too (form 1)
-                if (narrow) launch_split<LG, true, 1>(grid, s, a, bound); else launch_split<LG, false, 1>(grid, s, a, bound);
-            }
-            return;
-        }
-    } else if constexpr (!MULTI) {
-        if (split_applies<CONT, MULTI>(n, a, bound)) {
-            if (narrow_offsets_ok(a.E, n, a.flags)) launch_split<false, true, 0, true, true>(grid, s, a, bound);
-            else launch_split<false, false, 0, true, true>(grid, s, a, bound);
-            return;
-        }
+
+// Both step-kernel templates (bsx_step_kernel.h, bsx_step_split.h) take these arguments: the game count of the launch and the pointers of a
+// wave's first loads lead, so that they arrive in SGPRs with the dispatch (-amdgpu-kernarg-preload-count=15, build.py).
+using StepKernel = void (*)(const int64_t, const uint2* const, const uint2* const, const uint2* const, const void* const, const uint2* const,
+                            const uint32_t* const, const int, const StepArgs);
+
+// The one dispatch of a launch's team size and offset width to template arguments: f(std::integral_constant<int, N>, std::bool_constant<OFF32>)
+// with N = n for 1v1 ... 4v4 (kernels compiled for their team size), N = 0 beyond (n read at run time).
+template <class F>
+StepKernel by_team_and_offsets(int n, bool off32, F f) {
+    const auto w = [&](auto N) { return off32 ? f(N, std::true_type{}) : f(N, std::false_type{}); };
+    switch (n) {
+        case 1: return w(std::integral_constant<int, 1>{});
+        case 2: return w(std::integral_constant<int, 2>{});
+        case 3: return w(std::integral_constant<int, 3>{});
+        case 4: return w(std::integral_constant<int, 4>{});
+        default: return w(std::integral_constant<int, 0>{});
     }
-    if (narrow_offsets_ok(a.E, n, a.flags)) launch_for_n_w<CONT, MULTI, LG, true>(n, grid, block, s, a, bound);
-    else launch_for_n_w<CONT, MULTI, LG, false>(n, grid, block, s, a, bound);
 }
 
-// T == 0: one call (bsx_step_*);  T >= 1: bsx_step_many_* -- T calls in one launch, arrays with a leading T axis
+// The kernel choice and the launch of every step-kernel form: per call (MULTI = false), T calls in one launch (MULTI), their two-wave 1v1
+// forms, and the fused rollout (ACTOR: T x (actor -> step), MULTI as well).  `bound` = the games of the launch (a range's count).
+template <bool CONT, bool MULTI, bool ACTOR, bool LG>
+int launch_for_n(const StepArgs& a, int64_t bound, void* stream) {
+    const int n = a.n;
+    const bool two_wave = !ACTOR && split_applies<CONT, MULTI>(n, a, bound);
+    const StepKernel k = by_team_and_offsets(n, narrow_offsets_ok(a.E, n, a.flags), [&](auto N_, auto OFF32_) -> StepKernel {
+        constexpr int N = decltype(N_)::value;
+        constexpr bool OFF32 = decltype(OFF32_)::value;
+        if constexpr (ACTOR) {
+            if constexpr (N == 0) return nullptr;          // (never: the fused rollout is built for 1v1 ... 4v4 and refuses larger teams)
+            else return bsx_step_kernel<N, CONT, true, true, false, OFF32>;
+        } else {
+            if constexpr (N == 1 && !(CONT && MULTI)) {
+                if (two_wave) {
+                    if constexpr (MULTI)                   // two workgroups on some SIMD: the outputs wave that repeats no game logic (form 2);
+                        return bound > SPLIT_MANY_FORM2_FROM ? bsx_step_split_kernel<LG, OFF32, 2>   // else the one that carries the state too (form 1)
+                                                             : bsx_step_split_kernel<LG, OFF32, 1>;
+                    else if constexpr (CONT)
+                        return bsx_step_split_kernel<false, OFF32, 0, true, true>;
+                    else                                   // seven waves per SIMD: no room beside the first waves for the geometry wave's draw
+                        return bound <= SPLIT_DRAW_MAX_GAMES ? bsx_step_split_kernel<LG, OFF32, 0, false, true>
+                                                             : bsx_step_split_kernel<LG, OFF32, 0>;
+                }
+            }
+            return bsx_step_kernel<N, CONT, MULTI, false, LG, OFF32>;
+        }
+    });
+    // a workgroup per 64 agents -- one wave, or the two waves of the two-wave kernels -- or, in the fused rollout, per 32 games = G/2 waves
+    // (an MFMA tile is 32 rows of ONE actor, bsx_step_kernel.h)
+    const dim3 grid(ACTOR ? unsigned((bound + 31) / 32) : unsigned(grid_for(bound, n, SPB * WPB)));
+    const dim3 block(ACTOR ? SPB * group_width(n) / 2 : (two_wave ? 2 * SPB : SPB * WPB));
+    hipLaunchKernelGGL(k, grid, block, 0, static_cast<hipStream_t>(stream),
+                       bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a);
+    return int(hipGetLastError());
+}
+
+// The StepArgs fields every step-kernel launch sets; the rest stay zero unless the step or the rollout path sets them.
+StepArgs step_args(void* state, int64_t E, int n, int T, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner,
+                   uint8_t* env_done_t, const BsxRewards* cfg, uint32_t flags, uint64_t seed, int64_t env_offset) {
+    StepArgs a{};
+    a.st = state_ptrs(state, E, n);
+    a.E = E; a.n = n; a.T = T;
+    a.rew = rew; a.done = done; a.env_done = env_done; a.winner = winner; a.env_done_t = env_done_t;
+    a.cfg = *cfg; a.flags = flags; a.seed = seed; a.env_offset = env_offset; a.tie_tick = tie_tick_const(n);
+    a.scripted_team = -1;                                  // (no scripted opponent)
+    return a;
+}
+
+// What tells the six step entry points apart besides CONT: a game range (bsx_step_*_range; count < 0 = the rest of the batch) and
+// T >= 1 calls in one launch (bsx_step_many_*: arrays with a leading T axis, every tick's outputs kept when store_all).
+struct StepCall { int64_t first = 0, count = -1; int T = 0; int store_all = 0; uint8_t* env_done_t = nullptr; };
+
 template <bool CONT>
-int launch_step(void* state, int64_t E, int n, const void* actions, int action_kind, const double* u, float* obs,
-                float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, const BsxRewards* cfg, uint32_t flags,
-                uint64_t seed, int64_t env_offset, void* stream, int T = 0, int store_all = 0, uint8_t* env_done_t = nullptr,
-                int64_t first = 0, int64_t count = -1) {
-    if (T < 0 || T > BSX_MAX_T) return BSX_E_ARG;
-    if (count < 0) count = E - first;
+int step(const StepCall& c, void* state, int64_t E, int n, const void* actions, int action_kind, const double* u, float* obs, float* rew,
+         uint8_t* done, uint8_t* env_done, uint8_t* winner, const BsxRewards* cfg, uint32_t flags, uint64_t seed, int64_t env_offset,
+         void* stream) {
+    const int T = c.T;
+    const int64_t first = c.first, count = c.count < 0 ? E - first : c.count;
     // a sub-range of the games (bsx_step_*_range): whole 256-game blocks, so that every array the launch is handed stays aligned as the
     // full arrays are; the one-call form only (a multi-tick launch strides its per-tick arrays by the games it steps)
-    if (first < 0 || count <= 0 || first > E - count || (first & 255) || ((first || count != E) && T != 0)) return BSX_E_ARG;
-    if (!state || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N || !obs || !rew || !done || !cfg) return BSX_E_ARG;
-    if (!actions && !(flags & BSX_F_EMPTY_CALL)) return BSX_E_ARG;
-    if (!aligned(state, 256) || !aligned(obs, 4) || !aligned(rew, 4) || (u && !aligned(u, 8))) return BSX_E_ALIGN;
+    if (T < 0 || T > BSX_MAX_T || first < 0 || count <= 0 || first > E - count || (first & 255) || ((first || count != E) && T != 0))
+        return BSX_E_ARG;
+    if (!obs || !rew || !done || !cfg || (!actions && (T || !(flags & BSX_F_EMPTY_CALL)))) return BSX_E_ARG;   // (an empty call is a single call)
+    if (const int rc = check_games(state, E, n)) return rc;
+    if (!aligned(obs, 4) || !aligned(rew, 4) || (u && !aligned(u, 8))) return BSX_E_ALIGN;
     if (!CONT && action_kind == BSX_ACT_LOGITS_F32 && !aligned(actions, 16)) return BSX_E_ALIGN;
     if (!CONT && action_kind != BSX_ACT_I32 && action_kind != BSX_ACT_LOGITS_F32) return BSX_E_ARG;
     if (CONT && action_kind != BSX_ACT_F32 && action_kind != BSX_ACT_F64 && action_kind != BSX_ACT_F32X4) return BSX_E_ARG;
     if (CONT && action_kind == BSX_ACT_F32X4 && !aligned(actions, 16)) return BSX_E_ALIGN;
     if (!family_claim(state, CONT)) return BSX_E_FAMILY;
-    StepArgs a;
-    a.st = state_ptrs(state, E, n);
-    a.E = E; a.n = n; a.actions = actions; a.action_kind = action_kind; a.u = u;
+    StepArgs a = step_args(state, E, n, T, rew, done, env_done, winner, c.env_done_t, cfg, flags, seed, env_offset);
+    a.actions = actions; a.action_kind = action_kind; a.u = u; a.obs = obs;
     if (!actions) { a.actions = state; a.action_kind = -1; }   // empty call: the kernel reads (and ignores) one mapped word instead of selecting a pointer
-    a.obs = obs; a.rew = rew; a.done = done; a.env_done = env_done; a.winner = winner; a.env_done_t = env_done_t;
-    a.cfg = *cfg; a.flags = flags; a.seed = seed; a.env_offset = env_offset; a.tie_tick = bsx_tie_tick(n);
     const int64_t EA = E * 2 * n;
-    a.aw = nullptr; a.aprec = 0; a.scripted_team = -1; a.iseed = 0; a.obs0 = nullptr; a.scores = nullptr; a.scores_ts = 0; a.nz = BsxActorNoise{};
-    a.aseed = 0; a.aseq = 0; a.aseq_base = nullptr;
-    a.T = T;
     a.act_tb = EA * (CONT ? (action_kind == BSX_ACT_F32 ? 12 : (action_kind == BSX_ACT_F64 ? 24 : 16)) : (action_kind == BSX_ACT_I32 ? 4 : 16));
     a.u_ts = EA;
-    a.obs_ts = store_all ? EA * (3 * n + 2) : 0; a.rew_ts = store_all ? EA : 0; a.done_ts = store_all ? EA : 0;
+    a.obs_ts = c.store_all ? EA * (3 * n + 2) : 0; a.rew_ts = c.store_all ? EA : 0; a.done_ts = c.store_all ? EA : 0;
     if (first) {
         // Every array is indexed by game, by agent row (game * 2n + plane) or by wave block (the bullet pools), the two birth-tick rings by
         // slot * (E * 2n) + agent row with the stride taken from a.E: advancing each pointer to the range's first row turns the kernel's
@@ -382,17 +405,53 @@ int launch_step(void* state, int64_t E, int n, const void* actions, int action_k
         if (winner) a.winner += first;
         a.env_offset += first;                             // the draws are keyed by the global game index
     }
-    const dim3 grid(grid_for(count, n, SPB * WPB)), block(SPB * WPB);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const bool lg = !CONT && action_kind == BSX_ACT_LOGITS_F32;
-    if (T == 0) {
-        if (lg) launch_for_n<CONT, false, !CONT>(n, grid, block, s, a, count);
-        else launch_for_n<CONT, false, false>(n, grid, block, s, a, count);
-    } else {
-        if (lg) launch_for_n<CONT, true, !CONT>(n, grid, block, s, a, count);
-        else launch_for_n<CONT, true, false>(n, grid, block, s, a, count);
-    }
-    return int(hipGetLastError());
+    if (T == 0) return lg ? launch_for_n<CONT, false, false, !CONT>(a, count, stream) : launch_for_n<CONT, false, false, false>(a, count, stream);
+    return lg ? launch_for_n<CONT, true, false, !CONT>(a, count, stream) : launch_for_n<CONT, true, false, false>(a, count, stream);
+}
+
+// T x (actor -> step) in one launch; CONT = continuous actions (three actor outputs, BSX_ACT_F32X4 rows)
+template <bool CONT>
+int rollout(void* state, int64_t E, int n, int T, const float* weights, int precision, int scripted_team, uint64_t scripted_seed, float* obs,
+            float* scores, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg,
+            uint32_t flags, const BsxActorNoise* noise, uint64_t actor_seed, uint64_t seq, const uint64_t* seq_base, uint64_t seed,
+            int64_t env_offset, void* stream) {
+    if (T < 1 || T > BSX_MAX_T || !weights || !obs || !scores || !rew || !done || !cfg || (flags & BSX_F_EMPTY_CALL) ||
+        (precision != BSX_ACTOR_F32 && precision != BSX_ACTOR_BF16X3 && precision != BSX_ACTOR_BF16X6) || scripted_team < -1 || scripted_team > 1)
+        return BSX_E_ARG;
+    if (const int rc = check_games(state, E, n, 256, 4)) return rc;
+    if (!aligned(weights, 16) || !aligned(scores, 16) || !aligned(obs, 4) || !aligned(rew, 4)) return BSX_E_ALIGN;
+    BsxActorNoise nz = {};
+    if (noise) nz = *noise;
+    if (nz.ou_scale > 0.f && (!nz.ou_state || !aligned(nz.ou_state, 16))) return nz.ou_state ? BSX_E_ALIGN : BSX_E_ARG;
+    if (nz.z_inject || nz.u_inject) return BSX_E_ARG;    // injected draws are per call: bsx_actor_forward only
+    if (nz.sample_mode != 0 && (nz.sample_mode != 1 || !(nz.temperature > 0.f) || CONT)) return BSX_E_ARG;   // a categorical head belongs to discrete actions
+    if ((nz.logp && !aligned(nz.logp, 4)) || (nz.value_weights && !aligned(nz.value_weights, 16))) return BSX_E_ALIGN;
+    if (nz.value_weights && (n != 1 || !nz.value || !aligned(nz.value, 4))) return BSX_E_ARG;          // the value head rides in the 1v1 kernel only
+    if (!family_claim(state, CONT)) return BSX_E_FAMILY;
+    const int64_t EA = E * 2 * n, D = 3 * n + 2;
+    StepArgs a = step_args(state, E, n, T, rew, done, env_done, winner, env_done_t, cfg, flags, seed, env_offset);
+    a.action_kind = CONT ? BSX_ACT_F32X4 : BSX_ACT_LOGITS_F32;
+    a.obs = obs + EA * D; a.obs_ts = EA * D; a.rew_ts = EA; a.done_ts = EA;
+    a.aw = weights; a.aprec = precision; a.scripted_team = scripted_team; a.obs0 = obs; a.scores = scores; a.scores_ts = EA * 4; a.nz = nz;
+    a.aseed = actor_seed; a.aseq = seq; a.aseq_base = seq_base; a.iseed = scripted_seed;
+    return launch_for_n<CONT, true, true, false>(a, E, stream);
+}
+
+// The heading table through the host libm, exactly as calc_new_xy evaluates it (sprites.py:40-41) with speed*time = 215*0.1: built on
+// first use (a function-local static is initialised once, thread-safely) and never written again, so state_init copies from it as is.
+const std::array<double2, 361>& heading_table() {
+    static const std::array<double2, 361> lut = [] {
+        std::array<double2, 361> t;
+        const double st = 215 * 0.1;
+        for (int d = 0; d <= 360; ++d) {
+            const double ang = -(double(d) * DEG2RAD);
+            t[d].x = st * cos(ang);
+            t[d].y = st * sin(ang);
+        }
+        return t;
+    }();
+    return lut;
 }
 
 }  // namespace
@@ -411,41 +470,23 @@ int bsx_host_device_pointer(void* host, void** device) {
     return int(hipHostGetDevicePointer(device, host, 0));
 }
 
-int bsx_tie_tick(int n) {
-    // battle_env.py:168,316-319: total_time += 0.1 (binary64) until >= 10 + 2n
-    const double max_time = double(10 + n * 2);
-    volatile double t = 0.0;
-    int k = 0;
-    for (;;) {
-        t = t + 0.1;
-        ++k;
-        if (t >= max_time) return k;
-    }
-}
+int bsx_tie_tick(int n) { return tie_tick_const(n); }     // battle_env.py:168,316-319: total_time += 0.1 (binary64) until >= 10 + 2n
 
 int bsx_state_bytes(int64_t E, int n, size_t* bytes) {
-    if (E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N || !bytes) return BSX_E_ARG;
+    if (const int rc = check_games(bytes, E, n, 1)) return rc;
     *bytes = make_layout(E, n).total;
     return 0;
 }
 
 int bsx_state_init(void* state, int64_t E, int n, void* stream) {
-    if (!state || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
-    if (!aligned(state, 256)) return BSX_E_ALIGN;
+    if (const int rc = check_games(state, E, n)) return rc;
     const Layout L = make_layout(E, n);
     family_forget(state);
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t err = hipMemsetAsync(state, 0, L.total, s);
     if (err != hipSuccess) return int(err);
-    // heading table through the host libm, exactly as calc_new_xy evaluates it (sprites.py:40-41) with speed*time = 215*0.1
-    static double2 lut[361];
-    const double st = 215 * 0.1;
-    for (int d = 0; d <= 360; ++d) {
-        const double ang = -(double(d) * DEG2RAD);
-        lut[d].x = st * cos(ang);
-        lut[d].y = st * sin(ang);
-    }
-    err = hipMemcpyAsync(static_cast<char*>(state) + L.lut, lut, sizeof(lut), hipMemcpyHostToDevice, s);
+    const std::array<double2, 361>& lut = heading_table();
+    err = hipMemcpyAsync(static_cast<char*>(state) + L.lut, lut.data(), sizeof(double2) * lut.size(), hipMemcpyHostToDevice, s);
     if (err != hipSuccess) return int(err);
     // every env starts finished (done = 1), so a step before the first reset is the inert call of battle_env.py:303-306
     hipLaunchKernelGGL(bsx_mark_done_kernel, dim3(unsigned((E + TPB - 1) / TPB)), dim3(TPB), 0, s,
@@ -461,8 +502,8 @@ int bsx_state_release(void* state) {
 
 int bsx_reset(void* state, int64_t E, int n, const uint8_t* reset_mask, const int32_t* spawn, uint64_t seed,
               uint64_t nonce, int64_t env_offset, float* obs, void* stream) {
-    if (!state || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
-    if (!aligned(state, 256) || (spawn && !aligned(spawn, 4)) || (obs && !aligned(obs, 4))) return BSX_E_ALIGN;
+    if (const int rc = check_games(state, E, n)) return rc;
+    if ((spawn && !aligned(spawn, 4)) || (obs && !aligned(obs, 4))) return BSX_E_ALIGN;
     if (!reset_mask) family_forget(state);                  // every game re-spawned: whole-degree headings, either family may follow
     ResetArgs a{state_ptrs(state, E, n), E, n, reset_mask, spawn, seed, nonce, env_offset, obs, 0};
     hipLaunchKernelGGL(bsx_reset_kernel, dim3(grid_for(E, n)), dim3(TPB), 0, static_cast<hipStream_t>(stream), a);
@@ -472,111 +513,55 @@ int bsx_reset(void* state, int64_t E, int n, const uint8_t* reset_mask, const in
 int bsx_step_discrete(void* state, int64_t E, int n, const void* actions, int action_kind, const double* u, float* obs,
                       float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, const BsxRewards* cfg,
                       uint32_t flags, uint64_t seed, int64_t env_offset, void* stream) {
-    return launch_step<false>(state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed,
-                              env_offset, stream);
+    return step<false>({}, state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed, env_offset, stream);
 }
 
 int bsx_step_continuous(void* state, int64_t E, int n, const void* actions, int action_kind, const double* u,
                         float* obs, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner,
                         const BsxRewards* cfg, uint32_t flags, uint64_t seed, int64_t env_offset, void* stream) {
-    return launch_step<true>(state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed,
-                             env_offset, stream);
+    return step<true>({}, state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed, env_offset, stream);
 }
 
 int bsx_step_discrete_range(void* state, int64_t E, int n, int64_t first, int64_t count, const void* actions, int action_kind, const double* u,
                             float* obs, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, const BsxRewards* cfg,
                             uint32_t flags, uint64_t seed, int64_t env_offset, void* stream) {
-    return launch_step<false>(state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed,
-                              env_offset, stream, 0, 0, nullptr, first, count);
+    return step<false>({first, count}, state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed, env_offset, stream);
 }
 
 int bsx_step_continuous_range(void* state, int64_t E, int n, int64_t first, int64_t count, const void* actions, int action_kind, const double* u,
                               float* obs, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, const BsxRewards* cfg,
                               uint32_t flags, uint64_t seed, int64_t env_offset, void* stream) {
-    return launch_step<true>(state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed,
-                             env_offset, stream, 0, 0, nullptr, first, count);
+    return step<true>({first, count}, state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed, env_offset, stream);
 }
 
 int bsx_step_many_discrete(void* state, int64_t E, int n, int T, const void* actions, int action_kind, const double* u,
                            float* obs, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg,
                            uint32_t flags, int store_all, uint64_t seed, int64_t env_offset, void* stream) {
-    if (T < 1 || !actions) return BSX_E_ARG;
-    return launch_step<false>(state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed,
-                              env_offset, stream, T, store_all, env_done_t);
+    return T < 1 ? BSX_E_ARG : step<false>({0, -1, T, store_all, env_done_t}, state, E, n, actions, action_kind, u, obs, rew, done, env_done,
+                                           winner, cfg, flags, seed, env_offset, stream);
 }
 
 int bsx_step_many_continuous(void* state, int64_t E, int n, int T, const void* actions, int action_kind, const double* u,
                              float* obs, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg,
                              uint32_t flags, int store_all, uint64_t seed, int64_t env_offset, void* stream) {
-    if (T < 1 || !actions) return BSX_E_ARG;
-    return launch_step<true>(state, E, n, actions, action_kind, u, obs, rew, done, env_done, winner, cfg, flags, seed,
-                              env_offset, stream, T, store_all, env_done_t);
+    return T < 1 ? BSX_E_ARG : step<true>({0, -1, T, store_all, env_done_t}, state, E, n, actions, action_kind, u, obs, rew, done, env_done,
+                                          winner, cfg, flags, seed, env_offset, stream);
 }
-
-}  // extern "C"
-
-namespace {
-// T x (actor -> step) in one launch; CONT = continuous actions (three actor outputs, BSX_ACT_F32X4 rows)
-template <bool CONT, bool OFF32>
-void launch_rollout_w(int n, dim3 grid, hipStream_t s, const StepArgs& a) {
-    switch (n) {
-        case 1: hipLaunchKernelGGL((bsx_step_kernel<1, CONT, true, true, false, OFF32>), grid, dim3(SPB * 1), 0, s, a.E, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-        case 2: hipLaunchKernelGGL((bsx_step_kernel<2, CONT, true, true, false, OFF32>), grid, dim3(SPB * 2), 0, s, a.E, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-        case 3: hipLaunchKernelGGL((bsx_step_kernel<3, CONT, true, true, false, OFF32>), grid, dim3(SPB * 4), 0, s, a.E, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-        default: hipLaunchKernelGGL((bsx_step_kernel<4, CONT, true, true, false, OFF32>), grid, dim3(SPB * 4), 0, s, a.E, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a); break;
-    }
-}
-template <bool CONT>
-int launch_rollout(void* state, int64_t E, int n, int T, const float* weights, int precision, int scripted_team, uint64_t scripted_seed, float* obs, float* scores, float* rew,
-                   uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg, uint32_t flags,
-                   const BsxActorNoise* noise, uint64_t actor_seed, uint64_t seq, const uint64_t* seq_base, uint64_t seed,
-                   int64_t env_offset, void* stream) {
-    if (!state || E <= 0 || E > BSX_MAX_E || n < 1 || n > 4 || T < 1 || T > BSX_MAX_T || !weights || !obs || !scores || !rew || !done || !cfg)
-        return BSX_E_ARG;
-    if ((flags & BSX_F_EMPTY_CALL) || (precision != BSX_ACTOR_F32 && precision != BSX_ACTOR_BF16X3 && precision != BSX_ACTOR_BF16X6) ||
-        scripted_team < -1 || scripted_team > 1) return BSX_E_ARG;
-    if (!aligned(state, 256) || !aligned(weights, 16) || !aligned(scores, 16) || !aligned(obs, 4) || !aligned(rew, 4)) return BSX_E_ALIGN;
-    BsxActorNoise nz = {};
-    if (noise) nz = *noise;
-    if (nz.ou_scale > 0.f && (!nz.ou_state || !aligned(nz.ou_state, 16))) return nz.ou_state ? BSX_E_ALIGN : BSX_E_ARG;
-    if (nz.z_inject || nz.u_inject) return BSX_E_ARG;    // injected draws are per call: bsx_actor_forward only
-    if (nz.sample_mode != 0 && (nz.sample_mode != 1 || !(nz.temperature > 0.f) || CONT)) return BSX_E_ARG;   // a categorical head belongs to discrete actions
-    if ((nz.logp && !aligned(nz.logp, 4)) || (nz.value_weights && !aligned(nz.value_weights, 16))) return BSX_E_ALIGN;
-    if (nz.value_weights && (n != 1 || !nz.value || !aligned(nz.value, 4))) return BSX_E_ARG;          // the value head rides in the 1v1 kernel only
-    if (!family_claim(state, CONT)) return BSX_E_FAMILY;
-    const int64_t EA = E * 2 * n, D = 3 * n + 2;
-    StepArgs a;
-    a.st = state_ptrs(state, E, n);
-    a.E = E; a.n = n; a.actions = nullptr; a.action_kind = CONT ? BSX_ACT_F32X4 : BSX_ACT_LOGITS_F32; a.u = nullptr;
-    a.obs = obs + EA * D; a.rew = rew; a.done = done; a.env_done = env_done; a.winner = winner; a.env_done_t = env_done_t;
-    a.cfg = *cfg; a.flags = flags; a.seed = seed; a.env_offset = env_offset; a.tie_tick = bsx_tie_tick(n);
-    a.T = T; a.act_tb = 0; a.u_ts = 0; a.obs_ts = EA * D; a.rew_ts = EA; a.done_ts = EA;
-    a.aw = weights; a.aprec = precision; a.scripted_team = scripted_team; a.obs0 = obs; a.scores = scores; a.scores_ts = EA * 4; a.nz = nz; a.aseed = actor_seed; a.aseq = seq;
-    a.aseq_base = seq_base; a.iseed = scripted_seed;
-    const dim3 grid(unsigned((E + 31) / 32));            // a workgroup = 32 games = G/2 waves
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (narrow_offsets_ok(E, n, flags)) launch_rollout_w<CONT, true>(n, grid, s, a);
-    else launch_rollout_w<CONT, false>(n, grid, s, a);
-    return int(hipGetLastError());
-}
-}  // namespace
-
-extern "C" {
 
 int bsx_rollout_discrete(void* state, int64_t E, int n, int T, const float* weights, int precision, int scripted_team, float* obs, float* scores, float* rew,
                          uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg, uint32_t flags,
                          const BsxActorNoise* noise, uint64_t actor_seed, uint64_t seq, const uint64_t* seq_base, uint64_t seed,
                          int64_t env_offset, void* stream) {
-    return launch_rollout<false>(state, E, n, T, weights, precision, scripted_team, 0, obs, scores, rew, done, env_done, winner, env_done_t, cfg, flags,
-                                 noise, actor_seed, seq, seq_base, seed, env_offset, stream);
+    return rollout<false>(state, E, n, T, weights, precision, scripted_team, 0, obs, scores, rew, done, env_done, winner, env_done_t, cfg, flags,
+                          noise, actor_seed, seq, seq_base, seed, env_offset, stream);
 }
 
 int bsx_rollout_continuous(void* state, int64_t E, int n, int T, const float* weights, int precision, int scripted_team, uint64_t scripted_seed, float* obs, float* scores, float* rew,
                            uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg, uint32_t flags,
                            const BsxActorNoise* noise, uint64_t actor_seed, uint64_t seq, const uint64_t* seq_base, uint64_t seed,
                            int64_t env_offset, void* stream) {
-    return launch_rollout<true>(state, E, n, T, weights, precision, scripted_team, scripted_seed, obs, scores, rew, done, env_done, winner, env_done_t, cfg, flags,
-                                noise, actor_seed, seq, seq_base, seed, env_offset, stream);
+    return rollout<true>(state, E, n, T, weights, precision, scripted_team, scripted_seed, obs, scores, rew, done, env_done, winner, env_done_t, cfg, flags,
+                         noise, actor_seed, seq, seq_base, seed, env_offset, stream);
 }
 
 // Self-test of atan2_pixels against the device library on the square [-R, R]^2 of argument pairs: out[0] = pairs whose 64-bit
@@ -610,8 +595,9 @@ int bsx_selftest_atan2(int R, uint64_t* out, void* stream) {
 }
 
 int bsx_observe(void* state, int64_t E, int n, float* obs, void* stream) {
-    if (!state || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N || !obs) return BSX_E_ARG;
-    if (!aligned(state, 256) || !aligned(obs, 4)) return BSX_E_ALIGN;
+    if (!obs) return BSX_E_ARG;
+    if (const int rc = check_games(state, E, n)) return rc;
+    if (!aligned(obs, 4)) return BSX_E_ALIGN;
     // same kernel as reset with nothing selected: it only stages the poses and writes the rows (battle_env.py:202-244)
     ResetArgs a{state_ptrs(state, E, n), E, n, nullptr, nullptr, 0, 0, 0, obs, 1};
     hipLaunchKernelGGL(bsx_reset_kernel, dim3(grid_for(E, n)), dim3(TPB), 0, static_cast<hipStream_t>(stream), a);
@@ -619,8 +605,8 @@ int bsx_observe(void* state, int64_t E, int n, float* obs, void* stream) {
 }
 
 int bsx_export_state(const void* state, int64_t E, int n, const BsxExport* out, void* stream) {
-    if (!state || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N || !out) return BSX_E_ARG;
-    if (!aligned(state, 256)) return BSX_E_ALIGN;
+    if (!out) return BSX_E_ARG;
+    if (const int rc = check_games(state, E, n)) return rc;
     ExportArgs a{state_ptrs(const_cast<void*>(state), E, n), E, n, *out, bsx_tie_tick(n)};
     const size_t EA = size_t(E) * 2 * n;
     hipLaunchKernelGGL(bsx_export_kernel, dim3(unsigned((EA + TPB - 1) / TPB)), dim3(TPB), 0,
@@ -629,9 +615,9 @@ int bsx_export_state(const void* state, int64_t E, int n, const BsxExport* out, 
 }
 
 int bsx_instinct_discrete(const float* obs, void* actions, int out_kind, int64_t E, int n, int team, void* stream) {
-    if (!obs || !actions || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N || team < 0 || team > 2) return BSX_E_ARG;
-    if (out_kind != BSX_ACT_I32 && out_kind != BSX_ACT_LOGITS_F32) return BSX_E_ARG;
-    if (!aligned(obs, 4) || !aligned(actions, out_kind == BSX_ACT_I32 ? 4 : 16)) return BSX_E_ALIGN;
+    if (!actions || team < 0 || team > 2 || (out_kind != BSX_ACT_I32 && out_kind != BSX_ACT_LOGITS_F32)) return BSX_E_ARG;
+    if (const int rc = check_games(obs, E, n, 4)) return rc;
+    if (!aligned(actions, out_kind == BSX_ACT_I32 ? 4 : 16)) return BSX_E_ALIGN;
     InstinctArgs a{obs, actions, nullptr, E, n, team, out_kind, 0, 0, 0, nullptr};
     const size_t EA = size_t(E) * 2 * n;
     hipLaunchKernelGGL(bsx_instinct_kernel, dim3(unsigned((EA + TPB - 1) / TPB)), dim3(TPB), 0, static_cast<hipStream_t>(stream), a);
@@ -640,8 +626,9 @@ int bsx_instinct_discrete(const float* obs, void* actions, int out_kind, int64_t
 
 int bsx_instinct_continuous(const float* obs, double* actions, const double* rnd, int64_t E, int n, int team,
                             uint64_t seed, uint64_t seq, const uint64_t* seq_base, void* stream) {
-    if (!obs || !actions || E <= 0 || E > BSX_MAX_E || n < 1 || n > BSX_MAX_N || team < 0 || team > 2) return BSX_E_ARG;
-    if (!aligned(obs, 4) || !aligned(actions, 8) || (rnd && !aligned(rnd, 8))) return BSX_E_ALIGN;
+    if (!actions || team < 0 || team > 2) return BSX_E_ARG;
+    if (const int rc = check_games(obs, E, n, 4)) return rc;
+    if (!aligned(actions, 8) || (rnd && !aligned(rnd, 8))) return BSX_E_ALIGN;
     InstinctArgs a{obs, actions, rnd, E, n, team, 0, 1, seed, seq, seq_base};
     const size_t EA = size_t(E) * 2 * n;
     hipLaunchKernelGGL(bsx_instinct_kernel, dim3(unsigned((EA + TPB - 1) / TPB)), dim3(TPB), 0, static_cast<hipStream_t>(stream), a);

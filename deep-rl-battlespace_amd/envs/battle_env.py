@@ -380,26 +380,21 @@ class parallel_env:
         env_done_ptr: where this call's env_done [E] goes instead of the env-owned tensor (a rollout's per-tick record; the
         caller copies the last one back into `self._env_done`).
         games: (first, count) = step only that range of the games (bsx_step_*_range; every pointer still the full array's)."""
-        flags = self._base_flags | (_lib.F_EMPTY_CALL if empty else 0)
-        if games is not None:
+        args = (self._p_state, self.n_envs, self.n_agents, act_ptr, kind, u_ptr, obs_ptr, rew_ptr, done_ptr,
+                env_done_ptr if env_done_ptr is not None else self._p_env_done, self._p_winner, self._cfg_ref,
+                self._base_flags | (_lib.F_EMPTY_CALL if empty else 0), self.seed, self.env_offset, self._stream())
+        if games is None:
+            fn = self._lib.bsx_step_continuous if self.continuous_actions else self._lib.bsx_step_discrete
+        else:                                              # the range form: (first, count) after (state, E, n)
             fn = self._lib.bsx_step_continuous_range if self.continuous_actions else self._lib.bsx_step_discrete_range
-            with self._guard():
-                _lib.check(fn(self._p_state, self.n_envs, self.n_agents, int(games[0]), int(games[1]), act_ptr, kind, u_ptr, obs_ptr,
-                              rew_ptr, done_ptr, env_done_ptr if env_done_ptr is not None else self._p_env_done, self._p_winner,
-                              self._cfg_ref, flags, self.seed, self.env_offset, self._stream()), "bsx_step_range")
-            return
-        fn = self._lib.bsx_step_continuous if self.continuous_actions else self._lib.bsx_step_discrete
+            args = args[:3] + (int(games[0]), int(games[1])) + args[3:]
         if _current_device() == self._dev_index:           # the normal one-process-per-GPU case: no context object at all on the per-call path
-            rc = fn(self._p_state, self.n_envs, self.n_agents, act_ptr, kind, u_ptr, obs_ptr, rew_ptr, done_ptr,
-                    env_done_ptr if env_done_ptr is not None else self._p_env_done, self._p_winner,
-                    self._cfg_ref, flags, self.seed, self.env_offset, self._stream())
+            rc = fn(*args)
         else:
             with torch.cuda.device(self.device):
-                rc = fn(self._p_state, self.n_envs, self.n_agents, act_ptr, kind, u_ptr, obs_ptr, rew_ptr, done_ptr,
-                        env_done_ptr if env_done_ptr is not None else self._p_env_done, self._p_winner,
-                        self._cfg_ref, flags, self.seed, self.env_offset, self._stream())
+                rc = fn(*args)
         if rc:
-            _lib.check(rc, "bsx_step")
+            _lib.check(rc, "bsx_step" if games is None else "bsx_step_range")
 
     def _check_action_series(self, actions):
         """actions for T calls: [T, E, A] int32 | [T, E, A, 4] float32 | [T, E, A, 3] float32/float64 (continuous) |
@@ -501,6 +496,21 @@ class parallel_env:
         from ..sharding import chain_ranges
         return chain_ranges(self.n_envs, self.n_agents, chains)
 
+    def fork_join(self, ranges, body, side):
+        """body(games) for every game range of chain_ranges(), each on its own stream: range 0 on the current one, range r on side[r - 1],
+        forked from and joined into the current stream (inside a capture: branches of the graph).  One range is the whole batch: body(None)."""
+        if len(ranges) == 1:
+            body(None)
+            return
+        main = torch.cuda.current_stream(self.device)
+        for s in side:
+            s.wait_stream(main)
+        for r, games in enumerate(ranges):
+            with torch.cuda.stream(main if r == 0 else side[r - 1]):
+                body(games)
+        for s in side:
+            main.wait_stream(s)
+
     def capture_steps(self, actions, store=False, chains="auto"):
         """Capture T consecutive step() launches into ONE HIP graph (the launch-bound inner loop of a rollout).
 
@@ -534,21 +544,16 @@ class parallel_env:
         else:
             obs, rew, done = self._obs, self._rew, self._done
         step_bytes = actions[0].numel() * actions.element_size()
+
+        def steps(games):
+            for t in range(T):
+                o, w, d = (obs[t], rew[t], done[t]) if store else (obs, rew, done)
+                self._launch(actions.data_ptr() + t * step_bytes, kind, False, None, o.data_ptr(), w.data_ptr(), d.data_ptr(), games=games)
         graph = torch.cuda.CUDAGraph()
         torch.cuda.synchronize(self.device)
         side = [torch.cuda.Stream(self.device) for _ in ranges[1:]]
         with torch.cuda.graph(graph):
-            main = torch.cuda.current_stream(self.device)
-            for s in side:
-                s.wait_stream(main)
-            for r, games in enumerate(ranges):
-                with torch.cuda.stream(main if r == 0 else side[r - 1]):
-                    for t in range(T):
-                        o, w, d = (obs[t], rew[t], done[t]) if store else (obs, rew, done)
-                        self._launch(actions.data_ptr() + t * step_bytes, kind, False, None, o.data_ptr(), w.data_ptr(), d.data_ptr(),
-                                     games=games if len(ranges) > 1 else None)
-            for s in side:
-                main.wait_stream(s)
+            self.fork_join(ranges, steps, side)
         self._graph_keepalive = (actions, obs, rew, done, side)
         return graph, (obs, rew, done.view(torch.bool))
 

@@ -346,23 +346,16 @@ class PolicyRollout:
         return self.env_done[:self.T] == 0
 
     def _tick(self, t, games=None):
-        if games is not None:                          # a chain's tick: the fused actor and the step over one range of the games
-            ou = dict(self.ou, env_done=self.env_done[t] if self.ou["restart"] else None) if self.ou is not None else None
-            sample = dict(self._sample, logp=self.logp[t]) if self._sample is not None else None
-            value = dict(weights=self._value_w, out=self.value[t]) if self._value_w is not None else None
-            self.fused.forward_into(self.obs[t], self.scores[t], self.noise_std, seq=t, seq_base=self._seq_base, ou=ou, sample=sample,
-                                    value=value, games=games)
-            self.env._launch(self.scores[t].data_ptr(), self._kind, False, None,
-                             self.obs[t + 1].data_ptr(), self.rew[t].data_ptr(), self._done[t].data_ptr(),
-                             env_done_ptr=self.env_done[t + 1].data_ptr(), games=games)
-            return
+        """Tick t of every game, or -- games = (first, count), a chain's tick -- of one range of them (the fused actor only: chains > 1
+        keeps the scripted opponent and the torch actor out)."""
         if self.fused is not None:
             # graph arguments are frozen: the noise key is (seed, seq_base + t, row) with seq_base a device word that the
             # graph advances by T once per replay (_body)
             ou = dict(self.ou, env_done=self.env_done[t] if self.ou["restart"] else None) if self.ou is not None else None
             sample = dict(self._sample, logp=self.logp[t]) if self._sample is not None else None
             value = dict(weights=self._value_w, out=self.value[t]) if self._value_w is not None else None
-            self.fused.forward_into(self.obs[t], self.scores[t], self.noise_std, seq=t, seq_base=self._seq_base, ou=ou, sample=sample, value=value)
+            self.fused.forward_into(self.obs[t], self.scores[t], self.noise_std, seq=t, seq_base=self._seq_base, ou=ou, sample=sample, value=value,
+                                    games=games)
             if self._act64 is not None:
                 cols = slice(self.opponent._cols[0], self.opponent._cols[-1] + 1)   # a team's planes are adjacent columns (a slice: nothing is uploaded while capturing)
                 self._act64.copy_(self.scores[t][..., :3])
@@ -377,7 +370,7 @@ class PolicyRollout:
                 self.opponent.write_actions(out=self.scores[t], obs=self.obs[t])
             self.env._launch(self.scores[t].data_ptr(), self._kind, False, None,
                              self.obs[t + 1].data_ptr(), self.rew[t].data_ptr(), self._done[t].data_ptr(),
-                             env_done_ptr=self.env_done[t + 1].data_ptr())
+                             env_done_ptr=self.env_done[t + 1].data_ptr(), games=games)
             return
         with torch.no_grad():
             s = self.actor(self.obs[t])
@@ -423,21 +416,13 @@ class PolicyRollout:
                                      scripted_seed=0 if self.opponent is None else self.opponent.seed)
         else:
             ranges = self.env.chain_ranges(self.chains)
-            if len(ranges) == 1:
+            if self._side is None:
+                self._side = [torch.cuda.Stream(self.env.device) for _ in ranges[1:]]
+
+            def ticks(games):
                 for t in range(self.T):
-                    self._tick(t)
-            else:
-                main = torch.cuda.current_stream(self.env.device)
-                if self._side is None:
-                    self._side = [torch.cuda.Stream(self.env.device) for _ in ranges[1:]]
-                for s in self._side:
-                    s.wait_stream(main)
-                for r, games in enumerate(ranges):
-                    with torch.cuda.stream(main if r == 0 else self._side[r - 1]):
-                        for t in range(self.T):
-                            self._tick(t, games)
-                for s in self._side:
-                    main.wait_stream(s)
+                    self._tick(t, games)
+            self.env.fork_join(ranges, ticks, self._side)
             self.env._env_done.copy_(self.env_done[self.T])        # the per-tick launches wrote their flags into the record
         self._seq_base.add_(self.T)                    # fresh exploration-noise keys for the next run
 

@@ -81,6 +81,128 @@ def test_bad_arguments_are_rejected_before_any_launch():
     assert lib.bsx_actor_forward(ok, ok, ok, 4, 1, 0, None, 0, 0, None, -5, None) == -1   # negative env_offset
     assert lib.bsx_build_flags() == 0                                                      # the in-tree library is the product build
 
+    # Every entry point that takes games: one call per rejected condition, and calls that break two conditions at once -- one BSX_E_ARG,
+    # one BSX_E_ALIGN -- so that the order in which each entry point checks is pinned too.  Fake addresses only: every call is refused
+    # before anything reaches HIP (one that got through would return a HIP error on a machine without a GPU).
+    A, M = 4096, 4096 + 8                      # a 256-byte aligned address and one aligned to 8 bytes only (neither is dereferenced)
+    ARG, ALIGN = -1, -2
+    rw = ctypes.byref(L.BsxRewards(100, 10, -1, -5, -20))
+    big = (1 << 30) + 1                        # BSX_MAX_E + 1
+
+    def noise(**fields):
+        nz = L.BsxActorNoise()
+        for k, v in fields.items():
+            setattr(nz, k, v)
+        return ctypes.byref(nz)
+
+    def step(cont, state=A, E=4, n=1, act=A, kind=0, u=None, obs=A, rew=A, done=A, cfg=rw, flags=0):
+        fn = lib.bsx_step_continuous if cont else lib.bsx_step_discrete
+        return fn(state, E, n, act, kind, u, obs, rew, done, None, None, cfg, flags, 0, 0, None)
+
+    def step_range(cont, state=A, E=1024, n=1, first=256, count=256, act=A, kind=0, u=None, obs=A, rew=A, done=A, cfg=rw, flags=0):
+        fn = lib.bsx_step_continuous_range if cont else lib.bsx_step_discrete_range
+        return fn(state, E, n, first, count, act, kind, u, obs, rew, done, None, None, cfg, flags, 0, 0, None)
+
+    def many(cont, state=A, E=4, n=1, T=2, act=A, kind=0, u=None, obs=A, rew=A, done=A, cfg=rw, flags=0):
+        fn = lib.bsx_step_many_continuous if cont else lib.bsx_step_many_discrete
+        return fn(state, E, n, T, act, kind, u, obs, rew, done, None, None, None, cfg, flags, 1, 0, 0, None)
+
+    def rollout(cont, state=A, E=4, n=1, T=8, w=A, prec=0, team=-1, obs=A, scores=A, rew=A, done=A, cfg=rw, flags=0, nz=None):
+        if cont:
+            return lib.bsx_rollout_continuous(state, E, n, T, w, prec, team, 0, obs, scores, rew, done, None, None, None, cfg, flags, nz,
+                                              0, 0, None, 0, 0, None)
+        return lib.bsx_rollout_discrete(state, E, n, T, w, prec, team, obs, scores, rew, done, None, None, None, cfg, flags, nz,
+                                        0, 0, None, 0, 0, None)
+
+    sizes = [dict(state=None), dict(E=0), dict(E=big), dict(n=0), dict(n=17)]
+    for cont in (False, True):
+        bad_kind = 3 if cont else 2
+        wide_kind = 2 if cont else 1                            # the 16-byte rows: BSX_ACT_F32X4 / BSX_ACT_LOGITS_F32
+        cases = [(ARG, kw) for kw in sizes + [dict(obs=None), dict(rew=None), dict(done=None), dict(cfg=None), dict(act=None),
+                                              dict(kind=bad_kind), dict(kind=-1)]]
+        cases += [(ALIGN, kw) for kw in (dict(state=M), dict(obs=A + 2), dict(rew=A + 2), dict(u=A + 4), dict(kind=wide_kind, act=M))]
+        cases += [(ARG, dict(state=M, obs=None)), (ARG, dict(state=M, act=None)), (ARG, dict(obs=A + 2, n=0)),
+                  (ALIGN, dict(state=M, kind=bad_kind)), (ALIGN, dict(u=A + 4, kind=bad_kind))]
+        for want, kw in cases:
+            assert step(cont, **kw) == want, ("step", cont, kw)
+        for want, kw in cases + [(ARG, dict(first=100)), (ARG, dict(count=0)), (ARG, dict(first=-256)), (ARG, dict(first=768, count=512)),
+                                 (ARG, dict(first=100, state=M)), (ARG, dict(count=0, obs=A + 2))]:
+            assert step_range(cont, **kw) == want, ("range", cont, kw)
+        for want, kw in cases + [
+                (ARG, dict(T=0)), (ARG, dict(T=65536)), (ARG, dict(act=None, flags=2)), (ARG, dict(T=0, state=M)),
+                (ARG, dict(act=None, obs=A + 2)), (ARG, dict(T=65536, u=A + 4))]:
+            assert many(cont, **kw) == want, ("many", cont, kw)
+        cases = [(ARG, kw) for kw in sizes + [dict(n=5), dict(T=0), dict(T=65536), dict(w=None), dict(obs=None), dict(scores=None),
+                                              dict(rew=None), dict(done=None), dict(cfg=None), dict(flags=2), dict(prec=3),
+                                              dict(team=-2), dict(team=2), dict(nz=noise(ou_scale=0.5)), dict(nz=noise(z_inject=A)),
+                                              dict(nz=noise(u_inject=A)), dict(nz=noise(sample_mode=2, temperature=1.0)),
+                                              dict(nz=noise(sample_mode=1))]]
+        cases += [(ALIGN, kw) for kw in (dict(state=M), dict(w=M), dict(scores=M), dict(obs=A + 2), dict(rew=A + 2),
+                                         dict(nz=noise(ou_scale=0.5, ou_state=M)), dict(nz=noise(logp=A + 2)),
+                                         dict(nz=noise(value_weights=M, value=A)))]
+        cases += [(ARG, dict(state=M, prec=3)), (ARG, dict(state=M, team=2)), (ARG, dict(w=M, n=5)), (ARG, dict(obs=A + 2, flags=2)),
+                  (ALIGN, dict(w=M, nz=noise(z_inject=A))), (ALIGN, dict(nz=noise(ou_scale=0.5, ou_state=M, z_inject=A))),
+                  (ARG, dict(nz=noise(z_inject=A, logp=A + 2))), (ALIGN, dict(nz=noise(logp=A + 2, value_weights=A)))]
+        if cont:
+            cases += [(ARG, dict(nz=noise(sample_mode=1, temperature=1.0))), (ALIGN, dict(scores=M, nz=noise(sample_mode=1, temperature=1.0)))]
+        else:
+            cases += [(ARG, dict(n=2, nz=noise(value_weights=A, value=A))), (ARG, dict(nz=noise(value_weights=A))),
+                      (ARG, dict(nz=noise(value_weights=A, value=A + 2))), (ALIGN, dict(obs=A + 2, nz=noise(value_weights=A)))]
+        for want, kw in cases:
+            assert rollout(cont, **kw) == want, ("rollout", cont, kw)
+
+    def reset(state=A, E=4, n=1, spawn=None, obs=None):
+        return lib.bsx_reset(state, E, n, None, spawn, 0, 0, 0, obs, None)
+
+    def observe(state=A, E=4, n=1, obs=A):
+        return lib.bsx_observe(state, E, n, obs, None)
+
+    out = L.BsxExport()
+
+    def export(state=A, E=4, n=1, out=ctypes.byref(out)):
+        return lib.bsx_export_state(state, E, n, out, None)
+
+    def init(state=M, E=4, n=1):
+        return lib.bsx_state_init(state, E, n, None)
+
+    for fn, cases in ((reset, [(ALIGN, dict(state=M)), (ALIGN, dict(spawn=A + 2)), (ALIGN, dict(obs=A + 2)), (ARG, dict(n=0, spawn=A + 2)),
+                               (ARG, dict(state=M, E=0))]),
+                      (observe, [(ARG, dict(obs=None)), (ALIGN, dict(state=M)), (ALIGN, dict(obs=A + 2)), (ARG, dict(state=M, obs=None))]),
+                      (export, [(ARG, dict(out=None)), (ALIGN, dict(state=M)), (ARG, dict(state=M, out=None))]),
+                      (init, [(ALIGN, dict()), (ARG, dict(state=None)), (ARG, dict(n=0)), (ARG, dict(E=big))])):
+        if fn is not init:
+            cases = [(ARG, kw) for kw in sizes] + cases
+        for want, kw in cases:
+            assert fn(**kw) == want, (fn.__name__, kw)
+
+    def instinct(cont, obs=A, act=A, kind=0, rnd=None, E=4, n=1, team=2):
+        if cont:
+            return lib.bsx_instinct_continuous(obs, act, rnd, E, n, team, 0, 0, None, None)
+        return lib.bsx_instinct_discrete(obs, act, kind, E, n, team, None)
+
+    sizes = [dict(obs=None), dict(act=None), dict(E=0), dict(E=big), dict(n=0), dict(n=17), dict(team=-1), dict(team=3)]
+    for want, kw in [(ARG, kw) for kw in sizes + [dict(kind=2)]] + [
+            (ALIGN, dict(obs=A + 2)), (ALIGN, dict(act=A + 2)), (ALIGN, dict(kind=1, act=M)), (ARG, dict(obs=A + 2, kind=2)),
+            (ARG, dict(obs=A + 2, team=3)), (ARG, dict(act=A + 2, n=0))]:
+        assert instinct(False, **kw) == want, ("instinct_discrete", kw)
+    for want, kw in [(ARG, kw) for kw in sizes] + [
+            (ALIGN, dict(obs=A + 2)), (ALIGN, dict(act=A + 4)), (ALIGN, dict(rnd=A + 4)), (ARG, dict(rnd=A + 4, team=3)),
+            (ARG, dict(obs=A + 2, act=None))]:
+        assert instinct(True, **kw) == want, ("instinct_continuous", kw)
+
+    def actor(w=A, obs=A, scores=A, E=4, n=1, prec=0, nz=None, off=0):
+        return lib.bsx_actor_forward(w, obs, scores, E, n, prec, nz, 0, 0, None, off, None)
+
+    for want, kw in [(ARG, kw) for kw in (dict(w=None), dict(obs=None), dict(scores=None), dict(E=0), dict(E=big), dict(n=0), dict(n=17),
+                                          dict(prec=3), dict(off=-1), dict(nz=noise(ou_scale=0.5)), dict(nz=noise(sample_mode=2)),
+                                          dict(nz=noise(value_weights=A)))] + [
+            (ALIGN, dict(w=M)), (ALIGN, dict(scores=M)), (ALIGN, dict(obs=A + 2)), (ALIGN, dict(nz=noise(ou_scale=0.5, ou_state=M))),
+            (ALIGN, dict(nz=noise(z_inject=M))), (ALIGN, dict(nz=noise(u_inject=M))), (ALIGN, dict(nz=noise(value_weights=A, value=A + 2))),
+            (ARG, dict(w=M, prec=3)), (ARG, dict(obs=A + 2, scores=None)), (ALIGN, dict(obs=A + 2, off=-1)),
+            (ALIGN, dict(nz=noise(z_inject=M, sample_mode=2))),
+            (ARG, dict(nz=noise(sample_mode=2, u_inject=M)))]:
+        assert actor(**kw) == want, ("actor_forward", kw)
+
 
 def test_env_refuses_to_run_without_gpu_or_library():
     import torch
