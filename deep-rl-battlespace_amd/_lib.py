@@ -47,6 +47,20 @@ class BsxExport(ctypes.Structure):
     _fields_ = [(f, c_void_p) for f in EXPORT_FIELDS]
 
 
+class BsxReplayRing(ctypes.Structure):
+    _fields_ = [("obs", c_void_p), ("obs_next", c_void_p), ("act", c_void_p), ("rew", c_void_p), ("done", c_void_p),
+                ("counter", c_void_p), ("M", c_int64), ("nA", c_int), ("D", c_int), ("n_act", c_int)]
+
+
+class BsxReplaySource(ctypes.Structure):
+    _fields_ = [("obs", c_void_p), ("obs_row", c_int64), ("obs_col", c_int64),
+                ("obs_next", c_void_p), ("obs_next_row", c_int64), ("obs_next_col", c_int64),
+                ("act", c_void_p), ("act_row", c_int64), ("act_col", c_int64),
+                ("rew", c_void_p), ("rew_row", c_int64), ("rew_col", c_int64),
+                ("done", c_void_p), ("done_row", c_int64), ("done_col", c_int64),
+                ("skip", c_void_p), ("skip_row", c_int64)]
+
+
 # name -> (restype, argtypes): every symbol include/battlespace_hip.h declares
 SIGNATURES = {
     "bsx_abi_version": (c_int, []),
@@ -84,6 +98,10 @@ SIGNATURES = {
     "bsx_actor_blob_floats": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "bsx_actor_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(BsxActorNoise), c_uint64, c_uint64,
                                   c_void_p, c_int64, c_void_p]),
+    "bsx_replay_workspace_bytes": (c_int, [c_int64, ctypes.POINTER(c_size_t)]),
+    "bsx_replay_append": (c_int, [ctypes.POINTER(BsxReplayRing), ctypes.POINTER(BsxReplaySource), c_int64, c_void_p, c_void_p, c_void_p]),
+    "bsx_replay_sample": (c_int, [ctypes.POINTER(BsxReplayRing), c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -42,7 +42,9 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_step_multi_tick.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_step_two_wave.hip"), PER_CALL_FLAGS),
            (os.path.join(CSRC, "bsx_step_rollout.hip"), STEP_FLAGS),
-           (os.path.join(CSRC, "bsx_actor.hip"), ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"])]
+           (os.path.join(CSRC, "bsx_actor.hip"), ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+           # the replay ring (append / sample): copies bits and draws integers, no floating-point arithmetic to pin
+           (os.path.join(CSRC, "bsx_replay.hip"), [])]
 
 
 def _stale():

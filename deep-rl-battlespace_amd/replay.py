@@ -101,3 +101,113 @@ class ReplayBuffer:
 
     def is_ready(self):
         return self.mem_cntr >= self.batch_size
+
+
+class DeviceReplayBuffer(ReplayBuffer):
+    """The same ring with its control on the device too: the counter is a device int64 and storing and sampling are HIP kernels
+    (csrc/bsx_replay.hip: bsx_replay_append / bsx_replay_sample) that never wait for the host, so a rollout, its store and a
+    learner batch can be one captured HIP graph (`PolicyRollout.capture(then=...)`).  Same memory tensors and layout as
+    ReplayBuffer (state_mem / new_state_mem views included), and the same rows, bit for bit, for the same inputs.
+
+        buf = DeviceReplayBuffer(1_000_000, 512, env.possible_red, env.obs_size, env.obs_size * n, 4, device="cuda", seed=0)
+        buf.append_rollout(ro, range(n))      # asynchronous; returns the device word holding the number of rows stored
+        batch = buf.sample()                  # asynchronous; tensors the NEXT sample() overwrites; buf.last_idx = the rows drawn
+
+    `sample()` draws with Philox4x32-10 keyed by (seed, a draw counter on the device, position in the batch) instead of the torch
+    generator; `sample(idx=...)` is the base behaviour (parity runs).  `mem_cntr` and `is_ready()` read the device counter: one
+    host synchronisation each, a convenience for host code, not for the collect loop."""
+
+    def __init__(self, mem_size, batch_size, agent_list, obs_size, critic_dims, n_actions, device="cuda", generator=None, seed=0):
+        self._counter = torch.zeros(1, dtype=torch.int64, device=device)   # first: the base constructor assigns mem_cntr = 0
+        super().__init__(mem_size, batch_size, agent_list, obs_size, critic_dims, n_actions, device=device, generator=generator)
+        from . import _lib
+        self._lib = _lib
+        nA, D, M, B, k = self.n_agents, int(obs_size), self.mem_size, self.batch_size, self.n_actions
+        if not (1 <= nA <= _lib.MAX_N and 1 <= D <= 3 * _lib.MAX_N + 2 and k in (3, 4) and 1 <= M < 2 ** 31 and 1 <= B < 2 ** 31):
+            raise ValueError("the device ring takes 1..16 agents, observations of 1..50 floats, 3 or 4 actions, mem_size and batch_size "
+                             "in [1, 2^31)")
+        self.seed = int(seed)
+        dev = self.actor_states.device
+        self._draws = torch.zeros(1, dtype=torch.int64, device=dev)       # the sampler's sequence word, advanced once per sample()
+        self._stored = torch.zeros(1, dtype=torch.int64, device=dev)      # rows kept by the latest append
+        # append workspaces are only ever added: a captured graph keeps the address it was recorded with
+        self._workspaces = [torch.empty(0, dtype=torch.int64, device=dev)]
+        kw = dict(device=dev, dtype=torch.float32)
+        self._b_obs, self._b_obs_ = torch.zeros((B, nA, D), **kw), torch.zeros((B, nA, D), **kw)
+        self._b_act, self._b_rew = torch.zeros((B, nA, k), **kw), torch.zeros((B, nA), **kw)
+        self._b_done = torch.zeros((B, nA), device=dev, dtype=torch.bool)
+        self.last_idx = torch.zeros(B, device=dev, dtype=torch.int64)
+        self._ring = _lib.BsxReplayRing(self.actor_states.data_ptr(), self.actor_new_states.data_ptr(), self.action_mem.data_ptr(),
+                                        self.rew_mem.data_ptr(), self.done_mem.data_ptr(), self._counter.data_ptr(), M, nA, D, k)
+
+    @property
+    def mem_cntr(self):
+        return int(self._counter.item())
+
+    @mem_cntr.setter
+    def mem_cntr(self, value):
+        if int(value) < 0:
+            raise ValueError("mem_cntr counts the rows ever stored: it cannot be negative")
+        self._counter.fill_(int(value))
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.actor_states.device).cuda_stream
+
+    def _append(self, src, rows):
+        import ctypes
+        lib = self._lib.load()
+        need = ctypes.c_size_t()
+        self._lib.check(lib.bsx_replay_workspace_bytes(rows, ctypes.byref(need)), "bsx_replay_workspace_bytes")
+        if self._workspaces[-1].numel() * 8 < need.value:
+            self._workspaces.append(torch.empty((need.value + 7) // 8, dtype=torch.int64, device=self.actor_states.device))
+        self._lib.check(lib.bsx_replay_append(ctypes.byref(self._ring), ctypes.byref(src), rows, self._workspaces[-1].data_ptr(),
+                                              self._stored.data_ptr(), self._stream()), "bsx_replay_append")
+        return self._stored
+
+    def _put(self, obs, act, rew, obs_, done):
+        """Dense rows (what store_transition builds): obs / obs_ [R, nA, obs], act [R, nA, n_actions], rew [R, nA], done bool [R, nA]."""
+        R, nA, D, k = obs.shape[0], self.n_agents, self.actor_states.shape[2], self.n_actions
+        if R == 0:
+            return
+        obs, act, rew, obs_ = (t.to(torch.float32).contiguous() for t in (obs, act, rew, obs_))
+        done = done.to(torch.bool).contiguous().view(torch.uint8)
+        if obs.shape != (R, nA, D) or obs_.shape != (R, nA, D) or act.shape != (R, nA, k) or rew.shape != (R, nA) or done.shape != (R, nA):
+            raise ValueError("rows must be [R, nA, obs], [R, nA, n_actions], [R, nA], [R, nA, obs], [R, nA]")
+        src = self._lib.BsxReplaySource(obs.data_ptr(), nA * D, D, obs_.data_ptr(), nA * D, D, act.data_ptr(), nA * k, k,
+                                        rew.data_ptr(), nA, 1, done.data_ptr(), nA, 1, None, 0)
+        self._append(src, R)
+
+    def append_rollout(self, rollout, columns):
+        """store_rollout without the host: the kept rows of a PolicyRollout (running games only, tick-major) go into the ring straight
+        from the rollout's tensors.  Asynchronous and capturable.  `columns`: this team's env columns, a contiguous range (as
+        instinct.Team._cols are).  Returns the device int64 [1] holding the number of rows stored (overwritten by the next append)."""
+        cols = [int(c) for c in columns]
+        T, (_, E, A, D) = rollout.T, tuple(rollout.obs.shape)
+        c0 = cols[0] if cols else 0
+        if len(cols) != self.n_agents or cols != list(range(c0, c0 + len(cols))) or c0 < 0 or c0 + len(cols) > A:
+            raise ValueError("columns must be a contiguous range of len(agent_list) env columns")
+        if D != self.actor_states.shape[2] or rollout.obs.device != self.actor_states.device:
+            raise ValueError("the rollout's observations do not fit this ring")
+        src = self._lib.BsxReplaySource(rollout.obs.data_ptr() + 4 * c0 * D, A * D, D, rollout.obs[1].data_ptr() + 4 * c0 * D, A * D, D,
+                                        rollout.scores.data_ptr() + 16 * c0, A * 4, 4, rollout.rew.data_ptr() + 4 * c0, A, 1,
+                                        rollout._done.data_ptr() + c0, A, 1, rollout.env_done.data_ptr(), 1)
+        return self._append(src, T * E)
+
+    def store_rollout(self, rollout, columns):
+        """append_rollout, then the number of rows stored as a Python int (one host synchronisation): the base's return."""
+        return int(self.append_rollout(rollout, columns).item())
+
+    def sample(self, idx=None):
+        """The base's tuple, drawn and gathered in one HIP launch (capturable).  Its tensors are views of buffers that the NEXT
+        sample() overwrites; `last_idx` holds the indices drawn.  idx: the base behaviour (parity runs)."""
+        if idx is not None:
+            return super().sample(idx)
+        import ctypes
+        lib, B = self._lib.load(), self.batch_size
+        self._lib.check(lib.bsx_replay_sample(ctypes.byref(self._ring), B, self.seed, 0, self._draws.data_ptr(), self.last_idx.data_ptr(),
+                                              self._b_obs.data_ptr(), self._b_obs_.data_ptr(), self._b_act.data_ptr(), self._b_rew.data_ptr(),
+                                              self._b_done.data_ptr(), self._stream()), "bsx_replay_sample")
+        self._draws.add_(1)                              # fresh indices next call, and on every replay of a captured graph
+        o, o_, a = self._b_obs, self._b_obs_, self._b_act
+        return (o.transpose(0, 1), o.reshape(B, -1), a.transpose(0, 1), self._b_rew,
+                o_.transpose(0, 1), o_.reshape(B, -1), self._b_done)

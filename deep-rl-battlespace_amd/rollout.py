@@ -388,8 +388,11 @@ class PolicyRollout:
         self.obs[self.T].copy_(self.env._obs)          # every run starts by moving obs[T] to obs[0]
         self.env_done[self.T].copy_(self.env._env_done)
 
-    def capture(self):
-        """Record the T ticks into a HIP graph (one warm-up pass runs first, on a side stream, as torch requires)."""
+    def capture(self, then=None):
+        """Record the T ticks into a HIP graph (one warm-up pass runs first, on a side stream, as torch requires).
+        then: optional callable recorded into the same graph after the ticks -- e.g. the store and a learner batch,
+        `then=lambda: (buf.append_rollout(ro, range(n)), buf.sample())` with a replay.DeviceReplayBuffer -- so that one run()
+        is rollout, store and sample with no host involvement.  It must only enqueue work (no synchronisation)."""
         s = torch.cuda.Stream(device=self.env.device)
         s.wait_stream(torch.cuda.current_stream(self.env.device))
         with torch.cuda.stream(s):
@@ -400,6 +403,8 @@ class PolicyRollout:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self._body()
+            if then is not None:
+                then()
         return self
 
     def _body(self):

@@ -280,6 +280,61 @@ int bsx_instinct_discrete(const float* obs, void* actions, int out_kind, int64_t
 int bsx_instinct_continuous(const float* obs, double* actions, const double* rnd, int64_t E, int n, int team,
                             uint64_t seed, uint64_t seq, const uint64_t* seq_base, void* stream);
 
+/* ---- the replay ring on device (maddpg/buffer.py:3-67, deep-rl-battlespace_amd/replay.py): append a rollout's transitions and draw
+ * a learner batch with no host round trip, so that rollout -> store -> sample can be one captured HIP graph.
+ *
+ * The ring: M rows of nA agents, float32 obs / obs_next [M][nA][D], act [M][nA][n_act], rew [M][nA], uint8 (bool) done [M][nA], and
+ * `counter`, a device int64 = rows ever stored (the reference's mem_cntr; row k of all time sits at k % M).
+ * 1 <= M < 2^31, 1 <= nA <= BSX_MAX_N, 1 <= D <= 3*BSX_MAX_N + 2, n_act 3 (continuous) or 4 (discrete). */
+typedef struct BsxReplayRing {
+    float* obs;              /* actor_states      float32 [M][nA][D] */
+    float* obs_next;         /* actor_new_states  float32 [M][nA][D] */
+    float* act;              /* action_mem        float32 [M][nA][n_act] */
+    float* rew;              /* rew_mem           float32 [M][nA] */
+    uint8_t* done;           /* done_mem          uint8 [M][nA], 0 / 1 */
+    int64_t* counter;        /* device int64, 8-byte aligned, >= 0 (a negative value is read as an empty ring by the sampler
+                                and wraps modulo M in an append: never an address outside the ring) */
+    int64_t M;
+    int nA, D, n_act;
+} BsxReplayRing;
+
+/* Where source row r (0 <= r < rows) of an append lives.  Field f of agent column c is the contiguous run of `width` elements at
+ * f + r*f_row + c*f_col (strides in ELEMENTS, >= 0; width D for obs / obs_next, n_act for act -- the source row may be wider, e.g. the
+ * rollout's 4-wide score rows under a 3-action ring --, 1 for rew / done).  skip (nullable): uint8 at skip + r*skip_row, non-zero =
+ * row r is not a transition and is not stored.  Two layouts need no copy:
+ *   - a PolicyRollout record, in place: r = t*E + e, obs = &obs[0][0][c0], obs_next = &obs[1][0][c0] (row stride A*D, column stride D),
+ *     act = &scores[0][0][c0] (A*4, 4), rew = &rew[0][0][c0] and done = &done[0][0][c0] (A, 1), skip = env_done (1): the rows of
+ *     running games only (replay.py ReplayBuffer.store_rollout);
+ *   - dense [rows][nA][...] arrays (ReplayBuffer.store_transition), skip = NULL. */
+typedef struct BsxReplaySource {
+    const float* obs; int64_t obs_row, obs_col;
+    const float* obs_next; int64_t obs_next_row, obs_next_col;
+    const float* act; int64_t act_row, act_col;
+    const float* rew; int64_t rew_row, rew_col;
+    const uint8_t* done; int64_t done_row, done_col;
+    const uint8_t* skip; int64_t skip_row;
+} BsxReplaySource;
+
+/* Size of the workspace bsx_replay_append needs for `rows` source rows (1 <= rows < 2^31): 16 + 8 * ceil(rows / 256) bytes. */
+int bsx_replay_workspace_bytes(int64_t rows, size_t* bytes);
+
+/* ReplayBuffer.store_rollout / _put (replay.py; maddpg/buffer.py:25-47), on device.  The kept rows (skip byte zero) take ranks
+ * k = 0 .. R-1 in source order; with old = *counter, rank k goes to ring row (old + k) % M -- if R > M only the ranks k >= R - M,
+ * the newest M rows, as the reference's ring keeps them -- and *counter becomes old + R.  `stored` (nullable, device int64) receives R.
+ * Bit for bit what the torch path stores (done bytes are written as 0 / 1).  Three launches (count kept rows per 256-row tile, one
+ * workgroup scans the counts and moves the counter, scatter); no inter-workgroup waits.  workspace: 8-byte aligned, at least
+ * bsx_replay_workspace_bytes(rows); it must not be in use by another call in flight. */
+int bsx_replay_append(const BsxReplayRing* ring, const BsxReplaySource* src, int64_t rows, void* workspace, int64_t* stored,
+                      void* stream);
+
+/* ReplayBuffer.sample (maddpg/buffer.py:49-67): B indices drawn uniformly with replacement from [0, min(*counter, M)) -- Philox4x32-10
+ * keyed by (seed, seq + *seq_base, b), mapped by multiply-shift (bias below M / 2^32); all zero while the ring is empty -- and the rows
+ * they name, gathered in one pass: idx int64 [B], obs / obs_next float32 [B][nA][D], act [B][nA][n_act], rew [B][nA], done uint8 [B][nA].
+ * seq_base (nullable): a device word the caller advances once per call, so that replays of a captured graph draw fresh indices.
+ * 1 <= B < 2^31. */
+int bsx_replay_sample(const BsxReplayRing* ring, int64_t B, uint64_t seed, uint64_t seq, const uint64_t* seq_base, int64_t* idx,
+                      float* obs, float* obs_next, float* act, float* rew, uint8_t* done, void* stream);
+
 /* Host helper: the call number on which the time-limit tie fires for n-per-team -- the reference accumulates
  * total_time += 0.1 in binary64 and compares >= 10+2n (battle_env.py:168,316-319): 121, 141, 161, 181, 200 ... */
 int bsx_tie_tick(int n);
