@@ -95,6 +95,7 @@ SIGNATURES = {
     "bsx_selftest_atan2": (c_int, [c_int, c_void_p, c_void_p]),
     "bsx_instinct_discrete": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "bsx_instinct_continuous": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "bsx_instinct_continuous_shard": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
     "bsx_actor_blob_floats": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "bsx_actor_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(BsxActorNoise), c_uint64, c_uint64,
                                   c_void_p, c_int64, c_void_p]),

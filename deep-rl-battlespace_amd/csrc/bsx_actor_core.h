@@ -107,13 +107,15 @@ __device__ inline float4 normals4(uint64_t seed, uint64_t seq, uint64_t grow, ui
     return make_float4(m0 * c0, m0 * s0, m1 * c1, m1 * s1);
 }
 
-// Four uniforms in (0, 1) from one Philox4x32-10 block, keyed like normals4 (own salt): the categorical policy's Gumbel draws.
+// Four uniforms from one Philox4x32-10 block, keyed like normals4 (own salt): the categorical policy's Gumbel draws.  23 bits per
+// word, (code + 0.5) * 2^-23: every value is exact and strictly inside (0, 1).  (A 24-bit code needs 25 significant bits once
+// the + 0.5 is added: the top code rounded to exactly 1.0, where -log(-log u) is +inf and forces the action.)
 __device__ inline float4 uniforms4(uint64_t seed, uint64_t seq, uint64_t grow, uint32_t salt) {
 #pragma clang fp contract(fast)
     const uint4 r = philox4x32_10(make_uint4(uint32_t(grow), uint32_t(grow >> 32), uint32_t(seq), uint32_t(seq >> 32) ^ salt),
                                   make_uint2(uint32_t(seed), uint32_t(seed >> 32) ^ 0xA5A5A5A5u));
-    const float k = 1.0f / 16777216.0f;
-    return make_float4((float(r.x >> 8) + 0.5f) * k, (float(r.y >> 8) + 0.5f) * k, (float(r.z >> 8) + 0.5f) * k, (float(r.w >> 8) + 0.5f) * k);
+    const float k = 1.0f / 8388608.0f;
+    return make_float4((float(r.x >> 9) + 0.5f) * k, (float(r.y >> 9) + 0.5f) * k, (float(r.z >> 9) + 0.5f) * k, (float(r.w >> 9) + 0.5f) * k);
 }
 
 // tanh of the head sums + bias, exploration noise, clamp (maddpg/networks.py:85, maddpg/agent.py:30-31) for ONE row.

@@ -23,7 +23,8 @@ __device__ inline int instinct_choose(OB ob, int n, double& td, double& ta) {
 }
 // The scripted opponent's continuous action (instinct/agent.py:41-54) for the chosen target at distance td / angle ta: shoot with
 // probability 0.6 inside 2/3 of the shot distance and 20 degrees, speed from the distance, turn toward the target, uniform(-0.15,
-// 0.15) noise on all three, clip.  Draws: row g of the launch, sequence number seq (bsx_instinct_continuous's keying).
+// 0.15) noise on all three, clip.  Draws: job-wide row g = (env_offset + e) * A + a, sequence number seq (bsx_instinct_continuous's
+// keying), so the noise a game sees does not depend on the sharding.
 __device__ inline void instinct_continuous_draws(uint64_t seed, uint64_t seq, uint64_t g, double& r0, double& n0, double& n1, double& n2) {
     const uint4 r = philox4x32_10(make_uint4(uint32_t(g), uint32_t(g >> 32) ^ 0x10000000u, uint32_t(seq), uint32_t(seq >> 32)),
                                   make_uint2(uint32_t(seed), uint32_t(seed >> 32)));

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(TPB) void bsx_export_kernel(const ExportArgs p) {
 // computes under its pinned numpy.
 struct InstinctArgs {
     const float* obs; void* actions; const double* rnd; int64_t E; int n; int team; int out_kind; int continuous;
-    uint64_t seed; uint64_t seq; const uint64_t* seq_base;
+    uint64_t seed; uint64_t seq; const uint64_t* seq_base; int64_t env_offset;
 };
 
 __global__ __launch_bounds__(TPB) void bsx_instinct_kernel(const InstinctArgs p) {
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(TPB) void bsx_instinct_kernel(const InstinctArgs p)
     }
     double r0, n0, n1, n2;                                        // agent.py:41-54
     if (p.rnd) { r0 = p.rnd[4 * g]; n0 = p.rnd[4 * g + 1]; n1 = p.rnd[4 * g + 2]; n2 = p.rnd[4 * g + 3]; }
-    else instinct_continuous_draws(p.seed, p.seq + (p.seq_base ? *p.seq_base : 0ull), uint64_t(g), r0, n0, n1, n2);
+    else instinct_continuous_draws(p.seed, p.seq + (p.seq_base ? *p.seq_base : 0ull), uint64_t(p.env_offset) * uint64_t(A) + g, r0, n0, n1, n2);
     double* out = static_cast<double*>(p.actions) + 3 * g;
     instinct_continuous_action(td, ta, r0, n0, n1, n2, out[0], out[1], out[2]);
 }
@@ -618,7 +618,18 @@ int bsx_instinct_discrete(const float* obs, void* actions, int out_kind, int64_t
     if (!actions || team < 0 || team > 2 || (out_kind != BSX_ACT_I32 && out_kind != BSX_ACT_LOGITS_F32)) return BSX_E_ARG;
     if (const int rc = check_games(obs, E, n, 4)) return rc;
     if (!aligned(actions, out_kind == BSX_ACT_I32 ? 4 : 16)) return BSX_E_ALIGN;
-    InstinctArgs a{obs, actions, nullptr, E, n, team, out_kind, 0, 0, 0, nullptr};
+    InstinctArgs a{obs, actions, nullptr, E, n, team, out_kind, 0, 0, 0, nullptr, 0};
+    const size_t EA = size_t(E) * 2 * n;
+    hipLaunchKernelGGL(bsx_instinct_kernel, dim3(unsigned((EA + TPB - 1) / TPB)), dim3(TPB), 0, static_cast<hipStream_t>(stream), a);
+    return int(hipGetLastError());
+}
+
+int bsx_instinct_continuous_shard(const float* obs, double* actions, const double* rnd, int64_t E, int n, int team,
+                                  uint64_t seed, uint64_t seq, const uint64_t* seq_base, int64_t env_offset, void* stream) {
+    if (!actions || team < 0 || team > 2 || env_offset < 0) return BSX_E_ARG;
+    if (const int rc = check_games(obs, E, n, 4)) return rc;
+    if (!aligned(actions, 8) || (rnd && !aligned(rnd, 8))) return BSX_E_ALIGN;
+    InstinctArgs a{obs, actions, rnd, E, n, team, 0, 1, seed, seq, seq_base, env_offset};
     const size_t EA = size_t(E) * 2 * n;
     hipLaunchKernelGGL(bsx_instinct_kernel, dim3(unsigned((EA + TPB - 1) / TPB)), dim3(TPB), 0, static_cast<hipStream_t>(stream), a);
     return int(hipGetLastError());
@@ -626,13 +637,7 @@ int bsx_instinct_discrete(const float* obs, void* actions, int out_kind, int64_t
 
 int bsx_instinct_continuous(const float* obs, double* actions, const double* rnd, int64_t E, int n, int team,
                             uint64_t seed, uint64_t seq, const uint64_t* seq_base, void* stream) {
-    if (!actions || team < 0 || team > 2) return BSX_E_ARG;
-    if (const int rc = check_games(obs, E, n, 4)) return rc;
-    if (!aligned(actions, 8) || (rnd && !aligned(rnd, 8))) return BSX_E_ALIGN;
-    InstinctArgs a{obs, actions, rnd, E, n, team, 0, 1, seed, seq, seq_base};
-    const size_t EA = size_t(E) * 2 * n;
-    hipLaunchKernelGGL(bsx_instinct_kernel, dim3(unsigned((EA + TPB - 1) / TPB)), dim3(TPB), 0, static_cast<hipStream_t>(stream), a);
-    return int(hipGetLastError());
+    return bsx_instinct_continuous_shard(obs, actions, rnd, E, n, team, seed, seq, seq_base, 0, stream);
 }
 
 }  // extern "C"

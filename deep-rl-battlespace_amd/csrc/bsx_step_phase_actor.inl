@@ -50,7 +50,7 @@
             if constexpr (!CONT) r4 = one_hot_scores(sact);                     // ... as one-hot score rows
             else {
                 double r0, n0, n1, n2;
-                instinct_continuous_draws(p.iseed, aseq, uint64_t(row), r0, n0, n1, n2);
+                instinct_continuous_draws(p.iseed, aseq, uint64_t(p.env_offset) * uint64_t(A) + row, r0, n0, n1, n2);
                 instinct_continuous_action(td_, ta_, r0, n0, n1, n2, sd0, sd1, sd2);
                 r4 = make_float4(float(sd0), float(sd1), float(sd2), 0.f);      // the record holds them rounded to float32; the step takes the binary64 values
             }

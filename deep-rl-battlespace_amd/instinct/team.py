@@ -59,11 +59,11 @@ class Team:
             if seq is None:                                    # (a caller that captures the call into a graph passes its own number + a device word)
                 self.seq += 1
                 seq = self.seq
-            _lib.check(self._lib.bsx_instinct_continuous(obs_ptr, out.data_ptr(),
+            _lib.check(self._lib.bsx_instinct_continuous_shard(obs_ptr, out.data_ptr(),
                                                          rnd_t.data_ptr() if rnd_t is not None else None, E, env.n_agents,
                                                          self.team, self.seed, int(seq),
-                                                         seq_base.data_ptr() if seq_base is not None else None, stream),
-                       "bsx_instinct_continuous")
+                                                         seq_base.data_ptr() if seq_base is not None else None, env.env_offset, stream),
+                       "bsx_instinct_continuous_shard")
             return out
         if out.dtype == torch.int32 and tuple(out.shape) == (E, A):
             kind = _lib.ACT_I32

@@ -204,6 +204,25 @@ def test_bad_arguments_are_rejected_before_any_launch():
         assert actor(**kw) == want, ("actor_forward", kw)
 
 
+def test_sharded_continuous_instinct_rejects_what_the_unsharded_one_does_and_a_negative_offset():
+    """bsx_instinct_continuous_shard (the scripted opponent's draws keyed by the job-wide row): every refusal of bsx_instinct_continuous
+    at any env_offset >= 0, and a negative env_offset as BSX_E_ARG -- before the alignment checks.  Fake addresses: nothing launches."""
+    lib = _lib().load()
+    A, ARG, ALIGN, big = 4096, -1, -2, (1 << 30) + 1
+
+    def shard(obs=A, act=A, rnd=None, E=4, n=1, team=2, off=0):
+        return lib.bsx_instinct_continuous_shard(obs, act, rnd, E, n, team, 0, 0, None, off, None)
+
+    cases = [(ARG, dict(obs=None)), (ARG, dict(act=None)), (ARG, dict(E=0)), (ARG, dict(E=big)), (ARG, dict(n=0)), (ARG, dict(n=17)),
+             (ARG, dict(team=-1)), (ARG, dict(team=3)), (ALIGN, dict(obs=A + 2)), (ALIGN, dict(act=A + 4)), (ALIGN, dict(rnd=A + 4)),
+             (ARG, dict(rnd=A + 4, team=3)), (ARG, dict(obs=A + 2, act=None))]
+    for off in (0, 5000, (1 << 40)):
+        for want, kw in cases:
+            assert shard(off=off, **kw) == want, (off, kw)
+    for kw in (dict(), dict(obs=A + 2), dict(rnd=A + 4), dict(act=A + 4)):
+        assert shard(off=-1, **kw) == ARG and shard(off=-(1 << 40), **kw) == ARG, kw
+
+
 def test_env_refuses_to_run_without_gpu_or_library():
     import torch
     import deep_rl_battlespace_amd as bsx
