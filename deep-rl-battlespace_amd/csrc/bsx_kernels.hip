@@ -295,8 +295,7 @@ inline bool split_applies(int n, const StepArgs& a, int64_t bound) {
 
 // Both step-kernel templates (bsx_step_kernel.h, bsx_step_split.h) take these arguments: the game count of the launch and the pointers of a
 // wave's first loads lead, so that they arrive in SGPRs with the dispatch (-amdgpu-kernarg-preload-count=15, build.py).
-using StepKernel = void (*)(const int64_t, const uint2* const, const uint2* const, const uint2* const, const void* const, const uint2* const,
-                            const uint32_t* const, const int, const StepArgs);
+using StepKernel = void (*)(BSX_STEP_KERNEL_PARAMS);
 
 // The one dispatch of a launch's team size and offset width to template arguments: f(std::integral_constant<int, N>, std::bool_constant<OFF32>)
 // with N = n for 1v1 ... 4v4 (kernels compiled for their team size), N = 0 beyond (n read at run time).

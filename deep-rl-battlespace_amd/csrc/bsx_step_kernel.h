@@ -33,6 +33,13 @@ struct StepArgs {
     uint64_t iseed;                                      // continuous scripted opponent in the fused rollout: its Philox seed (bsx_instinct_continuous's `seed`)
 };
 
+// The parameters of both step-kernel templates (bsx_step_kernel below, bsx_step_split_kernel in bsx_step_split.h), as their definitions,
+// their explicit instantiations (bsx_step_instances.h) and the launcher's StepKernel (bsx_kernels.hip) spell them: the eight leading ones
+// arrive in SGPRs with the dispatch (see bsx_step_kernel), the argument block follows.
+#define BSX_STEP_KERNEL_PARAMS                                                                                                           \
+    const int64_t E_, const uint2* const envc_, const uint2* const envd_, const uint2* const plane_, const void* const act_,               \
+        const uint2* const bent_, const uint32_t* const bcnt_, const int kind_, const bsxk::StepArgs p_
+
 // Observation row for one agent from the LDS-staged block (battle_env.py:202-244).
 // s_* are indexed by thread id; `gl` = first thread of this env's group.
 template <int N>
@@ -99,12 +106,20 @@ template <class T> __device__ inline T* elem(T* base, uint32_t i) {
     return reinterpret_cast<T*>(reinterpret_cast<byte_t*>(base) + uint32_t(i * uint32_t(sizeof(T))));
 }
 template <class T> __device__ inline T* elem(T* base, size_t i) { return base + i; }
+// MULTI, the end of a tick: the only memory one tick hands to the next is this WAVE's own: its pool entries (stored by one lane, loaded by
+// another of the same wave next tick) plus its LDS rows.  A wavefront's vector memory operations are performed in order through the one L1
+// of its CU, whatever the lane, so wavefront scope is enough: a compiler ordering point, no s_waitcnt -- this tick's stores (observation
+// rows included) drain while the next tick computes.
+__device__ inline void end_of_tick() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 // (the multi-tick 2v2 kernels are compiled for four waves per SIMD: 65 536 games are 4 096 of their waves = four per SIMD, and at 129 ... 135
 //  registers -- three resident waves -- the launch ran as two rounds: 6.9 us per tick against 6.2 for round 3's 125-register kernel)
 template <int N, bool CONT, bool MULTI, bool ACTOR = false, bool LG = false, bool OFF32 = false>
 __global__ __launch_bounds__(SPB * (ACTOR ? group_width(N > 0 ? N : 1) / 2 : WPB)) __attribute__((amdgpu_waves_per_eu((ACTOR && N > 1) ? 2 : ((!ACTOR && MULTI && N == 2) ? 4 : 1))))
-void bsx_step_kernel(const int64_t E_, const uint2* const envc_, const uint2* const envd_, const uint2* const plane_, const void* const act_,
-                     const uint2* const bent_, const uint32_t* const bcnt_, const int kind_, const StepArgs p_) {
+void bsx_step_kernel(BSX_STEP_KERNEL_PARAMS) {
     const StepArgs& p = p_;                              // (the tick loop of the multi-tick forms shadows this name: see there)
     // The eight leading arguments repeat p.E, p.st.envc, p.st.envd, p.st.plane, p.actions, p.st.bent, p.st.bcnt, p.action_kind: fifteen
     // dwords that the dispatcher preloads into SGPRs (-amdgpu-kernarg-preload-count), so that a wave's first loads need nothing
@@ -133,79 +148,8 @@ void bsx_step_kernel(const int64_t E_, const uint2* const envc_, const uint2* co
     // out-of-range lanes read a valid row (the last one) and never store: loads stay unconditional
     const ixs_t ec = env_ok ? e : ixs_t(E_ - 1);
     const ix_t g = ix_t(ec) * A + (a < A ? a : A - 1);
-    constexpr int NE = (N > 0) ? N : 1;                  // compile-time enemy count (runtime-n build reads LDS in loops)
-
-    // LDS is private to this wavefront: accesses are volatile (program order) and the hardware runs one wave's LDS
-    // operations in order, so cross-lane hand-offs need no s_barrier -- only a compiler scheduling fence.
-    constexpr int DROW = (N > 0) ? 3 * N + 2 : 3 * BSX_MAX_N + 2;
-    __shared__ volatile int s_x_all[WAVES * SPB], s_y_all[WAVES * SPB], s_hp_all[WAVES * SPB];
-    __shared__ volatile int s_bhit_all[WAVES * SPB];     // base hits, index gl + shooter team
-    __shared__ __attribute__((aligned(16))) float s_obs_all[WAVES * SPB * DROW];   // observation rows, [wave][lane][D]
-    __shared__ __attribute__((aligned(16))) float s_small[ACTOR ? (N == 1 ? 4 : 2 * N) * bsx_actor::SMALL : 4];   // per-neuron vectors + heads of the actors (1v1: + the two value heads')
-    __shared__ int s_act_all[(ACTOR && !CONT && WAVES > 1) ? WAVES * SPB : 1];       // arg-max per row, ACTOR with several waves
-    __shared__ float s_actf_all[(ACTOR && CONT && WAVES > 1) ? WAVES * SPB * 3 : 1];  // continuous: [speed, turn, shoot] per row
-    __shared__ double s_actd_all[(ACTOR && CONT && WAVES > 1) ? WAVES * SPB * 3 : 1]; // ... of a scripted team's rows, binary64
-    __shared__ int s_gdone_all[(ACTOR && WAVES > 1) ? 32 : 1];                       // game-over flag per game of the workgroup
-    // n >= 2: every plane-to-plane pair is computed ONCE, by one of its two planes, and handed to the other through these
-    __shared__ float s_pd_all[(N >= 2) ? WAVES * SPB * N : 1];      // range (symmetric)
-    __shared__ double s_pr_all[(N >= 2) ? WAVES * SPB * N : 1];     // the owner's bearing in radians, [0, 2 pi)
-    // wave-packed bullet pass: the wave's pool entries (and this call's shots behind them) are WORK SLOTS, one per lane and round
-    __shared__ __attribute__((aligned(8))) u32x2 s_new_all[WAVES * SPB];   // this call's shots as pool entries (age 0, the PRE-move pose), by shot rank
-    __shared__ uint32_t s_agg_all[WAVES * SPB];          // per owner: misses << 16 | base hits << 24
-    // The rectangles a bullet is tested against (enemy base, enemy planes' sprites), staged per owner / per plane for the work slots.
-    // 1v1: as (lower corner, upper corner) pairs of packed (x, y) halves BIASED by +64, so that no half is ever negative and the
-    // corners are plain 32-bit adds of packed literals: a bullet at b overlaps <=> no half of (b - lower) | (upper - b) is negative
-    // (C2 7.33 -> 7.20 us against the centre form: ~15 instructions fewer per round where the instruction count is the bound).
-    // 4v4 and the runtime-n kernel: the centre (x | alive << 15 | y << 16) and the margins as constants in the slot -- measured faster there
-    // (round 3: 4v4 23.1 us against 24.7 with corners; round 4, with the table shot: 20.5 against 20.8).  2v2 / 3v3 take the corner form
-    // since round 4 (with the table shot 10.22 -> 9.67 and 17.97 -> 17.05 us; profiles/r04_experiments.json).
-    constexpr bool CORNERS = N >= 1 && N <= 3;
-    typedef typename std::conditional<CORNERS, u32x2, uint32_t>::type rect_t;
-    __shared__ __attribute__((aligned(8))) rect_t s_eb_all[WAVES * SPB];        // per owner: the enemy base, dx in [-33, 33], dy in [-32, 31]
-    __shared__ __attribute__((aligned(8))) rect_t s_pq_all[WAVES * SPB];        // per plane: its post-move sprite, dx in [-27, 27], dy in [-25, 24]; dead: never hit
-    // rect(centre, alive, margins below / above): what the owner side stages
-    auto make_rect = [](uint32_t c, bool alive, int xl, int yl, int xh, int yh) {
-        if constexpr (CORNERS) return alive ? u32x2{c + pk_const(PK_BIAS - xl, PK_BIAS - yl), c + pk_const(PK_BIAS + xh, PK_BIAS + yh)} : u32x2{0x7F007F00u, 0u};
-        else return c | (alive ? 0x8000u : 0u);
-    };
-    // 0 / -1: does the bullet at b (CORNERS: biased) overlap the rectangle?
-    auto hits_rect = [](s16x2 b, rect_t r, int xl, int yl, int xh, int yh) {
-        if constexpr (CORNERS) return ~pk_any_negative(pk_bits(b - as_pk(r.x)) | pk_bits(as_pk(r.y) - b));
-        else {
-            const s16x2 d = b - as_pk(r & ENT_XY);
-            return ~pk_any_negative(pk_bits(d + as_pk(pk_const(xl, yl))) | pk_bits(as_pk(pk_const(xh, yh)) - d)) & (int(r << 16) >> 31);
-        }
-    };
-    // per owner: what a work slot must know about its bullet's owner: the owner's tick % 12 (the exact-path ring) | 16: the owner's game
-    // is in its physics call (its bullets fly) | 32: the game is being re-spawned by this call (its bullets are dropped)
-    constexpr uint32_t OWN_PHYS = 16u, OWN_DROP = 32u;
-    __shared__ uint32_t s_fl_all[WAVES * SPB];
-    __shared__ __attribute__((aligned(16))) double s_nd_all[WAVES * SPB * 2];   // per owner: this call's shot's float64 step (written and read on the exact path only)
-    // plane-overlap candidates per owner, by AGE (rare): FW bits per age (which enemy planes the bullet of that age overlaps), and where
-    // that bullet's entry now sits in the pool (for the tombstone of a consumed bullet)
-    constexpr int FW = (N > 0 && N <= 4) ? 4 : 16;       // bits per overlap field
-    constexpr int OW = (FW == 4) ? 1 : 3;                // 64-bit words holding the 12 fields
-    __shared__ unsigned long long s_ov_all[WAVES * SPB * OW];
-    __shared__ uint16_t s_pp_all[WAVES * SPB * K];
-    auto* const s_new = BSX_LDS(u32x2, s_new_all) + wave * SPB;
-    auto* const s_agg = BSX_LDS(uint32_t, s_agg_all) + wave * SPB;
-    auto* const s_eb = BSX_LDS(rect_t, s_eb_all) + wave * SPB;
-    auto* const s_pq = BSX_LDS(rect_t, s_pq_all) + wave * SPB;
-    auto* const s_fl = BSX_LDS(uint32_t, s_fl_all) + wave * SPB;
-    auto* const s_nd = BSX_LDS(double, s_nd_all) + wave * SPB * 2;
-    auto* const s_ov = BSX_LDS(unsigned long long, s_ov_all) + wave * SPB * OW;
-    auto* const s_pp = BSX_LDS(uint16_t, s_pp_all) + wave * SPB * K;
-#pragma unroll
-    for (int q = 0; q < OW; ++q) s_ov[tid * OW + q] = 0ull;   // cleared again by whoever finds them set
-    float* const s_pd = s_pd_all + ((N >= 2) ? wave * SPB * N : 0);
-    double* const s_pr = s_pr_all + ((N >= 2) ? wave * SPB * N : 0);
-    // (explicit LDS address space: a volatile access through a generic pointer compiles to flat_load / flat_store)
-    typedef __attribute__((address_space(3))) volatile int lds_vint;
-    lds_vint* const s_x = (lds_vint*)(uintptr_t)(s_x_all) + wave * SPB;
-    lds_vint* const s_y = (lds_vint*)(uintptr_t)(s_y_all) + wave * SPB;
-    lds_vint* const s_hp = (lds_vint*)(uintptr_t)(s_hp_all) + wave * SPB;
-    lds_vint* const s_bhit = (lds_vint*)(uintptr_t)(s_bhit_all) + wave * SPB;
-    float* const s_obs = s_obs_all + wave * SPB * DROW;
+    constexpr int MANY = -1; constexpr bool DRAW = false;   // (not a two-wave form: the LDS layout's hand-off arrays are one element)
+#include "bsx_step_lds.inl"
 
     const bool has_act = kind_ >= 0;                     // an empty call (step({})) comes with action_kind -1 and a dummy, mapped action pointer
     // Raw inputs of one call (decoded at the top of the tick that uses them).
@@ -385,13 +329,11 @@ void bsx_step_kernel(const int64_t E_, const uint2* const envc_, const uint2* co
     // R_*: which parts of the tick this wave runs -- here all of them.  The two-wave 1v1 kernels (bsx_step_split.h: the product's kernels for
     // discrete 1v1 launches up to 114 688 games per call / 65 536 per multi-tick launch, continuous up to 81 920 per call) include the same
     // phase files once per wave with different parts switched on; the phases guard their side effects by these constants and the rest falls
-    // to dead-code elimination.  With every part on, every guard is a compile-time `true` (the ISA of all 76 kernels is unchanged by the guards).
+    // to dead-code elimination.  With every part on, every guard is a compile-time `true` (the ISA of all 76 kernels is unchanged by the guards);
+    // the two kernels share the LDS layout (bsx_step_lds.inl), the parameter list (BSX_STEP_KERNEL_PARAMS) and end_of_tick().
     constexpr bool R_BULLETS = true, R_MOVE = true, R_STAGE = true, R_GEOM = true, R_OUTCOME = true, R_ST_STATE = true, R_ST_OUT = true, R_POSE_LDS = false;
     constexpr int R_RDV_COUNTS = 0, R_GEOM_LDS = 0, R_PUB = 0, R_DRAW_LDS = 0;
     auto split_rendezvous = [] {};                       // (names of the split kernel's role code: never reached here)
-    uint32_t* const s_npl = nullptr;
-    v4f_t* const s_gm = nullptr;
-    v4u_t* const s_t0 = nullptr; v4u_t* const s_pub = nullptr; v4u_t* const s_rw = nullptr;
 #include "bsx_step_phase_actor.inl"
 #include "bsx_step_phase_shot.inl"
 #include "bsx_step_phase_move.inl"
@@ -402,13 +344,7 @@ void bsx_step_kernel(const int64_t E_, const uint2* const envc_, const uint2* co
     STAMP(7);
     if (MULTI) {
         games += uint32_t(cnt_delta.x);
-        // The only memory one tick hands to the next is this WAVE's own: its pool entries (stored by one lane, loaded by another of the
-        // same wave next tick) plus its LDS rows.  A wavefront's vector memory operations are performed in order through the one L1 of
-        // its CU, whatever the lane, so wavefront scope is enough: a compiler ordering point, no s_waitcnt -- this tick's stores
-        // (observation rows included) drain while the next tick computes.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        end_of_tick();
         STAMP(9);
     }
     }   // tick loop

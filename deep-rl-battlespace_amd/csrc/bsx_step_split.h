@@ -45,7 +45,9 @@
 // (7.13 -> 7.5 ... 8.1): above 98 304 games the launcher takes DRAW = false, the first wave draws itself.
 //
 // How.  No second copy of the game logic: the kernel includes the SAME phase files as bsx_step_kernel, once per wave, with the R_*
-// constants of the wave's role.  The phases guard their side effects (LDS staging, stores, the pool pass, the rendezvous) by them;
+// constants of the wave's role, and the same LDS layout (bsx_step_lds.inl, one set of 64 agents that the two waves share), parameter list
+// (BSX_STEP_KERNEL_PARAMS) and end-of-tick fence (end_of_tick).  What stays its own: the role dispatch below, the rendezvous, and each
+// role's first loads and tick head (the role bodies) -- a shared form of those reorders the multi-tick kernels' instructions.  The phases guard their side effects (LDS staging, stores, the pool pass, the rendezvous) by them;
 // everything that only feeds a guarded-off side effect is dead code to the compiler.  Results are those of the one-wave kernels bit
 // for bit: every size the launcher gives to one of these kernels is run against the C oracle (tests/test_hip_fullsize.py), and
 // tests/test_hip_split.py runs them against the one-wave kernels.
@@ -58,8 +60,7 @@ namespace bsxk {
 // DRAW (per call only): the geometry wave also computes the call's Philox block (below); without it the first wave draws itself, as in round 5.
 template <bool LG, bool OFF32, int MANY = 0, bool CONT_ = false, bool DRAW = false>
 __global__ __launch_bounds__(2 * SPB)
-void bsx_step_split_kernel(const int64_t E_, const uint2* const envc_, const uint2* const envd_, const uint2* const plane_, const void* const act_,
-                           const uint2* const bent_, const uint32_t* const bcnt_, const int kind_, const StepArgs p_) {
+void bsx_step_split_kernel(BSX_STEP_KERNEL_PARAMS) {
     constexpr int N = 1;
     constexpr bool CONT = CONT_, MULTI = MANY != 0, ACTOR = false;
     // continuous actions (bsx_step_continuous): the per-call form only -- its geometry wave needs nothing but the poses, so only the
@@ -86,64 +87,7 @@ void bsx_step_split_kernel(const int64_t E_, const uint2* const envc_, const uin
     const ix_t EA = ix_t(MULTI ? E_ : p.E) * ix_t(A);
     const ixs_t ec = env_ok ? e : ixs_t(E_ - 1);
     const ix_t g = ix_t(ec) * A + (a < A ? a : A - 1);
-    constexpr int NE = 1;
-    constexpr int DROW = 3 * N + 2;
-    __shared__ volatile int s_x_all[SPB], s_y_all[SPB], s_hp_all[SPB];
-    __shared__ volatile int s_bhit_all[SPB];
-    __shared__ __attribute__((aligned(16))) float s_obs_all[4];
-    __shared__ __attribute__((aligned(16))) float s_small[4];
-    __shared__ int s_act_all[1];
-    __shared__ float s_actf_all[1];
-    __shared__ double s_actd_all[1];
-    __shared__ int s_gdone_all[1];
-    __shared__ float s_pd_all[1];
-    __shared__ double s_pr_all[1];
-    __shared__ __attribute__((aligned(8))) u32x2 s_new_all[SPB];
-    __shared__ uint32_t s_agg_all[SPB];
-    __shared__ uint32_t s_npl_all[2 * SPB];              // the bullets' counts per shooter (misses | base hits << 8 | plane hits << 16), by tick parity
-    __shared__ __attribute__((aligned(16))) v4u_t s_t0_all[MANY == 0 ? SPB : 1];  // per call: the post-move poses (position, heading, enemy base), wave 0 -> geometry wave
-    __shared__ __attribute__((aligned(16))) v4u_t s_pub_all[MANY == 2 ? 2 * SPB : 1];   // MANY = 2: what a tick's outputs need, game wave -> outputs wave, by tick parity
-    __shared__ __attribute__((aligned(16))) v4f_t s_gm_all[SPB];                  // per call: the four observation values, geometry wave -> storing wave
-    __shared__ __attribute__((aligned(16))) v4u_t s_rw_all[DRAW ? SPB : 1];  // per call: the call's Philox block per lane (jitter or re-spawn), geometry wave -> first wave
-    constexpr bool CORNERS = true;
-    typedef u32x2 rect_t;
-    __shared__ __attribute__((aligned(8))) rect_t s_eb_all[SPB];
-    __shared__ __attribute__((aligned(8))) rect_t s_pq_all[SPB];
-    auto make_rect = [](uint32_t c, bool alive, int xl, int yl, int xh, int yh) {
-        return alive ? u32x2{c + pk_const(PK_BIAS - xl, PK_BIAS - yl), c + pk_const(PK_BIAS + xh, PK_BIAS + yh)} : u32x2{0x7F007F00u, 0u};
-    };
-    auto hits_rect = [](s16x2 b, rect_t r, int xl, int yl, int xh, int yh) {
-        return ~pk_any_negative(pk_bits(b - as_pk(r.x)) | pk_bits(as_pk(r.y) - b));
-    };
-    constexpr uint32_t OWN_PHYS = 16u, OWN_DROP = 32u;
-    __shared__ uint32_t s_fl_all[SPB];
-    __shared__ __attribute__((aligned(16))) double s_nd_all[SPB * 2];
-    constexpr int FW = 4, OW = 1;
-    __shared__ unsigned long long s_ov_all[SPB * OW];
-    __shared__ uint16_t s_pp_all[SPB * K];
-    auto* const s_new = BSX_LDS(u32x2, s_new_all);
-    auto* const s_agg = BSX_LDS(uint32_t, s_agg_all);
-    auto* const s_npl = BSX_LDS(uint32_t, s_npl_all);
-    auto* const s_gm = (__attribute__((address_space(3))) volatile v4f_t*)(uintptr_t)(s_gm_all);
-    auto* const s_pub = (__attribute__((address_space(3))) volatile v4u_t*)(uintptr_t)(s_pub_all);
-    auto* const s_t0 = (__attribute__((address_space(3))) volatile v4u_t*)(uintptr_t)(s_t0_all);
-    auto* const s_rw = (__attribute__((address_space(3))) volatile v4u_t*)(uintptr_t)(s_rw_all);
-    auto* const s_eb = BSX_LDS(rect_t, s_eb_all);
-    auto* const s_pq = BSX_LDS(rect_t, s_pq_all);
-    auto* const s_fl = BSX_LDS(uint32_t, s_fl_all);
-    auto* const s_nd = BSX_LDS(double, s_nd_all);
-    auto* const s_ov = BSX_LDS(unsigned long long, s_ov_all);
-    auto* const s_pp = BSX_LDS(uint16_t, s_pp_all);
-    float* const s_pd = s_pd_all;
-    double* const s_pr = s_pr_all;
-    typedef __attribute__((address_space(3))) volatile int lds_vint;
-    lds_vint* const s_x = (lds_vint*)(uintptr_t)(s_x_all);
-    lds_vint* const s_y = (lds_vint*)(uintptr_t)(s_y_all);
-    lds_vint* const s_hp = (lds_vint*)(uintptr_t)(s_hp_all);
-    lds_vint* const s_bhit = (lds_vint*)(uintptr_t)(s_bhit_all);
-    float* const s_obs = s_obs_all;
-    (void)s_small; (void)s_act_all; (void)s_actf_all; (void)s_actd_all; (void)s_gdone_all; (void)s_obs; (void)s_pd; (void)s_pr;
-    (void)s_x; (void)s_y; (void)s_hp; (void)s_bhit; (void)DROW; (void)wave; (void)EA;
+#include "bsx_step_lds.inl"
     // the two waves of a workgroup meet: every LDS operation of this wave has landed (lgkmcnt) before it arrives, nothing of it is
     // reordered across (the LDS arrays are volatile; the asm is a compiler fence).  Global stores in flight (the shot's heading in the
     // export ring, pool entries) are NOT waited for: nothing the other wave reads travels through global memory.

@@ -14,9 +14,7 @@
         float* const obs_t = p.obs;
         float* const rew_t = p.rew;
         uint8_t* const done_t = p.done;
-        (void)eb; (void)u_t; (void)obs_t; (void)rew_t; (void)done_t; (void)EAt;
         RawIn rin_next = {}; DecIn din_next = {-1, 0.0};             // (named by the phases behind `if (MULTI ...)`: never reached in this form)
-        (void)rin_next; (void)din_next;
         // ---- T0: every load of the call, back to back
         int x = 0, y = 0, hp = 0;
         uint32_t games = 0;
@@ -26,11 +24,10 @@
         uint2 pool_first = make_uint2(0u, 0u);
         int act = -1;
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, uu_in = 0.0;
-        (void)a0; (void)a1; (void)a2;
         STAMP(0);
         {
             uint2 ecw, edw, prw;
-            double dirf = 0.0; (void)dirf;
+            double dirf = 0.0;
             ecw = *elem(envc_, ix_t(ec));
             edw = *elem(envd_, ix_t(ec));
             prw = *elem(plane_, gt);

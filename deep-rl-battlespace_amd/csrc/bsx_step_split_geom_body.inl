@@ -43,12 +43,11 @@
         // what the phase file names besides: the exact-shot store is the first wave's (R_BULLETS), this wave takes no part in it
         constexpr bool R_BULLETS = false, R_GEOM = true, CHEAP_SHOT = false;
         constexpr int R_GEOM_LDS = 1;
-        const int team = 0, lane = tid, ks = 0, gl = tid & ~(G - 1), eb = gl;
+        const int team = 0, ks = 0, gl = tid & ~(G - 1), eb = gl;
         const bool shot_exact = false, spawn = false, nexact = false;
         double nbdir = 0.0;
         double2 nd = make_double2(0.0, 0.0);
         const ix_t gt = g, EAt = 0;
-        (void)lane; (void)ks; (void)shot_exact; (void)spawn; (void)nexact; (void)nbdir; (void)nd; (void)gt; (void)EAt; (void)team; (void)gl; (void)eb;
 #include "bsx_step_phase_geometry.inl"
         STAMP(4); STAMP(5); STAMP(6);
         split_rendezvous();                              // the hand-over before the stores (bsx_step_phase_stores.inl, R_GEOM_LDS)

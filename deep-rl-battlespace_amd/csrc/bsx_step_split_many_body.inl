@@ -31,7 +31,6 @@
             float* const obs_t = p.obs + int64_t(tk) * p.obs_ts;
             float* const rew_t = p.rew + int64_t(tk) * p.rew_ts;
             uint8_t* const done_t = p.done + int64_t(tk) * p.done_ts;
-            (void)eb; (void)u_t; (void)obs_t; (void)rew_t; (void)done_t; (void)EAt; (void)env_offset_t;
             if (tk == 0) {
                 const uint2 ecw = *elem(envc_, ix_t(ec));
                 const uint2 edw = *elem(envd_, ix_t(ec));
@@ -49,7 +48,6 @@
             const DecIn din = din_next;
             int act = din.act;
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, uu_in = din.uu;
-            (void)a0; (void)a1; (void)a2;
 #include "bsx_step_phase_actor.inl"
 #include "bsx_step_phase_shot.inl"
 #include "bsx_step_phase_move.inl"
@@ -58,8 +56,6 @@
 #include "bsx_step_phase_outcome.inl"
 #include "bsx_step_phase_stores.inl"
             games += uint32_t(cnt_delta.x);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            end_of_tick();
         }
     }

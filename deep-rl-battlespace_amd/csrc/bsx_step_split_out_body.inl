@@ -3,7 +3,6 @@
 // observation geometry and the output stores of bsx_step_kernel's phase files on them -- none of the game logic, no loads.
     {
         RawIn rin_next = {}; DecIn din_next = {-1, 0.0};
-        (void)rin_next; (void)din_next;
         for (int tk = 0; tk < p_.T; ++tk) {
             ix_t gt = g, EAt = EA;
             asm volatile("" : "+v"(gt));
@@ -19,7 +18,6 @@
             float* const obs_t = p.obs + int64_t(tk) * p.obs_ts;
             float* const rew_t = p.rew + int64_t(tk) * p.rew_ts;
             uint8_t* const done_t = p.done + int64_t(tk) * p.done_ts;
-            (void)eb; (void)EAt; (void)gl;
             split_rendezvous();                          // the game wave has published this tick
             const v4u_t pb = s_pub[(tk & 1) * SPB + tid];
             int x = sx16(pb.x), y = sy16(pb.x), hp = 0;
@@ -36,7 +34,6 @@
             const bool shot_exact = false, spawn = false, nexact = false;
             const double nbdir = 0.0; double2 nd = make_double2(0.0, 0.0); const int ks = 0;
             const int4 cnt_delta = make_int4(0, 0, 0, 0); const uint32_t games = 0u; const uint32_t pc = 0u;
-            (void)hp; (void)nbdir; (void)nd; (void)ks; (void)cnt_delta; (void)games; (void)pc; (void)shot_exact; (void)spawn; (void)nexact; (void)mode;
 #include "bsx_step_phase_geometry.inl"
 #include "bsx_step_phase_stores.inl"
         }
