@@ -10,10 +10,12 @@ Only what the hot path needs lives here:
   instinct/      the reference's scripted opponent, evaluated on device (next row f-2)
   rollout.py     on-device actor + step loop in one HIP graph (next row f-1); csrc/bsx_actor.hip is its MFMA actor
   replay.py      device-resident transition ring, mirror of maddpg/buffer.py (next row f-3)
+  advantage.py   GAE advantages / returns / per-agent mask of a rollout on device, for on-policy learners (csrc/bsx_advantage.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
-from . import envs, instinct  # noqa: F401
+from . import advantage, envs, instinct  # noqa: F401
+from .advantage import gae  # noqa: F401
 from .envs.battle_env import parallel_env  # noqa: F401
 
-__all__ = ["envs", "instinct", "parallel_env"]
+__all__ = ["advantage", "envs", "gae", "instinct", "parallel_env"]

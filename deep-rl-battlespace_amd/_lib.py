@@ -61,6 +61,10 @@ class BsxReplaySource(ctypes.Structure):
                 ("skip", c_void_p), ("skip_row", c_int64)]
 
 
+class BsxGaeIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("rew", "value", "done", "env_done", "last_value", "done_prev", "adv", "ret", "mask")]
+
+
 # name -> (restype, argtypes): every symbol include/battlespace_hip.h declares
 SIGNATURES = {
     "bsx_abi_version": (c_int, []),
@@ -103,6 +107,8 @@ SIGNATURES = {
     "bsx_replay_append": (c_int, [ctypes.POINTER(BsxReplayRing), ctypes.POINTER(BsxReplaySource), c_int64, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_sample": (c_int, [ctypes.POINTER(BsxReplayRing), c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsx_gae_workspace_bytes": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_gae": (c_int, [ctypes.POINTER(BsxGaeIo), c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -44,7 +44,9 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_step_rollout.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_actor.hip"), ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
            # the replay ring (append / sample): copies bits and draws integers, no floating-point arithmetic to pin
-           (os.path.join(CSRC, "bsx_replay.hip"), [])]
+           (os.path.join(CSRC, "bsx_replay.hip"), []),
+           # GAE advantages: float32 operations each rounded on their own, as tests/gae_util.py restates them
+           (os.path.join(CSRC, "bsx_advantage.hip"), ["-ffp-contract=off"])]
 
 
 def _stale():

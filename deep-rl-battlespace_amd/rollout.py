@@ -242,6 +242,8 @@ class PolicyRollout:
         ro.valid[t]                    # bool [E]: tick t found the game running.  A tick on a FINISHED game is the reference's
                                        # inert call (battle_env.py:303-306) or, with auto_reset, the re-spawn: its row pairs the old
                                        # game's last observation with the new game's first and is not a transition
+        ro.adv[t], ro.ret[t], ro.mask[t]  # gae=dict(gamma, lam[, normalize]) with a value_actor: GAE advantages and returns of the
+                                       # rows that are the agent's own decisions (advantage.gae), computed inside the same run
 
     The env must be batched, discrete, rng='philox'; auto_reset is recommended (finished games re-spawn in place).
     Exploration noise on the score vectors is Gaussian (noise_std) and/or the reference's Ornstein-Uhlenbeck process
@@ -249,7 +251,7 @@ class PolicyRollout:
     kernel and restarted per game; then clamp(-1, 1) as maddpg/agent.py:31 does."""
 
     def __init__(self, env, actor, T, noise_std=0.0, fused=True, seed=0, opponent=None, ou_scale=0.0, one_launch=False,
-                 precision="f32", ou_restart=True, sample=None, temperature=1.0, value_actor=None, chains="auto"):
+                 precision="f32", ou_restart=True, sample=None, temperature=1.0, value_actor=None, chains="auto", gae=None):
         """actor: a StackedActor.  fused=True evaluates it with the hand-written HIP kernel (FusedActor), False with
         torch ops (the fp32 reference of the same op).  opponent: an `instinct.Team` that plays its team's planes
         instead of the actor (the reference's training setup, main.py:119-122: learned red vs scripted blue): its
@@ -325,6 +327,26 @@ class PolicyRollout:
                 raise ValueError("the one-launch rollout takes a value head at 1v1 only (use the graph form)")
             self.value_actor, self._value_w = value_actor, value_actor.pack()
             self.value = torch.zeros((T, E, A), dtype=torch.float32, device=dev)
+        # gae=dict(gamma, lam[, normalize]): an on-policy learner's inputs, computed in the same graph after the ticks (advantage.gae):
+        # last_value = V(obs[T]) by one value-only pass of the fused actor, then adv / ret / mask [T, E, A] and, with normalize, adv_stats
+        # = (n, mean, std).  _done_prev carries the agents' done flags from one run to the next (start() seeds it from the env).
+        self._gae = None
+        if gae is not None:
+            if value_actor is None:
+                raise ValueError("gae= needs a value_actor (the bootstrap value V(obs[T]) and value[t] come from it)")
+            from . import advantage
+            self._gae = dict(gamma=float(gae["gamma"]), lam=float(gae["lam"]), normalize=bool(gae.get("normalize", False)))
+            advantage.check_rates(self._gae["gamma"], self._gae["lam"])
+            self.adv = torch.zeros((T, E, A), dtype=torch.float32, device=dev)
+            self.ret = torch.zeros((T, E, A), dtype=torch.float32, device=dev)
+            self._mask = torch.zeros((T, E, A), dtype=torch.uint8, device=dev)
+            self.mask = self._mask.view(torch.bool)
+            self.last_value = torch.zeros((E, A), dtype=torch.float32, device=dev)
+            self.adv_stats = torch.zeros(3, dtype=torch.float64, device=dev)
+            self._done_prev = torch.zeros((E, A), dtype=torch.uint8, device=dev)
+            self._lv_scores = torch.zeros((E, A, 4), dtype=torch.float32, device=dev)      # the actor half of the value pass (not read)
+            self._gae_ws = (torch.empty(advantage.workspace_bytes(E, A, T), dtype=torch.uint8, device=dev)
+                            if self._gae["normalize"] else None)
         self.obs = torch.empty((T + 1, E, A, D), dtype=torch.float32, device=dev)
         # discrete: 4 action scores, arg-maxed in the step kernel; continuous: [speed, turn, shoot] + one unused column
         self.scores = torch.zeros((T, E, A, 4), dtype=torch.float32, device=dev)
@@ -387,6 +409,8 @@ class PolicyRollout:
         """Begin from the env's current observations (call after env.reset())."""
         self.obs[self.T].copy_(self.env._obs)          # every run starts by moving obs[T] to obs[0]
         self.env_done[self.T].copy_(self.env._env_done)
+        if self._gae is not None:
+            self._done_prev.copy_(self.env._done)
 
     def capture(self, then=None):
         """Record the T ticks into a HIP graph (one warm-up pass runs first, on a side stream, as torch requires).
@@ -429,7 +453,18 @@ class PolicyRollout:
                     self._tick(t, games)
             self.env.fork_join(ranges, ticks, self._side)
             self.env._env_done.copy_(self.env_done[self.T])        # the per-tick launches wrote their flags into the record
+        if self._gae is not None:
+            self._advantages()
         self._seq_base.add_(self.T)                    # fresh exploration-noise keys for the next run
+
+    def _advantages(self):
+        """V(obs[T]) into last_value, then GAE over this run's records.  The value pass draws nothing (no noise, no sample, no OU state)
+        and takes an explicit sequence number: the actor's `seq`, `_seq_base` and every noise state stay as the ticks left them."""
+        from . import advantage
+        self.fused.forward_into(self.obs[self.T], self._lv_scores, 0.0, seq=0, value=dict(weights=self._value_w, out=self.last_value))
+        g = self._gae
+        advantage.gae(self.rew, self.value, self.last_value, self._done, self.env_done, self._done_prev, g["gamma"], g["lam"],
+                      normalize=g["normalize"], out=(self.adv, self.ret, self._mask), stats=self.adv_stats, workspace=self._gae_ws)
 
     def run(self):
         """T ticks (asynchronous).  Afterwards obs[0..T], scores, rew, done hold this rollout's transitions."""
