@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- agent-steps/sec of the fused Battlespace step() on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline and nothing else: it sets up, warms up, times the K-step blocks, writes --dump-outputs and
+prints the line.  --full adds everything else this script measures, after the timed region: the CPU baseline, the other
+workloads (4v4, 1 M games, bullet-heavy, continuous, multi-tick, chained graphs, policy rollouts, the drop-in surface) and the two
+live rocprofv3 --pmc passes; --no-cpu-baseline / --no-other-workloads / --no-live-traffic leave one of them out of a --full run.
 
 Launched plainly with --gpus N > 1 this process touches no GPU: it starts N children (one per GPU, RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1), waits for them and exits with their code; rank 0's child prints the
@@ -35,13 +40,13 @@ duration (B); peak = 8 TB/s; frac = achieved / peak is the contract figure (prin
 then more than the launch moves).  frac_on_traffic is the same duration against the bytes that actually reached HBM: PMC
 FETCH_SIZE x 2 + WRITE_SIZE, collected by two child runs of this script under `rocprofv3 --kernel-trace --pmc` (one counter per
 pass, as MI355X_MICROARCH.md prescribes) right after the timed region -- the counters cannot be read from inside this process;
-`traffic_source` says so, or names the profiles/traffic.json series that was used instead (`--no-live-traffic`, no rocprofv3, a
-profiler already attached, N > 1; always for `other_workloads`).  frac_claimed = min(frac, frac_on_traffic) is the figure to quote;
-live_aware_bytes_per_launch is what this build's layout must move with the measured bullet load (b_live below).
+`traffic_source` says so, or names the profiles/traffic.json series that was used instead (a run without --full, `--no-live-traffic`,
+no rocprofv3, a profiler already attached, N > 1; always for `other_workloads`).  frac_claimed = min(frac, frac_on_traffic) is the
+figure to quote; live_aware_bytes_per_launch is what this build's layout must move with the measured bullet load (b_live below).
 chained_graphs (not the headline; `--chains P` runs any workload that way): the same K steps with every graph's launches as P
 independent chains over game ranges (parallel_env.capture_steps(chains=P), bsx_step_*_range): per step the whole batch still
 advances one tick -- as P launches that wait only for their own range's previous launch.  Same games bit for bit.
-cpu_baseline: the CPU oracle (oracle/battlespace_ref.py, the scalar Python restatement of the reference's step()) on
+cpu_baseline (--full): the CPU oracle (oracle/battlespace_ref.py, the scalar Python restatement of the reference's step()) on
 configs[0] -- 1 game of 1v1, the same uniform random actions, reset on done -- one process PINNED to one host core of this box
 (BASELINE.md section 3); beside it the same port at 4v4 (`port_4v4`, the same-run CPU figure for configs[2]) and, as context, the C
 port on all cores and the reference's own survey-time figures.
@@ -330,11 +335,14 @@ def parse_args(argv=None):
                          "nothing else (profiles/r06_traced_runs.json: why)")
     ap.add_argument("--one-wave", action="store_true", help="A/B: keep the one-wave 1v1 kernels (BSX_F_ONE_WAVE) where the library would take a two-wave form; same results")
     ap.add_argument("--no-stagger", action="store_true", help="leave all games on the same clock (time-limit ties in lock-step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the extra (non-headline) measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the CPU baseline, the other workloads and the headline's HBM bytes (the three "
+                         "legs below); without it a run measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full: skip the extra (non-headline) measurements")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) that measure the headline's HBM bytes; "
-                         "roofline.traffic then comes from profiles/traffic.json")
+                    help="--full: do not run the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) that measure the headline's HBM "
+                         "bytes; roofline.traffic then comes from profiles/traffic.json")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default=None,
                     help="process-group backend for the barrier / timing reduction (nccl = RCCL; gloo only to rehearse N>1 on a 1-GPU box)")
     ap.add_argument("--rehearse-on-device0", action="store_true",
@@ -345,7 +353,10 @@ def parse_args(argv=None):
                          "the same timed path and write what its last step returned (rank 0's shard) as DIR/obs.npy, rew.npy, done.npy "
                          "(float32; a seeded sample of the games, listed in DIR/games.npy, when they would exceed 64 MB): the same "
                          "arguments give the same inputs, so two builds can be compared output for output")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:                                       # a plain run: the headline alone, none of the legs that run after it
+        args.no_cpu_baseline = args.no_other_workloads = args.no_live_traffic = True
+    return args
 
 
 DUMP_LIMIT_BYTES = 64 << 20

@@ -145,15 +145,15 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
 
 
 def test_bench_measures_the_headline_hbm_traffic_live():
-    """roofline.traffic is measured by the run itself: bench.py re-runs its workload in two child passes under `rocprofv3
+    """roofline.traffic is measured by the run itself (--full): bench.py re-runs its workload in two child passes under `rocprofv3
     --kernel-trace --pmc` (FETCH_SIZE, WRITE_SIZE separately) and reports (2 x fetch + write) KiB per launch, with the source
     spelled out; frac_on_traffic follows from it."""
     import json, os, shutil, subprocess, sys
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not installed")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "200", "--warmup", "20", "--repeats", "2", "--no-cpu-baseline",
-                          "--no-other-workloads"], capture_output=True, text=True, timeout=600, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "200", "--warmup", "20", "--repeats", "2", "--full",
+                          "--no-cpu-baseline", "--no-other-workloads"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     r = d["roofline"]

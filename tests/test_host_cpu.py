@@ -559,6 +559,20 @@ def test_rank_affinity_blocks_are_disjoint_and_follow_the_cards_numa_nodes(tmp_p
         assert all(g[0]["cores"] == g[1] and g[0]["how"] == "plain" for g in got) and not set(got[0][1]) & set(got[1][1])
 
 
+def test_a_plain_bench_run_measures_the_headline_alone():
+    """`bench.py` without --full leaves out every leg that runs after the headline (CPU baseline, other workloads, live counter
+    passes); --full runs them all, and a --no-* option still leaves its own leg out of a --full run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    legs = ("no_cpu_baseline", "no_other_workloads", "no_live_traffic")
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not a.full and all(getattr(a, k) for k in legs) and (a.steps, a.warmup) == (20, 5)
+    f = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert f.full and not any(getattr(f, k) for k in legs)
+    g = bench.parse_args(["--full", "--no-live-traffic"])
+    assert g.no_live_traffic and not g.no_cpu_baseline and not g.no_other_workloads
+
+
 def test_bench_line_helpers_survive_failed_variants_and_describe_a_multi_rank_job():
     """(1) ADVICE r4: a rollout variant that failed is recorded as {"error": ...}; the compact summary (the line's last key) must turn
     it into null instead of raising -- the line must always be printed.  (2) the N > 1 fields computed from per-rank samples."""

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs ON THE GPU BOX (via gpurun): the evidence bundle for one measurement series.
 #   tools/profile_round.sh <tag>      e.g. r02_a
-# 1) plain bench lines (default run with every workload; the driver's `--steps 20 --warmup 5` form)
+# 1) bench lines with --full (every workload; the default steps and the driver's `--steps 20 --warmup 5` form)
 # 2) rocprofv3 --kernel-trace --stats of both forms (kernel summary CSV)
 # 3) per workload, separate --pmc passes for FETCH_SIZE and WRITE_SIZE (never combined with other trace domains), plus SQ_* / TCC
 #    passes for the headline.  Output: gpurun_out/<tag>/...; condensed into profiles/ by tools/collect_profile.py <tag>.
@@ -14,8 +14,8 @@ mkdir -p $O
 trap 'for d in $O/pmc_*/ $O/stats $O/stats20; do rm -rf $d; done' EXIT   # (the raw counter CSVs are tens of MB: never left behind, however the script ends)
 B="--no-cpu-baseline --no-other-workloads --no-live-traffic"   # (the runs below are themselves under rocprofv3: no nested passes)
 echo "[$(date +%T)] bench lines"
-timeout -k 10 400 python bench.py > $O/bench_default.json
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json
+timeout -k 10 400 python bench.py --full > $O/bench_default.json
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $O/bench_steps20.json
 echo "[$(date +%T)] rocprof stats"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py $B > $O/bench_C2_under_rocprof.json 2> $O/stats.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats20 -- python bench.py --steps 20 --warmup 5 $B > $O/bench_steps20_under_rocprof.json 2> $O/stats20.err
