@@ -261,8 +261,8 @@ inline bool family_claim(const void* state, bool cont) {
     if (f == 0) f = cont ? 2 : 1;
     return f == (cont ? 2 : 1);
 }
-inline int grid_for(int64_t E, int n, int tpb = TPB) {
-    const int epb = tpb / group_width(n);
+inline int grid_for(int64_t E, int n) {             // reset / observe: 256 threads = TPB / G games per workgroup
+    const int epb = TPB / group_width(n);
     return int((E + epb - 1) / epb);
 }
 
@@ -340,9 +340,10 @@ int launch_for_n(const StepArgs& a, int64_t bound, void* stream) {
         }
     });
     // a workgroup per 64 agents -- one wave, or the two waves of the two-wave kernels -- or, in the fused rollout, per 32 games = G/2 waves
-    // (an MFMA tile is 32 rows of ONE actor, bsx_step_kernel.h)
-    const dim3 grid(ACTOR ? unsigned((bound + 31) / 32) : unsigned(grid_for(bound, n, SPB * WPB)));
-    const dim3 block(ACTOR ? SPB * group_width(n) / 2 : (two_wave ? 2 * SPB : SPB * WPB));
+    // (an MFMA tile is 32 rows of ONE actor, bsx_step_kernel.h); wave_blocks (bsx_state.h) counts a pool for every wave this starts
+    const StepGeometry geo = step_geometry(ACTOR ? FORM_ROLLOUT : (two_wave ? FORM_TWO_WAVE : FORM_ONE_WAVE), bound, n);
+    const dim3 grid(unsigned(geo.groups));
+    const dim3 block(SPB * geo.waves);
     hipLaunchKernelGGL(k, grid, block, 0, static_cast<hipStream_t>(stream),
                        bound, a.st.envc, a.st.envd, a.st.plane, a.actions, a.st.bent, a.st.bcnt, a.action_kind, a);
     return int(hipGetLastError());
@@ -418,7 +419,7 @@ int rollout(void* state, int64_t E, int n, int T, const float* weights, int prec
     if (T < 1 || T > BSX_MAX_T || !weights || !obs || !scores || !rew || !done || !cfg || (flags & BSX_F_EMPTY_CALL) ||
         (precision != BSX_ACTOR_F32 && precision != BSX_ACTOR_BF16X3 && precision != BSX_ACTOR_BF16X6) || scripted_team < -1 || scripted_team > 1)
         return BSX_E_ARG;
-    if (const int rc = check_games(state, E, n, 256, 4)) return rc;
+    if (const int rc = check_games(state, E, n, 256, ROLLOUT_MAX_N)) return rc;
     if (!aligned(weights, 16) || !aligned(scores, 16) || !aligned(obs, 4) || !aligned(rew, 4)) return BSX_E_ALIGN;
     BsxActorNoise nz = {};
     if (noise) nz = *noise;

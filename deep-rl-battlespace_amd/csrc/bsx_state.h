@@ -65,7 +65,28 @@ __host__ __device__ constexpr int group_width(int n) {
     while (g < 2 * n) g <<= 1;
     return g;
 }
-__host__ __device__ inline int64_t wave_blocks(int64_t E, int n) { const int epb = 64 / group_width(n); return (E + epb - 1) / epb; }
+constexpr int ROLLOUT_MAX_N = 4;                  // the fused rollout is built for 1v1 ... 4v4
+
+// The launch geometry of the step-kernel forms (launch_for_n, bsx_kernels.hip): `groups` workgroups of `waves` wavefronts over `games`
+// games.  Wave w of workgroup b works on the pool of wave block b * pools + w * pools / waves -- its own one, or, in the two-wave 1v1
+// kernels, the one pool its workgroup's two waves share.  A wave block is 64 lanes = 64 / G games whatever the form, so pools stay
+// indexed by e / (64 / G) and a launch over a range of games starts at block first / (64 / G).
+enum StepForm : int { FORM_ONE_WAVE = 0, FORM_TWO_WAVE = 1, FORM_ROLLOUT = 2 };
+struct StepGeometry { int64_t groups; int waves, pools; };
+__host__ __device__ inline StepGeometry step_geometry(int form, int64_t games, int n) {
+    const int G = group_width(n), epb = 64 / G;
+    if (form == FORM_ROLLOUT) return {(games + 31) / 32, G / 2, G / 2};   // 32 games = G/2 waves (an MFMA tile is 32 rows of ONE actor)
+    if (form == FORM_TWO_WAVE) return {(games + epb - 1) / epb, 2, 1};    // 1v1: two waves on one block's games and pool
+    return {(games + WPB * epb - 1) / (WPB * epb), WPB, WPB};
+}
+// Pools the state holds: one for every wave the widest launch over the E games starts.  For n <= ROLLOUT_MAX_N that is the fused
+// rollout, whose last workgroup covers 32 games even when fewer are left: its waves wholly beyond the batch load their pool's first
+// row and count and store the count back (bsx_step_kernel.h), so they get pools of their own, zeroed by bsx_state_init and never
+// holding a game.  Beyond that, and for every E that is a multiple of 32, this is ceil(E / (64 / G)): one pool per block of games.
+__host__ __device__ inline int64_t wave_blocks(int64_t E, int n) {
+    const StepGeometry w = step_geometry(n <= ROLLOUT_MAX_N ? FORM_ROLLOUT : FORM_ONE_WAVE, E, n);
+    return w.groups * w.pools;
+}
 
 __host__ __device__ inline Layout make_layout(int64_t E, int n) {
     Layout L;

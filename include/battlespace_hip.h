@@ -76,7 +76,8 @@ int bsx_build_flags(void);
  * Holds what parallel_env holds between calls (battle_env.py:165-184,254-276): planes, bases, bullets, time, flags,
  * win/tie counters, plus the 361-entry discrete-heading displacement table.  Layout (ABI 14): 8-byte plane and game records, the
  * base positions in an array of their own, and one dense bullet pool per block of 64 lanes (= 64 / G games, G = the next power of two
- * >= 2n): what a step() moves is what the game holds, not the 12 bullet slots per plane the reference's objects reserve. */
+ * >= 2n; for n <= 4 as many as the fused rollout's waves, G/2 per 32 games): what a step() moves is what the game holds, not the 12 bullet
+ * slots per plane the reference's objects reserve. */
 int bsx_state_bytes(int64_t E, int n, size_t* bytes);
 
 /* One-time initialisation of a state block: zeroes it and uploads the heading table

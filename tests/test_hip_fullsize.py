@@ -737,10 +737,12 @@ def test_continuous_policy_rollout(fused):
         PolicyRollout(env, StackedActor(A, D, 4, device="cuda"), T)                 # discrete head on a continuous env
 
 
-@pytest.mark.parametrize("E,n", [(1, 1), (31, 1), (5, 4), (33, 3), (2, 2)])
+@pytest.mark.parametrize("E,n", [(1, 1), (31, 1), (5, 4), (33, 3), (2, 2), (1, 3), (7, 3), (3, 4), (9, 2)])
 def test_one_launch_rollout_tiny_and_ragged_batches(E, n):
-    """Workgroups of the fused rollout cover 32 games: batches smaller than that, and waves that lie entirely beyond the
-    batch, must neither read nor write out of range -- and still play what the per-tick kernels play."""
+    """Workgroups of the fused rollout cover 32 games: batches smaller than that, and batches whose last workgroup has waves wholly
+    beyond the last game, play what the per-tick kernels play -- observations, scores, rewards, dones and the exported state bit for
+    bit -- and leave a guard tensor allocated behind the rollout buffers as it was.  (Where such waves read and write: the pools
+    test_footprint_cpu.py checks; every buffer in a guard slab: test_hip_guards.py.)"""
     from deep_rl_battlespace_amd.rollout import PolicyRollout, StackedActor
     T = 12
     torch.manual_seed(E + n)

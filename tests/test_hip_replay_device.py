@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from guard_util import guards_intact as _guards_intact, slab as _slab
+
 pytestmark = pytest.mark.gpu
 
 RING_FIELDS = ("actor_states", "actor_new_states", "action_mem", "rew_mem", "done_mem")
@@ -211,16 +213,6 @@ def test_sampler_range_uniformity_determinism_and_tuple():
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(cap.last_idx, draws[0][k]), k
-
-
-def _slab(n, dtype, fill, pad=256):
-    """A tensor of n elements with `pad` guard elements on either side: (whole slab, the inner view)."""
-    t = torch.full((n + 2 * pad,), fill, dtype=dtype, device="cuda")
-    return t, t[pad:pad + n]
-
-
-def _guards_intact(slab, fill, n, pad=256):
-    return bool((slab[:pad] == fill).all()) and bool((slab[pad + n:] == fill).all())
 
 
 def test_no_stray_writes_at_a_ragged_size():
