@@ -39,6 +39,10 @@ class BsxActorNoise(ctypes.Structure):
                 ("value_weights", ctypes.c_void_p), ("value", ctypes.c_void_p)]
 
 
+class BsxGaussianHead(ctypes.Structure):
+    _fields_ = [("log_std", ctypes.c_void_p), ("logp", ctypes.c_void_p)]
+
+
 EXPORT_FIELDS = ("px", "py", "pdir", "php", "palive", "base_xy", "bhp", "tick", "env_done", "winner",
                  "bl_live", "bl_x", "bl_y", "bl_dir", "counters")
 
@@ -91,6 +95,10 @@ SIGNATURES = {
     "bsx_rollout_continuous": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, ctypes.POINTER(BsxRewards), c_uint32, ctypes.POINTER(BsxActorNoise), c_uint64,
                                        c_uint64, c_void_p, c_uint64, c_int64, c_void_p]),
+    "bsx_rollout_continuous_gaussian": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_uint64, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(BsxRewards), c_uint32,
+                                                ctypes.POINTER(BsxActorNoise), ctypes.POINTER(BsxGaussianHead), c_uint64, c_uint64, c_void_p,
+                                                c_uint64, c_int64, c_void_p]),
     "bsx_observe": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "bsx_export_state": (c_int, [c_void_p, c_int64, c_int, ctypes.POINTER(BsxExport), c_void_p]),
     "bsx_tie_tick": (c_int, [c_int]),
@@ -103,6 +111,8 @@ SIGNATURES = {
     "bsx_actor_blob_floats": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "bsx_actor_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(BsxActorNoise), c_uint64, c_uint64,
                                   c_void_p, c_int64, c_void_p]),
+    "bsx_actor_forward_gaussian": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(BsxActorNoise),
+                                           ctypes.POINTER(BsxGaussianHead), c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
     "bsx_replay_workspace_bytes": (c_int, [c_int64, ctypes.POINTER(c_size_t)]),
     "bsx_replay_append": (c_int, [ctypes.POINTER(BsxReplayRing), ctypes.POINTER(BsxReplaySource), c_int64, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_sample": (c_int, [ctypes.POINTER(BsxReplayRing), c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -118,6 +118,11 @@ __device__ inline float4 uniforms4(uint64_t seed, uint64_t seq, uint64_t grow, u
     return make_float4((float(r.x >> 9) + 0.5f) * k, (float(r.y >> 9) + 0.5f) * k, (float(r.z >> 9) + 0.5f) * k, (float(r.w >> 9) + 0.5f) * k);
 }
 
+// The salt of the Gaussian policy head's normals (finish_row<true>), distinct from the three in use: 0x00000000 (exploration noise, or the
+// OU increment), 0x80000000 (the white term beside OU), 0x40000000 (the categorical head's uniforms).
+constexpr uint32_t GAUSS_SALT = 0xC0000000u;
+constexpr float HALF_LOG_2PI = 0.91893853320467274f;   // log(2 pi) / 2
+
 // tanh of the head sums + bias, exploration noise, clamp (maddpg/networks.py:85, maddpg/agent.py:30-31) for ONE row.
 // `row` indexes this launch's arrays (OU state, injected normals); `grow` = the job-wide row (env_offset + e)*A + a keys the
 // draws, so the noise a game sees does not depend on the sharding.  Optional Ornstein-Uhlenbeck state at ou_state[row]
@@ -125,13 +130,27 @@ __device__ inline float4 uniforms4(uint64_t seed, uint64_t seq, uint64_t grow, u
 // own draw (salt) -- the OU increment and the white term are independent.  `store`: this lane owns a real row.
 // sample_mode 1 (categorical policy): the row becomes scores / temperature + Gumbel noise -- its arg-max is a draw from
 // softmax(scores / temperature) -- and the drawn action's log-probability goes to nz.logp[orow] (orow: the row in a [T][E*A] record).
-template <class NZ>   // BsxActorNoise, in whatever address space the caller holds it (the fused kernels read it from the kernarg segment)
+// GAUSS (continuous actions: bsx_actor_forward_gaussian, bsx_rollout_continuous_gaussian): the Gaussian policy head instead of all of the
+// above -- the Gaussian noise term with one sigma per column and no clamp.  mu = the tanh row, sigma_k = exp(log_std[k]) (`log_std`: the
+// row's plane's three values, read here, late), a = mu + sigma * z with z = columns 0..2 of the injected normals or of normals4 under
+// GAUSS_SALT; the row goes out UNCLIPPED with column 3 = 0, and log N(a; mu, sigma) summed over the three columns goes to logp[orow]
+// (nullable).  No tanh-squash correction: the clip to [-1, 1] belongs to the env's step (battle_env.py:295-297), not to the policy.
+template <bool GAUSS = false, class NZ>   // NZ: BsxActorNoise, in whatever address space the caller holds it (the fused kernels read it from the kernarg segment)
 __device__ inline float4 finish_row(float4 r4, const float4 b3, const NZ& nz, uint64_t seed, uint64_t seq,
-                                    size_t row, uint64_t grow, bool game_over, bool store, size_t orow) {
+                                    size_t row, uint64_t grow, bool game_over, bool store, size_t orow,
+                                    const float* log_std = nullptr, float* logp = nullptr) {
     // No implicit contraction in here: the stand-alone actor kernel and the fused rollout must produce the same bits, and which
     // multiply the back end would fuse into which add depends on the code around the call.  Every fused operation is spelled out.
 #pragma clang fp contract(off)
     r4.x = tanhf(r4.x + b3.x); r4.y = tanhf(r4.y + b3.y); r4.z = tanhf(r4.z + b3.z); r4.w = tanhf(r4.w + b3.w);
+    if constexpr (GAUSS) {
+        const float4 z = nz.z_inject ? reinterpret_cast<const float4*>(nz.z_inject)[row] : normals4(seed, seq, grow, GAUSS_SALT);
+        const float l0 = log_std[0], l1 = log_std[1], l2 = log_std[2];
+        r4.x = fmaf(expf(l0), z.x, r4.x); r4.y = fmaf(expf(l1), z.y, r4.y); r4.z = fmaf(expf(l2), z.z, r4.z); r4.w = 0.f;
+        const float q = fmaf(-0.5f * z.x, z.x, -l0) + fmaf(-0.5f * z.y, z.y, -l1) + fmaf(-0.5f * z.z, z.z, -l2);
+        if (store && logp) logp[orow] = q - 3.0f * HALF_LOG_2PI;
+        return r4;
+    }
     if (nz.gaussian_std > 0.f || nz.ou_scale > 0.f) {
         const float4 z = nz.z_inject ? reinterpret_cast<const float4*>(nz.z_inject)[row] : normals4(seed, seq, grow, 0u);
         if (nz.ou_scale > 0.f) {

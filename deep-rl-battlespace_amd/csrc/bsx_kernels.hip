@@ -415,14 +415,19 @@ template <bool CONT>
 int rollout(void* state, int64_t E, int n, int T, const float* weights, int precision, int scripted_team, uint64_t scripted_seed, float* obs,
             float* scores, float* rew, uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg,
             uint32_t flags, const BsxActorNoise* noise, uint64_t actor_seed, uint64_t seq, const uint64_t* seq_base, uint64_t seed,
-            int64_t env_offset, void* stream) {
+            int64_t env_offset, void* stream, bool gauss = false, const BsxGaussianHead* head = nullptr) {
     if (T < 1 || T > BSX_MAX_T || !weights || !obs || !scores || !rew || !done || !cfg || (flags & BSX_F_EMPTY_CALL) ||
         (precision != BSX_ACTOR_F32 && precision != BSX_ACTOR_BF16X3 && precision != BSX_ACTOR_BF16X6) || scripted_team < -1 || scripted_team > 1)
         return BSX_E_ARG;
+    if (gauss && (!head || !head->log_std)) return BSX_E_ARG;       // (bsx_rollout_continuous_gaussian: the head is required)
     if (const int rc = check_games(state, E, n, 256, ROLLOUT_MAX_N)) return rc;
     if (!aligned(weights, 16) || !aligned(scores, 16) || !aligned(obs, 4) || !aligned(rew, 4)) return BSX_E_ALIGN;
     BsxActorNoise nz = {};
     if (noise) nz = *noise;
+    if (gauss) {                                         // the Gaussian head replaces the exploration noise and the categorical head
+        if (nz.gaussian_std > 0.f || nz.ou_scale > 0.f || nz.sample_mode != 0 || nz.u_inject || nz.logp) return BSX_E_ARG;
+        if (!aligned(head->log_std, 4) || (head->logp && !aligned(head->logp, 4))) return BSX_E_ALIGN;
+    }
     if (nz.ou_scale > 0.f && (!nz.ou_state || !aligned(nz.ou_state, 16))) return nz.ou_state ? BSX_E_ALIGN : BSX_E_ARG;
     if (nz.z_inject || nz.u_inject) return BSX_E_ARG;    // injected draws are per call: bsx_actor_forward only
     if (nz.sample_mode != 0 && (nz.sample_mode != 1 || !(nz.temperature > 0.f) || CONT)) return BSX_E_ARG;   // a categorical head belongs to discrete actions
@@ -435,6 +440,7 @@ int rollout(void* state, int64_t E, int n, int T, const float* weights, int prec
     a.obs = obs + EA * D; a.obs_ts = EA * D; a.rew_ts = EA; a.done_ts = EA;
     a.aw = weights; a.aprec = precision; a.scripted_team = scripted_team; a.obs0 = obs; a.scores = scores; a.scores_ts = EA * 4; a.nz = nz;
     a.aseed = actor_seed; a.aseq = seq; a.aseq_base = seq_base; a.iseed = scripted_seed;
+    if (gauss) a.gh = *head;
     return launch_for_n<CONT, true, true, false>(a, E, stream);
 }
 
@@ -562,6 +568,15 @@ int bsx_rollout_continuous(void* state, int64_t E, int n, int T, const float* we
                            int64_t env_offset, void* stream) {
     return rollout<true>(state, E, n, T, weights, precision, scripted_team, scripted_seed, obs, scores, rew, done, env_done, winner, env_done_t, cfg, flags,
                          noise, actor_seed, seq, seq_base, seed, env_offset, stream);
+}
+
+int bsx_rollout_continuous_gaussian(void* state, int64_t E, int n, int T, const float* weights, int precision, int scripted_team,
+                                    uint64_t scripted_seed, float* obs, float* scores, float* rew,
+                                    uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg,
+                                    uint32_t flags, const BsxActorNoise* noise, const BsxGaussianHead* head, uint64_t actor_seed,
+                                    uint64_t seq, const uint64_t* seq_base, uint64_t seed, int64_t env_offset, void* stream) {
+    return rollout<true>(state, E, n, T, weights, precision, scripted_team, scripted_seed, obs, scores, rew, done, env_done, winner, env_done_t, cfg, flags,
+                         noise, actor_seed, seq, seq_base, seed, env_offset, stream, true, head);
 }
 
 // Self-test of atan2_pixels against the device library on the square [-R, R]^2 of argument pairs: out[0] = pairs whose 64-bit

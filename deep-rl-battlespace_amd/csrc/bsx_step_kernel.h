@@ -31,6 +31,7 @@ struct StepArgs {
     // fused rollout (bsx_rollout_discrete): the actor in front of every tick
     const float* aw; int aprec; int scripted_team /* -1 none, 0 red, 1 blue */; const float* obs0; float* scores; int64_t scores_ts; BsxActorNoise nz; uint64_t aseed, aseq; const uint64_t* aseq_base;
     uint64_t iseed;                                      // continuous scripted opponent in the fused rollout: its Philox seed (bsx_instinct_continuous's `seed`)
+    BsxGaussianHead gh;                                  // continuous fused rollout: the Gaussian policy head (bsx_rollout_continuous_gaussian; log_std null = none)
 };
 
 // The parameters of both step-kernel templates (bsx_step_kernel below, bsx_step_split_kernel in bsx_step_split.h), as their definitions,

@@ -1,7 +1,7 @@
 // bsx_step_phase_actor.inl -- a PHASE of bsx_step_kernel's tick (bsx_step_kernel.h includes it inside the kernel body, in tick order; it shares the
 // kernel's locals, so this is a textual unit for reading and review, not a function): fused rollout only (ACTOR): this tick's actions = arg-max / squash of actor(obs) on the wave's LDS observation rows (MFMA, bsx_actor_core.h), or the
-// scripted opponent's.  Reads: s_obs_all, s_small, er.done, p (weights, noise, seeds).  Writes: act (discrete) or a0, a1, a2 (continuous), p.scores,
-// p.nz.logp / value.  Compiles to nothing in the per-step and multi-tick kernels.
+// scripted opponent's.  Reads: s_obs_all, s_small, er.done, p (weights, noise, Gaussian head, seeds).  Writes: act (discrete) or a0, a1, a2 (continuous),
+// p.scores, p.nz.logp / p.gh.logp (continuous instances only) / value.  Compiles to nothing in the per-step and multi-tick kernels.
 // The contract (tools/check_phase_contract.py checks it against this file's text in the CPU suite; names are the kernel's locals):
 // @reads -
 // @writes  a0 a1 a2 act
@@ -53,6 +53,15 @@
                 instinct_continuous_draws(p.iseed, aseq, uint64_t(p.env_offset) * uint64_t(A) + row, r0, n0, n1, n2);
                 instinct_continuous_action(td_, ta_, r0, n0, n1, n2, sd0, sd1, sd2);
                 r4 = make_float4(float(sd0), float(sd1), float(sd2), 0.f);      // the record holds them rounded to float32; the step takes the binary64 values
+            }
+        } else if constexpr (CONT) {
+            if (p.gh.log_std) {                          // uniform: the Gaussian policy head; the lane's row is plane mine_c's, its three log-std
+                                                         // values a per-lane load (L1 / L2-resident), issued late
+                r4 = bsx_actor::finish_row<true>(r4, b3, p.nz, p.aseed, aseq, row, uint64_t(p.env_offset) * uint64_t(A) + row, false, row_ok,
+                                                 size_t(tk) * size_t(E_) * size_t(A) + row, p.gh.log_std + 3 * mine_c, p.gh.logp);
+            } else {
+                r4 = bsx_actor::finish_row(r4, b3, p.nz, p.aseed, aseq, row, uint64_t(p.env_offset) * uint64_t(A) + row, game_over, row_ok,
+                                           size_t(tk) * size_t(E_) * size_t(A) + row);
             }
         } else {
             r4 = bsx_actor::finish_row(r4, b3, p.nz, p.aseed, aseq, row, uint64_t(p.env_offset) * uint64_t(A) + row, game_over, row_ok,

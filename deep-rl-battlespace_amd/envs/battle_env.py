@@ -472,8 +472,9 @@ class parallel_env:
         return obs, rew, done.view(torch.bool)
 
     def _launch_rollout(self, T, weights_ptr, precision, scripted_team, obs_ptr, scores_ptr, rew_ptr, done_ptr, noise, actor_seed, seq,
-                        seq_base_ptr, env_done_t_ptr=None, scripted_seed=0):
-        """Enqueue bsx_rollout_discrete / bsx_rollout_continuous: T ticks of (actor -> step) in one launch (rollout.PolicyRollout)."""
+                        seq_base_ptr, env_done_t_ptr=None, scripted_seed=0, head=None):
+        """Enqueue bsx_rollout_discrete / bsx_rollout_continuous: T ticks of (actor -> step) in one launch (rollout.PolicyRollout).
+        head: a BsxGaussianHead (continuous only) = bsx_rollout_continuous_gaussian."""
         if self.n_agents > 4:
             raise ValueError("the one-launch rollout is built for 1v1 ... 4v4")
         flags = self._base_flags
@@ -481,7 +482,14 @@ class parallel_env:
                   ctypes.byref(noise) if noise is not None else None, int(actor_seed), int(seq), seq_base_ptr, self.seed,
                   self.env_offset, self._stream())
         with self._guard():
-            if self.continuous_actions:
+            if head is not None:
+                if not self.continuous_actions:
+                    raise ValueError("the Gaussian policy head is for a continuous-action env")
+                _lib.check(self._lib.bsx_rollout_continuous_gaussian(
+                    self._state.data_ptr(), self.n_envs, self.n_agents, int(T), weights_ptr, int(precision), int(scripted_team),
+                    int(scripted_seed) & 0xFFFFFFFFFFFFFFFF, obs_ptr, scores_ptr, rew_ptr, done_ptr, *common[:5], common[5],
+                    ctypes.byref(head), *common[6:]), "bsx_rollout_continuous_gaussian")
+            elif self.continuous_actions:
                 _lib.check(self._lib.bsx_rollout_continuous(self._state.data_ptr(), self.n_envs, self.n_agents, int(T), weights_ptr,
                                                             int(precision), int(scripted_team), int(scripted_seed) & 0xFFFFFFFFFFFFFFFF,
                                                             obs_ptr, scores_ptr, rew_ptr, done_ptr, *common),

@@ -201,35 +201,79 @@ class FusedActor:
             nz.ou_keep = 0 if ou.get("restart", True) else 1
         return nz
 
-    def forward_into(self, obs, scores, noise_std=0.0, seq=None, seq_base=None, ou=None, z=None, sample=None, value=None, games=None):
+    def head_struct(self, E, gaussian, noise_std=0.0, ou=None, sample=None):
+        """BsxGaussianHead for E games (continuous-action actors): gaussian = dict(log_std[, logp]) -- the Gaussian policy head.  `log_std` a
+        contiguous float32 [A, 3] device tensor, one row per plane, read by the kernel at every launch (kept by reference: an in-place
+        update is seen by the next replay of a captured graph); `logp` a contiguous float32 tensor ([E, A], or [T, E, A] for a one-launch
+        rollout) that receives log N(a; mu, sigma) summed over the three columns.  The head replaces the exploration noise and the
+        categorical head: noise_std, ou and sample are refused with it."""
+        if self.actor.n_actions != 3:
+            raise ValueError("the Gaussian policy head needs a continuous-action actor (3 outputs)")
+        if noise_std > 0.0 or ou is not None or sample is not None:
+            raise ValueError("the Gaussian policy head excludes exploration noise (noise_std, ou) and the categorical head (sample)")
+        ls, lp = gaussian["log_std"], gaussian.get("logp")
+        if (not isinstance(ls, torch.Tensor) or ls.dtype != torch.float32 or not ls.is_contiguous() or tuple(ls.shape) != (2 * self.n, 3)
+                or ls.device != self.weights.device):
+            raise ValueError("gaussian['log_std'] must be a contiguous float32 [A, 3] tensor on the actor's device")
+        if lp is not None and (lp.dtype != torch.float32 or not lp.is_contiguous() or tuple(lp.shape[-2:]) != (E, 2 * self.n)):
+            raise ValueError("gaussian['logp'] must be a contiguous float32 [.., E, A] tensor")
+        return _lib.BsxGaussianHead(ls.data_ptr(), lp.data_ptr() if lp is not None else None)
+
+    def forward_into(self, obs, scores, noise_std=0.0, seq=None, seq_base=None, ou=None, z=None, sample=None, value=None, games=None,
+                     gaussian=None):
         """obs f32 [E, A, D] (contiguous) -> scores f32 [E, A, 4] (contiguous, 16-byte aligned), on the current stream.
         noise_std: Gaussian exploration noise.  ou: optional dict(scale, state[, theta, sigma, mu, env_done]) for the
         reference's Ornstein-Uhlenbeck noise (utils/noise.py): `state` is a float32 [E, A, 4] tensor updated in place,
         `env_done` a uint8 [E] tensor whose set rows restart the process.
         seq_base: optional int64 device tensor (1 element) added to `seq` in-kernel (for captured graphs).
         games: (first, count) = evaluate only that range of the games (every tensor still the full one; the noise is keyed by the
-        global row, so the draws are those of the full call)."""
+        global row, so the draws are those of the full call).
+        gaussian: dict(log_std[, logp]) -- the Gaussian policy head (head_struct; continuous actors): `scores` receives the unclipped draws
+        a = mu + exp(log_std) * z, column 3 = 0; `z` (if given) supplies the normals of columns 0..2 instead of the in-kernel draws."""
         off = self.env_offset
         if games is not None:
             sl = slice(int(games[0]), int(games[0]) + int(games[1]))
             cut = lambda d, keys: None if d is None else dict(d, **{k: d[k][sl] for k in keys if d.get(k) is not None})   # noqa: E731
             obs, scores, z = obs[sl], scores[sl], (z[sl] if z is not None else None)
             ou, sample, value = cut(ou, ("state", "env_done")), cut(sample, ("logp", "u")), cut(value, ("out",))
+            gaussian = cut(gaussian, ("logp",))
             off += int(games[0])
         E = obs.shape[0]
         if seq is None:
             self.seq += 1
             seq = self.seq
+        head = self.head_struct(E, gaussian, noise_std, ou, sample) if gaussian is not None else None
         nz = self.noise_struct(E, noise_std, ou, z, sample, value)
-        _lib.check(self._lib.bsx_actor_forward(self.weights.data_ptr(), obs.data_ptr(), scores.data_ptr(), E, self.n, self.precision,
-                                               _lib.ctypes.byref(nz) if nz is not None else None, self.seed, int(seq),
-                                               seq_base.data_ptr() if seq_base is not None else None, off,
-                                               torch.cuda.current_stream(obs.device).cuda_stream), "bsx_actor_forward")
+        if head is not None and nz is None and z is not None:       # the head's injected normals with no other noise field
+            if z.dtype != torch.float32 or tuple(z.shape) != (E, 2 * self.n, 4) or not z.is_contiguous():
+                raise ValueError("z must be a contiguous float32 [E, A, 4] tensor")
+            nz = _lib.BsxActorNoise()
+            nz.z_inject = z.data_ptr()
+        args = (self.weights.data_ptr(), obs.data_ptr(), scores.data_ptr(), E, self.n, self.precision,
+                _lib.ctypes.byref(nz) if nz is not None else None)
+        tail = (self.seed, int(seq), seq_base.data_ptr() if seq_base is not None else None, off, torch.cuda.current_stream(obs.device).cuda_stream)
+        if head is not None:
+            _lib.check(self._lib.bsx_actor_forward_gaussian(*args, _lib.ctypes.byref(head), *tail), "bsx_actor_forward_gaussian")
+        else:
+            _lib.check(self._lib.bsx_actor_forward(*args, *tail), "bsx_actor_forward")
         return scores
 
     def __call__(self, obs, noise_std=0.0, seq=None):
         scores = torch.empty((*obs.shape[:2], 4), dtype=torch.float32, device=obs.device)
         return self.forward_into(obs.contiguous(), scores, noise_std, seq)
+
+
+def gaussian_log_prob(actor, log_std, obs, actions):
+    """The Gaussian policy head on the learner's side (what a PPO update takes the ratio of): (logp, entropy), each [.., E, A], of
+    `actions` [.., E, A, 3 or 4] (the recorded, unclipped rows; a fourth column is ignored) under Normal(tanh(actor(obs)), exp(log_std)),
+    summed over the three action columns.  actor: a StackedActor with 3 outputs; log_std: [A, 3]; obs: [.., E, A, D].  Differentiable in
+    the actor's parameters and log_std; the float32 reference of the in-kernel head (bsx_actor_forward_gaussian)."""
+    A, D = obs.shape[-2], obs.shape[-1]
+    mu = actor(obs.reshape(-1, A, D)).reshape(*obs.shape[:-1], 3)
+    z = (actions[..., :3] - mu) * torch.exp(-log_std)
+    logp = (-0.5 * z * z - log_std).sum(-1) - 1.5 * math.log(2.0 * math.pi)
+    entropy = (log_std + 0.5 * (1.0 + math.log(2.0 * math.pi))).sum(-1).expand_as(logp)
+    return logp, entropy
 
 
 class PolicyRollout:
@@ -244,6 +288,12 @@ class PolicyRollout:
                                        # game's last observation with the new game's first and is not a transition
         ro.adv[t], ro.ret[t], ro.mask[t]  # gae=dict(gamma, lam[, normalize]) with a value_actor: GAE advantages and returns of the
                                        # rows that are the agent's own decisions (advantage.gae), computed inside the same run
+        ro.logp[t]                     # sample="categorical" / "gaussian": the log-probability of the action taken
+
+    Continuous PPO (a continuous env): sample="gaussian" with log_std = a float32 [A, 3] tensor (one row per plane, kept by reference, read at
+    every replay) draws a = tanh(actor(obs)) + exp(log_std) * z in-kernel; scores[t][..., :3] record the unclipped draws (the env's step
+    clips them to [-1, 1], as the reference's does), logp[t] = Normal(mu, sigma).log_prob(a).sum(-1) -- gaussian_log_prob() is its learner
+    side.  Rows a scripted opponent plays carry logp 0.
 
     The env must be batched, discrete, rng='philox'; auto_reset is recommended (finished games re-spawn in place).
     Exploration noise on the score vectors is Gaussian (noise_std) and/or the reference's Ornstein-Uhlenbeck process
@@ -251,7 +301,7 @@ class PolicyRollout:
     kernel and restarted per game; then clamp(-1, 1) as maddpg/agent.py:31 does."""
 
     def __init__(self, env, actor, T, noise_std=0.0, fused=True, seed=0, opponent=None, ou_scale=0.0, one_launch=False,
-                 precision="f32", ou_restart=True, sample=None, temperature=1.0, value_actor=None, chains="auto", gae=None):
+                 precision="f32", ou_restart=True, sample=None, temperature=1.0, value_actor=None, chains="auto", gae=None, log_std=None):
         """actor: a StackedActor.  fused=True evaluates it with the hand-written HIP kernel (FusedActor), False with
         torch ops (the fp32 reference of the same op).  opponent: an `instinct.Team` that plays its team's planes
         instead of the actor (the reference's training setup, main.py:119-122: learned red vs scripted blue): its
@@ -313,12 +363,29 @@ class PolicyRollout:
         # the action is DRAWN from softmax(scores / temperature) in-kernel, `logp[t]` holds its log-probability; value_actor (a
         # StackedActor with one output per agent) adds `value[t]` = V(obs[t]).  Fused actor only; the one-launch form takes the value
         # head at 1v1.
-        if sample not in (None, "categorical"):
-            raise ValueError("sample must be None or 'categorical'")
-        if (sample is not None or value_actor is not None) and (not fused or self.continuous):
-            raise ValueError("the categorical / value heads need the fused actor and a discrete env")
+        # sample="gaussian" (continuous env): the Gaussian policy head -- a = tanh(actor(obs)) + exp(log_std) * z drawn in-kernel, recorded
+        # unclipped, with its log-probability in logp[t]; `log_std` (float32 [A, 3]) is the caller's tensor, kept by reference.
+        if sample not in (None, "categorical", "gaussian"):
+            raise ValueError("sample must be None, 'categorical' or 'gaussian'")
+        if sample == "categorical" and (not fused or self.continuous):
+            raise ValueError("the categorical head needs the fused actor and a discrete env")
+        if value_actor is not None and not fused:
+            raise ValueError("the value head needs the fused actor")
+        self._gauss = None
+        if sample == "gaussian":
+            if not fused or not self.continuous:
+                raise ValueError("the Gaussian policy head needs the fused actor and a continuous env")
+            if self.noise_std > 0.0 or ou_scale > 0.0:
+                raise ValueError("the Gaussian policy head excludes exploration noise (noise_std, ou_scale)")
+            if (not isinstance(log_std, torch.Tensor) or log_std.dtype != torch.float32 or not log_std.is_contiguous()
+                    or tuple(log_std.shape) != (A, 3) or log_std.device != torch.device(dev)):
+                raise ValueError("log_std must be a contiguous float32 [A, 3] tensor on the env's device")
+            self._gauss = dict(log_std=log_std)
+        elif log_std is not None:
+            raise ValueError("log_std belongs to sample='gaussian'")
+        self.log_std = log_std
         self.logp = torch.zeros((T, E, A), dtype=torch.float32, device=dev) if sample is not None else None
-        self._sample = dict(temperature=float(temperature)) if sample is not None else None
+        self._sample = dict(temperature=float(temperature)) if sample == "categorical" else None
         self.value, self._value_w = None, None
         if value_actor is not None:
             if value_actor.n_actions != 1 or value_actor.n_actors != A or value_actor.obs_len != D:
@@ -376,14 +443,17 @@ class PolicyRollout:
             ou = dict(self.ou, env_done=self.env_done[t] if self.ou["restart"] else None) if self.ou is not None else None
             sample = dict(self._sample, logp=self.logp[t]) if self._sample is not None else None
             value = dict(weights=self._value_w, out=self.value[t]) if self._value_w is not None else None
+            gaussian = dict(self._gauss, logp=self.logp[t]) if self._gauss is not None else None
             self.fused.forward_into(self.obs[t], self.scores[t], self.noise_std, seq=t, seq_base=self._seq_base, ou=ou, sample=sample, value=value,
-                                    games=games)
+                                    games=games, gaussian=gaussian)
             if self._act64 is not None:
                 cols = slice(self.opponent._cols[0], self.opponent._cols[-1] + 1)   # a team's planes are adjacent columns (a slice: nothing is uploaded while capturing)
                 self._act64.copy_(self.scores[t][..., :3])
                 self.opponent.write_actions(out=self._act64, obs=self.obs[t], seq=t, seq_base=self._seq_base)
                 self.scores[t][:, cols, :3] = self._act64[:, cols].float()      # the record: the scripted rows rounded to float32, as the one-launch form writes them
                 self.scores[t][:, cols, 3] = 0.0
+                if self._gauss is not None:
+                    self.logp[t][:, cols] = 0.0                                  # the actor's draws on those rows were not played
                 self.env._launch(self._act64.data_ptr(), _lib.ACT_F64, False, None,
                                  self.obs[t + 1].data_ptr(), self.rew[t].data_ptr(), self._done[t].data_ptr(),
                                  env_done_ptr=self.env_done[t + 1].data_ptr())
@@ -438,11 +508,12 @@ class PolicyRollout:
             sample = dict(self._sample, logp=self.logp) if self._sample is not None else None
             value = dict(weights=self._value_w, out=self.value) if self._value_w is not None else None
             nz = self.fused.noise_struct(self.env.n_envs, self.noise_std, self.ou, sample=sample, value=value)
+            head = (self.fused.head_struct(self.env.n_envs, dict(self._gauss, logp=self.logp)) if self._gauss is not None else None)
             self.env._launch_rollout(self.T, self.fused.weights.data_ptr(), self.fused.precision,
                                      -1 if self.opponent is None else self.opponent.team, self.obs.data_ptr(), self.scores.data_ptr(),
                                      self.rew.data_ptr(), self._done.data_ptr(), nz, self.fused.seed, 0, self._seq_base.data_ptr(),
                                      env_done_t_ptr=self.env_done[1].data_ptr(),
-                                     scripted_seed=0 if self.opponent is None else self.opponent.seed)
+                                     scripted_seed=0 if self.opponent is None else self.opponent.seed, head=head)
         else:
             ranges = self.env.chain_ranges(self.chains)
             if self._side is None:

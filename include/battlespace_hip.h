@@ -237,6 +237,28 @@ int bsx_actor_forward(const float* weights, const float* obs, float* scores, int
                       const BsxActorNoise* noise, uint64_t seed, uint64_t seq, const uint64_t* seq_base, int64_t env_offset,
                       void* stream);
 
+/* ---- the Gaussian policy head of a continuous-action PPO / A2C learner: a diagonal Gaussian with a state-independent log-std per
+ * action dimension and plane.  For every row a learned actor plays:
+ *   mu = tanh(head + b3) (columns 0..2 = speed, turn, shoot: the actor's output), sigma_k = exp(log_std[a][k]),
+ *   a = mu + sigma * z, z ~ N(0, I): columns x, y, z of the Philox normals keyed like every other actor draw (seed, seq + *seq_base,
+ *       job-wide row (env_offset + e)*A + a), under a salt of their own;
+ *   the row written to `scores` is the UNCLIPPED a, column 3 = 0.  The step clips continuous actions to [-1, 1] itself
+ *       (battle_env.py:295-297), so the env plays what the reference plays for that action and the record is the policy's sample;
+ *   logp = sum_k (-z_k^2 / 2 - log_std_k) - 3/2 log(2 pi) = Normal(mu, sigma).log_prob(a).sum(-1).  No tanh-squash correction:
+ *       the clip belongs to the env, not to the policy.
+ * The head replaces the exploration noise and the categorical head: with it, gaussian_std > 0, ou_scale > 0, sample_mode != 0,
+ * u_inject and BsxActorNoise.logp are refused (BSX_E_ARG).  A value head (value_weights / value) may ride along as usual. */
+typedef struct BsxGaussianHead {
+    const float* log_std;     /* float32 [A*3], 4-byte aligned, required: read at every launch (a captured graph sees in-place updates) */
+    float* logp;              /* nullable float32 [E*A] (bsx_rollout_continuous_gaussian: [T][E*A]), 4-byte aligned */
+} BsxGaussianHead;
+/* bsx_actor_forward with the Gaussian head, for a continuous-action actor: noise->z_inject (nullable) supplies the policy's normals in
+ * columns 0..2, per call (tests).  BSX_E_ARG: a null head or log_std, or a refused noise field; BSX_E_ALIGN: log_std or logp misaligned;
+ * otherwise the checks and codes of bsx_actor_forward, in its order. */
+int bsx_actor_forward_gaussian(const float* weights, const float* obs, float* scores, int64_t E, int n, int precision,
+                               const BsxActorNoise* noise, const BsxGaussianHead* head, uint64_t seed, uint64_t seq,
+                               const uint64_t* seq_base, int64_t env_offset, void* stream);
+
 /* The caller's rollout loop -- `for t in range(T): actions = actor(obs) (+ noise, clamp); obs, rew, done = step(actions)`
  * (main.py:177-181 with maddpg/agent.py:25-33) -- in ONE launch: T x (bsx_actor_forward -> bsx_step_discrete with
  * BSX_ACT_LOGITS_F32), same results bit for bit.  A wavefront keeps its games' observation rows in LDS (the step writes
@@ -270,6 +292,15 @@ int bsx_rollout_continuous(void* state, int64_t E, int n, int T, const float* we
                            uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg, uint32_t flags,
                            const BsxActorNoise* noise, uint64_t actor_seed, uint64_t seq, const uint64_t* seq_base,
                            uint64_t seed, int64_t env_offset, void* stream);
+/* bsx_rollout_continuous with the Gaussian head (above) on every row an actor plays: `scores` [T][E*A*4] records the unclipped draws,
+ * head->logp [T][E*A] their log-probabilities.  The scripted opponent's rows (scripted_team) are played as in bsx_rollout_continuous;
+ * their logp is never written (callers zero the buffer).  A value head is taken at n = 1, as bsx_rollout_continuous takes it; injected
+ * draws are refused.  Same results, bit for bit, as T x (bsx_actor_forward_gaussian -> bsx_step_continuous with BSX_ACT_F32X4). */
+int bsx_rollout_continuous_gaussian(void* state, int64_t E, int n, int T, const float* weights, int precision, int scripted_team,
+                                    uint64_t scripted_seed, float* obs, float* scores, float* rew,
+                                    uint8_t* done, uint8_t* env_done, uint8_t* winner, uint8_t* env_done_t, const BsxRewards* cfg,
+                                    uint32_t flags, const BsxActorNoise* noise, const BsxGaussianHead* head, uint64_t actor_seed,
+                                    uint64_t seq, const uint64_t* seq_base, uint64_t seed, int64_t env_offset, void* stream);
 
 /* ---- the reference's scripted opponent on device (instinct/agent.py:10-62, instinct/team.py:3-15): a pure function of
  * the observation rows.  Writes ONLY the rows of `team` (0 red, 1 blue, 2 both) so a learned policy can fill the others

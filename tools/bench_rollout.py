@@ -18,21 +18,33 @@ ap.add_argument("--rollout-only", action="store_true", help="skip the env-alone 
 ap.add_argument("--chains", default="1", help="graph form: the batch as this many chains of (actor -> step) pairs over game ranges, or 'auto' "
                                            "(PolicyRollout's default); 1 = one pair per tick over the whole batch: what the kernel-stats and traffic tools profile")
 ap.add_argument("--scripted-blue", action="store_true", help="blue is the scripted opponent (instinct.Team), red the actor: main.py:119-122")
+ap.add_argument("--continuous", action="store_true", help="continuous actions: a 3-output actor (bsx_rollout_continuous in one launch)")
+ap.add_argument("--sample", default="none", choices=("none", "categorical", "gaussian"),
+                help="policy-gradient head: categorical (discrete, temperature 1) or gaussian (continuous, log_std = -0.5); no exploration noise")
+ap.add_argument("--value", action="store_true", help="add a value head (a StackedActor with one output per agent)")
 args = ap.parse_args()
 E, n, T = args.envs, args.n_agents, args.T
 A, D = 2 * n, 3 * n + 2
-env = bsx.parallel_env(n_agents=n, n_envs=E, auto_reset=True, seed=1234)
+env = bsx.parallel_env(n_agents=n, n_envs=E, auto_reset=True, seed=1234, continuous_actions=args.continuous)
 env.reset()
 torch.manual_seed(0)
-actor = StackedActor(A, D, 4, device="cuda")
+actor = StackedActor(A, D, 3 if args.continuous else 4, device="cuda")
 with torch.no_grad():
     actor.w3.mul_(100.0)
 opp = None
 if args.scripted_blue:
     from deep_rl_battlespace_amd import instinct
     opp = instinct.Team(env.possible_blue, env.possible_red, env)
+heads = {}
+if args.sample != "none":
+    heads = dict(sample=args.sample)
+    args.noise = 0.0
+    if args.sample == "gaussian":
+        heads["log_std"] = torch.full((A, 3), -0.5, device="cuda")
+if args.value:
+    heads["value_actor"] = StackedActor(A, D, 1, device="cuda")
 ro = PolicyRollout(env, actor, T, noise_std=args.noise, fused=not args.torch_actor, one_launch=args.one_launch, precision=args.precision,
-                   opponent=opp, chains=1 if args.one_launch or args.torch_actor or opp is not None else (args.chains if args.chains == "auto" else int(args.chains)))
+                   opponent=opp, **heads, chains=1 if args.one_launch or args.torch_actor or opp is not None else (args.chains if args.chains == "auto" else int(args.chains)))
 ro.start(); ro.capture()
 
 
@@ -48,7 +60,9 @@ def timed(fn, reps):
 
 t_roll = timed(ro.run, args.reps) / T
 if args.rollout_only:
-    print(json.dumps({"rollout_us_per_tick": round(t_roll * 1e6, 2), "rollout_agent_steps_per_s": round(E * A / t_roll, 1)}))
+    print(json.dumps({"rollout_us_per_tick": round(t_roll * 1e6, 2), "rollout_agent_steps_per_s": round(E * A / t_roll, 1),
+                      "games": E, "n": n, "T": T, "one_launch": args.one_launch, "continuous": args.continuous, "sample": args.sample,
+                      "value": args.value, "precision": args.precision}))
     sys.exit(0)
 # env alone (same score-vector input path), actor alone
 g_env, _ = env.capture_steps(ro.scores)
