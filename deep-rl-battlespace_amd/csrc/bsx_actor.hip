@@ -18,7 +18,7 @@
 //   * LayerNorm needs a row's 64 neurons: 32 registers of the lane plus the partner lane l^32 -> one xor-32 shuffle.
 //   * the 64 -> 4 head is 128 VALU FMAs per lane on the accumulator registers plus the same xor-32 add.
 // A workgroup = 4 waves x 64 rows of ONE agent (blockIdx.y); the small per-neuron vectors and the head weights are
-// staged once in LDS.  Checked against a torch fp32 reference (2e-5), not bit-exact with it; bit-exact with the fused
+// staged once in LDS.  Checked against a float64 reference at a small multiple of float32's own error (tests/test_hip_actor_float64.py), not bit-exact with torch; bit-exact with the fused
 // rollout kernel, which runs the same per-tile arithmetic (bsx_actor_core.h): both files are built with -ffp-contract=off
 // (so that library code such as tanhf compiles the same in both) and the core functions pin contraction themselves.
 

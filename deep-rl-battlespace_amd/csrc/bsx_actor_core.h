@@ -200,13 +200,18 @@ __device__ inline float4 finish_row(float4 r4, const float4 b3, const NZ& nz, ui
 //
 // PREC = BSX_ACTOR_BF16X3 (1): the 64 x 64 layer on the bf16 matrix path with both operands split in two bf16 terms, x = xh + xl,
 // w = wh + wl, and three products wh*xh + wh*xl + wl*xh accumulated in f32 (the dropped wl*xl and the split residue are ~2^-16
-// relative: about 1e-5 on a score, against 4e-3 for plain bf16).  v_mfma_f32_32x32x16_bf16 retires 16x the multiply-adds per cycle of
+// relative on the layer: about 20x what float32's own rounding loses on a head sum, against ~5000x for plain bf16 -- the absolute
+// figure moves with the weights, see below).  v_mfma_f32_32x32x16_bf16 retires 16x the multiply-adds per cycle of
 // the f32 MFMA -- whose rate equals packed-f32 VALU and which does not overlap with vector instructions -- so the layer costs 24
 // matrix instructions of 32 cycles instead of 64 of 64.
 // PREC = BSX_ACTOR_BF16X6 (2): THREE terms per operand (8 + 8 + 8 significant bits = float32's 24) and the six products of order up to
 // 2^-16 -- wh*xh, wh*xm, wm*xh, wh*xl, wm*xm, wl*xh, added smallest first; what is dropped is below 2^-24 relative, the size of a
 // float32 rounding -- 48 matrix instructions of 32 cycles: float32-class accuracy (not the fmaf chain's bits) at 2.7x the f32 MFMA rate.
 // Layer 1 (K = 6) and everything else stay f32 in every mode.
+// Measured against a float64 reference, |error| of a head sum before tanh, max / mean (tests/test_hip_actor_float64.py,
+// profiles/actor_float64.json): freshly initialised weights (|head sum| < 2.5): f32 and bf16x6 6e-7 / 7e-8, bf16x3 1.6e-5 / 1.6e-6;
+// the reference's shipped 2v2 checkpoints (|W2| up to 10.9, LayerNorm gains up to 5, head sums up to 75): f32 and bf16x6 7e-5 / 3e-6,
+// bf16x3 1.1e-3 / 6e-5 (up to 3e-4 on a tanh score).  Each mode stays within 2x (mean) / 4x (max) of what its arithmetic must lose.
 // ROLL: the 64 x 64 layer's operands as a ROLLING window instead of all at once -- the first groups are requested behind layer 1's
 // loads, group g + AHEAD right before group g is multiplied (f32: a group = the eight registers of four K steps, 8 MFMAs = 512
 // cycles, AHEAD = 3; bf16: a group = one K step's terms for both output tiles, AHEAD = 2), so that at most AHEAD + 1 groups are

@@ -227,10 +227,12 @@ typedef struct BsxActorNoise {
                                  bsx_rollout_* take a value head for n = 1 only (the per-tick form for any n). */
 } BsxActorNoise;
 /* precision of the 64 x 64 layer: exact float32 (an fmaf chain, bit for bit), or both operands split in two bf16 terms and
- * three bf16 matrix products accumulated in float32 (about 1e-5 on a score; 16x the matrix rate).  All else is float32. */
+ * three bf16 matrix products accumulated in float32 (16x the matrix rate; loses about 20x float32's own rounding error on a head sum:
+ * against float64, max / mean 1.6e-5 / 1.6e-6 with freshly initialised weights, 1.1e-3 / 6e-5 -- up to 3e-4 on a tanh score -- with
+ * the reference's shipped 2v2 checkpoints, where exact float32 itself loses 7e-5 / 3e-6).  All else is float32. */
 #define BSX_ACTOR_F32 0
 #define BSX_ACTOR_BF16X3 1
-#define BSX_ACTOR_BF16X6 2   /* three bf16 terms per operand, six products: float32-class accuracy (~1e-7), 48 matrix instructions of 32 cycles
+#define BSX_ACTOR_BF16X6 2   /* three bf16 terms per operand, six products: float32-class accuracy (the figures of exact float32 at either weight scale), 48 matrix instructions of 32 cycles
                                instead of 64 of 64; every actor entry point, every team size */
 int bsx_actor_blob_floats(int obs_len, int* floats_per_agent);
 int bsx_actor_forward(const float* weights, const float* obs, float* scores, int64_t E, int n, int precision,

@@ -1,0 +1,289 @@
+"""The actor kernels (bsx_actor_forward, its value and Gaussian heads, the fused one-launch rollouts) against a float64 reference of the
+same network, at fresh-weight AND trained-weight scale (tests/actor_ref_util.py; its conditions are pinned in
+tests/test_actor_reference_cpu.py).
+
+What is compared is the head sum BEFORE tanh -- read with no kernel change by feeding one head column at a time as a value head
+(as_critics) -- so that nothing is hidden by saturation, and the bound is a small multiple of what the arithmetic of the mode itself
+loses on the same inputs:
+    e_k  the kernel's |error| against float64        e_t  torch float32's (CPU)        e_m  the split model's (2 terms bf16x3, 3 terms bf16x6)
+    f32:          mean(e_k) <= 2 mean(e_t)                 max(e_k) <= 4 max(e_t)
+    split modes:  mean(e_k) <= 2 (mean(e_m) + mean(e_t))   max(e_k) <= 4 (max(e_m) + max(e_t))
+(actor_ref_util.bounds says where 2 and 4 come from.)  Scores: |score - tanh(y64)| <= sech^2(y64) * B + 4 * 2^-24 with B the max bound.
+Every test prints what it measured before it asserts (-s shows the table; tools/micro/actor_precision.py writes it to a file)."""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import actor_ref_util as au
+
+pytestmark = pytest.mark.gpu
+
+
+def _row(tag, mode, e_k, e_t, e_m, bmax, bmean):
+    print(f"{tag:34s} {mode:6s} e_k {e_k.max():.2e} / {e_k.mean():.2e}   e_t {e_t.max():.2e} / {e_t.mean():.2e}   "
+          f"e_m {e_m.max():.2e} / {e_m.mean():.2e}   bound {bmax:.2e} / {bmean:.2e}   (max / mean)")
+
+
+def _model_err(mode, e_t, e_m2, e_m3):
+    return np.zeros(1) if mode == "f32" else (e_m2 if au.TERMS[mode] == 2 else e_m3)
+
+
+def _check_sums(tag, mode, sums, y, e_t, e_m2, e_m3):
+    """The head-sum conditions on every value of `sums`; returns the max bound B."""
+    assert sums.shape == y.shape and np.isfinite(sums).all()
+    e_k = np.abs(sums - y)
+    bmax, bmean = au.bounds(mode, e_t, e_m2, e_m3)
+    _row(tag, mode, e_k, e_t, _model_err(mode, e_t, e_m2, e_m3), bmax, bmean)
+    assert e_k.mean() <= bmean, (tag, mode, "mean", e_k.mean(), bmean)
+    assert e_k.max() <= bmax, (tag, mode, "max", e_k.max(), bmax, np.unravel_index(e_k.argmax(), e_k.shape))
+    return bmax
+
+
+def _check_scores(tag, mode, scores, y, B):
+    assert scores.shape == y.shape
+    over = np.abs(scores - np.tanh(y)) - au.score_budget(y, B)
+    body = np.abs(y) < 1
+    print(f"{tag:34s} {mode:6s} scores: max |score - tanh(y64)| {np.abs(scores - np.tanh(y)).max():.2e} "
+          f"({np.abs(scores - np.tanh(y))[body].max() if body.any() else 0:.2e} on the {int(body.sum())} outputs with |y64| < 1), "
+          f"closest to its budget {over.max():+.2e}")
+    assert over.max() <= 0, (tag, mode, over.max(), np.unravel_index(over.argmax(), over.shape))
+
+
+# ---------------------------------------------------------------------------------------------------- the dense classes
+@functools.lru_cache(maxsize=None)
+def _play_rows():
+    """Observation rows the shipped checkpoints meet in actual play: a few replays of a 2v2 rollout, every tick's rows."""
+    import deep_rl_battlespace_amd as bsx
+    from deep_rl_battlespace_amd.rollout import PolicyRollout
+    actor, _ = au.shipped(2)
+    env = bsx.parallel_env(n_agents=2, n_envs=256, seed=5, auto_reset=True, device="cuda")
+    env.reset()
+    ro = PolicyRollout(env, actor.to("cuda"), 16, noise_std=0.1, seed=1)
+    ro.start()
+    rows = []
+    for _ in range(4):
+        ro.run()
+        torch.cuda.synchronize()
+        rows.append(ro.obs[1:].reshape(-1, 4, 8).cpu())
+    rows = torch.cat(rows)
+    return rows[torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(3))].contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def _dense(cls, n):
+    if cls != "shipped":
+        actor, obs = au.CLASSES[cls](n)
+        return (actor, obs) + au.reference_errors(cls, n)
+    actor, obs = au.shipped(n, play_rows=_play_rows())
+    ref = au.errors_of(actor, obs)
+    assert int((np.abs(ref[0]) < 1).sum()) >= 1000               # (the CPU test's condition, on the rows with the played ones in)
+    return (actor, obs) + ref
+
+
+@pytest.mark.parametrize("mode", au.MODES)
+@pytest.mark.parametrize("cls,n", au.COMBOS)
+def test_head_sums_and_scores_against_float64(cls, n, mode):
+    """All E * A * 4 head sums (E * A * 3 for a continuous actor: n = 3, 6) of the stand-alone kernel, nothing masked; then the scores;
+    then `one way of reading a head sum`: the score is tanh of the value read through as_critics -- in f32 mode that value comes from
+    tile_forward<F32> and the score from the stand-alone kernel's inline layer code, two texts of one arithmetic that nothing else
+    compares -- within 2 float32 spacings (tanhf against a correctly rounded tanh)."""
+    actor, obs, y, e_t, e_m2, e_m3 = _dense(cls, n)
+    scores, sums = au.kernel_outputs(actor, obs, n, mode)
+    tag = f"{cls} n={n} E={obs.shape[0]}"
+    B = _check_sums(tag, mode, sums, y, e_t, e_m2, e_m3)
+    _check_scores(tag, mode, scores, y, B)
+    ulps = au.ulps32(scores, np.tanh(sums))
+    print(f"{tag:34s} {mode:6s} score against tanh(its own head sum): max {ulps.max():.2f} float32 spacings")
+    assert ulps.max() <= 2.0, (tag, mode, ulps.max())
+
+
+# ---------------------------------------------------------------------------------------------------- localisation
+@pytest.mark.parametrize("mode", au.MODES)
+@pytest.mark.parametrize("layer", [1, 2])
+def test_each_hidden_neuron_alone_against_float64(layer, mode):
+    """64 one-neuron networks per layer (actor_ref_util.localisation_case; 8 launches of 8 agents at 4v4): the output depends on the input
+    through ONE accumulator register of ONE lane half, so a swapped nid() index, a dropped term of the rolling window or a wrong
+    wb[s][mo][t] is an O(1) error in the case of that register -- and the failure names it -- where the dense cases dilute it by 64.
+    Each case is held to the bounds of the mode under test on its own rows."""
+    n, bad, worst = 4, [], (0.0, None)
+    for launch in range(8):
+        actor, obs, neurons, active = au.localisation_case(layer, launch, n=n)
+        assert min(active) >= 0.25
+        y, e_t, e_m2, e_m3 = au.errors_of(actor, obs)
+        scores, sums = au.kernel_outputs(actor, obs, n, mode)
+        for a, j in enumerate(neurons):
+            e_k = np.abs(sums[:, a] - y[:, a])
+            bmax, bmean = au.bounds(mode, e_t[:, a], e_m2[:, a], e_m3[:, a])
+            _row(f"layer {layer} neuron {j:2d} (m={j >> 5} v={(j & 3) + 4 * ((j & 31) >> 3)} hh={(j >> 2) & 1})", mode, e_k, e_t[:, a],
+                 _model_err(mode, e_t[:, a], e_m2[:, a], e_m3[:, a]), bmax, bmean)
+            if not (e_k.max() <= bmax and e_k.mean() <= bmean):
+                bad.append((j, float(e_k.max()), float(bmax), float(e_k.mean()), float(bmean)))
+            worst = max(worst, (float(e_k.max() / bmax), j))
+            over = np.abs(scores[:, a] - np.tanh(y[:, a])) - au.score_budget(y[:, a], bmax)
+            if over.max() > 0:
+                bad.append((j, "score", float(over.max())))
+    print(f"layer {layer} {mode}: largest max(e_k) / bound = {worst[0]:.3f} at neuron {worst[1]}")
+    assert not bad, f"layer {layer} {mode}: neurons (register of tile m, lane half hh) off their bounds: {bad}"
+
+
+@pytest.mark.parametrize("mode", au.MODES)
+@pytest.mark.parametrize("layer", [1, 2])
+def test_each_hidden_neuron_alone_through_the_one_launch_rollout(layer, mode):
+    """The same 64 + 64 one-neuron networks through the fused 4v4 rollout kernel, whose 64 x 64 layer reads its weights through the
+    ROLLING window (tile_forward<.., ROLL = true>): a window group fetched from the wrong place is an O(1) error in the cases of that
+    group's neurons.  The rollout's first tick reads the rows handed to it (obs[T] of the previous run, here the case's own rows); what
+    is visible is the tanh score, held to the score budget of the case -- the head sums of these networks stay below 2 (tanh's slope
+    above 0.07), so tanh hides nothing."""
+    import deep_rl_battlespace_amd as bsx
+    from deep_rl_battlespace_amd.rollout import PolicyRollout
+    n, bad, worst = 4, [], (-1.0, None)
+    for launch in range(8):
+        actor, obs, neurons, active = au.localisation_case(layer, launch, n=n)
+        assert min(active) >= 0.25
+        y, e_t, e_m2, e_m3 = au.errors_of(actor, obs)
+        assert np.abs(y).max() < 2                              # (a condition of the cases, checked on the CPU as well)
+        env = bsx.parallel_env(n_agents=n, n_envs=obs.shape[0], seed=3, auto_reset=True, device="cuda")
+        env.reset()
+        ro = PolicyRollout(env, actor.to("cuda"), 2, seed=2, one_launch=True, precision=mode)
+        assert ro.one_launch
+        ro.start()
+        ro.obs[ro.T].copy_(obs.to("cuda"))
+        ro.run()
+        torch.cuda.synchronize()
+        assert torch.equal(ro.obs[0].cpu(), obs)
+        scores = ro.scores[0].double().cpu().numpy()
+        for a, j in enumerate(neurons):
+            bmax, _ = au.bounds(mode, e_t[:, a], e_m2[:, a], e_m3[:, a])
+            err = np.abs(scores[:, a] - np.tanh(y[:, a]))
+            over = err - au.score_budget(y[:, a], bmax)
+            worst = max(worst, (float((err / au.score_budget(y[:, a], bmax)).max()), j))
+            if over.max() > 0:
+                bad.append((j, float(err.max()), float(bmax)))
+    print(f"one launch 4v4, layer {layer} {mode}: largest share of a score budget {worst[0]:.3f} at neuron {worst[1]}")
+    assert not bad, f"layer {layer} {mode}: neurons (max score error, head-sum bound) off their budget: {bad}"
+
+
+# ---------------------------------------------------------------------------------------------------- the fused rollout forms
+def _rollout(n, mode, one_launch, value, E, T=8):
+    import deep_rl_battlespace_amd as bsx
+    from deep_rl_battlespace_amd.rollout import PolicyRollout
+    actor, _ = au.shipped(2) if n == 2 else au.trained_like(n, outputs=4)
+    critic = None
+    if value:
+        critic, _ = au.trained_like(n, seed=5, outputs=1)
+    env = bsx.parallel_env(n_agents=n, n_envs=E, seed=11 + n, auto_reset=True, device="cuda")
+    env.reset()
+    ro = PolicyRollout(env, actor.to("cuda"), T, seed=2, one_launch=one_launch, precision=mode,
+                       value_actor=critic.to("cuda") if value else None, chains=1)
+    ro.start()
+    if not one_launch:
+        ro.capture()
+    for _ in range(2):
+        ro.run()
+    torch.cuda.synchronize()
+    return actor, critic, ro
+
+
+def _check_rollout(tag, mode, actor, critic, ro, ticks):
+    for t in ticks:
+        obs = ro.obs[t].cpu()
+        y, e_t, e_m2, e_m3 = au.errors_of(actor, obs)
+        B, _ = au.bounds(mode, e_t, e_m2, e_m3)
+        e_m = _model_err(mode, e_t, e_m2, e_m3)
+        print(f"{tag} t={t} {mode}: e_t {e_t.max():.2e} / {e_t.mean():.2e}, e_m {e_m.max():.2e} / {e_m.mean():.2e}, B {B:.2e}")
+        _check_scores(f"{tag} t={t}", mode, ro.scores[t].double().cpu().numpy(), y, B)
+        if critic is not None:
+            ref = au.errors_of(critic, obs)
+            _check_sums(f"{tag} t={t} value", mode, ro.value[t].double().cpu().numpy()[..., None], *ref)
+
+
+@pytest.mark.parametrize("mode", au.MODES)
+@pytest.mark.parametrize("n", [1, 2, 3, 4])
+def test_one_launch_rollout_scores_against_float64_at_trained_scale(n, mode):
+    """PolicyRollout(one_launch=True): the fused kernels' actor (tile_forward<.., ROLL = true> at 2v2 ... 4v4, the rolling weight window)
+    on the rows the games themselves produce, shipped checkpoints at 2v2 and trained-like weights elsewhere: scores[t] against float64 on
+    obs[t] at the score budget, tick 0 and a later one; at 1v1 the value head's raw sums at the head-sum bounds as well."""
+    actor, critic, ro = _rollout(n, mode, True, n == 1, E=997)
+    assert ro.one_launch
+    _check_rollout(f"one launch {n}v{n}", mode, actor, critic, ro, (0, 5))
+
+
+@pytest.mark.parametrize("mode", au.MODES)
+def test_graph_rollout_with_a_value_head_against_float64(mode):
+    actor, critic, ro = _rollout(2, mode, False, True, E=997)
+    assert ro.graph is not None
+    _check_rollout("graph 2v2", mode, actor, critic, ro, (0, 5))
+
+
+# ---------------------------------------------------------------------------------------------------- the Gaussian head
+@pytest.mark.parametrize("mode", au.MODES)
+@pytest.mark.parametrize("n", [1, 3])
+def test_gaussian_head_against_float64_at_trained_scale(n, mode):
+    """Injected normals, trained-like weights with three outputs, log_std = (-5, 0, 1) on the three columns.
+    Action:  |a - (tanh(y64) + sigma z)| <= score budget + 2^-23 |a|                  (sigma = exp(log_std) in float64)
+    logp:    |logp - log N(a; tanh(y64), sigma)| <= sum_k score budget_k / sigma_k * |z'_k| + 8 float32 spacings of the largest term of
+             the sum (the terms: z'^2 / 2 and log_std per column, 3/2 log 2 pi), z' = (a - tanh(y64)) / sigma from the RECORDED action:
+             an error of mu is divided by sigma -- 150 times at sigma = e^-5 -- and enters -z'^2 / 2 with slope |z'|."""
+    from deep_rl_battlespace_amd.rollout import FusedActor
+    actor, obs = au.trained_like(n, outputs=3)
+    y, e_t, e_m2, e_m3 = au.errors_of(actor, obs)
+    B, _ = au.bounds(mode, e_t, e_m2, e_m3)
+    E, A = obs.shape[:2]
+    z = torch.randn((E, A, 4), generator=torch.Generator().manual_seed(n))
+    ls = torch.tensor([-5.0, 0.0, 1.0]).repeat(A, 1).contiguous()
+    scores = torch.full((E, A, 4), 7.0, device="cuda")
+    logp = torch.full((E, A), 7.0, device="cuda")
+    FusedActor(actor.to("cuda"), n, precision=mode).forward_into(obs.to("cuda"), scores, seq=3, z=z.to("cuda"),
+                                                                gaussian=dict(log_std=ls.to("cuda"), logp=logp))
+    torch.cuda.synchronize()
+    a = scores.double().cpu().numpy()
+    assert (a[..., 3] == 0).all()
+    a, z64, ls64, mu = a[..., :3], z[..., :3].double().numpy(), ls.double().numpy(), np.tanh(y)
+    sigma = np.exp(ls64)
+    budget = au.score_budget(y, B)
+    over_a = np.abs(a - (mu + sigma * z64)) - (budget + 2.0 ** -23 * np.abs(a))
+    zr = (a - mu) / sigma
+    terms = np.concatenate([0.5 * zr * zr, np.abs(ls64) + 0 * zr, np.full(zr.shape[:-1] + (1,), 1.5 * math.log(2 * math.pi))], -1)
+    want = (-0.5 * zr * zr - ls64).sum(-1) - 1.5 * math.log(2 * math.pi)
+    lp_budget = (budget / sigma * np.abs(zr)).sum(-1) + 8 * np.spacing(terms.max(-1).astype(np.float32)).astype(np.float64)
+    err_lp = np.abs(logp.double().cpu().numpy() - want)
+    print(f"gaussian n={n} {mode}: action error max {np.abs(a - (mu + sigma * z64)).max():.2e} (closest to its budget {over_a.max():+.2e}), "
+          f"logp error max {err_lp.max():.2e} / mean {err_lp.mean():.2e}, largest share of its budget {(err_lp / lp_budget).max():.3f}")
+    assert over_a.max() <= 0, (over_a.max(), np.unravel_index(over_a.argmax(), over_a.shape))
+    assert (err_lp <= lp_budget).all(), float((err_lp / lp_budget).max())
+
+
+# ---------------------------------------------------------------------------------------------------- non-finite rows
+@pytest.mark.parametrize("mode", au.MODES)
+def test_non_finite_rows_do_not_touch_the_other_games(mode):
+    """One game with a NaN observation and one with an inf among finite ones (each in one plane's row only): every other row -- the
+    poisoned games' other planes included -- is bit-equal to a run without them.  What the poisoned rows return is printed, not
+    asserted: INTEGRATION.md records it (the kernels take no position on non-finite input)."""
+    from deep_rl_battlespace_amd.rollout import FusedActor
+    n = 2
+    actor, obs = au.shipped(n)
+    critic, _ = au.trained_like(n, seed=5, outputs=1)
+    fa = FusedActor(actor.to("cuda"), n, precision=mode)
+    vw = critic.to("cuda").pack()
+
+    def run(o):
+        s = torch.full((o.shape[0], 2 * n, 4), 7.0, device="cuda")
+        v = torch.full((o.shape[0], 2 * n), 7.0, device="cuda")
+        fa.forward_into(o.to("cuda").contiguous(), s, seq=1, value=dict(weights=vw, out=v))
+        torch.cuda.synchronize()
+        return s.cpu(), v.cpu()
+    clean_s, clean_v = run(obs)
+    bad = obs.clone()
+    e_nan, e_inf = 40, 4000                                     # (row 40 of the first wave: tile 1, lower lane half; a game of a late block)
+    bad[e_nan, 1, 3] = float("nan")
+    bad[e_inf, 2, 0] = float("inf")
+    s, v = run(bad)
+    keep = torch.ones(s.shape[:2], dtype=torch.bool)
+    keep[e_nan, 1] = False; keep[e_inf, 2] = False
+    print(f"{mode}: NaN observation -> scores {s[e_nan, 1].tolist()} value {float(v[e_nan, 1])}; "
+          f"inf observation -> scores {s[e_inf, 2].tolist()} value {float(v[e_inf, 2])}")
+    assert torch.equal(s[keep].view(torch.int32), clean_s[keep].view(torch.int32))
+    assert torch.equal(v[keep].view(torch.int32), clean_v[keep].view(torch.int32))

@@ -53,7 +53,9 @@ def test_head_with_injected_normals_equals_torch(n, precision):
         want = mu + torch.exp(ls) * z[..., :3]
         want_lp, _ = gaussian_log_prob(actor, ls, obs, scores)
         dist_lp = torch.distributions.Normal(mu, torch.exp(ls)).log_prob(scores[..., :3]).sum(-1)
-    tol = 1.0 if precision != "bf16x3" else 40.0      # bf16x3: ~1e-5 on a tanh score (test_hip_rollout_oracle.py scales the same way)
+    # bf16x3: ~1e-5 on a tanh score AT THIS (fresh) WEIGHT SCALE (test_hip_rollout_oracle.py scales the same way); the budgets that follow
+    # from a float64 reference, at trained-weight scale too, are in tests/test_hip_actor_float64.py
+    tol = 1.0 if precision != "bf16x3" else 40.0
     torch.testing.assert_close(scores[..., :3], want, rtol=0, atol=2e-5 * tol)
     assert bool((scores[..., 3] == 0).all())
     assert float(scores[..., :3].abs().max()) > 1.0                                # unclipped

@@ -60,119 +60,29 @@ def test_replay_buffer_ring_and_sample_layout_follow_the_reference():
     assert sorted(big.rew_mem[:, 0].tolist()) == [7., 8., 9., 10., 11.] and big.mem_cntr == 12
 
 
-def _mfma_32x32x2(avec, bvec, acc):
-    """v_mfma_f32_32x32x2_f32 on host arrays indexed by lane: A[i = l&31][k = l>>5], B[k = l>>5][j = l&31],
-    D[i = (v&3) + 8(v>>2) + 4(l>>5)][j = l&31] in register v of lane l (cdna_hip_programming.md section 3)."""
-    lanes = np.arange(64)
-    Am = np.zeros((32, 2)); Bm = np.zeros((2, 32))
-    Am[lanes & 31, lanes >> 5] = avec
-    Bm[lanes >> 5, lanes & 31] = bvec
-    Dm = Am @ Bm
-    for v in range(16):
-        acc[v] += Dm[(v & 3) + 8 * (v >> 2) + 4 * (lanes >> 5), lanes & 31]
-
-
-def _mfma_32x32x16(a8, b8, acc):
-    """v_mfma_f32_32x32x16_bf16 on host arrays [lane, 8]: A[i = l&31][k = 8(l>>5) + e], B[k = 8(l>>5) + e][j = l&31], same D map."""
-    lanes = np.arange(64)
-    Am = np.zeros((32, 16)); Bm = np.zeros((16, 32))
-    for e in range(8):
-        Am[lanes & 31, 8 * (lanes >> 5) + e] = a8[:, e]
-        Bm[8 * (lanes >> 5) + e, lanes & 31] = b8[:, e]
-    Dm = Am @ Bm
-    for v in range(16):
-        acc[v] += Dm[(v & 3) + 8 * (v >> 2) + 4 * (lanes >> 5), lanes & 31]
-
-
-def _bf16(x):
-    """round-to-nearest-even float32 -> bfloat16, returned as float64 values"""
-    return torch.as_tensor(np.asarray(x, np.float32)).to(torch.bfloat16).float().numpy().astype(np.float64)
-
-
 @pytest.mark.parametrize("n", [1, 2])
 def test_packed_actor_blob_drives_the_mfma_fragment_arithmetic(n):
     """StackedActor.pack() + the kernel's index arithmetic (csrc/bsx_actor.hip), emulated lane by lane on the host with
-    the documented MFMA fragment maps, reproduce the plain forward: pins the blob layout of include/battlespace_hip.h."""
+    the documented MFMA fragment maps (actor_ref_util.mfma_emulation), reproduce the plain forward: pins the blob layout of
+    include/battlespace_hip.h."""
+    from actor_ref_util import mfma_emulation
     from deep_rl_battlespace_amd.rollout import StackedActor
     torch.manual_seed(n)
     A, D = 2 * n, 3 * n + 2
     act = StackedActor(A, D, 4)
     with torch.no_grad():
         act.g1.uniform_(0.5, 1.5); act.h1.uniform_(-.3, .3); act.g2.uniform_(0.5, 1.5); act.h2.uniform_(-.3, .3); act.w3.mul_(50)
-    blob = act.pack().numpy()
-    Dp = (D + 1) & ~1
-    ow2 = 64 * Dp; osm = ow2 + 4096; ow3 = osm + 384; ob3 = ow3 + 256
-    assert blob.shape == (A, ob3 + 4 + 6144)
     obs = torch.rand(64, A, D) * 2 - 1
     want = act(obs).detach().numpy()
-    lanes = np.arange(64); hh = lanes >> 5
-    for a in range(A):
-        W = blob[a]
-        sm = W[osm:osm + 384].reshape(6, 2, 2, 16)                    # [vector][hh][mo][v]
-        x = obs[:, a, :].numpy()
-        acc1 = np.zeros((2, 2, 16, 64))
-        for mo in range(2):
-            for nt in range(2):
-                acc1[mo, nt] = sm[0][hh, mo].T
-        for s in range(Dp // 2):
-            k = 2 * s + hh
-            for mo in range(2):
-                avec = W[(mo * (Dp // 2) + s) * 64:(mo * (Dp // 2) + s) * 64 + 64]
-                for nt in range(2):
-                    bvec = np.where(k < D, x[32 * nt + (lanes & 31), np.minimum(k, D - 1)], 0.0)
-                    _mfma_32x32x2(avec, bvec, acc1[mo, nt])
-
-        def ln(acc, gi, bi):
-            for nt in range(2):
-                for c in range(32):
-                    cols = [c, c + 32]
-                    vals = acc[:, nt][:, :, cols].reshape(-1)
-                    mean = vals.mean(); rstd = 1 / np.sqrt(((vals - mean) ** 2).mean() + 1e-5)
-                    for h2 in range(2):
-                        for mo in range(2):
-                            acc[mo, nt, :, c + 32 * h2] = np.maximum((acc[mo, nt, :, c + 32 * h2] - mean) * rstd * sm[gi, h2, mo] + sm[bi, h2, mo], 0)
-        ln(acc1, 1, 2)
-        acc2 = np.zeros((2, 2, 16, 64))
-        for mo in range(2):
-            for nt in range(2):
-                acc2[mo, nt] = sm[3][hh, mo].T
-        w2 = W[ow2:ow2 + 4096].reshape(2, 2, 4, 64, 4)
-        for mt in range(2):
-            for v in range(16):
-                for mo in range(2):
-                    for nt in range(2):
-                        _mfma_32x32x2(w2[mo, mt, v >> 2, :, v & 3], acc1[mt, nt, v], acc2[mo, nt])
-        # the same layer from the bfloat16 section: W2B[mo][s][term 3][lane][i]; "bf16x3" = three products of the first two terms per
-        # K step, "bf16x6" = six products of all three terms (float32-class accuracy)
-        w2b = (W[ob3 + 4:ob3 + 4 + 6144].view(np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64).reshape(2, 4, 3, 64, 8)
-        w2ref = np.zeros((2, 4, 64, 8))                                                # the float32 weights the terms sum to
-        nid = lambda m, v, h2: 32 * m + (v & 3) + 8 * (v >> 2) + 4 * h2              # noqa: E731
-        acc2b = np.zeros((2, 2, 16, 64)); acc2c = np.zeros((2, 2, 16, 64))
-        for mo in range(2):
-            for nt in range(2):
-                acc2b[mo, nt] = sm[3][hh, mo].T; acc2c[mo, nt] = sm[3][hh, mo].T
-        for s4 in range(4):
-            for nt in range(2):
-                x = np.stack([acc1[s4 >> 1, nt, 8 * (s4 & 1) + i] for i in range(8)], axis=1)          # [lane, 8]
-                x = x.astype(np.float32).astype(np.float64)                              # the kernel splits float32 accumulator values
-                xh = _bf16(x); xm = _bf16(x - xh); xl = _bf16(x - xh - xm)
-                for mo in range(2):
-                    wh, wm, wl = w2b[mo, s4, 0], w2b[mo, s4, 1], w2b[mo, s4, 2]
-                    _mfma_32x32x16(wm, xh, acc2b[mo, nt]); _mfma_32x32x16(wh, xm, acc2b[mo, nt]); _mfma_32x32x16(wh, xh, acc2b[mo, nt])
-                    for wa, xa in ((wl, xh), (wm, xm), (wh, xl), (wm, xh), (wh, xm), (wh, xh)):
-                        _mfma_32x32x16(wa, xa, acc2c[mo, nt])
+    for a, em in enumerate(mfma_emulation(act, obs)):
+        acc2, acc2b, acc2c = em["acc2"], em["acc2b"], em["acc2c"]
         assert np.abs(acc2c - acc2).max() < 3e-6 * max(1.0, np.abs(acc2).max())   # six products: float32-class (the emulation's acc1 is float64)
         err_split = np.abs(acc2b - acc2).max()
         assert err_split < 2e-4 * max(1.0, np.abs(acc2).max()), err_split         # ~2^-16 relative; plain bf16 would be ~4e-3
-        ln(acc2, 4, 5); ln(acc2b, 4, 5); ln(acc2c, 4, 5)
-        w3 = W[ow3:ow3 + 256].reshape(2, 2, 16, 4); b3 = W[ob3:ob3 + 4]
-        for acc, tol in ((acc2, 2e-5), (acc2b, 1e-4), (acc2c, 2e-5)):
-            out = np.zeros((64, 4))
-            for nt in range(2):
-                for c in range(32):
-                    o = sum(acc[mt, nt, v, c + 32 * h2] * w3[h2, mt, v] for h2 in range(2) for mt in range(2) for v in range(16))
-                    out[32 * nt + c] = np.tanh(o + b3)
-            np.testing.assert_allclose(out, want[:, a, :], atol=tol)
+        # absolute bars on the tanh output at fresh-weight scale; the float64 reference and the bars that follow from it are in
+        # tests/test_actor_reference_cpu.py
+        for name, tol in (("f32", 2e-5), ("bf16x3", 1e-4), ("bf16x6", 2e-5)):
+            np.testing.assert_allclose(np.tanh(em["sums"][name]), want[:, a, :], atol=tol)
 
 
 def test_replay_ring_reproduces_the_reference_buffer_on_cpu():
