@@ -113,6 +113,9 @@ SIGNATURES = {
                                   c_void_p, c_int64, c_void_p]),
     "bsx_actor_forward_gaussian": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(BsxActorNoise),
                                            ctypes.POINTER(BsxGaussianHead), c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
+    "bsx_actor_grad_floats": (c_int, [c_int, ctypes.POINTER(c_int)]),
+    "bsx_actor_grad_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_actor_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_workspace_bytes": (c_int, [c_int64, ctypes.POINTER(c_size_t)]),
     "bsx_replay_append": (c_int, [ctypes.POINTER(BsxReplayRing), ctypes.POINTER(BsxReplaySource), c_int64, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_sample": (c_int, [ctypes.POINTER(BsxReplayRing), c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,

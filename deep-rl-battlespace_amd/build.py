@@ -43,6 +43,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_step_two_wave.hip"), PER_CALL_FLAGS),
            (os.path.join(CSRC, "bsx_step_rollout.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_actor.hip"), ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+           # the actor's training pass (forward recomputed + backward): the actor's flags, its forward is the actor's arithmetic
+           (os.path.join(CSRC, "bsx_actor_grad.hip"), ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
            # the replay ring (append / sample): copies bits and draws integers, no floating-point arithmetic to pin
            (os.path.join(CSRC, "bsx_replay.hip"), []),
            # GAE advantages: float32 operations each rounded on their own, as tests/gae_util.py restates them

@@ -266,13 +266,18 @@ class FusedActor:
         return self.forward_into(obs.contiguous(), scores, noise_std, seq)
 
 
-def gaussian_log_prob(actor, log_std, obs, actions):
+def gaussian_log_prob(actor, log_std, obs, actions, fused=False):
     """The Gaussian policy head on the learner's side (what a PPO update takes the ratio of): (logp, entropy), each [.., E, A], of
     `actions` [.., E, A, 3 or 4] (the recorded, unclipped rows; a fourth column is ignored) under Normal(tanh(actor(obs)), exp(log_std)),
     summed over the three action columns.  actor: a StackedActor with 3 outputs; log_std: [A, 3]; obs: [.., E, A, D].  Differentiable in
-    the actor's parameters and log_std; the float32 reference of the in-kernel head (bsx_actor_forward_gaussian)."""
+    the actor's parameters and log_std; the float32 reference of the in-kernel head (bsx_actor_forward_gaussian).
+    fused=True evaluates and back-propagates mu with learner.fused_apply (one HIP kernel each way; log_std's gradient stays torch's)."""
     A, D = obs.shape[-2], obs.shape[-1]
-    mu = actor(obs.reshape(-1, A, D)).reshape(*obs.shape[:-1], 3)
+    if fused:
+        from .learner import fused_apply
+        mu = fused_apply(actor, obs)
+    else:
+        mu = actor(obs.reshape(-1, A, D)).reshape(*obs.shape[:-1], 3)
     z = (actions[..., :3] - mu) * torch.exp(-log_std)
     logp = (-0.5 * z * z - log_std).sum(-1) - 1.5 * math.log(2.0 * math.pi)
     entropy = (log_std + 0.5 * (1.0 + math.log(2.0 * math.pi))).sum(-1).expand_as(logp)
@@ -292,6 +297,7 @@ class PolicyRollout:
         ro.adv[t], ro.ret[t], ro.mask[t]  # gae=dict(gamma, lam[, normalize]) with a value_actor: GAE advantages and returns of the
                                        # rows that are the agent's own decisions (advantage.gae), computed inside the same run
         ro.logp[t]                     # sample="categorical" / "gaussian": the log-probability of the action taken
+                                       # (learner side: learner.categorical_log_prob / gaussian_log_prob; fused=True = one kernel each way)
 
     Continuous PPO (a continuous env): sample="gaussian" with log_std = a float32 [A, 3] tensor (one row per plane, kept by reference, read at
     every replay) draws a = tanh(actor(obs)) + exp(log_std) * z in-kernel; scores[t][..., :3] record the unclipped draws (the env's step

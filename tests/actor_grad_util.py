@@ -1,0 +1,145 @@
+"""What the tests of the actor's fused training pass (learner.fused_apply, csrc/bsx_actor_grad.hip) share:
+
+  CASES            (class, n, outputs, squash) on the input classes of actor_ref_util
+  reference        per case, cached: the float64 autograd gradients g64 (torch on the CPU, loss = (y * go).sum()), the float32 ones g32 of
+                   the same network (the yardstick: what float32 itself loses on these inputs), the upstream gradient go and the share of
+                   rows it leaves out
+  kink_free_go     go with the ReLU kinks left out BY CONSTRUCTION: a hidden unit whose post-LayerNorm value is within rounding of 0 flips
+                   its mask between float32 and float64 and moves a summed gradient by a whole row's contribution (~1/R of the sum, against
+                   ~1e-7 for rounding), so go = 0 on every row (e, a) where, in float64, any of the 128 post-LayerNorm pre-ReLU values has
+                   |y| < 1e-4.  The same go feeds the reference, the yardstick and the kernel
+  permutation_spread   how far the yardstick's own error moves when the rows are summed in another order
+  factors / check  the bound: per tensor, mean(e_k) <= fm mean(e_t) and max(e_k) <= fx max(e_t), with (fm, fx) = the project's (2, 4)
+                   (actor_ref_util.F32_FACTORS) except where the recorded spread of the yardstick reaches them
+                   (profiles/actor_grad_float64.json says where and why)
+
+Nothing here imports the native library."""
+import functools
+import json
+import os
+
+import numpy as np
+import torch
+
+import actor_ref_util as R
+
+PARAMS = R.PARAMS
+KINK = 1e-4
+KINK_CAP = 0.05
+PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "actor_grad_float64.json")
+
+# (class, n, outputs, squash).  Left out, seed 0: dead_half at n = 3 (one agent's constant all -1 row has a kink unit: 57.6 % of its rows would go)
+# and fresh at n = 3 (15.4 % for the same reason).  The rest stay below KINK_CAP, which test_actor_grad_cpu.py checks.
+CASES = (("fresh", 1, 4, True), ("fresh", 4, 4, True), ("shipped", 2, 4, True), ("trained_like", 1, 4, True),
+         ("trained_like", 4, 4, True), ("trained_like", 3, 3, True), ("fresh", 2, 3, True), ("flat_rows", 2, 4, True), ("wide_obs", 2, 4, True),
+         ("dead_half", 1, 4, True), ("fresh", 1, 1, False), ("trained_like", 3, 1, False))
+
+
+def case_id(case):
+    return "%s-n%d-out%d-%s" % (case[0], case[1], case[2], "tanh" if case[3] else "raw")
+
+
+def with_outputs(actor, outputs):
+    """The actor with its head cut (or kept) to `outputs` columns: the body is the class's own."""
+    if actor.n_actions == outputs:
+        return actor
+    a = R._new(actor.n_actors, actor.obs_len, outputs)
+    with torch.no_grad():
+        for k in R.BODY:
+            getattr(a, k).copy_(getattr(actor, k))
+        a.w3.copy_(actor.w3[:, :, :outputs]); a.b3.copy_(actor.b3[:, :, :outputs])
+    return a
+
+
+def pre_relu64(actor, obs):
+    """float64 [A, R, 128]: the post-LayerNorm, pre-ReLU values of both hidden layers."""
+    a = R.to_float64(actor)
+    with torch.no_grad():
+        x = obs.detach().cpu().double().transpose(0, 1)
+        y1 = a._ln(torch.baddbmm(a.b1, x, a.w1), a.g1, a.h1)
+        y2 = a._ln(torch.baddbmm(a.b2, torch.relu(y1), a.w2), a.g2, a.h2)
+    return torch.cat([y1, y2], -1)
+
+
+def kink_free_go(actor, obs, seed=0):
+    """(go float32 [R, A, outputs], share [A]): standard normals, 0 on the rows with a hidden unit within KINK of its ReLU's kink."""
+    near = (pre_relu64(actor, obs).abs() < KINK).any(-1).transpose(0, 1)           # [R, A]
+    g = torch.Generator().manual_seed(3000 + seed)
+    go = torch.randn((obs.shape[0], actor.n_actors, actor.n_actions), generator=g)
+    go[near] = 0.0
+    return go, near.double().mean(0).numpy()
+
+
+def autograd_grads(actor, obs, go, squash, dtype):
+    """{name: float64 array}: d (y * go).sum() / d parameter, torch autograd on the CPU in `dtype`."""
+    a = R.to_float64(actor) if dtype == torch.float64 else R.to_cpu32(actor)
+    y = a(obs.detach().cpu().to(dtype), squash=squash)
+    (y * go.to(dtype)).sum().backward()
+    return {k: getattr(a, k).grad.double().numpy() for k in PARAMS}
+
+
+def build_case(case, rows=None, seed=0):
+    cls, n, outputs, squash = case
+    actor, obs = R.CLASSES[cls](n, seed)
+    actor = with_outputs(actor, outputs)
+    if rows is not None:
+        obs = obs[:rows].contiguous()
+    go, share = kink_free_go(actor, obs, seed)
+    return actor, obs, go, share
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case, rows=None):
+    """(actor, obs, go, g64, g32, share) of a case, computed once and shared: treat every part as read-only."""
+    actor, obs, go, share = build_case(case, rows)
+    g64 = autograd_grads(actor, obs, go, case[3], torch.float64)
+    g32 = autograd_grads(actor, obs, go, case[3], torch.float32)
+    return actor, obs, go, g64, g32, share
+
+
+def permutation_spread(case, perms=8):
+    """{name: (max ratio, mean ratio)}: over `perms` row permutations, how far max(e_t) and mean(e_t) move from the unpermuted yardstick
+    (the larger of p / base and base / p)."""
+    actor, obs, go, g64, g32, _ = reference(case)
+    out = {k: [1.0, 1.0] for k in PARAMS}
+    for p in range(perms):
+        idx = torch.randperm(obs.shape[0], generator=torch.Generator().manual_seed(4000 + p))
+        gp = autograd_grads(actor, obs[idx].contiguous(), go[idx].contiguous(), case[3], torch.float32)
+        for k in PARAMS:
+            e0, e1 = np.abs(g32[k] - g64[k]), np.abs(gp[k] - g64[k])
+            for i, f in enumerate((np.max, np.mean)):
+                a, b = float(f(e0)), float(f(e1))
+                if a > 0 and b > 0:
+                    out[k][i] = max(out[k][i], a / b, b / a)
+    return {k: tuple(v) for k, v in out.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def factors():
+    """{name: (mean factor, max factor)} from profiles/actor_grad_float64.json."""
+    f = json.load(open(PROFILE))["factors"]
+    return {k: tuple(f[k]) for k in PARAMS}
+
+
+def ratios(got, g64, g32):
+    """{name: (mean(e_k) / mean(e_t), max(e_k) / max(e_t), max(e_k) / max|g64|)}."""
+    out = {}
+    for k in PARAMS:
+        ek, et = np.abs(np.asarray(got[k], np.float64) - g64[k]), np.abs(g32[k] - g64[k])
+        out[k] = (float(ek.mean() / et.mean()) if et.mean() > 0 else (0.0 if ek.mean() == 0 else float("inf")),
+                  float(ek.max() / et.max()) if et.max() > 0 else (0.0 if ek.max() == 0 else float("inf")),
+                  float(ek.max() / max(np.abs(g64[k]).max(), 1e-300)))
+    return out
+
+
+def check(got, g64, g32, what=""):
+    """Every tensor within its factors of the yardstick's error; prints the figures first.  Returns the ratios."""
+    r = ratios(got, g64, g32)
+    bad = []
+    for k in PARAMS:
+        fm, fx = factors()[k]
+        print(f"{what} {k}: mean ratio {r[k][0]:.3f} (<= {fm}), max ratio {r[k][1]:.3f} (<= {fx}), max error / max|g| {r[k][2]:.2e}")
+        if not (r[k][0] <= fm and r[k][1] <= fx):
+            bad.append((k, r[k]))
+    assert not bad, (what, bad)
+    return r

@@ -1,0 +1,339 @@
+"""The actor's fused training pass on the MI355X (bsx_actor_grad, learner.fused_apply): every parameter gradient against float64 autograd at
+a small multiple of what float32 autograd itself loses on the same inputs (tests/actor_grad_util.py: ReLU kinks left out by construction,
+factors from profiles/actor_grad_float64.json); the layout of the gradient row; ragged row counts between guard slabs; the same bits on
+every call and from a captured graph; a PPO loss on a continuous and a discrete rollout record, fused path against torch path; the
+learner-side log-probabilities against the rollout's recorded ones."""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import actor_grad_util as U
+import actor_ref_util as R
+from guard_util import Buffers
+
+pytestmark = pytest.mark.gpu
+
+LOGP_TOL = 1e-4                   # recorded logp against the float32 torch head: tests/test_hip_gaussian_head.py (assert_close(logp, want_lp, atol=1e-4))
+RAGGED = (1, 31, 32, 33, 63, 65, 255, 257)
+
+
+def _to(actor, device="cuda", dtype=torch.float32):
+    a = R._new(actor.n_actors, actor.obs_len, actor.n_actions, dtype=dtype, device=device)
+    with torch.no_grad():
+        for k in U.PARAMS:
+            getattr(a, k).copy_(getattr(actor, k).detach().to(device=device, dtype=dtype))
+    return a
+
+
+def _fused_grads(actor_cpu, obs_cpu, go_cpu, squash):
+    from deep_rl_battlespace_amd.learner import fused_apply
+    actor, obs, go = _to(actor_cpu), obs_cpu.to("cuda").contiguous(), go_cpu.to("cuda")
+    y = fused_apply(actor, obs, squash=squash)
+    (y * go).sum().backward()
+    torch.cuda.synchronize()
+    return actor, obs, y.detach(), {k: getattr(actor, k).grad.double().cpu().numpy() for k in U.PARAMS}
+
+
+# ---------------------------------------------------------------------------------------------------- 1. against float64
+@pytest.mark.parametrize("case", U.CASES, ids=U.case_id)
+def test_gradients_stay_within_the_float32_yardstick_of_float64_autograd(case):
+    from deep_rl_battlespace_amd.rollout import FusedActor
+    actor_cpu, obs_cpu, go, g64, g32, share = U.reference(case)
+    assert float(share.max()) <= U.KINK_CAP
+    n, na, squash = case[1], case[2], case[3]
+    actor, obs, y, got = _fused_grads(actor_cpu, obs_cpu, go, squash)
+    assert y.shape == (obs.shape[0], 2 * n, na)
+    # the forward is the rollout's own float32 kernel: FusedActor's bits
+    fa = FusedActor(actor, n)
+    scores = torch.full((*obs.shape[:2], 4), 7.0, device="cuda")
+    if squash:
+        fa.forward_into(obs, scores, seq=1)
+        assert torch.equal(y, scores[..., :na])
+        assert na == 4 or bool((scores[..., na:] == 0).all())
+    else:
+        out = torch.full(obs.shape[:2], 7.0, device="cuda")
+        fa.forward_into(obs, scores, seq=1, value=dict(weights=actor.pack(), out=out))
+        assert torch.equal(y[..., 0], out)
+    U.check(got, g64, g32, "KERNEL " + U.case_id(case))
+
+
+# ---------------------------------------------------------------------------------------------------- 2. layout
+def test_one_column_of_one_agent_reaches_only_that_agents_row_and_that_head_column():
+    n, Rr, agent, col = 4, 300, 5, 2
+    actor_cpu, obs = R.fresh(n)
+    obs = obs[:Rr].contiguous()
+    go = torch.zeros((Rr, 2 * n, 4))
+    go[:, agent, col] = torch.randn(Rr, generator=torch.Generator().manual_seed(1))
+    actor, _, _, got = _fused_grads(actor_cpu, obs, go, True)
+    for k in U.PARAMS:
+        g = got[k]
+        others = np.delete(g, agent, axis=0)
+        assert not others.any(), k                                  # exactly 0, not small
+        assert np.abs(g[agent]).max() > 0, k
+    for k in ("w3", "b3"):
+        assert not np.delete(got[k][agent], col, axis=-1).any(), k
+    g64 = U.autograd_grads(actor_cpu, obs, go, True, torch.float64)
+    for k in U.PARAMS:
+        assert np.abs(got[k] - g64[k]).max() <= 1e-5 * np.abs(g64[k]).max(), k
+
+
+# ---------------------------------------------------------------------------------------------------- 3. ragged sizes, guards
+def _raw_call(actor, obs, go4, squash=1, guarded=True):
+    """bsx_actor_grad on guarded buffers: (grad [A, G] clone, names of the buffers with a damaged guard, workspace bytes)."""
+    from deep_rl_battlespace_amd import _lib
+    from deep_rl_battlespace_amd.learner import grad_floats
+    lib = _lib.load()
+    Rr, A, D = obs.shape
+    n = A // 2
+    nb = _lib.c_size_t()
+    _lib.check(lib.bsx_actor_grad_workspace_bytes(Rr, n, _lib.ctypes.byref(nb)), "bsx_actor_grad_workspace_bytes")
+    B = Buffers(guarded)
+    o = B("obs", (Rr, A, D), torch.float32); o.copy_(obs)
+    g = B("grad_out", (Rr, A, 4), torch.float32); g.copy_(go4)
+    out = B("grad", (A, grad_floats(D)), torch.float32, init=7.0)
+    ws = B("workspace", (nb.value // 4,), torch.float32, init=7.0)
+    blob = actor.pack()
+    _lib.check(lib.bsx_actor_grad(blob.data_ptr(), o.data_ptr(), g.data_ptr(), Rr, n, squash, out.data_ptr(), ws.data_ptr(),
+                                  torch.cuda.current_stream().cuda_stream), "bsx_actor_grad")
+    torch.cuda.synchronize()
+    return out.clone(), B.stray(), nb.value
+
+
+@pytest.mark.parametrize("n", [1, 4])
+@pytest.mark.parametrize("rows", RAGGED)
+def test_ragged_row_counts_keep_their_guards_and_the_float64_bound(rows, n):
+    from deep_rl_battlespace_amd.learner import split_grad
+    case = ("fresh", n, 4, True)
+    actor_cpu, obs, go, g64, g32, _ = U.reference(case, rows)
+    assert obs.shape[0] == rows
+    actor = _to(actor_cpu)
+    grad, stray, _ = _raw_call(actor, obs.to("cuda"), go.to("cuda"))
+    assert not stray, stray
+    got = {k: g.double().cpu().numpy() for k, g in zip(U.PARAMS, split_grad(grad, 4))}
+    U.check(got, g64, g32, f"RAGGED rows={rows} n={n}")
+
+
+@pytest.mark.parametrize("n", [1, 4])
+def test_rows_appended_with_zero_gradient_change_no_bit_when_the_grid_is_the_same(n):
+    rows, more = 257, 300                                           # 9 and 10 tiles: three workgroups per agent either way
+    actor_cpu, obs_all = R.fresh(n)
+    actor = _to(actor_cpu)
+    go = torch.randn((more, 2 * n, 4), generator=torch.Generator().manual_seed(2))
+    go[rows:] = 0.0
+    a, stray_a, ws_a = _raw_call(actor, obs_all[:rows].to("cuda"), go[:rows].to("cuda"))
+    b, stray_b, ws_b = _raw_call(actor, obs_all[:more].to("cuda"), go.to("cuda"))
+    assert ws_a == ws_b                                             # the same number of partial rows: the same partition of the tiles
+    assert not stray_a and not stray_b
+    assert torch.equal(a, b)
+    assert bool((a != 7.0).all())                                   # grad is overwritten everywhere
+
+
+# ---------------------------------------------------------------------------------------------------- 4. determinism, graphs
+def test_the_same_inputs_give_the_same_bits_eagerly_and_from_a_captured_graph():
+    from deep_rl_battlespace_amd.learner import fused_apply, fused_grad, split_grad
+    from deep_rl_battlespace_amd.rollout import FusedActor
+    n, Rr = 2, 1000
+    actor_cpu, obs = R.fresh(n, outputs=3)
+    actor, obs = _to(actor_cpu), obs[:Rr].to("cuda").contiguous()
+    go = torch.randn((Rr, 2 * n, 3), device="cuda")
+
+    def step():
+        for k in U.PARAMS:
+            getattr(actor, k).grad = None
+        y = fused_apply(actor, obs)
+        (y * go).sum().backward()
+        return y.detach()
+    y1 = step().clone(); g1 = [getattr(actor, k).grad.clone() for k in U.PARAMS]
+    y2 = step().clone(); g2 = [getattr(actor, k).grad.clone() for k in U.PARAMS]
+    torch.cuda.synchronize()
+    assert torch.equal(y1, y2) and all(torch.equal(a, b) for a, b in zip(g1, g2))
+    # the same step as a captured graph: pack, forward and the backward call, enqueued on the capturing stream
+    fa = FusedActor(actor, n)
+    scores = torch.zeros((Rr, 2 * n, 4), device="cuda")
+
+    def calls():
+        fa.refresh()
+        fa.forward_into(obs, scores, seq=1)
+        return fused_grad(actor, fa.weights, obs, go, True)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        calls()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        row = calls()
+    for _ in range(2):
+        row.zero_(); scores.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(scores[..., :3], y1)
+        for k, a, b in zip(U.PARAMS, split_grad(row, 3), g1):
+            assert torch.equal(a, b), k
+    # the backward reads the blob the forward packed: parameters moved in between do not reach it
+    for k in U.PARAMS:
+        getattr(actor, k).grad = None
+    y = fused_apply(actor, obs)
+    with torch.no_grad():
+        for k in U.PARAMS:
+            getattr(actor, k).mul_(1.5)
+    (y * go).sum().backward()
+    torch.cuda.synchronize()
+    for k, b in zip(U.PARAMS, g1):
+        assert torch.equal(getattr(actor, k).grad, b), k
+
+
+def test_fused_apply_refuses_what_it_documents():
+    from deep_rl_battlespace_amd.learner import fused_apply
+    from deep_rl_battlespace_amd.rollout import StackedActor
+    A, D = 2, 5
+    obs = torch.rand((9, A, D), device="cuda")
+    actor = StackedActor(A, D, 4, device="cuda")
+    with pytest.raises(ValueError, match="float32"):
+        fused_apply(actor, obs.double())
+    with pytest.raises(ValueError, match="float32"):
+        fused_apply(StackedActor(A, D, 4, device="cuda", dtype=torch.float64), obs)
+    with pytest.raises(ValueError, match="require"):
+        fused_apply(actor, obs.clone().requires_grad_())
+    with pytest.raises(ValueError, match="64"):
+        fused_apply(StackedActor(A, D, 4, fc1_dims=32, device="cuda"), obs)
+    with pytest.raises(ValueError, match="value head"):
+        fused_apply(actor, obs, squash=False)
+    with pytest.raises(ValueError, match="CUDA"):
+        fused_apply(actor, obs.cpu())
+    with pytest.raises(ValueError):
+        fused_apply(actor, obs[:, :, :4])
+    assert fused_apply(actor, obs.reshape(3, 3, A, D)).shape == (3, 3, A, 4)
+
+
+# ---------------------------------------------------------------------------------------------------- 5. end to end: a PPO loss
+TAU, CLIP = 0.7, 0.2
+
+
+@functools.lru_cache(maxsize=None)
+def _record(kind):
+    """One small rollout with GAE: the records a PPO update reads, on the CPU (read-only), and the networks that produced them."""
+    import deep_rl_battlespace_amd as bsx
+    from deep_rl_battlespace_amd.rollout import PolicyRollout, StackedActor
+    n, E, T = 1, 96, 8
+    A, D = 2 * n, 3 * n + 2
+    cont = kind == "gaussian"
+    torch.manual_seed(11)
+    actor, critic = StackedActor(A, D, 3 if cont else 4, device="cuda"), StackedActor(A, D, 1, device="cuda")
+    with torch.no_grad():
+        actor.w3.mul_(60.0); critic.w3.mul_(100.0)
+    env = bsx.parallel_env(n_agents=n, n_envs=E, seed=41, auto_reset=True, continuous_actions=cont, device="cuda")
+    env.reset()
+    ls = torch.full((A, 3), -0.5, device="cuda") if cont else None
+    kw = dict(sample="gaussian", log_std=ls) if cont else dict(sample="categorical", temperature=TAU)
+    ro = PolicyRollout(env, actor, T, seed=3, value_actor=critic, gae=dict(gamma=0.99, lam=0.95), **kw)
+    ro.start(); ro.capture()
+    ro.run(); ro.run()
+    torch.cuda.synchronize()
+    act = ro.scores.clone() if cont else ro.scores.argmax(-1)
+    rec = dict(obs=ro.obs[:T].clone(), act=act, logp=ro.logp.clone(), adv=ro.adv.clone(), ret=ro.ret.clone(), mask=ro.mask.clone())
+    return actor, critic, ls, {k: v.cpu() for k, v in rec.items()}
+
+
+def _logp(actor, ls, obs, act, kind, fused):
+    from deep_rl_battlespace_amd.learner import categorical_log_prob
+    from deep_rl_battlespace_amd.rollout import gaussian_log_prob
+    if kind == "gaussian":
+        return gaussian_log_prob(actor, ls, obs, act, fused=fused)
+    return categorical_log_prob(actor, obs, act, temperature=TAU, fused=fused)
+
+
+def _ppo(actor, critic, ls, rec, keep, kind, fused, device, dtype, perm=None):
+    """(loss, actor grads, critic grads, log_std grad) of the clipped surrogate + value loss - entropy bonus over the kept rows, the rows
+    flattened (and permuted: another summation order of the same loss)."""
+    from deep_rl_battlespace_amd.learner import fused_apply
+    a, c = _to(actor, device, dtype), _to(critic, device, dtype)
+    l = ls.detach().to(device=device, dtype=dtype).requires_grad_() if ls is not None else None
+    A, D = rec["obs"].shape[-2:]
+    flat = dict(obs=rec["obs"].reshape(-1, A, D), act=rec["act"].reshape(-1, A, *rec["act"].shape[3:]), logp=rec["logp"].reshape(-1, A),
+                adv=rec["adv"].reshape(-1, A), ret=rec["ret"].reshape(-1, A), keep=keep.reshape(-1, A))
+    if perm is not None:
+        flat = {k: v[perm] for k, v in flat.items()}
+    f = {k: (v.to(device=device, dtype=dtype) if v.is_floating_point() else v.to(device)).contiguous() for k, v in flat.items()}
+    logp, ent = _logp(a, l, f["obs"], f["act"], kind, fused)
+    v = fused_apply(c, f["obs"], squash=False)[..., 0] if fused else c(f["obs"], squash=False)[..., 0]
+    ratio = torch.exp(logp - f["logp"])
+    surr = torch.minimum(ratio * f["adv"], ratio.clamp(1 - CLIP, 1 + CLIP) * f["adv"])
+    w = f["keep"].to(dtype)
+    loss = (-(surr * w).sum() + 0.5 * ((v - f["ret"]) ** 2 * w).sum() - 0.01 * (ent * w).sum()) / w.sum()
+    loss.backward()
+    grads = lambda m: {k: getattr(m, k).grad.double().cpu().numpy() for k in U.PARAMS}   # noqa: E731
+    return float(loss.detach().double()), grads(a), grads(c), (l.grad.double().cpu().numpy() if l is not None else None), ratio.detach().double().cpu()
+
+
+@pytest.mark.parametrize("kind", ["gaussian", "categorical"])
+def test_ppo_loss_and_gradients_fused_against_torch_on_a_rollout_record(kind):
+    actor0, critic, ls, rec = _record(kind)
+    critic = _to(critic, "cpu")
+    ls_cpu = ls.cpu() if ls is not None else None
+    T, E, A, D = rec["obs"].shape
+    flat_obs = rec["obs"].reshape(-1, A, D)
+    # the learner is a step away from the policy that played, so that ratios leave 1 and some are clipped: the smallest step of a fixed
+    # ladder that clips between 5 % and 60 % of the rows (chosen on the float64 reference alone)
+    for scale in (0.03, 0.06, 0.12, 0.25, 0.5, 1.0):
+        actor = _to(actor0, "cpu")
+        g = torch.Generator().manual_seed(5)
+        with torch.no_grad():
+            for k in U.PARAMS:
+                p = getattr(actor, k)
+                p.add_(scale * p.abs().mean() * torch.randn(p.shape, generator=g))
+        # rows kept: the agent's own decisions (mask), away from every kink of the loss in float64 -- a hidden unit of either network
+        # within 1e-4 of its ReLU's kink, a ratio within 1e-4 of a clip boundary -- for the reason actor_grad_util states; the same rows
+        # in every path
+        near = (U.pre_relu64(actor, flat_obs).abs() < U.KINK).any(-1) | (U.pre_relu64(critic, flat_obs).abs() < U.KINK).any(-1)
+        keep = rec["mask"] & ~near.transpose(0, 1).reshape(T, E, A)
+        _, _, _, _, r64 = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float64)
+        r64 = r64.reshape(T, E, A)
+        keep = keep & ((r64 - (1 - CLIP)).abs() > 1e-4) & ((r64 - (1 + CLIP)).abs() > 1e-4)
+        kept, clipped = int(keep.sum()), int((keep & ((r64 < 1 - CLIP) | (r64 > 1 + CLIP))).sum())
+        print(kind, "step", scale, "rows kept", kept, "of", int(rec["mask"].sum()), "masked; clipped", clipped)
+        if 0.05 * kept <= clipped <= 0.6 * kept:
+            break
+    assert kept >= 0.9 * int(rec["mask"].sum()) and kept >= 500 and 0.05 * kept <= clipped <= 0.6 * kept
+    L64, a64, c64, l64, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float64)
+    L32, a32, c32, l32, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float32)
+    Lt, _, _, lt, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cuda", torch.float32)
+    Lf, af, cf, lf, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, True, "cuda", torch.float32)
+    # what the torch path itself loses on this record: the float32 loss under 8 orders of the rows, against float64
+    e_loss, e_ls = abs(Lt - L64), (np.abs(lt - l64).max() if ls is not None else 0.0)
+    for p in range(8):
+        perm = torch.randperm(T * E, generator=torch.Generator().manual_seed(4000 + p))
+        Lp, _, _, lp, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cuda", torch.float32, perm)
+        e_loss = max(e_loss, abs(Lp - L64))
+        if ls is not None:
+            e_ls = max(e_ls, np.abs(lp - l64).max())
+    # a float32 loss cannot be expected closer to float64 than half a float32 spacing at its size, whatever the nine orders happened to hit
+    e_loss = max(e_loss, 0.5 * float(np.spacing(np.float32(abs(L64)))))
+    print(kind, f"loss float64 {L64:.9g} fused {Lf:.9g} torch {Lt:.9g}; |fused - torch| {abs(Lf - Lt):.3e}, |fused - f64| {abs(Lf - L64):.3e}, "
+                f"torch's own error (max of 9 row orders, at least half a float32 spacing) {e_loss:.3e}")
+    # both are float32 evaluations of the same loss, each off float64 by about e_loss: 4 e_loss is the project's factor on a maximum
+    assert abs(Lf - Lt) <= 4 * e_loss and abs(Lf - L64) <= 4 * e_loss
+    U.check(af, a64, a32, f"PPO {kind} actor")
+    U.check(cf, c64, c32, f"PPO {kind} critic")
+    if ls is not None:
+        print(kind, f"log_std gradient: |fused - f64| {np.abs(lf - l64).max():.3e}, torch's own error {e_ls:.3e}, max |g| {np.abs(l64).max():.3e}")
+        assert np.abs(lf - l64).max() <= 4 * e_ls
+
+
+@pytest.mark.parametrize("kind", ["gaussian", "categorical"])
+def test_fused_log_probabilities_match_the_rollouts_recorded_ones(kind):
+    actor, critic, ls, rec = _record(kind)
+    obs, act = rec["obs"].to("cuda"), rec["act"].to("cuda")
+    with torch.no_grad():
+        logp_f, ent_f = _logp(actor, ls, obs, act, kind, True)
+        logp_t, ent_t = _logp(actor, ls, obs, act, kind, False)
+    m = rec["mask"].to("cuda")
+    assert int(m.sum()) > 500
+    torch.testing.assert_close(logp_f[m], rec["logp"].to("cuda")[m], rtol=0, atol=LOGP_TOL)
+    torch.testing.assert_close(logp_f, logp_t, rtol=0, atol=LOGP_TOL)
+    torch.testing.assert_close(ent_f, ent_t, rtol=0, atol=LOGP_TOL)
+    assert math.isfinite(float(logp_f.sum()))
