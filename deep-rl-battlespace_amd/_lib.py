@@ -69,6 +69,10 @@ class BsxGaeIo(ctypes.Structure):
     _fields_ = [(f, c_void_p) for f in ("rew", "value", "done", "env_done", "last_value", "done_prev", "adv", "ret", "mask")]
 
 
+class BsxPpoIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("y", "v", "rec", "logp_old", "adv", "ret", "mask", "v_old", "log_std", "g_pi", "g_v", "g_log_std")]
+
+
 # name -> (restype, argtypes): every symbol include/battlespace_hip.h declares
 SIGNATURES = {
     "bsx_abi_version": (c_int, []),
@@ -122,6 +126,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsx_gae_workspace_bytes": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_gae": (c_int, [ctypes.POINTER(BsxGaeIo), c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_ppo_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_ppo_head": (c_int, [ctypes.POINTER(BsxPpoIo), c_int64, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                             ctypes.c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -48,7 +48,9 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            # the replay ring (append / sample): copies bits and draws integers, no floating-point arithmetic to pin
            (os.path.join(CSRC, "bsx_replay.hip"), []),
            # GAE advantages: float32 operations each rounded on their own, as tests/gae_util.py restates them
-           (os.path.join(CSRC, "bsx_advantage.hip"), ["-ffp-contract=off"])]
+           (os.path.join(CSRC, "bsx_advantage.hip"), ["-ffp-contract=off"]),
+           # the PPO loss head: float32 element-wise terms held to a float64 reference, not to bits: contraction allowed
+           (os.path.join(CSRC, "bsx_ppo_head.hip"), [])]
 
 
 def _stale():

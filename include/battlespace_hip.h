@@ -447,6 +447,76 @@ int bsx_actor_grad_workspace_bytes(int64_t R, int n, size_t* bytes);          /*
 int bsx_actor_grad(const float* weights, const float* obs, const float* grad_out, int64_t R, int n, int squash,
                    float* grad, void* workspace, void* stream);
 
+/* ---- the PPO loss head (deep-rl-battlespace_amd/learner.py: ppo_head, PPOLearner; csrc/bsx_ppo_head.hip): from the forward's outputs
+ * and a rollout's records to the two grad_out tensors bsx_actor_grad takes, log_std's gradient and the loss statistics, in one pass.
+ *
+ * Rows are a rollout's [T][E] flattened, R = T*E (1 <= R <= BSX_MAX_E); element (r, a) is one agent's decision, A = 2n, 1 <= n <= BSX_MAX_N.
+ * Every array is contiguous; the float32 [..][4] ones are 16-byte aligned, the float32 [R][A] and [A][3] ones 4-byte, mask 1-byte.
+ *   y          float32 [R][A][4]: the policy network's forward output (bsx_actor_forward's scores).  kind 0: the four tanh scores;
+ *              kind 1: mu in columns 0..2 (column 3 is read and ignored)
+ *   v          float32 [R][A]: the value head's forward output
+ *   rec        float32 [R][A][4]: the rollout's `scores` record as it stands.  kind 0: the perturbed scores -- the played action a* is
+ *              their FIRST maximum (what the step kernel's arg-max takes), found here; kind 1: the unclipped draws in columns 0..2
+ *   logp_old, adv, ret   float32 [R][A]: the rollout's records;   mask uint8 [R][A]: bsx_gae's mask (any non-zero byte counts)
+ *   v_old      float32 [R][A] or NULL: the rollout's value record; NULL = no value clipping (vclip is not read)
+ *   log_std    float32 [A][3], kind 1 only (not read with kind 0: may be NULL)
+ *   g_pi, g_v  float32 [R][A][4] (out, overwritten everywhere): bsx_actor_grad's grad_out of the policy network (squash = 1) and of the
+ *              value network (squash = 0).  g_v carries column 0, its other columns are +0; g_pi column 3 is +0 with kind 1
+ *   g_log_std  float32 [A][3] (out, kind 1 only; not written with kind 0: may be NULL) */
+typedef struct BsxPpoIo {
+    const float* y;
+    const float* v;
+    const float* rec;
+    const float* logp_old;
+    const float* adv;
+    const float* ret;
+    const uint8_t* mask;
+    const float* v_old;
+    const float* log_std;
+    float* g_pi;
+    float* g_v;
+    float* g_log_std;
+} BsxPpoIo;
+
+/* Size of bsx_ppo_head's workspace: 2 048 bytes of partial counts and 8 (8 + 3 A) bytes per workgroup of the head pass (for either kind).
+ * BSX_E_ARG: null bytes, R or A out of range. */
+int bsx_ppo_head_workspace_bytes(int64_t R, int A, size_t* bytes);
+
+/* N = the number of elements with mask != 0 over the whole call.  Per element with mask != 0, in float32 with the device's expf / logf
+ * (contraction to fused multiply-adds allowed):
+ *   kind 0 (categorical):  s = y / temperature,  lp_j = (s_j - max s) - log sum_k exp(s_k - max s),  p_j = exp(lp_j),  logp = lp[a*],
+ *     H = -sum p lp;   dlogp/dy_j = ((j == a*) - p_j) / temperature,   dH/dy_j = -p_j (lp_j + H) / temperature
+ *   kind 1 (Gaussian):  z_k = (rec_k - y_k) exp(-log_std[a][k]),  logp = sum_k (-z_k^2 / 2 - log_std[a][k]) - 1.5 log 2 pi,
+ *     H = sum_k log_std[a][k] + 1.5 (1 + log 2 pi);   dlogp/dy_k = z_k exp(-log_std[a][k]),  dlogp/dlog_std_k = z_k^2 - 1,  dH/dlog_std_k = 1
+ *     (z, z^2, the sum and logp - logp_old are formed in float64 from the float32 inputs and rounded once: a float32 sum of terms of
+ *     size z^2 / 2 would carry ~1e-6 into the ratio's exponent; every value that goes on is float32)
+ *   policy:  ratio = exp(logp - logp_old),  surr = min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv);  the row is CLIPPED when
+ *     (adv > 0 && ratio > 1 + clip) || (adv < 0 && ratio < 1 - clip);   dsurr/dlogp = clipped ? 0 : ratio adv
+ *   value:   lv = (v - ret)^2 / 2,  dlv/dv = v - ret;  with v_old: vc = v_old + clamp(v - v_old, -vclip, vclip), and where
+ *     |v - v_old| > vclip && (vc - ret)^2 > (v - ret)^2:  lv = (vc - ret)^2 / 2,  dlv/dv = 0
+ *   row loss = -surr + c_v lv - c_e H
+ *   g_pi_j = (-dsurr/dlogp dlogp/dy_j - c_e dH/dy_j) / N,   g_v[0] = c_v dlv/dv / N     (x / N is float32(float64(x) * (1 / float64(N))))
+ *   g_log_std[a][k] = (the float64 sum over agent a's rows of the float32 terms -dsurr/dlogp (z_k^2 - 1) - c_e) / N, rounded to float32
+ *   stats[8] (device, float64) = N, then the means over the N rows -- float64 sums of the float32 per-row terms, divided by N -- of the
+ *     row loss, -surr, lv, H, (ratio - 1) - (logp - logp_old) (an approximate KL; evaluated from d = logp - logp_old as d^2 (1/2 + d/6 +
+ *     .. + d^8/10!) for |d| < 1/2 and as expm1f(d) - d beyond, neither of which cancels against the 1), clipped ? 1 : 0 (the clipped
+ *     share); stats[7] = 0.
+ * An element with mask == 0 writes +0 to its eight gradient floats and contributes to nothing, whatever its other inputs hold (NaN and
+ * infinities included: it is selected out, never multiplied by 0).  N = 0: every gradient is +0 and stats is all 0.
+ * Deterministic: no floating-point atomics.  Three launches on `stream`: an integer count of mask (partial counts of up to 256
+ * workgroups); the head pass -- every workgroup adds the partial counts to N, then takes J consecutive tiles of (256 / A) A consecutive
+ * elements, one thread per element, adds its statistics and log_std terms per thread over the tiles, then over the workgroup in a
+ * fixed order, and stores them to the workspace; one workgroup that adds those partial rows in a fixed order.  J and the grid depend on
+ * (R, A) alone: the same inputs give the same bits on every call.  No host synchronisation: capturable in a HIP graph.
+ * workspace: 8-byte aligned, at least bsx_ppo_head_workspace_bytes(R, A), not in use by another call in flight; stats: 8-byte aligned.
+ * Refusals, before any launch, in this order: BSX_E_ARG for a null io, y, v, rec, logp_old, adv, ret, mask, g_pi, g_v, workspace or
+ * stats; a kind other than 0 / 1; clip outside (0, 1), c_v or c_e negative or not finite, with kind 0 a temperature that is not a
+ * finite number > 0, with v_old a vclip that is not (NaN: all refused); R < 1, R > BSX_MAX_E, A odd or A / 2 outside
+ * 1 .. BSX_MAX_N; with kind 1 a null log_std or g_log_std.  Then BSX_E_ALIGN for y, rec, g_pi or g_v off a 16-byte boundary; v,
+ * logp_old, adv, ret or v_old off a 4-byte one; with kind 1 log_std or g_log_std off a 4-byte one; workspace or stats off an 8-byte one. */
+int bsx_ppo_head(const BsxPpoIo* io, int64_t R, int A, int kind, float temperature, float clip, float vclip, float c_v, float c_e,
+                 void* workspace, double* stats, void* stream);
+
 /* Host helper: the call number on which the time-limit tie fires for n-per-team -- the reference accumulates
  * total_time += 0.1 in binary64 and compares >= 10+2n (battle_env.py:168,316-319): 121, 141, 161, 181, 200 ... */
 int bsx_tie_tick(int n);
