@@ -1,6 +1,7 @@
 """What the tests of the actor's fused training pass (learner.fused_apply, csrc/bsx_actor_grad.hip) share:
 
-  CASES            (class, n, outputs, squash) on the input classes of actor_ref_util
+  CASES            (class, n, outputs, squash) on the input classes of actor_ref_util, team sizes 1 .. 16; LARGE: (n, rows) with many rows
+  plan             workgroups per agent and rounds of a launch, from the library's own workspace size
   reference        per case, cached: the float64 autograd gradients g64 (torch on the CPU, loss = (y * go).sum()), the float32 ones g32 of
                    the same network (the yardstick: what float32 itself loses on these inputs), the upstream gradient go and the share of
                    rows it leaves out
@@ -13,7 +14,7 @@
                    (actor_ref_util.F32_FACTORS) except where the recorded spread of the yardstick reaches them
                    (profiles/actor_grad_float64.json says where and why)
 
-Nothing here imports the native library."""
+Nothing here imports the native library but plan()."""
 import functools
 import json
 import os
@@ -28,11 +29,35 @@ KINK = 1e-4
 KINK_CAP = 0.05
 PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "actor_grad_float64.json")
 
-# (class, n, outputs, squash).  Left out, seed 0: dead_half at n = 3 (one agent's constant all -1 row has a kink unit: 57.6 % of its rows would go)
-# and fresh at n = 3 (15.4 % for the same reason).  The rest stay below KINK_CAP, which test_actor_grad_cpu.py checks.
+# (class, n, outputs, squash).  Left out, seed 0: dead_half at n = 3 (one agent's constant all -1 row has a kink unit: 57.6 % of its rows would go),
+# fresh at n = 3 (15.4 % for the same reason) and fresh at n = 13 and n = 16 (15.1 % for the same reason: the wide teams below n = 12 are fresh,
+# the ones above trained_like).  The rest stay below KINK_CAP, which test_actor_grad_cpu.py checks.
+# Team sizes 5 .. 10 reach D = 3n + 2 = 17, 26 and 32 (the 32-column x image with little or no zero padding); n >= 11 has D > 32 and takes the
+# kernel's two-tile dW1 form (D = 35, 41, 50).  With 512 / (2n) workgroups per agent at most, the dense row count makes the workgroups of
+# n = 8, 10, 11 go round their tile loop twice and those of n = 13, 16 three times (MULTI_ROUND; test_actor_grad_cpu.py derives it from
+# the workspace size, so that a change of the cap cannot quietly turn these back into one-round cases).
 CASES = (("fresh", 1, 4, True), ("fresh", 4, 4, True), ("shipped", 2, 4, True), ("trained_like", 1, 4, True),
          ("trained_like", 4, 4, True), ("trained_like", 3, 3, True), ("fresh", 2, 3, True), ("flat_rows", 2, 4, True), ("wide_obs", 2, 4, True),
-         ("dead_half", 1, 4, True), ("fresh", 1, 1, False), ("trained_like", 3, 1, False))
+         ("dead_half", 1, 4, True), ("fresh", 1, 1, False), ("trained_like", 3, 1, False),
+         ("fresh", 5, 4, True), ("fresh", 8, 4, True), ("fresh", 10, 4, True), ("fresh", 11, 4, True), ("trained_like", 11, 3, True),
+         ("trained_like", 13, 1, False), ("trained_like", 16, 4, True), ("trained_like", 16, 1, False))
+MULTI_ROUND = tuple(c for c in CASES if c[1] >= 8)
+# (n, rows) of the regime the kernel was written for, at small teams: many rows, the workgroup cap reached, two rounds.  (1, 33 000) has 1 032
+# tiles on 256 workgroups per agent (the merge kernel's widest input); the last round of both is nearly empty: most waves lie beyond R.
+LARGE = ((1, 33000), (4, 8300))
+
+
+def plan(rows, n):
+    """(workgroups per agent P, rounds) of bsx_actor_grad at (rows, n), P read back from the workspace size the library asks for."""
+    import ctypes
+    from deep_rl_battlespace_amd import _lib
+    nb = _lib.c_size_t()
+    _lib.check(_lib.load().bsx_actor_grad_workspace_bytes(rows, n, ctypes.byref(nb)), "bsx_actor_grad_workspace_bytes")
+    G = 64 * (3 * n + 2) + 4096 + 6 * 64 + 260
+    assert nb.value % (2 * n * G * 4) == 0
+    P = nb.value // (2 * n * G * 4)
+    tiles = (rows + 31) // 32
+    return P, (tiles + 4 * P - 1) // (4 * P)
 
 
 def case_id(case):
@@ -97,14 +122,27 @@ def reference(case, rows=None):
     return actor, obs, go, g64, g32, share
 
 
+@functools.lru_cache(maxsize=None)
+def reference_large(n, rows, seed=0):
+    """The same tuple for a LARGE pair: the fresh class's actor on `rows` of its observations (uniform, every seventh row all -1)."""
+    actor = R._fresh_actor(n, 10 + n + seed)
+    obs = R._uniform_obs(n, seed, E=rows)
+    obs[::7] = -1.0
+    go, share = kink_free_go(actor, obs, seed)
+    g64 = autograd_grads(actor, obs, go, True, torch.float64)
+    g32 = autograd_grads(actor, obs, go, True, torch.float32)
+    return actor, obs, go, g64, g32, share
+
+
 def permutation_spread(case, perms=8):
     """{name: (max ratio, mean ratio)}: over `perms` row permutations, how far max(e_t) and mean(e_t) move from the unpermuted yardstick
-    (the larger of p / base and base / p)."""
-    actor, obs, go, g64, g32, _ = reference(case)
+    (the larger of p / base and base / p).  `case`: one of CASES, or a reference tuple."""
+    actor, obs, go, g64, g32, _ = reference(case) if isinstance(case[0], str) else case
+    squash = case[3] if isinstance(case[0], str) else True
     out = {k: [1.0, 1.0] for k in PARAMS}
     for p in range(perms):
         idx = torch.randperm(obs.shape[0], generator=torch.Generator().manual_seed(4000 + p))
-        gp = autograd_grads(actor, obs[idx].contiguous(), go[idx].contiguous(), case[3], torch.float32)
+        gp = autograd_grads(actor, obs[idx].contiguous(), go[idx].contiguous(), squash, torch.float32)
         for k in PARAMS:
             e0, e1 = np.abs(g32[k] - g64[k]), np.abs(gp[k] - g64[k])
             for i, f in enumerate((np.max, np.mean)):

@@ -31,7 +31,12 @@ KINK = 1e-4
 LADDER = (0.03, 0.06, 0.12, 0.25, 0.5, 1.0)
 CLIP, VCLIP, TAU, C_V, C_E = 0.2, 0.2, 0.7, 0.5, 0.01
 FILTER_CAP = 0.01                       # the filter may remove at most 1 % of the masked rows
-SHAPES = ((1000, 1), (257, 3), (512, 4))                         # (R, n) of the float64 test; the ragged test cuts rows off the first two
+# (R, n) of the float64 test.  Up to n = 4 a workgroup's 256 threads are all at work (S = 256 or 252 of them) and the per-agent log_std
+# reduction runs on 8 threads per column; the wide teams take its other forms and other merge shapes: n = 5 (A = 10: S = 250, 8 parts),
+# n = 11 (A = 22: S = 242, 66 columns, 3 parts), n = 13 (A = 26: S = 234, 78 columns, 3 parts), n = 16 (A = 32: 96 columns, 2 parts, partial
+# rows of 104 doubles)
+SHAPES = ((1000, 1), (257, 3), (512, 4), (257, 5), (130, 11), (97, 13), (200, 16))
+RAGGED_SHAPES = {1: SHAPES[0], 3: SHAPES[1], 11: SHAPES[4], 16: SHAPES[6]}       # n -> the shape the ragged test cuts its rows off
 LARGE = (262209, 1)                     # 2 049 tiles of 256 elements (the last one ragged): beyond 2 048 a workgroup of the head pass takes two tiles
 LARGE_STEP = dict(categorical=0.25, gaussian=0.06)               # the step the ladder ends on at (1000, 1): the ladder itself is not run at this size
 KINDS = ("categorical", "gaussian")

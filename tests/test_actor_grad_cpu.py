@@ -1,7 +1,9 @@
 """CPU-side checks of the actor's fused training pass (bsx_actor_grad*, learner.fused_apply / categorical_log_prob): the header, the
 library and the binding agree on the three entry points; sizes follow their formulas; every refusal comes before any launch, in the
 documented order (fake addresses only: no call here reaches a kernel); the conditions the GPU tests' float64 bounds rest on -- the share
-of rows left out for ReLU kinks, the spread of the float32 yardstick under row permutations -- hold on the reference alone; a gradient row
+of rows left out for ReLU kinks, the spread of the float32 yardstick under row permutations -- hold on the reference alone, at every team
+size from 1 to 16 and on the two many-row inputs; the row counts of the multi-round cases still make the workgroups go round more than
+once, and the wide teams still have D > 32, by the library's own workspace size; a gradient row
 splits into the ten parameter shapes where torch.cat would put them; the learner-side categorical head equals torch.distributions."""
 import ctypes
 import json
@@ -114,6 +116,50 @@ def test_the_factors_cover_what_row_order_alone_does_to_the_float32_yardstick(ca
         assert spread[k][0] < f[k][1] and spread[k][1] < f[k][0], (k, spread[k], f[k])
         if k != "b3":
             assert f[k] == (2.0, 4.0)
+
+
+@pytest.mark.parametrize("n,rows", U.LARGE, ids=lambda v: str(v))
+def test_the_many_row_inputs_meet_the_same_two_conditions(n, rows):
+    """The (n, rows) pairs of actor_grad_util.LARGE: the kink share below the cap and the yardstick's spread inside the factors, as above."""
+    ref = U.reference_large(n, rows)
+    actor, obs, go, g64, g32, share = ref
+    print("large", n, rows, "largest per-agent share", float(share.max()))
+    assert obs.shape == (rows, 2 * n, 3 * n + 2) and float(share.max()) <= U.KINK_CAP, share
+    assert np.allclose((go == 0).all(-1).double().mean(0).numpy(), share)
+    assert bool((obs[::7] == -1.0).all()) and all(np.isfinite(g64[k]).all() and np.abs(g64[k]).max() > 0 for k in U.PARAMS)
+    spread = U.permutation_spread(ref, 8)
+    f = U.factors()
+    for k in U.PARAMS:
+        print("large", n, rows, k, "max moved by %.2f, mean by %.2f" % spread[k])
+        assert spread[k][0] < f[k][1] and spread[k][1] < f[k][0], (k, spread[k], f[k])
+
+
+def test_the_multi_round_cases_still_go_round_twice_and_the_wide_teams_still_take_the_two_tile_kernel():
+    """bsx_actor_grad caps the workgroups per agent, and a workgroup takes four 32-row tiles per round: P workgroups per agent (read back
+    from the workspace size: bytes / (2n G 4)) make ceil(ceil(R / 32) / (4 P)) rounds.  The cases the GPU tests count on for the round loop
+    (accumulators kept across rounds, LDS images overwritten, a last round that is mostly beyond R) must have rounds >= 2 at their row
+    counts, and the cases they count on for the two-tile dW1 kernel D = 3n + 2 > 32: a later change of the cap has to move these row
+    counts with it."""
+    rounds = {}
+    for case in U.CASES:
+        rows, n = 5001 - 2 * case[1], case[1]
+        P, rounds[case] = U.plan(rows, n)
+        assert 1 <= P <= 512 // (2 * n)
+        print(U.case_id(case), "rows", rows, "workgroups per agent", P, "rounds", rounds[case])
+    assert {c[1] for c in U.MULTI_ROUND} == {8, 10, 11, 13, 16}
+    assert all(rounds[c] >= 2 for c in U.MULTI_ROUND)
+    assert all(rounds[c] == 3 for c in U.CASES if c[1] == 16) and sum(c[1] == 16 for c in U.CASES) == 2
+    assert all(rounds[c] == 1 for c in U.CASES if c[1] <= 5)                       # the one-round path keeps its cases too
+    wide = [c for c in U.CASES if c[1] >= 11]
+    assert len(wide) == 5 and all(3 * c[1] + 2 > 32 for c in wide) and {3 * c[1] + 2 for c in U.CASES if 5 <= c[1] <= 10} == {17, 26, 32}
+    for n, rows in U.LARGE:
+        P, r = U.plan(rows, n)
+        print("large", n, rows, "workgroups per agent", P, "rounds", r)
+        assert r == 2 and P == 512 // (2 * n)
+    assert U.plan(33000, 1)[0] == 256                                              # the merge kernel's widest input
+    # the ragged, appended-rows, layout and graph legs at 16 a side (tests/test_hip_actor_grad.py)
+    assert U.plan(2048, 16) == (16, 1) and U.plan(2049, 16) == (16, 2) and U.plan(2081, 16) == (16, 2) and U.plan(2100, 16) == (16, 2)
+    assert U.plan(257, 11)[1] == 1 and U.plan(300, 16)[1] == 1
 
 
 def test_a_gradient_row_splits_where_cat_of_the_flattened_parameters_puts_it():

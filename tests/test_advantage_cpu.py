@@ -116,6 +116,30 @@ def test_restatement_matches_textbook_gae_on_single_episodes(T):
                 np.testing.assert_allclose(r[:, 0, col], wr, rtol=1e-5, atol=1e-5 * (1 + np.abs(wr).max()))
 
 
+@pytest.mark.parametrize("E,A", [(2, 6), (4, 10)])
+def test_restatement_matches_textbook_gae_per_column_on_teams_whose_rows_are_no_multiple_of_four(E, A):
+    """The shapes at which a lane of the kernel has columns of two games (A = 6, 10 with an even E; tests/test_hip_advantage.py STRADDLE):
+    the restatement the kernel is held to, column by column against the textbook loop, each game with its own terminal tick."""
+    rng = np.random.default_rng(100 * E + A)
+    T, gamma, lam = 9, 0.97, 0.9
+    rew, value, lv, _, _, _ = random_case(rng, T, E, A)
+    done = np.zeros((T, E, A), np.uint8)
+    done[T - 1, ::2] = 1                                 # every other game ends on the last tick, its neighbours are cut off by the rollout's end
+    a, r, m, c, _ = gae_ref(rew, value, lv, done, np.zeros((T + 1, E), np.uint8), np.zeros((E, A), np.uint8), gamma, lam)
+    assert m.all() and np.array_equal(c, done[T - 1])
+    for e in range(E):
+        for col in range(A):
+            wa, wr = textbook_gae(rew[:, e, col].astype(np.float64), value[:, e, col].astype(np.float64), float(lv[e, col]), done[:, e, col],
+                                  gamma, lam)
+            np.testing.assert_allclose(a[:, e, col], wa, rtol=1e-5, atol=1e-5 * (1 + np.abs(wa).max()))
+            np.testing.assert_allclose(r[:, e, col], wr, rtol=1e-5, atol=1e-5 * (1 + np.abs(wr).max()))
+    # a finished game's rows are masked by ITS env_done flag, not its neighbour's: game 0 finished at tick 3 on, game 1 never
+    env_done = np.zeros((T + 1, E), np.uint8)
+    env_done[3:, 0] = 1
+    _, _, m2, _, _ = gae_ref(rew, value, lv, done, env_done, np.zeros((E, A), np.uint8), gamma, lam)
+    assert not m2[3:, 0].any() and m2[:3, 0].all() and m2[:, 1:].all()
+
+
 def test_restatement_normalisation_edge_cases():
     rng = np.random.default_rng(0)
     rew, value, lv, done, env_done, prev = random_case(rng, 4, 3, 2)

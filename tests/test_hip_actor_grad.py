@@ -1,8 +1,10 @@
 """The actor's fused training pass on the MI355X (bsx_actor_grad, learner.fused_apply): every parameter gradient against float64 autograd at
 a small multiple of what float32 autograd itself loses on the same inputs (tests/actor_grad_util.py: ReLU kinks left out by construction,
-factors from profiles/actor_grad_float64.json); the layout of the gradient row; ragged row counts between guard slabs; the same bits on
-every call and from a captured graph; a PPO loss on a continuous and a discrete rollout record, fused path against torch path; the
-learner-side log-probabilities against the rollout's recorded ones."""
+factors from profiles/actor_grad_float64.json), at team sizes from 1 to 16 -- both dW1 forms of the kernel, D <= 32 (up to exactly 32) and
+D > 32 -- and at row counts that make a workgroup go round its tile loop once, twice and three times, the many-row regime at the
+workgroup cap among them; the layout of the gradient row; ragged row counts between guard slabs, on both sides of the first second
+round; the same bits on every call and from a captured graph, at 2 and at 16 a side; a PPO loss on a continuous and a discrete rollout
+record, fused path against torch path; the learner-side log-probabilities against the rollout's recorded ones."""
 import functools
 import math
 
@@ -18,6 +20,9 @@ pytestmark = pytest.mark.gpu
 
 LOGP_TOL = 1e-4                   # recorded logp against the float32 torch head: tests/test_hip_gaussian_head.py (assert_close(logp, want_lp, atol=1e-4))
 RAGGED = (1, 31, 32, 33, 63, 65, 255, 257)
+# (rows, n).  n = 16: 16 workgroups per agent, so 2 048 rows are the last one-round size and 2 049 is ONE valid row in round 2 (every
+# other lane of that round reads row R - 1 with grad_out = 0); n = 11: the two-tile dW1 kernel below and above a workgroup's 128 rows
+RAGGED_CASES = [(r, n) for n in (1, 4) for r in RAGGED] + [(r, 16) for r in (1, 33, 2047, 2048, 2049, 2081)] + [(31, 11), (257, 11)]
 
 
 def _to(actor, device="cuda", dtype=torch.float32):
@@ -60,9 +65,20 @@ def test_gradients_stay_within_the_float32_yardstick_of_float64_autograd(case):
     U.check(got, g64, g32, "KERNEL " + U.case_id(case))
 
 
+@pytest.mark.parametrize("n,rows", U.LARGE)
+def test_many_rows_at_the_workgroup_cap_keep_the_float64_bound_over_two_rounds(n, rows):
+    """The regime the kernel was written for, at the smallest size that reaches it: 512 / (2n) workgroups per agent, each going round
+    twice (tests/test_actor_grad_cpu.py derives both from the workspace size), the second round nearly empty; at n = 1 the merge kernel
+    adds 256 partial rows per agent.  The same reference, yardstick and factors as above."""
+    actor_cpu, obs_cpu, go, g64, g32, share = U.reference_large(n, rows)
+    assert float(share.max()) <= U.KINK_CAP and U.plan(rows, n) == (512 // (2 * n), 2)
+    actor, obs, y, got = _fused_grads(actor_cpu, obs_cpu, go, True)
+    assert y.shape == (rows, 2 * n, 4)
+    U.check(got, g64, g32, f"LARGE n={n} rows={rows}")
+
+
 # ---------------------------------------------------------------------------------------------------- 2. layout
-def test_one_column_of_one_agent_reaches_only_that_agents_row_and_that_head_column():
-    n, Rr, agent, col = 4, 300, 5, 2
+def _one_column_of_one_agent(n, Rr, agent, col):
     actor_cpu, obs = R.fresh(n)
     obs = obs[:Rr].contiguous()
     go = torch.zeros((Rr, 2 * n, 4))
@@ -78,6 +94,17 @@ def test_one_column_of_one_agent_reaches_only_that_agents_row_and_that_head_colu
     g64 = U.autograd_grads(actor_cpu, obs, go, True, torch.float64)
     for k in U.PARAMS:
         assert np.abs(got[k] - g64[k]).max() <= 1e-5 * np.abs(g64[k]).max(), k
+    return got
+
+
+def test_one_column_of_one_agent_reaches_only_that_agents_row_and_that_head_column():
+    _one_column_of_one_agent(4, 300, 5, 2)
+
+
+def test_one_column_of_one_agent_of_sixteen_a_side_reaches_only_its_row_and_all_fifty_input_rows_of_w1():
+    """D = 50: the two-tile dW1 kernel; w1's rows k = 32 .. 49 come from the waves' upper tiles and are held to float64 like the rest."""
+    got = _one_column_of_one_agent(16, 300, 21, 2)
+    assert got["w1"].shape == (32, 50, 64) and bool((np.abs(got["w1"][21]).max(-1) > 0).all())
 
 
 # ---------------------------------------------------------------------------------------------------- 3. ragged sizes, guards
@@ -102,11 +129,10 @@ def _raw_call(actor, obs, go4, squash=1, guarded=True):
     return out.clone(), B.stray(), nb.value
 
 
-@pytest.mark.parametrize("n", [1, 4])
-@pytest.mark.parametrize("rows", RAGGED)
+@pytest.mark.parametrize("rows,n", RAGGED_CASES)
 def test_ragged_row_counts_keep_their_guards_and_the_float64_bound(rows, n):
     from deep_rl_battlespace_amd.learner import split_grad
-    case = ("fresh", n, 4, True)
+    case = ("fresh" if n <= 4 else "trained_like", n, 4, True)
     actor_cpu, obs, go, g64, g32, _ = U.reference(case, rows)
     assert obs.shape[0] == rows
     actor = _to(actor_cpu)
@@ -116,9 +142,10 @@ def test_ragged_row_counts_keep_their_guards_and_the_float64_bound(rows, n):
     U.check(got, g64, g32, f"RAGGED rows={rows} n={n}")
 
 
-@pytest.mark.parametrize("n", [1, 4])
+@pytest.mark.parametrize("n", [1, 4, 16])
 def test_rows_appended_with_zero_gradient_change_no_bit_when_the_grid_is_the_same(n):
-    rows, more = 257, 300                                           # 9 and 10 tiles: three workgroups per agent either way
+    # 9 and 10 tiles: three workgroups per agent either way; n = 16: 65 and 66 tiles on 16 workgroups, the appended rows in round 2
+    rows, more = (2049, 2100) if n == 16 else (257, 300)
     actor_cpu, obs_all = R.fresh(n)
     actor = _to(actor_cpu)
     go = torch.randn((more, 2 * n, 4), generator=torch.Generator().manual_seed(2))
@@ -132,10 +159,9 @@ def test_rows_appended_with_zero_gradient_change_no_bit_when_the_grid_is_the_sam
 
 
 # ---------------------------------------------------------------------------------------------------- 4. determinism, graphs
-def test_the_same_inputs_give_the_same_bits_eagerly_and_from_a_captured_graph():
+def _same_bits_eagerly_and_from_a_graph(n, Rr):
     from deep_rl_battlespace_amd.learner import fused_apply, fused_grad, split_grad
     from deep_rl_battlespace_amd.rollout import FusedActor
-    n, Rr = 2, 1000
     actor_cpu, obs = R.fresh(n, outputs=3)
     actor, obs = _to(actor_cpu), obs[:Rr].to("cuda").contiguous()
     go = torch.randn((Rr, 2 * n, 3), device="cuda")
@@ -185,6 +211,15 @@ def test_the_same_inputs_give_the_same_bits_eagerly_and_from_a_captured_graph():
     torch.cuda.synchronize()
     for k, b in zip(U.PARAMS, g1):
         assert torch.equal(getattr(actor, k).grad, b), k
+
+
+def test_the_same_inputs_give_the_same_bits_eagerly_and_from_a_captured_graph():
+    _same_bits_eagerly_and_from_a_graph(2, 1000)
+
+
+def test_sixteen_a_side_over_two_rounds_gives_the_same_bits_eagerly_and_from_a_captured_graph():
+    assert U.plan(2100, 16)[1] == 2
+    _same_bits_eagerly_and_from_a_graph(16, 2100)
 
 
 def test_fused_apply_refuses_what_it_documents():

@@ -1,5 +1,5 @@
 """GAE on the MI355X (csrc/bsx_advantage.hip, advantage.gae, PolicyRollout(gae=)): bit for bit the numpy restatement of
-tests/gae_util.py on random records of every shape class, normalised to the restatement's float64 statistics, the same bits on every
+tests/gae_util.py on random records of every shape class (teams up to 16 a side; lanes whose 4 columns lie in two games), normalised to the restatement's float64 statistics, the same bits on every
 call and graph replay, nothing written outside the outputs; inside a rollout, computed from the rollout's own records without
 disturbing them."""
 import numpy as np
@@ -50,7 +50,13 @@ def _assert_exact(got, want, what):
     assert np.array_equal(c, wc), (what, "done_prev")
 
 
-SHAPES = [(1, 2), (3, 2), (63, 2), (64, 2), (65, 4), (127, 2), (257, 8), (1000, 4), (77, 6)]
+# (E, A).  A lane owns 4 adjacent columns of a tick's E*A where E*A is a multiple of 4, else 2.  With 4, a lane's columns lie in TWO games
+# (the kernel's e0 / e1 / split, env_done read per column) exactly where A is no multiple of 4: A = 6, 10, 14, .. with an even E.  STRADDLE
+# are those shapes; (3, 32) is the widest team at 4 columns (never across a game), (33, 10) and (77, 6) take 2 columns.
+STRADDLE = [(2, 6), (64, 6), (66, 10), (6, 14), (4, 22), (2, 26)]
+assert all(E * A % 4 == 0 and A % 4 != 0 for E, A in STRADDLE)
+SHAPES = [(1, 2), (3, 2), (63, 2), (64, 2), (65, 4), (127, 2), (257, 8), (1000, 4), (77, 6)] + STRADDLE + [(3, 32), (33, 10)]
+assert (3 * 32) % 4 == 0 and 32 % 4 == 0 and (33 * 10) % 4 != 0
 
 
 @pytest.mark.parametrize("T", [1, 2, 7, 32, 129])
@@ -86,7 +92,7 @@ def _assert_normalised(got, want, what):
 
 def test_normalised_advantages_and_stats_match_the_restatement():
     rng = np.random.default_rng(11)
-    for T, E, A in ((1, 5, 2), (7, 63, 2), (32, 257, 8), (129, 100, 4), (32, 65536, 2)):
+    for T, E, A in ((1, 5, 2), (7, 63, 2), (32, 257, 8), (129, 100, 4), (32, 65536, 2), (32, 64, 6), (7, 6, 10)):
         case = random_case(rng, T, E, A)
         case[0][...] += 0.5                                                      # a mean well away from 0: the 1e-12 bound is relative
         _assert_normalised(_run(case, 0.99, 0.95, True), gae_ref(*case, 0.99, 0.95, True), (T, E, A))

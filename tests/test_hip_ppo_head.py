@@ -1,6 +1,6 @@
 """The PPO loss head on the MI355X (bsx_ppo_head, learner.ppo_head): both gradient tensors, log_std's gradient and the statistics against
 the float64 restatement of the contract at a small multiple of what torch float32 autograd itself loses on the same inputs
-(tests/ppo_head_util.py: the kinks of the loss left out by construction); ragged row counts between guard slabs; masked-out elements
+(tests/ppo_head_util.py: the kinks of the loss left out by construction), teams from 1 to 16 a side; ragged row counts between guard slabs; masked-out elements
 holding NaN and infinities; the same bits on every call and from a captured graph of a whole minibatch; ties of the arg-max; refusals."""
 import numpy as np
 import pytest
@@ -12,6 +12,7 @@ from guard_util import Buffers
 pytestmark = pytest.mark.gpu
 
 RAGGED = (1, 31, 33, 63, 65, 255, 257)
+RAGGED_CASES = [(r, n) for n in (1, 3) for r in RAGGED] + [(r, n) for n in (11, 16) for r in (1, 33, 65)]      # (rows, n)
 KW = dict(clip=P.CLIP, c_v=P.C_V, c_e=P.C_E)
 
 
@@ -68,10 +69,9 @@ def test_workgroups_that_take_more_than_one_tile_keep_the_bounds_and_their_guard
 
 # ---------------------------------------------------------------------------------------------------- 2. ragged sizes, guards
 @pytest.mark.parametrize("kind", P.KINDS)
-@pytest.mark.parametrize("n", [1, 3])
-@pytest.mark.parametrize("rows", RAGGED)
+@pytest.mark.parametrize("rows,n", RAGGED_CASES)
 def test_ragged_row_counts_keep_their_guards_overwrite_every_output_and_keep_the_float64_bound(rows, n, kind):
-    inp, ref, yard, e_stats, e_ls = P.case(kind, *(P.SHAPES[0] if n == 1 else P.SHAPES[1]), True, cut=rows)
+    inp, ref, yard, e_stats, e_ls = P.case(kind, *P.RAGGED_SHAPES[n], True, cut=rows)
     assert inp["adv"].shape == (rows, 2 * n)
     fills = []
     for fill in (7.0, -3.0):                                           # an output float that keeps BOTH fills was not written
@@ -85,7 +85,12 @@ def test_ragged_row_counts_keep_their_guards_overwrite_every_output_and_keep_the
 # ---------------------------------------------------------------------------------------------------- 3. the mask
 @pytest.mark.parametrize("kind", P.KINDS)
 def test_masked_out_elements_write_plus_zero_and_reach_nothing_whatever_they_hold(kind):
-    inp, _, _ = P.inputs(kind, 257, 3)
+    for shape in ((257, 3), (97, 13)):                                  # 13 a side: 234 of a workgroup's 256 threads at work
+        _masked_out_elements(kind, shape)
+
+
+def _masked_out_elements(kind, shape):
+    inp, _, _ = P.inputs(kind, *shape)
     off = inp["mask"] == 0
     assert 100 < int(off.sum()) < off.numel() - 100
     bad = {k: v.clone() for k, v in inp.items()}
@@ -117,6 +122,8 @@ def test_the_same_inputs_give_the_same_bits_on_every_call(kind):
     assert _same_bits(a, b)
     wide, _, _ = P.inputs(kind, 512, 4)
     assert _same_bits(_call(wide, kind, False)[0], _call(wide, kind, False, fill=-1.0)[0])
+    widest, _, _ = P.inputs(kind, 200, 16)                              # 25 workgroups; two parts per log_std column, partial rows of 104
+    assert _same_bits(_call(widest, kind)[0], _call(widest, kind, fill=-1.0)[0])
 
 
 @pytest.mark.parametrize("kind", P.KINDS)

@@ -66,7 +66,12 @@ def test_the_large_case_meets_the_same_conditions_at_its_fixed_step(kind):
 
 @pytest.mark.parametrize("kind", P.KINDS)
 def test_masked_out_rows_with_nan_inputs_leave_the_restatement_unchanged(kind):
-    inp, _, _ = P.inputs(kind, 257, 3)
+    for shape in ((257, 3), (97, 13)):
+        _masked_out_rows(kind, shape)
+
+
+def _masked_out_rows(kind, shape):
+    inp, _, _ = P.inputs(kind, *shape)
     ref = P.reference(inp, kind)
     off = inp["mask"] == 0
     assert int(off.sum()) > 100
