@@ -126,6 +126,8 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsx_gae_workspace_bytes": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_gae": (c_int, [ctypes.POINTER(BsxGaeIo), c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_gae_agents": (c_int, [ctypes.POINTER(BsxGaeIo), c_void_p, c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p,
+                               c_void_p]),
     "bsx_ppo_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_ppo_head": (c_int, [ctypes.POINTER(BsxPpoIo), c_int64, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                              ctypes.c_float, c_void_p, c_void_p, c_void_p]),

@@ -13,6 +13,10 @@ One launch on the current stream, with no host synchronisation, so it can be cap
 normalize=True adds a masked float64 mean / unbiased std of the advantages (two more launches, fixed merge order: the same bits on every
 call) into `stats` = (n, mean, std) and scales the masked advantages by them; `ret` stays as it is.  Works on any tensors of these shapes,
 e.g. a continuous-action rollout whose values come from the caller's own torch critic.
+
+agents= (bool / uint8 [A] on the device; `bsx_gae_agents`): the agents the actor plays.  One whose flag is 0 -- a scripted opponent's plane --
+has no decisions: mask 0 and adv = ret = +0 on all of its rows, which are in none of the statistics; its carry in `done_prev` is still
+updated.  PolicyRollout(opponent=..., gae=...) passes the learned team's flags.
 """
 from collections import namedtuple
 
@@ -57,8 +61,9 @@ def _need(x, name, shape, dtypes, dev):
 _F32, _FLAG = (torch.float32,), (torch.uint8, torch.bool)
 
 
-def gae(rew, value, last_value, done, env_done, done_prev, gamma, lam, *, normalize=False, out=None, stats=None, workspace=None):
+def gae(rew, value, last_value, done, env_done, done_prev, gamma, lam, *, normalize=False, out=None, stats=None, workspace=None, agents=None):
     """-> Gae(adv f32 [T, E, A], ret f32 [T, E, A], mask bool [T, E, A], stats f64 [3] or None); done_prev is updated in place.
+    agents: optional bool / uint8 [A] device tensor, 0 = an agent the actor does not play (no decisions: see the module's docstring).
     out: optional (adv, ret, mask) to write into (mask uint8 or bool).  stats (f64 [3]) and workspace (uint8, at least
     workspace_bytes(E, A, T)) are allocated when normalize=True and they are not given -- pass them for a captured graph."""
     if not isinstance(rew, torch.Tensor) or rew.dim() != 3:
@@ -78,6 +83,8 @@ def gae(rew, value, last_value, done, env_done, done_prev, gamma, lam, *, normal
         raise ValueError(f"env_done must be a [T(+1), E] tensor with at least {T} rows")
     _need(env_done, "env_done", (env_done.shape[0], E), _FLAG, dev)
     _need(done_prev, "done_prev", (E, A), _FLAG, dev)
+    if agents is not None:
+        _need(agents, "agents", (A,), _FLAG, dev)
     if out is None:
         adv, ret = torch.empty_like(rew), torch.empty_like(rew)
         mask = torch.empty((T, E, A), dtype=torch.uint8, device=dev)
@@ -98,7 +105,7 @@ def gae(rew, value, last_value, done, env_done, done_prev, gamma, lam, *, normal
     io = _lib.BsxGaeIo(rew.data_ptr(), value.data_ptr(), done.data_ptr(), env_done.data_ptr(), last_value.data_ptr(), done_prev.data_ptr(),
                        adv.data_ptr(), ret.data_ptr(), mask.data_ptr())
     lib = _lib.load()
-    _lib.check(lib.bsx_gae(_lib.ctypes.byref(io), int(T), int(E), int(A), float(gamma), float(lam), 1 if normalize else 0,
-                           workspace.data_ptr() if normalize else None, stats.data_ptr() if normalize else None,
-                           torch.cuda.current_stream(dev).cuda_stream), "bsx_gae")
+    _lib.check(lib.bsx_gae_agents(_lib.ctypes.byref(io), agents.data_ptr() if agents is not None else None, int(T), int(E), int(A), float(gamma),
+                                  float(lam), 1 if normalize else 0, workspace.data_ptr() if normalize else None,
+                                  stats.data_ptr() if normalize else None, torch.cuda.current_stream(dev).cuda_stream), "bsx_gae_agents")
     return Gae(adv, ret, mask.view(torch.bool) if mask.dtype == torch.uint8 else mask, stats if normalize else None)

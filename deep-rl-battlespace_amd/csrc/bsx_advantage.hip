@@ -3,6 +3,7 @@
 // The on-policy counterpart of bsx_replay.hip: what a PPO update needs from a PolicyRollout's [T][E][A] records (rew, value, done,
 // env_done) plus V(obs[T]), computed inside the rollout's graph with no host round trip.  The recurrence runs backwards over T, so a lane
 // owns W adjacent columns (agent rows e*A + a) for all T ticks and walks them from T-1 down to 0:
+// bsx_gae_agents adds a per-agent flag to the mask (a scripted opponent's agents have no decisions); bsx_gae is that call with no flag.
 //   1. gae    -- (bsx_gae_kernel; bsx_gae_stats_kernel with normalisation) one wavefront per 64*W columns.  Each lane loads W columns at a time (f32 x W, u8 x W: 1 KiB / 256 B per wave instruction
 //               at W = 4) and issues the loads of U ticks before the dependent adv chain consumes them.  With normalisation it also
 //               reduces the masked advantages of its tile to (n, mean, M2) in float64 (per-chunk moments merged by Chan's formula, then a
@@ -37,6 +38,7 @@ struct GaeArgs {
     int T, A;
     float gamma, gl;              // gl = gamma * lam, rounded once
     double* part;                 // normalise: workspace [tiles][3] = (n, mean, M2) of each tile's masked advantages
+    const uint8_t* agent_on;      // bsx_gae_agents: [A] flags, 0 = the actor does not play this agent (no decisions); NULL = every agent
 };
 
 __device__ inline uint32_t byte_of(uint32_t b, int j) { return (b >> (8 * j)) & 0xffu; }
@@ -70,6 +72,15 @@ __device__ inline void gae_body(const GaeArgs& p) {
         const int64_t c0 = g * W, e0 = c0 / p.A, e1 = (c0 + W - 1) / p.A;
         const int split = int(e1 * p.A - c0);
         const uint8_t* env_done = p.io.env_done;
+        uint32_t on = 0xffffffffu;                                     // byte j: column j's agent is played by the actor
+        if (p.agent_on) {
+            on = 0u;
+#pragma unroll
+            for (int j = 0; j < W; ++j) {                              // column j's agent: (c0 + j) mod A.  One wrap is enough: c0 mod A + j <= A + 2 < 2A for A >= 4, and at A = 2 c0 (a multiple of the even W) is a multiple of A, so a = j <= 3 < 2A
+                const int a = int(c0 - e0 * p.A) + j;
+                on |= p.agent_on[a >= p.A ? a - p.A : a] != 0 ? 1u << (8 * j) : 0u;
+            }
+        }
         const float gamma = p.gamma, gl = p.gl;
         F vn = reinterpret_cast<const F*>(p.io.last_value)[g];         // value[t+1]; V(obs[T]) at t = T-1
         F an = F(0.0f);                                                // adv[t+1]; 0 at t = T-1
@@ -100,7 +111,7 @@ __device__ inline void gae_body(const GaeArgs& p) {
                     B m = 0;
 #pragma unroll
                     for (int j = 0; j < W; ++j) {
-                        const bool run = (j < split ? d0[k] : d1[k]) == 0 && byte_of(dp[k], j) == 0;
+                        const bool run = (j < split ? d0[k] : d1[k]) == 0 && byte_of(dp[k], j) == 0 && byte_of(on, j) != 0;
                         const bool term = byte_of(dn, j) != 0;
                         const float nv = term ? 0.0f : vn[j];
                         const float anj = term ? 0.0f : an[j];
@@ -229,6 +240,11 @@ int bsx_gae_workspace_bytes(int64_t E, int A, int T, size_t* bytes) {
 }
 
 int bsx_gae(const BsxGaeIo* io, int T, int64_t E, int A, float gamma, float lam, int normalize, void* workspace, double* stats, void* stream) {
+    return bsx_gae_agents(io, nullptr, T, E, A, gamma, lam, normalize, workspace, stats, stream);
+}
+
+int bsx_gae_agents(const BsxGaeIo* io, const uint8_t* agent_on, int T, int64_t E, int A, float gamma, float lam, int normalize, void* workspace,
+                   double* stats, void* stream) {
     if (!io || !io->rew || !io->value || !io->done || !io->env_done || !io->last_value || !io->done_prev || !io->adv || !io->ret || !io->mask)
         return BSX_E_ARG;
     if (T < 1 || T > BSX_MAX_T || bad_team(A) || bad_rate(gamma) || bad_rate(lam)) return BSX_E_ARG;
@@ -239,7 +255,7 @@ int bsx_gae(const BsxGaeIo* io, int T, int64_t E, int A, float gamma, float lam,
         !aligned(io->done_prev, 4) || !aligned(io->mask, 4) || !aligned(workspace, 8) || !aligned(stats, 8)) return BSX_E_ALIGN;
     const int W = width_of(E, A);
     const int64_t tiles = tiles_of(E, A), NW = E * A / W;
-    GaeArgs a{*io, E, NW, T, A, gamma, gamma * lam, static_cast<double*>(workspace)};
+    GaeArgs a{*io, E, NW, T, A, gamma, gamma * lam, static_cast<double*>(workspace), agent_on};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const hipError_t e = W == 4 ? launch_gae<4>(a, tiles, normalize, s) : launch_gae<2>(a, tiles, normalize, s);
     if (e || !normalize) return int(e);

@@ -320,6 +320,11 @@ class PPOLearner:
     norm if asked, steps the optimiser (torch Adam over both networks and, for the Gaussian head, log_std -- ~5 k floats per agent: not
     the hot path) and re-packs the rollout's weights, so that the next run() plays the updated policy.
 
+    A rollout with a scripted opponent (PolicyRollout(opponent=instinct.Team(...))) trains the learned team only: the rollout's mask is 0
+    on every row of a scripted agent, so the head's statistics (n, loss, approx_kl, clip_fraction, ...) and max_grad_norm's global norm
+    are the learned team's, every gradient float of a scripted agent's networks and log_std row is +0, and an update leaves its
+    parameters as they are (an optimiser with weight decay aside).
+
     rollout: a PolicyRollout with sample="categorical" or "gaussian", a value_actor and gae= (ValueError otherwise).  vclip: clip the
     value loss around the rollout's recorded values.  optimizer: any torch optimiser over the parameters, instead of Adam(lr)."""
 

@@ -295,7 +295,9 @@ class PolicyRollout:
                                        # inert call (battle_env.py:303-306) or, with auto_reset, the re-spawn: its row pairs the old
                                        # game's last observation with the new game's first and is not a transition
         ro.adv[t], ro.ret[t], ro.mask[t]  # gae=dict(gamma, lam[, normalize]) with a value_actor: GAE advantages and returns of the
-                                       # rows that are the agent's own decisions (advantage.gae), computed inside the same run
+                                       # rows that are the agent's own decisions (advantage.gae), computed inside the same run.
+                                       # With opponent=, the scripted team's agents have none: mask 0 and adv = ret = +0 on all their
+                                       # rows, and adv_stats / the normalisation cover the learned team alone
         ro.logp[t]                     # sample="categorical" / "gaussian": the log-probability of the action taken
                                        # (learner side: learner.categorical_log_prob / gaussian_log_prob; fused=True = one kernel each way)
 
@@ -423,6 +425,12 @@ class PolicyRollout:
             self._lv_scores = torch.zeros((E, A, 4), dtype=torch.float32, device=dev)      # the actor half of the value pass (not read)
             self._gae_ws = (torch.empty(advantage.workspace_bytes(E, A, T), dtype=torch.uint8, device=dev)
                             if self._gae["normalize"] else None)
+            # a scripted opponent's planes are not the actor's decisions: GAE takes the learned team's flags (advantage.gae(agents=)) --
+            # built here, so that nothing is uploaded while capturing
+            self._gae_agents = None
+            if opponent is not None:
+                self._gae_agents = torch.ones(A, dtype=torch.uint8, device=dev)
+                self._gae_agents[opponent._cols] = 0
         self.obs = torch.empty((T + 1, E, A, D), dtype=torch.float32, device=dev)
         # discrete: 4 action scores, arg-maxed in the step kernel; continuous: [speed, turn, shoot] + one unused column
         self.scores = torch.zeros((T, E, A, 4), dtype=torch.float32, device=dev)
@@ -544,7 +552,8 @@ class PolicyRollout:
         self.fused.forward_into(self.obs[self.T], self._lv_scores, 0.0, seq=0, value=dict(weights=self._value_w, out=self.last_value))
         g = self._gae
         advantage.gae(self.rew, self.value, self.last_value, self._done, self.env_done, self._done_prev, g["gamma"], g["lam"],
-                      normalize=g["normalize"], out=(self.adv, self.ret, self._mask), stats=self.adv_stats, workspace=self._gae_ws)
+                      normalize=g["normalize"], out=(self.adv, self.ret, self._mask), stats=self.adv_stats, workspace=self._gae_ws,
+                      agents=self._gae_agents)
 
     def run(self):
         """T ticks (asynchronous).  Afterwards obs[0..T], scores, rew, done hold this rollout's transitions."""

@@ -415,6 +415,15 @@ int bsx_gae_workspace_bytes(int64_t E, int A, int T, size_t* bytes);
  * sharding has no collective on the step path. */
 int bsx_gae(const BsxGaeIo* io, int T, int64_t E, int A, float gamma, float lam, int normalize, void* workspace, double* stats, void* stream);
 
+/* bsx_gae over the agents the actor plays.  agent_on: uint8 [A] on the device (any alignment), or NULL = bsx_gae itself, bit for bit.
+ * An agent the actor does not play -- agent_on[a] == 0: a scripted opponent's planes, PolicyRollout(opponent=) -- has no decisions:
+ *   m[t] = env_done[t][e] == 0 && (t == 0 ? done_prev : done[t-1]) == 0 && (agent_on == NULL || agent_on[a] != 0)
+ * so adv = ret = +0 and mask = 0 on ALL of its rows, and they are in neither n, mean nor std of normalize = 1 (the statistics and the
+ * scaled advantages are the played agents' alone); the columns with agent_on[a] != 0 are exactly bsx_gae's.  done_prev = done[T-1] is
+ * still written for every column.  Same refusals, launches and workspace as bsx_gae. */
+int bsx_gae_agents(const BsxGaeIo* io, const uint8_t* agent_on, int T, int64_t E, int A, float gamma, float lam, int normalize, void* workspace,
+                   double* stats, void* stream);
+
 /* ---- the training pass of the actor / value MLP (deep-rl-battlespace_amd/learner.py, csrc/bsx_actor_grad.hip): the gradient of
  * L = sum over rows <grad_out, y> in the ten parameter tensors, the forward recomputed in registers -- no activation is saved by
  * bsx_actor_forward and none is read here -- so that a learner's backward over a rollout's records needs one call.

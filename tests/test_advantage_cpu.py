@@ -15,7 +15,7 @@ import torch
 from gae_util import gae_ref, random_case, textbook_gae
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("bsx_gae_workspace_bytes", "bsx_gae")
+NAMES = ("bsx_gae_workspace_bytes", "bsx_gae", "bsx_gae_agents")
 ARG, ALIGN = -1, -2
 P = 4096                      # a 256-byte aligned fake address (never dereferenced)
 
@@ -152,6 +152,74 @@ def test_restatement_normalisation_edge_cases():
     prev[0, 1] = 1
     a, _, m, _, st = gae_ref(rew, value, lv, done, env_done, prev, 0.9, 0.9, normalize=True)
     assert m.sum() == 1 and st[0] == 1 and st[2] == 0 and a[m][0] == 0.0
+
+
+@pytest.mark.parametrize("T,E,A", [(5, 7, 4), (3, 5, 6)])
+def test_restatement_with_agents_flagged_off_gives_them_no_decisions(T, E, A):
+    """gae_ref(agents=f): the flagged-on columns are those of the call without the flag (a column's recurrence reads no other column),
+    the others are all +0 with mask 0, the carry is every column's, and the normalisation is over the flagged-on masked rows alone."""
+    rng = np.random.default_rng(10 * T + A)
+    case = random_case(rng, T, E, A, 0.15, 0.1, 0.2)
+    plain = gae_ref(*case, 0.97, 0.9)
+    irregular = np.array([(7 * a + 3) % 5 < 3 for a in range(A)], np.uint8)
+    for f in (np.array([1] * (A // 2) + [0] * (A // 2), np.uint8), np.array([0] * (A // 2) + [1] * (A // 2), np.uint8), irregular):
+        on = f.astype(bool)
+        assert on.any() and not on.all()
+        a, r, m, c, st = gae_ref(*case, 0.97, 0.9, agents=f)
+        assert st is None and np.array_equal(c, plain[3])                       # the carry is done[T-1] of every column
+        for got, want in ((a, plain[0]), (r, plain[1])):
+            assert np.array_equal(got[..., on].view(np.int32), want[..., on].view(np.int32))
+            assert (got[..., ~on].view(np.int32) == 0).all()                    # +0 bits
+        assert np.array_equal(m[..., on], plain[2][..., on]) and not m[..., ~on].any() and m.any()
+        for kernel_order in (False, True):
+            an, rn, mn, cn, st = gae_ref(*case, 0.97, 0.9, normalize=True, agents=f, kernel_order=kernel_order)
+            x = a[m].astype(np.float64)                                         # the flagged-on masked rows alone
+            assert np.array_equal(mn, m) and np.array_equal(rn, r) and np.array_equal(cn, c)
+            assert st[0] == m.sum() == x.size < plain[2].sum()
+            assert st[1] == pytest.approx(x.mean(), rel=1e-12, abs=1e-15) and st[2] == pytest.approx(x.std(ddof=1), rel=1e-12)
+            assert np.array_equal(an[m], ((x - st[1]) / (st[2] + 1e-8)).astype(np.float32)) and (an[~m].view(np.int32) == 0).all()
+    # all flags set is no flag
+    for got, want in zip(gae_ref(*case, 0.97, 0.9, normalize=True, agents=np.ones(A, np.uint8)), gae_ref(*case, 0.97, 0.9, normalize=True)):
+        assert np.array_equal(got, want)
+
+
+def test_kernel_order_statistics_use_the_kernels_constants_and_stay_numpys_to_rounding():
+    import gae_util
+    src = open(os.path.join(ROOT, "deep-rl-battlespace_amd", "csrc", "bsx_advantage.hip")).read()
+    for name, value in (("WAVE", gae_util.WAVE), ("U", gae_util.U), ("MERGE_TPB", gae_util.MERGE_TPB)):
+        m = re.search(r"constexpr int %s = (\d+);" % name, src)
+        assert m and int(m.group(1)) == value, name
+    rng = np.random.default_rng(5)
+    # more than one chunk of ticks, more than one tile of lanes at both widths, more than one round of the merge (> 256 tiles)
+    for T, E, A in ((19, 70, 6), (9, 300, 2), (3, 33000, 2)):
+        case = random_case(rng, T, E, A)
+        case[0][...] += 0.5
+        adv, _, mask, _, _ = gae_ref(*case, 0.99, 0.95)
+        n, mean, std = gae_util.stats_in_kernel_order(adv, mask)
+        x = adv[mask].astype(np.float64)
+        assert n == x.size and mean == pytest.approx(x.mean(), rel=1e-12) and std == pytest.approx(x.std(ddof=1), rel=1e-12), (T, E, A)
+
+
+def test_gae_agents_is_declared_next_to_bsx_gae_and_bsx_gae_is_that_call_without_the_flag():
+    hdr = open(os.path.join(ROOT, "include", "battlespace_hip.h")).read()
+    m = re.search(r"^int\s+bsx_gae_agents\s*\(([^;]*)\)\s*;", hdr, flags=re.M)
+    assert m and "const uint8_t* agent_on" in m.group(1) and "const BsxGaeIo* io" in m.group(1)
+    assert hdr.index("int bsx_gae(") < m.start()                               # its contract is written next to bsx_gae's
+    L = _lib()
+    sig, plain = L.SIGNATURES["bsx_gae_agents"], L.SIGNATURES["bsx_gae"]
+    assert sig[0] is plain[0] and sig[1] == plain[1][:1] + [ctypes.c_void_p] + plain[1][1:]     # io, agent_on, then bsx_gae's own
+    assert [f for f, _ in L.BsxGaeIo._fields_] == list(IO_FIELDS)               # the struct did not grow: old callers keep working
+    from deep_rl_battlespace_amd.advantage import gae
+    p = inspect.signature(gae).parameters
+    assert p["agents"].kind == p["agents"].KEYWORD_ONLY and p["agents"].default is None
+    # refused before any launch like bsx_gae (fake addresses); an agent_on of any alignment is taken
+    lib = L.load()
+    io = L.BsxGaeIo(*([P] * 9))
+    assert lib.bsx_gae_agents(ctypes.byref(io), P + 1, 0, 64, 2, 0.99, 0.95, 0, None, None, None) == ARG
+    assert lib.bsx_gae_agents(ctypes.byref(io), P + 1, 8, 64, 3, 0.99, 0.95, 0, None, None, None) == ARG
+    assert lib.bsx_gae_agents(None, None, 8, 64, 2, 0.99, 0.95, 0, None, None, None) == ARG
+    io.mask = P + 2
+    assert lib.bsx_gae_agents(ctypes.byref(io), P + 1, 8, 64, 2, 0.99, 0.95, 0, None, None, None) == ALIGN
 
 
 def test_gae_symbols_are_declared_exported_and_bound():

@@ -398,7 +398,7 @@ def test_actor_forward_stays_inside_its_buffers():
                 _assert_same(got, want, (E, n, precision))
 
 
-def _gae(buf, T, E, A, normalize, case):
+def _gae(buf, T, E, A, normalize, case, agents=None):
     L = _L()
     lib = L.load()
     rew, value, done, env_done, lv, prev = (buf(k, v.numel(), v.dtype) for k, v in
@@ -413,8 +413,13 @@ def _gae(buf, T, E, A, normalize, case):
         ws, stats = buf("workspace", nb.value, u8, 0), buf("stats", 3, f64, -7.0)
     io = L.BsxGaeIo(rew.data_ptr(), value.data_ptr(), done.data_ptr(), env_done.data_ptr(), lv.data_ptr(), prev.data_ptr(), adv.data_ptr(),
                     ret.data_ptr(), mask.data_ptr())
-    _ok(lib.bsx_gae(ctypes.byref(io), T, E, A, 0.97, 0.9, normalize, ws.data_ptr() if normalize else None,
-                    stats.data_ptr() if normalize else None, _s()), "bsx_gae")
+    tail = (T, E, A, 0.97, 0.9, normalize, ws.data_ptr() if normalize else None, stats.data_ptr() if normalize else None, _s())
+    if agents is None:
+        _ok(lib.bsx_gae(ctypes.byref(io), *tail), "bsx_gae")
+    else:                                                   # the flags behind ONE pad byte: a byte array takes any alignment
+        on = buf("agent_on", A + 1, u8)[1:]
+        on.copy_(agents)
+        _ok(lib.bsx_gae_agents(ctypes.byref(io), on.data_ptr(), *tail), "bsx_gae_agents")
     return [(k, t.clone()) for k, t in (("adv", adv), ("ret", ret), ("mask", mask), ("done_prev", prev))] + \
         ([("stats", stats)] if normalize else [])
 
@@ -441,3 +446,17 @@ def test_gae_stays_inside_its_buffers_when_columns_are_not_a_multiple_of_four(T)
                 r = {k: v.cpu().numpy() for k, v in got}
                 assert np.array_equal(r["adv"].reshape(T, E, A), adv) and np.array_equal(r["ret"].reshape(T, E, A), ret), (T, E, A)
                 assert np.array_equal(r["mask"].reshape(T, E, A).astype(bool), mask) and np.array_equal(r["done_prev"].reshape(E, A), prev), (T, E, A)
+            # the same call with one team flagged off (bsx_gae_agents): nothing outside the buffers, the restatement's bits
+            flag = torch.tensor([1] * (A // 2) + [0] * (A // 2), dtype=u8)
+            guarded = Buffers(True)
+            got = _gae(guarded, T, E, A, normalize, case, agents=flag)
+            torch.cuda.synchronize()
+            assert not guarded.stray(), ("writes outside the buffers", T, E, A, normalize, "agents", guarded.stray())
+            rew, value, done, env_done, lv, prev = (v.numpy() for v in case)
+            adv, ret, mask, prev, st = gae_ref(rew, value, lv, done, env_done, prev, 0.97, 0.9, bool(normalize), agents=flag.numpy(), kernel_order=True)
+            r = {k: v.cpu().numpy() for k, v in got}
+            assert np.array_equal(r["ret"].reshape(T, E, A).view(np.int32), ret.view(np.int32)), (T, E, A, "agents")
+            assert np.array_equal(r["mask"].reshape(T, E, A).astype(bool), mask) and np.array_equal(r["done_prev"].reshape(E, A), prev), (T, E, A, "agents")
+            assert np.array_equal(r["adv"].reshape(T, E, A).view(np.int32), adv.view(np.int32)), (T, E, A, normalize, "agents")
+            if normalize:                                   # the statistics in the kernel's own merge order: to the bit
+                assert np.array_equal(r["stats"].view(np.int64), st.view(np.int64)), (T, E, A, "agents", r["stats"], st)

@@ -82,6 +82,73 @@ def test_ragged_row_counts_keep_their_guards_overwrite_every_output_and_keep_the
     P.check(_numpy(res), ref, yard, e_stats, e_ls, kind, f"RAGGED {kind} rows={rows} n={n}")
 
 
+# ---------------------------------------------------------------------------------------------------- 2b. inputs off a 16-byte boundary
+def _placed(t, offset, fill):
+    """A device copy of `t` that starts `offset` elements into a 16-byte aligned slab holding `fill` around it."""
+    slab = torch.full((t.numel() + 32,), fill, dtype=t.dtype, device="cuda")
+    assert slab.data_ptr() % 16 == 0
+    view = slab[offset:offset + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() == slab.data_ptr() + offset * t.element_size() and view.is_contiguous()
+    return view
+
+
+def _count_regime(offset, M):
+    """Which parts of bsx_ppo_count_kernel's split see a mask of M bytes that starts `offset` bytes past a 16-byte boundary: the bytes
+    before the first boundary (head, cut to M), whole 16-byte groups (body), the rest (tail) -- its pointer arithmetic restated."""
+    head = (16 - offset % 16) % 16
+    if head > M:
+        return "cut head"                                                # M < head: every byte is a head byte, no boundary is reached
+    groups = (M - head) // 16
+    tail = M - head - 16 * groups
+    return "+".join(name for name, there in (("head", head), ("body", groups), ("tail", tail)) if there)
+
+
+UNALIGNED_ROWS = {1: (1, 3, 7, 9), 3: (1, 3)}                            # n -> rows with M = A rows in {2, 6, 14, 18}
+assert sorted({2 * n * r for n, rs in UNALIGNED_ROWS.items() for r in rs}) == [2, 6, 14, 18]
+
+
+@pytest.mark.parametrize("vold", [True, False], ids=["vclip", "plain"])
+@pytest.mark.parametrize("kind", P.KINDS)
+@pytest.mark.parametrize("shape", [(257, 1), (97, 3)], ids=lambda s: "R%d-n%d" % s)
+def test_records_off_a_sixteen_byte_boundary_give_the_bits_of_fresh_copies(shape, kind, vold):
+    """A learner's minibatch hands the head views of a rollout's records: the float32 [R][A] arrays at any 4-byte offset, the mask at any
+    byte (the header says so).  The mask at every byte offset 0 .. 15 and the floats at every float offset 0 .. 3 of an aligned slab,
+    at the full shape and at M = A R = 2, 6, 14, 18 mask bytes (the count pass's head alone, head and tail, and fewer bytes than its
+    head): every output has the bits of the call on freshly allocated copies, and N is the host's count."""
+    from deep_rl_battlespace_amd.learner import ppo_head
+    n = shape[1]
+    full = P.build(kind, *shape, 0.1)
+    seen = set()
+    for rows in (shape[0],) + UNALIGNED_ROWS[n]:
+        inp = P.head(full, rows)
+        M = rows * 2 * n
+        dev = {k: v.contiguous().to("cuda") for k, v in inp.items()}
+        extra = dict(temperature=P.TAU) if kind == "categorical" else dict(log_std=dev["log_std"])
+
+        def call(t):
+            kw = dict(extra, v_old=t["v_old"], vclip=P.VCLIP) if vold else extra
+            return ppo_head(kind, dev["y"], t["v"], dev["rec"], t["logp_old"], t["adv"], t["ret"], t["mask"], **KW, **kw)
+        want = call(dev)
+        count = int((inp["mask"] != 0).sum())
+        assert float(want.stats[0]) == count
+        for offset in range(16):
+            at = {k: _placed(inp[k].contiguous(), offset % 4, float("nan")) for k in ("v", "logp_old", "adv", "ret", "v_old")}
+            at["mask"] = _placed(inp["mask"].contiguous(), offset, 1)                 # set bytes around it: a byte counted beyond M shows in N
+            assert at["mask"].data_ptr() % 16 == offset and all(at[k].data_ptr() % 16 == 4 * (offset % 4) for k in ("v", "adv"))
+            got = call(at)
+            torch.cuda.synchronize()
+            assert _same_bits(got, want), (rows, offset)
+            assert float(got.stats[0]) == count, (rows, offset)
+            if rows != shape[0]:
+                seen.add((_count_regime(offset, M), M))
+    print(kind, shape, sorted(seen))
+    # by hand: 2 bytes at offset 3 end before the boundary, at 14 on it, at 15 beyond it; 18 bytes at 14 are head and one whole group
+    want = ({("cut head", 2), ("head", 2), ("head+tail", 2), ("tail", 2), ("head", 14), ("head+tail", 14), ("body+tail", 18), ("head+body", 18),
+             ("head+body+tail", 18)} if n == 1 else {("cut head", 6), ("head", 6), ("head+tail", 6), ("tail", 6), ("head+body", 18), ("head+tail", 18)})
+    assert seen >= want, sorted(want - seen)
+
+
 # ---------------------------------------------------------------------------------------------------- 3. the mask
 @pytest.mark.parametrize("kind", P.KINDS)
 def test_masked_out_elements_write_plus_zero_and_reach_nothing_whatever_they_hold(kind):
