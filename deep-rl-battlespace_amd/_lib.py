@@ -73,6 +73,15 @@ class BsxPpoIo(ctypes.Structure):
     _fields_ = [(f, c_void_p) for f in ("y", "v", "rec", "logp_old", "adv", "ret", "mask", "v_old", "log_std", "g_pi", "g_v", "g_log_std")]
 
 
+class BsxAdamNet(ctypes.Structure):
+    _fields_ = [("p", c_void_p * 10), ("grad", c_void_p), ("m", c_void_p), ("v", c_void_p), ("blob", c_void_p), ("n_actions", c_int)]
+
+
+class BsxAdamIo(ctypes.Structure):
+    _fields_ = [("net", BsxAdamNet * 2), ("nets", c_int), ("log_std", c_void_p), ("g_log_std", c_void_p), ("m_ls", c_void_p),
+                ("v_ls", c_void_p), ("hyper", c_void_p), ("step", c_void_p)]
+
+
 # name -> (restype, argtypes): every symbol include/battlespace_hip.h declares
 SIGNATURES = {
     "bsx_abi_version": (c_int, []),
@@ -131,6 +140,8 @@ SIGNATURES = {
     "bsx_ppo_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_ppo_head": (c_int, [ctypes.POINTER(BsxPpoIo), c_int64, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                              ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "bsx_adam_step_workspace_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_adam_step": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -50,7 +50,9 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            # GAE advantages: float32 operations each rounded on their own, as tests/gae_util.py restates them
            (os.path.join(CSRC, "bsx_advantage.hip"), ["-ffp-contract=off"]),
            # the PPO loss head: float32 element-wise terms held to a float64 reference, not to bits: contraction allowed
-           (os.path.join(CSRC, "bsx_ppo_head.hip"), [])]
+           (os.path.join(CSRC, "bsx_ppo_head.hip"), []),
+           # the optimiser step (clip + Adam + pack): float32 element-wise, held to a float64 reference; the blob it packs is bit copies
+           (os.path.join(CSRC, "bsx_adam_step.hip"), [])]
 
 
 def _stale():

@@ -12,7 +12,10 @@ weights.  Deterministic (no floating-point atomics): the same inputs give the sa
   split_grad(row, n_actions)                                    a [A, G] gradient row as the ten parameter shapes (views, no gather)
   ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, ...)      the clipped-surrogate PPO loss between the two: from the forward's outputs
                                                                 and a rollout's records to both grad_out tensors, one pass (bsx_ppo_head)
-  PPOLearner(rollout, ...)                                      minibatch_grads / update: the PPO update of a PolicyRollout's networks
+  AdamState(net_or_log_std), adam_step(nets, grads, states, ...) clip_grad_norm_ + Adam.step() + pack() of one or two networks (and log_std)
+                                                                as two launches: rows in, parameters, moments and packed blobs out (bsx_adam_step)
+  PPOLearner(rollout, ...)                                      minibatch_grads / update: the PPO update of a PolicyRollout's networks;
+                                                                device_step=True: the whole update on device, capture() makes it one graph
 """
 import math
 from collections import namedtuple
@@ -302,6 +305,134 @@ def ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, *, clip, c_v, c_e, tempe
     return PpoHead(g_pi, g_v, g_ls if k == 1 else None, stats)
 
 
+# ------------------------------------------------------------------------------------------------ the optimiser step
+HYPER = ("lr", "beta1", "beta2", "eps", "max_grad_norm", "reserved", "reserved", "reserved")
+ADAM_STATS = ("step", "grad_norm", "clip_coef", "lr")
+
+
+class AdamState:
+    """The Adam moments adam_step keeps for one network or for log_std: `m` and `v`, float32 zeros.  For a StackedActor they are [A, G]
+    rows in bsx_actor_grad's layout (split_grad cuts them into the ten parameter shapes; the pad columns of w3 / b3 stay +0), for a
+    tensor (the Gaussian head's log_std, [A, 3]) they have its shape."""
+
+    def __init__(self, net_or_log_std):
+        x = net_or_log_std
+        if isinstance(x, torch.Tensor):
+            shape, dev = tuple(x.shape), x.device
+        else:
+            shape, dev = (x.n_actors, grad_floats(x.obs_len)), x.w1.device
+        self.m = torch.zeros(shape, dtype=torch.float32, device=dev)
+        self.v = torch.zeros(shape, dtype=torch.float32, device=dev)
+
+
+def adam_hyper(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, device="cuda"):
+    """adam_step's `hyper`: float32 [8] on the device in the order of learner.HYPER; max_grad_norm None (or 0) = no clipping."""
+    lr = _number(lr, "lr", lambda x: x >= 0.0, "a number >= 0")
+    try:
+        b1, b2 = betas
+    except (TypeError, ValueError):
+        raise ValueError(f"betas must be a pair of numbers in [0, 1), got {betas!r}") from None
+    b1 = _number(b1, "betas[0]", lambda x: 0.0 <= x < 1.0, "a number in [0, 1)")
+    b2 = _number(b2, "betas[1]", lambda x: 0.0 <= x < 1.0, "a number in [0, 1)")
+    eps = _number(eps, "eps", lambda x: x >= 0.0, "a number >= 0")
+    mgn = 0.0 if max_grad_norm is None else _number(max_grad_norm, "max_grad_norm", lambda x: x >= 0.0, "a number >= 0")
+    return torch.tensor([lr, b1, b2, eps, mgn, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
+
+
+def adam_step_workspace_bytes(n, nets):
+    """Bytes of the workspace adam_step needs for `nets` networks of 2n agents."""
+    lib, nb = _lib.load(), _lib.c_size_t()
+    _lib.check(lib.bsx_adam_step_workspace_bytes(int(n), int(nets), _lib.ctypes.byref(nb)), "bsx_adam_step_workspace_bytes")
+    return nb.value
+
+
+def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_std=None, log_std_state=None, stats=None, workspace=None):
+    """torch's clip_grad_norm_(params, max_grad_norm) + Adam.step() (no weight decay, no amsgrad) + StackedActor.pack(), as ONE device
+    pass of two launches (csrc/bsx_adam_step.hip, `bsx_adam_step`; the exact contract is written out in include/battlespace_hip.h)
+    -> stats f64 [4] on the device, in the order of learner.ADAM_STATS.
+
+    nets: one or two StackedActors of the same A and D (float32, on one GPU, contiguous parameters): updated in place.  grads: per
+    network the float32 [A, G] gradient row of bsx_actor_grad (fused_grad / PPOLearner.minibatch_grads), read only.  states: per
+    network an AdamState.  blobs: per network a float32 [A, blob floats] tensor that receives, in every float, what net.pack() makes of
+    the updated parameters (a rollout's `fused.weights`).  log_std, g_log_std (float32 [A, 3]) and log_std_state (an AdamState of it):
+    the Gaussian head's, all three or none.  The global norm is taken over everything in the call.
+    hyper: float32 [8] on the device (adam_hyper; learner.HYPER) and step: an int64 device tensor of one element, the steps taken so
+    far, advanced by the call -- both are read on the device at every launch, so a captured call follows a changed learning rate and
+    counts on from replay to replay.  The .grad of the parameters is neither read nor written.  Deterministic; no host synchronisation.
+    stats (f64 [4]) and workspace (at least adam_step_workspace_bytes(n, len(nets)) bytes, 8-byte aligned): pass both and nothing is
+    allocated (a captured graph)."""
+    for name, x in (("nets", nets), ("grads", grads), ("states", states), ("blobs", blobs)):
+        if not isinstance(x, (list, tuple)):
+            raise TypeError(f"{name} must be a list or tuple, one entry per network")
+    if len(nets) not in (1, 2) or not len(nets) == len(grads) == len(states) == len(blobs):
+        raise ValueError("nets, grads, states and blobs must have one entry each for one or two networks")
+    first = nets[0]
+    if not all(hasattr(first, k) for k in PARAMS) or not isinstance(first.w1, torch.Tensor):
+        raise TypeError("nets[0] must be a StackedActor")
+    dev, A, D = first.w1.device, first.n_actors, first.obs_len
+    if dev.type != "cuda":
+        raise ValueError("adam_step runs on the GPU: nets[0].w1 is on " + str(dev))
+    if A < 2 or A % 2 or A > 2 * _lib.MAX_N or D != 3 * (A // 2) + 2:
+        raise ValueError(f"nets[0] has {A} agents and obs_len {D}: an even A in 2 .. {2 * _lib.MAX_N} and D = 3 A / 2 + 2 are needed")
+    G = grad_floats(D)
+    io = _lib.BsxAdamIo()
+    io.nets = len(nets)
+    for i, (net, g, st, blob) in enumerate(zip(nets, grads, states, blobs)):
+        if not all(hasattr(net, k) for k in PARAMS):
+            raise TypeError(f"nets[{i}] must be a StackedActor")
+        if net.n_actors != A or net.obs_len != D:
+            raise ValueError(f"nets[{i}] must have the {A} agents and obs_len {D} of nets[0]")
+        na = net.n_actions
+        if na not in (1, 3, 4):
+            raise ValueError(f"nets[{i}].n_actions must be 1, 3 or 4, got {na}")
+        shapes = [(A, D, H)] + [(A, 1, H)] * 3 + [(A, H, H)] + [(A, 1, H)] * 3 + [(A, H, na), (A, 1, na)]
+        for q, (k, shape) in enumerate(zip(PARAMS, shapes)):
+            _need(getattr(net, k), f"nets[{i}].{k}", shape, _F32, dev)
+            io.net[i].p[q] = getattr(net, k).data_ptr()
+        if not isinstance(st, AdamState):
+            raise TypeError(f"states[{i}] must be an AdamState")
+        _need(g, f"grads[{i}]", (A, G), _F32, dev)
+        _need(st.m, f"states[{i}].m", (A, G), _F32, dev)
+        _need(st.v, f"states[{i}].v", (A, G), _F32, dev)
+        _need(blob, f"blobs[{i}]", (A, blob_floats(D)), _F32, dev)
+        io.net[i].grad, io.net[i].m, io.net[i].v, io.net[i].blob, io.net[i].n_actions = g.data_ptr(), st.m.data_ptr(), st.v.data_ptr(), blob.data_ptr(), na
+    given = [x is not None for x in (log_std, g_log_std, log_std_state)]
+    if any(given) and not all(given):
+        raise ValueError("log_std, g_log_std and log_std_state go together: all three or none")
+    if all(given):
+        if not isinstance(log_std_state, AdamState):
+            raise TypeError("log_std_state must be an AdamState")
+        _need(log_std, "log_std", (A, 3), _F32, dev)
+        _need(g_log_std, "g_log_std", (A, 3), _F32, dev)
+        _need(log_std_state.m, "log_std_state.m", (A, 3), _F32, dev)
+        _need(log_std_state.v, "log_std_state.v", (A, 3), _F32, dev)
+        io.log_std, io.g_log_std, io.m_ls, io.v_ls = log_std.data_ptr(), g_log_std.data_ptr(), log_std_state.m.data_ptr(), log_std_state.v.data_ptr()
+    _need(hyper, "hyper", (8,), _F32, dev)
+    if not isinstance(step, torch.Tensor):
+        raise TypeError("step must be a torch.Tensor")
+    _need(step, "step", tuple(step.shape) if step.numel() == 1 else (1,), (torch.int64,), dev)
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float64, device=dev)
+    _need(stats, "stats", (4,), (torch.float64,), dev)
+    nb = adam_step_workspace_bytes(A // 2, len(nets))
+    if workspace is None:
+        workspace = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+    if (not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous()
+            or workspace.numel() * workspace.element_size() < nb):
+        raise ValueError(f"workspace must be a contiguous tensor of at least {nb} bytes on {dev}")
+    io.hyper, io.step = hyper.data_ptr(), step.data_ptr()
+    _lib.check(_lib.load().bsx_adam_step(_lib.ctypes.byref(io), A // 2, workspace.data_ptr(), stats.data_ptr(),
+                                         torch.cuda.current_stream(dev).cuda_stream), "bsx_adam_step")
+    return stats
+
+
+def blob_floats(obs_len):
+    """Floats per agent of the packed blob bsx_actor_forward reads (StackedActor.pack()): bsx_actor_blob_floats."""
+    nf = _lib.c_int()
+    _lib.check(_lib.load().bsx_actor_blob_floats(int(obs_len), _lib.ctypes.byref(nf)), "bsx_actor_blob_floats")
+    return nf.value
+
+
 class PPOLearner:
     """The PPO update of a PolicyRollout's two networks, on device:
 
@@ -325,10 +456,22 @@ class PPOLearner:
     are the learned team's, every gradient float of a scripted agent's networks and log_std row is +0, and an update leaves its
     parameters as they are (an optimiser with weight decay aside).
 
-    rollout: a PolicyRollout with sample="categorical" or "gaussian", a value_actor and gae= (ValueError otherwise).  vclip: clip the
-    value loss around the rollout's recorded values.  optimizer: any torch optimiser over the parameters, instead of Adam(lr)."""
+    device_step=True: the optimiser step is adam_step (bsx_adam_step) -- clipping, Adam(lr, betas, eps) and both packs in two launches
+    that take the gradient rows as they are.  update() then calls neither install, torch's clipping, a torch optimiser nor pack(): a
+    minibatch is five calls (ten launches), nothing is allocated from the second update on, and the parameters' .grad stays unset (None) on this
+    path.  The blobs the step writes are the rollout's own (ro.fused.weights, ro._value_w), which minibatch_grads reads as well, so the
+    next run() plays the updated policy with no refresh.  The learning rate and the step count live on the device (`hyper`,
+    `step_count`): set_lr(x) changes the rate without a host synchronisation, `step_stats` (f64 [epochs * minibatches, 4], columns in the
+    order of learner.ADAM_STATS) records step, gradient norm, clip coefficient and lr of every step.  A caller who edits the parameters
+    from outside calls sync() to re-pack both blobs.  capture() records the whole update -- epochs x minibatches steps -- as ONE graph
+    on one stream; update() replays it from then on.
 
-    def __init__(self, rollout, *, clip=0.2, c_v=0.5, c_e=0.01, vclip=None, epochs=4, minibatches=4, lr=3e-4, max_grad_norm=None, optimizer=None):
+    rollout: a PolicyRollout with sample="categorical" or "gaussian", a value_actor and gae= (ValueError otherwise).  vclip: clip the
+    value loss around the rollout's recorded values.  optimizer: any torch optimiser over the parameters, instead of Adam(lr, betas, eps)
+    (a ValueError with device_step=True)."""
+
+    def __init__(self, rollout, *, clip=0.2, c_v=0.5, c_e=0.01, vclip=None, epochs=4, minibatches=4, lr=3e-4, max_grad_norm=None, optimizer=None,
+                 device_step=False, betas=(0.9, 0.999), eps=1e-8):
         ro = rollout
         if getattr(ro, "_sample", None) is None and getattr(ro, "_gauss", None) is None:
             raise ValueError("PPOLearner needs a PolicyRollout with sample='categorical' or 'gaussian' (it reads the recorded logp)")
@@ -352,9 +495,22 @@ class PPOLearner:
         self.params = [getattr(self.actor, k) for k in PARAMS] + [getattr(self.critic, k) for k in PARAMS]
         if self.log_std is not None:
             self.params.append(self.log_std)
-        self.optimizer = optimizer if optimizer is not None else torch.optim.Adam(self.params, lr=lr)
         dev = ro.obs.device
-        self._blob_a, self._blob_v = torch.empty_like(ro.fused.weights), torch.empty_like(ro._value_w)
+        self.device_step, self._graph = bool(device_step), None
+        if self.device_step:
+            if optimizer is not None:
+                raise ValueError("device_step=True steps with bsx_adam_step: an optimizer= cannot be used with it")
+            self.optimizer = None
+            self.hyper = adam_hyper(lr, betas, eps, self.max_grad_norm, dev)
+            self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.adam_a, self.adam_v = AdamState(self.actor), AdamState(self.critic)
+            self.adam_ls = AdamState(self.log_std) if self.log_std is not None else None
+            self.step_stats = torch.zeros((epochs * minibatches, 4), dtype=torch.float64, device=dev)
+            self._adam_ws = torch.empty((adam_step_workspace_bytes(self.actor.n_actors // 2, 2) + 7) // 8, dtype=torch.int64, device=dev)
+            self._blob_a, self._blob_v = ro.fused.weights, ro._value_w       # the step packs into the blobs the rollout plays from
+        else:
+            self.optimizer = optimizer if optimizer is not None else torch.optim.Adam(self.params, lr=lr, betas=betas, eps=eps)
+            self._blob_a, self._blob_v = torch.empty_like(ro.fused.weights), torch.empty_like(ro._value_w)
         self._by_rows = {}
         self.stats = torch.zeros((epochs * minibatches, 8), dtype=torch.float64, device=dev)
 
@@ -369,10 +525,12 @@ class PPOLearner:
                                     ws=torch.empty((ppo_head_workspace_bytes(R, A) + 7) // 8, dtype=torch.int64, device=dev))
         return self._by_rows[R]
 
-    def minibatch_grads(self, t0, t1):
+    def minibatch_grads(self, t0, t1, pack=True, stats=None):
         """The loss of ticks [t0, t1) of the rollout's current records under the CURRENT parameters -> (actor row [A, G], critic row
         [A, G], g_log_std [A, 3] or None, stats f64 [8]): the rows in bsx_actor_grad's layout (split_grad cuts them), all four cached
-        buffers that the next call with the same tick count overwrites."""
+        buffers that the next call with the same tick count overwrites.  pack=False: the learner's blobs already hold the current
+        parameters (adam_step wrote them) -- three launches fewer and no temporaries.  stats: an f64 [8] tensor the head writes
+        instead of the cached one."""
         ro, lib = self.rollout, _lib.load()
         t0, t1 = int(t0), int(t1)
         if not 0 <= t0 < t1 <= ro.T:
@@ -381,8 +539,9 @@ class PPOLearner:
         n, R, dev = A // 2, (t1 - t0) * E, ro.obs.device
         b = self._head_buffers(R)
         obs = ro.obs[t0:t1].view(R, A, D)
-        self.actor.pack(out=self._blob_a)
-        self.critic.pack(out=self._blob_v)
+        if pack:
+            self.actor.pack(out=self._blob_a)
+            self.critic.pack(out=self._blob_v)
         nz = _lib.BsxActorNoise()
         nz.value_weights, nz.value = self._blob_v.data_ptr(), b["v"].data_ptr()
         _lib.check(lib.bsx_actor_forward(self._blob_a.data_ptr(), obs.data_ptr(), b["y"].data_ptr(), R, n, _lib.ACTOR_F32, _lib.ctypes.byref(nz),
@@ -391,7 +550,7 @@ class PPOLearner:
         head = ppo_head(self.kind, b["y"], b["v"], flat(ro.scores), flat(ro.logp), flat(ro.adv), flat(ro.ret), flat(ro._mask),
                         clip=self.clip, c_v=self.c_v, c_e=self.c_e, temperature=self.temperature, log_std=self.log_std,
                         v_old=flat(ro.value) if self.vclip is not None else None, vclip=self.vclip,
-                        out=(b["g_pi"], b["g_v"], b["g_ls"], b["stats"]), workspace=b["ws"])
+                        out=(b["g_pi"], b["g_v"], b["g_ls"], b["stats"] if stats is None else stats), workspace=b["ws"])
         # the head's outputs ARE bsx_actor_grad's grad_out (four columns, the unused ones +0): fused_grad's call without its padded copy
         row_a = _actor_grad(lib, _buffers(self.actor).get(R, n, dev, lib, go=False), self._blob_a, obs, head.g_pi, True)
         row_v = _actor_grad(lib, _buffers(self.critic).get(R, n, dev, lib, go=False), self._blob_v, obs, head.g_v, False)
@@ -415,6 +574,12 @@ class PPOLearner:
         """epochs x minibatches optimiser steps over the rollout's current records, the minibatches in tick order in every epoch; then the
         rollout's packed weights are refreshed.  -> stats f64 [epochs * minibatches, 8] on the device (a cached buffer; no host sync)."""
         ro = self.rollout
+        if self.device_step:
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self._device_update()
+            return self.stats
         span, i = ro.T // self.minibatches, 0
         for _ in range(self.epochs):
             for m in range(self.minibatches):
@@ -428,3 +593,59 @@ class PPOLearner:
         ro.fused.refresh()
         self.critic.pack(out=ro._value_w)
         return self.stats
+
+    # -------------------------------------------------------------------------------------------- device_step=True
+    def _need_device_step(self, what):
+        if not self.device_step:
+            raise ValueError(f"{what} needs PPOLearner(device_step=True)")
+
+    def _device_update(self):
+        """epochs x minibatches times: the five-launch minibatch on the blobs as they stand, the head's statistics straight into
+        stats[i], then adam_step on the rows.  Cached buffers only; no host synchronisation."""
+        span, i = self.rollout.T // self.minibatches, 0
+        ls = self.log_std
+        for _ in range(self.epochs):
+            for m in range(self.minibatches):
+                row_a, row_v, g_ls, _ = self.minibatch_grads(m * span, (m + 1) * span, pack=False, stats=self.stats[i])
+                adam_step([self.actor, self.critic], [row_a, row_v], [self.adam_a, self.adam_v], [self._blob_a, self._blob_v], self.hyper,
+                          self.step_count, log_std=ls, g_log_std=g_ls if ls is not None else None, log_std_state=self.adam_ls,
+                          stats=self.step_stats[i], workspace=self._adam_ws)
+                i += 1
+
+    def _state(self):
+        """Every tensor an update writes that outlives it."""
+        out = list(self.params) + [self.adam_a.m, self.adam_a.v, self.adam_v.m, self.adam_v.v, self.step_count, self._blob_a, self._blob_v,
+                                   self.stats, self.step_stats]
+        if self.adam_ls is not None:
+            out += [self.adam_ls.m, self.adam_ls.v]
+        return out
+
+    def set_lr(self, lr):
+        """The learning rate of the steps from now on, written to `hyper` on the device (a fill on the current stream: no host
+        synchronisation); a captured update reads it at every replay."""
+        self._need_device_step("set_lr")
+        self.hyper[0].fill_(_number(lr, "lr", lambda x: x >= 0.0, "a number >= 0"))
+
+    def sync(self):
+        """Re-pack both blobs from the parameters, once: for a caller who has edited the parameters from outside (loaded a checkpoint)."""
+        self._need_device_step("sync")
+        self.actor.pack(out=self._blob_a)
+        self.critic.pack(out=self._blob_v)
+
+    def capture(self):
+        """Record the whole update() -- epochs x minibatches minibatches and steps -- as one graph on one stream; update() replays it from
+        then on.  One eager update runs first as the warm-up (buffers, kernel modules) and is undone: capture() leaves parameters,
+        moments, step count, blobs and statistics bit for bit as they were."""
+        self._need_device_step("capture")
+        dev = self.rollout.obs.device
+        with torch.no_grad():
+            keep = [t.detach().clone() for t in self._state()]
+            self._device_update()
+            for t, k in zip(self._state(), keep):
+                t.detach().copy_(k)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._device_update()
+        self._graph = graph
+        return self

@@ -526,6 +526,69 @@ int bsx_ppo_head_workspace_bytes(int64_t R, int A, size_t* bytes);
 int bsx_ppo_head(const BsxPpoIo* io, int64_t R, int A, int kind, float temperature, float clip, float vclip, float c_v, float c_e,
                  void* workspace, double* stats, void* stream);
 
+/* ---- the optimiser step (deep-rl-battlespace_amd/learner.py: adam_step, PPOLearner(device_step=True); csrc/bsx_adam_step.hip): torch's
+ * clip_grad_norm_(params, max_grad_norm) followed by Adam.step() (no weight decay, no amsgrad) over one or two StackedActor networks and,
+ * optionally, the Gaussian head's log_std -- from the gradient rows bsx_actor_grad writes to updated parameters, Adam moments and the packed
+ * weight blobs bsx_actor_forward reads.  A = 2n agents, D = 3n + 2, G = bsx_actor_grad_floats(D).  Per network:
+ *   p[10]      float32, contiguous, the parameters in the order w1 b1 g1 h1 w2 b2 g2 h2 w3 b3 (learner.PARAMS) and StackedActor's shapes:
+ *              [A][D][64], [A][1][64] x 3, [A][64][64], [A][1][64] x 3, [A][64][n_actions], [A][1][n_actions]; updated in place
+ *   grad       float32 [A][G], read only: bsx_actor_grad's row (w1[D][64] | b1 | g1 | h1 | w2[64][64] | b2 | g2 | h2 | w3[64][4] | b3[4]);
+ *              columns n_actions..3 of w3 / b3 have no parameter behind them: they are not read
+ *   m, v       float32 [A][G], the Adam moments in the same layout, updated in place; the pad columns of w3 / b3 are not touched (they stay +0)
+ *   blob       float32 [A][bsx_actor_blob_floats(D)] (out): EVERY float is written -- W1A with its zero pad row when D is odd, W2A, the six
+ *              vectors, W3P / b3 with zero pad columns, W2B's three bfloat16 terms (round to nearest even, residuals in float32): bit for bit
+ *              what StackedActor.pack() makes of the updated parameters
+ *   n_actions  1, 3 or 4
+ * and once per call:
+ *   log_std, g_log_std (read only), m_ls, v_ls   float32 [A][3] each, or all four NULL
+ *   hyper      float32 [8] on the device: lr, beta1, beta2, eps, max_grad_norm (0 = no clipping), three reserved floats
+ *   step       int64 on the device: the number of steps taken so far; the call stores step + 1
+ * hyper and step are READ ON THE DEVICE at every launch (as log_std is by the rollout): a captured graph follows a learning-rate schedule
+ * and its step count advances from replay to replay. */
+typedef struct BsxAdamNet {
+    float* p[10];
+    const float* grad;
+    float* m;
+    float* v;
+    float* blob;
+    int n_actions;
+} BsxAdamNet;
+
+typedef struct BsxAdamIo {
+    BsxAdamNet net[2];
+    int nets;                  /* 1 or 2: net[1] is not read with 1 */
+    float* log_std;
+    const float* g_log_std;
+    float* m_ls;
+    float* v_ls;
+    const float* hyper;
+    int64_t* step;
+} BsxAdamIo;
+
+/* Size of bsx_adam_step's workspace: eight float64 scalars of the call and one float64 partial norm per (network, agent) row and for
+ * log_std.  BSX_E_ARG: null bytes, n out of 1 .. BSX_MAX_N, nets other than 1 or 2. */
+int bsx_adam_step_workspace_bytes(int n, int nets, size_t* bytes);
+
+/* norm = the 2-norm over every parameter element of the call (both networks and log_std): a float64 sum of the squares of the float32
+ *   gradients in a fixed order -- per workgroup (one per row) per thread over a fixed stride, a shuffle tree, the waves in order; then the
+ *   workgroups' partials by one fixed tree.  No floating-point atomics: the same inputs give the same bits on every call.
+ * coef = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1, in float64, applied as a float32 (coef = 1 leaves every gradient bit)
+ * t = step + 1, stored to step;  the two bias corrections 1 - beta1^t and 1 - beta2^t are formed in float64 ONCE per call, from the float32
+ *   hyper values: step_size = float32(lr / (1 - beta1^t)), c2 = float32(sqrt(1 - beta2^t)); 1 - beta1 and 1 - beta2 likewise
+ * per element, float32 (contraction to fused multiply-adds allowed), g = coef grad:
+ *   m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g g;   p = p - step_size (m / (sqrt(v) / c2 + eps))
+ *   (an element with grad = m = v = +0 keeps p, m and v bit for bit)
+ * stats[4] (device, float64): t, norm, coef, lr.
+ * Two launches on `stream`: the partial norms (workgroup 0 also advances `step` and leaves the call's scalars in the workspace), then the
+ * apply / pack pass, one workgroup per row, each of which adds the at most 65 partials in the same order -- a merge launch of its own
+ * would only add latency.  No host synchronisation: capturable in a HIP graph.
+ * workspace: 8-byte aligned, at least bsx_adam_step_workspace_bytes(n, nets), not in use by another call in flight; stats: 8-byte aligned.
+ * Refusals, before any launch, in this order: BSX_E_ARG for a null io, workspace, stats, hyper or step; n out of 1 .. BSX_MAX_N; nets other
+ * than 1 or 2; per network a null parameter, grad, m, v or blob or an n_actions other than 1, 3, 4; some but not all of log_std, g_log_std,
+ * m_ls, v_ls null.  Then BSX_E_ALIGN for a parameter off a 4-byte boundary; grad, m, v or blob (the row bases) off a 16-byte one; log_std,
+ * g_log_std, m_ls, v_ls or hyper off a 4-byte one; step, workspace or stats off an 8-byte one. */
+int bsx_adam_step(const BsxAdamIo* io, int n, void* workspace, double* stats, void* stream);
+
 /* Host helper: the call number on which the time-limit tie fires for n-per-team -- the reference accumulates
  * total_time += 0.1 in binary64 and compares >= 10+2n (battle_env.py:168,316-319): 121, 141, 161, 181, 200 ... */
 int bsx_tie_tick(int n);

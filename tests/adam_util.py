@@ -1,0 +1,101 @@
+"""What the tests of the fused optimiser step (learner.adam_step, csrc/bsx_adam_step.hip) share:
+
+  reference_step     the contract of include/battlespace_hip.h (bsx_adam_step) restated in float64 numpy: torch's clip_grad_norm_ followed
+                     by Adam.step(), no weight decay, no amsgrad, over a flat list of arrays
+  hyper32            hyperparameters as the float32 values the device reads (`hyper` is a float32 tensor): the restatement, torch's own
+                     float32 Adam and the kernel are all given exactly these numbers
+  row_to_tensors / tensors_to_row   a [A, G] row in bsx_actor_grad's layout <-> the ten parameter shapes of a StackedActor
+  random_rows        gradient rows with magnitudes spread over 1e-4 .. 1, the pad columns of w3 / b3 at +0
+  pooled_errors      mean and maximum |x - reference| over a network's ten tensors as ONE vector (the step is element-wise: a
+                     per-tensor maximum over the eight floats of a b3 is noise)
+"""
+import numpy as np
+import torch
+
+PARAMS = ("w1", "b1", "g1", "h1", "w2", "b2", "g2", "h2", "w3", "b3")
+H = 64
+
+
+def grad_floats(D):
+    return H * D + H * H + 6 * H + H * 4 + 4
+
+
+def hyper32(lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=0.0):
+    """dict of Python floats that are exactly representable in float32: what the device reads from `hyper`."""
+    f = lambda x: float(np.float32(x))     # noqa: E731
+    return dict(lr=f(lr), beta1=f(beta1), beta2=f(beta2), eps=f(eps), max_grad_norm=f(max_grad_norm))
+
+
+def reference_step(params, grads, m, v, t, hp):
+    """One step in float64.  params, grads, m, v: lists of numpy arrays of matching shapes (any float dtype: converted); t: the steps
+    taken so far; hp: hyper32(...) -> (params, m, v, t + 1, norm, coef), new arrays.
+      norm = sqrt(sum of g^2 over everything);  coef = min(1, max_norm / (norm + 1e-6)) (1 with max_norm = 0);  g = coef grad
+      m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps),  t the NEW count"""
+    lr, b1, b2, eps, mx = hp["lr"], hp["beta1"], hp["beta2"], hp["eps"], hp["max_grad_norm"]
+    g64 = [np.asarray(g, np.float64) for g in grads]
+    norm = float(np.sqrt(sum(float((g * g).sum()) for g in g64)))
+    coef = min(1.0, mx / (norm + 1e-6)) if mx > 0.0 else 1.0
+    t = int(t) + 1
+    step_size, c2 = lr / (1.0 - b1 ** t), np.sqrt(1.0 - b2 ** t)
+    P, M, V = [], [], []
+    for p, g, m_, v_ in zip(params, g64, m, v):
+        g = coef * g
+        mn = b1 * np.asarray(m_, np.float64) + (1.0 - b1) * g
+        vn = b2 * np.asarray(v_, np.float64) + (1.0 - b2) * g * g
+        P.append(np.asarray(p, np.float64) - step_size * mn / (np.sqrt(vn) / c2 + eps))
+        M.append(mn)
+        V.append(vn)
+    return P, M, V, t, norm, coef
+
+
+def row_to_tensors(row, n_actions):
+    """row [A, G] (numpy or torch, bsx_actor_grad's layout: w1[D][64] | b1 | g1 | h1 | w2[64][64] | b2 | g2 | h2 | w3[64][4] | b3[4]) -> the ten
+    arrays in PARAMS order in a StackedActor's shapes, w3 / b3 cut to n_actions columns (contiguous copies)."""
+    A, G = row.shape
+    D = (G - grad_floats(0)) // H
+    assert grad_floats(D) == G, G
+    out, o = [], 0
+    for k in PARAMS:
+        shape = dict(w1=(D, H), w2=(H, H), w3=(H, 4), b3=(1, 4)).get(k, (1, H))
+        n = shape[0] * shape[1]
+        x = row[:, o:o + n].reshape(A, *shape)
+        o += n
+        if k in ("w3", "b3"):
+            x = x[:, :, :n_actions]
+        out.append(x.copy() if isinstance(x, np.ndarray) else x.contiguous().clone())
+    assert o == G
+    return out
+
+
+def tensors_to_row(tensors):
+    """The inverse: ten numpy arrays -> a float64 [A, G] row, the pad columns of w3 / b3 at 0."""
+    A = tensors[0].shape[0]
+    cols = []
+    for k, x in zip(PARAMS, tensors):
+        x = np.asarray(x, np.float64)
+        if k in ("w3", "b3") and x.shape[2] < 4:
+            x = np.concatenate([x, np.zeros((A, x.shape[1], 4 - x.shape[2]))], axis=2)
+        cols.append(x.reshape(A, -1))
+    return np.concatenate(cols, axis=1)
+
+
+def random_rows(A, D, n_actions, gen, scale=1.0):
+    """float32 [A, G] on the CPU: sign * 10^U(-4, 0) * scale per element, +0 in the pad columns of w3 / b3.  gen: a torch.Generator."""
+    G = grad_floats(D)
+    mag = torch.pow(10.0, -4.0 * torch.rand((A, G), generator=gen, dtype=torch.float64))
+    sign = torch.where(torch.rand((A, G), generator=gen) < 0.5, -1.0, 1.0).double()
+    row = (scale * sign * mag).float()
+    tail = row[:, G - (H * 4 + 4):].view(A, H + 1, 4)
+    tail[:, :, n_actions:] = 0.0
+    return row
+
+
+def net_arrays(net):
+    """A StackedActor's ten parameters as float32 numpy arrays (copies)."""
+    return [getattr(net, k).detach().cpu().numpy().copy() for k in PARAMS]
+
+
+def pooled_errors(got, ref):
+    """got, ref: lists of arrays of matching shapes -> (mean, max) of |got - ref| over all of them as one vector (float64)."""
+    d = np.concatenate([np.abs(np.asarray(g, np.float64) - np.asarray(r, np.float64)).ravel() for g, r in zip(got, ref)])
+    return float(d.mean()), float(d.max())

@@ -1,0 +1,324 @@
+"""The fused optimiser step on the GPU (learner.adam_step, csrc/bsx_adam_step.hip): the blob it packs against StackedActor.pack() bit for
+bit, its arithmetic against the float64 restatement of tests/adam_util.py with torch's own float32 clip_grad_norm_ + Adam as the
+yardstick, its statistics, determinism, guard words and the agent whose gradient is zero.
+
+Shapes, the smallest that reach every layout case: n = 1 (D = 5, odd: W1A has a pad row), n = 2 (D = 8), n = 3 with a 3-column actor and
+log_std, n = 16 (A = 32, D = 50), each with a 1-column value network beside the policy network, and one single-network call."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import adam_util as U
+import guard_util as GU
+
+pytestmark = pytest.mark.gpu
+
+#        id            n  n_actions log_std value net
+CONFIGS = {"n1": (1, 4, False, True), "n2": (2, 4, False, True), "n3-gaussian": (3, 3, True, True), "n16": (16, 4, False, True),
+           "n2-single": (2, 4, False, False)}
+STEPS = 5
+
+
+class Case:
+    """One or two networks, their Adam state, blobs (pre-filled with a non-zero pattern), log_std, hyper, counter, stats and workspace on
+    the GPU.  alloc: a guard_util.Buffers -- every buffer the step writes is then a view between guard bytes."""
+
+    def __init__(self, config, hp, seed=0, alloc=None):
+        from deep_rl_battlespace_amd import learner
+        from deep_rl_battlespace_amd.rollout import StackedActor
+        n, na, with_ls, with_value = CONFIGS[config]
+        self.n, self.A, self.D = n, 2 * n, 3 * n + 2
+        A, D = self.A, self.D
+        alloc = alloc or GU.Buffers(False)
+        torch.manual_seed(100 + seed)
+        self.nets = [StackedActor(A, D, na, device="cuda")] + ([StackedActor(A, D, 1, device="cuda")] if with_value else [])
+        self.states, self.blobs = [], []
+        for i, net in enumerate(self.nets):
+            for k in U.PARAMS:                                              # the parameters as views of the allocator's buffers
+                p = getattr(net, k)
+                buf = alloc(f"net{i}.{k}", p.shape, torch.float32)
+                buf.copy_(p.detach())
+                setattr(net, k, torch.nn.Parameter(buf))
+                assert getattr(net, k).data_ptr() == buf.data_ptr()
+            st = learner.AdamState(net)
+            st.m, st.v = alloc(f"net{i}.m", st.m.shape, torch.float32), alloc(f"net{i}.v", st.v.shape, torch.float32)
+            self.states.append(st)
+            self.blobs.append(alloc(f"net{i}.blob", (A, learner.blob_floats(D)), torch.float32, init=-7.25))
+        self.log_std = self.ls_state = None
+        if with_ls:
+            self.log_std = alloc("log_std", (A, 3), torch.float32, init=-0.5)
+            self.ls_state = learner.AdamState(self.log_std)
+            self.ls_state.m, self.ls_state.v = alloc("ls.m", (A, 3), torch.float32), alloc("ls.v", (A, 3), torch.float32)
+        self.hyper = learner.adam_hyper(hp["lr"], (hp["beta1"], hp["beta2"]), hp["eps"], hp["max_grad_norm"])
+        self.step = alloc("step", (1,), torch.int64)
+        self.stats = alloc("stats", (4,), torch.float64, init=-1)
+        nb = learner.adam_step_workspace_bytes(n, len(self.nets))
+        self.ws = alloc("ws", ((nb + 7) // 8,), torch.int64)
+
+    def draw(self, gen, scale=1.0):
+        """Fresh gradients on the GPU: one row per network, and log_std's."""
+        rows = [U.random_rows(self.A, self.D, net.n_actions, gen, scale).cuda() for net in self.nets]
+        g_ls = (scale * torch.randn((self.A, 3), generator=gen)).cuda() if self.log_std is not None else None
+        return rows, g_ls
+
+    def run(self, rows, g_ls):
+        from deep_rl_battlespace_amd import learner
+        return learner.adam_step(self.nets, rows, self.states, self.blobs, self.hyper, self.step, log_std=self.log_std, g_log_std=g_ls,
+                                 log_std_state=self.ls_state, stats=self.stats, workspace=self.ws)
+
+    def tensors(self):
+        """Everything the step writes, by name."""
+        out = {"step": self.step, "stats": self.stats}
+        for i, (net, st, blob) in enumerate(zip(self.nets, self.states, self.blobs)):
+            out.update({f"net{i}.{k}": getattr(net, k).detach() for k in U.PARAMS})
+            out.update({f"net{i}.m": st.m, f"net{i}.v": st.v, f"net{i}.blob": blob})
+        if self.log_std is not None:
+            out.update({"log_std": self.log_std, "ls.m": self.ls_state.m, "ls.v": self.ls_state.v})
+        return out
+
+    def bits(self):
+        torch.cuda.synchronize()
+        return {k: v.clone().view(torch.int32 if v.element_size() == 4 else torch.int64) for k, v in self.tensors().items()}
+
+    def groups(self):
+        """Per network (params, m, v) as lists of numpy arrays in ten-tensor shapes; log_std rides with the policy network."""
+        out = []
+        for i, (net, st) in enumerate(zip(self.nets, self.states)):
+            P = U.net_arrays(net)
+            M, V = U.row_to_tensors(st.m.cpu().numpy(), net.n_actions), U.row_to_tensors(st.v.cpu().numpy(), net.n_actions)
+            if i == 0 and self.log_std is not None:
+                P.append(self.log_std.cpu().numpy().copy()); M.append(self.ls_state.m.cpu().numpy().copy()); V.append(self.ls_state.v.cpu().numpy().copy())
+            out.append((P, M, V))
+        return out
+
+
+def _same_bits(a, b):
+    return [k for k in a if not torch.equal(a[k], b[k])]
+
+
+def _blobs_are_packs(case, where):
+    for i, (net, blob) in enumerate(zip(case.nets, case.blobs)):
+        want = net.pack()
+        assert blob.shape == want.shape
+        bad = (blob.view(torch.int32) != want.view(torch.int32)).nonzero()
+        assert bad.numel() == 0, (where, i, bad[:4].tolist())
+
+
+def _flat_split(case, rows, g_ls):
+    """The call's gradients as one list per network in ten-tensor shapes (torch, GPU), log_std's with the policy network."""
+    out = []
+    for i, (net, row) in enumerate(zip(case.nets, rows)):
+        g = U.row_to_tensors(row, net.n_actions)
+        if i == 0 and g_ls is not None:
+            g.append(g_ls.clone())
+        out.append(g)
+    return out
+
+
+class TorchPath:
+    """torch's float32 clip_grad_norm_ + Adam on the GPU over copies of a case's parameters: the yardstick."""
+
+    def __init__(self, case, hp, t0):
+        self.hp = hp
+        self.params = []
+        for i, net in enumerate(case.nets):
+            ps = [getattr(net, k).detach().clone().requires_grad_() for k in U.PARAMS]
+            if i == 0 and case.log_std is not None:
+                ps.append(case.log_std.clone().requires_grad_())
+            self.params.append(ps)
+        self.flat = [p for ps in self.params for p in ps]
+        self.opt = torch.optim.Adam(self.flat, lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
+        for p in self.flat:
+            self.opt.state[p] = dict(step=torch.tensor(float(t0)), exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
+
+    def set_counter(self, t):
+        for p in self.flat:
+            self.opt.state[p]["step"].fill_(float(t))
+
+    def step(self, grads):
+        for ps, gs in zip(self.params, grads):
+            for p, g in zip(ps, gs):
+                p.grad = g.clone()
+        if self.hp["max_grad_norm"] > 0.0:
+            torch.nn.utils.clip_grad_norm_(self.flat, self.hp["max_grad_norm"])
+        self.opt.step()
+
+    def groups(self):
+        f = lambda x: x.detach().cpu().numpy()     # noqa: E731
+        return [([f(p) for p in ps], [f(self.opt.state[p]["exp_avg"]) for p in ps], [f(self.opt.state[p]["exp_avg_sq"]) for p in ps])
+                for ps in self.params]
+
+
+def _record(config, leg, ratios):
+    """BSX_ADAM_RATIOS_OUT=<file>: append the measured ratios as one JSON line (how profiles/adam_step.json's accuracy table is made)."""
+    print(f"adam_step {config} {leg}: " + ", ".join(f"{k} {m:.3f}/{x:.3f}" for k, (m, x) in sorted(ratios.items())))
+    path = os.environ.get("BSX_ADAM_RATIOS_OUT")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps(dict(config=config, leg=leg, ratios={k: [round(m, 4), round(x, 4)] for k, (m, x) in ratios.items()})) + "\n")
+
+
+#       leg                lr     counter set to (before step index)   what it shows
+LEGS = {"lr3e-4-from-0": (3e-4, {}),                                 # the usual start: bias corrections far from 1
+        "counter-1000-after-3": (3e-4, {3: 1000}),                   # ... and then near 1: b^t through a large t
+        "lr0.05-counter-1000": (0.05, {0: 1000})}                    # a parameter-sized step: the step's own arithmetic shows
+
+
+@pytest.mark.parametrize("leg", list(LEGS))
+@pytest.mark.parametrize("config", list(CONFIGS))
+def test_five_steps_match_the_float64_restatement_as_well_as_torch_does_and_every_blob_is_the_pack(config, leg):
+    """Five steps with fresh gradients each (steps 2 and 4 a tenth of the others: max_grad_norm, half the first step's norm, bites on
+    1, 3, 5 only).  After EVERY step both blobs equal pack() of the parameters bit for bit and stats holds the exact step, the norm and the
+    clip coefficient within 1e-10 relative of float64 (an N-term float64 sum of exact squares is off by at most (N - 1) 2^-53, N <=
+    5.1e5) and the float32 lr.  After the five steps, per network and for each of parameters, m, v, pooled over the ten tensors: mean
+    |error| against the float64 restatement at most 2x that of torch's own float32 clip_grad_norm_ + Adam on the same inputs, maximum at
+    most 4x."""
+    lr, counter = LEGS[leg]
+    gen = torch.Generator().manual_seed(17)
+    probe = Case(config, U.hyper32(lr=lr))
+    rows, g_ls = probe.draw(gen)
+    first = float(np.sqrt(sum(float((g.double() ** 2).sum()) for g in rows + ([g_ls] if g_ls is not None else []))))
+    hp = U.hyper32(lr=lr, max_grad_norm=0.5 * first)
+    case = Case(config, hp)
+    yard = TorchPath(case, hp, 0)
+    ref = [[[np.asarray(x, np.float64) for x in grp] for grp in g] for g in case.groups()]
+    t, coefs = 0, []
+    gen = torch.Generator().manual_seed(17)
+    for s in range(STEPS):
+        if s in counter:
+            t = counter[s]
+            case.step.fill_(t)
+            yard.set_counter(t)
+        rows, g_ls = case.draw(gen, 0.1 if s in (1, 3) else 1.0)
+        grads = _flat_split(case, rows, g_ls)
+        stats = case.run(rows, g_ls)
+        yard.step(grads)
+        # the float64 restatement over everything in the call at once (one global norm)
+        sizes = [len(g) for g in grads]
+        flat = lambda j: [x for grp in ref for x in grp[j]]     # noqa: E731
+        P, M, V, t, norm, coef = U.reference_step(flat(0), [g.cpu().numpy() for gs in grads for g in gs], flat(1), flat(2), t, hp)
+        o = 0
+        for i, k in enumerate(sizes):
+            ref[i] = [P[o:o + k], M[o:o + k], V[o:o + k]]
+            o += k
+        coefs.append(coef)
+        _blobs_are_packs(case, (config, leg, s))
+        got = stats.cpu().numpy()
+        assert got[0] == t and int(case.step) == t
+        assert abs(got[1] - norm) <= 1e-10 * norm and abs(got[2] - coef) <= 1e-10 * coef and got[3] == hp["lr"], (got, norm, coef)
+    assert [c < 1.0 for c in coefs] == [True, False, True, False, True], coefs
+    ratios, failed = {}, []
+    for i, (mine, torchs, want) in enumerate(zip(case.groups(), yard.groups(), ref)):
+        for j, what in enumerate(("p", "m", "v")):
+            (em, ex), (tm, tx) = U.pooled_errors(mine[j], want[j]), U.pooled_errors(torchs[j], want[j])
+            assert tm > 0.0 and tx > 0.0
+            ratios[f"net{i}.{what}"] = (em / tm, ex / tx)
+            if em > 2.0 * tm or ex > 4.0 * tx:
+                failed.append((i, what, em, tm, ex, tx))
+    _record(config, leg, ratios)
+    assert not failed, failed
+
+
+@pytest.mark.parametrize("config", ["n1", "n3-gaussian"])
+def test_no_clipping_and_a_bound_that_never_bites_give_the_bits_of_coefficient_one(config):
+    gen = torch.Generator().manual_seed(23)
+    off, huge = Case(config, U.hyper32()), Case(config, U.hyper32(max_grad_norm=1e30))
+    for _ in range(2):
+        rows, g_ls = off.draw(gen)
+        off.run(rows, g_ls)
+        huge.run(rows, g_ls)
+        a, b = off.bits(), huge.bits()
+        assert _same_bits({k: v for k, v in a.items() if k != "stats"}, b) == []
+        assert float(off.stats[2]) == 1.0 == float(huge.stats[2]) and torch.equal(off.stats, huge.stats)
+    # a bound of 1 does bite on these gradients: 1e30 above was a bound that did not, not a switch that is ignored
+    clipped = Case(config, U.hyper32(max_grad_norm=1.0))
+    gen = torch.Generator().manual_seed(23)
+    rows, g_ls = clipped.draw(gen)
+    clipped.run(rows, g_ls)
+    assert float(clipped.stats[2]) < 1.0
+
+
+@pytest.mark.parametrize("config", ["n3-gaussian", "n16"])
+def test_two_calls_from_copies_of_one_state_give_identical_bits_and_leave_the_guards_alone(config):
+    hp = U.hyper32(max_grad_norm=5.0)
+    alloc = GU.Buffers(True)
+    a, b = Case(config, hp, alloc=alloc), Case(config, hp)
+    gen = torch.Generator().manual_seed(29)
+    for _ in range(2):
+        rows, g_ls = a.draw(gen)
+        a.run(rows, g_ls)
+        b.run([r.clone() for r in rows], g_ls.clone() if g_ls is not None else None)
+    assert _same_bits(a.bits(), b.bits()) == []
+    assert int(a.step) == 2 and float(a.stats[2]) < 1.0
+    assert alloc.stray() == []
+    _blobs_are_packs(a, config)
+
+
+@pytest.mark.parametrize("max_grad_norm", [0.0, 1.0])
+def test_an_agent_with_a_zero_gradient_and_zero_moments_keeps_every_bit(max_grad_norm):
+    """What a scripted opponent's agents are to the learner: gradient rows of +0, moments +0.  Parameters, moments and the blob row stay
+    as they are, with clipping on and off; the other agents move."""
+    case = Case("n3-gaussian", U.hyper32(lr=0.01, max_grad_norm=max_grad_norm))
+    for net, blob in zip(case.nets, case.blobs):
+        blob.copy_(net.pack())
+    frozen = [1, 4]
+    before = case.bits()
+    rows, g_ls = case.draw(torch.Generator().manual_seed(31))
+    for r in rows:
+        r[frozen] = 0.0
+    g_ls[frozen] = 0.0
+    case.run(rows, g_ls)
+    after = case.bits()
+    assert (float(case.stats[2]) < 1.0) == (max_grad_norm > 0.0)
+    for k in before:
+        if k in ("step", "stats"):
+            continue
+        assert torch.equal(before[k][frozen], after[k][frozen]), k
+        others = [a for a in range(case.A) if a not in frozen]
+        assert not torch.equal(before[k][others], after[k][others]), k
+
+
+def test_the_binding_refuses_wrong_tensors_by_name():
+    from deep_rl_battlespace_amd import learner
+    case = Case("n3-gaussian", U.hyper32())
+    rows, g_ls = case.draw(torch.Generator().manual_seed(37))
+    kw = dict(log_std=case.log_std, g_log_std=g_ls, log_std_state=case.ls_state)
+
+    def call(nets=case.nets, rows=rows, states=case.states, blobs=case.blobs, hyper=case.hyper, step=case.step, **over):
+        return learner.adam_step(nets, rows, states, blobs, hyper, step, **dict(kw, **over))
+    before = case.bits()
+    with pytest.raises(TypeError, match=r"grads\[0\]"):
+        call(rows=[rows[0].double(), rows[1]])
+    with pytest.raises(ValueError, match=r"grads\[1\]"):
+        call(rows=[rows[0], rows[1][:, :-1]])
+    with pytest.raises(ValueError, match=r"grads\[0\].*contiguous"):
+        call(rows=[rows[0].t().contiguous().t(), rows[1]])
+    with pytest.raises(ValueError, match=r"grads\[0\] is on"):
+        call(rows=[rows[0].cpu(), rows[1]])
+    with pytest.raises(ValueError, match=r"blobs\[1\]"):
+        call(blobs=[case.blobs[0], case.blobs[1][:, 1:]])
+    with pytest.raises(TypeError, match=r"states\[0\]"):
+        call(states=[None, case.states[1]])
+    with pytest.raises(ValueError, match="all three or none"):
+        call(g_log_std=None)
+    with pytest.raises(ValueError, match="g_log_std"):
+        call(g_log_std=g_ls[:, :2])
+    with pytest.raises(ValueError, match="hyper"):
+        call(hyper=case.hyper[:5])
+    with pytest.raises(TypeError, match="step"):
+        call(step=case.step.int())
+    with pytest.raises(TypeError, match="step"):
+        call(step=3)
+    with pytest.raises(ValueError, match="workspace"):
+        call(workspace=torch.empty(2, dtype=torch.int64, device="cuda"))
+    with pytest.raises(TypeError, match="stats"):
+        call(stats=torch.empty(4, device="cuda"))
+    w2 = case.nets[0].w2
+    case.nets[0].w2 = torch.nn.Parameter(w2.detach().transpose(1, 2))
+    with pytest.raises(ValueError, match=r"nets\[0\]\.w2.*contiguous"):
+        call()
+    case.nets[0].w2 = w2
+    assert _same_bits(before, case.bits()) == []                    # nothing was launched by a refused call

@@ -16,7 +16,20 @@ is a few back-to-back steps between two events.  Reported per path: the median, 
   minibatch  (c) PPOLearner.minibatch_grads over a real PolicyRollout's records (pack, one forward with the value head, the loss head,
              two backward calls) against StackedActor forwards, the torch loss and autograd into both networks' parameters
 Sizes: R x A = 2 097 152 x 2 (one T = 32 rollout of 65 536 x 1v1) and 524 288 x 8 (T = 8 of 65 536 x 4v4).  One JSON line on stdout, also
-written to --out with the command."""
+written to --out with the command.
+
+    python tools/bench_ppo_update.py --adam [--blocks 7] [--ratios ratios.jsonl] [--out profiles/adam_step.json]
+
+measures the optimiser step instead (learner.adam_step: bsx_adam_step; PPOLearner(device_step=True)), as two alternating A/B pairs at
+65 536 x 1v1 and 4 096 x 1v1, T = 32, categorical head, max_grad_norm 0.5:
+  step       (a) one optimiser step on fixed gradient rows: install + clip_grad_norm_ + torch Adam + two pack() against adam_step
+             (eager, with the binding's argument checks on the host; and sixteen of them captured: the two launches' device time)
+  update     (b) a whole update(), epochs = 4, minibatches = 4: the default path eager against device_step=True captured (one graph replay)
+Per path and block: host wall clock to a final synchronise and device time between two events (ms per step / update); and once per path
+the GPU activities of one call as torch's profiler sees them (kernels, copies, fills; the captured update's are counted on its eager
+form; null where the profiler gives none) and the peak
+allocation beyond what is held.  --ratios: the accuracy table tests/test_hip_adam_step.py writes with BSX_ADAM_RATIOS_OUT (error against
+the float64 restatement over torch's own, mean / max per network and quantity), copied into the result."""
 import argparse
 import json
 import math
@@ -49,11 +62,144 @@ def torch_loss(torch, kind, y, v, act, logp_old, adv, ret, w, v_old, log_std):
     return (-(surr * w).sum() + C_V * (lv * w).sum() - C_E * (ent * w).sum()) / w.sum()
 
 
+ADAM_SIZES = ((32, 65536, 1), (32, 4096, 1))     # (T, E, n)
+
+
+def adam_pairs(args):
+    """--adam: the two A/B pairs of the optimiser step -> the result dict."""
+    import time
+    import torch
+    import deep_rl_battlespace_amd as bsx
+    from deep_rl_battlespace_amd.learner import PPOLearner, adam_step
+    from deep_rl_battlespace_amd.rollout import PolicyRollout, StackedActor
+
+    def block(step, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        for _ in range(reps):
+            step()
+        e1.record()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / reps, e0.elapsed_time(e1) / reps
+
+    def stats(x):
+        m = statistics.median(x)
+        return dict(median_ms=round(m, 4), min_ms=round(min(x), 4), max_ms=round(max(x), 4), spread=round((max(x) - min(x)) / m, 4))
+
+    def gpu_activities(step):
+        """Kernels, copies and fills one call puts on the GPU, counted by torch's profiler; None if it records no device activity."""
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                step()
+                torch.cuda.synchronize()
+            return sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA")) or None
+        except Exception as exc:                                          # a build without device tracing: the count is left out
+            print(f"[bench_ppo_update] no launch count: {exc}", file=sys.stderr)
+            return None
+
+    def peak_of(step):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        step()
+        torch.cuda.synchronize()
+        return int(torch.cuda.max_memory_allocated() - base)
+
+    def pair(slow, fast, slow_reps, fast_reps, count_fast=None):
+        """count_fast: the eager form of a captured `fast` (the profiler does not always see the kernels of a graph replay)."""
+        for step in (slow, fast, slow, fast):
+            step()
+        torch.cuda.synchronize()
+        a, b = [], []
+        for _ in range(args.blocks):
+            a.append(block(slow, slow_reps))
+            b.append(block(fast, fast_reps))
+        out = {}
+        for name, x, step, count in (("torch", a, slow, slow), ("device", b, fast, count_fast or fast)):
+            out[name] = dict(host_wall=stats([w for w, _ in x]), device_events=stats([d for _, d in x]), gpu_activities=gpu_activities(count),
+                             peak_bytes=peak_of(step))
+        for key in ("host_wall", "device_events"):
+            t, f = out["torch"][key], out["device"][key]
+            out[f"torch_over_device_{key}"] = round(t["median_ms"] / f["median_ms"], 2)
+            out[f"device_faster_beyond_spread_{key}"] = bool(f["max_ms"] < t["min_ms"])
+        return out
+
+    torch.manual_seed(0)
+    mgn, epochs, minibatches = 0.5, 4, 4
+    result = dict(command=f"python tools/bench_ppo_update.py --adam --blocks {args.blocks}", device=torch.cuda.get_device_name(0), blocks=args.blocks,
+                  max_grad_norm=mgn, epochs=epochs, minibatches=minibatches, sizes=[])
+    for T, E, n in ADAM_SIZES:
+        A, D = 2 * n, 3 * n + 2
+        actor, critic = StackedActor(A, D, 4, device="cuda"), StackedActor(A, D, 1, device="cuda")
+        with torch.no_grad():
+            actor.w3.mul_(50.0); critic.w3.mul_(50.0)
+        env = bsx.parallel_env(n_agents=n, n_envs=E, seed=1, auto_reset=True, device="cuda")
+        env.reset()
+        ro = PolicyRollout(env, actor, T, seed=3, sample="categorical", temperature=TAU, value_actor=critic, gae=dict(gamma=0.99, lam=0.95), chains=1)
+        ro.start(); ro.capture()
+        ro.run(); ro.run()
+        torch.cuda.synchronize()
+        kw = dict(clip=CLIP, c_v=C_V, c_e=C_E, vclip=VCLIP, epochs=epochs, minibatches=minibatches, max_grad_norm=mgn)
+        plain, device = PPOLearner(ro, **kw), PPOLearner(ro, device_step=True, **kw)
+        row_a, row_v, _, _ = (r.clone() if r is not None else None for r in device.minibatch_grads(0, T // minibatches, pack=False))
+        blob_a, blob_v = torch.empty_like(ro.fused.weights), torch.empty_like(ro._value_w)
+
+        def torch_step():
+            plain.install(row_a, row_v, None)
+            torch.nn.utils.clip_grad_norm_(plain.params, mgn)
+            plain.optimizer.step()
+            actor.pack(out=blob_a)
+            critic.pack(out=blob_v)
+
+        def device_step():
+            adam_step([actor, critic], [row_a, row_v], [device.adam_a, device.adam_v], [device._blob_a, device._blob_v], device.hyper,
+                      device.step_count, stats=device.step_stats[0], workspace=device._adam_ws)
+        entry = dict(n=n, ticks=T, games=E, rows_per_minibatch=T // minibatches * E, step=pair(torch_step, device_step, 8, 64))
+        # the step's own device time: the eager call above is bound by the binding's argument checks on the host
+        sixteen = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(sixteen):
+            for _ in range(16):
+                device_step()
+        sixteen.replay()
+        entry["step"]["device_captured_ms_per_step"] = stats([block(sixteen.replay, 8)[1] / 16 for _ in range(args.blocks)])
+        del sixteen
+        device.sync()
+        eager = PPOLearner(ro, device_step=True, **kw)
+        eager.update()
+        device.sync()
+        device.capture()
+        entry["update"] = pair(plain.update, device.update, 1, 1, count_fast=eager.update)
+        entry["update"]["optimiser_steps"] = epochs * minibatches
+        result["sizes"].append(entry)
+        del ro, plain, device, env, actor, critic
+        torch.cuda.empty_cache()
+    if args.ratios:
+        result["error_over_torch_float32_mean_max"] = [json.loads(line) for line in open(args.ratios) if line.strip()]
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_update.json"))
+    ap.add_argument("--adam", action="store_true", help="measure the optimiser step (adam_step) instead: profiles/adam_step.json")
+    ap.add_argument("--ratios", default=None, help="with --adam: the accuracy table written by tests/test_hip_adam_step.py")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "adam_step.json" if args.adam else "ppo_update.json")
+    if args.adam:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_ppo_update.py measures on the GPU: none found")
+        result = adam_pairs(args)
+        print(json.dumps(result))
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(result, indent=1) + "\n")
+        return
     import torch
     import deep_rl_battlespace_amd as bsx
     from deep_rl_battlespace_amd import advantage
