@@ -4,6 +4,7 @@ Only what the hot path needs lives here:
   csrc/          hand-written HIP kernels for gfx950 + the C ABI of include/battlespace_hip.h
   build.py       hipcc recipe for csrc/ (in-tree libbattlespace_hip.so)
   _lib.py        ctypes binding of the C ABI (fails loudly when the library is missing)
+  _args.py       the tensor, number and workspace checks of advantage.py and learner.py
   envs/battle_env.py   `parallel_env`: the reference's PettingZoo ParallelEnv surface, batched over n_envs
   spaces.py      Box / Discrete metadata containers (gym is not a dependency)
   sharding.py    one contiguous env range per rank (no collective on the step path)

@@ -19,10 +19,12 @@ has no decisions: mask 0 and adv = ret = +0 on all of its rows, which are in non
 updated.  PolicyRollout(opponent=..., gae=...) passes the learned team's flags.
 """
 from collections import namedtuple
+from functools import partial
 
 import torch
 
 from . import _lib
+from ._args import _F32, _FLAG, _need, _workspace
 
 Gae = namedtuple("Gae", "adv ret mask stats")
 
@@ -45,22 +47,6 @@ def workspace_bytes(E, A, T):
     return n.value
 
 
-def _need(x, name, shape, dtypes, dev):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if x.dtype not in dtypes:
-        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
-    if tuple(x.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(x.shape)}")
-    if x.device != dev:
-        raise ValueError(f"{name} is on {x.device}, rew on {dev}")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-
-
-_F32, _FLAG = (torch.float32,), (torch.uint8, torch.bool)
-
-
 def gae(rew, value, last_value, done, env_done, done_prev, gamma, lam, *, normalize=False, out=None, stats=None, workspace=None, agents=None):
     """-> Gae(adv f32 [T, E, A], ret f32 [T, E, A], mask bool [T, E, A], stats f64 [3] or None); done_prev is updated in place.
     agents: optional bool / uint8 [A] device tensor, 0 = an agent the actor does not play (no decisions: see the module's docstring).
@@ -75,33 +61,30 @@ def gae(rew, value, last_value, done, env_done, done_prev, gamma, lam, *, normal
     if T < 1 or E < 1 or A < 2 or A % 2:
         raise ValueError(f"rew has shape {tuple(rew.shape)}: T >= 1, E >= 1 and an even A >= 2 are needed")
     check_rates(gamma, lam)
-    _need(rew, "rew", (T, E, A), _F32, dev)
-    _need(value, "value", (T, E, A), _F32, dev)
-    _need(last_value, "last_value", (E, A), _F32, dev)
-    _need(done, "done", (T, E, A), _FLAG, dev)
+    need = partial(_need, dev=dev, anchor="rew")
+    need(rew, "rew", (T, E, A), _F32)
+    need(value, "value", (T, E, A), _F32)
+    need(last_value, "last_value", (E, A), _F32)
+    need(done, "done", (T, E, A), _FLAG)
     if not isinstance(env_done, torch.Tensor) or env_done.dim() != 2 or env_done.shape[0] < T:
         raise ValueError(f"env_done must be a [T(+1), E] tensor with at least {T} rows")
-    _need(env_done, "env_done", (env_done.shape[0], E), _FLAG, dev)
-    _need(done_prev, "done_prev", (E, A), _FLAG, dev)
+    need(env_done, "env_done", (env_done.shape[0], E), _FLAG)
+    need(done_prev, "done_prev", (E, A), _FLAG)
     if agents is not None:
-        _need(agents, "agents", (A,), _FLAG, dev)
+        need(agents, "agents", (A,), _FLAG)
     if out is None:
         adv, ret = torch.empty_like(rew), torch.empty_like(rew)
         mask = torch.empty((T, E, A), dtype=torch.uint8, device=dev)
     else:
         adv, ret, mask = out
-        _need(adv, "out adv", (T, E, A), _F32, dev)
-        _need(ret, "out ret", (T, E, A), _F32, dev)
-        _need(mask, "out mask", (T, E, A), _FLAG, dev)
+        need(adv, "out adv", (T, E, A), _F32)
+        need(ret, "out ret", (T, E, A), _F32)
+        need(mask, "out mask", (T, E, A), _FLAG)
     if normalize:
         if stats is None:
             stats = torch.zeros(3, dtype=torch.float64, device=dev)
-        _need(stats, "stats", (3,), (torch.float64,), dev)
-        nb = workspace_bytes(E, A, T)
-        if workspace is None:
-            workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-        if workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < nb:
-            raise ValueError(f"workspace must be a contiguous tensor of at least {nb} bytes on {dev}")
+        need(stats, "stats", (3,), (torch.float64,))
+        workspace = _workspace(workspace, workspace_bytes(E, A, T), dev)
     io = _lib.BsxGaeIo(rew.data_ptr(), value.data_ptr(), done.data_ptr(), env_done.data_ptr(), last_value.data_ptr(), done_prev.data_ptr(),
                        adv.data_ptr(), ret.data_ptr(), mask.data_ptr())
     lib = _lib.load()

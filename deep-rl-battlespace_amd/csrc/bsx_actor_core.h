@@ -10,34 +10,13 @@
 #include <stdint.h>
 
 #include "battlespace_hip.h"
+#include "bsx_actor_layout.h"   // H, NA, nid, the packed blob (off_*, blob_floats) and the gradient row
 
 namespace bsx_actor {
 
-constexpr int H = 64;            // fc1_dims = fc2_dims = 64 (main.py:15-16)
-constexpr int NA = 4;            // discrete action scores
 constexpr int SMALL = 6 * H + H * NA + NA;   // per-agent LDS block: b1 g1 be1 b2 g2 be2 | W3P | b3
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// packed blob per agent (floats); Dp = obs_len rounded up to even
-//   W1A[mo 2][s Dp/2][lane 64]                 W1[k = 2s + (lane>>5)][32*mo + (lane&31)], 0 for k >= D
-//   W2A[mo 2][mt 2][vq 4][lane 64][t 4]        W2[k = nid(mt, 4*vq+t, lane>>5)][32*mo + (lane&31)]
-//   small: b1p g1p be1p b2p g2p be2p, each [hh 2][mo 2][v 16] = value[nid(mo, v, hh)]
-//   W3P[hh 2][mt 2][v 16][4]                   W3[k = nid(mt, v, hh)][0..3]
-//   b3[4]
-//   W2B[mo 2][s 4][term 3][lane 64][i 8] bf16  the 64 x 64 layer once more, split in bf16 terms: term 0 = bf16(W2), term 1 =
-//                                              bf16(W2 - term 0), term 2 = bf16(W2 - term 0 - term 1), of
-//                                              W2[k = nid(s>>1, 8*(s&1) + i, lane>>5)][32*mo + (lane&31)]
-//                                              (BSX_ACTOR_BF16X3 reads terms 0-1, BSX_ACTOR_BF16X6 all three)
-// nid(m, v, hh) = 32*m + (v&3) + 8*(v>>2) + 4*hh  -- the neuron held by accumulator register v of tile m in lane half hh
-__host__ __device__ constexpr int dpad(int D) { return (D + 1) & ~1; }
-__host__ __device__ constexpr int off_w2(int D) { return H * dpad(D); }
-__host__ __device__ constexpr int off_small(int D) { return off_w2(D) + H * H; }
-__host__ __device__ constexpr int off_w3(int D) { return off_small(D) + 6 * H; }
-__host__ __device__ constexpr int off_b3(int D) { return off_w3(D) + H * NA; }
-__host__ __device__ constexpr int off_w2b(int D) { return off_b3(D) + NA; }            // 16-byte aligned: every section is a multiple of 4 floats
-__host__ __device__ constexpr int blob_floats(int D) { return off_w2b(D) + H * H * 3 / 2; }     // 3 bf16 terms = 6 bytes per weight
-
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ inline uint4 philox4x32_10(uint4 ctr, uint2 key) {
@@ -58,8 +37,14 @@ __device__ inline uint4 philox4x32_10(uint4 ctr, uint2 key) {
 // variance, eps 1e-5).  A row's 64 neurons = 32 registers of the lane + the partner lane l^32.  gp / bp: this lane half's
 // gain / bias vectors, [mo 2][v 16] floats in LDS (8-byte aligned).  Written on register PAIRS so that the adds, multiplies
 // and FMAs issue as packed-f32 instructions (v_pk_add / v_pk_mul / v_pk_fma_f32: two values per issue slot).
+// Returns rstd.  `keep`: ln_drop (the forward: nothing more), or ln_keep{x0, x1} (the training pass, bsx_actor_grad.hip), which also
+// receives x^ = (a - mean) * rstd of the tile -- the forward's operations stay what they are, two stores are added.  (x^ is formed ahead
+// of the stores to a0 / a1: from that order the training pass compiles to the schedule it is tuned at; the forward drops the line.)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ inline void ln_relu_tile(f32x16& a0, f32x16& a1, const float* __restrict__ gp, const float* __restrict__ bp) {
+struct ln_drop { static constexpr bool keeps = false; };
+struct ln_keep { static constexpr bool keeps = true; f32x16& x0; f32x16& x1; };
+template <class KEEP = ln_drop>
+__device__ inline float ln_relu_tile(f32x16& a0, f32x16& a1, const float* __restrict__ gp, const float* __restrict__ bp, KEEP keep = {}) {
 #pragma clang fp contract(fast)
     f32x2 s2 = {0.f, 0.f};
 #pragma unroll
@@ -84,13 +69,18 @@ __device__ inline void ln_relu_tile(f32x16& a0, f32x16& a1, const float* __restr
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const f32x2 y = d0[i] * (r2 * g2[i]) + b2[i];
+        [[maybe_unused]] const f32x2 xh = d0[i] * r2;
         a0[2 * i] = fmaxf(y.x, 0.f); a0[2 * i + 1] = fmaxf(y.y, 0.f);
+        if constexpr (KEEP::keeps) { keep.x0[2 * i] = xh.x; keep.x0[2 * i + 1] = xh.y; }
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const f32x2 y = d1[i] * (r2 * g2[8 + i]) + b2[8 + i];
+        [[maybe_unused]] const f32x2 xh = d1[i] * r2;
         a1[2 * i] = fmaxf(y.x, 0.f); a1[2 * i + 1] = fmaxf(y.y, 0.f);
+        if constexpr (KEEP::keeps) { keep.x1[2 * i] = xh.x; keep.x1[2 * i + 1] = xh.y; }
     }
+    return rstd;
 }
 
 // Four standard normals from one Philox4x32-10 block (Box-Muller), keyed by (seed, seq ^ salt, global row).

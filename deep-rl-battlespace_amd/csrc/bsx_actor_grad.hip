@@ -53,9 +53,6 @@ struct GradArgs {
     int64_t R; int A; int D; int squash; int rounds;
 };
 
-__host__ __device__ constexpr int grad_floats(int D) { return H * D + H * H + 6 * H + H * NA + NA; }
-__host__ __device__ constexpr int nid(int m, int v, int hh) { return 32 * m + (v & 3) + 8 * (v >> 2) + 4 * hh; }
-
 // workgroups per agent: a function of (R, n) alone
 inline int partials(int64_t R, int n) {
     const int64_t rounds = ((R + 31) / 32 + WAVES - 1) / WAVES;
@@ -68,46 +65,6 @@ __device__ inline void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// ln_relu_tile (bsx_actor_core.h), operation for operation, which also hands out x^ = (a - mean) * rstd and rstd
-__device__ inline float ln_relu_keep(f32x16& a0, f32x16& a1, f32x16& x0, f32x16& x1, const float* __restrict__ gp, const float* __restrict__ bp) {
-#pragma clang fp contract(fast)
-    f32x2 s2 = {0.f, 0.f};
-#pragma unroll
-    for (int v = 0; v < 16; v += 2) s2 += f32x2{a0[v], a0[v + 1]};
-#pragma unroll
-    for (int v = 0; v < 16; v += 2) s2 += f32x2{a1[v], a1[v + 1]};
-    float s = s2.x + s2.y;
-    s += __shfl_xor(s, 32);
-    const float mean = s * (1.0f / H);
-    const f32x2 m2 = {mean, mean};
-    f32x2 d0[8], d1[8], q2 = {0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { d0[i] = f32x2{a0[2 * i], a0[2 * i + 1]} - m2; q2 += d0[i] * d0[i]; }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { d1[i] = f32x2{a1[2 * i], a1[2 * i + 1]} - m2; q2 += d1[i] * d1[i]; }
-    float q = q2.x + q2.y;
-    q += __shfl_xor(q, 32);
-    const float rstd = rsqrtf(q * (1.0f / H) + 1e-5f);
-    const f32x2 r2 = {rstd, rstd};
-    const f32x2* g2 = reinterpret_cast<const f32x2*>(gp);
-    const f32x2* b2 = reinterpret_cast<const f32x2*>(bp);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const f32x2 y = d0[i] * (r2 * g2[i]) + b2[i];
-        const f32x2 xh = d0[i] * r2;
-        a0[2 * i] = fmaxf(y.x, 0.f); a0[2 * i + 1] = fmaxf(y.y, 0.f);
-        x0[2 * i] = xh.x; x0[2 * i + 1] = xh.y;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const f32x2 y = d1[i] * (r2 * g2[8 + i]) + b2[8 + i];
-        const f32x2 xh = d1[i] * r2;
-        a1[2 * i] = fmaxf(y.x, 0.f); a1[2 * i + 1] = fmaxf(y.y, 0.f);
-        x1[2 * i] = xh.x; x1[2 * i + 1] = xh.y;
-    }
-    return rstd;
 }
 
 // LayerNorm backward on one tile, in place: d = dy in, da out.  dx^ = dy g,  da = rstd (dx^ - mean64(dx^) - x^ mean64(dx^ x^))
@@ -171,10 +128,7 @@ __global__ __launch_bounds__(TPB, 2) void bsx_actor_grad_kernel(const GradArgs p
     const int I3 = I2 + IMG;                                      // h2, dy2, dy1
     for (int i = tid; i < SMALL / 4; i += TPB)
         reinterpret_cast<float4*>(s_small)[i] = reinterpret_cast<const float4*>(W + off_small(D))[i];
-    for (int i = tid; i < H * H; i += TPB) {                      // W2A[mo][mt][vq][lane][t] = W2[32 mt + t + 8 vq + 4 (lane>>5)][32 mo + (lane&31)]
-        const int t = i & 3, ln = (i >> 2) & 63, vq = (i >> 8) & 3, mt = (i >> 10) & 1, mo = i >> 11;
-        s_w2[(32 * mt + t + 8 * vq + 4 * (ln >> 5)) * IS + 32 * mo + (ln & 31)] = W[off_w2(D) + i];
-    }
+    for (int i = tid; i < H * H; i += TPB) s_w2[w2a_k(i) * IS + w2a_j(i)] = W[off_w2(D) + i];     // the W2A section, un-permuted
     __syncthreads();
     const float4 b3 = *reinterpret_cast<const float4*>(s_small + 6 * H + H * NA);
 
@@ -208,7 +162,7 @@ __global__ __launch_bounds__(TPB, 2) void bsx_actor_grad_kernel(const GradArgs p
             t0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, t0, 0, 0, 0);
             t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, t1, 0, 0, 0);
         }
-        const float rstd1 = ln_relu_keep(t0, t1, x0, x1, sm + 1 * H, sm + 2 * H);
+        const float rstd1 = ln_relu_tile(t0, t1, sm + 1 * H, sm + 2 * H, ln_keep{x0, x1});
         img_write(lds, I0, c, hh, x0, x1);
         img_write(lds, I1, c, hh, t0, t1);
         // ---- layer 2: the K index runs over layer 1's accumulator registers, in tile_forward's order
@@ -226,7 +180,7 @@ __global__ __launch_bounds__(TPB, 2) void bsx_actor_grad_kernel(const GradArgs p
                 u1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[32], hv, u1, 0, 0, 0);
             }
         }
-        const float rstd2 = ln_relu_keep(u0, u1, x0, x1, sm + 4 * H, sm + 5 * H);
+        const float rstd2 = ln_relu_tile(u0, u1, sm + 4 * H, sm + 5 * H, ln_keep{x0, x1});
         img_write(lds, I3, c, hh, u0, u1);
         // ---- head, ds
         const float4* w3 = reinterpret_cast<const float4*>(ssm + 6 * H) + hh * 32;   // [hh][mt][v] float4
@@ -407,7 +361,7 @@ __global__ __launch_bounds__(TPB, 2) void bsx_actor_grad_kernel(const GradArgs p
     float* red = lds + LDS_IMG;                                   // [wave][VEC], then the upper waves' dW1 tiles
 #pragma unroll
     for (int v = 0; v < 16; ++v)
-        out[H * D + 3 * H + (32 * (ew >> 1) + (v & 3) + 8 * (v >> 2) + 4 * eh) * H + 32 * (ew & 1) + ec] = accW2[v];
+        out[row_w2(D) + nid(ew >> 1, v, eh) * H + 32 * (ew & 1) + ec] = accW2[v];
     red[ew * VEC + 0 * H + el] = db1; red[ew * VEC + 1 * H + el] = dg1; red[ew * VEC + 2 * H + el] = dh1v;
     red[ew * VEC + 3 * H + el] = db2; red[ew * VEC + 4 * H + el] = dg2; red[ew * VEC + 5 * H + el] = dh2v;
     red[ew * VEC + 6 * H + el * NA + 0] = accW3.x; red[ew * VEC + 6 * H + el * NA + 1] = accW3.y;
@@ -425,7 +379,7 @@ __global__ __launch_bounds__(TPB, 2) void bsx_actor_grad_kernel(const GradArgs p
     if (MT1 == 2 || ew < 2) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int k = 32 * (MT1 == 2 ? ew >> 1 : 0) + (v & 3) + 8 * (v >> 2) + 4 * eh;
+            const int k = nid(MT1 == 2 ? ew >> 1 : 0, v, eh);
             float g = accW1[v];
             if (MT1 == 1) g += red1[(ew * 16 + v) * 64 + el];
             if (k < D) out[k * H + 32 * (ew & 1) + ec] = g;
@@ -433,7 +387,7 @@ __global__ __launch_bounds__(TPB, 2) void bsx_actor_grad_kernel(const GradArgs p
     }
     for (int i = etid; i < VEC; i += TPB) {
         const float g = (red[0 * VEC + i] + red[1 * VEC + i]) + (red[2 * VEC + i] + red[3 * VEC + i]);
-        out[i < 3 * H ? H * D + i : H * D + H * H + i] = g;
+        out[i < 3 * H ? row_b1(D) + i : row_b1(D) + H * H + i] = g;           // VEC is the row from b1 on with w2 (H * H floats) taken out
     }
 }
 

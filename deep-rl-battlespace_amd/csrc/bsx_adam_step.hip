@@ -18,18 +18,18 @@
 #include <stdint.h>
 
 #include "battlespace_hip.h"
-#include "bsx_actor_core.h"
+#include "bsx_actor_layout.h"
 #include "bsx_args.h"
+#include "bsx_block_sum.h"
 
 namespace {
 
-using bsx_actor::H;
+using namespace bsx_actor;
 
 constexpr int NORM_TPB = 1024;                            // a row is 5 .. 8 floats per thread: the passes are latency, not bandwidth
 constexpr int APPLY_TPB = 1024;
 constexpr int D_MAX = 3 * BSX_MAX_N + 2;
-constexpr int G_TAIL = H * H + 6 * H + H * 4 + 4;         // a gradient row after w1: b1 g1 h1 | w2 | b2 g2 h2 | w3[64][4] | b3[4]
-constexpr int G_MAX = H * D_MAX + G_TAIL;
+constexpr int G_MAX = grad_floats(D_MAX);
 constexpr int SCALARS = 8;                                // workspace doubles ahead of the partials: t | lr | lr / (1 - b1^t) | sqrt(1 - b2^t) | b1 | b2 | eps | max_norm
 constexpr int PART_MAX = 4 * BSX_MAX_N + 1;
 
@@ -44,13 +44,12 @@ struct Args {
 // false = a pad column of w3 / b3 (no parameter behind it)
 struct Where { int k, i; };
 __device__ inline bool locate(int j, int D, int na, Where& w) {
-    const int o1 = H * D, o2 = o1 + 3 * H, o3 = o2 + H * H, o4 = o3 + 3 * H, o5 = o4 + H * 4;
-    if (j < o1) { w.k = 0; w.i = j; return true; }
-    if (j < o2) { const int r = j - o1; w.k = 1 + r / H; w.i = r % H; return true; }
-    if (j < o3) { w.k = 4; w.i = j - o2; return true; }
-    if (j < o4) { const int r = j - o3; w.k = 5 + r / H; w.i = r % H; return true; }
-    if (j < o5) { const int r = j - o4, c = r & 3; w.k = 8; w.i = (r >> 2) * na + c; return c < na; }
-    const int c = j - o5;
+    if (j < row_b1(D)) { w.k = 0; w.i = j; return true; }
+    if (j < row_w2(D)) { const int r = j - row_b1(D); w.k = 1 + r / H; w.i = r % H; return true; }
+    if (j < row_b2(D)) { w.k = 4; w.i = j - row_w2(D); return true; }
+    if (j < row_w3(D)) { const int r = j - row_b2(D); w.k = 5 + r / H; w.i = r % H; return true; }
+    if (j < row_b3(D)) { const int r = j - row_w3(D), c = r & 3; w.k = 8; w.i = (r >> 2) * na + c; return c < na; }
+    const int c = j - row_b3(D);
     w.k = 9; w.i = c;
     return c < na;
 }
@@ -81,18 +80,6 @@ __device__ inline float* param_ptr(const BsxAdamIo& io, int net, int k) {
     return p;
 }
 
-template <int NW>
-__device__ inline double block_sum_f64(double x, double* s_w) {          // lanes by a fixed shuffle tree, then the waves in order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) t += s_w[w];
-    return t;
-}
-
 __global__ __launch_bounds__(NORM_TPB) void bsx_adam_norm_kernel(const Args p) {
     __shared__ double s_w[NORM_TPB / 64];
     const int tid = threadIdx.x, b = blockIdx.x;
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(NORM_TPB) void bsx_adam_norm_kernel(const Args p) {
     if (b < p.rows) {
         const int net = b / p.A, a = b - net * p.A;
         const Net N = pick(p.io, net);
-        const int G = H * p.D + G_TAIL;
+        const int G = grad_floats(p.D);
         const float* g = N.grad + size_t(a) * G;
 #pragma unroll 4
         for (int j = tid; j < G; j += NORM_TPB) {
@@ -111,7 +98,7 @@ __global__ __launch_bounds__(NORM_TPB) void bsx_adam_norm_kernel(const Args p) {
     } else {
         for (int j = tid; j < 3 * p.A; j += NORM_TPB) { const double x = double(p.io.g_log_std[j]); acc += x * x; }
     }
-    acc = block_sum_f64<NORM_TPB / 64>(acc, s_w);
+    acc = block_sum<double, NORM_TPB / 64>(acc, s_w);
     if (tid == 0) {
         p.ws[SCALARS + b] = acc;
         if (b == 0) {
@@ -137,8 +124,6 @@ __device__ inline uint32_t bf16_rne(float x) {                  // torch's float
 }
 __device__ inline float bf16_float(uint32_t h) { return __uint_as_float(h << 16); }
 
-__device__ inline int nid(int m, int v, int hh) { return 32 * m + (v & 3) + 8 * (v >> 2) + 4 * hh; }
-
 // term 0 / 1 / 2 of W2B's split of w, residuals in float32 as StackedActor.pack() takes them
 __device__ inline uint32_t w2b_term(float w, int term) {
     const uint32_t h = bf16_rne(w);
@@ -151,35 +136,33 @@ __device__ inline uint32_t w2b_term(float w, int term) {
 
 // float f of an agent's blob from its parameters in the gradient row's layout (s: LDS, pad columns of w3 / b3 hold +0)
 __device__ inline float blob_float(const float* s, int f, int D) {
-    const int oW1 = 0, oB1 = H * D, oW2 = oB1 + 3 * H, oB2 = oW2 + H * H, oW3 = oB2 + 3 * H;
-    const int Dp = bsx_actor::dpad(D);
-    if (f < bsx_actor::off_w2(D)) {                              // W1A[mo][s][lane]
+    const int Dp = dpad(D);
+    if (f < off_w2(D)) {                                         // W1A[mo][s][lane]
         const int lane = f & 63, r = f >> 6, hp = Dp / 2, mo = r / hp, sp = r - mo * hp;
         const int k = 2 * sp + (lane >> 5), j = 32 * mo + (lane & 31);
-        return k < D ? s[oW1 + k * H + j] : 0.0f;
+        return k < D ? s[k * H + j] : 0.0f;                      // (w1 is the head of the row)
     }
-    if (f < bsx_actor::off_small(D)) {                           // W2A[mo][mt][vq][lane][t]
-        const int r = f - bsx_actor::off_w2(D);
-        const int t = r & 3, lane = (r >> 2) & 63, vq = (r >> 8) & 3, mt = (r >> 10) & 1, mo = r >> 11;
-        return s[oW2 + nid(mt, 4 * vq + t, lane >> 5) * H + 32 * mo + (lane & 31)];
+    if (f < off_small(D)) {                                      // W2A[mo][mt][vq][lane][t]
+        const int r = f - off_w2(D);
+        return s[row_w2(D) + w2a_k(r) * H + w2a_j(r)];
     }
-    if (f < bsx_actor::off_w3(D)) {                              // b1 g1 h1 b2 g2 h2, each [hh][mo][v]
-        const int r = f - bsx_actor::off_small(D);
+    if (f < off_w3(D)) {                                         // b1 g1 h1 b2 g2 h2, each [hh][mo][v]
+        const int r = f - off_small(D);
         const int vec = r >> 6, q = r & 63, v = q & 15, mo = (q >> 4) & 1, hh = q >> 5;
-        return s[(vec < 3 ? oB1 + vec * H : oB2 + (vec - 3) * H) + nid(mo, v, hh)];
+        return s[(vec < 3 ? row_b1(D) + vec * H : row_b2(D) + (vec - 3) * H) + nid(mo, v, hh)];
     }
-    if (f < bsx_actor::off_b3(D)) {                              // W3P[hh][mt][v][4]
-        const int r = f - bsx_actor::off_w3(D);
+    if (f < off_b3(D)) {                                         // W3P[hh][mt][v][4]
+        const int r = f - off_w3(D);
         const int c = r & 3, v = (r >> 2) & 15, mt = (r >> 6) & 1, hh = r >> 7;
-        return s[oW3 + nid(mt, v, hh) * 4 + c];
+        return s[row_w3(D) + nid(mt, v, hh) * NA + c];
     }
-    if (f < bsx_actor::off_w2b(D)) return s[oW3 + H * 4 + (f - bsx_actor::off_b3(D))];
+    if (f < off_w2b(D)) return s[row_b3(D) + (f - off_b3(D))];
     // W2B[mo][s][term][lane][i], two bfloat16 (i even, i + 1) per float slot, the even one in the low half
-    const int e = 2 * (f - bsx_actor::off_w2b(D));
+    const int e = 2 * (f - off_w2b(D));
     const int i = e & 7, lane = (e >> 3) & 63, rest = e >> 9, term = rest % 3, sq = (rest / 3) & 3, mo = rest / 12;
     const int col = 32 * mo + (lane & 31), hh = lane >> 5;
-    const float w0 = s[oW2 + nid(sq >> 1, 8 * (sq & 1) + i, hh) * H + col];
-    const float w1 = s[oW2 + nid(sq >> 1, 8 * (sq & 1) + i + 1, hh) * H + col];
+    const float w0 = s[row_w2(D) + nid(sq >> 1, 8 * (sq & 1) + i, hh) * H + col];
+    const float w1 = s[row_w2(D) + nid(sq >> 1, 8 * (sq & 1) + i + 1, hh) * H + col];
     return __uint_as_float(w2b_term(w0, term) | (w2b_term(w1, term) << 16));
 }
 
@@ -233,7 +216,7 @@ __global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p)
     }
     const int net = b / p.A, a = b - net * p.A, D = p.D;
     const Net N = pick(p.io, net);
-    const int na = N.na, G = H * D + G_TAIL;
+    const int na = N.na, G = grad_floats(D);
     const float* grad = N.grad + size_t(a) * G;
     float* mrow = N.m + size_t(a) * G;
     float* vrow = N.v + size_t(a) * G;
@@ -250,7 +233,7 @@ __global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p)
         s_p[j] = x;
     }
     __syncthreads();
-    const int BF = bsx_actor::blob_floats(D);
+    const int BF = blob_floats(D);
     float* blob = N.blob + size_t(a) * BF;
     for (int f = tid; f < BF; f += APPLY_TPB) blob[f] = blob_float(s_p, f, D);
 }

@@ -18,6 +18,7 @@
 
 #include "battlespace_hip.h"
 #include "bsx_args.h"
+#include "bsx_block_sum.h"
 
 namespace {
 
@@ -84,19 +85,6 @@ __device__ inline float kl_term(float x) {
     return (x * x) * q;
 }
 
-// the sum of `x` over the workgroup, in every thread (integers: any order gives the same result)
-template <int NW>
-__device__ inline int64_t block_sum_i64(int64_t x, int64_t* s_w) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    int64_t t = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) t += s_w[w];
-    return t;
-}
-
 __global__ __launch_bounds__(TPB) void bsx_ppo_count_kernel(const uint8_t* mask, int64_t M, int64_t* counts) {
     __shared__ int64_t s_w[WAVES];
     const int64_t g = int64_t(blockIdx.x) * TPB + threadIdx.x, stride = int64_t(gridDim.x) * TPB;
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(TPB) void bsx_ppo_count_kernel(const uint8_t* mask,
         n += nonzero_bytes(q.x) + nonzero_bytes(q.y) + nonzero_bytes(q.z) + nonzero_bytes(q.w);
     }
     if (g < M - tail0) n += mask[tail0 + g] != 0;
-    n = block_sum_i64<WAVES>(n, s_w);
+    n = block_sum<int64_t, WAVES>(n, s_w);
     if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(TPB) void bsx_ppo_head_kernel(const HeadArgs p) {
     __shared__ double s_ls[GAUSS ? 3 : 1][GAUSS ? TPB : 1];
     __shared__ double s_lp[GAUSS ? TPB : 1];                 // [P][3 A], 3 A P <= 256
     const int tid = threadIdx.x;
-    const int64_t N = block_sum_i64<WAVES>(tid < p.count_blocks ? p.counts[tid] : 0, s_cnt);
+    const int64_t N = block_sum<int64_t, WAVES>(tid < p.count_blocks ? p.counts[tid] : 0, s_cnt);
     const double inv_n = N > 0 ? 1.0 / double(N) : 0.0;
     const bool lane_on = tid < p.S;
     const int a = tid % p.A;
@@ -273,7 +261,7 @@ __global__ __launch_bounds__(MERGE_TPB) void bsx_ppo_merge_kernel(const int64_t*
     __shared__ int64_t s_cnt[MERGE_TPB / 64];
     __shared__ double s_q[MERGE_TPB], s_r[MERGE_TPB];
     const int tid = threadIdx.x;
-    const int64_t N = block_sum_i64<MERGE_TPB / 64>(tid < count_blocks ? counts[tid] : 0, s_cnt);
+    const int64_t N = block_sum<int64_t, MERGE_TPB / 64>(tid < count_blocks ? counts[tid] : 0, s_cnt);
     const int Q = MERGE_TPB / C, c = tid % C, q = tid / C, G = Q < 16 ? Q : 16;
     if (q < Q) {
         double t = 0.0;

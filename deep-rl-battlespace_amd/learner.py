@@ -17,42 +17,43 @@ weights.  Deterministic (no floating-point atomics): the same inputs give the sa
   PPOLearner(rollout, ...)                                      minibatch_grads / update: the PPO update of a PolicyRollout's networks;
                                                                 device_step=True: the whole update on device, capture() makes it one graph
 """
-import math
 from collections import namedtuple
+from functools import partial
 
 import torch
 
 from . import _lib
+from ._args import _F32, _FLAG, _need, _number, _workspace
 
-PARAMS = ("w1", "b1", "g1", "h1", "w2", "b2", "g2", "h2", "w3", "b3")
 H = 64
+# The ten parameters of a StackedActor in the order of bsx_actor_grad's [A, G] row (csrc/bsx_actor_layout.h holds the kernels' side of it):
+# name, rows as a function of D = obs_len, columns in the row, and whether the parameter keeps only the first n_actions of those columns.
+# grad_floats, split_grad, AdamState's shape and adam_step's parameter checks follow from it.
+_D, _ONE, _HID = (lambda D: D), (lambda D: 1), (lambda D: H)
+_TABLE = (("w1", _D, H, False), ("b1", _ONE, H, False), ("g1", _ONE, H, False), ("h1", _ONE, H, False),
+          ("w2", _HID, H, False), ("b2", _ONE, H, False), ("g2", _ONE, H, False), ("h2", _ONE, H, False),
+          ("w3", _HID, 4, True), ("b3", _ONE, 4, True))
+PARAMS = tuple(name for name, *_ in _TABLE)
 
 
 def grad_floats(obs_len):
     """G of bsx_actor_grad: w1[D][64] | b1 | g1 | h1 | w2[64][64] | b2 | g2 | h2 | w3[64][4] | b3[4]."""
-    return H * obs_len + H * H + 6 * H + H * 4 + 4
+    return sum(rows(obs_len) * cols for _, rows, cols, _ in _TABLE)
 
 
 def split_grad(row, n_actions):
     """row [A, G] (the layout of bsx_actor_grad's `grad`) -> the ten gradients in PARAMS order, shaped like a StackedActor's parameters:
     views of `row`; w3 / b3 cut to their first n_actions columns."""
     A, G = row.shape
-    D = (G - (H * H + 6 * H + H * 4 + 4)) // H
+    D = (G - grad_floats(0)) // H
     if grad_floats(D) != G:
         raise ValueError(f"a gradient row of {G} floats matches no observation length")
     out, o = [], 0
-
-    def take(n):
-        nonlocal o
-        v = row[:, o:o + n]
+    for _, rows, cols, cut in _TABLE:
+        n = rows(D) * cols
+        v = row[:, o:o + n].view(A, rows(D), cols)
+        out.append(v[:, :, :n_actions] if cut else v)
         o += n
-        return v
-    out.append(take(H * D).view(A, D, H))
-    out += [take(H).view(A, 1, H) for _ in range(3)]
-    out.append(take(H * H).view(A, H, H))
-    out += [take(H).view(A, 1, H) for _ in range(3)]
-    out.append(take(H * 4).view(A, H, 4)[:, :, :n_actions])
-    out.append(take(4).view(A, 1, 4)[:, :, :n_actions])
     return out
 
 
@@ -106,21 +107,15 @@ class _FusedApply(torch.autograd.Function):
     @staticmethod
     def forward(ctx, actor, obs, squash, *params):
         lib = _lib.load()
-        A, D, na = actor.n_actors, actor.obs_len, actor.n_actions
-        n, R = A // 2, obs.shape[0]
+        A, na, R = actor.n_actors, actor.n_actions, obs.shape[0]
         blob = actor.pack()                                      # a fresh blob: backward reads THIS one, not the parameters of later
-        stream = torch.cuda.current_stream(obs.device).cuda_stream
         scores = torch.empty((R, A, 4), dtype=torch.float32, device=obs.device)
         if squash:
-            _lib.check(lib.bsx_actor_forward(blob.data_ptr(), obs.data_ptr(), scores.data_ptr(), R, n, _lib.ACTOR_F32, None, 0, 0, None, 0,
-                                             stream), "bsx_actor_forward")
+            _actor_forward(lib, blob, obs, scores)
             y = scores[..., :na]
         else:                                                    # the value path: the same blob once more as the value head
             value = torch.empty((R, A), dtype=torch.float32, device=obs.device)
-            nz = _lib.BsxActorNoise()
-            nz.value_weights, nz.value = blob.data_ptr(), value.data_ptr()
-            _lib.check(lib.bsx_actor_forward(blob.data_ptr(), obs.data_ptr(), scores.data_ptr(), R, n, _lib.ACTOR_F32, _lib.ctypes.byref(nz),
-                                             0, 0, None, 0, stream), "bsx_actor_forward")
+            _actor_forward(lib, blob, obs, scores, blob, value)
             y = value.unsqueeze(-1)
         ctx.save_for_backward(obs, blob)
         ctx.actor, ctx.squash = actor, bool(squash)
@@ -134,6 +129,19 @@ class _FusedApply(torch.autograd.Function):
         # overwritten by the next call
         grads = split_grad(row.clone(), ctx.actor.n_actions)
         return (None, None, None, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])])
+
+
+def _actor_forward(lib, blob, obs, scores, value_blob=None, value=None):
+    """bsx_actor_forward on the current stream, float32 and without noise: the network packed in `blob` on obs [R, A, D] -> scores [R, A, 4];
+    with value_blob and value [R, A], the value head packed in value_blob in the same launch."""
+    R, A = obs.shape[0], obs.shape[1]
+    nz = None
+    if value_blob is not None:
+        nz = _lib.BsxActorNoise()
+        nz.value_weights, nz.value = value_blob.data_ptr(), value.data_ptr()
+    _lib.check(lib.bsx_actor_forward(blob.data_ptr(), obs.data_ptr(), scores.data_ptr(), R, A // 2, _lib.ACTOR_F32,
+                                     _lib.ctypes.byref(nz) if nz is not None else None, 0, 0, None, 0,
+                                     torch.cuda.current_stream(obs.device).cuda_stream), "bsx_actor_forward")
 
 
 def fused_grad(actor, blob, obs, grad_out, squash=True):
@@ -197,31 +205,19 @@ def categorical_log_prob(actor, obs, actions, temperature=1.0, fused=False):
 PpoHead = namedtuple("PpoHead", "g_pi g_v g_log_std stats")
 KINDS = {"categorical": 0, "gaussian": 1, 0: 0, 1: 1}
 STATS = ("n", "loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "reserved")
-_F32, _FLAG = (torch.float32,), (torch.uint8, torch.bool)
 
 
-def _need(x, name, shape, dtypes, dev):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if x.dtype not in dtypes:
-        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
-    if tuple(x.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(x.shape)}")
-    if x.device != dev:
-        raise ValueError(f"{name} is on {x.device}, y on {dev}")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
+# the ranges of the hyper-parameters, stated once: ppo_head, adam_hyper, PPOLearner and set_lr all check through _hyper
+_SHARE = (lambda x: 0.0 < x < 1.0, "a number in (0, 1)")
+_WEIGHT = (lambda x: x >= 0.0, "a number >= 0")
+_POSITIVE = (lambda x: x > 0.0, "a number > 0")
+_BETA = (lambda x: 0.0 <= x < 1.0, "a number in [0, 1)")
+_HYPER = {"clip": _SHARE, "c_v": _WEIGHT, "c_e": _WEIGHT, "temperature": _POSITIVE, "vclip": _POSITIVE, "lr": _WEIGHT, "betas[0]": _BETA,
+          "betas[1]": _BETA, "eps": _WEIGHT, "max_grad_norm": _WEIGHT}       # (max_grad_norm 0: adam_hyper's spelling of "no clipping")
 
 
-def _number(x, name, ok, what):
-    try:
-        x = float(x)
-        good = ok(x) and math.isfinite(x)
-    except (TypeError, ValueError):
-        good = False
-    if not good:
-        raise ValueError(f"{name} must be {what}, got {x!r}")
-    return x
+def _hyper(name, x, rng=None):
+    return _number(x, name, *(rng or _HYPER[name]))
 
 
 def ppo_head_workspace_bytes(R, A):
@@ -258,26 +254,27 @@ def ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, *, clip, c_v, c_e, tempe
     if R < 1 or A < 2 or A % 2 or A > 2 * _lib.MAX_N:
         raise ValueError(f"y has shape {tuple(y.shape)}: R >= 1 and an even A in 2 .. {2 * _lib.MAX_N} are needed")
     lead = tuple(y.shape[:-2])
-    _need(y, "y", (*lead, A, 4), _F32, dev)
-    _need(v, "v", (*lead, A), _F32, dev)
-    _need(rec, "rec", (*lead, A, 4), _F32, dev)
-    _need(logp_old, "logp_old", (*lead, A), _F32, dev)
-    _need(adv, "adv", (*lead, A), _F32, dev)
-    _need(ret, "ret", (*lead, A), _F32, dev)
-    _need(mask, "mask", (*lead, A), _FLAG, dev)
-    clip = _number(clip, "clip", lambda x: 0.0 < x < 1.0, "a number in (0, 1)")
-    c_v = _number(c_v, "c_v", lambda x: x >= 0.0, "a number >= 0")
-    c_e = _number(c_e, "c_e", lambda x: x >= 0.0, "a number >= 0")
-    temperature = _number(temperature, "temperature", lambda x: x > 0.0, "a number > 0")
+    need = partial(_need, dev=dev, anchor="y")
+    need(y, "y", (*lead, A, 4), _F32)
+    need(v, "v", (*lead, A), _F32)
+    need(rec, "rec", (*lead, A, 4), _F32)
+    need(logp_old, "logp_old", (*lead, A), _F32)
+    need(adv, "adv", (*lead, A), _F32)
+    need(ret, "ret", (*lead, A), _F32)
+    need(mask, "mask", (*lead, A), _FLAG)
+    clip = _hyper("clip", clip)
+    c_v = _hyper("c_v", c_v)
+    c_e = _hyper("c_e", c_e)
+    temperature = _hyper("temperature", temperature)
     if (v_old is None) != (vclip is None):
         raise ValueError("v_old and vclip go together: the value loss is clipped around v_old by vclip, or not at all")
     if v_old is not None:
-        _need(v_old, "v_old", (*lead, A), _F32, dev)
-        vclip = _number(vclip, "vclip", lambda x: x > 0.0, "a number > 0")
+        need(v_old, "v_old", (*lead, A), _F32)
+        vclip = _hyper("vclip", vclip)
     if k == 1:
         if log_std is None:
             raise ValueError("kind 'gaussian' needs log_std, a float32 [A, 3] tensor")
-        _need(log_std, "log_std", (A, 3), _F32, dev)
+        need(log_std, "log_std", (A, 3), _F32)
     elif log_std is not None:
         raise ValueError("log_std belongs to kind 'gaussian'")
     if out is None:
@@ -286,17 +283,12 @@ def ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, *, clip, c_v, c_e, tempe
         stats = torch.empty(8, dtype=torch.float64, device=dev)
     else:
         g_pi, g_v, g_ls, stats = out
-        _need(g_pi, "out g_pi", (*lead, A, 4), _F32, dev)
-        _need(g_v, "out g_v", (*lead, A, 4), _F32, dev)
+        need(g_pi, "out g_pi", (*lead, A, 4), _F32)
+        need(g_v, "out g_v", (*lead, A, 4), _F32)
         if k == 1:
-            _need(g_ls, "out g_log_std", (A, 3), _F32, dev)
-        _need(stats, "out stats", (8,), (torch.float64,), dev)
-    nb = ppo_head_workspace_bytes(R, A)
-    if workspace is None:
-        workspace = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
-    if (not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous()
-            or workspace.numel() * workspace.element_size() < nb):
-        raise ValueError(f"workspace must be a contiguous tensor of at least {nb} bytes on {dev}")
+            need(g_ls, "out g_log_std", (A, 3), _F32)
+        need(stats, "out stats", (8,), (torch.float64,))
+    workspace = _workspace(workspace, ppo_head_workspace_bytes(R, A), dev)
     io = _lib.BsxPpoIo(y.data_ptr(), v.data_ptr(), rec.data_ptr(), logp_old.data_ptr(), adv.data_ptr(), ret.data_ptr(), mask.data_ptr(),
                        v_old.data_ptr() if v_old is not None else None, log_std.data_ptr() if k == 1 else None,
                        g_pi.data_ptr(), g_v.data_ptr(), g_ls.data_ptr() if k == 1 else None)
@@ -327,15 +319,15 @@ class AdamState:
 
 def adam_hyper(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, device="cuda"):
     """adam_step's `hyper`: float32 [8] on the device in the order of learner.HYPER; max_grad_norm None (or 0) = no clipping."""
-    lr = _number(lr, "lr", lambda x: x >= 0.0, "a number >= 0")
+    lr = _hyper("lr", lr)
     try:
         b1, b2 = betas
     except (TypeError, ValueError):
         raise ValueError(f"betas must be a pair of numbers in [0, 1), got {betas!r}") from None
-    b1 = _number(b1, "betas[0]", lambda x: 0.0 <= x < 1.0, "a number in [0, 1)")
-    b2 = _number(b2, "betas[1]", lambda x: 0.0 <= x < 1.0, "a number in [0, 1)")
-    eps = _number(eps, "eps", lambda x: x >= 0.0, "a number >= 0")
-    mgn = 0.0 if max_grad_norm is None else _number(max_grad_norm, "max_grad_norm", lambda x: x >= 0.0, "a number >= 0")
+    b1 = _hyper("betas[0]", b1)
+    b2 = _hyper("betas[1]", b2)
+    eps = _hyper("eps", eps)
+    mgn = 0.0 if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm)
     return torch.tensor([lr, b1, b2, eps, mgn, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
 
 
@@ -375,6 +367,7 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     if A < 2 or A % 2 or A > 2 * _lib.MAX_N or D != 3 * (A // 2) + 2:
         raise ValueError(f"nets[0] has {A} agents and obs_len {D}: an even A in 2 .. {2 * _lib.MAX_N} and D = 3 A / 2 + 2 are needed")
     G = grad_floats(D)
+    need = partial(_need, dev=dev, anchor="y")                   # ("y": the wording these messages have always had)
     io = _lib.BsxAdamIo()
     io.nets = len(nets)
     for i, (net, g, st, blob) in enumerate(zip(nets, grads, states, blobs)):
@@ -385,16 +378,15 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
         na = net.n_actions
         if na not in (1, 3, 4):
             raise ValueError(f"nets[{i}].n_actions must be 1, 3 or 4, got {na}")
-        shapes = [(A, D, H)] + [(A, 1, H)] * 3 + [(A, H, H)] + [(A, 1, H)] * 3 + [(A, H, na), (A, 1, na)]
-        for q, (k, shape) in enumerate(zip(PARAMS, shapes)):
-            _need(getattr(net, k), f"nets[{i}].{k}", shape, _F32, dev)
+        for q, (k, rows, cols, cut) in enumerate(_TABLE):
+            need(getattr(net, k), f"nets[{i}].{k}", (A, rows(D), na if cut else cols), _F32)
             io.net[i].p[q] = getattr(net, k).data_ptr()
         if not isinstance(st, AdamState):
             raise TypeError(f"states[{i}] must be an AdamState")
-        _need(g, f"grads[{i}]", (A, G), _F32, dev)
-        _need(st.m, f"states[{i}].m", (A, G), _F32, dev)
-        _need(st.v, f"states[{i}].v", (A, G), _F32, dev)
-        _need(blob, f"blobs[{i}]", (A, blob_floats(D)), _F32, dev)
+        need(g, f"grads[{i}]", (A, G), _F32)
+        need(st.m, f"states[{i}].m", (A, G), _F32)
+        need(st.v, f"states[{i}].v", (A, G), _F32)
+        need(blob, f"blobs[{i}]", (A, blob_floats(D)), _F32)
         io.net[i].grad, io.net[i].m, io.net[i].v, io.net[i].blob, io.net[i].n_actions = g.data_ptr(), st.m.data_ptr(), st.v.data_ptr(), blob.data_ptr(), na
     given = [x is not None for x in (log_std, g_log_std, log_std_state)]
     if any(given) and not all(given):
@@ -402,24 +394,19 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     if all(given):
         if not isinstance(log_std_state, AdamState):
             raise TypeError("log_std_state must be an AdamState")
-        _need(log_std, "log_std", (A, 3), _F32, dev)
-        _need(g_log_std, "g_log_std", (A, 3), _F32, dev)
-        _need(log_std_state.m, "log_std_state.m", (A, 3), _F32, dev)
-        _need(log_std_state.v, "log_std_state.v", (A, 3), _F32, dev)
+        need(log_std, "log_std", (A, 3), _F32)
+        need(g_log_std, "g_log_std", (A, 3), _F32)
+        need(log_std_state.m, "log_std_state.m", (A, 3), _F32)
+        need(log_std_state.v, "log_std_state.v", (A, 3), _F32)
         io.log_std, io.g_log_std, io.m_ls, io.v_ls = log_std.data_ptr(), g_log_std.data_ptr(), log_std_state.m.data_ptr(), log_std_state.v.data_ptr()
-    _need(hyper, "hyper", (8,), _F32, dev)
+    need(hyper, "hyper", (8,), _F32)
     if not isinstance(step, torch.Tensor):
         raise TypeError("step must be a torch.Tensor")
-    _need(step, "step", tuple(step.shape) if step.numel() == 1 else (1,), (torch.int64,), dev)
+    need(step, "step", tuple(step.shape) if step.numel() == 1 else (1,), (torch.int64,))
     if stats is None:
         stats = torch.empty(4, dtype=torch.float64, device=dev)
-    _need(stats, "stats", (4,), (torch.float64,), dev)
-    nb = adam_step_workspace_bytes(A // 2, len(nets))
-    if workspace is None:
-        workspace = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
-    if (not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous()
-            or workspace.numel() * workspace.element_size() < nb):
-        raise ValueError(f"workspace must be a contiguous tensor of at least {nb} bytes on {dev}")
+    need(stats, "stats", (4,), (torch.float64,))
+    workspace = _workspace(workspace, adam_step_workspace_bytes(A // 2, len(nets)), dev)
     io.hyper, io.step = hyper.data_ptr(), step.data_ptr()
     _lib.check(_lib.load().bsx_adam_step(_lib.ctypes.byref(io), A // 2, workspace.data_ptr(), stats.data_ptr(),
                                          torch.cuda.current_stream(dev).cuda_stream), "bsx_adam_step")
@@ -484,12 +471,12 @@ class PPOLearner:
         self.kind = "gaussian" if ro._gauss is not None else "categorical"
         self.temperature = ro._sample["temperature"] if self.kind == "categorical" else 1.0
         self.log_std = ro.log_std if self.kind == "gaussian" else None
-        self.clip = _number(clip, "clip", lambda x: 0.0 < x < 1.0, "a number in (0, 1)")
-        self.c_v = _number(c_v, "c_v", lambda x: x >= 0.0, "a number >= 0")
-        self.c_e = _number(c_e, "c_e", lambda x: x >= 0.0, "a number >= 0")
-        self.vclip = None if vclip is None else _number(vclip, "vclip", lambda x: x > 0.0, "a number > 0")
+        self.clip = _hyper("clip", clip)
+        self.c_v = _hyper("c_v", c_v)
+        self.c_e = _hyper("c_e", c_e)
+        self.vclip = None if vclip is None else _hyper("vclip", vclip)
         self.epochs, self.minibatches = epochs, minibatches
-        self.max_grad_norm = None if max_grad_norm is None else _number(max_grad_norm, "max_grad_norm", lambda x: x > 0.0, "a number > 0")
+        self.max_grad_norm = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)   # (no clipping is None here)
         _check(self.actor, ro.obs[:1])
         _check(self.critic, ro.obs[:1])
         self.params = [getattr(self.actor, k) for k in PARAMS] + [getattr(self.critic, k) for k in PARAMS]
@@ -506,7 +493,7 @@ class PPOLearner:
             self.adam_a, self.adam_v = AdamState(self.actor), AdamState(self.critic)
             self.adam_ls = AdamState(self.log_std) if self.log_std is not None else None
             self.step_stats = torch.zeros((epochs * minibatches, 4), dtype=torch.float64, device=dev)
-            self._adam_ws = torch.empty((adam_step_workspace_bytes(self.actor.n_actors // 2, 2) + 7) // 8, dtype=torch.int64, device=dev)
+            self._adam_ws = _workspace(None, adam_step_workspace_bytes(self.actor.n_actors // 2, 2), dev)
             self._blob_a, self._blob_v = ro.fused.weights, ro._value_w       # the step packs into the blobs the rollout plays from
         else:
             self.optimizer = optimizer if optimizer is not None else torch.optim.Adam(self.params, lr=lr, betas=betas, eps=eps)
@@ -522,7 +509,7 @@ class PPOLearner:
             self._by_rows[R] = dict(y=f(R, A, 4), v=f(R, A), g_pi=f(R, A, 4), g_v=f(R, A, 4),
                                     g_ls=f(A, 3) if self.kind == "gaussian" else None,
                                     stats=torch.empty(8, dtype=torch.float64, device=dev),
-                                    ws=torch.empty((ppo_head_workspace_bytes(R, A) + 7) // 8, dtype=torch.int64, device=dev))
+                                    ws=_workspace(None, ppo_head_workspace_bytes(R, A), dev))
         return self._by_rows[R]
 
     def minibatch_grads(self, t0, t1, pack=True, stats=None):
@@ -542,10 +529,7 @@ class PPOLearner:
         if pack:
             self.actor.pack(out=self._blob_a)
             self.critic.pack(out=self._blob_v)
-        nz = _lib.BsxActorNoise()
-        nz.value_weights, nz.value = self._blob_v.data_ptr(), b["v"].data_ptr()
-        _lib.check(lib.bsx_actor_forward(self._blob_a.data_ptr(), obs.data_ptr(), b["y"].data_ptr(), R, n, _lib.ACTOR_F32, _lib.ctypes.byref(nz),
-                                         0, 0, None, 0, torch.cuda.current_stream(dev).cuda_stream), "bsx_actor_forward")
+        _actor_forward(lib, self._blob_a, obs, b["y"], self._blob_v, b["v"])
         flat = lambda x: x[t0:t1].view(R, A, *x.shape[3:])                           # noqa: E731
         head = ppo_head(self.kind, b["y"], b["v"], flat(ro.scores), flat(ro.logp), flat(ro.adv), flat(ro.ret), flat(ro._mask),
                         clip=self.clip, c_v=self.c_v, c_e=self.c_e, temperature=self.temperature, log_std=self.log_std,
@@ -570,6 +554,13 @@ class PPOLearner:
                     self.log_std.grad = torch.empty_like(self.log_std)
                 self.log_std.grad.copy_(g_log_std)
 
+    def _schedule(self):
+        """(i, t0, t1) of the optimiser steps of one update: epochs x minibatches, the minibatches in tick order in every epoch."""
+        span = self.rollout.T // self.minibatches
+        for i in range(self.epochs * self.minibatches):
+            m = i % self.minibatches
+            yield i, m * span, (m + 1) * span
+
     def update(self):
         """epochs x minibatches optimiser steps over the rollout's current records, the minibatches in tick order in every epoch; then the
         rollout's packed weights are refreshed.  -> stats f64 [epochs * minibatches, 8] on the device (a cached buffer; no host sync)."""
@@ -580,16 +571,13 @@ class PPOLearner:
             else:
                 self._device_update()
             return self.stats
-        span, i = ro.T // self.minibatches, 0
-        for _ in range(self.epochs):
-            for m in range(self.minibatches):
-                row_a, row_v, g_ls, stats = self.minibatch_grads(m * span, (m + 1) * span)
-                self.install(row_a, row_v, g_ls)
-                if self.max_grad_norm is not None:
-                    torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
-                self.optimizer.step()
-                self.stats[i].copy_(stats)
-                i += 1
+        for i, t0, t1 in self._schedule():
+            row_a, row_v, g_ls, stats = self.minibatch_grads(t0, t1)
+            self.install(row_a, row_v, g_ls)
+            if self.max_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+            self.optimizer.step()
+            self.stats[i].copy_(stats)
         ro.fused.refresh()
         self.critic.pack(out=ro._value_w)
         return self.stats
@@ -602,15 +590,12 @@ class PPOLearner:
     def _device_update(self):
         """epochs x minibatches times: the five-launch minibatch on the blobs as they stand, the head's statistics straight into
         stats[i], then adam_step on the rows.  Cached buffers only; no host synchronisation."""
-        span, i = self.rollout.T // self.minibatches, 0
         ls = self.log_std
-        for _ in range(self.epochs):
-            for m in range(self.minibatches):
-                row_a, row_v, g_ls, _ = self.minibatch_grads(m * span, (m + 1) * span, pack=False, stats=self.stats[i])
-                adam_step([self.actor, self.critic], [row_a, row_v], [self.adam_a, self.adam_v], [self._blob_a, self._blob_v], self.hyper,
-                          self.step_count, log_std=ls, g_log_std=g_ls if ls is not None else None, log_std_state=self.adam_ls,
-                          stats=self.step_stats[i], workspace=self._adam_ws)
-                i += 1
+        for i, t0, t1 in self._schedule():
+            row_a, row_v, g_ls, _ = self.minibatch_grads(t0, t1, pack=False, stats=self.stats[i])
+            adam_step([self.actor, self.critic], [row_a, row_v], [self.adam_a, self.adam_v], [self._blob_a, self._blob_v], self.hyper,
+                      self.step_count, log_std=ls, g_log_std=g_ls if ls is not None else None, log_std_state=self.adam_ls,
+                      stats=self.step_stats[i], workspace=self._adam_ws)
 
     def _state(self):
         """Every tensor an update writes that outlives it."""
@@ -624,7 +609,7 @@ class PPOLearner:
         """The learning rate of the steps from now on, written to `hyper` on the device (a fill on the current stream: no host
         synchronisation); a captured update reads it at every replay."""
         self._need_device_step("set_lr")
-        self.hyper[0].fill_(_number(lr, "lr", lambda x: x >= 0.0, "a number >= 0"))
+        self.hyper[0].fill_(_hyper("lr", lr))
 
     def sync(self):
         """Re-pack both blobs from the parameters, once: for a caller who has edited the parameters from outside (loaded a checkpoint)."""
