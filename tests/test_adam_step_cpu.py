@@ -1,5 +1,6 @@
 """The fused optimiser step without a GPU: the float64 restatement the GPU tests measure against (tests/adam_util.py) is pinned to
-torch's own clip_grad_norm_ + Adam in float64, the row layout to learner.split_grad, and the C entry points' refusals are host-only."""
+torch's own clip_grad_norm_ + Adam in float64, the row layout and the pad mask to learner.split_grad, the integer restatement of the blob's
+bfloat16 split to CPU StackedActor.pack() at weights that force every rounding case, and the C entry points' refusals are host-only."""
 import ctypes
 
 import numpy as np
@@ -60,6 +61,64 @@ def test_the_row_layout_matches_split_grad_and_round_trips():
         tail = row[:, -(64 * 4 + 4):].view(A, 65, 4)
         assert bool((tail[:, :, na:] == 0).all()) and bool((tail[:, :, :na] != 0).all())
         assert learner.blob_floats(D) == 64 * (D + D % 2) + 10884
+
+
+def test_the_pad_mask_marks_exactly_the_row_elements_no_parameter_stands_behind():
+    """Against row_to_tensors (itself pinned to learner.split_grad above): the elements of a row that reach one of the ten tensors are
+    the unmasked ones, in order; random_rows holds +0 exactly where the mask is set."""
+    gen = torch.Generator().manual_seed(7)
+    for A, D, na in ((2, 5, 4), (6, 11, 3), (4, 8, 1)):
+        G = U.grad_floats(D)
+        mask = U.pad_mask(D, na)
+        assert mask.shape == (G,) and mask.dtype == np.bool_ and int(mask.sum()) == 65 * (4 - na)
+        assert not mask[:G - 260].any()
+        assert np.array_equal(mask[G - 260:].reshape(65, 4), np.broadcast_to(np.arange(4) >= na, (65, 4)))
+        row = np.arange(A * G, dtype=np.float64).reshape(A, G)
+        kept = np.concatenate([t.reshape(A, -1) for t in U.row_to_tensors(row, na)], axis=1)
+        assert np.array_equal(kept, row[:, ~mask])
+        rnd = U.random_rows(A, D, na, gen).numpy()
+        assert np.array_equal(rnd == 0, np.broadcast_to(mask, (A, G))) and not np.signbit(rnd[:, mask]).any()
+
+
+def test_the_integer_restatement_of_the_bf16_split_is_pack_where_rounding_is_decided():
+    """w2 = adam_util.w2_edge_weights: ties, one bit either side of them, carries into the exponent, +-0, exponents -60 .. 60.  The W2B
+    part of CPU StackedActor.pack() equals adam_util.w2b_words on every element, for a 4-column and a 1-column network, and the three terms sum to
+    the weight exactly (3 x 8 significant bits cover float32's 24).  Non-finite weights are a diverged run and are not covered."""
+    from deep_rl_battlespace_amd.rollout import StackedActor
+    A, D = 4, 8
+    w2 = U.w2_edge_weights(A, seed=11)
+    bits = w2.view(np.uint32)
+    # the set is what it says: every crafted pattern in every agent, both zeros, exponents inside +-60, nothing non-finite
+    for a in range(A):
+        have = set(bits[a].ravel().tolist())
+        assert {0x00000000, 0x80000000} <= have
+        for e in U.W2_EDGE_EXPONENTS:
+            for up in U.W2_EDGE_UPPER:
+                for lo in U.W2_EDGE_LOW:
+                    assert {((e + 127) << 23) | (up << 16) | lo, (1 << 31) | ((e + 127) << 23) | (up << 16) | lo} <= have
+    expo = ((bits >> 23) & 0xff).astype(np.int64) - 127
+    nz = (bits & 0x7fffffff) != 0
+    assert expo[nz].min() == -60 and expo[nz].max() == 60 and int((~nz).sum()) == 2 * A
+    assert not np.array_equal(bits[0], bits[1])                                 # shuffled per agent
+    # the rounding rule on a few patterns by hand: below a tie, ties to even, above a tie, the carry into the exponent, -0
+    hand = np.array([0x3f807fff, 0x3f808000, 0x3f818000, 0x3f808001, 0x3fffffff, 0x3fff8000, 0x80000000], dtype=np.uint32)
+    assert U.bf16_rne_bits(hand).tolist() == [0x3f80, 0x3f80, 0x3f82, 0x3f81, 0x4000, 0x4000, 0x8000]
+    assert np.array_equal(U.bf16_rne_bits(bits), torch.from_numpy(w2.copy()).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16))
+    h, m, l = U.w2b_split(w2)
+    total = sum(U.bf16_bits_to_float(x).astype(np.float64) for x in (h, m, l))
+    assert np.array_equal(total, w2.astype(np.float64))
+    for x in (h, m, l):                                                           # no term is subnormal or non-finite
+        e = (x >> 7) & 0xff
+        assert bool(((e != 0xff) & ((e != 0) | ((x & 0x7f) == 0))).all())
+    for na in (4, 1):
+        net = StackedActor(A, D, na)
+        with torch.no_grad():
+            net.w2.copy_(torch.from_numpy(w2.copy()))
+        blob = net.pack().numpy().view(np.uint32)
+        assert blob.shape[1] == 64 * D + 10884 and U.W2B_FLOATS == 6144
+        mine = U.w2b_words(w2)
+        bad = np.argwhere(blob[:, -U.W2B_FLOATS:] != mine)
+        assert bad.size == 0, bad[:4].tolist()
 
 
 def test_the_c_entry_points_refuse_what_the_header_documents_before_any_launch():
