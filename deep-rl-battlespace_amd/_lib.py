@@ -82,6 +82,13 @@ class BsxAdamIo(ctypes.Structure):
                 ("v_ls", c_void_p), ("hyper", c_void_p), ("step", c_void_p)]
 
 
+MINIBATCH_FIELDS = ("obs", "rec", "logp", "adv", "ret", "value", "mask")
+
+
+class BsxMinibatchIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in MINIBATCH_FIELDS + tuple("dst_" + f for f in MINIBATCH_FIELDS) + ("idx",)]
+
+
 # name -> (restype, argtypes): every symbol include/battlespace_hip.h declares
 SIGNATURES = {
     "bsx_abi_version": (c_int, []),
@@ -142,6 +149,9 @@ SIGNATURES = {
                              ctypes.c_float, c_void_p, c_void_p, c_void_p]),
     "bsx_adam_step_workspace_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_adam_step": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
+                                     c_void_p]),
 }
 
 _lib = None

@@ -52,7 +52,9 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            # the PPO loss head: float32 element-wise terms held to a float64 reference, not to bits: contraction allowed
            (os.path.join(CSRC, "bsx_ppo_head.hip"), []),
            # the optimiser step (clip + Adam + pack): float32 element-wise, held to a float64 reference; the blob it packs is bit copies
-           (os.path.join(CSRC, "bsx_adam_step.hip"), [])]
+           (os.path.join(CSRC, "bsx_adam_step.hip"), []),
+           # the keyed row permutation and the minibatch gather: integer arithmetic and bit copies
+           (os.path.join(CSRC, "bsx_shuffle.hip"), [])]
 
 
 def _stale():

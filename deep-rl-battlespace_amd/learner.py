@@ -14,8 +14,11 @@ weights.  Deterministic (no floating-point atomics): the same inputs give the sa
                                                                 and a rollout's records to both grad_out tensors, one pass (bsx_ppo_head)
   AdamState(net_or_log_std), adam_step(nets, grads, states, ...) clip_grad_norm_ + Adam.step() + pack() of one or two networks (and log_std)
                                                                 as two launches: rows in, parameters, moments and packed blobs out (bsx_adam_step)
+  shuffle_rows(N, first, R, seed, seq, ...)                     a keyed permutation of [0, N) evaluated per position (bsx_shuffle_rows)
+  minibatch_gather(src, dst, first, R, seed, seq, ...)          one shuffled minibatch's records through it, one launch (bsx_minibatch_gather)
   PPOLearner(rollout, ...)                                      minibatch_grads / update: the PPO update of a PolicyRollout's networks;
-                                                                device_step=True: the whole update on device, capture() makes it one graph
+                                                                device_step=True: the whole update on device, capture() makes it one graph;
+                                                                shuffle=True: a fresh permutation of the T x E rows per epoch
 """
 from collections import namedtuple
 from functools import partial
@@ -413,6 +416,101 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     return stats
 
 
+# ------------------------------------------------------------------------------------------------ shuffled minibatches
+GATHER_ROWS = 32                         # destination rows per workgroup of bsx_minibatch_gather (csrc/bsx_shuffle.hip: ROWS)
+_I64 = (torch.int64,)
+# One minibatch's records, source or destination: obs f32 [rows, A, D], rec f32 [rows, A, 4], logp, adv, ret f32 [rows, A], mask uint8 or
+# bool [rows, A], value f32 [rows, A] or None, and on the destination idx int64 [rows]
+Minibatch = namedtuple("Minibatch", "obs rec logp adv ret mask value idx", defaults=(None, None))
+
+
+def _word(x, name):
+    """int(x) in [0, 2^64): a Philox seed or sequence number."""
+    if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x < 1 << 64:
+        raise ValueError(f"{name} must be an int in [0, 2^64), got {x!r}")
+    return x
+
+
+def _rows(N, first, R):
+    """(N, first, R) as ints: 1 <= N < 2^31 and a non-empty range [first, first + R) inside [0, N)."""
+    N, first, R = int(N), int(first), int(R)
+    if not 1 <= N < 1 << 31:
+        raise ValueError(f"N must be in [1, 2^31), got {N}")
+    if R < 1 or first < 0 or first + R > N:
+        raise ValueError(f"rows [{first}, {first} + {R}) are not a non-empty range inside [0, {N})")
+    return N, first, R
+
+
+def _seq_base(seq_base, dev):
+    if seq_base is None:
+        return None
+    if not isinstance(seq_base, torch.Tensor):
+        raise TypeError("seq_base must be a torch.Tensor")
+    _need(seq_base, "seq_base", tuple(seq_base.shape) if seq_base.numel() == 1 else (1,), _I64, dev, "the call's tensors")
+    return seq_base.data_ptr()
+
+
+def shuffle_rows(N, first, R, seed, seq, seq_base=None, out=None, device="cuda"):
+    """Positions [first, first + R) of the keyed permutation of [0, N) (csrc/bsx_shuffle.hip, `bsx_shuffle_rows`; the construction is
+    written out in include/battlespace_hip.h) -> int64 [R] on the device: the source row of every position.  A bijection of [0, N) for
+    every (seed, seq + seq_base): seed, seq ints in [0, 2^64); seq_base an int64 device tensor of one element, read on the device at
+    every launch (a captured call draws afresh once the caller advances it), or None.  One launch on the current stream, no host
+    synchronisation.  out: an int64 [R] tensor to write into (nothing is allocated then); its device is the call's."""
+    N, first, R = _rows(N, first, R)
+    seed, seq = _word(seed, "seed"), _word(seq, "seq")
+    if out is None:
+        out = torch.empty(R, dtype=torch.int64, device=device)
+    elif not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a torch.Tensor")
+    dev = out.device
+    if dev.type != "cuda":
+        raise ValueError("shuffle_rows runs on the GPU: out is on " + str(dev))
+    _need(out, "out", (R,), _I64, dev, "out")
+    _lib.check(_lib.load().bsx_shuffle_rows(N, first, R, seed, seq, _seq_base(seq_base, dev), out.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "bsx_shuffle_rows")
+    return out
+
+
+def minibatch_gather(src, dst, first, R, seed, seq, seq_base=None):
+    """One minibatch of a shuffled epoch in one launch (csrc/bsx_shuffle.hip, `bsx_minibatch_gather`): for r in [0, R), dst.idx[r] =
+    perm(first + r) and row r of every field of dst = row dst.idx[r] of src, bit for bit -> dst.
+
+    src, dst: a learner.Minibatch (or any sequence in its order).  src holds the N rows the permutation is over -- obs f32 [N, A, D]
+    (leading axes are flattened: a rollout's [T, E, A, D] records are N = T E rows), rec f32 [N, A, 4], logp, adv, ret f32 [N, A], mask
+    uint8 or bool [N, A], value f32 [N, A] or None --, dst the same fields with R rows and idx int64 [R]; value on both sides or on
+    neither.  seed, seq, seq_base: shuffle_rows'.  The M calls first = m R of one (seed, seq) hold every source row exactly once.
+    Contiguous tensors on one GPU; dst must not overlap src.  No host synchronisation, nothing allocated."""
+    src, dst = Minibatch(*src), Minibatch(*dst)
+    obs = src.obs
+    if not isinstance(obs, torch.Tensor) or obs.dim() < 3:
+        raise ValueError("src.obs must be a float32 [N, A, D] tensor")
+    dev, A, D = obs.device, obs.shape[-2], obs.shape[-1]
+    if dev.type != "cuda":
+        raise ValueError("minibatch_gather runs on the GPU: src.obs is on " + str(dev))
+    if A < 2 or A % 2 or A > 2 * _lib.MAX_N or not 1 <= D <= 3 * _lib.MAX_N + 2:
+        raise ValueError(f"src.obs has shape {tuple(obs.shape)}: an even A in 2 .. {2 * _lib.MAX_N} and D in 1 .. {3 * _lib.MAX_N + 2} are needed")
+    lead = tuple(obs.shape[:-2])
+    N, first, R = _rows(obs.numel() // (A * D), first, R)
+    seed, seq = _word(seed, "seed"), _word(seq, "seq")
+    if (src.value is None) != (dst.value is None):
+        raise ValueError("value goes on both sides or on neither: src.value and dst.value")
+    need = partial(_need, dev=dev, anchor="src.obs")
+    io = _lib.BsxMinibatchIo()
+    for side, t, rows, pre in (("src", src, lead, ""), ("dst", dst, (R,), "dst_")):
+        for f, tail, dtypes in (("obs", (A, D), _F32), ("rec", (A, 4), _F32), ("logp", (A,), _F32), ("adv", (A,), _F32), ("ret", (A,), _F32),
+                                ("mask", (A,), _FLAG), ("value", (A,), _F32)):
+            x = getattr(t, f)
+            if f == "value" and x is None:
+                continue
+            need(x, f"{side}.{f}", (*rows, *tail), dtypes)
+            setattr(io, pre + f, x.data_ptr())
+    need(dst.idx, "dst.idx", (R,), _I64)
+    io.idx = dst.idx.data_ptr()
+    _lib.check(_lib.load().bsx_minibatch_gather(_lib.ctypes.byref(io), N, first, R, A, D, seed, seq, _seq_base(seq_base, dev),
+                                                torch.cuda.current_stream(dev).cuda_stream), "bsx_minibatch_gather")
+    return dst
+
+
 def blob_floats(obs_len):
     """Floats per agent of the packed blob bsx_actor_forward reads (StackedActor.pack()): bsx_actor_blob_floats."""
     nf = _lib.c_int()
@@ -453,12 +551,21 @@ class PPOLearner:
     from outside calls sync() to re-pack both blobs.  capture() records the whole update -- epochs x minibatches steps -- as ONE graph
     on one stream; update() replays it from then on.
 
+    shuffle=True: every epoch cuts a fresh permutation of the T x E rows into the minibatches, instead of the same tick ranges in the same
+    order.  Optimiser step i (epoch j = i // minibatches, minibatch m = i % minibatches) starts with ONE minibatch_gather of rows
+    [m R, (m + 1) R), R = T E / minibatches, of the permutation keyed by (shuffle_seed, j + shuffle_base) into cached buffers of the
+    unshuffled minibatch's size (shuffled_grads); the forward, the head, both backward calls and the step run on those.  `minibatch_idx`
+    (int64 [epochs * minibatches, R]) holds the source rows of every step; `shuffle_base` (an int64 device word) moves by `epochs` at the
+    end of every update, on the stream and inside a captured update, so every update and every replay shuffles afresh with no host work.
+    Both optimiser paths take it.  shuffle_seed: an int in [0, 2^64); None takes the rollout's seed (the permutation's stream has a salt of
+    its own).  shuffle=False (the default) is the tick-range path, bit for bit.
+
     rollout: a PolicyRollout with sample="categorical" or "gaussian", a value_actor and gae= (ValueError otherwise).  vclip: clip the
     value loss around the rollout's recorded values.  optimizer: any torch optimiser over the parameters, instead of Adam(lr, betas, eps)
     (a ValueError with device_step=True)."""
 
     def __init__(self, rollout, *, clip=0.2, c_v=0.5, c_e=0.01, vclip=None, epochs=4, minibatches=4, lr=3e-4, max_grad_norm=None, optimizer=None,
-                 device_step=False, betas=(0.9, 0.999), eps=1e-8):
+                 device_step=False, betas=(0.9, 0.999), eps=1e-8, shuffle=False, shuffle_seed=None):
         ro = rollout
         if getattr(ro, "_sample", None) is None and getattr(ro, "_gauss", None) is None:
             raise ValueError("PPOLearner needs a PolicyRollout with sample='categorical' or 'gaussian' (it reads the recorded logp)")
@@ -467,6 +574,12 @@ class PPOLearner:
         epochs, minibatches = int(epochs), int(minibatches)
         if epochs < 1 or minibatches < 1 or ro.T % minibatches:
             raise ValueError(f"epochs >= 1 and a minibatches >= 1 that divides T = {ro.T} are needed (a minibatch is a range of whole ticks)")
+        if not isinstance(shuffle, bool):
+            raise ValueError(f"shuffle must be True or False, got {shuffle!r}")
+        if shuffle_seed is not None and not shuffle:
+            raise ValueError("shuffle_seed belongs to shuffle=True")
+        self.shuffle = shuffle
+        self.shuffle_seed = (int(ro.fused.seed) & ((1 << 64) - 1) if shuffle_seed is None else _word(shuffle_seed, "shuffle_seed")) if shuffle else None
         self.rollout, self.actor, self.critic = ro, ro.actor, ro.value_actor
         self.kind = "gaussian" if ro._gauss is not None else "categorical"
         self.temperature = ro._sample["temperature"] if self.kind == "categorical" else 1.0
@@ -500,6 +613,14 @@ class PPOLearner:
             self._blob_a, self._blob_v = torch.empty_like(ro.fused.weights), torch.empty_like(ro._value_w)
         self._by_rows = {}
         self.stats = torch.zeros((epochs * minibatches, 8), dtype=torch.float64, device=dev)
+        if shuffle:
+            T, E, A, D = ro.T, *ro.obs.shape[1:]
+            R = T * E // minibatches
+            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+            self.shuffle_base = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.minibatch_idx = torch.zeros((epochs * minibatches, R), dtype=torch.int64, device=dev)
+            self._gathered = Minibatch(f(R, A, D), f(R, A, 4), f(R, A), f(R, A), f(R, A), torch.empty((R, A), dtype=torch.uint8, device=dev),
+                                       f(R, A) if self.vclip is not None else None)
 
     def _head_buffers(self, R):
         """The forward's outputs and the head's, per row count: allocated once."""
@@ -518,22 +639,49 @@ class PPOLearner:
         buffers that the next call with the same tick count overwrites.  pack=False: the learner's blobs already hold the current
         parameters (adam_step wrote them) -- three launches fewer and no temporaries.  stats: an f64 [8] tensor the head writes
         instead of the cached one."""
-        ro, lib = self.rollout, _lib.load()
+        ro = self.rollout
         t0, t1 = int(t0), int(t1)
         if not 0 <= t0 < t1 <= ro.T:
             raise ValueError(f"ticks [{t0}, {t1}) are not a range inside the rollout's T = {ro.T}")
-        E, A, D = ro.obs.shape[1:]
-        n, R, dev = A // 2, (t1 - t0) * E, ro.obs.device
+        E, A = ro.obs.shape[1:3]
+        R = (t1 - t0) * E
+        flat = lambda x: x[t0:t1].view(R, A, *x.shape[3:])                           # noqa: E731
+        return self._grads(Minibatch(flat(ro.obs), flat(ro.scores), flat(ro.logp), flat(ro.adv), flat(ro.ret), flat(ro._mask),
+                                     flat(ro.value) if self.vclip is not None else None), pack, stats)
+
+    def shuffled_grads(self, i, pack=True, stats=None):
+        """minibatch_grads for optimiser step i of a shuffled update (shuffle=True): epoch j = i // minibatches, minibatch m = i %
+        minibatches.  ONE bsx_minibatch_gather -- N = T E rows, first = m R, R = T E / minibatches, keyed by (shuffle_seed, j +
+        shuffle_base) -- copies the step's rows of obs[:T], scores, logp, adv, ret, mask (and value, with vclip) into cached buffers
+        and their source rows into minibatch_idx[i]; the forward, the head and the two backward calls then run on those."""
+        return self._grads(self._gather(i), pack, stats)
+
+    def _gather(self, i):
+        """Step i's rows into the cached buffers and their source rows into minibatch_idx[i] -> the buffers, a Minibatch."""
+        if not self.shuffle:
+            raise ValueError("shuffled_grads needs PPOLearner(shuffle=True)")
+        ro, i = self.rollout, int(i)
+        if not 0 <= i < self.epochs * self.minibatches:
+            raise ValueError(f"step {i} is not one of the {self.epochs * self.minibatches} steps of an update")
+        T, R = ro.T, self.minibatch_idx.shape[1]
+        src = Minibatch(ro.obs[:T], ro.scores, ro.logp, ro.adv, ro.ret, ro._mask, ro.value if self.vclip is not None else None)
+        minibatch_gather(src, self._gathered._replace(idx=self.minibatch_idx[i]), (i % self.minibatches) * R, R, self.shuffle_seed,
+                         i // self.minibatches, self.shuffle_base)
+        return self._gathered
+
+    def _grads(self, mb, pack, stats):
+        """The five calls of a minibatch on its records `mb` (a Minibatch of R contiguous rows: views of a tick range, or gathered)."""
+        lib, obs = _lib.load(), mb.obs
+        R, A = obs.shape[:2]
+        n, dev = A // 2, obs.device
         b = self._head_buffers(R)
-        obs = ro.obs[t0:t1].view(R, A, D)
         if pack:
             self.actor.pack(out=self._blob_a)
             self.critic.pack(out=self._blob_v)
         _actor_forward(lib, self._blob_a, obs, b["y"], self._blob_v, b["v"])
-        flat = lambda x: x[t0:t1].view(R, A, *x.shape[3:])                           # noqa: E731
-        head = ppo_head(self.kind, b["y"], b["v"], flat(ro.scores), flat(ro.logp), flat(ro.adv), flat(ro.ret), flat(ro._mask),
+        head = ppo_head(self.kind, b["y"], b["v"], mb.rec, mb.logp, mb.adv, mb.ret, mb.mask,
                         clip=self.clip, c_v=self.c_v, c_e=self.c_e, temperature=self.temperature, log_std=self.log_std,
-                        v_old=flat(ro.value) if self.vclip is not None else None, vclip=self.vclip,
+                        v_old=mb.value, vclip=self.vclip,
                         out=(b["g_pi"], b["g_v"], b["g_ls"], b["stats"] if stats is None else stats), workspace=b["ws"])
         # the head's outputs ARE bsx_actor_grad's grad_out (four columns, the unused ones +0): fused_grad's call without its padded copy
         row_a = _actor_grad(lib, _buffers(self.actor).get(R, n, dev, lib, go=False), self._blob_a, obs, head.g_pi, True)
@@ -562,8 +710,8 @@ class PPOLearner:
             yield i, m * span, (m + 1) * span
 
     def update(self):
-        """epochs x minibatches optimiser steps over the rollout's current records, the minibatches in tick order in every epoch; then the
-        rollout's packed weights are refreshed.  -> stats f64 [epochs * minibatches, 8] on the device (a cached buffer; no host sync)."""
+        """epochs x minibatches optimiser steps over the rollout's current records, the minibatches in tick order in every epoch (shuffle=True:
+        a fresh permutation of the rows per epoch); then the rollout's packed weights are refreshed.  -> stats f64 [epochs * minibatches, 8] on the device (a cached buffer; no host sync)."""
         ro = self.rollout
         if self.device_step:
             if self._graph is not None:
@@ -572,7 +720,7 @@ class PPOLearner:
                 self._device_update()
             return self.stats
         for i, t0, t1 in self._schedule():
-            row_a, row_v, g_ls, stats = self.minibatch_grads(t0, t1)
+            row_a, row_v, g_ls, stats = self.shuffled_grads(i) if self.shuffle else self.minibatch_grads(t0, t1)
             self.install(row_a, row_v, g_ls)
             if self.max_grad_norm is not None:
                 torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
@@ -580,6 +728,8 @@ class PPOLearner:
             self.stats[i].copy_(stats)
         ro.fused.refresh()
         self.critic.pack(out=ro._value_w)
+        if self.shuffle:
+            self.shuffle_base.add_(self.epochs)
         return self.stats
 
     # -------------------------------------------------------------------------------------------- device_step=True
@@ -592,10 +742,15 @@ class PPOLearner:
         stats[i], then adam_step on the rows.  Cached buffers only; no host synchronisation."""
         ls = self.log_std
         for i, t0, t1 in self._schedule():
-            row_a, row_v, g_ls, _ = self.minibatch_grads(t0, t1, pack=False, stats=self.stats[i])
+            if self.shuffle:
+                row_a, row_v, g_ls, _ = self.shuffled_grads(i, pack=False, stats=self.stats[i])
+            else:
+                row_a, row_v, g_ls, _ = self.minibatch_grads(t0, t1, pack=False, stats=self.stats[i])
             adam_step([self.actor, self.critic], [row_a, row_v], [self.adam_a, self.adam_v], [self._blob_a, self._blob_v], self.hyper,
                       self.step_count, log_std=ls, g_log_std=g_ls if ls is not None else None, log_std_state=self.adam_ls,
                       stats=self.step_stats[i], workspace=self._adam_ws)
+        if self.shuffle:
+            self.shuffle_base.add_(self.epochs)                  # on the stream, inside a captured update: the next one draws afresh
 
     def _state(self):
         """Every tensor an update writes that outlives it."""
@@ -603,6 +758,8 @@ class PPOLearner:
                                    self.stats, self.step_stats]
         if self.adam_ls is not None:
             out += [self.adam_ls.m, self.adam_ls.v]
+        if self.shuffle:
+            out += [self.shuffle_base, self.minibatch_idx]
         return out
 
     def set_lr(self, lr):

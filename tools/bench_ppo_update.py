@@ -29,7 +29,15 @@ Per path and block: host wall clock to a final synchronise and device time betwe
 the GPU activities of one call as torch's profiler sees them (kernels, copies, fills; the captured update's are counted on its eager
 form; null where the profiler gives none) and the peak
 allocation beyond what is held.  --ratios: the accuracy table tests/test_hip_adam_step.py writes with BSX_ADAM_RATIOS_OUT (error against
-the float64 restatement over torch's own, mean / max per network and quantity), copied into the result."""
+the float64 restatement over torch's own, mean / max per network and quantity), copied into the result.
+
+    python tools/bench_ppo_update.py --shuffle [--blocks 7] [--out profiles/ppo_shuffle.json]
+
+measures what shuffled minibatches cost (PPOLearner(shuffle=True): one bsx_minibatch_gather per optimiser step), at the two sizes of --adam:
+  update     the captured update(), epochs = 4, minibatches = 4, with shuffle=False and shuffle=True: two learners on one rollout, as
+             ALTERNATING blocks in one process (device events; the unshuffled learner of the same tree and run is the reference)
+  gather     bsx_minibatch_gather alone: the sixteen gathers of one update captured as one graph, device time per gather, and the bytes it
+             moves (every field read once and written once, the index written) over that time"""
 import argparse
 import json
 import math
@@ -182,20 +190,85 @@ def adam_pairs(args):
     return result
 
 
+def shuffle_pairs(args):
+    """--shuffle: the captured update with and without shuffled minibatches, and the gather alone -> the result dict."""
+    import torch
+    import deep_rl_battlespace_amd as bsx
+    from deep_rl_battlespace_amd.learner import GATHER_ROWS, PPOLearner
+    from deep_rl_battlespace_amd.rollout import PolicyRollout, StackedActor
+
+    def block(step, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            step()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def stats(x):
+        m = statistics.median(x)
+        return dict(median_ms=round(m, 4), min_ms=round(min(x), 4), max_ms=round(max(x), 4), spread=round((max(x) - min(x)) / m, 4))
+
+    torch.manual_seed(0)
+    mgn, epochs, minibatches = 0.5, 4, 4
+    result = dict(command=f"python tools/bench_ppo_update.py --shuffle --blocks {args.blocks}", device=torch.cuda.get_device_name(0), blocks=args.blocks,
+                  max_grad_norm=mgn, epochs=epochs, minibatches=minibatches, rows_per_workgroup=GATHER_ROWS, sizes=[])
+    for T, E, n in ADAM_SIZES:
+        A, D = 2 * n, 3 * n + 2
+        actor, critic = StackedActor(A, D, 4, device="cuda"), StackedActor(A, D, 1, device="cuda")
+        with torch.no_grad():
+            actor.w3.mul_(50.0); critic.w3.mul_(50.0)
+        env = bsx.parallel_env(n_agents=n, n_envs=E, seed=1, auto_reset=True, device="cuda")
+        env.reset()
+        ro = PolicyRollout(env, actor, T, seed=3, sample="categorical", temperature=TAU, value_actor=critic, gae=dict(gamma=0.99, lam=0.95), chains=1)
+        ro.start(); ro.capture()
+        ro.run(); ro.run()
+        torch.cuda.synchronize()
+        kw = dict(clip=CLIP, c_v=C_V, c_e=C_E, vclip=VCLIP, epochs=epochs, minibatches=minibatches, max_grad_norm=mgn, device_step=True)
+        plain, mixed = PPOLearner(ro, **kw).capture(), PPOLearner(ro, shuffle=True, **kw).capture()
+        for step in (plain.update, mixed.update, plain.update, mixed.update):
+            step()
+        a, b = [], []
+        for _ in range(args.blocks):
+            a.append(block(plain.update, 4))
+            b.append(block(mixed.update, 4))
+        t, f = stats(a), stats(b)
+        entry = dict(n=n, ticks=T, games=E, rows=T * E, rows_per_minibatch=T * E // minibatches,
+                     update=dict(unshuffled=t, shuffled=f, shuffled_over_unshuffled=round(f["median_ms"] / t["median_ms"], 4),
+                                 difference_beyond_the_spreads=bool(f["min_ms"] > t["max_ms"])))
+        # the gather alone: the sixteen gathers of one update as one graph (an eager call is bound by the binding's checks on the host)
+        sixteen = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(sixteen):
+            for i in range(epochs * minibatches):
+                mixed._gather(i)                                    # (the gather only: not the five calls after it)
+        sixteen.replay()
+        g = stats([block(sixteen.replay, 8) / (epochs * minibatches) for _ in range(args.blocks)])
+        row_bytes = 2 * (A * (D + 4 + 4) * 4 + A) + 8               # seven fields read and written, the index written
+        entry["gather"] = dict(g, bytes_per_row=row_bytes, gb_per_s=round(row_bytes * (T * E // minibatches) / (g["median_ms"] * 1e-3) / 1e9, 1),
+                               share_of_the_unshuffled_update=round(epochs * minibatches * g["median_ms"] / t["median_ms"], 4))
+        result["sizes"].append(entry)
+        del sixteen, plain, mixed, ro, env, actor, critic
+        torch.cuda.empty_cache()
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--adam", action="store_true", help="measure the optimiser step (adam_step) instead: profiles/adam_step.json")
+    ap.add_argument("--shuffle", action="store_true", help="measure shuffled minibatches (PPOLearner(shuffle=True)) instead: profiles/ppo_shuffle.json")
     ap.add_argument("--ratios", default=None, help="with --adam: the accuracy table written by tests/test_hip_adam_step.py")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "adam_step.json" if args.adam else "ppo_update.json")
-    if args.adam:
+        args.out = os.path.join(ROOT, "profiles", "ppo_shuffle.json" if args.shuffle else "adam_step.json" if args.adam else "ppo_update.json")
+    if args.adam or args.shuffle:
         import torch
         if not torch.cuda.is_available():
             raise SystemExit("bench_ppo_update.py measures on the GPU: none found")
-        result = adam_pairs(args)
+        result = shuffle_pairs(args) if args.shuffle else adam_pairs(args)
         print(json.dumps(result))
         with open(args.out, "w") as fh:
             fh.write(json.dumps(result, indent=1) + "\n")
