@@ -14,15 +14,17 @@ Only what the hot path needs lives here:
   advantage.py   GAE advantages / returns / per-agent mask of a rollout on device, for on-policy learners (csrc/bsx_advantage.hip)
   learner.py     the actor / value MLP as one fused forward and one fused backward for on-device learners (csrc/bsx_actor_grad.hip),
                  the PPO loss head between them and the minibatch update over a rollout's records (csrc/bsx_ppo_head.hip),
-                 the fused clip + Adam + pack step that makes a whole update one graph (csrc/bsx_adam_step.hip),
+                 the fused clip + Adam + pack step that makes a whole update one graph, and its tied form for agents that share one
+                 policy per team (csrc/bsx_adam_step.hip),
                  a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
 from . import advantage, envs, instinct, learner  # noqa: F401
 from .advantage import gae  # noqa: F401
-from .learner import AdamState, Minibatch, PPOLearner, adam_step, categorical_log_prob, fused_apply, minibatch_gather, ppo_head, shuffle_rows  # noqa: F401
+from .learner import (AdamState, Minibatch, PPOLearner, adam_step, categorical_log_prob, fused_apply, is_tied, minibatch_gather, ppo_head,  # noqa: F401
+                      share_group, shuffle_rows, tie_)
 from .envs.battle_env import parallel_env  # noqa: F401
 
-__all__ = ["AdamState", "Minibatch", "PPOLearner", "adam_step", "advantage", "categorical_log_prob", "envs", "fused_apply", "gae", "instinct", "learner", "minibatch_gather",
-           "parallel_env", "ppo_head", "shuffle_rows"]
+__all__ = ["AdamState", "Minibatch", "PPOLearner", "adam_step", "advantage", "categorical_log_prob", "envs", "fused_apply", "gae", "instinct", "is_tied", "learner",
+           "minibatch_gather", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "tie_"]

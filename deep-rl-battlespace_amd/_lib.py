@@ -149,6 +149,7 @@ SIGNATURES = {
                              ctypes.c_float, c_void_p, c_void_p, c_void_p]),
     "bsx_adam_step_workspace_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_adam_step": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_adam_step_shared": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
                                      c_void_p]),

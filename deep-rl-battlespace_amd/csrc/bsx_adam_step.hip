@@ -12,6 +12,12 @@
 //               the new parameters in LDS in the row's layout and writes every float of the row's blob from there.  Workgroup 0 writes stats.
 // `step` and `hyper` are read on the device at every launch: a captured graph follows a learning-rate schedule and counts its own steps.
 // No floating-point atomics, no flags or spins; the grid is a function of (n, nets, log_std given) alone: the same inputs give the same bits.
+//
+// bsx_adam_step_shared ties the agents in consecutive groups of `group` to one set of parameters: the gradient of a shared parameter is
+// the float32 sum of its members' rows in agent order.  The same two launches over the same grid: every member's workgroup forms the
+// group's sum for itself, in both passes -- no workgroup writes another's row, nothing is added to the workspace -- and only a leader's
+// workgroup (the first agent of a group) contributes a partial norm, so a shared parameter counts once.  group = 1 is bsx_adam_step:
+// the sum is the row's own element.  Both kernels are templates on TIED: the untied call's instances hold no loop over members.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -38,6 +44,7 @@ struct Args {
     int A, D, rows, parts;                                // rows = nets * A network rows; parts = rows (+ 1 with log_std)
     double* ws;
     double* stats;
+    int group;                                            // agents per tied group, consecutive; 1 = every agent on its own (last: the untied instances never load it)
 };
 
 // where element j of a gradient row lives: k = the parameter's index in learner.PARAMS, i = the float inside agent a's slice of it;
@@ -80,6 +87,19 @@ __device__ inline float* param_ptr(const BsxAdamIo& io, int net, int k) {
     return p;
 }
 
+// element j of a group's gradient: its `group` members' rows (`stride` floats apart, the leader's first) added in agent order, plain
+// float32 additions from the leader's value on -- ((g_l + g_l+1) + g_l+2) + ...; untied (group = 1) the leader's own element
+template <int TIED>
+__device__ inline float group_grad(const float* leader, int j, int stride, int group) {
+    float s = leader[j];
+    if constexpr (TIED) {
+#pragma unroll 4
+        for (int k = 1; k < group; ++k) s += leader[size_t(k) * stride + j];
+    }
+    return s;
+}
+
+template <int TIED>
 __global__ __launch_bounds__(NORM_TPB) void bsx_adam_norm_kernel(const Args p) {
     __shared__ double s_w[NORM_TPB / 64];
     const int tid = threadIdx.x, b = blockIdx.x;
@@ -89,14 +109,25 @@ __global__ __launch_bounds__(NORM_TPB) void bsx_adam_norm_kernel(const Args p) {
         const Net N = pick(p.io, net);
         const int G = grad_floats(p.D);
         const float* g = N.grad + size_t(a) * G;
+        if constexpr (!TIED) {
 #pragma unroll 4
-        for (int j = tid; j < G; j += NORM_TPB) {
-            Where w;
-            const double x = double(g[j]);
-            if (locate(j, p.D, N.na, w)) acc += x * x;
+            for (int j = tid; j < G; j += NORM_TPB) {
+                Where w;
+                const double x = double(g[j]);
+                if (locate(j, p.D, N.na, w)) acc += x * x;
+            }
+        } else if (a % p.group == 0) {                           // a leader: the group's sum counts once; a follower's partial is +0
+            for (int j = tid; j < G; j += NORM_TPB) {
+                Where w;
+                if (locate(j, p.D, N.na, w)) { const double x = double(group_grad<1>(g, j, G, p.group)); acc += x * x; }
+            }
         }
     } else {
-        for (int j = tid; j < 3 * p.A; j += NORM_TPB) { const double x = double(p.io.g_log_std[j]); acc += x * x; }
+        for (int j = tid; j < 3 * p.A; j += NORM_TPB) {
+            if (TIED && (j / 3) % p.group) continue;             // leader rows only
+            const double x = double(group_grad<TIED>(p.io.g_log_std, j, 3, p.group));
+            acc += x * x;
+        }
     }
     acc = block_sum<double, NORM_TPB / 64>(acc, s_w);
     if (tid == 0) {
@@ -177,6 +208,7 @@ __device__ inline float adam_element(const Scalars& c, float grad, float& m, flo
     return p - c.step_size * (m / denom);
 }
 
+template <int TIED>
 __global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p) {
     __shared__ float s_p[G_MAX];
     __shared__ double s_norm2;
@@ -209,7 +241,10 @@ __global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p)
     if (b >= p.rows) {                                           // log_std: [A][3], no blob
         for (int j = tid; j < 3 * p.A; j += APPLY_TPB) {
             float m = p.io.m_ls[j], v = p.io.v_ls[j];
-            const float x = adam_element(c, p.io.g_log_std[j], m, v, p.io.log_std[j]);
+            float g;
+            if constexpr (TIED) g = group_grad<1>(p.io.g_log_std + 3 * (j / 3 / p.group * p.group), j % 3, 3, p.group);   // from the leader's row on
+            else g = p.io.g_log_std[j];
+            const float x = adam_element(c, g, m, v, p.io.log_std[j]);
             p.io.m_ls[j] = m; p.io.v_ls[j] = v; p.io.log_std[j] = x;
         }
         return;
@@ -217,7 +252,7 @@ __global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p)
     const int net = b / p.A, a = b - net * p.A, D = p.D;
     const Net N = pick(p.io, net);
     const int na = N.na, G = grad_floats(D);
-    const float* grad = N.grad + size_t(a) * G;
+    const float* grad = N.grad + size_t(TIED ? a / p.group * p.group : a) * G;   // tied: the group leader's row
     float* mrow = N.m + size_t(a) * G;
     float* vrow = N.v + size_t(a) * G;
 #pragma unroll 2
@@ -227,7 +262,7 @@ __global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p)
         if (locate(j, D, na, w)) {
             float* q = param_ptr(p.io, net, w.k) + size_t(a) * param_row_floats(w.k, D, na) + w.i;
             float m = mrow[j], v = vrow[j];
-            x = adam_element(c, grad[j], m, v, *q);
+            x = adam_element(c, group_grad<TIED>(grad, j, G, p.group), m, v, *q);
             mrow[j] = m; vrow[j] = v; *q = x;
         }
         s_p[j] = x;
@@ -264,8 +299,13 @@ int bsx_adam_step_workspace_bytes(int n, int nets, size_t* bytes) {
 }
 
 int bsx_adam_step(const BsxAdamIo* io, int n, void* workspace, double* stats, void* stream) {
+    return bsx_adam_step_shared(io, n, 1, workspace, stats, stream);
+}
+
+int bsx_adam_step_shared(const BsxAdamIo* io, int n, int group, void* workspace, double* stats, void* stream) {
     if (!io || !workspace || !stats || !io->hyper || !io->step) return BSX_E_ARG;
     if (n < 1 || n > BSX_MAX_N || (io->nets != 1 && io->nets != 2)) return BSX_E_ARG;
+    if (group != 1 && group != 2 * n && (group < 2 || n % group)) return BSX_E_ARG;
     for (int k = 0; k < io->nets; ++k)
         if (const int rc = check_net(io->net[k])) return rc;
     const int given = (io->log_std != nullptr) + (io->g_log_std != nullptr) + (io->m_ls != nullptr) + (io->v_ls != nullptr);
@@ -281,13 +321,15 @@ int bsx_adam_step(const BsxAdamIo* io, int n, void* workspace, double* stats, vo
     a.D = 3 * n + 2;
     a.rows = io->nets * a.A;
     a.parts = a.rows + (given ? 1 : 0);
+    a.group = group;
     a.ws = static_cast<double*>(workspace);
     a.stats = stats;
     static_assert(PART_MAX <= 128, "the apply pass adds two partials per lane of one wave");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(bsx_adam_norm_kernel, dim3(unsigned(a.parts)), dim3(NORM_TPB), 0, s, a);
+    const bool tied = group > 1;
+    hipLaunchKernelGGL(tied ? bsx_adam_norm_kernel<1> : bsx_adam_norm_kernel<0>, dim3(unsigned(a.parts)), dim3(NORM_TPB), 0, s, a);
     if (const hipError_t e = hipGetLastError()) return int(e);
-    hipLaunchKernelGGL(bsx_adam_apply_kernel, dim3(unsigned(a.parts)), dim3(APPLY_TPB), 0, s, a);
+    hipLaunchKernelGGL(tied ? bsx_adam_apply_kernel<1> : bsx_adam_apply_kernel<0>, dim3(unsigned(a.parts)), dim3(APPLY_TPB), 0, s, a);
     return int(hipGetLastError());
 }
 

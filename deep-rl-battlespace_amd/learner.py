@@ -14,11 +14,15 @@ weights.  Deterministic (no floating-point atomics): the same inputs give the sa
                                                                 and a rollout's records to both grad_out tensors, one pass (bsx_ppo_head)
   AdamState(net_or_log_std), adam_step(nets, grads, states, ...) clip_grad_norm_ + Adam.step() + pack() of one or two networks (and log_std)
                                                                 as two launches: rows in, parameters, moments and packed blobs out (bsx_adam_step)
+  share_group(share, n), tie_(x, group), is_tied(x, group)      agents that share parameters: consecutive groups of `group` agents hold
+                                                                identical networks; adam_step(..., group=g) steps a group with the sum of
+                                                                its members' gradient rows (bsx_adam_step_shared)
   shuffle_rows(N, first, R, seed, seq, ...)                     a keyed permutation of [0, N) evaluated per position (bsx_shuffle_rows)
   minibatch_gather(src, dst, first, R, seed, seq, ...)          one shuffled minibatch's records through it, one launch (bsx_minibatch_gather)
   PPOLearner(rollout, ...)                                      minibatch_grads / update: the PPO update of a PolicyRollout's networks;
                                                                 device_step=True: the whole update on device, capture() makes it one graph;
-                                                                shuffle=True: a fresh permutation of the T x E rows per epoch
+                                                                shuffle=True: a fresh permutation of the T x E rows per epoch;
+                                                                share="team": one policy and one value function per team
 """
 from collections import namedtuple
 from functools import partial
@@ -334,6 +338,74 @@ def adam_hyper(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, device
     return torch.tensor([lr, b1, b2, eps, mgn, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
 
 
+def share_group(share, n):
+    """The agents per tied group of a 2n-agent network -> int.  share: None = 1 (every agent on its own), "team" = n (one set of
+    parameters per team), "all" = 2n (one for everyone), or an int g: 1, or >= 2 and a divisor of n (consecutive blocks of g agents that
+    never straddle the two teams), or 2n -- bsx_adam_step_shared's rule.  Agent a belongs to group a // g, whose leader is its first
+    agent.  ValueError for anything else."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n must be >= 1, got {n}")
+    if share is None:
+        return 1
+    if isinstance(share, str):
+        if share not in ("team", "all"):
+            raise ValueError(f"share must be None, 'team', 'all' or an int, got {share!r}")
+        return n if share == "team" else 2 * n
+    if isinstance(share, bool) or not isinstance(share, int):
+        raise ValueError(f"share must be None, 'team', 'all' or an int, got {share!r}")
+    g = share
+    if g != 1 and g != 2 * n and (g < 2 or n % g):
+        raise ValueError(f"a group of {g} does not fit {n} agents a side: 1, a divisor of {n} that is >= 2, or {2 * n} are possible")
+    return g
+
+
+def _tied_tensors(x):
+    """The [A, ...] tensors of x: a StackedActor's ten parameters, an AdamState's two moments, or x itself."""
+    if isinstance(x, torch.Tensor):
+        return [x]
+    if isinstance(x, AdamState):
+        return [x.m, x.v]
+    if all(hasattr(x, k) for k in PARAMS):
+        return [getattr(x, k) for k in PARAMS]
+    raise TypeError("a StackedActor, an AdamState or an [A, ...] tensor is needed")
+
+
+def _tied_group(t, group):
+    """group checked against t's leading axis A = 2n -> (A, g)."""
+    if t.dim() < 1 or t.shape[0] < 2 or t.shape[0] % 2:
+        raise ValueError(f"a tensor of shape {tuple(t.shape)} has no leading axis of A = 2n agents")
+    A = t.shape[0]
+    if isinstance(group, bool) or not isinstance(group, int):
+        raise ValueError(f"group must be an int (learner.share_group), got {group!r}")
+    return A, share_group(group, A // 2)
+
+
+def tie_(x, group):
+    """Copy every group leader's slice over its group's members, in place and under no_grad -> x.  x: a StackedActor (all ten
+    parameters), an AdamState (both moments) or an [A, ...] tensor such as log_std; group: share_group's int.  What PPOLearner(share=)
+    asks of its networks, done BEFORE the rollout packs them (or followed by ro.fused.refresh() and critic.pack(out=ro._value_w))."""
+    with torch.no_grad():
+        for t in _tied_tensors(x):
+            A, g = _tied_group(t, group)
+            if g > 1:
+                v = t.detach().view(A // g, g, *t.shape[1:])
+                v.copy_(v[:, :1].clone().expand_as(v))
+    return x
+
+
+def is_tied(x, group):
+    """Whether every member of every group of x (tie_'s argument) equals its leader -> bool; one host synchronisation."""
+    ok = None
+    for t in _tied_tensors(x):
+        A, g = _tied_group(t, group)
+        if g > 1:
+            v = t.detach().view(A // g, g, *t.shape[1:])
+            same = (v == v[:, :1]).all()
+            ok = same if ok is None else ok & same
+    return True if ok is None else bool(ok)
+
+
 def adam_step_workspace_bytes(n, nets):
     """Bytes of the workspace adam_step needs for `nets` networks of 2n agents."""
     lib, nb = _lib.load(), _lib.c_size_t()
@@ -341,7 +413,8 @@ def adam_step_workspace_bytes(n, nets):
     return nb.value
 
 
-def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_std=None, log_std_state=None, stats=None, workspace=None):
+def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_std=None, log_std_state=None, stats=None, workspace=None,
+              group=1):
     """torch's clip_grad_norm_(params, max_grad_norm) + Adam.step() (no weight decay, no amsgrad) + StackedActor.pack(), as ONE device
     pass of two launches (csrc/bsx_adam_step.hip, `bsx_adam_step`; the exact contract is written out in include/battlespace_hip.h)
     -> stats f64 [4] on the device, in the order of learner.ADAM_STATS.
@@ -355,7 +428,11 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     far, advanced by the call -- both are read on the device at every launch, so a captured call follows a changed learning rate and
     counts on from replay to replay.  The .grad of the parameters is neither read nor written.  Deterministic; no host synchronisation.
     stats (f64 [4]) and workspace (at least adam_step_workspace_bytes(n, len(nets)) bytes, 8-byte aligned): pass both and nothing is
-    allocated (a captured graph)."""
+    allocated (a captured graph).
+    group > 1 (share_group) is the tied step, `bsx_adam_step_shared`: the agents in consecutive blocks of `group` share parameters.  The
+    gradient of a group is the float32 sum of its members' rows in agent order (and of their g_log_std rows), it counts once in the
+    global norm, and every member's parameters, moments and blob row are stepped with it from that member's own values -- members
+    that are identical before the call (tie_) are identical after it.  group = 1 is the untied step, bit for bit."""
     for name, x in (("nets", nets), ("grads", grads), ("states", states), ("blobs", blobs)):
         if not isinstance(x, (list, tuple)):
             raise TypeError(f"{name} must be a list or tuple, one entry per network")
@@ -370,6 +447,9 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     if A < 2 or A % 2 or A > 2 * _lib.MAX_N or D != 3 * (A // 2) + 2:
         raise ValueError(f"nets[0] has {A} agents and obs_len {D}: an even A in 2 .. {2 * _lib.MAX_N} and D = 3 A / 2 + 2 are needed")
     G = grad_floats(D)
+    if isinstance(group, bool) or not isinstance(group, int):
+        raise ValueError(f"group must be an int (learner.share_group), got {group!r}")
+    group = share_group(group, A // 2)
     need = partial(_need, dev=dev, anchor="y")                   # ("y": the wording these messages have always had)
     io = _lib.BsxAdamIo()
     io.nets = len(nets)
@@ -411,8 +491,12 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     need(stats, "stats", (4,), (torch.float64,))
     workspace = _workspace(workspace, adam_step_workspace_bytes(A // 2, len(nets)), dev)
     io.hyper, io.step = hyper.data_ptr(), step.data_ptr()
-    _lib.check(_lib.load().bsx_adam_step(_lib.ctypes.byref(io), A // 2, workspace.data_ptr(), stats.data_ptr(),
-                                         torch.cuda.current_stream(dev).cuda_stream), "bsx_adam_step")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if group > 1:
+        _lib.check(_lib.load().bsx_adam_step_shared(_lib.ctypes.byref(io), A // 2, group, workspace.data_ptr(), stats.data_ptr(), stream),
+                   "bsx_adam_step_shared")
+    else:
+        _lib.check(_lib.load().bsx_adam_step(_lib.ctypes.byref(io), A // 2, workspace.data_ptr(), stats.data_ptr(), stream), "bsx_adam_step")
     return stats
 
 
@@ -560,12 +644,30 @@ class PPOLearner:
     Both optimiser paths take it.  shuffle_seed: an int in [0, 2^64); None takes the rollout's seed (the permutation's stream has a salt of
     its own).  shuffle=False (the default) is the tick-range path, bit for bit.
 
+    share="team" / "all" / an int (share_group): parameter sharing, as MAPPO trains -- one policy and one value function per team, for
+    everyone, or per block of g adjacent agents of a team.  The StackedActors keep their A slices; the members of a group hold
+    identical ones, so the rollout, the forward, the backward and the loss are what they are without sharing, and the gradient of a
+    shared parameter is the sum of its members' rows (the loss is a mean over all masked rows of all agents).  Tie first, then build:
+
+        tie_(actor, g); tie_(critic, g); tie_(log_std, g)       # g = share_group("team", n); before PolicyRollout packs them
+        ro = PolicyRollout(env, actor, T, ..., value_actor=critic, log_std=log_std)
+        learner = PPOLearner(ro, share="team", device_step=True)
+
+    (or tie and re-pack: ro.fused.refresh(); critic.pack(out=ro._value_w)).  The constructor checks is_tied on the actor, the critic and
+    log_std -- one host synchronisation -- and raises a ValueError otherwise: it never ties for the caller.  `group` holds the group
+    size.  device_step=True: every step is adam_step(group=g) -- the members' sum on the device, once in the global norm, every
+    member stepped from its own values, so the members stay identical bit for bit; capture(), set_lr, sync and shuffle=True are
+    unchanged.  device_step=False: install puts a group's sum on its leader's .grad slice and +0 on its followers', clipping and the
+    optimiser run as without sharing, and the leaders' slices are copied over their followers after every step.  With a scripted
+    opponent share="all" is a ValueError (the scripted team's parameters are left alone); share="team" trains the learned team's one
+    policy and keeps every bit of the scripted team's.  share=None (the default) is the unshared update, bit for bit.
+
     rollout: a PolicyRollout with sample="categorical" or "gaussian", a value_actor and gae= (ValueError otherwise).  vclip: clip the
     value loss around the rollout's recorded values.  optimizer: any torch optimiser over the parameters, instead of Adam(lr, betas, eps)
     (a ValueError with device_step=True)."""
 
     def __init__(self, rollout, *, clip=0.2, c_v=0.5, c_e=0.01, vclip=None, epochs=4, minibatches=4, lr=3e-4, max_grad_norm=None, optimizer=None,
-                 device_step=False, betas=(0.9, 0.999), eps=1e-8, shuffle=False, shuffle_seed=None):
+                 device_step=False, betas=(0.9, 0.999), eps=1e-8, shuffle=False, shuffle_seed=None, share=None):
         ro = rollout
         if getattr(ro, "_sample", None) is None and getattr(ro, "_gauss", None) is None:
             raise ValueError("PPOLearner needs a PolicyRollout with sample='categorical' or 'gaussian' (it reads the recorded logp)")
@@ -592,6 +694,18 @@ class PPOLearner:
         self.max_grad_norm = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)   # (no clipping is None here)
         _check(self.actor, ro.obs[:1])
         _check(self.critic, ro.obs[:1])
+        A = self.actor.n_actors
+        self.group = share_group(share, A // 2)
+        if self.group > 1:
+            if getattr(ro, "opponent", None) is not None and self.group == A:
+                raise ValueError("a rollout with a scripted opponent cannot share one policy across both teams (share='all'): the scripted "
+                                 "team's parameters are left alone; use share='team'")
+            for name, x in (("actor", self.actor), ("value_actor", self.critic), ("log_std", self.log_std)):
+                if x is not None and not is_tied(x, self.group):
+                    raise ValueError(f"share={share!r} needs networks that are already shared: the rollout's {name} differs inside a group of "
+                                     f"{self.group} agents.  Tie actor, value_actor and log_std with learner.tie_(x, {self.group}) before "
+                                     "building the PolicyRollout, or tie them and re-pack with ro.fused.refresh() and "
+                                     "critic.pack(out=ro._value_w)")
         self.params = [getattr(self.actor, k) for k in PARAMS] + [getattr(self.critic, k) for k in PARAMS]
         if self.log_std is not None:
             self.params.append(self.log_std)
@@ -689,10 +803,11 @@ class PPOLearner:
         return row_a, row_v, head.g_log_std, head.stats
 
     def install(self, row_a, row_v, g_log_std):
-        """The gradient rows onto the parameters' .grad (copies: the rows are overwritten by the next minibatch)."""
+        """The gradient rows onto the parameters' .grad (copies: the rows are overwritten by the next minibatch).  With share=: every
+        group's sum (float32, in agent order from the leader's row on) on its leader's slice and +0 on its followers'."""
         with torch.no_grad():
             for net, row in ((self.actor, row_a), (self.critic, row_v)):
-                for k, g in zip(PARAMS, split_grad(row, net.n_actions)):
+                for k, g in zip(PARAMS, split_grad(self._group_sum(row), net.n_actions)):
                     p = getattr(net, k)
                     if p.grad is None:
                         p.grad = torch.empty_like(p)
@@ -700,7 +815,28 @@ class PPOLearner:
             if self.log_std is not None:
                 if self.log_std.grad is None:
                     self.log_std.grad = torch.empty_like(self.log_std)
-                self.log_std.grad.copy_(g_log_std)
+                self.log_std.grad.copy_(self._group_sum(g_log_std))
+
+    def _group_sum(self, row):
+        """row [A, ...] -> the same shape with every group's float32 sum, members added in agent order, at its leader and +0 at its
+        followers (a new tensor); share=None: row itself."""
+        g = self.group
+        if g == 1:
+            return row
+        v = row.view(row.shape[0] // g, g, *row.shape[1:])
+        out = torch.zeros_like(v)
+        acc = v[:, 0].clone()
+        for k in range(1, g):
+            acc += v[:, k]
+        out[:, 0] = acc
+        return out.view(row.shape)
+
+    def _tie_params(self):
+        """The leaders' parameter slices over their followers (the torch path, after the optimiser's step)."""
+        if self.group > 1:
+            for x in (self.actor, self.critic, self.log_std):
+                if x is not None:
+                    tie_(x, self.group)
 
     def _schedule(self):
         """(i, t0, t1) of the optimiser steps of one update: epochs x minibatches, the minibatches in tick order in every epoch."""
@@ -725,6 +861,7 @@ class PPOLearner:
             if self.max_grad_norm is not None:
                 torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
             self.optimizer.step()
+            self._tie_params()
             self.stats[i].copy_(stats)
         ro.fused.refresh()
         self.critic.pack(out=ro._value_w)
@@ -748,7 +885,7 @@ class PPOLearner:
                 row_a, row_v, g_ls, _ = self.minibatch_grads(t0, t1, pack=False, stats=self.stats[i])
             adam_step([self.actor, self.critic], [row_a, row_v], [self.adam_a, self.adam_v], [self._blob_a, self._blob_v], self.hyper,
                       self.step_count, log_std=ls, g_log_std=g_ls if ls is not None else None, log_std_state=self.adam_ls,
-                      stats=self.step_stats[i], workspace=self._adam_ws)
+                      stats=self.step_stats[i], workspace=self._adam_ws, group=self.group)
         if self.shuffle:
             self.shuffle_base.add_(self.epochs)                  # on the stream, inside a captured update: the next one draws afresh
 

@@ -589,6 +589,31 @@ int bsx_adam_step_workspace_bytes(int n, int nets, size_t* bytes);
  * g_log_std, m_ls, v_ls or hyper off a 4-byte one; step, workspace or stats off an 8-byte one. */
 int bsx_adam_step(const BsxAdamIo* io, int n, void* workspace, double* stats, void* stream);
 
+/* The tied step (learner.py: adam_step(group=), PPOLearner(share=)): bsx_adam_step for agents that share parameters -- one policy and one
+ * value function per team, as MAPPO trains them.  The agents are tied in consecutive blocks of `group`: agent a belongs to group a / group,
+ * whose leader is its first agent.  Tied agents hold identical parameters, moments and blob rows (the caller's part: learner.tie_); the
+ * forward, the backward and the loss need no change, and the gradient of a shared parameter is the sum of its members' rows.
+ *   group      1 (every agent on its own: bsx_adam_step, bit for bit), or >= 2 and a divisor of n (groups never straddle the two
+ *              teams), or 2n (one set of parameters for everyone)
+ *   gsum[j]    = ((grad[l][j] + grad[l + 1][j]) + grad[l + 2][j]) + ... over the group's members in ascending agent order from the
+ *              leader l: plain float32 additions, not reassociated, no float64.  The same for the rows of g_log_std.  The pad columns of
+ *              w3 / b3 are not read in any member's row.
+ *   norm       the partials stay one per (network, agent) row and one for log_std, with the per-thread stride and the merge tree of
+ *              bsx_adam_step: a leader's partial is the float64 sum of the squares of gsum over its row's real elements, a follower's
+ *              is +0.0, log_std's runs over the leaders' rows only -- a shared parameter counts once in the global norm
+ *   apply      EVERY member's m, v and p are updated from gsum and that member's own old values, and every member's blob row is
+ *              written from its own new parameters: members that are bit-identical before the call are bit-identical after it
+ * So the call equals bsx_adam_step, from the same state, on gradient rows that hold gsum at every leader and +0 at every follower: the
+ * leaders' parameters, moments and blob rows and stats are bit-equal between the two, and here the followers equal their leader.  A
+ * group whose gsum, m and v are all +0 keeps every bit.  Everything else is bsx_adam_step's: hyper and step read on the device, two
+ * launches, the same workspace (bsx_adam_step_workspace_bytes), no atomics, flags or spins, a grid that is a function of (n, nets,
+ * log_std given) alone.  Every member's workgroup forms the group's sum for itself in both passes (a gradient row is read `group`
+ * times); no workgroup writes another's row.
+ * Refusals, before any launch, in this order: BSX_E_ARG for a null io, workspace, stats, hyper or step; n out of 1 .. BSX_MAX_N; nets
+ * other than 1 or 2; a group that is none of the above (0, negative, not a divisor of n and not 2n, above 2n); then the per-network and
+ * log_std rules and the BSX_E_ALIGN rules of bsx_adam_step, as there. */
+int bsx_adam_step_shared(const BsxAdamIo* io, int n, int group, void* workspace, double* stats, void* stream);
+
 /* ---- shuffled minibatches (deep-rl-battlespace_amd/learner.py: shuffle_rows, minibatch_gather, PPOLearner(shuffle=True);
  * csrc/bsx_shuffle.hip): a keyed permutation of the N = T x E rows of a rollout, evaluated per position -- O(1), no sort, no workspace,
  * no atomics --, and the gather of one minibatch's rows through it.
