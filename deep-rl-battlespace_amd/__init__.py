@@ -22,9 +22,9 @@ There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
 from . import advantage, envs, instinct, learner  # noqa: F401
 from .advantage import gae  # noqa: F401
-from .learner import (AdamState, Minibatch, PPOLearner, adam_step, categorical_log_prob, fused_apply, is_tied, minibatch_gather, ppo_head,  # noqa: F401
-                      share_group, shuffle_rows, tie_)
+from .learner import (AdamState, Minibatch, PPOLearner, adam_step, categorical_log_prob, fused_apply, fused_mlp, is_tied, minibatch_gather, mlp_grad,  # noqa: F401
+                      ppo_head, share_group, shuffle_rows, tie_)
 from .envs.battle_env import parallel_env  # noqa: F401
 
-__all__ = ["AdamState", "Minibatch", "PPOLearner", "adam_step", "advantage", "categorical_log_prob", "envs", "fused_apply", "gae", "instinct", "is_tied", "learner",
-           "minibatch_gather", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "tie_"]
+__all__ = ["AdamState", "Minibatch", "PPOLearner", "adam_step", "advantage", "categorical_log_prob", "envs", "fused_apply", "fused_mlp", "gae", "instinct", "is_tied", "learner",
+           "minibatch_gather", "mlp_grad", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "tie_"]

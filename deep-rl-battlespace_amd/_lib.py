@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("BSX_LIB_PATH") or os.path.join(_HERE, "csrc", "libbat
 ABI_VERSION = 14
 BULLET_SLOTS = 12
 MAX_N = 16
+MLP_MAX_D = 64
 MAX_T = 65535
 ACTOR_F32, ACTOR_BF16X3, ACTOR_BF16X6 = 0, 1, 2
 F_AUTO_RESET = 1
@@ -136,6 +137,9 @@ SIGNATURES = {
     "bsx_actor_grad_floats": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "bsx_actor_grad_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_actor_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_mlp_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "bsx_mlp_grad_workspace_bytes": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_mlp_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_workspace_bytes": (c_int, [c_int64, ctypes.POINTER(c_size_t)]),
     "bsx_replay_append": (c_int, [ctypes.POINTER(BsxReplayRing), ctypes.POINTER(BsxReplaySource), c_int64, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_sample": (c_int, [ctypes.POINTER(BsxReplayRing), c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,

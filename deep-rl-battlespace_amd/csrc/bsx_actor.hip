@@ -124,4 +124,19 @@ int bsx_actor_forward_gaussian(const float* weights, const float* obs, float* sc
     return actor_forward(weights, obs, scores, E, n, precision, noise, true, head, seed, seq, seq_base, env_offset, stream);
 }
 
+// The float32 kernel without noise on any agent count and input width (the kernel reads A and D at run time); with `raw`, the value path
+// on the same blob: head column 0 before tanh.
+int bsx_mlp_forward(const float* weights, const float* x, float* y, float* raw, int64_t R, int A, int D, void* stream) {
+    if (!x || !y) return BSX_E_ARG;
+    if (!weights || !mlp_shape(R, A, D)) return BSX_E_ARG;
+    if (!aligned(weights, 16) || !aligned(y, 16) || !aligned(x, 4) || !aligned(raw, 4)) return BSX_E_ALIGN;
+    BsxActorNoise nz = {};
+    if (raw) { nz.value_weights = weights; nz.value = raw; }
+    const ActorArgs a{weights, x, y, R, A, D, nz, 0, 0, nullptr, 0};
+    const int rows_per_block = (TPB / 64) * ROWS_PER_WAVE;
+    const dim3 grid(unsigned((R + rows_per_block - 1) / rows_per_block), unsigned(A)), block(TPB);
+    hipLaunchKernelGGL(bsx_actor_kernel<BSX_ACTOR_F32>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    return int(hipGetLastError());
+}
+
 }  // extern "C"

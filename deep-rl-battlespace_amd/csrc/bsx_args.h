@@ -16,3 +16,8 @@ inline int check_games(const void* p, int64_t E, int n, size_t align = 256, int 
     if (!p || E <= 0 || E > BSX_MAX_E || n < 1 || n > n_max) return BSX_E_ARG;
     return aligned(p, align) ? 0 : BSX_E_ALIGN;
 }
+
+// the ranges of the bsx_mlp_* entry points: any agent count up to 2 * BSX_MAX_N (odd ones too) and any input width up to BSX_MLP_MAX_D
+inline bool mlp_shape(int64_t R, int A, int D) {
+    return R >= 1 && R <= BSX_MAX_E && A >= 1 && A <= 2 * BSX_MAX_N && D >= 1 && D <= BSX_MLP_MAX_D;
+}

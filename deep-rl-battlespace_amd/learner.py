@@ -9,6 +9,9 @@ weights.  Deterministic (no floating-point atomics): the same inputs give the sa
   categorical_log_prob(actor, obs, actions, temperature, fused) the learner side of PolicyRollout(sample="categorical")
   rollout.gaussian_log_prob(..., fused=True)                    the learner side of sample="gaussian", through fused_apply
   fused_grad(actor, blob, obs, grad_out, squash)                the backward alone: one bsx_actor_grad call, the [A, G] gradient row
+  fused_mlp(net, x, squash=True)                                the same network on ANY input [..., A, D] (A <= 32, D <= 64: a Q critic on
+                                                                obs (+) action), differentiable in the parameters and in x (bsx_mlp_grad)
+  mlp_grad(net, blob, x, grad_out, squash, input_grad)          its backward alone, capturable: (the [A, G] gradient row, grad_x)
   split_grad(row, n_actions)                                    a [A, G] gradient row as the ten parameter shapes (views, no gather)
   ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, ...)      the clipped-surrogate PPO loss between the two: from the forward's outputs
                                                                 and a rollout's records to both grad_out tensors, one pass (bsx_ppo_head)
@@ -186,6 +189,117 @@ def fused_apply(actor, obs, squash=True):
     flat = obs.detach().reshape(-1, A, D).contiguous()
     y = _FusedApply.apply(actor, flat, bool(squash), *[getattr(actor, k) for k in PARAMS])
     return y.reshape(*obs.shape[:-1], actor.n_actions)
+
+
+# ------------------------------------------------------------------------------------------------ any input width, and its gradient
+class _MlpBuffers:
+    """Per network: the buffers of bsx_mlp_grad by (R, A, D, device) -- the workspace, the [A, G] output row, the 4-column grad_out
+    (columns beyond n_actions stay 0) and, once asked for, grad_x -- so that a captured learner step does not allocate them again."""
+
+    def __init__(self):
+        self.by_key = {}
+
+    def get(self, R, A, D, device, lib, input_grad):
+        key = (int(R), int(A), int(D), str(device))
+        if key not in self.by_key:
+            nb = _lib.c_size_t()
+            _lib.check(lib.bsx_mlp_grad_workspace_bytes(R, A, D, _lib.ctypes.byref(nb)), "bsx_mlp_grad_workspace_bytes")
+            self.by_key[key] = dict(ws=torch.empty(((nb.value + 3) // 4,), dtype=torch.float32, device=device),
+                                    grad=torch.empty((A, grad_floats(D)), dtype=torch.float32, device=device),
+                                    go=torch.zeros((R, A, 4), dtype=torch.float32, device=device), gx=None)
+        buf = self.by_key[key]
+        if input_grad and buf["gx"] is None:
+            buf["gx"] = torch.empty((R, A, D), dtype=torch.float32, device=device)
+        return buf
+
+
+def _check_mlp(net, x, squash, what):
+    """fused_apply's refusals without the A = 2n, D = 3n + 2 tie and without the one of an input that requires grad."""
+    ps = [getattr(net, k) for k in PARAMS]
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or any(not p.is_cuda for p in ps):
+        raise ValueError(f"{what} runs on the GPU: the network and x must be CUDA tensors")
+    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in ps):
+        raise ValueError(f"{what} is float32: the network and x must be float32")
+    if net.w1.shape[2] != H or net.w2.shape[1] != H or net.w2.shape[2] != H:
+        raise ValueError("the fused MLP kernels are built for fc1 = fc2 = 64")
+    A, D = net.n_actors, net.obs_len
+    if not 1 <= A <= 2 * _lib.MAX_N or not 1 <= D <= _lib.MLP_MAX_D or net.n_actions not in (1, 3, 4):
+        raise ValueError(f"the fused MLP kernels take 1 .. {2 * _lib.MAX_N} agents, 1 .. {_lib.MLP_MAX_D} inputs and 1, 3 or 4 outputs, "
+                         f"got {A}, {D} and {net.n_actions}")
+    if x.dim() < 2 or tuple(x.shape[-2:]) != (A, D) or x.numel() == 0:
+        raise ValueError(f"x must be [..., {A}, {D}] and not empty, got {tuple(x.shape)}")
+    if x.device != net.w1.device:
+        raise ValueError("the network and x must be on the same device")
+    if not squash and net.n_actions != 1:
+        raise ValueError("squash=False is the value head: a StackedActor with one output")
+
+
+def mlp_grad(net, blob, x, grad_out, squash=True, input_grad=True):
+    """One bsx_mlp_grad call on the current stream -> (row, grad_x): the [A, G] gradient row (split_grad cuts it) of sum <grad_out, y> for
+    the network packed in `blob` (net.pack()) on x float32 [R, A, D], and the gradient of the same sum with respect to x, float32
+    [R, A, D] (None with input_grad=False: the launch is then bsx_actor_grad's kernel).  grad_out: float32 [R, A, n_actions].  net: a
+    StackedActor of any n_actors in 1 .. 32 and obs_len in 1 .. 64.  The capturable form: the row, grad_x, the workspace and the
+    4-column copy of grad_out are the network's cached buffers for (R, A, D, device) -- overwritten by the next call with the same key --
+    and nothing is allocated from the second call on.  fused_mlp's backward is this call.  ValueError: fused_mlp's refusals, a blob or
+    a grad_out of another shape."""
+    _check_mlp(net, x, squash, "mlp_grad")
+    A, D, na = net.n_actors, net.obs_len, net.n_actions
+    if x.dim() != 3:
+        raise ValueError(f"x must be [R, {A}, {D}], got {tuple(x.shape)}")
+    R, dev = x.shape[0], x.device
+    need = partial(_need, dev=dev, anchor="x")
+    need(x, "x", (R, A, D), _F32)
+    need(grad_out, "grad_out", (R, A, na), _F32)
+    need(blob, "blob", (A, H * ((D + 1) & ~1) + grad_floats(0) + H * H * 3 // 2), _F32)
+    lib = _lib.load()
+    b = net.__dict__.get("_bsx_mlp_buffers")
+    if b is None:
+        b = net.__dict__["_bsx_mlp_buffers"] = _MlpBuffers()
+    buf = b.get(R, A, D, dev, lib, input_grad)
+    buf["go"][..., :na].copy_(grad_out)                          # padded to 4 columns: the others hold 0 from the allocation on
+    gx = buf["gx"] if input_grad else None
+    _lib.check(lib.bsx_mlp_grad(blob.data_ptr(), x.data_ptr(), buf["go"].data_ptr(), R, A, D, int(bool(squash)), buf["grad"].data_ptr(),
+                                gx.data_ptr() if gx is not None else None, buf["ws"].data_ptr(),
+                                torch.cuda.current_stream(dev).cuda_stream), "bsx_mlp_grad")
+    return buf["grad"], gx
+
+
+class _FusedMlp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, x, squash, *params):
+        A, D, na, R = net.n_actors, net.obs_len, net.n_actions, x.shape[0]
+        blob = net.pack()                                        # a fresh blob: backward reads THIS one, not the parameters of later
+        y = torch.empty((R, A, 4), dtype=torch.float32, device=x.device)
+        raw = None if squash else torch.empty((R, A), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().bsx_mlp_forward(blob.data_ptr(), x.data_ptr(), y.data_ptr(), raw.data_ptr() if raw is not None else None,
+                                               R, A, D, torch.cuda.current_stream(x.device).cuda_stream), "bsx_mlp_forward")
+        ctx.save_for_backward(x, blob)
+        ctx.net, ctx.squash = net, bool(squash)
+        return y[..., :na] if squash else raw.unsqueeze(-1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, blob = ctx.saved_tensors
+        row, gx = mlp_grad(ctx.net, blob, x, gy.contiguous(), ctx.squash, input_grad=ctx.needs_input_grad[1])
+        # copies, as in fused_apply: autograd may keep what it is handed, the cached buffers are overwritten by the next call
+        grads = split_grad(row.clone(), ctx.net.n_actions)
+        return (None, gx.clone() if gx is not None else None, None, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])])
+
+
+def fused_mlp(net, x, squash=True):
+    """net(x) as one HIP kernel forward and one backward, for an input that is not an observation row: x float32 [..., A, D] ->
+    [..., A, n_actions], tanh-squashed (squash=True) or the raw head (squash=False: a value or Q head, n_actions = 1).  net: a
+    StackedActor on the GPU, float32, fc1 = fc2 = 64, with any n_actors in 1 .. 32, obs_len in 1 .. 64 and 1, 3 or 4 outputs -- a
+    Q critic on obs (+) action, for one.  Differentiable in the ten parameters AND in x when x requires grad (the deterministic policy
+    gradient: dQ/da back through the actor); once differentiable.  The backward is one bsx_mlp_grad call on the blob the forward packed.
+    At A = 2n, D = 3n + 2 the outputs and the parameter gradients are fused_apply's bits.  ValueError: tensors off the GPU, not
+    float32, other hidden sizes, sizes out of range, an x that is not [..., A, D], squash=False with more than one output."""
+    _check_mlp(net, x, squash, "fused_mlp")
+    A, D = net.n_actors, net.obs_len
+    flat = x.reshape(-1, A, D).contiguous()
+    y = _FusedMlp.apply(net, flat, bool(squash), *[getattr(net, k) for k in PARAMS])
+    return y.reshape(*x.shape[:-1], net.n_actions)
 
 
 def categorical_log_prob(actor, obs, actions, temperature=1.0, fused=False):

@@ -456,6 +456,39 @@ int bsx_actor_grad_workspace_bytes(int64_t R, int n, size_t* bytes);          /*
 int bsx_actor_grad(const float* weights, const float* obs, const float* grad_out, int64_t R, int n, int squash,
                    float* grad, void* workspace, void* stream);
 
+/* ---- the same network on an input that is not an observation row, and its gradient with respect to that input: what a DDPG-family
+ * learner needs (a Q critic reads obs (+) action: 9 floats at 1v1, 24 for the reference's 2v2 critic; the deterministic policy gradient
+ * is dQ/da pushed back through the actor).  learner.py: fused_mlp, mlp_grad.  Common to the three entries:
+ *   1 <= A <= 2 * BSX_MAX_N agents (odd counts allowed), 1 <= D <= BSX_MLP_MAX_D inputs, 1 <= R <= BSX_MAX_E rows;
+ *   weights    StackedActor.pack()'s blob for obs_len = D: 64 Dp + 4096 + 6 * 64 + 260 + 6144 floats per agent (Dp = D rounded up to
+ *              even; the layout of bsx_actor_forward's blob), 16-byte aligned
+ *   x          float32 [R][A][D], 4-byte aligned.
+ * bsx_mlp_forward: bsx_actor_forward's BSX_ACTOR_F32 kernel without noise (no new kernel).
+ *   y          float32 [R][A][4], 16-byte aligned, required: the tanh-squashed head
+ *   raw        nullable float32 [R][A], 4-byte aligned: head column 0 plus its bias BEFORE tanh (what a value or Q head returns); taken
+ *              through the value path with value_weights = weights.
+ * At (A, D) = (2n, 3n + 2) both outputs are bit for bit bsx_actor_forward's, called that way.  Refusals, before the launch, in this
+ * order: BSX_E_ARG for a null x or y, then for a null weights or R, A, D out of range; BSX_E_ALIGN for weights, then y, off a 16-byte
+ * boundary, then x, then raw, off a 4-byte one.  One launch on `stream`.
+ * bsx_mlp_grad: bsx_actor_grad's pass (everything said there holds, with A for 2n: P = min(ceil(ceil(R / 32) / 4), max(1, 512 / A))) and,
+ * with grad_x, the gradient of the same L with respect to x:  dx = da1 W1^T, per row -- no sum over rows, the same bits on every call.
+ *   grad_out   float32 [R][A][4], 16-byte aligned, as bsx_actor_grad's
+ *   grad       float32 [A][G], G = 64 D + 4096 + 6 * 64 + 260, bsx_actor_grad's row, required
+ *   grad_x     nullable float32 [R][A][D], 4-byte aligned (out): exactly R A D floats are written.  NULL: the launch is
+ *              bsx_actor_grad's own kernel
+ *   workspace  4-byte aligned, at least bsx_mlp_grad_workspace_bytes(R, A, D) = 4 A P G bytes
+ * At (A, D) = (2n, 3n + 2), grad is bit for bit bsx_actor_grad's, with and without grad_x, and the workspace size is
+ * bsx_actor_grad_workspace_bytes(R, n).  Refusals, before any launch, in this order: BSX_E_ARG for a null x / grad_out / grad /
+ * workspace or a squash other than 0 / 1, then for a null weights or R, A, D out of range; BSX_E_ALIGN for weights, then grad_out, off a
+ * 16-byte boundary, then x, grad, grad_x, workspace off a 4-byte one.  Two launches on `stream`, no host synchronisation: capturable. */
+#define BSX_MLP_MAX_D 64      /* the x image of the backward is 64 columns wide (MT1 = 2) */
+int bsx_mlp_forward(const float* weights, const float* x, float* y, float* raw,
+                    int64_t R, int A, int D, void* stream);
+int bsx_mlp_grad_workspace_bytes(int64_t R, int A, int D, size_t* bytes);     /* BSX_E_ARG: null bytes, R, A or D out of range */
+int bsx_mlp_grad(const float* weights, const float* x, const float* grad_out,
+                 int64_t R, int A, int D, int squash,
+                 float* grad, float* grad_x, void* workspace, void* stream);
+
 /* ---- the PPO loss head (deep-rl-battlespace_amd/learner.py: ppo_head, PPOLearner; csrc/bsx_ppo_head.hip): from the forward's outputs
  * and a rollout's records to the two grad_out tensors bsx_actor_grad takes, log_std's gradient and the loss statistics, in one pass.
  *
