@@ -211,18 +211,17 @@ int bsx_actor_grad_floats(int obs_len, int* floats_per_agent) {
     return 0;
 }
 
+// The two observation-shaped entries are bsx_mlp_grad's at (A, D) = (2n, 3n + 2) with no grad_x: the team size is checked here (it is
+// what 2n and 3n + 2 are made of), everything else there -- every BSX_E_ARG before every BSX_E_ALIGN, weights and grad_out at 16 bytes.
 int bsx_actor_grad_workspace_bytes(int64_t R, int n, size_t* bytes) {
-    if (!bytes || R < 1 || R > BSX_MAX_E || n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
-    *bytes = size_t(2 * n) * size_t(partials(R, 2 * n)) * size_t(grad_floats(3 * n + 2)) * sizeof(float);
-    return 0;
+    if (n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
+    return bsx_mlp_grad_workspace_bytes(R, 2 * n, 3 * n + 2, bytes);
 }
 
 int bsx_actor_grad(const float* weights, const float* obs, const float* grad_out, int64_t R, int n, int squash,
                    float* grad, void* workspace, void* stream) {
-    if (!obs || !grad_out || !grad || !workspace || (squash != 0 && squash != 1)) return BSX_E_ARG;
-    if (const int rc = check_games(weights, R, n, 16)) return rc;
-    if (!aligned(grad_out, 16) || !aligned(obs, 4) || !aligned(grad, 4) || !aligned(workspace, 4)) return BSX_E_ALIGN;
-    return launch_grad(weights, obs, grad_out, R, 2 * n, 3 * n + 2, squash, grad, nullptr, workspace, stream);
+    if (n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
+    return bsx_mlp_grad(weights, obs, grad_out, R, 2 * n, 3 * n + 2, squash, grad, nullptr, workspace, stream);
 }
 
 int bsx_mlp_grad_workspace_bytes(int64_t R, int A, int D, size_t* bytes) {

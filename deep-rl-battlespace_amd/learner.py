@@ -1,14 +1,16 @@
 """The learner's side of a PolicyRollout: the actor / value MLP as ONE fused forward and ONE fused backward (csrc/bsx_actor_grad.hip).
 
 `StackedActor.forward` under torch autograd is ~20 memory-bound passes over [A, R, 64] activations forward and twice that backward, and it
-saves every one of them.  `fused_apply` evaluates the same network with the rollout's own float32 kernel (`bsx_actor_forward`) and
-back-propagates with `bsx_actor_grad`, which recomputes the forward in registers: nothing is saved but the observations and the packed
-weights.  Deterministic (no floating-point atomics): the same inputs give the same gradient bits on every call.
+saves every one of them.  `fused_apply` evaluates the same network with the rollout's own float32 kernel (`bsx_mlp_forward`:
+bsx_actor_forward's kernel) and back-propagates with `bsx_mlp_grad` (bsx_actor_grad's kernel), which recomputes the forward in
+registers: nothing is saved but the observations and the packed weights.  Deterministic (no floating-point atomics): the same inputs
+give the same gradient bits on every call.  There is ONE path: fused_apply is fused_mlp on detached observation rows, fused_grad is
+mlp_grad without the input gradient, and a network holds one set of cached buffers for all of them and for a PPOLearner.
 
   fused_apply(actor, obs, squash=True)                          the network, differentiable in the actor's ten parameters
   categorical_log_prob(actor, obs, actions, temperature, fused) the learner side of PolicyRollout(sample="categorical")
   rollout.gaussian_log_prob(..., fused=True)                    the learner side of sample="gaussian", through fused_apply
-  fused_grad(actor, blob, obs, grad_out, squash)                the backward alone: one bsx_actor_grad call, the [A, G] gradient row
+  fused_grad(actor, blob, obs, grad_out, squash)                the backward alone: mlp_grad(..., input_grad=False)[0], the [A, G] gradient row
   fused_mlp(net, x, squash=True)                                the same network on ANY input [..., A, D] (A <= 32, D <= 64: a Q critic on
                                                                 obs (+) action), differentiable in the parameters and in x (bsx_mlp_grad)
   mlp_grad(net, blob, x, grad_out, squash, input_grad)          its backward alone, capturable: (the [A, G] gradient row, grad_x)
@@ -67,78 +69,63 @@ def split_grad(row, n_actions):
     return out
 
 
-class _GradBuffers:
-    """Per actor: the buffers of bsx_actor_grad by (R, n, device) -- the workspace, the kernel's [A, G] output row, the 4-column
-    grad_out (columns beyond n_actions stay 0) -- so that a captured learner step does not allocate them again."""
+class _Buffers:
+    """Per network: the buffers of bsx_mlp_grad by (R, A, D, device) -- the workspace and the kernel's [A, G] output row, and once asked for
+    the 4-column grad_out (columns beyond n_actions stay 0) and grad_x -- so that a captured learner step does not allocate them again."""
 
     def __init__(self):
         self.by_key = {}
 
-    def get(self, R, n, device, lib, go=True):
+    def get(self, R, A, D, device, lib, go=False, gx=False):
         """go=False: for a caller that brings its own 4-column grad_out (PPOLearner: the head's outputs) -- none is allocated."""
-        key = (int(R), int(n), str(device))
+        key = (int(R), int(A), int(D), str(device))
         if key not in self.by_key:
-            A, D = 2 * n, 3 * n + 2
             nb = _lib.c_size_t()
-            _lib.check(lib.bsx_actor_grad_workspace_bytes(R, n, _lib.ctypes.byref(nb)), "bsx_actor_grad_workspace_bytes")
+            _lib.check(lib.bsx_mlp_grad_workspace_bytes(R, A, D, _lib.ctypes.byref(nb)), "bsx_mlp_grad_workspace_bytes")
             self.by_key[key] = dict(ws=torch.empty(((nb.value + 3) // 4,), dtype=torch.float32, device=device),
-                                    grad=torch.empty((A, grad_floats(D)), dtype=torch.float32, device=device), go=None)
+                                    grad=torch.empty((A, grad_floats(D)), dtype=torch.float32, device=device), go=None, gx=None)
         buf = self.by_key[key]
         if go and buf["go"] is None:
-            buf["go"] = torch.zeros((R, 2 * n, 4), dtype=torch.float32, device=device)
+            buf["go"] = torch.zeros((R, A, 4), dtype=torch.float32, device=device)
+        if gx and buf["gx"] is None:
+            buf["gx"] = torch.empty((R, A, D), dtype=torch.float32, device=device)
         return buf
 
 
-def _buffers(actor):
-    b = actor.__dict__.get("_bsx_grad_buffers")
+def _buffers(net):
+    """The network's one buffer cache: fused_apply, fused_mlp, fused_grad, mlp_grad and PPOLearner all go through it."""
+    b = net.__dict__.get("_bsx_mlp_buffers")
     if b is None:
-        b = actor.__dict__["_bsx_grad_buffers"] = _GradBuffers()
+        b = net.__dict__["_bsx_mlp_buffers"] = _Buffers()
     return b
 
 
-def _check(actor, obs):
-    ps = [getattr(actor, k) for k in PARAMS]
-    if not isinstance(obs, torch.Tensor) or not obs.is_cuda or any(not p.is_cuda for p in ps):
-        raise ValueError("fused_apply runs on the GPU: the actor and obs must be CUDA tensors")
-    if obs.dtype != torch.float32 or any(p.dtype != torch.float32 for p in ps):
-        raise ValueError("fused_apply is float32: the actor and obs must be float32")
-    if actor.w1.shape[2] != H or actor.w2.shape[1] != H or actor.w2.shape[2] != H:
-        raise ValueError("the fused actor kernels are built for fc1 = fc2 = 64")
-    if obs.requires_grad:
-        raise ValueError("fused_apply gives no gradient with respect to obs: pass a tensor that does not require grad")
-    A, D = actor.n_actors, actor.obs_len
-    if obs.dim() < 2 or tuple(obs.shape[-2:]) != (A, D) or A % 2 or D != 3 * (A // 2) + 2 or obs.numel() == 0:
-        raise ValueError(f"obs must be [..., {A}, {D}] with A = 2n agents and D = 3n + 2")
-    if obs.device != actor.w1.device:
-        raise ValueError("the actor and obs must be on the same device")
-
-
-class _FusedApply(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, actor, obs, squash, *params):
-        lib = _lib.load()
-        A, na, R = actor.n_actors, actor.n_actions, obs.shape[0]
-        blob = actor.pack()                                      # a fresh blob: backward reads THIS one, not the parameters of later
-        scores = torch.empty((R, A, 4), dtype=torch.float32, device=obs.device)
-        if squash:
-            _actor_forward(lib, blob, obs, scores)
-            y = scores[..., :na]
-        else:                                                    # the value path: the same blob once more as the value head
-            value = torch.empty((R, A), dtype=torch.float32, device=obs.device)
-            _actor_forward(lib, blob, obs, scores, blob, value)
-            y = value.unsqueeze(-1)
-        ctx.save_for_backward(obs, blob)
-        ctx.actor, ctx.squash = actor, bool(squash)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        obs, blob = ctx.saved_tensors
-        row = fused_grad(ctx.actor, blob, obs, gy, ctx.squash)
-        # the gradients handed to autograd are views of ONE copy of the row: a parameter's .grad may keep them, the cached row is
-        # overwritten by the next call
-        grads = split_grad(row.clone(), ctx.actor.n_actions)
-        return (None, None, None, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])])
+def _check_mlp(net, x, squash, what, obs_shaped=False):
+    """The refusals of every fused path, in the order they fire.  obs_shaped: fused_apply's two on top, after the checks of the tensors
+    and before those of the sizes -- an input that requires grad, and anything but observation rows (A = 2n agents, D = 3n + 2)."""
+    ps = [getattr(net, k) for k in PARAMS]
+    both = "the actor and obs" if obs_shaped else "the network and x"
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or any(not p.is_cuda for p in ps):
+        raise ValueError(f"{what} runs on the GPU: {both} must be CUDA tensors")
+    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in ps):
+        raise ValueError(f"{what} is float32: {both} must be float32")
+    if net.w1.shape[2] != H or net.w2.shape[1] != H or net.w2.shape[2] != H:
+        raise ValueError("the fused MLP kernels are built for fc1 = fc2 = 64")
+    A, D = net.n_actors, net.obs_len
+    if obs_shaped:
+        if x.requires_grad:
+            raise ValueError(f"{what} gives no gradient with respect to obs: pass a tensor that does not require grad")
+        if x.dim() < 2 or tuple(x.shape[-2:]) != (A, D) or A % 2 or D != 3 * (A // 2) + 2 or x.numel() == 0:
+            raise ValueError(f"obs must be [..., {A}, {D}] with A = 2n agents and D = 3n + 2")
+    if not 1 <= A <= 2 * _lib.MAX_N or not 1 <= D <= _lib.MLP_MAX_D or net.n_actions not in (1, 3, 4):
+        raise ValueError(f"the fused MLP kernels take 1 .. {2 * _lib.MAX_N} agents, 1 .. {_lib.MLP_MAX_D} inputs and 1, 3 or 4 outputs, "
+                         f"got {A}, {D} and {net.n_actions}")
+    if x.dim() < 2 or tuple(x.shape[-2:]) != (A, D) or x.numel() == 0:
+        raise ValueError(f"x must be [..., {A}, {D}] and not empty, got {tuple(x.shape)}")
+    if x.device != net.w1.device:
+        raise ValueError(f"{both} must be on the same device")
+    if not squash and net.n_actions != 1:
+        raise ValueError("squash=False is the value head: a StackedActor with one output")
 
 
 def _actor_forward(lib, blob, obs, scores, value_blob=None, value=None):
@@ -154,84 +141,14 @@ def _actor_forward(lib, blob, obs, scores, value_blob=None, value=None):
                                      torch.cuda.current_stream(obs.device).cuda_stream), "bsx_actor_forward")
 
 
-def fused_grad(actor, blob, obs, grad_out, squash=True):
-    """One bsx_actor_grad call on the current stream: the [A, G] gradient row (split_grad cuts it) of sum <grad_out, y> for the network
-    packed in `blob` (actor.pack()) on obs float32 [R, A, D]; grad_out [R, A, n_actions].  The row, the workspace and the 4-column copy of
-    grad_out are the actor's cached buffers for (R, n, device): the row is overwritten by the next call with the same key, and nothing is
-    allocated from the second call on.  fused_apply's backward is this call."""
-    lib = _lib.load()
-    A, na = actor.n_actors, actor.n_actions
-    n, R = A // 2, obs.shape[0]
-    buf = _buffers(actor).get(R, n, obs.device, lib)
-    go = buf["go"]
-    go[..., :na].copy_(grad_out)                                 # padded to 4 columns: the others hold 0 from the allocation on
-    return _actor_grad(lib, buf, blob, obs, go, squash)
-
-
-def _actor_grad(lib, buf, blob, obs, go4, squash):
-    """bsx_actor_grad on a grad_out that already has the kernel's 4-column layout (fused_grad's padded copy, or bsx_ppo_head's g_pi / g_v)."""
-    R, A = obs.shape[0], obs.shape[1]
-    _lib.check(lib.bsx_actor_grad(blob.data_ptr(), obs.data_ptr(), go4.data_ptr(), R, A // 2, int(bool(squash)), buf["grad"].data_ptr(),
-                                  buf["ws"].data_ptr(), torch.cuda.current_stream(obs.device).cuda_stream), "bsx_actor_grad")
+def _mlp_grad(lib, buf, blob, x, go4, squash, gx=None):
+    """bsx_mlp_grad on the current stream, unchecked, on a grad_out that already has the kernel's 4-column layout (mlp_grad's padded copy,
+    or bsx_ppo_head's g_pi / g_v) -> buf's row.  gx: the [R, A, D] tensor grad_x is written to; None is bsx_actor_grad's kernel."""
+    R, A, D = x.shape
+    _lib.check(lib.bsx_mlp_grad(blob.data_ptr(), x.data_ptr(), go4.data_ptr(), R, A, D, int(bool(squash)), buf["grad"].data_ptr(),
+                                gx.data_ptr() if gx is not None else None, buf["ws"].data_ptr(),
+                                torch.cuda.current_stream(x.device).cuda_stream), "bsx_mlp_grad")
     return buf["grad"]
-
-
-def fused_apply(actor, obs, squash=True):
-    """actor(obs) as one HIP kernel forward and one backward: obs float32 [..., A, D] -> [..., A, n_actions], tanh-squashed (squash=True,
-    an actor: exactly FusedActor's float32 scores) or the raw head (squash=False: a value head, n_actions = 1).  Differentiable in the
-    ten parameters of `actor` (a StackedActor on the GPU, float32, fc1 = fc2 = 64) and NOT in obs.  The backward reads the blob the
-    forward packed, so an optimiser step between the two does not move it; its workspace and output row are cached on the actor per
-    (rows, n, device).  ValueError: tensors off the GPU, not float32, other hidden sizes, an obs that requires grad."""
-    _check(actor, obs)
-    if not squash and actor.n_actions != 1:
-        raise ValueError("squash=False is the value head: a StackedActor with one output")
-    A, D = actor.n_actors, actor.obs_len
-    flat = obs.detach().reshape(-1, A, D).contiguous()
-    y = _FusedApply.apply(actor, flat, bool(squash), *[getattr(actor, k) for k in PARAMS])
-    return y.reshape(*obs.shape[:-1], actor.n_actions)
-
-
-# ------------------------------------------------------------------------------------------------ any input width, and its gradient
-class _MlpBuffers:
-    """Per network: the buffers of bsx_mlp_grad by (R, A, D, device) -- the workspace, the [A, G] output row, the 4-column grad_out
-    (columns beyond n_actions stay 0) and, once asked for, grad_x -- so that a captured learner step does not allocate them again."""
-
-    def __init__(self):
-        self.by_key = {}
-
-    def get(self, R, A, D, device, lib, input_grad):
-        key = (int(R), int(A), int(D), str(device))
-        if key not in self.by_key:
-            nb = _lib.c_size_t()
-            _lib.check(lib.bsx_mlp_grad_workspace_bytes(R, A, D, _lib.ctypes.byref(nb)), "bsx_mlp_grad_workspace_bytes")
-            self.by_key[key] = dict(ws=torch.empty(((nb.value + 3) // 4,), dtype=torch.float32, device=device),
-                                    grad=torch.empty((A, grad_floats(D)), dtype=torch.float32, device=device),
-                                    go=torch.zeros((R, A, 4), dtype=torch.float32, device=device), gx=None)
-        buf = self.by_key[key]
-        if input_grad and buf["gx"] is None:
-            buf["gx"] = torch.empty((R, A, D), dtype=torch.float32, device=device)
-        return buf
-
-
-def _check_mlp(net, x, squash, what):
-    """fused_apply's refusals without the A = 2n, D = 3n + 2 tie and without the one of an input that requires grad."""
-    ps = [getattr(net, k) for k in PARAMS]
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or any(not p.is_cuda for p in ps):
-        raise ValueError(f"{what} runs on the GPU: the network and x must be CUDA tensors")
-    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in ps):
-        raise ValueError(f"{what} is float32: the network and x must be float32")
-    if net.w1.shape[2] != H or net.w2.shape[1] != H or net.w2.shape[2] != H:
-        raise ValueError("the fused MLP kernels are built for fc1 = fc2 = 64")
-    A, D = net.n_actors, net.obs_len
-    if not 1 <= A <= 2 * _lib.MAX_N or not 1 <= D <= _lib.MLP_MAX_D or net.n_actions not in (1, 3, 4):
-        raise ValueError(f"the fused MLP kernels take 1 .. {2 * _lib.MAX_N} agents, 1 .. {_lib.MLP_MAX_D} inputs and 1, 3 or 4 outputs, "
-                         f"got {A}, {D} and {net.n_actions}")
-    if x.dim() < 2 or tuple(x.shape[-2:]) != (A, D) or x.numel() == 0:
-        raise ValueError(f"x must be [..., {A}, {D}] and not empty, got {tuple(x.shape)}")
-    if x.device != net.w1.device:
-        raise ValueError("the network and x must be on the same device")
-    if not squash and net.n_actions != 1:
-        raise ValueError("squash=False is the value head: a StackedActor with one output")
 
 
 def mlp_grad(net, blob, x, grad_out, squash=True, input_grad=True):
@@ -239,9 +156,10 @@ def mlp_grad(net, blob, x, grad_out, squash=True, input_grad=True):
     the network packed in `blob` (net.pack()) on x float32 [R, A, D], and the gradient of the same sum with respect to x, float32
     [R, A, D] (None with input_grad=False: the launch is then bsx_actor_grad's kernel).  grad_out: float32 [R, A, n_actions].  net: a
     StackedActor of any n_actors in 1 .. 32 and obs_len in 1 .. 64.  The capturable form: the row, grad_x, the workspace and the
-    4-column copy of grad_out are the network's cached buffers for (R, A, D, device) -- overwritten by the next call with the same key --
-    and nothing is allocated from the second call on.  fused_mlp's backward is this call.  ValueError: fused_mlp's refusals, a blob or
-    a grad_out of another shape."""
+    4-column copy of grad_out are the network's cached buffers for (R, A, D, device) -- ONE set per network, whichever of fused_apply,
+    fused_mlp, fused_grad, mlp_grad or a PPOLearner asks: a row or grad_x one call returned is overwritten by the next call with the
+    same key -- and nothing is allocated from the second call on.  The backward of fused_mlp and of fused_apply is this call.
+    ValueError: fused_mlp's refusals, a blob or a grad_out of another shape."""
     _check_mlp(net, x, squash, "mlp_grad")
     A, D, na = net.n_actors, net.obs_len, net.n_actions
     if x.dim() != 3:
@@ -252,16 +170,16 @@ def mlp_grad(net, blob, x, grad_out, squash=True, input_grad=True):
     need(grad_out, "grad_out", (R, A, na), _F32)
     need(blob, "blob", (A, H * ((D + 1) & ~1) + grad_floats(0) + H * H * 3 // 2), _F32)
     lib = _lib.load()
-    b = net.__dict__.get("_bsx_mlp_buffers")
-    if b is None:
-        b = net.__dict__["_bsx_mlp_buffers"] = _MlpBuffers()
-    buf = b.get(R, A, D, dev, lib, input_grad)
+    buf = _buffers(net).get(R, A, D, dev, lib, go=True, gx=input_grad)
     buf["go"][..., :na].copy_(grad_out)                          # padded to 4 columns: the others hold 0 from the allocation on
     gx = buf["gx"] if input_grad else None
-    _lib.check(lib.bsx_mlp_grad(blob.data_ptr(), x.data_ptr(), buf["go"].data_ptr(), R, A, D, int(bool(squash)), buf["grad"].data_ptr(),
-                                gx.data_ptr() if gx is not None else None, buf["ws"].data_ptr(),
-                                torch.cuda.current_stream(dev).cuda_stream), "bsx_mlp_grad")
-    return buf["grad"], gx
+    return _mlp_grad(lib, buf, blob, x, buf["go"], squash, gx), gx
+
+
+def fused_grad(actor, blob, obs, grad_out, squash=True):
+    """mlp_grad without the input gradient, for an actor on its observations -> the [A, G] gradient row alone: one launch of
+    bsx_actor_grad's kernel.  mlp_grad's checks, and its cached buffers: the row is overwritten by the next call with the same key."""
+    return mlp_grad(actor, blob, obs, grad_out, squash, input_grad=False)[0]
 
 
 class _FusedMlp(torch.autograd.Function):
@@ -282,24 +200,41 @@ class _FusedMlp(torch.autograd.Function):
     def backward(ctx, gy):
         x, blob = ctx.saved_tensors
         row, gx = mlp_grad(ctx.net, blob, x, gy.contiguous(), ctx.squash, input_grad=ctx.needs_input_grad[1])
-        # copies, as in fused_apply: autograd may keep what it is handed, the cached buffers are overwritten by the next call
+        # copies: autograd may keep what it is handed (a parameter's .grad: views of ONE copy of the row), the cached buffers are
+        # overwritten by the next call
         grads = split_grad(row.clone(), ctx.net.n_actions)
         return (None, gx.clone() if gx is not None else None, None, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])])
 
 
+def _apply(net, x, squash):
+    """_FusedMlp on x [..., A, D] flattened to rows -> [..., A, n_actions]."""
+    A, D = net.n_actors, net.obs_len
+    y = _FusedMlp.apply(net, x.reshape(-1, A, D).contiguous(), bool(squash), *[getattr(net, k) for k in PARAMS])
+    return y.reshape(*x.shape[:-1], net.n_actions)
+
+
+def fused_apply(actor, obs, squash=True):
+    """actor(obs) as one HIP kernel forward and one backward: obs float32 [..., A, D] -> [..., A, n_actions], tanh-squashed (squash=True,
+    an actor: exactly FusedActor's float32 scores) or the raw head (squash=False: a value head, n_actions = 1).  Differentiable, once,
+    in the ten parameters of `actor` (a StackedActor on the GPU, float32, fc1 = fc2 = 64) and NOT in obs: fused_mlp on observation rows
+    (A = 2n, D = 3n + 2) that are detached -- the same forward and the same backward (mlp_grad without the input gradient, on the blob
+    the forward packed: an optimiser step between the two does not move it), and the same cached buffers on the actor.
+    ValueError: fused_mlp's refusals, an obs that requires grad, an obs that is not [..., 2n, 3n + 2]."""
+    _check_mlp(actor, obs, squash, "fused_apply", obs_shaped=True)
+    return _apply(actor, obs.detach(), squash)
+
+
 def fused_mlp(net, x, squash=True):
-    """net(x) as one HIP kernel forward and one backward, for an input that is not an observation row: x float32 [..., A, D] ->
+    """net(x) as one HIP kernel forward and one backward, for an input that need not be an observation row: x float32 [..., A, D] ->
     [..., A, n_actions], tanh-squashed (squash=True) or the raw head (squash=False: a value or Q head, n_actions = 1).  net: a
     StackedActor on the GPU, float32, fc1 = fc2 = 64, with any n_actors in 1 .. 32, obs_len in 1 .. 64 and 1, 3 or 4 outputs -- a
     Q critic on obs (+) action, for one.  Differentiable in the ten parameters AND in x when x requires grad (the deterministic policy
-    gradient: dQ/da back through the actor); once differentiable.  The backward is one bsx_mlp_grad call on the blob the forward packed.
-    At A = 2n, D = 3n + 2 the outputs and the parameter gradients are fused_apply's bits.  ValueError: tensors off the GPU, not
-    float32, other hidden sizes, sizes out of range, an x that is not [..., A, D], squash=False with more than one output."""
+    gradient: dQ/da back through the actor); once differentiable.  The backward is one mlp_grad call on the blob the forward packed;
+    its buffers are cached on the network (mlp_grad says how).  At A = 2n, D = 3n + 2 the outputs and the parameter gradients are the
+    bits of bsx_actor_forward and bsx_actor_grad.  ValueError: tensors off the GPU, not float32, other hidden sizes, sizes out of
+    range, an x that is not [..., A, D], squash=False with more than one output."""
     _check_mlp(net, x, squash, "fused_mlp")
-    A, D = net.n_actors, net.obs_len
-    flat = x.reshape(-1, A, D).contiguous()
-    y = _FusedMlp.apply(net, flat, bool(squash), *[getattr(net, k) for k in PARAMS])
-    return y.reshape(*x.shape[:-1], net.n_actions)
+    return _apply(net, x, squash)
 
 
 def categorical_log_prob(actor, obs, actions, temperature=1.0, fused=False):
@@ -728,7 +663,7 @@ class PPOLearner:
 
     A minibatch is a contiguous range of whole ticks [t0, t1) (T % minibatches == 0): views of the tick-major records, no gather; every
     minibatch holds all E games.  minibatch_grads is five calls on the current stream -- pack both networks, ONE bsx_actor_forward that
-    returns scores and value, bsx_ppo_head, bsx_actor_grad for the actor and for the critic -- with cached buffers: no host
+    returns scores and value, bsx_ppo_head, bsx_mlp_grad (bsx_actor_grad's kernel) for the actor and for the critic -- with cached buffers: no host
     synchronisation, and nothing is allocated from the second call of a size on (pack's own temporaries aside), so it can be captured.
     update() runs epochs x minibatches of it in tick order, installs the gradients on the parameters (split_grad), clips their global
     norm if asked, steps the optimiser (torch Adam over both networks and, for the Gaussian head, log_std -- ~5 k floats per agent: not
@@ -806,8 +741,8 @@ class PPOLearner:
         self.vclip = None if vclip is None else _hyper("vclip", vclip)
         self.epochs, self.minibatches = epochs, minibatches
         self.max_grad_norm = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)   # (no clipping is None here)
-        _check(self.actor, ro.obs[:1])
-        _check(self.critic, ro.obs[:1])
+        _check_mlp(self.actor, ro.obs[:1], True, "fused_apply", obs_shaped=True)     # the observation check, under fused_apply's name
+        _check_mlp(self.critic, ro.obs[:1], True, "fused_apply", obs_shaped=True)
         A = self.actor.n_actors
         self.group = share_group(share, A // 2)
         if self.group > 1:
@@ -900,8 +835,7 @@ class PPOLearner:
     def _grads(self, mb, pack, stats):
         """The five calls of a minibatch on its records `mb` (a Minibatch of R contiguous rows: views of a tick range, or gathered)."""
         lib, obs = _lib.load(), mb.obs
-        R, A = obs.shape[:2]
-        n, dev = A // 2, obs.device
+        (R, A, D), dev = obs.shape, obs.device
         b = self._head_buffers(R)
         if pack:
             self.actor.pack(out=self._blob_a)
@@ -911,9 +845,9 @@ class PPOLearner:
                         clip=self.clip, c_v=self.c_v, c_e=self.c_e, temperature=self.temperature, log_std=self.log_std,
                         v_old=mb.value, vclip=self.vclip,
                         out=(b["g_pi"], b["g_v"], b["g_ls"], b["stats"] if stats is None else stats), workspace=b["ws"])
-        # the head's outputs ARE bsx_actor_grad's grad_out (four columns, the unused ones +0): fused_grad's call without its padded copy
-        row_a = _actor_grad(lib, _buffers(self.actor).get(R, n, dev, lib, go=False), self._blob_a, obs, head.g_pi, True)
-        row_v = _actor_grad(lib, _buffers(self.critic).get(R, n, dev, lib, go=False), self._blob_v, obs, head.g_v, False)
+        # the head's outputs ARE bsx_mlp_grad's grad_out (four columns, the unused ones +0): mlp_grad's call without its padded copy
+        row_a = _mlp_grad(lib, _buffers(self.actor).get(R, A, D, dev, lib), self._blob_a, obs, head.g_pi, True)
+        row_v = _mlp_grad(lib, _buffers(self.critic).get(R, A, D, dev, lib), self._blob_v, obs, head.g_v, False)
         return row_a, row_v, head.g_log_std, head.stats
 
     def install(self, row_a, row_v, g_log_std):

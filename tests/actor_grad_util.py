@@ -1,7 +1,7 @@
 """What the tests of the actor's fused training pass (learner.fused_apply, csrc/bsx_actor_grad.hip) share:
 
   CASES            (class, n, outputs, squash) on the input classes of actor_ref_util, team sizes 1 .. 16; LARGE: (n, rows) with many rows
-  plan             workgroups per agent and rounds of a launch, from the library's own workspace size
+  plan             workgroups per agent and rounds of a launch at (rows, A, D), from the library's own workspace size
   reference        per case, cached: the float64 autograd gradients g64 (torch on the CPU, loss = (y * go).sum()), the float32 ones g32 of
                    the same network (the yardstick: what float32 itself loses on these inputs), the upstream gradient go and the share of
                    rows it leaves out
@@ -9,11 +9,14 @@
                    its mask between float32 and float64 and moves a summed gradient by a whole row's contribution (~1/R of the sum, against
                    ~1e-7 for rounding), so go = 0 on every row (e, a) where, in float64, any of the 128 post-LayerNorm pre-ReLU values has
                    |y| < 1e-4.  The same go feeds the reference, the yardstick and the kernel
-  permutation_spread   how far the yardstick's own error moves when the rows are summed in another order
-  factors / check  the bound: per tensor, mean(e_k) <= fm mean(e_t) and max(e_k) <= fx max(e_t), with (fm, fx) = the project's (2, 4)
-                   (actor_ref_util.F32_FACTORS) except where the recorded spread of the yardstick reaches them
+  spread / row_permutation_spread / permutation_spread   how far the yardstick's own error moves under an equivalent float32
+                   evaluation: the accumulator, the rows summed in another order, and the latter for a case of this file
+  factors / ratios / check  the bound: per tensor, mean(e_k) <= fm mean(e_t) and max(e_k) <= fx max(e_t), with (fm, fx) = the project's
+                   (2, 4) (actor_ref_util.F32_FACTORS) except where the recorded spread of the yardstick reaches them
                    (profiles/actor_grad_float64.json says where and why)
 
+plan, autograd_grads (with the input's gradient as an eleventh tensor "x" on request), spread, row_permutation_spread, ratios and check
+are the one yardstick of every fused-gradient test: tests/mlp_grad_util.py brings its own cases and factors and imports these.
 Nothing here imports the native library but plan()."""
 import functools
 import json
@@ -47,15 +50,16 @@ MULTI_ROUND = tuple(c for c in CASES if c[1] >= 8)
 LARGE = ((1, 33000), (4, 8300))
 
 
-def plan(rows, n):
-    """(workgroups per agent P, rounds) of bsx_actor_grad at (rows, n), P read back from the workspace size the library asks for."""
+def plan(rows, A, D):
+    """(workgroups per agent P, rounds) of bsx_mlp_grad at (rows, A, D) -- bsx_actor_grad at (rows, n) is (rows, 2n, 3n + 2) --, P read
+    back from the workspace size the library asks for."""
     import ctypes
     from deep_rl_battlespace_amd import _lib
     nb = _lib.c_size_t()
-    _lib.check(_lib.load().bsx_actor_grad_workspace_bytes(rows, n, ctypes.byref(nb)), "bsx_actor_grad_workspace_bytes")
-    G = 64 * (3 * n + 2) + 4096 + 6 * 64 + 260
-    assert nb.value % (2 * n * G * 4) == 0
-    P = nb.value // (2 * n * G * 4)
+    _lib.check(_lib.load().bsx_mlp_grad_workspace_bytes(rows, A, D, ctypes.byref(nb)), "bsx_mlp_grad_workspace_bytes")
+    G = 64 * D + 4096 + 6 * 64 + 260
+    assert nb.value % (A * G * 4) == 0
+    P = nb.value // (A * G * 4)
     tiles = (rows + 31) // 32
     return P, (tiles + 4 * P - 1) // (4 * P)
 
@@ -95,12 +99,15 @@ def kink_free_go(actor, obs, seed=0):
     return go, near.double().mean(0).numpy()
 
 
-def autograd_grads(actor, obs, go, squash, dtype):
-    """{name: float64 array}: d (y * go).sum() / d parameter, torch autograd on the CPU in `dtype`."""
-    a = R.to_float64(actor) if dtype == torch.float64 else R.to_cpu32(actor)
-    y = a(obs.detach().cpu().to(dtype), squash=squash)
-    (y * go.to(dtype)).sum().backward()
-    return {k: getattr(a, k).grad.double().numpy() for k in PARAMS}
+def autograd_grads(net, x, go, squash, dtype, input_grad=False):
+    """{name: float64 array}: d (y * go).sum() / d parameter, torch autograd on the CPU in `dtype`; input_grad: and d / d x, as "x"."""
+    a = R.to_float64(net) if dtype == torch.float64 else R.to_cpu32(net)
+    xx = x.detach().cpu().to(dtype).requires_grad_(input_grad)
+    (a(xx, squash=squash) * go.to(dtype)).sum().backward()
+    out = {k: getattr(a, k).grad.double().numpy() for k in PARAMS}
+    if input_grad:
+        out["x"] = xx.grad.double().numpy()
+    return out
 
 
 def build_case(case, rows=None, seed=0):
@@ -134,22 +141,36 @@ def reference_large(n, rows, seed=0):
     return actor, obs, go, g64, g32, share
 
 
-def permutation_spread(case, perms=8):
-    """{name: (max ratio, mean ratio)}: over `perms` row permutations, how far max(e_t) and mean(e_t) move from the unpermuted yardstick
-    (the larger of p / base and base / p).  `case`: one of CASES, or a reference tuple."""
-    actor, obs, go, g64, g32, _ = reference(case) if isinstance(case[0], str) else case
-    squash = case[3] if isinstance(case[0], str) else True
-    out = {k: [1.0, 1.0] for k in PARAMS}
-    for p in range(perms):
-        idx = torch.randperm(obs.shape[0], generator=torch.Generator().manual_seed(4000 + p))
-        gp = autograd_grads(actor, obs[idx].contiguous(), go[idx].contiguous(), squash, torch.float32)
-        for k in PARAMS:
+def spread(g64, g32, others, names=PARAMS):
+    """{name: (max ratio, mean ratio)}: how far max(e_t) and mean(e_t) of the float32 yardstick g32 move over `others`, equivalent
+    float32 evaluations of the same gradients (the larger of p / base and base / p; an error of exactly 0 on either side is skipped)."""
+    out = {k: [1.0, 1.0] for k in names}
+    for gp in others:
+        for k in names:
             e0, e1 = np.abs(g32[k] - g64[k]), np.abs(gp[k] - g64[k])
             for i, f in enumerate((np.max, np.mean)):
                 a, b = float(f(e0)), float(f(e1))
                 if a > 0 and b > 0:
                     out[k][i] = max(out[k][i], a / b, b / a)
     return {k: tuple(v) for k, v in out.items()}
+
+
+def row_permutation_spread(net, x, go, g64, g32, squash, names=PARAMS, perms=8):
+    """spread over `perms` orders of the rows (seeds 4000 + p): the same network, the same rows, another summation order.  With "x" in
+    `names` the input's gradient is compared row by row."""
+    def permuted(p):
+        idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(4000 + p))
+        gp = autograd_grads(net, x[idx].contiguous(), go[idx].contiguous(), squash, torch.float32, "x" in names)
+        if "x" in names:
+            gp["x"] = gp["x"][torch.argsort(idx).numpy()]
+        return gp
+    return spread(g64, g32, (permuted(p) for p in range(perms if x.shape[0] > 1 else 0)), names)
+
+
+def permutation_spread(case, perms=8):
+    """row_permutation_spread of `case`: one of CASES, or a reference tuple."""
+    actor, obs, go, g64, g32, _ = reference(case) if isinstance(case[0], str) else case
+    return row_permutation_spread(actor, obs, go, g64, g32, case[3] if isinstance(case[0], str) else True, PARAMS, perms)
 
 
 @functools.lru_cache(maxsize=None)
@@ -159,10 +180,10 @@ def factors():
     return {k: tuple(f[k]) for k in PARAMS}
 
 
-def ratios(got, g64, g32):
-    """{name: (mean(e_k) / mean(e_t), max(e_k) / max(e_t), max(e_k) / max|g64|)}."""
+def ratios(got, g64, g32, names=PARAMS):
+    """{name: (mean(e_k) / mean(e_t), max(e_k) / max(e_t), max(e_k) / max|g64|)}; 0 / 0 counts as 0, x / 0 as inf."""
     out = {}
-    for k in PARAMS:
+    for k in names:
         ek, et = np.abs(np.asarray(got[k], np.float64) - g64[k]), np.abs(g32[k] - g64[k])
         out[k] = (float(ek.mean() / et.mean()) if et.mean() > 0 else (0.0 if ek.mean() == 0 else float("inf")),
                   float(ek.max() / et.max()) if et.max() > 0 else (0.0 if ek.max() == 0 else float("inf")),
@@ -170,14 +191,13 @@ def ratios(got, g64, g32):
     return out
 
 
-def check(got, g64, g32, what=""):
-    """Every tensor within its factors of the yardstick's error; prints the figures first.  Returns the ratios."""
-    r = ratios(got, g64, g32)
-    bad = []
-    for k in PARAMS:
-        fm, fx = factors()[k]
-        print(f"{what} {k}: mean ratio {r[k][0]:.3f} (<= {fm}), max ratio {r[k][1]:.3f} (<= {fx}), max error / max|g| {r[k][2]:.2e}")
-        if not (r[k][0] <= fm and r[k][1] <= fx):
-            bad.append((k, r[k]))
+def check(got, g64, g32, what="", names=PARAMS, factor_of=None):
+    """Every tensor of `names` within its factors (fm, fx) = factor_of(name) of the yardstick's error -- the actor's recorded factors()
+    unless the caller brings its own; prints the figures first.  Returns the ratios."""
+    r = ratios(got, g64, g32, names)
+    f = {k: (factor_of or factors().__getitem__)(k) for k in names}
+    for k in names:
+        print(f"{what} {k}: mean ratio {r[k][0]:.3f} (<= {f[k][0]}), max ratio {r[k][1]:.3f} (<= {f[k][1]}), max error / max|g| {r[k][2]:.2e}")
+    bad = [(k, r[k]) for k in names if not (r[k][0] <= f[k][0] and r[k][1] <= f[k][1])]
     assert not bad, (what, bad)
     return r

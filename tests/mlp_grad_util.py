@@ -6,14 +6,14 @@ bsx_mlp_grad) share:
   build / reference   per case, cached: the network, x uniform in [-1, 1], a kink-free go (actor_grad_util.kink_free_go: 0 on every row
                    where, in float64, a pre-ReLU value is within 1e-4 of 0), the float64 autograd gradients of (y * go).sum() in the ten
                    parameters AND in x (torch on the CPU), the float32 ones of the same (the yardstick), the share of rows left out
-  ratios / check   the bound of actor_grad_util, with x as an eleventh tensor: mean(e_k) <= fm mean(e_t), max(e_k) <= fx max(e_t),
+  ratios / check   actor_grad_util's, with x as an eleventh tensor: mean(e_k) <= fm mean(e_t), max(e_k) <= fx max(e_t),
                    (fm, fx) = actor_ref_util.F32_FACTORS = (2, 4) for every tensor, except where the recorded spread of the yardstick
-                   itself reaches them (profiles/mlp_input_grad.json says where and why)
+                   itself reaches them (factor_of: profiles/mlp_input_grad.json says where and why)
   unit_permutation_spread   how far the yardstick's own error moves when the SAME network is written with its hidden units in another
                    order (another summation order of the same float32 sums): the spread a one-row case has, where no row order exists
-  row_permutation_spread    the same under another order of the rows (actor_grad_util.permutation_spread's method): what moves b3
+  row_permutation_spread    the same under another order of the rows (actor_grad_util.row_permutation_spread): what moves b3
   factor_rule      the rule that turns a recorded spread into factors, stated once (tools/measure_mlp_grad.py writes what it gives)
-  plan             workgroups per agent and rounds of a bsx_mlp_grad launch, from the library's own workspace size
+  plan / spread    actor_grad_util's: workgroups per agent and rounds of a bsx_mlp_grad launch; the spread accumulator
   ddpg_case        one DDPG step at 1v1: actor 5 -> 4, critic 9 -> 1, 96 rows, the row weights w that leave both networks' kinks out
 
 Nothing here imports the native library but plan()."""
@@ -21,7 +21,6 @@ import functools
 import json
 import os
 
-import numpy as np
 import torch
 
 import actor_grad_util as U
@@ -30,7 +29,7 @@ import actor_ref_util as R
 PARAMS = U.PARAMS
 TENSORS = PARAMS + ("x",)
 FM, FX = R.F32_FACTORS
-KINK_CAP = U.KINK_CAP
+KINK_CAP, plan, spread = U.KINK_CAP, U.plan, U.spread
 PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mlp_input_grad.json")
 
 # (A, D, outputs, squash, row counts): what each line reaches is said in the comment behind it
@@ -77,13 +76,13 @@ def build(case, seed=0):
 
 
 def autograd_grads(net, x, go, squash, dtype):
-    """{tensor: float64 array}: d (y * go).sum() / d (the ten parameters, x), torch autograd on the CPU in `dtype`."""
-    a = R.to_float64(net) if dtype == torch.float64 else R.to_cpu32(net)
-    xx = x.detach().cpu().to(dtype).requires_grad_()
-    (a(xx, squash=squash) * go.to(dtype)).sum().backward()
-    out = {k: getattr(a, k).grad.double().numpy() for k in PARAMS}
-    out["x"] = xx.grad.double().numpy()
-    return out
+    """actor_grad_util.autograd_grads with the input's gradient: the ten parameters and "x"."""
+    return U.autograd_grads(net, x, go, squash, dtype, input_grad=True)
+
+
+def ratios(got, g64, g32, names=TENSORS):
+    """actor_grad_util.ratios over x as well."""
+    return U.ratios(got, g64, g32, names)
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,8 +97,8 @@ def unit_permutation_spread(case, perms=8):
     taken in another order), how far max(e_t) and mean(e_t) of the float32 yardstick move from the unpermuted one (the larger of p / base
     and base / p).  No kernel output enters."""
     net, x, go, g64, g32, _ = reference(case)
-    out = {k: [1.0, 1.0] for k in TENSORS}
-    for p in range(perms):
+
+    def permuted(p):
         g = torch.Generator().manual_seed(6000 + p)
         p1, p2 = torch.randperm(64, generator=g), torch.randperm(64, generator=g)
         q1, q2 = torch.argsort(p1), torch.argsort(p2)
@@ -114,31 +113,15 @@ def unit_permutation_spread(case, perms=8):
         back["w1"] = gp["w1"][:, :, q1]; back["w2"] = gp["w2"][:, q1][:, :, q2]; back["w3"] = gp["w3"][:, q2]
         for k, qq in (("b1", q1), ("g1", q1), ("h1", q1), ("b2", q2), ("g2", q2), ("h2", q2)):
             back[k] = gp[k][:, :, qq]
-        for k in TENSORS:
-            e0, e1 = np.abs(g32[k] - g64[k]), np.abs(back[k] - g64[k])
-            for i, f in enumerate((np.max, np.mean)):
-                a, b = float(f(e0)), float(f(e1))
-                if a > 0 and b > 0:
-                    out[k][i] = max(out[k][i], a / b, b / a)
-    return {k: tuple(v) for k, v in out.items()}
+        return back
+    return spread(g64, g32, (permuted(p) for p in range(perms)), TENSORS)
 
 
 def row_permutation_spread(case, perms=8):
-    """{tensor: (max ratio, mean ratio)}: the same under `perms` orders of the ROWS (actor_grad_util.permutation_spread's method and
-    seeds): what moves a sum over rows such as b3, which has one value per agent and output.  x's gradient is compared row by row."""
+    """{tensor: (max ratio, mean ratio)}: the same under `perms` orders of the ROWS (actor_grad_util.row_permutation_spread: its method
+    and seeds): what moves a sum over rows such as b3, which has one value per agent and output.  x's gradient is compared row by row."""
     net, x, go, g64, g32, _ = reference(case)
-    out = {k: [1.0, 1.0] for k in TENSORS}
-    for p in range(perms if x.shape[0] > 1 else 0):
-        idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(4000 + p))
-        gp = autograd_grads(net, x[idx].contiguous(), go[idx].contiguous(), case[3], torch.float32)
-        gp["x"] = gp["x"][torch.argsort(idx).numpy()]
-        for k in TENSORS:
-            e0, e1 = np.abs(g32[k] - g64[k]), np.abs(gp[k] - g64[k])
-            for i, f in enumerate((np.max, np.mean)):
-                a, b = float(f(e0)), float(f(e1))
-                if a > 0 and b > 0:
-                    out[k][i] = max(out[k][i], a / b, b / a)
-    return {k: tuple(v) for k, v in out.items()}
+    return U.row_permutation_spread(net, x, go, g64, g32, case[3], TENSORS, perms)
 
 
 def factor_rule(max_spread, mean_spread):
@@ -174,40 +157,14 @@ def factors():
     return {cid: {k: tuple(v) for k, v in t.items()} for cid, t in f.items()}
 
 
-def ratios(got, g64, g32, names=TENSORS):
-    """{tensor: (mean(e_k) / mean(e_t), max(e_k) / max(e_t), max(e_k) / max|g64|)}; 0 / 0 counts as 0, x / 0 as inf."""
-    out = {}
-    for k in names:
-        ek, et = np.abs(np.asarray(got[k], np.float64) - g64[k]), np.abs(g32[k] - g64[k])
-        out[k] = (float(ek.mean() / et.mean()) if et.mean() > 0 else (0.0 if ek.mean() == 0 else float("inf")),
-                  float(ek.max() / et.max()) if et.max() > 0 else (0.0 if ek.max() == 0 else float("inf")),
-                  float(ek.max() / max(np.abs(g64[k]).max(), 1e-300)))
-    return out
+def factor_of(cid):
+    """name -> (fm, fx) for case `cid`: its recorded exception, the one under "*", or (FM, FX)."""
+    return lambda k: factors().get(cid, {}).get(k, factors().get("*", {}).get(k, (FM, FX)))
 
 
 def check(got, g64, g32, what="", names=TENSORS, cid=None):
-    """Every tensor within its factors of the yardstick's error -- (FM, FX), or case `cid`'s recorded exception; prints the figures
-    first.  Returns the ratios."""
-    r = ratios(got, g64, g32, names)
-    f = {k: factors().get(cid, {}).get(k, factors().get("*", {}).get(k, (FM, FX))) for k in names}
-    for k in names:
-        print(f"{what} {k}: mean ratio {r[k][0]:.3f} (<= {f[k][0]}), max ratio {r[k][1]:.3f} (<= {f[k][1]}), max error / max|g| {r[k][2]:.2e}")
-    bad = [(k, r[k]) for k in names if not (r[k][0] <= f[k][0] and r[k][1] <= f[k][1])]
-    assert not bad, (what, bad)
-    return r
-
-
-def plan(rows, A, D):
-    """(workgroups per agent P, rounds) of bsx_mlp_grad at (rows, A, D), P read back from the workspace size the library asks for."""
-    import ctypes
-    from deep_rl_battlespace_amd import _lib
-    nb = _lib.c_size_t()
-    _lib.check(_lib.load().bsx_mlp_grad_workspace_bytes(rows, A, D, ctypes.byref(nb)), "bsx_mlp_grad_workspace_bytes")
-    G = 64 * D + 4096 + 6 * 64 + 260
-    assert nb.value % (A * G * 4) == 0
-    P = nb.value // (A * G * 4)
-    tiles = (rows + 31) // 32
-    return P, (tiles + 4 * P - 1) // (4 * P)
+    """actor_grad_util.check with case `cid`'s factors.  Returns the ratios."""
+    return U.check(got, g64, g32, what, names, factor_of(cid))
 
 
 # ------------------------------------------------------------------------------------------------ one DDPG step

@@ -72,6 +72,23 @@ def test_workspace_bytes_is_positive_monotone_in_rows_bounded_and_refuses_what_t
     assert lib.bsx_actor_grad_workspace_bytes(10, 1, None) == ARG
 
 
+def test_the_workspace_is_the_mlp_entrys_at_2n_agents_and_3n_plus_2_inputs_and_both_refuse_the_same_sizes():
+    """bsx_actor_grad_workspace_bytes(R, n) delegates to bsx_mlp_grad_workspace_bytes(R, 2n, 3n + 2): the same bytes at every (n, rows)
+    the GPU tests run -- CASES at their dense row count, LARGE -- and at one row; BSX_E_ARG from both for a team size or a row count
+    out of range.  Size queries: no GPU is touched."""
+    L = _lib(); lib = L.load()
+    sizes = {(c[1], 5001 - 2 * c[1]) for c in U.CASES} | set(U.LARGE) | {(n, 1) for n in range(1, MAX_N + 1)}
+    for n, rows in sorted(sizes):
+        a, b = L.c_size_t(0), L.c_size_t(1)
+        assert lib.bsx_actor_grad_workspace_bytes(rows, n, ctypes.byref(a)) == 0
+        assert lib.bsx_mlp_grad_workspace_bytes(rows, 2 * n, 3 * n + 2, ctypes.byref(b)) == 0
+        assert a.value == b.value > 0, (n, rows)
+    for n, rows in ((0, 10), (MAX_N + 1, 10), (1, 0)):
+        a, b = L.c_size_t(7), L.c_size_t(7)
+        assert lib.bsx_actor_grad_workspace_bytes(rows, n, ctypes.byref(a)) == ARG and a.value == 7
+        assert lib.bsx_mlp_grad_workspace_bytes(rows, 2 * n, 3 * n + 2, ctypes.byref(b)) == ARG and b.value == 7
+
+
 def test_actor_grad_refuses_before_any_launch_in_the_documented_order():
     lib = _lib().load()
 
@@ -143,7 +160,7 @@ def test_the_multi_round_cases_still_go_round_twice_and_the_wide_teams_still_tak
     rounds = {}
     for case in U.CASES:
         rows, n = 5001 - 2 * case[1], case[1]
-        P, rounds[case] = U.plan(rows, n)
+        P, rounds[case] = U.plan(rows, 2 * n, 3 * n + 2)
         assert 1 <= P <= 512 // (2 * n)
         print(U.case_id(case), "rows", rows, "workgroups per agent", P, "rounds", rounds[case])
     assert {c[1] for c in U.MULTI_ROUND} == {8, 10, 11, 13, 16}
@@ -153,13 +170,13 @@ def test_the_multi_round_cases_still_go_round_twice_and_the_wide_teams_still_tak
     wide = [c for c in U.CASES if c[1] >= 11]
     assert len(wide) == 5 and all(3 * c[1] + 2 > 32 for c in wide) and {3 * c[1] + 2 for c in U.CASES if 5 <= c[1] <= 10} == {17, 26, 32}
     for n, rows in U.LARGE:
-        P, r = U.plan(rows, n)
+        P, r = U.plan(rows, 2 * n, 3 * n + 2)
         print("large", n, rows, "workgroups per agent", P, "rounds", r)
         assert r == 2 and P == 512 // (2 * n)
-    assert U.plan(33000, 1)[0] == 256                                              # the merge kernel's widest input
+    assert U.plan(33000, 2, 5)[0] == 256                                           # the merge kernel's widest input
     # the ragged, appended-rows, layout and graph legs at 16 a side (tests/test_hip_actor_grad.py)
-    assert U.plan(2048, 16) == (16, 1) and U.plan(2049, 16) == (16, 2) and U.plan(2081, 16) == (16, 2) and U.plan(2100, 16) == (16, 2)
-    assert U.plan(257, 11)[1] == 1 and U.plan(300, 16)[1] == 1
+    assert U.plan(2048, 32, 50) == (16, 1) and U.plan(2049, 32, 50) == (16, 2) and U.plan(2081, 32, 50) == (16, 2) and U.plan(2100, 32, 50) == (16, 2)
+    assert U.plan(257, 22, 35)[1] == 1 and U.plan(300, 32, 50)[1] == 1
 
 
 def test_a_gradient_row_splits_where_cat_of_the_flattened_parameters_puts_it():

@@ -71,7 +71,7 @@ def test_many_rows_at_the_workgroup_cap_keep_the_float64_bound_over_two_rounds(n
     twice (tests/test_actor_grad_cpu.py derives both from the workspace size), the second round nearly empty; at n = 1 the merge kernel
     adds 256 partial rows per agent.  The same reference, yardstick and factors as above."""
     actor_cpu, obs_cpu, go, g64, g32, share = U.reference_large(n, rows)
-    assert float(share.max()) <= U.KINK_CAP and U.plan(rows, n) == (512 // (2 * n), 2)
+    assert float(share.max()) <= U.KINK_CAP and U.plan(rows, 2 * n, 3 * n + 2) == (512 // (2 * n), 2)
     actor, obs, y, got = _fused_grads(actor_cpu, obs_cpu, go, True)
     assert y.shape == (rows, 2 * n, 4)
     U.check(got, g64, g32, f"LARGE n={n} rows={rows}")
@@ -218,7 +218,7 @@ def test_the_same_inputs_give_the_same_bits_eagerly_and_from_a_captured_graph():
 
 
 def test_sixteen_a_side_over_two_rounds_gives_the_same_bits_eagerly_and_from_a_captured_graph():
-    assert U.plan(2100, 16)[1] == 2
+    assert U.plan(2100, 32, 50)[1] == 2
     _same_bits_eagerly_and_from_a_graph(16, 2100)
 
 

@@ -2,8 +2,9 @@
 the ten parameter gradients and grad_x against float64 autograd at (2, 4) times what float32 autograd itself loses on the same inputs
 (tests/mlp_grad_util.py: ReLU kinks left out by construction; a larger factor only where profiles/mlp_input_grad.json records that the
 yardstick itself moves by as much: one-row cases, and b3 under row order), on the table of shapes from one row of one input to 32 agents over two
-rounds; exact zeros where grad_out is zero; the bits of bsx_actor_forward / bsx_actor_grad / fused_apply at (2n, 3n + 2), with and
-without grad_x; guard slabs around grad_x at ragged sizes; the same bits on every call and from a captured graph; one DDPG step whose
+rounds; exact zeros where grad_out is zero; the bits of bsx_actor_forward / bsx_actor_grad at (2n, 3n + 2), with and without grad_x,
+from the raw entries and from fused_apply and fused_mlp (one path in learner.py: both are held to the raw actor entries, not to each
+other), and the one buffer set they share on a network; guard slabs around grad_x at ragged sizes; the same bits on every call and from a captured graph; one DDPG step whose
 actor gradients come through the critic's input gradient; the documented refusals."""
 import numpy as np
 import pytest
@@ -81,8 +82,10 @@ def _raw_grad(lib, L, blob, x, go4, squash, A, D, how):
 
 @pytest.mark.parametrize("n,rows", [(1, 129), (2, 129), (16, 129), (16, 2100)])
 def test_at_2n_agents_and_3n_plus_2_inputs_the_entries_give_the_actor_entries_bits(n, rows):
+    """bsx_actor_grad delegates to bsx_mlp_grad with grad_x = NULL, so the backward's `plain` comparison holds the delegation (the team
+    size to (A, D)) and `with_dx` the second kernel; what anchors the kernels themselves are the float64 tests of this file and of
+    tests/test_hip_actor_grad.py."""
     from deep_rl_battlespace_amd import _lib as L
-    from deep_rl_battlespace_amd.learner import fused_apply, fused_mlp
     lib = L.load()
     A, D = 2 * n, 3 * n + 2
     torch.manual_seed(20 + n)
@@ -110,20 +113,77 @@ def test_at_2n_agents_and_3n_plus_2_inputs_the_entries_give_the_actor_entries_bi
     L.check(lib.bsx_mlp_forward(blob.data_ptr(), x.data_ptr(), y2.data_ptr(), None, rows, A, D, _stream()), "bsx_mlp_forward")
     torch.cuda.synchronize()
     assert torch.equal(y1, y0) and torch.equal(v1, v0) and torch.equal(y2, y0) and bool((y0 != 7.0).all()) and bool((v0 != 7.0).all())
-    # the autograd functions: outputs and the ten parameter gradients
-    for m, squash in ((net, True), (critic, False)):
-        go = torch.randn((rows, A, m.n_actions), device="cuda")
-        res = []
-        for f in (fused_apply, fused_mlp):
-            for k in M.PARAMS:
-                getattr(m, k).grad = None
-            y = f(m, x, squash=squash)
-            (y * go).sum().backward()
-            res.append((y.detach().clone(), [getattr(m, k).grad.clone() for k in M.PARAMS]))
+    # the autograd functions: outputs and the ten parameter gradients, each against the raw actor entries
+    _both_functions_give_the_raw_actor_entries_bits(net, x, True)
+    _both_functions_give_the_raw_actor_entries_bits(critic, x, False)
+
+
+def _both_functions_give_the_raw_actor_entries_bits(net, x, squash):
+    """fused_apply and fused_mlp (x not requiring grad) on `net`: the output and the ten .grad tensors are, bit for bit, what direct
+    ctypes calls of bsx_actor_forward and bsx_actor_grad give on the same blob, x and padded grad_out."""
+    from deep_rl_battlespace_amd import _lib as L
+    from deep_rl_battlespace_amd.learner import fused_apply, fused_mlp, split_grad
+    lib = L.load()
+    (rows, A, D), na = x.shape, net.n_actions
+    go = torch.randn((rows, A, na), device="cuda")
+    go4 = torch.zeros((rows, A, 4), device="cuda")
+    go4[..., :na] = go
+    blob = net.pack()
+    y0, v0 = torch.full((rows, A, 4), 7.0, device="cuda"), torch.full((rows, A), 7.0, device="cuda")
+    nz = L.BsxActorNoise()
+    nz.value_weights, nz.value = blob.data_ptr(), v0.data_ptr()
+    L.check(lib.bsx_actor_forward(blob.data_ptr(), x.data_ptr(), y0.data_ptr(), rows, A // 2, L.ACTOR_F32, L.ctypes.byref(nz), 0, 0, None, 0,
+                                  _stream()), "bsx_actor_forward")
+    row, _ = _raw_grad(lib, L, blob, x, go4, int(squash), A, D, "actor")
+    want_y, want = (y0[..., :na] if squash else v0.unsqueeze(-1)), split_grad(row, na)
+    assert bool((y0 != 7.0).all()) and bool((v0 != 7.0).all()) and bool((row != 7.0).all())
+    for f in (fused_apply, fused_mlp):
+        for k in M.PARAMS:
+            getattr(net, k).grad = None
+        y = f(net, x, squash=squash)
+        (y * go).sum().backward()
         torch.cuda.synchronize()
-        assert torch.equal(res[0][0], res[1][0])
-        for k, a, b in zip(M.PARAMS, res[0][1], res[1][1]):
-            assert torch.equal(a, b), k
+        assert y.shape == (rows, A, na) and torch.equal(y.detach(), want_y), f.__name__
+        for k, w in zip(M.PARAMS, want):
+            assert torch.equal(getattr(net, k).grad, w), (f.__name__, k)
+        assert x.grad is None
+
+
+# (1, 129): D = 5, one dW1 tile and a ragged last tile; (11, 129): D = 35, the first two-tile (MT1 = 2) size of an actor
+@pytest.mark.parametrize("squash,outputs", [(True, 4), (False, 1)])
+@pytest.mark.parametrize("n,rows", [(1, 129), (11, 129)])
+def test_fused_apply_and_fused_mlp_give_the_bits_of_the_raw_actor_entries(n, rows, squash, outputs):
+    A, D = 2 * n, 3 * n + 2
+    torch.manual_seed(60 + n + outputs)
+    net = R._new(A, D, outputs, device="cuda")
+    _both_functions_give_the_raw_actor_entries_bits(net, torch.rand((rows, A, D), device="cuda") * 2 - 1, squash)
+
+
+def test_a_network_used_through_both_functions_holds_one_buffer_set_and_allocates_once():
+    """fused_apply, fused_mlp without and fused_mlp with an input gradient on ONE 1v1 actor: one cache with one key, the same workspace
+    and gradient row throughout, grad_x from the third on, and nothing new from a fourth call."""
+    from deep_rl_battlespace_amd.learner import _buffers, fused_apply, fused_mlp
+    A, D, rows = 2, 5, 33
+    torch.manual_seed(9)
+    net = R._new(A, D, 4, device="cuda")
+    x, go = torch.rand((rows, A, D), device="cuda") * 2 - 1, torch.randn((rows, A, 4), device="cuda")
+    xg = x.clone().requires_grad_()
+
+    def step(f, xx):
+        for k in M.PARAMS:
+            getattr(net, k).grad = None
+        xx.grad = None
+        (f(net, xx) * go).sum().backward()
+        torch.cuda.synchronize()
+        assert len([a for a in vars(net) if a.startswith("_bsx") and a.endswith("buffers")]) == 1
+        (key, buf), = _buffers(net).by_key.items()                 # one cache with one key
+        return key, buf["ws"].data_ptr(), buf["grad"].data_ptr(), (buf["gx"].data_ptr() if buf["gx"] is not None else None)
+    first, second, third = step(fused_apply, x), step(fused_mlp, x), step(fused_mlp, xg)
+    assert first[0] == (rows, A, D, "cuda:0") and first[3] is None
+    assert second == first
+    assert third[:3] == first[:3] and third[3] is not None and xg.grad is not None and bool(xg.grad.any())
+    held = torch.cuda.memory_allocated()
+    assert step(fused_mlp, xg) == third and torch.cuda.memory_allocated() == held
 
 
 # ---------------------------------------------------------------------------------------------------- 3. guards

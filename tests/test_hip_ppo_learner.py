@@ -220,7 +220,7 @@ def _five_calls_on_clones(learner, t0, t1):
     """minibatch_grads(t0, t1) written out -- pack, forward, ppo_head, bsx_actor_grad twice -- on .clone()s of the sliced records
     (fresh allocations: aligned, whatever the views' offsets are) and buffers of its own -> (actor row, critic row, g_log_std, stats)."""
     from deep_rl_battlespace_amd import _lib
-    from deep_rl_battlespace_amd.learner import _GradBuffers, _actor_grad, ppo_head
+    from deep_rl_battlespace_amd.learner import _Buffers, _mlp_grad, ppo_head
     ro, lib = learner.rollout, _lib.load()
     E, A, D = ro.obs.shape[1:]
     n, R, dev = A // 2, (t1 - t0) * E, ro.obs.device
@@ -235,8 +235,8 @@ def _five_calls_on_clones(learner, t0, t1):
     head = ppo_head(learner.kind, y, v, flat(ro.scores), flat(ro.logp), flat(ro.adv), flat(ro.ret), flat(ro._mask), clip=learner.clip,
                     c_v=learner.c_v, c_e=learner.c_e, temperature=learner.temperature, log_std=learner.log_std,
                     v_old=flat(ro.value) if learner.vclip is not None else None, vclip=learner.vclip)
-    row_a = _actor_grad(lib, _GradBuffers().get(R, n, dev, lib, go=False), blob_a, obs, head.g_pi, True)
-    row_v = _actor_grad(lib, _GradBuffers().get(R, n, dev, lib, go=False), blob_v, obs, head.g_v, False)
+    row_a = _mlp_grad(lib, _Buffers().get(R, A, D, dev, lib), blob_a, obs, head.g_pi, True)
+    row_v = _mlp_grad(lib, _Buffers().get(R, A, D, dev, lib), blob_v, obs, head.g_v, False)
     return row_a, row_v, head.g_log_std, head.stats
 
 

@@ -63,7 +63,7 @@ def _by_hand(ro, kind, minibatch_of):
     """STEPS optimiser steps on the rollout's own blobs from the raw calls: the forward, the head, both backward calls on fresh buffers,
     adam_step -> what DU._everything lists (shared tensors, moments, count, head rows, step rows[, log_std moments])."""
     from deep_rl_battlespace_amd import _lib
-    from deep_rl_battlespace_amd.learner import AdamState, _actor_forward, _actor_grad, _GradBuffers, adam_hyper, adam_step, ppo_head
+    from deep_rl_battlespace_amd.learner import AdamState, _actor_forward, _Buffers, _mlp_grad, adam_hyper, adam_step, ppo_head
     lib = _lib.load()
     nets = [ro.actor, ro.value_actor]
     states = [AdamState(ro.actor), AdamState(ro.value_actor)]
@@ -72,13 +72,13 @@ def _by_hand(ro, kind, minibatch_of):
     head_rows, step_rows = [], []
     for i in range(STEPS):
         mb = minibatch_of(i)
-        R, A = mb.obs.shape[:2]
+        R, A, D = mb.obs.shape
         y, v = torch.empty((R, A, 4), device="cuda"), torch.empty((R, A), device="cuda")
         _actor_forward(lib, ro.fused.weights, mb.obs, y, ro._value_w, v)
         head = ppo_head(kind, y, v, mb.rec, mb.logp, mb.adv, mb.ret, mb.mask, clip=KW["clip"], c_v=KW["c_v"], c_e=KW["c_e"],
                         temperature=L.TAU if kind == "categorical" else 1.0, log_std=ro.log_std if kind == "gaussian" else None,
                         v_old=mb.value, vclip=KW["vclip"])
-        rows = [_actor_grad(lib, _GradBuffers().get(R, A // 2, "cuda:0", lib, go=False), blob, mb.obs, g, squash)
+        rows = [_mlp_grad(lib, _Buffers().get(R, A, D, "cuda:0", lib), blob, mb.obs, g, squash)
                 for blob, g, squash in ((ro.fused.weights, head.g_pi, True), (ro._value_w, head.g_v, False))]
         head_rows.append(head.stats)
         step_rows.append(adam_step(nets, rows, states, [ro.fused.weights, ro._value_w], hyper, count,

@@ -29,7 +29,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlp_input_grad.json"))
     args = ap.parse_args()
-    import numpy as np
     import torch
     import actor_ref_util as R
     import mlp_grad_util as M
@@ -54,16 +53,7 @@ def main():
         return out
 
     def spread(ga, g32, g64, names):
-        out = {}
-        for k in names:
-            e0, e1 = np.abs(g32[k] - g64[k]), np.abs(ga[k] - g64[k])
-            s = [1.0, 1.0]
-            for i, f in enumerate((np.max, np.mean)):
-                a, b = float(f(e0)), float(f(e1))
-                if a > 0 and b > 0:
-                    s[i] = max(a / b, b / a)
-            out[k] = [round(s[0], 2), round(s[1], 2)]
-        return out
+        return {k: [round(v[0], 2), round(v[1], 2)] for k, v in M.spread(g64, g32, [ga], names).items()}
 
     kernel, sp_gpu, sp_unit, sp_row, raw = {}, {}, {}, {}, {}
     for case in M.CASES:
