@@ -83,6 +83,14 @@ class BsxAdamIo(ctypes.Structure):
                 ("v_ls", c_void_p), ("hyper", c_void_p), ("step", c_void_p)]
 
 
+class BsxAdamTarget(ctypes.Structure):
+    _fields_ = [("p", c_void_p * 10), ("blob", c_void_p)]
+
+
+class BsxAdamTargets(ctypes.Structure):
+    _fields_ = [("net", BsxAdamTarget * 2)]
+
+
 MINIBATCH_FIELDS = ("obs", "rec", "logp", "adv", "ret", "value", "mask")
 
 
@@ -154,6 +162,8 @@ SIGNATURES = {
     "bsx_adam_step_workspace_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_adam_step": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_adam_step_shared": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_adam_step_mlp_workspace_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_adam_step_mlp": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_int, c_int, ctypes.POINTER(BsxAdamTargets), c_void_p, c_void_p, c_void_p]),
     "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
                                      c_void_p]),

@@ -18,6 +18,14 @@
 // group's sum for itself, in both passes -- no workgroup writes another's row, nothing is added to the workspace -- and only a leader's
 // workgroup (the first agent of a group) contributes a partial norm, so a shared parameter counts once.  group = 1 is bsx_adam_step:
 // the sum is the row's own element.  Both kernels are templates on TIED: the untied call's instances hold no loop over members.
+//
+// bsx_adam_step_mlp is the one path behind all three entries: any (A, D) the fused MLP kernels take (A <= 32, odd allowed, D <= 64: a row
+// of up to 8 836 floats, 35 KB of LDS), any group that divides A, and per network an optional Polyak target.  A workgroup whose network
+// has a target goes on after its blob: t = (1 - tau) t + tau p per element against its own LDS image of the new parameters, the blended
+// value back into the image, and the target's blob from the image by the same blob_float -- no second image, no further launch.  tau is
+// hyper[5], read in the apply pass.  The Polyak work is the template parameter POLYAK of the apply body: the instances without it
+// (bsx_adam_apply_kernel, every call in which no network has a target) hold no load or branch for it and take the kernel argument
+// they always took: the targets' pointers ride in the Polyak instances' argument alone.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -32,12 +40,13 @@ namespace {
 
 using namespace bsx_actor;
 
-constexpr int NORM_TPB = 1024;                            // a row is 5 .. 8 floats per thread: the passes are latency, not bandwidth
+constexpr int NORM_TPB = 1024;                            // a row is 5 .. 9 floats per thread: the passes are latency, not bandwidth
 constexpr int APPLY_TPB = 1024;
-constexpr int D_MAX = 3 * BSX_MAX_N + 2;
+constexpr int D_MAX = BSX_MLP_MAX_D;
 constexpr int G_MAX = grad_floats(D_MAX);
 constexpr int SCALARS = 8;                                // workspace doubles ahead of the partials: t | lr | lr / (1 - b1^t) | sqrt(1 - b2^t) | b1 | b2 | eps | max_norm
 constexpr int PART_MAX = 4 * BSX_MAX_N + 1;
+static_assert(G_MAX == 8836 && G_MAX * sizeof(float) + 64 <= 64 * 1024, "the apply pass keeps one row in static LDS");
 
 struct Args {
     BsxAdamIo io;
@@ -45,6 +54,11 @@ struct Args {
     double* ws;
     double* stats;
     int group;                                            // agents per tied group, consecutive; 1 = every agent on its own (last: the untied instances never load it)
+};
+// the argument of the Polyak instances alone: a call without targets passes the 176 bytes of pointers to no kernel
+struct PolyakArgs {
+    Args a;
+    BsxAdamTargets tg;                                    // all NULL for a network without a target
 };
 
 // where element j of a gradient row lives: k = the parameter's index in learner.PARAMS, i = the float inside agent a's slice of it;
@@ -84,6 +98,14 @@ __device__ inline float* param_ptr(const BsxAdamIo& io, int net, int k) {
     float* p = second ? io.net[1].p[0] : io.net[0].p[0];
 #pragma unroll
     for (int q = 1; q < 10; ++q) p = k == q ? (second ? io.net[1].p[q] : io.net[0].p[q]) : p;
+    return p;
+}
+
+// parameter k of one network's target, with constant indices like param_ptr
+__device__ inline float* target_ptr(const BsxAdamTarget& T, int k) {
+    float* p = T.p[0];
+#pragma unroll
+    for (int q = 1; q < 10; ++q) p = k == q ? T.p[q] : p;
     return p;
 }
 
@@ -208,8 +230,29 @@ __device__ inline float adam_element(const Scalars& c, float grad, float& m, flo
     return p - c.step_size * (m / denom);
 }
 
-template <int TIED>
-__global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p) {
+// the Polyak half of a workgroup whose network has target T (T.blob = nullptr: it has none): t = (1 - tau) t + tau p per element
+// against the LDS image s of the new parameters, the blended value back into the image, the target's blob row from the image
+__device__ __forceinline__ void polyak_row(const BsxAdamTarget& T, float tau, float* s, int a, int D, int na) {
+    if (!T.blob) return;                                         // (the whole workgroup: no barrier is left behind)
+    const int tid = threadIdx.x, G = grad_floats(D), BF = blob_floats(D);
+    float* tblob = T.blob + size_t(a) * BF;
+    const float omt = float(1.0 - double(tau));
+    __syncthreads();                                             // the blob pass has read the image
+    for (int j = tid; j < G; j += APPLY_TPB) {                   // thread and j as in the first loop: the pad columns keep their +0
+        Where w;
+        if (locate(j, D, na, w)) {
+            float* q = target_ptr(T, w.k) + size_t(a) * param_row_floats(w.k, D, na) + w.i;
+            const float t = fmaf(omt, *q, tau * s[j]);
+            *q = t;
+            s[j] = t;
+        }
+    }
+    __syncthreads();
+    for (int f = tid; f < BF; f += APPLY_TPB) tblob[f] = blob_float(s, f, D);
+}
+
+template <int TIED, int POLYAK>
+__device__ __forceinline__ void apply_body(const Args& p, const BsxAdamTargets* tg) {
     __shared__ float s_p[G_MAX];
     __shared__ double s_norm2;
     const int tid = threadIdx.x, b = blockIdx.x;
@@ -271,7 +314,17 @@ __global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p)
     const int BF = blob_floats(D);
     float* blob = N.blob + size_t(a) * BF;
     for (int f = tid; f < BF; f += APPLY_TPB) blob[f] = blob_float(s_p, f, D);
+    if constexpr (POLYAK) {                                      // (a branch per network, not a select per pointer: eleven pointers live, not twenty-two)
+        if (net == 1) polyak_row(tg->net[1], p.io.hyper[5], s_p, a, D, na);
+        else polyak_row(tg->net[0], p.io.hyper[5], s_p, a, D, na);
+    }
 }
+
+template <int TIED>
+__global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_kernel(const Args p) { apply_body<TIED, 0>(p, nullptr); }
+
+template <int TIED>
+__global__ __launch_bounds__(APPLY_TPB) void bsx_adam_apply_polyak_kernel(const PolyakArgs p) { apply_body<TIED, 1>(p.a, &p.tg); }
 
 int check_net(const BsxAdamNet& N) {
     for (int k = 0; k < 10; ++k)
@@ -279,6 +332,13 @@ int check_net(const BsxAdamNet& N) {
     if (!N.grad || !N.m || !N.v || !N.blob) return BSX_E_ARG;
     if (N.n_actions != 1 && N.n_actions != 3 && N.n_actions != 4) return BSX_E_ARG;
     return 0;
+}
+
+// 0: no target, 1: a whole one, BSX_E_ARG: some but not all of the eleven pointers
+int check_target(const BsxAdamTarget& T) {
+    int given = T.blob != nullptr;
+    for (int k = 0; k < 10; ++k) given += T.p[k] != nullptr;
+    return given == 0 ? 0 : given == 11 ? 1 : BSX_E_ARG;
 }
 
 int check_net_align(const BsxAdamNet& N) {
@@ -292,33 +352,61 @@ int check_net_align(const BsxAdamNet& N) {
 
 extern "C" {
 
-int bsx_adam_step_workspace_bytes(int n, int nets, size_t* bytes) {
-    if (!bytes || n < 1 || n > BSX_MAX_N || (nets != 1 && nets != 2)) return BSX_E_ARG;
-    *bytes = size_t(8) * size_t(SCALARS + nets * 2 * n + 1);
+int bsx_adam_step_mlp_workspace_bytes(int A, int nets, size_t* bytes) {
+    if (!bytes || A < 1 || A > 2 * BSX_MAX_N || (nets != 1 && nets != 2)) return BSX_E_ARG;
+    *bytes = size_t(8) * size_t(SCALARS + nets * A + 1);
     return 0;
+}
+
+int bsx_adam_step_workspace_bytes(int n, int nets, size_t* bytes) {
+    if (n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
+    return bsx_adam_step_mlp_workspace_bytes(2 * n, nets, bytes);
 }
 
 int bsx_adam_step(const BsxAdamIo* io, int n, void* workspace, double* stats, void* stream) {
     return bsx_adam_step_shared(io, n, 1, workspace, stats, stream);
 }
 
+// the two entries of the actor's shape: their own rules for n and group (BSX_E_ARG, like everything ahead of the alignment rules), then
+// the one path at (2n, 3n + 2) without targets
 int bsx_adam_step_shared(const BsxAdamIo* io, int n, int group, void* workspace, double* stats, void* stream) {
-    if (!io || !workspace || !stats || !io->hyper || !io->step) return BSX_E_ARG;
-    if (n < 1 || n > BSX_MAX_N || (io->nets != 1 && io->nets != 2)) return BSX_E_ARG;
+    if (n < 1 || n > BSX_MAX_N) return BSX_E_ARG;
     if (group != 1 && group != 2 * n && (group < 2 || n % group)) return BSX_E_ARG;
+    return bsx_adam_step_mlp(io, 2 * n, 3 * n + 2, group, nullptr, workspace, stats, stream);
+}
+
+int bsx_adam_step_mlp(const BsxAdamIo* io, int A, int D, int group, const BsxAdamTargets* targets, void* workspace, double* stats,
+                      void* stream) {
+    if (!io || !workspace || !stats || !io->hyper || !io->step) return BSX_E_ARG;
+    if (A < 1 || A > 2 * BSX_MAX_N || D < 1 || D > BSX_MLP_MAX_D || (io->nets != 1 && io->nets != 2)) return BSX_E_ARG;
+    if (group < 1 || A % group) return BSX_E_ARG;
     for (int k = 0; k < io->nets; ++k)
         if (const int rc = check_net(io->net[k])) return rc;
     const int given = (io->log_std != nullptr) + (io->g_log_std != nullptr) + (io->m_ls != nullptr) + (io->v_ls != nullptr);
     if (given != 0 && given != 4) return BSX_E_ARG;
+    bool polyak = false;
+    for (int k = 0; targets && k < io->nets; ++k) {
+        const int rc = check_target(targets->net[k]);
+        if (rc < 0) return rc;
+        polyak |= rc == 1;
+    }
     for (int k = 0; k < io->nets; ++k)
         if (const int rc = check_net_align(io->net[k])) return rc;
     if (!aligned(io->log_std, 4) || !aligned(io->g_log_std, 4) || !aligned(io->m_ls, 4) || !aligned(io->v_ls, 4)) return BSX_E_ALIGN;
     if (!aligned(io->hyper, 4) || !aligned(io->step, 8) || !aligned(workspace, 8) || !aligned(stats, 8)) return BSX_E_ALIGN;
-    Args a;
+    PolyakArgs pa;
+    Args& a = pa.a;
     a.io = *io;
     if (io->nets == 1) a.io.net[1] = io->net[0];                 // never selected; keeps the argument free of unset pointers
-    a.A = 2 * n;
-    a.D = 3 * n + 2;
+    pa.tg = BsxAdamTargets{};
+    for (int k = 0; polyak && k < io->nets; ++k) {
+        for (int q = 0; q < 10; ++q)
+            if (!aligned(targets->net[k].p[q], 4)) return BSX_E_ALIGN;
+        if (!aligned(targets->net[k].blob, 16)) return BSX_E_ALIGN;
+        pa.tg.net[k] = targets->net[k];
+    }
+    a.A = A;
+    a.D = D;
     a.rows = io->nets * a.A;
     a.parts = a.rows + (given ? 1 : 0);
     a.group = group;
@@ -329,7 +417,8 @@ int bsx_adam_step_shared(const BsxAdamIo* io, int n, int group, void* workspace,
     const bool tied = group > 1;
     hipLaunchKernelGGL(tied ? bsx_adam_norm_kernel<1> : bsx_adam_norm_kernel<0>, dim3(unsigned(a.parts)), dim3(NORM_TPB), 0, s, a);
     if (const hipError_t e = hipGetLastError()) return int(e);
-    hipLaunchKernelGGL(tied ? bsx_adam_apply_kernel<1> : bsx_adam_apply_kernel<0>, dim3(unsigned(a.parts)), dim3(APPLY_TPB), 0, s, a);
+    if (polyak) hipLaunchKernelGGL(tied ? bsx_adam_apply_polyak_kernel<1> : bsx_adam_apply_polyak_kernel<0>, dim3(unsigned(a.parts)), dim3(APPLY_TPB), 0, s, pa);
+    else hipLaunchKernelGGL(tied ? bsx_adam_apply_kernel<1> : bsx_adam_apply_kernel<0>, dim3(unsigned(a.parts)), dim3(APPLY_TPB), 0, s, a);
     return int(hipGetLastError());
 }
 

@@ -22,6 +22,9 @@ mlp_grad without the input gradient, and a network holds one set of cached buffe
   share_group(share, n), tie_(x, group), is_tied(x, group)      agents that share parameters: consecutive groups of `group` agents hold
                                                                 identical networks; adam_step(..., group=g) steps a group with the sum of
                                                                 its members' gradient rows (bsx_adam_step_shared)
+  mlp_adam_step(nets, grads, states, blobs, hyper, step, ...)   the same step for any network fused_mlp takes (a Q critic, an odd A), with
+                                                                Polyak target networks and their packed blobs kept in the same pass:
+                                                                t = (1 - tau) t + tau p, tau = hyper[5] (bsx_adam_step_mlp)
   shuffle_rows(N, first, R, seed, seq, ...)                     a keyed permutation of [0, N) evaluated per position (bsx_shuffle_rows)
   minibatch_gather(src, dst, first, R, seed, seq, ...)          one shuffled minibatch's records through it, one launch (bsx_minibatch_gather)
   PPOLearner(rollout, ...)                                      minibatch_grads / update: the PPO update of a PolicyRollout's networks;
@@ -51,6 +54,12 @@ PARAMS = tuple(name for name, *_ in _TABLE)
 def grad_floats(obs_len):
     """G of bsx_actor_grad: w1[D][64] | b1 | g1 | h1 | w2[64][64] | b2 | g2 | h2 | w3[64][4] | b3[4]."""
     return sum(rows(obs_len) * cols for _, rows, cols, _ in _TABLE)
+
+
+def _mlp_blob_floats(obs_len):
+    """Floats per agent of StackedActor.pack()'s blob at any input width of the fused MLP kernels: W1A over obs_len rounded up to even,
+    then W2A, the six vectors, W3P, b3 and W2B's three bfloat16 terms (blob_floats asks the library, which answers for an actor's widths)."""
+    return H * ((obs_len + 1) & ~1) + grad_floats(0) + H * H * 3 // 2
 
 
 def split_grad(row, n_actions):
@@ -168,7 +177,7 @@ def mlp_grad(net, blob, x, grad_out, squash=True, input_grad=True):
     need = partial(_need, dev=dev, anchor="x")
     need(x, "x", (R, A, D), _F32)
     need(grad_out, "grad_out", (R, A, na), _F32)
-    need(blob, "blob", (A, H * ((D + 1) & ~1) + grad_floats(0) + H * H * 3 // 2), _F32)
+    need(blob, "blob", (A, _mlp_blob_floats(D)), _F32)
     lib = _lib.load()
     buf = _buffers(net).get(R, A, D, dev, lib, go=True, gx=input_grad)
     buf["go"][..., :na].copy_(grad_out)                          # padded to 4 columns: the others hold 0 from the allocation on
@@ -268,8 +277,9 @@ _SHARE = (lambda x: 0.0 < x < 1.0, "a number in (0, 1)")
 _WEIGHT = (lambda x: x >= 0.0, "a number >= 0")
 _POSITIVE = (lambda x: x > 0.0, "a number > 0")
 _BETA = (lambda x: 0.0 <= x < 1.0, "a number in [0, 1)")
+_UNIT = (lambda x: 0.0 <= x <= 1.0, "a number in [0, 1]")
 _HYPER = {"clip": _SHARE, "c_v": _WEIGHT, "c_e": _WEIGHT, "temperature": _POSITIVE, "vclip": _POSITIVE, "lr": _WEIGHT, "betas[0]": _BETA,
-          "betas[1]": _BETA, "eps": _WEIGHT, "max_grad_norm": _WEIGHT}       # (max_grad_norm 0: adam_hyper's spelling of "no clipping")
+          "betas[1]": _BETA, "eps": _WEIGHT, "max_grad_norm": _WEIGHT, "tau": _UNIT}       # (max_grad_norm 0: adam_hyper's spelling of "no clipping")
 
 
 def _hyper(name, x, rng=None):
@@ -354,7 +364,7 @@ def ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, *, clip, c_v, c_e, tempe
 
 
 # ------------------------------------------------------------------------------------------------ the optimiser step
-HYPER = ("lr", "beta1", "beta2", "eps", "max_grad_norm", "reserved", "reserved", "reserved")
+HYPER = ("lr", "beta1", "beta2", "eps", "max_grad_norm", "tau", "reserved", "reserved")
 ADAM_STATS = ("step", "grad_norm", "clip_coef", "lr")
 
 
@@ -373,8 +383,9 @@ class AdamState:
         self.v = torch.zeros(shape, dtype=torch.float32, device=dev)
 
 
-def adam_hyper(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, device="cuda"):
-    """adam_step's `hyper`: float32 [8] on the device in the order of learner.HYPER; max_grad_norm None (or 0) = no clipping."""
+def adam_hyper(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, device="cuda", tau=0.0):
+    """adam_step's `hyper`: float32 [8] on the device in the order of learner.HYPER; max_grad_norm None (or 0) = no clipping.  tau in
+    [0, 1]: the Polyak rate of mlp_adam_step's targets (adam_step does not read it)."""
     lr = _hyper("lr", lr)
     try:
         b1, b2 = betas
@@ -384,7 +395,8 @@ def adam_hyper(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, device
     b2 = _hyper("betas[1]", b2)
     eps = _hyper("eps", eps)
     mgn = 0.0 if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm)
-    return torch.tensor([lr, b1, b2, eps, mgn, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
+    tau = _hyper("tau", tau)
+    return torch.tensor([lr, b1, b2, eps, mgn, tau, 0.0, 0.0], dtype=torch.float32, device=device)
 
 
 def share_group(share, n):
@@ -482,6 +494,39 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     gradient of a group is the float32 sum of its members' rows in agent order (and of their g_log_std rows), it counts once in the
     global norm, and every member's parameters, moments and blob row are stepped with it from that member's own values -- members
     that are identical before the call (tie_) are identical after it.  group = 1 is the untied step, bit for bit."""
+    return _adam_step("adam_step", False, nets, grads, states, blobs, hyper, step, log_std, g_log_std, log_std_state, stats, workspace, group)
+
+
+def mlp_adam_step_workspace_bytes(A, nets):
+    """Bytes of the workspace mlp_adam_step needs for `nets` networks of A agents (adam_step_workspace_bytes(n, nets) at A = 2n)."""
+    lib, nb = _lib.load(), _lib.c_size_t()
+    _lib.check(lib.bsx_adam_step_mlp_workspace_bytes(int(A), int(nets), _lib.ctypes.byref(nb)), "bsx_adam_step_mlp_workspace_bytes")
+    return nb.value
+
+
+def mlp_adam_step(nets, grads, states, blobs, hyper, step, *, targets=None, target_blobs=None, log_std=None, g_log_std=None,
+                  log_std_state=None, stats=None, workspace=None, group=1):
+    """adam_step for any StackedActor fused_mlp takes -- 1 .. 32 agents, odd counts allowed, 1 .. 64 inputs: a Q critic on obs (+) action
+    -- with, per network, a Polyak target kept in the same two launches (`bsx_adam_step_mlp`, include/battlespace_hip.h) -> stats f64 [4].
+
+    nets, grads, states, blobs, hyper, step, log_std, g_log_std, log_std_state, stats, workspace: adam_step's, word for word, with the
+    workspace of mlp_adam_step_workspace_bytes(A, len(nets)).  At an actor's shape and without targets the call leaves adam_step's bits.
+    targets: a list with, per network, a StackedActor of the same (A, D, n_actions) or None; target_blobs: a list with, per network, a
+    float32 tensor of the shape of blobs[i] ([A, blob floats]: net.pack()'s) or None, matching targets.  After a network's step, per element in float32,
+        t = (1 - tau) t + tau p,        tau = hyper[5] (adam_hyper(tau=)), read on the device at every launch,
+    and target_blobs[i] receives, in every float, what targets[i].pack() makes of the blended target: what the next target forward
+    (bsx_mlp_forward) reads.  The .grad of the targets is neither read nor written.
+    group: any divisor of A, 1 = every agent on its own; the tied step of adam_step(group=) for consecutive blocks of `group` agents.
+    Each member's target is blended with that member's own new parameters: targets tied before the call (tie_) are tied after it."""
+    return _adam_step("mlp_adam_step", True, nets, grads, states, blobs, hyper, step, log_std, g_log_std, log_std_state, stats, workspace,
+                      group, targets, target_blobs)
+
+
+def _adam_step(what, free, nets, grads, states, blobs, hyper, step, log_std, g_log_std, log_std_state, stats, workspace, group,
+               targets=None, target_blobs=None):
+    """The one body of adam_step (free=False: an actor's shape, A = 2n and D = 3n + 2, share_group's groups, no targets) and mlp_adam_step
+    (free=True: any shape of the fused MLP kernels, any group that divides A, Polyak targets): the checks in the order they fire, the
+    argument structs, the call."""
     for name, x in (("nets", nets), ("grads", grads), ("states", states), ("blobs", blobs)):
         if not isinstance(x, (list, tuple)):
             raise TypeError(f"{name} must be a list or tuple, one entry per network")
@@ -491,17 +536,27 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     if not all(hasattr(first, k) for k in PARAMS) or not isinstance(first.w1, torch.Tensor):
         raise TypeError("nets[0] must be a StackedActor")
     dev, A, D = first.w1.device, first.n_actors, first.obs_len
+    with_targets = free and (targets is not None or target_blobs is not None)
+    if with_targets:
+        _check_targets(nets, targets, target_blobs)
     if dev.type != "cuda":
-        raise ValueError("adam_step runs on the GPU: nets[0].w1 is on " + str(dev))
-    if A < 2 or A % 2 or A > 2 * _lib.MAX_N or D != 3 * (A // 2) + 2:
+        raise ValueError(what + " runs on the GPU: nets[0].w1 is on " + str(dev))
+    if free:
+        if not 1 <= A <= 2 * _lib.MAX_N or not 1 <= D <= _lib.MLP_MAX_D:
+            raise ValueError(f"nets[0] has {A} agents and obs_len {D}: 1 .. {2 * _lib.MAX_N} agents and 1 .. {_lib.MLP_MAX_D} inputs are needed")
+    elif A < 2 or A % 2 or A > 2 * _lib.MAX_N or D != 3 * (A // 2) + 2:
         raise ValueError(f"nets[0] has {A} agents and obs_len {D}: an even A in 2 .. {2 * _lib.MAX_N} and D = 3 A / 2 + 2 are needed")
     G = grad_floats(D)
     if isinstance(group, bool) or not isinstance(group, int):
         raise ValueError(f"group must be an int (learner.share_group), got {group!r}")
-    group = share_group(group, A // 2)
+    if not free:
+        group = share_group(group, A // 2)
+    elif group < 1 or A % group:
+        raise ValueError(f"a group of {group} does not divide {A} agents")
     need = partial(_need, dev=dev, anchor="y")                   # ("y": the wording these messages have always had)
     io = _lib.BsxAdamIo()
     io.nets = len(nets)
+    tg = _lib.BsxAdamTargets()
     for i, (net, g, st, blob) in enumerate(zip(nets, grads, states, blobs)):
         if not all(hasattr(net, k) for k in PARAMS):
             raise TypeError(f"nets[{i}] must be a StackedActor")
@@ -518,8 +573,14 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
         need(g, f"grads[{i}]", (A, G), _F32)
         need(st.m, f"states[{i}].m", (A, G), _F32)
         need(st.v, f"states[{i}].v", (A, G), _F32)
-        need(blob, f"blobs[{i}]", (A, blob_floats(D)), _F32)
+        need(blob, f"blobs[{i}]", (A, _mlp_blob_floats(D)), _F32)
         io.net[i].grad, io.net[i].m, io.net[i].v, io.net[i].blob, io.net[i].n_actions = g.data_ptr(), st.m.data_ptr(), st.v.data_ptr(), blob.data_ptr(), na
+        if with_targets and targets[i] is not None:
+            for q, (k, rows, cols, cut) in enumerate(_TABLE):
+                need(getattr(targets[i], k), f"targets[{i}].{k}", (A, rows(D), na if cut else cols), _F32)
+                tg.net[i].p[q] = getattr(targets[i], k).data_ptr()
+            need(target_blobs[i], f"target_blobs[{i}]", (A, _mlp_blob_floats(D)), _F32)
+            tg.net[i].blob = target_blobs[i].data_ptr()
     given = [x is not None for x in (log_std, g_log_std, log_std_state)]
     if any(given) and not all(given):
         raise ValueError("log_std, g_log_std and log_std_state go together: all three or none")
@@ -538,15 +599,47 @@ def adam_step(nets, grads, states, blobs, hyper, step, *, log_std=None, g_log_st
     if stats is None:
         stats = torch.empty(4, dtype=torch.float64, device=dev)
     need(stats, "stats", (4,), (torch.float64,))
-    workspace = _workspace(workspace, adam_step_workspace_bytes(A // 2, len(nets)), dev)
+    workspace = _workspace(workspace, mlp_adam_step_workspace_bytes(A, len(nets)), dev)
     io.hyper, io.step = hyper.data_ptr(), step.data_ptr()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    if group > 1:
-        _lib.check(_lib.load().bsx_adam_step_shared(_lib.ctypes.byref(io), A // 2, group, workspace.data_ptr(), stats.data_ptr(), stream),
-                   "bsx_adam_step_shared")
+    lib, ref = _lib.load(), _lib.ctypes.byref
+    if free:
+        _lib.check(lib.bsx_adam_step_mlp(ref(io), A, D, group, ref(tg) if with_targets else None, workspace.data_ptr(), stats.data_ptr(),
+                                         stream), "bsx_adam_step_mlp")
+    elif group > 1:
+        _lib.check(lib.bsx_adam_step_shared(ref(io), A // 2, group, workspace.data_ptr(), stats.data_ptr(), stream), "bsx_adam_step_shared")
     else:
-        _lib.check(_lib.load().bsx_adam_step(_lib.ctypes.byref(io), A // 2, workspace.data_ptr(), stats.data_ptr(), stream), "bsx_adam_step")
+        _lib.check(lib.bsx_adam_step(ref(io), A // 2, workspace.data_ptr(), stats.data_ptr(), stream), "bsx_adam_step")
     return stats
+
+
+def _check_targets(nets, targets, target_blobs):
+    """What mlp_adam_step asks of targets / target_blobs before any device is looked at: two lists of one entry per network, None in
+    both or in neither, a StackedActor of its network's (A, D, n_actions), a tensor of the blob's shape."""
+    if targets is None or target_blobs is None:
+        raise ValueError("targets and target_blobs go together: both or neither")
+    for name, x in (("targets", targets), ("target_blobs", target_blobs)):
+        if not isinstance(x, (list, tuple)):
+            raise TypeError(f"{name} must be a list or tuple, one entry (or None) per network")
+        if len(x) != len(nets):
+            raise ValueError(f"{name} must have one entry (or None) per network: {len(nets)}, got {len(x)}")
+    for i, (net, t, tb) in enumerate(zip(nets, targets, target_blobs)):
+        if (t is None) != (tb is None):
+            raise ValueError(f"targets[{i}] and target_blobs[{i}] go together: both or None")
+        if t is None:
+            continue
+        if not all(hasattr(t, k) for k in PARAMS):
+            raise TypeError(f"targets[{i}] must be a StackedActor or None")
+        if t is net:
+            raise ValueError(f"targets[{i}] is nets[{i}] itself: a target is a network of its own")
+        want = tuple(getattr(net, k, None) for k in ("n_actors", "obs_len", "n_actions"))
+        have = (t.n_actors, t.obs_len, t.n_actions)
+        if have != want:
+            raise ValueError(f"targets[{i}] must have the (agents, obs_len, n_actions) = {want} of nets[{i}], got {have}")
+        if not isinstance(tb, torch.Tensor):
+            raise TypeError(f"target_blobs[{i}] must be a torch.Tensor")
+        if tuple(tb.shape) != (t.n_actors, _mlp_blob_floats(t.obs_len)):
+            raise ValueError(f"target_blobs[{i}] must have shape {(t.n_actors, _mlp_blob_floats(t.obs_len))}, got {tuple(tb.shape)}")
 
 
 # ------------------------------------------------------------------------------------------------ shuffled minibatches

@@ -574,7 +574,8 @@ int bsx_ppo_head(const BsxPpoIo* io, int64_t R, int A, int kind, float temperatu
  *   n_actions  1, 3 or 4
  * and once per call:
  *   log_std, g_log_std (read only), m_ls, v_ls   float32 [A][3] each, or all four NULL
- *   hyper      float32 [8] on the device: lr, beta1, beta2, eps, max_grad_norm (0 = no clipping), three reserved floats
+ *   hyper      float32 [8] on the device: lr, beta1, beta2, eps, max_grad_norm (0 = no clipping), tau (hyper[5]: the Polyak rate of
+ *              bsx_adam_step_mlp's targets; bsx_adam_step and bsx_adam_step_shared ignore it), two reserved floats
  *   step       int64 on the device: the number of steps taken so far; the call stores step + 1
  * hyper and step are READ ON THE DEVICE at every launch (as log_std is by the rollout): a captured graph follows a learning-rate schedule
  * and its step count advances from replay to replay. */
@@ -646,6 +647,54 @@ int bsx_adam_step(const BsxAdamIo* io, int n, void* workspace, double* stats, vo
  * other than 1 or 2; a group that is none of the above (0, negative, not a divisor of n and not 2n, above 2n); then the per-network and
  * log_std rules and the BSX_E_ALIGN rules of bsx_adam_step, as there. */
 int bsx_adam_step_shared(const BsxAdamIo* io, int n, int group, void* workspace, double* stats, void* stream);
+
+/* The free-width step with Polyak targets (learner.py: mlp_adam_step): bsx_adam_step_shared for any network bsx_mlp_forward / bsx_mlp_grad
+ * take -- a Q critic on obs (+) action, an odd number of agents -- and, per network, a target network kept in the same pass, as a
+ * DDPG / TD3 / MADDPG update ends.  bsx_adam_step(io, n, ..) is this call at (A, D) = (2n, 3n + 2) with group 1 and no targets, and
+ * bsx_adam_step_shared(io, n, group, ..) the same with its group: same launches, same workspace, same bits.
+ *   A          1 .. 2 * BSX_MAX_N agents, odd counts allowed;  D  1 .. BSX_MLP_MAX_D inputs: one (A, D) for every network of the call.
+ *              BsxAdamIo as above with G = 64 D + 4 740 floats (bsx_actor_grad_floats beyond its D <= 50: at most 8 836, D = 64) and blob
+ *              rows of F = 64 (D + D % 2) + 10 884 floats (bsx_actor_blob_floats likewise: the blob bsx_mlp_forward reads)
+ *   group      any divisor of A, 1 = every agent on its own; consecutive blocks of `group` agents are tied with bsx_adam_step_shared's
+ *              semantics, word for word: gsum in agent order from the leader, leaders alone contribute a partial norm (a follower's is
+ *              +0.0), every member is stepped from gsum and its own old values
+ *   targets    NULL = none.  Per network a BsxAdamTarget: the ten parameters of the target network in p[] (StackedActor's shapes, as
+ *              BsxAdamNet.p: n_actions columns, no pad columns; updated in place) and its packed blob [A][F] (out);
+ *              all eleven pointers set, or all eleven NULL = this network has no target.  targets->net[1] is not read with one network.
+ *   tau        hyper[5], float32, READ ON THE DEVICE at every launch like lr: a captured graph follows a changed tau.  1 - tau is formed
+ *              once per call in float64 from the float32 tau and rounded to float32, the way 1 - beta1 is.
+ * Polyak: after agent a's new parameters p are known, the same workgroup updates agent a's target parameters, per element in float32
+ * (contraction to a fused multiply-add allowed)
+ *   t = (1 - tau) t + tau p
+ * and then writes EVERY float of agent a's target blob row from the updated target: bit for bit what pack() makes of the target network --
+ * W1A's zero pad row at odd D, the zero pad columns of W3P / b3, W2B's three bfloat16 terms.  tau = 1 leaves t = p and a target blob row
+ * equal to the network's; tau = 0 keeps every target element (a -0.0 may become +0.0: it is added to a zero) and still writes the blob.
+ * Tied agents: each member's target is blended with that member's own new parameters, so targets that are tied before are tied after.
+ * A network without a target and log_std are stepped exactly as without `targets`; the kernels of a call in which no network has a
+ * target hold no Polyak loads or branches.  The target does not enter the norm, the moments or stats.
+ * Everything else is bsx_adam_step's: norm, coef, the bias corrections, the element rule, stats[4], hyper and step read on the device, two
+ * launches (partial norms; apply + pack (+ blend + pack)), one workgroup per (network, agent) row and one for log_std, at most 65
+ * partials, no atomics, flags or spins, a grid that is a function of (A, nets, log_std given) alone, no host synchronisation.
+ * workspace: 8-byte aligned, at least bsx_adam_step_mlp_workspace_bytes(A, nets) = 8 (8 + nets A + 1) bytes -- eight float64 scalars and
+ * one float64 partial per row and for log_std: bsx_adam_step_workspace_bytes(n, nets) at A = 2n --, not in use by another call in flight.
+ * Refusals, before any launch, in this order: BSX_E_ARG for a null io, workspace, stats, hyper or step; A out of 1 .. 2 * BSX_MAX_N; D out
+ * of 1 .. BSX_MLP_MAX_D; nets other than 1 or 2; a group < 1 or that does not divide A; per network a null parameter, grad, m, v or blob
+ * or an n_actions other than 1, 3, 4; some but not all of log_std, g_log_std, m_ls, v_ls null; a BsxAdamTarget of a network in use with
+ * some but not all of its eleven pointers set.  Then BSX_E_ALIGN, bsx_adam_step's rules and after them: a target parameter off a 4-byte
+ * boundary, a target blob off a 16-byte one. */
+typedef struct BsxAdamTarget {
+    float* p[10];
+    float* blob;
+} BsxAdamTarget;
+
+typedef struct BsxAdamTargets {
+    BsxAdamTarget net[2];
+} BsxAdamTargets;
+
+/* BSX_E_ARG: null bytes, A out of 1 .. 2 * BSX_MAX_N, nets other than 1 or 2. */
+int bsx_adam_step_mlp_workspace_bytes(int A, int nets, size_t* bytes);
+int bsx_adam_step_mlp(const BsxAdamIo* io, int A, int D, int group, const BsxAdamTargets* targets, void* workspace, double* stats,
+                      void* stream);
 
 /* ---- shuffled minibatches (deep-rl-battlespace_amd/learner.py: shuffle_rows, minibatch_gather, PPOLearner(shuffle=True);
  * csrc/bsx_shuffle.hip): a keyed permutation of the N = T x E rows of a rollout, evaluated per position -- O(1), no sort, no workspace,
