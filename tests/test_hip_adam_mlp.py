@@ -12,77 +12,36 @@ of the target's blob), poisoned pad columns, the agent with a zero gradient, tie
 Measured on an MI355X (profiles/adam_step_mlp.json holds every figure): over the 18 (shape, leg) cases the largest mean ratio of the
 kernel's error to torch's is 1.05 (parameters), 1.14 (m), 1.05 (v) and 0.90 (targets), the largest maximum ratio 1.21, 1.36, 1.02 and
 1.00 -- inside the bars of 2 and 4 everywhere."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import adam_case_util as C
 import adam_mlp_util as MU
 import adam_util as U
 import guard_util as GU
 
 pytestmark = pytest.mark.gpu
 
-STEPS = 5
+BARS = dict(env="BSX_ADAM_MLP_RATIOS_OUT", key="shape")        # =<file>: the five-step ratios as JSON lines for tools/measure_adam_mlp.py
+
+
+def _new(A, D, nas, hp, seed=0, **kw):
+    return C.Case(A, D, nas, hp, seed=300 + seed, **kw)
 
 
 def _case(shape, hp, **kw):
     A, D, na, wide = MU.SHAPES[shape]
-    return MU.Case(A, D, (na, 1) if wide else (na,), hp, with_ls=wide, **kw)
+    return _new(A, D, (na, 1) if wide else (na,), hp, with_ls=wide, **kw)
 
 
 def _first_norm(shape, seed):
     """The float64 norm of the first gradients Case.draw gives from a generator seeded with `seed`."""
     A, D, na, wide = MU.SHAPES[shape]
-    gen = torch.Generator().manual_seed(seed)
-    gs = [U.random_rows(A, D, k, gen) for k in ((na, 1) if wide else (na,))] + ([torch.randn((A, 3), generator=gen)] if wide else [])
-    return float(np.sqrt(sum(float((g.double() ** 2).sum()) for g in gs)))
+    return C.first_norm(A, D, (na, 1) if wide else (na,), wide, seed)
 
 
-def _record(shape, leg, ratios):
-    """BSX_ADAM_MLP_RATIOS_OUT=<file>: append the measured ratios as one JSON line (tools/measure_adam_mlp.py folds them into
-    profiles/adam_step_mlp.json)."""
-    print(f"mlp_adam_step {shape} {leg}: " + ", ".join(f"{k} {m:.3f}/{x:.3f}" for k, (m, x) in sorted(ratios.items())))
-    path = os.environ.get("BSX_ADAM_MLP_RATIOS_OUT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(dict(shape=shape, leg=leg, ratios={k: [round(m, 4), round(x, 4)] for k, (m, x) in ratios.items()})) + "\n")
-
-
-def _meets_the_bars(case, yard, ref, shape, leg):
-    """Per network and for each of parameters, m, v and targets, pooled over the ten tensors (log_std with network 0's p, m, v): mean
-    |error| against the float64 restatement at most 2x that of torch's own float32 path on the same inputs, maximum at most 4x."""
-    ratios, failed = {}, []
-    for i, (mine, torchs, want) in enumerate(zip(case.groups(), yard.groups(), ref)):
-        for j, what in enumerate(("p", "m", "v", "target")):
-            keep = [k for k, x in enumerate(want[j]) if x is not None]
-            if not keep:
-                continue
-            pick = lambda xs: [xs[k] for k in keep]     # noqa: E731
-            (em, ex), (tm, tx) = U.pooled_errors(pick(mine[j]), pick(want[j])), U.pooled_errors(pick(torchs[j]), pick(want[j]))
-            assert tm > 0.0 and tx > 0.0
-            ratios[f"net{i}.{what}"] = (em / tm, ex / tx)
-            if em > 2.0 * tm or ex > 4.0 * tx:
-                failed.append((i, what, em, tm, ex, tx))
-    _record(shape, leg, ratios)
-    assert not failed, failed
-
-
-def _check_stats(case, stats, t, norm, coef, hp):
-    got = stats.cpu().numpy()
-    assert got[0] == t and int(case.step) == t, (got, int(case.step), t)
-    assert abs(got[1] - norm) <= 1e-10 * norm and abs(got[2] - coef) <= 1e-10 * coef and got[3] == hp["lr"], (got, norm, coef)
-
-
-#       leg                lr     counter set to (before step index)   what it shows
-LEGS = {"lr3e-4-from-0": (3e-4, {}),                                 # the usual start: bias corrections far from 1
-        "counter-1000-after-3": (3e-4, {3: 1000}),                   # ... and then near 1: b^t through a large t
-        "lr0.05-counter-1000": (0.05, {0: 1000})}                    # a parameter-sized step: the step's own arithmetic shows
-
-
-@pytest.mark.parametrize("leg", list(LEGS))
+@pytest.mark.parametrize("leg", list(C.LEGS))
 @pytest.mark.parametrize("shape", list(MU.SHAPES))
 def test_five_steps_match_the_float64_restatement_as_well_as_torch_does_targets_included(shape, leg):
     """Five steps with fresh gradients each (steps 2 and 4 a tenth of the others: max_grad_norm, half the first step's norm, bites on 1,
@@ -91,28 +50,28 @@ def test_five_steps_match_the_float64_restatement_as_well_as_torch_does_targets_
     sum of exact squares is off by at most (N - 1) 2^-53, N <= 5.7e5 here) and the float32 lr.  After the five steps, per network and for
     each of parameters, m, v and targets, pooled over the ten tensors: mean |error| against the float64 restatement at most 2x that of
     torch's own float32 clip_grad_norm_ + Adam + target.mul_(1 - tau).add_(p, alpha=tau) on the same inputs, maximum at most 4x."""
-    lr, counter = LEGS[leg]
+    lr, counter = C.LEGS[leg]
     hp = U.hyper32(lr=lr, max_grad_norm=0.5 * _first_norm(shape, 17))
     case = _case(shape, hp)
-    yard = MU.TorchPath(case, hp, MU.TAU)
-    ref = MU.start(case)
+    yard = C.TorchPath(case, hp, MU.TAU)
+    ref = C.start(case)
     t, coefs = 0, []
     gen = torch.Generator().manual_seed(17)
-    for s in range(STEPS):
+    for s in range(C.STEPS):
         if s in counter:
             t = counter[s]
             case.step.fill_(t)
             yard.set_counter(t)
         rows, g_ls = case.draw(gen, 0.1 if s in (1, 3) else 1.0)
-        grads = MU.flat_split(case, rows, g_ls)
+        grads = C.flat_split(case, rows, g_ls)
         stats = case.run(rows, g_ls)
         yard.step(grads)
-        t, norm, coef = MU.advance(ref, grads, t, hp, MU.TAU)
+        t, norm, coef = C.advance(ref, grads, t, hp, MU.TAU)
         coefs.append(coef)
-        MU.blobs_are_packs(case, (shape, leg, s))
-        _check_stats(case, stats, t, norm, coef, hp)
+        C.blobs_are_packs(case, (shape, leg, s))
+        C.check_stats(case, stats, t, norm, coef, hp)
     assert [c < 1.0 for c in coefs] == [True, False, True, False, True], coefs
-    _meets_the_bars(case, yard, ref, shape, leg)
+    C.meets_the_bars(case, yard, ref, shape, leg, **BARS)
 
 
 @pytest.mark.parametrize("tied", [False, True], ids=["group1", "group2n"])
@@ -123,11 +82,11 @@ def test_at_an_actors_shape_and_without_targets_the_call_leaves_the_older_entrie
     from deep_rl_battlespace_amd import learner
     A, D, group = 2 * n, 3 * n + 2, 2 * n if tied else 1
     hp = U.hyper32(lr=0.01, max_grad_norm=1.0)
-    old, new = (MU.Case(A, D, (4, 1), hp, with_ls=True, targets=(False, False), seed=5, group=group) for _ in range(2))
+    old, new = (_new(A, D, (4, 1), hp, with_ls=True, targets=(False, False), seed=5, group=group) for _ in range(2))
     if tied:
         old.tie()
         new.load(old)
-    assert MU.same_bits(old.bits(), new.bits()) == []
+    assert C.same_bits(old.bits(), new.bits()) == []
     gen = torch.Generator().manual_seed(61)
     for s in range(2):
         rows, g_ls = old.draw(gen)
@@ -135,11 +94,11 @@ def test_at_an_actors_shape_and_without_targets_the_call_leaves_the_older_entrie
                           log_std_state=old.ls_state, stats=old.stats, workspace=old.ws, group=group)
         new.run([r.clone() for r in rows], g_ls.clone())
         a, b = old.bits(), new.bits()
-        assert sorted(a) == sorted(b) and MU.same_bits(a, b) == [], (s, MU.same_bits(a, b))
+        assert sorted(a) == sorted(b) and C.same_bits(a, b) == [], (s, C.same_bits(a, b))
         assert int(new.step) == s + 1 and float(new.stats[2]) < 1.0
         if tied:
             assert all(learner.is_tied(x, group) for x in new.nets + new.states + [new.log_std, new.ls_state])
-    MU.blobs_are_packs(new, (n, tied))
+    C.blobs_are_packs(new, (n, tied))
 
 
 @pytest.mark.parametrize("shape", ["a3-d9", "a5-d51-na3", "a2-d64-na4", "a32-d64-two-nets-log-std"])
@@ -153,10 +112,10 @@ def test_two_calls_from_copies_of_one_state_give_identical_bits_and_leave_the_gu
         a.run(rows, g_ls)
         b.run([r.clone() for r in rows], g_ls.clone() if g_ls is not None else None)
     x, y = a.bits(), b.bits()
-    assert sorted(x) == sorted(y) and MU.same_bits(x, y) == []
+    assert sorted(x) == sorted(y) and C.same_bits(x, y) == []
     assert any(k.startswith("target") for k in x) and int(a.step) == 2 and float(a.stats[2]) < 1.0
     assert alloc.stray() == []
-    MU.blobs_are_packs(a, shape)
+    C.blobs_are_packs(a, shape)
 
 
 @pytest.mark.parametrize("shape", ["a3-d9", "a5-d51-na3"])
@@ -177,9 +136,10 @@ def test_tau_one_makes_the_target_the_network_and_tau_zero_keeps_it_and_still_wr
         assert torch.equal(y[f"target0.{k}"], before[f"target0.{k}"]) and not torch.equal(y[f"net0.{k}"], before[f"net0.{k}"]), k
     assert torch.equal(x["target0.blob"], x["net0.blob"])
     assert not torch.equal(y["target0.blob"], before["target0.blob"])
-    assert MU.same_bits({k: v for k, v in x.items() if k.startswith(("net", "st"))}, y) == []
-    MU.blobs_are_packs(one, (shape, "tau 1"))
-    MU.blobs_are_packs(zero, (shape, "tau 0"))
+    own = lambda bits: {k: v for k, v in bits.items() if k.startswith(("net", "st"))}     # noqa: E731
+    assert C.same_bits(own(x), own(y)) == []
+    C.blobs_are_packs(one, (shape, "tau 1"))
+    C.blobs_are_packs(zero, (shape, "tau 0"))
 
 
 def test_a_tau_changed_in_hyper_between_two_replays_of_a_captured_call_is_followed():
@@ -206,19 +166,19 @@ def test_a_tau_changed_in_hyper_between_two_replays_of_a_captured_call_is_follow
         eager.hyper[5] = tau
         graph.replay()
         eager.run(kept, g_ls)
-        assert MU.same_bits(cap.bits(), eager.bits()) == [], tau
+        assert C.same_bits(cap.bits(), eager.bits()) == [], tau
     x = cap.bits()
     assert int(cap.step) == 2 and all(torch.equal(x[f"target0.{k}"], x[f"net0.{k}"]) for k in U.PARAMS)
     assert torch.equal(x["target0.blob"], x["net0.blob"])
-    MU.blobs_are_packs(cap, "captured")
+    C.blobs_are_packs(cap, "captured")
 
 
 def test_a_network_without_a_target_beside_one_with_is_stepped_as_in_the_call_without_targets():
     """targets = [None, a target]: everything of the first network, of log_std and stats hold the bits of the same call without any
     target (so do the second network's own outputs), and the second network's target and its blob are kept up."""
     hp = U.hyper32(lr=0.01, max_grad_norm=1.0)
-    mixed = MU.Case(4, 24, (3, 1), hp, with_ls=True, targets=(False, True), seed=9)
-    plain = MU.Case(4, 24, (3, 1), hp, with_ls=True, targets=(False, False), seed=9)
+    mixed = _new(4, 24, (3, 1), hp, with_ls=True, targets=(False, True), seed=9)
+    plain = _new(4, 24, (3, 1), hp, with_ls=True, targets=(False, False), seed=9)
     plain.load(mixed)
     gen = torch.Generator().manual_seed(73)
     before = mixed.bits()
@@ -228,9 +188,9 @@ def test_a_network_without_a_target_beside_one_with_is_stepped_as_in_the_call_wi
         plain.run([r.clone() for r in rows], g_ls.clone())
     x, y = mixed.bits(), plain.bits()
     assert sorted(k for k in x if k not in y) == sorted([f"target1.{k}" for k in U.PARAMS] + ["target1.blob"])
-    assert MU.same_bits(y, x) == [] and float(mixed.stats[2]) < 1.0
+    assert C.same_bits(y, x, common=True) == [] and float(mixed.stats[2]) < 1.0
     assert all(not torch.equal(x[f"target1.{k}"], before[f"target1.{k}"]) for k in ("w1", "b1", "w2", "b2", "w3", "b3"))
-    MU.blobs_are_packs(mixed, "mixed")
+    C.blobs_are_packs(mixed, "mixed")
 
 
 def test_the_bf16_split_of_the_target_blob_is_pack_where_rounding_is_decided():
@@ -239,7 +199,7 @@ def test_the_bf16_split_of_the_target_blob_is_pack_where_rounding_is_decided():
     non-zero element kept (a -0 is added to a zero and may come back +0: the header says so), every W2B word of the target's blob
     equals the integer restatement adam_util.w2b_words of the target's w2, and the whole blob is pack()."""
     hp = U.hyper32(lr=0.01, max_grad_norm=1.0)
-    case = MU.Case(2, 8, (4, 1), hp, tau=0.0, seed=11)
+    case = _new(2, 8, (4, 1), hp, tau=0.0, seed=11)
     w2s = [U.w2_edge_weights(case.A, seed=79 + i) for i in range(2)]
     with torch.no_grad():
         for tgt, w2 in zip(case.targets, w2s):
@@ -255,7 +215,7 @@ def test_the_bf16_split_of_the_target_blob_is_pack_where_rounding_is_decided():
         words = after[f"target{i}.blob"].cpu().numpy().view(np.uint32)[:, -U.W2B_FLOATS:]
         bad = np.argwhere(words != U.w2b_words(got.view(np.float32)))
         assert bad.size == 0, ("restatement", i, bad[:4].tolist())
-    MU.blobs_are_packs(case, "bf16 edges")
+    C.blobs_are_packs(case, "bf16 edges")
 
 
 @pytest.mark.parametrize("poison", [float("nan"), 1e30], ids=["nan", "1e30"])
@@ -291,8 +251,8 @@ def test_poisoned_pad_columns_are_neither_read_nor_written(shape, poison):
                 assert bool((y[k][:, mask] == sentinel).all()) and bool((x[k][:, mask] == 0).all()), (s, k)
             else:
                 assert torch.equal(x[k], y[k]), (s, k)
-        MU.blobs_are_packs(a, (shape, s, "a"))
-        MU.blobs_are_packs(b, (shape, s, "b"))
+        C.blobs_are_packs(a, (shape, s, "a"))
+        C.blobs_are_packs(b, (shape, s, "b"))
 
 
 @pytest.mark.parametrize("max_grad_norm", [0.0, 1.0])
@@ -323,7 +283,7 @@ def test_an_agent_with_a_zero_gradient_and_zero_moments_keeps_every_bit_and_its_
     half = MU.polyak([before["target0.w2"].view(torch.float32).cpu().numpy()], [before["net0.w2"].view(torch.float32).cpu().numpy()], 0.5)[0]
     got = after["target0.w2"].view(torch.float32).cpu().numpy()
     assert float(np.abs(got[frozen] - half[frozen]).max()) <= 2.0 ** -24 * float(np.abs(half[frozen]).max())
-    MU.blobs_are_packs(case, max_grad_norm)
+    C.blobs_are_packs(case, max_grad_norm)
 
 
 @pytest.mark.parametrize("A,D,group", [(3, 9, 3), (6, 24, 2)])
@@ -335,9 +295,9 @@ def test_the_tied_call_at_free_width_is_the_untied_call_on_the_groups_sums(A, D,
     share_group's groups of an even A, which neither of these is; the test of the older entries' bits asks it at group = 2n)."""
     from deep_rl_battlespace_amd import learner
     hp = U.hyper32(lr=0.01, max_grad_norm=1.0)
-    tied = MU.Case(A, D, (1,), hp, tau=0.25, seed=13, group=group)
+    tied = _new(A, D, (1,), hp, tau=0.25, seed=13, group=group)
     tied.tie()
-    untied = MU.Case(A, D, (1,), hp, tau=0.25, seed=13, group=1)
+    untied = _new(A, D, (1,), hp, tau=0.25, seed=13, group=1)
     untied.load(tied)
     leaders = list(range(0, A, group))
     gen = torch.Generator().manual_seed(89)
@@ -365,7 +325,7 @@ def test_the_tied_call_at_free_width_is_the_untied_call_on_the_groups_sums(A, D,
         for blob in tied.blobs + tied.target_blobs:
             v = blob.view(A // group, group, -1).view(torch.int32)
             assert bool((v == v[:, :1]).all())
-    MU.blobs_are_packs(tied, (A, D, group))
+    C.blobs_are_packs(tied, (A, D, group))
 
 
 def _mlp_forward(blob, x, y4, raw):
@@ -384,7 +344,7 @@ def test_one_ddpg_update_with_targets_replays_as_one_graph_without_allocating():
     from deep_rl_battlespace_amd import learner
     R, A, Do, Na, gamma = 64, 2, 5, 3, 0.95
     hp = U.hyper32(lr=1e-3, max_grad_norm=0.5)
-    actor, critic = MU.Case(A, Do, (Na,), hp, tau=0.05, seed=17), MU.Case(A, Do + Na, (1,), hp, tau=0.05, seed=19)
+    actor, critic = _new(A, Do, (Na,), hp, tau=0.05, seed=17), _new(A, Do + Na, (1,), hp, tau=0.05, seed=19)
     for c in (actor, critic):
         c.blobs[0].copy_(c.nets[0].pack())
         c.target_blobs[0].copy_(c.targets[0].pack())
@@ -452,5 +412,5 @@ def test_one_ddpg_update_with_targets_replays_as_one_graph_without_allocating():
     replayed = state()
     assert [k for k in eager if not torch.equal(eager[k], replayed[k])] == []
     assert int(actor.step) == 3 == int(critic.step)
-    MU.blobs_are_packs(actor, "ddpg actor")
-    MU.blobs_are_packs(critic, "ddpg critic")
+    C.blobs_are_packs(actor, "ddpg actor")
+    C.blobs_are_packs(critic, "ddpg critic")

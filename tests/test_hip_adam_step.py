@@ -8,13 +8,11 @@ Shapes, the smallest that reach every layout case: n = 1 (D = 5, odd: W1A has a 
 log_std, n = 16 (A = 32, D = 50), each with a 1-column value network beside the policy network, and one single-network call; n = 16
 with log_std (65 partials, the most a call can have: the workspace at its largest, the last partial in its last word); the policy-only
 Gaussian step (one network and log_std: the log_std workgroup is block A) at n = 1 and n = 16; a value network alone."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import adam_case_util as C
 import adam_util as U
 import guard_util as GU
 
@@ -24,209 +22,20 @@ pytestmark = pytest.mark.gpu
 CONFIGS = {"n1": (1, 4, False, True), "n2": (2, 4, False, True), "n3-gaussian": (3, 3, True, True), "n16": (16, 4, False, True),
            "n2-single": (2, 4, False, False), "n16-gaussian": (16, 3, True, True), "n1-policy-gaussian": (1, 3, True, False),
            "n16-policy-gaussian": (16, 3, True, False), "n2-value-only": (2, 1, False, False)}
-STEPS = 5
+RATIOS = "BSX_ADAM_RATIOS_OUT"        # =<file>: the five-step ratios as JSON lines (how profiles/adam_step.json's accuracy table is made)
 
 
-class Case:
-    """One or two networks, their Adam state, blobs (pre-filled with a non-zero pattern), log_std, hyper, counter, stats and workspace on
-    the GPU.  alloc: a guard_util.Buffers -- every buffer the step writes is then a view between guard bytes."""
-
-    def __init__(self, config, hp, seed=0, alloc=None):
-        from deep_rl_battlespace_amd import learner
-        from deep_rl_battlespace_amd.rollout import StackedActor
-        n, na, with_ls, with_value = CONFIGS[config]
-        self.n, self.A, self.D = n, 2 * n, 3 * n + 2
-        A, D = self.A, self.D
-        alloc = alloc or GU.Buffers(False)
-        torch.manual_seed(100 + seed)
-        self.nets = [StackedActor(A, D, na, device="cuda")] + ([StackedActor(A, D, 1, device="cuda")] if with_value else [])
-        self.states, self.blobs = [], []
-        for i, net in enumerate(self.nets):
-            for k in U.PARAMS:                                              # the parameters as views of the allocator's buffers
-                p = getattr(net, k)
-                buf = alloc(f"net{i}.{k}", p.shape, torch.float32)
-                buf.copy_(p.detach())
-                setattr(net, k, torch.nn.Parameter(buf))
-                assert getattr(net, k).data_ptr() == buf.data_ptr()
-            st = learner.AdamState(net)
-            st.m, st.v = alloc(f"net{i}.m", st.m.shape, torch.float32), alloc(f"net{i}.v", st.v.shape, torch.float32)
-            self.states.append(st)
-            self.blobs.append(alloc(f"net{i}.blob", (A, learner.blob_floats(D)), torch.float32, init=-7.25))
-        self.log_std = self.ls_state = None
-        if with_ls:
-            self.log_std = alloc("log_std", (A, 3), torch.float32, init=-0.5)
-            self.ls_state = learner.AdamState(self.log_std)
-            self.ls_state.m, self.ls_state.v = alloc("ls.m", (A, 3), torch.float32), alloc("ls.v", (A, 3), torch.float32)
-        self.hyper = learner.adam_hyper(hp["lr"], (hp["beta1"], hp["beta2"]), hp["eps"], hp["max_grad_norm"])
-        self.step = alloc("step", (1,), torch.int64)
-        self.stats = alloc("stats", (4,), torch.float64, init=-1)
-        nb = learner.adam_step_workspace_bytes(n, len(self.nets))
-        self.ws = alloc("ws", ((nb + 7) // 8,), torch.int64)
-
-    def set_hyper(self, hp):
-        from deep_rl_battlespace_amd import learner
-        self.hyper = learner.adam_hyper(hp["lr"], (hp["beta1"], hp["beta2"]), hp["eps"], hp["max_grad_norm"])
-
-    def zeros(self):
-        """Gradients of +0 in the shapes draw() gives."""
-        rows = [torch.zeros_like(st.m) for st in self.states]
-        return rows, (torch.zeros_like(self.log_std) if self.log_std is not None else None)
-
-    def blobs_from_pack(self):
-        for net, blob in zip(self.nets, self.blobs):
-            blob.copy_(net.pack())
-
-    def draw(self, gen, scale=1.0):
-        """Fresh gradients on the GPU: one row per network, and log_std's."""
-        rows = [U.random_rows(self.A, self.D, net.n_actions, gen, scale).cuda() for net in self.nets]
-        g_ls = (scale * torch.randn((self.A, 3), generator=gen)).cuda() if self.log_std is not None else None
-        return rows, g_ls
-
-    def run(self, rows, g_ls):
-        from deep_rl_battlespace_amd import learner
-        return learner.adam_step(self.nets, rows, self.states, self.blobs, self.hyper, self.step, log_std=self.log_std, g_log_std=g_ls,
-                                 log_std_state=self.ls_state, stats=self.stats, workspace=self.ws)
-
-    def tensors(self):
-        """Everything the step writes, by name."""
-        out = {"step": self.step, "stats": self.stats}
-        for i, (net, st, blob) in enumerate(zip(self.nets, self.states, self.blobs)):
-            out.update({f"net{i}.{k}": getattr(net, k).detach() for k in U.PARAMS})
-            out.update({f"net{i}.m": st.m, f"net{i}.v": st.v, f"net{i}.blob": blob})
-        if self.log_std is not None:
-            out.update({"log_std": self.log_std, "ls.m": self.ls_state.m, "ls.v": self.ls_state.v})
-        return out
-
-    def bits(self):
-        torch.cuda.synchronize()
-        return {k: v.clone().view(torch.int32 if v.element_size() == 4 else torch.int64) for k, v in self.tensors().items()}
-
-    def groups(self):
-        """Per network (params, m, v) as lists of numpy arrays in ten-tensor shapes; log_std rides with the policy network."""
-        out = []
-        for i, (net, st) in enumerate(zip(self.nets, self.states)):
-            P = U.net_arrays(net)
-            M, V = U.row_to_tensors(st.m.cpu().numpy(), net.n_actions), U.row_to_tensors(st.v.cpu().numpy(), net.n_actions)
-            if i == 0 and self.log_std is not None:
-                P.append(self.log_std.cpu().numpy().copy()); M.append(self.ls_state.m.cpu().numpy().copy()); V.append(self.ls_state.v.cpu().numpy().copy())
-            out.append((P, M, V))
-        return out
+def _shape(config):
+    n, na, with_ls, with_value = CONFIGS[config]
+    return 2 * n, 3 * n + 2, (na, 1) if with_value else (na,), with_ls
 
 
-def _same_bits(a, b):
-    return [k for k in a if not torch.equal(a[k], b[k])]
+def _case(config, hp, seed=0, **kw):
+    A, D, nas, with_ls = _shape(config)
+    return C.Case(A, D, nas, hp, with_ls=with_ls, seed=100 + seed, entry="adam", **kw)
 
 
-def _blobs_are_packs(case, where):
-    for i, (net, blob) in enumerate(zip(case.nets, case.blobs)):
-        want = net.pack()
-        assert blob.shape == want.shape
-        bad = (blob.view(torch.int32) != want.view(torch.int32)).nonzero()
-        assert bad.numel() == 0, (where, i, bad[:4].tolist())
-
-
-def _flat_split(case, rows, g_ls):
-    """The call's gradients as one list per network in ten-tensor shapes (torch, GPU), log_std's with the policy network."""
-    out = []
-    for i, (net, row) in enumerate(zip(case.nets, rows)):
-        g = U.row_to_tensors(row, net.n_actions)
-        if i == 0 and g_ls is not None:
-            g.append(g_ls.clone())
-        out.append(g)
-    return out
-
-
-class TorchPath:
-    """torch's float32 clip_grad_norm_ + Adam on the GPU over copies of a case's parameters: the yardstick."""
-
-    def __init__(self, case, hp, t0):
-        self.hp = hp
-        self.params = []
-        for i, net in enumerate(case.nets):
-            ps = [getattr(net, k).detach().clone().requires_grad_() for k in U.PARAMS]
-            if i == 0 and case.log_std is not None:
-                ps.append(case.log_std.clone().requires_grad_())
-            self.params.append(ps)
-        self.flat = [p for ps in self.params for p in ps]
-        self.opt = torch.optim.Adam(self.flat, lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
-        for p in self.flat:
-            self.opt.state[p] = dict(step=torch.tensor(float(t0)), exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
-
-    def set_counter(self, t):
-        for p in self.flat:
-            self.opt.state[p]["step"].fill_(float(t))
-
-    def step(self, grads):
-        for ps, gs in zip(self.params, grads):
-            for p, g in zip(ps, gs):
-                p.grad = g.clone()
-        if self.hp["max_grad_norm"] > 0.0:
-            torch.nn.utils.clip_grad_norm_(self.flat, self.hp["max_grad_norm"])
-        self.opt.step()
-
-    def groups(self):
-        f = lambda x: x.detach().cpu().numpy()     # noqa: E731
-        return [([f(p) for p in ps], [f(self.opt.state[p]["exp_avg"]) for p in ps], [f(self.opt.state[p]["exp_avg_sq"]) for p in ps])
-                for ps in self.params]
-
-
-def _record(config, leg, ratios):
-    """BSX_ADAM_RATIOS_OUT=<file>: append the measured ratios as one JSON line (how profiles/adam_step.json's accuracy table is made)."""
-    print(f"adam_step {config} {leg}: " + ", ".join(f"{k} {m:.3f}/{x:.3f}" for k, (m, x) in sorted(ratios.items())))
-    path = os.environ.get("BSX_ADAM_RATIOS_OUT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(dict(config=config, leg=leg, ratios={k: [round(m, 4), round(x, 4)] for k, (m, x) in ratios.items()})) + "\n")
-
-
-def _start(case):
-    """The float64 restatement's state at a case's present parameters and moments: per network [P, M, V]."""
-    return [[[np.asarray(x, np.float64) for x in grp] for grp in g] for g in case.groups()]
-
-
-def _reference(ref, grads, t, hp):
-    """One step of the float64 restatement over everything in the call at once (one global norm); ref (per network [P, M, V]) is
-    advanced in place -> (t + 1, norm, coef)."""
-    sizes = [len(g) for g in grads]
-    flat = lambda j: [x for grp in ref for x in grp[j]]     # noqa: E731
-    P, M, V, t, norm, coef = U.reference_step(flat(0), [g.cpu().numpy() for gs in grads for g in gs], flat(1), flat(2), t, hp)
-    o = 0
-    for i, k in enumerate(sizes):
-        ref[i] = [P[o:o + k], M[o:o + k], V[o:o + k]]
-        o += k
-    return t, norm, coef
-
-
-def _meets_the_bars(case, yard, ref, config, leg, which=("p", "m", "v")):
-    """Per network and for each of parameters, m, v, pooled over the ten tensors: mean |error| against the float64 restatement at most
-    2x that of torch's own float32 path on the same inputs, maximum at most 4x."""
-    ratios, failed = {}, []
-    for i, (mine, torchs, want) in enumerate(zip(case.groups(), yard.groups(), ref)):
-        for j, what in enumerate(("p", "m", "v")):
-            if what not in which:
-                continue
-            (em, ex), (tm, tx) = U.pooled_errors(mine[j], want[j]), U.pooled_errors(torchs[j], want[j])
-            assert tm > 0.0 and tx > 0.0
-            ratios[f"net{i}.{what}"] = (em / tm, ex / tx)
-            if em > 2.0 * tm or ex > 4.0 * tx:
-                failed.append((i, what, em, tm, ex, tx))
-    _record(config, leg, ratios)
-    assert not failed, failed
-
-
-def _check_stats(case, stats, t, norm, coef, hp):
-    got = stats.cpu().numpy()
-    assert got[0] == t and int(case.step) == t, (got, int(case.step), t)
-    assert abs(got[1] - norm) <= 1e-10 * norm and abs(got[2] - coef) <= 1e-10 * coef and got[3] == hp["lr"], (got, norm, coef)
-
-
-#       leg                lr     counter set to (before step index)   what it shows
-LEGS = {"lr3e-4-from-0": (3e-4, {}),                                 # the usual start: bias corrections far from 1
-        "counter-1000-after-3": (3e-4, {3: 1000}),                   # ... and then near 1: b^t through a large t
-        "lr0.05-counter-1000": (0.05, {0: 1000})}                    # a parameter-sized step: the step's own arithmetic shows
-
-
-@pytest.mark.parametrize("leg", list(LEGS))
+@pytest.mark.parametrize("leg", list(C.LEGS))
 @pytest.mark.parametrize("config", list(CONFIGS))
 def test_five_steps_match_the_float64_restatement_as_well_as_torch_does_and_every_blob_is_the_pack(config, leg):
     """Five steps with fresh gradients each (steps 2 and 4 a tenth of the others: max_grad_norm, half the first step's norm, bites on
@@ -235,49 +44,44 @@ def test_five_steps_match_the_float64_restatement_as_well_as_torch_does_and_ever
     5.1e5) and the float32 lr.  After the five steps, per network and for each of parameters, m, v, pooled over the ten tensors: mean
     |error| against the float64 restatement at most 2x that of torch's own float32 clip_grad_norm_ + Adam on the same inputs, maximum at
     most 4x."""
-    lr, counter = LEGS[leg]
-    gen = torch.Generator().manual_seed(17)
-    probe = Case(config, U.hyper32(lr=lr))
-    rows, g_ls = probe.draw(gen)
-    first = float(np.sqrt(sum(float((g.double() ** 2).sum()) for g in rows + ([g_ls] if g_ls is not None else []))))
+    lr, counter = C.LEGS[leg]
+    first = C.first_norm(*_shape(config), seed=17)
     hp = U.hyper32(lr=lr, max_grad_norm=0.5 * first)
-    case = Case(config, hp)
-    yard = TorchPath(case, hp, 0)
-    ref = _start(case)
+    case = _case(config, hp)
+    yard = C.TorchPath(case, hp)
+    ref = C.start(case)
     t, coefs = 0, []
     gen = torch.Generator().manual_seed(17)
-    for s in range(STEPS):
+    for s in range(C.STEPS):
         if s in counter:
             t = counter[s]
             case.step.fill_(t)
             yard.set_counter(t)
         rows, g_ls = case.draw(gen, 0.1 if s in (1, 3) else 1.0)
-        grads = _flat_split(case, rows, g_ls)
+        grads = C.flat_split(case, rows, g_ls)
         stats = case.run(rows, g_ls)
         yard.step(grads)
-        t, norm, coef = _reference(ref, grads, t, hp)
+        t, norm, coef = C.advance(ref, grads, t, hp)
         coefs.append(coef)
-        _blobs_are_packs(case, (config, leg, s))
-        got = stats.cpu().numpy()
-        assert got[0] == t and int(case.step) == t
-        assert abs(got[1] - norm) <= 1e-10 * norm and abs(got[2] - coef) <= 1e-10 * coef and got[3] == hp["lr"], (got, norm, coef)
+        C.blobs_are_packs(case, (config, leg, s))
+        C.check_stats(case, stats, t, norm, coef, hp)
     assert [c < 1.0 for c in coefs] == [True, False, True, False, True], coefs
-    _meets_the_bars(case, yard, ref, config, leg)
+    C.meets_the_bars(case, yard, ref, config, leg, env=RATIOS)
 
 
 @pytest.mark.parametrize("config", ["n1", "n3-gaussian"])
 def test_no_clipping_and_a_bound_that_never_bites_give_the_bits_of_coefficient_one(config):
     gen = torch.Generator().manual_seed(23)
-    off, huge = Case(config, U.hyper32()), Case(config, U.hyper32(max_grad_norm=1e30))
+    off, huge = _case(config, U.hyper32()), _case(config, U.hyper32(max_grad_norm=1e30))
     for _ in range(2):
         rows, g_ls = off.draw(gen)
         off.run(rows, g_ls)
         huge.run(rows, g_ls)
-        a, b = off.bits(), huge.bits()
-        assert _same_bits({k: v for k, v in a.items() if k != "stats"}, b) == []
+        a, b = ({k: v for k, v in c.bits().items() if k != "stats"} for c in (off, huge))
+        assert C.same_bits(a, b) == []
         assert float(off.stats[2]) == 1.0 == float(huge.stats[2]) and torch.equal(off.stats, huge.stats)
     # a bound of 1 does bite on these gradients: 1e30 above was a bound that did not, not a switch that is ignored
-    clipped = Case(config, U.hyper32(max_grad_norm=1.0))
+    clipped = _case(config, U.hyper32(max_grad_norm=1.0))
     gen = torch.Generator().manual_seed(23)
     rows, g_ls = clipped.draw(gen)
     clipped.run(rows, g_ls)
@@ -288,23 +92,23 @@ def test_no_clipping_and_a_bound_that_never_bites_give_the_bits_of_coefficient_o
 def test_two_calls_from_copies_of_one_state_give_identical_bits_and_leave_the_guards_alone(config):
     hp = U.hyper32(max_grad_norm=5.0)
     alloc = GU.Buffers(True)
-    a, b = Case(config, hp, alloc=alloc), Case(config, hp)
+    a, b = _case(config, hp, alloc=alloc), _case(config, hp)
     gen = torch.Generator().manual_seed(29)
     for _ in range(2):
         rows, g_ls = a.draw(gen)
         a.run(rows, g_ls)
         b.run([r.clone() for r in rows], g_ls.clone() if g_ls is not None else None)
-    assert _same_bits(a.bits(), b.bits()) == []
+    assert C.same_bits(a.bits(), b.bits()) == []
     assert int(a.step) == 2 and float(a.stats[2]) < 1.0
     assert alloc.stray() == []
-    _blobs_are_packs(a, config)
+    C.blobs_are_packs(a, config)
 
 
 @pytest.mark.parametrize("max_grad_norm", [0.0, 1.0])
 def test_an_agent_with_a_zero_gradient_and_zero_moments_keeps_every_bit(max_grad_norm):
     """What a scripted opponent's agents are to the learner: gradient rows of +0, moments +0.  Parameters, moments and the blob row stay
     as they are, with clipping on and off; the other agents move."""
-    case = Case("n3-gaussian", U.hyper32(lr=0.01, max_grad_norm=max_grad_norm))
+    case = _case("n3-gaussian", U.hyper32(lr=0.01, max_grad_norm=max_grad_norm))
     for net, blob in zip(case.nets, case.blobs):
         blob.copy_(net.pack())
     frozen = [1, 4]
@@ -326,7 +130,7 @@ def test_an_agent_with_a_zero_gradient_and_zero_moments_keeps_every_bit(max_grad
 
 def test_the_binding_refuses_wrong_tensors_by_name():
     from deep_rl_battlespace_amd import learner
-    case = Case("n3-gaussian", U.hyper32())
+    case = _case("n3-gaussian", U.hyper32())
     rows, g_ls = case.draw(torch.Generator().manual_seed(37))
     kw = dict(log_std=case.log_std, g_log_std=g_ls, log_std_state=case.ls_state)
 
@@ -364,7 +168,7 @@ def test_the_binding_refuses_wrong_tensors_by_name():
     with pytest.raises(ValueError, match=r"nets\[0\]\.w2.*contiguous"):
         call()
     case.nets[0].w2 = w2
-    assert _same_bits(before, case.bits()) == []                    # nothing was launched by a refused call
+    assert C.same_bits(before, case.bits()) == []                    # nothing was launched by a refused call
 
 
 def _row_of(case, index):
@@ -381,7 +185,7 @@ def test_each_partial_norm_alone_reaches_the_clip_and_only_its_row_moves(config,
     stats is that row's alone (1e-10 relative), the coefficient bites, the row behind the index moves in every tensor and every other
     parameter, moment and blob row keeps its bits (grad = m = v = +0 keeps p, m, v; the blobs start as pack()).  At n = 16 with two
     networks and log_std, index 64 is the one partial a lane adds as its second; at one network and log_std the last index is block A."""
-    case = Case(config, U.hyper32(lr=0.01))
+    case = _case(config, U.hyper32(lr=0.01))
     case.blobs_from_pack()
     drawn, drawn_ls = case.draw(torch.Generator().manual_seed(41 + index))
     rows, g_ls = case.zeros()
@@ -401,7 +205,7 @@ def test_each_partial_norm_alone_reaches_the_clip_and_only_its_row_moves(config,
     after = case.bits()
     coef = hp["max_grad_norm"] / (norm + 1e-6)
     print(f"adam_step {config} partial {index}: norm {float(stats[1])!r} want {norm!r}, coef {float(stats[2])!r} want {coef!r}")
-    _check_stats(case, stats, 1, norm, coef, hp)
+    C.check_stats(case, stats, 1, norm, coef, hp)
     assert float(stats[2]) < 1.0
     for k in before:
         if k in ("step", "stats"):
@@ -414,7 +218,7 @@ def test_each_partial_norm_alone_reaches_the_clip_and_only_its_row_moves(config,
             assert not torch.equal(before[k][agent], after[k][agent]), k
         else:
             assert torch.equal(before[k], after[k]), k
-    _blobs_are_packs(case, (config, index))
+    C.blobs_are_packs(case, (config, index))
 
 
 @pytest.mark.parametrize("poison", [float("nan"), 1e30], ids=["nan", "1e30"])
@@ -425,7 +229,7 @@ def test_poisoned_pad_columns_are_neither_read_nor_written(config, poison):
     equals A's bit for bit outside the moments' pads -- the norm and the coefficient in stats among them --, B's pads still hold 7.25,
     A's +0, and every blob is pack() (whose pad columns are +0)."""
     hp = U.hyper32(lr=0.01, max_grad_norm=1.0)
-    a, b = Case(config, hp, seed=3), Case(config, hp, seed=3)
+    a, b = _case(config, hp, seed=3), _case(config, hp, seed=3)
     masks = [torch.from_numpy(U.pad_mask(a.D, net.n_actions)).cuda() for net in a.nets]
     assert any(int(m.sum()) for m in masks)
     sentinel = torch.tensor(7.25).view(torch.int32).item()
@@ -451,8 +255,8 @@ def test_poisoned_pad_columns_are_neither_read_nor_written(config, poison):
                 assert bool((y[k][:, mask] == sentinel).all()) and bool((x[k][:, mask] == 0).all()), (s, k)
             else:
                 assert torch.equal(x[k], y[k]), (s, k, x[k].view(-1)[:4], y[k].view(-1)[:4])
-        _blobs_are_packs(a, (config, s, "a"))
-        _blobs_are_packs(b, (config, s, "b"))
+        C.blobs_are_packs(a, (config, s, "a"))
+        C.blobs_are_packs(b, (config, s, "b"))
 
 
 @pytest.mark.parametrize("max_grad_norm", [0.0, 1.0])
@@ -465,7 +269,7 @@ def test_the_bf16_split_of_the_blob_is_pack_where_rounding_is_decided(config, ma
     test_adam_step_cpu.py); the whole blob equals pack() of a CPU copy of the network and pack() on the GPU.  Non-finite weights are a
     diverged run and are not covered."""
     from deep_rl_battlespace_amd.rollout import StackedActor
-    case = Case(config, U.hyper32(max_grad_norm=max_grad_norm))
+    case = _case(config, U.hyper32(max_grad_norm=max_grad_norm))
     w2s = [U.w2_edge_weights(case.A, seed=47 + i) for i in range(len(case.nets))]
     with torch.no_grad():
         for net, w2 in zip(case.nets, w2s):
@@ -475,7 +279,8 @@ def test_the_bf16_split_of_the_blob_is_pack_where_rounding_is_decided(config, ma
         assert np.array_equal(before[f"net{i}.w2"].cpu().numpy().view(np.uint32), w2.view(np.uint32))
     case.run(*case.zeros())
     after = case.bits()
-    assert _same_bits({k: v for k, v in before.items() if k not in ("step", "stats") and not k.endswith(".blob")}, after) == []
+    kept = lambda bits: {k: v for k, v in bits.items() if k not in ("step", "stats") and not k.endswith(".blob")}     # noqa: E731
+    assert C.same_bits(kept(before), kept(after)) == []
     assert int(case.step) == 1 and float(case.stats[1]) == 0.0 and float(case.stats[2]) == 1.0
     for i, (net, w2) in enumerate(zip(case.nets, w2s)):
         got = after[f"net{i}.blob"].cpu().numpy().view(np.uint32)
@@ -499,31 +304,28 @@ def test_a_counter_beyond_int32_counts_exactly_and_steps_with_bias_corrections_o
     max_grad_norm, half the first norm, bites on 1 and 3), stats[0] and `step` hold the exact count after each, every blob is pack(), and
     the result meets the five-step test's bars.  For t >= 2^24 both bias corrections are exactly 1 in float64 (0.999^t < 2^-53 from about
     t = 36 700 on), so the torch yardstick, whose counter is a float32, runs with it at 2^24, where it stays."""
-    gen = torch.Generator().manual_seed(53)
-    probe = Case(config, U.hyper32())
-    rows, g_ls = probe.draw(gen)
-    first = float(np.sqrt(sum(float((g.double() ** 2).sum()) for g in rows + ([g_ls] if g_ls is not None else []))))
+    first = C.first_norm(*_shape(config), seed=53)
     hp = U.hyper32(max_grad_norm=0.5 * first)
     assert 1.0 - hp["beta1"] ** 2 ** 24 == 1.0 == 1.0 - hp["beta2"] ** 2 ** 24
-    case = Case(config, hp)
-    yard = TorchPath(case, hp, 2 ** 24)
-    ref = _start(case)
+    case = _case(config, hp)
+    yard = C.TorchPath(case, hp, t0=2 ** 24)
+    ref = C.start(case)
     case.step.fill_(t0)
     t, coefs = t0, []
     gen = torch.Generator().manual_seed(53)
     for s in range(3):
         rows, g_ls = case.draw(gen, 0.1 if s == 1 else 1.0)
-        grads = _flat_split(case, rows, g_ls)
+        grads = C.flat_split(case, rows, g_ls)
         stats = case.run(rows, g_ls)
         yard.step(grads)
-        t, norm, coef = _reference(ref, grads, t, hp)
+        t, norm, coef = C.advance(ref, grads, t, hp)
         coefs.append(coef)
         assert t == t0 + s + 1
-        _check_stats(case, stats, t, norm, coef, hp)
-        _blobs_are_packs(case, (config, t0, s))
+        C.check_stats(case, stats, t, norm, coef, hp)
+        C.blobs_are_packs(case, (config, t0, s))
     assert [c < 1.0 for c in coefs] == [True, False, True], coefs
     assert all(float(yard.opt.state[p]["step"]) == 2 ** 24 for p in yard.flat)
-    _meets_the_bars(case, yard, ref, config, f"counter-{t0}")
+    C.meets_the_bars(case, yard, ref, config, f"counter-{t0}", env=RATIOS)
 
 
 def test_a_learning_rate_of_zero_moves_the_moments_and_no_parameter():
@@ -531,36 +333,36 @@ def test_a_learning_rate_of_zero_moves_the_moments_and_no_parameter():
     meet the bars; `step` advances and stats[3] is 0."""
     config = "n3-gaussian"
     hp = U.hyper32(lr=0.0, max_grad_norm=1.0)
-    case = Case(config, hp)
+    case = _case(config, hp)
     case.blobs_from_pack()
-    yard = TorchPath(case, hp, 0)
-    ref = _start(case)
+    yard = C.TorchPath(case, hp)
+    ref = C.start(case)
     before = case.bits()
     gen, t = torch.Generator().manual_seed(59), 0
     for s in range(2):
         rows, g_ls = case.draw(gen)
-        grads = _flat_split(case, rows, g_ls)
+        grads = C.flat_split(case, rows, g_ls)
         stats = case.run(rows, g_ls)
         yard.step(grads)
-        t, norm, coef = _reference(ref, grads, t, hp)
-        _check_stats(case, stats, t, norm, coef, hp)
+        t, norm, coef = C.advance(ref, grads, t, hp)
+        C.check_stats(case, stats, t, norm, coef, hp)
         assert coef < 1.0 and float(stats[3]) == 0.0
     after = case.bits()
     moments = [k for k in before if k.endswith((".m", ".v"))]
     assert len(moments) == 2 * len(case.nets) + 2
-    assert sorted(_same_bits(before, after)) == sorted(moments + ["step", "stats"])
+    assert sorted(C.same_bits(before, after)) == sorted(moments + ["step", "stats"])
     assert int(case.step) == 2
-    _meets_the_bars(case, yard, ref, config, "lr0", which=("m", "v"))
+    C.meets_the_bars(case, yard, ref, config, "lr0", which=("m", "v"), env=RATIOS)
 
 
 def test_an_all_zero_gradient_under_clipping_has_norm_zero_and_coefficient_exactly_one():
     """Every gradient +0 with max_grad_norm = 1: norm = 0, coef = min(1, 1 / 1e-6) = 1 exactly; moments are +0, so nothing but `step`
     and stats changes (the blobs hold pack() before the call and after it)."""
-    case = Case("n3-gaussian", U.hyper32(lr=0.01, max_grad_norm=1.0))
+    case = _case("n3-gaussian", U.hyper32(lr=0.01, max_grad_norm=1.0))
     case.blobs_from_pack()
     before = case.bits()
     stats = case.run(*case.zeros())
     after = case.bits()
     assert stats.tolist() == [1.0, 0.0, 1.0, U.hyper32(lr=0.01)["lr"]]
-    assert sorted(_same_bits(before, after)) == ["stats", "step"] and int(case.step) == 1
-    _blobs_are_packs(case, "all-zero")
+    assert sorted(C.same_bits(before, after)) == ["stats", "step"] and int(case.step) == 1
+    C.blobs_are_packs(case, "all-zero")
