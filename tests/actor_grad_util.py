@@ -14,10 +14,12 @@
   factors / ratios / check  the bound: per tensor, mean(e_k) <= fm mean(e_t) and max(e_k) <= fx max(e_t), with (fm, fx) = the project's
                    (2, 4) (actor_ref_util.F32_FACTORS) except where the recorded spread of the yardstick reaches them
                    (profiles/actor_grad_float64.json says where and why)
+  CLIP, TAU, _to, _logp, _ppo   the PPO loss in torch (clipped surrogate + value loss - entropy bonus over the kept rows of a rollout
+                   record) that tests/test_hip_actor_grad.py and tests/test_hip_ppo_learner.py both hold the fused paths to
 
 plan, autograd_grads (with the input's gradient as an eleventh tensor "x" on request), spread, row_permutation_spread, ratios and check
 are the one yardstick of every fused-gradient test: tests/mlp_grad_util.py brings its own cases and factors and imports these.
-Nothing here imports the native library but plan()."""
+Nothing here imports the native library but plan() and the fused legs of _logp and _ppo."""
 import functools
 import json
 import os
@@ -201,3 +203,46 @@ def check(got, g64, g32, what="", names=PARAMS, factor_of=None):
     bad = [(k, r[k]) for k in names if not (r[k][0] <= f[k][0] and r[k][1] <= f[k][1])]
     assert not bad, (what, bad)
     return r
+
+
+# ---------------------------------------------------------------------------------------------------- the PPO loss, in torch
+TAU, CLIP = 0.7, 0.2
+
+
+def _to(actor, device="cuda", dtype=torch.float32):
+    a = R._new(actor.n_actors, actor.obs_len, actor.n_actions, dtype=dtype, device=device)
+    with torch.no_grad():
+        for k in PARAMS:
+            getattr(a, k).copy_(getattr(actor, k).detach().to(device=device, dtype=dtype))
+    return a
+
+
+def _logp(actor, ls, obs, act, kind, fused):
+    from deep_rl_battlespace_amd.learner import categorical_log_prob
+    from deep_rl_battlespace_amd.rollout import gaussian_log_prob
+    if kind == "gaussian":
+        return gaussian_log_prob(actor, ls, obs, act, fused=fused)
+    return categorical_log_prob(actor, obs, act, temperature=TAU, fused=fused)
+
+
+def _ppo(actor, critic, ls, rec, keep, kind, fused, device, dtype, perm=None):
+    """(loss, actor grads, critic grads, log_std grad) of the clipped surrogate + value loss - entropy bonus over the kept rows, the rows
+    flattened (and permuted: another summation order of the same loss)."""
+    from deep_rl_battlespace_amd.learner import fused_apply
+    a, c = _to(actor, device, dtype), _to(critic, device, dtype)
+    l = ls.detach().to(device=device, dtype=dtype).requires_grad_() if ls is not None else None
+    A, D = rec["obs"].shape[-2:]
+    flat = dict(obs=rec["obs"].reshape(-1, A, D), act=rec["act"].reshape(-1, A, *rec["act"].shape[3:]), logp=rec["logp"].reshape(-1, A),
+                adv=rec["adv"].reshape(-1, A), ret=rec["ret"].reshape(-1, A), keep=keep.reshape(-1, A))
+    if perm is not None:
+        flat = {k: v[perm] for k, v in flat.items()}
+    f = {k: (v.to(device=device, dtype=dtype) if v.is_floating_point() else v.to(device)).contiguous() for k, v in flat.items()}
+    logp, ent = _logp(a, l, f["obs"], f["act"], kind, fused)
+    v = fused_apply(c, f["obs"], squash=False)[..., 0] if fused else c(f["obs"], squash=False)[..., 0]
+    ratio = torch.exp(logp - f["logp"])
+    surr = torch.minimum(ratio * f["adv"], ratio.clamp(1 - CLIP, 1 + CLIP) * f["adv"])
+    w = f["keep"].to(dtype)
+    loss = (-(surr * w).sum() + 0.5 * ((v - f["ret"]) ** 2 * w).sum() - 0.01 * (ent * w).sum()) / w.sum()
+    loss.backward()
+    grads = lambda m: {k: getattr(m, k).grad.double().cpu().numpy() for k in PARAMS}   # noqa: E731
+    return float(loss.detach().double()), grads(a), grads(c), (l.grad.double().cpu().numpy() if l is not None else None), ratio.detach().double().cpu()

@@ -2,7 +2,7 @@
 
   reference        the contract of include/battlespace_hip.h (bsx_ppo_head) restated in float64 numpy: g_pi, g_v, g_log_std, stats
   torch_loss       the same loss written the way a user would (log_softmax / gather / clamp / torch.minimum / torch.maximum, as
-                   tests/test_hip_actor_grad.py::_ppo words it) with autograd from y, v (and log_std): in float64 the check of the
+                   tests/actor_grad_util.py::_ppo words it) with autograd from y, v (and log_std): in float64 the check of the
                    restatement, in float32 the yardstick -- what float32 itself loses on these inputs
   build            inputs: a behaviour policy y_old and a learner policy y a `step` away in pre-tanh space; categorical rec = y_old /
                    temperature + Gumbel noise, Gaussian rec = y_old + exp(log_std) z; logp_old from y_old; adv, v_old, v, ret normals;

@@ -14,6 +14,7 @@ import torch
 
 import actor_grad_util as U
 import actor_ref_util as R
+from actor_grad_util import CLIP, TAU, _logp, _ppo, _to
 from guard_util import Buffers
 
 pytestmark = pytest.mark.gpu
@@ -23,14 +24,6 @@ RAGGED = (1, 31, 32, 33, 63, 65, 255, 257)
 # (rows, n).  n = 16: 16 workgroups per agent, so 2 048 rows are the last one-round size and 2 049 is ONE valid row in round 2 (every
 # other lane of that round reads row R - 1 with grad_out = 0); n = 11: the two-tile dW1 kernel below and above a workgroup's 128 rows
 RAGGED_CASES = [(r, n) for n in (1, 4) for r in RAGGED] + [(r, 16) for r in (1, 33, 2047, 2048, 2049, 2081)] + [(31, 11), (257, 11)]
-
-
-def _to(actor, device="cuda", dtype=torch.float32):
-    a = R._new(actor.n_actors, actor.obs_len, actor.n_actions, dtype=dtype, device=device)
-    with torch.no_grad():
-        for k in U.PARAMS:
-            getattr(a, k).copy_(getattr(actor, k).detach().to(device=device, dtype=dtype))
-    return a
 
 
 def _fused_grads(actor_cpu, obs_cpu, go_cpu, squash):
@@ -246,9 +239,6 @@ def test_fused_apply_refuses_what_it_documents():
 
 
 # ---------------------------------------------------------------------------------------------------- 5. end to end: a PPO loss
-TAU, CLIP = 0.7, 0.2
-
-
 @functools.lru_cache(maxsize=None)
 def _record(kind):
     """One small rollout with GAE: the records a PPO update reads, on the CPU (read-only), and the networks that produced them."""
@@ -272,37 +262,6 @@ def _record(kind):
     act = ro.scores.clone() if cont else ro.scores.argmax(-1)
     rec = dict(obs=ro.obs[:T].clone(), act=act, logp=ro.logp.clone(), adv=ro.adv.clone(), ret=ro.ret.clone(), mask=ro.mask.clone())
     return actor, critic, ls, {k: v.cpu() for k, v in rec.items()}
-
-
-def _logp(actor, ls, obs, act, kind, fused):
-    from deep_rl_battlespace_amd.learner import categorical_log_prob
-    from deep_rl_battlespace_amd.rollout import gaussian_log_prob
-    if kind == "gaussian":
-        return gaussian_log_prob(actor, ls, obs, act, fused=fused)
-    return categorical_log_prob(actor, obs, act, temperature=TAU, fused=fused)
-
-
-def _ppo(actor, critic, ls, rec, keep, kind, fused, device, dtype, perm=None):
-    """(loss, actor grads, critic grads, log_std grad) of the clipped surrogate + value loss - entropy bonus over the kept rows, the rows
-    flattened (and permuted: another summation order of the same loss)."""
-    from deep_rl_battlespace_amd.learner import fused_apply
-    a, c = _to(actor, device, dtype), _to(critic, device, dtype)
-    l = ls.detach().to(device=device, dtype=dtype).requires_grad_() if ls is not None else None
-    A, D = rec["obs"].shape[-2:]
-    flat = dict(obs=rec["obs"].reshape(-1, A, D), act=rec["act"].reshape(-1, A, *rec["act"].shape[3:]), logp=rec["logp"].reshape(-1, A),
-                adv=rec["adv"].reshape(-1, A), ret=rec["ret"].reshape(-1, A), keep=keep.reshape(-1, A))
-    if perm is not None:
-        flat = {k: v[perm] for k, v in flat.items()}
-    f = {k: (v.to(device=device, dtype=dtype) if v.is_floating_point() else v.to(device)).contiguous() for k, v in flat.items()}
-    logp, ent = _logp(a, l, f["obs"], f["act"], kind, fused)
-    v = fused_apply(c, f["obs"], squash=False)[..., 0] if fused else c(f["obs"], squash=False)[..., 0]
-    ratio = torch.exp(logp - f["logp"])
-    surr = torch.minimum(ratio * f["adv"], ratio.clamp(1 - CLIP, 1 + CLIP) * f["adv"])
-    w = f["keep"].to(dtype)
-    loss = (-(surr * w).sum() + 0.5 * ((v - f["ret"]) ** 2 * w).sum() - 0.01 * (ent * w).sum()) / w.sum()
-    loss.backward()
-    grads = lambda m: {k: getattr(m, k).grad.double().cpu().numpy() for k in U.PARAMS}   # noqa: E731
-    return float(loss.detach().double()), grads(a), grads(c), (l.grad.double().cpu().numpy() if l is not None else None), ratio.detach().double().cpu()
 
 
 @pytest.mark.parametrize("kind", ["gaussian", "categorical"])

@@ -1,13 +1,14 @@
 """learner.PPOLearner on the MI355X, over the small rollout record of the existing PPO test: one minibatch's gradients and loss against
-the torch loss of tests/test_hip_actor_grad.py (`_ppo`: the same reference, the same bounds); update() against the same sequence written
-out by hand, bit for bit, with nothing allocated the second time and the rollout playing the updated weights; constructor refusals."""
+the torch loss of tests/test_hip_actor_grad.py (actor_grad_util._ppo: the same reference, the same bounds); update() against the same
+sequence written out by hand, bit for bit, with nothing allocated the second time and the rollout playing the updated weights;
+constructor refusals."""
 import numpy as np
 import pytest
 import torch
 
 import actor_grad_util as U
 import ppo_learner_util as L
-from test_hip_actor_grad import CLIP, _ppo, _to
+from actor_grad_util import CLIP, _logp, _ppo, _to
 
 pytestmark = pytest.mark.gpu
 
@@ -156,7 +157,6 @@ def test_on_the_policy_that_played_nothing_is_clipped_and_the_records_meet_float
     import actor_ref_util as R
     from deep_rl_battlespace_amd.learner import PPOLearner, fused_apply
     from deep_rl_battlespace_amd.rollout import FusedActor
-    from test_hip_actor_grad import _logp
     kind, kw, _ = {**CONFIGS, **OPPONENT_CONFIGS}[config]
     ro = L.small_rollout(kind, **kw)
     cont = kind == "gaussian"
@@ -217,27 +217,15 @@ def _state(learner):
 
 
 def _five_calls_on_clones(learner, t0, t1):
-    """minibatch_grads(t0, t1) written out -- pack, forward, ppo_head, bsx_actor_grad twice -- on .clone()s of the sliced records
-    (fresh allocations: aligned, whatever the views' offsets are) and buffers of its own -> (actor row, critic row, g_log_std, stats)."""
-    from deep_rl_battlespace_amd import _lib
-    from deep_rl_battlespace_amd.learner import _Buffers, _mlp_grad, ppo_head
-    ro, lib = learner.rollout, _lib.load()
-    E, A, D = ro.obs.shape[1:]
-    n, R, dev = A // 2, (t1 - t0) * E, ro.obs.device
-    obs = ro.obs[t0:t1].clone().view(R, A, D)
-    blob_a, blob_v = ro.actor.pack(), ro.value_actor.pack()
-    y, v = torch.empty((R, A, 4), device=dev), torch.empty((R, A), device=dev)
-    nz = _lib.BsxActorNoise()
-    nz.value_weights, nz.value = blob_v.data_ptr(), v.data_ptr()
-    _lib.check(lib.bsx_actor_forward(blob_a.data_ptr(), obs.data_ptr(), y.data_ptr(), R, n, _lib.ACTOR_F32, _lib.ctypes.byref(nz), 0, 0, None, 0,
-                                     torch.cuda.current_stream(dev).cuda_stream), "bsx_actor_forward")
-    flat = lambda x: x[t0:t1].clone().view(R, A, *x.shape[3:])                    # noqa: E731
-    head = ppo_head(learner.kind, y, v, flat(ro.scores), flat(ro.logp), flat(ro.adv), flat(ro.ret), flat(ro._mask), clip=learner.clip,
-                    c_v=learner.c_v, c_e=learner.c_e, temperature=learner.temperature, log_std=learner.log_std,
-                    v_old=flat(ro.value) if learner.vclip is not None else None, vclip=learner.vclip)
-    row_a = _mlp_grad(lib, _Buffers().get(R, A, D, dev, lib), blob_a, obs, head.g_pi, True)
-    row_v = _mlp_grad(lib, _Buffers().get(R, A, D, dev, lib), blob_v, obs, head.g_v, False)
-    return row_a, row_v, head.g_log_std, head.stats
+    """minibatch_grads(t0, t1) written out -- pack, then ppo_learner_util.five_calls -- on .clone()s of the sliced records (fresh
+    allocations: aligned, whatever the views' offsets are) and buffers of its own -> (actor row, critic row, g_log_std, stats)."""
+    from deep_rl_battlespace_amd.learner import Minibatch
+    ro = learner.rollout
+    assert learner.temperature == (L.TAU if learner.kind == "categorical" else 1.0) and learner.vclip is not None
+    flat = lambda x: x[t0:t1].clone().view(-1, *x.shape[2:])                      # noqa: E731
+    mb = Minibatch(flat(ro.obs), flat(ro.scores), flat(ro.logp), flat(ro.adv), flat(ro.ret), flat(ro._mask), flat(ro.value))
+    return L.five_calls(ro, learner.kind, mb, ro.actor.pack(), ro.value_actor.pack(),
+                        dict(clip=learner.clip, c_v=learner.c_v, c_e=learner.c_e, vclip=learner.vclip))
 
 
 def _update_equals_the_sequence_by_hand(ro, kw, grads):
@@ -285,19 +273,8 @@ def test_update_is_the_hand_written_sequence_bit_for_bit_allocates_once_and_reac
     ro = L.small_rollout(kind)
     kw = dict(clip=0.2, c_v=0.5, c_e=0.01, vclip=0.2, epochs=2, minibatches=2)
     hand = _update_equals_the_sequence_by_hand(ro, kw, lambda learner, t0, t1: learner.minibatch_grads(t0, t1))
-    # a second update allocates nothing: the same buffers, at the same addresses
-    def held():                                                                 # noqa: E306
-        out = {("head", R, k): v.data_ptr() for R, b in hand._by_rows.items() for k, v in b.items() if v is not None}
-        for net in (ro.actor, ro.value_actor):
-            for key, b in _buffers(net).by_key.items():
-                out.update({(id(net), key, k): (v.data_ptr() if v is not None else None) for k, v in b.items()})
-        return out
-    hand.update()
-    before = held()
+    L.allocates_nothing(hand, in_use=False)                                     # the same buffers, at the same addresses
     assert len(hand._by_rows) == 1 and all(b["go"] is None for b in _buffers(ro.actor).by_key.values())
-    hand.update()
-    torch.cuda.synchronize()
-    assert held() == before
     assert torch.equal(ro.fused.weights, ro.actor.pack())
     ro.run()
     torch.cuda.synchronize()

@@ -2,9 +2,7 @@
 forward, the head, two backward calls, adam_step) and the permutation's restatement, the torch-optimiser path, the captured update against
 an eager twin over fresh rollouts, allocation, one full-batch step against the unshuffled one, a scripted opponent, and shuffle=False
 against the same hand sequence on tick ranges.  The rollout is tests/ppo_learner_util.small_rollout (n = 1, E = 96, T = 8, both kinds; one
-case at n = 3), the hyper-parameters those of tests/test_hip_ppo_device_update.py."""
-import gc
-
+case at n = 3); the hyper-parameters and the harness are that file's."""
 import numpy as np
 import pytest
 import torch
@@ -12,20 +10,9 @@ import torch
 import ppo_head_util as H
 import ppo_learner_util as L
 import shuffle_util as S
-import test_hip_ppo_device_update as DU
+from ppo_learner_util import KW, STEPS
 
 pytestmark = pytest.mark.gpu
-KW = DU.KW
-STEPS = KW["epochs"] * KW["minibatches"]
-
-
-def _own(learner):
-    return DU._own(learner) + ([learner.shuffle_base, learner.minibatch_idx] if learner.shuffle else [])
-
-
-def _everything(learner):
-    torch.cuda.synchronize()
-    return [t.detach().clone() for t in DU._shared(learner.rollout) + _own(learner)]
 
 
 def _restated_idx(ro, seed, first_seq, epochs=KW["epochs"], M=KW["minibatches"]):
@@ -61,57 +48,34 @@ def _gathered(ro, i, idx_rows, seed):
 
 def _by_hand(ro, kind, minibatch_of):
     """STEPS optimiser steps on the rollout's own blobs from the raw calls: the forward, the head, both backward calls on fresh buffers,
-    adam_step -> what DU._everything lists (shared tensors, moments, count, head rows, step rows[, log_std moments])."""
-    from deep_rl_battlespace_amd import _lib
-    from deep_rl_battlespace_amd.learner import AdamState, _actor_forward, _Buffers, _mlp_grad, adam_hyper, adam_step, ppo_head
-    lib = _lib.load()
-    nets = [ro.actor, ro.value_actor]
-    states = [AdamState(ro.actor), AdamState(ro.value_actor)]
-    ls_state = AdamState(ro.log_std) if kind == "gaussian" else None
-    hyper, count = adam_hyper(KW["lr"], (0.9, 0.999), 1e-8, KW["max_grad_norm"]), torch.zeros(1, dtype=torch.int64, device="cuda")
-    head_rows, step_rows = [], []
-    for i in range(STEPS):
-        mb = minibatch_of(i)
-        R, A, D = mb.obs.shape
-        y, v = torch.empty((R, A, 4), device="cuda"), torch.empty((R, A), device="cuda")
-        _actor_forward(lib, ro.fused.weights, mb.obs, y, ro._value_w, v)
-        head = ppo_head(kind, y, v, mb.rec, mb.logp, mb.adv, mb.ret, mb.mask, clip=KW["clip"], c_v=KW["c_v"], c_e=KW["c_e"],
-                        temperature=L.TAU if kind == "categorical" else 1.0, log_std=ro.log_std if kind == "gaussian" else None,
-                        v_old=mb.value, vclip=KW["vclip"])
-        rows = [_mlp_grad(lib, _Buffers().get(R, A, D, "cuda:0", lib), blob, mb.obs, g, squash)
-                for blob, g, squash in ((ro.fused.weights, head.g_pi, True), (ro._value_w, head.g_v, False))]
-        head_rows.append(head.stats)
-        step_rows.append(adam_step(nets, rows, states, [ro.fused.weights, ro._value_w], hyper, count,
-                                   log_std=ro.log_std if ls_state else None, g_log_std=head.g_log_std, log_std_state=ls_state))
-    torch.cuda.synchronize()
-    return [t.detach().clone() for t in DU._shared(ro)] + [states[0].m, states[0].v, states[1].m, states[1].v, count, torch.stack(head_rows),
-                                                            torch.stack(step_rows)] + ([ls_state.m, ls_state.v] if ls_state else [])
+    adam_step."""
+    return L.by_hand(ro, kind, lambda i: L.five_calls(ro, kind, minibatch_of(i), ro.fused.weights, ro._value_w, L.HEAD_KW))
 
 
 @pytest.mark.parametrize("kind,n", [("gaussian", 1), ("categorical", 1), ("categorical", 3)])
 def test_the_shuffled_device_update_is_the_hand_written_sequence_and_the_restated_rows(kind, n):
     from deep_rl_battlespace_amd.learner import PPOLearner
     ro = L.small_rollout(kind, n=n, E=96 if n == 1 else 48)
-    start = DU._keep(ro)
+    start = L.keep(ro)
     learner = PPOLearner(ro, device_step=True, shuffle=True, **KW)
     assert learner.shuffle_seed == ro.fused.seed and int(learner.shuffle_base) == 0
     stats = learner.update()
-    got = _everything(learner)
+    got = L.everything(learner)
     assert stats.shape == (STEPS, 8) and bool(torch.isfinite(stats).all()) and bool((stats[:, 0] > 100).all())
-    assert int(learner.shuffle_base) == KW["epochs"] and int(learner.step_count) == STEPS and DU._blobs_are_packs(ro)
+    assert int(learner.shuffle_base) == KW["epochs"] and int(learner.step_count) == STEPS and L.blobs_are_packs(ro)
     want_idx = _restated_idx(ro, ro.fused.seed, 0)
     assert learner.minibatch_idx.shape == want_idx.shape and torch.equal(learner.minibatch_idx, want_idx)
     for j in range(KW["epochs"]):                                                   # every epoch takes every row exactly once
         rows = learner.minibatch_idx[j * KW["minibatches"]:(j + 1) * KW["minibatches"]].reshape(-1)
         assert torch.equal(rows.sort().values, torch.arange(rows.numel(), device="cuda"))
     assert not torch.equal(learner.minibatch_idx[:KW["minibatches"]], learner.minibatch_idx[KW["minibatches"]:2 * KW["minibatches"]])
-    DU._restore(ro, start)
+    L.restore(ro, start)
     idx_rows = []
     want = _by_hand(ro, kind, lambda i: _gathered(ro, i, idx_rows, ro.fused.seed))
-    assert DU._equal(got[:-2], want)
+    assert L.names(learner)[-2:] == ["shuffle_base", "minibatch_idx"] and L.equal(got[:-2], want)
     assert torch.equal(got[-1], torch.stack(idx_rows)) and int(got[-2]) == KW["epochs"]
     # another seed is another shuffle
-    DU._restore(ro, start)
+    L.restore(ro, start)
     other = PPOLearner(ro, device_step=True, shuffle=True, shuffle_seed=2 ** 63 + 5, **KW)
     other.update()
     torch.cuda.synchronize()
@@ -122,80 +86,52 @@ def test_the_shuffled_device_update_is_the_hand_written_sequence_and_the_restate
 def test_shuffle_false_is_still_the_hand_written_sequence_on_tick_ranges(kind):
     from deep_rl_battlespace_amd.learner import PPOLearner
     ro = L.small_rollout(kind)
-    start = DU._keep(ro)
+    start = L.keep(ro)
     learner = PPOLearner(ro, device_step=True, shuffle=False, **KW)
     assert not hasattr(learner, "minibatch_idx") and len(learner._state()) == len(PPOLearner(ro, device_step=True, **KW)._state())
     learner.update()
-    got = DU._everything(learner)
-    DU._restore(ro, start)
-    assert DU._equal(got, _by_hand(ro, kind, lambda i: _tick_range(ro, i)))
+    got = L.everything(learner)
+    L.restore(ro, start)
+    assert L.equal(got, _by_hand(ro, kind, lambda i: _tick_range(ro, i)))
 
 
 @pytest.mark.parametrize("kind", ["gaussian", "categorical"])
 def test_the_torch_optimiser_path_shuffles_the_same_rows(kind):
     from deep_rl_battlespace_amd.learner import PPOLearner
     ro = L.small_rollout(kind)
-    start = DU._keep(ro)
+    start = L.keep(ro)
     device = PPOLearner(ro, device_step=True, shuffle=True, **KW)
     first = device.update()[0].clone()
-    DU._restore(ro, start)
+    L.restore(ro, start)
     plain = PPOLearner(ro, shuffle=True, **KW)
     stats = plain.update()
     torch.cuda.synchronize()
     assert torch.equal(stats[0], first)                                             # the same rows, the same blobs, the same head
     assert bool(torch.isfinite(stats).all()) and torch.equal(plain.minibatch_idx, device.minibatch_idx)
-    assert int(plain.shuffle_base) == KW["epochs"] and DU._blobs_are_packs(ro) and not torch.equal(DU._shared(ro)[0], start[0])
+    assert int(plain.shuffle_base) == KW["epochs"] and L.blobs_are_packs(ro) and not torch.equal(L.shared(ro)[0], start[0])
     plain.update()
     torch.cuda.synchronize()
     assert int(plain.shuffle_base) == 2 * KW["epochs"] and torch.equal(plain.minibatch_idx, _restated_idx(ro, ro.fused.seed, KW["epochs"]))
 
 
-def _held(learner):
-    out = DU._held(learner)
-    out.update({("gathered", k): v.data_ptr() for k, v in learner._gathered._asdict().items() if v is not None})
-    out.update(shuffle_base=learner.shuffle_base.data_ptr(), minibatch_idx=learner.minibatch_idx.data_ptr())
-    return out
-
-
 @pytest.mark.parametrize("kind", ["gaussian", "categorical"])
 def test_the_captured_shuffled_update_is_the_eager_one_draws_afresh_and_allocates_nothing(kind):
-    """Twin learners on one rollout, one eager, one captured; what they share is put back between their turns (the scheme of
-    tests/test_hip_ppo_device_update.py).  Each keeps its own shuffle_base: both advance by `epochs` per update."""
+    """Each twin keeps its own shuffle_base: both advance by `epochs` per update."""
     from deep_rl_battlespace_amd.learner import PPOLearner
     ro = L.small_rollout(kind)
-    eager, graph = (PPOLearner(ro, device_step=True, shuffle=True, **KW) for _ in range(2))
-    start, own = DU._keep(ro), _everything(graph)
-    assert graph.capture() is graph
-    assert DU._equal(_everything(graph), own) and int(graph.shuffle_base) == 0     # capture() itself moved nothing
     seen = []
-    for update in range(2):
-        eager.update()
-        a = _everything(eager)
-        DU._restore(ro, start)
-        graph.update()
-        b = _everything(graph)
-        assert DU._equal(a, b), update
+
+    def each(update, graph):
         assert int(graph.shuffle_base) == (update + 1) * KW["epochs"]
         assert torch.equal(graph.minibatch_idx, _restated_idx(ro, ro.fused.seed, update * KW["epochs"])), update
         seen.append(graph.minibatch_idx.clone())
-        assert DU._blobs_are_packs(ro)
-        ro.run()                                                                    # fresh records under the updated policy
-        start = DU._keep(ro)
+    eager, graph, start = L.eager_and_captured(ro, lambda: PPOLearner(ro, device_step=True, shuffle=True, **KW), each=each)
     assert not torch.equal(seen[0], seen[1])
-    # (garbage of earlier tests that the collector happens to free during an update would show as a change in memory_allocated)
-    gc.collect()
-    before, in_use = _held(graph), torch.cuda.memory_allocated()
-    graph.update()
-    torch.cuda.synchronize()
-    assert torch.cuda.memory_allocated() == in_use and _held(graph) == before
+    L.allocates_nothing(graph, warm=False)
     assert int(graph.shuffle_base) == 3 * KW["epochs"] and int(graph.step_count) == 3 * STEPS
     # the eager learner allocates nothing either from its second update on
-    DU._restore(ro, start)
-    gc.collect()
-    before, in_use = _held(eager), torch.cuda.memory_allocated()
-    eager.update()
-    torch.cuda.synchronize()
-    assert torch.cuda.memory_allocated() == in_use and _held(eager) == before
+    L.restore(ro, start)
+    L.allocates_nothing(eager, warm=False)
 
 
 @pytest.mark.parametrize("kind", ["gaussian", "categorical"])
@@ -206,12 +142,12 @@ def test_one_full_batch_step_sees_the_unshuffled_steps_rows_in_another_order(kin
     from deep_rl_battlespace_amd.learner import PPOLearner
     ro = L.small_rollout(kind)
     kw = dict(KW, epochs=1, minibatches=1)
-    start = DU._keep(ro)
+    start = L.keep(ro)
     plain, mixed = PPOLearner(ro, device_step=True, **kw), PPOLearner(ro, device_step=True, shuffle=True, **kw)
     R, A = ro.T * ro.obs.shape[1], ro.obs.shape[2]
     got = {}
     for name, learner in (("unshuffled", plain), ("shuffled", mixed)):
-        DU._restore(ro, start)
+        L.restore(ro, start)
         stats = learner.update().clone()
         b = learner._by_rows[R]
         torch.cuda.synchronize()
@@ -249,15 +185,9 @@ def test_a_scripted_opponents_agents_keep_every_bit_under_a_shuffled_update(kind
     from deep_rl_battlespace_amd.learner import PPOLearner
     n = 2
     ro = L.small_rollout(kind, n=n, opponent="blue")
-    scripted, learned = L.scripted_columns(n, "blue")
     learner = PPOLearner(ro, device_step=True, shuffle=True, **KW)
-    before = DU._everything(learner)
+    before = L.everything(learner)
     learner.update()
-    after = DU._everything(learner)
-    assert int(learner.step_count) == STEPS and int(learner.shuffle_base) == KW["epochs"] and DU._blobs_are_packs(ro)
-    per_agent = 22 + (1 if kind == "gaussian" else 0)                               # parameters, blobs[, log_std]: rows are agents
-    moments = (list(range(per_agent, per_agent + 4)) + list(range(per_agent + 7, len(before))))
-    for i in list(range(per_agent)) + moments:
-        bits = lambda x, cols: x[cols].contiguous().view(torch.int32)               # noqa: E731
-        assert torch.equal(bits(before[i], scripted), bits(after[i], scripted)), i
-        assert not torch.equal(bits(before[i], learned), bits(after[i], learned)), i
+    after = L.everything(learner)
+    assert int(learner.step_count) == STEPS and int(learner.shuffle_base) == KW["epochs"] and L.blobs_are_packs(ro)
+    L.scripted_keep_every_bit_and_learned_move(learner, before, after, *L.scripted_columns(n, "blue"))

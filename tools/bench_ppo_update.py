@@ -9,7 +9,7 @@ is a few back-to-back steps between two events.  Reported per path: the median, 
 (max - min) / median.
   head       (a) ppo_head alone, into given buffers, against (b) the torch loss from leaf tensors y, v (and log_std) to y.grad and v.grad --
              log_softmax / gather / exp / clamp / minimum / masking / sums and their autograd mirror, the form of
-             tests/test_hip_actor_grad.py::_ppo; the played actions (rec.argmax) are handed to the torch path ready-made.  Peak memory
+             tests/actor_grad_util.py::_ppo; the played actions (rec.argmax) are handed to the torch path ready-made.  Peak memory
              allocated by one step of each beyond what is held before it.  The fused head's traffic -- the bytes the algorithm moves
              (86 per element with v_old: 16 y + 16 rec + 5 x 4 + 1 mask, read; the mask once more by the count pass; 32 written) over its
              time -- next to bsx_gae's on the same card (19 bytes per element: rew, value, adv, ret, done, mask, and done once more)

@@ -41,7 +41,7 @@ def main():
     import test_hip_ppo_learner as M
     out = {
         "what": "tests/test_hip_ppo_learner.py on an MI355X: one PPOLearner minibatch over a PolicyRollout's own records against the float64 "
-                "torch loss (`_ppo` of tests/test_hip_actor_grad.py), and the records on the policy that played, per configuration; T = 8",
+                "torch loss (`_ppo` of tests/actor_grad_util.py), and the records on the policy that played, per configuration; T = 8",
         "bounds": "unchanged: per gradient tensor (2 x mean, 4 x max) of torch float32's own error (actor_grad_util.check), the loss and "
                   "log_std's gradient within 4 x torch's own error over 9 row orders; rows: kept >= 0.9 masked, kept >= 500, 5 % .. 60 % of "
                   "the kept rows clipped, at most KINK_CAP = 5 % of the masked rows near a ReLU kink -- on the float64 reference alone",
