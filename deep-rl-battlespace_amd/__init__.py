@@ -17,15 +17,19 @@ Only what the hot path needs lives here:
                  the fused clip + Adam + pack step that makes a whole update one graph, and its tied form for agents that share one
                  policy per team, and the same step for a network of any width with Polyak target networks kept in the same pass
                  (csrc/bsx_adam_step.hip),
-                 a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip)
+                 a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip),
+                 the critic join, TD head and action gradient of a DDPG update and DDPGLearner, the MADDPG update of a team from
+                 its replay ring as one graph (csrc/bsx_ddpg_head.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
 from . import advantage, envs, instinct, learner  # noqa: F401
 from .advantage import gae  # noqa: F401
-from .learner import (AdamState, Minibatch, PPOLearner, adam_step, categorical_log_prob, fused_apply, fused_mlp, is_tied, minibatch_gather, mlp_adam_step,  # noqa: F401
+from .learner import (TD_STATS, AdamState, DDPGLearner, Minibatch, PPOLearner, adam_step, ddpg_action_grad, ddpg_inputs, ddpg_put_actions, td_head,  # noqa: F401
+                      td_head_workspace_bytes, categorical_log_prob, fused_apply, fused_mlp, is_tied, minibatch_gather, mlp_adam_step,  # noqa: F401
                       mlp_adam_step_workspace_bytes, mlp_grad, ppo_head, share_group, shuffle_rows, tie_)
 from .envs.battle_env import parallel_env  # noqa: F401
 
-__all__ = ["AdamState", "Minibatch", "PPOLearner", "adam_step", "advantage", "categorical_log_prob", "envs", "fused_apply", "fused_mlp", "gae", "instinct", "is_tied", "learner",
-           "minibatch_gather", "mlp_adam_step", "mlp_adam_step_workspace_bytes", "mlp_grad", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "tie_"]
+__all__ = ["AdamState", "DDPGLearner", "Minibatch", "PPOLearner", "adam_step", "advantage", "categorical_log_prob", "ddpg_action_grad", "ddpg_inputs", "ddpg_put_actions", "envs", "fused_apply", "fused_mlp", "gae", "instinct", "is_tied", "learner",
+           "minibatch_gather", "mlp_adam_step", "mlp_adam_step_workspace_bytes", "mlp_grad", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "TD_STATS",
+           "td_head", "td_head_workspace_bytes", "tie_"]

@@ -91,6 +91,14 @@ class BsxAdamTargets(ctypes.Structure):
     _fields_ = [("net", BsxAdamTarget * 2)]
 
 
+class BsxDdpgBatch(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("obs", "obs_next", "act")]
+
+
+class BsxTdIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("q", "q_next", "rew", "done", "weight", "g_q", "g_pi", "td")]
+
+
 MINIBATCH_FIELDS = ("obs", "rec", "logp", "adv", "ret", "value", "mask")
 
 
@@ -164,6 +172,11 @@ SIGNATURES = {
     "bsx_adam_step_shared": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_adam_step_mlp_workspace_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_adam_step_mlp": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_int, c_int, ctypes.POINTER(BsxAdamTargets), c_void_p, c_void_p, c_void_p]),
+    "bsx_ddpg_inputs": (c_int, [ctypes.POINTER(BsxDdpgBatch), c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsx_ddpg_put_actions": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "bsx_td_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_td_head": (c_int, [ctypes.POINTER(BsxTdIo), c_int64, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "bsx_ddpg_action_grad": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
                                      c_void_p]),

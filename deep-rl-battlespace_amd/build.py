@@ -53,6 +53,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_ppo_head.hip"), []),
            # the optimiser step (clip + Adam + pack): float32 element-wise, held to a float64 reference; the blob it packs is bit copies
            (os.path.join(CSRC, "bsx_adam_step.hip"), []),
+           # between the MLP calls of a DDPG update: bit copies, and a TD head whose one multiply-add is an explicit fmaf
+           (os.path.join(CSRC, "bsx_ddpg_head.hip"), []),
            # the keyed row permutation and the minibatch gather: integer arithmetic and bit copies
            (os.path.join(CSRC, "bsx_shuffle.hip"), [])]
 

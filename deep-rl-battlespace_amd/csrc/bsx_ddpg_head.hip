@@ -1,0 +1,262 @@
+// bsx_ddpg_head.hip -- what lies between the fused MLP calls of a DDPG / MADDPG update (include/battlespace_hip.h: bsx_ddpg_*, bsx_td_head), gfx950.
+//
+// A sampled batch (obs, obs_next [B][nA][Do], act [B][nA][k]) becomes the critic's three inputs, a network's 4-wide output rows go into
+// a critic input's action columns, the critic's outputs become the TD target and both grad_out tensors, and the critic's input gradient
+// gives the actor's grad_out.  Row (b, i) of a critic input holds Dc floats:
+//   own      obs[b][i] (+) a[b][i]                                     Dc = Do + k
+//   central  obs[b][0] .. obs[b][nA-1] (+) a[b][0] .. a[b][nA-1]       Dc = nA (Do + k): the same row for every agent i of b
+//   1. inputs       one thread per float of x_cur: the batch's part of x_cur, x_next and x_pi, one launch;
+//   2. put_actions  one thread per (row, action slot): a 16-byte load of y4, k dword stores;
+//   3. td_head      one thread per element and tile of 256, J consecutive tiles per workgroup; the float32 terms of the statistics are
+//                   added in float64 per thread, then across the workgroup in a fixed order (bsx_block_sum.h), and stored to the
+//                   workspace; ONE workgroup adds the workgroups' partial rows in a fixed order and writes stats;
+//   4. action_grad  one thread per row: k dword loads of grad_x, a 16-byte store of g_a4.
+// Rows of 9, 24 or 45 floats are not 16-byte aligned: the critic inputs and grad_x are read and written by the dword; the 16-byte
+// accesses are those of the [..][4] tensors.  Every index is 64-bit: there is one path whatever the size.  No floating-point atomics,
+// no flags or spins; every grid is a function of the sizes alone: the same inputs give the same bits on every call.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "battlespace_hip.h"
+#include "bsx_args.h"
+#include "bsx_block_sum.h"
+
+namespace {
+
+constexpr int TPB = 256;
+constexpr int WAVES = TPB / 64;
+constexpr int MERGE_TPB = 1024;
+constexpr int64_t COPY_MAX_BLOCKS = 65536;     // the copy kernels stride over their elements beyond 2^24 threads
+constexpr int64_t HEAD_MAX_BLOCKS = 1024;      // the head: one tile per workgroup up to 1 024 workgroups (four per CU), then more tiles each
+constexpr int STAT_COLS = 8;                   // a partial row: 0 | w d^2 | q | y | |d| | done | w | 0
+constexpr int NS = 6;
+constexpr int MAX_DO = 3 * BSX_MAX_N + 2;      // an observation row of the widest team
+
+typedef float F4 __attribute__((ext_vector_type(4)));
+
+struct Shape {                                 // a checked (B, nA, Do, k, central)
+    int64_t B;
+    int nA, Do, k, central, Dc, W;             // W: the observation columns of a critic row (Do, or nA Do)
+};
+
+// the ranges every bsx_ddpg_* entry shares -> false for anything outside them, Dc > BSX_MLP_MAX_D (4v4 central: 72) included
+bool shape_of(int64_t B, int nA, int Do, int k, int central, Shape* s) {
+    if (B < 1 || B >= (INT64_C(1) << 31) || nA < 1 || nA > BSX_MAX_N || Do < 1 || Do > MAX_DO || (k != 3 && k != 4)) return false;
+    if (central != 0 && central != 1) return false;
+    const int Dc = central ? nA * (Do + k) : Do + k;
+    if (Dc > BSX_MLP_MAX_D) return false;
+    *s = Shape{B, nA, Do, k, central, Dc, central ? nA * Do : Do};
+    return true;
+}
+
+unsigned copy_blocks(int64_t threads) {
+    const int64_t b = (threads + TPB - 1) / TPB;
+    return unsigned(b < COPY_MAX_BLOCKS ? b : COPY_MAX_BLOCKS);
+}
+
+__global__ __launch_bounds__(TPB) void bsx_ddpg_inputs_kernel(const BsxDdpgBatch batch, const Shape s, float* x_cur, float* x_next, float* x_pi) {
+    const int64_t M = s.B * s.nA * s.Dc, stride = int64_t(gridDim.x) * TPB;
+    for (int64_t e = int64_t(blockIdx.x) * TPB + threadIdx.x; e < M; e += stride) {
+        const int64_t r = e / s.Dc, b = r / s.nA;
+        const int c = int(e - r * s.Dc);
+        const int64_t row = s.central ? b : r;                 // the batch row this critic row reads: its own, or the whole team's
+        const int slots = s.central ? s.nA : 1;
+        if (c < s.W) {
+            const int64_t src = row * s.W + c;
+            const float o = batch.obs[src];
+            x_cur[e] = o;
+            x_pi[e] = o;
+            x_next[e] = batch.obs_next[src];
+        } else {
+            const float a = batch.act[row * (slots * s.k) + (c - s.W)];
+            x_cur[e] = a;
+            if (s.central) x_pi[e] = a;                        // the other agents' slots keep the replayed actions (put_actions fills slot i)
+        }
+    }
+}
+
+// thread (r, slot): own, or central with own_only: slot = the row's own agent, one per row; central without: every slot of every row
+__global__ __launch_bounds__(TPB) void bsx_ddpg_put_actions_kernel(const float* y4, const Shape s, int every_slot, float* x) {
+    const int S = every_slot ? s.nA : 1;
+    const int64_t M = s.B * s.nA * S, stride = int64_t(gridDim.x) * TPB;
+    const F4* y = reinterpret_cast<const F4*>(y4);
+    for (int64_t e = int64_t(blockIdx.x) * TPB + threadIdx.x; e < M; e += stride) {
+        const int64_t r = e / S, b = r / s.nA;
+        const int i = int(r - b * s.nA), slot = every_slot ? int(e - r * S) : i;
+        const F4 a = y[s.central ? b * s.nA + slot : r];
+        float* dst = x + r * s.Dc + s.W + (s.central ? slot * s.k : 0);
+        dst[0] = a[0];
+        dst[1] = a[1];
+        dst[2] = a[2];
+        if (s.k == 4) dst[3] = a[3];
+    }
+}
+
+__global__ __launch_bounds__(TPB) void bsx_ddpg_action_grad_kernel(const float* gx, const Shape s, float* g_a4) {
+    const int64_t M = s.B * s.nA, stride = int64_t(gridDim.x) * TPB;
+    F4* g = reinterpret_cast<F4*>(g_a4);
+    for (int64_t r = int64_t(blockIdx.x) * TPB + threadIdx.x; r < M; r += stride) {
+        const int i = int(r % s.nA);
+        const float* src = gx + r * s.Dc + s.W + (s.central ? i * s.k : 0);
+        F4 a;
+        a[0] = src[0];
+        a[1] = src[1];
+        a[2] = src[2];
+        a[3] = s.k == 4 ? src[3] : 0.0f;
+        g[r] = a;
+    }
+}
+
+struct Plan {                                  // the head's launch shape: a function of (B, nA) alone
+    int64_t M, tiles, blocks;
+    int J;
+};
+
+Plan plan_of(int64_t B, int nA) {
+    Plan p;
+    p.M = B * nA;
+    p.tiles = (p.M + TPB - 1) / TPB;
+    const int64_t J = (p.tiles + HEAD_MAX_BLOCKS - 1) / HEAD_MAX_BLOCKS;
+    p.blocks = (p.tiles + J - 1) / J;
+    p.J = int(J);
+    return p;
+}
+
+struct HeadArgs {
+    BsxTdIo io;
+    int64_t M, tiles;
+    int J;
+    float gamma, s1, s2;                       // s1 = float(1.0 / B), s2 = float(2.0 / B)
+    double* part;                              // workspace: [blocks][STAT_COLS] partial rows
+};
+
+template <int WEIGHT>                          // 1: io.weight is given
+__global__ __launch_bounds__(TPB) void bsx_td_head_kernel(const HeadArgs p) {
+    __shared__ double s_w[NS][WAVES];
+    const int tid = threadIdx.x;
+    double acc[NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    F4* gq4 = reinterpret_cast<F4*>(p.io.g_q);
+    F4* gpi4 = reinterpret_cast<F4*>(p.io.g_pi);
+    const int64_t tile0 = int64_t(blockIdx.x) * p.J;
+    for (int j = 0; j < p.J; ++j) {
+        const int64_t tile = tile0 + j, i = tile * TPB + tid;
+        if (tile >= p.tiles || i >= p.M) continue;
+        const float q = p.io.q[i], rew = p.io.rew[i];
+        const bool over = p.io.done[i] != 0;
+        const float qn = over ? 0.0f : p.io.q_next[i];             // select, never multiply: a finished row's q_next stays out, NaN included
+        const float w = WEIGHT ? p.io.weight[i] : 1.0f;
+        const float y = fmaf(p.gamma, qn, rew);
+        const float d = q - y, wd = w * d;
+        F4 gq = F4(0.0f), gp = F4(0.0f);
+        gq[0] = wd * p.s2;
+        gp[0] = -(w * p.s1);
+        gq4[i] = gq;
+        gpi4[i] = gp;
+        if (p.io.td) p.io.td[i] = y;
+        acc[0] += double(wd * d);
+        acc[1] += double(q);
+        acc[2] += double(y);
+        acc[3] += double(fabsf(d));
+        acc[4] += over ? 1.0 : 0.0;
+        acc[5] += double(w);
+    }
+    double sum[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
+    if (tid < STAT_COLS) {
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
+        p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
+    }
+}
+
+// Q = 1024 / 8 threads per column; thread (q, c) adds the partial rows q, q + Q, .. in order; then 16 threads per column add every
+// 16th of those sums, and one thread the rest -- a fixed order throughout
+__global__ __launch_bounds__(MERGE_TPB) void bsx_td_merge_kernel(const double* part, int64_t blocks, int64_t M, double* stats) {
+    constexpr int C = STAT_COLS, Q = MERGE_TPB / C, G = 16;
+    __shared__ double s_q[MERGE_TPB], s_r[G * C];
+    const int tid = threadIdx.x, c = tid % C, q = tid / C;
+    double t = 0.0;
+    for (int64_t b = q; b < blocks; b += Q) t += part[b * C + c];
+    s_q[q * C + c] = t;
+    __syncthreads();
+    if (q < G) {
+        double u = 0.0;
+        for (int k = q; k < Q; k += G) u += s_q[k * C + c];
+        s_r[q * C + c] = u;
+    }
+    __syncthreads();
+    if (tid < C) {
+        double u = 0.0;
+        for (int k = 0; k < G; ++k) u += s_r[k * C + tid];
+        stats[tid] = tid == 0 ? double(M) : (tid == C - 1 ? 0.0 : u / double(M));
+    }
+}
+
+bool td_shape(int64_t B, int nA) { return B >= 1 && B < (INT64_C(1) << 31) && nA >= 1 && nA <= BSX_MAX_N; }
+
+}  // namespace
+
+extern "C" {
+
+int bsx_ddpg_inputs(const BsxDdpgBatch* batch, int64_t B, int nA, int Do, int k, int central, float* x_cur, float* x_next, float* x_pi,
+                    void* stream) {
+    Shape s;
+    if (!batch || !batch->obs || !batch->obs_next || !batch->act || !x_cur || !x_next || !x_pi) return BSX_E_ARG;
+    if (!shape_of(B, nA, Do, k, central, &s)) return BSX_E_ARG;
+    if (!aligned(batch->obs, 4) || !aligned(batch->obs_next, 4) || !aligned(batch->act, 4) || !aligned(x_cur, 4) || !aligned(x_next, 4) ||
+        !aligned(x_pi, 4))
+        return BSX_E_ALIGN;
+    hipLaunchKernelGGL(bsx_ddpg_inputs_kernel, dim3(copy_blocks(s.B * s.nA * s.Dc)), dim3(TPB), 0, static_cast<hipStream_t>(stream), *batch, s,
+                       x_cur, x_next, x_pi);
+    return int(hipGetLastError());
+}
+
+int bsx_ddpg_put_actions(const float* y4, int64_t B, int nA, int Do, int k, int central, int own_only, float* x, void* stream) {
+    Shape s;
+    if (!y4 || !x || (own_only != 0 && own_only != 1)) return BSX_E_ARG;
+    if (!shape_of(B, nA, Do, k, central, &s)) return BSX_E_ARG;
+    if (!aligned(y4, 16) || !aligned(x, 4)) return BSX_E_ALIGN;
+    const int every_slot = central && !own_only;
+    hipLaunchKernelGGL(bsx_ddpg_put_actions_kernel, dim3(copy_blocks(s.B * s.nA * (every_slot ? s.nA : 1))), dim3(TPB), 0,
+                       static_cast<hipStream_t>(stream), y4, s, every_slot, x);
+    return int(hipGetLastError());
+}
+
+int bsx_ddpg_action_grad(const float* gx, int64_t B, int nA, int Do, int k, int central, float* g_a4, void* stream) {
+    Shape s;
+    if (!gx || !g_a4) return BSX_E_ARG;
+    if (!shape_of(B, nA, Do, k, central, &s)) return BSX_E_ARG;
+    if (!aligned(g_a4, 16) || !aligned(gx, 4)) return BSX_E_ALIGN;
+    hipLaunchKernelGGL(bsx_ddpg_action_grad_kernel, dim3(copy_blocks(s.B * s.nA)), dim3(TPB), 0, static_cast<hipStream_t>(stream), gx, s, g_a4);
+    return int(hipGetLastError());
+}
+
+int bsx_td_head_workspace_bytes(int64_t B, int nA, size_t* bytes) {
+    if (!bytes || !td_shape(B, nA)) return BSX_E_ARG;
+    *bytes = size_t(plan_of(B, nA).blocks) * STAT_COLS * 8;
+    return 0;
+}
+
+int bsx_td_head(const BsxTdIo* io, int64_t B, int nA, float gamma, void* workspace, double* stats, void* stream) {
+    if (!io || !io->q || !io->q_next || !io->rew || !io->done || !io->g_q || !io->g_pi || !workspace || !stats) return BSX_E_ARG;
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return BSX_E_ARG;                   // NaN too
+    if (!td_shape(B, nA)) return BSX_E_ARG;
+    if (!aligned(io->g_q, 16) || !aligned(io->g_pi, 16)) return BSX_E_ALIGN;
+    if (!aligned(io->q, 4) || !aligned(io->q_next, 4) || !aligned(io->rew, 4) || !aligned(io->weight, 4) || !aligned(io->td, 4)) return BSX_E_ALIGN;
+    if (!aligned(workspace, 8) || !aligned(stats, 8)) return BSX_E_ALIGN;
+    const Plan p = plan_of(B, nA);
+    double* part = static_cast<double*>(workspace);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const HeadArgs a{*io, p.M, p.tiles, p.J, gamma, float(1.0 / double(B)), float(2.0 / double(B)), part};
+    if (io->weight) hipLaunchKernelGGL(bsx_td_head_kernel<1>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
+    else hipLaunchKernelGGL(bsx_td_head_kernel<0>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
+    if (const hipError_t e = hipGetLastError()) return int(e);
+    hipLaunchKernelGGL(bsx_td_merge_kernel, dim3(1), dim3(MERGE_TPB), 0, s, static_cast<const double*>(part), p.blocks, p.M, stats);
+    return int(hipGetLastError());
+}
+
+}  // extern "C"

@@ -696,6 +696,85 @@ int bsx_adam_step_mlp_workspace_bytes(int A, int nets, size_t* bytes);
 int bsx_adam_step_mlp(const BsxAdamIo* io, int A, int D, int group, const BsxAdamTargets* targets, void* workspace, double* stats,
                       void* stream);
 
+/* ---- between the fused MLP calls of a DDPG / MADDPG update (deep-rl-battlespace_amd/learner.py: ddpg_inputs, ddpg_put_actions, td_head,
+ * ddpg_action_grad, DDPGLearner; csrc/bsx_ddpg_head.hip): the critic's inputs from a sampled batch, a network's actions into them, the
+ * TD target with both grad_out tensors, and the actor's grad_out from the critic's input gradient.  Common to the entries:
+ *   B        batch rows, 1 <= B < 2^31;   nA  the team's agents, 1 .. BSX_MAX_N;   Do  observation floats, 1 .. 3 * BSX_MAX_N + 2;
+ *   k        action columns, 3 or 4;   central  0 or 1
+ *   Dc       the critic's input width: Do + k (central = 0: every agent's critic on its own observation and action) or nA (Do + k)
+ *            (central = 1: on the team's joint observation and action).  Dc <= BSX_MLP_MAX_D: up to 3v3 central (9, 24, 45 inputs);
+ *            4v4 central (72) is refused
+ *   row (b, i) of a critic input [B][nA][Dc]:   own      obs[b][i] (+) a[b][i]
+ *                                               central  obs[b][0] .. obs[b][nA-1] (+) a[b][0] .. a[b][nA-1]   (the same for every i)
+ * Every array is contiguous float32 unless said otherwise; the [..][4] ones are 16-byte aligned, the others 4-byte (rows of 9, 24 or 45
+ * floats are not 16-byte aligned: they are read and written by the dword).  Every launch goes on `stream`; no host synchronisation, no
+ * floating-point atomics, flags or spins; every grid is a function of the sizes alone: the same inputs give the same bits on every call.
+ * Every refusal happens before any launch: BSX_E_ARG for a null pointer or a size out of range (Dc > BSX_MLP_MAX_D included), then
+ * BSX_E_ALIGN.
+ *
+ * bsx_ddpg_inputs: everything that comes from the sampled batch alone, one launch.
+ *   batch    obs, obs_next [B][nA][Do], act [B][nA][k]  (bsx_replay_sample's)
+ *   x_cur    [B][nA][Dc] (out, written whole): the observations with the replayed actions
+ *   x_next   [B][nA][Dc] (out): its observation columns from obs_next; its action columns are left as they are
+ *   x_pi     [B][nA][Dc] (out): its observation columns from obs; central = 1: every action slot from act (the replayed actions);
+ *            central = 0: its action columns are left as they are */
+typedef struct BsxDdpgBatch {
+    const float* obs;
+    const float* obs_next;
+    const float* act;
+} BsxDdpgBatch;
+int bsx_ddpg_inputs(const BsxDdpgBatch* batch, int64_t B, int nA, int Do, int k, int central, float* x_cur, float* x_next, float* x_pi,
+                    void* stream);
+
+/* The first k columns of a network's output rows y4 [B][nA][4] (bsx_mlp_forward's y) into the action columns of x [B][nA][Dc], one
+ * launch; nothing else of x is written.
+ *   own_only = 0   row (b, i) receives the actions of all agents of row b, agent j's into slot j: the target actors' actions into x_next
+ *   own_only = 1   row (b, i) receives agent i's action alone, into slot i: pi_i(o_i) into x_pi, whose other slots keep the replayed
+ *                  actions -- MADDPG's policy gradient as Lowe et al. state it
+ * With central = 0 a row has one slot and the two are the same.  BSX_E_ARG also for an own_only other than 0 / 1. */
+int bsx_ddpg_put_actions(const float* y4, int64_t B, int nA, int Do, int k, int central, int own_only, float* x, void* stream);
+
+/* The TD target and both grad_out tensors from the critic's outputs, one pass (two launches).
+ *   q, q_next, rew   [B][nA]: the critic on x_cur, the target critic on x_next (raw heads), the batch's rewards
+ *   done     uint8 [B][nA], 1-byte aligned (any non-zero byte counts)
+ *   weight   [B][nA] or NULL = 1 for every element (the hook of a prioritised sampler)
+ *   g_q, g_pi  [B][nA][4] (out, overwritten everywhere);   td  [B][nA] (out) or NULL */
+typedef struct BsxTdIo {
+    const float* q;
+    const float* q_next;
+    const float* rew;
+    const uint8_t* done;
+    const float* weight;
+    float* g_q;
+    float* g_pi;
+    float* td;
+} BsxTdIo;
+
+/* Size of bsx_td_head's workspace: 64 bytes per workgroup of the head pass.  BSX_E_ARG: null bytes, B or nA out of range. */
+int bsx_td_head_workspace_bytes(int64_t B, int nA, size_t* bytes);
+
+/* Per element, in float32, with w = weight or 1, s1 = float(1.0 / B) and s2 = float(2.0 / B) (formed in float64, rounded once):
+ *   qn = done ? 0 : q_next       (selected, never multiplied: a finished row's q_next stays out, NaN and infinities included)
+ *   y  = fmaf(gamma, qn, rew),   d = q - y
+ *   g_q[0]  = (w * d) * s2       g_pi[0] = -(w * s1)       td = y;       columns 1 .. 3 of g_q and g_pi are +0
+ * g_q is the critic's grad_out (squash = 0) for the sum over agents of mean_b w (Q - y)^2, y held fixed; g_pi seeds the critic's
+ * input-gradient pass for the sum over agents of -mean_b w Q.
+ * stats[8] (device, float64): n = B nA, then the means over the n elements -- float64 sums of the float32 per-element terms, divided by n --
+ * of (w * d) * d, q, y, |d|, done != 0 and w; stats[7] = 0.
+ * Launches: the head pass -- a workgroup takes J consecutive tiles of 256 elements, one thread per element, J = 1 up to 1 024 tiles and
+ * ceil(tiles / 1 024) beyond; it adds its terms per thread over the tiles, then over the workgroup in a fixed order, and stores them to
+ * the workspace --, then one workgroup that adds those partial rows in a fixed order.
+ * workspace: 8-byte aligned, at least bsx_td_head_workspace_bytes(B, nA), not in use by another call in flight; stats: 8-byte aligned.
+ * Refusals, before any launch, in this order: BSX_E_ARG for a null io, q, q_next, rew, done, g_q, g_pi, workspace or stats; a gamma
+ * outside [0, 1] (NaN too); B or nA out of range.  Then BSX_E_ALIGN for g_q or g_pi off a 16-byte boundary; q, q_next, rew, weight or
+ * td off a 4-byte one; workspace or stats off an 8-byte one. */
+int bsx_td_head(const BsxTdIo* io, int64_t B, int nA, float gamma, void* workspace, double* stats, void* stream);
+
+/* The actor's grad_out from the critic's input gradient, one launch: agent i's own k action columns of row (b, i) of gx [B][nA][Dc]
+ * (bsx_mlp_grad's grad_x on x_pi) -- they start at column Do (central = 0) or nA Do + i k (central = 1) -- into g_a4 [B][nA][4] (out,
+ * overwritten everywhere; column 3 is +0 when k = 3): bsx_mlp_grad's grad_out for the actor (squash = 1). */
+int bsx_ddpg_action_grad(const float* gx, int64_t B, int nA, int Do, int k, int central, float* g_a4, void* stream);
+
 /* ---- shuffled minibatches (deep-rl-battlespace_amd/learner.py: shuffle_rows, minibatch_gather, PPOLearner(shuffle=True);
  * csrc/bsx_shuffle.hip): a keyed permutation of the N = T x E rows of a rollout, evaluated per position -- O(1), no sort, no workspace,
  * no atomics --, and the gather of one minibatch's rows through it.

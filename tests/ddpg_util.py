@@ -1,0 +1,485 @@
+"""What the tests of the DDPG head kernels (csrc/bsx_ddpg_head.hip: learner.ddpg_inputs, ddpg_put_actions, td_head, ddpg_action_grad)
+and of DDPGLearner share:
+
+  SHAPES / plan      (B, nA, Do, k, central) at the smallest sizes each mechanism can go wrong at; the head's launch plan restated
+  join, ref_inputs, ref_put_actions, ref_action_grad, ref_td_head   the contracts of include/battlespace_hip.h restated in numpy: the
+                     three copies on arrays of any dtype (they move bits), the TD head in float64
+  td_inputs / torch_td / td_case / check_td   the TD head's inputs (rounded to float32 once), the head as a torch user writes it with
+                     autograd from q -- in float64 the check of the restatement, in float32 the yardstick --, both cached per shape, and
+                     the bounds: (2 x mean, 4 x max) of the yardstick's error for g_q, g_pi and td (actor_ref_util.F32_FACTORS; a wider
+                     factor only where profiles/ddpg_float64.json records one and why), stats within 4 x the yardstick's own error over
+                     9 row orders, at least half a float32 spacing
+  learner_case       networks (mlp_grad_util.make_net "gains", w3 scaled by 60 and 100 as mlp_grad_util.ddpg_case does), ring rows, a
+                     fixed batch and the row weights that leave every ReLU kink out, chosen in float64 alone
+  maddpg_grads       the critic's and the actor's gradients of the two MADDPG losses by torch autograd on the CPU, in any dtype
+  Hand               one update by hand from the public primitives, holding what a DDPGLearner holds under the same names
+  snapshot           every tensor an update writes, as bits
+  torch_update       the torch composition: StackedActor under autograd, clip_grad_norm_, torch Adam, foreach Polyak
+  bandit / reward    the learning check's ring and its held-out reward
+
+Nothing here imports the native library at import time."""
+import copy
+import functools
+import json
+import os
+
+import numpy as np
+import torch
+
+import actor_grad_util as U
+import actor_ref_util as R
+import mlp_grad_util as M
+
+PARAMS = U.PARAMS
+FM, FX = R.F32_FACTORS
+PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ddpg_float64.json")
+# (B, nA, Do, k, central).  The last: 16 385 x 16 = 262 160 elements = 1 025 tiles of 256, the first B at nA = 16 at which a workgroup of
+# the head pass takes two tiles (J = 2: 513 workgroups), and the merge's 128 threads per column go round their partial rows five times
+SHAPES = ((1, 1, 1, 3, 0), (97, 1, 5, 3, 0), (97, 1, 5, 3, 1), (161, 2, 8, 4, 1), (129, 3, 11, 4, 1), (130, 16, 50, 4, 0), (64, 2, 5, 3, 1),
+          (16385, 16, 1, 3, 0))
+LARGE = SHAPES[-1]
+LEARNER_SHAPES = ((64, 2, 5, 4, 0), (161, 2, 8, 4, 1), (129, 3, 11, 4, 1))
+KINK_SHAPES = ((161, 2, 8, 4), (129, 3, 11, 4), (97, 1, 5, 3), (130, 16, 50, 4))
+GAMMA = 0.95
+# learner_case's generators start here.  Picked on the float64 reference alone: the share of elements the kink filter leaves out moves
+# between 0.6 % and 5.7 % from seed to seed (384 hidden values per element, each within 1e-4 of 0 with probability ~1e-4); of the bases
+# 0, 10, 20, 30 this is the one at which seeds 0 .. 2 stay under actor_grad_util.KINK_CAP at every shape of KINK_SHAPES (1.0 % .. 4.4 %)
+CASE_SEED = 30
+TD_NAMES = ("g_q", "g_pi", "td")
+STAT_NAMES = ("critic_loss", "q", "target", "abs_td", "done", "weight")       # stats[1..6]
+
+
+def shape_id(s):
+    return "B%d-nA%d-Do%d-k%d-%s" % (*s[:4], "central" if s[4] else "own")
+
+
+def width(nA, Do, k, central):
+    return nA * (Do + k) if central else Do + k
+
+
+def plan(B, nA):
+    """(tiles, tiles per workgroup J, workgroups, rounds of the merge) of bsx_td_head, as the header states them."""
+    tiles = -(-B * nA // 256)
+    J = -(-tiles // 1024)
+    blocks = -(-tiles // J)
+    return tiles, J, blocks, -(-blocks // 128)
+
+
+# ------------------------------------------------------------------------------------------------ the three copies
+def join(obs, act, central):
+    """obs [B, nA, Do], act [B, nA, k] -> the critic input [B, nA, Dc] (a new array of obs's dtype)."""
+    if not central:
+        return np.concatenate([obs, act], -1)
+    B, nA, _ = obs.shape
+    row = np.concatenate([obs.reshape(B, -1), act.reshape(B, -1)], -1)
+    return np.repeat(row[:, None, :], nA, axis=1)
+
+
+def ref_inputs(obs, obs_next, act, central, x_cur, x_next, x_pi):
+    """bsx_ddpg_inputs on what the three outputs held before -> new (x_cur, x_next, x_pi)."""
+    nA, Do = obs.shape[1:]
+    W = nA * Do if central else Do
+    cur, nxt = join(obs, act, central), join(obs_next, act, central)
+    x_next, x_pi = x_next.copy(), x_pi.copy()
+    x_next[..., :W] = nxt[..., :W]
+    x_pi[..., :W] = cur[..., :W]
+    if central:
+        x_pi[..., W:] = cur[..., W:]
+    return cur, x_next, x_pi
+
+
+def ref_put_actions(y4, x, Do, k, central, own_only):
+    """bsx_ddpg_put_actions -> a new x."""
+    B, nA, _ = y4.shape
+    x = x.copy()
+    if not central:
+        x[..., Do:Do + k] = y4[..., :k]
+    elif not own_only:
+        x[..., nA * Do:] = y4[:, None, :, :k].reshape(B, 1, nA * k)
+    else:
+        for i in range(nA):
+            x[:, i, nA * Do + i * k:nA * Do + (i + 1) * k] = y4[:, i, :k]
+    return x
+
+
+def ref_action_grad(gx, Do, k, central):
+    """bsx_ddpg_action_grad -> g_a4 [B, nA, 4] of gx's dtype; column 3 is +0 with three actions."""
+    B, nA, _ = gx.shape
+    out = np.zeros((B, nA, 4), gx.dtype)
+    for i in range(nA):
+        c0 = nA * Do + i * k if central else Do
+        out[:, i, :k] = gx[:, i, c0:c0 + k]
+    return out
+
+
+def batch_arrays(shape, seed=0):
+    """(obs, obs_next, act) float32 numpy of a shape, standard normals."""
+    B, nA, Do, k, _ = shape
+    g = np.random.default_rng(100 + seed)
+    return tuple(g.standard_normal(s).astype(np.float32) for s in ((B, nA, Do), (B, nA, Do), (B, nA, k)))
+
+
+# ------------------------------------------------------------------------------------------------ the TD head
+def ref_td_head(inp, gamma=GAMMA, weight=True):
+    """The contract in float64 numpy -> dict(g_q, g_pi [B, nA, 4], td [B, nA], stats [8]).  inp: td_inputs'; weight=False: w = 1."""
+    f = {k: v.double().numpy() for k, v in inp.items()}
+    B, nA = f["q"].shape
+    over = f["done"] != 0
+    w = f["weight"] if weight else np.ones((B, nA))
+    with np.errstate(all="ignore"):
+        y = gamma * np.where(over, 0.0, f["q_next"]) + f["rew"]
+    d = f["q"] - y
+    g_q, g_pi = np.zeros((B, nA, 4)), np.zeros((B, nA, 4))
+    g_q[..., 0] = w * d * (2.0 / B)
+    g_pi[..., 0] = -w * (1.0 / B)
+    n = float(B * nA)
+    stats = np.array([n, (w * d * d).sum() / n, f["q"].sum() / n, y.sum() / n, np.abs(d).sum() / n, over.sum() / n, w.sum() / n, 0.0])
+    return dict(g_q=g_q, g_pi=g_pi, td=y, stats=stats)
+
+
+def td_inputs(B, nA, seed=0):
+    """{q, q_next, rew, weight: float32, done: uint8} CPU tensors [B, nA]: normals, done Bernoulli 0.2, weights uniform in [0.5, 1.5]."""
+    g = torch.Generator().manual_seed(8000 + seed + 7 * B + nA)
+    rnd = lambda: torch.randn((B, nA), generator=g)           # noqa: E731
+    return dict(q=rnd(), q_next=rnd(), rew=rnd(), done=(torch.rand((B, nA), generator=g) < 0.2).to(torch.uint8),
+                weight=torch.rand((B, nA), generator=g) + 0.5)
+
+
+def torch_td(inp, dtype, gamma=GAMMA, weight=True, perm=None):
+    """The head as a torch user writes it, on the CPU in `dtype`, with autograd from q -> dict of float64 numpy (g_q and g_pi padded to
+    4 columns; the statistics computed in `dtype`).  perm: the rows in another order (the gradients come back in the original one)."""
+    t = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in inp.items()}
+    if perm is not None:
+        t = {k: v[perm] for k, v in t.items()}
+    q, q_pi = t["q"].clone().requires_grad_(), t["q"].clone().requires_grad_()
+    w = t["weight"] if weight else torch.ones_like(t["q"])
+    y = t["rew"] + gamma * (1.0 - t["done"].to(dtype)) * t["q_next"]
+    critic_loss = (w * (q - y) ** 2).mean(0).sum()
+    actor_loss = -(w * q_pi).mean(0).sum()
+    critic_loss.backward()
+    actor_loss.backward()
+    g_q, g_pi = torch.zeros((*q.shape, 4), dtype=dtype), torch.zeros((*q.shape, 4), dtype=dtype)
+    g_q[..., 0], g_pi[..., 0] = q.grad, q_pi.grad
+    td = y
+    if perm is not None:
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(perm.numel())
+        g_q, g_pi, td = g_q[inv], g_pi[inv], td[inv]
+    with torch.no_grad():
+        d = q - y
+        num = lambda x: float(x.double())                     # noqa: E731
+        stats = np.array([float(q.numel()), num((w * d * d).mean()), num(q.mean()), num(y.mean()), num(d.abs().mean()),
+                          num(t["done"].to(dtype).mean()), num(w.mean()), 0.0])
+    return dict(g_q=g_q.double().numpy(), g_pi=g_pi.double().numpy(), td=td.detach().double().numpy(), stats=stats)
+
+
+@functools.lru_cache(maxsize=None)
+def td_case(B, nA, weight=True, perms=8):
+    """(inputs, float64 reference, float32 yardstick, the yardstick's own error on stats [8]: the largest over the given order and
+    `perms` permutations of the rows).  Computed once and shared: read-only."""
+    inp = td_inputs(B, nA)
+    ref, yard = ref_td_head(inp, weight=weight), torch_td(inp, torch.float32, weight=weight)
+    e_stats = np.abs(yard["stats"] - ref["stats"])
+    for p in range(perms if B > 1 else 0):
+        r = torch_td(inp, torch.float32, weight=weight, perm=torch.randperm(B, generator=torch.Generator().manual_seed(4000 + p)))
+        e_stats = np.maximum(e_stats, np.abs(r["stats"] - ref["stats"]))
+    return inp, ref, yard, e_stats
+
+
+@functools.lru_cache(maxsize=None)
+def factors():
+    """{tensor: (mean factor, max factor)}: the project's (2, 4), or what profiles/ddpg_float64.json records for a tensor (with why)."""
+    out = {k: (FM, FX) for k in TD_NAMES}
+    if os.path.exists(PROFILE):
+        for k, v in json.load(open(PROFILE)).get("factors", {}).items():
+            out[k] = tuple(v)
+    return out
+
+
+def check_td(got, ref, yard, e_stats, what=""):
+    """got: dict(g_q, g_pi, td, stats) of float64 numpy from the kernel.  Prints every figure, then asserts."""
+    bad = []
+    for k in TD_NAMES:
+        ek, et = np.abs(got[k] - ref[k]), np.abs(yard[k] - ref[k])
+        fm, fx = factors()[k]
+        print(f"{what} {k}: kernel mean / max error {ek.mean():.3e} / {ek.max():.3e}, yardstick {et.mean():.3e} / {et.max():.3e} "
+              f"(factors {fm}, {fx}); max|x| {np.abs(ref[k]).max():.3e}")
+        if not (ek.mean() <= fm * et.mean() and ek.max() <= fx * et.max()):
+            bad.append(k)
+    if not (got["stats"][0] == ref["stats"][0] and got["stats"][7] == 0.0):
+        bad.append("n")
+    for i, name in enumerate(STAT_NAMES, start=1):
+        tol = 4 * max(e_stats[i], 0.5 * float(np.spacing(np.float32(abs(ref["stats"][i])))))
+        err = abs(got["stats"][i] - ref["stats"][i])
+        print(f"{what} stats.{name}: float64 {ref['stats'][i]:.9g}, kernel error {err:.3e}, yardstick's own (9 row orders) {e_stats[i]:.3e}, bound {tol:.3e}")
+        if not err <= tol:
+            bad.append(name)
+    assert not bad, (what, bad)
+
+
+# ------------------------------------------------------------------------------------------------ the learner's case
+def ring_rows(N, nA, Do, k, seed=0, done_share=0.2):
+    """(obs, act, rew, obs_next, done) of N transitions, CPU float32 / bool: observations and actions uniform in [-1, 1], rewards normal."""
+    g = torch.Generator().manual_seed(9000 + seed + 13 * N + nA)
+    uni = lambda *s: torch.rand(s, generator=g) * 2 - 1       # noqa: E731
+    return uni(N, nA, Do), uni(N, nA, k), torch.randn((N, nA), generator=g), uni(N, nA, Do), torch.rand((N, nA), generator=g) < done_share
+
+
+def make_nets(nA, Do, k, central, seed=0):
+    """(actor, critic) on the CPU: mlp_grad_util.make_net "gains", head weights scaled to sums of order 1 as mlp_grad_util.ddpg_case does."""
+    actor, critic = M.make_net(nA, Do, k, "gains", seed + 1), M.make_net(nA, width(nA, Do, k, central), 1, "gains", seed + 2)
+    with torch.no_grad():
+        critic.w3.mul_(100.0); actor.w3.mul_(60.0)
+    return actor, critic
+
+
+def _t(x):
+    return torch.from_numpy(np.ascontiguousarray(x))
+
+
+def joins64(actor, obs, obs_next, act, central, target_actor=None):
+    """(x_cur, x_next, x_pi) float64 tensors [B, nA, Dc] of a batch in float64: a' from target_actor (the actor itself if none)."""
+    nA, Do = obs.shape[1:]
+    k = act.shape[2]
+    a64, t64 = R.to_float64(actor), R.to_float64(target_actor if target_actor is not None else actor)
+    with torch.no_grad():
+        pi, a_next = a64(obs.double()).numpy(), t64(obs_next.double()).numpy()
+    o, o2, a = obs.double().numpy(), obs_next.double().numpy(), act.double().numpy()
+    pad = lambda y: np.concatenate([y, np.zeros((*y.shape[:2], 4 - k))], -1)       # noqa: E731
+    x_cur = join(o, a, central)
+    x_next = ref_put_actions(pad(a_next), join(o2, a, central), Do, k, central, False)
+    x_pi = ref_put_actions(pad(pi), x_cur, Do, k, central, True)
+    return _t(x_cur), _t(x_next), _t(x_pi)
+
+
+@functools.lru_cache(maxsize=None)
+def learner_case(shape, seed=0):
+    """(actor, critic, rows, idx, w, share) of a learner shape: the networks, N = 4 B ring rows, the B fixed row indices of the first
+    batch, and w [B, nA]: standard normal row weights, 0 where, in float64, a pre-ReLU value is within actor_grad_util.KINK of 0 -- the
+    critic's at x_cur and at x_pi, the actor's at obs; share: the part of the elements left out.  Read-only."""
+    B, nA, Do, k, central = shape
+    seed += CASE_SEED
+    actor, critic = make_nets(nA, Do, k, central, seed)
+    rows = ring_rows(4 * B, nA, Do, k, seed)
+    g = torch.Generator().manual_seed(9500 + seed)
+    idx = torch.randint(0, 4 * B, (B,), generator=g)
+    obs, act, _, obs_next, _ = (r[idx] for r in rows)
+    x_cur, _, x_pi = joins64(actor, obs, obs_next, act, central)
+    near = (U.pre_relu64(actor, obs).abs() < U.KINK).any(-1) | (U.pre_relu64(critic, x_cur).abs() < U.KINK).any(-1) | \
+        (U.pre_relu64(critic, x_pi).abs() < U.KINK).any(-1)
+    near = near.transpose(0, 1)                                   # [B, nA]
+    w = torch.randn((B, nA), generator=g)
+    w[near] = 0.0
+    return actor, critic, rows, idx, w, float(near.double().mean())
+
+
+def maddpg_grads(actor, critic, batch, w, central, dtype, gamma=GAMMA, target_actor=None, target_critic=None):
+    """({critic tensor: grad}, {actor tensor: grad}) as float64 arrays, torch autograd on the CPU in `dtype`, of
+        critic:  sum_i mean_b w (Q_i(x_cur) - y)^2,  y = r + gamma (1 - done) Q'_i(x_next) held fixed, a' = the target actors' actions
+        actor:   sum_i -mean_b w Q_i(x_pi),  x_pi = x_cur with agent i's own action slot replaced by pi_i(o_i)
+    batch: (obs, act, rew, obs_next, done) of B rows; the targets default to the networks themselves."""
+    def to(net):
+        a = R._new(net.n_actors, net.obs_len, net.n_actions, dtype=dtype)
+        with torch.no_grad():
+            for p in PARAMS:
+                getattr(a, p).copy_(getattr(net, p).detach().cpu().to(dtype))
+        return a
+    a, c = to(actor), to(critic)
+    ta, tc = to(target_actor if target_actor is not None else actor), to(target_critic if target_critic is not None else critic)
+    obs, act, rew, obs_next = (t.detach().cpu().to(dtype) for t in (batch[0], batch[1], batch[2], batch[3]))
+    notdone, w = 1.0 - batch[4].detach().cpu().to(dtype), w.detach().cpu().to(dtype)
+    B, nA, k = act.shape
+
+    def joined(o, actions):
+        if not central:
+            return torch.cat([o, actions], -1)
+        return torch.cat([o.reshape(B, 1, -1), actions.reshape(B, 1, -1)], -1).expand(B, nA, -1)
+    with torch.no_grad():
+        y = rew + gamma * notdone * tc(joined(obs_next, ta(obs_next)), squash=False)[..., 0]
+    critic_loss = (w * (c(joined(obs, act), squash=False)[..., 0] - y) ** 2).mean(0).sum()
+    gc = torch.autograd.grad(critic_loss, [getattr(c, p) for p in PARAMS])
+    pi = a(obs)
+    if central:                                                    # row (b, i): the replayed actions with slot i replaced by pi_i(o_i)
+        own = torch.eye(nA, dtype=dtype).view(1, nA, nA, 1)
+        actions = own * pi.unsqueeze(1) + (1.0 - own) * act.unsqueeze(1)              # [B, i, slot, k]
+        x_pi = torch.cat([obs.reshape(B, 1, -1).expand(B, nA, -1), actions.reshape(B, nA, nA * k)], -1)
+    else:
+        x_pi = torch.cat([obs, pi], -1)
+    actor_loss = -(w * c(x_pi, squash=False)[..., 0]).mean(0).sum()
+    ga = torch.autograd.grad(actor_loss, [getattr(a, p) for p in PARAMS])
+    num = lambda gs: {p: g.double().numpy() for p, g in zip(PARAMS, gs)}            # noqa: E731
+    return num(gc), num(ga)
+
+
+# ------------------------------------------------------------------------------------------------ one update by hand
+STATE = ("_blob_a", "_blob_c", "_blob_ta", "_blob_tc", "step_actor", "step_critic", "stats", "step_stats_actor", "step_stats_critic")
+
+
+def snapshot(x):
+    """{name: bits} of everything an update of x (a DDPGLearner or a Hand) writes that outlives it, the ring's draw counter included."""
+    torch.cuda.synchronize()
+    out = {k: getattr(x, k).detach().clone() for k in STATE}
+    out["draws"] = x.buffer._draws.clone()
+    for name in ("actor", "critic", "target_actor", "target_critic"):
+        for p in PARAMS:
+            out[f"{name}.{p}"] = getattr(getattr(x, name), p).detach().view(torch.int32).clone()
+    for name in ("adam_actor", "adam_critic"):
+        out[name + ".m"], out[name + ".v"] = (t.view(torch.int32).clone() for t in (getattr(x, name).m, getattr(x, name).v))
+    return {k: (v.view(torch.int32) if v.dtype == torch.float32 else v.view(torch.int64) if v.dtype == torch.float64 else v) for k, v in out.items()}
+
+
+def differing(a, b):
+    return [k for k in a if not torch.equal(a[k], b[k])]
+
+
+class Hand:
+    """What a DDPGLearner holds, under the same names, and its update written out with the public primitives alone: the ring's
+    sample(), ddpg_inputs, bsx_mlp_forward, ddpg_put_actions, td_head, mlp_grad (its padded copy of grad_out included), mlp_adam_step,
+    ddpg_action_grad."""
+
+    def __init__(self, buffer, actor, critic, central, gamma=GAMMA, tau=0.01, lr_actor=1e-3, lr_critic=1e-3, max_grad_norm=None, updates=1):
+        from deep_rl_battlespace_amd import learner as L
+        self.buffer, self.actor, self.critic, self.central, self.gamma = buffer, actor, critic, bool(central), gamma
+        self.target_actor, self.target_critic = copy.deepcopy(actor), copy.deepcopy(critic)
+        for t in (self.target_actor, self.target_critic):
+            t.__dict__.pop("_bsx_mlp_buffers", None)
+        self._blob_a, self._blob_c, self._blob_ta, self._blob_tc = (n.pack() for n in (actor, critic, self.target_actor, self.target_critic))
+        dev = actor.w1.device
+        self.adam_actor, self.adam_critic = L.AdamState(actor), L.AdamState(critic)
+        self.hyper_actor = L.adam_hyper(lr_actor, max_grad_norm=max_grad_norm, device=dev, tau=tau)
+        self.hyper_critic = L.adam_hyper(lr_critic, max_grad_norm=max_grad_norm, device=dev, tau=tau)
+        self.step_actor, self.step_critic = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
+        self.stats = torch.zeros((updates, 8), dtype=torch.float64, device=dev)
+        self.step_stats_actor, self.step_stats_critic = (torch.zeros((updates, 4), dtype=torch.float64, device=dev) for _ in range(2))
+        self.updates = updates
+
+    def update(self):
+        for u in range(self.updates):
+            s = self.buffer.sample()
+            self.step(s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6], u)
+        return self.stats
+
+    def step(self, obs, act, rew, obs_next, done, u, weight=None, adam=True):
+        """The ten steps on a batch -> (critic row, actor row): copies of mlp_grad's cached rows."""
+        from deep_rl_battlespace_amd import _lib, learner as L
+        lib, c = _lib.load(), self.central
+        obs, act, obs_next = obs.contiguous(), act.contiguous(), obs_next.contiguous()
+        (B, nA, Do), k, dev = obs.shape, act.shape[2], obs.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def forward(blob, x, raw=False):
+            y4 = torch.empty((B, nA, 4), device=dev)
+            r = torch.empty((B, nA), device=dev) if raw else None
+            _lib.check(lib.bsx_mlp_forward(blob.data_ptr(), x.data_ptr(), y4.data_ptr(), r.data_ptr() if raw else None, B, nA, x.shape[2], stream),
+                       "bsx_mlp_forward")
+            return r if raw else y4
+        x_cur, x_next, x_pi = L.ddpg_inputs(obs, obs_next, act, central=c)
+        L.ddpg_put_actions(forward(self._blob_ta, obs_next), x_next, Do, k, central=c, own_only=False)
+        q_next, q = forward(self._blob_tc, x_next, True), forward(self._blob_c, x_cur, True)
+        head = L.td_head(q, q_next, rew, done, self.gamma, weight=weight)
+        self.stats[u].copy_(head.stats)
+        row_c = L.mlp_grad(self.critic, self._blob_c, x_cur, head.g_q[..., :1].contiguous(), squash=False, input_grad=False)[0].clone()
+        if adam:
+            L.mlp_adam_step([self.critic], [row_c], [self.adam_critic], [self._blob_c], self.hyper_critic, self.step_critic,
+                            targets=[self.target_critic], target_blobs=[self._blob_tc], stats=self.step_stats_critic[u])
+        L.ddpg_put_actions(forward(self._blob_a, obs), x_pi, Do, k, central=c, own_only=True)
+        _, gx = L.mlp_grad(self.critic, self._blob_c, x_pi, head.g_pi[..., :1].contiguous(), squash=False, input_grad=True)
+        g_a4 = L.ddpg_action_grad(gx, Do, k, central=c)
+        row_a = L.mlp_grad(self.actor, self._blob_a, obs, g_a4[..., :k].contiguous(), squash=True, input_grad=False)[0].clone()
+        if adam:
+            L.mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
+                            targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u])
+        return row_c, row_a
+
+
+def ring(rows, B, seed=3, device="cuda"):
+    """A DeviceReplayBuffer of len(rows) transitions filled through _put with `rows` (ring_rows'), batches of B."""
+    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer
+    obs, act, rew, obs_next, done = rows
+    N, nA, Do = obs.shape
+    buf = DeviceReplayBuffer(N, B, list(range(nA)), Do, Do * nA, act.shape[2], device=device, seed=seed)
+    buf._put(obs.to(device), act.to(device), rew.to(device), obs_next.to(device), done.to(device))
+    return buf
+
+
+def gpu_copy(net, device="cuda"):
+    return U._to(net, device)
+
+
+# ------------------------------------------------------------------------------------------------ the torch composition, the bandit
+def torch_update(actor, critic, target_actor, target_critic, opt_a, opt_c, batch, central, gamma=GAMMA, tau=0.01, max_grad_norm=None):
+    """One MADDPG update the way a torch user writes it (any device): autograd through StackedActor, clip_grad_norm_, the two Adam
+    steps (critic first, the actor against the stepped critic), foreach Polyak."""
+    obs, act, rew, obs_next, done = batch
+    B, nA, k = act.shape
+
+    def joined(o, actions):
+        if not central:
+            return torch.cat([o, actions], -1)
+        return torch.cat([o.reshape(B, 1, -1), actions.reshape(B, 1, -1)], -1).expand(B, nA, -1)
+    with torch.no_grad():
+        y = rew + gamma * (1.0 - done.to(rew.dtype)) * target_critic(joined(obs_next, target_actor(obs_next)), squash=False)[..., 0]
+    opt_c.zero_grad(set_to_none=True)
+    ((critic(joined(obs, act), squash=False)[..., 0] - y) ** 2).mean(0).sum().backward()
+    if max_grad_norm is not None:
+        torch.nn.utils.clip_grad_norm_(critic.parameters(), max_grad_norm)
+    opt_c.step()
+    pi = actor(obs)
+    if central:
+        own = torch.eye(nA, dtype=pi.dtype, device=pi.device).view(1, nA, nA, 1)
+        actions = own * pi.unsqueeze(1) + (1.0 - own) * act.unsqueeze(1)
+        x_pi = torch.cat([obs.reshape(B, 1, -1).expand(B, nA, -1), actions.reshape(B, nA, nA * k)], -1)
+    else:
+        x_pi = torch.cat([obs, pi], -1)
+    opt_a.zero_grad(set_to_none=True)
+    (-critic(x_pi, squash=False)[..., 0].mean(0).sum()).backward()
+    if max_grad_norm is not None:
+        torch.nn.utils.clip_grad_norm_(actor.parameters(), max_grad_norm)
+    opt_a.step()
+    with torch.no_grad():
+        for t, n in ((target_actor, actor), (target_critic, critic)):
+            ts, ns = list(t.parameters()), list(n.parameters())
+            torch._foreach_mul_(ts, 1.0 - tau)
+            torch._foreach_add_(ts, ns, alpha=tau)
+
+
+BANDIT = dict(nA=2, Do=5, k=4, rows=2048, B=256, held_out=1024, lr=1e-3, tau=0.01)
+
+
+def bandit_reward(obs, a):
+    """r = -mean_k (a_k - 0.5 sign(o_k))^2 over the k action columns, against the first k observation columns -> [.., nA]."""
+    return -((a - 0.5 * torch.sign(obs[..., :a.shape[-1]])) ** 2).mean(-1)
+
+
+def bandit_rows(seed=0):
+    """The bandit ring (every row finished: done = 1, the next observation plays no part) and a held-out observation set."""
+    b = BANDIT
+    g = torch.Generator().manual_seed(9900 + seed)
+    uni = lambda *s: torch.rand(s, generator=g) * 2 - 1       # noqa: E731
+    obs, act = uni(b["rows"], b["nA"], b["Do"]), uni(b["rows"], b["nA"], b["k"])
+    rows = (obs, act, bandit_reward(obs, act), uni(b["rows"], b["nA"], b["Do"]), torch.ones((b["rows"], b["nA"]), dtype=torch.bool))
+    return rows, uni(b["held_out"], b["nA"], b["Do"])
+
+
+def bandit_nets(seed=0):
+    """(actor, critic) on the CPU, freshly initialised (own critic: 9 -> 1)."""
+    b = BANDIT
+    torch.manual_seed(9950 + seed)
+    return R._new(b["nA"], b["Do"], b["k"]), R._new(b["nA"], b["Do"] + b["k"], 1)
+
+
+def bandit_torch_run(N, seed=0):
+    """(initial reward, reward after N updates) of the torch composition on the CPU: batches drawn with a torch generator."""
+    b = BANDIT
+    rows, held = bandit_rows(seed)
+    actor, critic = bandit_nets(seed)
+    ta, tc = copy.deepcopy(actor), copy.deepcopy(critic)
+    oa, oc = torch.optim.Adam(actor.parameters(), lr=b["lr"]), torch.optim.Adam(critic.parameters(), lr=b["lr"])
+    g = torch.Generator().manual_seed(9990 + seed)
+    with torch.no_grad():
+        r0 = float(bandit_reward(held, actor(held)).mean())
+    for _ in range(N):
+        idx = torch.randint(0, b["rows"], (b["B"],), generator=g)
+        torch_update(actor, critic, ta, tc, oa, oc, tuple(r[idx] for r in rows), False, tau=b["tau"])
+    with torch.no_grad():
+        return r0, float(bandit_reward(held, actor(held)).mean())

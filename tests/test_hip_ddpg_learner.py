@@ -1,0 +1,232 @@
+"""DDPGLearner on the MI355X: an update is, bit for bit, the sequence of the public primitives written out by hand
+(tests/ddpg_util.py: Hand); a captured update replays as one graph with fresh draws and allocates nothing; the first update's two
+gradient rows against float64 CPU autograd of the two MADDPG losses with torch float32 autograd as the yardstick; finished rows keep the
+targets out; set_lr reaches a captured graph; publish writes the team's rows alone; and a bandit on which the captured updates must
+learn at least half of what the torch composition learns."""
+import gc
+import json
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import ddpg_util as D
+import mlp_grad_util as M
+
+pytestmark = pytest.mark.gpu
+
+KW = dict(gamma=D.GAMMA, tau=0.05, lr_actor=1e-3, lr_critic=2e-3, max_grad_norm=0.5)
+
+
+def _pair(shape, updates=1, rows=None, **kw):
+    """(a DDPGLearner, a Hand) from equal copies of the shape's starting state, each on a ring of its own with the same rows and seed."""
+    from deep_rl_battlespace_amd.learner import DDPGLearner
+    B, nA, Do, k, central = shape
+    actor, critic, case_rows, *_ = D.learner_case(shape)
+    rows = case_rows if rows is None else rows
+    kw = {**KW, **kw}
+    learner = DDPGLearner(D.ring(rows, B), D.gpu_copy(actor), D.gpu_copy(critic), critic_input="central" if central else "own", updates=updates, **kw)
+    hand = D.Hand(D.ring(rows, B), D.gpu_copy(actor), D.gpu_copy(critic), central, updates=updates, **kw)
+    return learner, hand
+
+
+def _blobs_are_packs(x):
+    for net, blob in ((x.actor, x._blob_a), (x.critic, x._blob_c), (x.target_actor, x._blob_ta), (x.target_critic, x._blob_tc)):
+        assert torch.equal(net.pack().view(torch.int32), blob.view(torch.int32))
+
+
+@pytest.mark.parametrize("shape", D.LEARNER_SHAPES, ids=D.shape_id)
+def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(shape):
+    learner, hand = _pair(shape)
+    start = D.snapshot(learner)
+    assert D.differing(start, D.snapshot(hand)) == []
+    for u in range(3):
+        stats = learner.update()
+        hand.update()
+        a, b = D.snapshot(learner), D.snapshot(hand)
+        assert D.differing(a, b) == [], (u, D.differing(a, b))
+        assert stats is learner.stats and float(stats[0, 0]) == shape[0] * shape[1]
+    assert int(learner.step_actor) == 3 == int(learner.step_critic) and int(learner.buffer._draws) == 3
+    assert torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
+    moved = set(D.differing(start, a))
+    assert {"actor.w1", "critic.w1", "target_actor.w2", "target_critic.w2", "_blob_a", "_blob_c", "_blob_ta", "_blob_tc", "adam_actor.m",
+            "adam_critic.v", "stats", "step_stats_actor", "step_stats_critic", "draws"} <= moved
+    _blobs_are_packs(learner)
+
+
+@pytest.mark.parametrize("shape", D.LEARNER_SHAPES, ids=D.shape_id)
+def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_allocates_nothing(shape):
+    captured, _ = _pair(shape, updates=2)
+    eager, _ = _pair(shape, updates=2)
+    start = D.snapshot(captured)
+    assert captured.capture() is captured
+    assert D.differing(start, D.snapshot(captured)) == []                     # a capture runs nothing
+    draws = []
+    for u in range(3):
+        captured.update()
+        eager.update()
+        draws.append(captured.buffer.last_idx.clone())
+        a, b = D.snapshot(captured), D.snapshot(eager)
+        assert D.differing(a, b) == [], (u, D.differing(a, b))
+    assert not torch.equal(draws[0], draws[1]) and not torch.equal(draws[1], draws[2])        # fresh draws
+    assert int(captured.step_actor) == 6 == int(captured.step_critic) and int(captured.buffer._draws) == 6
+    _blobs_are_packs(captured)
+    del a, b
+    torch.cuda.synchronize()
+    gc.collect()                                                              # (as ppo_learner_util.allocates_nothing reads it)
+    held = torch.cuda.memory_allocated()
+    captured.update()
+    captured.update()
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == held
+
+
+@pytest.mark.parametrize("shape", D.LEARNER_SHAPES, ids=D.shape_id)
+def test_the_first_updates_gradient_rows_against_float64_autograd_of_the_two_maddpg_losses(shape):
+    """The ring sampled with fixed idx, the kink-free weights passed as `weight` through the primitives; no optimiser step, so both rows
+    are gradients at the starting parameters.  torch float32 autograd on the CPU is the yardstick (mlp_grad_util.check)."""
+    from deep_rl_battlespace_amd.learner import split_grad
+    B, nA, Do, k, central = shape
+    actor, critic, rows, idx, w, share = D.learner_case(shape)
+    assert share < D.U.KINK_CAP
+    _, hand = _pair(shape)
+    s = hand.buffer.sample(idx)
+    dev_batch = (s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6])
+    batch = tuple(r[idx] for r in rows)
+    for got, want in zip(dev_batch, batch):
+        assert torch.equal(got.cpu(), want)
+    row_c, row_a = hand.step(*dev_batch, 0, weight=w.cuda(), adam=False)
+    torch.cuda.synchronize()
+    gc64, ga64 = D.maddpg_grads(actor, critic, batch, w, central, torch.float64)
+    gc32, ga32 = D.maddpg_grads(actor, critic, batch, w, central, torch.float32)
+    num = lambda row, na: {p: g.double().cpu().numpy() for p, g in zip(D.PARAMS, split_grad(row, na))}     # noqa: E731
+    M.check(num(row_c, 1), gc64, gc32, f"DDPG critic {D.shape_id(shape)}", names=D.PARAMS)
+    M.check(num(row_a, k), ga64, ga32, f"DDPG actor {D.shape_id(shape)}", names=D.PARAMS)
+    assert all(float(np.abs(g).max()) > 0 for g in list(gc64.values()) + list(ga64.values()))
+
+
+def test_finished_rows_keep_the_target_networks_out_of_every_gradient():
+    """done = 1 on every row: y = rew.  Two learners whose target networks differ (NaN-free) leave the same bits in the actor, the
+    critic, their moments, their blobs and the statistics."""
+    shape = D.LEARNER_SHAPES[1]
+    _, _, rows, *_ = D.learner_case(shape)
+    rows = (*rows[:4], torch.ones_like(rows[4]))
+    a, _ = _pair(shape, rows=rows)
+    b, _ = _pair(shape, rows=rows)
+    with torch.no_grad():
+        for t in (b.target_actor, b.target_critic):
+            for p in t.parameters():
+                p.add_(0.25 * torch.randn(p.shape, generator=torch.Generator().manual_seed(5)).to(p.device))
+    b.sync()
+    _blobs_are_packs(b)
+    for _ in range(2):
+        a.update()
+        b.update()
+    x, y = D.snapshot(a), D.snapshot(b)
+    diff = D.differing(x, y)
+    assert diff and all(k.startswith("target_") or k in ("_blob_ta", "_blob_tc") for k in diff), diff
+    assert float(a.stats[0, 5]) == 1.0 and torch.equal(a.td.view(torch.int32), a.buffer._b_rew.view(torch.int32))
+
+
+def test_set_lr_reaches_a_captured_update():
+    shape = D.LEARNER_SHAPES[0]
+    learner, _ = _pair(shape)
+    learner.capture()
+    learner.set_lr(actor=0.0, critic=0.0)
+    before = D.snapshot(learner)
+    learner.update()
+    after = D.snapshot(learner)
+    same = [k for k in before if k.startswith(("actor.", "critic."))]
+    assert all(torch.equal(before[k], after[k]) for k in same) and int(learner.step_actor) == 1
+    assert float(learner.step_stats_actor[0, 3]) == 0.0 == float(learner.step_stats_critic[0, 3])
+    learner.set_lr(actor=2e-3)
+    learner.update()
+    assert float(learner.step_stats_actor[0, 3]) == float(np.float32(2e-3)) and float(learner.step_stats_critic[0, 3]) == 0.0
+    moved = D.differing(after, D.snapshot(learner))
+    assert "actor.w1" in moved and not [k for k in moved if k.startswith("critic.")]
+    with pytest.raises(ValueError):
+        learner.set_lr(actor=-1.0)
+
+
+@pytest.mark.parametrize("c0", [0, 2])
+def test_publish_writes_the_teams_blob_rows_and_parameter_slices_and_nothing_else(c0):
+    from deep_rl_battlespace_amd.rollout import FusedActor, StackedActor
+    shape = D.LEARNER_SHAPES[1]                                               # 2v2: the rollout's actor has 4 agents of obs_len 8
+    learner, _ = _pair(shape)
+    learner.update()
+    torch.manual_seed(3)
+    ro_actor = StackedActor(4, 8, 4, device="cuda")
+    ro = types.SimpleNamespace(actor=ro_actor, fused=FusedActor(ro_actor, 2))
+    blob0 = ro.fused.weights.clone()
+    params0 = {p: getattr(ro_actor, p).detach().clone() for p in D.PARAMS}
+    learner.publish(ro, range(c0, c0 + 2))
+    torch.cuda.synchronize()
+    team, rest = slice(c0, c0 + 2), slice(2 - c0, 4 - c0)
+    bits = lambda t: t.detach().view(torch.int32)                             # noqa: E731
+    assert torch.equal(bits(ro.fused.weights[team]), bits(learner._blob_a)) and torch.equal(bits(ro.fused.weights[rest]), bits(blob0[rest]))
+    assert not torch.equal(bits(ro.fused.weights[team]), bits(blob0[team]))
+    for p in D.PARAMS:
+        assert torch.equal(bits(getattr(ro_actor, p)[team]), bits(getattr(learner.actor, p))), p
+        assert torch.equal(bits(getattr(ro_actor, p)[rest]), bits(params0[p][rest])), p
+    assert torch.equal(bits(ro_actor.pack()), bits(ro.fused.weights))         # the rows published are the pack of the slices published
+    for cols in ([0, 2], range(3, 5), range(0, 3)):
+        with pytest.raises(ValueError, match="contiguous range"):
+            learner.publish(ro, cols)
+    with pytest.raises(ValueError, match="obs_len 8"):
+        learner.publish(types.SimpleNamespace(actor=StackedActor(4, 5, 4, device="cuda"), fused=None), range(0, 2))
+
+
+def test_the_constructor_names_the_shape_it_wanted():
+    from deep_rl_battlespace_amd.learner import DDPGLearner
+    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer, ReplayBuffer
+    from deep_rl_battlespace_amd.rollout import StackedActor
+    buf = DeviceReplayBuffer(64, 16, list(range(2)), 8, 16, 4, device="cuda")
+    actor = StackedActor(2, 8, 4, device="cuda")
+    learner = DDPGLearner(buf, actor)
+    assert (learner.critic.n_actors, learner.critic.obs_len, learner.critic.n_actions) == (2, 24, 1) and learner.stats.shape == (1, 8)
+    assert DDPGLearner(buf, actor, critic_input="own", updates=3).step_stats_critic.shape == (3, 4)
+    with pytest.raises(ValueError, match=r"StackedActor\(2, 8, 4\)"):
+        DDPGLearner(buf, StackedActor(2, 5, 4, device="cuda"))
+    with pytest.raises(ValueError, match=r"StackedActor\(2, 24, 1\)"):
+        DDPGLearner(buf, actor, StackedActor(2, 12, 1, device="cuda"))
+    with pytest.raises(ValueError, match=r"StackedActor\(2, 12, 1\)"):
+        DDPGLearner(buf, actor, StackedActor(2, 24, 1, device="cuda"), critic_input="own")
+    with pytest.raises(ValueError, match="DeviceReplayBuffer"):
+        DDPGLearner(ReplayBuffer(64, 16, list(range(2)), 8, 16, 4, device="cuda"), actor)
+    with pytest.raises(ValueError, match="critic_input"):
+        DDPGLearner(buf, actor, critic_input="joint")
+    for kw in (dict(gamma=1.5), dict(tau=-0.1), dict(lr_actor=-1.0), dict(max_grad_norm=0.0), dict(updates=0)):
+        with pytest.raises(ValueError):
+            DDPGLearner(buf, actor, **kw)
+    wide = DeviceReplayBuffer(64, 16, list(range(4)), 14, 56, 4, device="cuda")
+    with pytest.raises(ValueError, match="4v4 central is 72"):
+        DDPGLearner(wide, StackedActor(4, 14, 4, device="cuda"))
+    assert DDPGLearner(wide, StackedActor(4, 14, 4, device="cuda"), critic_input="own").Dc == 18
+
+
+def test_captured_updates_on_a_bandit_learn_at_least_half_of_what_the_torch_composition_learns():
+    """A bandit ring: every row finished, r = -mean_k (a_k - 0.5 sign(o_k))^2, own critics.  N and the torch composition's figures are
+    recorded in profiles/ddpg_float64.json, chosen on the CPU with the torch composition alone, which itself closes at least half of the
+    gap from its initial reward to 0 in N updates (re-run here: a fraction of a second)."""
+    from deep_rl_battlespace_amd.learner import DDPGLearner
+    rec = json.load(open(D.PROFILE))["bandit"]
+    N, b = rec["N"], D.BANDIT
+    r0, r_torch = D.bandit_torch_run(N)
+    closed_torch = (r_torch - r0) / (0.0 - r0)
+    assert abs(r0 - rec["initial_reward"]) < 1e-6 and closed_torch >= 0.5
+    rows, held = D.bandit_rows()
+    actor, critic = D.bandit_nets()
+    learner = DDPGLearner(D.ring(rows, b["B"]), D.gpu_copy(actor), D.gpu_copy(critic), critic_input="own", tau=b["tau"], lr_actor=b["lr"],
+                          lr_critic=b["lr"], updates=10).capture()
+    assert N % 10 == 0
+    for _ in range(N // 10):
+        learner.update()
+    with torch.no_grad():
+        before = float(D.bandit_reward(held, actor(held)).mean())
+        after = float(D.bandit_reward(held, learner.actor(held.cuda()).cpu()).mean())
+    closed = (after - before) / (0.0 - before)
+    print(f"bandit, N = {N}: reward {before:.4f} -> {after:.4f} (closed {closed:.3f} of the gap); torch composition -> {r_torch:.4f} "
+          f"(closed {closed_torch:.3f}; recorded {rec['torch_closed']:.3f})")
+    assert abs(before - r0) < 1e-6 and int(learner.step_actor) == N
+    assert closed >= 0.5 * closed_torch
