@@ -4,7 +4,7 @@ Only what the hot path needs lives here:
   csrc/          hand-written HIP kernels for gfx950 + the C ABI of include/battlespace_hip.h
   build.py       hipcc recipe for csrc/ (in-tree libbattlespace_hip.so)
   _lib.py        ctypes binding of the C ABI (fails loudly when the library is missing)
-  _args.py       the tensor, number and workspace checks of advantage.py and learner.py
+  _args.py       the tensor, number and workspace checks of advantage.py and learner/
   envs/battle_env.py   `parallel_env`: the reference's PettingZoo ParallelEnv surface, batched over n_envs
   spaces.py      Box / Discrete metadata containers (gym is not a dependency)
   sharding.py    one contiguous env range per rank (no collective on the step path)
@@ -12,13 +12,14 @@ Only what the hot path needs lives here:
   rollout.py     on-device actor + step loop in one HIP graph (next row f-1); csrc/bsx_actor.hip is its MFMA actor
   replay.py      device-resident transition ring, mirror of maddpg/buffer.py (next row f-3)
   advantage.py   GAE advantages / returns / per-agent mask of a rollout on device, for on-policy learners (csrc/bsx_advantage.hip)
-  learner.py     the actor / value MLP as one fused forward and one fused backward for on-device learners (csrc/bsx_actor_grad.hip),
-                 the PPO loss head between them and the minibatch update over a rollout's records (csrc/bsx_ppo_head.hip),
-                 the fused clip + Adam + pack step that makes a whole update one graph, and its tied form for agents that share one
+  learner/       the on-device learners, one module per kernel family:
+    mlp.py       the actor / value MLP as one fused forward and one fused backward for on-device learners (csrc/bsx_actor_grad.hip)
+    ppo.py       the PPO loss head between them and the minibatch update over a rollout's records, PPOLearner (csrc/bsx_ppo_head.hip)
+    adam.py      the fused clip + Adam + pack step that makes a whole update one graph, and its tied form for agents that share one
                  policy per team, and the same step for a network of any width with Polyak target networks kept in the same pass
-                 (csrc/bsx_adam_step.hip),
-                 a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip),
-                 the critic join, TD head and action gradient of a DDPG update and DDPGLearner, the MADDPG update of a team from
+                 (csrc/bsx_adam_step.hip)
+    shuffle.py   a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip)
+    ddpg.py      the critic join, TD head and action gradient of a DDPG update and DDPGLearner, the MADDPG update of a team from
                  its replay ring as one graph (csrc/bsx_ddpg_head.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.

@@ -1,4 +1,4 @@
-"""Argument checks of the learner-side bindings (advantage.py, learner.py): one tensor check, one number check, one workspace helper."""
+"""Argument checks of the learner-side bindings (advantage.py, learner/): one tensor check, one number check, one workspace helper."""
 import math
 
 import torch

@@ -222,3 +222,10 @@ def check(rc, what):
         raise ValueError(f"{what}: this state block was advanced by the other action family (BSX_E_FAMILY): a block is discrete or "
                          f"continuous from its first step until every game is reset")
     raise RuntimeError(f"{what}: HIP error {rc}")
+
+
+def query_bytes(entry, *sizes):
+    """What a `*_workspace_bytes` entry answers for the given sizes: entry(int(size) ..., &bytes), checked under the entry's name."""
+    nb = c_size_t()
+    check(getattr(load(), entry)(*map(int, sizes), ctypes.byref(nb)), entry)
+    return nb.value

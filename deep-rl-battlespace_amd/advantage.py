@@ -42,9 +42,7 @@ def check_rates(gamma, lam):
 
 def workspace_bytes(E, A, T):
     """Bytes of the workspace that gae(..., normalize=True) needs for E games of A agents and T ticks."""
-    lib, n = _lib.load(), _lib.c_size_t()
-    _lib.check(lib.bsx_gae_workspace_bytes(int(E), int(A), int(T), _lib.ctypes.byref(n)), "bsx_gae_workspace_bytes")
-    return n.value
+    return _lib.query_bytes("bsx_gae_workspace_bytes", E, A, T)
 
 
 def gae(rew, value, last_value, done, env_done, done_prev, gamma, lam, *, normalize=False, out=None, stats=None, workspace=None, agents=None):

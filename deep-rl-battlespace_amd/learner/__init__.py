@@ -1,0 +1,23 @@
+"""The learner's side of a PolicyRollout and of a DeviceReplayBuffer, on device: one module per kernel family, each with its own catalogue.
+
+  mlp.py      the actor / value / Q MLP as ONE fused forward and ONE fused backward, its cached buffers and its one check (csrc/bsx_actor_grad.hip)
+  adam.py     clip + Adam + pack as two launches: the actors' step, its tied form, the free-width form with Polyak targets (csrc/bsx_adam_step.hip)
+  shuffle.py  a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip)
+  ppo.py      the PPO loss head and PPOLearner, the update of a rollout's two networks (csrc/bsx_ppo_head.hip)
+  ddpg.py     the critic join, TD head and action gradient, and DDPGLearner, the MADDPG update of a team from its ring (csrc/bsx_ddpg_head.hip)
+  _common.py  what more than one of them uses: the hyper-parameter ranges, the stream, the capture of an update as one graph
+
+A PPO minibatch:  [minibatch_gather] -> bsx_actor_forward with the value head -> ppo_head -> bsx_mlp_grad of the actor, of the critic -> adam_step.
+A DDPG update:    buffer.sample -> ddpg_inputs -> target actor, ddpg_put_actions -> target critic, critic -> td_head -> bsx_mlp_grad, mlp_adam_step of the
+                  critic -> actor, ddpg_put_actions -> bsx_mlp_grad of the critic for grad_x, ddpg_action_grad -> bsx_mlp_grad, mlp_adam_step of the actor.
+"""
+from . import adam, ddpg, mlp
+from .adam import (ADAM_STATS, HYPER, AdamState, adam_hyper, adam_step, adam_step_workspace_bytes, is_tied, mlp_adam_step,  # noqa: F401
+                   mlp_adam_step_workspace_bytes, share_group, tie_)
+from .ddpg import MAX_OBS, TD_STATS, DDPGLearner, TdHead, ddpg_action_grad, ddpg_inputs, ddpg_put_actions, td_head, td_head_workspace_bytes  # noqa: F401
+from .mlp import H, PARAMS, blob_floats, categorical_log_prob, fused_apply, fused_grad, fused_mlp, grad_floats, mlp_grad, split_grad  # noqa: F401
+from .ppo import KINDS, STATS, PPOLearner, PpoHead, ppo_head, ppo_head_workspace_bytes  # noqa: F401
+from .shuffle import GATHER_ROWS, Minibatch, minibatch_gather, shuffle_rows  # noqa: F401
+
+_Buffers, _buffers, _actor_forward, _mlp_forward, _mlp_grad, _tied_tensors, _critic_width = (  # used by tests/ and tools/
+    mlp._Buffers, mlp._buffers, mlp._actor_forward, mlp._mlp_forward, mlp._mlp_grad, adam._tied_tensors, ddpg._critic_width)

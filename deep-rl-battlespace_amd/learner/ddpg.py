@@ -1,0 +1,310 @@
+"""The DDPG / MADDPG update on device (csrc/bsx_ddpg_head.hip): what lies between the fused MLP calls, and the learner around it.
+
+  ddpg_inputs, ddpg_put_actions, td_head, ddpg_action_grad      the critic's inputs from a batch, actions into them, the TD target, the actor's grad_out
+  DDPGLearner(buffer, actor, critic=None, ...)                  the MADDPG update of a team from its DeviceReplayBuffer; capture() makes it one graph
+"""
+import copy
+from collections import namedtuple
+from functools import partial
+
+import torch
+
+from .. import _lib
+from .._args import _F32, _FLAG, _need, _workspace
+from ..replay import DeviceReplayBuffer
+from ..rollout import StackedActor
+from ._common import _POSITIVE, _capture, _f32, _hyper, _stream
+from .adam import AdamState, adam_hyper, mlp_adam_step, mlp_adam_step_workspace_bytes
+from .mlp import PARAMS, _buffers, _check_mlp, _is_stacked, _mlp_forward, _mlp_grad
+
+TdHead = namedtuple("TdHead", "g_q g_pi td stats")
+TD_STATS = ("n", "critic_loss", "q", "target", "abs_td", "done", "weight", "reserved")
+MAX_OBS = 3 * _lib.MAX_N + 2
+
+
+def _critic_width(nA, Do, k, central):
+    """Dc of a critic input after the checks every ddpg_* call shares (bsx_ddpg_*'s ranges) -> int."""
+    if not 1 <= nA <= _lib.MAX_N or not 1 <= Do <= MAX_OBS or k not in (3, 4):
+        raise ValueError(f"1 .. {_lib.MAX_N} agents, observations of 1 .. {MAX_OBS} floats and 3 or 4 action columns are needed, got {nA}, {Do} and {k}")
+    Dc = nA * (Do + k) if central else Do + k
+    if Dc > _lib.MLP_MAX_D:
+        raise ValueError(f"a central critic of {nA} agents reads {nA} x ({Do} + {k}) = {Dc} inputs: the fused MLP kernels take at most "
+                         f"{_lib.MLP_MAX_D} (the reference's form fits up to 3v3: 9, 24 and 45 inputs; 4v4 central is 72) -- use critic_input='own'")
+    return Dc
+
+
+def _batch_rows(x, name):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError(f"{name} must be a float32 [B, nA, columns] tensor")
+    if x.device.type != "cuda":
+        raise ValueError(f"the ddpg calls run on the GPU: {name} is on {x.device}")
+    if not 1 <= x.shape[0] < 1 << 31:
+        raise ValueError(f"{name} has {x.shape[0]} rows: 1 <= B < 2^31 is needed")
+    return x.shape[0], x.shape[1], x.device
+
+
+def ddpg_inputs(obs, obs_next, act, *, central=True, out=None):
+    """Everything of the critic's three inputs that comes from the sampled batch alone, in one launch (csrc/bsx_ddpg_head.hip,
+    `bsx_ddpg_inputs`; include/battlespace_hip.h) -> (x_cur, x_next, x_pi), each float32 [B, nA, Dc].
+
+    obs, obs_next float32 [B, nA, Do], act float32 [B, nA, k] (k = 3 or 4): a DeviceReplayBuffer's batch.  central=False: row (b, i) is
+    obs[b, i] (+) a[b, i], Dc = Do + k; central=True: the team's joint observation and action, obs[b, 0] .. obs[b, nA-1] (+) a[b, 0] ..
+    a[b, nA-1], Dc = nA (Do + k) <= 64.  x_cur is written whole (the replayed actions); x_next gets obs_next's columns and x_pi obs's,
+    and with central=True every action slot of x_pi the replayed actions; the action columns ddpg_put_actions fills later are left as
+    they are.  out: the three tensors to write into (nothing is allocated then); without it they are new and zero elsewhere."""
+    B, nA, dev = _batch_rows(obs, "obs")
+    Do, k = obs.shape[2], act.shape[2] if isinstance(act, torch.Tensor) and act.dim() == 3 else 0
+    Dc = _critic_width(nA, Do, k, central)
+    need = partial(_need, dev=dev, anchor="obs")
+    need(obs, "obs", (B, nA, Do), _F32)
+    need(obs_next, "obs_next", (B, nA, Do), _F32)
+    need(act, "act", (B, nA, k), _F32)
+    if out is None:
+        out = tuple(torch.zeros((B, nA, Dc), dtype=torch.float32, device=dev) for _ in range(3))
+    x_cur, x_next, x_pi = out
+    for x, name in zip(out, ("out x_cur", "out x_next", "out x_pi")):
+        need(x, name, (B, nA, Dc), _F32)
+    batch = _lib.BsxDdpgBatch(obs.data_ptr(), obs_next.data_ptr(), act.data_ptr())
+    _lib.check(_lib.load().bsx_ddpg_inputs(_lib.ctypes.byref(batch), B, nA, Do, k, int(bool(central)), x_cur.data_ptr(), x_next.data_ptr(),
+                                           x_pi.data_ptr(), _stream(dev)), "bsx_ddpg_inputs")
+    return x_cur, x_next, x_pi
+
+
+def ddpg_put_actions(y4, x, obs_len, n_actions, *, central=True, own_only=False):
+    """The first n_actions columns of a network's output rows y4 float32 [B, nA, 4] (bsx_mlp_forward's) into the action columns of the
+    critic input x float32 [B, nA, Dc], in one launch (`bsx_ddpg_put_actions`) -> x.  own_only=False: row (b, i) receives the actions
+    of all agents of row b (the target actors' actions into x_next); own_only=True: agent i's alone, into slot i (pi_i(o_i) into x_pi,
+    whose other slots keep the replayed actions).  With central=False the two are the same.  Nothing else of x is written."""
+    B, nA, dev = _batch_rows(y4, "y4")
+    Do, k = int(obs_len), int(n_actions)
+    Dc = _critic_width(nA, Do, k, central)
+    need = partial(_need, dev=dev, anchor="y4")
+    need(y4, "y4", (B, nA, 4), _F32)
+    need(x, "x", (B, nA, Dc), _F32)
+    _lib.check(_lib.load().bsx_ddpg_put_actions(y4.data_ptr(), B, nA, Do, k, int(bool(central)), int(bool(own_only)), x.data_ptr(),
+                                                _stream(dev)), "bsx_ddpg_put_actions")
+    return x
+
+
+def ddpg_action_grad(gx, obs_len, n_actions, *, central=True, out=None):
+    """Agent i's own action columns of row (b, i) of the critic's input gradient gx float32 [B, nA, Dc] (mlp_grad's grad_x on x_pi)
+    -> g_a4 float32 [B, nA, 4]: the actor's grad_out as bsx_mlp_grad takes it (squash=True), column 3 +0 with three actions.  One
+    launch (`bsx_ddpg_action_grad`).  out: the tensor to write into."""
+    B, nA, dev = _batch_rows(gx, "gx")
+    Do, k = int(obs_len), int(n_actions)
+    Dc = _critic_width(nA, Do, k, central)
+    need = partial(_need, dev=dev, anchor="gx")
+    need(gx, "gx", (B, nA, Dc), _F32)
+    if out is None:
+        out = torch.empty((B, nA, 4), dtype=torch.float32, device=dev)
+    need(out, "out", (B, nA, 4), _F32)
+    _lib.check(_lib.load().bsx_ddpg_action_grad(gx.data_ptr(), B, nA, Do, k, int(bool(central)), out.data_ptr(), _stream(dev)),
+               "bsx_ddpg_action_grad")
+    return out
+
+
+def td_head_workspace_bytes(B, nA):
+    """Bytes of the workspace td_head needs for B rows of nA agents."""
+    return _lib.query_bytes("bsx_td_head_workspace_bytes", B, nA)
+
+
+def td_head(q, q_next, rew, done, gamma, *, weight=None, out=None, workspace=None):
+    """The TD target and both grad_out tensors of a DDPG update from the critic's outputs, in one pass (csrc/bsx_ddpg_head.hip,
+    `bsx_td_head`; the exact contract is written out in include/battlespace_hip.h) -> TdHead(g_q, g_pi, td, stats).
+
+    q, q_next, rew float32 [B, nA]: the critic on x_cur, the target critic on x_next (raw heads) and the rewards; done uint8 or bool
+    [B, nA]; weight float32 [B, nA] or None (1 everywhere; the hook of a prioritised sampler); gamma in [0, 1].  Per element
+    y = fmaf(gamma, done ? 0 : q_next, rew), d = q - y;  g_q[..., 0] = (w d) float(2 / B): the critic's grad_out (squash=False) for the
+    sum over agents of mean_b w (Q - y)^2;  g_pi[..., 0] = -(w float(1 / B)): the seed of the critic's input-gradient pass for the sum
+    over agents of -mean_b w Q;  td = y.  Columns 1 .. 3 of both are +0.  stats f64 [8] on the device in the order of learner.TD_STATS:
+    means over the B nA elements.  Deterministic; two launches on the current stream, no host synchronisation.  out: optional
+    (g_q, g_pi, td or None, stats) to write into and workspace (at least td_head_workspace_bytes(B, nA) bytes, 8-byte aligned) -- pass
+    both and nothing is allocated (a captured graph)."""
+    if not isinstance(q, torch.Tensor) or q.dim() != 2:
+        raise ValueError("q must be a float32 [B, nA] tensor")
+    dev, (B, nA) = q.device, q.shape
+    if dev.type != "cuda":
+        raise ValueError("td_head runs on the GPU: q is on " + str(dev))
+    if not 1 <= B < 1 << 31 or not 1 <= nA <= _lib.MAX_N:
+        raise ValueError(f"q has shape {tuple(q.shape)}: 1 <= B < 2^31 and 1 .. {_lib.MAX_N} agents are needed")
+    gamma = _hyper("gamma", gamma)
+    need = partial(_need, dev=dev, anchor="q")
+    for x, name in ((q, "q"), (q_next, "q_next"), (rew, "rew")):
+        need(x, name, (B, nA), _F32)
+    need(done, "done", (B, nA), _FLAG)
+    if weight is not None:
+        need(weight, "weight", (B, nA), _F32)
+    if out is None:
+        f = _f32(torch.empty, dev)
+        out = (f(B, nA, 4), f(B, nA, 4), f(B, nA), torch.empty(8, dtype=torch.float64, device=dev))
+    g_q, g_pi, td, stats = out
+    need(g_q, "out g_q", (B, nA, 4), _F32)
+    need(g_pi, "out g_pi", (B, nA, 4), _F32)
+    if td is not None:
+        need(td, "out td", (B, nA), _F32)
+    need(stats, "out stats", (8,), (torch.float64,))
+    workspace = _workspace(workspace, td_head_workspace_bytes(B, nA), dev)
+    io = _lib.BsxTdIo(q.data_ptr(), q_next.data_ptr(), rew.data_ptr(), done.data_ptr(), weight.data_ptr() if weight is not None else None,
+                      g_q.data_ptr(), g_pi.data_ptr(), td.data_ptr() if td is not None else None)
+    _lib.check(_lib.load().bsx_td_head(_lib.ctypes.byref(io), B, nA, gamma, workspace.data_ptr(), stats.data_ptr(), _stream(dev)), "bsx_td_head")
+    return TdHead(g_q, g_pi, td, stats)
+
+
+class DDPGLearner:
+    """The MADDPG update of a team from its replay ring, on device: per-agent actors, one critic per agent on the team's joint
+    observation and action (critic_input="central", the reference's form; Lowe et al. 2017) or on the agent's own
+    (critic_input="own": independent DDPG), soft target networks, Adam.
+
+        buf = DeviceReplayBuffer(1_000_000, 512, env.possible_red, env.obs_size, env.obs_size * n, 4, seed=0)
+        learner = DDPGLearner(buf, actor)                 # actor: StackedActor(n, obs_size, 4); a critic StackedActor(n, Dc, 1) is made
+        learner.capture()
+        while training:
+            ro.run(); buf.append_rollout(ro, range(n))
+            stats = learner.update()                      # f64 [updates, 8] on the device, columns in the order of learner.TD_STATS
+            learner.publish(ro, range(n))                 # the rollout plays the updated actors
+
+    One update, on the current stream, with cached buffers and no host synchronisation:
+       1. buffer.sample()                                          the batch, drawn on the device
+       2. ddpg_inputs                                              x_cur, and the batch's part of x_next and x_pi
+       3. target actor on obs_next, ddpg_put_actions(own_only=False)   a' into x_next
+       4. target critic on x_next -> q_next;  5. critic on x_cur -> q
+       6. td_head                                                  y = r + gamma (1 - done) q_next, g_q, g_pi, the statistics
+       7. mlp_grad of the critic on x_cur with g_q, mlp_adam_step of the critic with its target
+       8. actor on obs, ddpg_put_actions(own_only=True)            pi_i(o_i) into slot i of x_pi; the other slots keep the replayed actions
+       9. mlp_grad of the STEPPED critic on x_pi with g_pi -> grad_x, ddpg_action_grad
+      10. mlp_grad of the actor on obs with that, mlp_adam_step of the actor with its target
+    Every forward reads a packed blob (bsx_mlp_forward) that the steps keep current; nothing is allocated from the second update on.
+
+    buffer: a DeviceReplayBuffer; its n_agents, observation size and n_actions give nA, Do and k, its batch_size B.  actor: a
+    StackedActor(nA, Do, k) on the buffer's device; critic: a StackedActor(nA, Dc, 1), Dc = nA (Do + k) central (at most 64: up to 3v3)
+    or Do + k own; one is made if none is given.  The learner owns deep copies of both as targets (`target_actor`, `target_critic`),
+    the four packed blobs, two AdamStates, two hyper rows (adam_hyper with tau: `hyper_actor`, `hyper_critic`), two step counters, and
+    the statistics: `stats` f64 [updates, 8] (TD_STATS) and `step_stats_actor` / `step_stats_critic` f64 [updates, 4] (ADAM_STATS).
+    update() runs `updates` updates and returns `stats`; capture() records them as ONE graph, the ring's draw included, that update()
+    replays from then on; set_lr writes the device hyper rows; sync() re-packs all four blobs after an outside edit of the networks;
+    publish copies the actors into a rollout.  Parameter sharing, a second critic (TD3) and prioritised sampling are not here
+    (td_head's `weight` is the hook for the last)."""
+
+    def __init__(self, buffer, actor, critic=None, *, critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3, lr_critic=1e-3,
+                 betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=1):
+        if not isinstance(buffer, DeviceReplayBuffer):
+            raise ValueError("DDPGLearner needs a DeviceReplayBuffer (it samples on the device)")
+        if critic_input not in ("central", "own"):
+            raise ValueError(f"critic_input must be 'central' or 'own', got {critic_input!r}")
+        self.buffer, self.central = buffer, critic_input == "central"
+        nA, Do, k, B = buffer.n_agents, buffer.actor_states.shape[2], buffer.n_actions, buffer.batch_size
+        dev = buffer.actor_states.device
+        Dc = _critic_width(nA, Do, k, self.central)
+        self.nA, self.Do, self.k, self.B, self.Dc = nA, Do, k, B, Dc
+        self.gamma = _hyper("gamma", gamma)
+        self.updates = int(updates)
+        if self.updates < 1:
+            raise ValueError(f"updates must be >= 1, got {updates!r}")
+        mgn = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)
+        if critic is None:
+            critic = StackedActor(nA, Dc, 1, device=dev)
+        for net, name, want in ((actor, "actor", (nA, Do, k)), (critic, "critic", (nA, Dc, 1))):
+            have = tuple(getattr(net, a, None) for a in ("n_actors", "obs_len", "n_actions"))
+            if not _is_stacked(net) or have != want:
+                raise ValueError(f"{name} must be a StackedActor{want} for this buffer and critic_input={critic_input!r}, got "
+                                 f"{'StackedActor' + str(have) if None not in have else type(net).__name__}")
+        f = _f32(torch.zeros, dev)                               # zero-filled: what no kernel of an update writes stays +0
+        self._x_cur, self._x_next, self._x_pi = f(B, nA, Dc), f(B, nA, Dc), f(B, nA, Dc)
+        _check_mlp(actor, buffer._b_obs, True, "DDPGLearner")
+        _check_mlp(critic, self._x_cur, False, "DDPGLearner")
+        self.actor, self.critic = actor, critic
+        self.target_actor, self.target_critic = copy.deepcopy(actor), copy.deepcopy(critic)
+        for t in (self.target_actor, self.target_critic):
+            t.__dict__.pop("_bsx_mlp_buffers", None)             # (a deep copy takes the network's cached buffers along)
+            t.requires_grad_(False)
+        self._blob_a, self._blob_c, self._blob_ta, self._blob_tc = (x.pack() for x in (actor, critic, self.target_actor, self.target_critic))
+        self.adam_actor, self.adam_critic = AdamState(actor), AdamState(critic)
+        self.hyper_actor, self.hyper_critic = (adam_hyper(lr, betas, eps, mgn, dev, tau) for lr in (lr_actor, lr_critic))
+        self.step_actor, self.step_critic = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
+        self.stats = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
+        self.step_stats_actor, self.step_stats_critic = (torch.zeros((self.updates, 4), dtype=torch.float64, device=dev) for _ in range(2))
+        self._y4, self._yq4, self._g_q, self._g_pi, self._g_a4 = (f(B, nA, 4) for _ in range(5))
+        self._q, self._q_next, self.td = f(B, nA), f(B, nA), f(B, nA)
+        self._head_ws = _workspace(None, td_head_workspace_bytes(B, nA), dev)
+        self._adam_ws = _workspace(None, mlp_adam_step_workspace_bytes(nA, 1), dev)
+        self._buf_a = _buffers(actor).get(B, nA, Do, dev)
+        self._buf_c = _buffers(critic).get(B, nA, Dc, dev, gx=True)
+        self._graph = None
+
+    def _update(self, u):
+        """Update u of a call: the ten steps of the class's docstring."""
+        lib, buf = _lib.load(), self.buffer
+        buf.sample()
+        obs, obs_next, act, rew, done = buf._b_obs, buf._b_obs_, buf._b_act, buf._b_rew, buf._b_done
+        Do, k, c = self.Do, self.k, self.central
+        ddpg_inputs(obs, obs_next, act, central=c, out=(self._x_cur, self._x_next, self._x_pi))
+        _mlp_forward(lib, self._blob_ta, obs_next, self._y4)
+        ddpg_put_actions(self._y4, self._x_next, Do, k, central=c, own_only=False)
+        _mlp_forward(lib, self._blob_tc, self._x_next, self._yq4, self._q_next)
+        _mlp_forward(lib, self._blob_c, self._x_cur, self._yq4, self._q)
+        td_head(self._q, self._q_next, rew, done, self.gamma, out=(self._g_q, self._g_pi, self.td, self.stats[u]), workspace=self._head_ws)
+        row_c = _mlp_grad(lib, self._buf_c, self._blob_c, self._x_cur, self._g_q, False)
+        mlp_adam_step([self.critic], [row_c], [self.adam_critic], [self._blob_c], self.hyper_critic, self.step_critic,
+                      targets=[self.target_critic], target_blobs=[self._blob_tc], stats=self.step_stats_critic[u], workspace=self._adam_ws)
+        _mlp_forward(lib, self._blob_a, obs, self._y4)
+        ddpg_put_actions(self._y4, self._x_pi, Do, k, central=c, own_only=True)
+        _mlp_grad(lib, self._buf_c, self._blob_c, self._x_pi, self._g_pi, False, self._buf_c["gx"])
+        ddpg_action_grad(self._buf_c["gx"], Do, k, central=c, out=self._g_a4)
+        row_a = _mlp_grad(lib, self._buf_a, self._blob_a, obs, self._g_a4, True)
+        mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
+                      targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u], workspace=self._adam_ws)
+
+    def _run(self):
+        for u in range(self.updates):
+            self._update(u)
+
+    def update(self):
+        """`updates` updates, each on a fresh draw of the ring -> stats f64 [updates, 8] on the device (a cached buffer; no host
+        synchronisation).  The ring must hold at least one row."""
+        (self._graph.replay if self._graph is not None else self._run)()
+        return self.stats
+
+    def _state(self):
+        """Every tensor an update writes that outlives it."""
+        return ([self.buffer._draws, self.step_actor, self.step_critic, self._blob_a, self._blob_c, self._blob_ta, self._blob_tc, self.stats,
+                 self.step_stats_actor, self.step_stats_critic] + [t for st in (self.adam_actor, self.adam_critic) for t in (st.m, st.v)]
+                + [getattr(net, p) for net in (self.actor, self.critic, self.target_actor, self.target_critic) for p in PARAMS])
+
+    def capture(self):
+        """Record the whole update() -- `updates` updates, the ring's draws included -- as one graph on one stream; update() replays it
+        from then on.  One eager update runs first as the warm-up and is undone: capture() leaves parameters, targets, moments, step
+        counts, blobs, statistics and the ring's draw counter bit for bit as they were."""
+        self._graph = _capture(self._run, self._state, self.buffer.actor_states.device)
+        return self
+
+    def set_lr(self, actor=None, critic=None):
+        """The learning rates of the steps from now on, written to the hyper rows on the device (fills on the current stream: no host
+        synchronisation); a captured update reads them at every replay.  None leaves a rate as it is."""
+        for hyper, lr in ((self.hyper_actor, actor), (self.hyper_critic, critic)):
+            if lr is not None:
+                hyper[0].fill_(_hyper("lr", lr))
+
+    def sync(self):
+        """Re-pack all four blobs from their networks, once: for a caller who has edited parameters or targets from outside."""
+        for net, blob in ((self.actor, self._blob_a), (self.critic, self._blob_c), (self.target_actor, self._blob_ta),
+                          (self.target_critic, self._blob_tc)):
+            net.pack(out=blob)
+
+    def publish(self, rollout, columns):
+        """The team's actors into a PolicyRollout that plays them: the actor's blob rows into rollout.fused.weights[c0 : c0 + nA] (a blob
+        row is per agent and depends on obs_len alone) and the ten parameter slices into rollout.actor.  columns: this team's env
+        columns, a contiguous range, as append_rollout takes.  Device copies on the current stream (capturable); every other row of the
+        rollout's blob and parameters is left untouched."""
+        cols = [int(c) for c in columns]
+        c0 = cols[0] if cols else 0
+        ra = rollout.actor
+        if len(cols) != self.nA or cols != list(range(c0, c0 + len(cols))) or c0 < 0 or c0 + len(cols) > ra.n_actors:
+            raise ValueError(f"columns must be a contiguous range of {self.nA} of the rollout's {ra.n_actors} env columns")
+        if (ra.obs_len, ra.n_actions) != (self.Do, self.k) or ra.w1.device != self.actor.w1.device:
+            raise ValueError(f"the rollout's actor must have obs_len {self.Do} and {self.k} actions on {self.actor.w1.device}, got "
+                             f"{ra.obs_len} and {ra.n_actions} on {ra.w1.device}")
+        with torch.no_grad():
+            if rollout.fused is not None:
+                rollout.fused.weights[c0:c0 + self.nA].copy_(self._blob_a)
+            for p in PARAMS:
+                getattr(ra, p)[c0:c0 + self.nA].copy_(getattr(self.actor, p))

@@ -1,5 +1,5 @@
 """The GPU-side harness of the optimiser step's tests (learner.adam_step, learner.adam_step(group=), learner.mlp_adam_step: one body,
-learner._adam_step, and one kernel path, bsx_adam_step_mlp).  tests/test_hip_adam_step.py, test_hip_adam_shared.py, test_hip_adam_mlp.py
+learner.adam._adam_step, and one kernel path, bsx_adam_step_mlp).  tests/test_hip_adam_step.py, test_hip_adam_shared.py, test_hip_adam_mlp.py
 and tools/measure_adam_mlp.py build on it; the float64 arithmetic stays on the host side, in adam_util.py, shared_step_util.py and
 adam_mlp_util.py.
 

@@ -3,7 +3,7 @@ the ten parameter gradients and grad_x against float64 autograd at (2, 4) times 
 (tests/mlp_grad_util.py: ReLU kinks left out by construction; a larger factor only where profiles/mlp_input_grad.json records that the
 yardstick itself moves by as much: one-row cases, and b3 under row order), on the table of shapes from one row of one input to 32 agents over two
 rounds; exact zeros where grad_out is zero; the bits of bsx_actor_forward / bsx_actor_grad at (2n, 3n + 2), with and without grad_x,
-from the raw entries and from fused_apply and fused_mlp (one path in learner.py: both are held to the raw actor entries, not to each
+from the raw entries and from fused_apply and fused_mlp (one path in learner/mlp.py: both are held to the raw actor entries, not to each
 other), and the one buffer set they share on a network; guard slabs around grad_x at ragged sizes; the same bits on every call and from a captured graph; one DDPG step whose
 actor gradients come through the critic's input gradient; the documented refusals."""
 import numpy as np
