@@ -12,6 +12,12 @@ and of DDPGLearner share:
   learner_case       networks (mlp_grad_util.make_net "gains", w3 scaled by 60 and 100 as mlp_grad_util.ddpg_case does), ring rows, a
                      fixed batch and the row weights that leave every ReLU kink out, chosen in float64 alone
   maddpg_grads       the critic's and the actor's gradients of the two MADDPG losses by torch autograd on the CPU, in any dtype
+  stepped_case / update_reference   a whole update from target networks that are NOT the networks: the critic's gradient, the critic's
+                     step with its Polyak target (adam_mlp_util.reference_step), the actor's gradient at the STEPPED critic, the actor's
+                     step, the statistics -- in float64, and the same in float32 on the CPU as the yardstick; the row weights leave
+                     the stepped critic's kinks out too (a fixed point); wrong_variants: the misreadings the case tells apart;
+                     stepped_spread / stepped_exceptions / stepped_factor_of: the yardstick's own spread over row orders and the factors
+                     profiles/ddpg_float64.json records from it; check_step: adam_case_util.meets_the_bars' bars on one network
   Hand               one update by hand from the public primitives, holding what a DDPGLearner holds under the same names
   snapshot           every tensor an update writes, as bits
   torch_update       the torch composition: StackedActor under autograd, clip_grad_norm_, torch Adam, foreach Polyak
@@ -22,12 +28,15 @@ import copy
 import functools
 import json
 import os
+import types
 
 import numpy as np
 import torch
 
 import actor_grad_util as U
 import actor_ref_util as R
+import adam_mlp_util as AM
+import adam_util as AU
 import mlp_grad_util as M
 
 PARAMS = U.PARAMS
@@ -38,13 +47,32 @@ PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 SHAPES = ((1, 1, 1, 3, 0), (97, 1, 5, 3, 0), (97, 1, 5, 3, 1), (161, 2, 8, 4, 1), (129, 3, 11, 4, 1), (130, 16, 50, 4, 0), (64, 2, 5, 3, 1),
           (16385, 16, 1, 3, 0))
 LARGE = SHAPES[-1]
-LEARNER_SHAPES = ((64, 2, 5, 4, 0), (161, 2, 8, 4, 1), (129, 3, 11, 4, 1))
+# the learner's: 1v1, 2v2 and 3v3 at k = 4, then the shapes DDPG is for -- a continuous env (k = 3: the head pads to 4, g_a4's column 3 is
+# +0) at 1v1 own and central and at 2v2 central, 4v4 with own critics (Dc = 18), 16 agents with own critics (Do = 50, Dc = 54: the widest
+# actor input) and a batch of one row
+LEARNER_SHAPES = ((64, 2, 5, 4, 0), (161, 2, 8, 4, 1), (129, 3, 11, 4, 1), (97, 1, 5, 3, 0), (97, 1, 5, 3, 1), (96, 2, 8, 3, 1),
+                  (65, 4, 14, 4, 0), (130, 16, 50, 4, 0), (1, 1, 5, 4, 1))
 KINK_SHAPES = ((161, 2, 8, 4), (129, 3, 11, 4), (97, 1, 5, 3), (130, 16, 50, 4))
 GAMMA = 0.95
 # learner_case's generators start here.  Picked on the float64 reference alone: the share of elements the kink filter leaves out moves
 # between 0.6 % and 5.7 % from seed to seed (384 hidden values per element, each within 1e-4 of 0 with probability ~1e-4); of the bases
 # 0, 10, 20, 30 this is the one at which seeds 0 .. 2 stay under actor_grad_util.KINK_CAP at every shape of KINK_SHAPES (1.0 % .. 4.4 %)
 CASE_SEED = 30
+# the learner suite's hyper-parameters, and stepped_case's: the same with eps = 1e-3 for both steps.  That eps is a condition, not a
+# tuning: Adam's first step is lr g / (|g| + eps), whose slope in g is at most lr / eps.  At eps = 1e-8 a gradient component of the size
+# of float32's own error (about 1e-8) moves its parameter by up to lr, and the device's stepped critic and the reference's would
+# differ by far more than actor_grad_util.KINK; at eps = 1e-3 a 1e-8 error in g moves a parameter by 2e-8
+KW = dict(gamma=GAMMA, tau=0.05, lr_actor=1e-3, lr_critic=2e-3, max_grad_norm=0.5)
+STEP_KW = dict(KW, betas=(0.9, 0.999), eps=1e-3)
+# stepped_case's seed per shape, 0 where none is given.  Picked on the float64 reference alone, as CASE_SEED was: per shape the first
+# seed from 0 at which the kink filter closes within MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP.
+# Measured (share left out / rounds): 3v3 central 5.68 % / 2 at seed 0 and 4.65 % / 4 at seed 1; 16 agents own 6.25 % / 9 and
+# 4.66 % / 4; every other shape passes at seed 0 (0 % .. 4.04 %, 0 .. 2 rounds).  One base for all shapes was looked for first
+# (80 bases): the 16-agent shape passes at one base in five (zeroing a row moves its agent's stepped critic by about KINK, so the
+# filter closes slowly) and no base passed everywhere.  (96, 2, 8, 3, 1), the 2v2 k = 3 shape, passes at seed 0 as it is
+STEP_SEEDS = {(129, 3, 11, 4, 1): 1, (130, 16, 50, 4, 0): 1}
+MAX_ROUNDS = 4                                      # of stepped_case's kink filter
+SHARP = ("w1", "w2", "w3", "b3")                     # the tensors the sharpness check of test_ddpg_cpu.py reads
 TD_NAMES = ("g_q", "g_pi", "td")
 STAT_NAMES = ("critic_loss", "q", "target", "abs_td", "done", "weight")       # stats[1..6]
 
@@ -206,15 +234,22 @@ def check_td(got, ref, yard, e_stats, what=""):
               f"(factors {fm}, {fx}); max|x| {np.abs(ref[k]).max():.3e}")
         if not (ek.mean() <= fm * et.mean() and ek.max() <= fx * et.max()):
             bad.append(k)
-    if not (got["stats"][0] == ref["stats"][0] and got["stats"][7] == 0.0):
+    bad += stats_out_of_bounds(got["stats"], ref["stats"], e_stats, what)
+    assert not bad, (what, bad)
+
+
+def stats_out_of_bounds(got, ref, e_stats, what=""):
+    """The statistics' part of check_td -> the names out of bounds.  got, ref: float64 [8]; prints every figure."""
+    bad = []
+    if not (got[0] == ref[0] and got[7] == 0.0):
         bad.append("n")
     for i, name in enumerate(STAT_NAMES, start=1):
-        tol = 4 * max(e_stats[i], 0.5 * float(np.spacing(np.float32(abs(ref["stats"][i])))))
-        err = abs(got["stats"][i] - ref["stats"][i])
-        print(f"{what} stats.{name}: float64 {ref['stats'][i]:.9g}, kernel error {err:.3e}, yardstick's own (9 row orders) {e_stats[i]:.3e}, bound {tol:.3e}")
+        tol = 4 * max(e_stats[i], 0.5 * float(np.spacing(np.float32(abs(ref[i])))))
+        err = abs(got[i] - ref[i])
+        print(f"{what} stats.{name}: float64 {ref[i]:.9g}, kernel error {err:.3e}, yardstick's own (9 row orders) {e_stats[i]:.3e}, bound {tol:.3e}")
         if not err <= tol:
             bad.append(name)
-    assert not bad, (what, bad)
+    return bad
 
 
 # ------------------------------------------------------------------------------------------------ the learner's case
@@ -273,11 +308,12 @@ def learner_case(shape, seed=0):
     return actor, critic, rows, idx, w, float(near.double().mean())
 
 
-def maddpg_grads(actor, critic, batch, w, central, dtype, gamma=GAMMA, target_actor=None, target_critic=None):
+def maddpg_grads(actor, critic, batch, w, central, dtype, gamma=GAMMA, target_actor=None, target_critic=None, critic_pi=None):
     """({critic tensor: grad}, {actor tensor: grad}) as float64 arrays, torch autograd on the CPU in `dtype`, of
         critic:  sum_i mean_b w (Q_i(x_cur) - y)^2,  y = r + gamma (1 - done) Q'_i(x_next) held fixed, a' = the target actors' actions
         actor:   sum_i -mean_b w Q_i(x_pi),  x_pi = x_cur with agent i's own action slot replaced by pi_i(o_i)
-    batch: (obs, act, rew, obs_next, done) of B rows; the targets default to the networks themselves."""
+    batch: (obs, act, rew, obs_next, done) of B rows; the targets default to the networks themselves.  critic_pi: the critic the
+    actor's loss reads (an update's stepped critic; networks of any dtype are taken), `critic` itself if none."""
     def to(net):
         a = R._new(net.n_actors, net.obs_len, net.n_actions, dtype=dtype)
         with torch.no_grad():
@@ -285,6 +321,7 @@ def maddpg_grads(actor, critic, batch, w, central, dtype, gamma=GAMMA, target_ac
                 getattr(a, p).copy_(getattr(net, p).detach().cpu().to(dtype))
         return a
     a, c = to(actor), to(critic)
+    c_pi = to(critic_pi) if critic_pi is not None else c
     ta, tc = to(target_actor if target_actor is not None else actor), to(target_critic if target_critic is not None else critic)
     obs, act, rew, obs_next = (t.detach().cpu().to(dtype) for t in (batch[0], batch[1], batch[2], batch[3]))
     notdone, w = 1.0 - batch[4].detach().cpu().to(dtype), w.detach().cpu().to(dtype)
@@ -305,10 +342,192 @@ def maddpg_grads(actor, critic, batch, w, central, dtype, gamma=GAMMA, target_ac
         x_pi = torch.cat([obs.reshape(B, 1, -1).expand(B, nA, -1), actions.reshape(B, nA, nA * k)], -1)
     else:
         x_pi = torch.cat([obs, pi], -1)
-    actor_loss = -(w * c(x_pi, squash=False)[..., 0]).mean(0).sum()
+    actor_loss = -(w * c_pi(x_pi, squash=False)[..., 0]).mean(0).sum()
     ga = torch.autograd.grad(actor_loss, [getattr(a, p) for p in PARAMS])
     num = lambda gs: {p: g.double().numpy() for p, g in zip(PARAMS, gs)}            # noqa: E731
     return num(gc), num(ga)
+
+
+# ------------------------------------------------------------------------------------------------ a whole update with distinct targets
+def _net_of(arrays, like, dtype):
+    """A StackedActor of `like`'s shape on the CPU in `dtype` holding the ten arrays."""
+    net = R._new(like.n_actors, like.obs_len, like.n_actions, dtype=dtype)
+    with torch.no_grad():
+        for p, x in zip(PARAMS, arrays):
+            getattr(net, p).copy_(torch.as_tensor(np.asarray(x)).to(dtype))
+    return net
+
+
+def _step64(net, grads, target, lr, kw):
+    """adam_mlp_util.reference_step of a network's first step from zero moments -> dict(p, m, v, target: lists of ten float64 arrays,
+    norm, coef, net: the stepped network in float64)."""
+    hp = AU.hyper32(lr, *kw["betas"], kw["eps"], kw["max_grad_norm"] or 0.0)
+    P0 = AU.net_arrays(net)
+    Z = [np.zeros(x.shape) for x in P0]
+    P, M_, V, T, _, norm, coef = AM.reference_step(P0, [grads[p] for p in PARAMS], Z, Z, AU.net_arrays(target), 0, hp,
+                                                   float(np.float32(kw["tau"])))
+    return dict(p=P, m=M_, v=V, target=T, norm=norm, coef=coef, net=_net_of(P, net, torch.float64))
+
+
+def _step32(net, grads, target, lr, kw):
+    """The same step as a torch user takes it, in float32 on the CPU: clip_grad_norm_, torch.optim.Adam, target.mul_(1 - tau).add_(p,
+    alpha=tau) (adam_case_util.TorchPath's composition) -> the same dict, the arrays float32."""
+    hp = AU.hyper32(lr, *kw["betas"], kw["eps"], kw["max_grad_norm"] or 0.0)
+    tau = float(np.float32(kw["tau"]))
+    ps = [getattr(net, p).detach().clone().float().requires_grad_() for p in PARAMS]
+    ts = [getattr(target, p).detach().clone().float() for p in PARAMS]
+    for p, name in zip(ps, PARAMS):
+        p.grad = torch.from_numpy(grads[name]).float()
+    if hp["max_grad_norm"] > 0.0:
+        torch.nn.utils.clip_grad_norm_(ps, hp["max_grad_norm"])
+    opt = torch.optim.Adam(ps, lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
+    opt.step()
+    with torch.no_grad():
+        for t, p in zip(ts, ps):
+            t.mul_(1.0 - tau).add_(p, alpha=tau)
+    f = lambda xs: [x.detach().numpy() for x in xs]               # noqa: E731
+    return dict(p=f(ps), m=f([opt.state[p]["exp_avg"] for p in ps]), v=f([opt.state[p]["exp_avg_sq"] for p in ps]), target=f(ts),
+                net=_net_of(f(ps), net, torch.float32))
+
+
+def _q_inputs(actor, critic, ta, tc, batch, w, central, dtype):
+    """ref_td_head's inputs of a batch: q = the critic on x_cur and q_next = the target critic on x_next (a' from the target actor),
+    both evaluated on the CPU in `dtype`."""
+    obs, act, rew, obs_next, done = batch
+    B, nA, _ = act.shape
+    to = lambda n: R.to_float64(n) if dtype == torch.float64 else R.to_cpu32(n)     # noqa: E731
+    joined = lambda o, a: (torch.cat([o, a], -1) if not central else                # noqa: E731
+                           torch.cat([o.reshape(B, 1, -1), a.reshape(B, 1, -1)], -1).expand(B, nA, -1))
+    with torch.no_grad():
+        o, o2, a = obs.to(dtype), obs_next.to(dtype), act.to(dtype)
+        q = to(critic)(joined(o, a), squash=False)[..., 0]
+        q_next = to(tc)(joined(o2, to(ta)(o2)), squash=False)[..., 0]
+    return dict(q=q, q_next=q_next, rew=rew, done=done.to(torch.uint8), weight=w)
+
+
+def update_reference(actor, critic, ta, tc, batch, w, central, dtype, kw=None, perm=None):
+    """One whole update on the CPU in `dtype` (float64: the reference, with adam_mlp_util.reference_step as the two steps; float32:
+    the yardstick, torch's own Adam) -> dict(gc, ga: {tensor: grad}; critic, actor: _step64's / _step32's dict; inp: the TD head's
+    inputs).  The five parts: the critic's gradient with the target networks in y; the critic's step with its Polyak target; the
+    actor's gradient at THAT critic; the actor's step with its target; the TD head's inputs for the statistics.
+    perm: the batch's rows in another order (another float32 summation order of the same sums)."""
+    kw = kw or STEP_KW
+    if perm is not None:
+        batch, w = tuple(t[perm] for t in batch), w[perm]
+    gc, _ = maddpg_grads(actor, critic, batch, w, central, dtype, kw["gamma"], ta, tc)
+    step = _step64 if dtype == torch.float64 else _step32
+    sc = step(critic, gc, tc, kw["lr_critic"], kw)
+    _, ga = maddpg_grads(actor, critic, batch, w, central, dtype, kw["gamma"], ta, tc, critic_pi=sc["net"])
+    sa = step(actor, ga, ta, kw["lr_actor"], kw)
+    return dict(gc=gc, ga=ga, critic=sc, actor=sa, inp=_q_inputs(actor, critic, ta, tc, batch, w, central, dtype))
+
+
+def perturbed(net, gen, scale=0.05):
+    """A copy of a CPU network with scale * randn added to every parameter."""
+    out = R.to_cpu32(net)
+    with torch.no_grad():
+        for p in PARAMS:
+            getattr(out, p).add_(scale * torch.randn(getattr(out, p).shape, generator=gen))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def stepped_case(shape, seed=None):
+    """One update from learner_case's networks, ring rows and idx (at `seed`: STEP_SEEDS' for the shape if none is given) with target networks that are NOT the networks (each parameter plus
+    0.05 randn) and STEP_KW's hyper-parameters, on the CPU -> a namespace of
+      actor, critic, ta, tc, rows, idx, batch   the starting state (float32, CPU)
+      w, share, rounds   the row weights: learner_case's, and 0 also where the STEPPED critic (float64) has a pre-ReLU value within
+                         actor_grad_util.KINK of 0 at x_pi -- zeroing rows moves the critic's gradient and so the stepped critic, so the
+                         filter is repeated to its fixed point (`rounds` zeroing rounds, at most 4); share: the part left out at the end
+      ref, yard          update_reference in float64 and in float32
+      stats, e_stats     ref_td_head's float64 statistics and the float32 yardstick's own error on them over 9 row orders (td_case's)
+    Read-only."""
+    B, nA, Do, k, central = shape
+    seed = STEP_SEEDS.get(shape, 0) if seed is None else seed
+    actor, critic, rows, idx, w0, _ = learner_case(shape, seed)
+    g = torch.Generator().manual_seed(9700 + seed)
+    ta, tc = perturbed(actor, g), perturbed(critic, g)
+    batch = tuple(r[idx] for r in rows)
+    x_pi = joins64(actor, batch[0], batch[3], batch[1], central)[2]
+    w, rounds = w0.clone(), 0
+    while True:
+        ref = update_reference(actor, critic, ta, tc, batch, w, central, torch.float64)
+        near = (U.pre_relu64(ref["critic"]["net"], x_pi).abs() < U.KINK).any(-1).transpose(0, 1) & (w != 0)
+        if not near.any():
+            break
+        rounds += 1
+        assert rounds <= MAX_ROUNDS, (shape, seed, rounds)
+        w[near] = 0.0
+    yard = update_reference(actor, critic, ta, tc, batch, w, central, torch.float32)
+    stats = ref_td_head(ref["inp"])["stats"]
+    e_stats = np.abs(torch_td(yard["inp"], torch.float32)["stats"] - stats)
+    for p in range(8 if B > 1 else 0):
+        perm = torch.randperm(B, generator=torch.Generator().manual_seed(4000 + p))
+        e_stats = np.maximum(e_stats, np.abs(torch_td(yard["inp"], torch.float32, perm=perm)["stats"] - stats))
+    return types.SimpleNamespace(seed=seed, actor=actor, critic=critic, ta=ta, tc=tc, rows=rows, idx=idx, batch=batch, w=w, rounds=rounds,
+                                 share=float((w == 0).double().mean()), ref=ref, yard=yard, stats=stats, e_stats=e_stats)
+
+
+def wrong_variants(case, central):
+    """{name: ({tensor: |wrong - right| mean}, {tensor: the yardstick's mean error})} in float64: the critic's gradient with the live
+    networks as targets, with the live actor alone, with the live critic alone, and the actor's gradient at the UNSTEPPED critic."""
+    c = case
+    f = lambda **k: maddpg_grads(c.actor, c.critic, c.batch, c.w, central, torch.float64, STEP_KW["gamma"], **k)     # noqa: E731
+    wrong = {"live nets as targets": (f()[0], "gc"), "live actor only": (f(target_critic=c.tc)[0], "gc"),
+             "live critic only": (f(target_actor=c.ta)[0], "gc"), "actor at the unstepped critic": (f()[1], "ga")}
+    dist = lambda a, b: {p: float(np.abs(a[p] - b[p]).mean()) for p in SHARP}       # noqa: E731
+    return {name: (dist(g, c.ref[which]), dist(c.yard[which], c.ref[which])) for name, (g, which) in wrong.items()}
+
+
+def stepped_spread(shape, perms=8):
+    """{"gc" / "ga": {tensor: (max ratio, mean ratio)}}: how far the float32 yardstick's own error on the two gradients of stepped_case
+    moves when the batch's rows are summed in another order (actor_grad_util.spread; seeds 4000 + p).  No kernel output enters."""
+    c = stepped_case(shape)
+    others = [update_reference(c.actor, c.critic, c.ta, c.tc, c.batch, c.w, shape[4], torch.float32,
+                               perm=torch.randperm(shape[0], generator=torch.Generator().manual_seed(4000 + p)))
+              for p in range(perms if shape[0] > 1 else 0)]
+    return {which: U.spread(c.ref[which], c.yard[which], [o[which] for o in others]) for which in ("gc", "ga")}
+
+
+def stepped_exceptions(spreads):
+    """{shape id or "*": {"gc" / "ga": {tensor: [fm, fx]}}} from {shape id: stepped_spread's}: mlp_grad_util.factor_rule per shape,
+    gradient and tensor where it is not (2, 4); b3, the tensor with one value per agent and output, gets ONE pair for every shape and
+    both gradients, under "*": the rule on its largest spread (mlp_grad_util.exceptions_from's convention)."""
+    out, b3 = {}, [1.0, 1.0]
+    for sid, by in spreads.items():
+        for which, d in by.items():
+            for k, (mx, mn) in d.items():
+                if k == "b3":
+                    b3 = [max(b3[0], mx), max(b3[1], mn)]
+                elif M.factor_rule(mx, mn) != (FM, FX):
+                    out.setdefault(sid, {}).setdefault(which, {})[k] = list(M.factor_rule(mx, mn))
+    if M.factor_rule(*b3) != (FM, FX):
+        out["*"] = {"b3": list(M.factor_rule(*b3))}
+    return out
+
+
+def stepped_factor_of(shape, which):
+    """name -> (fm, fx) for a gradient of stepped_case: the exception profiles/ddpg_float64.json records (with the spread it came
+    from) for the shape or under "*", (2, 4) where it records none."""
+    f = json.load(open(PROFILE)).get("stepped", {}).get("factors", {})
+    own = f.get(shape_id(shape), {}).get(which, {})
+    return lambda name: tuple(own.get(name, f.get("*", {}).get(name, (FM, FX))))
+
+
+def check_step(got, ref, yard, what, out=None):
+    """adam_case_util.meets_the_bars' bars on one network's step: for each of parameters, m, v and target, pooled over the ten
+    tensors, mean |error| against the float64 step at most 2x the float32 yardstick's and the maximum at most 4x.  got: dict(p, m, v,
+    target) of lists of ten arrays from the device.  Prints the ratios (and keeps them in `out`), then asserts."""
+    bad = []
+    for k in ("p", "m", "v", "target"):
+        (em, ex), (tm, tx) = AU.pooled_errors(got[k], ref[k]), AU.pooled_errors(yard[k], ref[k])
+        assert tm > 0.0 and tx > 0.0, (what, k)
+        print(f"{what} {k}: mean ratio {em / tm:.3f} (<= 2), max ratio {ex / tx:.3f} (<= 4)")
+        if out is not None:
+            out[f"{what}.{k}"] = [round(em / tm, 4), round(ex / tx, 4)]
+        if em > 2.0 * tm or ex > 4.0 * tx:
+            bad.append((k, em, tm, ex, tx))
+    assert not bad, (what, bad)
 
 
 # ------------------------------------------------------------------------------------------------ one update by hand
@@ -337,7 +556,8 @@ class Hand:
     sample(), ddpg_inputs, bsx_mlp_forward, ddpg_put_actions, td_head, mlp_grad (its padded copy of grad_out included), mlp_adam_step,
     ddpg_action_grad."""
 
-    def __init__(self, buffer, actor, critic, central, gamma=GAMMA, tau=0.01, lr_actor=1e-3, lr_critic=1e-3, max_grad_norm=None, updates=1):
+    def __init__(self, buffer, actor, critic, central, gamma=GAMMA, tau=0.01, lr_actor=1e-3, lr_critic=1e-3, max_grad_norm=None, updates=1,
+                 betas=(0.9, 0.999), eps=1e-8):
         from deep_rl_battlespace_amd import learner as L
         self.buffer, self.actor, self.critic, self.central, self.gamma = buffer, actor, critic, bool(central), gamma
         self.target_actor, self.target_critic = copy.deepcopy(actor), copy.deepcopy(critic)
@@ -346,8 +566,8 @@ class Hand:
         self._blob_a, self._blob_c, self._blob_ta, self._blob_tc = (n.pack() for n in (actor, critic, self.target_actor, self.target_critic))
         dev = actor.w1.device
         self.adam_actor, self.adam_critic = L.AdamState(actor), L.AdamState(critic)
-        self.hyper_actor = L.adam_hyper(lr_actor, max_grad_norm=max_grad_norm, device=dev, tau=tau)
-        self.hyper_critic = L.adam_hyper(lr_critic, max_grad_norm=max_grad_norm, device=dev, tau=tau)
+        self.hyper_actor = L.adam_hyper(lr_actor, betas, eps, max_grad_norm, dev, tau)
+        self.hyper_critic = L.adam_hyper(lr_critic, betas, eps, max_grad_norm, dev, tau)
         self.step_actor, self.step_critic = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
         self.stats = torch.zeros((updates, 8), dtype=torch.float64, device=dev)
         self.step_stats_actor, self.step_stats_critic = (torch.zeros((updates, 4), dtype=torch.float64, device=dev) for _ in range(2))

@@ -1,7 +1,10 @@
 """The DDPG head's entry points without a GPU: header, library and binding agree; the workspace follows its formula; every refusal
 comes before any launch (fake addresses); the numpy restatements of tests/ddpg_util.py are what torch indexing and torch float64
-autograd give; the learner case's kink filter stays under its cap; DDPGLearner and the bindings refuse on the host."""
+autograd give; the learner case's kink filter stays under its cap; the stepped case (a whole update from distinct target networks)
+stays under the cap at its fixed point, and every misreading of the update lies far from its float64 reference; DDPGLearner and the
+bindings refuse on the host."""
 import ctypes
+import json
 import os
 import re
 
@@ -170,6 +173,69 @@ def test_the_kink_filter_of_the_learner_case_stays_under_the_cap(shape):
             *_, w, share = D.learner_case((B, nA, Do, k, central), seed)
             print(shape, "central" if central else "own", "seed", seed, f"left out {100 * share:.2f} %")
             assert share < U.KINK_CAP and float((w == 0).double().mean()) == share
+
+
+@pytest.mark.parametrize("shape", D.LEARNER_SHAPES, ids=D.shape_id)
+def test_the_stepped_case_stays_under_the_cap_and_its_kink_filter_has_reached_its_fixed_point(shape):
+    """stepped_case's row weights are 0 also where the STEPPED critic has a pre-ReLU value within KINK of 0 at x_pi; zeroing a row moves
+    that critic, so the filter is repeated.  It closed within MAX_ROUNDS and under the cap (both conditions on the float64 reference:
+    STEP_SEEDS), and at the end no row that still has a weight lies near a kink of the final stepped critic -- nor of the starting
+    networks, whose filter (learner_case's) the weights started from."""
+    B, nA, Do, k, central = shape
+    c = D.stepped_case(shape)
+    print(D.shape_id(shape), f"seed {c.seed}: left out {100 * c.share:.2f} % after {c.rounds} zeroing rounds")
+    assert c.share < U.KINK_CAP and c.rounds <= D.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
+    obs, act, _, obs_next, _ = c.batch
+    x_cur, _, x_pi = D.joins64(c.actor, obs, obs_next, act, central)
+    stepped = c.ref["critic"]["net"]
+    assert stepped.w1.dtype == torch.float64 and not torch.equal(stepped.w1, c.critic.w1.double())
+    near = torch.zeros((B, nA), dtype=torch.bool)
+    for net, x in ((stepped, x_pi), (c.critic, x_pi), (c.critic, x_cur), (c.actor, obs)):
+        near |= (U.pre_relu64(net, x).abs() < U.KINK).any(-1).transpose(0, 1)
+    assert not (near & (c.w != 0)).any()
+    _, _, _, _, w0, _ = D.learner_case(shape, c.seed)
+    assert bool(((c.w == 0) | (c.w == w0)).all()) and bool((w0[c.w != 0] != 0).all())      # rows were only ever zeroed
+    # the reference's own step: the targets moved by tau towards the stepped networks, the moments are the first step's
+    tau = float(np.float32(D.STEP_KW["tau"]))
+    for net, start, target in ((c.ref["critic"], c.critic, c.tc), (c.ref["actor"], c.actor, c.ta)):
+        for p, new, t_new, m in zip(D.PARAMS, net["p"], net["target"], net["m"]):
+            t0 = getattr(target, p).detach().double().numpy()
+            assert np.allclose(t_new, (1 - tau) * t0 + tau * new, rtol=0, atol=1e-15)
+            assert np.abs(new - getattr(start, p).detach().double().numpy()).max() <= 1.0001 * max(D.STEP_KW["lr_critic"], D.STEP_KW["lr_actor"])
+        assert 0.0 < net["coef"] <= 1.0 and net["norm"] > 0.0
+
+
+@pytest.mark.parametrize("shape", D.LEARNER_SHAPES, ids=D.shape_id)
+def test_every_wrong_reading_of_the_update_lies_far_from_the_reference(shape):
+    """What the float64 test of the update on the GPU can tell apart, shown on the CPU in float64 alone: the critic's gradient with the
+    live networks in place of the targets (both, the actor alone, the critic alone) and the actor's gradient at the unstepped critic
+    each lie, in the mean over w1, w2, w3 and b3 each, at least 1000 x the float32 yardstick's mean error from the right gradient -- a
+    condition (measured: 2e5 x and more), so a learner that made one of these mistakes cannot pass within the (2, 4) bars."""
+    c = D.stepped_case(shape)
+    assert not bool(c.batch[4].all())                             # some row is unfinished: the targets are read at all
+    smallest = {}
+    for name, (dist, yard) in D.wrong_variants(c, shape[4]).items():
+        ratios = {p: dist[p] / yard[p] for p in D.SHARP}
+        smallest[name] = min(ratios.values())
+        assert all(yard[p] > 0.0 for p in D.SHARP) and min(ratios.values()) >= 1000.0, (name, ratios)
+    print(D.shape_id(shape), "smallest wrong-variant ratio: " + ", ".join(f"{k} {v:.3g}" for k, v in smallest.items()))
+
+
+def test_the_profile_records_the_stepped_cases_and_its_factors_are_the_rule_on_the_recorded_spread():
+    """profiles/ddpg_float64.json: per shape the seed, the share left out and the rounds stepped_case gives; the factor exceptions are
+    mlp_grad_util.factor_rule of the yardstick's recorded spread and nothing else; every recorded kernel ratio lies within its bars."""
+    rec = json.load(open(D.PROFILE))["stepped"]
+    assert rec["factors"] == D.stepped_exceptions(rec["spread"]) and set(rec["factors"]) <= {"*"}
+    assert set(rec["cases"]) == set(rec["spread"]) == set(rec["kernel"]) == {D.shape_id(s) for s in D.LEARNER_SHAPES}
+    for shape in D.LEARNER_SHAPES:
+        c, r = D.stepped_case(shape), rec["cases"][D.shape_id(shape)]
+        assert r["seed"] == c.seed == D.STEP_SEEDS.get(shape, 0) and r["zeroing_rounds"] == c.rounds
+        assert abs(r["left_out_percent"] - 100 * c.share) <= 0.005 + 1e-9
+        assert min(rec["sharpness"][D.shape_id(shape)].values()) >= 1000
+        for name, (mean, mx) in rec["kernel"][D.shape_id(shape)].items():
+            which, tensor = name.split(".")
+            fm, fx = D.stepped_factor_of(shape, which)(tensor) if which in ("gc", "ga") else (D.FM, D.FX)
+            assert mean <= fm and mx <= fx, (shape, name)
 
 
 def test_the_maddpg_losses_of_the_reference_agree_with_the_by_hand_joins_in_float64():

@@ -1,29 +1,33 @@
 """DDPGLearner on the MI355X: an update is, bit for bit, the sequence of the public primitives written out by hand
 (tests/ddpg_util.py: Hand); a captured update replays as one graph with fresh draws and allocates nothing; the first update's two
-gradient rows against float64 CPU autograd of the two MADDPG losses with torch float32 autograd as the yardstick; finished rows keep the
-targets out; set_lr reaches a captured graph; publish writes the team's rows alone; and a bandit on which the captured updates must
-learn at least half of what the torch composition learns."""
+gradient rows against float64 CPU autograd of the two MADDPG losses with torch float32 autograd as the yardstick; a whole update from
+target networks that are not the networks -- both gradient rows, both steps, both Polyak targets, the statistics -- against float64, and
+a learner from such targets against the by-hand update; finished rows keep the targets out; set_lr reaches a captured graph; publish
+writes the team's rows alone; and a bandit on which the captured updates must learn at least half of what the torch composition learns."""
 import gc
 import json
+import os
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import adam_util as AU
 import ddpg_util as D
 import mlp_grad_util as M
 
 pytestmark = pytest.mark.gpu
 
-KW = dict(gamma=D.GAMMA, tau=0.05, lr_actor=1e-3, lr_critic=2e-3, max_grad_norm=0.5)
+KW = D.KW
 
 
-def _pair(shape, updates=1, rows=None, **kw):
-    """(a DDPGLearner, a Hand) from equal copies of the shape's starting state, each on a ring of its own with the same rows and seed."""
+def _pair(shape, updates=1, rows=None, seed=0, **kw):
+    """(a DDPGLearner, a Hand) from equal copies of the shape's starting state (learner_case at `seed`), each on a ring of its own with
+    the same rows and seed."""
     from deep_rl_battlespace_amd.learner import DDPGLearner
     B, nA, Do, k, central = shape
-    actor, critic, case_rows, *_ = D.learner_case(shape)
+    actor, critic, case_rows, *_ = D.learner_case(shape, seed)
     rows = case_rows if rows is None else rows
     kw = {**KW, **kw}
     learner = DDPGLearner(D.ring(rows, B), D.gpu_copy(actor), D.gpu_copy(critic), critic_input="central" if central else "own", updates=updates, **kw)
@@ -53,6 +57,10 @@ def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(
     assert {"actor.w1", "critic.w1", "target_actor.w2", "target_critic.w2", "_blob_a", "_blob_c", "_blob_ta", "_blob_tc", "adam_actor.m",
             "adam_critic.v", "stats", "step_stats_actor", "step_stats_critic", "draws"} <= moved
     _blobs_are_packs(learner)
+    if shape[3] == 3:                                                         # three actions: the head's fourth column carries nothing
+        pad = torch.from_numpy(AU.pad_mask(shape[2], 3)).cuda()
+        assert pad.sum() == 65 and not learner._g_a4.view(torch.int32)[..., 3].any()
+        assert not learner._buf_a["grad"].view(torch.int32)[:, pad].any() and learner._buf_a["grad"][:, ~pad].abs().max() > 0
 
 
 @pytest.mark.parametrize("shape", D.LEARNER_SHAPES, ids=D.shape_id)
@@ -69,7 +77,8 @@ def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_dra
         draws.append(captured.buffer.last_idx.clone())
         a, b = D.snapshot(captured), D.snapshot(eager)
         assert D.differing(a, b) == [], (u, D.differing(a, b))
-    assert not torch.equal(draws[0], draws[1]) and not torch.equal(draws[1], draws[2])        # fresh draws
+    # fresh draws (a batch of one row draws one of four indices: there the draw counter below and the eager twin say it)
+    assert shape[0] == 1 or (not torch.equal(draws[0], draws[1]) and not torch.equal(draws[1], draws[2]))
     assert int(captured.step_actor) == 6 == int(captured.step_critic) and int(captured.buffer._draws) == 6
     _blobs_are_packs(captured)
     del a, b
@@ -104,6 +113,91 @@ def test_the_first_updates_gradient_rows_against_float64_autograd_of_the_two_mad
     M.check(num(row_c, 1), gc64, gc32, f"DDPG critic {D.shape_id(shape)}", names=D.PARAMS)
     M.check(num(row_a, k), ga64, ga32, f"DDPG actor {D.shape_id(shape)}", names=D.PARAMS)
     assert all(float(np.abs(g).max()) > 0 for g in list(gc64.values()) + list(ga64.values()))
+
+
+def _set_targets(x, case, sync=False):
+    """The case's target networks into x's (a Hand or a DDPGLearner) and their blobs: re-packed in place, or through sync()."""
+    with torch.no_grad():
+        for t, src, blob in ((x.target_actor, case.ta, x._blob_ta), (x.target_critic, case.tc, x._blob_tc)):
+            for p in D.PARAMS:
+                getattr(t, p).copy_(getattr(src, p))
+            if not sync:
+                t.pack(out=blob)
+    if sync:
+        x.sync()
+
+
+def _step_arrays(x, which):
+    """dict(p, m, v, target) of lists of ten numpy arrays: x's network `which` ("actor" / "critic"), its moments and its target."""
+    net, state = getattr(x, which), getattr(x, "adam_" + which)
+    cut = lambda row: AU.row_to_tensors(row.detach().cpu().numpy(), net.n_actions)     # noqa: E731
+    return dict(p=AU.net_arrays(net), m=cut(state.m), v=cut(state.v), target=AU.net_arrays(getattr(x, "target_" + which)))
+
+
+@pytest.mark.parametrize("shape", D.LEARNER_SHAPES, ids=D.shape_id)
+def test_an_update_with_distinct_targets_and_a_stepped_critic_against_float64(shape):
+    """One whole update through the primitives (Hand.step with both optimiser steps) from target networks that are NOT the networks,
+    against ddpg_util.stepped_case's float64 reference with the same computation in float32 on the CPU as the yardstick: the critic's
+    gradient row reads y from the target critic on the target actors' actions, the actor's row is taken at the STEPPED critic
+    (tests/test_ddpg_cpu.py: each misreading lies 2e5 yardstick errors away), networks, moments and Polyak targets hold the bars of
+    adam_case_util.meets_the_bars, the statistics check_td's, and the four blobs are the packs of what they stand for.
+    BSX_DDPG_RATIOS_OUT names a file the measured ratios are appended to (profiles/ddpg_float64.json records them)."""
+    from deep_rl_battlespace_amd.learner import split_grad
+    B, nA, Do, k, central = shape
+    c = D.stepped_case(shape)
+    assert c.share < D.U.KINK_CAP
+    _, hand = _pair(shape, seed=c.seed, **D.STEP_KW)
+    _set_targets(hand, c)
+    _blobs_are_packs(hand)
+    s = hand.buffer.sample(c.idx)
+    dev_batch = (s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6])
+    for got, want in zip(dev_batch, c.batch):
+        assert torch.equal(got.cpu(), want)
+    row_c, row_a = hand.step(*dev_batch, 0, weight=c.w.cuda(), adam=True)
+    torch.cuda.synchronize()
+    sid, rec = D.shape_id(shape), {}
+    num = lambda row, na: {p: g.double().cpu().numpy() for p, g in zip(D.PARAMS, split_grad(row, na))}     # noqa: E731
+    for which, row, na in (("gc", row_c, 1), ("ga", row_a, k)):
+        r = D.U.check(num(row, na), c.ref[which], c.yard[which], f"DDPG {which} {sid}", D.PARAMS, D.stepped_factor_of(shape, which))
+        rec.update({f"{which}.{p}": [round(v[0], 4), round(v[1], 4)] for p, v in r.items()})
+    for which in ("critic", "actor"):
+        D.check_step(_step_arrays(hand, which), c.ref[which], c.yard[which], which, rec)
+    assert int(hand.step_critic) == 1 == int(hand.step_actor)
+    for which, stats, row in (("critic", hand.step_stats_critic, row_c), ("actor", hand.step_stats_actor, row_a)):
+        # (adam_case_util.check_stats' bound: the norm of the row the step read -- checked against float64 above -- and the clip
+        # coefficient from it, both float64 on the device)
+        got, norm = stats[0].cpu().numpy(), float(row.double().square().sum().sqrt())
+        coef = min(1.0, float(np.float32(D.STEP_KW["max_grad_norm"])) / (norm + 1e-6))
+        assert got[0] == 1 and abs(got[1] - norm) <= 1e-10 * norm and abs(got[2] - coef) <= 1e-10 * coef, (which, got, norm, coef)
+        assert coef < 1.0                                         # both steps are clipped at every shape: the coefficient is in the check
+    bad = D.stats_out_of_bounds(hand.stats[0].cpu().numpy(), c.stats, c.e_stats, f"DDPG {sid}")
+    assert not bad, bad
+    _blobs_are_packs(hand)
+    path = os.environ.get("BSX_DDPG_RATIOS_OUT")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps({"shape": sid, "ratios": rec}) + "\n")
+
+
+def test_a_learners_updates_from_distinct_targets_are_the_by_hand_updates_bit_for_bit():
+    """The same starting state on a DDPGLearner (its targets edited from outside, then sync()) and a Hand: three updates leave the same
+    bits, which carries the float64 checks of the Hand over to the learner where the targets differ from the networks."""
+    shape = D.LEARNER_SHAPES[1]
+    c = D.stepped_case(shape)
+    learner, hand = _pair(shape, seed=c.seed, **D.STEP_KW)
+    _set_targets(learner, c, sync=True)
+    _set_targets(hand, c)
+    _blobs_are_packs(learner)
+    start = D.snapshot(learner)
+    assert D.differing(start, D.snapshot(hand)) == []
+    assert not torch.equal(start["target_critic.w1"], start["critic.w1"]) and not torch.equal(start["_blob_ta"], start["_blob_a"])
+    for u in range(3):
+        learner.update()
+        hand.update()
+        a, b = D.snapshot(learner), D.snapshot(hand)
+        assert D.differing(a, b) == [], (u, D.differing(a, b))
+    assert int(learner.step_critic) == 3 and {"critic.w1", "target_critic.w1", "target_actor.w1"} <= set(D.differing(start, a))
+    _blobs_are_packs(learner)
 
 
 def test_finished_rows_keep_the_target_networks_out_of_every_gradient():
