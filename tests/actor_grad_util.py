@@ -11,23 +11,22 @@
                    |y| < 1e-4.  The same go feeds the reference, the yardstick and the kernel
   spread / row_permutation_spread / permutation_spread   how far the yardstick's own error moves under an equivalent float32
                    evaluation: the accumulator, the rows summed in another order, and the latter for a case of this file
-  factors / ratios / check  the bound: per tensor, mean(e_k) <= fm mean(e_t) and max(e_k) <= fx max(e_t), with (fm, fx) = the project's
-                   (2, 4) (actor_ref_util.F32_FACTORS) except where the recorded spread of the yardstick reaches them
-                   (profiles/actor_grad_float64.json says where and why)
-  CLIP, TAU, _to, _logp, _ppo   the PPO loss in torch (clipped surrogate + value loss - entropy bonus over the kept rows of a rollout
+  factors / check  the bound: yardstick_util's per-tensor bars, with (fm, fx) = the project's (2, 4) (yardstick_util.FACTORS)
+                   except where the recorded spread of the yardstick reaches them (profiles/actor_grad_float64.json says where and why)
+  CLIP, TAU, _to, _logp, _ppo, _ppo_own_error   the PPO loss in torch (clipped surrogate + value loss - entropy bonus over the kept rows of a rollout
                    record) that tests/test_hip_actor_grad.py and tests/test_hip_ppo_learner.py both hold the fused paths to
 
-plan, autograd_grads (with the input's gradient as an eleventh tensor "x" on request), spread, row_permutation_spread, ratios and check
+plan, autograd_grads (with the input's gradient as an eleventh tensor "x" on request), spread, row_permutation_spread and check
 are the one yardstick of every fused-gradient test: tests/mlp_grad_util.py brings its own cases and factors and imports these.
 Nothing here imports the native library but plan() and the fused legs of _logp and _ppo."""
 import functools
-import json
 import os
 
 import numpy as np
 import torch
 
 import actor_ref_util as R
+import yardstick_util as Y
 
 PARAMS = R.PARAMS
 KINK = 1e-4
@@ -92,9 +91,14 @@ def pre_relu64(actor, obs):
     return torch.cat([y1, y2], -1)
 
 
+def near_kink(*evaluations):
+    """bool [R, A]: where, in float64, a hidden unit of any of the (network, input [R, A, D]) pairs is within KINK of its ReLU's kink."""
+    return functools.reduce(torch.logical_or, ((pre_relu64(net, x).abs() < KINK).any(-1) for net, x in evaluations)).transpose(0, 1)
+
+
 def kink_free_go(actor, obs, seed=0):
     """(go float32 [R, A, outputs], share [A]): standard normals, 0 on the rows with a hidden unit within KINK of its ReLU's kink."""
-    near = (pre_relu64(actor, obs).abs() < KINK).any(-1).transpose(0, 1)           # [R, A]
+    near = near_kink((actor, obs))
     g = torch.Generator().manual_seed(3000 + seed)
     go = torch.randn((obs.shape[0], actor.n_actors, actor.n_actions), generator=g)
     go[near] = 0.0
@@ -158,15 +162,14 @@ def spread(g64, g32, others, names=PARAMS):
 
 
 def row_permutation_spread(net, x, go, g64, g32, squash, names=PARAMS, perms=8):
-    """spread over `perms` orders of the rows (seeds 4000 + p): the same network, the same rows, another summation order.  With "x" in
-    `names` the input's gradient is compared row by row."""
-    def permuted(p):
-        idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(4000 + p))
+    """spread over `perms` orders of the rows (yardstick_util.row_orders): the same network, the same rows, another summation order.
+    With "x" in `names` the input's gradient is compared row by row."""
+    def permuted(idx):
         gp = autograd_grads(net, x[idx].contiguous(), go[idx].contiguous(), squash, torch.float32, "x" in names)
         if "x" in names:
             gp["x"] = gp["x"][torch.argsort(idx).numpy()]
         return gp
-    return spread(g64, g32, (permuted(p) for p in range(perms if x.shape[0] > 1 else 0)), names)
+    return spread(g64, g32, (permuted(idx) for idx in list(Y.row_orders(x.shape[0], perms))[1:]), names)
 
 
 def permutation_spread(case, perms=8):
@@ -178,30 +181,14 @@ def permutation_spread(case, perms=8):
 @functools.lru_cache(maxsize=None)
 def factors():
     """{name: (mean factor, max factor)} from profiles/actor_grad_float64.json."""
-    f = json.load(open(PROFILE))["factors"]
-    return {k: tuple(f[k]) for k in PARAMS}
-
-
-def ratios(got, g64, g32, names=PARAMS):
-    """{name: (mean(e_k) / mean(e_t), max(e_k) / max(e_t), max(e_k) / max|g64|)}; 0 / 0 counts as 0, x / 0 as inf."""
-    out = {}
-    for k in names:
-        ek, et = np.abs(np.asarray(got[k], np.float64) - g64[k]), np.abs(g32[k] - g64[k])
-        out[k] = (float(ek.mean() / et.mean()) if et.mean() > 0 else (0.0 if ek.mean() == 0 else float("inf")),
-                  float(ek.max() / et.max()) if et.max() > 0 else (0.0 if ek.max() == 0 else float("inf")),
-                  float(ek.max() / max(np.abs(g64[k]).max(), 1e-300)))
-    return out
+    return {k: Y.factor_of(Y.recorded(PROFILE, "factors"))(k) for k in PARAMS}
 
 
 def check(got, g64, g32, what="", names=PARAMS, factor_of=None):
     """Every tensor of `names` within its factors (fm, fx) = factor_of(name) of the yardstick's error -- the actor's recorded factors()
     unless the caller brings its own; prints the figures first.  Returns the ratios."""
-    r = ratios(got, g64, g32, names)
-    f = {k: (factor_of or factors().__getitem__)(k) for k in names}
-    for k in names:
-        print(f"{what} {k}: mean ratio {r[k][0]:.3f} (<= {f[k][0]}), max ratio {r[k][1]:.3f} (<= {f[k][1]}), max error / max|g| {r[k][2]:.2e}")
-    bad = [(k, r[k]) for k in names if not (r[k][0] <= f[k][0] and r[k][1] <= f[k][1])]
-    assert not bad, (what, bad)
+    r, bad = Y.check_tensors([(k, got[k], g64[k], g32[k], (factor_of or factors().__getitem__)(k)) for k in names], what, "ratios")
+    assert not bad, (what, [(k, r[k]) for k in bad])
     return r
 
 
@@ -210,11 +197,7 @@ TAU, CLIP = 0.7, 0.2
 
 
 def _to(actor, device="cuda", dtype=torch.float32):
-    a = R._new(actor.n_actors, actor.obs_len, actor.n_actions, dtype=dtype, device=device)
-    with torch.no_grad():
-        for k in PARAMS:
-            getattr(a, k).copy_(getattr(actor, k).detach().to(device=device, dtype=dtype))
-    return a
+    return R.to(actor, device, dtype)
 
 
 def _logp(actor, ls, obs, act, kind, fused):
@@ -246,3 +229,47 @@ def _ppo(actor, critic, ls, rec, keep, kind, fused, device, dtype, perm=None):
     loss.backward()
     grads = lambda m: {k: getattr(m, k).grad.double().cpu().numpy() for k in PARAMS}   # noqa: E731
     return float(loss.detach().double()), grads(a), grads(c), (l.grad.double().cpu().numpy() if l is not None else None), ratio.detach().double().cpu()
+
+
+def nudge(net, scale, seed=5):
+    """Every parameter moved by scale * mean|p| * a standard normal (drawn on the CPU: the same step on every device)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for k in PARAMS:
+            p = getattr(net, k)
+            p.add_((scale * p.abs().mean().cpu() * torch.randn(p.shape, generator=g)).to(p.device))
+
+
+def _ppo_ladder(actor0, critic, ls, rec, kind, cols=None):
+    """The learner's policy a step away from the one that played (actor0 nudged), so that ratios leave 1 and some are clipped: the
+    smallest step of a fixed ladder that clips 5 % .. 60 % of the kept rows, chosen on the float64 reference alone.  Rows kept: the
+    agents' own decisions (mask; of the agent columns `cols` only: a scripted team's are not) away from every kink of the loss in float64
+    -- a hidden unit of either network or a ratio within KINK of a kink -- the same in every path.  -> (actor, critic, ls on the CPU,
+    keep [T, E, A], the figures)."""
+    critic, ls = _to(critic, "cpu"), (ls.cpu() if ls is not None else None)
+    T, E, A, D = rec["obs"].shape
+    flat_obs = rec["obs"].reshape(-1, A, D)
+    on = torch.zeros(A, dtype=torch.bool)
+    on[list(range(A)) if cols is None else cols] = True
+    masked = rec["mask"] & on
+    for scale in (0.03, 0.06, 0.12, 0.25, 0.5, 1.0):
+        actor = _to(actor0, "cpu")
+        nudge(actor, scale)
+        near = near_kink((actor, flat_obs), (critic, flat_obs)).reshape(T, E, A)
+        keep = masked & ~near
+        r64 = _ppo(actor, critic, ls, rec, keep, kind, False, "cpu", torch.float64)[4].reshape(T, E, A)
+        keep = keep & ((r64 - (1 - CLIP)).abs() > KINK) & ((r64 - (1 + CLIP)).abs() > KINK)
+        kept, clipped = int(keep.sum()), int((keep & ((r64 < 1 - CLIP) | (r64 > 1 + CLIP))).sum())
+        kink = float((masked & near).sum()) / max(int(masked.sum()), 1)
+        print(kind, "step", scale, "rows kept", kept, "of", int(masked.sum()), "masked; clipped", clipped)
+        if 0.05 * kept <= clipped <= 0.6 * kept:
+            break
+    return actor, critic, ls, keep, dict(step=scale, masked=int(masked.sum()), kept=kept, clipped=clipped, kink_share=kink)
+
+
+def _ppo_own_error(actor, critic, ls, rec, keep, kind, L64, l64):
+    """What the torch path itself loses on a record: _ppo in float32 on the GPU over yardstick_util.row_orders of the flattened rows,
+    against the float64 loss L64 and log_std gradient l64 -> (the loss in the given order, yardstick_util.scalar_bound of its largest
+    error, the largest error of log_std's gradient or 0.0 without one)."""
+    runs = [_ppo(actor, critic, ls, rec, keep, kind, False, "cuda", torch.float32, order) for order in Y.row_orders(keep[..., 0].numel())]
+    return runs[0][0], Y.scalar_bound(L64, max(abs(r[0] - L64) for r in runs)), (max(abs(r[3] - l64).max() for r in runs) if ls is not None else 0.0)

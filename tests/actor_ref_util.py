@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from trace_util import GOLDEN
+from yardstick_util import FACTORS as F32_FACTORS      # mean(e_k) <= 2 mean(e_t), max(e_k) <= 4 max(e_t): yardstick_util says where 2 and 4 come from
 
 MODES = ("f32", "bf16x6", "bf16x3")
 TERMS = {"bf16x3": 2, "bf16x6": 3}
@@ -27,7 +28,6 @@ BODY = PARAMS[:8]
 # class -> the team sizes it is run at (shipped: the checkpoints are 2v2 networks; trained_like: where no checkpoint exists)
 CLASS_SIZES = {"fresh": (1, 2, 3, 4, 6, 8), "shipped": (2,), "trained_like": (1, 3, 4), "flat_rows": (1, 2, 3, 4),
                "dead_half": (1, 2, 3, 4), "wide_obs": (1, 2, 3, 4)}
-F32_FACTORS = (2.0, 4.0)          # mean(e_k) <= 2 mean(e_t), max(e_k) <= 4 max(e_t): see bounds()
 ULP1 = 2.0 ** -24                 # half a float32 spacing just below 1: the unit of the absolute slack on a tanh output
 
 
@@ -42,21 +42,16 @@ def _new(A, D, na, dtype=torch.float32, device=None):
     return StackedActor(A, D, na, dtype=dtype, device=device)
 
 
-def to_float64(actor):
-    """A StackedActor(..., dtype=float64) copy on the CPU (float32 -> float64 is exact)."""
-    a = _new(actor.n_actors, actor.obs_len, actor.n_actions, dtype=torch.float64)
+def to(actor, device="cpu", dtype=torch.float32):
+    """A StackedActor copy of `actor` on `device` in `dtype` (float32 -> float64 is exact)."""
+    a = _new(actor.n_actors, actor.obs_len, actor.n_actions, dtype=dtype, device=device)
     with torch.no_grad():
         for k in PARAMS:
-            getattr(a, k).copy_(getattr(actor, k).detach().cpu().double())
+            getattr(a, k).copy_(getattr(actor, k).detach().to(device=device, dtype=dtype))
     return a
 
 
-def to_cpu32(actor):
-    a = _new(actor.n_actors, actor.obs_len, actor.n_actions)
-    with torch.no_grad():
-        for k in PARAMS:
-            getattr(a, k).copy_(getattr(actor, k).detach().cpu().float())
-    return a
+to_float64, to_cpu32 = functools.partial(to, dtype=torch.float64), to
 
 
 def head_sums64(actor, obs):
@@ -376,9 +371,7 @@ def errors_of(actor, obs):
 def bounds(mode, e_t, e_m2, e_m3):
     """(max bound, mean bound) of a precision mode's head sums.
     f32: mean(e_k) <= 2 mean(e_t), max(e_k) <= 4 max(e_t).  Split modes: mean(e_k) <= 2 (mean(e_m) + mean(e_t)), max(e_k) <= 4 (max(e_m) +
-    max(e_t)) with e_m the split model of the mode's term count.  Where 2 and 4 come from: across summation orders of the same float32
-    network on the CPU the mean error moved by at most 1.13x and the max by at most 1.3x; rsqrtf and packed FMAs cost a few ulp more;
-    the next-worse arithmetic (two bf16 terms instead of float32) loses 16 to 24 times more.  The factors are conditions, not fits."""
+    max(e_t)) with e_m the split model of the mode's term count.  yardstick_util.FACTORS says where 2 and 4 come from."""
     fm, fx = F32_FACTORS
     if mode == "f32":
         return fx * e_t.max(), fm * e_t.mean()

@@ -20,10 +20,12 @@ import os
 import numpy as np
 import torch
 
+import actor_ref_util as R
 import adam_mlp_util as MU
 import adam_util as U
 import guard_util as GU
 import shared_step_util as S
+import yardstick_util as Y
 
 STEPS = 5
 #       leg                lr     counter set to (before step index)   what it shows
@@ -36,12 +38,7 @@ AGENT_AXIS = lambda k: k not in ("step", "stats")     # noqa: E731     (a name o
 
 def clone_net(net, device=None):
     """A StackedActor with the bits of `net`'s parameters, on `device` (default: net's)."""
-    from deep_rl_battlespace_amd.rollout import StackedActor
-    out = StackedActor(net.n_actors, net.obs_len, net.n_actions, device=device or net.w1.device)
-    with torch.no_grad():
-        for k in U.PARAMS:
-            getattr(out, k).copy_(getattr(net, k).detach())
-    return out
+    return R.to(net, device or net.w1.device)
 
 
 class Case:
@@ -322,7 +319,7 @@ def record(name, leg, ratios, what="adam_step", env=None, key="config"):
 def meets_the_bars(case, yard, ref, name, leg, which=("p", "m", "v", "target"), env=None, key="config"):
     """Per network and for each of parameters, m, v and targets, pooled over the group leaders' ten tensors (log_std with network 0's
     p, m, v): mean |error| against the float64 restatement at most 2x that of torch's own float32 path on the same inputs, maximum at
-    most 4x.  Tensors without a reference (no target) are left out, and a column without any."""
+    most 4x (yardstick_util's pooled bars: a NaN fails).  Tensors without a reference (no target) are left out, and a column without any."""
     ratios, failed = {}, []
     for i, (mine, torchs, want) in enumerate(zip(case.groups(leaders=True), yard.groups(), ref)):
         for j, what in enumerate(("p", "m", "v", "target")[:len(want)]):
@@ -331,11 +328,11 @@ def meets_the_bars(case, yard, ref, name, leg, which=("p", "m", "v", "target"), 
                 continue
             pick = lambda xs: [xs[k] for k in keep]     # noqa: E731
             lead = [x[::case.group] for x in pick(want[j])]
-            (em, ex), (tm, tx) = U.pooled_errors(pick(mine[j]), lead), U.pooled_errors(pick(torchs[j]), lead)
+            tm, tx = Y.errors(pick(torchs[j]), lead)
             assert tm > 0.0 and tx > 0.0
-            ratios[f"net{i}.{what}"] = (em / tm, ex / tx)
-            if em > 2.0 * tm or ex > 4.0 * tx:
-                failed.append((i, what, em, tm, ex, tx))
+            ratios[f"net{i}.{what}"] = Y.error_ratios(pick(mine[j]), lead, pick(torchs[j]))
+            if not Y.within(ratios[f"net{i}.{what}"]):
+                failed.append((i, what, ratios[f"net{i}.{what}"], tm, tx))
     record(name, leg, ratios, ("mlp_adam_step" if case.entry == "mlp" else "adam_step") + (" shared" if case.group > 1 else ""), env, key)
     assert not failed, failed
 

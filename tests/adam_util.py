@@ -9,11 +9,12 @@
   pad_mask           where those pad columns are in a row
   w2b_words          the bfloat16 part of StackedActor.pack()'s blob restated on uint32 bit patterns (round to nearest even by hand, residuals
                      in float32, the blob's index map), and w2_edge_weights, a w2 that forces ties, their neighbours, carries and +-0
-  pooled_errors      mean and maximum |x - reference| over a network's ten tensors as ONE vector (the step is element-wise: a
-                     per-tensor maximum over the eight floats of a b3 is noise)
-"""
+
+The bars a step is held to are yardstick_util's, pooled over a network's ten tensors."""
 import numpy as np
 import torch
+
+import yardstick_util as Y
 
 PARAMS = ("w1", "b1", "g1", "h1", "w2", "b2", "g2", "h2", "w3", "b3")
 H = 64
@@ -170,7 +171,10 @@ def net_arrays(net):
     return [getattr(net, k).detach().cpu().numpy().copy() for k in PARAMS]
 
 
-def pooled_errors(got, ref):
-    """got, ref: lists of arrays of matching shapes -> (mean, max) of |got - ref| over all of them as one vector (float64)."""
-    d = np.concatenate([np.abs(np.asarray(g, np.float64) - np.asarray(r, np.float64)).ravel() for g, r in zip(got, ref)])
-    return float(d.mean()), float(d.max())
+def check_step(got, ref, yard, what, out=None, names=("p", "m", "v", "target")):
+    """yardstick_util's bars on one network's optimiser step, each of `names` pooled over the network's tensors.  got, ref, yard: {name:
+    list of arrays} from the device, the float64 step and the float32 yardstick (off float64 somewhere).  Prints, keeps the ratios in `out`."""
+    assert all(e > 0.0 for k in names for e in Y.errors(yard[k], ref[k])), what
+    r, bad = Y.check_tensors([(k, got[k], ref[k], yard[k], Y.FACTORS) for k in names], what, "pooled")
+    (out if out is not None else {}).update({f"{what}.{k}": [round(v[0], 4), round(v[1], 4)] for k, v in r.items()})
+    assert not bad, (what, bad, r)

@@ -6,11 +6,12 @@ and of DDPGLearner share:
                      three copies on arrays of any dtype (they move bits), the TD head in float64
   td_inputs / torch_td / td_case / check_td   the TD head's inputs (rounded to float32 once), the head as a torch user writes it with
                      autograd from q -- in float64 the check of the restatement, in float32 the yardstick --, both cached per shape, and
-                     the bounds: (2 x mean, 4 x max) of the yardstick's error for g_q, g_pi and td (actor_ref_util.F32_FACTORS; a wider
-                     factor only where profiles/ddpg_float64.json records one and why), stats within 4 x the yardstick's own error over
-                     9 row orders, at least half a float32 spacing
+                     yardstick_util's bounds: (2 x mean, 4 x max) of the yardstick's error for g_q, g_pi and td (a wider factor only
+                     where profiles/ddpg_float64.json records one and why), stats within its scalar_bound of own_error, the
+                     yardstick's own error over 9 row orders
   learner_case       networks (mlp_grad_util.make_net "gains", w3 scaled by 60 and 100 as mlp_grad_util.ddpg_case does), ring rows, a
                      fixed batch and the row weights that leave every ReLU kink out, chosen in float64 alone
+  joined / joined_pi the critic's inputs as a torch user writes them: the one torch statement of the join every composition here reads
   maddpg_grads       the critic's and the actor's gradients of the two MADDPG losses by torch autograd on the CPU, in any dtype
   stepped_case / update_reference   a whole update from target networks that are NOT the networks: the critic's gradient, the critic's
                      step with its Polyak target (adam_mlp_util.reference_step), the actor's gradient at the STEPPED critic, the actor's
@@ -26,7 +27,6 @@ and of DDPGLearner share:
 Nothing here imports the native library at import time."""
 import copy
 import functools
-import json
 import os
 import types
 
@@ -38,9 +38,10 @@ import actor_ref_util as R
 import adam_mlp_util as AM
 import adam_util as AU
 import mlp_grad_util as M
+import yardstick_util as Y
 
 PARAMS = U.PARAMS
-FM, FX = R.F32_FACTORS
+FM, FX = Y.FACTORS
 PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ddpg_float64.json")
 # (B, nA, Do, k, central).  The last: 16 385 x 16 = 262 160 elements = 1 025 tiles of 256, the first B at nA = 16 at which a workgroup of
 # the head pass takes two tiles (J = 2: 513 workgroups), and the merge's 128 threads per column go round their partial rows five times
@@ -101,6 +102,24 @@ def join(obs, act, central):
     B, nA, _ = obs.shape
     row = np.concatenate([obs.reshape(B, -1), act.reshape(B, -1)], -1)
     return np.repeat(row[:, None, :], nA, axis=1)
+
+
+def joined(obs, act, central):
+    """join as a torch user writes it (any dtype and device, under autograd)."""
+    if not central:
+        return torch.cat([obs, act], -1)
+    B, nA, _ = obs.shape
+    return torch.cat([obs.reshape(B, 1, -1), act.reshape(B, 1, -1)], -1).expand(B, nA, -1)
+
+
+def joined_pi(obs, act, pi, central):
+    """x_pi as a torch user writes it: row (b, i) is the replayed joint action with slot i replaced by pi_i(o_i)."""
+    if not central:
+        return torch.cat([obs, pi], -1)
+    B, nA, k = act.shape
+    own = torch.eye(nA, dtype=pi.dtype, device=pi.device).view(1, nA, nA, 1)
+    actions = own * pi.unsqueeze(1) + (1.0 - own) * act.unsqueeze(1)                  # [B, i, slot, k]
+    return torch.cat([obs.reshape(B, 1, -1).expand(B, nA, -1), actions.reshape(B, nA, nA * k)], -1)
 
 
 def ref_inputs(obs, obs_next, act, central, x_cur, x_next, x_pi):
@@ -190,8 +209,7 @@ def torch_td(inp, dtype, gamma=GAMMA, weight=True, perm=None):
     g_q[..., 0], g_pi[..., 0] = q.grad, q_pi.grad
     td = y
     if perm is not None:
-        inv = torch.empty_like(perm)
-        inv[perm] = torch.arange(perm.numel())
+        inv = torch.argsort(perm)
         g_q, g_pi, td = g_q[inv], g_pi[inv], td[inv]
     with torch.no_grad():
         d = q - y
@@ -207,49 +225,26 @@ def td_case(B, nA, weight=True, perms=8):
     `perms` permutations of the rows).  Computed once and shared: read-only."""
     inp = td_inputs(B, nA)
     ref, yard = ref_td_head(inp, weight=weight), torch_td(inp, torch.float32, weight=weight)
-    e_stats = np.abs(yard["stats"] - ref["stats"])
-    for p in range(perms if B > 1 else 0):
-        r = torch_td(inp, torch.float32, weight=weight, perm=torch.randperm(B, generator=torch.Generator().manual_seed(4000 + p)))
-        e_stats = np.maximum(e_stats, np.abs(r["stats"] - ref["stats"]))
-    return inp, ref, yard, e_stats
+    return inp, ref, yard, Y.own_error(lambda order: torch_td(inp, torch.float32, weight=weight, perm=order), ref, B, perms)[0]
 
 
 @functools.lru_cache(maxsize=None)
 def factors():
     """{tensor: (mean factor, max factor)}: the project's (2, 4), or what profiles/ddpg_float64.json records for a tensor (with why)."""
-    out = {k: (FM, FX) for k in TD_NAMES}
-    if os.path.exists(PROFILE):
-        for k, v in json.load(open(PROFILE)).get("factors", {}).items():
-            out[k] = tuple(v)
-    return out
+    return {k: Y.factor_of(Y.recorded(PROFILE, "factors"))(k) for k in TD_NAMES}
 
 
 def check_td(got, ref, yard, e_stats, what=""):
     """got: dict(g_q, g_pi, td, stats) of float64 numpy from the kernel.  Prints every figure, then asserts."""
-    bad = []
-    for k in TD_NAMES:
-        ek, et = np.abs(got[k] - ref[k]), np.abs(yard[k] - ref[k])
-        fm, fx = factors()[k]
-        print(f"{what} {k}: kernel mean / max error {ek.mean():.3e} / {ek.max():.3e}, yardstick {et.mean():.3e} / {et.max():.3e} "
-              f"(factors {fm}, {fx}); max|x| {np.abs(ref[k]).max():.3e}")
-        if not (ek.mean() <= fm * et.mean() and ek.max() <= fx * et.max()):
-            bad.append(k)
+    bad = Y.check_tensors([(k, got[k], ref[k], yard[k], factors()[k]) for k in TD_NAMES], what, unit="x")[1]
     bad += stats_out_of_bounds(got["stats"], ref["stats"], e_stats, what)
     assert not bad, (what, bad)
 
 
 def stats_out_of_bounds(got, ref, e_stats, what=""):
     """The statistics' part of check_td -> the names out of bounds.  got, ref: float64 [8]; prints every figure."""
-    bad = []
-    if not (got[0] == ref[0] and got[7] == 0.0):
-        bad.append("n")
-    for i, name in enumerate(STAT_NAMES, start=1):
-        tol = 4 * max(e_stats[i], 0.5 * float(np.spacing(np.float32(abs(ref[i])))))
-        err = abs(got[i] - ref[i])
-        print(f"{what} stats.{name}: float64 {ref[i]:.9g}, kernel error {err:.3e}, yardstick's own (9 row orders) {e_stats[i]:.3e}, bound {tol:.3e}")
-        if not err <= tol:
-            bad.append(name)
-    return bad
+    counts = [] if got[0] == ref[0] and got[7] == 0.0 else ["n"]
+    return counts + Y.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, what)
 
 
 # ------------------------------------------------------------------------------------------------ the learner's case
@@ -300,9 +295,7 @@ def learner_case(shape, seed=0):
     idx = torch.randint(0, 4 * B, (B,), generator=g)
     obs, act, _, obs_next, _ = (r[idx] for r in rows)
     x_cur, _, x_pi = joins64(actor, obs, obs_next, act, central)
-    near = (U.pre_relu64(actor, obs).abs() < U.KINK).any(-1) | (U.pre_relu64(critic, x_cur).abs() < U.KINK).any(-1) | \
-        (U.pre_relu64(critic, x_pi).abs() < U.KINK).any(-1)
-    near = near.transpose(0, 1)                                   # [B, nA]
+    near = U.near_kink((actor, obs), (critic, x_cur), (critic, x_pi))
     w = torch.randn((B, nA), generator=g)
     w[near] = 0.0
     return actor, critic, rows, idx, w, float(near.double().mean())
@@ -314,35 +307,17 @@ def maddpg_grads(actor, critic, batch, w, central, dtype, gamma=GAMMA, target_ac
         actor:   sum_i -mean_b w Q_i(x_pi),  x_pi = x_cur with agent i's own action slot replaced by pi_i(o_i)
     batch: (obs, act, rew, obs_next, done) of B rows; the targets default to the networks themselves.  critic_pi: the critic the
     actor's loss reads (an update's stepped critic; networks of any dtype are taken), `critic` itself if none."""
-    def to(net):
-        a = R._new(net.n_actors, net.obs_len, net.n_actions, dtype=dtype)
-        with torch.no_grad():
-            for p in PARAMS:
-                getattr(a, p).copy_(getattr(net, p).detach().cpu().to(dtype))
-        return a
+    to = lambda net: U._to(net, "cpu", dtype)                      # noqa: E731
     a, c = to(actor), to(critic)
     c_pi = to(critic_pi) if critic_pi is not None else c
     ta, tc = to(target_actor if target_actor is not None else actor), to(target_critic if target_critic is not None else critic)
     obs, act, rew, obs_next = (t.detach().cpu().to(dtype) for t in (batch[0], batch[1], batch[2], batch[3]))
     notdone, w = 1.0 - batch[4].detach().cpu().to(dtype), w.detach().cpu().to(dtype)
-    B, nA, k = act.shape
-
-    def joined(o, actions):
-        if not central:
-            return torch.cat([o, actions], -1)
-        return torch.cat([o.reshape(B, 1, -1), actions.reshape(B, 1, -1)], -1).expand(B, nA, -1)
     with torch.no_grad():
-        y = rew + gamma * notdone * tc(joined(obs_next, ta(obs_next)), squash=False)[..., 0]
-    critic_loss = (w * (c(joined(obs, act), squash=False)[..., 0] - y) ** 2).mean(0).sum()
+        y = rew + gamma * notdone * tc(joined(obs_next, ta(obs_next), central), squash=False)[..., 0]
+    critic_loss = (w * (c(joined(obs, act, central), squash=False)[..., 0] - y) ** 2).mean(0).sum()
     gc = torch.autograd.grad(critic_loss, [getattr(c, p) for p in PARAMS])
-    pi = a(obs)
-    if central:                                                    # row (b, i): the replayed actions with slot i replaced by pi_i(o_i)
-        own = torch.eye(nA, dtype=dtype).view(1, nA, nA, 1)
-        actions = own * pi.unsqueeze(1) + (1.0 - own) * act.unsqueeze(1)              # [B, i, slot, k]
-        x_pi = torch.cat([obs.reshape(B, 1, -1).expand(B, nA, -1), actions.reshape(B, nA, nA * k)], -1)
-    else:
-        x_pi = torch.cat([obs, pi], -1)
-    actor_loss = -(w * c_pi(x_pi, squash=False)[..., 0]).mean(0).sum()
+    actor_loss = -(w * c_pi(joined_pi(obs, act, a(obs), central), squash=False)[..., 0]).mean(0).sum()
     ga = torch.autograd.grad(actor_loss, [getattr(a, p) for p in PARAMS])
     num = lambda gs: {p: g.double().numpy() for p, g in zip(PARAMS, gs)}            # noqa: E731
     return num(gc), num(ga)
@@ -394,14 +369,11 @@ def _q_inputs(actor, critic, ta, tc, batch, w, central, dtype):
     """ref_td_head's inputs of a batch: q = the critic on x_cur and q_next = the target critic on x_next (a' from the target actor),
     both evaluated on the CPU in `dtype`."""
     obs, act, rew, obs_next, done = batch
-    B, nA, _ = act.shape
-    to = lambda n: R.to_float64(n) if dtype == torch.float64 else R.to_cpu32(n)     # noqa: E731
-    joined = lambda o, a: (torch.cat([o, a], -1) if not central else                # noqa: E731
-                           torch.cat([o.reshape(B, 1, -1), a.reshape(B, 1, -1)], -1).expand(B, nA, -1))
+    to = lambda n: U._to(n, "cpu", dtype)                          # noqa: E731
     with torch.no_grad():
         o, o2, a = obs.to(dtype), obs_next.to(dtype), act.to(dtype)
-        q = to(critic)(joined(o, a), squash=False)[..., 0]
-        q_next = to(tc)(joined(o2, to(ta)(o2)), squash=False)[..., 0]
+        q = to(critic)(joined(o, a, central), squash=False)[..., 0]
+        q_next = to(tc)(joined(o2, to(ta)(o2), central), squash=False)[..., 0]
     return dict(q=q, q_next=q_next, rew=rew, done=done.to(torch.uint8), weight=w)
 
 
@@ -442,7 +414,7 @@ def stepped_case(shape, seed=None):
       ref, yard          update_reference in float64 and in float32
       stats, e_stats     ref_td_head's float64 statistics and the float32 yardstick's own error on them over 9 row orders (td_case's)
     Read-only."""
-    B, nA, Do, k, central = shape
+    central = shape[4]
     seed = STEP_SEEDS.get(shape, 0) if seed is None else seed
     actor, critic, rows, idx, w0, _ = learner_case(shape, seed)
     g = torch.Generator().manual_seed(9700 + seed)
@@ -452,7 +424,7 @@ def stepped_case(shape, seed=None):
     w, rounds = w0.clone(), 0
     while True:
         ref = update_reference(actor, critic, ta, tc, batch, w, central, torch.float64)
-        near = (U.pre_relu64(ref["critic"]["net"], x_pi).abs() < U.KINK).any(-1).transpose(0, 1) & (w != 0)
+        near = U.near_kink((ref["critic"]["net"], x_pi)) & (w != 0)
         if not near.any():
             break
         rounds += 1
@@ -460,12 +432,9 @@ def stepped_case(shape, seed=None):
         w[near] = 0.0
     yard = update_reference(actor, critic, ta, tc, batch, w, central, torch.float32)
     stats = ref_td_head(ref["inp"])["stats"]
-    e_stats = np.abs(torch_td(yard["inp"], torch.float32)["stats"] - stats)
-    for p in range(8 if B > 1 else 0):
-        perm = torch.randperm(B, generator=torch.Generator().manual_seed(4000 + p))
-        e_stats = np.maximum(e_stats, np.abs(torch_td(yard["inp"], torch.float32, perm=perm)["stats"] - stats))
     return types.SimpleNamespace(seed=seed, actor=actor, critic=critic, ta=ta, tc=tc, rows=rows, idx=idx, batch=batch, w=w, rounds=rounds,
-                                 share=float((w == 0).double().mean()), ref=ref, yard=yard, stats=stats, e_stats=e_stats)
+                                 share=float((w == 0).double().mean()), ref=ref, yard=yard, stats=stats,
+                                 e_stats=Y.own_error(lambda order: torch_td(yard["inp"], torch.float32, perm=order), dict(stats=stats), shape[0])[0])
 
 
 def wrong_variants(case, central):
@@ -481,53 +450,24 @@ def wrong_variants(case, central):
 
 def stepped_spread(shape, perms=8):
     """{"gc" / "ga": {tensor: (max ratio, mean ratio)}}: how far the float32 yardstick's own error on the two gradients of stepped_case
-    moves when the batch's rows are summed in another order (actor_grad_util.spread; seeds 4000 + p).  No kernel output enters."""
+    moves when the batch's rows are summed in another order (actor_grad_util.spread over yardstick_util.row_orders).  No kernel output enters."""
     c = stepped_case(shape)
-    others = [update_reference(c.actor, c.critic, c.ta, c.tc, c.batch, c.w, shape[4], torch.float32,
-                               perm=torch.randperm(shape[0], generator=torch.Generator().manual_seed(4000 + p)))
-              for p in range(perms if shape[0] > 1 else 0)]
+    others = [update_reference(c.actor, c.critic, c.ta, c.tc, c.batch, c.w, shape[4], torch.float32, perm=order)
+              for order in list(Y.row_orders(shape[0], perms))[1:]]
     return {which: U.spread(c.ref[which], c.yard[which], [o[which] for o in others]) for which in ("gc", "ga")}
 
 
-def stepped_exceptions(spreads):
-    """{shape id or "*": {"gc" / "ga": {tensor: [fm, fx]}}} from {shape id: stepped_spread's}: mlp_grad_util.factor_rule per shape,
-    gradient and tensor where it is not (2, 4); b3, the tensor with one value per agent and output, gets ONE pair for every shape and
-    both gradients, under "*": the rule on its largest spread (mlp_grad_util.exceptions_from's convention)."""
-    out, b3 = {}, [1.0, 1.0]
-    for sid, by in spreads.items():
-        for which, d in by.items():
-            for k, (mx, mn) in d.items():
-                if k == "b3":
-                    b3 = [max(b3[0], mx), max(b3[1], mn)]
-                elif M.factor_rule(mx, mn) != (FM, FX):
-                    out.setdefault(sid, {}).setdefault(which, {})[k] = list(M.factor_rule(mx, mn))
-    if M.factor_rule(*b3) != (FM, FX):
-        out["*"] = {"b3": list(M.factor_rule(*b3))}
-    return out
+stepped_exceptions = Y.exceptions_from              # {shape id or "*": {"gc" / "ga": {tensor: [fm, fx]}}} from {shape id: stepped_spread's}
 
 
 def stepped_factor_of(shape, which):
     """name -> (fm, fx) for a gradient of stepped_case: the exception profiles/ddpg_float64.json records (with the spread it came
     from) for the shape or under "*", (2, 4) where it records none."""
-    f = json.load(open(PROFILE)).get("stepped", {}).get("factors", {})
-    own = f.get(shape_id(shape), {}).get(which, {})
-    return lambda name: tuple(own.get(name, f.get("*", {}).get(name, (FM, FX))))
+    f = Y.recorded(PROFILE, "stepped", "factors")
+    return Y.factor_of(f.get(shape_id(shape), {}).get(which, {}), f.get("*", {}))
 
 
-def check_step(got, ref, yard, what, out=None):
-    """adam_case_util.meets_the_bars' bars on one network's step: for each of parameters, m, v and target, pooled over the ten
-    tensors, mean |error| against the float64 step at most 2x the float32 yardstick's and the maximum at most 4x.  got: dict(p, m, v,
-    target) of lists of ten arrays from the device.  Prints the ratios (and keeps them in `out`), then asserts."""
-    bad = []
-    for k in ("p", "m", "v", "target"):
-        (em, ex), (tm, tx) = AU.pooled_errors(got[k], ref[k]), AU.pooled_errors(yard[k], ref[k])
-        assert tm > 0.0 and tx > 0.0, (what, k)
-        print(f"{what} {k}: mean ratio {em / tm:.3f} (<= 2), max ratio {ex / tx:.3f} (<= 4)")
-        if out is not None:
-            out[f"{what}.{k}"] = [round(em / tm, 4), round(ex / tx, 4)]
-        if em > 2.0 * tm or ex > 4.0 * tx:
-            bad.append((k, em, tm, ex, tx))
-    assert not bad, (what, bad)
+check_step = AU.check_step
 
 
 # ------------------------------------------------------------------------------------------------ one update by hand
@@ -622,8 +562,7 @@ def ring(rows, B, seed=3, device="cuda"):
     return buf
 
 
-def gpu_copy(net, device="cuda"):
-    return U._to(net, device)
+gpu_copy = U._to
 
 
 # ------------------------------------------------------------------------------------------------ the torch composition, the bandit
@@ -631,28 +570,15 @@ def torch_update(actor, critic, target_actor, target_critic, opt_a, opt_c, batch
     """One MADDPG update the way a torch user writes it (any device): autograd through StackedActor, clip_grad_norm_, the two Adam
     steps (critic first, the actor against the stepped critic), foreach Polyak."""
     obs, act, rew, obs_next, done = batch
-    B, nA, k = act.shape
-
-    def joined(o, actions):
-        if not central:
-            return torch.cat([o, actions], -1)
-        return torch.cat([o.reshape(B, 1, -1), actions.reshape(B, 1, -1)], -1).expand(B, nA, -1)
     with torch.no_grad():
-        y = rew + gamma * (1.0 - done.to(rew.dtype)) * target_critic(joined(obs_next, target_actor(obs_next)), squash=False)[..., 0]
+        y = rew + gamma * (1.0 - done.to(rew.dtype)) * target_critic(joined(obs_next, target_actor(obs_next), central), squash=False)[..., 0]
     opt_c.zero_grad(set_to_none=True)
-    ((critic(joined(obs, act), squash=False)[..., 0] - y) ** 2).mean(0).sum().backward()
+    ((critic(joined(obs, act, central), squash=False)[..., 0] - y) ** 2).mean(0).sum().backward()
     if max_grad_norm is not None:
         torch.nn.utils.clip_grad_norm_(critic.parameters(), max_grad_norm)
     opt_c.step()
-    pi = actor(obs)
-    if central:
-        own = torch.eye(nA, dtype=pi.dtype, device=pi.device).view(1, nA, nA, 1)
-        actions = own * pi.unsqueeze(1) + (1.0 - own) * act.unsqueeze(1)
-        x_pi = torch.cat([obs.reshape(B, 1, -1).expand(B, nA, -1), actions.reshape(B, nA, nA * k)], -1)
-    else:
-        x_pi = torch.cat([obs, pi], -1)
     opt_a.zero_grad(set_to_none=True)
-    (-critic(x_pi, squash=False)[..., 0].mean(0).sum()).backward()
+    (-critic(joined_pi(obs, act, actor(obs), central), squash=False)[..., 0].mean(0).sum()).backward()
     if max_grad_norm is not None:
         torch.nn.utils.clip_grad_norm_(actor.parameters(), max_grad_norm)
     opt_a.step()

@@ -6,29 +6,29 @@ bsx_mlp_grad) share:
   build / reference   per case, cached: the network, x uniform in [-1, 1], a kink-free go (actor_grad_util.kink_free_go: 0 on every row
                    where, in float64, a pre-ReLU value is within 1e-4 of 0), the float64 autograd gradients of (y * go).sum() in the ten
                    parameters AND in x (torch on the CPU), the float32 ones of the same (the yardstick), the share of rows left out
-  ratios / check   actor_grad_util's, with x as an eleventh tensor: mean(e_k) <= fm mean(e_t), max(e_k) <= fx max(e_t),
-                   (fm, fx) = actor_ref_util.F32_FACTORS = (2, 4) for every tensor, except where the recorded spread of the yardstick
-                   itself reaches them (factor_of: profiles/mlp_input_grad.json says where and why)
+  check            actor_grad_util's, with x as an eleventh tensor: mean(e_k) <= fm mean(e_t), max(e_k) <= fx max(e_t),
+                   (fm, fx) = yardstick_util.FACTORS = (2, 4) for every tensor, except where the recorded spread of the yardstick
+                   itself reaches them (factors: profiles/mlp_input_grad.json says where and why)
   unit_permutation_spread   how far the yardstick's own error moves when the SAME network is written with its hidden units in another
                    order (another summation order of the same float32 sums): the spread a one-row case has, where no row order exists
   row_permutation_spread    the same under another order of the rows (actor_grad_util.row_permutation_spread): what moves b3
-  factor_rule      the rule that turns a recorded spread into factors, stated once (tools/measure_mlp_grad.py writes what it gives)
+  factor_rule      yardstick_util's: the rule that turns a recorded spread into factors (tools/measure_mlp_grad.py writes what it gives)
   plan / spread    actor_grad_util's: workgroups per agent and rounds of a bsx_mlp_grad launch; the spread accumulator
   ddpg_case        one DDPG step at 1v1: actor 5 -> 4, critic 9 -> 1, 96 rows, the row weights w that leave both networks' kinks out
 
 Nothing here imports the native library but plan()."""
 import functools
-import json
 import os
 
 import torch
 
 import actor_grad_util as U
 import actor_ref_util as R
+import yardstick_util as Y
 
 PARAMS = U.PARAMS
 TENSORS = PARAMS + ("x",)
-FM, FX = R.F32_FACTORS
+(FM, FX), factor_rule = Y.FACTORS, Y.factor_rule
 KINK_CAP, plan, spread = U.KINK_CAP, U.plan, U.spread
 PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mlp_input_grad.json")
 
@@ -75,14 +75,7 @@ def build(case, seed=0):
     return net, x, go, share
 
 
-def autograd_grads(net, x, go, squash, dtype):
-    """actor_grad_util.autograd_grads with the input's gradient: the ten parameters and "x"."""
-    return U.autograd_grads(net, x, go, squash, dtype, input_grad=True)
-
-
-def ratios(got, g64, g32, names=TENSORS):
-    """actor_grad_util.ratios over x as well."""
-    return U.ratios(got, g64, g32, names)
+autograd_grads = functools.partial(U.autograd_grads, input_grad=True)        # the ten parameters' gradients and "x", the input's
 
 
 @functools.lru_cache(maxsize=None)
@@ -124,47 +117,22 @@ def row_permutation_spread(case, perms=8):
     return U.row_permutation_spread(net, x, go, g64, g32, case[3], TENSORS, perms)
 
 
-def factor_rule(max_spread, mean_spread):
-    """(fm, fx) from a tensor's recorded yardstick spread: the project's (2, 4) while the spread stays below them; where the yardstick's
-    own mean moves by 2x or its max by 4x under an equivalent float32 evaluation, twice the recorded spread (what profiles/
-    actor_grad_float64.json does for b3), never less than (2, 4)."""
-    if mean_spread < FM and max_spread < FX:
-        return (FM, FX)
-    return (max(FM, round(2 * mean_spread, 2)), max(FX, round(2 * max_spread, 2)))
-
-
 def exceptions_from(spreads):
-    """{case id or "*": {tensor: [fm, fx]}} from {source: {case id: {tensor: [max ratio, mean ratio]}}}: per case and tensor, factor_rule
-    of the largest recorded spread over the sources where it is not (FM, FX); b3, the tensor with one value per agent and output, gets ONE
-    pair for every case, under "*": factor_rule of its largest spread over all cases (what profiles/actor_grad_float64.json does)."""
-    out, b3 = {}, [1.0, 1.0]
-    for cid in (case_id(c) for c in CASES):
-        for k in TENSORS:
-            mx, mn = max(s[cid][k][0] for s in spreads.values()), max(s[cid][k][1] for s in spreads.values())
-            if k == "b3":
-                b3 = [max(b3[0], mx), max(b3[1], mn)]
-            elif factor_rule(mx, mn) != (FM, FX):
-                out.setdefault(cid, {})[k] = list(factor_rule(mx, mn))
-    if factor_rule(*b3) != (FM, FX):
-        out["*"] = {"b3": list(factor_rule(*b3))}
-    return out
+    """{case id or "*": {tensor: [fm, fx]}} from {source: {case id: {tensor: [max ratio, mean ratio]}}}: yardstick_util.exceptions_from
+    on, per case and tensor, the largest recorded spread over the sources."""
+    return Y.exceptions_from({cid: {k: [max(s[cid][k][i] for s in spreads.values()) for i in (0, 1)] for k in TENSORS}
+                              for cid in map(case_id, CASES)})
 
 
 @functools.lru_cache(maxsize=None)
 def factors():
     """{case id or "*": {tensor: (fm, fx)}}: the exceptions recorded in profiles/mlp_input_grad.json; everything else is (FM, FX)."""
-    f = json.load(open(PROFILE)).get("factors", {}).get("exceptions", {})
-    return {cid: {k: tuple(v) for k, v in t.items()} for cid, t in f.items()}
-
-
-def factor_of(cid):
-    """name -> (fm, fx) for case `cid`: its recorded exception, the one under "*", or (FM, FX)."""
-    return lambda k: factors().get(cid, {}).get(k, factors().get("*", {}).get(k, (FM, FX)))
+    return {cid: {k: tuple(v) for k, v in t.items()} for cid, t in Y.recorded(PROFILE, "factors", "exceptions").items()}
 
 
 def check(got, g64, g32, what="", names=TENSORS, cid=None):
-    """actor_grad_util.check with case `cid`'s factors.  Returns the ratios."""
-    return U.check(got, g64, g32, what, names, factor_of(cid))
+    """actor_grad_util.check with case `cid`'s factors: its recorded exception, the one under "*", or (FM, FX).  Returns the ratios."""
+    return U.check(got, g64, g32, what, names, Y.factor_of(factors().get(cid, {}), factors().get("*", {})))
 
 
 # ------------------------------------------------------------------------------------------------ one DDPG step
@@ -187,9 +155,7 @@ def ddpg_case(seed=0):
     target = torch.randn((rows, A), generator=g)
     with torch.no_grad():
         pi = R.to_float64(actor)(obs.double())
-    near = (U.pre_relu64(actor, obs).abs() < U.KINK).any(-1) | (U.pre_relu64(critic, torch.cat([obs, act], -1)).abs() < U.KINK).any(-1) | \
-        (U.pre_relu64(critic, torch.cat([obs.double(), pi], -1)).abs() < U.KINK).any(-1)
-    near = near.transpose(0, 1)                                    # [R, A]
+    near = U.near_kink((actor, obs), (critic, torch.cat([obs, act], -1)), (critic, torch.cat([obs.double(), pi], -1)))
     w = torch.randn((rows, A), generator=g)
     w[near] = 0.0
     return actor, critic, obs, act, target, w, float(near.double().mean())
@@ -206,13 +172,7 @@ def ddpg_losses(actor, critic, obs, act, target, w, apply):
 def ddpg_grads(actor, critic, obs, act, target, w, dtype, device="cpu", apply=None):
     """({actor tensor: grad}, {critic tensor: grad}) as float64 arrays: the actor's ten gradients of the actor loss (they come through the
     critic's INPUT gradient) and the critic's ten of the critic loss."""
-    def to(net):
-        a = R._new(net.n_actors, net.obs_len, net.n_actions, dtype=dtype, device=device)
-        with torch.no_grad():
-            for k in PARAMS:
-                getattr(a, k).copy_(getattr(net, k).detach().to(device=device, dtype=dtype))
-        return a
-    a, c = to(actor), to(critic)
+    a, c = U._to(actor, device, dtype), U._to(critic, device, dtype)
     t = [v.to(device=device, dtype=dtype) for v in (obs, act, target, w)]
     la, lc = ddpg_losses(a, c, *t, apply or (lambda net, x, squash: net(x, squash=squash)))
     ga = torch.autograd.grad(la, [getattr(a, k) for k in PARAMS], retain_graph=True)

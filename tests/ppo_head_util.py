@@ -12,20 +12,19 @@
                    loss and a row's whole gradient moves, for the reason actor_grad_util.py states for ReLU kinks
   case             the smallest step of LADDER for which 5 % .. 60 % of the kept rows have a ratio outside [1 - clip, 1 + clip] -- chosen
                    on the float64 reference alone --, its filtered inputs, the float64 reference and the float32 yardstick, cached
-  check            the bounds: per gradient tensor (2 x mean, 4 x max) of the yardstick's error (actor_ref_util.F32_FACTORS, except where
-                   profiles/ppo_head_float64.json records a wider factor and why); stats and g_log_std within 4 x the yardstick's own
-                   error over 9 row orders, at least half a float32 spacing
+  check            yardstick_util's bounds: per gradient tensor (2 x mean, 4 x max) of the yardstick's error (except where
+                   profiles/ppo_head_float64.json records a wider factor and why); stats and g_log_std within its scalar_bound of
+                   own_errors, the yardstick's own error over 9 row orders
 
 Nothing here imports the native library."""
 import functools
-import json
 import math
 import os
 
 import numpy as np
 import torch
 
-import actor_ref_util as R
+import yardstick_util as Y
 
 KINK = 1e-4
 LADDER = (0.03, 0.06, 0.12, 0.25, 0.5, 1.0)
@@ -200,9 +199,7 @@ def torch_loss(inp, kind, dtype, vold=True, perm=None, clip=CLIP, vclip=VCLIP, t
     g_pi, g_v = y.grad, torch.zeros_like(y.grad)
     g_v[..., 0] = v.grad
     if perm is not None:
-        inv = torch.empty_like(perm)
-        inv[perm] = torch.arange(perm.numel())
-        g_pi, g_v = g_pi[inv], g_v[inv]
+        g_pi, g_v = g_pi[torch.argsort(perm)], g_v[torch.argsort(perm)]
     num = lambda x: x.detach().double().numpy()           # noqa: E731
     stats = np.array([float(n), float(loss.detach().double()), float(pol.detach().double()), float(val.detach().double()),
                       float(en.detach().double()), float(kl.double()), float(share.double()), 0.0])
@@ -217,54 +214,37 @@ def case(kind, rows, n, vold, cut=None, step=None, perms=8):
     if cut is not None:
         inp = head(inp, cut)
     ref = reference(inp, kind, vold)
-    N = ref["stats"][0]
-    yard = torch_loss(inp, kind, torch.float32, vold) if N > 0 else ref          # no masked row: torch's mean is 0 / 0, the contract says all 0
-    e_stats = np.zeros(8)
-    e_ls = 0.0
-    if N > 0:
-        runs = [yard] + [torch_loss(inp, kind, torch.float32, vold, torch.randperm(inp["adv"].shape[0], generator=torch.Generator().manual_seed(4000 + p)))
-                         for p in range(perms)]
-        for r in runs:
-            e_stats = np.maximum(e_stats, np.abs(r["stats"] - ref["stats"]))
-            if kind == "gaussian":
-                e_ls = max(e_ls, float(np.abs(r["g_log_std"] - ref["g_log_std"]).max()))
-    return inp, ref, yard, e_stats, e_ls
+    if ref["stats"][0] == 0:                    # no masked row: torch's mean is 0 / 0, the contract says all 0
+        return inp, ref, ref, np.zeros(8), 0.0
+    yard = torch_loss(inp, kind, torch.float32, vold)
+    return (inp, ref, yard) + own_errors(inp, ref, kind, vold, perms)
+
+
+def own_errors(inp, ref, kind, vold=True, perms=8, **par):
+    """(e_stats [8], e_ls): the float32 yardstick's own error on the statistics and on g_log_std (0.0 for a categorical head), the
+    largest over yardstick_util.row_orders; par: torch_loss' clip, vclip, tau, c_v, c_e."""
+    e = Y.own_error(lambda order: torch_loss(inp, kind, torch.float32, vold, order, **par), ref, inp["adv"].shape[0], perms,
+                    ("stats", "g_log_std")[:2 if kind == "gaussian" else 1])
+    return e[0], float(e[1].max()) if kind == "gaussian" else 0.0
 
 
 @functools.lru_cache(maxsize=None)
 def factors():
     """{tensor: (mean factor, max factor)}: the project's (2, 4), or what profiles/ppo_head_float64.json records for a tensor (with why)."""
-    out = {k: tuple(R.F32_FACTORS) for k in ("g_pi", "g_v")}
-    if os.path.exists(PROFILE):
-        for k, v in json.load(open(PROFILE)).get("factors", {}).items():
-            out[k] = tuple(v)
-    return out
+    return {k: Y.factor_of(Y.recorded(PROFILE, "factors"))(k) for k in ("g_pi", "g_v")}
 
 
 def check(got, ref, yard, e_stats, e_ls, kind, what=""):
     """got: dict(g_pi, g_v, g_log_std, stats) of float64 numpy from the kernel.  Prints every figure, then asserts."""
-    bad = []
-    for k in ("g_pi", "g_v"):
-        ek, et = np.abs(got[k] - ref[k]), np.abs(yard[k] - ref[k])
-        fm, fx = factors()[k]
-        print(f"{what} {k}: kernel mean / max error {ek.mean():.3e} / {ek.max():.3e}, yardstick {et.mean():.3e} / {et.max():.3e} "
-              f"(factors {fm}, {fx}); max|g| {np.abs(ref[k]).max():.3e}")
-        if not (ek.mean() <= fm * et.mean() and ek.max() <= fx * et.max()):
-            bad.append(k)
+    bad = Y.check_tensors([(k, got[k], ref[k], yard[k], factors()[k]) for k in ("g_pi", "g_v")], what)[1]
     if not (got["stats"][0] == ref["stats"][0] and got["stats"][7] == 0.0):
         bad.append("N")
     if ref["stats"][0] > 0 and abs(got["stats"][6] - ref["stats"][6]) > 1e-12:        # a count over N: the same rows are clipped (kinks left out)
         bad.append("clipped share")
-    for i, name in enumerate(STAT_NAMES, start=1):
-        tol = 4 * max(e_stats[i], 0.5 * float(np.spacing(np.float32(abs(ref["stats"][i])))))
-        err = abs(got["stats"][i] - ref["stats"][i])
-        print(f"{what} stats.{name}: float64 {ref['stats'][i]:.9g}, kernel error {err:.3e}, yardstick's own (9 row orders) {e_stats[i]:.3e}, bound {tol:.3e}")
-        if not err <= tol:
-            bad.append(name)
+    bad += Y.stats_out_of_bounds(got["stats"], ref["stats"], e_stats, STAT_NAMES, what)
     if kind == "gaussian":
         r = ref["g_log_std"]
-        tol = 4 * max(e_ls, 0.5 * float(np.spacing(np.float32(np.abs(r).max()))))
-        err = float(np.abs(got["g_log_std"] - r).max())
+        tol, err = Y.scalar_bound(r, e_ls), float(np.abs(got["g_log_std"] - r).max())
         print(f"{what} g_log_std: kernel error {err:.3e}, yardstick's own (9 row orders) {e_ls:.3e}, bound {tol:.3e}, max|g| {np.abs(r).max():.3e}")
         if not err <= tol:
             bad.append("g_log_std")

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 import adam_util as U
+from actor_grad_util import nudge     # noqa: F401     (the suites' step away from the policy that played, beside the ladder that takes it)
 
 PARAMS = ("w1", "b1", "g1", "h1", "w2", "b2", "g2", "h2", "w3", "b3")
 TAU = 0.7
@@ -53,19 +54,17 @@ def small_rollout(kind, gae=True, sample=True, T=8, n=1, E=96, one_launch=False,
     return ro
 
 
+def record(ro, t0=0, t1=None):
+    """What a PPO update reads of ticks t0 .. t1 (default: all T) of a rollout's records, on the CPU; a categorical policy's actions as indices."""
+    act = ro.scores.clone() if ro.log_std is not None else ro.scores.argmax(-1)
+    rec = dict(obs=ro.obs[:ro.T].clone(), act=act, logp=ro.logp.clone(), adv=ro.adv.clone(), ret=ro.ret.clone(), mask=ro.mask.clone())
+    return {k: v[t0:t1].cpu() for k, v in rec.items()}
+
+
 def scripted_columns(n, opponent):
     """(scripted, learned) agent columns of a rollout with opponent "red" / "blue" / None: a team's planes are adjacent columns, red first."""
     red, blue = list(range(n)), list(range(n, 2 * n))
     return {None: ([], red + blue), "red": (red, blue), "blue": (blue, red)}[opponent]
-
-
-def nudge(net, scale, seed=5):
-    """Every parameter moved by scale * mean|p| * a standard normal (drawn on the CPU: the same step on every device)."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for k in PARAMS:
-            p = getattr(net, k)
-            p.add_((scale * p.abs().mean().cpu() * torch.randn(p.shape, generator=g)).to(p.device))
 
 
 # ---------------------------------------------------------------------------------------------------- what an update moves
@@ -300,12 +299,6 @@ def first_step_meets_the_bars(ro, kw, reference_step, g=1, norm_rtol=1e-10):
     tor_m, tor_v = state("exp_avg"), state("exp_avg_sq")
     tor_m[0].append(default.optimizer.state[ro.log_std]["exp_avg"].cpu().numpy())
     tor_v[0].append(default.optimizer.state[ro.log_std]["exp_avg_sq"].cpu().numpy())
-    failed = []
     for i in range(2):
-        for what, mine, theirs, want in (("p", got, tor, ref_p), ("m", got_m, tor_m, ref_m), ("v", got_v, tor_v, ref_v)):
-            (em, ex), (tm, tx) = U.pooled_errors(lead(mine[i]), lead(want[i])), U.pooled_errors(lead(theirs[i]), lead(want[i]))
-            print(f"net{i}.{what}: device {em:.3e} / {ex:.3e}, torch {tm:.3e} / {tx:.3e}")
-            assert tm > 0.0 and tx > 0.0
-            if em > 2.0 * tm or ex > 4.0 * tx:
-                failed.append((i, what, em, tm, ex, tx))
-    assert not failed, failed
+        pmv = lambda p, m, v: dict(p=lead(p[i]), m=lead(m[i]), v=lead(v[i]))     # noqa: E731
+        U.check_step(pmv(got, got_m, got_v), pmv(ref_p, ref_m, ref_v), pmv(tor, tor_m, tor_v), f"net{i}", names=("p", "m", "v"))

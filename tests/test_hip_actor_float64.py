@@ -8,7 +8,7 @@ loses on the same inputs:
     e_k  the kernel's |error| against float64        e_t  torch float32's (CPU)        e_m  the split model's (2 terms bf16x3, 3 terms bf16x6)
     f32:          mean(e_k) <= 2 mean(e_t)                 max(e_k) <= 4 max(e_t)
     split modes:  mean(e_k) <= 2 (mean(e_m) + mean(e_t))   max(e_k) <= 4 (max(e_m) + max(e_t))
-(actor_ref_util.bounds says where 2 and 4 come from.)  Scores: |score - tanh(y64)| <= sech^2(y64) * B + 4 * 2^-24 with B the max bound.
+(yardstick_util.FACTORS says where 2 and 4 come from.)  Scores: |score - tanh(y64)| <= sech^2(y64) * B + 4 * 2^-24 with B the max bound.
 Every test prints what it measured before it asserts (-s shows the table; tools/micro/actor_precision.py writes it to a file)."""
 import functools
 import math

@@ -14,7 +14,9 @@ import torch
 
 import actor_grad_util as U
 import actor_ref_util as R
-from actor_grad_util import CLIP, TAU, _logp, _ppo, _to
+import ppo_learner_util as L
+import yardstick_util as Y
+from actor_grad_util import _logp, _ppo, _ppo_ladder, _ppo_own_error, _to
 from guard_util import Buffers
 
 pytestmark = pytest.mark.gpu
@@ -241,81 +243,33 @@ def test_fused_apply_refuses_what_it_documents():
 # ---------------------------------------------------------------------------------------------------- 5. end to end: a PPO loss
 @functools.lru_cache(maxsize=None)
 def _record(kind):
-    """One small rollout with GAE: the records a PPO update reads, on the CPU (read-only), and the networks that produced them."""
-    import deep_rl_battlespace_amd as bsx
-    from deep_rl_battlespace_amd.rollout import PolicyRollout, StackedActor
-    n, E, T = 1, 96, 8
-    A, D = 2 * n, 3 * n + 2
-    cont = kind == "gaussian"
-    torch.manual_seed(11)
-    actor, critic = StackedActor(A, D, 3 if cont else 4, device="cuda"), StackedActor(A, D, 1, device="cuda")
-    with torch.no_grad():
-        actor.w3.mul_(60.0); critic.w3.mul_(100.0)
-    env = bsx.parallel_env(n_agents=n, n_envs=E, seed=41, auto_reset=True, continuous_actions=cont, device="cuda")
-    env.reset()
-    ls = torch.full((A, 3), -0.5, device="cuda") if cont else None
-    kw = dict(sample="gaussian", log_std=ls) if cont else dict(sample="categorical", temperature=TAU)
-    ro = PolicyRollout(env, actor, T, seed=3, value_actor=critic, gae=dict(gamma=0.99, lam=0.95), **kw)
-    ro.start(); ro.capture()
-    ro.run(); ro.run()
-    torch.cuda.synchronize()
-    act = ro.scores.clone() if cont else ro.scores.argmax(-1)
-    rec = dict(obs=ro.obs[:T].clone(), act=act, logp=ro.logp.clone(), adv=ro.adv.clone(), ret=ro.ret.clone(), mask=ro.mask.clone())
-    return actor, critic, ls, {k: v.cpu() for k, v in rec.items()}
+    """ppo_learner_util's small rollout (n = 1, E = 96, T = 8, with GAE): the records a PPO update reads, on the CPU (read-only), and the
+    networks that produced them."""
+    ro = L.small_rollout(kind)
+    return ro.actor, ro.value_actor, ro.log_std, L.record(ro)
 
 
 @pytest.mark.parametrize("kind", ["gaussian", "categorical"])
 def test_ppo_loss_and_gradients_fused_against_torch_on_a_rollout_record(kind):
     actor0, critic, ls, rec = _record(kind)
-    critic = _to(critic, "cpu")
-    ls_cpu = ls.cpu() if ls is not None else None
-    T, E, A, D = rec["obs"].shape
-    flat_obs = rec["obs"].reshape(-1, A, D)
-    # the learner is a step away from the policy that played, so that ratios leave 1 and some are clipped: the smallest step of a fixed
-    # ladder that clips between 5 % and 60 % of the rows (chosen on the float64 reference alone)
-    for scale in (0.03, 0.06, 0.12, 0.25, 0.5, 1.0):
-        actor = _to(actor0, "cpu")
-        g = torch.Generator().manual_seed(5)
-        with torch.no_grad():
-            for k in U.PARAMS:
-                p = getattr(actor, k)
-                p.add_(scale * p.abs().mean() * torch.randn(p.shape, generator=g))
-        # rows kept: the agent's own decisions (mask), away from every kink of the loss in float64 -- a hidden unit of either network
-        # within 1e-4 of its ReLU's kink, a ratio within 1e-4 of a clip boundary -- for the reason actor_grad_util states; the same rows
-        # in every path
-        near = (U.pre_relu64(actor, flat_obs).abs() < U.KINK).any(-1) | (U.pre_relu64(critic, flat_obs).abs() < U.KINK).any(-1)
-        keep = rec["mask"] & ~near.transpose(0, 1).reshape(T, E, A)
-        _, _, _, _, r64 = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float64)
-        r64 = r64.reshape(T, E, A)
-        keep = keep & ((r64 - (1 - CLIP)).abs() > 1e-4) & ((r64 - (1 + CLIP)).abs() > 1e-4)
-        kept, clipped = int(keep.sum()), int((keep & ((r64 < 1 - CLIP) | (r64 > 1 + CLIP))).sum())
-        print(kind, "step", scale, "rows kept", kept, "of", int(rec["mask"].sum()), "masked; clipped", clipped)
-        if 0.05 * kept <= clipped <= 0.6 * kept:
-            break
-    assert kept >= 0.9 * int(rec["mask"].sum()) and kept >= 500 and 0.05 * kept <= clipped <= 0.6 * kept
+    # the learner is a step of actor_grad_util's ladder away from the policy that played; the same kept rows in every path
+    actor, critic, ls_cpu, keep, fig = _ppo_ladder(actor0, critic, ls, rec, kind)
+    kept, clipped = fig["kept"], fig["clipped"]
+    assert kept >= 0.9 * fig["masked"] and kept >= 500 and 0.05 * kept <= clipped <= 0.6 * kept
     L64, a64, c64, l64, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float64)
     L32, a32, c32, l32, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float32)
-    Lt, _, _, lt, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cuda", torch.float32)
+    # what the torch path itself loses on this record: the float32 loss in the given order and under 8 others, against float64
+    Lt, bound, e_ls = _ppo_own_error(actor, critic, ls_cpu, rec, keep, kind, L64, l64)
     Lf, af, cf, lf, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, True, "cuda", torch.float32)
-    # what the torch path itself loses on this record: the float32 loss under 8 orders of the rows, against float64
-    e_loss, e_ls = abs(Lt - L64), (np.abs(lt - l64).max() if ls is not None else 0.0)
-    for p in range(8):
-        perm = torch.randperm(T * E, generator=torch.Generator().manual_seed(4000 + p))
-        Lp, _, _, lp, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cuda", torch.float32, perm)
-        e_loss = max(e_loss, abs(Lp - L64))
-        if ls is not None:
-            e_ls = max(e_ls, np.abs(lp - l64).max())
-    # a float32 loss cannot be expected closer to float64 than half a float32 spacing at its size, whatever the nine orders happened to hit
-    e_loss = max(e_loss, 0.5 * float(np.spacing(np.float32(abs(L64)))))
     print(kind, f"loss float64 {L64:.9g} fused {Lf:.9g} torch {Lt:.9g}; |fused - torch| {abs(Lf - Lt):.3e}, |fused - f64| {abs(Lf - L64):.3e}, "
-                f"torch's own error (max of 9 row orders, at least half a float32 spacing) {e_loss:.3e}")
-    # both are float32 evaluations of the same loss, each off float64 by about e_loss: 4 e_loss is the project's factor on a maximum
-    assert abs(Lf - Lt) <= 4 * e_loss and abs(Lf - L64) <= 4 * e_loss
+                f"torch's own error (max of 9 row orders, at least half a float32 spacing) {bound / Y.FACTORS[1]:.3e}")
+    # both are float32 evaluations of the same loss, each off float64 by about torch's own error: yardstick_util.scalar_bound of it
+    assert abs(Lf - Lt) <= bound and abs(Lf - L64) <= bound
     U.check(af, a64, a32, f"PPO {kind} actor")
     U.check(cf, c64, c32, f"PPO {kind} critic")
     if ls is not None:
         print(kind, f"log_std gradient: |fused - f64| {np.abs(lf - l64).max():.3e}, torch's own error {e_ls:.3e}, max |g| {np.abs(l64).max():.3e}")
-        assert np.abs(lf - l64).max() <= 4 * e_ls
+        assert np.abs(lf - l64).max() <= Y.FACTORS[1] * e_ls
 
 
 @pytest.mark.parametrize("kind", ["gaussian", "categorical"])

@@ -8,16 +8,10 @@ import torch
 
 import actor_grad_util as U
 import ppo_learner_util as L
-from actor_grad_util import CLIP, _logp, _ppo, _to
+import yardstick_util as Y
+from actor_grad_util import CLIP, _logp, _ppo, _ppo_ladder, _ppo_own_error, _to
 
 pytestmark = pytest.mark.gpu
-
-
-def _record(ro, cont, t0=0, t1=None):
-    t1 = ro.T if t1 is None else t1
-    act = ro.scores.clone() if cont else ro.scores.argmax(-1)
-    rec = dict(obs=ro.obs[:ro.T].clone(), act=act, logp=ro.logp.clone(), adv=ro.adv.clone(), ret=ro.ret.clone(), mask=ro.mask.clone())
-    return {k: v[t0:t1].cpu() for k, v in rec.items()}
 
 
 # (kind, rollout arguments, minibatch ticks or None for all T, the scripted team or None).  T = 8.  The two 1v1 graph cases are the
@@ -45,34 +39,6 @@ OPPONENT_CONFIGS = {
 FIGURES = {}                                                                    # what the tests measured, by configuration (tools/measure_ppo_learner.py writes the profile from it)
 
 
-def _reference_policy(ro, kind, rec, cols):
-    """The ladder of the fused PPO test on the float64 reference alone: the smallest step that clips 5 % .. 60 % of the kept rows ->
-    (actor, critic, log_std on the CPU, keep, figures).  cols: the agent columns whose rows may be kept (a scripted team's are not)."""
-    cont = kind == "gaussian"
-    actor0, critic = _to(ro.actor, "cpu"), _to(ro.value_actor, "cpu")
-    ls_cpu = ro.log_std.cpu() if cont else None
-    T, E, A, D = rec["obs"].shape
-    flat_obs = rec["obs"].reshape(-1, A, D)
-    on = torch.zeros(A, dtype=torch.bool)
-    on[cols] = True
-    masked = rec["mask"] & on
-    for scale in (0.03, 0.06, 0.12, 0.25, 0.5, 1.0):
-        actor = _to(actor0, "cpu")
-        L.nudge(actor, scale)
-        near = (U.pre_relu64(actor, flat_obs).abs() < U.KINK).any(-1) | (U.pre_relu64(critic, flat_obs).abs() < U.KINK).any(-1)
-        near = near.transpose(0, 1).reshape(T, E, A)
-        keep = masked & ~near
-        r64 = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float64)[4].reshape(T, E, A)
-        keep = keep & ((r64 - (1 - CLIP)).abs() > 1e-4) & ((r64 - (1 + CLIP)).abs() > 1e-4)
-        kept, clipped = int(keep.sum()), int((keep & ((r64 < 1 - CLIP) | (r64 > 1 + CLIP))).sum())
-        kink = float((masked & near).sum()) / max(int(masked.sum()), 1)
-        print(kind, "step", scale, "rows kept", kept, "of", int(masked.sum()), "masked; clipped", clipped, "; near a ReLU kink", f"{kink:.4f}")
-        if 0.05 * kept <= clipped <= 0.6 * kept:
-            break
-    fig = dict(step=scale, masked=int(masked.sum()), kept=kept, clipped=clipped, kink_share=kink)
-    return actor, critic, ls_cpu, keep, fig
-
-
 def _conditions(fig):
     return (fig["kept"] >= 0.9 * fig["masked"] and fig["kept"] >= 500 and 0.05 * fig["kept"] <= fig["clipped"] <= 0.6 * fig["kept"]
             and fig["kink_share"] <= U.KINK_CAP)
@@ -83,24 +49,15 @@ def _minibatch_against_float64(ro, kind, ticks=None, cols=None, what=""):
     from deep_rl_battlespace_amd.learner import PPOLearner, split_grad
     cont = kind == "gaussian"
     t0, t1 = ticks or (0, ro.T)
-    rec = _record(ro, cont, t0, t1)
-    T, E, A, D = rec["obs"].shape
-    cols = list(range(A)) if cols is None else cols
+    rec = L.record(ro, t0, t1)
     # the learner's policy is one step of the existing test's ladder away from the one that played; rows kept as there
-    actor, critic, ls_cpu, keep, fig = _reference_policy(ro, kind, rec, cols)
+    actor, critic, ls_cpu, keep, fig = _ppo_ladder(ro.actor, ro.value_actor, ro.log_std, rec, kind, cols)
     kept = fig["kept"]
+    print(what, "near a ReLU kink", f"{fig['kink_share']:.4f}")
     assert _conditions(fig), fig
     L64, a64, c64, l64, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float64)
     _, a32, c32, _, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cpu", torch.float32)
-    Lt, _, _, lt, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cuda", torch.float32)
-    e_loss, e_ls = abs(Lt - L64), (np.abs(lt - l64).max() if cont else 0.0)
-    for p in range(8):
-        perm = torch.randperm(T * E, generator=torch.Generator().manual_seed(4000 + p))
-        Lp, _, _, lp, _ = _ppo(actor, critic, ls_cpu, rec, keep, kind, False, "cuda", torch.float32, perm)
-        e_loss = max(e_loss, abs(Lp - L64))
-        if cont:
-            e_ls = max(e_ls, np.abs(lp - l64).max())
-    e_loss = max(e_loss, 0.5 * float(np.spacing(np.float32(abs(L64)))))
+    Lt, bound, e_ls = _ppo_own_error(actor, critic, ls_cpu, rec, keep, kind, L64, l64)
     # the learner over the rollout itself: its actor moved to the learner's policy, its mask cut to the kept rows
     with torch.no_grad():
         for k in U.PARAMS:
@@ -115,17 +72,17 @@ def _minibatch_against_float64(ro, kind, ticks=None, cols=None, what=""):
     Lf = float(stats[1])
     assert float(stats[0]) == kept
     print(what, f"loss float64 {L64:.9g} learner {Lf:.9g} torch {Lt:.9g}; |learner - torch| {abs(Lf - Lt):.3e}, |learner - f64| {abs(Lf - L64):.3e}, "
-                f"torch's own error (max of 9 row orders, at least half a float32 spacing) {e_loss:.3e}")
-    assert abs(Lf - Lt) <= 4 * e_loss and abs(Lf - L64) <= 4 * e_loss
+                f"torch's own error (max of 9 row orders, at least half a float32 spacing) {bound / Y.FACTORS[1]:.3e}")
+    assert abs(Lf - Lt) <= bound and abs(Lf - L64) <= bound
     ra = U.check(af, a64, a32, f"PPO learner {what} actor")
     rc = U.check(cf, c64, c32, f"PPO learner {what} critic")
-    fig.update(loss_error_over_torchs=abs(Lf - L64) / e_loss,
+    fig.update(loss_error_over_torchs=Y.FACTORS[1] * abs(Lf - L64) / bound,
                actor_mean_ratio=max(r[0] for r in ra.values()), actor_max_ratio=max(r[1] for r in ra.values()),
                critic_mean_ratio=max(r[0] for r in rc.values()), critic_max_ratio=max(r[1] for r in rc.values()))
     if cont:
         lf = g_ls.double().cpu().numpy()
         print(what, f"log_std gradient: |learner - f64| {np.abs(lf - l64).max():.3e}, torch's own error {e_ls:.3e}, max |g| {np.abs(l64).max():.3e}")
-        assert np.abs(lf - l64).max() <= 4 * e_ls
+        assert np.abs(lf - l64).max() <= Y.FACTORS[1] * e_ls
         fig["log_std_error_over_torchs"] = float(np.abs(lf - l64).max() / e_ls) if e_ls > 0 else 0.0
     else:
         assert g_ls is None
@@ -142,12 +99,6 @@ def test_one_minibatch_meets_the_bounds_of_the_fused_ppo_loss_against_torch(conf
 
 
 # ---------------------------------------------------------------------------------------------------- 1b. on the policy that played
-def _error_ratios(got, yard, ref):
-    """(mean(e_got) / mean(e_yard), max(e_got) / max(e_yard)) against the float64 `ref`."""
-    eg, ey = (got.double() - ref).abs(), (yard.double() - ref).abs()
-    return float(eg.mean() / ey.mean()), float(eg.max() / ey.max())
-
-
 @pytest.mark.parametrize("config", list(CONFIGS) + list(OPPONENT_CONFIGS))
 def test_on_the_policy_that_played_nothing_is_clipped_and_the_records_meet_float64(config):
     """Before anything moves the learner's policy IS the rollout's: a minibatch over all T ticks counts the rollout's own masked rows and
@@ -168,7 +119,7 @@ def test_on_the_policy_that_played_nothing_is_clipped_and_the_records_meet_float
     assert float(stats[0]) == float(m.sum()) and float(stats[6]) == 0.0, stats
     assert int(m.sum()) >= 500 and not m[..., torch.tensor(scripted, dtype=torch.long)].any()
     obs, act = ro.obs[:T].clone(), (ro.scores.clone() if cont else ro.scores.argmax(-1))
-    fm, fx = R.F32_FACTORS
+    fm, fx = Y.FACTORS
     fig, bad = {}, []
     with torch.no_grad():
         a64, c64 = R.to_float64(ro.actor), R.to_float64(ro.value_actor)
@@ -185,11 +136,11 @@ def test_on_the_policy_that_played_nothing_is_clipped_and_the_records_meet_float
         v_learner = fused_apply(ro.value_actor, obs, squash=False)[..., 0].cpu()
         for name, got, yard, ref in (("recorded logp", ro.logp.cpu(), lp32, lp64), ("learner logp", lp_learner, lp32, lp64),
                                      ("recorded value", ro.value.cpu(), v32, v64), ("learner value", v_learner, v32, v64)):
-            rm, rx = _error_ratios(got[m], yard[m], ref[m])
+            rm, rx = Y.error_ratios(got[m], ref[m], yard[m])
             print(config, f"{name}: mean ratio {rm:.3f} (<= {fm}), max ratio {rx:.3f} (<= {fx}); torch float32's own max error "
-                          f"{float((yard[m].double() - ref[m]).abs().max()):.3e}")
+                          f"{Y.errors(yard[m], ref[m])[1]:.3e}")
             fig[name.replace(" ", "_")] = (rm, rx)
-            if not (rm <= fm and rx <= fx):
+            if not Y.within((rm, rx)):
                 bad.append((name, rm, rx))
         # the ratio a learner would see had the rollout evaluated its actor in bf16x3: exp(logp(bf16x3 scores) - float64 logp) - 1
         y = FusedActor(ro.actor, ro.env.n_agents, precision="bf16x3")(obs.view(-1, A, D).contiguous(), seq=1).view(T, -1, A, 4).cpu().double()

@@ -32,6 +32,7 @@ def main():
     import torch
     import actor_ref_util as R
     import mlp_grad_util as M
+    import yardstick_util as Y
     from deep_rl_battlespace_amd.learner import fused_mlp
     if not torch.cuda.is_available():
         raise SystemExit("measure_mlp_grad.py measures on the GPU: none found")
@@ -55,6 +56,14 @@ def main():
     def spread(ga, g32, g64, names):
         return {k: [round(v[0], 2), round(v[1], 2)] for k, v in M.spread(g64, g32, [ga], names).items()}
 
+    def ratios(got, g64, g32, names=M.TENSORS):
+        """{name: (mean(e_k) / mean(e_t), max(e_k) / max(e_t), max(e_k) / max|g64|)}"""
+        return {k: (*Y.error_ratios(got[k], g64[k], g32[k]), Y.errors(got[k], g64[k])[1] / max(float(abs(g64[k]).max()), 1e-300)) for k in names}
+
+    def figures(r, factor_of, names):
+        return {k: dict(mean_ratio=round(r[k][0], 3), max_ratio=round(r[k][1], 3), max_error_over_max_gradient=float("%.3g" % r[k][2]),
+                        within=Y.within(r[k][:2], factor_of(k))) for k in names}
+
     kernel, sp_gpu, sp_unit, sp_row, raw = {}, {}, {}, {}, {}
     for case in M.CASES:
         cid = M.case_id(case)
@@ -62,13 +71,11 @@ def main():
         sp_gpu[cid] = spread(gpu_grads(net, x, go, case[3], False), g32, g64, M.TENSORS)
         sp_unit[cid] = {k: [round(v[0], 2), round(v[1], 2)] for k, v in M.unit_permutation_spread(case, 8).items()}
         sp_row[cid] = {k: [round(v[0], 2), round(v[1], 2)] for k, v in M.row_permutation_spread(case, 8).items()}
-        raw[cid] = M.ratios(gpu_grads(net, x, go, case[3], True), g64, g32)
+        raw[cid] = ratios(gpu_grads(net, x, go, case[3], True), g64, g32)
     exceptions = M.exceptions_from(dict(torch_gpu=sp_gpu, unit_permutation=sp_unit, row_permutation=sp_row))
     for case in M.CASES:
-        cid, r = M.case_id(case), raw[M.case_id(case)]
-        f = {k: exceptions.get(cid, {}).get(k, exceptions.get("*", {}).get(k, (M.FM, M.FX))) for k in M.TENSORS}
-        kernel[cid] = {k: dict(mean_ratio=round(r[k][0], 3), max_ratio=round(r[k][1], 3), max_error_over_max_gradient=float("%.3g" % r[k][2]),
-                               within=bool(r[k][0] <= f[k][0] and r[k][1] <= f[k][1])) for k in M.TENSORS}
+        cid = M.case_id(case)
+        kernel[cid] = figures(raw[cid], Y.factor_of(exceptions.get(cid, {}), exceptions.get("*", {})), M.TENSORS)
         print(cid, "largest kernel ratios", max(v["mean_ratio"] for v in kernel[cid].values()), max(v["max_ratio"] for v in kernel[cid].values()),
               "missed:", [k for k, v in kernel[cid].items() if not v["within"]], flush=True)
     # the DDPG step: the actor's and the critic's ten tensors, (2, 4) but for b3's pair
@@ -79,10 +86,7 @@ def main():
     af, cf = M.ddpg_grads(*dd[:6], torch.float32, "cuda", lambda net, x, squash: fused_mlp(net, x, squash=squash))
     for name, got, t, g64, g32 in (("ddpg-actor", af, at, a64, a32), ("ddpg-critic", cf, ct, c64, c32)):
         sp_gpu[name] = spread(t, g32, g64, M.PARAMS)
-        r = M.ratios(got, g64, g32, M.PARAMS)
-        kernel[name] = {k: dict(mean_ratio=round(r[k][0], 3), max_ratio=round(r[k][1], 3), max_error_over_max_gradient=float("%.3g" % r[k][2]),
-                                within=bool(r[k][0] <= exceptions.get("*", {}).get(k, (M.FM, M.FX))[0] and
-                                            r[k][1] <= exceptions.get("*", {}).get(k, (M.FM, M.FX))[1])) for k in M.PARAMS}
+        kernel[name] = figures(ratios(got, g64, g32, M.PARAMS), Y.factor_of({}, exceptions.get("*", {})), M.PARAMS)
         print(name, "largest kernel ratios", max(v["mean_ratio"] for v in kernel[name].values()), max(v["max_ratio"] for v in kernel[name].values()), flush=True)
     old = json.load(open(args.out)) if os.path.exists(args.out) else {}
     result = dict(what="Accuracy of bsx_mlp_grad (parameter row and grad_x) on the cases of tests/test_hip_mlp_grad.py, and the timings of "

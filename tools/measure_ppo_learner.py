@@ -58,8 +58,7 @@ def main():
         for seed in SEEDS:
             ro = L.small_rollout(kind, **dict(kw, seed=seed))
             a, b = ticks or (0, ro.T)
-            rec = M._record(ro, kind == "gaussian", a, b)
-            fig = M._reference_policy(ro, kind, rec, list(range(rec["obs"].shape[2])) if cols is None else cols)[4]
+            fig = M._ppo_ladder(ro.actor, ro.value_actor, ro.log_std, L.record(ro, a, b), kind, cols)[4]
             fig["meets"] = bool(M._conditions(fig))
             c["seeds_tried"][str(seed)] = fig
             if fig["meets"]:
