@@ -306,7 +306,11 @@ class PolicyRollout:
     clips them to [-1, 1], as the reference's does), logp[t] = Normal(mu, sigma).log_prob(a).sum(-1) -- gaussian_log_prob() is its learner
     side.  Rows a scripted opponent plays carry logp 0.
 
-    The env must be batched, discrete, rng='philox'; auto_reset is recommended (finished games re-spawn in place).
+    The env must be batched, rng='philox', discrete or continuous (4 or 3 actor outputs); auto_reset is recommended (finished games
+    re-spawn in place).  Without auto_reset a finished game stays inert until the host re-spawns it between two runs:
+    `ro.run(); env.reset(mask=finished); ro.start()` -- start() takes the observations, env_done and (with gae=) the done flags of every game
+    from the env again, the games outside the mask continue where the run left them.  With ou_restart it also restarts the OU rows of the games
+    re-spawned that way (to mu = 0.0; every other row keeps its bits), since no tick of the next run finds them finished.
     Exploration noise on the score vectors is Gaussian (noise_std) and/or the reference's Ornstein-Uhlenbeck process
     (ou_scale = main.py's curr_noise; utils/noise.py), whose state is one more [E, A, 4] tensor updated inside the actor
     kernel and restarted per game; then clamp(-1, 1) as maddpg/agent.py:31 does."""
@@ -407,7 +411,8 @@ class PolicyRollout:
             self.value = torch.zeros((T, E, A), dtype=torch.float32, device=dev)
         # gae=dict(gamma, lam[, normalize]): an on-policy learner's inputs, computed in the same graph after the ticks (advantage.gae):
         # last_value = V(obs[T]) by one value-only pass of the fused actor, then adv / ret / mask [T, E, A] and, with normalize, adv_stats
-        # = (n, mean, std).  _done_prev carries the agents' done flags from one run to the next (start() seeds it from the env).
+        # = (n, mean, std).  _done_prev carries the agents' done flags from one run to the next (start() seeds it from the env, which
+        # every run hands its last flags).
         self._gae = None
         if gae is not None:
             if value_actor is None:
@@ -493,7 +498,12 @@ class PolicyRollout:
                          env_done_ptr=self.env_done[t + 1].data_ptr())
 
     def start(self):
-        """Begin from the env's current observations (call after env.reset())."""
+        """Begin from the env's current observations (call after env.reset(), or after env.reset(mask=...) between two runs)."""
+        if self.ou is not None and self.ou["restart"]:
+            # games that this rollout left finished and the host has re-spawned since: the next run finds env_done[0] == 0 for them, so
+            # no tick restarts their process -- it starts again from mu (0.0) here, as main.py:155 does at every game start
+            fresh = (self.env_done[self.T] != 0) & (self.env._env_done == 0)
+            self.ou["state"][fresh] = 0.0
         self.obs[self.T].copy_(self.env._obs)          # every run starts by moving obs[T] to obs[0]
         self.env_done[self.T].copy_(self.env._env_done)
         if self._gae is not None:
@@ -543,6 +553,9 @@ class PolicyRollout:
             self.env._env_done.copy_(self.env_done[self.T])        # the per-tick launches wrote their flags into the record
         if self._gae is not None:
             self._advantages()
+            # no tick writes the env's own done flags (they go into the record): hand it the last tick's, so that a start() after
+            # env.reset(mask=...) seeds the carry with 0 for the re-spawned games and with the run's last flags for every other game
+            self.env._done.copy_(self._done_prev)
         self._seq_base.add_(self.T)                    # fresh exploration-noise keys for the next run
 
     def _advantages(self):

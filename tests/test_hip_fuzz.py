@@ -50,3 +50,18 @@ def test_random_policy_rollouts_replayed_by_the_c_oracle(seed):
         assert bad is None, (bad, case)
         forms.add(case["form"])
     assert len(forms) >= 2
+
+
+@pytest.mark.parametrize("seed", [33, 34])
+def test_random_policy_rollouts_with_auto_reset_drawn(seed):
+    """The same, with `auto_reset` drawn too (from a generator of its own: the cases of seeds 31 and 32 above stay what they are): where it
+    is False a finished game stays inert, and every third run the host re-spawns the finished games on both sides and calls start()."""
+    import fuzz_util as fz
+    rng, auto_rng = np.random.default_rng(seed), np.random.default_rng(1000 + seed)
+    forms, manual = set(), 0
+    for _ in range(12):
+        case = fz.draw_rollout_case(rng, auto_rng)
+        bad, st = fz.run_rollout_case(case)
+        assert bad is None, (bad, case)
+        forms.add(case["form"]); manual += not case["auto_reset"]
+    assert manual >= 3 and len(forms) >= 2

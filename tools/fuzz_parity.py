@@ -26,12 +26,13 @@ def main():
     ap.add_argument("--rollout-share", type=float, default=0.1, help="share of cases that run a PolicyRollout in a random form and let the C oracle replay its games")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
+    auto_rng = np.random.default_rng(args.seed + (1 << 32))      # the rollout cases' auto_reset field: a generator of its own
     t0 = time.time()
     by, total = {}, dict(cases=0, agent_steps=0, vals=0, exact=0)
     while (time.time() - t0 < args.seconds) and (not args.cases or total["cases"] < args.cases):
         r_kind = rng.random()
         dropin, rollout = r_kind < args.dropin_share, args.dropin_share <= r_kind < args.dropin_share + args.rollout_share
-        case = draw_dropin_case(rng) if dropin else (draw_rollout_case(rng) if rollout else draw_case(rng, args.max_envs))
+        case = draw_dropin_case(rng) if dropin else (draw_rollout_case(rng, auto_rng) if rollout else draw_case(rng, args.max_envs))
         try:
             bad, st = run_dropin_case(case) if dropin else (run_rollout_case(case) if rollout else run_case(case))
         except Exception as exc:                                 # an argument the build refuses is a finding too
@@ -47,7 +48,8 @@ def main():
         if rollout:
             total["agent_steps"] += case["E"] * 2 * case["n"] * case["T"] * case["runs"]
             for key in ("policy rollout", f"rollout form={case['form']}", f"rollout noise={case['noise']}", f"rollout opponent={case['opponent']}",
-                        f"rollout precision={case['precision']}", f"n={case['n']}"):
+                        f"rollout precision={case['precision']}", f"n={case['n']}",
+                        "rollout auto_reset" if case["auto_reset"] else "rollout masked_resets"):
                 by[key] = by.get(key, 0) + 1
             continue
         total["agent_steps"] += case["E"] * 2 * case["n"] * (case["T"] - case["T"] % case["K"])
