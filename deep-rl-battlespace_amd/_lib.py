@@ -20,6 +20,7 @@ F_WIDE_OFFSETS = 4
 F_ONE_WAVE = 8
 ACT_I32, ACT_LOGITS_F32 = 0, 1
 ACT_F32, ACT_F64, ACT_F32X4 = 0, 1, 2
+PRIO_FANOUT, PRIO_ONE, PRIO_SALT = 64, 65536, 0x3C6EF372
 WINNER_NAMES = ("none", "red", "blue", "tie")
 
 c_void_p, c_int, c_int64, c_uint32, c_uint64, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
@@ -64,6 +65,10 @@ class BsxReplaySource(ctypes.Structure):
                 ("rew", c_void_p), ("rew_row", c_int64), ("rew_col", c_int64),
                 ("done", c_void_p), ("done_row", c_int64), ("done_col", c_int64),
                 ("skip", c_void_p), ("skip_row", c_int64)]
+
+
+class BsxPrioTree(ctypes.Structure):
+    _fields_ = [("leaves", c_void_p), ("nodes", c_void_p), ("max_priority", c_void_p), ("hyper", c_void_p), ("M", c_int64)]
 
 
 class BsxGaeIo(ctypes.Structure):
@@ -160,6 +165,13 @@ SIGNATURES = {
     "bsx_replay_append": (c_int, [ctypes.POINTER(BsxReplayRing), ctypes.POINTER(BsxReplaySource), c_int64, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_sample": (c_int, [ctypes.POINTER(BsxReplayRing), c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsx_replay_prio_bytes": (c_int, [c_int64, ctypes.POINTER(c_size_t)]),
+    "bsx_replay_prio_rebuild": (c_int, [ctypes.POINTER(BsxPrioTree), c_void_p]),
+    "bsx_replay_prio_sample": (c_int, [ctypes.POINTER(BsxReplayRing), ctypes.POINTER(BsxPrioTree), c_int64, c_uint64, c_uint64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsx_replay_prio_weights": (c_int, [ctypes.POINTER(BsxPrioTree), c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_replay_prio_update": (c_int, [ctypes.POINTER(BsxPrioTree), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "bsx_replay_prio_append": (c_int, [ctypes.POINTER(BsxPrioTree), c_void_p, c_void_p, c_int64, c_void_p]),
     "bsx_gae_workspace_bytes": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_gae": (c_int, [ctypes.POINTER(BsxGaeIo), c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_gae_agents": (c_int, [ctypes.POINTER(BsxGaeIo), c_void_p, c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p,

@@ -47,6 +47,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_actor_grad.hip"), ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
            # the replay ring (append / sample): copies bits and draws integers, no floating-point arithmetic to pin
            (os.path.join(CSRC, "bsx_replay.hip"), []),
+           # the prioritised draw: integer sums and searches; its two powf (priority, weight) are held to float64, not to bits
+           (os.path.join(CSRC, "bsx_replay_prio.hip"), []),
            # GAE advantages: float32 operations each rounded on their own, as tests/gae_util.py restates them
            (os.path.join(CSRC, "bsx_advantage.hip"), ["-ffp-contract=off"]),
            # the PPO loss head: float32 element-wise terms held to a float64 reference, not to bits: contraction allowed

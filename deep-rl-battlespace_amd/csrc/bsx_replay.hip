@@ -18,10 +18,11 @@
 #include "battlespace_hip.h"
 #include "bsx_actor_core.h"
 #include "bsx_args.h"
+#include "bsx_replay_ring.h"
 
 namespace {
 
-constexpr int TPB = 256;          // threads per workgroup = source rows per tile (append)
+using namespace bsx_ring;        // TPB (threads per workgroup = source rows per tile of an append), gather_rows, the ring checks
 // draws per sampling workgroup: its 256 lanes walk 32 rows' words (a 4v4 row is 56 words per observation), a few loads each instead of
 // a long dependent chain -- with 256 draws per workgroup the gather was latency-bound (4v4, B = 512: two workgroups, 78 us)
 constexpr int DRAWS = 32;
@@ -147,15 +148,6 @@ __global__ __launch_bounds__(TPB) void bsx_replay_scatter_kernel(const AppendArg
     scatter_field(g.done, s.done, s.done_row, s.done_col, g.nA, 1, n, s_src, s_dst, tid);
 }
 
-// n rows of one field: out row b0 + i <- ring row s_row[i]; both sides are dense rows of W words (n <= DRAWS).
-template <typename T>
-__device__ inline void gather_field(T* __restrict__ out, const T* __restrict__ ring, int W, int64_t b0, int n, const int64_t* s_row, int tid) {
-    for (int j = tid; j < n * W; j += TPB) {
-        const int i = j / W, rem = j - i * W;
-        out[(b0 + i) * W + rem] = ring[s_row[i] * W + rem];
-    }
-}
-
 __global__ __launch_bounds__(TPB) void bsx_replay_sample_kernel(const SampleArgs p) {
     __shared__ int64_t s_row[DRAWS];
     const int tid = threadIdx.x;
@@ -172,30 +164,10 @@ __global__ __launch_bounds__(TPB) void bsx_replay_sample_kernel(const SampleArgs
         p.idx[b] = row;
     }
     __syncthreads();
-    const BsxReplayRing& g = p.ring;
-    const int WD = g.nA * g.D;
-    gather_field(reinterpret_cast<uint32_t*>(p.obs), reinterpret_cast<const uint32_t*>(g.obs), WD, b0, n, s_row, tid);
-    gather_field(reinterpret_cast<uint32_t*>(p.obs_next), reinterpret_cast<const uint32_t*>(g.obs_next), WD, b0, n, s_row, tid);
-    gather_field(reinterpret_cast<uint32_t*>(p.act), reinterpret_cast<const uint32_t*>(g.act), g.nA * g.n_act, b0, n, s_row, tid);
-    gather_field(reinterpret_cast<uint32_t*>(p.rew), reinterpret_cast<const uint32_t*>(g.rew), g.nA, b0, n, s_row, tid);
-    gather_field(p.done, g.done, g.nA, b0, n, s_row, tid);
+    gather_rows(p.ring, p.obs, p.obs_next, p.act, p.rew, p.done, b0, n, s_row, tid);
 }
-
-constexpr int64_t MAX_ROWS = (int64_t(1) << 31) - 1;
 
 int64_t tiles_of(int64_t rows) { return (rows + TPB - 1) / TPB; }
-
-// BSX_E_ARG for a ring that is missing a pointer or has a shape out of range; 0 otherwise (alignment: ring_misaligned)
-int check_ring(const BsxReplayRing* g) {
-    if (!g || !g->obs || !g->obs_next || !g->act || !g->rew || !g->done || !g->counter) return BSX_E_ARG;
-    if (g->M < 1 || g->M > MAX_ROWS || g->nA < 1 || g->nA > BSX_MAX_N || g->D < 1 || g->D > 3 * BSX_MAX_N + 2) return BSX_E_ARG;
-    if (g->n_act != 3 && g->n_act != 4) return BSX_E_ARG;
-    return 0;
-}
-
-bool ring_misaligned(const BsxReplayRing* g) {
-    return !aligned(g->obs, 4) || !aligned(g->obs_next, 4) || !aligned(g->act, 4) || !aligned(g->rew, 4) || !aligned(g->counter, 8);
-}
 
 }  // namespace
 

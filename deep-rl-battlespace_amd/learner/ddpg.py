@@ -11,7 +11,7 @@ import torch
 
 from .. import _lib
 from .._args import _F32, _FLAG, _need, _workspace
-from ..replay import DeviceReplayBuffer
+from ..replay import DeviceReplayBuffer, PrioritizedReplayBuffer
 from ..rollout import StackedActor
 from ._common import _POSITIVE, _capture, _f32, _hyper, _stream
 from .adam import AdamState, adam_hyper, mlp_adam_step, mlp_adam_step_workspace_bytes
@@ -169,6 +169,7 @@ class DDPGLearner:
        3. target actor on obs_next, ddpg_put_actions(own_only=False)   a' into x_next
        4. target critic on x_next -> q_next;  5. critic on x_cur -> q
        6. td_head                                                  y = r + gamma (1 - done) q_next, g_q, g_pi, the statistics
+          (a PrioritizedReplayBuffer: with weight = buffer.weights, then buffer.update_priorities(q, y): the rows' new priorities)
        7. mlp_grad of the critic on x_cur with g_q, mlp_adam_step of the critic with its target
        8. actor on obs, ddpg_put_actions(own_only=True)            pi_i(o_i) into slot i of x_pi; the other slots keep the replayed actions
        9. mlp_grad of the STEPPED critic on x_pi with g_pi -> grad_x, ddpg_action_grad
@@ -182,8 +183,11 @@ class DDPGLearner:
     the statistics: `stats` f64 [updates, 8] (TD_STATS) and `step_stats_actor` / `step_stats_critic` f64 [updates, 4] (ADAM_STATS).
     update() runs `updates` updates and returns `stats`; capture() records them as ONE graph, the ring's draw included, that update()
     replays from then on; set_lr writes the device hyper rows; sync() re-packs all four blobs after an outside edit of the networks;
-    publish copies the actors into a rollout.  Parameter sharing, a second critic (TD3) and prioritised sampling are not here
-    (td_head's `weight` is the hook for the last)."""
+    publish copies the actors into a rollout.  With a replay.PrioritizedReplayBuffer the draw of step 1 is proportional to the
+    ring's priorities, step 6 weighs both losses by the batch's importance weights (`buffer.weights`; TD_STATS' `weight` column is their
+    mean), and directly after it, before the critic's step, the rows drawn get new priorities from |q - y| (`buffer.update_priorities`):
+    six more launches per update at 2^20 rows (the weights; five of the priority update), inside the same graph; with a plain DeviceReplayBuffer every launch is as it was.
+    Parameter sharing and a second critic (TD3) are not here."""
 
     def __init__(self, buffer, actor, critic=None, *, critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3, lr_critic=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=1):
@@ -229,6 +233,7 @@ class DDPGLearner:
         self._adam_ws = _workspace(None, mlp_adam_step_workspace_bytes(nA, 1), dev)
         self._buf_a = _buffers(actor).get(B, nA, Do, dev)
         self._buf_c = _buffers(critic).get(B, nA, Dc, dev, gx=True)
+        self._prioritized = isinstance(buffer, PrioritizedReplayBuffer)
         self._graph = None
 
     def _update(self, u):
@@ -242,7 +247,10 @@ class DDPGLearner:
         ddpg_put_actions(self._y4, self._x_next, Do, k, central=c, own_only=False)
         _mlp_forward(lib, self._blob_tc, self._x_next, self._yq4, self._q_next)
         _mlp_forward(lib, self._blob_c, self._x_cur, self._yq4, self._q)
-        td_head(self._q, self._q_next, rew, done, self.gamma, out=(self._g_q, self._g_pi, self.td, self.stats[u]), workspace=self._head_ws)
+        td_head(self._q, self._q_next, rew, done, self.gamma, weight=buf.weights if self._prioritized else None,
+                out=(self._g_q, self._g_pi, self.td, self.stats[u]), workspace=self._head_ws)
+        if self._prioritized:
+            buf.update_priorities(self._q, self.td)
         row_c = _mlp_grad(lib, self._buf_c, self._blob_c, self._x_cur, self._g_q, False)
         mlp_adam_step([self.critic], [row_c], [self.adam_critic], [self._blob_c], self.hyper_critic, self.step_critic,
                       targets=[self.target_critic], target_blobs=[self._blob_tc], stats=self.step_stats_critic[u], workspace=self._adam_ws)
@@ -268,12 +276,14 @@ class DDPGLearner:
         """Every tensor an update writes that outlives it."""
         return ([self.buffer._draws, self.step_actor, self.step_critic, self._blob_a, self._blob_c, self._blob_ta, self._blob_tc, self.stats,
                  self.step_stats_actor, self.step_stats_critic] + [t for st in (self.adam_actor, self.adam_critic) for t in (st.m, st.v)]
-                + [getattr(net, p) for net in (self.actor, self.critic, self.target_actor, self.target_critic) for p in PARAMS])
+                + [getattr(net, p) for net in (self.actor, self.critic, self.target_actor, self.target_critic) for p in PARAMS]
+                + ([self.buffer._leaves, self.buffer.tree, self.buffer.max_priority] if self._prioritized else []))
 
     def capture(self):
         """Record the whole update() -- `updates` updates, the ring's draws included -- as one graph on one stream; update() replays it
         from then on.  One eager update runs first as the warm-up and is undone: capture() leaves parameters, targets, moments, step
-        counts, blobs, statistics and the ring's draw counter bit for bit as they were."""
+        counts, blobs, statistics, the ring's draw counter and (a prioritised ring) its priorities, tree and max_priority bit for bit as
+        they were."""
         self._graph = _capture(self._run, self._state, self.buffer.actor_states.device)
         return self
 

@@ -211,3 +211,126 @@ class DeviceReplayBuffer(ReplayBuffer):
         o, o_, a = self._b_obs, self._b_obs_, self._b_act
         return (o.transpose(0, 1), o.reshape(B, -1), a.transpose(0, 1), self._b_rew,
                 o_.transpose(0, 1), o_.reshape(B, -1), self._b_done)
+
+
+def prio_levels(M):
+    """The int64 levels of the sum tree over M rows (include/battlespace_hip.h, BsxPrioTree) -> [(offset, count), ...] bottom-up, in
+    nodes of the one node buffer: level 0 has ceil(M / 64) nodes (each the sum of 64 leaves), every next one ceil(previous / 64), the last
+    is the root.  The leaves are a buffer of their own: uint32 [64 * ceil(M / 64)]."""
+    M = int(M)
+    if not 1 <= M < 2 ** 31:
+        raise ValueError("prio_levels: 1 <= M < 2^31 is needed")
+    out, off, n = [], 0, -(-M // 64)
+    while True:
+        out.append((off, n))
+        if n == 1:
+            return out
+        off, n = off + n, -(-n // 64)
+
+
+class PrioritizedReplayBuffer(DeviceReplayBuffer):
+    """DeviceReplayBuffer with proportional prioritised sampling (Schaul et al. 2016) kept wholly on the device
+    (csrc/bsx_replay_prio.hip; the contract is written out in include/battlespace_hip.h at BsxPrioTree): a sum tree of fan-out 64 over
+    integer priorities that `sample()`, the three store calls and `update_priorities()` keep current, O(B log M) words per call, all of
+    it asynchronous, capturable and free of allocation after construction.
+
+        buf = PrioritizedReplayBuffer(1_000_000, 512, env.possible_red, env.obs_size, env.obs_size * n, 4, seed=0, alpha=0.6, beta=0.4)
+        buf.append_rollout(ro, range(n))       # the new rows get `max_priority`
+        batch = buf.sample()                   # P(row) = p / sum p; buf.weights [B, nA] = (p_min / p) ^ beta, buf.last_idx = the rows
+        buf.update_priorities(q, y)            # p = (min(max_i |q - y|, delta_max) + eps) ^ alpha for the rows of last_idx
+
+    A priority is a uint32 fixed-point number of scale 2^16 (65536 = 1.0): 0 = never stored (never drawn), a stored row has 1 .. 2^31,
+    and every tree node is the exact int64 sum of its children, so tree and draw are reproducible bit for bit (tests/prio_util.py
+    restates them in numpy).  Public state, all on the device:
+      priorities    the M leaves, an int32-TYPED view of the uint32 words (torch has no arithmetic on uint32): 2^31 reads as -2^31,
+                    `priorities.view(torch.uint32)` or `& 0xFFFFFFFF` in int64 gives the value.  Write it, then call rebuild_tree()
+      tree          int64 [nodes]: the levels of prio_levels(M), concatenated bottom-up; the last word is the root, the sum of all
+      max_priority  int32-typed [1]: the largest priority an update has written (65536 at first); what a fresh row gets
+      prio_hyper    float32 [4]: alpha, beta, eps, delta_max (set_alpha / set_beta fill it: a captured graph reads it at every replay)
+      weights       float32 [B, nA]: the latest batch's importance weights, normalised by the batch's largest, one value across a row
+    `sample(idx=...)` returns the given rows (the base behaviour) and fills `weights` and `last_idx` for them.  Setting `mem_cntr` is
+    refused: the tree would no longer describe the ring."""
+
+    def __init__(self, mem_size, batch_size, agent_list, obs_size, critic_dims, n_actions, device="cuda", generator=None, seed=0,
+                 alpha=0.6, beta=0.4, eps=1e-6, delta_max=32.0):
+        super().__init__(mem_size, batch_size, agent_list, obs_size, critic_dims, n_actions, device=device, generator=generator, seed=seed)
+        hyper = [float(alpha), float(beta), float(eps), float(delta_max)]
+        if not (hyper[0] >= 0.0 and hyper[1] >= 0.0 and hyper[2] >= 0.0 and hyper[3] > 0.0):
+            raise ValueError("alpha, beta and eps must be >= 0 and delta_max > 0")
+        dev, M, B = self.actor_states.device, self.mem_size, self.batch_size
+        levels = prio_levels(M)
+        self._leaves = torch.zeros(64 * levels[0][1], dtype=torch.int32, device=dev)
+        self.priorities = self._leaves[:M]
+        self.tree = torch.zeros(levels[-1][0] + 1, dtype=torch.int64, device=dev)
+        self.max_priority = torch.full((1,), 65536, dtype=torch.int32, device=dev)
+        self.prio_hyper = torch.tensor(hyper, dtype=torch.float32, device=dev)
+        self.weights = torch.zeros((B, self.n_agents), dtype=torch.float32, device=dev)
+        self._drawn = torch.zeros(B, dtype=torch.int32, device=dev)        # the leaves of the rows drawn: the weights' workspace
+        self._tree = self._lib.BsxPrioTree(self._leaves.data_ptr(), self.tree.data_ptr(), self.max_priority.data_ptr(),
+                                           self.prio_hyper.data_ptr(), M)
+        if dev.type == "cuda":
+            self.rebuild_tree()
+
+    mem_cntr = property(DeviceReplayBuffer.mem_cntr.fget)
+
+    @mem_cntr.setter
+    def mem_cntr(self, value):
+        if "_tree" in self.__dict__:                 # (the base constructor's `mem_cntr = 0` comes before the tree)
+            raise ValueError("mem_cntr of a PrioritizedReplayBuffer cannot be set: the priority tree would no longer describe the ring")
+
+    def _prio(self, entry, *args):
+        import ctypes
+        self._lib.check(getattr(self._lib.load(), entry)(ctypes.byref(self._tree), *args, self._stream()), entry)
+
+    def rebuild_tree(self):
+        """Every level of `tree` recomputed from `priorities`: after they have been written directly.  Asynchronous."""
+        self._prio("bsx_replay_prio_rebuild")
+
+    def set_alpha(self, alpha):
+        """The exponent of the priorities written from now on (a device fill: no host synchronisation; leaves already written stay)."""
+        if not float(alpha) >= 0.0:
+            raise ValueError("alpha must be >= 0")
+        self.prio_hyper[0].fill_(float(alpha))
+
+    def set_beta(self, beta):
+        """The exponent of the importance weights from the next sample() on, inside a captured graph too (a device fill)."""
+        if not float(beta) >= 0.0:
+            raise ValueError("beta must be >= 0")
+        self.prio_hyper[1].fill_(float(beta))
+
+    def _append(self, src, rows):
+        """The ring's three launches, then bsx_replay_prio_append: the rows just written get max_priority, the tree is repaired."""
+        stored = super()._append(src, rows)
+        self._prio("bsx_replay_prio_append", self._counter.data_ptr(), stored.data_ptr(), rows)
+        return stored
+
+    def sample(self, idx=None):
+        """The base's tuple, drawn in proportion to the priorities and gathered in one launch, `weights` in a second; `last_idx` holds the
+        rows.  idx: these rows instead (the base's checks and one host synchronisation), with `weights` and `last_idx` filled for them."""
+        import ctypes
+        B = self.batch_size
+        if idx is not None:
+            out = ReplayBuffer.sample(self, idx)
+            self.last_idx.copy_(torch.as_tensor(idx, device=self.last_idx.device).long())
+            self._prio("bsx_replay_prio_weights", self.last_idx.data_ptr(), B, self.n_agents, self.weights.data_ptr(), self._drawn.data_ptr())
+            return out
+        self._lib.check(self._lib.load().bsx_replay_prio_sample(
+            ctypes.byref(self._ring), ctypes.byref(self._tree), B, self.seed, 0, self._draws.data_ptr(), self.last_idx.data_ptr(),
+            self._b_obs.data_ptr(), self._b_obs_.data_ptr(), self._b_act.data_ptr(), self._b_rew.data_ptr(), self._b_done.data_ptr(),
+            self.weights.data_ptr(), self._drawn.data_ptr(), self._stream()), "bsx_replay_prio_sample")
+        self._draws.add_(1)
+        o, o_, a = self._b_obs, self._b_obs_, self._b_act
+        return (o.transpose(0, 1), o.reshape(B, -1), a.transpose(0, 1), self._b_rew,
+                o_.transpose(0, 1), o_.reshape(B, -1), self._b_done)
+
+    def update_priorities(self, q, y, idx=None):
+        """New priorities for the rows of idx (int64 [B]; `last_idx` if None) from q and y float32 [B, nA] -- td_head's q and td: per row
+        the largest |q - y| of its agents, clipped to delta_max (a NaN counts as delta_max), + eps, to the power alpha; a row named more
+        than once keeps the largest; max_priority and the tree follow.  Asynchronous; 5 launches at M = 2^20."""
+        B, nA = self.batch_size, self.n_agents
+        idx = self.last_idx if idx is None else idx
+        for t, name, shape, dtype in ((q, "q", (B, nA), torch.float32), (y, "y", (B, nA), torch.float32), (idx, "idx", (B,), torch.int64)):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() \
+                    or t.device != self._leaves.device:
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {self._leaves.device}")
+        self._prio("bsx_replay_prio_update", idx.data_ptr(), q.data_ptr(), y.data_ptr(), B, nA)

@@ -375,6 +375,73 @@ int bsx_replay_append(const BsxReplayRing* ring, const BsxReplaySource* src, int
 int bsx_replay_sample(const BsxReplayRing* ring, int64_t B, uint64_t seed, uint64_t seq, const uint64_t* seq_base, int64_t* idx,
                       float* obs, float* obs_next, float* act, float* rew, uint8_t* done, void* stream);
 
+/* ---- proportional prioritised replay on that ring (Schaul et al. 2016; csrc/bsx_replay_prio.hip, replay.PrioritizedReplayBuffer):
+ * a sum tree that the sampler, the appender and the learner keep current on the device, O(B log M) words per call.
+ *
+ * Priorities are integers.  A leaf is a uint32 fixed-point priority p of scale 2^16 (BSX_PRIO_ONE = 1.0): p = 0 is a row never
+ * stored, which can never be drawn; a stored row has p in [1, 2^31].  Every inner node is the int64 SUM OF ITS CHILDREN.  Integer sums
+ * are exact and order-free, so the tree has one right value whatever order a kernel adds in, and with M < 2^31 rows the root stays
+ * below 2^62.  Everything downstream of the leaves -- the tree and the draw -- is therefore exact; only the float -> leaf conversion
+ * and the weights carry a tolerance.
+ *
+ * Layout.  Fan-out BSX_PRIO_FANOUT = 64 (one wavefront reads one node's children, one per lane).  leaves: uint32
+ * [64 * ceil(M / 64)], the pad 0.  nodes: int64 levels of ceil(previous / 64) nodes each above them -- level 0 has ceil(M / 64) nodes, each
+ * the sum of 64 leaves -- up to a single root, concatenated bottom-up with no padding (replay.prio_levels(M) lists (offset, count));
+ * child c of node n of a level is node 64 n + c of the level below, absent (0) past that level's count.
+ * max_priority: a device uint32, the largest p ever written by an update (the caller initialises it to BSX_PRIO_ONE); fresh rows get it.
+ * hyper: float32 [4] on the device, 16-byte aligned: alpha, beta, eps, delta_max.  Every kernel reads it at launch, so a captured graph
+ * sees a new value with no host work. */
+#define BSX_PRIO_FANOUT 64
+#define BSX_PRIO_ONE 65536u
+#define BSX_PRIO_SALT 0x3C6EF372u   /* the prioritised draw's Philox key salt (the uniform sampler's is 0x5EED5A3C) */
+typedef struct BsxPrioTree {
+    uint32_t* leaves;        /* uint32 [64 * ceil(M / 64)], 4-byte aligned */
+    int64_t* nodes;          /* int64 [bsx_replay_prio_bytes(M) / 8], 8-byte aligned */
+    uint32_t* max_priority;  /* device uint32 */
+    const float* hyper;      /* float32 [4]: alpha, beta, eps, delta_max; 16-byte aligned */
+    int64_t M;               /* the ring's rows, 1 <= M < 2^31 */
+} BsxPrioTree;
+
+/* Size of the node buffer for M rows: 8 bytes per node of every level. */
+int bsx_replay_prio_bytes(int64_t M, size_t* bytes);
+
+/* Every level recomputed from the leaves (after the caller has written leaves directly): one launch per level of more than 64 nodes,
+ * then one workgroup for the levels above. */
+int bsx_replay_prio_rebuild(const BsxPrioTree* tree, void* stream);
+
+/* The draw.  For batch position b: w = Philox4x32-10 with bsx_replay_sample's counter (b, b >> 32, seq, seq >> 32), seq = seq + *seq_base,
+ * and key (seed, (seed >> 32) ^ BSX_PRIO_SALT); r = (uint64(w.y) << 32) | w.x; u = mulhi64(r, total), total the root.  Descend from the
+ * root: at a node take the first child j whose inclusive prefix sum exceeds u, subtract the exclusive prefix, go on; idx[b] is the leaf
+ * reached = searchsorted(cumsum(leaves), u, side = right), exactly.  Draws are independent and with replacement.  The five fields of
+ * the rows are gathered as bsx_replay_sample gathers them.  weights float32 [B][nA] = (p_min / p_b) ^ beta in every column of row b, p_b
+ * the leaf drawn and p_min the smallest of the batch (an exact integer minimum): importance weights normalised by the batch's
+ * largest, so n and total cancel.  The power is taken in binary64 (the integers are exact there) and rounded to float32 once; beta = 0
+ * gives exactly 1.  total = 0 (an empty ring): every idx is 0 and every weight +0.0.  A tree that does not sum
+ * its leaves (written without a rebuild) still never yields an address outside the tree or the ring.
+ * workspace: 4 B bytes, 4-byte aligned (the leaves drawn).  tree->M must be ring->M.  Two launches (draw + gather; weights). */
+int bsx_replay_prio_sample(const BsxReplayRing* ring, const BsxPrioTree* tree, int64_t B, uint64_t seed, uint64_t seq, const uint64_t* seq_base,
+                           int64_t* idx, float* obs, float* obs_next, float* act, float* rew, uint8_t* done, float* weights, void* workspace,
+                           void* stream);
+
+/* The same weights for rows the caller names: idx int64 [B] (rows outside [0, M) and rows never stored get +0.0 and take no part in
+ * p_min).  Two launches. */
+int bsx_replay_prio_weights(const BsxPrioTree* tree, const int64_t* idx, int64_t B, int nA, float* weights, void* workspace, void* stream);
+
+/* Priorities from TD errors.  q, y float32 [B][nA] (bsx_td_head's q and td).  For batch row b: delta = max_i fminf(|q[b][i] - y[b][i]|,
+ * delta_max) -- fminf's rule: a NaN error counts as delta_max, the tree never holds garbage --, pi = powf(delta + eps, alpha) in float32,
+ * p = clamp(rint(pi * 65536), 1, 2^31); alpha = 0 gives BSX_PRIO_ONE for every row.  Leaf idx[b] becomes p; a row named more than once
+ * gets the LARGEST of its occurrences' p (an integer maximum: order-free); *max_priority becomes the maximum of itself and every p
+ * written; every ancestor of a touched leaf is again the exact sum of its children.  Rows outside [0, M) are skipped.
+ * Launches: clear, integer max, one per level of more than 64 nodes (a wave per batch row recomputes the row's ancestor from its 64
+ * children; a level with no more nodes than B, whole), one workgroup for the levels above: 5 at M = 2^20. */
+int bsx_replay_prio_update(const BsxPrioTree* tree, const int64_t* idx, const float* q, const float* y, int64_t B, int nA, void* stream);
+
+/* After bsx_replay_append(ring, ..., rows, ..., stored): the rows it wrote get the priority *max_priority and the tree is repaired.
+ * With s = min(*stored, M) they are (*counter - s + j) mod M for j < s, known only on the device: grids are sized by `rows` (the append's
+ * upper bound) and surplus threads exit; s = 0 changes nothing.  The range is contiguous mod M, so per level the touched nodes are
+ * one or two contiguous runs: one wave per touched node.  Launches: leaves, one per level of more than 64 nodes, the top. */
+int bsx_replay_prio_append(const BsxPrioTree* tree, const int64_t* counter, const int64_t* stored, int64_t rows, void* stream);
+
 /* ---- GAE(gamma, lambda) advantages and returns on device (deep-rl-battlespace_amd/advantage.py): what a PPO update needs from a
  * rollout's records, computed with no host round trip so that it can sit in the rollout's captured graph.
  *

@@ -1,0 +1,450 @@
+"""The prioritised replay ring (csrc/bsx_replay_prio.hip, replay.PrioritizedReplayBuffer) on the MI355X against tests/prio_util.py:
+the tree's every level and the rows drawn are the numpy reference's, exactly; the gathered fields are the ring's rows; the weights and
+the priorities written from TD errors hold the float64 yardstick's bars; an update leaves the integer maximum per row and an append
+max_priority on the rows just written, with every level again the exact sum of the leaves; nothing is written outside the buffers; and
+a DDPGLearner on such a ring is, bit for bit, the by-hand sequence of the public calls, captured or not."""
+import gc
+
+import numpy as np
+import pytest
+import torch
+
+import ddpg_util as D
+import guard_util as G
+import prio_util as PU
+import yardstick_util as Y
+
+pytestmark = pytest.mark.gpu
+
+RING_FIELDS = ("actor_states", "actor_new_states", "action_mem", "rew_mem", "done_mem")
+OBS = 8
+SIZES = (5, 64, 65, 4097)           # a single ragged node, an exact node, a one-leaf tail, three levels ragged at two of them
+TEAMS = ((1, 3), (3, 4))            # (nA, k)
+BATCHES = (1, 33, 512)
+
+
+def _buf(M, B, nA=1, k=4, seed=0, D_=OBS, **kw):
+    from deep_rl_battlespace_amd.replay import PrioritizedReplayBuffer
+    return PrioritizedReplayBuffer(M, B, list(range(nA)), D_, D_ * nA, k, device="cuda", seed=seed, **kw)
+
+
+def _plain(M, B, nA=1, k=4, seed=0, D_=OBS):
+    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer
+    return DeviceReplayBuffer(M, B, list(range(nA)), D_, D_ * nA, k, device="cuda", seed=seed)
+
+
+def _fill_ring(buf, seed=0):
+    """mem_size random rows through _put: a full ring (the tests then write the priorities they want)."""
+    buf._put(*_rows(buf.mem_size, buf.n_agents, buf.n_actions, seed))
+
+
+def _set_leaves(buf, p):
+    buf.priorities.copy_(PU.as_leaves(p))
+    buf.rebuild_tree()
+
+
+def _leaves(buf):
+    return PU.unsigned(buf.priorities)
+
+
+def _assert_tree_exact(buf, what=""):
+    """Every level is the exact sum of the leaves read back; the pad leaves are 0."""
+    torch.cuda.synchronize()
+    assert np.array_equal(buf.tree.cpu().numpy(), PU.node_buffer(_leaves(buf))), what
+    assert not buf._leaves[buf.mem_size:].any(), what
+
+
+def _rows_of_batch(buf, idx):
+    """The five fields of ring rows idx, as the [B, nA, ...] buffers sample() fills."""
+    return [getattr(buf, f)[idx] for f in RING_FIELDS]
+
+
+def _batch(buf):
+    return [buf._b_obs, buf._b_obs_, buf._b_act, buf._b_rew, buf._b_done]
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+# ------------------------------------------------------------------------------------------------ draw and weights
+@pytest.mark.parametrize("B", BATCHES)
+@pytest.mark.parametrize("team", TEAMS, ids=lambda t: f"nA{t[0]}-k{t[1]}")
+@pytest.mark.parametrize("M", SIZES)
+def test_the_tree_the_rows_drawn_the_gathered_fields_and_the_weights(M, team, B):
+    nA, k = team
+    buf = _buf(M, B, nA, k, seed=9)
+    _fill_ring(buf)
+    p = PU.random_leaves(M)
+    _set_leaves(buf, p)
+    _assert_tree_exact(buf)
+    assert np.array_equal(_leaves(buf), p) and int(buf.tree[-1]) == int(p.sum())
+    beta = float(buf.prio_hyper[1])
+    for call in range(3):
+        res = buf.sample()
+        torch.cuda.synchronize()
+        want = PU.draw_rows(p, 9, call, B)
+        assert np.array_equal(buf.last_idx.cpu().numpy(), want), call                   # every b, exactly
+        assert (p[want] > 0).all() and int(buf._draws) == call + 1
+        for got, ring in zip(_batch(buf), _rows_of_batch(buf, buf.last_idx)):
+            assert torch.equal(_bits(got), _bits(ring)), call                           # the ring's rows, bit for bit
+        assert res[0].shape == (nA, B, OBS) and torch.equal(res[0], buf._b_obs.transpose(0, 1)) and res[3] is buf._b_rew
+        w = buf.weights.cpu().numpy()
+        assert w.shape == (B, nA) and (w == w[:, :1]).all()                              # one value across a row's columns
+        ref, yard = PU.weights_ref(p[want], beta), PU.weights_yard(p[want], beta)
+        assert ref.max() == 1.0 and w.max() == 1.0
+        _, bad = Y.check_tensors([("weights", w[:, 0].astype(np.float64), ref, yard, Y.FACTORS)], f"M{M} B{B} call {call}", unit="w")
+        assert not bad
+    buf.set_beta(0.0)
+    buf.sample()
+    assert bool((buf.weights == 1.0).all())                                              # beta = 0: exactly 1
+    # the rows a caller names: the base's tuple, weights and last_idx for them
+    idx = torch.from_numpy(np.flatnonzero(p)[np.arange(B) % int((p > 0).sum())]).cuda()
+    buf.set_beta(0.7)
+    res = buf.sample(idx=idx)
+    torch.cuda.synchronize()
+    assert torch.equal(buf.last_idx, idx) and torch.equal(res[3], buf.rew_mem[idx]) and torch.equal(res[0], buf.actor_states[idx].transpose(0, 1))
+    w, rows = buf.weights.cpu().numpy(), idx.cpu().numpy()
+    _, bad = Y.check_tensors([("weights", w[:, 0].astype(np.float64), PU.weights_ref(p[rows], 0.7), PU.weights_yard(p[rows], 0.7), Y.FACTORS)],
+                             f"M{M} B{B} idx", unit="w")
+    assert not bad and (w == w[:, :1]).all() and int(buf._draws) == 4
+
+
+@pytest.mark.parametrize("M", SIZES)
+def test_an_empty_ring_draws_row_0_with_weight_plus_zero(M):
+    buf = _buf(M, 33, 3, 4)
+    buf.weights.fill_(7.0)
+    buf.last_idx.fill_(3)
+    res = buf.sample()
+    torch.cuda.synchronize()
+    assert not buf.last_idx.any() and not buf.weights.view(torch.int32).any()           # +0.0: no bit set
+    assert all(float(t.float().abs().max()) == 0.0 for t in res) and not buf.tree.any()
+
+
+def test_set_beta_reaches_a_captured_sample():
+    M, B = 4097, 512
+    buf, eager = _buf(M, B, 3, 4, seed=5), _buf(M, B, 3, 4, seed=5)
+    p = PU.random_leaves(M, seed=1)
+    for b in (buf, eager):
+        _set_leaves(b, p)
+    buf.sample(); buf._draws.zero_()                                                      # warm-up outside the capture
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        buf.sample()
+    for call, beta in enumerate((0.4, 1.0, 0.0)):
+        buf.set_beta(beta); eager.set_beta(beta)
+        graph.replay(); eager.sample()
+        torch.cuda.synchronize()
+        rows = PU.draw_rows(p, 5, call, B)
+        assert np.array_equal(buf.last_idx.cpu().numpy(), rows)                          # fresh draws at every replay
+        assert torch.equal(buf.weights.view(torch.int32), eager.weights.view(torch.int32))
+        w = buf.weights[:, 0].double().cpu().numpy()
+        _, bad = Y.check_tensors([("weights", w, PU.weights_ref(p[rows], beta), PU.weights_yard(p[rows], beta), Y.FACTORS)], f"beta {beta}", unit="w")
+        assert not bad and (beta != 0.0 or (w == 1.0).all()) and (beta == 0.0 or w.min() < 1.0)
+    with pytest.raises(ValueError):
+        buf.set_beta(-1.0)
+
+
+# ------------------------------------------------------------------------------------------------ update
+def _td_pairs(B, nA, seed):
+    """q, y float32 [B, nA]: errors from 1e-4 to 1e3 (some above delta_max = 32), a NaN in about one row in eight."""
+    g = np.random.default_rng(seed)
+    y = g.standard_normal((B, nA)).astype(np.float32)
+    q = (y + g.choice([-1.0, 1.0], (B, nA)) * 10.0 ** g.uniform(-4.0, 3.0, (B, nA))).astype(np.float32)
+    q[g.random((B, nA)) < 0.125 / nA] = np.nan
+    return q, y
+
+
+@pytest.mark.parametrize("M,B,nA", [(5, 64, 3), (64, 33, 1), (65, 512, 3), (4097, 33, 1), (4097, 512, 3), (5, 1, 1)])
+def test_update_writes_the_integer_maximum_per_row_and_repairs_every_level(M, B, nA):
+    buf, one = _buf(M, B, nA, 4), _buf(M, 1, nA, 4)
+    old = PU.random_leaves(M, seed=2)
+    _set_leaves(buf, old)
+    g = np.random.default_rng(50 + M + B)
+    rows = g.integers(0, M, B)
+    if B > 1:
+        rows[-1] = rows[0]                                                               # at least one row named twice
+    idx = torch.from_numpy(rows).cuda()
+    q, y = _td_pairs(B, nA, 60 + M + B)
+    assert B < 8 or (np.isnan(q).any() and (np.abs(q - y) > 32.0).any() and (np.abs(q - y) < 1.0).any())
+    tq, ty = torch.from_numpy(q).cuda(), torch.from_numpy(y).cuda()
+    buf.update_priorities(tq, ty, idx)
+    # what the kernel writes per occurrence: the same inputs one row per call (B = 1), each on a row of its own ring
+    occ = torch.zeros(B, dtype=torch.int32, device="cuda")
+    for b in range(B):
+        one.update_priorities(tq[b:b + 1], ty[b:b + 1], idx[b:b + 1])
+        occ[b:b + 1].copy_(one.priorities[idx[b:b + 1]])
+    torch.cuda.synchronize()
+    occ = PU.unsigned(occ)
+    got = _leaves(buf)
+    assert np.array_equal(got, PU.update_max(old, rows, occ))                            # the maximum per named row; the others untouched
+    assert len(np.unique(rows)) < B or B == 1
+    assert PU.unsigned(buf.max_priority)[0] == max(PU.ONE, int(occ.max())) and (occ >= 1).all() and (occ <= PU.P_MAX).all()
+    _assert_tree_exact(buf)
+    _assert_tree_exact(one)
+    hyper = buf.prio_hyper.cpu().numpy()
+    named = np.unique(rows)
+    per_row = lambda x: np.array([x[rows == r].max() for r in named])                   # noqa: E731
+    ref, yard = per_row(PU.priority_ref(q, y, hyper)), per_row(PU.priority_yard(q, y, hyper))
+    ratios = Y.error_ratios(got[named].astype(np.float64), ref, yard)
+    print(f"M{M} B{B} nA{nA}: leaf error ratios mean {ratios[0]:.3f} (<= {Y.FACTORS[0]}), max {ratios[1]:.3f} (<= {Y.FACTORS[1]}); "
+          f"errors {Y.errors(got[named].astype(np.float64), ref)}, yardstick {Y.errors(yard, ref)}")
+    assert Y.within(ratios)
+    nan_rows = rows[np.isnan(q).any(1)]
+    top = float(np.rint(PU.priority_ref(np.full((1, 1), 99.0, np.float32), np.zeros((1, 1), np.float32), hyper)[0]))
+    assert all(abs(float(got[r]) - top) <= 1.0 for r in nan_rows)                        # a NaN error counts as delta_max
+    # idx defaults to last_idx; alpha = 0 writes 1.0 for every row (a device fill: set_alpha)
+    buf.set_alpha(0.0)
+    buf.last_idx.copy_(idx)
+    buf.update_priorities(tq, ty)
+    torch.cuda.synchronize()
+    want = got.copy(); want[rows] = PU.ONE
+    assert np.array_equal(_leaves(buf), want)
+    _assert_tree_exact(buf)
+    for bad in (tq[:, :0], tq.double(), tq.cpu()):
+        with pytest.raises(ValueError):
+            buf.update_priorities(bad, ty, idx)
+
+
+# ------------------------------------------------------------------------------------------------ append
+def _rows(R, nA, k, seed):
+    g = torch.Generator(device="cuda"); g.manual_seed(seed)
+    rnd = lambda *s: torch.randn(s, generator=g, device="cuda")                         # noqa: E731
+    return rnd(R, nA, OBS), rnd(R, nA, k), rnd(R, nA), rnd(R, nA, OBS), torch.rand((R, nA), generator=g, device="cuda") < 0.3
+
+
+def _assert_same_ring(buf, twin, what):
+    for f in RING_FIELDS:
+        assert torch.equal(_bits(getattr(buf, f)), _bits(getattr(twin, f))), (what, f)
+    assert buf.mem_cntr == twin.mem_cntr, what
+
+
+@pytest.mark.parametrize("M,nA,k", [(5, 1, 3), (64, 3, 4), (65, 1, 3), (4097, 3, 4)])
+def test_store_transition_rows_get_max_priority_across_the_wrap_and_past_the_ring(M, nA, k):
+    """Dense rows through _put (what store_transition builds): a first fill that stops just before the wrap, a store across it, one of
+    more rows than the ring holds, one single row -- each against DeviceReplayBuffer for the ring and prio_util.append_range for the leaves."""
+    buf, twin = _buf(M, 4, nA, k), _plain(M, 4, nA, k)
+    want = np.zeros(M, np.int64)
+    counter = 0
+    for step, (R, maxp) in enumerate(((max(M - 2, 1), 65536), (min(5, M), 200_001), (M + 70, 1 << 31), (1, 77), (2 * M, 65_537))):
+        buf.max_priority.copy_(PU.as_leaves([maxp]))                                     # raised first: the rows must carry this value
+        rows = _rows(R, nA, k, 10 * M + step)
+        for b in (buf, twin):
+            b._put(rows[0], rows[1], rows[2], rows[3], rows[4])
+        counter += R
+        want = PU.append_range(want, counter, R, maxp)
+        torch.cuda.synchronize()
+        assert np.array_equal(_leaves(buf), want), step
+        assert int(buf._stored) == R and PU.unsigned(buf.max_priority)[0] == maxp
+        _assert_tree_exact(buf, step)
+        _assert_same_ring(buf, twin, step)
+        assert step != 0 or M == 1 or (want[:max(M - 2, 1)] > 0).all() and (M < 3 or not want[M - 2:].any())     # rows never stored are still 0
+    agents = list(range(nA))
+    d = {a: torch.randn(3, OBS) for a in agents}
+    act = {a: torch.randn(3, k) for a in agents}
+    flag = {a: torch.zeros(3, dtype=torch.bool) for a in agents}
+    for b in (buf, twin):
+        b.store_transition(d, act, {a: torch.randn(3, generator=torch.Generator().manual_seed(1)) for a in agents}, d, flag)
+    counter += 3
+    torch.cuda.synchronize()
+    assert np.array_equal(_leaves(buf), PU.append_range(want, counter, 3, 65_537))
+    _assert_tree_exact(buf, "store_transition")
+    _assert_same_ring(buf, twin, "store_transition")
+
+
+def _rollout(n, E, T, seed):
+    from deep_rl_battlespace_amd import instinct, parallel_env
+    from deep_rl_battlespace_amd.rollout import PolicyRollout, StackedActor
+    env = parallel_env(n_agents=n, n_envs=E, seed=seed, auto_reset=True, continuous_actions=False); env.reset()
+    torch.manual_seed(seed)
+    actor = StackedActor(2 * n, 3 * n + 2, 4, device="cuda")
+    ro = PolicyRollout(env, actor, T, noise_std=0.2, one_launch=True, opponent=instinct.Team(env.possible_blue, env.possible_red, env))
+    ro.start()
+    return env, ro
+
+
+@pytest.mark.parametrize("n,M", [(1, 4097), (2, 500), (1, 200)], ids=["1v1-M4097", "2v2-M500-wraps", "1v1-M200-more-rows-than-ring"])
+def test_append_rollout_of_a_real_rollout_with_finished_games(n, M):
+    """E = 96, T = 4: four appends of a rollout's records with a third of the game-ticks marked finished (their rows are skipped), then
+    one with every game finished (stored = 0: nothing happens) -- ring against DeviceReplayBuffer, leaves against append_range."""
+    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer, PrioritizedReplayBuffer
+    E, T = 96, 4
+    env, ro = _rollout(n, E, T, seed=30 + n)
+    args = (M, 33, env.possible_red, env.obs_size, env.obs_size * n, 4)
+    buf, twin = PrioritizedReplayBuffer(*args, device="cuda", seed=1), DeviceReplayBuffer(*args, device="cuda", seed=1)
+    want, counter = np.zeros(M, np.int64), 0
+    g = torch.Generator(device="cuda"); g.manual_seed(8)
+    for rep, maxp in enumerate((65536, 300_000, 65_999, 1 << 31, 123)):
+        ro.run()
+        ro.env_done[:T].copy_(torch.rand((T, E), generator=g, device="cuda") < (1.0 / 3.0) if rep < 4 else torch.ones((T, E), device="cuda"))
+        buf.max_priority.copy_(PU.as_leaves([maxp]))
+        word = buf.append_rollout(ro, range(n))
+        stored = int(word.item())
+        assert twin.store_rollout(ro, range(n)) == stored == int((ro.env_done[:T] == 0).sum())
+        counter += stored
+        before = want
+        want = PU.append_range(want, counter, stored, maxp)
+        assert np.array_equal(_leaves(buf), want), rep
+        _assert_tree_exact(buf, rep)
+        _assert_same_ring(buf, twin, rep)
+        assert (0 < stored < E * T) if rep < 4 else (stored == 0 and np.array_equal(want, before))
+    assert counter > M or M == 4097
+    assert M != 4097 or (not want[counter:].any() and (want[:counter] > 0).all())      # rows never stored are still 0
+    assert M != 200 or stored == 0 and (want > 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ guards
+def test_no_stray_writes_from_sample_update_or_append():
+    """M = 4097, B = 33: leaves, nodes, weights, last_idx, max_priority and the weights' workspace inside guard slabs."""
+    from deep_rl_battlespace_amd import _lib
+    M, B, nA = 4097, 33, 3
+    buf = _buf(M, B, nA, 4, seed=2)
+    mk = G.Buffers(guarded=True)
+    buf._leaves = mk("leaves", buf._leaves.shape, torch.int32)
+    buf.priorities = buf._leaves[:M]
+    buf.tree = mk("nodes", buf.tree.shape, torch.int64)
+    buf.weights = mk("weights", (B, nA), torch.float32)
+    buf.last_idx = mk("last_idx", (B,), torch.int64)
+    buf.max_priority = mk("max_priority", (1,), torch.int32, init=65536)
+    buf._drawn = mk("drawn", (B,), torch.int32)
+    buf._tree = _lib.BsxPrioTree(buf._leaves.data_ptr(), buf.tree.data_ptr(), buf.max_priority.data_ptr(), buf.prio_hyper.data_ptr(), M)
+    buf.rebuild_tree()
+    for step, R in enumerate((M - 3, 70, 5000, 1)):                                       # up to the wrap, across it, past the ring, one row
+        buf._put(*_rows(R, nA, 4, step))
+        _assert_tree_exact(buf, step)
+    p = PU.random_leaves(M, seed=4)
+    p[M - 1] = 1 << 31                                                                   # the last row, under the one-leaf tail node
+    _set_leaves(buf, p)
+    for call in range(3):
+        buf.sample()
+        q, y = (torch.from_numpy(a).cuda() for a in _td_pairs(B, nA, call))
+        buf.update_priorities(q, y)
+        _assert_tree_exact(buf, call)
+    buf.last_idx.copy_(torch.arange(M - B, M, device="cuda"))                            # the rows at the very end of the ring
+    buf.update_priorities(q, y)
+    buf.sample(idx=buf.last_idx.clone())
+    _assert_tree_exact(buf, "end")
+    assert mk.stray() == []
+
+
+# ------------------------------------------------------------------------------------------------ the learner
+LEARNER_SHAPES = ((33, 2, 8, 4, 1), (512, 1, 5, 4, 0))         # 2v2 central at B = 33, 1v1 own at B = 512
+
+
+def _prio_ring(rows, B, seed=3):
+    """A PrioritizedReplayBuffer of len(rows) transitions filled through _put (ddpg_util.ring's, prioritised)."""
+    obs, act, rew, obs_next, done = (r.cuda() for r in rows)
+    N, nA, Do = obs.shape
+    buf = _buf(N, B, nA, act.shape[2], seed=seed, D_=Do)
+    buf._put(obs, act, rew, obs_next, done)
+    return buf
+
+
+def _learner(shape, updates=1):
+    from deep_rl_battlespace_amd.learner import DDPGLearner
+    actor, critic, rows, *_ = D.learner_case(shape)
+    return DDPGLearner(_prio_ring(rows, shape[0]), D.gpu_copy(actor), D.gpu_copy(critic), critic_input="central" if shape[4] else "own",
+                       updates=updates, **D.KW)
+
+
+def _snapshot(x):
+    """ddpg_util.snapshot plus the ring's priorities, tree and max_priority."""
+    out = D.snapshot(x)
+    out.update(leaves=x.buffer._leaves.clone(), tree=x.buffer.tree.clone(), max_priority=x.buffer.max_priority.clone())
+    return out
+
+
+@pytest.mark.parametrize("shape", LEARNER_SHAPES, ids=D.shape_id)
+def test_a_learner_on_a_prioritised_ring_is_the_by_hand_sequence_of_the_public_calls(shape, monkeypatch):
+    """By hand: buf.sample(), ddpg_util.Hand.step(..., weight=buf.weights), and buf.update_priorities(q, td) directly after td_head,
+    before the critic's step, where DDPGLearner's docstring puts it (Hand.step calls learner.td_head: the update is hooked on there)."""
+    from deep_rl_battlespace_amd import learner as L
+    learner = _learner(shape)
+    actor, critic, rows, *_ = D.learner_case(shape)
+    hand = D.Hand(_prio_ring(rows, shape[0]), D.gpu_copy(actor), D.gpu_copy(critic), shape[4], **D.KW)
+    real, calls = L.td_head, []
+
+    def td_head_then_priorities(q, q_next, rew, done, gamma, **kw):
+        head = real(q, q_next, rew, done, gamma, **kw)
+        assert kw["weight"] is hand.buffer.weights
+        hand.buffer.update_priorities(q, head.td)
+        calls.append(1)
+        return head
+    start = _snapshot(learner)
+    assert D.differing(start, _snapshot(hand)) == []
+    for u in range(3):
+        stats = learner.update()
+        s = hand.buffer.sample()
+        monkeypatch.setattr(L, "td_head", td_head_then_priorities)
+        hand.step(s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6], 0, weight=hand.buffer.weights)
+        monkeypatch.setattr(L, "td_head", real)
+        a, b = _snapshot(learner), _snapshot(hand)
+        assert D.differing(a, b) == [] and len(calls) == u + 1, (u, D.differing(a, b))
+        assert torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
+        assert torch.equal(learner.buffer.weights.view(torch.int32), hand.buffer.weights.view(torch.int32))
+        _assert_tree_exact(learner.buffer, u)
+        # TD_STATS' weight column is the mean of the batch's weights
+        w = learner.buffer.weights.double().cpu().numpy().ravel()
+        w32 = torch.from_numpy(w).float()
+        own = max(abs(float((w32 if o is None else w32[o]).mean()) - w.mean()) for o in Y.row_orders(len(w)))
+        err, bound = abs(float(stats[0, 6]) - w.mean()), Y.scalar_bound(w.mean(), own)
+        print(f"{D.shape_id(shape)} update {u}: mean weight {w.mean():.9g}, stats error {err:.3e}, bound {bound:.3e}")
+        assert err <= bound and (u == 0 or w.min() < 1.0)
+    assert {"leaves", "tree", "max_priority", "actor.w1", "critic.w1", "draws"} <= set(D.differing(start, a))
+    assert int(learner.buffer._draws) == 3 and PU.unsigned(learner.buffer.max_priority)[0] > PU.ONE
+
+
+@pytest.mark.parametrize("shape", LEARNER_SHAPES, ids=D.shape_id)
+def test_a_captured_update_on_a_prioritised_ring_replays_the_eager_updates_and_allocates_nothing(shape):
+    captured, eager = _learner(shape, updates=2), _learner(shape, updates=2)
+    start = _snapshot(captured)
+    state = [t.detach().clone() for t in captured._state()]
+    assert captured.capture() is captured
+    assert D.differing(start, _snapshot(captured)) == []                                # capture() leaves everything as it was
+    assert all(torch.equal(_bits(a), _bits(b.detach())) for a, b in zip(state, captured._state())) and len(state) == len(eager._state())
+    assert any(t is captured.buffer._leaves for t in captured._state()) and any(t is captured.buffer.tree for t in captured._state())
+    draws = []
+    for u in range(3):
+        captured.update()
+        eager.update()
+        draws.append(captured.buffer.last_idx.clone())
+        a, b = _snapshot(captured), _snapshot(eager)
+        assert D.differing(a, b) == [], (u, D.differing(a, b))
+        _assert_tree_exact(captured.buffer, u)
+    assert not torch.equal(draws[0], draws[1]) and not torch.equal(draws[1], draws[2]) and int(captured.buffer._draws) == 6
+    del a, b
+    torch.cuda.synchronize()
+    gc.collect()
+    held = torch.cuda.memory_allocated()
+    captured.update()
+    captured.update()
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == held
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_rollout_append_and_learner_update_as_one_graph_leave_an_exact_tree(n):
+    from deep_rl_battlespace_amd.learner import DDPGLearner
+    from deep_rl_battlespace_amd.replay import PrioritizedReplayBuffer
+    from deep_rl_battlespace_amd.rollout import StackedActor
+    E, T, M, B = 96, 4, 700, 33
+    env, ro = _rollout(n, E, T, seed=50 + n)
+    buf = PrioritizedReplayBuffer(M, B, env.possible_red, env.obs_size, env.obs_size * n, 4, device="cuda", seed=4)
+    torch.manual_seed(2)
+    learner = DDPGLearner(buf, StackedActor(n, env.obs_size, 4, device="cuda"), critic_input="central", **D.KW)
+    ro.run()
+    buf.append_rollout(ro, range(n))
+    learner.update()                                                                     # the warm-up: buffers, outside the capture
+    _assert_tree_exact(buf, "eager")
+    ro.capture(then=lambda: (buf.append_rollout(ro, range(n)), learner.update()))
+    for rep in range(2):
+        before = buf.mem_cntr
+        ro.run()
+        _assert_tree_exact(buf, rep)
+        stored = int(buf._stored)
+        assert 0 < stored <= E * T and stored == buf.mem_cntr - before and int(buf._draws) == 2 + rep
+        leaves = _leaves(buf)
+        assert (leaves[:min(buf.mem_cntr, M)] > 0).all() and (buf.mem_cntr >= M or not leaves[buf.mem_cntr:].any())
+        assert bool(torch.isfinite(learner.stats).all()) and float(learner.stats[0, 6]) > 0.0
+    assert buf.mem_cntr > M                                                              # the second replay wrapped the ring
