@@ -22,6 +22,8 @@ Only what the hot path needs lives here:
     shuffle.py   a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip)
     ddpg.py      the critic join, TD head and action gradient of a DDPG update and DDPGLearner, the MADDPG update of a team from
                  its replay ring as one graph (csrc/bsx_ddpg_head.hip)
+    td3.py       what TD3 adds to it: target policy smoothing, the TD head of two critics, and TD3Learner with its delayed actor and
+                 target step (csrc/bsx_td3_head.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
@@ -30,9 +32,10 @@ from .advantage import gae  # noqa: F401
 from .learner import (TD_STATS, AdamState, DDPGLearner, Minibatch, PPOLearner, adam_step, ddpg_action_grad, ddpg_inputs, ddpg_put_actions, td_head,  # noqa: F401
                       td_head_workspace_bytes, categorical_log_prob, fused_apply, fused_mlp, is_tied, minibatch_gather, mlp_adam_step,  # noqa: F401
                       mlp_adam_step_workspace_bytes, mlp_grad, ppo_head, share_group, shuffle_rows, tie_)
+from .learner import TD3_STATS, TD3Learner, td3_head, td3_head_workspace_bytes, td3_smooth_actions  # noqa: F401
 from .envs.battle_env import parallel_env  # noqa: F401
 from .replay import PrioritizedReplayBuffer  # noqa: F401
 
 __all__ = ["AdamState", "DDPGLearner", "Minibatch", "PPOLearner", "PrioritizedReplayBuffer", "adam_step", "advantage", "categorical_log_prob", "ddpg_action_grad", "ddpg_inputs", "ddpg_put_actions", "envs", "fused_apply", "fused_mlp", "gae", "instinct", "is_tied", "learner",
            "minibatch_gather", "mlp_adam_step", "mlp_adam_step_workspace_bytes", "mlp_grad", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "TD_STATS",
-           "td_head", "td_head_workspace_bytes", "tie_"]
+           "td_head", "td_head_workspace_bytes", "tie_", "TD3Learner", "TD3_STATS", "td3_head", "td3_head_workspace_bytes", "td3_smooth_actions"]

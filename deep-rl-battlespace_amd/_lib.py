@@ -104,6 +104,10 @@ class BsxTdIo(ctypes.Structure):
     _fields_ = [(f, c_void_p) for f in ("q", "q_next", "rew", "done", "weight", "g_q", "g_pi", "td")]
 
 
+class BsxTd3Io(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("q1", "q2", "q1_next", "q2_next", "rew", "done", "weight", "g_q1", "g_q2", "g_pi", "td")]
+
+
 MINIBATCH_FIELDS = ("obs", "rec", "logp", "adv", "ret", "value", "mask")
 
 
@@ -189,6 +193,10 @@ SIGNATURES = {
     "bsx_td_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_td_head": (c_int, [ctypes.POINTER(BsxTdIo), c_int64, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
     "bsx_ddpg_action_grad": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "bsx_td3_smooth_actions": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_uint64, c_uint64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "bsx_td3_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_td3_head": (c_int, [ctypes.POINTER(BsxTd3Io), c_int64, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
     "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
                                      c_void_p]),

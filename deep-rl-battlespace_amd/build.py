@@ -57,6 +57,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_adam_step.hip"), []),
            # between the MLP calls of a DDPG update: bit copies, and a TD head whose one multiply-add is an explicit fmaf
            (os.path.join(CSRC, "bsx_ddpg_head.hip"), []),
+           # TD3's smoothing and twin-critic head: the smoothing's operations each rounded on their own, as tests/td3_util.py restates them
+           (os.path.join(CSRC, "bsx_td3_head.hip"), ["-ffp-contract=off"]),
            # the keyed row permutation and the minibatch gather: integer arithmetic and bit copies
            (os.path.join(CSRC, "bsx_shuffle.hip"), [])]
 

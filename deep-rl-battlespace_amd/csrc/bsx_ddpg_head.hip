@@ -22,39 +22,11 @@
 #include "battlespace_hip.h"
 #include "bsx_args.h"
 #include "bsx_block_sum.h"
+#include "bsx_ddpg_shared.h"         // TPB, the checked shape, the head's launch plan and the one-workgroup merge (shared with bsx_td3_head.hip)
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int WAVES = TPB / 64;
-constexpr int MERGE_TPB = 1024;
-constexpr int64_t COPY_MAX_BLOCKS = 65536;     // the copy kernels stride over their elements beyond 2^24 threads
-constexpr int64_t HEAD_MAX_BLOCKS = 1024;      // the head: one tile per workgroup up to 1 024 workgroups (four per CU), then more tiles each
-constexpr int STAT_COLS = 8;                   // a partial row: 0 | w d^2 | q | y | |d| | done | w | 0
-constexpr int NS = 6;
-constexpr int MAX_DO = 3 * BSX_MAX_N + 2;      // an observation row of the widest team
-
-typedef float F4 __attribute__((ext_vector_type(4)));
-
-struct Shape {                                 // a checked (B, nA, Do, k, central)
-    int64_t B;
-    int nA, Do, k, central, Dc, W;             // W: the observation columns of a critic row (Do, or nA Do)
-};
-
-// the ranges every bsx_ddpg_* entry shares -> false for anything outside them, Dc > BSX_MLP_MAX_D (4v4 central: 72) included
-bool shape_of(int64_t B, int nA, int Do, int k, int central, Shape* s) {
-    if (B < 1 || B >= (INT64_C(1) << 31) || nA < 1 || nA > BSX_MAX_N || Do < 1 || Do > MAX_DO || (k != 3 && k != 4)) return false;
-    if (central != 0 && central != 1) return false;
-    const int Dc = central ? nA * (Do + k) : Do + k;
-    if (Dc > BSX_MLP_MAX_D) return false;
-    *s = Shape{B, nA, Do, k, central, Dc, central ? nA * Do : Do};
-    return true;
-}
-
-unsigned copy_blocks(int64_t threads) {
-    const int64_t b = (threads + TPB - 1) / TPB;
-    return unsigned(b < COPY_MAX_BLOCKS ? b : COPY_MAX_BLOCKS);
-}
+constexpr int NS = 6;                          // a partial row: 0 | w d^2 | q | y | |d| | done | w | 0
 
 __global__ __launch_bounds__(TPB) void bsx_ddpg_inputs_kernel(const BsxDdpgBatch batch, const Shape s, float* x_cur, float* x_next, float* x_pi) {
     const int64_t M = s.B * s.nA * s.Dc, stride = int64_t(gridDim.x) * TPB;
@@ -109,21 +81,6 @@ __global__ __launch_bounds__(TPB) void bsx_ddpg_action_grad_kernel(const float* 
     }
 }
 
-struct Plan {                                  // the head's launch shape: a function of (B, nA) alone
-    int64_t M, tiles, blocks;
-    int J;
-};
-
-Plan plan_of(int64_t B, int nA) {
-    Plan p;
-    p.M = B * nA;
-    p.tiles = (p.M + TPB - 1) / TPB;
-    const int64_t J = (p.tiles + HEAD_MAX_BLOCKS - 1) / HEAD_MAX_BLOCKS;
-    p.blocks = (p.tiles + J - 1) / J;
-    p.J = int(J);
-    return p;
-}
-
 struct HeadArgs {
     BsxTdIo io;
     int64_t M, tiles;
@@ -172,31 +129,6 @@ __global__ __launch_bounds__(TPB) void bsx_td_head_kernel(const HeadArgs p) {
         p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
     }
 }
-
-// Q = 1024 / 8 threads per column; thread (q, c) adds the partial rows q, q + Q, .. in order; then 16 threads per column add every
-// 16th of those sums, and one thread the rest -- a fixed order throughout
-__global__ __launch_bounds__(MERGE_TPB) void bsx_td_merge_kernel(const double* part, int64_t blocks, int64_t M, double* stats) {
-    constexpr int C = STAT_COLS, Q = MERGE_TPB / C, G = 16;
-    __shared__ double s_q[MERGE_TPB], s_r[G * C];
-    const int tid = threadIdx.x, c = tid % C, q = tid / C;
-    double t = 0.0;
-    for (int64_t b = q; b < blocks; b += Q) t += part[b * C + c];
-    s_q[q * C + c] = t;
-    __syncthreads();
-    if (q < G) {
-        double u = 0.0;
-        for (int k = q; k < Q; k += G) u += s_q[k * C + c];
-        s_r[q * C + c] = u;
-    }
-    __syncthreads();
-    if (tid < C) {
-        double u = 0.0;
-        for (int k = 0; k < G; ++k) u += s_r[k * C + tid];
-        stats[tid] = tid == 0 ? double(M) : (tid == C - 1 ? 0.0 : u / double(M));
-    }
-}
-
-bool td_shape(int64_t B, int nA) { return B >= 1 && B < (INT64_C(1) << 31) && nA >= 1 && nA <= BSX_MAX_N; }
 
 }  // namespace
 
@@ -255,7 +187,7 @@ int bsx_td_head(const BsxTdIo* io, int64_t B, int nA, float gamma, void* workspa
     if (io->weight) hipLaunchKernelGGL(bsx_td_head_kernel<1>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
     else hipLaunchKernelGGL(bsx_td_head_kernel<0>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
     if (const hipError_t e = hipGetLastError()) return int(e);
-    hipLaunchKernelGGL(bsx_td_merge_kernel, dim3(1), dim3(MERGE_TPB), 0, s, static_cast<const double*>(part), p.blocks, p.M, stats);
+    hipLaunchKernelGGL(bsx_td_merge_kernel<false>, dim3(1), dim3(MERGE_TPB), 0, s, static_cast<const double*>(part), p.blocks, p.M, stats);
     return int(hipGetLastError());
 }
 

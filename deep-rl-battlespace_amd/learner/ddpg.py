@@ -187,12 +187,12 @@ class DDPGLearner:
     ring's priorities, step 6 weighs both losses by the batch's importance weights (`buffer.weights`; TD_STATS' `weight` column is their
     mean), and directly after it, before the critic's step, the rows drawn get new priorities from |q - y| (`buffer.update_priorities`):
     six more launches per update at 2^20 rows (the weights; five of the priority update), inside the same graph; with a plain DeviceReplayBuffer every launch is as it was.
-    Parameter sharing and a second critic (TD3) are not here."""
+    A second critic, smoothed targets and a delayed actor step (TD3) are learner.TD3Learner's; parameter sharing is not here."""
 
     def __init__(self, buffer, actor, critic=None, *, critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3, lr_critic=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=1):
         if not isinstance(buffer, DeviceReplayBuffer):
-            raise ValueError("DDPGLearner needs a DeviceReplayBuffer (it samples on the device)")
+            raise ValueError(f"{type(self).__name__} needs a DeviceReplayBuffer (it samples on the device)")
         if critic_input not in ("central", "own"):
             raise ValueError(f"critic_input must be 'central' or 'own', got {critic_input!r}")
         self.buffer, self.central = buffer, critic_input == "central"
@@ -214,8 +214,8 @@ class DDPGLearner:
                                  f"{'StackedActor' + str(have) if None not in have else type(net).__name__}")
         f = _f32(torch.zeros, dev)                               # zero-filled: what no kernel of an update writes stays +0
         self._x_cur, self._x_next, self._x_pi = f(B, nA, Dc), f(B, nA, Dc), f(B, nA, Dc)
-        _check_mlp(actor, buffer._b_obs, True, "DDPGLearner")
-        _check_mlp(critic, self._x_cur, False, "DDPGLearner")
+        _check_mlp(actor, buffer._b_obs, True, type(self).__name__)
+        _check_mlp(critic, self._x_cur, False, type(self).__name__)
         self.actor, self.critic = actor, critic
         self.target_actor, self.target_critic = copy.deepcopy(actor), copy.deepcopy(critic)
         for t in (self.target_actor, self.target_critic):

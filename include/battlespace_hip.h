@@ -842,6 +842,69 @@ int bsx_td_head(const BsxTdIo* io, int64_t B, int nA, float gamma, void* workspa
  * overwritten everywhere; column 3 is +0 when k = 3): bsx_mlp_grad's grad_out for the actor (squash = 1). */
 int bsx_ddpg_action_grad(const float* gx, int64_t B, int nA, int Do, int k, int central, float* g_a4, void* stream);
 
+/* ---- what TD3 / MATD3 (Fujimoto et al. 2018) adds to that update (deep-rl-battlespace_amd/learner/td3.py: td3_smooth_actions, td3_head,
+ * TD3Learner; csrc/bsx_td3_head.hip): target policy smoothing and the TD head of two critics.  B, nA, Do, k, central, Dc, the layouts,
+ * the alignments and the rules above hold as they stand: every launch on `stream`, no host synchronisation, no floating-point atomics,
+ * flags or spins, grids a function of the sizes alone, the same inputs the same bits on every call, every refusal before any launch.
+ *
+ * bsx_td3_smooth_actions: the target actors' actions, smoothed, into the action columns of x [B][nA][Dc] (x_next), one launch.
+ *   y4        [B][nA][4]: the target actors' output rows (bsx_mlp_forward's y)
+ *   sigma, clip   >= 0 (a NaN or a negative value for either: BSX_E_ARG)
+ *   z_inject  [B][nA][4], 16-byte aligned, or NULL: the normals, per call (tests)
+ *   seed, seq, seq_base   without z_inject, z = bsx_actor's normals4(seed, seq + *seq_base, b nA + j, 0x20000000): four standard normals
+ *             of one Philox4x32-10 block, the salt distinct from the four in use (0x00000000, 0x80000000, 0x40000000, 0xC0000000).
+ *             seq_base: a device word, 8-byte aligned, or NULL = 0; it is read on the device, so the replays of a captured graph draw
+ *             fresh noise when the caller advances it
+ * Per (b, j) and action column c < k, in float32, every operation rounded once and none contracted, with
+ * clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v) (a NaN stays a NaN):
+ *   n  = clamp(sigma * z[c], -clip, clip)        a' = clamp(y4[b][j][c] + n, -1, 1)
+ * a' goes where bsx_ddpg_put_actions(own_only = 0) writes: central = 1: slot j of EVERY row (b, i); central = 0: the own action columns
+ * of row (b, j).  The noise is keyed by (b, j), never by the critic row: the nA rows of b hold the same bits.  Nothing else of x is
+ * written; with k = 3 the fourth normal is unused.
+ * Refusals, in this order: BSX_E_ARG for a null y4 or x; a size out of range (bsx_ddpg_put_actions' checks); a sigma or a clip that is
+ * negative or NaN.  Then BSX_E_ALIGN for y4 or z_inject off a 16-byte boundary, x off a 4-byte one, seq_base off an 8-byte one. */
+int bsx_td3_smooth_actions(const float* y4, int64_t B, int nA, int Do, int k, int central, float sigma, float clip, uint64_t seed,
+                           uint64_t seq, const uint64_t* seq_base, const float* z_inject, float* x, void* stream);
+
+/* The TD target from the smaller of two target critics and the grad_out tensors of both critics and the actor, one pass (two launches).
+ *   q1, q2, q1_next, q2_next, rew   [B][nA]: the critics on x_cur, the target critics on x_next (raw heads), the batch's rewards
+ *   done     uint8 [B][nA], 1-byte aligned (any non-zero byte counts)
+ *   weight   [B][nA] or NULL = 1 for every element
+ *   g_q1, g_q2, g_pi  [B][nA][4] (out, overwritten everywhere);   td  [B][nA] (out) or NULL */
+typedef struct BsxTd3Io {
+    const float* q1;
+    const float* q2;
+    const float* q1_next;
+    const float* q2_next;
+    const float* rew;
+    const uint8_t* done;
+    const float* weight;
+    float* g_q1;
+    float* g_q2;
+    float* g_pi;
+    float* td;
+} BsxTd3Io;
+
+/* Size of bsx_td3_head's workspace: 64 bytes per workgroup of the head pass, bsx_td_head's plan.  BSX_E_ARG: null bytes, B or nA out
+ * of range. */
+int bsx_td3_head_workspace_bytes(int64_t B, int nA, size_t* bytes);
+
+/* Per element, in float32, with w = weight or 1, s1 = float(1.0 / B) and s2 = float(2.0 / B) (formed in float64, rounded once):
+ *   m  = (q1_next < q2_next || q1_next != q1_next) ? q1_next : q2_next     (np.minimum's rule: a NaN in either is a NaN)
+ *   qn = done ? 0 : m            (selected, never multiplied: a finished row's q_next stay out, NaN and infinities included)
+ *   y  = fmaf(gamma, qn, rew),   d1 = q1 - y,   d2 = q2 - y
+ *   g_q1[0] = (w * d1) * s2      g_q2[0] = (w * d2) * s2      g_pi[0] = -(w * s1)      td = y;      columns 1 .. 3 of all three are +0
+ * y, g_q1 and g_pi are bsx_td_head's expressions: with q2 = q1 and q2_next = q1_next they are its bits.  g_q1 and g_q2 are the critics'
+ * grad_out (squash = 0) for the sum over agents of mean_b w ((Q1 - y)^2 + (Q2 - y)^2), y held fixed; g_pi seeds critic 1's input-
+ * gradient pass for the sum over agents of -mean_b w Q1: the actor reads critic 1 alone.
+ * stats[8] (device, float64): n = B nA, then the means over the n elements -- float64 sums of the float32 per-element terms, divided by
+ * n -- of (w * d1) * d1 and (w * d2) * d2 (both terms added in float64: the critic loss), q1, y, |d1|, done != 0, w and |q1 - q2|.
+ * Launches, workspace and the order of the sums: bsx_td_head's.
+ * Refusals, before any launch, in this order: BSX_E_ARG for a null io, q1, q2, q1_next, q2_next, rew, done, g_q1, g_q2, g_pi, workspace
+ * or stats; a gamma outside [0, 1] (NaN too); B or nA out of range.  Then BSX_E_ALIGN for g_q1, g_q2 or g_pi off a 16-byte boundary; q1,
+ * q2, q1_next, q2_next, rew, weight or td off a 4-byte one; workspace or stats off an 8-byte one. */
+int bsx_td3_head(const BsxTd3Io* io, int64_t B, int nA, float gamma, void* workspace, double* stats, void* stream);
+
 /* ---- shuffled minibatches (deep-rl-battlespace_amd/learner.py: shuffle_rows, minibatch_gather, PPOLearner(shuffle=True);
  * csrc/bsx_shuffle.hip): a keyed permutation of the N = T x E rows of a rollout, evaluated per position -- O(1), no sort, no workspace,
  * no atomics --, and the gather of one minibatch's rows through it.

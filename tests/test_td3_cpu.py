@@ -1,0 +1,222 @@
+"""The TD3 entry points without a GPU: header, library and binding agree and the ABI version stays; the head's workspace follows
+bsx_td_head's formula; every refusal the header documents comes before any launch (fake addresses); TD3Learner's constructor refuses
+on the host; the numpy restatements of tests/td3_util.py are what torch float64 autograd and torch.clamp give; the whole-update case
+stays under the kink cap at its fixed point, every misreading of the update lies far from its float64 reference, and
+profiles/td3_float64.json records what the case gives."""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import ddpg_util as D
+import td3_util as T
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("bsx_td3_smooth_actions", "bsx_td3_head_workspace_bytes", "bsx_td3_head")
+ARG, ALIGN = -1, -2
+A16, A8, A4, A1 = 4096, 4096 + 8, 4096 + 4, 4096 + 1
+NAN = float("nan")
+
+
+def _L():
+    from deep_rl_battlespace_amd import _lib
+    return _lib
+
+
+def test_header_library_and_binding_agree_on_the_new_entries_and_the_abi_stays():
+    L = _L()
+    hdr = open(os.path.join(ROOT, "include", "battlespace_hip.h")).read()
+    lib = L.load()
+    for name in ENTRIES:
+        m = re.search(r"^int\s+%s\s*\(([^;]*)\);" % name, hdr, flags=re.M)
+        assert m and name in L.SIGNATURES and hasattr(lib, name), name
+        assert len(L.SIGNATURES[name][1]) == m.group(1).count(",") + 1, name
+    assert L.ABI_VERSION == 14 == lib.bsx_abi_version() and "#define BSX_ABI_VERSION 14" in hdr
+    fields = ("q1", "q2", "q1_next", "q2_next", "rew", "done", "weight", "g_q1", "g_q2", "g_pi", "td")
+    body = re.search(r"typedef struct BsxTd3Io \{(.*?)\} BsxTd3Io;", hdr, flags=re.S).group(1)
+    assert tuple(re.findall(r"(\w+);", body)) == fields == tuple(f for f, _ in L.BsxTd3Io._fields_)
+    import deep_rl_battlespace_amd as pkg
+    for name in ("TD3Learner", "td3_smooth_actions", "td3_head", "td3_head_workspace_bytes", "TD3_STATS"):
+        assert name in pkg.__all__ and getattr(pkg, name) is getattr(pkg.learner, name)
+    assert pkg.TD3_STATS == ("n", "critic_loss", "q", "target", "abs_td", "done", "weight", "q_gap")
+    assert pkg.TD3_STATS[:7] == pkg.TD_STATS[:7] and issubclass(pkg.TD3Learner, pkg.DDPGLearner)
+    assert "TD3Learner" in pkg.DDPGLearner.__doc__ and "are not here" not in pkg.DDPGLearner.__doc__.split("TD3Learner")[0][-120:]
+    assert hex(T.SALT) in hdr.lower() and T.SALT not in T.OTHER_SALTS and len(set(T.OTHER_SALTS)) == 4
+
+
+def test_the_workspace_is_64_bytes_per_workgroup_of_td_heads_plan():
+    lib, nb, nb0 = _L().load(), ctypes.c_size_t(), ctypes.c_size_t()
+    for B, nA in T.HEAD_SHAPES + ((512, 2), (65536, 2), (16384, 16), ((1 << 31) - 1, 16)):
+        assert lib.bsx_td3_head_workspace_bytes(B, nA, ctypes.byref(nb)) == 0 == lib.bsx_td_head_workspace_bytes(B, nA, ctypes.byref(nb0))
+        assert nb.value == 64 * D.plan(B, nA)[2] == nb0.value, (B, nA)
+    B, nA = T.HEAD_SHAPES[-1]
+    assert D.plan(B, nA)[1] == 2 and D.plan(B, nA)[3] > 1 and all(D.plan(*s)[1] == 1 for s in T.HEAD_SHAPES[:-1])
+    for B_, nA_ in ((0, 2), (1 << 31, 2), (10, 0), (10, 17)):
+        assert lib.bsx_td3_head_workspace_bytes(B_, nA_, ctypes.byref(nb)) == ARG
+    assert lib.bsx_td3_head_workspace_bytes(10, 2, None) == ARG
+
+
+def test_every_entry_refuses_what_the_header_documents_before_any_launch():
+    """Fake addresses only: every call is refused before anything reaches HIP."""
+    L = _L()
+    lib = L.load()
+
+    def smooth(B=100, nA=2, Do=8, k=4, central=1, sigma=0.2, clip=0.5, y4=A16, x=A4, seq_base=None, z=None):
+        return lib.bsx_td3_smooth_actions(y4, B, nA, Do, k, central, sigma, clip, 1, 2, seq_base, z, x, None)
+
+    for kw in [dict(B=0), dict(B=1 << 31), dict(nA=0), dict(nA=17), dict(Do=0), dict(Do=51), dict(k=2), dict(k=5), dict(central=2),
+               dict(central=-1), dict(nA=4, Do=14, k=4, central=1), dict(nA=2, Do=30, k=4, central=1),       # Dc = 72 and 68 > 64
+               dict(y4=None), dict(x=None), dict(sigma=-0.1), dict(sigma=NAN), dict(clip=-0.1), dict(clip=NAN), dict(sigma=-float("inf"))]:
+        assert smooth(**kw) == ARG, kw
+    for kw in (dict(y4=A4), dict(y4=A8), dict(z=A4), dict(z=A8), dict(x=A1), dict(seq_base=A4), dict(seq_base=A1)):
+        assert smooth(**kw) == ALIGN, kw
+    for kw in (dict(y4=A4, k=5), dict(x=A1, sigma=NAN), dict(z=A4, clip=-1.0), dict(seq_base=A4, nA=17)):   # argument rules before alignment rules
+        assert smooth(**kw) == ARG, kw
+    assert smooth(z=A4, sigma=0.0, clip=0.0) == ALIGN                                    # the ends of the ranges are in
+
+    fields = [f for f, _ in L.BsxTd3Io._fields_]
+
+    def head(B=100, nA=2, gamma=0.95, ws=A16, stats=A16, io=True, **ptr):
+        st = L.BsxTd3Io(**{f: ptr.get(f, None if f in ("weight", "td") else A16) for f in fields})
+        return lib.bsx_td3_head(ctypes.byref(st) if io else None, B, nA, gamma, ws, stats, None)
+
+    for kw in [dict(io=False), dict(ws=None), dict(stats=None)] + [{f: None} for f in fields if f not in ("weight", "td")] + \
+            [dict(gamma=-0.01), dict(gamma=1.01), dict(gamma=NAN), dict(gamma=float("inf")), dict(B=0), dict(B=1 << 31), dict(nA=0), dict(nA=17)]:
+        assert head(**kw) == ARG, kw
+    for kw in [{f: A4} for f in ("g_q1", "g_q2", "g_pi")] + [{f: A1} for f in ("q1", "q2", "q1_next", "q2_next", "rew", "weight", "td")] + \
+            [dict(ws=A4), dict(stats=A4)]:
+        assert head(**kw) == ALIGN, kw
+    for kw in (dict(g_q2=A4, gamma=2.0), dict(ws=A4, B=0), dict(q2=A1, rew=None)):
+        assert head(**kw) == ARG, kw
+    assert head(g_q2=A4, done=A1, gamma=0.0) == ALIGN and head(g_pi=A4, gamma=1.0) == ALIGN  # done at any byte; the ends of [0, 1] are in
+
+
+def test_the_bindings_and_the_learners_constructor_refuse_on_the_host():
+    from deep_rl_battlespace_amd import learner as L
+    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer
+    from deep_rl_battlespace_amd.rollout import StackedActor
+    z = torch.zeros((4, 2))
+    with pytest.raises(ValueError, match="GPU"):
+        L.td3_head(z, z, z, z, z, torch.zeros((4, 2), dtype=torch.uint8), 0.9)
+    with pytest.raises(ValueError, match="GPU"):
+        L.td3_smooth_actions(torch.zeros((4, 2, 4)), torch.zeros((4, 2, 24)), 8, 4, sigma=0.2, clip=0.5, seed=0)
+    with pytest.raises(ValueError, match="DeviceReplayBuffer"):
+        L.TD3Learner(object(), None)
+    critic = StackedActor(2, 24, 1)
+    for kw, match in ((dict(critic=critic, critic2=critic), "critic2 is critic itself"), (dict(updates=3, policy_delay=2), "multiple of policy_delay"),
+                      (dict(updates=1), "multiple of policy_delay"), (dict(policy_delay=0), "policy_delay must be"),
+                      (dict(policy_delay=-2), "policy_delay must be"), (dict(target_noise=-0.1), "target_noise"), (dict(target_noise=NAN), "target_noise"),
+                      (dict(noise_clip=-0.5), "noise_clip"), (dict(noise_clip=NAN), "noise_clip")):
+        with pytest.raises(ValueError, match=match):                 # each fires before the buffer is looked at
+            L.TD3Learner(object(), None, **kw)
+    buf = DeviceReplayBuffer(64, 16, list(range(2)), 8, 16, 4, device="cpu")
+    with pytest.raises(ValueError):                                  # DDPGLearner's own checks follow: a CPU ring has nothing to run on
+        L.TD3Learner(buf, StackedActor(2, 8, 4))
+
+
+@pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
+@pytest.mark.parametrize("BnA", sorted({s[:2] for s in D.SHAPES}), ids=lambda s: "B%d-nA%d" % s)
+def test_the_head_restatement_is_float64_autograd_of_the_two_critic_losses_and_of_minus_mean_w_q1(BnA, weight):
+    inp = T.td3_inputs(*BnA)
+    ref, t64 = T.ref_td3_head(inp, weight=weight), T.torch_td3(inp, torch.float64, weight=weight)
+    for k in T.TD_NAMES:
+        err = float(np.abs(ref[k] - t64[k]).max() / np.abs(t64[k]).max())
+        assert err <= 1e-12, (k, err)
+    assert ref["stats"][0] == t64["stats"][0] == inp["q1"].numel()
+    for i in range(1, 8):
+        assert abs(ref["stats"][i] - t64["stats"][i]) <= 1e-12 * max(abs(t64["stats"][i]), 1e-300), i
+    assert all(not ref[k][..., 1:].any() for k in ("g_q1", "g_q2", "g_pi"))
+    # with the second critic a copy of the first the head is ddpg_util's, and q_gap is 0
+    same = dict(inp, q2=inp["q1"], q2_next=inp["q1_next"])
+    one = D.ref_td_head(dict(q=inp["q1"], q_next=inp["q1_next"], rew=inp["rew"], done=inp["done"], weight=inp["weight"]), weight=weight)
+    two = T.ref_td3_head(same, weight=weight)
+    assert all(np.array_equal(two[a], one[b]) for a, b in (("g_q1", "g_q"), ("g_q2", "g_q"), ("g_pi", "g_pi"), ("td", "td")))
+    assert two["stats"][7] == 0.0 and np.allclose(two["stats"][1], 2 * one["stats"][1], rtol=1e-12) and np.array_equal(two["stats"][2:7], one["stats"][2:7])
+    # a finished row keeps both q_next out, NaN included; on a running row a NaN in either alone reaches td
+    over = inp["done"].numpy() != 0
+    nan = torch.tensor(NAN)
+    bad = dict(inp, q1_next=torch.where(inp["done"] != 0, nan, inp["q1_next"]), q2_next=torch.where(inp["done"] != 0, nan, inp["q2_next"]))
+    assert all(np.array_equal(T.ref_td3_head(bad, weight=weight)[k], ref[k]) for k in T.TD_NAMES + ("stats",))
+    for which in ("q1_next", "q2_next"):
+        td = T.ref_td3_head(dict(inp, **{which: torch.full_like(inp[which], NAN)}), weight=weight)["td"]
+        assert np.isnan(td[~over]).all() and np.array_equal(td[over], ref["td"][over])
+
+
+@pytest.mark.parametrize("shape", D.SHAPES[:-1], ids=D.shape_id)
+def test_the_smoothing_restatement_is_torch_clamp_joined_as_ddpg_util_joins(shape):
+    B, nA, Do, k, central = shape
+    _, obs_next, act = D.batch_arrays(shape)
+    g = np.random.default_rng(21)
+    y4 = np.tanh(2.0 * g.standard_normal((B, nA, 4))).astype(np.float32)
+    z = g.standard_normal((B, nA, 4)).astype(np.float32)
+    for sigma, clip in ((0.2, 0.5), (1.0, 0.5), (0.0, 0.5), (0.7, 100.0)):
+        x = T.ref_smooth(y4, z, D.join(obs_next, act, central), Do, k, central, sigma, clip)
+        t = lambda a: torch.from_numpy(a)                          # noqa: E731
+        a = torch.clamp(t(y4) + torch.clamp(np.float32(sigma) * t(z), -clip, clip), -1.0, 1.0)
+        want = D.joined(t(obs_next), a[..., :k], bool(central))
+        assert x.dtype == np.float32 and np.array_equal(x, want.numpy()), (sigma, clip)
+    hit = T.smoothed(y4, z, 1.0, 0.5) - y4
+    assert (np.abs(T.smoothed(y4, z, 1.0, 0.5)) <= 1.0).all() and (B * nA < 50 or (np.abs(T.clamp(z, -0.5, 0.5)) == 0.5).mean() > 0.3) and hit.any()
+    # a NaN stays a NaN through both clamps, and the float64 form is the same expression
+    bad = z.copy()
+    bad[0, 0, 0] = np.nan
+    assert np.isnan(T.smoothed(y4, bad, 0.2, 0.5)[0, 0, 0]) and not np.isnan(T.smoothed(y4, bad, 0.2, 0.5)[0, 0, 1:]).any()
+    assert np.abs(T.smoothed(y4.astype(np.float64), z.astype(np.float64), 0.2, 0.5) - T.smoothed(y4, z, 0.2, 0.5)).max() < 1e-6
+
+
+@pytest.mark.parametrize("shape", T.MAIN_SHAPES, ids=D.shape_id)
+def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_misreading_lies_far(shape):
+    """td3_util.stepped_case's row weights are 0 where, in float64, a pre-ReLU value lies within KINK of 0: of either critic at x_cur, of
+    the actor at obs, of the STEPPED critic 1 at x_pi (iterated: zeroing a row moves the step).  Under the cap, closed within
+    MAX_ROUNDS (conditions on the float64 reference: td3_util.STEP_SEEDS), and each misreading -- y from target critic 1 alone, the
+    noise left out, the actor's gradient through critic 2 -- lies at least 1000 yardstick mean errors from the reference in each of
+    w1, w2, w3, b3 (measured: 1.8e5 and more).  profiles/td3_float64.json records all of it."""
+    B, nA, Do, k, central = shape
+    c = T.stepped_case(shape)
+    print(D.shape_id(shape), f"seed {c.seed}: left out {100 * c.share:.2f} % after {c.rounds} zeroing rounds")
+    assert c.share < D.U.KINK_CAP and c.rounds <= D.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
+    obs, act, _, obs_next, _ = c.batch
+    x_cur, _, x_pi = D.joins64(c.nets[0], obs, obs_next, act, central)
+    stepped = c.ref["critic"]["net"]
+    assert stepped.w1.dtype == torch.float64 and not torch.equal(stepped.w1, c.nets[1].w1.double())
+    near = D.U.near_kink((stepped, x_pi), (c.nets[1], x_cur), (c.nets[2], x_cur), (c.nets[0], obs))
+    assert not (near & (c.w != 0)).any()
+    # ONE norm over both critics: the joint step's coefficient is one number, and both steps are clipped
+    assert c.ref["critic"]["coef"] == c.ref["critic2"]["coef"] < 1.0 and c.ref["critic"]["norm"] == c.ref["critic2"]["norm"]
+    n1 = np.sqrt(sum(float((g ** 2).sum()) for which in ("gc1", "gc2") for g in c.ref[which].values()))
+    assert abs(n1 - c.ref["critic"]["norm"]) <= 1e-6 * n1 and c.ref["actor"]["coef"] < 1.0                  # (hyper32 rounds max_grad_norm)
+    assert not bool(c.batch[4].all()) and not torch.equal(c.targets[1].w1, c.nets[1].w1) and not torch.equal(c.nets[1].w1, c.nets[2].w1)
+    for name, (dist, yard) in T.wrong_variants(c, central).items():
+        ratios = {p: dist[p] / yard[p] for p in D.SHARP}
+        print(D.shape_id(shape), name, "smallest ratio %.3g" % min(ratios.values()))
+        assert all(yard[p] > 0.0 for p in D.SHARP) and min(ratios.values()) >= 1000.0, (name, ratios)
+    rec = json.load(open(T.PROFILE))["stepped"]
+    r = rec["cases"][D.shape_id(shape)]
+    assert r["seed"] == c.seed == T.STEP_SEEDS.get(shape, 0) and r["zeroing_rounds"] == c.rounds
+    assert abs(r["left_out_percent"] - 100 * c.share) <= 0.005 + 1e-9 and min(rec["sharpness"][D.shape_id(shape)].values()) >= 1000
+
+
+def test_the_profile_s_factors_are_the_rule_on_its_recorded_spread_and_the_bandit_s_n_is_the_compositions():
+    """profiles/td3_float64.json: the head's factor exceptions are yardstick_util.factor_rule of the recorded spread of the yardstick
+    itself and nothing else, the spread is what td3_util.head_spread gives (re-run here at the shapes that cost nothing), and only the
+    one-element shape has an exception; every recorded kernel ratio of the whole update lies within the bars."""
+    rec = json.load(open(T.PROFILE))
+    assert rec["factors"] == T.Y.exceptions_from(rec["head_spread"]) and set(rec["factors"]) <= {T.head_id(1, 1, True), T.head_id(1, 1, False)}
+    assert set(rec["head_spread"]) == {T.head_id(B, nA, w) for B, nA in T.HEAD_SHAPES for w in (True, False)}
+    for B, nA in T.HEAD_SHAPES[:-1]:
+        for w in (True, False):
+            got = {k: [round(float(x), 4) for x in v] for k, v in T.head_spread(B, nA, w).items()}
+            assert got == rec["head_spread"][T.head_id(B, nA, w)], (B, nA, w)
+    assert T.factors(161, 2, True)("g_q2") == T.Y.FACTORS and T.factors(1, 1, True)("g_q1") == T.Y.FACTORS
+    st = rec["stepped"]
+    assert set(st["cases"]) == set(st["sharpness"]) == {D.shape_id(s) for s in T.MAIN_SHAPES}
+    for shape in T.MAIN_SHAPES:
+        for name, (mean, mx) in st["kernel"].get(D.shape_id(shape), {}).items():
+            assert mean <= T.Y.FACTORS[0] and mx <= T.Y.FACTORS[1], (shape, name)
+    b = rec["bandit"]
+    assert b["N"] % 10 == 0 and b["policy_delay"] == 2 and b["torch_closed"] >= 0.5
+    assert {k: b[k] for k in D.BANDIT} == D.BANDIT
