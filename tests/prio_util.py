@@ -8,13 +8,22 @@ exact, and the GPU tests compare bit for bit:
   append_range, update_max           the leaves after an append of `stored` rows and after an update, in integers
   priority_ref / priority_yard       p from TD errors: float64 (unrounded, clamped) and the float32 torch evaluation, rounded as the kernel rounds
   weights_ref / weights_yard         (p_min / p) ^ beta in float64 and in float32 torch
+  random_leaves, needle_leaves, heavy_leaves, edge_rows   leaf patterns: log-uniform with zeros, a few non-zero rows at the node boundaries
+                                     of every level, and all near 2^31 with an odd total (past 2^53 at five levels)
+  stamp_ring, stamps                 the row index written into the ring's rows, and read back from a gathered batch
 Nothing here imports the native library."""
+import functools
+
 import numpy as np
 import torch
 
 import philox_util as P
 
 FAN, ONE, P_MAX, SALT = 64, 65536, 1 << 31, 0x3C6EF372
+# The sizes at which the tree is checked at depth: 64^2 and 64^3 exact (two and three levels, all of them the tail workgroup's), 64^3 + 1
+# (four levels, every level ragged: its last node has one child) and 64^4 + 67 (five levels; rows 2^24 + 1 and 2^24 + 3 exist)
+M4, M5 = 64 ** 3 + 1, 64 ** 4 + 67
+DEEP_SIZES = (64 ** 2, 64 ** 3, M4, M5)
 
 
 def levels(M):
@@ -150,6 +159,60 @@ def random_leaves(M, seed=0):
         zero[np.isin(p, (1, P_MAX))] = False
         p[zero] = 0
     return p
+
+
+def needle_leaves(M, rows, p=ONE):
+    """All M leaves 0 but the named rows, which hold p: a draw can only land on them, wherever in the tree they sit."""
+    out = np.zeros(int(M), np.int64)
+    out[np.asarray(rows, np.int64)] = int(p)
+    return out
+
+
+def edge_rows(M):
+    """The rows on either side of every node boundary of every level (64^k - 1 and 64^k), the first row and the last two, and where
+    M reaches them 2^24 + 1 and 2^24 + 3 (odd integers no float32 holds) -> the sorted int64 rows below M."""
+    rows = {0, M - 2, M - 1, (1 << 24) + 1, (1 << 24) + 3}
+    edge = FAN
+    while edge <= M:
+        rows |= {edge - 1, edge}
+        edge *= FAN
+    return np.array(sorted(r for r in rows if 0 <= r < M), np.int64)
+
+
+def heavy_leaves(M):
+    """Every leaf 2^31 or 2^31 - 1, an odd number of them the latter: an odd total, so its lowest bit is set and a total carried through a
+    double anywhere past 2^53 (reached from M = 2^22 + 1 on) would come out wrong."""
+    g = np.random.default_rng(9000 + M)
+    less = g.random(int(M)) < 0.5
+    less[0] ^= less.sum() % 2 == 0
+    p = P_MAX - less.astype(np.int64)
+    total = int(p.sum())
+    assert total % 2 == 1 and (M < (1 << 24) or total > 1 << 53)
+    return p
+
+
+PATTERNS = ("random", "needles", "heavy")
+
+
+@functools.lru_cache(maxsize=None)
+def pattern_leaves(M, pattern):
+    """random_leaves(M), equal needles on edge_rows(M) or heavy_leaves(M), built once per process and read-only (five levels: seconds)."""
+    p = {"random": random_leaves, "needles": lambda m: needle_leaves(m, edge_rows(m)), "heavy": heavy_leaves}[pattern](M)
+    p.flags.writeable = False
+    return p
+
+
+def stamp_ring(buf):
+    """The row index, as an int32 bit pattern, into word 0 of every row of the ring's three wide fields: a gathered batch then carries
+    the rows it was read from in its own bits, whatever last_idx says.  Stands in for a fill where a test is about the draw."""
+    stamp = torch.arange(buf.mem_size, dtype=torch.int32, device=buf.actor_states.device)
+    for field in (buf.actor_states, buf.actor_new_states, buf.action_mem):
+        field.view(torch.int32).view(buf.mem_size, -1)[:, 0] = stamp
+
+
+def stamps(batch_field):
+    """Word 0 of every row of a gathered [B, nA, W] field, as the int64 row indices stamp_ring wrote."""
+    return batch_field.view(torch.int32).view(batch_field.shape[0], -1)[:, 0].cpu().numpy().astype(np.int64)
 
 
 def as_leaves(p, device="cuda"):

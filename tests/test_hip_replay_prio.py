@@ -2,7 +2,9 @@
 the tree's every level and the rows drawn are the numpy reference's, exactly; the gathered fields are the ring's rows; the weights and
 the priorities written from TD errors hold the float64 yardstick's bars; an update leaves the integer maximum per row and an append
 max_priority on the rows just written, with every level again the exact sum of the leaves; nothing is written outside the buffers; and
-a DDPGLearner on such a ring is, bit for bit, the by-hand sequence of the public calls, captured or not."""
+a DDPGLearner on such a ring is, bit for bit, the by-hand sequence of the public calls, captured or not.  The trees here have three
+levels at the most (M = 5, 64, 65, 4097); four and five levels, where a level's repair sums nodes instead of leaves, are
+tests/test_hip_replay_prio_deep.py's.  The helpers both files use are in tests/prio_ring_util.py."""
 import gc
 
 import numpy as np
@@ -13,45 +15,20 @@ import ddpg_util as D
 import guard_util as G
 import prio_util as PU
 import yardstick_util as Y
+from prio_ring_util import OBS, RING_FIELDS
+from prio_ring_util import assert_same_ring as _assert_same_ring, assert_tree_exact as _assert_tree_exact, bits as _bits, buf as _buf
+from prio_ring_util import leaves as _leaves, plain as _plain, rows as _rows, set_leaves as _set_leaves, td_pairs as _td_pairs
 
 pytestmark = pytest.mark.gpu
 
-RING_FIELDS = ("actor_states", "actor_new_states", "action_mem", "rew_mem", "done_mem")
-OBS = 8
 SIZES = (5, 64, 65, 4097)           # a single ragged node, an exact node, a one-leaf tail, three levels ragged at two of them
 TEAMS = ((1, 3), (3, 4))            # (nA, k)
 BATCHES = (1, 33, 512)
 
 
-def _buf(M, B, nA=1, k=4, seed=0, D_=OBS, **kw):
-    from deep_rl_battlespace_amd.replay import PrioritizedReplayBuffer
-    return PrioritizedReplayBuffer(M, B, list(range(nA)), D_, D_ * nA, k, device="cuda", seed=seed, **kw)
-
-
-def _plain(M, B, nA=1, k=4, seed=0, D_=OBS):
-    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer
-    return DeviceReplayBuffer(M, B, list(range(nA)), D_, D_ * nA, k, device="cuda", seed=seed)
-
-
 def _fill_ring(buf, seed=0):
     """mem_size random rows through _put: a full ring (the tests then write the priorities they want)."""
     buf._put(*_rows(buf.mem_size, buf.n_agents, buf.n_actions, seed))
-
-
-def _set_leaves(buf, p):
-    buf.priorities.copy_(PU.as_leaves(p))
-    buf.rebuild_tree()
-
-
-def _leaves(buf):
-    return PU.unsigned(buf.priorities)
-
-
-def _assert_tree_exact(buf, what=""):
-    """Every level is the exact sum of the leaves read back; the pad leaves are 0."""
-    torch.cuda.synchronize()
-    assert np.array_equal(buf.tree.cpu().numpy(), PU.node_buffer(_leaves(buf))), what
-    assert not buf._leaves[buf.mem_size:].any(), what
 
 
 def _rows_of_batch(buf, idx):
@@ -61,10 +38,6 @@ def _rows_of_batch(buf, idx):
 
 def _batch(buf):
     return [buf._b_obs, buf._b_obs_, buf._b_act, buf._b_rew, buf._b_done]
-
-
-def _bits(t):
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
 
 
 # ------------------------------------------------------------------------------------------------ draw and weights
@@ -147,15 +120,6 @@ def test_set_beta_reaches_a_captured_sample():
 
 
 # ------------------------------------------------------------------------------------------------ update
-def _td_pairs(B, nA, seed):
-    """q, y float32 [B, nA]: errors from 1e-4 to 1e3 (some above delta_max = 32), a NaN in about one row in eight."""
-    g = np.random.default_rng(seed)
-    y = g.standard_normal((B, nA)).astype(np.float32)
-    q = (y + g.choice([-1.0, 1.0], (B, nA)) * 10.0 ** g.uniform(-4.0, 3.0, (B, nA))).astype(np.float32)
-    q[g.random((B, nA)) < 0.125 / nA] = np.nan
-    return q, y
-
-
 @pytest.mark.parametrize("M,B,nA", [(5, 64, 3), (64, 33, 1), (65, 512, 3), (4097, 33, 1), (4097, 512, 3), (5, 1, 1)])
 def test_update_writes_the_integer_maximum_per_row_and_repairs_every_level(M, B, nA):
     buf, one = _buf(M, B, nA, 4), _buf(M, 1, nA, 4)
@@ -208,18 +172,6 @@ def test_update_writes_the_integer_maximum_per_row_and_repairs_every_level(M, B,
 
 
 # ------------------------------------------------------------------------------------------------ append
-def _rows(R, nA, k, seed):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    rnd = lambda *s: torch.randn(s, generator=g, device="cuda")                         # noqa: E731
-    return rnd(R, nA, OBS), rnd(R, nA, k), rnd(R, nA), rnd(R, nA, OBS), torch.rand((R, nA), generator=g, device="cuda") < 0.3
-
-
-def _assert_same_ring(buf, twin, what):
-    for f in RING_FIELDS:
-        assert torch.equal(_bits(getattr(buf, f)), _bits(getattr(twin, f))), (what, f)
-    assert buf.mem_cntr == twin.mem_cntr, what
-
-
 @pytest.mark.parametrize("M,nA,k", [(5, 1, 3), (64, 3, 4), (65, 1, 3), (4097, 3, 4)])
 def test_store_transition_rows_get_max_priority_across_the_wrap_and_past_the_ring(M, nA, k):
     """Dense rows through _put (what store_transition builds): a first fill that stops just before the wrap, a store across it, one of

@@ -1,7 +1,8 @@
 """CPU-side checks of the prioritised replay ring (csrc/bsx_replay_prio.hip): its entry points are declared, exported and bound, the
 node buffer's size against replay.prio_levels, argument validation before any launch (fake addresses only: a call that got through
-would return a HIP error on a machine without a GPU), the Python surface, and the numpy reference of tests/prio_util.py itself.  No
-kernel is launched here."""
+would return a HIP error on a machine without a GPU), the Python surface, and the numpy reference of tests/prio_util.py itself: at
+M = 4097 (three levels) and, before the GPU is held to it there, at 64^3 + 1 and 64^4 + 67 (four and five levels; the level counts
+of the four sizes of tests/test_hip_replay_prio_deep.py are written out in DEEP_LEVELS).  No kernel is launched here."""
 import ctypes
 import inspect
 import os
@@ -17,7 +18,9 @@ NAMES = ("bsx_replay_prio_bytes", "bsx_replay_prio_rebuild", "bsx_replay_prio_sa
          "bsx_replay_prio_append")
 ARG, ALIGN = -1, -2
 A = 4096                      # a 256-byte aligned fake address (never dereferenced)
-SIZES = (1, 63, 64, 65, 4096, 4097, (1 << 31) - 1)
+SIZES = (1, 63, 64, 65, 4096, 4097, 262_144, 262_145, 16_777_283, (1 << 31) - 1)
+# the level counts, bottom-up, of the sizes the GPU suite checks at depth (tests/test_hip_replay_prio_deep.py), written out
+DEEP_LEVELS = {4096: (64, 1), 262_144: (4096, 64, 1), 262_145: (4097, 65, 2, 1), 16_777_283: (262_146, 4097, 65, 2, 1)}
 
 
 def _lib():
@@ -49,6 +52,18 @@ def test_node_buffer_bytes_match_prio_levels(M):
         assert o1 == o0 + c0 and c1 == -(-c0 // 64)
     sz = ctypes.c_size_t()
     assert _lib().load().bsx_replay_prio_bytes(M, ctypes.byref(sz)) == 0 and sz.value == 8 * sum(c for _, c in lv)
+
+
+@pytest.mark.parametrize("M", sorted(DEEP_LEVELS))
+def test_levels_and_node_buffer_bytes_at_four_and_five_levels_are_the_literal_counts(M):
+    from deep_rl_battlespace_amd.replay import prio_levels
+    counts = DEEP_LEVELS[M]
+    offsets = tuple(sum(counts[:k]) for k in range(len(counts)))
+    assert tuple(PU.DEEP_SIZES) == tuple(sorted(DEEP_LEVELS)) and (PU.M4, PU.M5) == (262_145, 16_777_283)
+    assert PU.levels(M) == prio_levels(M) == list(zip(offsets, counts))
+    sz = ctypes.c_size_t()
+    assert _lib().load().bsx_replay_prio_bytes(M, ctypes.byref(sz)) == 0 and sz.value == 8 * sum(counts)
+    assert {262_145: 8 * 4165, 16_777_283: 8 * 266_311}.get(M, sz.value) == sz.value
 
 
 def test_node_buffer_bytes_refusals():
@@ -217,6 +232,43 @@ def test_reference_descent_is_searchsorted():
     edge = np.array([0, int(leaves.sum()) - 1], np.int64)                      # the first and the last unit of mass
     assert np.array_equal(PU.descend(leaves, edge), PU.rows_of(leaves, edge))
     assert PU.rows_of(leaves, edge)[0] == np.flatnonzero(leaves)[0] and PU.rows_of(leaves, edge)[1] == np.flatnonzero(leaves)[-1]
+
+
+def test_reference_leaf_patterns_and_edge_rows():
+    assert PU.edge_rows(4096).tolist() == [0, 63, 64, 4094, 4095]
+    assert PU.edge_rows(262_144).tolist() == [0, 63, 64, 4095, 4096, 262_142, 262_143]
+    assert PU.edge_rows(PU.M4).tolist() == [0, 63, 64, 4095, 4096, 262_143, 262_144]
+    top = 1 << 24
+    assert PU.edge_rows(PU.M5).tolist() == [0, 63, 64, 4095, 4096, 262_143, 262_144, top - 1, top, top + 1, top + 3, PU.M5 - 2, PU.M5 - 1]
+    assert int(np.float32(top + 1)) == top and int(np.float32(top + 3)) == top + 4                 # neither survives a float32
+    p = PU.needle_leaves(70, [0, 69], 5)
+    assert p.dtype == np.int64 and p.sum() == 10 and p[0] == p[69] == 5
+    for M in (5, 64, PU.M4):
+        h = PU.heavy_leaves(M)
+        assert h.dtype == np.int64 and set(np.unique(h)) <= {PU.P_MAX - 1, PU.P_MAX} and int(h.sum()) % 2 == 1
+    assert PU.pattern_leaves(PU.M4, "needles") is PU.pattern_leaves(PU.M4, "needles") and not PU.pattern_leaves(PU.M4, "needles").flags.writeable
+
+
+@pytest.mark.parametrize("pattern", PU.PATTERNS)
+@pytest.mark.parametrize("M", [PU.M4, PU.M5])
+def test_reference_descent_is_searchsorted_at_four_and_five_levels(M, pattern):
+    """10 000 draws per leaf pattern: the descent through four and five levels names the rows of cumsum + searchsorted, the needles on
+    the node boundaries are all found (the odd rows above 2^24 among them) and a total past 2^53 keeps its lowest bit."""
+    leaves = PU.pattern_leaves(M, pattern)
+    lv, total = PU.tree_levels(leaves), int(leaves.sum())
+    assert tuple(len(x) for x in lv) == DEEP_LEVELS[M] and int(lv[-1][0]) == total and len(PU.node_buffer(leaves)) == sum(DEEP_LEVELS[M])
+    u = PU.draw_u(2, 0, 10_000, total)
+    rows = PU.rows_of(leaves, u)
+    assert np.array_equal(PU.descend(leaves, u), rows) and (leaves[rows] > 0).all()
+    edge = np.array([0, total - 1], np.int64)
+    assert np.array_equal(PU.descend(leaves, edge), PU.rows_of(leaves, edge))
+    assert PU.rows_of(leaves, edge).tolist() == [np.flatnonzero(leaves)[0], np.flatnonzero(leaves)[-1]]
+    if pattern == "needles":
+        assert set(rows) == set(PU.edge_rows(M))
+    if pattern == "heavy":
+        assert total % 2 == 1 and (M != PU.M5 or (total > 1 << 53 and int(float(total)) != total))
+    if pattern == "random":
+        assert len(np.unique(rows >> 12)) >= 64 and len(np.unique(rows)) > 5000            # draws from all over the ring
 
 
 def test_reference_append_update_priorities_and_weights():
