@@ -24,6 +24,8 @@ Only what the hot path needs lives here:
                  its replay ring as one graph (csrc/bsx_ddpg_head.hip)
     td3.py       what TD3 adds to it: target policy smoothing, the TD head of two critics, and TD3Learner with its delayed actor and
                  target step (csrc/bsx_td3_head.hip)
+    sac.py       soft actor-critic on the same ring: the Gaussian policy's reparameterised draw, the soft twin head, the gradients
+                 of log_std and of the temperature, and SACLearner (csrc/bsx_sac_head.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
@@ -33,9 +35,13 @@ from .learner import (TD_STATS, AdamState, DDPGLearner, Minibatch, PPOLearner, a
                       td_head_workspace_bytes, categorical_log_prob, fused_apply, fused_mlp, is_tied, minibatch_gather, mlp_adam_step,  # noqa: F401
                       mlp_adam_step_workspace_bytes, mlp_grad, ppo_head, share_group, shuffle_rows, tie_)
 from .learner import TD3_STATS, TD3Learner, td3_head, td3_head_workspace_bytes, td3_smooth_actions  # noqa: F401
+from .learner import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
+                      sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
 from .envs.battle_env import parallel_env  # noqa: F401
 from .replay import PrioritizedReplayBuffer  # noqa: F401
 
 __all__ = ["AdamState", "DDPGLearner", "Minibatch", "PPOLearner", "PrioritizedReplayBuffer", "adam_step", "advantage", "categorical_log_prob", "ddpg_action_grad", "ddpg_inputs", "ddpg_put_actions", "envs", "fused_apply", "fused_mlp", "gae", "instinct", "is_tied", "learner",
            "minibatch_gather", "mlp_adam_step", "mlp_adam_step_workspace_bytes", "mlp_grad", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "TD_STATS",
-           "td_head", "td_head_workspace_bytes", "tie_", "TD3Learner", "TD3_STATS", "td3_head", "td3_head_workspace_bytes", "td3_smooth_actions"]
+           "td_head", "td_head_workspace_bytes", "tie_", "TD3Learner", "TD3_STATS", "td3_head", "td3_head_workspace_bytes", "td3_smooth_actions",
+           "SACLearner", "SAC_PI_STATS", "SAC_STATS", "SacHead", "SacPolicyGrad", "sac_head", "sac_head_workspace_bytes", "sac_policy_grad",
+           "sac_policy_grad_workspace_bytes", "sac_policy_seed", "sac_sample_actions"]

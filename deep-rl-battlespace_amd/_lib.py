@@ -21,6 +21,7 @@ F_ONE_WAVE = 8
 ACT_I32, ACT_LOGITS_F32 = 0, 1
 ACT_F32, ACT_F64, ACT_F32X4 = 0, 1, 2
 PRIO_FANOUT, PRIO_ONE, PRIO_SALT = 64, 65536, 0x3C6EF372
+SAC_SALT = 0x60000000
 WINNER_NAMES = ("none", "red", "blue", "tie")
 
 c_void_p, c_int, c_int64, c_uint32, c_uint64, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
@@ -106,6 +107,15 @@ class BsxTdIo(ctypes.Structure):
 
 class BsxTd3Io(ctypes.Structure):
     _fields_ = [(f, c_void_p) for f in ("q1", "q2", "q1_next", "q2_next", "rew", "done", "weight", "g_q1", "g_q2", "g_pi", "td")]
+
+
+class BsxSacIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("q1", "q2", "q1_next", "q2_next", "logp_next", "rew", "done", "weight", "log_alpha", "g_q1", "g_q2", "td")]
+
+
+class BsxSacPolicyIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("gx1", "gx2", "z", "logp", "q1_pi", "q2_pi", "weight", "log_std", "log_alpha", "g_a4", "g_log_std",
+                                        "g_log_alpha", "alpha_m", "alpha_v", "hyper", "step")]
 
 
 MINIBATCH_FIELDS = ("obs", "rec", "logp", "adv", "ret", "value", "mask")
@@ -197,6 +207,14 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p]),
     "bsx_td3_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_td3_head": (c_int, [ctypes.POINTER(BsxTd3Io), c_int64, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "bsx_sac_sample_actions": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsx_sac_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_sac_head": (c_int, [ctypes.POINTER(BsxSacIo), c_int64, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "bsx_sac_policy_seed": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_sac_policy_grad_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_sac_policy_grad": (c_int, [ctypes.POINTER(BsxSacPolicyIo), c_int64, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p,
+                                    c_void_p]),
     "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
                                      c_void_p]),

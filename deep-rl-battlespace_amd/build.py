@@ -59,6 +59,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_ddpg_head.hip"), []),
            # TD3's smoothing and twin-critic head: the smoothing's operations each rounded on their own, as tests/td3_util.py restates them
            (os.path.join(CSRC, "bsx_td3_head.hip"), ["-ffp-contract=off"]),
+           # SAC's sampling, soft head and policy gradients: every operation rounded on its own, as tests/sac_util.py restates them
+           (os.path.join(CSRC, "bsx_sac_head.hip"), ["-ffp-contract=off"]),
            # the keyed row permutation and the minibatch gather: integer arithmetic and bit copies
            (os.path.join(CSRC, "bsx_shuffle.hip"), [])]
 

@@ -6,6 +6,7 @@
   ppo.py      the PPO loss head and PPOLearner, the update of a rollout's two networks (csrc/bsx_ppo_head.hip)
   ddpg.py     the critic join, TD head and action gradient, and DDPGLearner, the MADDPG update of a team from its ring (csrc/bsx_ddpg_head.hip)
   td3.py      target policy smoothing, the TD head of two critics, and TD3Learner: twin critics, a delayed actor and target step (csrc/bsx_td3_head.hip)
+  sac.py      the Gaussian policy's reparameterised draw, the soft twin head, the policy's seeds and gradients, and SACLearner (csrc/bsx_sac_head.hip)
   _common.py  what more than one of them uses: the hyper-parameter ranges, the stream, the capture of an update as one graph
 
 A PPO minibatch:  [minibatch_gather] -> bsx_actor_forward with the value head -> ppo_head -> bsx_mlp_grad of the actor, of the critic -> adam_step.
@@ -13,6 +14,10 @@ A DDPG update:    buffer.sample -> ddpg_inputs -> target actor, ddpg_put_actions
                   critic -> actor, ddpg_put_actions -> bsx_mlp_grad of the critic for grad_x, ddpg_action_grad -> bsx_mlp_grad, mlp_adam_step of the actor.
 A TD3 update:     as DDPG's, with td3_smooth_actions in place of the first ddpg_put_actions, both target critics and both critics -> td3_head ->
                   bsx_mlp_grad of each critic, ONE mlp_adam_step of both; the actor's half, and every Polyak target, once per policy_delay updates.
+A SAC update:     as TD3's without its delay, the CURRENT actor and sac_sample_actions in place of the target actor and td3_smooth_actions (a' ~ pi
+                  with logp'), both target critics and both critics -> sac_head -> bsx_mlp_grad of each critic, ONE mlp_adam_step of both with their
+                  targets -> actor, sac_sample_actions (a ~ pi with logp, z) -> both stepped critics, sac_policy_seed -> bsx_mlp_grad of each critic
+                  for grad_x -> sac_policy_grad (g_a4, g_log_std, log_alpha's step) -> bsx_mlp_grad, mlp_adam_step of the actor with log_std.
 """
 from . import adam, ddpg, mlp
 from .adam import (ADAM_STATS, HYPER, AdamState, adam_hyper, adam_step, adam_step_workspace_bytes, is_tied, mlp_adam_step,  # noqa: F401
@@ -21,6 +26,8 @@ from .ddpg import MAX_OBS, TD_STATS, DDPGLearner, TdHead, ddpg_action_grad, ddpg
 from .mlp import H, PARAMS, blob_floats, categorical_log_prob, fused_apply, fused_grad, fused_mlp, grad_floats, mlp_grad, split_grad  # noqa: F401
 from .ppo import KINDS, STATS, PPOLearner, PpoHead, ppo_head, ppo_head_workspace_bytes  # noqa: F401
 from .td3 import TD3_STATS, TD3Learner, Td3Head, td3_head, td3_head_workspace_bytes, td3_smooth_actions  # noqa: F401
+from .sac import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
+                  sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
 from .shuffle import GATHER_ROWS, Minibatch, minibatch_gather, shuffle_rows  # noqa: F401
 
 _Buffers, _buffers, _actor_forward, _mlp_forward, _mlp_grad, _tied_tensors, _critic_width = (  # used by tests/ and tools/

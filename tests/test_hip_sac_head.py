@@ -1,0 +1,294 @@
+"""The SAC kernels on the MI355X (csrc/bsx_sac_head.hip: learner.sac_head, sac_sample_actions, sac_policy_seed, sac_policy_grad): the
+soft twin head against its float64 restatement at a small multiple of what torch float32 autograd itself loses on the same inputs
+(tests/sac_util.py), between guard slabs; its reduction to bsx_td3_head at alpha = 0 bit for bit; finished rows and a NaN logp_next;
+the draw with injected normals against float64 with every other float of x untouched, its reduction to ddpg_put_actions at log_std =
+-inf, and its own Philox normals under a salt of its own; the policy's seeds bit for bit; the policy's gradients against float64 and
+the temperature's Adam step."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import ddpg_util as D
+import philox_util as PU
+import sac_util as S
+import yardstick_util as Y
+from guard_util import Buffers
+
+pytestmark = pytest.mark.gpu
+
+SEED, SEQ, SEQ_BASE = 0x1234ABCD5678, 7, (1 << 33) + 1000
+NORMAL_TOL = 1e-5                 # |z - z64| <= NORMAL_TOL * (1 + |z64|), tests/test_hip_gaussian_head.py's rule
+NAN = float("nan")
+SENTINEL = np.int32(0x7FC0BEEF)   # a NaN with a payload: no arithmetic produces it
+
+
+def _bits(t):
+    return t.detach().cpu().numpy().view(np.int32)
+
+
+def _same_bits(a, b):
+    return all(x is None and y is None or torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
+
+
+def _put(G, inp):
+    dev = {}
+    for k, v in inp.items():
+        dev[k] = G(k, tuple(v.shape), v.dtype)
+        dev[k].copy_(v)
+    return dev
+
+
+# ---------------------------------------------------------------------------------------------------- 1. the soft twin head
+def _head(inp, weight=True, gamma=D.GAMMA, guarded=False, fill=7.0):
+    from deep_rl_battlespace_amd.learner import sac_head, sac_head_workspace_bytes
+    B, nA = inp["q1"].shape
+    G = Buffers(guarded)
+    dev = _put(G, inp)
+    out = tuple(G(k, (B, nA, 4), torch.float32, init=fill) for k in ("g_q1", "g_q2")) + \
+        (G("td", (B, nA), torch.float32, init=fill), G("stats", (8,), torch.float64, init=fill))
+    ws = G("workspace", (sac_head_workspace_bytes(B, nA) // 8,), torch.int64, init=-1)
+    res = sac_head(dev["q1"], dev["q2"], dev["q1_next"], dev["q2_next"], dev["logp_next"], dev["rew"], dev["done"], dev["log_alpha"], gamma,
+                   weight=dev["weight"] if weight else None, out=out, workspace=ws)
+    torch.cuda.synchronize()
+    assert all(a is b for a, b in zip(res, out))
+    return res, G.stray()
+
+
+def _numpy(res, names):
+    return dict({k: getattr(res, k).double().cpu().numpy() for k in names}, stats=res.stats.cpu().numpy())
+
+
+@pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
+@pytest.mark.parametrize("BnA", S.HEAD_SHAPES, ids=lambda s: "B%d-nA%d" % s)
+def test_the_soft_head_stays_within_the_float32_yardstick_of_the_float64_contract_between_guard_slabs(BnA, weight):
+    """Every shape of td3_util.HEAD_SHAPES, the last with two tiles per workgroup and five merge rounds, at the project's (2, 4) or the
+    factor yardstick_util's rule makes of the yardstick's own recorded spread (profiles/sac_float64.json).  Two fills: an output float
+    that keeps both was not written; the two calls leave the same bits."""
+    inp, ref, yard, e_stats = S.sac_case(*BnA, weight)
+    fills = []
+    for fill in (7.0, -3.0):
+        res, stray = _head(inp, weight, guarded=True, fill=fill)
+        assert not stray, stray
+        fills.append([t.clone() for t in res])
+    assert _same_bits(*fills)
+    S.check_sac(_numpy(res, S.TD_NAMES), ref, yard, e_stats, "SAC " + S.head_id(*BnA, weight), S.factors(*BnA, weight))
+    assert all(not _bits(getattr(res, k))[..., 1:].any() for k in ("g_q1", "g_q2"))       # columns 1 .. 3: +0
+
+
+@pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
+@pytest.mark.parametrize("BnA", (S.HEAD_SHAPES[2], S.HEAD_SHAPES[-1]), ids=lambda s: "B%d-nA%d" % s)
+def test_with_alpha_exactly_zero_the_head_is_bsx_td3_heads_bit_for_bit(BnA, weight):
+    from deep_rl_battlespace_amd.learner import td3_head
+    inp, *_ = S.sac_case(*BnA)
+    res, _ = _head(dict(inp, log_alpha=torch.full_like(inp["log_alpha"], -math.inf)), weight)
+    dev = {k: v.cuda() for k, v in inp.items()}
+    two = td3_head(dev["q1"], dev["q2"], dev["q1_next"], dev["q2_next"], dev["rew"], dev["done"], D.GAMMA, weight=dev["weight"] if weight else None)
+    torch.cuda.synchronize()
+    assert _same_bits((res.g_q1, res.g_q2, res.td), (two.g_q1, two.g_q2, two.td))
+    assert torch.equal(res.stats.view(torch.int64), two.stats.view(torch.int64))
+    plain, _ = _head(inp, weight)
+    assert not _same_bits((plain.td,), (res.td,))                               # and the entropy term is in y otherwise
+
+
+def test_a_finished_row_keeps_a_nan_logp_next_out_and_a_running_row_carries_it():
+    B, nA = S.HEAD_SHAPES[2]
+    inp, *_ = S.sac_case(B, nA)
+    over = inp["done"] != 0
+    assert 20 < int(over.sum()) < B * nA - 20
+    nan = torch.tensor(NAN)
+    base, _ = _head(inp)
+    out, _ = _head(dict(inp, logp_next=torch.where(over, nan, inp["logp_next"]), q1_next=torch.where(over, nan, inp["q1_next"])))
+    assert _same_bits(base, out) and bool(torch.isfinite(out.stats).all())
+    res, _ = _head(dict(inp, logp_next=torch.full_like(inp["logp_next"], NAN)))
+    td = res.td.cpu()
+    assert bool(torch.isnan(td[~over]).all()) and torch.equal(td[over].view(torch.int32), base.td.cpu()[over].view(torch.int32))
+    for which in ("q1_next", "q2_next"):                                         # td3_head's NaN rule for the smaller of the two
+        res, _ = _head(dict(inp, **{which: torch.full_like(inp[which], NAN)}))
+        assert bool(torch.isnan(res.td.cpu()[~over]).all()), which
+    # each agent's own temperature: agent 1's alone moved, agent 0's column keeps its bits
+    la = inp["log_alpha"].clone()
+    la[1] += 1.0
+    moved, _ = _head(dict(inp, log_alpha=la))
+    assert torch.equal(moved.td[:, 0].view(torch.int32), base.td[:, 0].view(torch.int32)) and not torch.equal(moved.td[:, 1], base.td[:, 1])
+
+
+# ---------------------------------------------------------------------------------------------------- 2. the draw
+def _x(G, shape, name="x"):
+    B, nA, Do, k, central = shape
+    x = G(name, (B, nA, D.width(nA, Do, k, central)), torch.float32)
+    x.view(torch.int32).fill_(int(SENTINEL))
+    return x
+
+
+@pytest.mark.parametrize("own_only", [False, True], ids=["every-slot", "own-only"])
+@pytest.mark.parametrize("shape", S.SAMPLE_SHAPES, ids=D.shape_id)
+def test_the_draw_with_injected_normals_is_its_float64_restatement_and_writes_nothing_else(shape, own_only):
+    """Between guard slabs; x starts as a sentinel bit pattern and every float outside the slots ddpg_put_actions(own_only) writes keeps
+    it.  a and logp against float64 by yardstick_util's bars (expf is the device's: no bit equality), the yardstick being the draw as a
+    torch user writes it in float32; z_out is the injected normals with column 3 = +0, bit for bit."""
+    from deep_rl_battlespace_amd.learner import ddpg_put_actions, sac_sample_actions
+    B, nA, Do, k, central = shape
+    y4, ls, z = S.sample_arrays(shape)
+    G = Buffers(True)
+    dev = _put(G, dict(y4=torch.from_numpy(y4), log_std=torch.from_numpy(ls), z=torch.from_numpy(z)))
+    x = _x(G, shape)
+    x0 = x.cpu().numpy()
+    logp, z_out = G("logp", (B, nA), torch.float32, init=7.0), G("z_out", (B, nA, 4), torch.float32, init=7.0)
+    res = sac_sample_actions(dev["y4"], dev["log_std"], x, Do, k, seed=SEED, z=dev["z"], central=bool(central), own_only=own_only,
+                             out=(logp, z_out))
+    torch.cuda.synchronize()
+    assert res[0] is x and res[1] is logp and res[2] is z_out and not G.stray(), G.stray()
+    got = x.cpu().numpy()
+    want, want_lp = S.ref_sample(y4.astype(np.float64), ls, z, np.zeros_like(x0, np.float64), Do, central, own_only)
+    written = D.ref_put_actions(np.ones((B, nA, 4), np.float32), np.zeros_like(x0), Do, 3, central, own_only) != 0
+    assert (got.view(np.int32)[~written] == SENTINEL).all() and not (got.view(np.int32)[written] == SENTINEL).any()
+    a32, lp32 = S.torch_sample(y4, ls, z)
+    a4 = np.concatenate([a32, np.zeros((B, nA, 1))], -1)
+    yard_x = D.ref_put_actions(a4, np.zeros_like(x0, np.float64), Do, 3, central, own_only)
+    bad = Y.check_tensors([("a", got.astype(np.float64)[written], want[written], yard_x[written], Y.FACTORS),
+                           ("logp", logp.double().cpu().numpy(), want_lp, lp32, Y.FACTORS)], "SAC draw " + D.shape_id(shape), unit="x")[1]
+    assert not bad, bad
+    zz = z.copy()
+    zz[..., 3] = 0.0
+    assert np.array_equal(_bits(z_out), zz.view(np.int32))
+    if central and not own_only:
+        W = nA * Do
+        assert all(np.array_equal(got.view(np.int32)[:, 0, W:], got.view(np.int32)[:, i, W:]) for i in range(1, nA))
+    # log_std = -inf: sigma = 0, the draw is the mean, bit for bit what ddpg_put_actions writes
+    a, b = _x(Buffers(False), shape), _x(Buffers(False), shape)
+    sac_sample_actions(dev["y4"], torch.full_like(dev["log_std"], -math.inf), a, Do, k, seed=SEED, z=dev["z"], central=bool(central), own_only=own_only)
+    ddpg_put_actions(dev["y4"], b, Do, k, central=bool(central), own_only=own_only)
+    assert _same_bits((a,), (b,))
+    assert np.array_equal(_bits(dev["y4"]), y4.view(np.int32)) and np.array_equal(_bits(dev["z"]), z.view(np.int32))       # read only
+
+
+def _philox_draw(B, nA, seq_base, seed=SEED, seq=SEQ):
+    """(a [B, nA, 3], z_out, logp) the kernel makes of y4 = 0 and log_std = 0 with its own Philox normals (own critics)."""
+    from deep_rl_battlespace_amd.learner import sac_sample_actions
+    Do = 2
+    y4, ls = torch.zeros((B, nA, 4), device="cuda"), torch.zeros((nA, 3), device="cuda")
+    x = torch.full((B, nA, Do + 3), 9.0, device="cuda")
+    base = torch.tensor([seq_base], dtype=torch.int64, device="cuda")
+    _, logp, z_out = sac_sample_actions(y4, ls, x, Do, 3, seed=seed, seq=seq, seq_base=base, central=False)
+    torch.cuda.synchronize()
+    assert bool((x[..., :Do] == 9.0).all()) and int(base) == seq_base
+    return x[..., Do:].double().cpu().numpy(), z_out.double().cpu().numpy(), logp.double().cpu().numpy()
+
+
+def test_the_draws_own_normals_are_philox_normals_under_a_salt_of_their_own_and_another_word_draws_other_noise():
+    """y4 = 0, log_std = 0, B nA = 4133: a = z, so the action columns and z_out are philox_util.normals4(seed, seq + seq_base, b nA + j,
+    0x60000000) -- and far from the draws at each of the five other salts."""
+    B, nA = 4133, 1
+    a, z_out, logp = _philox_draw(B, nA, SEQ_BASE)
+    z = S.philox_normals(SEED, SEQ + SEQ_BASE, B, nA)
+    err = np.abs(a - z[..., :3]) / (1.0 + np.abs(z[..., :3]))
+    print(f"max |a - z64| / (1 + |z64|) = {err.max():.3e} (bar {NORMAL_TOL:.3e})")
+    assert float(err.max()) <= NORMAL_TOL and np.array_equal(z_out[..., :3], a) and not z_out[..., 3].any()
+    want_lp = (-0.5 * a * a).sum(-1) - 3.0 * S.HALF_LOG_2PI
+    assert float(np.abs(logp - want_lp).max()) <= 1e-5
+    grows = np.arange(B * nA, dtype=np.uint64)
+    assert len(set(S.OTHER_SALTS)) == 5 and S.SALT not in S.OTHER_SALTS
+    for other in S.OTHER_SALTS:
+        assert np.abs(a - PU.normals4(SEED, SEQ + SEQ_BASE, grows, other).reshape(B, nA, 4)[..., :3]).mean() > 0.5, hex(other)
+    assert np.array_equal(_philox_draw(4133 // 3, 3, SEQ_BASE)[0].reshape(-1, 3), a.reshape(-1, 3)[:4133 // 3 * 3])     # the key is b nA + j
+    assert np.array_equal(_philox_draw(B, nA, SEQ_BASE + SEQ, seq=0)[0], a)            # seq and the device word add up
+    other = _philox_draw(B, nA, SEQ_BASE + 1)[0]
+    assert (other != a).mean() > 0.99 and np.array_equal(_philox_draw(B, nA, SEQ_BASE)[0], a)
+
+
+# ---------------------------------------------------------------------------------------------------- 3. the policy's seeds
+@pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
+@pytest.mark.parametrize("BnA", S.HEAD_SHAPES[:5], ids=lambda s: "B%d-nA%d" % s)
+def test_the_policy_seeds_are_their_numpy_restatement_bit_for_bit_with_ties_and_nans(BnA, weight):
+    from deep_rl_battlespace_amd.learner import sac_policy_seed
+    B, nA = BnA
+    g = torch.Generator().manual_seed(60 + B + nA)
+    q1 = torch.randn((B, nA), generator=g)
+    q2 = q1 + 0.3 * torch.randn((B, nA), generator=g)
+    flat1, flat2 = q1.view(-1), q2.view(-1)
+    flat2[::5] = flat1[::5]                                                      # ties: critic 2
+    flat1[1::7] = NAN                                                            # a NaN in q1: critic 1
+    flat2[2::7] = NAN                                                            # a NaN in q2 alone: critic 2
+    w = torch.rand((B, nA), generator=g) + 0.5
+    G = Buffers(True)
+    dev = _put(G, dict(q1=q1, q2=q2, w=w))
+    out = (G("g1", (B, nA, 4), torch.float32, init=7.0), G("g2", (B, nA, 4), torch.float32, init=7.0))
+    res = sac_policy_seed(dev["q1"], dev["q2"], weight=dev["w"] if weight else None, out=out)
+    torch.cuda.synchronize()
+    assert res[0] is out[0] and res[1] is out[1] and not G.stray()
+    with np.errstate(all="ignore"):
+        w1, w2 = S.ref_policy_seed(q1.numpy(), q2.numpy(), w.numpy() if weight else None, B)
+    assert np.array_equal(_bits(out[0]), w1.view(np.int32)) and np.array_equal(_bits(out[1]), w2.view(np.int32))
+    picked = (_bits(out[0])[..., 0] != 0).astype(int) + (_bits(out[1])[..., 0] != 0).astype(int)
+    assert (picked == 1).all()                                                   # exactly one critic per element
+
+
+# ---------------------------------------------------------------------------------------------------- 4. the policy's gradients
+def _policy(inp, shape, weight=True, adam=None, guarded=True, te=S.TARGET_ENTROPY):
+    from deep_rl_battlespace_amd.learner import sac_policy_grad, sac_policy_grad_workspace_bytes
+    B, nA, Do, k, central = shape
+    G = Buffers(guarded)
+    dev = _put(G, inp)
+    out = (G("g_a4", (B, nA, 4), torch.float32, init=7.0), G("g_ls", (nA, 3), torch.float32, init=7.0), G("g_la", (nA,), torch.float32, init=7.0),
+           G("stats", (8,), torch.float64, init=7.0))
+    ws = G("workspace", (sac_policy_grad_workspace_bytes(B, nA) // 8,), torch.int64, init=-1)
+    kw = dict(alpha_state=adam[0], hyper=adam[1], step=adam[2]) if adam else {}
+    res = sac_policy_grad(dev["gx1"], dev["gx2"], dev["z"], dev["logp"], dev["q1_pi"], dev["q2_pi"], dev["log_std"], dev["log_alpha"], Do, k,
+                          target_entropy=te, weight=dev["weight"] if weight else None, central=bool(central), out=out, workspace=ws, **kw)
+    torch.cuda.synchronize()
+    assert all(a is b for a, b in zip(res, out)) and not G.stray(), G.stray()
+    return res, dev
+
+
+@pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
+@pytest.mark.parametrize("shape", S.GRAD_SHAPES, ids=D.shape_id)
+def test_the_policy_gradients_g_a4_bit_for_bit_and_the_sums_within_the_yardstick_of_float64(shape, weight):
+    """g_a4 is the float32 restatement bit for bit; g_log_std, g_log_alpha and the statistics against the float64 contract, each element
+    by yardstick_util.scalar_bound of what the same sums taken by torch in float32 lose over nine row orders (sac_util.sums_out_of_bounds
+    says why these per-agent sums are held as statistics).  Without Adam state log_alpha keeps its bits."""
+    B, nA, Do, k, central = shape
+    inp, ref, yard, own = S.policy_case(shape, weight)
+    res, dev = _policy(inp, shape, weight)
+    assert np.array_equal(_bits(res.g_a4), S.ga32(inp["gx1"].numpy(), inp["gx2"].numpy(), Do, central).view(np.int32))
+    got = dict(g_log_std=res.g_log_std.double().cpu().numpy(), g_log_alpha=res.g_log_alpha.double().cpu().numpy())
+    what = "SAC policy " + D.shape_id(shape)
+    bad = [b for k_ in ("g_log_std", "g_log_alpha") for b in S.sums_out_of_bounds(got[k_], ref[k_], own[k_], k_, what)]
+    bad += S.pi_stats_out_of_bounds(res.stats.cpu().numpy(), ref["stats"], own["stats"], what)
+    assert not bad, bad
+    assert torch.equal(dev["log_alpha"].cpu().view(torch.int32), inp["log_alpha"].view(torch.int32))
+    again, _ = _policy(inp, shape, weight, guarded=False)
+    assert _same_bits(res[:3], again[:3]) and torch.equal(res.stats.view(torch.int64), again.stats.view(torch.int64))
+
+
+@pytest.mark.parametrize("shape", (S.GRAD_SHAPES[3], S.GRAD_SHAPES[-1]), ids=D.shape_id)
+def test_with_adam_state_the_merge_takes_one_step_of_log_alpha_held_to_float64_adam_and_advances_the_word(shape):
+    """Two steps in a row from zero moments: log_alpha, m and v against adam_util.reference_step in float64 on the kernel's own float32
+    gradient, the yardstick torch.optim.Adam in float32 (test_hip_adam_mlp.py's bars: check_step, pooled); the gradients and statistics
+    of the call are those of the call without a step, bit for bit (log_alpha is read before it is written)."""
+    from deep_rl_battlespace_amd.learner import AdamState, adam_hyper
+    nA = shape[1]
+    inp, *_ = S.policy_case(shape)
+    plain, _ = _policy(inp, shape)
+    hp = S.AU.hyper32(3e-3, 0.9, 0.999, 1e-3, 0.0)
+    la = inp["log_alpha"].clone()
+    state, step = AdamState(la.cuda()), torch.zeros(1, dtype=torch.int64, device="cuda")
+    hyper = adam_hyper(hp["lr"], (hp["beta1"], hp["beta2"]), hp["eps"], 0.7, "cuda", 0.3)          # max_grad_norm and tau are not read
+    p64, m64, v64 = [la.double().numpy()], [np.zeros(nA)], [np.zeros(nA)]
+    p32 = la.clone().requires_grad_()
+    opt = torch.optim.Adam([p32], lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
+    for t in range(2):
+        res, dev = _policy(dict(inp, log_alpha=la), shape, adam=(state, hyper, step))
+        if t == 0:
+            assert _same_bits(plain[:3], res[:3]) and torch.equal(plain.stats.view(torch.int64), res.stats.view(torch.int64))
+        g = res.g_log_alpha.cpu()
+        p64, m64, v64, *_ = S.AU.reference_step(p64, [g.double().numpy()], m64, v64, t, hp)
+        p32.grad = g.clone()
+        opt.step()
+        la = dev["log_alpha"].cpu().clone()
+        assert int(step) == t + 1
+        got = dict(p=[la.numpy()], m=[state.m.cpu().numpy()], v=[state.v.cpu().numpy()])
+        yard = dict(p=[p32.detach().numpy()], m=[opt.state[p32]["exp_avg"].numpy()], v=[opt.state[p32]["exp_avg_sq"].numpy()])
+        S.AU.check_step(got, dict(p=p64, m=m64, v=v64), yard, f"log_alpha step {t + 1}", names=("p", "m", "v"))
+    assert not torch.equal(la, inp["log_alpha"])

@@ -1,0 +1,281 @@
+"""SACLearner on the MI355X: an update is, bit for bit, the sequence of the public primitives written out by hand (tests/sac_util.py:
+Hand), on a plain and on a prioritised ring; a captured update runs nothing, replays the eager updates with fresh draws and fresh noise
+and allocates nothing; with lr_alpha=None the temperature never moves; a whole update from target critics that are not the critics
+against float64; one iteration of the documented loop on a real continuous 1v1 env with a Gaussian rollout; and a bandit on which the
+captured updates must learn at least half of what the torch composition of the same SAC learns."""
+import gc
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ddpg_util as D
+import sac_util as S
+import td3_util as T
+
+pytestmark = pytest.mark.gpu
+
+KW = D.KW
+
+
+def _central(shape):
+    return "central" if shape[4] else "own"
+
+
+def _nets(shape, seed=0):
+    actor, critic, rows, *_ = D.learner_case(shape, seed)
+    return (D.gpu_copy(actor), D.gpu_copy(critic), D.gpu_copy(T.critic2_of(shape, seed))), rows
+
+
+def _learner(shape, ring=D.ring, seed=0, **kw):
+    from deep_rl_battlespace_amd.learner import SACLearner
+    made, rows = _nets(shape, seed)
+    return SACLearner(ring(rows, shape[0]), *made, critic_input=_central(shape), **{**KW, **kw})
+
+
+def _hand(shape, ring=D.ring, seed=0, **kw):
+    made, rows = _nets(shape, seed)
+    return S.Hand(ring(rows, shape[0]), *made, shape[4], **{**KW, **kw})
+
+
+HAND_CASES = [(s, D.ring) for s in S.HAND_SHAPES] + [(s, T.prio_ring) for s in S.HAND_SHAPES[:2]]
+
+
+@pytest.mark.parametrize("shape,ring", HAND_CASES, ids=[D.shape_id(s) + ("-prioritised" if r is T.prio_ring else "") for s, r in HAND_CASES])
+def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(shape, ring):
+    learner, hand = _learner(shape, ring, updates=2), _hand(shape, ring, updates=2)
+    start = S.snapshot(learner)
+    assert D.differing(start, S.snapshot(hand)) == []
+    for call in range(2):
+        stats = learner.update()
+        hand.update()
+        a, b = S.snapshot(learner), S.snapshot(hand)
+        assert D.differing(a, b) == [], (call, D.differing(a, b))
+        assert stats is learner.stats and stats.shape == (2, 8) and float(stats[1, 0]) == shape[0] * shape[1]
+        assert torch.equal(learner.td.view(torch.int32), hand.td.view(torch.int32))
+    assert int(learner.step_critic) == 4 == int(learner.step_actor) == int(learner.step_alpha) and int(learner.buffer._draws) == 4
+    assert int(learner._noise_draws) == 8                                      # two draws per update
+    assert torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
+    moved = set(D.differing(start, a))
+    assert {"actor.w1", "critic.w1", "critic2.w1", "target_critic.w2", "target_critic2.w2", "_blob_a", "_blob_c", "_blob_c2", "_blob_tc", "_blob_tc2",
+            "adam_actor.m", "adam_critic.v", "adam_critic2.v", "stats", "stats_pi", "step_stats_actor", "step_stats_critic", "draws", "noise_draws",
+            "log_std", "log_alpha", "adam_log_std.m", "adam_alpha.v", "step_alpha"} <= moved
+    assert ring is D.ring or {"leaves", "tree", "max_priority"} <= moved
+    # SAC has no target actor: the inherited one is never read or stepped
+    assert not {k for k in moved if k.startswith("target_actor.")} and "_blob_ta" not in moved
+    S.blobs_are_packs(learner)
+    pi = learner.stats_pi.cpu().numpy()
+    assert (pi[:, 0] == shape[0] * shape[1]).all() and (pi[:, 7] == 0).all() and ((0 <= pi[:, 6]) & (pi[:, 6] <= 1)).all()
+    # alpha's mean: four Adam steps of at most about lr_alpha = 3e-4 each from log 0.2;  q_gap: the critics differ
+    assert (np.abs(np.log(pi[:, 4] / 0.2)) <= 4 * 1.5 * 3e-4).all() and float(learner.stats[1, 7]) > 0.0
+
+
+@pytest.mark.parametrize("ring", [D.ring, T.prio_ring], ids=["uniform", "prioritised"])
+def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(ring):
+    shape = S.MAIN_SHAPES[0]
+    captured, eager = (_learner(shape, ring, updates=2) for _ in range(2))
+    start = S.snapshot(captured)
+    state = [t.detach().clone() for t in captured._state()]
+    assert captured.capture() is captured
+    assert D.differing(start, S.snapshot(captured)) == []                     # a capture runs nothing
+    assert all(torch.equal(a.view(torch.uint8), b.detach().view(torch.uint8)) for a, b in zip(state, captured._state()))
+    for t in (captured._noise_draws, captured.log_std, captured.log_alpha, captured.step_alpha, captured.adam_alpha.m, captured.adam_log_std.v,
+              captured._blob_c2, captured._blob_tc2, captured.stats_pi):
+        assert any(t is s for s in captured._state())
+    assert ring is D.ring or any(t is captured.buffer.tree for t in captured._state())
+    draws, tds, logps = [], [], []
+    for u in range(2):
+        captured.update()
+        eager.update()
+        draws.append(captured.buffer.last_idx.clone())
+        tds.append(captured.td.clone())
+        logps.append(captured._logp.clone())
+        a, b = S.snapshot(captured), S.snapshot(eager)
+        assert D.differing(a, b) == [], (u, D.differing(a, b))
+        assert torch.equal(captured.td.view(torch.int32), eager.td.view(torch.int32))
+    assert not torch.equal(draws[0], draws[1]) and not torch.equal(tds[0], tds[1]) and not torch.equal(logps[0], logps[1])
+    assert int(captured.buffer._draws) == 4 and int(captured._noise_draws) == 8 and int(captured.step_critic) == 4 == int(captured.step_alpha)
+    S.blobs_are_packs(captured)
+    del a, b
+    torch.cuda.synchronize()
+    gc.collect()
+    held = torch.cuda.memory_allocated()
+    captured.update()
+    captured.update()
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == held
+
+
+def test_with_lr_alpha_none_the_temperature_never_moves_and_set_lr_reaches_the_captured_step():
+    shape = S.MAIN_SHAPES[0]
+    fixed = _learner(shape, updates=2, lr_alpha=None, alpha=0.3).capture()
+    la0 = fixed.log_alpha.clone()
+    for _ in range(2):
+        fixed.update()
+    assert torch.equal(fixed.log_alpha.view(torch.int32), la0.view(torch.int32)) and int(fixed.step_alpha) == 0 and fixed.adam_alpha is None
+    assert float(la0[0]) == float(np.float32(math.log(0.3))) and int(fixed.step_actor) == 4
+    assert np.allclose(fixed.stats_pi[:, 4].cpu().numpy(), 0.3, rtol=1e-6)
+    with pytest.raises(ValueError, match="lr_alpha=None"):
+        fixed.set_lr(alpha=1e-3)
+    moving = _learner(shape, updates=1, lr_alpha=1e-2).capture()
+    moving.update()
+    la1 = moving.log_alpha.clone()
+    assert not torch.equal(la1, la0) and int(moving.step_alpha) == 1
+    moving.set_lr(alpha=0.0)                                                    # a rate of 0: the captured step reads it and stands still
+    moving.update()
+    assert torch.equal(moving.log_alpha.view(torch.int32), la1.view(torch.int32)) and int(moving.step_alpha) == 2
+    # the learner steps the caller's log_std in place
+    own = torch.full((shape[1], 3), -0.5, device="cuda")
+    made, rows = _nets(shape)
+    from deep_rl_battlespace_amd.learner import SACLearner
+    x = SACLearner(D.ring(rows, shape[0]), *made, log_std=own, critic_input=_central(shape), **KW)
+    x.update()
+    assert x.log_std is own and bool((own != -0.5).all())
+
+
+def _step_arrays(x, which):
+    net, state = getattr(x, which), getattr(x, "adam_" + which)
+    cut = lambda row: S.AU.row_to_tensors(row.detach().cpu().numpy(), net.n_actions)     # noqa: E731
+    out = dict(p=S.AU.net_arrays(net), m=cut(state.m), v=cut(state.v))
+    if which != "actor":
+        out["target"] = S.AU.net_arrays(getattr(x, "target_" + which))
+    return out
+
+
+@pytest.mark.parametrize("shape", S.MAIN_SHAPES, ids=D.shape_id)
+def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float64(shape):
+    """One whole update through the primitives (Hand.step, ddpg_util.STEP_KW, both draws' normals injected, random log_std and
+    log_alpha) from target critics that are NOT the critics, against sac_util.stepped_case's float64 reference with the same computation
+    in float32 on the CPU as the yardstick: both critics' gradient rows and their joint step with both targets, the actor's row at the
+    STEPPED critics and its step, log_std's gradient and step, log_alpha's gradient and step -- each pooled, ddpg_util.check_step's bars
+    (2, 4); log_std's and log_alpha's gradients, three numbers and one per agent, by (2, 4) or the factor yardstick_util's rule makes of
+    the yardstick's own recorded spread (profiles/sac_float64.json) -- and both statistics rows.  BSX_SAC_RATIOS_OUT names a file the measured ratios are appended to."""
+    from deep_rl_battlespace_amd.learner import split_grad
+    B, nA, Do, k, central = shape
+    c = S.stepped_case(shape)
+    assert c.share < D.U.KINK_CAP
+    hand = _hand(shape, seed=c.seed, updates=1, log_std=c.log_std.cuda().contiguous(), lr_alpha=S.ALPHA_LR, **D.STEP_KW)
+    hand.log_alpha.copy_(c.log_alpha)
+    for name, net in zip(("actor", "critic", "critic2"), c.nets):
+        assert all(torch.equal(getattr(getattr(hand, name), p).cpu(), getattr(net, p)) for p in D.PARAMS), name
+    with torch.no_grad():
+        for t, src, blob in ((hand.target_critic, c.targets[0], hand._blob_tc), (hand.target_critic2, c.targets[1], hand._blob_tc2)):
+            for p in D.PARAMS:
+                getattr(t, p).copy_(getattr(src, p))
+            t.pack(out=blob)
+    S.blobs_are_packs(hand)
+    s = hand.buffer.sample(c.idx)
+    dev_batch = (s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6])
+    for got, want in zip(dev_batch, c.batch):
+        assert torch.equal(got.cpu(), want)
+    out = hand.step(*dev_batch, 0, weight=c.w.cuda(), z_next=c.z_next.cuda(), z_pi=c.z_pi.cuda())
+    torch.cuda.synchronize()
+    sid, rec = D.shape_id(shape), {}
+    num = lambda row, na: [g.double().cpu().numpy() for g in split_grad(row, na)]          # noqa: E731
+    lst = lambda g: [g[p] for p in D.PARAMS]                                               # noqa: E731
+    print("SAC", sid)
+    got = dict(gc1=num(out["row_c"], 1), gc2=num(out["row_c2"], 1), ga=num(out["row_a"], k), g_ls=[out["g_log_std"].double().cpu().numpy()],
+               g_la=[out["g_log_alpha"].double().cpu().numpy()])
+    ref, yard = ({**{w_: lst(r[w_]) for w_ in ("gc1", "gc2", "ga")}, "g_ls": [r["g_ls"]], "g_la": [r["g_la"]]} for r in (c.ref, c.yard))
+    D.check_step(got, ref, yard, "row", rec, names=("gc1", "gc2", "ga"))
+    for which in ("critic", "critic2"):
+        D.check_step(_step_arrays(hand, which), c.ref[which], c.yard[which], which, rec)
+    D.check_step(_step_arrays(hand, "actor"), c.ref["actor"], c.yard["actor"], "actor", rec, names=("p", "m", "v"))
+    # what has one value per agent (and column): (2, 4), or the factor the rule makes of the yardstick's own recorded spread
+    arr = lambda *ts: dict(zip(("p", "m", "v"), (t.detach().double().cpu().numpy() for t in ts)))          # noqa: E731
+    mine = dict(g_ls=got["g_ls"][0], g_la=got["g_la"][0])
+    for name, step in (("log_std", arr(hand.log_std, hand.adam_log_std.m, hand.adam_log_std.v)),
+                       ("log_alpha", arr(hand.log_alpha, hand.adam_alpha.m, hand.adam_alpha.v))):
+        mine.update({f"{name}.{k_}": v for k_, v in step.items()})
+    f, r64, r32 = S.stepped_factor_of(shape), S.small(c.ref), S.small(c.yard)
+    ratios, bad = S.Y.check_tensors([(n_, mine[n_], r64[n_], r32[n_], f(n_)) for n_ in S.SMALL], "small", "pooled")
+    rec.update({f"small.{n_}": [round(v[0], 4), round(v[1], 4)] for n_, v in ratios.items()})
+    assert not bad, (bad, ratios)
+    assert int(hand.step_critic) == 1 == int(hand.step_actor) == int(hand.step_alpha) and int(hand._noise_draws) == 0
+    bad = T.stats_out_of_bounds(hand.stats[0].cpu().numpy(), c.stats, c.e_stats, f"SAC {sid}")
+    bad += S.pi_stats_out_of_bounds(hand.stats_pi[0].cpu().numpy(), c.stats_pi, c.e_stats_pi, f"SAC {sid} policy")
+    assert not bad, bad
+    S.blobs_are_packs(hand)
+    path = os.environ.get("BSX_SAC_RATIOS_OUT")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps({"shape": sid, "ratios": rec}) + "\n")
+
+
+def test_one_iteration_of_the_documented_loop_on_a_continuous_1v1_env_with_a_gaussian_rollout():
+    """tests/test_hip_ddpg_loop.py's first case -- 1v1 continuous, E = 32, T = 8, a scripted opponent, red plays -- with
+    PolicyRollout(sample="gaussian", log_std=...): run, append_rollout, update, publish; the team's rows of the rollout's log_std and of
+    its packed weights are the learner's bit for bit, the other team's rows are untouched, and the next run() plays with them."""
+    import deep_rl_battlespace_amd as bsx
+    from deep_rl_battlespace_amd import instinct
+    from deep_rl_battlespace_amd.learner import SACLearner
+    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer
+    from deep_rl_battlespace_amd.rollout import PolicyRollout, StackedActor
+    n, E, Tn, seed = 1, 32, 8, 41
+
+    def make():
+        env = bsx.parallel_env(n_agents=n, n_envs=E, seed=seed, auto_reset=True, continuous_actions=True); env.reset()
+        torch.manual_seed(seed)
+        actor = StackedActor(2 * n, 3 * n + 2, 3, device="cuda")
+        with torch.no_grad():
+            actor.w3.mul_(100.0)
+        log_std = torch.full((2 * n, 3), math.log(0.2), device="cuda")
+        ro = PolicyRollout(env, actor, Tn, noise_std=0.0, one_launch=True, sample="gaussian", log_std=log_std,
+                           opponent=instinct.Team(env.possible_blue, env.possible_red, env))
+        ro.start()
+        return env, ro
+    (env, ro), (_, base) = make(), make()
+    cols = range(n)
+    buf = DeviceReplayBuffer(600, 300, env.possible_red, env.obs_size, env.obs_size * n, 3, device="cuda", seed=3)
+    actor = StackedActor(n, ro.actor.obs_len, 3, device="cuda")
+    with torch.no_grad():
+        for p in D.PARAMS:
+            getattr(actor, p).copy_(getattr(ro.actor, p)[:n])
+    learner = SACLearner(buf, actor, critic_input="own", updates=2, **KW)
+    w0, ls0 = ro.fused.weights.clone(), ro.log_std.clone()
+    ro.run(); base.run()
+    assert torch.equal(ro.scores, base.scores)
+    assert int(buf.append_rollout(ro, cols).item()) > 0
+    learner.update()
+    learner.publish(ro, cols)
+    torch.cuda.synchronize()
+    assert torch.equal(ro.log_std[:n].view(torch.int32), learner.log_std.view(torch.int32)) and not torch.equal(ro.log_std[:n], ls0[:n])
+    assert torch.equal(ro.fused.weights[:n].view(torch.int32), learner._blob_a.view(torch.int32)) and not torch.equal(ro.fused.weights[:n], w0[:n])
+    assert torch.equal(ro.log_std[n:].view(torch.int32), ls0[n:].view(torch.int32))
+    assert torch.equal(ro.fused.weights[n:].view(torch.int32), w0[n:].view(torch.int32))
+    for p in D.PARAMS:
+        assert torch.equal(getattr(ro.actor, p)[:n], getattr(learner.actor, p)) and torch.equal(getattr(ro.actor, p)[n:], getattr(base.actor, p)[n:])
+    ro.run(); base.run()
+    torch.cuda.synchronize()
+    assert not torch.equal(ro.scores[..., :n, :], base.scores[..., :n, :])       # the next run() plays the published policy
+    assert bool(torch.isfinite(learner.stats).all()) and bool(torch.isfinite(learner.stats_pi).all())
+
+
+def test_captured_updates_on_a_bandit_learn_at_least_half_of_what_the_torch_composition_learns():
+    """ddpg_util's bandit at k = 3 (every row finished), own critics, a fixed temperature, updates = 10, captured.  N and the torch
+    composition's figures are recorded in profiles/sac_float64.json, chosen on the CPU with the torch composition of the same SAC alone,
+    which itself closes at least half of the gap from its initial reward to 0 in N updates (re-run here: a fraction of a second)."""
+    from deep_rl_battlespace_amd.learner import SACLearner
+    rec = json.load(open(S.PROFILE))["bandit"]
+    N, b = rec["N"], S.BANDIT
+    r0, r_torch = S.bandit_torch_run(N)
+    closed_torch = (r_torch - r0) / (0.0 - r0)
+    assert abs(r0 - rec["initial_reward"]) < 1e-6 and closed_torch >= 0.5 and {k: rec[k] for k in b} == b
+    rows, held = S.bandit_rows()
+    nets = S.bandit_nets()
+    learner = SACLearner(D.ring(rows, b["B"]), *(D.gpu_copy(x) for x in nets), critic_input="own", alpha=b["alpha"], lr_alpha=None, tau=b["tau"],
+                         lr_actor=b["lr"], lr_critic=b["lr"], updates=10).capture()
+    assert N % 10 == 0
+    for _ in range(N // 10):
+        learner.update()
+    with torch.no_grad():
+        before = float(D.bandit_reward(held, nets[0](held)).mean())
+        after = float(D.bandit_reward(held, learner.actor(held.cuda()).cpu()).mean())
+    closed = (after - before) / (0.0 - before)
+    print(f"bandit, N = {N}: reward {before:.4f} -> {after:.4f} (closed {closed:.3f} of the gap); torch composition of SAC -> {r_torch:.4f} "
+          f"(closed {closed_torch:.3f}; recorded {rec['torch_closed']:.3f})")
+    assert abs(before - r0) < 1e-6 and int(learner.step_actor) == N == int(learner.step_critic) and int(learner.step_alpha) == 0
+    assert closed >= 0.5 * closed_torch
