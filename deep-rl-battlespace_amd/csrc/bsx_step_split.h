@@ -43,6 +43,14 @@
 // 16 384 4.36 -> 4.22, 32 768 4.84 -> 4.65, 98 304 6.55 -> 6.40, bullet-heavy play 9.64 -> 9.45, continuous 7.65 -> 7.60
 // (profiles/r06_experiments.json).  At 114 688 games -- seven waves on a SIMD -- there is no room for the draw beside the first waves
 // (7.13 -> 7.5 ... 8.1): above 98 304 games the launcher takes DRAW = false, the first wave draws itself.
+// First loads (bsx_step_split_body.inl): the first wave issues its five record and pool loads -- addressed by arguments that arrive in
+// SGPRs with the dispatch -- before it waits for anything from the kernarg segment, whose first fetch is a cold scalar-cache miss at every
+// kernel boundary; only the action load (its address selects on the action kind, which comes from the segment) stands behind that wait.
+// 65 536 games 5.39 -> 5.32 us, 16 384 ... 114 688 games and the other action mixes likewise or unchanged.  Built against it and NOT kept,
+// each slower than its parent (profiles/kernarg_entry_fetch.json): the rest of the argument block pinned in SGPRs in one batch at entry
+// (+0.06 ... +0.12 us: what the compiler fetches next to its use mid-chain hits the scalar cache by then), the action load without its
+// select in front of the wait as well (+0.02 against the five), and the geometry wave holding the atan2 table across the pose
+// rendezvous (+0.02: that wave has no room before the rendezvous beyond the Philox block).
 //
 // How.  No second copy of the game logic: the kernel includes the SAME phase files as bsx_step_kernel, once per wave, with the R_*
 // constants of the wave's role, and the same LDS layout (bsx_step_lds.inl, one set of 64 agents that the two waves share), parameter list

@@ -2,7 +2,7 @@
 // constants): the first loads, the decode, and the seven phase files of bsx_step_kernel in tick order -- everything but the observation
 // geometry, which the second wave works out from the post-move poses this wave leaves in LDS (bsx_step_split_geom_body.inl).
     {
-        ix_t gt = g, EAt = ix_t(p.E) * ix_t(A);
+        ix_t gt = g;
         uint64_t seed_t = p.seed;
         int64_t env_offset_t = p.env_offset;
         constexpr int tie_tick = tie_tick_const(1);
@@ -15,7 +15,11 @@
         float* const rew_t = p.rew;
         uint8_t* const done_t = p.done;
         RawIn rin_next = {}; DecIn din_next = {-1, 0.0};             // (named by the phases behind `if (MULTI ...)`: never reached in this form)
-        // ---- T0: every load of the call, back to back
+        // ---- T0: every load of the call, back to back.  The five record and pool loads lead: their addresses come from arguments that arrived
+        // in SGPRs with the dispatch, so they are in flight BEFORE the wave waits for its first fetch from the kernarg segment (a cold
+        // scalar-cache miss at every kernel boundary) -- the action kind is the one leading argument that comes from there, and the action
+        // load's address selects on it.  Left to the scheduler, that wait stood in front of all six loads: C2 5.39 -> 5.32 us
+        // (profiles/kernarg_entry_fetch.json; tests/test_isa_scalar_loads.py holds the order in the eight discrete kernels).
         int x = 0, y = 0, hp = 0;
         uint32_t games = 0;
         double dir = 0.0;
@@ -31,6 +35,12 @@
             ecw = *elem(envc_, ix_t(ec));
             edw = *elem(envd_, ix_t(ec));
             prw = *elem(plane_, gt);
+            pool_first = *elem(bent_, pool0 + ix_t(lane));
+            const uint32_t pcw = *elem(bcnt_, ix_t(wblk));
+            __builtin_amdgcn_sched_barrier(0);           // (nothing below is scheduled in front of the five loads above)
+            int kind_l = kind_;
+            asm volatile("" : "+s"(kind_l));             // (the action kind, from the kernarg segment: named only HERE, so its wait stands here too)
+            const bool has_act = kind_l >= 0;
             const char* const abase = static_cast<const char*>(act_);
             float4 lg = make_float4(0.f, 0.f, 0.f, 0.f);
             int ai = -1;
@@ -60,14 +70,14 @@
                     else { a0 = c0; a1 = c1; a2 = c2; }
                 }
             } else if (has_act) act = LG ? argmax4(lg.x, lg.y, lg.z, lg.w) : ai;
-            pool_first = *elem(bent_, pool0 + ix_t(lane));
-            pc = __builtin_amdgcn_readfirstlane(*elem(bcnt_, ix_t(wblk)));
+            pc = __builtin_amdgcn_readfirstlane(pcw);
             if (p.u) uu_in = p.u[g];                     // (injected jitter: uniform branch)
             unpack_plane(prw, x, y, hp, dir);
             if constexpr (CONT) dir = (prw.y & PLANE_FRAC) ? dirf : dir;
             er = unpack_env(ecw, edw.x);
             games = edw.y;
         }
+        ix_t EAt = ix_t(p.E) * ix_t(A);                  // (p.E comes from the kernarg segment: named behind the first loads)
 #include "bsx_step_phase_actor.inl"
 #include "bsx_step_phase_shot.inl"
 #include "bsx_step_phase_move.inl"
