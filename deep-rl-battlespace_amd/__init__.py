@@ -11,7 +11,8 @@ Only what the hot path needs lives here:
   instinct/      the reference's scripted opponent, evaluated on device (next row f-2)
   rollout.py     on-device actor + step loop in one HIP graph (next row f-1); csrc/bsx_actor.hip is its MFMA actor
   replay.py      device-resident transition ring, mirror of maddpg/buffer.py (next row f-3), and its prioritised form: a sum tree of
-                 integer priorities kept current on the device (csrc/bsx_replay_prio.hip)
+                 integer priorities kept current on the device (csrc/bsx_replay_prio.hip); NStepAppender folds a rollout's records
+                 into n-step rows in front of either ring, carried across rollouts (csrc/bsx_replay_nstep.hip)
   advantage.py   GAE advantages / returns / per-agent mask of a rollout on device, for on-policy learners (csrc/bsx_advantage.hip)
   learner/       the on-device learners, one module per kernel family:
     mlp.py       the actor / value MLP as one fused forward and one fused backward for on-device learners (csrc/bsx_actor_grad.hip)
@@ -38,9 +39,9 @@ from .learner import TD3_STATS, TD3Learner, td3_head, td3_head_workspace_bytes, 
 from .learner import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
                       sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
 from .envs.battle_env import parallel_env  # noqa: F401
-from .replay import PrioritizedReplayBuffer  # noqa: F401
+from .replay import NStepAppender, PrioritizedReplayBuffer  # noqa: F401
 
-__all__ = ["AdamState", "DDPGLearner", "Minibatch", "PPOLearner", "PrioritizedReplayBuffer", "adam_step", "advantage", "categorical_log_prob", "ddpg_action_grad", "ddpg_inputs", "ddpg_put_actions", "envs", "fused_apply", "fused_mlp", "gae", "instinct", "is_tied", "learner",
+__all__ = ["AdamState", "DDPGLearner", "Minibatch", "NStepAppender", "PPOLearner", "PrioritizedReplayBuffer", "adam_step", "advantage", "categorical_log_prob", "ddpg_action_grad", "ddpg_inputs", "ddpg_put_actions", "envs", "fused_apply", "fused_mlp", "gae", "instinct", "is_tied", "learner",
            "minibatch_gather", "mlp_adam_step", "mlp_adam_step_workspace_bytes", "mlp_grad", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "TD_STATS",
            "td_head", "td_head_workspace_bytes", "tie_", "TD3Learner", "TD3_STATS", "td3_head", "td3_head_workspace_bytes", "td3_smooth_actions",
            "SACLearner", "SAC_PI_STATS", "SAC_STATS", "SacHead", "SacPolicyGrad", "sac_head", "sac_head_workspace_bytes", "sac_policy_grad",

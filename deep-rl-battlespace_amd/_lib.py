@@ -13,6 +13,7 @@ BULLET_SLOTS = 12
 MAX_N = 16
 MLP_MAX_D = 64
 MAX_T = 65535
+NSTEP_MAX = 16
 ACTOR_F32, ACTOR_BF16X3, ACTOR_BF16X6 = 0, 1, 2
 F_AUTO_RESET = 1
 F_EMPTY_CALL = 2
@@ -70,6 +71,10 @@ class BsxReplaySource(ctypes.Structure):
 
 class BsxPrioTree(ctypes.Structure):
     _fields_ = [("leaves", c_void_p), ("nodes", c_void_p), ("max_priority", c_void_p), ("hyper", c_void_p), ("M", c_int64)]
+
+
+class BsxNstepCarry(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("obs", "act", "rew", "done", "env_done", "valid")]
 
 
 class BsxGaeIo(ctypes.Structure):
@@ -186,6 +191,11 @@ SIGNATURES = {
     "bsx_replay_prio_weights": (c_int, [ctypes.POINTER(BsxPrioTree), c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_replay_prio_update": (c_int, [ctypes.POINTER(BsxPrioTree), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "bsx_replay_prio_append": (c_int, [ctypes.POINTER(BsxPrioTree), c_void_p, c_void_p, c_int64, c_void_p]),
+    "bsx_replay_nstep_workspace_bytes": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_replay_nstep_fold": (c_int, [ctypes.POINTER(BsxReplaySource), ctypes.POINTER(BsxNstepCarry), c_int, c_int64, c_int, c_int, c_int, c_int,
+                                      ctypes.c_float, c_void_p, ctypes.POINTER(BsxReplaySource), c_void_p]),
+    "bsx_replay_nstep_carry": (c_int, [ctypes.POINTER(BsxReplaySource), ctypes.POINTER(BsxNstepCarry), c_int, c_int64, c_int, c_int, c_int, c_int,
+                                       c_void_p]),
     "bsx_gae_workspace_bytes": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_gae": (c_int, [ctypes.POINTER(BsxGaeIo), c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_gae_agents": (c_int, [ctypes.POINTER(BsxGaeIo), c_void_p, c_int, c_int64, c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p,

@@ -49,6 +49,9 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_replay.hip"), []),
            # the prioritised draw: integer sums and searches; its two powf (priority, weight) are held to float64, not to bits
            (os.path.join(CSRC, "bsx_replay_prio.hip"), []),
+           # the n-step fold ahead of an append: bit copies and one fmaf chain per (row, agent), every operation rounded on its own, as
+           # tests/nstep_util.py restates it
+           (os.path.join(CSRC, "bsx_replay_nstep.hip"), ["-ffp-contract=off"]),
            # GAE advantages: float32 operations each rounded on their own, as tests/gae_util.py restates them
            (os.path.join(CSRC, "bsx_advantage.hip"), ["-ffp-contract=off"]),
            # the PPO loss head: float32 element-wise terms held to a float64 reference, not to bits: contraction allowed

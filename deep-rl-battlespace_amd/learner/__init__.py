@@ -18,6 +18,9 @@ A SAC update:     as TD3's without its delay, the CURRENT actor and sac_sample_a
                   with logp'), both target critics and both critics -> sac_head -> bsx_mlp_grad of each critic, ONE mlp_adam_step of both with their
                   targets -> actor, sac_sample_actions (a ~ pi with logp, z) -> both stepped critics, sac_policy_seed -> bsx_mlp_grad of each critic
                   for grad_x -> sac_policy_grad (g_a4, g_log_std, log_alpha's step) -> bsx_mlp_grad, mlp_adam_step of the actor with log_std.
+n-step targets:   the three off-policy updates are unchanged on a ring filled through replay.NStepAppender (rows whose reward is the folded
+                  n-step sum and whose obs_next lies up to n ticks on): the learner wants gamma=app.bootstrap_gamma, the appender's gamma^n.
+                  SAC's target then carries the entropy term at the bootstrap state only.
 """
 from . import adam, ddpg, mlp
 from .adam import (ADAM_STATS, HYPER, AdamState, adam_hyper, adam_step, adam_step_workspace_bytes, is_tied, mlp_adam_step,  # noqa: F401

@@ -188,7 +188,9 @@ class DDPGLearner:
     mean), and directly after it, before the critic's step, the rows drawn get new priorities from |q - y| (`buffer.update_priorities`):
     six more launches per update at 2^20 rows (the weights; five of the priority update), inside the same graph; with a plain DeviceReplayBuffer every launch is as it was.
     A second critic, smoothed targets and a delayed actor step (TD3) are learner.TD3Learner's, a stochastic policy with a learned spread
-    and temperature (SAC) is learner.SACLearner's; parameter sharing is not here."""
+    and temperature (SAC) is learner.SACLearner's; parameter sharing is not here.  n-step targets need nothing here: fill the ring
+    through replay.NStepAppender (rows with the folded n-step reward and obs_next up to n ticks on) and give the learner
+    gamma=app.bootstrap_gamma, the appender's gamma^n; step 6 is then the n-step target."""
 
     def __init__(self, buffer, actor, critic=None, *, critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3, lr_critic=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=1):

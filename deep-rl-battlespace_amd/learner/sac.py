@@ -248,7 +248,9 @@ class SACLearner(DDPGLearner):
     learner owns `critic2`, `target_critic2`, their blobs, `adam_critic2`, `log_std`, `adam_log_std`, `log_alpha`, `adam_alpha`,
     `hyper_alpha`, `step_alpha` and `_noise_draws`; `stats` is f64 [updates, 8] in the order of SAC_STATS, `stats_pi` f64 [updates, 8] in
     the order of SAC_PI_STATS.  update(), capture() and sync() are DDPGLearner's over all of it; set_lr takes alpha= as well; publish also
-    copies log_std into a rollout that has one.  Parameter sharing and a policy delay are not here."""
+    copies log_std into a rollout that has one.  Parameter sharing and a policy delay are not here.  On a ring filled through
+    replay.NStepAppender the head's target is the n-step one when the learner is given gamma=app.bootstrap_gamma; it then carries the
+    entropy term -alpha logp' at the bootstrap state only, not at the n - 1 states the folded reward passes."""
 
     def __init__(self, buffer, actor, critic=None, critic2=None, *, log_std=None, alpha=0.2, lr_alpha=3e-4, target_entropy=None,
                  critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3, lr_critic=1e-3, betas=(0.9, 0.999), eps=1e-8,

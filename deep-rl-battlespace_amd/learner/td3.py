@@ -130,7 +130,8 @@ class TD3Learner(DDPGLearner):
     state the learner owns `target_critic2`, two more blobs, `adam_critic2` and `_noise_draws`; `stats` is f64 [updates, 8] in the order
     of TD3_STATS, `step_stats_critic` holds the joint step of both critics, and the rows of `step_stats_actor` of updates without an
     actor step stay as they were.  update(), capture(), set_lr(), sync() (six blobs) and publish() are DDPGLearner's.  Parameter
-    sharing is not here."""
+    sharing is not here.  On a ring filled through replay.NStepAppender the head's target is the n-step one when the learner is given
+    gamma=app.bootstrap_gamma."""
 
     def __init__(self, buffer, actor, critic=None, critic2=None, *, critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3,
                  lr_critic=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=2, policy_delay=2, target_noise=0.2,

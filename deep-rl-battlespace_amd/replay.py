@@ -334,3 +334,111 @@ class PrioritizedReplayBuffer(DeviceReplayBuffer):
                     or t.device != self._leaves.device:
                 raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {self._leaves.device}")
         self._prio("bsx_replay_prio_update", idx.data_ptr(), q.data_ptr(), y.data_ptr(), B, nA)
+
+
+class NStepAppender:
+    """n-step returns in front of a device ring (csrc/bsx_replay_nstep.hip; the contract is written out in include/battlespace_hip.h at
+    BsxNstepCarry): a rollout's records are folded on the device into rows (obs[t], act[t], sum_j gamma^j rew[t+j], obs[t+m], done) and
+    stored through the ring's own append, so a DeviceReplayBuffer or a PrioritizedReplayBuffer, and every learner on it, gain n-step
+    targets with no change of their own: give the learner `gamma=app.bootstrap_gamma`.
+
+        app = NStepAppender(buf, n=3, gamma=0.95, T=ro.T, E=env.n_envs)
+        stored = app.append_rollout(ro, range(nA))                   # device int64 [1], as buf.append_rollout returns
+        learner = DDPGLearner(buf, actor, gamma=app.bootstrap_gamma) # likewise TD3Learner, SACLearner
+        app.reset_carry(mask)                                        # after an env.reset(mask=...) of running games
+
+    A window ends early at a game's end (m < n ticks; every agent's done is then set, so that one scalar gamma^n is exact in the heads).
+    The last n - 1 ticks of a rollout have windows that run into the next one: they are CARRIED, not stored, and the next call completes
+    and stores them first.  Every tick therefore reaches the ring once, in tick order, whatever T cuts the run into; `carry_valid` (uint8
+    [E], 0 at first) says whose carried ticks count, so the first call stores T - n + 1 ticks of each running game.  A game that the host
+    re-spawns between two calls (`env.reset(mask=...)`) must have its carried ticks dropped: `reset_carry(mask)`; games that end and
+    re-spawn inside a rollout (auto_reset) need nothing.  n = 1 stores exactly what `buf.append_rollout` stores.
+    Asynchronous, capturable (`PolicyRollout.capture(then=lambda: app.append_rollout(ro, cols))`), nothing is allocated after
+    construction.  Two more launches than the plain append (fold, carry) plus the staging traffic: profiles/nstep_append.json."""
+
+    def __init__(self, buf, n, gamma, T, E):
+        if not isinstance(buf, DeviceReplayBuffer):
+            raise ValueError("NStepAppender needs a DeviceReplayBuffer or a PrioritizedReplayBuffer")
+        n, T, E, gamma = int(n), int(T), int(E), float(gamma)
+        _lib = buf._lib
+        if not (1 <= n <= _lib.NSTEP_MAX and n <= T <= _lib.MAX_T and E >= 1 and T * E < 2 ** 31):
+            raise ValueError(f"NStepAppender takes 1 <= n <= {_lib.NSTEP_MAX}, n <= T <= {_lib.MAX_T}, E >= 1 and T * E < 2^31")
+        if not 0.0 <= gamma <= 1.0:                      # (a NaN fails both comparisons)
+            raise ValueError("gamma must lie in [0, 1]")
+        self.buf, self.n_step, self.gamma, self.T, self.E = buf, n, gamma, T, E
+        g = torch.ones((), dtype=torch.float32)
+        for _ in range(n):                               # g_n of the kernel's chain: float32 products, one rounding each
+            g = g * torch.tensor(gamma, dtype=torch.float32)
+        self.bootstrap_gamma = float(g)
+        nA, D, k, dev = buf.n_agents, buf.actor_states.shape[2], buf.n_actions, buf.actor_states.device
+        c = n - 1
+        self._c_obs = torch.zeros((c, E, nA, D), dtype=torch.float32, device=dev)
+        self._c_act = torch.zeros((c, E, nA, k), dtype=torch.float32, device=dev)
+        self._c_rew = torch.zeros((c, E, nA), dtype=torch.float32, device=dev)
+        self._c_done = torch.zeros((c, E, nA), dtype=torch.uint8, device=dev)
+        self._c_env_done = torch.zeros((c, E), dtype=torch.uint8, device=dev)
+        self.carry_valid = torch.zeros(E, dtype=torch.uint8, device=dev)
+        need = _lib.query_bytes("bsx_replay_nstep_workspace_bytes", T, E, nA, D, k, n)
+        self._staging = torch.empty((need + 3) // 4, dtype=torch.int32, device=dev)
+        self._folded = _lib.BsxReplaySource()
+        self._bind()
+        # the ring's own append workspace for T * E rows, now: nothing is allocated once rollouts are flowing (or being captured)
+        need = _lib.query_bytes("bsx_replay_workspace_bytes", T * E)
+        if buf._workspaces[-1].numel() * 8 < need:
+            buf._workspaces.append(torch.empty((need + 7) // 8, dtype=torch.int64, device=dev))
+
+    def _bind(self):
+        """The carry's addresses as the C entry points take them (n = 1: the empty tensors are passed as NULL)."""
+        ptr = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731
+        self._carry = self.buf._lib.BsxNstepCarry(ptr(self._c_obs), ptr(self._c_act), ptr(self._c_rew), ptr(self._c_done), ptr(self._c_env_done),
+                                                  self.carry_valid.data_ptr())
+
+    def reset_carry(self, mask=None):
+        """Drop the carried ticks of the games in `mask` (bool [E], on the device; None = every game): they are not stored, and the next
+        call starts those games' windows at its own first tick.  Asynchronous (a device fill)."""
+        if mask is None:
+            self.carry_valid.zero_()
+            return
+        mask = torch.as_tensor(mask, device=self.carry_valid.device)
+        if mask.dtype != torch.bool or tuple(mask.shape) != (self.E,):
+            raise ValueError("mask must be a bool tensor of shape [E]")
+        self.carry_valid.masked_fill_(mask, 0)
+
+    def append(self, obs, act, rew, done, env_done, columns):
+        """The fold and the store of one rollout-shaped record: obs float32 [T + 1, E, A, D], act float32 [T, E, A, >= n_actions] (the
+        first n_actions of each row are stored), rew float32 [T, E, A], done uint8 / bool [T, E, A] (the agent's flag after tick t),
+        env_done uint8 / bool [T + 1, E] (the game's flag BEFORE tick t), all contiguous and on the ring's device; `columns`: this team's
+        columns of the A axis, a contiguous range.  Returns the device int64 [1] of rows stored (overwritten by the next append)."""
+        import ctypes
+        buf, lib, T, E, n = self.buf, self.buf._lib.load(), self.T, self.E, self.n_step
+        nA, D, k, dev = buf.n_agents, buf.actor_states.shape[2], buf.n_actions, buf.actor_states.device
+        if obs.dim() != 4 or tuple(obs.shape[:2]) != (T + 1, E) or obs.shape[3] != D or obs.device != dev:
+            raise ValueError(f"the record's observations must be [T + 1, E, A, D] = [{T + 1}, {E}, A, {D}] on {dev}: this appender was built "
+                             f"for that rollout length, game count, observation width and device")
+        A = obs.shape[2]
+        byte = (torch.uint8, torch.bool)
+        for t, name, shape, dtypes in ((obs, "obs", (T + 1, E, A, D), (torch.float32,)), (act, "act", (T, E, A, act.shape[-1]), (torch.float32,)),
+                                       (rew, "rew", (T, E, A), (torch.float32,)), (done, "done", (T, E, A), byte),
+                                       (env_done, "env_done", (T + 1, E), byte)):
+            if tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{name} must be a contiguous {dtypes[0]} tensor of shape {shape} on {dev}")
+        Ka = act.shape[-1]
+        cols = [int(c) for c in columns]
+        c0 = cols[0] if cols else 0
+        if len(cols) != nA or cols != list(range(c0, c0 + len(cols))) or c0 < 0 or c0 + len(cols) > A or Ka < k:
+            raise ValueError("columns must be a contiguous range of len(agent_list) columns, act rows at least n_actions wide")
+        src = buf._lib.BsxReplaySource(obs.data_ptr() + 4 * c0 * D, A * D, D, None, 0, 0, act.data_ptr() + 4 * Ka * c0, A * Ka, Ka,
+                                       rew.data_ptr() + 4 * c0, A, 1, done.data_ptr() + c0, A, 1, env_done.data_ptr(), 1)
+        stream = buf._stream()
+        buf._lib.check(lib.bsx_replay_nstep_fold(ctypes.byref(src), ctypes.byref(self._carry), T, E, nA, D, k, n, self.gamma,
+                                                 self._staging.data_ptr(), ctypes.byref(self._folded), stream), "bsx_replay_nstep_fold")
+        stored = buf._append(self._folded, T * E)
+        buf._lib.check(lib.bsx_replay_nstep_carry(ctypes.byref(src), ctypes.byref(self._carry), T, E, nA, D, k, n, stream),
+                       "bsx_replay_nstep_carry")
+        return stored
+
+    def append_rollout(self, rollout, columns):
+        """`append` on a PolicyRollout's own tensors, read in place."""
+        if rollout.T != self.T:
+            raise ValueError(f"this appender was built for rollouts of T = {self.T} ticks")
+        return self.append(rollout.obs, rollout.scores, rollout.rew, rollout._done, rollout.env_done, columns)

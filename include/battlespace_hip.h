@@ -442,6 +442,64 @@ int bsx_replay_prio_update(const BsxPrioTree* tree, const int64_t* idx, const fl
  * one or two contiguous runs: one wave per touched node.  Launches: leaves, one per level of more than 64 nodes, the top. */
 int bsx_replay_prio_append(const BsxPrioTree* tree, const int64_t* counter, const int64_t* stored, int64_t rows, void* stream);
 
+/* ---- n-step returns for that ring, folded across rollouts (csrc/bsx_replay_nstep.hip, replay.NStepAppender): a rollout's records are
+ * folded on the device into a dense source of rows (obs[t], act[t], sum_j gamma^j rew[t+j], obs[t+m], done) that bsx_replay_append
+ * stores as it stores any source.  A head given gamma^n then computes the n-step target: no ring, tree or head kernel changes.
+ *
+ * The record is a BsxReplaySource read as a rollout of T ticks over E games, source row r = t*E + e: obs covers T + 1 ticks (row T*E + e
+ * is the observation after the last tick), act / rew / done cover T ticks, skip covers T + 1 ticks and is the game's env_done flag BEFORE
+ * tick t (row T: after the last tick; it must not be NULL here); obs_next is not read.  For a PolicyRollout in place: the pointers and
+ * strides of bsx_replay_append's first layout.
+ *
+ * The carry holds the previous call's last n - 1 ticks, dense: row j*E + e for carried tick j.  `valid` is one byte per game: 0 = the
+ * game's carried ticks are not transitions (nothing was carried yet, or the host re-spawned the game since).  With n = 1 the carry is
+ * empty and only `valid` is touched.
+ *
+ * Timeline.  Ticks u = 0 .. n-2 are the carry's, u = n-1 .. n-2+T the record's ticks 0 .. T-1; before(u, e) is the env_done flag before
+ * tick u, after(u, e) = before(u + 1, e) (for the carry's last tick: the record's row 0; for the record's last: its row T).  A call emits
+ * the T ticks u = 0 .. T-1 as rows u*E + e, in that order whatever happened inside the rollout: its last n - 1 ticks are never emitted
+ * by it, they become the next carry.  A run cut into rollouts therefore reaches the ring as the same rows in the same order as the
+ * uncut run.  Per emitted (u, e):
+ *   skip   = 1 if before(u, e) != 0, or if u < n - 1 and valid[e] == 0; else 0
+ *   m      = the smallest j + 1 in 1 .. n with after(u + j, e) != 0; n if there is none
+ *   per agent i, float32, every operation rounded on its own (an explicit fmaf, no contraction):
+ *            g_0 = 1, g_{j+1} = g_j * gamma;  R = rew[u], dead = done[u] != 0;
+ *            for j = 1 .. m-1:  if (!dead) R = fmaf(g_j, rew[u + j], R);  then dead |= done[u + j] != 0
+ *            (the reward of the tick on which an agent goes down is counted, later ones are not)
+ *   rew    = R;  done = dead, and 1 for every agent when m < n (the game ended inside the window: one scalar gamma^n stays exact)
+ *   obs, act = those of tick u (act: the first k of each column's words);  obs_next = obs[u + m], the observation after tick u + m - 1
+ * Bits are copied, never converted; done and skip bytes are written as 0 / 1.  With n = 1 the folded source holds the record's own rows.
+ * Ranges: 1 <= n <= BSX_NSTEP_MAX, n <= T <= BSX_MAX_T, 1 <= E, T*E < 2^31, nA / D / k as the ring's nA / D / n_act, gamma in [0, 1]. */
+#define BSX_NSTEP_MAX 16
+typedef struct BsxNstepCarry {
+    float* obs;              /* float32 [n-1][E][nA][D] */
+    float* act;              /* float32 [n-1][E][nA][k] */
+    float* rew;              /* float32 [n-1][E][nA] */
+    uint8_t* done;           /* uint8 [n-1][E][nA], 0 / 1 */
+    uint8_t* env_done;       /* uint8 [n-1][E]: the flag before each carried tick, 0 / 1 */
+    uint8_t* valid;          /* uint8 [E] (carry_valid) */
+} BsxNstepCarry;
+
+/* Size of the staging workspace of one fold: T*E*nA*(4*(2*D + k + 1) + 1) + T*E bytes -- obs, obs_next [T*E][nA][D], act [T*E][nA][k],
+ * rew [T*E][nA] (float32), then done [T*E][nA] and skip [T*E] (uint8), in that order.  BSX_E_ARG for a size out of range or bytes NULL. */
+int bsx_replay_nstep_workspace_bytes(int T, int64_t E, int nA, int D, int k, int n, size_t* bytes);
+
+/* The fold: ONE launch, a workgroup per 256 emitted rows (a thread per row for m and skip, a thread per (row, agent) for rew and done,
+ * then the tile's obs / obs_next / act words walked flat: consecutive lanes load and store consecutive words).  It reads the record and
+ * the carry and writes the workspace only.  `folded` (host memory) receives the dense source inside the workspace: hand it to
+ * bsx_replay_append with rows = T*E.  The workspace must stay untouched until that append has run.
+ * Refusals, before any launch, in this order.  BSX_E_ARG: a size out of range; rollout or carry NULL; a NULL obs / act / rew / done /
+ * skip of the record; a NULL valid; with n > 1 a NULL field of the carry; a negative stride; gamma outside [0, 1] or NaN; workspace or
+ * folded NULL.  BSX_E_ALIGN: the record's or the carry's obs / act / rew, or the workspace, off a 4-byte boundary. */
+int bsx_replay_nstep_fold(const BsxReplaySource* rollout, const BsxNstepCarry* carry, int T, int64_t E, int nA, int D, int k, int n,
+                          float gamma, void* workspace, BsxReplaySource* folded, void* stream);
+
+/* After the fold of the same record: its last n - 1 ticks (obs, act, rew, done, and skip's flags before them) become the carry and valid[e]
+ * = 1 for every game.  ONE launch, which reads the record and writes the carry: no launch both reads and overwrites carry words.
+ * Refusals as the fold's, less gamma, workspace and folded. */
+int bsx_replay_nstep_carry(const BsxReplaySource* rollout, const BsxNstepCarry* carry, int T, int64_t E, int nA, int D, int k, int n,
+                           void* stream);
+
 /* ---- GAE(gamma, lambda) advantages and returns on device (deep-rl-battlespace_amd/advantage.py): what a PPO update needs from a
  * rollout's records, computed with no host round trip so that it can sit in the rollout's captured graph.
  *
