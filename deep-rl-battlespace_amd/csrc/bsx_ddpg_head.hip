@@ -6,27 +6,22 @@
 //   own      obs[b][i] (+) a[b][i]                                     Dc = Do + k
 //   central  obs[b][0] .. obs[b][nA-1] (+) a[b][0] .. a[b][nA-1]       Dc = nA (Do + k): the same row for every agent i of b
 //   1. inputs       one thread per float of x_cur: the batch's part of x_cur, x_next and x_pi, one launch;
-//   2. put_actions  one thread per (row, action slot): a 16-byte load of y4, k dword stores;
-//   3. td_head      one thread per element and tile of 256, J consecutive tiles per workgroup; the float32 terms of the statistics are
-//                   added in float64 per thread, then across the workgroup in a fixed order (bsx_block_sum.h), and stored to the
-//                   workspace; ONE workgroup adds the workgroups' partial rows in a fixed order and writes stats;
+//   2. put_actions  one thread per (row, action slot): a 16-byte load of y4, k dword stores where bsx_ddpg_shared.h's action_slot says;
+//   3. td_head      the shared head pass (bsx_ddpg_shared.h: td_head_pass) with ONE critic: the kernel here hands it its argument, the
+//                   entry its own pointer lists; the plan, the sums, the merge and the rest of the entry are the header's;
 //   4. action_grad  one thread per row: k dword loads of grad_x, a 16-byte store of g_a4.
 // Rows of 9, 24 or 45 floats are not 16-byte aligned: the critic inputs and grad_x are read and written by the dword; the 16-byte
 // accesses are those of the [..][4] tensors.  Every index is 64-bit: there is one path whatever the size.  No floating-point atomics,
 // no flags or spins; every grid is a function of the sizes alone: the same inputs give the same bits on every call.
 
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 
 #include "battlespace_hip.h"
 #include "bsx_args.h"
-#include "bsx_block_sum.h"
-#include "bsx_ddpg_shared.h"         // TPB, the checked shape, the head's launch plan and the one-workgroup merge (shared with bsx_td3_head.hip)
+#include "bsx_ddpg_shared.h"         // TPB, the checked shape, action_slot, the head pass with its plan, merge and entry helpers
 
 namespace {
-
-constexpr int NS = 6;                          // a partial row: 0 | w d^2 | q | y | |d| | done | w | 0
 
 __global__ __launch_bounds__(TPB) void bsx_ddpg_inputs_kernel(const BsxDdpgBatch batch, const Shape s, float* x_cur, float* x_next, float* x_pi) {
     const int64_t M = s.B * s.nA * s.Dc, stride = int64_t(gridDim.x) * TPB;
@@ -58,11 +53,7 @@ __global__ __launch_bounds__(TPB) void bsx_ddpg_put_actions_kernel(const float* 
         const int64_t r = e / S, b = r / s.nA;
         const int i = int(r - b * s.nA), slot = every_slot ? int(e - r * S) : i;
         const F4 a = y[s.central ? b * s.nA + slot : r];
-        float* dst = x + r * s.Dc + s.W + (s.central ? slot * s.k : 0);
-        dst[0] = a[0];
-        dst[1] = a[1];
-        dst[2] = a[2];
-        if (s.k == 4) dst[3] = a[3];
+        store_row(action_slot(s, x, b, slot, r, false).dst, s.k, a[0], a[1], a[2], a[3]);      // one row per thread
     }
 }
 
@@ -91,43 +82,9 @@ struct HeadArgs {
 
 template <int WEIGHT>                          // 1: io.weight is given
 __global__ __launch_bounds__(TPB) void bsx_td_head_kernel(const HeadArgs p) {
-    __shared__ double s_w[NS][WAVES];
-    const int tid = threadIdx.x;
-    double acc[NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    F4* gq4 = reinterpret_cast<F4*>(p.io.g_q);
-    F4* gpi4 = reinterpret_cast<F4*>(p.io.g_pi);
-    const int64_t tile0 = int64_t(blockIdx.x) * p.J;
-    for (int j = 0; j < p.J; ++j) {
-        const int64_t tile = tile0 + j, i = tile * TPB + tid;
-        if (tile >= p.tiles || i >= p.M) continue;
-        const float q = p.io.q[i], rew = p.io.rew[i];
-        const bool over = p.io.done[i] != 0;
-        const float qn = over ? 0.0f : p.io.q_next[i];             // select, never multiply: a finished row's q_next stays out, NaN included
-        const float w = WEIGHT ? p.io.weight[i] : 1.0f;
-        const float y = fmaf(p.gamma, qn, rew);
-        const float d = q - y, wd = w * d;
-        F4 gq = F4(0.0f), gp = F4(0.0f);
-        gq[0] = wd * p.s2;
-        gp[0] = -(w * p.s1);
-        gq4[i] = gq;
-        gpi4[i] = gp;
-        if (p.io.td) p.io.td[i] = y;
-        acc[0] += double(wd * d);
-        acc[1] += double(q);
-        acc[2] += double(y);
-        acc[3] += double(fabsf(d));
-        acc[4] += over ? 1.0 : 0.0;
-        acc[5] += double(w);
-    }
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
-    if (tid < STAT_COLS) {
-        double t = 0.0;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
-        p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
-    }
+    const BsxTdIo& io = p.io;
+    td_head_pass<HEAD_ONE, WEIGHT>(HeadView{io.q, nullptr, io.q_next, nullptr, nullptr, nullptr, io.rew, io.done, io.weight, io.g_q, nullptr, io.g_pi,
+                                            io.td, p.M, p.tiles, p.J, 0, p.gamma, p.s1, p.s2, p.part});
 }
 
 }  // namespace
@@ -167,28 +124,15 @@ int bsx_ddpg_action_grad(const float* gx, int64_t B, int nA, int Do, int k, int 
     return int(hipGetLastError());
 }
 
-int bsx_td_head_workspace_bytes(int64_t B, int nA, size_t* bytes) {
-    if (!bytes || !td_shape(B, nA)) return BSX_E_ARG;
-    *bytes = size_t(plan_of(B, nA).blocks) * STAT_COLS * 8;
-    return 0;
-}
+int bsx_td_head_workspace_bytes(int64_t B, int nA, size_t* bytes) { return head_workspace_bytes(B, nA, bytes); }
 
 int bsx_td_head(const BsxTdIo* io, int64_t B, int nA, float gamma, void* workspace, double* stats, void* stream) {
-    if (!io || !io->q || !io->q_next || !io->rew || !io->done || !io->g_q || !io->g_pi || !workspace || !stats) return BSX_E_ARG;
-    if (!(gamma >= 0.0f && gamma <= 1.0f)) return BSX_E_ARG;                   // NaN too
-    if (!td_shape(B, nA)) return BSX_E_ARG;
+    if (!io || !io->q || !io->q_next || !io->rew || !io->done || !io->g_q || !io->g_pi) return BSX_E_ARG;
+    if (!head_ranges(gamma, B, nA, workspace, stats)) return BSX_E_ARG;
     if (!aligned(io->g_q, 16) || !aligned(io->g_pi, 16)) return BSX_E_ALIGN;
     if (!aligned(io->q, 4) || !aligned(io->q_next, 4) || !aligned(io->rew, 4) || !aligned(io->weight, 4) || !aligned(io->td, 4)) return BSX_E_ALIGN;
-    if (!aligned(workspace, 8) || !aligned(stats, 8)) return BSX_E_ALIGN;
-    const Plan p = plan_of(B, nA);
-    double* part = static_cast<double*>(workspace);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const HeadArgs a{*io, p.M, p.tiles, p.J, gamma, float(1.0 / double(B)), float(2.0 / double(B)), part};
-    if (io->weight) hipLaunchKernelGGL(bsx_td_head_kernel<1>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
-    else hipLaunchKernelGGL(bsx_td_head_kernel<0>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
-    if (const hipError_t e = hipGetLastError()) return int(e);
-    hipLaunchKernelGGL(bsx_td_merge_kernel<false>, dim3(1), dim3(MERGE_TPB), 0, s, static_cast<const double*>(part), p.blocks, p.M, stats);
-    return int(hipGetLastError());
+    const HeadArgs a{*io, 0, 0, 0, gamma, float(1.0 / double(B)), float(2.0 / double(B)), nullptr};
+    return launch_head<false>(bsx_td_head_kernel<1>, bsx_td_head_kernel<0>, io->weight != nullptr, a, B, nA, workspace, stats, stream);
 }
 
 }  // extern "C"

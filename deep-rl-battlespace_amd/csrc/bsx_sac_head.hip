@@ -3,9 +3,10 @@
 //   1. sample_actions  the reparameterised draw of the project's Gaussian policy (bsx_actor_core.h, finish_row<true>): a = mu + exp(log_std) z
 //                      into the action columns of a critic input, where bsx_ddpg_put_actions(own_only) writes, and its log-probability.
 //                      One thread per (b, j): ONE draw (normals4 under SAC_SALT, or the injected row), a 16-byte load of y4, three dword
-//                      stores per row written;
-//   2. sac_head        bsx_td3_head with the entropy term in the target: y = r + gamma (1 - done) (min(Q1', Q2') - alpha logp').  Its
-//                      launch plan, sums and merge (bsx_ddpg_shared.h);
+//                      stores per row written (bsx_ddpg_shared.h: action_slot);
+//   2. sac_head        bsx_td3_head with the entropy term in the target: y = r + gamma (1 - done) (min(Q1', Q2') - alpha logp'), and
+//                      written as that: the shared head pass (bsx_ddpg_shared.h: td_head_pass) of kind HEAD_SOFT -- one fmaf more than
+//                      HEAD_TWIN, no g_pi -- with the header's plan, sums, merge and entry helpers;
 //   3. policy_seed     the seeds of the two critics' input-gradient passes on x_pi: -(w / B) at the smaller critic, +0 at the other;
 //   4. policy_grad     the actor's grad_out from both critics' input gradients, log_std's and log_alpha's gradients and the policy's
 //                      statistics.  A tile is S = (256 / nA) nA elements, so a thread keeps its agent over its J tiles; the float32 terms
@@ -29,7 +30,6 @@
 namespace {
 
 constexpr uint32_t SAC_SALT = BSX_SAC_SALT;    // distinct from the five in use: 0x00000000, 0x80000000, 0x40000000, 0xC0000000, 0x20000000
-constexpr int NS = 7;                          // the head's partial row: bsx_td3_head's
 constexpr int NP = 6;                          // policy_grad's: 0 | w (alpha logp - m) | m | logp | alpha | w | picked 1 | 0 | per agent [nA][AG]
 constexpr int AG = 5;                          // per agent: g_a (sigma z) for the three columns | w s1 | (w s1) (logp + target_entropy)
 constexpr int LS_PARTS_MAX = 8;
@@ -69,14 +69,7 @@ __global__ __launch_bounds__(TPB) void bsx_sac_sample_kernel(const SampleArgs p,
         p.logp[r] = q - 3.0f * bsx_actor::HALF_LOG_2PI;
         if (zo) zo[r] = F4{z[0], z[1], z[2], 0.0f};
         // central without own_only: slot j of every row (b, i); central with it: slot j of row (b, j); own: the row's own columns
-        const bool every = s.central && !p.own_only;
-        const int rows = every ? s.nA : 1;
-        float* dst = p.x + (every ? b * s.nA : r) * s.Dc + s.W + (s.central ? j * s.k : 0);
-        for (int i = 0; i < rows; ++i, dst += s.Dc) {
-            dst[0] = a0;
-            dst[1] = a1;
-            dst[2] = a2;
-        }
+        store_actions(action_slot(s, p.x, b, j, r, s.central && !p.own_only), s.Dc, 3, a0, a1, a2, 0.0f);
     }
 }
 
@@ -90,49 +83,9 @@ struct HeadArgs {
 
 template <int WEIGHT>                          // 1: io.weight is given
 __global__ __launch_bounds__(TPB) void bsx_sac_head_kernel(const HeadArgs p) {
-    __shared__ double s_w[NS][WAVES];
-    const int tid = threadIdx.x;
-    double acc[NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    F4* gq14 = reinterpret_cast<F4*>(p.io.g_q1);
-    F4* gq24 = reinterpret_cast<F4*>(p.io.g_q2);
-    const int64_t tile0 = int64_t(blockIdx.x) * p.J;
-    for (int j = 0; j < p.J; ++j) {
-        const int64_t tile = tile0 + j, i = tile * TPB + tid;
-        if (tile >= p.tiles || i >= p.M) continue;
-        const float q = p.io.q1[i], q2 = p.io.q2[i], rew = p.io.rew[i];
-        const float n1 = p.io.q1_next[i], n2 = p.io.q2_next[i];
-        const bool over = p.io.done[i] != 0;
-        const float alpha = expf(p.io.log_alpha[i % p.nA]);
-        const float m = (n1 < n2 || n1 != n1) ? n1 : n2;           // np.minimum's rule: a NaN in either is a NaN
-        const float v = fmaf(-alpha, p.io.logp_next[i], m);        // the soft value of the next state
-        const float qn = over ? 0.0f : v;                          // select, never multiply: a finished row keeps m and logp_next out, NaN included
-        const float w = WEIGHT ? p.io.weight[i] : 1.0f;
-        const float y = fmaf(p.gamma, qn, rew);
-        const float d = q - y, wd = w * d;
-        const float d2 = q2 - y, wd2 = w * d2;
-        F4 gq = F4(0.0f), gq2 = F4(0.0f);
-        gq[0] = wd * p.s2;
-        gq2[0] = wd2 * p.s2;
-        gq14[i] = gq;
-        gq24[i] = gq2;
-        if (p.io.td) p.io.td[i] = y;
-        acc[0] += double(wd * d) + double(wd2 * d2);
-        acc[1] += double(q);
-        acc[2] += double(y);
-        acc[3] += double(fabsf(d));
-        acc[4] += over ? 1.0 : 0.0;
-        acc[5] += double(w);
-        acc[6] += double(fabsf(q - q2));
-    }
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
-    if (tid < STAT_COLS) {
-        double t = 0.0;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
-        p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
-    }
+    const BsxSacIo& io = p.io;
+    td_head_pass<HEAD_SOFT, WEIGHT>(HeadView{io.q1, io.q2, io.q1_next, io.q2_next, io.logp_next, io.log_alpha, io.rew, io.done, io.weight, io.g_q1,
+                                             io.g_q2, nullptr, io.td, p.M, p.tiles, p.J, p.nA, p.gamma, 0.0f, p.s2, p.part});
 }
 
 __global__ __launch_bounds__(TPB) void bsx_sac_seed_kernel(const float* q1, const float* q2, const float* weight, int64_t M, float s1, float* g_pi1,
@@ -325,32 +278,19 @@ int bsx_sac_sample_actions(const float* y4, const float* log_std, int64_t B, int
     return int(hipGetLastError());
 }
 
-int bsx_sac_head_workspace_bytes(int64_t B, int nA, size_t* bytes) {
-    if (!bytes || !td_shape(B, nA)) return BSX_E_ARG;
-    *bytes = size_t(plan_of(B, nA).blocks) * STAT_COLS * 8;
-    return 0;
-}
+int bsx_sac_head_workspace_bytes(int64_t B, int nA, size_t* bytes) { return head_workspace_bytes(B, nA, bytes); }
 
 int bsx_sac_head(const BsxSacIo* io, int64_t B, int nA, float gamma, void* workspace, double* stats, void* stream) {
     if (!io || !io->q1 || !io->q2 || !io->q1_next || !io->q2_next || !io->logp_next || !io->rew || !io->done || !io->log_alpha || !io->g_q1 ||
-        !io->g_q2 || !workspace || !stats)
+        !io->g_q2)
         return BSX_E_ARG;
-    if (!(gamma >= 0.0f && gamma <= 1.0f)) return BSX_E_ARG;                   // NaN too
-    if (!td_shape(B, nA)) return BSX_E_ARG;
+    if (!head_ranges(gamma, B, nA, workspace, stats)) return BSX_E_ARG;
     if (!aligned(io->g_q1, 16) || !aligned(io->g_q2, 16)) return BSX_E_ALIGN;
     if (!aligned(io->q1, 4) || !aligned(io->q2, 4) || !aligned(io->q1_next, 4) || !aligned(io->q2_next, 4) || !aligned(io->logp_next, 4) ||
         !aligned(io->rew, 4) || !aligned(io->weight, 4) || !aligned(io->log_alpha, 4) || !aligned(io->td, 4))
         return BSX_E_ALIGN;
-    if (!aligned(workspace, 8) || !aligned(stats, 8)) return BSX_E_ALIGN;
-    const Plan p = plan_of(B, nA);
-    double* part = static_cast<double*>(workspace);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const HeadArgs a{*io, p.M, p.tiles, p.J, nA, gamma, float(2.0 / double(B)), part};
-    if (io->weight) hipLaunchKernelGGL(bsx_sac_head_kernel<1>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
-    else hipLaunchKernelGGL(bsx_sac_head_kernel<0>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
-    if (const hipError_t e = hipGetLastError()) return int(e);
-    hipLaunchKernelGGL(bsx_td_merge_kernel<true>, dim3(1), dim3(MERGE_TPB), 0, s, static_cast<const double*>(part), p.blocks, p.M, stats);
-    return int(hipGetLastError());
+    const HeadArgs a{*io, 0, 0, 0, nA, gamma, float(2.0 / double(B)), nullptr};
+    return launch_head<true>(bsx_sac_head_kernel<1>, bsx_sac_head_kernel<0>, io->weight != nullptr, a, B, nA, workspace, stats, stream);
 }
 
 int bsx_sac_policy_seed(const float* q1_pi, const float* q2_pi, const float* weight, int64_t B, int nA, float* g_pi1, float* g_pi2, void* stream) {

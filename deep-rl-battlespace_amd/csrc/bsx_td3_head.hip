@@ -3,29 +3,27 @@
 //   1. smooth_actions  target policy smoothing: a' = clamp(y4 + clamp(sigma z, -clip, clip), -1, 1) into the action columns of x_next,
 //                      the slots bsx_ddpg_put_actions(own_only = 0) writes.  One thread per (b, j): ONE draw (normals4 under TD3_SALT, or
 //                      the injected row), a 16-byte load of y4, then k dword stores into agent j's slot of each of the nA rows of b
-//                      (central), or of its own row -- the noise is keyed by (b, j), so the rows of b hold the same bits;
+//                      (central), or of its own row (bsx_ddpg_shared.h: action_slot) -- the noise is keyed by (b, j), so the rows of b
+//                      hold the same bits;
 //   2. td3_head        clipped double-Q: y from the smaller of two target critics, both critics' grad_out, the actor's seed through
-//                      critic 1.  bsx_td_head's launch plan, sums and merge (bsx_ddpg_shared.h): one thread per element and tile of 256,
-//                      J consecutive tiles per workgroup, float64 per thread, a fixed order across the workgroup, ONE workgroup merges.
+//                      critic 1.  It is bsx_td_head with two critics, and written as that: the shared head pass (bsx_ddpg_shared.h:
+//                      td_head_pass) of kind HEAD_TWIN, with the header's plan, sums, merge and entry helpers.
 // Built with -ffp-contract=off: every operation of the smoothing is one float32 rounding (tests/td3_util.py restates it in numpy), and
 // the head's one multiply-add is an explicit fmaf; normals4 pins its own contraction mode.  Every index is 64-bit: there is one path
 // whatever the size.  No floating-point atomics, no flags or spins; every grid is a function of the sizes alone.
 
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 
 #include "battlespace_hip.h"
 #include "bsx_actor_core.h"          // normals4: the project's pinned Box-Muller draw
 #include "bsx_args.h"
-#include "bsx_block_sum.h"
 #include "bsx_ddpg_shared.h"
 
 namespace {
 
 // distinct from the four in use (bsx_actor_core.h): 0x00000000, 0x80000000, 0x40000000 and GAUSS_SALT = 0xC0000000
 constexpr uint32_t TD3_SALT = 0x20000000u;
-constexpr int NS = 7;                          // a partial row: 0 | w (d1^2 + d2^2) | q1 | y | |d1| | done | w | |q1 - q2|
 
 struct SmoothArgs {
     const float* y4;
@@ -60,14 +58,8 @@ __global__ __launch_bounds__(TPB) void bsx_td3_smooth_kernel(const SmoothArgs p,
             const float n = clampf(p.sigma * z[c], -p.clip, p.clip);
             out[c] = clampf(a[c] + n, -1.0f, 1.0f);
         }
-        const int rows = s.central ? s.nA : 1;                 // central: slot j of every row (b, i); own: the row's own columns
-        float* dst = p.x + (s.central ? b * s.nA : r) * s.Dc + s.W + (s.central ? j * s.k : 0);
-        for (int i = 0; i < rows; ++i, dst += s.Dc) {
-            dst[0] = out[0];
-            dst[1] = out[1];
-            dst[2] = out[2];
-            if (s.k == 4) dst[3] = out[3];
-        }
+        // central: slot j of every row (b, i); own: the row's own columns
+        store_actions(action_slot(s, p.x, b, j, r, s.central), s.Dc, s.k, out[0], out[1], out[2], out[3]);
     }
 }
 
@@ -81,50 +73,9 @@ struct HeadArgs {
 
 template <int WEIGHT>                          // 1: io.weight is given
 __global__ __launch_bounds__(TPB) void bsx_td3_head_kernel(const HeadArgs p) {
-    __shared__ double s_w[NS][WAVES];
-    const int tid = threadIdx.x;
-    double acc[NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    F4* gq14 = reinterpret_cast<F4*>(p.io.g_q1);
-    F4* gq24 = reinterpret_cast<F4*>(p.io.g_q2);
-    F4* gpi4 = reinterpret_cast<F4*>(p.io.g_pi);
-    const int64_t tile0 = int64_t(blockIdx.x) * p.J;
-    for (int j = 0; j < p.J; ++j) {
-        const int64_t tile = tile0 + j, i = tile * TPB + tid;
-        if (tile >= p.tiles || i >= p.M) continue;
-        const float q = p.io.q1[i], q2 = p.io.q2[i], rew = p.io.rew[i];
-        const float n1 = p.io.q1_next[i], n2 = p.io.q2_next[i];
-        const bool over = p.io.done[i] != 0;
-        const float m = (n1 < n2 || n1 != n1) ? n1 : n2;           // np.minimum's rule: a NaN in either is a NaN (fminf would drop it)
-        const float qn = over ? 0.0f : m;                          // select, never multiply: a finished row's q_next stay out, NaN included
-        const float w = WEIGHT ? p.io.weight[i] : 1.0f;
-        const float y = fmaf(p.gamma, qn, rew);
-        const float d = q - y, wd = w * d;
-        const float d2 = q2 - y, wd2 = w * d2;
-        F4 gq = F4(0.0f), gq2 = F4(0.0f), gp = F4(0.0f);
-        gq[0] = wd * p.s2;
-        gq2[0] = wd2 * p.s2;
-        gp[0] = -(w * p.s1);
-        gq14[i] = gq;
-        gq24[i] = gq2;
-        gpi4[i] = gp;
-        if (p.io.td) p.io.td[i] = y;
-        acc[0] += double(wd * d) + double(wd2 * d2);
-        acc[1] += double(q);
-        acc[2] += double(y);
-        acc[3] += double(fabsf(d));
-        acc[4] += over ? 1.0 : 0.0;
-        acc[5] += double(w);
-        acc[6] += double(fabsf(q - q2));
-    }
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
-    if (tid < STAT_COLS) {
-        double t = 0.0;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
-        p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
-    }
+    const BsxTd3Io& io = p.io;
+    td_head_pass<HEAD_TWIN, WEIGHT>(HeadView{io.q1, io.q2, io.q1_next, io.q2_next, nullptr, nullptr, io.rew, io.done, io.weight, io.g_q1, io.g_q2,
+                                             io.g_pi, io.td, p.M, p.tiles, p.J, 0, p.gamma, p.s1, p.s2, p.part});
 }
 
 }  // namespace
@@ -143,32 +94,17 @@ int bsx_td3_smooth_actions(const float* y4, int64_t B, int nA, int Do, int k, in
     return int(hipGetLastError());
 }
 
-int bsx_td3_head_workspace_bytes(int64_t B, int nA, size_t* bytes) {
-    if (!bytes || !td_shape(B, nA)) return BSX_E_ARG;
-    *bytes = size_t(plan_of(B, nA).blocks) * STAT_COLS * 8;
-    return 0;
-}
+int bsx_td3_head_workspace_bytes(int64_t B, int nA, size_t* bytes) { return head_workspace_bytes(B, nA, bytes); }
 
 int bsx_td3_head(const BsxTd3Io* io, int64_t B, int nA, float gamma, void* workspace, double* stats, void* stream) {
-    if (!io || !io->q1 || !io->q2 || !io->q1_next || !io->q2_next || !io->rew || !io->done || !io->g_q1 || !io->g_q2 || !io->g_pi || !workspace ||
-        !stats)
-        return BSX_E_ARG;
-    if (!(gamma >= 0.0f && gamma <= 1.0f)) return BSX_E_ARG;                   // NaN too
-    if (!td_shape(B, nA)) return BSX_E_ARG;
+    if (!io || !io->q1 || !io->q2 || !io->q1_next || !io->q2_next || !io->rew || !io->done || !io->g_q1 || !io->g_q2 || !io->g_pi) return BSX_E_ARG;
+    if (!head_ranges(gamma, B, nA, workspace, stats)) return BSX_E_ARG;
     if (!aligned(io->g_q1, 16) || !aligned(io->g_q2, 16) || !aligned(io->g_pi, 16)) return BSX_E_ALIGN;
     if (!aligned(io->q1, 4) || !aligned(io->q2, 4) || !aligned(io->q1_next, 4) || !aligned(io->q2_next, 4) || !aligned(io->rew, 4) ||
         !aligned(io->weight, 4) || !aligned(io->td, 4))
         return BSX_E_ALIGN;
-    if (!aligned(workspace, 8) || !aligned(stats, 8)) return BSX_E_ALIGN;
-    const Plan p = plan_of(B, nA);
-    double* part = static_cast<double*>(workspace);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const HeadArgs a{*io, p.M, p.tiles, p.J, gamma, float(1.0 / double(B)), float(2.0 / double(B)), part};
-    if (io->weight) hipLaunchKernelGGL(bsx_td3_head_kernel<1>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
-    else hipLaunchKernelGGL(bsx_td3_head_kernel<0>, dim3(unsigned(p.blocks)), dim3(TPB), 0, s, a);
-    if (const hipError_t e = hipGetLastError()) return int(e);
-    hipLaunchKernelGGL(bsx_td_merge_kernel<true>, dim3(1), dim3(MERGE_TPB), 0, s, static_cast<const double*>(part), p.blocks, p.M, stats);
-    return int(hipGetLastError());
+    const HeadArgs a{*io, 0, 0, 0, gamma, float(1.0 / double(B)), float(2.0 / double(B)), nullptr};
+    return launch_head<true>(bsx_td3_head_kernel<1>, bsx_td3_head_kernel<0>, io->weight != nullptr, a, B, nA, workspace, stats, stream);
 }
 
 }  // extern "C"

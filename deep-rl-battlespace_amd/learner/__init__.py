@@ -5,7 +5,8 @@
   shuffle.py  a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip)
   ppo.py      the PPO loss head and PPOLearner, the update of a rollout's two networks (csrc/bsx_ppo_head.hip)
   ddpg.py     the critic join, TD head and action gradient, and DDPGLearner, the MADDPG update of a team from its ring (csrc/bsx_ddpg_head.hip)
-  td3.py      target policy smoothing, the TD head of two critics, and TD3Learner: twin critics, a delayed actor and target step (csrc/bsx_td3_head.hip)
+  td3.py      target policy smoothing, the TD head of two critics, the second critic TD3Learner and SACLearner share, and TD3Learner: twin critics,
+              a delayed actor and target step (csrc/bsx_td3_head.hip)
   sac.py      the Gaussian policy's reparameterised draw, the soft twin head, the policy's seeds and gradients, and SACLearner (csrc/bsx_sac_head.hip)
   _common.py  what more than one of them uses: the hyper-parameter ranges, the stream, the capture of an update as one graph
 

@@ -1,5 +1,5 @@
-"""What more than one kernel family of the learner package uses: the ranges of the hyper-parameters, the current stream, a float32
-allocator, the check of a one-element int64 device word, and the capture of an update as one graph."""
+"""What more than one kernel family of the learner package uses: the ranges of the hyper-parameters, the current stream, the address of
+an optional tensor, a float32 allocator, the check of a one-element int64 device word, and the capture of an update as one graph."""
 import torch
 
 from .._args import _need, _number
@@ -18,8 +18,16 @@ def _hyper(name, x, rng=None):
     return _number(x, name, *(rng or _HYPER[name]))
 
 
+_U64 = (1 << 64) - 1                                            # a seed or a sequence number as the uint64 the C entries take
+
+
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _ptr(x):
+    """The address of an optional tensor: None (NULL) for None."""
+    return x.data_ptr() if x is not None else None
 
 
 def _f32(make, dev):

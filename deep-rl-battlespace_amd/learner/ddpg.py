@@ -13,11 +13,12 @@ from .. import _lib
 from .._args import _F32, _FLAG, _need, _workspace
 from ..replay import DeviceReplayBuffer, PrioritizedReplayBuffer
 from ..rollout import StackedActor
-from ._common import _POSITIVE, _capture, _f32, _hyper, _stream
+from ._common import _POSITIVE, _capture, _f32, _hyper, _ptr, _stream
 from .adam import AdamState, adam_hyper, mlp_adam_step, mlp_adam_step_workspace_bytes
 from .mlp import PARAMS, _buffers, _check_mlp, _is_stacked, _mlp_forward, _mlp_grad
 
 TdHead = namedtuple("TdHead", "g_q g_pi td stats")
+_Net = namedtuple("_Net", "net target blob target_blob adam buf q q_next g_q")      # a network as a learner holds it (DDPGLearner._net)
 TD_STATS = ("n", "critic_loss", "q", "target", "abs_td", "done", "weight", "reserved")
 MAX_OBS = 3 * _lib.MAX_N + 2
 
@@ -103,6 +104,48 @@ def ddpg_action_grad(gx, obs_len, n_actions, *, central=True, out=None):
     return out
 
 
+def _head_rows(q, what, name="q1"):
+    """The shape check of a call that takes [B, nA] rows: `q`, its first, gives B, nA and the device."""
+    if not isinstance(q, torch.Tensor) or q.dim() != 2:
+        raise ValueError(f"{name} must be a float32 [B, nA] tensor")
+    dev, (B, nA) = q.device, q.shape
+    if dev.type != "cuda":
+        raise ValueError(f"{what} runs on the GPU: {name} is on {dev}")
+    if not 1 <= B < 1 << 31 or not 1 <= nA <= _lib.MAX_N:
+        raise ValueError(f"{name} has shape {tuple(q.shape)}: 1 <= B < 2^31 and 1 .. {_lib.MAX_N} agents are needed")
+    return B, nA, dev
+
+
+def _head_args(what, rows, done, gamma, weight, grads, out, workspace, per_agent=()):
+    """The argument check td_head, td3_head and sac_head share -> (B, nA, dev, gamma, out, workspace).  rows: the (tensor, name) pairs of
+    the float32 [B, nA] inputs, the first giving the shape; per_agent: those of the float32 [nA] ones; grads: the names of the [B, nA, 4]
+    outputs.  out: (*grads, td or None, stats) to write into, or None for new tensors; workspace: bsx_<what>_workspace_bytes(B, nA) bytes,
+    or None for a new one."""
+    first, anchor = rows[0]
+    B, nA, dev = _head_rows(first, what, anchor)
+    gamma = _hyper("gamma", gamma)
+    need = partial(_need, dev=dev, anchor=anchor)
+    for x, name in rows:
+        need(x, name, (B, nA), _F32)
+    need(done, "done", (B, nA), _FLAG)
+    for x, name in per_agent:
+        need(x, name, (nA,), _F32)
+    if weight is not None:
+        need(weight, "weight", (B, nA), _F32)
+    if out is None:
+        f = _f32(torch.empty, dev)
+        out = (*(f(B, nA, 4) for _ in grads), f(B, nA), torch.empty(8, dtype=torch.float64, device=dev))
+    *g, td, stats = out
+    if len(g) != len(grads):
+        raise ValueError(f"out must be ({', '.join(grads)}, td or None, stats)")
+    for x, name in zip(g, grads):
+        need(x, "out " + name, (B, nA, 4), _F32)
+    if td is not None:
+        need(td, "out td", (B, nA), _F32)
+    need(stats, "out stats", (8,), (torch.float64,))
+    return B, nA, dev, gamma, out, _workspace(workspace, _lib.query_bytes(f"bsx_{what}_workspace_bytes", B, nA), dev)
+
+
 def td_head_workspace_bytes(B, nA):
     """Bytes of the workspace td_head needs for B rows of nA agents."""
     return _lib.query_bytes("bsx_td_head_workspace_bytes", B, nA)
@@ -120,32 +163,9 @@ def td_head(q, q_next, rew, done, gamma, *, weight=None, out=None, workspace=Non
     means over the B nA elements.  Deterministic; two launches on the current stream, no host synchronisation.  out: optional
     (g_q, g_pi, td or None, stats) to write into and workspace (at least td_head_workspace_bytes(B, nA) bytes, 8-byte aligned) -- pass
     both and nothing is allocated (a captured graph)."""
-    if not isinstance(q, torch.Tensor) or q.dim() != 2:
-        raise ValueError("q must be a float32 [B, nA] tensor")
-    dev, (B, nA) = q.device, q.shape
-    if dev.type != "cuda":
-        raise ValueError("td_head runs on the GPU: q is on " + str(dev))
-    if not 1 <= B < 1 << 31 or not 1 <= nA <= _lib.MAX_N:
-        raise ValueError(f"q has shape {tuple(q.shape)}: 1 <= B < 2^31 and 1 .. {_lib.MAX_N} agents are needed")
-    gamma = _hyper("gamma", gamma)
-    need = partial(_need, dev=dev, anchor="q")
-    for x, name in ((q, "q"), (q_next, "q_next"), (rew, "rew")):
-        need(x, name, (B, nA), _F32)
-    need(done, "done", (B, nA), _FLAG)
-    if weight is not None:
-        need(weight, "weight", (B, nA), _F32)
-    if out is None:
-        f = _f32(torch.empty, dev)
-        out = (f(B, nA, 4), f(B, nA, 4), f(B, nA), torch.empty(8, dtype=torch.float64, device=dev))
-    g_q, g_pi, td, stats = out
-    need(g_q, "out g_q", (B, nA, 4), _F32)
-    need(g_pi, "out g_pi", (B, nA, 4), _F32)
-    if td is not None:
-        need(td, "out td", (B, nA), _F32)
-    need(stats, "out stats", (8,), (torch.float64,))
-    workspace = _workspace(workspace, td_head_workspace_bytes(B, nA), dev)
-    io = _lib.BsxTdIo(q.data_ptr(), q_next.data_ptr(), rew.data_ptr(), done.data_ptr(), weight.data_ptr() if weight is not None else None,
-                      g_q.data_ptr(), g_pi.data_ptr(), td.data_ptr() if td is not None else None)
+    B, nA, dev, gamma, (g_q, g_pi, td, stats), workspace = _head_args("td_head", ((q, "q"), (q_next, "q_next"), (rew, "rew")), done, gamma, weight,
+                                                                     ("g_q", "g_pi"), out, workspace)
+    io = _lib.BsxTdIo(q.data_ptr(), q_next.data_ptr(), rew.data_ptr(), done.data_ptr(), _ptr(weight), g_q.data_ptr(), g_pi.data_ptr(), _ptr(td))
     _lib.check(_lib.load().bsx_td_head(_lib.ctypes.byref(io), B, nA, gamma, workspace.data_ptr(), stats.data_ptr(), _stream(dev)), "bsx_td_head")
     return TdHead(g_q, g_pi, td, stats)
 
@@ -175,6 +195,8 @@ class DDPGLearner:
        9. mlp_grad of the STEPPED critic on x_pi with g_pi -> grad_x, ddpg_action_grad
       10. mlp_grad of the actor on obs with that, mlp_adam_step of the actor with its target
     Every forward reads a packed blob (bsx_mlp_forward) that the steps keep current; nothing is allocated from the second update on.
+    Steps 3, 4 and 5, 6, 7 and 8 to 10 are methods (`_next_actions`, `_critics_forward`, `_head`, `_critics_step`, `_actor_half`) that run
+    over `critics`, the list of the critics' records: learner.TD3Learner and SACLearner put a second critic on it and override singly.
 
     buffer: a DeviceReplayBuffer; its n_agents, observation size and n_actions give nA, Do and k, its batch_size B.  actor: a
     StackedActor(nA, Do, k) on the buffer's device; critic: a StackedActor(nA, Dc, 1), Dc = nA (Do + k) central (at most 64: up to 3v3)
@@ -219,48 +241,83 @@ class DDPGLearner:
         self._x_cur, self._x_next, self._x_pi = f(B, nA, Dc), f(B, nA, Dc), f(B, nA, Dc)
         _check_mlp(actor, buffer._b_obs, True, type(self).__name__)
         _check_mlp(critic, self._x_cur, False, type(self).__name__)
-        self.actor, self.critic = actor, critic
-        self.target_actor, self.target_critic = copy.deepcopy(actor), copy.deepcopy(critic)
-        for t in (self.target_actor, self.target_critic):
-            t.__dict__.pop("_bsx_mlp_buffers", None)             # (a deep copy takes the network's cached buffers along)
-            t.requires_grad_(False)
-        self._blob_a, self._blob_c, self._blob_ta, self._blob_tc = (x.pack() for x in (actor, critic, self.target_actor, self.target_critic))
-        self.adam_actor, self.adam_critic = AdamState(actor), AdamState(critic)
+        self.critics = []
+        self._actor_net, c = self._net(actor, Do), self._net(critic, Dc, critic=True, gx=True)
+        self.actor, self.target_actor, self._blob_a, self._blob_ta, self.adam_actor, self._buf_a = self._actor_net[:6]
+        self.critic, self.target_critic, self._blob_c, self._blob_tc, self.adam_critic, self._buf_c = c[:6]
         self.hyper_actor, self.hyper_critic = (adam_hyper(lr, betas, eps, mgn, dev, tau) for lr in (lr_actor, lr_critic))
         self.step_actor, self.step_critic = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
         self.stats = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
         self.step_stats_actor, self.step_stats_critic = (torch.zeros((self.updates, 4), dtype=torch.float64, device=dev) for _ in range(2))
-        self._y4, self._yq4, self._g_q, self._g_pi, self._g_a4 = (f(B, nA, 4) for _ in range(5))
-        self._q, self._q_next, self.td = f(B, nA), f(B, nA), f(B, nA)
-        self._head_ws = _workspace(None, td_head_workspace_bytes(B, nA), dev)
+        self._y4, self._yq4, self._g_pi, self._g_a4 = (f(B, nA, 4) for _ in range(4))
+        self.td = f(B, nA)
+        self._head_ws = _workspace(None, td_head_workspace_bytes(B, nA), dev)        # (the three heads share one plan: one size)
         self._adam_ws = _workspace(None, mlp_adam_step_workspace_bytes(nA, 1), dev)
-        self._buf_a = _buffers(actor).get(B, nA, Do, dev)
-        self._buf_c = _buffers(critic).get(B, nA, Dc, dev, gx=True)
         self._prioritized = isinstance(buffer, PrioritizedReplayBuffer)
         self._graph = None
 
+    def _net(self, net, D, critic=False, gx=False):
+        """A network as the learner holds it -> _Net: with a deep copy as its target, both packed blobs, its AdamState and MLP buffers;
+        a critic also with its q, q_next and g_q tensors, and it joins `critics`, the list the update's loops run over."""
+        B, nA, dev = self.B, self.nA, self._x_cur.device
+        target = copy.deepcopy(net)
+        target.__dict__.pop("_bsx_mlp_buffers", None)            # (a deep copy takes the network's cached buffers along)
+        target.requires_grad_(False)
+        f = _f32(torch.zeros, dev)
+        rec = _Net(net, target, net.pack(), target.pack(), AdamState(net), _buffers(net).get(B, nA, D, dev, gx=gx),
+                   *((f(B, nA), f(B, nA), f(B, nA, 4)) if critic else (None, None, None)))
+        if critic:
+            self.critics.append(rec)
+        return rec
+
     def _update(self, u):
-        """Update u of a call: the ten steps of the class's docstring."""
-        lib, buf = _lib.load(), self.buffer
+        """Update u of a call: the steps of the class's docstring, each a method of its own that a subclass overrides singly."""
+        buf = self.buffer
         buf.sample()
-        obs, obs_next, act, rew, done = buf._b_obs, buf._b_obs_, buf._b_act, buf._b_rew, buf._b_done
-        Do, k, c = self.Do, self.k, self.central
-        ddpg_inputs(obs, obs_next, act, central=c, out=(self._x_cur, self._x_next, self._x_pi))
-        _mlp_forward(lib, self._blob_ta, obs_next, self._y4)
-        ddpg_put_actions(self._y4, self._x_next, Do, k, central=c, own_only=False)
-        _mlp_forward(lib, self._blob_tc, self._x_next, self._yq4, self._q_next)
-        _mlp_forward(lib, self._blob_c, self._x_cur, self._yq4, self._q)
-        td_head(self._q, self._q_next, rew, done, self.gamma, weight=buf.weights if self._prioritized else None,
-                out=(self._g_q, self._g_pi, self.td, self.stats[u]), workspace=self._head_ws)
+        ddpg_inputs(buf._b_obs, buf._b_obs_, buf._b_act, central=self.central, out=(self._x_cur, self._x_next, self._x_pi))
+        self._next_actions()
+        self._critics_forward()
+        self._head(u, buf.weights if self._prioritized else None)
         if self._prioritized:
-            buf.update_priorities(self._q, self.td)
-        row_c = _mlp_grad(lib, self._buf_c, self._blob_c, self._x_cur, self._g_q, False)
-        mlp_adam_step([self.critic], [row_c], [self.adam_critic], [self._blob_c], self.hyper_critic, self.step_critic,
-                      targets=[self.target_critic], target_blobs=[self._blob_tc], stats=self.step_stats_critic[u], workspace=self._adam_ws)
+            buf.update_priorities(self.critics[0].q, self.td)
+        self._critics_step(u)
+        self._actor_half(u)
+
+    def _next_actions(self):
+        """Step 3: the next state's actions into x_next."""
+        _mlp_forward(_lib.load(), self._blob_ta, self.buffer._b_obs_, self._y4)
+        ddpg_put_actions(self._y4, self._x_next, self.Do, self.k, central=self.central, own_only=False)
+
+    def _critics_forward(self):
+        """Steps 4 and 5: the target critics on x_next in order, then the critics on x_cur in order."""
+        lib = _lib.load()
+        for c in self.critics:
+            _mlp_forward(lib, c.target_blob, self._x_next, self._yq4, c.q_next)
+        for c in self.critics:
+            _mlp_forward(lib, c.blob, self._x_cur, self._yq4, c.q)
+
+    def _head(self, u, weight):
+        """Step 6: the TD target, the critics' grad_out and the statistics of update u."""
+        c, = self.critics
+        td_head(c.q, c.q_next, self.buffer._b_rew, self.buffer._b_done, self.gamma, weight=weight, out=(c.g_q, self._g_pi, self.td, self.stats[u]),
+                workspace=self._head_ws)
+
+    def _critics_step(self, u, polyak=True):
+        """Step 7: the critics' gradients in order, then ONE Adam step of them all; polyak: it carries their targets along."""
+        lib, cs = _lib.load(), self.critics
+        rows = [_mlp_grad(lib, c.buf, c.blob, self._x_cur, c.g_q, False) for c in cs]
+        targets = dict(targets=[c.target for c in cs], target_blobs=[c.target_blob for c in cs]) if polyak else {}
+        mlp_adam_step([c.net for c in cs], rows, [c.adam for c in cs], [c.blob for c in cs], self.hyper_critic, self.step_critic,
+                      stats=self.step_stats_critic[u], workspace=self._adam_ws, **targets)
+
+    def _actor_half(self, u):
+        """Steps 8 to 10: the deterministic policy gradient through the stepped critic 1, the actor's step with its target."""
+        lib, obs, c = _lib.load(), self.buffer._b_obs, self.critics[0]
+        Do, k, central = self.Do, self.k, self.central
         _mlp_forward(lib, self._blob_a, obs, self._y4)
-        ddpg_put_actions(self._y4, self._x_pi, Do, k, central=c, own_only=True)
-        _mlp_grad(lib, self._buf_c, self._blob_c, self._x_pi, self._g_pi, False, self._buf_c["gx"])
-        ddpg_action_grad(self._buf_c["gx"], Do, k, central=c, out=self._g_a4)
+        ddpg_put_actions(self._y4, self._x_pi, Do, k, central=central, own_only=True)
+        _mlp_grad(lib, c.buf, c.blob, self._x_pi, self._g_pi, False, c.buf["gx"])
+        ddpg_action_grad(c.buf["gx"], Do, k, central=central, out=self._g_a4)
         row_a = _mlp_grad(lib, self._buf_a, self._blob_a, obs, self._g_a4, True)
         mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
                       targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u], workspace=self._adam_ws)
@@ -277,9 +334,9 @@ class DDPGLearner:
 
     def _state(self):
         """Every tensor an update writes that outlives it."""
-        return ([self.buffer._draws, self.step_actor, self.step_critic, self._blob_a, self._blob_c, self._blob_ta, self._blob_tc, self.stats,
-                 self.step_stats_actor, self.step_stats_critic] + [t for st in (self.adam_actor, self.adam_critic) for t in (st.m, st.v)]
-                + [getattr(net, p) for net in (self.actor, self.critic, self.target_actor, self.target_critic) for p in PARAMS]
+        return ([self.buffer._draws, self.step_actor, self.step_critic, self.stats, self.step_stats_actor, self.step_stats_critic]
+                + [t for n in [self._actor_net] + self.critics for t in (n.blob, n.target_blob, n.adam.m, n.adam.v)]
+                + [getattr(net, p) for n in [self._actor_net] + self.critics for net in (n.net, n.target) for p in PARAMS]
                 + ([self.buffer._leaves, self.buffer.tree, self.buffer.max_priority] if self._prioritized else []))
 
     def capture(self):
@@ -298,10 +355,11 @@ class DDPGLearner:
                 hyper[0].fill_(_hyper("lr", lr))
 
     def sync(self):
-        """Re-pack all four blobs from their networks, once: for a caller who has edited parameters or targets from outside."""
-        for net, blob in ((self.actor, self._blob_a), (self.critic, self._blob_c), (self.target_actor, self._blob_ta),
-                          (self.target_critic, self._blob_tc)):
-            net.pack(out=blob)
+        """Re-pack every blob from its network (two per network: four, or six with a second critic), once: for a caller who has edited
+        parameters or targets from outside."""
+        for n in [self._actor_net] + self.critics:
+            n.net.pack(out=n.blob)
+            n.target.pack(out=n.target_blob)
 
     def publish(self, rollout, columns):
         """The team's actors into a PolicyRollout that plays them: the actor's blob rows into rollout.fused.weights[c0 : c0 + nA] (a blob

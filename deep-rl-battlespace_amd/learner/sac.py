@@ -4,8 +4,11 @@
                                                 soft TD head of two critics, the actor's seeds through the smaller critic, the gradients
                                                 of the actor's output, of log_std and of the temperature
   SACLearner(buffer, actor, critic=None, critic2=None, ...)   the Gaussian policy of PolicyRollout(sample="gaussian") trained from the ring; one graph
+
+The learner is td3.py's _TwinCriticLearner -- DDPGLearner's sequence of steps over two critics -- with the steps that are SAC's own: the next
+actions drawn from the current actor, the soft head, and an actor's half through both critics.  sac_head's argument check is ddpg.py's
+_head_args, td_head's and td3_head's too.
 """
-import copy
 import math
 from collections import namedtuple
 from functools import partial
@@ -13,19 +16,17 @@ from functools import partial
 import torch
 
 from .. import _lib
-from .._args import _F32, _FLAG, _need, _number, _workspace
-from ..rollout import StackedActor
-from ._common import _f32, _hyper, _int64_word, _stream
-from .adam import AdamState, adam_hyper, mlp_adam_step, mlp_adam_step_workspace_bytes
-from .ddpg import DDPGLearner, _batch_rows, _critic_width, ddpg_inputs
-from .mlp import PARAMS, _buffers, _check_mlp, _mlp_forward, _mlp_grad
-from .td3 import TD3_STATS
+from .._args import _F32, _need, _number, _workspace
+from ._common import _U64, _f32, _hyper, _int64_word, _ptr, _stream
+from .adam import AdamState, adam_hyper, mlp_adam_step
+from .ddpg import _batch_rows, _critic_width, _head_args, _head_rows
+from .mlp import _mlp_forward, _mlp_grad
+from .td3 import TD3_STATS, _TwinCriticLearner
 
 SacHead = namedtuple("SacHead", "g_q1 g_q2 td stats")
 SacPolicyGrad = namedtuple("SacPolicyGrad", "g_a4 g_log_std g_log_alpha stats")
 SAC_STATS = TD3_STATS
 SAC_PI_STATS = ("n", "actor_loss", "q_pi", "logp", "alpha", "weight", "picked_1", "reserved")
-_U64 = (1 << 64) - 1
 _FINITE = (lambda x: math.isfinite(x), "a finite number")
 _F64 = (torch.float64,)
 
@@ -34,10 +35,6 @@ def _three(k):
     if int(k) != 3:
         raise ValueError(f"the Gaussian policy has three action columns: n_actions must be 3, got {k!r}")
     return 3
-
-
-def _ptr(x):
-    return x.data_ptr() if x is not None else None
 
 
 def sac_sample_actions(y4, log_std, x, obs_len, n_actions=3, *, seed=0, seq=0, seq_base=None, z=None, central=True, own_only=False,
@@ -80,17 +77,6 @@ def sac_head_workspace_bytes(B, nA):
     return _lib.query_bytes("bsx_sac_head_workspace_bytes", B, nA)
 
 
-def _head_rows(q1, what):
-    if not isinstance(q1, torch.Tensor) or q1.dim() != 2:
-        raise ValueError("q1 must be a float32 [B, nA] tensor")
-    dev, (B, nA) = q1.device, q1.shape
-    if dev.type != "cuda":
-        raise ValueError(f"{what} runs on the GPU: q1 is on {dev}")
-    if not 1 <= B < 1 << 31 or not 1 <= nA <= _lib.MAX_N:
-        raise ValueError(f"q1 has shape {tuple(q1.shape)}: 1 <= B < 2^31 and 1 .. {_lib.MAX_N} agents are needed")
-    return B, nA, dev
-
-
 def sac_head(q1, q2, q1_next, q2_next, logp_next, rew, done, log_alpha, gamma, *, weight=None, out=None, workspace=None):
     """The soft TD target of two target critics and both critics' grad_out, in one pass (csrc/bsx_sac_head.hip, `bsx_sac_head`; the exact
     contract is written out in include/battlespace_hip.h) -> SacHead(g_q1, g_q2, td, stats).
@@ -101,25 +87,9 @@ def sac_head(q1, q2, q1_next, q2_next, logp_next, rew, done, log_alpha, gamma, *
     of y.  There is no g_pi (sac_policy_seed).  Deterministic; two launches on the current stream, no host synchronisation.  out: optional
     (g_q1, g_q2, td or None, stats) to write into and workspace (at least sac_head_workspace_bytes(B, nA) bytes, 8-byte aligned) -- pass
     both and nothing is allocated (a captured graph)."""
-    B, nA, dev = _head_rows(q1, "sac_head")
-    gamma = _hyper("gamma", gamma)
-    need = partial(_need, dev=dev, anchor="q1")
-    for x, name in ((q1, "q1"), (q2, "q2"), (q1_next, "q1_next"), (q2_next, "q2_next"), (logp_next, "logp_next"), (rew, "rew")):
-        need(x, name, (B, nA), _F32)
-    need(done, "done", (B, nA), _FLAG)
-    need(log_alpha, "log_alpha", (nA,), _F32)
-    if weight is not None:
-        need(weight, "weight", (B, nA), _F32)
-    if out is None:
-        f = _f32(torch.empty, dev)
-        out = (f(B, nA, 4), f(B, nA, 4), f(B, nA), torch.empty(8, dtype=torch.float64, device=dev))
-    g_q1, g_q2, td, stats = out
-    for x, name in ((g_q1, "out g_q1"), (g_q2, "out g_q2")):
-        need(x, name, (B, nA, 4), _F32)
-    if td is not None:
-        need(td, "out td", (B, nA), _F32)
-    need(stats, "out stats", (8,), _F64)
-    workspace = _workspace(workspace, sac_head_workspace_bytes(B, nA), dev)
+    rows = ((q1, "q1"), (q2, "q2"), (q1_next, "q1_next"), (q2_next, "q2_next"), (logp_next, "logp_next"), (rew, "rew"))
+    B, nA, dev, gamma, (g_q1, g_q2, td, stats), workspace = _head_args("sac_head", rows, done, gamma, weight, ("g_q1", "g_q2"), out, workspace,
+                                                                       per_agent=((log_alpha, "log_alpha"),))
     io = _lib.BsxSacIo(q1.data_ptr(), q2.data_ptr(), q1_next.data_ptr(), q2_next.data_ptr(), logp_next.data_ptr(), rew.data_ptr(), done.data_ptr(),
                        _ptr(weight), log_alpha.data_ptr(), g_q1.data_ptr(), g_q2.data_ptr(), _ptr(td))
     _lib.check(_lib.load().bsx_sac_head(_lib.ctypes.byref(io), B, nA, gamma, workspace.data_ptr(), stats.data_ptr(), _stream(dev)), "bsx_sac_head")
@@ -207,7 +177,7 @@ def sac_policy_grad(gx1, gx2, z, logp, q1_pi, q2_pi, log_std, log_alpha, obs_len
     return SacPolicyGrad(g_a4, g_ls, g_la, stats)
 
 
-class SACLearner(DDPGLearner):
+class SACLearner(_TwinCriticLearner):
     """The soft actor-critic update of a team from its replay ring, on device (Haarnoja et al. 2018, the twin-critic form with a learned
     temperature; per agent, with MADDPG's critic inputs): DDPGLearner's actor, ring and critic inputs, TD3Learner's two critics, and a
     stochastic policy -- the one PolicyRollout(sample="gaussian", log_std=...) plays: mu = the actor's tanh row, one learned log_std per
@@ -255,32 +225,17 @@ class SACLearner(DDPGLearner):
     def __init__(self, buffer, actor, critic=None, critic2=None, *, log_std=None, alpha=0.2, lr_alpha=3e-4, target_entropy=None,
                  critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3, lr_critic=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  max_grad_norm=None, updates=1, seed=0):
-        if critic2 is not None and critic2 is critic:
-            raise ValueError("critic2 is critic itself: the second critic is a network of its own")
         alpha = _number(alpha, "alpha", lambda x: 0.0 < x < math.inf, "a finite number > 0")
         lr_alpha = None if lr_alpha is None else _hyper("lr", lr_alpha)
         self.target_entropy = _number(-3.0 if target_entropy is None else target_entropy, "target_entropy", *_FINITE)
-        self.seed = int(seed)
         if getattr(buffer, "n_actions", 3) != 3:
             raise ValueError(f"SACLearner needs a buffer with 3 action columns (the Gaussian policy's), got {buffer.n_actions}")
-        super().__init__(buffer, actor, critic, critic_input=critic_input, gamma=gamma, tau=tau, lr_actor=lr_actor, lr_critic=lr_critic,
-                         betas=betas, eps=eps, max_grad_norm=max_grad_norm, updates=updates)
-        nA, B, Dc, dev = self.nA, self.B, self.Dc, self._x_cur.device
-        if critic2 is None:
-            critic2 = StackedActor(nA, Dc, 1, device=dev)
-        have = tuple(getattr(critic2, a, None) for a in ("n_actors", "obs_len", "n_actions"))
-        if have != (nA, Dc, 1):
-            raise ValueError(f"critic2 must be a StackedActor{(nA, Dc, 1)} for this buffer and critic_input={critic_input!r}, got "
-                             f"{'StackedActor' + str(have) if None not in have else type(critic2).__name__}")
-        _check_mlp(critic2, self._x_cur, False, "SACLearner")
+        super().__init__(buffer, actor, critic, critic2, seed=seed, gx2=True, critic_input=critic_input, gamma=gamma, tau=tau, lr_actor=lr_actor,
+                         lr_critic=lr_critic, betas=betas, eps=eps, max_grad_norm=max_grad_norm, updates=updates)
+        nA, B, dev = self.nA, self.B, self._x_cur.device
         if log_std is None:
             log_std = torch.full((nA, 3), math.log(0.2), dtype=torch.float32, device=dev)
         _need(log_std, "log_std", (nA, 3), _F32, dev, "the buffer")
-        self.critic2, self.target_critic2 = critic2, copy.deepcopy(critic2)
-        self.target_critic2.__dict__.pop("_bsx_mlp_buffers", None)
-        self.target_critic2.requires_grad_(False)
-        self._blob_c2, self._blob_tc2 = critic2.pack(), self.target_critic2.pack()
-        self.adam_critic2 = AdamState(critic2)
         self.log_std, self.adam_log_std = log_std, AdamState(log_std)
         self.log_alpha = torch.full((nA,), math.log(alpha), dtype=torch.float32, device=dev)
         self.learn_alpha = lr_alpha is not None
@@ -289,50 +244,37 @@ class SACLearner(DDPGLearner):
         self.step_alpha = torch.zeros(1, dtype=torch.int64, device=dev)
         self.stats_pi = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
         f = _f32(torch.zeros, dev)
-        self._g_q2, self._g_pi2 = f(B, nA, 4), f(B, nA, 4)
-        self._q2, self._q2_next, self._logp_next, self._logp = f(B, nA), f(B, nA), f(B, nA), f(B, nA)
-        self._z, self._g_log_std, self._g_log_alpha = f(B, nA, 4), f(nA, 3), f(nA)
-        self._noise_draws = torch.zeros(1, dtype=torch.int64, device=dev)       # the draws' sequence word, advanced once per sampling call
-        self._head_ws = _workspace(None, sac_head_workspace_bytes(B, nA), dev)
+        self._g_pi2, self._z = f(B, nA, 4), f(B, nA, 4)
+        self._logp_next, self._logp, self._g_log_std, self._g_log_alpha = f(B, nA), f(B, nA), f(nA, 3), f(nA)
         self._pi_ws = _workspace(None, sac_policy_grad_workspace_bytes(B, nA), dev)
-        self._adam_ws = _workspace(None, max(mlp_adam_step_workspace_bytes(nA, 1), mlp_adam_step_workspace_bytes(nA, 2)), dev)
-        self._buf_c2 = _buffers(critic2).get(B, nA, Dc, dev, gx=True)
 
-    def _update(self, u):
-        """Update u of a call: the ten steps of the class's docstring."""
-        lib, buf = _lib.load(), self.buffer
-        buf.sample()
-        obs, obs_next, act, rew, done = buf._b_obs, buf._b_obs_, buf._b_act, buf._b_rew, buf._b_done
-        Do, k, c = self.Do, self.k, self.central
-        weight = buf.weights if self._prioritized else None
-        ddpg_inputs(obs, obs_next, act, central=c, out=(self._x_cur, self._x_next, self._x_pi))
-        _mlp_forward(lib, self._blob_a, obs_next, self._y4)
-        sac_sample_actions(self._y4, self.log_std, self._x_next, Do, k, seed=self.seed, seq_base=self._noise_draws, central=c, own_only=False,
-                           out=(self._logp_next, None))
+    def _next_actions(self):
+        """Step 2: a draw from the CURRENT actor on obs_next into x_next, its log-probability kept; the sequence word advances."""
+        _mlp_forward(_lib.load(), self._blob_a, self.buffer._b_obs_, self._y4)
+        sac_sample_actions(self._y4, self.log_std, self._x_next, self.Do, self.k, seed=self.seed, seq_base=self._noise_draws,
+                           central=self.central, own_only=False, out=(self._logp_next, None))
         self._noise_draws.add_(1)                                # fresh noise at the next draw, and on every replay of a captured graph
-        _mlp_forward(lib, self._blob_tc, self._x_next, self._yq4, self._q_next)
-        _mlp_forward(lib, self._blob_tc2, self._x_next, self._yq4, self._q2_next)
-        _mlp_forward(lib, self._blob_c, self._x_cur, self._yq4, self._q)
-        _mlp_forward(lib, self._blob_c2, self._x_cur, self._yq4, self._q2)
-        sac_head(self._q, self._q2, self._q_next, self._q2_next, self._logp_next, rew, done, self.log_alpha, self.gamma, weight=weight,
-                 out=(self._g_q, self._g_q2, self.td, self.stats[u]), workspace=self._head_ws)
-        if self._prioritized:
-            buf.update_priorities(self._q, self.td)
-        row_c = _mlp_grad(lib, self._buf_c, self._blob_c, self._x_cur, self._g_q, False)
-        row_c2 = _mlp_grad(lib, self._buf_c2, self._blob_c2, self._x_cur, self._g_q2, False)
-        mlp_adam_step([self.critic, self.critic2], [row_c, row_c2], [self.adam_critic, self.adam_critic2], [self._blob_c, self._blob_c2],
-                      self.hyper_critic, self.step_critic, targets=[self.target_critic, self.target_critic2],
-                      target_blobs=[self._blob_tc, self._blob_tc2], stats=self.step_stats_critic[u], workspace=self._adam_ws)
+
+    def _head(self, u, weight):
+        c1, c2 = self.critics
+        sac_head(c1.q, c2.q, c1.q_next, c2.q_next, self._logp_next, self.buffer._b_rew, self.buffer._b_done, self.log_alpha, self.gamma,
+                 weight=weight, out=(c1.g_q, c2.g_q, self.td, self.stats[u]), workspace=self._head_ws)
+
+    def _actor_half(self, u):
+        """Steps 6 to 10: the policy's, log_std's and the temperature's gradients through both stepped critics, and their steps."""
+        lib, obs, (c1, c2) = _lib.load(), self.buffer._b_obs, self.critics
+        Do, k, c = self.Do, self.k, self.central
+        weight = self.buffer.weights if self._prioritized else None
         _mlp_forward(lib, self._blob_a, obs, self._y4)
         sac_sample_actions(self._y4, self.log_std, self._x_pi, Do, k, seed=self.seed, seq_base=self._noise_draws, central=c, own_only=True,
                            out=(self._logp, self._z))
         self._noise_draws.add_(1)
-        _mlp_forward(lib, self._blob_c, self._x_pi, self._yq4, self._q)
-        _mlp_forward(lib, self._blob_c2, self._x_pi, self._yq4, self._q2)
-        sac_policy_seed(self._q, self._q2, weight=weight, out=(self._g_pi, self._g_pi2))
-        _mlp_grad(lib, self._buf_c, self._blob_c, self._x_pi, self._g_pi, False, self._buf_c["gx"])
-        _mlp_grad(lib, self._buf_c2, self._blob_c2, self._x_pi, self._g_pi2, False, self._buf_c2["gx"])
-        sac_policy_grad(self._buf_c["gx"], self._buf_c2["gx"], self._z, self._logp, self._q, self._q2, self.log_std, self.log_alpha, Do, k,
+        for ci in (c1, c2):                                      # (q now holds the critic on x_pi)
+            _mlp_forward(lib, ci.blob, self._x_pi, self._yq4, ci.q)
+        sac_policy_seed(c1.q, c2.q, weight=weight, out=(self._g_pi, self._g_pi2))
+        for ci, seed in ((c1, self._g_pi), (c2, self._g_pi2)):
+            _mlp_grad(lib, ci.buf, ci.blob, self._x_pi, seed, False, ci.buf["gx"])
+        sac_policy_grad(c1.buf["gx"], c2.buf["gx"], self._z, self._logp, c1.q, c2.q, self.log_std, self.log_alpha, Do, k,
                         target_entropy=self.target_entropy, weight=weight, central=c, alpha_state=self.adam_alpha, hyper=self.hyper_alpha,
                         step=self.step_alpha if self.learn_alpha else None,
                         out=(self._g_a4, self._g_log_std, self._g_log_alpha, self.stats_pi[u]), workspace=self._pi_ws)
@@ -343,9 +285,7 @@ class SACLearner(DDPGLearner):
     def _state(self):
         """Every tensor an update writes that outlives it."""
         alpha = [self.adam_alpha.m, self.adam_alpha.v] if self.learn_alpha else []
-        return (super()._state() + [self._noise_draws, self._blob_c2, self._blob_tc2, self.adam_critic2.m, self.adam_critic2.v, self.stats_pi,
-                                    self.log_std, self.adam_log_std.m, self.adam_log_std.v, self.log_alpha, self.step_alpha] + alpha
-                + [getattr(net, p) for net in (self.critic2, self.target_critic2) for p in PARAMS])
+        return super()._state() + [self.stats_pi, self.log_std, self.adam_log_std.m, self.adam_log_std.v, self.log_alpha, self.step_alpha] + alpha
 
     def set_lr(self, actor=None, critic=None, alpha=None):
         """DDPGLearner.set_lr, and alpha=: the rate of the temperature's step (a learner made with lr_alpha=None has none to set)."""
@@ -354,13 +294,6 @@ class SACLearner(DDPGLearner):
             if not self.learn_alpha:
                 raise ValueError("this learner keeps log_alpha fixed (lr_alpha=None): there is no rate to set")
             self.hyper_alpha[0].fill_(_hyper("lr", alpha))
-
-    def sync(self):
-        """Re-pack all six blobs from their networks, once: for a caller who has edited parameters or targets from outside.  log_std and
-        log_alpha are read where they are: they need no re-packing."""
-        super().sync()
-        self.critic2.pack(out=self._blob_c2)
-        self.target_critic2.pack(out=self._blob_tc2)
 
     def publish(self, rollout, columns):
         """DDPGLearner.publish; a rollout with a `log_std` (sample="gaussian") also receives the learner's into its rows c0 : c0 + nA -- a

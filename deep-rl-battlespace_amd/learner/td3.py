@@ -2,24 +2,26 @@
 
   td3_smooth_actions, td3_head                  target policy smoothing into x_next, the TD head of two critics
   TD3Learner(buffer, actor, critic=None, critic2=None, ...)   twin critics, smoothed targets, a delayed actor and target step; one graph
+
+DDPGLearner's update is a sequence of steps over a list of critics (ddpg.py).  _TwinCriticLearner here puts a second critic on that list --
+the one place TD3Learner and learner.SACLearner get theirs from -- and TD3Learner overrides the steps that are TD3's: the next actions, the
+head, and when the targets and the actor move.  td3_head's argument check is ddpg.py's _head_args, td_head's and sac_head's too.
 """
-import copy
 from collections import namedtuple
 from functools import partial
 
 import torch
 
 from .. import _lib
-from .._args import _F32, _FLAG, _need, _workspace
+from .._args import _F32, _need, _workspace
 from ..rollout import StackedActor
-from ._common import _WEIGHT, _f32, _hyper, _int64_word, _stream
-from .adam import AdamState, mlp_adam_step, mlp_adam_step_workspace_bytes
-from .ddpg import DDPGLearner, _batch_rows, _critic_width, ddpg_action_grad, ddpg_inputs, ddpg_put_actions
-from .mlp import PARAMS, _buffers, _check_mlp, _mlp_forward, _mlp_grad
+from ._common import _U64, _WEIGHT, _hyper, _int64_word, _ptr, _stream
+from .adam import mlp_adam_step_workspace_bytes
+from .ddpg import DDPGLearner, _batch_rows, _critic_width, _head_args
+from .mlp import _check_mlp, _mlp_forward
 
 Td3Head = namedtuple("Td3Head", "g_q1 g_q2 g_pi td stats")
 TD3_STATS = ("n", "critic_loss", "q", "target", "abs_td", "done", "weight", "q_gap")
-_U64 = (1 << 64) - 1
 
 
 def td3_smooth_actions(y4, x, obs_len, n_actions, *, sigma, clip, seed, seq=0, seq_base=None, z=None, central=True):
@@ -44,8 +46,7 @@ def td3_smooth_actions(y4, x, obs_len, n_actions, *, sigma, clip, seed, seq=0, s
     if seq_base is not None:
         _int64_word(seq_base, "seq_base", dev, "y4")
     _lib.check(_lib.load().bsx_td3_smooth_actions(y4.data_ptr(), B, nA, Do, k, int(bool(central)), sigma, clip, int(seed) & _U64, int(seq) & _U64,
-                                                  seq_base.data_ptr() if seq_base is not None else None,
-                                                  z.data_ptr() if z is not None else None, x.data_ptr(), _stream(dev)), "bsx_td3_smooth_actions")
+                                                  _ptr(seq_base), _ptr(z), x.data_ptr(), _stream(dev)), "bsx_td3_smooth_actions")
     return x
 
 
@@ -67,38 +68,44 @@ def td3_head(q1, q2, q1_next, q2_next, rew, done, gamma, *, weight=None, out=Non
     learner.TD3_STATS: means over the B nA elements.  Deterministic; two launches on the current stream, no host synchronisation.
     out: optional (g_q1, g_q2, g_pi, td or None, stats) to write into and workspace (at least td3_head_workspace_bytes(B, nA) bytes,
     8-byte aligned) -- pass both and nothing is allocated (a captured graph)."""
-    if not isinstance(q1, torch.Tensor) or q1.dim() != 2:
-        raise ValueError("q1 must be a float32 [B, nA] tensor")
-    dev, (B, nA) = q1.device, q1.shape
-    if dev.type != "cuda":
-        raise ValueError("td3_head runs on the GPU: q1 is on " + str(dev))
-    if not 1 <= B < 1 << 31 or not 1 <= nA <= _lib.MAX_N:
-        raise ValueError(f"q1 has shape {tuple(q1.shape)}: 1 <= B < 2^31 and 1 .. {_lib.MAX_N} agents are needed")
-    gamma = _hyper("gamma", gamma)
-    need = partial(_need, dev=dev, anchor="q1")
-    for x, name in ((q1, "q1"), (q2, "q2"), (q1_next, "q1_next"), (q2_next, "q2_next"), (rew, "rew")):
-        need(x, name, (B, nA), _F32)
-    need(done, "done", (B, nA), _FLAG)
-    if weight is not None:
-        need(weight, "weight", (B, nA), _F32)
-    if out is None:
-        f = _f32(torch.empty, dev)
-        out = (f(B, nA, 4), f(B, nA, 4), f(B, nA, 4), f(B, nA), torch.empty(8, dtype=torch.float64, device=dev))
-    g_q1, g_q2, g_pi, td, stats = out
-    for x, name in ((g_q1, "out g_q1"), (g_q2, "out g_q2"), (g_pi, "out g_pi")):
-        need(x, name, (B, nA, 4), _F32)
-    if td is not None:
-        need(td, "out td", (B, nA), _F32)
-    need(stats, "out stats", (8,), (torch.float64,))
-    workspace = _workspace(workspace, td3_head_workspace_bytes(B, nA), dev)
-    io = _lib.BsxTd3Io(q1.data_ptr(), q2.data_ptr(), q1_next.data_ptr(), q2_next.data_ptr(), rew.data_ptr(), done.data_ptr(),
-                       weight.data_ptr() if weight is not None else None, g_q1.data_ptr(), g_q2.data_ptr(), g_pi.data_ptr(),
-                       td.data_ptr() if td is not None else None)
+    rows = ((q1, "q1"), (q2, "q2"), (q1_next, "q1_next"), (q2_next, "q2_next"), (rew, "rew"))
+    B, nA, dev, gamma, (g_q1, g_q2, g_pi, td, stats), workspace = _head_args("td3_head", rows, done, gamma, weight, ("g_q1", "g_q2", "g_pi"), out,
+                                                                             workspace)
+    io = _lib.BsxTd3Io(q1.data_ptr(), q2.data_ptr(), q1_next.data_ptr(), q2_next.data_ptr(), rew.data_ptr(), done.data_ptr(), _ptr(weight),
+                       g_q1.data_ptr(), g_q2.data_ptr(), g_pi.data_ptr(), _ptr(td))
     _lib.check(_lib.load().bsx_td3_head(_lib.ctypes.byref(io), B, nA, gamma, workspace.data_ptr(), stats.data_ptr(), _stream(dev)), "bsx_td3_head")
     return Td3Head(g_q1, g_q2, g_pi, td, stats)
 
 
-class TD3Learner(DDPGLearner):
+class _TwinCriticLearner(DDPGLearner):
+    """DDPGLearner with a second critic: what TD3Learner and SACLearner share, and no learner on its own (it has no head for two critics).
+    critic2: a second StackedActor(nA, Dc, 1), not `critic` itself; one is made if none is given.  On top of DDPGLearner's state it owns
+    `critic2`, `target_critic2`, their blobs `_blob_c2` and `_blob_tc2`, `adam_critic2` -- the second record of `critics`, so the
+    forwards, the gradients, the joint Adam step, capture() and sync() cover both -- and `_noise_draws`, the sequence word of the
+    subclass's draws (with `seed` their key), advanced by one per drawing call.  gx2: critic 2 also gives input gradients."""
+
+    def __init__(self, buffer, actor, critic, critic2, *, seed, gx2, critic_input, **kw):
+        if critic2 is not None and critic2 is critic:
+            raise ValueError("critic2 is critic itself: the second critic is a network of its own")
+        self.seed = int(seed)
+        super().__init__(buffer, actor, critic, critic_input=critic_input, **kw)
+        nA, Dc, dev = self.nA, self.Dc, self._x_cur.device
+        if critic2 is None:
+            critic2 = StackedActor(nA, Dc, 1, device=dev)
+        have = tuple(getattr(critic2, a, None) for a in ("n_actors", "obs_len", "n_actions"))
+        if have != (nA, Dc, 1):
+            raise ValueError(f"critic2 must be a StackedActor{(nA, Dc, 1)} for this buffer and critic_input={critic_input!r}, got "
+                             f"{'StackedActor' + str(have) if None not in have else type(critic2).__name__}")
+        _check_mlp(critic2, self._x_cur, False, type(self).__name__)
+        self.critic2, self.target_critic2, self._blob_c2, self._blob_tc2, self.adam_critic2 = self._net(critic2, Dc, critic=True, gx=gx2)[:5]
+        self._noise_draws = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._adam_ws = _workspace(None, max(mlp_adam_step_workspace_bytes(nA, 1), mlp_adam_step_workspace_bytes(nA, 2)), dev)
+
+    def _state(self):
+        return super()._state() + [self._noise_draws]
+
+
+class TD3Learner(_TwinCriticLearner):
     """The MATD3 update of a team from its replay ring, on device (Fujimoto et al. 2018; Ackermann et al. 2019 for the multi-agent form):
     DDPGLearner's networks, ring and critic inputs with TD3's three pieces -- a second critic and a target that bootstraps from the
     smaller of the two target critics; clipped Gaussian noise on the target actors' actions; the actor and ALL target networks stepped
@@ -129,89 +136,43 @@ class TD3Learner(DDPGLearner):
     a captured call keeps the schedule from replay to replay.  target_noise (sigma) and noise_clip are >= 0.  On top of DDPGLearner's
     state the learner owns `target_critic2`, two more blobs, `adam_critic2` and `_noise_draws`; `stats` is f64 [updates, 8] in the order
     of TD3_STATS, `step_stats_critic` holds the joint step of both critics, and the rows of `step_stats_actor` of updates without an
-    actor step stay as they were.  update(), capture(), set_lr(), sync() (six blobs) and publish() are DDPGLearner's.  Parameter
+    actor step stay as they were.  update(), capture(), set_lr(), sync() (six blobs) and publish() are DDPGLearner's, over the two
+    critics of _TwinCriticLearner; the steps of an update that are TD3's own are the methods below.  Parameter
     sharing is not here.  On a ring filled through replay.NStepAppender the head's target is the n-step one when the learner is given
     gamma=app.bootstrap_gamma."""
 
     def __init__(self, buffer, actor, critic=None, critic2=None, *, critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3,
                  lr_critic=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=2, policy_delay=2, target_noise=0.2,
                  noise_clip=0.5, seed=0):
-        if critic2 is not None and critic2 is critic:
-            raise ValueError("critic2 is critic itself: the second critic is a network of its own")
         if isinstance(policy_delay, bool) or not isinstance(policy_delay, int) or policy_delay < 1:
             raise ValueError(f"policy_delay must be an int >= 1, got {policy_delay!r}")
         if int(updates) < 1 or int(updates) % policy_delay:
             raise ValueError(f"updates must be a multiple of policy_delay = {policy_delay} (a call keeps the schedule), got {updates!r}")
         self.policy_delay = policy_delay
         self.target_noise, self.noise_clip = _hyper("target_noise", target_noise, _WEIGHT), _hyper("noise_clip", noise_clip, _WEIGHT)
-        self.seed = int(seed)
-        super().__init__(buffer, actor, critic, critic_input=critic_input, gamma=gamma, tau=tau, lr_actor=lr_actor, lr_critic=lr_critic,
-                         betas=betas, eps=eps, max_grad_norm=max_grad_norm, updates=updates)
-        nA, B, Dc, dev = self.nA, self.B, self.Dc, self._x_cur.device
-        if critic2 is None:
-            critic2 = StackedActor(nA, Dc, 1, device=dev)
-        have = tuple(getattr(critic2, a, None) for a in ("n_actors", "obs_len", "n_actions"))
-        if have != (nA, Dc, 1):
-            raise ValueError(f"critic2 must be a StackedActor{(nA, Dc, 1)} for this buffer and critic_input={critic_input!r}, got "
-                             f"{'StackedActor' + str(have) if None not in have else type(critic2).__name__}")
-        _check_mlp(critic2, self._x_cur, False, "TD3Learner")
-        self.critic2, self.target_critic2 = critic2, copy.deepcopy(critic2)
-        self.target_critic2.__dict__.pop("_bsx_mlp_buffers", None)
-        self.target_critic2.requires_grad_(False)
-        self._blob_c2, self._blob_tc2 = critic2.pack(), self.target_critic2.pack()
-        self.adam_critic2 = AdamState(critic2)
-        f = _f32(torch.zeros, dev)
-        self._g_q2, self._q2, self._q2_next = f(B, nA, 4), f(B, nA), f(B, nA)
-        self._noise_draws = torch.zeros(1, dtype=torch.int64, device=dev)       # the smoothing's sequence word, advanced once per smoothed update
-        self._head_ws = _workspace(None, td3_head_workspace_bytes(B, nA), dev)
-        self._adam_ws = _workspace(None, max(mlp_adam_step_workspace_bytes(nA, 1), mlp_adam_step_workspace_bytes(nA, 2)), dev)
-        self._buf_c2 = _buffers(critic2).get(B, nA, Dc, dev)
+        super().__init__(buffer, actor, critic, critic2, seed=seed, gx2=False, critic_input=critic_input, gamma=gamma, tau=tau, lr_actor=lr_actor,
+                         lr_critic=lr_critic, betas=betas, eps=eps, max_grad_norm=max_grad_norm, updates=updates)
 
-    def _update(self, u):
-        """Update u of a call: the six steps of the class's docstring."""
-        lib, buf = _lib.load(), self.buffer
-        buf.sample()
-        obs, obs_next, act, rew, done = buf._b_obs, buf._b_obs_, buf._b_act, buf._b_rew, buf._b_done
-        Do, k, c = self.Do, self.k, self.central
-        ddpg_inputs(obs, obs_next, act, central=c, out=(self._x_cur, self._x_next, self._x_pi))
-        _mlp_forward(lib, self._blob_ta, obs_next, self._y4)
-        if self.target_noise > 0.0:
-            td3_smooth_actions(self._y4, self._x_next, Do, k, sigma=self.target_noise, clip=self.noise_clip, seed=self.seed,
-                               seq_base=self._noise_draws, central=c)
-            self._noise_draws.add_(1)                            # fresh noise next update, and on every replay of a captured graph
-        else:
-            ddpg_put_actions(self._y4, self._x_next, Do, k, central=c, own_only=False)
-        _mlp_forward(lib, self._blob_tc, self._x_next, self._yq4, self._q_next)
-        _mlp_forward(lib, self._blob_tc2, self._x_next, self._yq4, self._q2_next)
-        _mlp_forward(lib, self._blob_c, self._x_cur, self._yq4, self._q)
-        _mlp_forward(lib, self._blob_c2, self._x_cur, self._yq4, self._q2)
-        td3_head(self._q, self._q2, self._q_next, self._q2_next, rew, done, self.gamma, weight=buf.weights if self._prioritized else None,
-                 out=(self._g_q, self._g_q2, self._g_pi, self.td, self.stats[u]), workspace=self._head_ws)
-        if self._prioritized:
-            buf.update_priorities(self._q, self.td)
-        row_c = _mlp_grad(lib, self._buf_c, self._blob_c, self._x_cur, self._g_q, False)
-        row_c2 = _mlp_grad(lib, self._buf_c2, self._blob_c2, self._x_cur, self._g_q2, False)
-        delayed = (u + 1) % self.policy_delay == 0
-        both = dict(targets=[self.target_critic, self.target_critic2], target_blobs=[self._blob_tc, self._blob_tc2]) if delayed else {}
-        mlp_adam_step([self.critic, self.critic2], [row_c, row_c2], [self.adam_critic, self.adam_critic2], [self._blob_c, self._blob_c2],
-                      self.hyper_critic, self.step_critic, stats=self.step_stats_critic[u], workspace=self._adam_ws, **both)
-        if not delayed:
-            return
-        _mlp_forward(lib, self._blob_a, obs, self._y4)
-        ddpg_put_actions(self._y4, self._x_pi, Do, k, central=c, own_only=True)
-        _mlp_grad(lib, self._buf_c, self._blob_c, self._x_pi, self._g_pi, False, self._buf_c["gx"])
-        ddpg_action_grad(self._buf_c["gx"], Do, k, central=c, out=self._g_a4)
-        row_a = _mlp_grad(lib, self._buf_a, self._blob_a, obs, self._g_a4, True)
-        mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
-                      targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u], workspace=self._adam_ws)
+    def _next_actions(self):
+        """Step 2: DDPGLearner's without noise; else the smoothed actions, and the sequence word advances."""
+        if not self.target_noise > 0.0:
+            return super()._next_actions()
+        _mlp_forward(_lib.load(), self._blob_ta, self.buffer._b_obs_, self._y4)
+        td3_smooth_actions(self._y4, self._x_next, self.Do, self.k, sigma=self.target_noise, clip=self.noise_clip, seed=self.seed,
+                           seq_base=self._noise_draws, central=self.central)
+        self._noise_draws.add_(1)                                # fresh noise next update, and on every replay of a captured graph
 
-    def _state(self):
-        """Every tensor an update writes that outlives it."""
-        return (super()._state() + [self._noise_draws, self._blob_c2, self._blob_tc2, self.adam_critic2.m, self.adam_critic2.v]
-                + [getattr(net, p) for net in (self.critic2, self.target_critic2) for p in PARAMS])
+    def _head(self, u, weight):
+        c1, c2 = self.critics
+        td3_head(c1.q, c2.q, c1.q_next, c2.q_next, self.buffer._b_rew, self.buffer._b_done, self.gamma, weight=weight,
+                 out=(c1.g_q, c2.g_q, self._g_pi, self.td, self.stats[u]), workspace=self._head_ws)
 
-    def sync(self):
-        """Re-pack all six blobs from their networks, once: for a caller who has edited parameters or targets from outside."""
-        super().sync()
-        self.critic2.pack(out=self._blob_c2)
-        self.target_critic2.pack(out=self._blob_tc2)
+    def _delayed(self, u):
+        return (u + 1) % self.policy_delay == 0
+
+    def _critics_step(self, u):
+        super()._critics_step(u, polyak=self._delayed(u))
+
+    def _actor_half(self, u):
+        if self._delayed(u):
+            super()._actor_half(u)

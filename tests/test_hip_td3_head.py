@@ -68,6 +68,18 @@ def test_the_twin_head_stays_within_the_float32_yardstick_of_the_float64_contrac
 
 
 @pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
+@pytest.mark.parametrize("BnA", T.HEAD_SHAPES, ids=lambda s: "B%d-nA%d" % s)
+def test_the_twin_heads_per_element_outputs_are_the_contracts_bits(BnA, weight):
+    """g_q1, g_q2, g_pi and td against td3_util.contract32, the header's contract operation by operation in float32: the same bits at
+    every shape, not only within the yardstick (the statistics are sums and stay with the test above)."""
+    inp, *_ = T.td3_case(*BnA, weight)
+    res, _ = _head(inp, weight)
+    want = T.contract32(inp, weight=weight)
+    for k in T.TD_NAMES:
+        assert np.array_equal(_bits(getattr(res, k)), want[k].astype(np.float32).view(np.int32)), k
+
+
+@pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
 @pytest.mark.parametrize("BnA", (T.HEAD_SHAPES[2], T.HEAD_SHAPES[-1]), ids=lambda s: "B%d-nA%d" % s)
 def test_with_the_second_critic_a_copy_of_the_first_the_head_is_bsx_td_heads_bit_for_bit(BnA, weight):
     from deep_rl_battlespace_amd.learner import td_head
