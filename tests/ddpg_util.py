@@ -1,14 +1,15 @@
 """What the tests of the DDPG head kernels (csrc/bsx_ddpg_head.hip: learner.ddpg_inputs, ddpg_put_actions, td_head, ddpg_action_grad)
-and of DDPGLearner share:
+and of DDPGLearner share, on top of tests/offpolicy_util.py (the head's machinery, the reference step, the kink filter, Hand, the bandit):
 
   SHAPES / plan      (B, nA, Do, k, central) at the smallest sizes each mechanism can go wrong at; the head's launch plan restated
-  join, ref_inputs, ref_put_actions, ref_action_grad, ref_td_head   the contracts of include/battlespace_hip.h restated in numpy: the
-                     three copies on arrays of any dtype (they move bits), the TD head in float64
-  td_inputs / torch_td / td_case / check_td   the TD head's inputs (rounded to float32 once), the head as a torch user writes it with
-                     autograd from q -- in float64 the check of the restatement, in float32 the yardstick --, both cached per shape, and
-                     yardstick_util's bounds: (2 x mean, 4 x max) of the yardstick's error for g_q, g_pi and td (a wider factor only
-                     where profiles/ddpg_float64.json records one and why), stats within its scalar_bound of own_error, the
-                     yardstick's own error over 9 row orders
+  join, ref_inputs, ref_put_actions, ref_action_grad   the three copies' contracts of include/battlespace_hip.h restated in numpy, on
+                     arrays of any dtype (they move bits)
+  td_inputs / HEAD   the TD head's inputs (rounded to float32 once) and its kind: the target from q_next, g_q and g_pi.  offpolicy_util.Head
+                     writes the rest over that: the float64 contract, the head as a torch user writes it with autograd from q -- in
+                     float64 the check of the restatement, in float32 the yardstick --, both cached per shape, and yardstick_util's
+                     bounds: (2 x mean, 4 x max) of the yardstick's error for g_q, g_pi and td (a wider factor only where
+                     profiles/ddpg_float64.json records one and why), stats within its scalar_bound of own_error, the yardstick's own
+                     error over 9 row orders
   learner_case       networks (mlp_grad_util.make_net "gains", w3 scaled by 60 and 100 as mlp_grad_util.ddpg_case does), ring rows, a
                      fixed batch and the row weights that leave every ReLU kink out, chosen in float64 alone
   joined / joined_pi the critic's inputs as a torch user writes them: the one torch statement of the join every composition here reads
@@ -19,10 +20,10 @@ and of DDPGLearner share:
                      the stepped critic's kinks out too (a fixed point); wrong_variants: the misreadings the case tells apart;
                      stepped_spread / stepped_exceptions / stepped_factor_of: the yardstick's own spread over row orders and the factors
                      profiles/ddpg_float64.json records from it; check_step: adam_case_util.meets_the_bars' bars on one network
-  Hand               one update by hand from the public primitives, holding what a DDPGLearner holds under the same names
+  Hand, SUITE        one update by hand from the public primitives, holding what a DDPGLearner holds under the same names
   snapshot           every tensor an update writes, as bits
-  torch_update       the torch composition: StackedActor under autograd, clip_grad_norm_, torch Adam, foreach Polyak
-  bandit / reward    the learning check's ring and its held-out reward
+  torch_update, bandit_torch_run   the torch composition: StackedActor under autograd, clip_grad_norm_, torch Adam, foreach Polyak; what
+                     it reaches on the bandit
 
 Nothing here imports the native library at import time."""
 import copy
@@ -35,9 +36,9 @@ import torch
 
 import actor_grad_util as U
 import actor_ref_util as R
-import adam_mlp_util as AM
 import adam_util as AU
 import mlp_grad_util as M
+import offpolicy_util as O
 import yardstick_util as Y
 
 PARAMS = U.PARAMS
@@ -54,7 +55,7 @@ LARGE = SHAPES[-1]
 LEARNER_SHAPES = ((64, 2, 5, 4, 0), (161, 2, 8, 4, 1), (129, 3, 11, 4, 1), (97, 1, 5, 3, 0), (97, 1, 5, 3, 1), (96, 2, 8, 3, 1),
                   (65, 4, 14, 4, 0), (130, 16, 50, 4, 0), (1, 1, 5, 4, 1))
 KINK_SHAPES = ((161, 2, 8, 4), (129, 3, 11, 4), (97, 1, 5, 3), (130, 16, 50, 4))
-GAMMA = 0.95
+GAMMA = O.GAMMA
 # learner_case's generators start here.  Picked on the float64 reference alone: the share of elements the kink filter leaves out moves
 # between 0.6 % and 5.7 % from seed to seed (384 hidden values per element, each within 1e-4 of 0 with probability ~1e-4); of the bases
 # 0, 10, 20, 30 this is the one at which seeds 0 .. 2 stay under actor_grad_util.KINK_CAP at every shape of KINK_SHAPES (1.0 % .. 4.4 %)
@@ -66,16 +67,13 @@ CASE_SEED = 30
 KW = dict(gamma=GAMMA, tau=0.05, lr_actor=1e-3, lr_critic=2e-3, max_grad_norm=0.5)
 STEP_KW = dict(KW, betas=(0.9, 0.999), eps=1e-3)
 # stepped_case's seed per shape, 0 where none is given.  Picked on the float64 reference alone, as CASE_SEED was: per shape the first
-# seed from 0 at which the kink filter closes within MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP.
+# seed from 0 at which the kink filter closes within offpolicy_util.MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP.
 # Measured (share left out / rounds): 3v3 central 5.68 % / 2 at seed 0 and 4.65 % / 4 at seed 1; 16 agents own 6.25 % / 9 and
 # 4.66 % / 4; every other shape passes at seed 0 (0 % .. 4.04 %, 0 .. 2 rounds).  One base for all shapes was looked for first
 # (80 bases): the 16-agent shape passes at one base in five (zeroing a row moves its agent's stepped critic by about KINK, so the
 # filter closes slowly) and no base passed everywhere.  (96, 2, 8, 3, 1), the 2v2 k = 3 shape, passes at seed 0 as it is
 STEP_SEEDS = {(129, 3, 11, 4, 1): 1, (130, 16, 50, 4, 0): 1}
-MAX_ROUNDS = 4                                      # of stepped_case's kink filter
 SHARP = ("w1", "w2", "w3", "b3")                     # the tensors the sharpness check of test_ddpg_cpu.py reads
-TD_NAMES = ("g_q", "g_pi", "td")
-STAT_NAMES = ("critic_loss", "q", "target", "abs_td", "done", "weight")       # stats[1..6]
 
 
 def shape_id(s):
@@ -167,23 +165,6 @@ def batch_arrays(shape, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------ the TD head
-def ref_td_head(inp, gamma=GAMMA, weight=True):
-    """The contract in float64 numpy -> dict(g_q, g_pi [B, nA, 4], td [B, nA], stats [8]).  inp: td_inputs'; weight=False: w = 1."""
-    f = {k: v.double().numpy() for k, v in inp.items()}
-    B, nA = f["q"].shape
-    over = f["done"] != 0
-    w = f["weight"] if weight else np.ones((B, nA))
-    with np.errstate(all="ignore"):
-        y = gamma * np.where(over, 0.0, f["q_next"]) + f["rew"]
-    d = f["q"] - y
-    g_q, g_pi = np.zeros((B, nA, 4)), np.zeros((B, nA, 4))
-    g_q[..., 0] = w * d * (2.0 / B)
-    g_pi[..., 0] = -w * (1.0 / B)
-    n = float(B * nA)
-    stats = np.array([n, (w * d * d).sum() / n, f["q"].sum() / n, y.sum() / n, np.abs(d).sum() / n, over.sum() / n, w.sum() / n, 0.0])
-    return dict(g_q=g_q, g_pi=g_pi, td=y, stats=stats)
-
-
 def td_inputs(B, nA, seed=0):
     """{q, q_next, rew, weight: float32, done: uint8} CPU tensors [B, nA]: normals, done Bernoulli 0.2, weights uniform in [0.5, 1.5]."""
     g = torch.Generator().manual_seed(8000 + seed + 7 * B + nA)
@@ -192,59 +173,8 @@ def td_inputs(B, nA, seed=0):
                 weight=torch.rand((B, nA), generator=g) + 0.5)
 
 
-def torch_td(inp, dtype, gamma=GAMMA, weight=True, perm=None):
-    """The head as a torch user writes it, on the CPU in `dtype`, with autograd from q -> dict of float64 numpy (g_q and g_pi padded to
-    4 columns; the statistics computed in `dtype`).  perm: the rows in another order (the gradients come back in the original one)."""
-    t = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in inp.items()}
-    if perm is not None:
-        t = {k: v[perm] for k, v in t.items()}
-    q, q_pi = t["q"].clone().requires_grad_(), t["q"].clone().requires_grad_()
-    w = t["weight"] if weight else torch.ones_like(t["q"])
-    y = t["rew"] + gamma * (1.0 - t["done"].to(dtype)) * t["q_next"]
-    critic_loss = (w * (q - y) ** 2).mean(0).sum()
-    actor_loss = -(w * q_pi).mean(0).sum()
-    critic_loss.backward()
-    actor_loss.backward()
-    g_q, g_pi = torch.zeros((*q.shape, 4), dtype=dtype), torch.zeros((*q.shape, 4), dtype=dtype)
-    g_q[..., 0], g_pi[..., 0] = q.grad, q_pi.grad
-    td = y
-    if perm is not None:
-        inv = torch.argsort(perm)
-        g_q, g_pi, td = g_q[inv], g_pi[inv], td[inv]
-    with torch.no_grad():
-        d = q - y
-        num = lambda x: float(x.double())                     # noqa: E731
-        stats = np.array([float(q.numel()), num((w * d * d).mean()), num(q.mean()), num(y.mean()), num(d.abs().mean()),
-                          num(t["done"].to(dtype).mean()), num(w.mean()), 0.0])
-    return dict(g_q=g_q.double().numpy(), g_pi=g_pi.double().numpy(), td=td.detach().double().numpy(), stats=stats)
-
-
-@functools.lru_cache(maxsize=None)
-def td_case(B, nA, weight=True, perms=8):
-    """(inputs, float64 reference, float32 yardstick, the yardstick's own error on stats [8]: the largest over the given order and
-    `perms` permutations of the rows).  Computed once and shared: read-only."""
-    inp = td_inputs(B, nA)
-    ref, yard = ref_td_head(inp, weight=weight), torch_td(inp, torch.float32, weight=weight)
-    return inp, ref, yard, Y.own_error(lambda order: torch_td(inp, torch.float32, weight=weight, perm=order), ref, B, perms)[0]
-
-
-@functools.lru_cache(maxsize=None)
-def factors():
-    """{tensor: (mean factor, max factor)}: the project's (2, 4), or what profiles/ddpg_float64.json records for a tensor (with why)."""
-    return {k: Y.factor_of(Y.recorded(PROFILE, "factors"))(k) for k in TD_NAMES}
-
-
-def check_td(got, ref, yard, e_stats, what=""):
-    """got: dict(g_q, g_pi, td, stats) of float64 numpy from the kernel.  Prints every figure, then asserts."""
-    bad = Y.check_tensors([(k, got[k], ref[k], yard[k], factors()[k]) for k in TD_NAMES], what, unit="x")[1]
-    bad += stats_out_of_bounds(got["stats"], ref["stats"], e_stats, what)
-    assert not bad, (what, bad)
-
-
-def stats_out_of_bounds(got, ref, e_stats, what=""):
-    """The statistics' part of check_td -> the names out of bounds.  got, ref: float64 [8]; prints every figure."""
-    counts = [] if got[0] == ref[0] and got[7] == 0.0 else ["n"]
-    return counts + Y.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, what)
+# y = r + gamma (1 - done) Q'(x_next); g_q from the critic's loss, g_pi from -mean w Q; stats[7] = 0
+HEAD = O.Head(td_inputs, ("q",), True, lambda f: f["q_next"], lambda t: t["q_next"], "td_head", ("q", "q_next", "rew", "done", "gamma"), PROFILE)
 
 
 # ------------------------------------------------------------------------------------------------ the learner's case
@@ -324,49 +254,8 @@ def maddpg_grads(actor, critic, batch, w, central, dtype, gamma=GAMMA, target_ac
 
 
 # ------------------------------------------------------------------------------------------------ a whole update with distinct targets
-def _net_of(arrays, like, dtype):
-    """A StackedActor of `like`'s shape on the CPU in `dtype` holding the ten arrays."""
-    net = R._new(like.n_actors, like.obs_len, like.n_actions, dtype=dtype)
-    with torch.no_grad():
-        for p, x in zip(PARAMS, arrays):
-            getattr(net, p).copy_(torch.as_tensor(np.asarray(x)).to(dtype))
-    return net
-
-
-def _step64(net, grads, target, lr, kw):
-    """adam_mlp_util.reference_step of a network's first step from zero moments -> dict(p, m, v, target: lists of ten float64 arrays,
-    norm, coef, net: the stepped network in float64)."""
-    hp = AU.hyper32(lr, *kw["betas"], kw["eps"], kw["max_grad_norm"] or 0.0)
-    P0 = AU.net_arrays(net)
-    Z = [np.zeros(x.shape) for x in P0]
-    P, M_, V, T, _, norm, coef = AM.reference_step(P0, [grads[p] for p in PARAMS], Z, Z, AU.net_arrays(target), 0, hp,
-                                                   float(np.float32(kw["tau"])))
-    return dict(p=P, m=M_, v=V, target=T, norm=norm, coef=coef, net=_net_of(P, net, torch.float64))
-
-
-def _step32(net, grads, target, lr, kw):
-    """The same step as a torch user takes it, in float32 on the CPU: clip_grad_norm_, torch.optim.Adam, target.mul_(1 - tau).add_(p,
-    alpha=tau) (adam_case_util.TorchPath's composition) -> the same dict, the arrays float32."""
-    hp = AU.hyper32(lr, *kw["betas"], kw["eps"], kw["max_grad_norm"] or 0.0)
-    tau = float(np.float32(kw["tau"]))
-    ps = [getattr(net, p).detach().clone().float().requires_grad_() for p in PARAMS]
-    ts = [getattr(target, p).detach().clone().float() for p in PARAMS]
-    for p, name in zip(ps, PARAMS):
-        p.grad = torch.from_numpy(grads[name]).float()
-    if hp["max_grad_norm"] > 0.0:
-        torch.nn.utils.clip_grad_norm_(ps, hp["max_grad_norm"])
-    opt = torch.optim.Adam(ps, lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
-    opt.step()
-    with torch.no_grad():
-        for t, p in zip(ts, ps):
-            t.mul_(1.0 - tau).add_(p, alpha=tau)
-    f = lambda xs: [x.detach().numpy() for x in xs]               # noqa: E731
-    return dict(p=f(ps), m=f([opt.state[p]["exp_avg"] for p in ps]), v=f([opt.state[p]["exp_avg_sq"] for p in ps]), target=f(ts),
-                net=_net_of(f(ps), net, torch.float32))
-
-
 def _q_inputs(actor, critic, ta, tc, batch, w, central, dtype):
-    """ref_td_head's inputs of a batch: q = the critic on x_cur and q_next = the target critic on x_next (a' from the target actor),
+    """HEAD.ref's inputs of a batch: q = the critic on x_cur and q_next = the target critic on x_next (a' from the target actor),
     both evaluated on the CPU in `dtype`."""
     obs, act, rew, obs_next, done = batch
     to = lambda n: U._to(n, "cpu", dtype)                          # noqa: E731
@@ -379,18 +268,17 @@ def _q_inputs(actor, critic, ta, tc, batch, w, central, dtype):
 
 def update_reference(actor, critic, ta, tc, batch, w, central, dtype, kw=None, perm=None):
     """One whole update on the CPU in `dtype` (float64: the reference, with adam_mlp_util.reference_step as the two steps; float32:
-    the yardstick, torch's own Adam) -> dict(gc, ga: {tensor: grad}; critic, actor: _step64's / _step32's dict; inp: the TD head's
-    inputs).  The five parts: the critic's gradient with the target networks in y; the critic's step with its Polyak target; the
+    the yardstick, torch's own Adam) -> dict(gc, ga: {tensor: grad}; critic, actor: offpolicy_util.first_step's dict; inp: the TD
+    head's inputs).  The five parts: the critic's gradient with the target networks in y; the critic's step with its Polyak target; the
     actor's gradient at THAT critic; the actor's step with its target; the TD head's inputs for the statistics.
     perm: the batch's rows in another order (another float32 summation order of the same sums)."""
     kw = kw or STEP_KW
     if perm is not None:
         batch, w = tuple(t[perm] for t in batch), w[perm]
     gc, _ = maddpg_grads(actor, critic, batch, w, central, dtype, kw["gamma"], ta, tc)
-    step = _step64 if dtype == torch.float64 else _step32
-    sc = step(critic, gc, tc, kw["lr_critic"], kw)
+    sc, = O.first_step([critic], [gc], [tc], kw["lr_critic"], kw, dtype)
     _, ga = maddpg_grads(actor, critic, batch, w, central, dtype, kw["gamma"], ta, tc, critic_pi=sc["net"])
-    sa = step(actor, ga, ta, kw["lr_actor"], kw)
+    sa, = O.first_step([actor], [ga], [ta], kw["lr_actor"], kw, dtype)
     return dict(gc=gc, ga=ga, critic=sc, actor=sa, inp=_q_inputs(actor, critic, ta, tc, batch, w, central, dtype))
 
 
@@ -412,7 +300,7 @@ def stepped_case(shape, seed=None):
                          actor_grad_util.KINK of 0 at x_pi -- zeroing rows moves the critic's gradient and so the stepped critic, so the
                          filter is repeated to its fixed point (`rounds` zeroing rounds, at most 4); share: the part left out at the end
       ref, yard          update_reference in float64 and in float32
-      stats, e_stats     ref_td_head's float64 statistics and the float32 yardstick's own error on them over 9 row orders (td_case's)
+      stats, e_stats     HEAD.ref's float64 statistics and the float32 yardstick's own error on them over 9 row orders (td_case's)
     Read-only."""
     central = shape[4]
     seed = STEP_SEEDS.get(shape, 0) if seed is None else seed
@@ -421,20 +309,14 @@ def stepped_case(shape, seed=None):
     ta, tc = perturbed(actor, g), perturbed(critic, g)
     batch = tuple(r[idx] for r in rows)
     x_pi = joins64(actor, batch[0], batch[3], batch[1], central)[2]
-    w, rounds = w0.clone(), 0
-    while True:
-        ref = update_reference(actor, critic, ta, tc, batch, w, central, torch.float64)
-        near = U.near_kink((ref["critic"]["net"], x_pi)) & (w != 0)
-        if not near.any():
-            break
-        rounds += 1
-        assert rounds <= MAX_ROUNDS, (shape, seed, rounds)
-        w[near] = 0.0
+    ref, w, rounds = O.kink_fixed_point(w0, lambda w: update_reference(actor, critic, ta, tc, batch, w, central, torch.float64),
+                                        lambda ref: U.near_kink((ref["critic"]["net"], x_pi)))
+    assert ref is not None, (shape, seed, rounds)
     yard = update_reference(actor, critic, ta, tc, batch, w, central, torch.float32)
-    stats = ref_td_head(ref["inp"])["stats"]
+    stats = HEAD.ref(ref["inp"])["stats"]
     return types.SimpleNamespace(seed=seed, actor=actor, critic=critic, ta=ta, tc=tc, rows=rows, idx=idx, batch=batch, w=w, rounds=rounds,
                                  share=float((w == 0).double().mean()), ref=ref, yard=yard, stats=stats,
-                                 e_stats=Y.own_error(lambda order: torch_td(yard["inp"], torch.float32, perm=order), dict(stats=stats), shape[0])[0])
+                                 e_stats=Y.own_error(lambda order: HEAD.autograd(yard["inp"], torch.float32, perm=order), dict(stats=stats), shape[0])[0])
 
 
 def wrong_variants(case, central):
@@ -444,8 +326,7 @@ def wrong_variants(case, central):
     f = lambda **k: maddpg_grads(c.actor, c.critic, c.batch, c.w, central, torch.float64, STEP_KW["gamma"], **k)     # noqa: E731
     wrong = {"live nets as targets": (f()[0], "gc"), "live actor only": (f(target_critic=c.tc)[0], "gc"),
              "live critic only": (f(target_actor=c.ta)[0], "gc"), "actor at the unstepped critic": (f()[1], "ga")}
-    dist = lambda a, b: {p: float(np.abs(a[p] - b[p]).mean()) for p in SHARP}       # noqa: E731
-    return {name: (dist(g, c.ref[which]), dist(c.yard[which], c.ref[which])) for name, (g, which) in wrong.items()}
+    return {name: O.distances(g, c.ref[which], c.yard[which], SHARP) for name, (g, which) in wrong.items()}
 
 
 def stepped_spread(shape, perms=8):
@@ -487,82 +368,28 @@ def snapshot(x):
     return {k: (v.view(torch.int32) if v.dtype == torch.float32 else v.view(torch.int64) if v.dtype == torch.float64 else v) for k, v in out.items()}
 
 
-def differing(a, b):
-    return [k for k in a if not torch.equal(a[k], b[k])]
-
-
-class Hand:
-    """What a DDPGLearner holds, under the same names, and its update written out with the public primitives alone: the ring's
-    sample(), ddpg_inputs, bsx_mlp_forward, ddpg_put_actions, td_head, mlp_grad (its padded copy of grad_out included), mlp_adam_step,
-    ddpg_action_grad."""
-
-    def __init__(self, buffer, actor, critic, central, gamma=GAMMA, tau=0.01, lr_actor=1e-3, lr_critic=1e-3, max_grad_norm=None, updates=1,
-                 betas=(0.9, 0.999), eps=1e-8):
-        from deep_rl_battlespace_amd import learner as L
-        self.buffer, self.actor, self.critic, self.central, self.gamma = buffer, actor, critic, bool(central), gamma
-        self.target_actor, self.target_critic = copy.deepcopy(actor), copy.deepcopy(critic)
-        for t in (self.target_actor, self.target_critic):
-            t.__dict__.pop("_bsx_mlp_buffers", None)
-        self._blob_a, self._blob_c, self._blob_ta, self._blob_tc = (n.pack() for n in (actor, critic, self.target_actor, self.target_critic))
-        dev = actor.w1.device
-        self.adam_actor, self.adam_critic = L.AdamState(actor), L.AdamState(critic)
-        self.hyper_actor = L.adam_hyper(lr_actor, betas, eps, max_grad_norm, dev, tau)
-        self.hyper_critic = L.adam_hyper(lr_critic, betas, eps, max_grad_norm, dev, tau)
-        self.step_actor, self.step_critic = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
-        self.stats = torch.zeros((updates, 8), dtype=torch.float64, device=dev)
-        self.step_stats_actor, self.step_stats_critic = (torch.zeros((updates, 4), dtype=torch.float64, device=dev) for _ in range(2))
-        self.updates = updates
-
-    def update(self):
-        for u in range(self.updates):
-            s = self.buffer.sample()
-            self.step(s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6], u)
-        return self.stats
+class Hand(O.Hand):
+    """What a DDPGLearner holds, under the same names, and its update written out with the public primitives alone: offpolicy_util.Hand's
+    and ddpg_inputs, td_head."""
 
     def step(self, obs, act, rew, obs_next, done, u, weight=None, adam=True):
         """The ten steps on a batch -> (critic row, actor row): copies of mlp_grad's cached rows."""
-        from deep_rl_battlespace_amd import _lib, learner as L
-        lib, c = _lib.load(), self.central
+        from deep_rl_battlespace_amd import learner as L
+        c = self.central
         obs, act, obs_next = obs.contiguous(), act.contiguous(), obs_next.contiguous()
-        (B, nA, Do), k, dev = obs.shape, act.shape[2], obs.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-
-        def forward(blob, x, raw=False):
-            y4 = torch.empty((B, nA, 4), device=dev)
-            r = torch.empty((B, nA), device=dev) if raw else None
-            _lib.check(lib.bsx_mlp_forward(blob.data_ptr(), x.data_ptr(), y4.data_ptr(), r.data_ptr() if raw else None, B, nA, x.shape[2], stream),
-                       "bsx_mlp_forward")
-            return r if raw else y4
+        Do, k = obs.shape[2], act.shape[2]
         x_cur, x_next, x_pi = L.ddpg_inputs(obs, obs_next, act, central=c)
-        L.ddpg_put_actions(forward(self._blob_ta, obs_next), x_next, Do, k, central=c, own_only=False)
-        q_next, q = forward(self._blob_tc, x_next, True), forward(self._blob_c, x_cur, True)
+        L.ddpg_put_actions(self.forward(self._blob_ta, obs_next), x_next, Do, k, central=c, own_only=False)
+        q_next, q = self.forward(self._blob_tc, x_next, True), self.forward(self._blob_c, x_cur, True)
         head = L.td_head(q, q_next, rew, done, self.gamma, weight=weight)
         self.stats[u].copy_(head.stats)
-        row_c = L.mlp_grad(self.critic, self._blob_c, x_cur, head.g_q[..., :1].contiguous(), squash=False, input_grad=False)[0].clone()
+        row_c, = self.critic_rows(x_cur, [head.g_q])
         if adam:
-            L.mlp_adam_step([self.critic], [row_c], [self.adam_critic], [self._blob_c], self.hyper_critic, self.step_critic,
-                            targets=[self.target_critic], target_blobs=[self._blob_tc], stats=self.step_stats_critic[u])
-        L.ddpg_put_actions(forward(self._blob_a, obs), x_pi, Do, k, central=c, own_only=True)
-        _, gx = L.mlp_grad(self.critic, self._blob_c, x_pi, head.g_pi[..., :1].contiguous(), squash=False, input_grad=True)
-        g_a4 = L.ddpg_action_grad(gx, Do, k, central=c)
-        row_a = L.mlp_grad(self.actor, self._blob_a, obs, g_a4[..., :k].contiguous(), squash=True, input_grad=False)[0].clone()
-        if adam:
-            L.mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
-                            targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u])
-        return row_c, row_a
+            self.critics_step([row_c], u)
+        return row_c, self.deterministic_actor_step(obs, x_pi, head.g_pi, k, u, adam)
 
 
-def ring(rows, B, seed=3, device="cuda"):
-    """A DeviceReplayBuffer of len(rows) transitions filled through _put with `rows` (ring_rows'), batches of B."""
-    from deep_rl_battlespace_amd.replay import DeviceReplayBuffer
-    obs, act, rew, obs_next, done = rows
-    N, nA, Do = obs.shape
-    buf = DeviceReplayBuffer(N, B, list(range(nA)), Do, Do * nA, act.shape[2], device=device, seed=seed)
-    buf._put(obs.to(device), act.to(device), rew.to(device), obs_next.to(device), done.to(device))
-    return buf
-
-
-gpu_copy = U._to
+SUITE = O.Suite("DDPGLearner", Hand, learner_case, KW)
 
 
 # ------------------------------------------------------------------------------------------------ the torch composition, the bandit
@@ -582,50 +409,18 @@ def torch_update(actor, critic, target_actor, target_critic, opt_a, opt_c, batch
     if max_grad_norm is not None:
         torch.nn.utils.clip_grad_norm_(actor.parameters(), max_grad_norm)
     opt_a.step()
-    with torch.no_grad():
-        for t, n in ((target_actor, actor), (target_critic, critic)):
-            ts, ns = list(t.parameters()), list(n.parameters())
-            torch._foreach_mul_(ts, 1.0 - tau)
-            torch._foreach_add_(ts, ns, alpha=tau)
-
-
-BANDIT = dict(nA=2, Do=5, k=4, rows=2048, B=256, held_out=1024, lr=1e-3, tau=0.01)
-
-
-def bandit_reward(obs, a):
-    """r = -mean_k (a_k - 0.5 sign(o_k))^2 over the k action columns, against the first k observation columns -> [.., nA]."""
-    return -((a - 0.5 * torch.sign(obs[..., :a.shape[-1]])) ** 2).mean(-1)
-
-
-def bandit_rows(seed=0):
-    """The bandit ring (every row finished: done = 1, the next observation plays no part) and a held-out observation set."""
-    b = BANDIT
-    g = torch.Generator().manual_seed(9900 + seed)
-    uni = lambda *s: torch.rand(s, generator=g) * 2 - 1       # noqa: E731
-    obs, act = uni(b["rows"], b["nA"], b["Do"]), uni(b["rows"], b["nA"], b["k"])
-    rows = (obs, act, bandit_reward(obs, act), uni(b["rows"], b["nA"], b["Do"]), torch.ones((b["rows"], b["nA"]), dtype=torch.bool))
-    return rows, uni(b["held_out"], b["nA"], b["Do"])
-
-
-def bandit_nets(seed=0):
-    """(actor, critic) on the CPU, freshly initialised (own critic: 9 -> 1)."""
-    b = BANDIT
-    torch.manual_seed(9950 + seed)
-    return R._new(b["nA"], b["Do"], b["k"]), R._new(b["nA"], b["Do"] + b["k"], 1)
+    O.polyak_((target_actor, target_critic), (actor, critic), tau)
 
 
 def bandit_torch_run(N, seed=0):
-    """(initial reward, reward after N updates) of the torch composition on the CPU: batches drawn with a torch generator."""
-    b = BANDIT
-    rows, held = bandit_rows(seed)
-    actor, critic = bandit_nets(seed)
-    ta, tc = copy.deepcopy(actor), copy.deepcopy(critic)
-    oa, oc = torch.optim.Adam(actor.parameters(), lr=b["lr"]), torch.optim.Adam(critic.parameters(), lr=b["lr"])
-    g = torch.Generator().manual_seed(9990 + seed)
-    with torch.no_grad():
-        r0 = float(bandit_reward(held, actor(held)).mean())
-    for _ in range(N):
-        idx = torch.randint(0, b["rows"], (b["B"],), generator=g)
-        torch_update(actor, critic, ta, tc, oa, oc, tuple(r[idx] for r in rows), False, tau=b["tau"])
-    with torch.no_grad():
-        return r0, float(bandit_reward(held, actor(held)).mean())
+    """(initial reward, reward after N updates) of the torch composition on offpolicy_util's bandit, on the CPU."""
+    b = O.BANDIT
+
+    def compose(seed):
+        actor, critic = O.bandit_nets(seed)
+        ta, tc = copy.deepcopy(actor), copy.deepcopy(critic)
+        oa, oc = torch.optim.Adam(actor.parameters(), lr=b["lr"]), torch.optim.Adam(critic.parameters(), lr=b["lr"])
+        return actor, lambda u, batch, g: torch_update(actor, critic, ta, tc, oa, oc, batch, False, tau=b["tau"])
+    return O.bandit_torch_run(N, compose, seed)
+
+

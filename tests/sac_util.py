@@ -1,17 +1,17 @@
 """What the tests of the SAC kernels (csrc/bsx_sac_head.hip: learner.sac_sample_actions, sac_head, sac_policy_seed, sac_policy_grad) and of
-SACLearner share, on top of tests/td3_util.py and tests/ddpg_util.py (the shapes, the joins, the learner's case, the joint step, the
-bandit), yardstick_util (the bars), philox_util (normals4), adam_util / adam_mlp_util (the float64 steps) and guard_util:
+SACLearner share, on top of tests/offpolicy_util.py (the head's machinery, the reference step, the kink filter, Hand, the bandit),
+tests/td3_util.py and tests/ddpg_util.py (the shapes, the joins, the learner's case), yardstick_util (the bars) and philox_util (normals4):
 
   gauss, ref_sample, torch_sample      the reparameterised draw and its log-probability: the contract in numpy (any dtype), x after the
                            call, and the draw as a torch user writes it
-  sac_inputs, ref_sac_head, torch_sac, sac_case, contract32, head_spread, factors, check_sac   the soft twin head: its inputs, its contract
-                           in float64 numpy, the head as a torch user writes it with autograd, cached per shape, and the bounds
+  sac_inputs, contract32, HEAD   the soft twin head: its inputs, its float32 contract operation by operation, and its kind: the soft
+                           target min(Q1', Q2') - alpha logp', g_q1 and g_q2 (offpolicy_util.Head writes the rest over that)
   ref_policy_seed, policy_inputs, ref_policy_grad, torch_policy_grad, policy_case, ga32   the seeds bit for bit; sac_policy_grad's contract
                            in float64, as a torch user writes it in float32, and g_a4's float32 restatement
   losses                   L_critic, L_pi and L_alpha as the issue writes them, under torch autograd in any dtype
-  Hand, snapshot, blobs_are_packs   one SAC update by hand from the public primitives, holding what a SACLearner holds under the same names
+  Hand, snapshot, SUITE    one SAC update by hand from the public primitives, holding what a SACLearner holds under the same names
   sac_grads, update_reference, stepped_case, wrong_variants   a whole update in float64 and float32 on the CPU with injected normals
-  torch_update, bandit_rows, bandit_nets, bandit_torch_run   the torch composition of the same SAC and what it reaches on the bandit at k = 3
+  torch_update, bandit_torch_run   the torch composition of the same SAC and what it reaches on the bandit at k = 3
 
 Nothing here imports the native library at import time."""
 import copy
@@ -24,12 +24,12 @@ import numpy as np
 import torch
 
 import ddpg_util as D
-import guard_util as G                # noqa: F401  (the suites take Buffers from here)
+import offpolicy_util as O
 import philox_util as PU
 import td3_util as T
 import yardstick_util as Y
 
-AU, AM, U, R, PARAMS = D.AU, T.AM, D.U, D.R, D.PARAMS
+AU, U, PARAMS = D.AU, D.U, D.PARAMS
 PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sac_float64.json")
 SALT = 0x60000000                                                   # include/battlespace_hip.h: BSX_SAC_SALT
 OTHER_SALTS = T.OTHER_SALTS + (T.SALT,)
@@ -42,11 +42,9 @@ GRAD_SHAPES = tuple(dict.fromkeys((B, nA, Do, 3, c) for B, nA, Do, _, _ in D.SHA
                                   if D.width(nA, Do, 3, c) <= 64)) + ((16385, 16, 1, 3, 0),)
 HAND_SHAPES = ((161, 2, 8, 3, 1), (97, 1, 5, 3, 0), (129, 3, 11, 3, 1), (1, 1, 5, 3, 1))
 MAIN_SHAPES = HAND_SHAPES[:2]
-TD_NAMES = ("g_q1", "g_q2", "td")
-STAT_NAMES = T.STAT_NAMES
 PI_STAT_NAMES = ("actor_loss", "q_pi", "logp", "alpha", "weight", "picked_1")       # stats_pi[1..6]
 # stepped_case's seed per shape: the first from 0 at which, on the float64 reference alone, the kink filter closes within
-# ddpg_util.MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP.  profiles/sac_float64.json records what every
+# offpolicy_util.MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP.  profiles/sac_float64.json records what every
 # seed tried gave
 STEP_SEEDS = {}
 if os.path.exists(PROFILE):
@@ -101,97 +99,28 @@ def sac_inputs(B, nA, seed=0):
                 log_alpha=math.log(0.2) + 0.3 * torch.randn((nA,), generator=g))
 
 
-def ref_sac_head(inp, gamma=D.GAMMA, weight=True):
-    """The contract in float64 numpy -> dict(g_q1, g_q2 [B, nA, 4], td [B, nA], stats [8])."""
-    f = {k: v.double().numpy() for k, v in inp.items()}
-    B, nA = f["q1"].shape
-    over = f["done"] != 0
-    w = f["weight"] if weight else np.ones((B, nA))
-    with np.errstate(all="ignore"):
-        v = np.minimum(f["q1_next"], f["q2_next"]) - np.exp(f["log_alpha"])[None] * f["logp_next"]
-        y = gamma * np.where(over, 0.0, v) + f["rew"]
-    d1, d2 = f["q1"] - y, f["q2"] - y
-    out = {k: np.zeros((B, nA, 4)) for k in ("g_q1", "g_q2")}
-    out["g_q1"][..., 0], out["g_q2"][..., 0] = w * d1 * (2.0 / B), w * d2 * (2.0 / B)
-    n = float(B * nA)
-    stats = np.array([n, (w * (d1 * d1 + d2 * d2)).sum() / n, f["q1"].sum() / n, y.sum() / n, np.abs(d1).sum() / n, over.sum() / n,
-                      w.sum() / n, np.abs(f["q1"] - f["q2"]).sum() / n])
-    return dict(out, td=y, stats=stats)
-
-
-def torch_sac(inp, dtype, gamma=D.GAMMA, weight=True, perm=None):
-    """The head as a torch user writes it, on the CPU in `dtype`, with autograd from q1 and q2 of L_critic = sum_i mean_b w ((Q1 - y)^2 +
-    (Q2 - y)^2), y = r + gamma (1 - done) (min(Q1', Q2') - alpha logp') -> dict of float64 numpy.  perm: the rows in another order."""
-    t = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in inp.items()}
-    la = t.pop("log_alpha")
-    if perm is not None:
-        t = {k: v[perm] for k, v in t.items()}
-    q1, q2 = (t[k].clone().requires_grad_() for k in ("q1", "q2"))
-    w = t["weight"] if weight else torch.ones_like(t["q1"])
-    y = t["rew"] + gamma * (1.0 - t["done"].to(dtype)) * (torch.minimum(t["q1_next"], t["q2_next"]) - torch.exp(la) * t["logp_next"])
-    ((w * (q1 - y) ** 2).mean(0).sum() + (w * (q2 - y) ** 2).mean(0).sum()).backward()
-    gs = {k: torch.zeros((*q1.shape, 4), dtype=dtype) for k in ("g_q1", "g_q2")}
-    gs["g_q1"][..., 0], gs["g_q2"][..., 0] = q1.grad, q2.grad
-    gs["td"] = y
-    if perm is not None:
-        inv = torch.argsort(perm)
-        gs = {k: v[inv] for k, v in gs.items()}
-    with torch.no_grad():
-        d1, d2 = q1 - y, q2 - y
-        num = lambda x: float(x.double())                     # noqa: E731
-        stats = np.array([float(q1.numel()), num((w * (d1 * d1 + d2 * d2)).mean()), num(q1.mean()), num(y.mean()), num(d1.abs().mean()),
-                          num(t["done"].to(dtype).mean()), num(w.mean()), num((q1 - q2).abs().mean())])
-    return dict({k: v.detach().double().numpy() for k, v in gs.items()}, stats=stats)
-
-
-@functools.lru_cache(maxsize=None)
-def sac_case(B, nA, weight=True, perms=8):
-    """(inputs, float64 reference, float32 yardstick, the yardstick's own error on stats [8] over 9 row orders).  Read-only."""
-    inp = sac_inputs(B, nA)
-    ref, yard = ref_sac_head(inp, weight=weight), torch_sac(inp, torch.float32, weight=weight)
-    return inp, ref, yard, Y.own_error(lambda order: torch_sac(inp, torch.float32, weight=weight, perm=order), ref, B, perms)[0]
-
-
-head_id = T.head_id
-
-
 def contract32(inp, gamma=D.GAMMA, weight=True):
     """The header's contract operation by operation in numpy float32 (each fmaf through float64: its product is exact there) -> the
-    three tensors as float64 arrays: a float32 evaluation of the head equivalent to torch_sac's, in the kernel's association."""
+    three tensors as float64 arrays: a float32 evaluation of the head equivalent to HEAD.autograd's, in the kernel's association."""
     f = {k: v.numpy() for k, v in inp.items()}
     B, nA = f["q1"].shape
     w = f["weight"] if weight else np.ones((B, nA), np.float32)
     f64 = lambda x: x.astype(np.float64)                          # noqa: E731
     with np.errstate(all="ignore"):
         alpha = np.exp(f["log_alpha"]).astype(np.float32)[None]
-        m = np.where((f["q1_next"] < f["q2_next"]) | (f["q1_next"] != f["q1_next"]), f["q1_next"], f["q2_next"])
-        v = (f64(-alpha) * f64(f["logp_next"]) + f64(m)).astype(np.float32)
-        qn = np.where(f["done"] != 0, np.float32(0.0), v)
-        y = (np.float64(np.float32(gamma)) * f64(qn) + f64(f["rew"])).astype(np.float32)
+        v = (f64(-alpha) * f64(f["logp_next"]) + f64(O.min32(f["q1_next"], f["q2_next"]))).astype(np.float32)
+        y = O.target32(gamma, f["done"], v, f["rew"])
     s2 = np.float32(2.0 / B)
     out = {k: np.zeros((B, nA, 4)) for k in ("g_q1", "g_q2")}
     out["g_q1"][..., 0], out["g_q2"][..., 0] = (w * (f["q1"] - y)) * s2, (w * (f["q2"] - y)) * s2
     return dict(out, td=y.astype(np.float64))
 
 
-def head_spread(B, nA, weight=True, perms=8):
-    """{tensor: (max ratio, mean ratio)}: how far the float32 yardstick's own error on the head's three tensors moves over equivalent
-    float32 evaluations -- the contract's association (contract32) and torch_sac over yardstick_util.row_orders.  No kernel output enters."""
-    inp, ref, yard, _ = sac_case(B, nA, weight)
-    others = [contract32(inp, weight=weight)] + [torch_sac(inp, torch.float32, weight=weight, perm=o) for o in list(Y.row_orders(B, perms))[1:]]
-    return U.spread(ref, yard, others, TD_NAMES)
-
-
-def factors(B, nA, weight):
-    """tensor -> (mean factor, max factor): the project's (2, 4), or what profiles/sac_float64.json records for the case from head_spread."""
-    return Y.factor_of(Y.recorded(PROFILE, "factors").get(head_id(B, nA, weight), {}))
-
-
-def check_sac(got, ref, yard, e_stats, what="", factor_of=None):
-    """got: dict(g_q1, g_q2, td, stats) of float64 numpy from the kernel.  Prints every figure, then asserts."""
-    bad = Y.check_tensors([(k, got[k], ref[k], yard[k], (factor_of or Y.factor_of({}))(k)) for k in TD_NAMES], what, unit="x")[1]
-    bad += T.stats_out_of_bounds(got["stats"], ref["stats"], e_stats, what)
-    assert not bad, (what, bad)
+# y = r + gamma (1 - done) (min(Q1', Q2')(x_next) - alpha logp'); g_q1 and g_q2 from L_critic, no g_pi (the policy's seeds are
+# sac_policy_seed's); stats[7] = mean |q1 - q2|
+HEAD = O.Head(sac_inputs, ("q1", "q2"), False, lambda f: np.minimum(f["q1_next"], f["q2_next"]) - np.exp(f["log_alpha"])[None] * f["logp_next"],
+              lambda t: torch.minimum(t["q1_next"], t["q2_next"]) - torch.exp(t["log_alpha"]) * t["logp_next"], "sac_head",
+              ("q1", "q2", "q1_next", "q2_next", "logp_next", "rew", "done", "log_alpha", "gamma"), PROFILE, contract32)
 
 
 # ------------------------------------------------------------------------------------------------ the policy's seeds and gradients
@@ -297,11 +226,6 @@ def sums_out_of_bounds(got, ref, own, name, what=""):
     return bad
 
 
-def pi_stats_out_of_bounds(got, ref, e_stats, what=""):
-    counts = [] if got[0] == ref[0] and got[7] == 0.0 else ["n"]
-    return counts + Y.stats_out_of_bounds(got, ref, e_stats, PI_STAT_NAMES, what)
-
-
 # ------------------------------------------------------------------------------------------------ the three losses under autograd
 def losses(nets, targets, log_std, log_alpha, batch, w, z_next, z_pi, central, dtype, gamma=D.GAMMA, te=TARGET_ENTROPY, critics_pi=None,
            entropy=True, next_actor=None, through="min", ls_alpha=True):
@@ -370,21 +294,15 @@ def snapshot(x):
     return out
 
 
-blobs_are_packs = T.blobs_are_packs
-
-
-class Hand(D.Hand):
-    """What a SACLearner holds, under the same names, and its update written out with the public primitives alone."""
+class Hand(O.Hand):
+    """What a SACLearner holds, under the same names, and its update written out with the public primitives alone: offpolicy_util.Hand's
+    and ddpg_inputs, sac_sample_actions, sac_head, sac_policy_seed, sac_policy_grad."""
 
     def __init__(self, buffer, actor, critic, critic2, central, log_std=None, alpha=0.2, lr_alpha=3e-4, target_entropy=TARGET_ENTROPY, seed=0,
                  **kw):
         from deep_rl_battlespace_amd import learner as L
-        super().__init__(buffer, actor, critic, central, **kw)
+        super().__init__(buffer, actor, critic, central, critic2, **kw)
         dev, nA = actor.w1.device, actor.n_actors
-        self.critic2, self.target_critic2 = critic2, copy.deepcopy(critic2)
-        self.target_critic2.__dict__.pop("_bsx_mlp_buffers", None)
-        self._blob_c2, self._blob_tc2 = critic2.pack(), self.target_critic2.pack()
-        self.adam_critic2 = L.AdamState(critic2)
         self.log_std = log_std if log_std is not None else torch.full((nA, 3), math.log(0.2), dtype=torch.float32, device=dev)
         self.adam_log_std = L.AdamState(self.log_std)
         self.log_alpha = torch.full((nA,), math.log(alpha), dtype=torch.float32, device=dev)
@@ -394,30 +312,14 @@ class Hand(D.Hand):
         self.stats_pi = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
         self.target_entropy, self.seed = target_entropy, seed
         self._noise_draws = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.prioritized = hasattr(buffer, "tree")
-
-    def update(self):
-        for u in range(self.updates):
-            s = self.buffer.sample()
-            self.step(s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6], u,
-                      weight=self.buffer.weights if self.prioritized else None)
-        return self.stats
 
     def step(self, obs, act, rew, obs_next, done, u, weight=None, z_next=None, z_pi=None):
         """The ten steps on a batch -> dict(row_c, row_c2, row_a: copies of mlp_grad's cached rows; g_log_std, g_log_alpha: copies).
         z_next, z_pi: the two draws' normals, injected (the sequence word stays)."""
-        from deep_rl_battlespace_amd import _lib, learner as L
-        lib, c = _lib.load(), self.central
+        from deep_rl_battlespace_amd import learner as L
+        c = self.central
         obs, act, obs_next = obs.contiguous(), act.contiguous(), obs_next.contiguous()
-        (B, nA, Do), k, dev = obs.shape, act.shape[2], obs.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-
-        def forward(blob, x, raw=False):
-            y4 = torch.empty((B, nA, 4), device=dev)
-            r = torch.empty((B, nA), device=dev) if raw else None
-            _lib.check(lib.bsx_mlp_forward(blob.data_ptr(), x.data_ptr(), y4.data_ptr(), r.data_ptr() if raw else None, B, nA, x.shape[2], stream),
-                       "bsx_mlp_forward")
-            return r if raw else y4
+        Do, k = obs.shape[2], act.shape[2]
 
         def draw(y4, x, own_only, z):
             if z is not None:
@@ -426,21 +328,18 @@ class Hand(D.Hand):
             self._noise_draws.add_(1)
             return out
         x_cur, x_next, x_pi = L.ddpg_inputs(obs, obs_next, act, central=c)
-        _, logp_next, _ = draw(forward(self._blob_a, obs_next), x_next, False, z_next)
-        q1_next, q2_next = forward(self._blob_tc, x_next, True), forward(self._blob_tc2, x_next, True)
-        q1, q2 = forward(self._blob_c, x_cur, True), forward(self._blob_c2, x_cur, True)
+        _, logp_next, _ = draw(self.forward(self._blob_a, obs_next), x_next, False, z_next)
+        q1_next, q2_next = self.forward(self._blob_tc, x_next, True), self.forward(self._blob_tc2, x_next, True)
+        q1, q2 = self.forward(self._blob_c, x_cur, True), self.forward(self._blob_c2, x_cur, True)
         head = L.sac_head(q1, q2, q1_next, q2_next, logp_next, rew, done, self.log_alpha, self.gamma, weight=weight)
         self.stats[u].copy_(head.stats)
         self.td = head.td
         if self.prioritized:
             self.buffer.update_priorities(q1, head.td)
-        row_c = L.mlp_grad(self.critic, self._blob_c, x_cur, head.g_q1[..., :1].contiguous(), squash=False, input_grad=False)[0].clone()
-        row_c2 = L.mlp_grad(self.critic2, self._blob_c2, x_cur, head.g_q2[..., :1].contiguous(), squash=False, input_grad=False)[0].clone()
-        L.mlp_adam_step([self.critic, self.critic2], [row_c, row_c2], [self.adam_critic, self.adam_critic2], [self._blob_c, self._blob_c2],
-                        self.hyper_critic, self.step_critic, targets=[self.target_critic, self.target_critic2],
-                        target_blobs=[self._blob_tc, self._blob_tc2], stats=self.step_stats_critic[u])
-        _, logp, z = draw(forward(self._blob_a, obs), x_pi, True, z_pi)
-        q1_pi, q2_pi = forward(self._blob_c, x_pi, True), forward(self._blob_c2, x_pi, True)
+        row_c, row_c2 = self.critic_rows(x_cur, [head.g_q1, head.g_q2])
+        self.critics_step([row_c, row_c2], u)
+        _, logp, z = draw(self.forward(self._blob_a, obs), x_pi, True, z_pi)
+        q1_pi, q2_pi = self.forward(self._blob_c, x_pi, True), self.forward(self._blob_c2, x_pi, True)
         s1, s2 = L.sac_policy_seed(q1_pi, q2_pi, weight=weight)
         _, gx1 = L.mlp_grad(self.critic, self._blob_c, x_pi, s1[..., :1].contiguous(), squash=False, input_grad=True)
         _, gx2 = L.mlp_grad(self.critic2, self._blob_c2, x_pi, s2[..., :1].contiguous(), squash=False, input_grad=True)
@@ -448,68 +347,38 @@ class Hand(D.Hand):
                                weight=weight, central=c, alpha_state=self.adam_alpha, hyper=self.hyper_alpha,
                                step=self.step_alpha if self.adam_alpha is not None else None)
         self.stats_pi[u].copy_(pg.stats)
-        row_a = L.mlp_grad(self.actor, self._blob_a, obs, pg.g_a4[..., :k].contiguous(), squash=True, input_grad=False)[0].clone()
+        row_a = self.actor_row(obs, pg.g_a4, k)
         L.mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor, log_std=self.log_std,
                         g_log_std=pg.g_log_std, log_std_state=self.adam_log_std, stats=self.step_stats_actor[u])
         return dict(row_c=row_c, row_c2=row_c2, row_a=row_a, g_log_std=pg.g_log_std.clone(), g_log_alpha=pg.g_log_alpha.clone())
+
+
+SUITE = O.Suite("SACLearner", Hand, D.learner_case, D.KW, T.critic2_of)
 
 
 # ------------------------------------------------------------------------------------------------ a whole update against float64
 ALPHA_LR = 3e-4
 
 
-def _actor_step(actor, ga, log_std, g_ls, kw, dtype):
-    """The actor's step with log_std in the same call (one clip norm over both, no targets) -> td3_util._joint_step64's dict plus
-    log_std, m_ls, v_ls.  float64: adam_mlp_util.reference_step; float32: clip_grad_norm_ and torch.optim.Adam over the eleven tensors."""
-    hp = AU.hyper32(kw["lr_actor"], *kw["betas"], kw["eps"], kw["max_grad_norm"] or 0.0)
-    if dtype == torch.float64:
-        P0 = AU.net_arrays(actor) + [log_std.detach().cpu().numpy()]
-        Z = [np.zeros(x.shape) for x in P0]
-        P, M_, V, _, _, norm, coef = AM.reference_step(P0, [ga[p] for p in PARAMS] + [g_ls], Z, Z, [None] * 11, 0, hp, 0.0)
-        return dict(p=P[:10], m=M_[:10], v=V[:10], ls=dict(p=[P[10]], m=[M_[10]], v=[V[10]]), norm=norm, coef=coef)
-    ps = [getattr(actor, p).detach().clone().float().requires_grad_() for p in PARAMS] + [log_std.detach().clone().float().requires_grad_()]
-    for p, g in zip(ps, [ga[name] for name in PARAMS] + [g_ls]):
-        p.grad = torch.from_numpy(np.ascontiguousarray(g)).float()
-    if hp["max_grad_norm"] > 0.0:
-        torch.nn.utils.clip_grad_norm_(ps, hp["max_grad_norm"])
-    opt = torch.optim.Adam(ps, lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
-    opt.step()
-    f = lambda xs: [x.detach().numpy() for x in xs]               # noqa: E731
-    m, v = f([opt.state[p]["exp_avg"] for p in ps]), f([opt.state[p]["exp_avg_sq"] for p in ps])
-    return dict(p=f(ps[:10]), m=m[:10], v=v[:10], ls=dict(p=f(ps[10:]), m=m[10:], v=v[10:]))
-
-
-def _alpha_step(log_alpha, g_la, kw, dtype):
-    """log_alpha's Adam step without clipping -> dict(p, m, v: one-element lists)."""
-    hp = AU.hyper32(ALPHA_LR, *kw["betas"], kw["eps"], 0.0)
-    if dtype == torch.float64:
-        P, M_, V, *_ = AU.reference_step([log_alpha.detach().cpu().numpy()], [g_la], [np.zeros(g_la.shape)], [np.zeros(g_la.shape)], 0, hp)
-        return dict(p=P, m=M_, v=V)
-    p = log_alpha.detach().clone().float().requires_grad_()
-    p.grad = torch.from_numpy(np.ascontiguousarray(g_la)).float()
-    opt = torch.optim.Adam([p], lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
-    opt.step()
-    return dict(p=[p.detach().numpy()], m=[opt.state[p]["exp_avg"].numpy()], v=[opt.state[p]["exp_avg_sq"].numpy()])
-
-
 def update_reference(nets, targets, log_std, log_alpha, batch, w, z_next, z_pi, central, dtype, kw=None, perm=None, **variant):
     """One whole SAC update on the CPU in `dtype` -> dict(gc1, gc2, ga, g_ls, g_la; critic, critic2 (the joint step with both Polyak
-    targets), actor (with ls: log_std's part), alpha: the steps; head, pi: the inputs of ref_sac_head / ref_policy_grad's statistics)."""
+    targets), actor (with ls: log_std's part), alpha: the steps; head, pi: the inputs of HEAD.ref / ref_policy_grad's statistics)."""
     kw = kw or D.STEP_KW
     if perm is not None:
         batch, w, z_next, z_pi = tuple(t[perm] for t in batch), w[perm], z_next[perm], z_pi[perm]
     args = (nets, targets, log_std, log_alpha, batch, w, z_next, z_pi, central, dtype, kw["gamma"])
     first = sac_grads(*args, **variant)
-    step = T._joint_step64 if dtype == torch.float64 else T._joint_step32
-    s1, s2 = step(nets[1:], [first["gc1"], first["gc2"]], targets, kw["lr_critic"], kw)
+    s1, s2 = O.first_step(nets[1:], [first["gc1"], first["gc2"]], targets, kw["lr_critic"], kw, dtype)
     second = sac_grads(*args, critics_pi=(s1["net"], s2["net"]), **variant)
+    # the actor's step with log_std in the same call (one clip norm over both, no target); log_alpha's on its own, unclipped
+    actor, ls = O.first_step(nets[:1], [second["ga"]], [None], kw["lr_actor"], kw, dtype, loose=[(log_std, second["g_ls"])])
+    alpha, = O.first_step((), (), (), ALPHA_LR, kw, dtype, loose=[(log_alpha, second["g_la"])], clip=False)
     ex1, ex2 = first["extras"], second["extras"]
     head = dict(q1=ex1["q1"], q2=ex1["q2"], q1_next=ex1["q1_next"], q2_next=ex1["q2_next"], logp_next=ex1["logp_next"], rew=batch[2].to(dtype),
                 done=batch[4].to(torch.uint8), weight=w.to(dtype), log_alpha=log_alpha.to(dtype))
     pi = dict(logp=ex2["logp"], q1_pi=ex2["q1_pi"], q2_pi=ex2["q2_pi"], weight=w.to(dtype), log_alpha=log_alpha.to(dtype))
     return dict(gc1=first["gc1"], gc2=first["gc2"], ga=second["ga"], g_ls=second["g_ls"], g_la=second["g_la"], critic=s1, critic2=s2,
-                actor=_actor_step(nets[0], second["ga"], log_std, second["g_ls"], kw, dtype), alpha=_alpha_step(log_alpha, second["g_la"], kw, dtype),
-                head=head, pi=pi, x_pi=ex2["x_pi"].contiguous())
+                actor=dict(actor, ls=ls), alpha=alpha, head=head, pi=pi, x_pi=ex2["x_pi"].contiguous())
 
 
 def pi_stats(pi, dtype=torch.float64):
@@ -545,16 +414,10 @@ def try_seed(shape, seed):
     w = torch.randn((B, nA), generator=g)
     x_cur = D.joined(batch[0].double(), batch[1].double(), central).contiguous()
     w[U.near_kink((actor, batch[0]), (critic, x_cur), (critic2, x_cur))] = 0.0
-    rounds = 0
-    while True:
-        ref = update_reference(nets, targets, log_std, log_alpha, batch, w, z_next, z_pi, central, torch.float64)
-        near = _kinks(ref, ref["x_pi"]) & (w != 0)
-        if not near.any():
-            break
-        rounds += 1
-        if rounds > D.MAX_ROUNDS:
-            return None, float((w == 0).double().mean()), rounds
-        w[near] = 0.0
+    ref, w, rounds = O.kink_fixed_point(w, lambda w: update_reference(nets, targets, log_std, log_alpha, batch, w, z_next, z_pi, central, torch.float64),
+                                        lambda ref: _kinks(ref, ref["x_pi"]))
+    if ref is None:
+        return None, float((w == 0).double().mean()), rounds
     case = types.SimpleNamespace(seed=seed, nets=nets, targets=targets, rows=rows, idx=idx, batch=batch, z_next=z_next, z_pi=z_pi, log_std=log_std,
                                  log_alpha=log_alpha, w=w, rounds=rounds, share=float((w == 0).double().mean()), ref=ref)
     return case, case.share, rounds
@@ -566,7 +429,7 @@ def stepped_case(shape, seed=None):
     critic2_of's second critic, two target critics that are NOT the critics (each parameter plus 0.05 randn), injected normals for both
     draws, random log_std (about -1) and log_alpha (about log 0.2), on the CPU.  w: standard normal row weights, 0 where, in float64, any
     of these lies within actor_grad_util.KINK of 0: a pre-ReLU value of either critic at x_cur, of the actor at obs, of either STEPPED
-    critic at x_pi, or |q1_pi - q2_pi| -- iterated to a fixed point (at most ddpg_util.MAX_ROUNDS zeroing rounds).  ref, yard:
+    critic at x_pi, or |q1_pi - q2_pi| -- iterated to a fixed point (at most offpolicy_util.MAX_ROUNDS zeroing rounds).  ref, yard:
     update_reference in float64 and float32; the statistics rows and the yardstick's own error over 9 row orders.  Read-only."""
     seed = STEP_SEEDS.get(tuple(shape), 0) if seed is None else seed
     c, share, rounds = try_seed(shape, seed)
@@ -575,8 +438,8 @@ def stepped_case(shape, seed=None):
     run = lambda order=None: update_reference(c.nets, c.targets, c.log_std, c.log_alpha, c.batch, c.w, c.z_next, c.z_pi, central,      # noqa: E731
                                               torch.float32, perm=order)
     c.yard = run()
-    c.stats, c.stats_pi = ref_sac_head(c.ref["head"])["stats"], pi_stats(c.ref["pi"])
-    c.e_stats = Y.own_error(lambda order: torch_sac(c.yard["head"], torch.float32, perm=order), dict(stats=c.stats), B)[0]
+    c.stats, c.stats_pi = HEAD.ref(c.ref["head"])["stats"], pi_stats(c.ref["pi"])
+    c.e_stats = Y.own_error(lambda order: HEAD.autograd(c.yard["head"], torch.float32, perm=order), dict(stats=c.stats), B)[0]
     perm_pi = lambda order: dict(stats=pi_stats({k: (v[order] if order is not None and v.dim() == 2 else v) for k, v in c.yard["pi"].items()},      # noqa: E731
                                                 torch.float32))
     c.e_stats_pi = Y.own_error(perm_pi, dict(stats=c.stats_pi), B)[0]
@@ -616,20 +479,18 @@ def wrong_variants(case, central):
     c = case
     g = torch.Generator().manual_seed(77)
     f = lambda **v: update_reference(c.nets, c.targets, c.log_std, c.log_alpha, c.batch, c.w, c.z_next, c.z_pi, central, torch.float64, **v)     # noqa: E731
-    dist = lambda a, b: {p: float(np.abs(a[p] - b[p]).mean()) for p in D.SHARP}       # noqa: E731
     out = {}
     for name, variant, which in (("the entropy term left out of y", dict(entropy=False), "gc1"),
                                  ("next actions from a perturbed copy of the actor", dict(next_actor=D.perturbed(c.nets[0], g)), "gc1"),
                                  ("the actor through critic 1 alone", dict(through="first"), "ga")):
-        out[name] = (dist(f(**variant)[which], c.ref[which]), dist(c.yard[which], c.ref[which]))
-    wrong = f(ls_alpha=False)["g_ls"]
-    out["g_log_std without its -alpha term"] = ({"log_std": float(np.abs(wrong - c.ref["g_ls"]).mean())},
-                                                {"log_std": float(np.abs(c.yard["g_ls"] - c.ref["g_ls"]).mean())})
+        out[name] = O.distances(f(**variant)[which], c.ref[which], c.yard[which], D.SHARP)
+    ls = lambda r: {"log_std": r["g_ls"]}                         # noqa: E731
+    out["g_log_std without its -alpha term"] = O.distances(ls(f(ls_alpha=False)), ls(c.ref), ls(c.yard), ("log_std",))
     return out
 
 
 # ------------------------------------------------------------------------------------------------ the torch composition, the bandit
-BANDIT = dict(D.BANDIT, k=3, alpha=0.02)
+BANDIT = dict(O.BANDIT, k=3, alpha=0.02)
 
 
 def torch_update(nets, targets, log_std, log_alpha, opt_a, opt_c, batch, central, gen, gamma=D.GAMMA, tau=0.01):
@@ -649,11 +510,7 @@ def torch_update(nets, targets, log_std, log_alpha, opt_a, opt_c, batch, central
     opt_c.zero_grad(set_to_none=True)
     (((c1(x_cur, squash=False)[..., 0] - y) ** 2).mean(0).sum() + ((c2(x_cur, squash=False)[..., 0] - y) ** 2).mean(0).sum()).backward()
     opt_c.step()
-    with torch.no_grad():
-        for t, n in zip(targets, nets[1:]):
-            ts, ns = list(t.parameters()), list(n.parameters())
-            torch._foreach_mul_(ts, 1.0 - tau)
-            torch._foreach_add_(ts, ns, alpha=tau)
+    O.polyak_(targets, nets[1:], tau)
     z = draw()
     logp = (-0.5 * z * z - log_std).sum(-1) - const
     x_pi = D.joined_pi(obs, act, actor(obs) + torch.exp(log_std) * z, central)
@@ -662,39 +519,17 @@ def torch_update(nets, targets, log_std, log_alpha, opt_a, opt_c, batch, central
     opt_a.step()
 
 
-def bandit_rows(seed=0):
-    """ddpg_util.bandit_rows at k = 3 (bandit_reward is generic in k)."""
-    b = BANDIT
-    g = torch.Generator().manual_seed(9900 + seed)
-    uni = lambda *s: torch.rand(s, generator=g) * 2 - 1       # noqa: E731
-    obs, act = uni(b["rows"], b["nA"], b["Do"]), uni(b["rows"], b["nA"], b["k"])
-    rows = (obs, act, D.bandit_reward(obs, act), uni(b["rows"], b["nA"], b["Do"]), torch.ones((b["rows"], b["nA"]), dtype=torch.bool))
-    return rows, uni(b["held_out"], b["nA"], b["Do"])
-
-
-def bandit_nets(seed=0):
-    """(actor, critic, critic2) on the CPU, freshly initialised (own critics: 8 -> 1)."""
-    b = BANDIT
-    torch.manual_seed(9950 + seed)
-    return R._new(b["nA"], b["Do"], b["k"]), R._new(b["nA"], b["Do"] + b["k"], 1), R._new(b["nA"], b["Do"] + b["k"], 1)
-
-
 def bandit_torch_run(N, seed=0):
-    """(initial reward, reward after N updates) of the torch composition of SAC (fixed alpha) on the bandit, on the CPU; the reward is
-    that of the policy's mean action."""
+    """(initial reward, reward after N updates) of the torch composition of SAC (fixed alpha) on the bandit at k = 3, on the CPU; the
+    reward is that of the policy's mean action; the second critic is drawn right after the first."""
     b = BANDIT
-    rows, held = bandit_rows(seed)
-    nets = bandit_nets(seed)
-    targets = tuple(copy.deepcopy(n) for n in nets[1:])
-    log_std = torch.full((b["nA"], 3), math.log(0.2), requires_grad=True)
-    log_alpha = torch.full((b["nA"],), math.log(b["alpha"]))
-    oa = torch.optim.Adam(list(nets[0].parameters()) + [log_std], lr=b["lr"])
-    oc = torch.optim.Adam(list(nets[1].parameters()) + list(nets[2].parameters()), lr=b["lr"])
-    g = torch.Generator().manual_seed(9990 + seed)
-    with torch.no_grad():
-        r0 = float(D.bandit_reward(held, nets[0](held)).mean())
-    for _ in range(N):
-        idx = torch.randint(0, b["rows"], (b["B"],), generator=g)
-        torch_update(nets, targets, log_std, log_alpha, oa, oc, tuple(r[idx] for r in rows), False, g, tau=b["tau"])
-    with torch.no_grad():
-        return r0, float(D.bandit_reward(held, nets[0](held)).mean())
+
+    def compose(seed):
+        nets = O.bandit_nets(seed, b, critic2="next")
+        targets = tuple(copy.deepcopy(n) for n in nets[1:])
+        log_std = torch.full((b["nA"], 3), math.log(0.2), requires_grad=True)
+        log_alpha = torch.full((b["nA"],), math.log(b["alpha"]))
+        oa = torch.optim.Adam(list(nets[0].parameters()) + [log_std], lr=b["lr"])
+        oc = torch.optim.Adam(list(nets[1].parameters()) + list(nets[2].parameters()), lr=b["lr"])
+        return nets[0], lambda u, batch, g: torch_update(nets, targets, log_std, log_alpha, oa, oc, batch, False, g, tau=b["tau"])
+    return O.bandit_torch_run(N, compose, seed, b)

@@ -1,17 +1,17 @@
 """What the tests of the TD3 kernels (csrc/bsx_td3_head.hip: learner.td3_smooth_actions, td3_head) and of TD3Learner share, on top of
-tests/ddpg_util.py (the shapes, the joins, the learner's case, the bandit), yardstick_util (the bars), philox_util (normals4),
-adam_mlp_util (the float64 step with Polyak targets) and guard_util:
+tests/offpolicy_util.py (the head's machinery, the reference step, the kink filter, Hand, the bandit), tests/ddpg_util.py (the shapes,
+the joins, the learner's case), yardstick_util (the bars) and philox_util (normals4):
 
   clamp, ref_smooth        the smoothing's contract restated in numpy, in the dtype it is given (float32: the kernel's bits)
-  td3_inputs, ref_td3_head, torch_td3, td3_case, contract32, head_spread, factors, check_td3   the twin head's inputs, its contract in float64 numpy, the head as a torch
-                           user writes it with autograd from q1 and q2, both cached per shape, and yardstick_util's bounds
-  critic2_of, Hand, snapshot, prio_ring   a second critic for a learner case; one TD3 update by hand from the public primitives, holding
+  td3_inputs, contract32, HEAD   the twin head's inputs, its float32 contract operation by operation, and its kind: the twin target
+                           min(Q1', Q2'), g_q1 and g_q2, g_pi from critic 1 (offpolicy_util.Head writes the rest over that)
+  critic2_of, Hand, snapshot, SUITE   a second critic for a learner case; one TD3 update by hand from the public primitives, holding
                            what a TD3Learner holds under the same names; every tensor an update writes, as bits
   td3_grads, update_reference, stepped_case, wrong_variants   a whole update (policy_delay = 1) from target networks that
                            are not the networks, with injected noise: both critics' gradients at the shared y, ONE joint step with one
                            clip norm and both Polyak targets, the actor's gradient at the STEPPED critic 1, the actor's step -- in
                            float64, and in float32 on the CPU as the yardstick; the kink filter iterated to its fixed point
-  torch_update, bandit_torch_run   the torch composition of TD3 and what it reaches on ddpg_util's bandit
+  torch_update, bandit_torch_run   the torch composition of TD3 and what it reaches on the bandit
 
 Nothing here imports the native library at import time."""
 import copy
@@ -22,24 +22,21 @@ import types
 import numpy as np
 import torch
 
-import adam_mlp_util as AM
 import ddpg_util as D
-import guard_util as G                # noqa: F401  (the suites take Buffers from here)
+import offpolicy_util as O
 import philox_util as PU
 import yardstick_util as Y
 
-AU, U, R, PARAMS = D.AU, D.U, D.R, D.PARAMS
+U, PARAMS = D.U, D.PARAMS
 PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "td3_float64.json")
 SALT = 0x20000000                                                   # bsx_td3_head.hip: TD3_SALT
 OTHER_SALTS = (PU.SALT_OU, PU.SALT_GAUSS_WITH_OU, PU.SALT_CATEGORICAL, 0xC0000000)
 HEAD_SHAPES = ((1, 1), (97, 1), (161, 2), (129, 3), (130, 16), (16385, 16))       # the issue's (B, nA); the last: J = 2, five merge rounds
 MAIN_SHAPES = ((161, 2, 8, 4, 1), (97, 1, 5, 3, 0))
 HAND_SHAPES = MAIN_SHAPES + ((129, 3, 11, 4, 1), (1, 1, 5, 4, 1))
-TD_NAMES = ("g_q1", "g_q2", "g_pi", "td")
-STAT_NAMES = D.STAT_NAMES + ("q_gap",)                               # stats[1..7]
 SIGMA, CLIP = 0.2, 0.5                                              # the learner's defaults, and the whole-update case's
 # stepped_case's seed per shape.  Picked on the float64 reference alone, as ddpg_util.STEP_SEEDS was: the first seed from 0 at which the
-# kink filter closes within ddpg_util.MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP (two critics at
+# kink filter closes within offpolicy_util.MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP (two critics at
 # x_cur: 768 hidden values per element instead of 384, so more is left out than in the DDPG case).  Measured (share left out / rounds)
 # at 2v2 central: 6.21 % / 2 at seed 0, no fixed point within 4 rounds at seeds 1 and 2, 5.59 % / 3 at seed 3, 4.35 % / 2 at seed 4;
 # 1v1 own passes at seed 0 (0 %, 0 rounds).  profiles/td3_float64.json records what the chosen seeds give
@@ -79,102 +76,25 @@ def td3_inputs(B, nA, seed=0):
                 q2_next=torch.randn((B, nA), generator=g), rew=base["rew"], done=base["done"], weight=base["weight"])
 
 
-def ref_td3_head(inp, gamma=D.GAMMA, weight=True):
-    """The contract in float64 numpy -> dict(g_q1, g_q2, g_pi [B, nA, 4], td [B, nA], stats [8])."""
-    f = {k: v.double().numpy() for k, v in inp.items()}
-    B, nA = f["q1"].shape
-    over = f["done"] != 0
-    w = f["weight"] if weight else np.ones((B, nA))
-    with np.errstate(all="ignore"):
-        y = gamma * np.where(over, 0.0, np.minimum(f["q1_next"], f["q2_next"])) + f["rew"]
-    d1, d2 = f["q1"] - y, f["q2"] - y
-    out = {k: np.zeros((B, nA, 4)) for k in ("g_q1", "g_q2", "g_pi")}
-    out["g_q1"][..., 0], out["g_q2"][..., 0], out["g_pi"][..., 0] = w * d1 * (2.0 / B), w * d2 * (2.0 / B), -w * (1.0 / B)
-    n = float(B * nA)
-    stats = np.array([n, (w * (d1 * d1 + d2 * d2)).sum() / n, f["q1"].sum() / n, y.sum() / n, np.abs(d1).sum() / n, over.sum() / n,
-                      w.sum() / n, np.abs(f["q1"] - f["q2"]).sum() / n])
-    return dict(out, td=y, stats=stats)
-
-
-def torch_td3(inp, dtype, gamma=D.GAMMA, weight=True, perm=None):
-    """The head as a torch user writes it, on the CPU in `dtype`, with autograd from q1 and q2 of the sum of the two critic losses and
-    of -mean w Q1 -> dict of float64 numpy (ddpg_util.torch_td's form).  perm: the rows in another order."""
-    t = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in inp.items()}
-    if perm is not None:
-        t = {k: v[perm] for k, v in t.items()}
-    q1, q2, q_pi = (t[k].clone().requires_grad_() for k in ("q1", "q2", "q1"))
-    w = t["weight"] if weight else torch.ones_like(t["q1"])
-    y = t["rew"] + gamma * (1.0 - t["done"].to(dtype)) * torch.minimum(t["q1_next"], t["q2_next"])
-    ((w * (q1 - y) ** 2).mean(0).sum() + (w * (q2 - y) ** 2).mean(0).sum()).backward()
-    (-(w * q_pi).mean(0).sum()).backward()
-    gs = {k: torch.zeros((*q1.shape, 4), dtype=dtype) for k in ("g_q1", "g_q2", "g_pi")}
-    gs["g_q1"][..., 0], gs["g_q2"][..., 0], gs["g_pi"][..., 0] = q1.grad, q2.grad, q_pi.grad
-    gs["td"] = y
-    if perm is not None:
-        inv = torch.argsort(perm)
-        gs = {k: v[inv] for k, v in gs.items()}
-    with torch.no_grad():
-        d1, d2 = q1 - y, q2 - y
-        num = lambda x: float(x.double())                     # noqa: E731
-        stats = np.array([float(q1.numel()), num((w * (d1 * d1 + d2 * d2)).mean()), num(q1.mean()), num(y.mean()), num(d1.abs().mean()),
-                          num(t["done"].to(dtype).mean()), num(w.mean()), num((q1 - q2).abs().mean())])
-    return dict({k: v.detach().double().numpy() for k, v in gs.items()}, stats=stats)
-
-
-@functools.lru_cache(maxsize=None)
-def td3_case(B, nA, weight=True, perms=8):
-    """(inputs, float64 reference, float32 yardstick, the yardstick's own error on stats [8] over 9 row orders).  Read-only."""
-    inp = td3_inputs(B, nA)
-    ref, yard = ref_td3_head(inp, weight=weight), torch_td3(inp, torch.float32, weight=weight)
-    return inp, ref, yard, Y.own_error(lambda order: torch_td3(inp, torch.float32, weight=weight, perm=order), ref, B, perms)[0]
-
-
-def head_id(B, nA, weight):
-    return "B%d-nA%d-%s" % (B, nA, "weighted" if weight else "plain")
-
-
 def contract32(inp, gamma=D.GAMMA, weight=True):
     """The header's contract operation by operation in numpy float32 (the fmaf through float64: its product is exact there) -> the
-    four tensors as float64 arrays: a float32 evaluation of the head equivalent to torch_td3's, in the kernel's association."""
+    four tensors as float64 arrays: a float32 evaluation of the head equivalent to HEAD.autograd's, in the kernel's association."""
     f = {k: v.numpy() for k, v in inp.items()}
     B, nA = f["q1"].shape
     one = np.float32(1.0)
     w = f["weight"] if weight else np.ones((B, nA), np.float32)
     with np.errstate(all="ignore"):
-        m = np.where((f["q1_next"] < f["q2_next"]) | (f["q1_next"] != f["q1_next"]), f["q1_next"], f["q2_next"])
-        qn = np.where(f["done"] != 0, np.float32(0.0), m)
-        y = (np.float64(np.float32(gamma)) * qn.astype(np.float64) + f["rew"].astype(np.float64)).astype(np.float32)
+        y = O.target32(gamma, f["done"], O.min32(f["q1_next"], f["q2_next"]), f["rew"])
     s1, s2 = np.float32(1.0 / B), np.float32(2.0 / B)
     out = {k: np.zeros((B, nA, 4)) for k in ("g_q1", "g_q2", "g_pi")}
     out["g_q1"][..., 0], out["g_q2"][..., 0], out["g_pi"][..., 0] = (w * (f["q1"] - y)) * s2, (w * (f["q2"] - y)) * s2, -((w * one) * s1)
     return dict(out, td=y.astype(np.float64))
 
 
-def head_spread(B, nA, weight=True, perms=8):
-    """{tensor: (max ratio, mean ratio)}: how far the float32 yardstick's own error on the head's four tensors moves over equivalent
-    float32 evaluations -- the contract's association (contract32) and torch_td3 over yardstick_util.row_orders.  No kernel output
-    enters.  With a handful of elements the error is a few draws of a rounding and moves by more than (2, 4): at B = nA = 1 it is ONE."""
-    inp, ref, yard, _ = td3_case(B, nA, weight)
-    others = [contract32(inp, weight=weight)] + [torch_td3(inp, torch.float32, weight=weight, perm=o) for o in list(Y.row_orders(B, perms))[1:]]
-    return U.spread(ref, yard, others, TD_NAMES)
-
-
-def factors(B, nA, weight):
-    """tensor -> (mean factor, max factor): the project's (2, 4), or what profiles/td3_float64.json records for the case from head_spread."""
-    return Y.factor_of(Y.recorded(PROFILE, "factors").get(head_id(B, nA, weight), {}))
-
-
-def stats_out_of_bounds(got, ref, e_stats, what=""):
-    counts = [] if got[0] == ref[0] else ["n"]
-    return counts + Y.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, what)
-
-
-def check_td3(got, ref, yard, e_stats, what="", factor_of=None):
-    """got: dict(g_q1, g_q2, g_pi, td, stats) of float64 numpy from the kernel; factor_of: factors(B, nA, weight).  Prints every figure,
-    then asserts."""
-    bad = Y.check_tensors([(k, got[k], ref[k], yard[k], (factor_of or Y.factor_of({}))(k)) for k in TD_NAMES], what, unit="x")[1]
-    bad += stats_out_of_bounds(got["stats"], ref["stats"], e_stats, what)
-    assert not bad, (what, bad)
+# y = r + gamma (1 - done) min(Q1', Q2')(x_next); g_q1 and g_q2 from the sum of the two critic losses, g_pi from -mean w Q1;
+# stats[7] = mean |q1 - q2|
+HEAD = O.Head(td3_inputs, ("q1", "q2"), True, lambda f: np.minimum(f["q1_next"], f["q2_next"]), lambda t: torch.minimum(t["q1_next"], t["q2_next"]),
+              "td3_head", ("q1", "q2", "q1_next", "q2_next", "rew", "done", "gamma"), PROFILE, contract32)
 
 
 # ------------------------------------------------------------------------------------------------ one update by hand
@@ -201,61 +121,27 @@ def snapshot(x):
     return out
 
 
-def blobs_are_packs(x):
-    for net, blob in ((x.actor, x._blob_a), (x.critic, x._blob_c), (x.target_actor, x._blob_ta), (x.target_critic, x._blob_tc),
-                      (x.critic2, x._blob_c2), (x.target_critic2, x._blob_tc2)):
-        assert torch.equal(net.pack().view(torch.int32), blob.view(torch.int32))
-
-
-def prio_ring(rows, B, seed=3):
-    """ddpg_util.ring's, prioritised."""
-    from deep_rl_battlespace_amd.replay import PrioritizedReplayBuffer
-    obs, act, rew, obs_next, done = (r.cuda() for r in rows)
-    N, nA, Do = obs.shape
-    buf = PrioritizedReplayBuffer(N, B, list(range(nA)), Do, Do * nA, act.shape[2], device="cuda", seed=seed)
-    buf._put(obs, act, rew, obs_next, done)
-    return buf
-
-
-class Hand(D.Hand):
-    """What a TD3Learner holds, under the same names, and its update written out with the public primitives alone: ddpg_util.Hand's and
-    td3_smooth_actions, td3_head, mlp_adam_step of two networks."""
+class Hand(O.Hand):
+    """What a TD3Learner holds, under the same names, and its update written out with the public primitives alone: offpolicy_util.Hand's
+    and ddpg_inputs, td3_smooth_actions, td3_head."""
 
     def __init__(self, buffer, actor, critic, critic2, central, policy_delay=2, target_noise=SIGMA, noise_clip=CLIP, seed=0, **kw):
-        from deep_rl_battlespace_amd import learner as L
-        super().__init__(buffer, actor, critic, central, **kw)
-        self.critic2, self.target_critic2 = critic2, copy.deepcopy(critic2)
-        self.target_critic2.__dict__.pop("_bsx_mlp_buffers", None)
-        self._blob_c2, self._blob_tc2 = critic2.pack(), self.target_critic2.pack()
-        self.adam_critic2 = L.AdamState(critic2)
+        super().__init__(buffer, actor, critic, central, critic2, **kw)
         self.policy_delay, self.target_noise, self.noise_clip, self.seed = policy_delay, target_noise, noise_clip, seed
         self._noise_draws = torch.zeros(1, dtype=torch.int64, device=actor.w1.device)
-        self.prioritized = hasattr(buffer, "tree")
 
-    def update(self, stop_after=None):
-        for u in range(self.updates if stop_after is None else stop_after):
-            s = self.buffer.sample()
-            self.step(s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6], u,
-                      weight=self.buffer.weights if self.prioritized else None, delayed=(u + 1) % self.policy_delay == 0)
-        return self.stats
+    def step_args(self, u):
+        return dict(super().step_args(u), delayed=(u + 1) % self.policy_delay == 0)
 
     def step(self, obs, act, rew, obs_next, done, u, weight=None, delayed=True, z=None):
         """The six steps on a batch -> (critic 1's row, critic 2's row, the actor's row or None): copies of mlp_grad's cached rows.
         z: the smoothing's normals, injected (the sequence word stays)."""
-        from deep_rl_battlespace_amd import _lib, learner as L
-        lib, c = _lib.load(), self.central
+        from deep_rl_battlespace_amd import learner as L
+        c = self.central
         obs, act, obs_next = obs.contiguous(), act.contiguous(), obs_next.contiguous()
-        (B, nA, Do), k, dev = obs.shape, act.shape[2], obs.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-
-        def forward(blob, x, raw=False):
-            y4 = torch.empty((B, nA, 4), device=dev)
-            r = torch.empty((B, nA), device=dev) if raw else None
-            _lib.check(lib.bsx_mlp_forward(blob.data_ptr(), x.data_ptr(), y4.data_ptr(), r.data_ptr() if raw else None, B, nA, x.shape[2], stream),
-                       "bsx_mlp_forward")
-            return r if raw else y4
+        Do, k = obs.shape[2], act.shape[2]
         x_cur, x_next, x_pi = L.ddpg_inputs(obs, obs_next, act, central=c)
-        y4 = forward(self._blob_ta, obs_next)
+        y4 = self.forward(self._blob_ta, obs_next)
         if z is not None:
             L.td3_smooth_actions(y4, x_next, Do, k, sigma=self.target_noise, clip=self.noise_clip, seed=self.seed, z=z, central=c)
         elif self.target_noise > 0.0:
@@ -264,27 +150,19 @@ class Hand(D.Hand):
             self._noise_draws.add_(1)
         else:
             L.ddpg_put_actions(y4, x_next, Do, k, central=c, own_only=False)
-        q1_next, q2_next = forward(self._blob_tc, x_next, True), forward(self._blob_tc2, x_next, True)
-        q1, q2 = forward(self._blob_c, x_cur, True), forward(self._blob_c2, x_cur, True)
+        q1_next, q2_next = self.forward(self._blob_tc, x_next, True), self.forward(self._blob_tc2, x_next, True)
+        q1, q2 = self.forward(self._blob_c, x_cur, True), self.forward(self._blob_c2, x_cur, True)
         head = L.td3_head(q1, q2, q1_next, q2_next, rew, done, self.gamma, weight=weight)
         self.stats[u].copy_(head.stats)
         self.td = head.td
         if self.prioritized:
             self.buffer.update_priorities(q1, head.td)
-        row_c = L.mlp_grad(self.critic, self._blob_c, x_cur, head.g_q1[..., :1].contiguous(), squash=False, input_grad=False)[0].clone()
-        row_c2 = L.mlp_grad(self.critic2, self._blob_c2, x_cur, head.g_q2[..., :1].contiguous(), squash=False, input_grad=False)[0].clone()
-        both = dict(targets=[self.target_critic, self.target_critic2], target_blobs=[self._blob_tc, self._blob_tc2]) if delayed else {}
-        L.mlp_adam_step([self.critic, self.critic2], [row_c, row_c2], [self.adam_critic, self.adam_critic2], [self._blob_c, self._blob_c2],
-                        self.hyper_critic, self.step_critic, stats=self.step_stats_critic[u], **both)
-        if not delayed:
-            return row_c, row_c2, None
-        L.ddpg_put_actions(forward(self._blob_a, obs), x_pi, Do, k, central=c, own_only=True)
-        _, gx = L.mlp_grad(self.critic, self._blob_c, x_pi, head.g_pi[..., :1].contiguous(), squash=False, input_grad=True)
-        g_a4 = L.ddpg_action_grad(gx, Do, k, central=c)
-        row_a = L.mlp_grad(self.actor, self._blob_a, obs, g_a4[..., :k].contiguous(), squash=True, input_grad=False)[0].clone()
-        L.mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
-                        targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u])
-        return row_c, row_c2, row_a
+        rows = self.critic_rows(x_cur, [head.g_q1, head.g_q2])
+        self.critics_step(rows, u, targets=delayed)
+        return (*rows, self.deterministic_actor_step(obs, x_pi, head.g_pi, k, u) if delayed else None)
+
+
+SUITE = O.Suite("TD3Learner", Hand, D.learner_case, D.KW, critic2_of)
 
 
 # ------------------------------------------------------------------------------------------------ a whole update against float64
@@ -315,41 +193,6 @@ def td3_grads(nets, targets, batch, w, z, central, dtype, gamma=D.GAMMA, sigma=S
     return num(g[:10]), num(g[10:]), num(ga), y
 
 
-def _joint_step64(nets, grads, targets, lr, kw):
-    """adam_mlp_util.reference_step of ONE call over every network of `nets` (one clip norm over all of them), the first step from zero
-    moments -> per network ddpg_util._step64's dict."""
-    hp = AU.hyper32(lr, *kw["betas"], kw["eps"], kw["max_grad_norm"] or 0.0)
-    P0 = [x for n in nets for x in AU.net_arrays(n)]
-    Z = [np.zeros(x.shape) for x in P0]
-    P, M_, V, T, _, norm, coef = AM.reference_step(P0, [g[p] for g in grads for p in PARAMS], Z, Z, [x for t in targets for x in AU.net_arrays(t)],
-                                                   0, hp, float(np.float32(kw["tau"])))
-    cut = lambda xs, i: xs[10 * i:10 * i + 10]                     # noqa: E731
-    return [dict(p=cut(P, i), m=cut(M_, i), v=cut(V, i), target=cut(T, i), norm=norm, coef=coef, net=D._net_of(cut(P, i), n, torch.float64))
-            for i, n in enumerate(nets)]
-
-
-def _joint_step32(nets, grads, targets, lr, kw):
-    """The same as a torch user takes it in float32 on the CPU: ONE clip_grad_norm_ and ONE torch.optim.Adam over all the networks'
-    parameters, then the Polyak line (ddpg_util._step32's composition)."""
-    hp = AU.hyper32(lr, *kw["betas"], kw["eps"], kw["max_grad_norm"] or 0.0)
-    tau = float(np.float32(kw["tau"]))
-    ps = [getattr(n, p).detach().clone().float().requires_grad_() for n in nets for p in PARAMS]
-    ts = [getattr(t, p).detach().clone().float() for t in targets for p in PARAMS]
-    for p, g in zip(ps, [g[name] for g in grads for name in PARAMS]):
-        p.grad = torch.from_numpy(g).float()
-    if hp["max_grad_norm"] > 0.0:
-        torch.nn.utils.clip_grad_norm_(ps, hp["max_grad_norm"])
-    opt = torch.optim.Adam(ps, lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
-    opt.step()
-    with torch.no_grad():
-        for t, p in zip(ts, ps):
-            t.mul_(1.0 - tau).add_(p, alpha=tau)
-    f = lambda xs: [x.detach().numpy() for x in xs]               # noqa: E731
-    cut = lambda xs, i: xs[10 * i:10 * i + 10]                     # noqa: E731
-    return [dict(p=f(cut(ps, i)), m=f([opt.state[p]["exp_avg"] for p in cut(ps, i)]), v=f([opt.state[p]["exp_avg_sq"] for p in cut(ps, i)]),
-                 target=f(cut(ts, i)), net=D._net_of(f(cut(ps, i)), n, torch.float32)) for i, n in enumerate(nets)]
-
-
 def update_reference(nets, targets, batch, w, z, central, dtype, kw=None, perm=None, **variant):
     """One whole TD3 update with policy_delay = 1 on the CPU in `dtype` -> dict(gc1, gc2, ga: {tensor: grad}; critic, critic2, actor: the
     steps' dicts; inp: the twin head's inputs).  variant: actor_through=2 (the misreading: the actor's gradient through the stepped
@@ -359,15 +202,14 @@ def update_reference(nets, targets, batch, w, z, central, dtype, kw=None, perm=N
         batch, w, z = tuple(t[perm] for t in batch), w[perm], z[perm]
     through = variant.pop("actor_through", 1)
     gc1, gc2, _, _ = td3_grads(nets, targets, batch, w, z, central, dtype, kw["gamma"], **variant)
-    step = _joint_step64 if dtype == torch.float64 else _joint_step32
-    s1, s2 = step(nets[1:], [gc1, gc2], targets[1:], kw["lr_critic"], kw)
+    s1, s2 = O.first_step(nets[1:], [gc1, gc2], targets[1:], kw["lr_critic"], kw, dtype)
     _, _, ga, _ = td3_grads(nets, targets, batch, w, z, central, dtype, kw["gamma"], critic_pi=(s1, s2)[through - 1]["net"], **variant)
-    sa, = step(nets[:1], [ga], targets[:1], kw["lr_actor"], kw)
+    sa, = O.first_step(nets[:1], [ga], targets[:1], kw["lr_actor"], kw, dtype)
     return dict(gc1=gc1, gc2=gc2, ga=ga, critic=s1, critic2=s2, actor=sa, inp=_q_inputs(nets, targets, batch, w, z, central, dtype, **variant))
 
 
 def _q_inputs(nets, targets, batch, w, z, central, dtype, sigma=SIGMA, clip=CLIP, **_):
-    """ref_td3_head's inputs of a batch, evaluated on the CPU in `dtype`."""
+    """HEAD.ref's inputs of a batch, evaluated on the CPU in `dtype`."""
     obs, act, rew, obs_next, done = batch
     to = lambda n: U._to(n, "cpu", dtype)                          # noqa: E731
     k = act.shape[2]
@@ -386,8 +228,8 @@ def stepped_case(shape, seed=None):
     second critic, three target networks that are NOT the networks (each parameter plus 0.05 randn) and injected normals z, on the CPU
     -> a namespace of nets, targets, rows, idx, batch, z; w, share, rounds: standard normal row weights, 0 where, in float64, a
     pre-ReLU value lies within actor_grad_util.KINK of 0 -- of either critic at x_cur, of the actor at obs, of the STEPPED critic 1 at
-    x_pi, the last iterated to its fixed point (at most ddpg_util.MAX_ROUNDS zeroing rounds) --; ref, yard: update_reference in float64
-    and float32; stats, e_stats: ref_td3_head's statistics and the float32 yardstick's own error over 9 row orders.  Read-only."""
+    x_pi, the last iterated to its fixed point (at most offpolicy_util.MAX_ROUNDS zeroing rounds) --; ref, yard: update_reference in float64
+    and float32; stats, e_stats: HEAD.ref's statistics and the float32 yardstick's own error over 9 row orders.  Read-only."""
     B, nA, Do, k, central = shape
     seed = STEP_SEEDS.get(shape, 0) if seed is None else seed
     actor, critic, rows, idx, *_ = D.learner_case(shape, seed)
@@ -400,18 +242,12 @@ def stepped_case(shape, seed=None):
     w = torch.randn((B, nA), generator=g)
     x_cur, _, x_pi = D.joins64(actor, batch[0], batch[3], batch[1], central)
     w[U.near_kink((actor, batch[0]), (critic, x_cur), (critic2, x_cur))] = 0.0
-    rounds = 0
-    while True:
-        ref = update_reference(nets, targets, batch, w, z, central, torch.float64)
-        near = U.near_kink((ref["critic"]["net"], x_pi)) & (w != 0)
-        if not near.any():
-            break
-        rounds += 1
-        assert rounds <= D.MAX_ROUNDS, (shape, seed, rounds)
-        w[near] = 0.0
+    ref, w, rounds = O.kink_fixed_point(w, lambda w: update_reference(nets, targets, batch, w, z, central, torch.float64),
+                                        lambda ref: U.near_kink((ref["critic"]["net"], x_pi)))
+    assert ref is not None, (shape, seed, rounds)
     yard = update_reference(nets, targets, batch, w, z, central, torch.float32)
-    stats = ref_td3_head(ref["inp"])["stats"]
-    e_stats = Y.own_error(lambda order: torch_td3(yard["inp"], torch.float32, perm=order), dict(stats=stats), B)[0]
+    stats = HEAD.ref(ref["inp"])["stats"]
+    e_stats = Y.own_error(lambda order: HEAD.autograd(yard["inp"], torch.float32, perm=order), dict(stats=stats), B)[0]
     return types.SimpleNamespace(seed=seed, nets=nets, targets=targets, rows=rows, idx=idx, batch=batch, z=z, w=w, rounds=rounds,
                                  share=float((w == 0).double().mean()), ref=ref, yard=yard, stats=stats, e_stats=e_stats)
 
@@ -423,8 +259,7 @@ def wrong_variants(case, central):
     f = lambda **v: update_reference(c.nets, c.targets, c.batch, c.w, c.z, central, torch.float64, **v)     # noqa: E731
     wrong = {"y from target critic 1 alone": (f(y_from="first")["gc1"], "gc1"), "the noise left out": (f(sigma=0.0)["gc1"], "gc1"),
              "the actor through critic 2": (f(actor_through=2)["ga"], "ga")}
-    dist = lambda a, b: {p: float(np.abs(a[p] - b[p]).mean()) for p in D.SHARP}       # noqa: E731
-    return {name: (dist(g, c.ref[which]), dist(c.yard[which], c.ref[which])) for name, (g, which) in wrong.items()}
+    return {name: O.distances(g, c.ref[which], c.yard[which], D.SHARP) for name, (g, which) in wrong.items()}
 
 
 GRADS = ("gc1", "gc2", "ga")
@@ -456,34 +291,18 @@ def torch_update(u, nets, targets, opt_a, opt_c, batch, central, gen, gamma=D.GA
     if max_grad_norm is not None:
         torch.nn.utils.clip_grad_norm_(actor.parameters(), max_grad_norm)
     opt_a.step()
-    with torch.no_grad():
-        for t, n in zip(targets, nets):
-            ts, ns = list(t.parameters()), list(n.parameters())
-            torch._foreach_mul_(ts, 1.0 - tau)
-            torch._foreach_add_(ts, ns, alpha=tau)
-
-
-def bandit_critic2(seed=0):
-    """The bandit's second critic, freshly initialised at a seed of its own (CPU)."""
-    b = D.BANDIT
-    torch.manual_seed(9960 + seed)
-    return R._new(b["nA"], b["Do"] + b["k"], 1)
+    O.polyak_(targets, nets, tau)
 
 
 def bandit_torch_run(N, seed=0, policy_delay=2):
-    """(initial reward, reward after N updates) of the torch composition of TD3 on ddpg_util's bandit, on the CPU."""
-    b = D.BANDIT
-    rows, held = D.bandit_rows(seed)
-    actor, critic = D.bandit_nets(seed)
-    nets = (actor, critic, bandit_critic2(seed))
-    targets = tuple(copy.deepcopy(n) for n in nets)
-    oa = torch.optim.Adam(actor.parameters(), lr=b["lr"])
-    oc = torch.optim.Adam(list(nets[1].parameters()) + list(nets[2].parameters()), lr=b["lr"])
-    g = torch.Generator().manual_seed(9990 + seed)
-    with torch.no_grad():
-        r0 = float(D.bandit_reward(held, actor(held)).mean())
-    for u in range(N):
-        idx = torch.randint(0, b["rows"], (b["B"],), generator=g)
-        torch_update(u, nets, targets, oa, oc, tuple(r[idx] for r in rows), False, g, tau=b["tau"], policy_delay=policy_delay)
-    with torch.no_grad():
-        return r0, float(D.bandit_reward(held, actor(held)).mean())
+    """(initial reward, reward after N updates) of the torch composition of TD3 on offpolicy_util's bandit, on the CPU; its second
+    critic is freshly initialised at a seed of its own."""
+    b = O.BANDIT
+
+    def compose(seed):
+        nets = O.bandit_nets(seed, critic2="reseeded")
+        targets = tuple(copy.deepcopy(n) for n in nets)
+        oa = torch.optim.Adam(nets[0].parameters(), lr=b["lr"])
+        oc = torch.optim.Adam(list(nets[1].parameters()) + list(nets[2].parameters()), lr=b["lr"])
+        return nets[0], lambda u, batch, g: torch_update(u, nets, targets, oa, oc, batch, False, g, tau=b["tau"], policy_delay=policy_delay)
+    return O.bandit_torch_run(N, compose, seed)

@@ -14,6 +14,7 @@ import torch
 
 import actor_grad_util as U
 import ddpg_util as D
+import offpolicy_util as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("bsx_ddpg_inputs", "bsx_ddpg_put_actions", "bsx_td_head_workspace_bytes", "bsx_td_head", "bsx_ddpg_action_grad")
@@ -145,8 +146,8 @@ def test_the_copy_restatements_are_torch_cat_and_indexing(shape):
 @pytest.mark.parametrize("shape", D.SHAPES, ids=D.shape_id)
 def test_the_td_restatement_is_float64_autograd_of_the_two_losses(shape, weight):
     inp = D.td_inputs(*shape[:2])
-    ref, t64 = D.ref_td_head(inp, weight=weight), D.torch_td(inp, torch.float64, weight=weight)
-    for k in D.TD_NAMES:
+    ref, t64 = D.HEAD.ref(inp, weight=weight), D.HEAD.autograd(inp, torch.float64, weight=weight)
+    for k in D.HEAD.names:
         err = float(np.abs(ref[k] - t64[k]).max() / np.abs(t64[k]).max())
         assert err <= 1e-12, (k, err)
     assert ref["stats"][0] == t64["stats"][0] == inp["q"].numel() and ref["stats"][7] == 0.0
@@ -157,8 +158,8 @@ def test_the_td_restatement_is_float64_autograd_of_the_two_losses(shape, weight)
     over = inp["done"].numpy() != 0
     assert np.array_equal(ref["td"][over], inp["rew"].double().numpy()[over])
     bad = dict(inp, q_next=torch.where(inp["done"] != 0, torch.tensor(float("nan")), inp["q_next"]))
-    assert all(np.array_equal(D.ref_td_head(bad, weight=weight)[k], ref[k]) for k in D.TD_NAMES + ("stats",))
-    assert np.array_equal(D.ref_td_head(inp, gamma=0.0)["td"], inp["rew"].double().numpy())
+    assert all(np.array_equal(D.HEAD.ref(bad, weight=weight)[k], ref[k]) for k in D.HEAD.names + ("stats",))
+    assert np.array_equal(D.HEAD.ref(inp, gamma=0.0)["td"], inp["rew"].double().numpy())
 
 
 @pytest.mark.parametrize("shape", D.KINK_SHAPES, ids=lambda s: "B%d-nA%d-Do%d-k%d" % s)
@@ -184,7 +185,7 @@ def test_the_stepped_case_stays_under_the_cap_and_its_kink_filter_has_reached_it
     B, nA, Do, k, central = shape
     c = D.stepped_case(shape)
     print(D.shape_id(shape), f"seed {c.seed}: left out {100 * c.share:.2f} % after {c.rounds} zeroing rounds")
-    assert c.share < U.KINK_CAP and c.rounds <= D.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
+    assert c.share < U.KINK_CAP and c.rounds <= O.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
     obs, act, _, obs_next, _ = c.batch
     x_cur, _, x_pi = D.joins64(c.actor, obs, obs_next, act, central)
     stepped = c.ref["critic"]["net"]

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 from guard_util import Buffers
 
 pytestmark = pytest.mark.gpu
@@ -14,8 +15,7 @@ pytestmark = pytest.mark.gpu
 COPY_SHAPES = D.SHAPES[:-1] + ((300, 16, 1, 3, 0),)     # (the head's larger shape has nothing for the copies: a second workgroup does)
 
 
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.int32)
+_bits, _same_bits = O.bits, O.same_bits
 
 
 def _same(t, want):
@@ -96,30 +96,8 @@ def test_central_and_own_leave_the_same_bits_for_a_team_of_one():
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the TD head
-def _head(inp, weight=True, gamma=D.GAMMA, guarded=False, fill=7.0, td=True):
-    from deep_rl_battlespace_amd.learner import td_head, td_head_workspace_bytes
-    B, nA = inp["q"].shape
-    G = Buffers(guarded)
-    dev = {}
-    for k, v in inp.items():
-        dev[k] = G(k, tuple(v.shape), v.dtype)
-        dev[k].copy_(v)
-    out = (G("g_q", (B, nA, 4), torch.float32, init=fill), G("g_pi", (B, nA, 4), torch.float32, init=fill),
-           G("td", (B, nA), torch.float32, init=fill) if td else None, G("stats", (8,), torch.float64, init=fill))
-    ws = G("workspace", (td_head_workspace_bytes(B, nA) // 8,), torch.int64, init=-1)
-    res = td_head(dev["q"], dev["q_next"], dev["rew"], dev["done"], gamma, weight=dev["weight"] if weight else None, out=out, workspace=ws)
-    torch.cuda.synchronize()
-    assert res.g_q is out[0] and res.g_pi is out[1] and res.td is out[2] and res.stats is out[3]
-    return res, G.stray()
-
-
-def _numpy(res):
-    return dict(g_q=res.g_q.double().cpu().numpy(), g_pi=res.g_pi.double().cpu().numpy(), td=res.td.double().cpu().numpy(),
-                stats=res.stats.cpu().numpy())
-
-
-def _same_bits(a, b):
-    return all(x is None and y is None or torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
+def _head(inp, *args, **kw):
+    return O.guarded_head(D.HEAD, inp, *args, **kw)
 
 
 @pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
@@ -128,21 +106,21 @@ def test_the_td_head_stays_within_the_float32_yardstick_of_the_float64_contract_
     """Every shape of the table, the larger one included (two tiles per workgroup, five rounds of the merge).  Two fills: an output
     float that keeps both was not written."""
     B, nA = shape[:2]
-    inp, ref, yard, e_stats = D.td_case(B, nA, weight)
+    inp, ref, yard, e_stats = D.HEAD.case(B, nA, weight)
     fills = []
     for fill in (7.0, -3.0):
         res, stray = _head(inp, weight, guarded=True, fill=fill)
         assert not stray, stray
         fills.append([t.clone() for t in res])
     assert _same_bits(*fills)
-    got = _numpy(res)
-    D.check_td(got, ref, yard, e_stats, f"TD {D.shape_id(shape)} {'weighted' if weight else 'plain'}")
+    D.HEAD.check(O.numpy_of(res, D.HEAD.names), ref, yard, e_stats, f"TD {D.shape_id(shape)} {'weighted' if weight else 'plain'}",
+                 D.HEAD.factors(B, nA, weight))
     assert not _bits(res.g_q)[..., 1:].any() and not _bits(res.g_pi)[..., 1:].any()           # columns 1 .. 3: +0
 
 
 def test_finished_rows_and_gamma_zero_give_the_reward_exactly_and_keep_q_next_out():
     B, nA = D.SHAPES[3][:2]
-    inp, *_ = D.td_case(B, nA)
+    inp, *_ = D.HEAD.case(B, nA)
     allover = dict(inp, done=torch.ones_like(inp["done"]), q_next=torch.full_like(inp["q_next"], float("nan")))
     res, _ = _head(allover)
     assert torch.equal(res.td.cpu().view(torch.int32), inp["rew"].view(torch.int32))
@@ -160,7 +138,7 @@ def test_finished_rows_and_gamma_zero_give_the_reward_exactly_and_keep_q_next_ou
 
 def test_no_weight_is_a_weight_of_ones_bit_for_bit_and_a_weight_of_zero_gives_zero_gradients():
     B, nA = D.SHAPES[4][:2]
-    inp, *_ = D.td_case(B, nA)
+    inp, *_ = D.HEAD.case(B, nA)
     none, _ = _head(inp, weight=False)
     ones, _ = _head(dict(inp, weight=torch.ones_like(inp["weight"])))
     assert _same_bits(none, ones)
@@ -179,7 +157,7 @@ def test_no_weight_is_a_weight_of_ones_bit_for_bit_and_a_weight_of_zero_gives_ze
 def test_the_same_bits_on_two_calls_and_from_a_captured_graph(shape):
     from deep_rl_battlespace_amd.learner import td_head, td_head_workspace_bytes
     B, nA = shape[:2]
-    inp, *_ = D.td_case(B, nA)
+    inp, *_ = D.HEAD.case(B, nA)
     first, _ = _head(inp)
     second, _ = _head(inp, fill=-3.0)
     assert _same_bits(first, second)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 
 pytestmark = pytest.mark.gpu
 
@@ -73,7 +74,7 @@ def _same(what, ro, tw, buf, buf2, learner, hand):
         assert torch.equal(getattr(buf, f), getattr(buf2, f)), (what, f)
     assert buf.mem_cntr == buf2.mem_cntr and torch.equal(buf.last_idx, buf2.last_idx), what
     a, b = D.snapshot(learner), D.snapshot(hand)
-    assert D.differing(a, b) == [], (what, D.differing(a, b))
+    assert O.differing(a, b) == [], (what, O.differing(a, b))
     assert torch.equal(ro.fused.weights.view(torch.int32), tw.fused.weights.view(torch.int32)), what
 
 
@@ -90,10 +91,10 @@ def test_the_documented_loop_equals_its_eager_twin_bit_for_bit(name):
     buf, buf2 = (DeviceReplayBuffer(c.M, c.B, agents, env.obs_size, env.obs_size * n, k, device="cuda", seed=3) for _ in range(2))
     actor, critic = _team_nets(ro, cols, c.central, seed)
     learner = DDPGLearner(buf, actor, critic, critic_input="central" if c.central else "own", updates=2, **D.KW)
-    hand = D.Hand(buf2, D.gpu_copy(actor), D.gpu_copy(critic), c.central, updates=2, **D.KW)
+    hand = D.Hand(buf2, O.gpu_copy(actor), O.gpu_copy(critic), c.central, updates=2, **D.KW)
     start = D.snapshot(learner)
-    assert learner.capture() is learner and D.differing(start, D.snapshot(learner)) == []     # on the empty ring, and it ran nothing
-    assert buf.mem_cntr == 0 and D.differing(start, D.snapshot(hand)) == []
+    assert learner.capture() is learner and O.differing(start, D.snapshot(learner)) == []     # on the empty ring, and it ran nothing
+    assert buf.mem_cntr == 0 and O.differing(start, D.snapshot(hand)) == []
     if c.then:
         ro.capture(then=lambda: buf.append_rollout(ro, cols))
     else:

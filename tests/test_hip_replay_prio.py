@@ -13,6 +13,7 @@ import torch
 
 import ddpg_util as D
 import guard_util as G
+import offpolicy_util as O
 import prio_util as PU
 import yardstick_util as Y
 from prio_ring_util import OBS, RING_FIELDS
@@ -284,19 +285,10 @@ def test_no_stray_writes_from_sample_update_or_append():
 LEARNER_SHAPES = ((33, 2, 8, 4, 1), (512, 1, 5, 4, 0))         # 2v2 central at B = 33, 1v1 own at B = 512
 
 
-def _prio_ring(rows, B, seed=3):
-    """A PrioritizedReplayBuffer of len(rows) transitions filled through _put (ddpg_util.ring's, prioritised)."""
-    obs, act, rew, obs_next, done = (r.cuda() for r in rows)
-    N, nA, Do = obs.shape
-    buf = _buf(N, B, nA, act.shape[2], seed=seed, D_=Do)
-    buf._put(obs, act, rew, obs_next, done)
-    return buf
-
-
 def _learner(shape, updates=1):
     from deep_rl_battlespace_amd.learner import DDPGLearner
     actor, critic, rows, *_ = D.learner_case(shape)
-    return DDPGLearner(_prio_ring(rows, shape[0]), D.gpu_copy(actor), D.gpu_copy(critic), critic_input="central" if shape[4] else "own",
+    return DDPGLearner(O.ring(rows, shape[0], prioritized=True), O.gpu_copy(actor), O.gpu_copy(critic), critic_input="central" if shape[4] else "own",
                        updates=updates, **D.KW)
 
 
@@ -314,7 +306,7 @@ def test_a_learner_on_a_prioritised_ring_is_the_by_hand_sequence_of_the_public_c
     from deep_rl_battlespace_amd import learner as L
     learner = _learner(shape)
     actor, critic, rows, *_ = D.learner_case(shape)
-    hand = D.Hand(_prio_ring(rows, shape[0]), D.gpu_copy(actor), D.gpu_copy(critic), shape[4], **D.KW)
+    hand = D.Hand(O.ring(rows, shape[0], prioritized=True), O.gpu_copy(actor), O.gpu_copy(critic), shape[4], **D.KW)
     real, calls = L.td_head, []
 
     def td_head_then_priorities(q, q_next, rew, done, gamma, **kw):
@@ -324,15 +316,15 @@ def test_a_learner_on_a_prioritised_ring_is_the_by_hand_sequence_of_the_public_c
         calls.append(1)
         return head
     start = _snapshot(learner)
-    assert D.differing(start, _snapshot(hand)) == []
+    assert O.differing(start, _snapshot(hand)) == []
     for u in range(3):
         stats = learner.update()
         s = hand.buffer.sample()
         monkeypatch.setattr(L, "td_head", td_head_then_priorities)
-        hand.step(s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6], 0, weight=hand.buffer.weights)
+        hand.step(*O.batch_of(s), 0, weight=hand.buffer.weights)
         monkeypatch.setattr(L, "td_head", real)
         a, b = _snapshot(learner), _snapshot(hand)
-        assert D.differing(a, b) == [] and len(calls) == u + 1, (u, D.differing(a, b))
+        assert O.differing(a, b) == [] and len(calls) == u + 1, (u, O.differing(a, b))
         assert torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
         assert torch.equal(learner.buffer.weights.view(torch.int32), hand.buffer.weights.view(torch.int32))
         _assert_tree_exact(learner.buffer, u)
@@ -343,7 +335,7 @@ def test_a_learner_on_a_prioritised_ring_is_the_by_hand_sequence_of_the_public_c
         err, bound = abs(float(stats[0, 6]) - w.mean()), Y.scalar_bound(w.mean(), own)
         print(f"{D.shape_id(shape)} update {u}: mean weight {w.mean():.9g}, stats error {err:.3e}, bound {bound:.3e}")
         assert err <= bound and (u == 0 or w.min() < 1.0)
-    assert {"leaves", "tree", "max_priority", "actor.w1", "critic.w1", "draws"} <= set(D.differing(start, a))
+    assert {"leaves", "tree", "max_priority", "actor.w1", "critic.w1", "draws"} <= set(O.differing(start, a))
     assert int(learner.buffer._draws) == 3 and PU.unsigned(learner.buffer.max_priority)[0] > PU.ONE
 
 
@@ -353,7 +345,7 @@ def test_a_captured_update_on_a_prioritised_ring_replays_the_eager_updates_and_a
     start = _snapshot(captured)
     state = [t.detach().clone() for t in captured._state()]
     assert captured.capture() is captured
-    assert D.differing(start, _snapshot(captured)) == []                                # capture() leaves everything as it was
+    assert O.differing(start, _snapshot(captured)) == []                                # capture() leaves everything as it was
     assert all(torch.equal(_bits(a), _bits(b.detach())) for a, b in zip(state, captured._state())) and len(state) == len(eager._state())
     assert any(t is captured.buffer._leaves for t in captured._state()) and any(t is captured.buffer.tree for t in captured._state())
     draws = []
@@ -362,7 +354,7 @@ def test_a_captured_update_on_a_prioritised_ring_replays_the_eager_updates_and_a
         eager.update()
         draws.append(captured.buffer.last_idx.clone())
         a, b = _snapshot(captured), _snapshot(eager)
-        assert D.differing(a, b) == [], (u, D.differing(a, b))
+        assert O.differing(a, b) == [], (u, O.differing(a, b))
         _assert_tree_exact(captured.buffer, u)
     assert not torch.equal(draws[0], draws[1]) and not torch.equal(draws[1], draws[2]) and int(captured.buffer._draws) == 6
     del a, b

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 import philox_util as PU
 import sac_util as S
 import yardstick_util as Y
@@ -19,45 +20,13 @@ from guard_util import Buffers
 pytestmark = pytest.mark.gpu
 
 SEED, SEQ, SEQ_BASE = 0x1234ABCD5678, 7, (1 << 33) + 1000
-NORMAL_TOL = 1e-5                 # |z - z64| <= NORMAL_TOL * (1 + |z64|), tests/test_hip_gaussian_head.py's rule
-NAN = float("nan")
-SENTINEL = np.int32(0x7FC0BEEF)   # a NaN with a payload: no arithmetic produces it
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.int32)
-
-
-def _same_bits(a, b):
-    return all(x is None and y is None or torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
-
-
-def _put(G, inp):
-    dev = {}
-    for k, v in inp.items():
-        dev[k] = G(k, tuple(v.shape), v.dtype)
-        dev[k].copy_(v)
-    return dev
+NORMAL_TOL, NAN, SENTINEL = O.NORMAL_TOL, O.NAN, O.SENTINEL
+_bits, _same_bits, _put = O.bits, O.same_bits, O.put
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the soft twin head
-def _head(inp, weight=True, gamma=D.GAMMA, guarded=False, fill=7.0):
-    from deep_rl_battlespace_amd.learner import sac_head, sac_head_workspace_bytes
-    B, nA = inp["q1"].shape
-    G = Buffers(guarded)
-    dev = _put(G, inp)
-    out = tuple(G(k, (B, nA, 4), torch.float32, init=fill) for k in ("g_q1", "g_q2")) + \
-        (G("td", (B, nA), torch.float32, init=fill), G("stats", (8,), torch.float64, init=fill))
-    ws = G("workspace", (sac_head_workspace_bytes(B, nA) // 8,), torch.int64, init=-1)
-    res = sac_head(dev["q1"], dev["q2"], dev["q1_next"], dev["q2_next"], dev["logp_next"], dev["rew"], dev["done"], dev["log_alpha"], gamma,
-                   weight=dev["weight"] if weight else None, out=out, workspace=ws)
-    torch.cuda.synchronize()
-    assert all(a is b for a, b in zip(res, out))
-    return res, G.stray()
-
-
-def _numpy(res, names):
-    return dict({k: getattr(res, k).double().cpu().numpy() for k in names}, stats=res.stats.cpu().numpy())
+def _head(inp, *args, **kw):
+    return O.guarded_head(S.HEAD, inp, *args, **kw)
 
 
 @pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
@@ -66,14 +35,14 @@ def test_the_soft_head_stays_within_the_float32_yardstick_of_the_float64_contrac
     """Every shape of td3_util.HEAD_SHAPES, the last with two tiles per workgroup and five merge rounds, at the project's (2, 4) or the
     factor yardstick_util's rule makes of the yardstick's own recorded spread (profiles/sac_float64.json).  Two fills: an output float
     that keeps both was not written; the two calls leave the same bits."""
-    inp, ref, yard, e_stats = S.sac_case(*BnA, weight)
+    inp, ref, yard, e_stats = S.HEAD.case(*BnA, weight)
     fills = []
     for fill in (7.0, -3.0):
         res, stray = _head(inp, weight, guarded=True, fill=fill)
         assert not stray, stray
         fills.append([t.clone() for t in res])
     assert _same_bits(*fills)
-    S.check_sac(_numpy(res, S.TD_NAMES), ref, yard, e_stats, "SAC " + S.head_id(*BnA, weight), S.factors(*BnA, weight))
+    S.HEAD.check(O.numpy_of(res, S.HEAD.names), ref, yard, e_stats, "SAC " + O.head_id(*BnA, weight), S.HEAD.factors(*BnA, weight))
     assert all(not _bits(getattr(res, k))[..., 1:].any() for k in ("g_q1", "g_q2"))       # columns 1 .. 3: +0
 
 
@@ -83,12 +52,12 @@ def test_the_soft_heads_per_element_outputs_are_the_contracts_bits(BnA, weight):
     """g_q1, g_q2 and td against sac_util.contract32, the header's contract operation by operation in float32: the same bits at every
     shape.  log_alpha is drawn from {-inf, 0} per agent -- alpha is exactly 0 or 1 in any implementation of exp, so the soft value's
     fmaf is in the comparison and no library rounding is."""
-    inp, *_ = S.sac_case(*BnA, weight)
+    inp, *_ = S.HEAD.case(*BnA, weight)
     g = torch.Generator().manual_seed(8900 + 7 * BnA[0] + BnA[1])
     inp = dict(inp, log_alpha=torch.where(torch.rand(BnA[1], generator=g) < 0.5, -math.inf, 0.0).to(torch.float32))
     res, _ = _head(inp, weight)
     want = S.contract32(inp, weight=weight)
-    for k in S.TD_NAMES:
+    for k in S.HEAD.names:
         assert np.array_equal(_bits(getattr(res, k)), want[k].astype(np.float32).view(np.int32)), k
 
 
@@ -96,7 +65,7 @@ def test_the_soft_heads_per_element_outputs_are_the_contracts_bits(BnA, weight):
 @pytest.mark.parametrize("BnA", (S.HEAD_SHAPES[2], S.HEAD_SHAPES[-1]), ids=lambda s: "B%d-nA%d" % s)
 def test_with_alpha_exactly_zero_the_head_is_bsx_td3_heads_bit_for_bit(BnA, weight):
     from deep_rl_battlespace_amd.learner import td3_head
-    inp, *_ = S.sac_case(*BnA)
+    inp, *_ = S.HEAD.case(*BnA)
     res, _ = _head(dict(inp, log_alpha=torch.full_like(inp["log_alpha"], -math.inf)), weight)
     dev = {k: v.cuda() for k, v in inp.items()}
     two = td3_head(dev["q1"], dev["q2"], dev["q1_next"], dev["q2_next"], dev["rew"], dev["done"], D.GAMMA, weight=dev["weight"] if weight else None)
@@ -109,7 +78,7 @@ def test_with_alpha_exactly_zero_the_head_is_bsx_td3_heads_bit_for_bit(BnA, weig
 
 def test_a_finished_row_keeps_a_nan_logp_next_out_and_a_running_row_carries_it():
     B, nA = S.HEAD_SHAPES[2]
-    inp, *_ = S.sac_case(B, nA)
+    inp, *_ = S.HEAD.case(B, nA)
     over = inp["done"] != 0
     assert 20 < int(over.sum()) < B * nA - 20
     nan = torch.tensor(NAN)
@@ -131,10 +100,7 @@ def test_a_finished_row_keeps_a_nan_logp_next_out_and_a_running_row_carries_it()
 
 # ---------------------------------------------------------------------------------------------------- 2. the draw
 def _x(G, shape, name="x"):
-    B, nA, Do, k, central = shape
-    x = G(name, (B, nA, D.width(nA, Do, k, central)), torch.float32)
-    x.view(torch.int32).fill_(int(SENTINEL))
-    return x
+    return O.sentinel_x(G, shape, D.width(*shape[1:]), name)
 
 
 @pytest.mark.parametrize("own_only", [False, True], ids=["every-slot", "own-only"])
@@ -270,7 +236,7 @@ def test_the_policy_gradients_g_a4_bit_for_bit_and_the_sums_within_the_yardstick
     got = dict(g_log_std=res.g_log_std.double().cpu().numpy(), g_log_alpha=res.g_log_alpha.double().cpu().numpy())
     what = "SAC policy " + D.shape_id(shape)
     bad = [b for k_ in ("g_log_std", "g_log_alpha") for b in S.sums_out_of_bounds(got[k_], ref[k_], own[k_], k_, what)]
-    bad += S.pi_stats_out_of_bounds(res.stats.cpu().numpy(), ref["stats"], own["stats"], what)
+    bad += O.stats_out_of_bounds(res.stats.cpu().numpy(), ref["stats"], own["stats"], S.PI_STAT_NAMES, what)
     assert not bad, bad
     assert torch.equal(dev["log_alpha"].cpu().view(torch.int32), inp["log_alpha"].view(torch.int32))
     again, _ = _policy(inp, shape, weight, guarded=False)

@@ -3,110 +3,78 @@ Hand), on a plain and on a prioritised ring; a captured update runs nothing, rep
 and allocates nothing; with lr_alpha=None the temperature never moves; a whole update from target critics that are not the critics
 against float64; one iteration of the documented loop on a real continuous 1v1 env with a Gaussian rollout; and a bandit on which the
 captured updates must learn at least half of what the torch composition of the same SAC learns."""
-import gc
-import json
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 import sac_util as S
-import td3_util as T
 
 pytestmark = pytest.mark.gpu
 
 KW = D.KW
 
 
-def _central(shape):
-    return "central" if shape[4] else "own"
+_learner, _hand = S.SUITE.learner, S.SUITE.hand
+
+HAND_CASES = [(s, False) for s in S.HAND_SHAPES] + [(s, True) for s in S.HAND_SHAPES[:2]]
 
 
-def _nets(shape, seed=0):
-    actor, critic, rows, *_ = D.learner_case(shape, seed)
-    return (D.gpu_copy(actor), D.gpu_copy(critic), D.gpu_copy(T.critic2_of(shape, seed))), rows
-
-
-def _learner(shape, ring=D.ring, seed=0, **kw):
-    from deep_rl_battlespace_amd.learner import SACLearner
-    made, rows = _nets(shape, seed)
-    return SACLearner(ring(rows, shape[0]), *made, critic_input=_central(shape), **{**KW, **kw})
-
-
-def _hand(shape, ring=D.ring, seed=0, **kw):
-    made, rows = _nets(shape, seed)
-    return S.Hand(ring(rows, shape[0]), *made, shape[4], **{**KW, **kw})
-
-
-HAND_CASES = [(s, D.ring) for s in S.HAND_SHAPES] + [(s, T.prio_ring) for s in S.HAND_SHAPES[:2]]
-
-
-@pytest.mark.parametrize("shape,ring", HAND_CASES, ids=[D.shape_id(s) + ("-prioritised" if r is T.prio_ring else "") for s, r in HAND_CASES])
-def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(shape, ring):
-    learner, hand = _learner(shape, ring, updates=2), _hand(shape, ring, updates=2)
+@pytest.mark.parametrize("shape,prio", HAND_CASES, ids=[D.shape_id(s) + ("-prioritised" if prio else "") for s, prio in HAND_CASES])
+def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(shape, prio):
+    learner, hand = _learner(shape, prio, updates=2), _hand(shape, prio, updates=2)
     start = S.snapshot(learner)
-    assert D.differing(start, S.snapshot(hand)) == []
+    assert O.differing(start, S.snapshot(hand)) == []
     for call in range(2):
         stats = learner.update()
         hand.update()
         a, b = S.snapshot(learner), S.snapshot(hand)
-        assert D.differing(a, b) == [], (call, D.differing(a, b))
+        assert O.differing(a, b) == [], (call, O.differing(a, b))
         assert stats is learner.stats and stats.shape == (2, 8) and float(stats[1, 0]) == shape[0] * shape[1]
         assert torch.equal(learner.td.view(torch.int32), hand.td.view(torch.int32))
     assert int(learner.step_critic) == 4 == int(learner.step_actor) == int(learner.step_alpha) and int(learner.buffer._draws) == 4
     assert int(learner._noise_draws) == 8                                      # two draws per update
     assert torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
-    moved = set(D.differing(start, a))
+    moved = set(O.differing(start, a))
     assert {"actor.w1", "critic.w1", "critic2.w1", "target_critic.w2", "target_critic2.w2", "_blob_a", "_blob_c", "_blob_c2", "_blob_tc", "_blob_tc2",
             "adam_actor.m", "adam_critic.v", "adam_critic2.v", "stats", "stats_pi", "step_stats_actor", "step_stats_critic", "draws", "noise_draws",
             "log_std", "log_alpha", "adam_log_std.m", "adam_alpha.v", "step_alpha"} <= moved
-    assert ring is D.ring or {"leaves", "tree", "max_priority"} <= moved
+    assert not prio or {"leaves", "tree", "max_priority"} <= moved
     # SAC has no target actor: the inherited one is never read or stepped
     assert not {k for k in moved if k.startswith("target_actor.")} and "_blob_ta" not in moved
-    S.blobs_are_packs(learner)
+    O.blobs_are_packs(learner)
     pi = learner.stats_pi.cpu().numpy()
     assert (pi[:, 0] == shape[0] * shape[1]).all() and (pi[:, 7] == 0).all() and ((0 <= pi[:, 6]) & (pi[:, 6] <= 1)).all()
     # alpha's mean: four Adam steps of at most about lr_alpha = 3e-4 each from log 0.2;  q_gap: the critics differ
     assert (np.abs(np.log(pi[:, 4] / 0.2)) <= 4 * 1.5 * 3e-4).all() and float(learner.stats[1, 7]) > 0.0
 
 
-@pytest.mark.parametrize("ring", [D.ring, T.prio_ring], ids=["uniform", "prioritised"])
-def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(ring):
+@pytest.mark.parametrize("prio", [False, True], ids=["uniform", "prioritised"])
+def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(prio):
     shape = S.MAIN_SHAPES[0]
-    captured, eager = (_learner(shape, ring, updates=2) for _ in range(2))
-    start = S.snapshot(captured)
+    captured, eager = (_learner(shape, prio, updates=2) for _ in range(2))
     state = [t.detach().clone() for t in captured._state()]
-    assert captured.capture() is captured
-    assert D.differing(start, S.snapshot(captured)) == []                     # a capture runs nothing
+    O.capture_runs_nothing(captured, S.snapshot)
     assert all(torch.equal(a.view(torch.uint8), b.detach().view(torch.uint8)) for a, b in zip(state, captured._state()))
     for t in (captured._noise_draws, captured.log_std, captured.log_alpha, captured.step_alpha, captured.adam_alpha.m, captured.adam_log_std.v,
               captured._blob_c2, captured._blob_tc2, captured.stats_pi):
         assert any(t is s for s in captured._state())
-    assert ring is D.ring or any(t is captured.buffer.tree for t in captured._state())
+    assert not prio or any(t is captured.buffer.tree for t in captured._state())
     draws, tds, logps = [], [], []
-    for u in range(2):
-        captured.update()
-        eager.update()
+
+    def each(u):
         draws.append(captured.buffer.last_idx.clone())
         tds.append(captured.td.clone())
         logps.append(captured._logp.clone())
-        a, b = S.snapshot(captured), S.snapshot(eager)
-        assert D.differing(a, b) == [], (u, D.differing(a, b))
         assert torch.equal(captured.td.view(torch.int32), eager.td.view(torch.int32))
+    O.replays_the_eager_updates(captured, eager, S.snapshot, 2, each)
     assert not torch.equal(draws[0], draws[1]) and not torch.equal(tds[0], tds[1]) and not torch.equal(logps[0], logps[1])
     assert int(captured.buffer._draws) == 4 and int(captured._noise_draws) == 8 and int(captured.step_critic) == 4 == int(captured.step_alpha)
-    S.blobs_are_packs(captured)
-    del a, b
-    torch.cuda.synchronize()
-    gc.collect()
-    held = torch.cuda.memory_allocated()
-    captured.update()
-    captured.update()
-    torch.cuda.synchronize()
-    assert torch.cuda.memory_allocated() == held
+    O.blobs_are_packs(captured)
+    O.allocates_nothing(captured)
 
 
 def test_with_lr_alpha_none_the_temperature_never_moves_and_set_lr_reaches_the_captured_step():
@@ -129,20 +97,9 @@ def test_with_lr_alpha_none_the_temperature_never_moves_and_set_lr_reaches_the_c
     assert torch.equal(moving.log_alpha.view(torch.int32), la1.view(torch.int32)) and int(moving.step_alpha) == 2
     # the learner steps the caller's log_std in place
     own = torch.full((shape[1], 3), -0.5, device="cuda")
-    made, rows = _nets(shape)
-    from deep_rl_battlespace_amd.learner import SACLearner
-    x = SACLearner(D.ring(rows, shape[0]), *made, log_std=own, critic_input=_central(shape), **KW)
+    x = _learner(shape, log_std=own)
     x.update()
     assert x.log_std is own and bool((own != -0.5).all())
-
-
-def _step_arrays(x, which):
-    net, state = getattr(x, which), getattr(x, "adam_" + which)
-    cut = lambda row: S.AU.row_to_tensors(row.detach().cpu().numpy(), net.n_actions)     # noqa: E731
-    out = dict(p=S.AU.net_arrays(net), m=cut(state.m), v=cut(state.v))
-    if which != "actor":
-        out["target"] = S.AU.net_arrays(getattr(x, "target_" + which))
-    return out
 
 
 @pytest.mark.parametrize("shape", S.MAIN_SHAPES, ids=D.shape_id)
@@ -153,7 +110,6 @@ def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float
     STEPPED critics and its step, log_std's gradient and step, log_alpha's gradient and step -- each pooled, ddpg_util.check_step's bars
     (2, 4); log_std's and log_alpha's gradients, three numbers and one per agent, by (2, 4) or the factor yardstick_util's rule makes of
     the yardstick's own recorded spread (profiles/sac_float64.json) -- and both statistics rows.  BSX_SAC_RATIOS_OUT names a file the measured ratios are appended to."""
-    from deep_rl_battlespace_amd.learner import split_grad
     B, nA, Do, k, central = shape
     c = S.stepped_case(shape)
     assert c.share < D.U.KINK_CAP
@@ -161,20 +117,12 @@ def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float
     hand.log_alpha.copy_(c.log_alpha)
     for name, net in zip(("actor", "critic", "critic2"), c.nets):
         assert all(torch.equal(getattr(getattr(hand, name), p).cpu(), getattr(net, p)) for p in D.PARAMS), name
-    with torch.no_grad():
-        for t, src, blob in ((hand.target_critic, c.targets[0], hand._blob_tc), (hand.target_critic2, c.targets[1], hand._blob_tc2)):
-            for p in D.PARAMS:
-                getattr(t, p).copy_(getattr(src, p))
-            t.pack(out=blob)
-    S.blobs_are_packs(hand)
-    s = hand.buffer.sample(c.idx)
-    dev_batch = (s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6])
-    for got, want in zip(dev_batch, c.batch):
-        assert torch.equal(got.cpu(), want)
-    out = hand.step(*dev_batch, 0, weight=c.w.cuda(), z_next=c.z_next.cuda(), z_pi=c.z_pi.cuda())
+    O.set_targets(hand, dict(zip(("critic", "critic2"), c.targets)))
+    O.blobs_are_packs(hand)
+    out = hand.step(*O.sample_is(hand, c.idx, c.batch), 0, weight=c.w.cuda(), z_next=c.z_next.cuda(), z_pi=c.z_pi.cuda())
     torch.cuda.synchronize()
     sid, rec = D.shape_id(shape), {}
-    num = lambda row, na: [g.double().cpu().numpy() for g in split_grad(row, na)]          # noqa: E731
+    num = lambda row, na: list(O.grad_arrays(row, na).values())                            # noqa: E731
     lst = lambda g: [g[p] for p in D.PARAMS]                                               # noqa: E731
     print("SAC", sid)
     got = dict(gc1=num(out["row_c"], 1), gc2=num(out["row_c2"], 1), ga=num(out["row_a"], k), g_ls=[out["g_log_std"].double().cpu().numpy()],
@@ -182,8 +130,8 @@ def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float
     ref, yard = ({**{w_: lst(r[w_]) for w_ in ("gc1", "gc2", "ga")}, "g_ls": [r["g_ls"]], "g_la": [r["g_la"]]} for r in (c.ref, c.yard))
     D.check_step(got, ref, yard, "row", rec, names=("gc1", "gc2", "ga"))
     for which in ("critic", "critic2"):
-        D.check_step(_step_arrays(hand, which), c.ref[which], c.yard[which], which, rec)
-    D.check_step(_step_arrays(hand, "actor"), c.ref["actor"], c.yard["actor"], "actor", rec, names=("p", "m", "v"))
+        D.check_step(O.step_arrays(hand, which), c.ref[which], c.yard[which], which, rec)
+    D.check_step(O.step_arrays(hand, "actor"), c.ref["actor"], c.yard["actor"], "actor", rec, names=("p", "m", "v"))
     # what has one value per agent (and column): (2, 4), or the factor the rule makes of the yardstick's own recorded spread
     arr = lambda *ts: dict(zip(("p", "m", "v"), (t.detach().double().cpu().numpy() for t in ts)))          # noqa: E731
     mine = dict(g_ls=got["g_ls"][0], g_la=got["g_la"][0])
@@ -195,14 +143,11 @@ def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float
     rec.update({f"small.{n_}": [round(v[0], 4), round(v[1], 4)] for n_, v in ratios.items()})
     assert not bad, (bad, ratios)
     assert int(hand.step_critic) == 1 == int(hand.step_actor) == int(hand.step_alpha) and int(hand._noise_draws) == 0
-    bad = T.stats_out_of_bounds(hand.stats[0].cpu().numpy(), c.stats, c.e_stats, f"SAC {sid}")
-    bad += S.pi_stats_out_of_bounds(hand.stats_pi[0].cpu().numpy(), c.stats_pi, c.e_stats_pi, f"SAC {sid} policy")
+    bad = S.HEAD.stats_out_of_bounds(hand.stats[0].cpu().numpy(), c.stats, c.e_stats, f"SAC {sid}")
+    bad += O.stats_out_of_bounds(hand.stats_pi[0].cpu().numpy(), c.stats_pi, c.e_stats_pi, S.PI_STAT_NAMES, f"SAC {sid} policy")
     assert not bad, bad
-    S.blobs_are_packs(hand)
-    path = os.environ.get("BSX_SAC_RATIOS_OUT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps({"shape": sid, "ratios": rec}) + "\n")
+    O.blobs_are_packs(hand)
+    O.append_ratios("BSX_SAC_RATIOS_OUT", sid, rec)
 
 
 def test_one_iteration_of_the_documented_loop_on_a_continuous_1v1_env_with_a_gaussian_rollout():
@@ -255,27 +200,13 @@ def test_one_iteration_of_the_documented_loop_on_a_continuous_1v1_env_with_a_gau
 
 
 def test_captured_updates_on_a_bandit_learn_at_least_half_of_what_the_torch_composition_learns():
-    """ddpg_util's bandit at k = 3 (every row finished), own critics, a fixed temperature, updates = 10, captured.  N and the torch
+    """offpolicy_util's bandit at k = 3 (every row finished), own critics, a fixed temperature, updates = 10, captured.  N and the torch
     composition's figures are recorded in profiles/sac_float64.json, chosen on the CPU with the torch composition of the same SAC alone,
     which itself closes at least half of the gap from its initial reward to 0 in N updates (re-run here: a fraction of a second)."""
     from deep_rl_battlespace_amd.learner import SACLearner
-    rec = json.load(open(S.PROFILE))["bandit"]
-    N, b = rec["N"], S.BANDIT
-    r0, r_torch = S.bandit_torch_run(N)
-    closed_torch = (r_torch - r0) / (0.0 - r0)
-    assert abs(r0 - rec["initial_reward"]) < 1e-6 and closed_torch >= 0.5 and {k: rec[k] for k in b} == b
-    rows, held = S.bandit_rows()
-    nets = S.bandit_nets()
-    learner = SACLearner(D.ring(rows, b["B"]), *(D.gpu_copy(x) for x in nets), critic_input="own", alpha=b["alpha"], lr_alpha=None, tau=b["tau"],
-                         lr_actor=b["lr"], lr_critic=b["lr"], updates=10).capture()
-    assert N % 10 == 0
-    for _ in range(N // 10):
-        learner.update()
-    with torch.no_grad():
-        before = float(D.bandit_reward(held, nets[0](held)).mean())
-        after = float(D.bandit_reward(held, learner.actor(held.cuda()).cpu()).mean())
-    closed = (after - before) / (0.0 - before)
-    print(f"bandit, N = {N}: reward {before:.4f} -> {after:.4f} (closed {closed:.3f} of the gap); torch composition of SAC -> {r_torch:.4f} "
-          f"(closed {closed_torch:.3f}; recorded {rec['torch_closed']:.3f})")
-    assert abs(before - r0) < 1e-6 and int(learner.step_actor) == N == int(learner.step_critic) and int(learner.step_alpha) == 0
-    assert closed >= 0.5 * closed_torch
+    b = S.BANDIT
+    make = lambda ring, *nets: SACLearner(ring, *nets, critic_input="own", alpha=b["alpha"], lr_alpha=None, tau=b["tau"], lr_actor=b["lr"],     # noqa: E731
+                                          lr_critic=b["lr"], updates=10)
+    learner, N, rec = O.bandit_test(S.PROFILE, S.bandit_torch_run, make, O.bandit_nets(b=b, critic2="next"), "torch composition of SAC", b)
+    assert {k: rec[k] for k in b} == b
+    assert int(learner.step_actor) == N == int(learner.step_critic) and int(learner.step_alpha) == 0

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 import philox_util as PU
 import td3_util as T
 from guard_util import Buffers
@@ -15,55 +16,29 @@ from guard_util import Buffers
 pytestmark = pytest.mark.gpu
 
 SEED, SEQ, SEQ_BASE = 0x1234ABCD5678, 7, (1 << 33) + 1000
-NORMAL_TOL = 1e-5                 # |z - z64| <= NORMAL_TOL * (1 + |z64|), tests/test_hip_gaussian_head.py's rule (+ one float32 rounding)
-NAN = float("nan")
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.int32)
-
-
-def _same_bits(a, b):
-    return all(x is None and y is None or torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
+NORMAL_TOL, NAN, SENTINEL = O.NORMAL_TOL, O.NAN, O.SENTINEL       # (the bar on the normals here: + one float32 rounding)
+_bits, _same_bits = O.bits, O.same_bits
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the twin head
-def _head(inp, weight=True, gamma=D.GAMMA, guarded=False, fill=7.0):
-    from deep_rl_battlespace_amd.learner import td3_head, td3_head_workspace_bytes
-    B, nA = inp["q1"].shape
-    G = Buffers(guarded)
-    dev = {}
-    for k, v in inp.items():
-        dev[k] = G(k, tuple(v.shape), v.dtype)
-        dev[k].copy_(v)
-    out = tuple(G(k, (B, nA, 4), torch.float32, init=fill) for k in ("g_q1", "g_q2", "g_pi")) + \
-        (G("td", (B, nA), torch.float32, init=fill), G("stats", (8,), torch.float64, init=fill))
-    ws = G("workspace", (td3_head_workspace_bytes(B, nA) // 8,), torch.int64, init=-1)
-    res = td3_head(dev["q1"], dev["q2"], dev["q1_next"], dev["q2_next"], dev["rew"], dev["done"], gamma,
-                   weight=dev["weight"] if weight else None, out=out, workspace=ws)
-    torch.cuda.synchronize()
-    assert all(a is b for a, b in zip(res, out))
-    return res, G.stray()
-
-
-def _numpy(res):
-    return dict({k: getattr(res, k).double().cpu().numpy() for k in T.TD_NAMES}, stats=res.stats.cpu().numpy())
+def _head(inp, *args, **kw):
+    return O.guarded_head(T.HEAD, inp, *args, **kw)
 
 
 @pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
 @pytest.mark.parametrize("BnA", T.HEAD_SHAPES, ids=lambda s: "B%d-nA%d" % s)
 def test_the_twin_head_stays_within_the_float32_yardstick_of_the_float64_contract_between_guard_slabs(BnA, weight):
     """Every shape of the issue, the larger one included (two tiles per workgroup, five rounds of the merge), at the project's (2, 4) --
-    but for the one-element shape, where profiles/td3_float64.json records the yardstick's own spread (td3_util.head_spread) and the
+    but for the one-element shape, where profiles/td3_float64.json records the yardstick's own spread (td3_util.HEAD.spread) and the
     factor the rule makes of it.  Two fills: an output float that keeps both was not written; the two calls leave the same bits."""
-    inp, ref, yard, e_stats = T.td3_case(*BnA, weight)
+    inp, ref, yard, e_stats = T.HEAD.case(*BnA, weight)
     fills = []
     for fill in (7.0, -3.0):
         res, stray = _head(inp, weight, guarded=True, fill=fill)
         assert not stray, stray
         fills.append([t.clone() for t in res])
     assert _same_bits(*fills)
-    T.check_td3(_numpy(res), ref, yard, e_stats, "TD3 " + T.head_id(*BnA, weight), T.factors(*BnA, weight))
+    T.HEAD.check(O.numpy_of(res, T.HEAD.names), ref, yard, e_stats, "TD3 " + O.head_id(*BnA, weight), T.HEAD.factors(*BnA, weight))
     assert all(not _bits(getattr(res, k))[..., 1:].any() for k in ("g_q1", "g_q2", "g_pi"))       # columns 1 .. 3: +0
 
 
@@ -72,10 +47,10 @@ def test_the_twin_head_stays_within_the_float32_yardstick_of_the_float64_contrac
 def test_the_twin_heads_per_element_outputs_are_the_contracts_bits(BnA, weight):
     """g_q1, g_q2, g_pi and td against td3_util.contract32, the header's contract operation by operation in float32: the same bits at
     every shape, not only within the yardstick (the statistics are sums and stay with the test above)."""
-    inp, *_ = T.td3_case(*BnA, weight)
+    inp, *_ = T.HEAD.case(*BnA, weight)
     res, _ = _head(inp, weight)
     want = T.contract32(inp, weight=weight)
-    for k in T.TD_NAMES:
+    for k in T.HEAD.names:
         assert np.array_equal(_bits(getattr(res, k)), want[k].astype(np.float32).view(np.int32)), k
 
 
@@ -83,7 +58,7 @@ def test_the_twin_heads_per_element_outputs_are_the_contracts_bits(BnA, weight):
 @pytest.mark.parametrize("BnA", (T.HEAD_SHAPES[2], T.HEAD_SHAPES[-1]), ids=lambda s: "B%d-nA%d" % s)
 def test_with_the_second_critic_a_copy_of_the_first_the_head_is_bsx_td_heads_bit_for_bit(BnA, weight):
     from deep_rl_battlespace_amd.learner import td_head
-    inp, *_ = T.td3_case(*BnA)
+    inp, *_ = T.HEAD.case(*BnA)
     res, _ = _head(dict(inp, q2=inp["q1"], q2_next=inp["q1_next"]), weight)
     dev = {k: v.cuda() for k, v in inp.items()}
     one = td_head(dev["q1"], dev["q1_next"], dev["rew"], dev["done"], D.GAMMA, weight=dev["weight"] if weight else None)
@@ -96,7 +71,7 @@ def test_with_the_second_critic_a_copy_of_the_first_the_head_is_bsx_td_heads_bit
 
 def test_a_finished_row_keeps_both_q_next_out_and_a_nan_in_either_target_critic_reaches_a_running_row():
     B, nA = T.HEAD_SHAPES[2]
-    inp, *_ = T.td3_case(B, nA)
+    inp, *_ = T.HEAD.case(B, nA)
     over = inp["done"] != 0
     assert 20 < int(over.sum()) < B * nA - 20
     nan = torch.tensor(NAN)
@@ -122,14 +97,8 @@ def test_a_finished_row_keeps_both_q_next_out_and_a_nan_in_either_target_critic_
 
 
 # ---------------------------------------------------------------------------------------------------- 2. the smoothing
-SENTINEL = np.int32(0x7FC0BEEF)           # a NaN with a payload: no arithmetic produces it
-
-
 def _x(G, shape, name="x"):
-    B, nA, Do, k, central = shape
-    x = G(name, (B, nA, D.width(nA, Do, k, central)), torch.float32)
-    x.view(torch.int32).fill_(int(SENTINEL))
-    return x
+    return O.sentinel_x(G, shape, D.width(*shape[1:]), name)
 
 
 # each (B, nA, Do) of ddpg_util.SHAPES with own and with central critics at k = 3 and 4, wherever the critic's input fits its 64 columns

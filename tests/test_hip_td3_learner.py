@@ -3,15 +3,12 @@ Hand), on a plain and on a prioritised ring; the delayed schedule; a captured up
 fresh draws and fresh noise and allocates nothing; with a copy of the critic as the second one, no noise and no delay it is
 DDPGLearner bit for bit; a whole update from target networks that are not the networks against float64; the smoothing reaches the
 target on running rows alone; and a bandit on which the captured updates must learn at least half of what the torch composition learns."""
-import gc
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 import td3_util as T
 
 pytestmark = pytest.mark.gpu
@@ -19,49 +16,31 @@ pytestmark = pytest.mark.gpu
 KW = D.KW
 
 
-def _central(shape):
-    return "central" if shape[4] else "own"
+_learner, _hand = T.SUITE.learner, T.SUITE.hand
+
+HAND_CASES = [(s, False) for s in T.HAND_SHAPES] + [(T.HAND_SHAPES[0], True)]      # (one case on a prioritised ring)
 
 
-def _nets(shape, seed=0):
-    actor, critic, rows, *_ = D.learner_case(shape, seed)
-    return (D.gpu_copy(actor), D.gpu_copy(critic), D.gpu_copy(T.critic2_of(shape, seed))), rows
-
-
-def _learner(shape, ring=D.ring, rows=None, seed=0, nets=None, **kw):
-    from deep_rl_battlespace_amd.learner import TD3Learner
-    made, case_rows = _nets(shape, seed)
-    return TD3Learner(ring(case_rows if rows is None else rows, shape[0]), *(nets or made), critic_input=_central(shape), **{**KW, **kw})
-
-
-def _hand(shape, ring=D.ring, rows=None, seed=0, **kw):
-    made, case_rows = _nets(shape, seed)
-    return T.Hand(ring(case_rows if rows is None else rows, shape[0]), *made, shape[4], **{**KW, **kw})
-
-
-HAND_CASES = [(s, D.ring) for s in T.HAND_SHAPES] + [(T.HAND_SHAPES[0], T.prio_ring)]      # (one case on a prioritised ring)
-
-
-@pytest.mark.parametrize("shape,ring", HAND_CASES, ids=[D.shape_id(s) + ("-prioritised" if r is T.prio_ring else "") for s, r in HAND_CASES])
-def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(shape, ring):
-    learner, hand = _learner(shape, ring, updates=2, policy_delay=2), _hand(shape, ring, updates=2, policy_delay=2)
+@pytest.mark.parametrize("shape,prio", HAND_CASES, ids=[D.shape_id(s) + ("-prioritised" if prio else "") for s, prio in HAND_CASES])
+def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(shape, prio):
+    learner, hand = _learner(shape, prio, updates=2, policy_delay=2), _hand(shape, prio, updates=2, policy_delay=2)
     start = T.snapshot(learner)
-    assert D.differing(start, T.snapshot(hand)) == []
+    assert O.differing(start, T.snapshot(hand)) == []
     for call in range(2):
         stats = learner.update()
         hand.update()
         a, b = T.snapshot(learner), T.snapshot(hand)
-        assert D.differing(a, b) == [], (call, D.differing(a, b))
+        assert O.differing(a, b) == [], (call, O.differing(a, b))
         assert stats is learner.stats and stats.shape == (2, 8) and float(stats[1, 0]) == shape[0] * shape[1]
         assert torch.equal(learner.td.view(torch.int32), hand.td.view(torch.int32))
     assert int(learner.step_critic) == 4 and int(learner.step_actor) == 2 and int(learner.buffer._draws) == 4 == int(learner._noise_draws)
     assert torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
-    moved = set(D.differing(start, a))
+    moved = set(O.differing(start, a))
     assert {"actor.w1", "critic.w1", "critic2.w1", "target_actor.w2", "target_critic.w2", "target_critic2.w2", "_blob_a", "_blob_c", "_blob_c2",
             "_blob_ta", "_blob_tc", "_blob_tc2", "adam_actor.m", "adam_critic.v", "adam_critic2.v", "stats", "step_stats_actor", "step_stats_critic",
             "draws", "noise_draws"} <= moved
-    assert ring is D.ring or {"leaves", "tree", "max_priority"} <= moved
-    T.blobs_are_packs(learner)
+    assert not prio or {"leaves", "tree", "max_priority"} <= moved
+    O.blobs_are_packs(learner)
     # the actor's step statistics of the updates without an actor step stay as they were; the joint step's norm is one number
     assert not learner.step_stats_actor[0].any() and float(learner.step_stats_actor[1, 0]) == 2.0
     assert float(learner.stats[1, 7]) > 0.0                                   # q_gap: the critics differ
@@ -78,7 +57,7 @@ def test_the_schedule_four_critic_steps_two_actor_steps_and_nothing_delayed_move
     hand = _hand(shape, updates=2, policy_delay=2)
     start = T.snapshot(hand)
     hand.update(stop_after=1)
-    moved = set(D.differing(start, T.snapshot(hand)))
+    moved = set(O.differing(start, T.snapshot(hand)))
     still = [k for k in start if k.startswith(("actor.", "target_", "adam_actor.")) or k in ("_blob_a", "_blob_ta", "_blob_tc", "_blob_tc2",
                                                                                            "step_actor", "step_stats_actor")]
     assert len(still) == 10 + 30 + 2 + 6 and not moved & set(still), sorted(moved & set(still))
@@ -87,50 +66,39 @@ def test_the_schedule_four_critic_steps_two_actor_steps_and_nothing_delayed_move
     # and the learner's own update 0 of a call of two leaves the same bits
     twin = _learner(shape, updates=2, policy_delay=2)
     twin._update(0)
-    assert D.differing(T.snapshot(twin), T.snapshot(hand)) == []
+    assert O.differing(T.snapshot(twin), T.snapshot(hand)) == []
 
 
-@pytest.mark.parametrize("ring", [D.ring, T.prio_ring], ids=["uniform", "prioritised"])
-def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(ring):
+@pytest.mark.parametrize("prio", [False, True], ids=["uniform", "prioritised"])
+def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(prio):
     shape = T.MAIN_SHAPES[0]
-    captured, eager = (_learner(shape, ring, updates=2, policy_delay=2) for _ in range(2))
-    start = T.snapshot(captured)
+    captured, eager = (_learner(shape, prio, updates=2, policy_delay=2) for _ in range(2))
     state = [t.detach().clone() for t in captured._state()]
-    assert captured.capture() is captured
-    assert D.differing(start, T.snapshot(captured)) == []                     # a capture runs nothing
+    O.capture_runs_nothing(captured, T.snapshot)
     assert all(torch.equal(a.view(torch.uint8), b.detach().view(torch.uint8)) for a, b in zip(state, captured._state()))
     assert any(t is captured._noise_draws for t in captured._state()) and len(state) == len(eager._state())
-    assert ring is D.ring or any(t is captured.buffer.tree for t in captured._state())
+    assert not prio or any(t is captured.buffer.tree for t in captured._state())
     draws, tds = [], []
-    for u in range(2):
-        captured.update()
-        eager.update()
+
+    def each(u):
         draws.append(captured.buffer.last_idx.clone())
         tds.append(captured.td.clone())
-        a, b = T.snapshot(captured), T.snapshot(eager)
-        assert D.differing(a, b) == [], (u, D.differing(a, b))
         assert torch.equal(captured.td.view(torch.int32), eager.td.view(torch.int32))
+    O.replays_the_eager_updates(captured, eager, T.snapshot, 2, each)
     assert not torch.equal(draws[0], draws[1]) and not torch.equal(tds[0], tds[1])
     assert int(captured.buffer._draws) == 4 == int(captured._noise_draws) and int(captured.step_critic) == 4 and int(captured.step_actor) == 2
-    T.blobs_are_packs(captured)
-    del a, b
-    torch.cuda.synchronize()
-    gc.collect()
-    held = torch.cuda.memory_allocated()
-    captured.update()
-    captured.update()
-    torch.cuda.synchronize()
-    assert torch.cuda.memory_allocated() == held
+    O.blobs_are_packs(captured)
+    O.allocates_nothing(captured)
 
 
 @pytest.mark.parametrize("shape", T.MAIN_SHAPES, ids=D.shape_id)
 def test_with_a_copy_of_the_critic_no_noise_and_no_delay_the_learner_is_ddpg_learner_bit_for_bit(shape):
     from deep_rl_battlespace_amd.learner import DDPGLearner
     kw = dict(KW, max_grad_norm=None)
-    (actor, critic, _), rows = _nets(shape)
-    td3 = _learner(shape, nets=(actor, critic, D.gpu_copy(critic)), updates=1, policy_delay=1, target_noise=0.0, max_grad_norm=None)
-    (actor, critic, _), _ = _nets(shape)
-    ddpg = DDPGLearner(D.ring(rows, shape[0]), actor, critic, critic_input=_central(shape), **kw)
+    (actor, critic, _), rows = T.SUITE.nets(shape)
+    td3 = _learner(shape, nets=(actor, critic, O.gpu_copy(critic)), updates=1, policy_delay=1, target_noise=0.0, max_grad_norm=None)
+    (actor, critic, _), _ = T.SUITE.nets(shape)
+    ddpg = DDPGLearner(O.ring(rows, shape[0]), actor, critic, critic_input=T.SUITE.central(shape), **kw)
     for _ in range(3):
         td3.update()
         ddpg.update()
@@ -145,22 +113,6 @@ def test_with_a_copy_of_the_critic_no_noise_and_no_delay_the_learner_is_ddpg_lea
     assert torch.equal(a["_blob_c2"], a["_blob_c"]) and torch.equal(a["_blob_tc2"], a["_blob_tc"]) and int(td3.step_actor) == 3
 
 
-def _set_targets(x, case):
-    """The case's three target networks into x's (a Hand), their blobs re-packed in place."""
-    with torch.no_grad():
-        for t, src, blob in ((x.target_actor, case.targets[0], x._blob_ta), (x.target_critic, case.targets[1], x._blob_tc),
-                             (x.target_critic2, case.targets[2], x._blob_tc2)):
-            for p in D.PARAMS:
-                getattr(t, p).copy_(getattr(src, p))
-            t.pack(out=blob)
-
-
-def _step_arrays(x, which):
-    net, state = getattr(x, which), getattr(x, "adam_" + which)
-    cut = lambda row: T.AU.row_to_tensors(row.detach().cpu().numpy(), net.n_actions)     # noqa: E731
-    return dict(p=T.AU.net_arrays(net), m=cut(state.m), v=cut(state.v), target=T.AU.net_arrays(getattr(x, "target_" + which)))
-
-
 @pytest.mark.parametrize("shape", T.MAIN_SHAPES, ids=D.shape_id)
 def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float64(shape):
     """One whole update through the primitives (Hand.step, policy_delay = 1, ddpg_util.STEP_KW, the smoothing's normals injected) from
@@ -169,42 +121,33 @@ def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float
     at the STEPPED critic 1, its step and target -- each row and each step pooled over its ten tensors, ddpg_util.check_step's bars --
     and the statistics (tests/test_td3_cpu.py: each misreading lies 1.8e5 yardstick errors
     away).  BSX_TD3_RATIOS_OUT names a file the measured ratios are appended to (profiles/td3_float64.json keeps them)."""
-    from deep_rl_battlespace_amd.learner import split_grad
     B, nA, Do, k, central = shape
     c = T.stepped_case(shape)
     assert c.share < D.U.KINK_CAP
     hand = _hand(shape, seed=c.seed, updates=1, policy_delay=1, **D.STEP_KW)
     for name, net in zip(("actor", "critic", "critic2"), c.nets):             # the case's networks are learner_case's and critic2_of's
         assert all(torch.equal(getattr(getattr(hand, name), p).cpu(), getattr(net, p)) for p in D.PARAMS), name
-    _set_targets(hand, c)
-    T.blobs_are_packs(hand)
-    s = hand.buffer.sample(c.idx)
-    dev_batch = (s[0].transpose(0, 1), s[2].transpose(0, 1), s[3], s[4].transpose(0, 1), s[6])
-    for got, want in zip(dev_batch, c.batch):
-        assert torch.equal(got.cpu(), want)
-    rows = hand.step(*dev_batch, 0, weight=c.w.cuda(), delayed=True, z=c.z.cuda())
+    O.set_targets(hand, dict(zip(("actor", "critic", "critic2"), c.targets)))
+    O.blobs_are_packs(hand)
+    rows = hand.step(*O.sample_is(hand, c.idx, c.batch), 0, weight=c.w.cuda(), delayed=True, z=c.z.cuda())
     torch.cuda.synchronize()
     sid, rec = D.shape_id(shape), {}
-    num = lambda row, na: {p: g.double().cpu().numpy() for p, g in zip(D.PARAMS, split_grad(row, na))}     # noqa: E731
     tens = lambda g: {which: [g[which][p] for p in D.PARAMS] for which in T.GRADS}            # noqa: E731
-    got = {which: num(row, na) for which, row, na in zip(T.GRADS, rows, (1, 1, k))}
+    got = {which: O.grad_arrays(row, na) for which, row, na in zip(T.GRADS, rows, (1, 1, k))}
     print("TD3", sid)
     D.check_step(tens(got), tens(c.ref), tens(c.yard), "row", rec, names=T.GRADS)             # each row pooled: check_step's bars
     for which in ("critic", "critic2", "actor"):
-        D.check_step(_step_arrays(hand, which), c.ref[which], c.yard[which], which, rec)
+        D.check_step(O.step_arrays(hand, which), c.ref[which], c.yard[which], which, rec)
     assert int(hand.step_critic) == 1 == int(hand.step_actor) and int(hand._noise_draws) == 0
     # ONE norm over both critics' rows, and the clip coefficient from it (adam_case_util.check_stats' bound)
     for stats, parts in ((hand.step_stats_critic, rows[:2]), (hand.step_stats_actor, rows[2:])):
         got, norm = stats[0].cpu().numpy(), float(sum(r.double().square().sum() for r in parts).sqrt())
         coef = min(1.0, float(np.float32(D.STEP_KW["max_grad_norm"])) / (norm + 1e-6))
         assert got[0] == 1 and abs(got[1] - norm) <= 1e-10 * norm and abs(got[2] - coef) <= 1e-10 * coef and coef < 1.0, (got, norm, coef)
-    bad = T.stats_out_of_bounds(hand.stats[0].cpu().numpy(), c.stats, c.e_stats, f"TD3 {sid}")
+    bad = T.HEAD.stats_out_of_bounds(hand.stats[0].cpu().numpy(), c.stats, c.e_stats, f"TD3 {sid}")
     assert not bad, bad
-    T.blobs_are_packs(hand)
-    path = os.environ.get("BSX_TD3_RATIOS_OUT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps({"shape": sid, "ratios": rec}) + "\n")
+    O.blobs_are_packs(hand)
+    O.append_ratios("BSX_TD3_RATIOS_OUT", sid, rec)
 
 
 def test_the_smoothing_reaches_the_target_on_running_rows_and_on_no_finished_one():
@@ -229,27 +172,12 @@ def test_the_smoothing_reaches_the_target_on_running_rows_and_on_no_finished_one
 
 
 def test_captured_updates_on_a_bandit_learn_at_least_half_of_what_the_torch_composition_learns():
-    """ddpg_util's bandit ring (every row finished), own critics, updates = 10 and policy_delay = 2, captured.  N and the torch
+    """offpolicy_util's bandit ring (every row finished), own critics, updates = 10 and policy_delay = 2, captured.  N and the torch
     composition's figures are recorded in profiles/td3_float64.json, chosen on the CPU with the torch composition of TD3 alone, which
     itself closes at least half of the gap from its initial reward to 0 in N updates (re-run here: a fraction of a second)."""
     from deep_rl_battlespace_amd.learner import TD3Learner
-    rec = json.load(open(T.PROFILE))["bandit"]
-    N, b = rec["N"], D.BANDIT
-    r0, r_torch = T.bandit_torch_run(N)
-    closed_torch = (r_torch - r0) / (0.0 - r0)
-    assert abs(r0 - rec["initial_reward"]) < 1e-6 and closed_torch >= 0.5
-    rows, held = D.bandit_rows()
-    actor, critic = D.bandit_nets()
-    learner = TD3Learner(D.ring(rows, b["B"]), D.gpu_copy(actor), D.gpu_copy(critic), D.gpu_copy(T.bandit_critic2()), critic_input="own",
-                         tau=b["tau"], lr_actor=b["lr"], lr_critic=b["lr"], updates=10, policy_delay=2).capture()
-    assert N % 10 == 0
-    for _ in range(N // 10):
-        learner.update()
-    with torch.no_grad():
-        before = float(D.bandit_reward(held, actor(held)).mean())
-        after = float(D.bandit_reward(held, learner.actor(held.cuda()).cpu()).mean())
-    closed = (after - before) / (0.0 - before)
-    print(f"bandit, N = {N}: reward {before:.4f} -> {after:.4f} (closed {closed:.3f} of the gap); torch composition of TD3 -> {r_torch:.4f} "
-          f"(closed {closed_torch:.3f}; recorded {rec['torch_closed']:.3f})")
-    assert abs(before - r0) < 1e-6 and int(learner.step_actor) == N // 2 and int(learner.step_critic) == N
-    assert closed >= 0.5 * closed_torch
+    b = O.BANDIT
+    make = lambda ring, *nets: TD3Learner(ring, *nets, critic_input="own", tau=b["tau"], lr_actor=b["lr"], lr_critic=b["lr"], updates=10,     # noqa: E731
+                                          policy_delay=2)
+    learner, N, _ = O.bandit_test(T.PROFILE, T.bandit_torch_run, make, O.bandit_nets(critic2="reseeded"), "torch composition of TD3")
+    assert int(learner.step_actor) == N // 2 and int(learner.step_critic) == N

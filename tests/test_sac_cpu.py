@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 import sac_util as S
 import td3_util as T
 
@@ -175,8 +176,8 @@ def test_the_bindings_and_the_learners_constructor_refuse_on_the_host():
 @pytest.mark.parametrize("BnA", sorted({s[:2] for s in D.SHAPES}), ids=lambda s: "B%d-nA%d" % s)
 def test_the_head_restatement_is_float64_autograd_of_l_critic(BnA, weight):
     inp = S.sac_inputs(*BnA)
-    ref, t64 = S.ref_sac_head(inp, weight=weight), S.torch_sac(inp, torch.float64, weight=weight)
-    for k in S.TD_NAMES:
+    ref, t64 = S.HEAD.ref(inp, weight=weight), S.HEAD.autograd(inp, torch.float64, weight=weight)
+    for k in S.HEAD.names:
         err = float(np.abs(ref[k] - t64[k]).max() / np.abs(t64[k]).max())
         assert err <= 1e-12, (k, err)
     assert ref["stats"][0] == t64["stats"][0] == inp["q1"].numel()
@@ -185,16 +186,16 @@ def test_the_head_restatement_is_float64_autograd_of_l_critic(BnA, weight):
     assert all(not ref[k][..., 1:].any() for k in ("g_q1", "g_q2"))
     # alpha = 0: td3_util's head; a finished row keeps a NaN logp_next out, a running row carries it
     zero = dict(inp, log_alpha=torch.full_like(inp["log_alpha"], -float("inf")))
-    two = T.ref_td3_head({k: v for k, v in inp.items() if k not in ("logp_next", "log_alpha")}, weight=weight)
-    assert all(np.array_equal(S.ref_sac_head(zero, weight=weight)[k], two[k]) for k in S.TD_NAMES + ("stats",))
+    two = T.HEAD.ref({k: v for k, v in inp.items() if k not in ("logp_next", "log_alpha")}, weight=weight)
+    assert all(np.array_equal(S.HEAD.ref(zero, weight=weight)[k], two[k]) for k in S.HEAD.names + ("stats",))
     over = inp["done"].numpy() != 0
     bad = dict(inp, logp_next=torch.where(inp["done"] != 0, torch.tensor(NAN), inp["logp_next"]))
-    assert all(np.array_equal(S.ref_sac_head(bad, weight=weight)[k], ref[k]) for k in S.TD_NAMES + ("stats",))
-    td = S.ref_sac_head(dict(inp, logp_next=torch.full_like(inp["logp_next"], NAN)), weight=weight)["td"]
+    assert all(np.array_equal(S.HEAD.ref(bad, weight=weight)[k], ref[k]) for k in S.HEAD.names + ("stats",))
+    td = S.HEAD.ref(dict(inp, logp_next=torch.full_like(inp["logp_next"], NAN)), weight=weight)["td"]
     assert np.isnan(td[~over]).all() and np.array_equal(td[over], ref["td"][over])
     # the float32 contract, operation by operation, is a float32 evaluation of the same head
     c32 = S.contract32(inp, weight=weight)
-    assert all(np.abs(c32[k] - ref[k]).max() <= 1e-5 * max(1.0, np.abs(ref[k]).max()) for k in S.TD_NAMES)
+    assert all(np.abs(c32[k] - ref[k]).max() <= 1e-5 * max(1.0, np.abs(ref[k]).max()) for k in S.HEAD.names)
 
 
 @pytest.mark.parametrize("shape", ((33, 2, 8, 3, 1), (17, 1, 5, 3, 0), (9, 3, 11, 3, 1)), ids=D.shape_id)
@@ -273,7 +274,7 @@ def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_
     r = rec["cases"][D.shape_id(shape)]
     c = S.stepped_case(shape)
     print(D.shape_id(shape), f"seed {c.seed}: left out {100 * c.share:.2f} % after {c.rounds} zeroing rounds")
-    assert c.share < D.U.KINK_CAP and c.rounds <= D.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
+    assert c.share < D.U.KINK_CAP and c.rounds <= O.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
     s1, s2 = c.ref["critic"]["net"], c.ref["critic2"]["net"]
     x_cur = D.joined(c.batch[0].double(), c.batch[1].double(), central).contiguous()
     near = D.U.near_kink((s1, c.ref["x_pi"]), (s2, c.ref["x_pi"]), (c.nets[1], x_cur), (c.nets[2], x_cur), (c.nets[0], c.batch[0]))
@@ -298,13 +299,13 @@ def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_
 
 def test_the_profile_s_factors_are_the_rule_on_its_recorded_spread_and_the_bandit_s_n_is_the_compositions():
     rec = json.load(open(S.PROFILE))
-    assert rec["factors"] == S.Y.exceptions_from(rec["head_spread"]) and set(rec["factors"]) <= {S.head_id(1, 1, True), S.head_id(1, 1, False)}
-    assert set(rec["head_spread"]) == {S.head_id(B, nA, w) for B, nA in S.HEAD_SHAPES for w in (True, False)}
+    assert rec["factors"] == S.Y.exceptions_from(rec["head_spread"]) and set(rec["factors"]) <= {O.head_id(1, 1, True), O.head_id(1, 1, False)}
+    assert set(rec["head_spread"]) == {O.head_id(B, nA, w) for B, nA in S.HEAD_SHAPES for w in (True, False)}
     for B, nA in S.HEAD_SHAPES[:-1]:
         for w in (True, False):
-            got = {k: [round(float(x), 4) for x in v] for k, v in S.head_spread(B, nA, w).items()}
-            assert got == rec["head_spread"][S.head_id(B, nA, w)], (B, nA, w)
-    assert S.factors(161, 2, True)("g_q2") == S.Y.FACTORS
+            got = {k: [round(float(x), 4) for x in v] for k, v in S.HEAD.spread(B, nA, w).items()}
+            assert got == rec["head_spread"][O.head_id(B, nA, w)], (B, nA, w)
+    assert S.HEAD.factors(161, 2, True)("g_q2") == S.Y.FACTORS
     st = rec["stepped"]
     assert set(st["cases"]) == set(st["sharpness"]) == {D.shape_id(s) for s in S.MAIN_SHAPES}
     assert st["factors"] == S.Y.exceptions_from(st["spread"]) and set(st["spread"]) == set(st["cases"])

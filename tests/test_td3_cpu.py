@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import ddpg_util as D
+import offpolicy_util as O
 import td3_util as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,8 +123,8 @@ def test_the_bindings_and_the_learners_constructor_refuse_on_the_host():
 @pytest.mark.parametrize("BnA", sorted({s[:2] for s in D.SHAPES}), ids=lambda s: "B%d-nA%d" % s)
 def test_the_head_restatement_is_float64_autograd_of_the_two_critic_losses_and_of_minus_mean_w_q1(BnA, weight):
     inp = T.td3_inputs(*BnA)
-    ref, t64 = T.ref_td3_head(inp, weight=weight), T.torch_td3(inp, torch.float64, weight=weight)
-    for k in T.TD_NAMES:
+    ref, t64 = T.HEAD.ref(inp, weight=weight), T.HEAD.autograd(inp, torch.float64, weight=weight)
+    for k in T.HEAD.names:
         err = float(np.abs(ref[k] - t64[k]).max() / np.abs(t64[k]).max())
         assert err <= 1e-12, (k, err)
     assert ref["stats"][0] == t64["stats"][0] == inp["q1"].numel()
@@ -132,17 +133,17 @@ def test_the_head_restatement_is_float64_autograd_of_the_two_critic_losses_and_o
     assert all(not ref[k][..., 1:].any() for k in ("g_q1", "g_q2", "g_pi"))
     # with the second critic a copy of the first the head is ddpg_util's, and q_gap is 0
     same = dict(inp, q2=inp["q1"], q2_next=inp["q1_next"])
-    one = D.ref_td_head(dict(q=inp["q1"], q_next=inp["q1_next"], rew=inp["rew"], done=inp["done"], weight=inp["weight"]), weight=weight)
-    two = T.ref_td3_head(same, weight=weight)
+    one = D.HEAD.ref(dict(q=inp["q1"], q_next=inp["q1_next"], rew=inp["rew"], done=inp["done"], weight=inp["weight"]), weight=weight)
+    two = T.HEAD.ref(same, weight=weight)
     assert all(np.array_equal(two[a], one[b]) for a, b in (("g_q1", "g_q"), ("g_q2", "g_q"), ("g_pi", "g_pi"), ("td", "td")))
     assert two["stats"][7] == 0.0 and np.allclose(two["stats"][1], 2 * one["stats"][1], rtol=1e-12) and np.array_equal(two["stats"][2:7], one["stats"][2:7])
     # a finished row keeps both q_next out, NaN included; on a running row a NaN in either alone reaches td
     over = inp["done"].numpy() != 0
     nan = torch.tensor(NAN)
     bad = dict(inp, q1_next=torch.where(inp["done"] != 0, nan, inp["q1_next"]), q2_next=torch.where(inp["done"] != 0, nan, inp["q2_next"]))
-    assert all(np.array_equal(T.ref_td3_head(bad, weight=weight)[k], ref[k]) for k in T.TD_NAMES + ("stats",))
+    assert all(np.array_equal(T.HEAD.ref(bad, weight=weight)[k], ref[k]) for k in T.HEAD.names + ("stats",))
     for which in ("q1_next", "q2_next"):
-        td = T.ref_td3_head(dict(inp, **{which: torch.full_like(inp[which], NAN)}), weight=weight)["td"]
+        td = T.HEAD.ref(dict(inp, **{which: torch.full_like(inp[which], NAN)}), weight=weight)["td"]
         assert np.isnan(td[~over]).all() and np.array_equal(td[over], ref["td"][over])
 
 
@@ -178,7 +179,7 @@ def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_
     B, nA, Do, k, central = shape
     c = T.stepped_case(shape)
     print(D.shape_id(shape), f"seed {c.seed}: left out {100 * c.share:.2f} % after {c.rounds} zeroing rounds")
-    assert c.share < D.U.KINK_CAP and c.rounds <= D.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
+    assert c.share < D.U.KINK_CAP and c.rounds <= O.MAX_ROUNDS and float((c.w == 0).double().mean()) == c.share
     obs, act, _, obs_next, _ = c.batch
     x_cur, _, x_pi = D.joins64(c.nets[0], obs, obs_next, act, central)
     stepped = c.ref["critic"]["net"]
@@ -202,16 +203,16 @@ def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_
 
 def test_the_profile_s_factors_are_the_rule_on_its_recorded_spread_and_the_bandit_s_n_is_the_compositions():
     """profiles/td3_float64.json: the head's factor exceptions are yardstick_util.factor_rule of the recorded spread of the yardstick
-    itself and nothing else, the spread is what td3_util.head_spread gives (re-run here at the shapes that cost nothing), and only the
+    itself and nothing else, the spread is what td3_util.HEAD.spread gives (re-run here at the shapes that cost nothing), and only the
     one-element shape has an exception; every recorded kernel ratio of the whole update lies within the bars."""
     rec = json.load(open(T.PROFILE))
-    assert rec["factors"] == T.Y.exceptions_from(rec["head_spread"]) and set(rec["factors"]) <= {T.head_id(1, 1, True), T.head_id(1, 1, False)}
-    assert set(rec["head_spread"]) == {T.head_id(B, nA, w) for B, nA in T.HEAD_SHAPES for w in (True, False)}
+    assert rec["factors"] == T.Y.exceptions_from(rec["head_spread"]) and set(rec["factors"]) <= {O.head_id(1, 1, True), O.head_id(1, 1, False)}
+    assert set(rec["head_spread"]) == {O.head_id(B, nA, w) for B, nA in T.HEAD_SHAPES for w in (True, False)}
     for B, nA in T.HEAD_SHAPES[:-1]:
         for w in (True, False):
-            got = {k: [round(float(x), 4) for x in v] for k, v in T.head_spread(B, nA, w).items()}
-            assert got == rec["head_spread"][T.head_id(B, nA, w)], (B, nA, w)
-    assert T.factors(161, 2, True)("g_q2") == T.Y.FACTORS and T.factors(1, 1, True)("g_q1") == T.Y.FACTORS
+            got = {k: [round(float(x), 4) for x in v] for k, v in T.HEAD.spread(B, nA, w).items()}
+            assert got == rec["head_spread"][O.head_id(B, nA, w)], (B, nA, w)
+    assert T.HEAD.factors(161, 2, True)("g_q2") == T.Y.FACTORS and T.HEAD.factors(1, 1, True)("g_q1") == T.Y.FACTORS
     st = rec["stepped"]
     assert set(st["cases"]) == set(st["sharpness"]) == {D.shape_id(s) for s in T.MAIN_SHAPES}
     for shape in T.MAIN_SHAPES:
@@ -219,4 +220,4 @@ def test_the_profile_s_factors_are_the_rule_on_its_recorded_spread_and_the_bandi
             assert mean <= T.Y.FACTORS[0] and mx <= T.Y.FACTORS[1], (shape, name)
     b = rec["bandit"]
     assert b["N"] % 10 == 0 and b["policy_delay"] == 2 and b["torch_closed"] >= 0.5
-    assert {k: b[k] for k in D.BANDIT} == D.BANDIT
+    assert {k: b[k] for k in O.BANDIT} == O.BANDIT
