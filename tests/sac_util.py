@@ -42,6 +42,13 @@ GRAD_SHAPES = tuple(dict.fromkeys((B, nA, Do, 3, c) for B, nA, Do, _, _ in D.SHA
                                   if D.width(nA, Do, 3, c) <= 64)) + ((16385, 16, 1, 3, 0),)
 HAND_SHAPES = ((161, 2, 8, 3, 1), (97, 1, 5, 3, 0), (129, 3, 11, 3, 1), (1, 1, 5, 3, 1))
 MAIN_SHAPES = HAND_SHAPES[:2]
+# td3_util.TEAM_SHAPES at k = 3: with own critics and nA > 1 every agent index of the composition -- both draws' key b nA + j, own_only's
+# slot, log_alpha[i], log_std[3 i ..], the joint step over 2 nA stacked networks -- is not 0
+TEAM_SHAPES = tuple((B, nA, Do, 3, c) for B, nA, Do, _, c in T.TEAM_SHAPES)
+AGENTS_SHAPE = TEAM_SHAPES[1]                                       # 4v4 own: the prioritised, the captured and the per-agent cases
+# the whole update against float64.  16 agents at B = 33 (528 elements: three head tiles and three policy tiles): at B = 130 the kink
+# filter closed at no seed in 0 .. 23 (two stepped critics and the |q1_pi - q2_pi| rule over 2080 elements)
+STEP_SHAPES = MAIN_SHAPES + ((64, 2, 5, 3, 0), (65, 4, 14, 3, 0), (96, 2, 8, 3, 1), (33, 16, 50, 3, 0))
 PI_STAT_NAMES = ("actor_loss", "q_pi", "logp", "alpha", "weight", "picked_1")       # stats_pi[1..6]
 # stepped_case's seed per shape: the first from 0 at which, on the float64 reference alone, the kink filter closes within
 # offpolicy_util.MAX_ROUNDS zeroing rounds and leaves out less than actor_grad_util.KINK_CAP.  profiles/sac_float64.json records what every
@@ -474,11 +481,19 @@ def stepped_factor_of(shape):
     return Y.factor_of(Y.recorded(PROFILE, "stepped", "factors").get(D.shape_id(shape), {}))
 
 
+ROLLED = dict(log_alpha="gc1", z_next="gc1", log_std="ga", z_pi="ga")        # what a misread agent index is judged on
+
+
 def wrong_variants(case, central):
-    """{name: (|wrong - right| mean per tensor, the yardstick's mean error per tensor)} in float64: the four misreadings of the issue."""
+    """{name: (|wrong - right| mean per tensor, the yardstick's mean error per tensor)} in float64: the four misreadings of the update and,
+    with more than one agent, the four of the agent index (ROLLED: agent j reads what belongs to agent j - 1)."""
     c = case
     g = torch.Generator().manual_seed(77)
-    f = lambda **v: update_reference(c.nets, c.targets, c.log_std, c.log_alpha, c.batch, c.w, c.z_next, c.z_pi, central, torch.float64, **v)     # noqa: E731
+    given = {k: getattr(c, k) for k in ("log_std", "log_alpha", "z_next", "z_pi")}
+
+    def f(rolled=None, **v):
+        t = dict(given, **({rolled: given[rolled].roll(1, 0 if rolled.startswith("log_") else 1)} if rolled else {}))
+        return update_reference(c.nets, c.targets, t["log_std"], t["log_alpha"], c.batch, c.w, t["z_next"], t["z_pi"], central, torch.float64, **v)
     out = {}
     for name, variant, which in (("the entropy term left out of y", dict(entropy=False), "gc1"),
                                  ("next actions from a perturbed copy of the actor", dict(next_actor=D.perturbed(c.nets[0], g)), "gc1"),
@@ -486,6 +501,8 @@ def wrong_variants(case, central):
         out[name] = O.distances(f(**variant)[which], c.ref[which], c.yard[which], D.SHARP)
     ls = lambda r: {"log_std": r["g_ls"]}                         # noqa: E731
     out["g_log_std without its -alpha term"] = O.distances(ls(f(ls_alpha=False)), ls(c.ref), ls(c.yard), ("log_std",))
+    for name, which in ROLLED.items() if c.log_alpha.numel() > 1 else ():
+        out[f"{name} rolled by one agent"] = O.distances(f(name)[which], c.ref[which], c.yard[which], D.SHARP)
     return out
 
 

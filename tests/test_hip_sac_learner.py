@@ -1,7 +1,7 @@
 """SACLearner on the MI355X: an update is, bit for bit, the sequence of the public primitives written out by hand (tests/sac_util.py:
-Hand), on a plain and on a prioritised ring; a captured update runs nothing, replays the eager updates with fresh draws and fresh noise
+Hand), on a plain and on a prioritised ring, own-critic teams of 2, 4 and 16 agents included; a captured update runs nothing, replays the eager updates with fresh draws and fresh noise
 and allocates nothing; with lr_alpha=None the temperature never moves; a whole update from target critics that are not the critics
-against float64; one iteration of the documented loop on a real continuous 1v1 env with a Gaussian rollout; and a bandit on which the
+against float64; with own critics one agent's temperature and spread reach that agent's target and gradients and no other's; one iteration of the documented loop on a real continuous 1v1 env with a Gaussian rollout; and a bandit on which the
 captured updates must learn at least half of what the torch composition of the same SAC learns."""
 import math
 
@@ -19,8 +19,10 @@ KW = D.KW
 
 
 _learner, _hand = S.SUITE.learner, S.SUITE.hand
+NO_CLIP = dict(D.STEP_KW, max_grad_norm=None)
 
 HAND_CASES = [(s, False) for s in S.HAND_SHAPES] + [(s, True) for s in S.HAND_SHAPES[:2]]
+HAND_CASES += [(s, False) for s in S.TEAM_SHAPES] + [(S.AGENTS_SHAPE, True)]       # (own-critic teams; one of them prioritised)
 
 
 @pytest.mark.parametrize("shape,prio", HAND_CASES, ids=[D.shape_id(s) + ("-prioritised" if prio else "") for s, prio in HAND_CASES])
@@ -52,9 +54,9 @@ def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(
     assert (np.abs(np.log(pi[:, 4] / 0.2)) <= 4 * 1.5 * 3e-4).all() and float(learner.stats[1, 7]) > 0.0
 
 
-@pytest.mark.parametrize("prio", [False, True], ids=["uniform", "prioritised"])
-def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(prio):
-    shape = S.MAIN_SHAPES[0]
+@pytest.mark.parametrize("prio,shape", [(False, S.MAIN_SHAPES[0]), (True, S.MAIN_SHAPES[0]), (False, S.AGENTS_SHAPE)],
+                         ids=["uniform", "prioritised", "uniform-" + D.shape_id(S.AGENTS_SHAPE)])
+def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(prio, shape):
     captured, eager = (_learner(shape, prio, updates=2) for _ in range(2))
     state = [t.detach().clone() for t in captured._state()]
     O.capture_runs_nothing(captured, S.snapshot)
@@ -102,7 +104,7 @@ def test_with_lr_alpha_none_the_temperature_never_moves_and_set_lr_reaches_the_c
     assert x.log_std is own and bool((own != -0.5).all())
 
 
-@pytest.mark.parametrize("shape", S.MAIN_SHAPES, ids=D.shape_id)
+@pytest.mark.parametrize("shape", S.STEP_SHAPES, ids=D.shape_id)
 def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float64(shape):
     """One whole update through the primitives (Hand.step, ddpg_util.STEP_KW, both draws' normals injected, random log_std and
     log_alpha) from target critics that are NOT the critics, against sac_util.stepped_case's float64 reference with the same computation
@@ -148,6 +150,36 @@ def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float
     assert not bad, bad
     O.blobs_are_packs(hand)
     O.append_ratios("BSX_SAC_RATIOS_OUT", sid, rec)
+
+
+@pytest.mark.parametrize("which", ["log_alpha", "log_std"])
+def test_every_agent_s_own_temperature_and_spread_reach_its_own_update_and_no_other_agent_s(which):
+    """4v4 with own critics, the same ring, networks, seed and so the same batch and the same Philox normals, no clipping (a clip norm is
+    one number over all agents) and ddpg_util.STEP_KW's eps (at 1e-8 Adam's first step is lr sign(g): a stepped critic would hardly see its
+    gradient move): with log_alpha[2], or log_std[2], alone changed, agent 2's column of td and its rows of critic 1's and
+    of the actor's gradient (through both stepped critics) differ, and those of agents 0, 1 and 3 keep their bits: own critics share
+    nothing between agents.  The device-side twin of test_sac_cpu.py's agent-index misreadings."""
+    shape, j = S.AGENTS_SHAPE, 2
+    nA = shape[1]
+    g = torch.Generator().manual_seed(32)
+    log_std, log_alpha = -1.0 + 0.3 * torch.randn((nA, 3), generator=g), math.log(0.2) + 0.3 * torch.randn((nA,), generator=g)
+    runs = []
+    for changed in (False, True):
+        ls, la = log_std.clone(), log_alpha.clone()
+        if changed:
+            (la if which == "log_alpha" else ls)[j] += 0.5
+        hand = _hand(shape, updates=1, log_std=ls.cuda(), **NO_CLIP)
+        hand.log_alpha.copy_(la)
+        out = hand.step(*O.batch_of(hand.buffer.sample()), 0)
+        torch.cuda.synchronize()
+        runs.append(dict(idx=hand.buffer.last_idx.clone(), td=hand.td.t().contiguous(), gc1=out["row_c"], ga=out["row_a"]))
+        assert int(hand._noise_draws) == 2
+    a, b = runs
+    assert torch.equal(a["idx"], b["idx"])
+    same = lambda x, y: torch.equal(x.view(torch.int32), y.view(torch.int32))                   # noqa: E731
+    for name in ("td", "gc1", "ga"):                                                            # each [nA, .]: one row per agent
+        assert a[name].shape[0] == nA and bool(torch.isfinite(a[name]).all())
+        assert [same(a[name][i], b[name][i]) for i in range(nA)] == [i != j for i in range(nA)], (which, name)
 
 
 def test_one_iteration_of_the_documented_loop_on_a_continuous_1v1_env_with_a_gaussian_rollout():

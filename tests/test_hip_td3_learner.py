@@ -1,8 +1,8 @@
 """TD3Learner on the MI355X: an update is, bit for bit, the sequence of the public primitives written out by hand (tests/td3_util.py:
-Hand), on a plain and on a prioritised ring; the delayed schedule; a captured update runs nothing, replays the eager updates with
+Hand), on a plain and on a prioritised ring, own-critic teams of 2, 4 and 16 agents included; the delayed schedule; a captured update runs nothing, replays the eager updates with
 fresh draws and fresh noise and allocates nothing; with a copy of the critic as the second one, no noise and no delay it is
 DDPGLearner bit for bit; a whole update from target networks that are not the networks against float64; the smoothing reaches the
-target on running rows alone; and a bandit on which the captured updates must learn at least half of what the torch composition learns."""
+target on running rows alone; with own critics one agent's noise reaches that agent's target and gradients and no other's; and a bandit on which the captured updates must learn at least half of what the torch composition learns."""
 import numpy as np
 import pytest
 import torch
@@ -19,6 +19,7 @@ KW = D.KW
 _learner, _hand = T.SUITE.learner, T.SUITE.hand
 
 HAND_CASES = [(s, False) for s in T.HAND_SHAPES] + [(T.HAND_SHAPES[0], True)]      # (one case on a prioritised ring)
+HAND_CASES += [(s, False) for s in T.TEAM_SHAPES] + [(T.AGENTS_SHAPE, True)]       # (own-critic teams, k = 3 with a team; one prioritised)
 
 
 @pytest.mark.parametrize("shape,prio", HAND_CASES, ids=[D.shape_id(s) + ("-prioritised" if prio else "") for s, prio in HAND_CASES])
@@ -69,9 +70,9 @@ def test_the_schedule_four_critic_steps_two_actor_steps_and_nothing_delayed_move
     assert O.differing(T.snapshot(twin), T.snapshot(hand)) == []
 
 
-@pytest.mark.parametrize("prio", [False, True], ids=["uniform", "prioritised"])
-def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(prio):
-    shape = T.MAIN_SHAPES[0]
+@pytest.mark.parametrize("prio,shape", [(False, T.MAIN_SHAPES[0]), (True, T.MAIN_SHAPES[0]), (False, T.AGENTS_SHAPE)],
+                         ids=["uniform", "prioritised", "uniform-" + D.shape_id(T.AGENTS_SHAPE)])
+def test_a_captured_update_runs_nothing_replays_the_eager_updates_with_fresh_draws_and_noise_and_allocates_nothing(prio, shape):
     captured, eager = (_learner(shape, prio, updates=2, policy_delay=2) for _ in range(2))
     state = [t.detach().clone() for t in captured._state()]
     O.capture_runs_nothing(captured, T.snapshot)
@@ -113,14 +114,14 @@ def test_with_a_copy_of_the_critic_no_noise_and_no_delay_the_learner_is_ddpg_lea
     assert torch.equal(a["_blob_c2"], a["_blob_c"]) and torch.equal(a["_blob_tc2"], a["_blob_tc"]) and int(td3.step_actor) == 3
 
 
-@pytest.mark.parametrize("shape", T.MAIN_SHAPES, ids=D.shape_id)
+@pytest.mark.parametrize("shape", T.STEP_SHAPES, ids=D.shape_id)
 def test_a_whole_update_with_distinct_targets_and_distinct_critics_against_float64(shape):
     """One whole update through the primitives (Hand.step, policy_delay = 1, ddpg_util.STEP_KW, the smoothing's normals injected) from
     target networks that are NOT the networks, against td3_util.stepped_case's float64 reference with the same computation in float32
     on the CPU as the yardstick: both critics' gradient rows at the shared y, the joint step and both Polyak targets, the actor's row
     at the STEPPED critic 1, its step and target -- each row and each step pooled over its ten tensors, ddpg_util.check_step's bars --
-    and the statistics (tests/test_td3_cpu.py: each misreading lies 1.8e5 yardstick errors
-    away).  BSX_TD3_RATIOS_OUT names a file the measured ratios are appended to (profiles/td3_float64.json keeps them)."""
+    and the statistics (tests/test_td3_cpu.py: each misreading, those of the agent index included, lies
+    1.8e5 yardstick errors away).  BSX_TD3_RATIOS_OUT names a file the measured ratios are appended to (profiles/td3_float64.json keeps them)."""
     B, nA, Do, k, central = shape
     c = T.stepped_case(shape)
     assert c.share < D.U.KINK_CAP
@@ -169,6 +170,34 @@ def test_the_smoothing_reaches_the_target_on_running_rows_and_on_no_finished_one
             assert float((noisy._x_next - plain._x_next).abs().max()) <= T.CLIP + 1e-6
         else:
             assert torch.equal(noisy.td.view(torch.int32), noisy.buffer._b_rew.view(torch.int32)) and float(noisy.stats[0, 5]) == 1.0
+
+
+def test_every_agent_s_own_noise_reaches_its_own_target_and_gradients_and_no_other_agent_s():
+    """4v4 with own critics, the same ring, networks and batch, no clipping (a clip norm is one number over all agents) and
+    ddpg_util.STEP_KW's eps (at 1e-8 Adam's first step is lr sign(g): the stepped critic would hardly see its gradient move): with the
+    injected normals of agent 2 alone replaced, agent 2's column of td and its rows of critic 1's and of the actor's gradient (through the
+    stepped critic 1) differ, and those of agents 0, 1 and 3 keep their bits: own critics share nothing between agents.  The device-side
+    twin of test_td3_cpu.py's agent-index misreading."""
+    shape, j = T.AGENTS_SHAPE, 2
+    B, nA = shape[:2]
+    g = torch.Generator().manual_seed(31)
+    z = torch.randn((B, nA, 4), generator=g)
+    other = z.clone()
+    other[:, j] = torch.randn((B, 4), generator=g)
+    runs = []
+    for noise in (z, other):
+        hand = _hand(shape, updates=1, policy_delay=1, **dict(D.STEP_KW, max_grad_norm=None))
+        batch = O.batch_of(hand.buffer.sample())
+        rows = hand.step(*batch, 0, delayed=True, z=noise.cuda())
+        torch.cuda.synchronize()
+        runs.append(dict(idx=hand.buffer.last_idx.clone(), td=hand.td.t().contiguous(), gc1=rows[0], ga=rows[2]))
+    a, b = runs
+    assert torch.equal(a["idx"], b["idx"])
+    same = lambda x, y: torch.equal(x.view(torch.int32), y.view(torch.int32))                   # noqa: E731
+    for name in ("td", "gc1", "ga"):                                                            # each [nA, .]: one row per agent
+        assert a[name].shape[0] == nA and bool(torch.isfinite(a[name]).all())
+        assert [same(a[name][i], b[name][i]) for i in range(nA)] == [i != j for i in range(nA)], name
+    assert float((a["td"][j] != b["td"][j]).float().mean()) > 0.5                               # (running rows: about 0.8 of them)
 
 
 def test_captured_updates_on_a_bandit_learn_at_least_half_of_what_the_torch_composition_learns():

@@ -263,12 +263,14 @@ def test_the_draws_restatement_is_the_rollouts_expression_joined_as_ddpg_util_jo
     assert np.array_equal(a0, y4[..., :3])                                                # sigma = 0: the mean itself
 
 
-@pytest.mark.parametrize("shape", S.MAIN_SHAPES, ids=D.shape_id)
+@pytest.mark.parametrize("shape", S.STEP_SHAPES, ids=D.shape_id)
 def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_misreading_lies_far(shape):
     """sac_util.stepped_case's row weights are 0 where, in float64, any of these lies within KINK of 0: a pre-ReLU value of either critic
     at x_cur, of the actor at obs, of either STEPPED critic at x_pi, or |q1_pi - q2_pi|.  Under the cap, closed within MAX_ROUNDS
     (conditions on the float64 reference: the seed is the first from 0 that meets them, profiles/sac_float64.json records every seed
-    tried), and each of the four misreadings lies at least 1000 yardstick mean errors from the reference."""
+    tried), and each of the four misreadings lies at least 1000 yardstick mean errors from the reference.  With more than one agent so
+    does each misreading of the agent index -- log_alpha, z_next (on critic 1's gradient), log_std, z_pi (on the actor's) rolled by one
+    agent (measured: 1.2e4 and more) --, which is why the case's log_std rows and log_alpha values differ from agent to agent."""
     B, nA, Do, k, central = shape
     rec = json.load(open(S.PROFILE))["stepped"]
     r = rec["cases"][D.shape_id(shape)]
@@ -284,12 +286,16 @@ def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_
     assert not bool(c.batch[4].all()) and not torch.equal(c.targets[0].w1, c.nets[1].w1) and not torch.equal(c.nets[1].w1, c.nets[2].w1)
     picked = float((c.ref["pi"]["q1_pi"] < c.ref["pi"]["q2_pi"]).double().mean())
     assert 0.05 < picked < 0.95 and c.stats_pi[6] == picked                             # both critics are the smaller one somewhere
-    for name, (dist, yard) in S.wrong_variants(c, central).items():
+    assert len({tuple(row) for row in c.log_std.tolist()}) == nA == len(set(c.log_alpha.tolist()))      # per agent, distinct
+    variants = S.wrong_variants(c, central)
+    assert len(variants) == 4 + (4 if nA > 1 else 0) and all((f"{k_} rolled by one agent" in variants) == (nA > 1) for k_ in S.ROLLED)
+    for name, (dist, yard) in variants.items():
         ratios = {p: dist[p] / yard[p] for p in dist}
         print(D.shape_id(shape), name, "smallest ratio %.3g" % min(ratios.values()))
         assert all(yard[p] > 0.0 for p in dist) and min(ratios.values()) >= 1000.0, (name, ratios)
     assert r["seed"] == c.seed == S.STEP_SEEDS.get(shape, 0) and r["zeroing_rounds"] == c.rounds and r["shape"] == list(shape)
     assert abs(r["left_out_percent"] - 100 * c.share) <= 0.005 + 1e-9 and min(rec["sharpness"][D.shape_id(shape)].values()) >= 1000
+    assert set(rec["sharpness"][D.shape_id(shape)]) == set(variants)
     tried = r["seeds_tried"]
     assert [t[0] for t in tried] == list(range(c.seed + 1)) and all(not (t[1] and t[2] < 100 * D.U.KINK_CAP) for t in tried[:-1]) and tried[-1][1]
     for seed in (0, c.seed // 2):                                                        # two of the recorded seeds, re-run
@@ -307,9 +313,10 @@ def test_the_profile_s_factors_are_the_rule_on_its_recorded_spread_and_the_bandi
             assert got == rec["head_spread"][O.head_id(B, nA, w)], (B, nA, w)
     assert S.HEAD.factors(161, 2, True)("g_q2") == S.Y.FACTORS
     st = rec["stepped"]
-    assert set(st["cases"]) == set(st["sharpness"]) == {D.shape_id(s) for s in S.MAIN_SHAPES}
+    assert set(st["cases"]) == set(st["sharpness"]) == {D.shape_id(s) for s in S.STEP_SHAPES} and set(st["kernel"]) <= set(st["cases"])
+    assert S.STEP_SHAPES[:2] == S.MAIN_SHAPES and set(S.STEP_SHAPES[2:5]) < set(S.TEAM_SHAPES) and S.STEP_SHAPES[5][1:] == S.TEAM_SHAPES[2][1:]
     assert st["factors"] == S.Y.exceptions_from(st["spread"]) and set(st["spread"]) == set(st["cases"])
-    for shape in S.MAIN_SHAPES:
+    for shape in S.STEP_SHAPES:
         sid = D.shape_id(shape)
         assert {k: [round(float(x), 4) for x in v] for k, v in S.stepped_spread(shape).items()} == st["spread"][sid], sid
         for name, (mean, mx) in st["kernel"].get(sid, {}).items():

@@ -169,13 +169,14 @@ def test_the_smoothing_restatement_is_torch_clamp_joined_as_ddpg_util_joins(shap
     assert np.abs(T.smoothed(y4.astype(np.float64), z.astype(np.float64), 0.2, 0.5) - T.smoothed(y4, z, 0.2, 0.5)).max() < 1e-6
 
 
-@pytest.mark.parametrize("shape", T.MAIN_SHAPES, ids=D.shape_id)
+@pytest.mark.parametrize("shape", T.STEP_SHAPES, ids=D.shape_id)
 def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_misreading_lies_far(shape):
     """td3_util.stepped_case's row weights are 0 where, in float64, a pre-ReLU value lies within KINK of 0: of either critic at x_cur, of
     the actor at obs, of the STEPPED critic 1 at x_pi (iterated: zeroing a row moves the step).  Under the cap, closed within
     MAX_ROUNDS (conditions on the float64 reference: td3_util.STEP_SEEDS), and each misreading -- y from target critic 1 alone, the
     noise left out, the actor's gradient through critic 2 -- lies at least 1000 yardstick mean errors from the reference in each of
-    w1, w2, w3, b3 (measured: 1.8e5 and more).  profiles/td3_float64.json records all of it."""
+    w1, w2, w3, b3 (measured: 1.8e5 and more).  With more than one agent the agent-index misreading is judged the same way: agent j
+    smoothed with the normals of agent j - 1 (measured: 2.0e5 and more).  profiles/td3_float64.json records all of it."""
     B, nA, Do, k, central = shape
     c = T.stepped_case(shape)
     print(D.shape_id(shape), f"seed {c.seed}: left out {100 * c.share:.2f} % after {c.rounds} zeroing rounds")
@@ -191,7 +192,9 @@ def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_
     n1 = np.sqrt(sum(float((g ** 2).sum()) for which in ("gc1", "gc2") for g in c.ref[which].values()))
     assert abs(n1 - c.ref["critic"]["norm"]) <= 1e-6 * n1 and c.ref["actor"]["coef"] < 1.0                  # (hyper32 rounds max_grad_norm)
     assert not bool(c.batch[4].all()) and not torch.equal(c.targets[1].w1, c.nets[1].w1) and not torch.equal(c.nets[1].w1, c.nets[2].w1)
-    for name, (dist, yard) in T.wrong_variants(c, central).items():
+    variants = T.wrong_variants(c, central)
+    assert (T.ROLLED in variants) == (nA > 1) and len(variants) == 3 + (nA > 1)
+    for name, (dist, yard) in variants.items():
         ratios = {p: dist[p] / yard[p] for p in D.SHARP}
         print(D.shape_id(shape), name, "smallest ratio %.3g" % min(ratios.values()))
         assert all(yard[p] > 0.0 for p in D.SHARP) and min(ratios.values()) >= 1000.0, (name, ratios)
@@ -199,6 +202,7 @@ def test_the_whole_update_case_stays_under_the_cap_at_its_fixed_point_and_every_
     r = rec["cases"][D.shape_id(shape)]
     assert r["seed"] == c.seed == T.STEP_SEEDS.get(shape, 0) and r["zeroing_rounds"] == c.rounds
     assert abs(r["left_out_percent"] - 100 * c.share) <= 0.005 + 1e-9 and min(rec["sharpness"][D.shape_id(shape)].values()) >= 1000
+    assert set(rec["sharpness"][D.shape_id(shape)]) == set(variants)
 
 
 def test_the_profile_s_factors_are_the_rule_on_its_recorded_spread_and_the_bandit_s_n_is_the_compositions():
@@ -214,8 +218,9 @@ def test_the_profile_s_factors_are_the_rule_on_its_recorded_spread_and_the_bandi
             assert got == rec["head_spread"][O.head_id(B, nA, w)], (B, nA, w)
     assert T.HEAD.factors(161, 2, True)("g_q2") == T.Y.FACTORS and T.HEAD.factors(1, 1, True)("g_q1") == T.Y.FACTORS
     st = rec["stepped"]
-    assert set(st["cases"]) == set(st["sharpness"]) == {D.shape_id(s) for s in T.MAIN_SHAPES}
-    for shape in T.MAIN_SHAPES:
+    assert set(st["cases"]) == set(st["sharpness"]) == {D.shape_id(s) for s in T.STEP_SHAPES} and set(st["kernel"]) <= set(st["cases"])
+    assert T.STEP_SHAPES[:2] == T.MAIN_SHAPES and set(T.STEP_SHAPES[2:]) == set(T.TEAM_SHAPES) <= set(D.LEARNER_SHAPES)
+    for shape in T.STEP_SHAPES:
         for name, (mean, mx) in st["kernel"].get(D.shape_id(shape), {}).items():
             assert mean <= T.Y.FACTORS[0] and mx <= T.Y.FACTORS[1], (shape, name)
     b = rec["bandit"]

@@ -8,7 +8,8 @@
             wider than the project's (2, 4) that yardstick_util.exceptions_from makes of it
   stepped   the whole-update case of tests/test_hip_td3_learner.py (td3_util.stepped_case), all on the CPU: per shape the seed, the share
             of elements the kink filter leaves out and its zeroing rounds; how far each misreading of the update lies from the float64
-            reference, in yardstick mean errors (the smallest over w1, w2, w3, b3).  --ratios: a file of JSON lines the GPU test
+            reference, in yardstick mean errors (the smallest over w1, w2, w3, b3; with more than one agent also the agent-index
+            misreading, the smoothing normals of agent j - 1).  --ratios: a file of JSON lines the GPU test
             appended under BSX_TD3_RATIOS_OUT, kept as "kernel"
   bandit    the learning check: the update count N, chosen HERE with the torch composition of TD3 alone -- the smallest candidate from
             which on it closes at least 60 % of the gap from its initial held-out reward to 0 (the test asks half) --, what the
@@ -40,7 +41,7 @@ def main():
     bandit = O.bandit_section(old, lambda N: T.bandit_torch_run(N, policy_delay=DELAY), bandit_learner, dict(O.BANDIT, policy_delay=DELAY))
     head, factors = O.head_sections(T.HEAD, T.HEAD_SHAPES)
     cases, sharp = {}, {}
-    for shape in T.MAIN_SHAPES:
+    for shape in T.STEP_SHAPES:
         c, sid = T.stepped_case(shape), D.shape_id(shape)
         cases[sid] = dict(seed=c.seed, left_out_percent=round(100 * c.share, 2), zeroing_rounds=c.rounds)
         sharp[sid] = O.sharpness(T.wrong_variants(c, shape[4]))
