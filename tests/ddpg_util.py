@@ -370,7 +370,9 @@ def snapshot(x):
 
 class Hand(O.Hand):
     """What a DDPGLearner holds, under the same names, and its update written out with the public primitives alone: offpolicy_util.Hand's
-    and ddpg_inputs, td_head."""
+    and ddpg_inputs, td_head.  own_priorities: on a prioritised ring step() also writes the drawn rows' new priorities directly after
+    td_head, where DDPGLearner does (tests/test_hip_replay_prio.py hooks them onto td_head instead; td3_util's and sac_util's always do)."""
+    own_priorities = False
 
     def step(self, obs, act, rew, obs_next, done, u, weight=None, adam=True):
         """The ten steps on a batch -> (critic row, actor row): copies of mlp_grad's cached rows."""
@@ -383,6 +385,8 @@ class Hand(O.Hand):
         q_next, q = self.forward(self._blob_tc, x_next, True), self.forward(self._blob_c, x_cur, True)
         head = L.td_head(q, q_next, rew, done, self.gamma, weight=weight)
         self.stats[u].copy_(head.stats)
+        if self.prioritized and self.own_priorities:
+            self.buffer.update_priorities(q, head.td)
         row_c, = self.critic_rows(x_cur, [head.g_q])
         if adam:
             self.critics_step([row_c], u)

@@ -179,6 +179,52 @@ def test_the_draws_own_normals_are_philox_normals_under_a_salt_of_their_own_and_
     assert (other != a).mean() > 0.99 and np.array_equal(_philox_draw(B, nA, SEQ_BASE)[0], a)
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_the_draw_is_the_rollouts_gaussian_head_kernel_against_kernel_bit_for_bit(n):
+    """sac_sample_actions' docstring calls the draw "the rollout's Gaussian head, operation for operation": the two kernels on the same
+    tanh rows, log_std and injected normals.  FusedActor.forward_into (float32, E = 129: two workgroups and a ragged last wave) gives the
+    tanh rows mu (the plain kernel at noise 0, as test_hip_gaussian_head.py's _draw reads them) and the head's draw a and logp for all
+    2n planes; sac_sample_actions on each team's columns of mu, log_std and z must write a's bits into the slots
+    ddpg_put_actions(own_only) names, nothing else of x, and logp's bits -- with own and with central critics.  log_std differs per plane
+    and column; rows 0 .. 3 of z are +0, -0, 25 and -1e4."""
+    from deep_rl_battlespace_amd.learner import sac_sample_actions
+    from deep_rl_battlespace_amd.rollout import FusedActor, StackedActor
+    E, A, Do = 129, 2 * n, 3 * n + 2
+    torch.manual_seed(5)
+    actor = StackedActor(A, Do, 3, device="cuda")
+    with torch.no_grad():
+        actor.w3.mul_(30.0)
+    fa = FusedActor(actor, n, precision="f32")
+    g = torch.Generator().manual_seed(70 + n)
+    obs = (torch.rand((E, A, Do), generator=g) * 2 - 1).cuda()
+    z = torch.randn((E, A, 4), generator=g)
+    z[0], z[1], z[2], z[3] = 0.0, -0.0, 25.0, -1.0e4
+    z = z.cuda()
+    ls = torch.linspace(-1.6, 0.5, A * 3).reshape(A, 3).cuda().contiguous()
+    mu, a = torch.empty((E, A, 4), device="cuda"), torch.empty((E, A, 4), device="cuda")
+    lp = torch.full((E, A), 7.0, device="cuda")
+    fa.forward_into(obs, mu, 0.0, seq=1)
+    fa.forward_into(obs, a, seq=1, z=z, gaussian=dict(log_std=ls, logp=lp))
+    torch.cuda.synchronize()
+    assert float(mu[..., :3].abs().max()) <= 1.0 < float(a[..., :3].abs().max()) and bool(torch.isfinite(lp).all())
+    assert torch.equal(a[0, :, :3], mu[0, :, :3]) and torch.equal(a[1, :, :3], mu[1, :, :3])          # z = +-0: the draw is the mean
+    for c0 in (0, n):                                                                # red's columns, blue's
+        cut = slice(c0, c0 + n)
+        y4, zz, l = mu[:, cut].contiguous(), z[:, cut].contiguous(), ls[cut].contiguous()
+        for central in (False, True):
+            for own_only in (False, True):
+                shape = (E, n, Do, 3, int(central))
+                x = _x(Buffers(False), shape)
+                x0 = x.cpu().numpy()
+                _, logp, z_out = sac_sample_actions(y4, l, x, Do, 3, z=zz, central=central, own_only=own_only)
+                torch.cuda.synchronize()
+                what = (n, c0, central, own_only)
+                assert np.array_equal(_bits(logp), _bits(lp[:, cut].contiguous())), what
+                want = D.ref_put_actions(a[:, cut].cpu().numpy(), x0, Do, 3, central, own_only)
+                assert np.array_equal(_bits(x), want.view(np.int32)), what
+                assert np.array_equal(_bits(z_out)[..., :3], _bits(zz)[..., :3]) and not _bits(z_out)[..., 3].any(), what
+
+
 # ---------------------------------------------------------------------------------------------------- 3. the policy's seeds
 @pytest.mark.parametrize("weight", [True, False], ids=["weighted", "plain"])
 @pytest.mark.parametrize("BnA", S.HEAD_SHAPES[:5], ids=lambda s: "B%d-nA%d" % s)
