@@ -27,6 +27,8 @@ Only what the hot path needs lives here:
                  target step (csrc/bsx_td3_head.hip)
     sac.py       soft actor-critic on the same ring: the Gaussian policy's reparameterised draw, the soft twin head, the gradients
                  of log_std and of the temperature, and SACLearner (csrc/bsx_sac_head.hip)
+    dqn.py       Q-learning for the discrete game on the same ring: the double-Q head, independent or VDN-mixed, and DQNLearner, whose
+                 bounded Q network is the very network the rollout plays (csrc/bsx_dqn_head.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
@@ -38,6 +40,7 @@ from .learner import (TD_STATS, AdamState, DDPGLearner, Minibatch, PPOLearner, a
 from .learner import TD3_STATS, TD3Learner, td3_head, td3_head_workspace_bytes, td3_smooth_actions  # noqa: F401
 from .learner import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
                       sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
+from .learner import DQN_STATS, DQNLearner, DqnHead, dqn_head, dqn_head_workspace_bytes  # noqa: F401
 from .envs.battle_env import parallel_env  # noqa: F401
 from .replay import NStepAppender, PrioritizedReplayBuffer  # noqa: F401
 
@@ -45,4 +48,5 @@ __all__ = ["AdamState", "DDPGLearner", "Minibatch", "NStepAppender", "PPOLearner
            "minibatch_gather", "mlp_adam_step", "mlp_adam_step_workspace_bytes", "mlp_grad", "parallel_env", "ppo_head", "share_group", "shuffle_rows", "TD_STATS",
            "td_head", "td_head_workspace_bytes", "tie_", "TD3Learner", "TD3_STATS", "td3_head", "td3_head_workspace_bytes", "td3_smooth_actions",
            "SACLearner", "SAC_PI_STATS", "SAC_STATS", "SacHead", "SacPolicyGrad", "sac_head", "sac_head_workspace_bytes", "sac_policy_grad",
-           "sac_policy_grad_workspace_bytes", "sac_policy_seed", "sac_sample_actions"]
+           "sac_policy_grad_workspace_bytes", "sac_policy_seed", "sac_sample_actions", "DQNLearner", "DQN_STATS", "DqnHead", "dqn_head",
+           "dqn_head_workspace_bytes"]

@@ -123,6 +123,10 @@ class BsxSacPolicyIo(ctypes.Structure):
                                         "g_log_alpha", "alpha_m", "alpha_v", "hyper", "step")]
 
 
+class BsxDqnIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("y_cur", "y_next_online", "y_next_target", "act", "rew", "done", "weight", "g4", "q", "td")]
+
+
 MINIBATCH_FIELDS = ("obs", "rec", "logp", "adv", "ret", "value", "mask")
 
 
@@ -225,6 +229,9 @@ SIGNATURES = {
     "bsx_sac_policy_grad_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_sac_policy_grad": (c_int, [ctypes.POINTER(BsxSacPolicyIo), c_int64, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p,
                                     c_void_p]),
+    "bsx_dqn_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_dqn_head": (c_int, [ctypes.POINTER(BsxDqnIo), c_int64, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_int, c_int, c_void_p,
+                             c_void_p, c_void_p]),
     "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
                                      c_void_p]),

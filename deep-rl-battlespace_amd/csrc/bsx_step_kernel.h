@@ -3,19 +3,9 @@
 // bsx_instinct.h, bsx_step_kernel.h) and by the three translation units that instantiate the step kernels; namespace bsxk.
 #pragma once
 
-namespace bsxk {
+#include "bsx_argmax4.h"             // argmax4: np.argmax over four scores, shared with the DQN head
 
-// np.argmax over four scores (battle_env.py:327-328): the first maximum; a NaN compares as the maximum.  The running maximum is a
-// register, not v[arg]: a dynamically indexed local array lives in scratch memory.
-__device__ inline int argmax4(float a, float b, float c, float d) {
-    int am = 0;
-    float best = a;
-    const float v[3] = {b, c, d};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        if (!(best != best) && (v[i] > best || v[i] != v[i])) { am = i + 1; best = v[i]; }
-    return am;
-}
+namespace bsxk {
 
 struct StepArgs {
     StatePtrs st;

@@ -8,6 +8,8 @@
   td3.py      target policy smoothing, the TD head of two critics, the second critic TD3Learner and SACLearner share, and TD3Learner: twin critics,
               a delayed actor and target step (csrc/bsx_td3_head.hip)
   sac.py      the Gaussian policy's reparameterised draw, the soft twin head, the policy's seeds and gradients, and SACLearner (csrc/bsx_sac_head.hip)
+  dqn.py      Q-learning for the discrete game: the double-Q head, independent or VDN-mixed, and DQNLearner, whose Q network is the network
+              the rollout plays (csrc/bsx_dqn_head.hip)
   _common.py  what more than one of them uses: the hyper-parameter ranges, the stream, the capture of an update as one graph
 
 A PPO minibatch:  [minibatch_gather] -> bsx_actor_forward with the value head -> ppo_head -> bsx_mlp_grad of the actor, of the critic -> adam_step.
@@ -19,7 +21,10 @@ A SAC update:     as TD3's without its delay, the CURRENT actor and sac_sample_a
                   with logp'), both target critics and both critics -> sac_head -> bsx_mlp_grad of each critic, ONE mlp_adam_step of both with their
                   targets -> actor, sac_sample_actions (a ~ pi with logp, z) -> both stepped critics, sac_policy_seed -> bsx_mlp_grad of each critic
                   for grad_x -> sac_policy_grad (g_a4, g_log_std, log_alpha's step) -> bsx_mlp_grad, mlp_adam_step of the actor with log_std.
-n-step targets:   the three off-policy updates are unchanged on a ring filled through replay.NStepAppender (rows whose reward is the folded
+A DQN update:     buffer.sample -> the online network on obs, [on obs_next: double Q], the target network on obs_next -> dqn_head (the replayed
+                  and the greedy next action by the step kernel's argmax4, independent or VDN) -> bsx_mlp_grad(squash) -> ONE mlp_adam_step with
+                  the Polyak target.  Q_i(o, a) = q_scale * tanh row: what the learner calls greedy is what a published rollout plays.
+n-step targets:   the off-policy updates are unchanged on a ring filled through replay.NStepAppender (rows whose reward is the folded
                   n-step sum and whose obs_next lies up to n ticks on): the learner wants gamma=app.bootstrap_gamma, the appender's gamma^n.
                   SAC's target then carries the entropy term at the bootstrap state only.
 """
@@ -32,6 +37,7 @@ from .ppo import KINDS, STATS, PPOLearner, PpoHead, ppo_head, ppo_head_workspace
 from .td3 import TD3_STATS, TD3Learner, Td3Head, td3_head, td3_head_workspace_bytes, td3_smooth_actions  # noqa: F401
 from .sac import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
                   sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
+from .dqn import DQN_STATS, DQNLearner, DqnHead, dqn_head, dqn_head_workspace_bytes  # noqa: F401
 from .shuffle import GATHER_ROWS, Minibatch, minibatch_gather, shuffle_rows  # noqa: F401
 
 _Buffers, _buffers, _actor_forward, _mlp_forward, _mlp_grad, _tied_tensors, _critic_width = (  # used by tests/ and tools/

@@ -2,6 +2,8 @@
 
   ddpg_inputs, ddpg_put_actions, td_head, ddpg_action_grad      the critic's inputs from a batch, actions into them, the TD target, the actor's grad_out
   DDPGLearner(buffer, actor, critic=None, ...)                  the MADDPG update of a team from its DeviceReplayBuffer; capture() makes it one graph
+  _RingLearner                                                  what a learner on a device ring holds and does whatever its algorithm: a network's record,
+                                                                the state list, update(), capture(), sync(), publish() -- DDPGLearner's and dqn.DQNLearner's base
 """
 import copy
 from collections import namedtuple
@@ -116,15 +118,25 @@ def _head_rows(q, what, name="q1"):
     return B, nA, dev
 
 
-def _head_args(what, rows, done, gamma, weight, grads, out, workspace, per_agent=()):
-    """The argument check td_head, td3_head and sac_head share -> (B, nA, dev, gamma, out, workspace).  rows: the (tensor, name) pairs of
-    the float32 [B, nA] inputs, the first giving the shape; per_agent: those of the float32 [nA] ones; grads: the names of the [B, nA, 4]
-    outputs.  out: (*grads, td or None, stats) to write into, or None for new tensors; workspace: bsx_<what>_workspace_bytes(B, nA) bytes,
-    or None for a new one."""
-    first, anchor = rows[0]
-    B, nA, dev = _head_rows(first, what, anchor)
+def _head_args(what, rows, done, gamma, weight, grads, out, workspace, per_agent=(), rows4=(), values=()):
+    """The argument check td_head, td3_head, sac_head and dqn_head share -> (B, nA, dev, gamma, out, workspace).  rows: the (tensor, name)
+    pairs of the float32 [B, nA] inputs, the first giving the shape; per_agent: those of the float32 [nA] ones; grads: the names of the
+    [B, nA, 4] outputs.  rows4: the pairs of float32 [B, nA, 4] inputs (dqn_head's network rows; a None among them is left out) -- where
+    there are any, the first of THEM gives the shape; values: the names of [B, nA] outputs that follow the grads (dqn_head's q).  out:
+    (*grads, *values, td or None, stats) to write into, or None for new tensors; workspace: bsx_<what>_workspace_bytes(B, nA) bytes, or
+    None for a new one."""
+    first, anchor = (rows4 or rows)[0]
+    if rows4:
+        if not isinstance(first, torch.Tensor) or first.dim() != 3:
+            raise ValueError(f"{anchor} must be a float32 [B, nA, 4] tensor")
+        B, nA, dev = _head_rows(first[..., 0], what, anchor)
+    else:
+        B, nA, dev = _head_rows(first, what, anchor)
     gamma = _hyper("gamma", gamma)
     need = partial(_need, dev=dev, anchor=anchor)
+    for x, name in rows4:
+        if x is not None:
+            need(x, name, (B, nA, 4), _F32)
     for x, name in rows:
         need(x, name, (B, nA), _F32)
     need(done, "done", (B, nA), _FLAG)
@@ -134,12 +146,14 @@ def _head_args(what, rows, done, gamma, weight, grads, out, workspace, per_agent
         need(weight, "weight", (B, nA), _F32)
     if out is None:
         f = _f32(torch.empty, dev)
-        out = (*(f(B, nA, 4) for _ in grads), f(B, nA), torch.empty(8, dtype=torch.float64, device=dev))
+        out = (*(f(B, nA, 4) for _ in grads), *(f(B, nA) for _ in values), f(B, nA), torch.empty(8, dtype=torch.float64, device=dev))
     *g, td, stats = out
-    if len(g) != len(grads):
-        raise ValueError(f"out must be ({', '.join(grads)}, td or None, stats)")
+    if len(g) != len(grads) + len(values):
+        raise ValueError(f"out must be ({', '.join(tuple(grads) + tuple(values))}, td or None, stats)")
     for x, name in zip(g, grads):
         need(x, "out " + name, (B, nA, 4), _F32)
+    for x, name in zip(g[len(grads):], values):
+        need(x, "out " + name, (B, nA), _F32)
     if td is not None:
         need(td, "out td", (B, nA), _F32)
     need(stats, "out stats", (8,), (torch.float64,))
@@ -170,7 +184,81 @@ def td_head(q, q_next, rew, done, gamma, *, weight=None, out=None, workspace=Non
     return TdHead(g_q, g_pi, td, stats)
 
 
-class DDPGLearner:
+class _RingLearner:
+    """What the learners that update networks from a device ring share, and no learner on its own: DDPGLearner (with TD3Learner and
+    SACLearner under it) and dqn.DQNLearner.  A subclass sets `buffer`, `B`, `nA`, `Do`, `k`, `updates`, `stats`, `_graph = None`, `critics`
+    (the list of its critics' records; empty without one) and `_actor_net`, the record of the network a rollout plays; it writes
+    `_update(u)` and `_state()`."""
+
+    def _net(self, net, D, critic=False, gx=False):
+        """A network as the learner holds it -> _Net: with a deep copy as its target, both packed blobs, its AdamState and MLP buffers;
+        a critic also with its q, q_next and g_q tensors, and it joins `critics`, the list the update's loops run over."""
+        B, nA, dev = self.B, self.nA, self.buffer.actor_states.device
+        target = copy.deepcopy(net)
+        target.__dict__.pop("_bsx_mlp_buffers", None)            # (a deep copy takes the network's cached buffers along)
+        target.requires_grad_(False)
+        f = _f32(torch.zeros, dev)
+        rec = _Net(net, target, net.pack(), target.pack(), AdamState(net), _buffers(net).get(B, nA, D, dev, gx=gx),
+                   *((f(B, nA), f(B, nA), f(B, nA, 4)) if critic else (None, None, None)))
+        if critic:
+            self.critics.append(rec)
+        return rec
+
+    def _nets(self):
+        """The records of every network the learner steps: the played network first, then the critics."""
+        return [self._actor_net] + self.critics
+
+    def _net_state(self):
+        """Of every network: its blobs and moments, then its parameters and its target's."""
+        return ([t for n in self._nets() for t in (n.blob, n.target_blob, n.adam.m, n.adam.v)]
+                + [getattr(net, p) for n in self._nets() for net in (n.net, n.target) for p in PARAMS])
+
+    def _run(self):
+        for u in range(self.updates):
+            self._update(u)
+
+    def update(self):
+        """`updates` updates, each on a fresh draw of the ring -> stats f64 [updates, 8] on the device (a cached buffer; no host
+        synchronisation).  The ring must hold at least one row."""
+        (self._graph.replay if self._graph is not None else self._run)()
+        return self.stats
+
+    def capture(self):
+        """Record the whole update() -- `updates` updates, the ring's draws included -- as one graph on one stream; update() replays it
+        from then on.  One eager update runs first as the warm-up and is undone: capture() leaves parameters, targets, moments, step
+        counts, blobs, statistics, the ring's draw counter and (a prioritised ring) its priorities, tree and max_priority bit for bit as
+        they were."""
+        self._graph = _capture(self._run, self._state, self.buffer.actor_states.device)
+        return self
+
+    def sync(self):
+        """Re-pack every blob from its network (two per network: four, six with a second critic, two for a DQNLearner), once: for a caller who has edited
+        parameters or targets from outside."""
+        for n in self._nets():
+            n.net.pack(out=n.blob)
+            n.target.pack(out=n.target_blob)
+
+    def publish(self, rollout, columns):
+        """The team's actors into a PolicyRollout that plays them: the actor's blob rows into rollout.fused.weights[c0 : c0 + nA] (a blob
+        row is per agent and depends on obs_len alone) and the ten parameter slices into rollout.actor.  columns: this team's env
+        columns, a contiguous range, as append_rollout takes.  Device copies on the current stream (capturable); every other row of the
+        rollout's blob and parameters is left untouched."""
+        cols = [int(c) for c in columns]
+        c0 = cols[0] if cols else 0
+        ra, net = rollout.actor, self._actor_net.net
+        if len(cols) != self.nA or cols != list(range(c0, c0 + len(cols))) or c0 < 0 or c0 + len(cols) > ra.n_actors:
+            raise ValueError(f"columns must be a contiguous range of {self.nA} of the rollout's {ra.n_actors} env columns")
+        if (ra.obs_len, ra.n_actions) != (self.Do, self.k) or ra.w1.device != net.w1.device:
+            raise ValueError(f"the rollout's actor must have obs_len {self.Do} and {self.k} actions on {net.w1.device}, got "
+                             f"{ra.obs_len} and {ra.n_actions} on {ra.w1.device}")
+        with torch.no_grad():
+            if rollout.fused is not None:
+                rollout.fused.weights[c0:c0 + self.nA].copy_(self._actor_net.blob)
+            for p in PARAMS:
+                getattr(ra, p)[c0:c0 + self.nA].copy_(getattr(net, p))
+
+
+class DDPGLearner(_RingLearner):
     """The MADDPG update of a team from its replay ring, on device: per-agent actors, one critic per agent on the team's joint
     observation and action (critic_input="central", the reference's form; Lowe et al. 2017) or on the agent's own
     (critic_input="own": independent DDPG), soft target networks, Adam.
@@ -256,20 +344,6 @@ class DDPGLearner:
         self._prioritized = isinstance(buffer, PrioritizedReplayBuffer)
         self._graph = None
 
-    def _net(self, net, D, critic=False, gx=False):
-        """A network as the learner holds it -> _Net: with a deep copy as its target, both packed blobs, its AdamState and MLP buffers;
-        a critic also with its q, q_next and g_q tensors, and it joins `critics`, the list the update's loops run over."""
-        B, nA, dev = self.B, self.nA, self._x_cur.device
-        target = copy.deepcopy(net)
-        target.__dict__.pop("_bsx_mlp_buffers", None)            # (a deep copy takes the network's cached buffers along)
-        target.requires_grad_(False)
-        f = _f32(torch.zeros, dev)
-        rec = _Net(net, target, net.pack(), target.pack(), AdamState(net), _buffers(net).get(B, nA, D, dev, gx=gx),
-                   *((f(B, nA), f(B, nA), f(B, nA, 4)) if critic else (None, None, None)))
-        if critic:
-            self.critics.append(rec)
-        return rec
-
     def _update(self, u):
         """Update u of a call: the steps of the class's docstring, each a method of its own that a subclass overrides singly."""
         buf = self.buffer
@@ -322,30 +396,11 @@ class DDPGLearner:
         mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
                       targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u], workspace=self._adam_ws)
 
-    def _run(self):
-        for u in range(self.updates):
-            self._update(u)
-
-    def update(self):
-        """`updates` updates, each on a fresh draw of the ring -> stats f64 [updates, 8] on the device (a cached buffer; no host
-        synchronisation).  The ring must hold at least one row."""
-        (self._graph.replay if self._graph is not None else self._run)()
-        return self.stats
-
     def _state(self):
         """Every tensor an update writes that outlives it."""
         return ([self.buffer._draws, self.step_actor, self.step_critic, self.stats, self.step_stats_actor, self.step_stats_critic]
-                + [t for n in [self._actor_net] + self.critics for t in (n.blob, n.target_blob, n.adam.m, n.adam.v)]
-                + [getattr(net, p) for n in [self._actor_net] + self.critics for net in (n.net, n.target) for p in PARAMS]
+                + self._net_state()
                 + ([self.buffer._leaves, self.buffer.tree, self.buffer.max_priority] if self._prioritized else []))
-
-    def capture(self):
-        """Record the whole update() -- `updates` updates, the ring's draws included -- as one graph on one stream; update() replays it
-        from then on.  One eager update runs first as the warm-up and is undone: capture() leaves parameters, targets, moments, step
-        counts, blobs, statistics, the ring's draw counter and (a prioritised ring) its priorities, tree and max_priority bit for bit as
-        they were."""
-        self._graph = _capture(self._run, self._state, self.buffer.actor_states.device)
-        return self
 
     def set_lr(self, actor=None, critic=None):
         """The learning rates of the steps from now on, written to the hyper rows on the device (fills on the current stream: no host
@@ -353,29 +408,3 @@ class DDPGLearner:
         for hyper, lr in ((self.hyper_actor, actor), (self.hyper_critic, critic)):
             if lr is not None:
                 hyper[0].fill_(_hyper("lr", lr))
-
-    def sync(self):
-        """Re-pack every blob from its network (two per network: four, or six with a second critic), once: for a caller who has edited
-        parameters or targets from outside."""
-        for n in [self._actor_net] + self.critics:
-            n.net.pack(out=n.blob)
-            n.target.pack(out=n.target_blob)
-
-    def publish(self, rollout, columns):
-        """The team's actors into a PolicyRollout that plays them: the actor's blob rows into rollout.fused.weights[c0 : c0 + nA] (a blob
-        row is per agent and depends on obs_len alone) and the ten parameter slices into rollout.actor.  columns: this team's env
-        columns, a contiguous range, as append_rollout takes.  Device copies on the current stream (capturable); every other row of the
-        rollout's blob and parameters is left untouched."""
-        cols = [int(c) for c in columns]
-        c0 = cols[0] if cols else 0
-        ra = rollout.actor
-        if len(cols) != self.nA or cols != list(range(c0, c0 + len(cols))) or c0 < 0 or c0 + len(cols) > ra.n_actors:
-            raise ValueError(f"columns must be a contiguous range of {self.nA} of the rollout's {ra.n_actors} env columns")
-        if (ra.obs_len, ra.n_actions) != (self.Do, self.k) or ra.w1.device != self.actor.w1.device:
-            raise ValueError(f"the rollout's actor must have obs_len {self.Do} and {self.k} actions on {self.actor.w1.device}, got "
-                             f"{ra.obs_len} and {ra.n_actions} on {ra.w1.device}")
-        with torch.no_grad():
-            if rollout.fused is not None:
-                rollout.fused.weights[c0:c0 + self.nA].copy_(self._blob_a)
-            for p in PARAMS:
-                getattr(ra, p)[c0:c0 + self.nA].copy_(getattr(self.actor, p))

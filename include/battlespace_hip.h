@@ -1095,6 +1095,65 @@ int bsx_sac_policy_grad_workspace_bytes(int64_t B, int nA, size_t* bytes);
 int bsx_sac_policy_grad(const BsxSacPolicyIo* io, int64_t B, int nA, int Do, int k, int central, float target_entropy, void* workspace,
                         double* stats, void* stream);
 
+/* ---- Q-learning for the discrete game (Mnih et al. 2015; double Q: van Hasselt et al. 2016; the team's mix: Sunehag et al. 2018, VDN)
+ * (deep-rl-battlespace_amd/learner/dqn.py: dqn_head, DQNLearner; csrc/bsx_dqn_head.hip).  The Q network of a team is the network its
+ * rollout plays, a StackedActor(nA, Do, 4), and its value is DEFINED as
+ *     Q_i(o, a) = q_scale * y4[i][a],      y4 = the tanh-squashed head row of bsx_mlp_forward,
+ * so the greedy action of the learner and the action a rollout of the published network plays (argmax4 below, on the same tanh row) are
+ * the same bits, ties and saturation included, and the backward is bsx_mlp_grad(squash = 1) as it stands.  Q is bounded by q_scale: the
+ * caller chooses q_scale >= r_max / (1 - gamma); a target beyond q_scale cannot be reached.  The rules above hold as they stand: every
+ * launch on `stream`, no host synchronisation, no floating-point atomics, flags or spins, a grid that is a function of (B, nA) alone,
+ * the same inputs the same bits on every call, every refusal before any launch.
+ *
+ * The TD target of (double) Q-learning, independent per agent or summed over the team, and the network's grad_out, one pass (two
+ * launches: bsx_td_head's plan).
+ *   y_cur, y_next_online, y_next_target   [B][nA][4], 16-byte aligned: the online network's rows on obs, on obs_next, and the target
+ *            network's on obs_next (bsx_mlp_forward's y).  y_next_online may be NULL with double_q = 0 (it is not read then)
+ *   act      [B][nA][4], 16-byte aligned: the replayed score rows (bsx_replay_sample's act, k = 4)
+ *   rew      [B][nA];   done  uint8 [B][nA], 1-byte aligned (any non-zero byte counts);   weight  [B][nA] or NULL = 1 for every element
+ *   g4       [B][nA][4] (out, overwritten everywhere);   q  [B][nA] (out);   td  [B][nA] (out) or NULL */
+typedef struct BsxDqnIo {
+    const float* y_cur;
+    const float* y_next_online;
+    const float* y_next_target;
+    const float* act;
+    const float* rew;
+    const uint8_t* done;
+    const float* weight;
+    float* g4;
+    float* q;
+    float* td;
+} BsxDqnIo;
+
+/* Size of bsx_dqn_head's workspace: bsx_td_head_workspace_bytes'.  BSX_E_ARG: null bytes, B or nA out of range. */
+int bsx_dqn_head_workspace_bytes(int64_t B, int nA, size_t* bytes);
+
+/* argmax4(row) is the step kernels' choice among four scores (csrc/bsx_argmax4.h): the first maximum; a NaN compares as the maximum.
+ * Per element (b, i), in float32, every operation rounded once, with s2 = float(2.0 / B) (formed in float64, rounded once):
+ *   a  = argmax4(act[b][i])                                           the replayed action
+ *   a' = argmax4((double_q ? y_next_online : y_next_target)[b][i])    the next state's greedy action
+ *   qn = done ? 0 : q_scale * y_next_target[b][i][a']    (selected, never multiplied: a finished row's next value stays out, NaN and
+ *                                                         infinities included)
+ *   qc = q_scale * y_cur[b][i][a]
+ * mix = 0 (independent):   y = fmaf(gamma, qn, rew),   Q = qc,   w = weight[b][i] or 1
+ * mix = 1 (VDN):           Q = the sum of qc over the row's agents, N that of qn, Rw that of rew -- each a float32 sum in agent order from
+ *                          agent 0 --,   y = fmaf(gamma, N, Rw),   w = weight[b][0] or 1;   every agent of the row carries the row's Q, y, w
+ * Then
+ *   d = Q - y,     c = (huber_delta > 0 && d == d) ? fminf(fmaxf(d, -huber_delta), huber_delta) : d      (a NaN stays a NaN)
+ *   g4[b][i][a] = ((w * c) * s2) * q_scale;   the other three columns of g4 are +0;     q[b][i] = Q;     td[b][i] = y
+ * g4 is bsx_mlp_grad's grad_out (squash = 1), y held fixed: independent, for the sum over agents of mean_b w l(Q_i - y_i); VDN, for
+ * mean_b w l(Q_tot - y_tot); l(d) = d^2, or with huber_delta > 0: |d| <= huber_delta ? d^2 : huber_delta (2 |d| - huber_delta).
+ * stats[8] (device, float64; learner.DQN_STATS): n = B nA, then the means over the n elements -- float64 sums of the float32
+ * per-element terms, divided by n -- of w l(d) (as (w * d) * d, or w * (huber_delta * (2 * |d| - huber_delta)) beyond the corner), Q, y,
+ * |d|, done != 0 and w; last, greedy = the mean of a == argmax4(y_cur[b][i]).
+ * Launches, workspace and the order of the sums: bsx_td_head's.  With mix = 1 every thread of a row adds the row's sums itself.
+ * Refusals, before any launch, in this order: BSX_E_ARG for a null io, y_cur, y_next_target, act, rew, done, g4, q, workspace or stats; a
+ * gamma outside [0, 1] (NaN too); B or nA out of range; a q_scale not above 0 (NaN too); a huber_delta below 0 (NaN too); a double_q or a
+ * mix outside {0, 1}; a null y_next_online with double_q = 1.  Then BSX_E_ALIGN for y_cur, y_next_online, y_next_target, act or g4 off a
+ * 16-byte boundary; rew, weight, q or td off a 4-byte one; workspace or stats off an 8-byte one. */
+int bsx_dqn_head(const BsxDqnIo* io, int64_t B, int nA, float gamma, float q_scale, float huber_delta, int double_q, int mix, void* workspace,
+                 double* stats, void* stream);
+
 /* ---- shuffled minibatches (deep-rl-battlespace_amd/learner.py: shuffle_rows, minibatch_gather, PPOLearner(shuffle=True);
  * csrc/bsx_shuffle.hip): a keyed permutation of the N = T x E rows of a rollout, evaluated per position -- O(1), no sort, no workspace,
  * no atomics --, and the gather of one minibatch's rows through it.
