@@ -29,6 +29,8 @@ Only what the hot path needs lives here:
                  of log_std and of the temperature, and SACLearner (csrc/bsx_sac_head.hip)
     dqn.py       Q-learning for the discrete game on the same ring: the double-Q head, independent or VDN-mixed, and DQNLearner, whose
                  bounded Q network is the very network the rollout plays (csrc/bsx_dqn_head.hip)
+    qmix.py      QMIX on the same ring: the monotone mixing head between the Q network and a hypernetwork that is itself a fused MLP, and
+                 QMIXLearner -- team values that are no sum of per-plane terms (csrc/bsx_qmix_head.hip)
   render.py      one game's exported state as an RGB image on the host, diagnostic (next row f-4)
 There is no CPU fallback: without the HIP library the env cannot be constructed.
 """
@@ -41,6 +43,7 @@ from .learner import TD3_STATS, TD3Learner, td3_head, td3_head_workspace_bytes, 
 from .learner import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
                       sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
 from .learner import DQN_STATS, DQNLearner, DqnHead, dqn_head, dqn_head_workspace_bytes  # noqa: F401
+from .learner import QMIX_STATS, QMIXLearner, QmixHead, qmix_head, qmix_head_workspace_bytes, qmix_inputs, qmix_members  # noqa: F401
 from .envs.battle_env import parallel_env  # noqa: F401
 from .replay import NStepAppender, PrioritizedReplayBuffer  # noqa: F401
 
@@ -49,4 +52,5 @@ __all__ = ["AdamState", "DDPGLearner", "Minibatch", "NStepAppender", "PPOLearner
            "td_head", "td_head_workspace_bytes", "tie_", "TD3Learner", "TD3_STATS", "td3_head", "td3_head_workspace_bytes", "td3_smooth_actions",
            "SACLearner", "SAC_PI_STATS", "SAC_STATS", "SacHead", "SacPolicyGrad", "sac_head", "sac_head_workspace_bytes", "sac_policy_grad",
            "sac_policy_grad_workspace_bytes", "sac_policy_seed", "sac_sample_actions", "DQNLearner", "DQN_STATS", "DqnHead", "dqn_head",
-           "dqn_head_workspace_bytes"]
+           "dqn_head_workspace_bytes", "QMIXLearner", "QMIX_STATS", "QmixHead", "qmix_head", "qmix_head_workspace_bytes", "qmix_inputs",
+           "qmix_members"]

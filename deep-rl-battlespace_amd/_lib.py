@@ -23,6 +23,7 @@ ACT_I32, ACT_LOGITS_F32 = 0, 1
 ACT_F32, ACT_F64, ACT_F32X4 = 0, 1, 2
 PRIO_FANOUT, PRIO_ONE, PRIO_SALT = 64, 65536, 0x3C6EF372
 SAC_SALT = 0x60000000
+QMIX_MAX_AGENTS, QMIX_EMBEDS = 4, (4, 8, 16)
 WINNER_NAMES = ("none", "red", "blue", "tie")
 
 c_void_p, c_int, c_int64, c_uint32, c_uint64, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
@@ -125,6 +126,11 @@ class BsxSacPolicyIo(ctypes.Structure):
 
 class BsxDqnIo(ctypes.Structure):
     _fields_ = [(f, c_void_p) for f in ("y_cur", "y_next_online", "y_next_target", "act", "rew", "done", "weight", "g4", "q", "td")]
+
+
+class BsxQmixIo(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in ("y_cur", "y_next_online", "y_next_target", "hy_cur", "hy_next_target", "act", "rew", "done", "weight",
+                                        "g4", "gh", "q", "td")]
 
 
 MINIBATCH_FIELDS = ("obs", "rec", "logp", "adv", "ret", "value", "mask")
@@ -232,6 +238,11 @@ SIGNATURES = {
     "bsx_dqn_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_dqn_head": (c_int, [ctypes.POINTER(BsxDqnIo), c_int64, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_int, c_int, c_void_p,
                              c_void_p, c_void_p]),
+    "bsx_qmix_members": (c_int, [c_int, c_int, ctypes.POINTER(c_int)]),
+    "bsx_qmix_inputs": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsx_qmix_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "bsx_qmix_head": (c_int, [ctypes.POINTER(BsxQmixIo), c_int64, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_int, c_void_p,
+                              c_void_p, c_void_p]),
     "bsx_shuffle_rows": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "bsx_minibatch_gather": (c_int, [ctypes.POINTER(BsxMinibatchIo), c_int64, c_int64, c_int64, c_int, c_int, c_uint64, c_uint64, c_void_p,
                                      c_void_p]),

@@ -66,6 +66,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_sac_head.hip"), ["-ffp-contract=off"]),
            # the DQN head of the discrete game: every operation rounded on its own, as tests/dqn_util.py restates them
            (os.path.join(CSRC, "bsx_dqn_head.hip"), ["-ffp-contract=off"]),
+           # the QMIX head: the monotone mix, its TD target and both networks' grad_out, every operation rounded on its own (tests/qmix_util.py)
+           (os.path.join(CSRC, "bsx_qmix_head.hip"), ["-ffp-contract=off"]),
            # the keyed row permutation and the minibatch gather: integer arithmetic and bit copies
            (os.path.join(CSRC, "bsx_shuffle.hip"), [])]
 

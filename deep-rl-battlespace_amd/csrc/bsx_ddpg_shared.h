@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "battlespace_hip.h"
+#include "bsx_argmax4.h"
 #include "bsx_args.h"
 #include "bsx_block_sum.h"
 
@@ -26,6 +27,11 @@ constexpr int64_t COPY_MAX_BLOCKS = 65536;     // the copy kernels stride over t
 constexpr int MAX_DO = 3 * BSX_MAX_N + 2;      // an observation row of the widest team
 
 typedef float F4 __attribute__((ext_vector_type(4)));
+
+// a row of four scores as the discrete heads (bsx_dqn_head.hip, bsx_qmix_head.hip) read it: the step kernels' choice, and column a of a
+// row by selects -- a dynamically indexed vector would live in scratch memory
+__device__ __forceinline__ int argmax_row(const F4 v) { return bsxk::argmax4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ float pick(const F4 v, int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : (a == 2 ? v[2] : v[3])); }
 
 struct Shape {                                 // a checked (B, nA, Do, k, central)
     int64_t B;

@@ -28,11 +28,6 @@ struct HeadArgs {
     double* part;                              // workspace: [blocks][STAT_COLS] partial rows
 };
 
-__device__ __forceinline__ int argmax_row(const F4 v) { return bsxk::argmax4(v[0], v[1], v[2], v[3]); }
-
-// column a of a row by selects: a dynamically indexed vector would live in scratch memory
-__device__ __forceinline__ float pick(const F4 v, int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : (a == 2 ? v[2] : v[3])); }
-
 struct Elem {                                  // what element (b, i) contributes on its own
     float qc, qn;
     int a;

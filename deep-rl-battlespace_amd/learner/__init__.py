@@ -10,6 +10,8 @@
   sac.py      the Gaussian policy's reparameterised draw, the soft twin head, the policy's seeds and gradients, and SACLearner (csrc/bsx_sac_head.hip)
   dqn.py      Q-learning for the discrete game: the double-Q head, independent or VDN-mixed, and DQNLearner, whose Q network is the network
               the rollout plays (csrc/bsx_dqn_head.hip)
+  qmix.py     QMIX for the discrete game: the monotone mixing head between the Q network and a hypernetwork the fused MLP kernels already take,
+              and QMIXLearner (csrc/bsx_qmix_head.hip)
   _common.py  what more than one of them uses: the hyper-parameter ranges, the stream, the capture of an update as one graph
 
 A PPO minibatch:  [minibatch_gather] -> bsx_actor_forward with the value head -> ppo_head -> bsx_mlp_grad of the actor, of the critic -> adam_step.
@@ -24,6 +26,9 @@ A SAC update:     as TD3's without its delay, the CURRENT actor and sac_sample_a
 A DQN update:     buffer.sample -> the online network on obs, [on obs_next: double Q], the target network on obs_next -> dqn_head (the replayed
                   and the greedy next action by the step kernel's argmax4, independent or VDN) -> bsx_mlp_grad(squash) -> ONE mlp_adam_step with
                   the Polyak target.  Q_i(o, a) = q_scale * tanh row: what the learner calls greedy is what a published rollout plays.
+A QMIX update:    buffer.sample -> the three forwards of a DQN update -> qmix_inputs -> the mixer on x_cur, the target mixer on x_next (their tanh
+                  rows are the mix's weights) -> qmix_head (Q_tot = the monotone mix of the replayed actions' values, its double-Q target, g4 and
+                  gh) -> bsx_mlp_grad(squash) of the Q network, of the mixer -> mlp_adam_step of each with its Polyak target.
 n-step targets:   the off-policy updates are unchanged on a ring filled through replay.NStepAppender (rows whose reward is the folded
                   n-step sum and whose obs_next lies up to n ticks on): the learner wants gamma=app.bootstrap_gamma, the appender's gamma^n.
                   SAC's target then carries the entropy term at the bootstrap state only.
@@ -38,6 +43,7 @@ from .td3 import TD3_STATS, TD3Learner, Td3Head, td3_head, td3_head_workspace_by
 from .sac import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
                   sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
 from .dqn import DQN_STATS, DQNLearner, DqnHead, dqn_head, dqn_head_workspace_bytes  # noqa: F401
+from .qmix import QMIX_STATS, QMIXLearner, QmixHead, qmix_head, qmix_head_workspace_bytes, qmix_inputs, qmix_members  # noqa: F401
 from .shuffle import GATHER_ROWS, Minibatch, minibatch_gather, shuffle_rows  # noqa: F401
 
 _Buffers, _buffers, _actor_forward, _mlp_forward, _mlp_grad, _tied_tensors, _critic_width = (  # used by tests/ and tools/

@@ -3,7 +3,7 @@
   ddpg_inputs, ddpg_put_actions, td_head, ddpg_action_grad      the critic's inputs from a batch, actions into them, the TD target, the actor's grad_out
   DDPGLearner(buffer, actor, critic=None, ...)                  the MADDPG update of a team from its DeviceReplayBuffer; capture() makes it one graph
   _RingLearner                                                  what a learner on a device ring holds and does whatever its algorithm: a network's record,
-                                                                the state list, update(), capture(), sync(), publish() -- DDPGLearner's and dqn.DQNLearner's base
+                                                                the state list, update(), capture(), sync(), publish() -- DDPGLearner's, dqn.DQNLearner's and qmix.QMIXLearner's base
 """
 import copy
 from collections import namedtuple
@@ -119,7 +119,7 @@ def _head_rows(q, what, name="q1"):
 
 
 def _head_args(what, rows, done, gamma, weight, grads, out, workspace, per_agent=(), rows4=(), values=()):
-    """The argument check td_head, td3_head, sac_head and dqn_head share -> (B, nA, dev, gamma, out, workspace).  rows: the (tensor, name)
+    """The argument check td_head, td3_head, sac_head, dqn_head and qmix_head share -> (B, nA, dev, gamma, out, workspace).  rows: the (tensor, name)
     pairs of the float32 [B, nA] inputs, the first giving the shape; per_agent: those of the float32 [nA] ones; grads: the names of the
     [B, nA, 4] outputs.  rows4: the pairs of float32 [B, nA, 4] inputs (dqn_head's network rows; a None among them is left out) -- where
     there are any, the first of THEM gives the shape; values: the names of [B, nA] outputs that follow the grads (dqn_head's q).  out:
@@ -186,14 +186,15 @@ def td_head(q, q_next, rew, done, gamma, *, weight=None, out=None, workspace=Non
 
 class _RingLearner:
     """What the learners that update networks from a device ring share, and no learner on its own: DDPGLearner (with TD3Learner and
-    SACLearner under it) and dqn.DQNLearner.  A subclass sets `buffer`, `B`, `nA`, `Do`, `k`, `updates`, `stats`, `_graph = None`, `critics`
+    SACLearner under it), dqn.DQNLearner and qmix.QMIXLearner.  A subclass sets `buffer`, `B`, `nA`, `Do`, `k`, `updates`, `stats`, `_graph = None`, `critics`
     (the list of its critics' records; empty without one) and `_actor_net`, the record of the network a rollout plays; it writes
     `_update(u)` and `_state()`."""
 
-    def _net(self, net, D, critic=False, gx=False):
+    def _net(self, net, D, critic=False, gx=False, members=None):
         """A network as the learner holds it -> _Net: with a deep copy as its target, both packed blobs, its AdamState and MLP buffers;
-        a critic also with its q, q_next and g_q tensors, and it joins `critics`, the list the update's loops run over."""
-        B, nA, dev = self.B, self.nA, self.buffer.actor_states.device
+        a critic also with its q, q_next and g_q tensors, and it joins `critics`, the list the update's loops run over.  members: the
+        network's member count where it is not the team's nA (qmix.QMIXLearner's mixer): its MLP buffers are that wide."""
+        B, nA, dev = self.B, self.nA if members is None else int(members), self.buffer.actor_states.device
         target = copy.deepcopy(net)
         target.__dict__.pop("_bsx_mlp_buffers", None)            # (a deep copy takes the network's cached buffers along)
         target.requires_grad_(False)
@@ -232,7 +233,7 @@ class _RingLearner:
         return self
 
     def sync(self):
-        """Re-pack every blob from its network (two per network: four, six with a second critic, two for a DQNLearner), once: for a caller who has edited
+        """Re-pack every blob from its network (two per network: four, six with a second critic, two for a DQNLearner, four for a QMIXLearner), once: for a caller who has edited
         parameters or targets from outside."""
         for n in self._nets():
             n.net.pack(out=n.blob)
