@@ -8,6 +8,8 @@ and yardstick_util.py:
                      check of the restatement (g4 is d loss / d y4), in float32 the yardstick of the statistics
   head_inputs, corner_inputs, HEAD_SHAPES, FORMS   the head suite's inputs (rounded to float32 once), the rows built to hit the corners
                      of the contract, and its case table
+  SPLIT_SHAPES, LARGE_SHAPES, PLANS, LARGE_FORMS, head_cases, split_rows   the shapes at which a VDN row lies across two tiles or
+                     workgroups and a workgroup takes J = 2 or 3 tiles, with the plan each must get
   guarded_head       learner.dqn_head with every input, output and the workspace between guard slabs
   TEAMS, learner_case, torch_loss, update_reference, stepped_case   a whole update on the CPU in float64 (the reference) and float32
                      (the yardstick): autograd through StackedActor of the DQN loss, offpolicy_util.first_step as the optimiser step;
@@ -45,11 +47,43 @@ STAT_NAMES = ("loss", "q", "target", "abs_td", "done", "weight", "greedy")      
 HEAD_SHAPES = ((1, 1), (5, 3), (257, 2), (300, 16))
 # (mix, double, huber delta, weighted): both mixes, double on and off, Huber off and delta = 1, weighted and plain
 FORMS = tuple((mix, dbl, delta, w) for mix in ("independent", "vdn") for dbl in (True, False) for delta in (0.0, DELTA) for w in (True, False))
+# The smallest shapes at which the launch plan (bsx_ddpg_shared.h: plan_of; tiles of TILE elements, at most MAX_BLOCKS workgroups of J
+# consecutive tiles) leaves its one-tile-per-workgroup corner, (B, nA) -> (tiles, J, workgroups):
+#   SPLIT_SHAPES   a VDN row across two tiles and workgroups: at (171, 3) row 85 is elements 255 .. 257 and row 170 (510 .. 512) ends the
+#                  grid; at (103, 5) a 5-agent row lies across tiles 0 and 1.  Every form runs
+#   LARGE_SHAPES   J = 2 with split rows at every workgroup edge, two live threads in the last workgroup and one tile past `tiles`;
+#                  bsx_td3_head's own (16385, 16), the widest team; J = 3, which tells blockIdx * J from a hard-coded 2.  LARGE_FORMS run:
+#                  every template bit takes both values
+TILE, MAX_BLOCKS = 256, 1024
+SPLIT_SHAPES = ((171, 3), (103, 5))
+LARGE_SHAPES = ((87382, 3), (16385, 16), (174763, 3))
+PLANS = {(171, 3): (3, 1, 3), (103, 5): (3, 1, 3), (87382, 3): (1025, 2, 513), (16385, 16): (1025, 2, 513), (174763, 3): (2049, 3, 683)}
+LARGE_FORMS = (("vdn", True, DELTA, True), ("vdn", False, 0.0, False), ("independent", True, 0.0, True), ("independent", False, DELTA, False))
+LARGE_PERMS = 2                     # the yardstick's row orders beside the given one at the LARGE_SHAPES (8 elsewhere): a test stays at seconds
 
 
 def form_id(form):
     mix, dbl, delta, w = form
     return "%s-%s-%s-%s" % (mix, "double" if dbl else "single", "huber" if delta else "mse", "weighted" if w else "plain")
+
+
+def shape_id(s):
+    return "B%d-nA%d" % s
+
+
+def head_cases():
+    """[(shape, form)] of the head suite: every form at HEAD_SHAPES and SPLIT_SHAPES, LARGE_FORMS at LARGE_SHAPES."""
+    return [(s, f) for s in HEAD_SHAPES + SPLIT_SHAPES for f in FORMS] + [(s, f) for s in LARGE_SHAPES for f in LARGE_FORMS]
+
+
+def head_case_id(c):
+    return shape_id(c[0]) + "-" + form_id(c[1])
+
+
+def split_rows(B, nA):
+    """The rows whose nA elements lie in two tiles."""
+    b = np.arange(B, dtype=np.int64)
+    return np.flatnonzero((b * nA) // TILE != (b * nA + nA - 1) // TILE)
 
 
 # ------------------------------------------------------------------------------------------------ the head's contract
@@ -265,15 +299,21 @@ def head_case(B, nA, form, perms=8):
     return inp, ref, yard, Y.own_error(lambda order: torch_head(inp, torch.float32, perm=order, **kw), ref, B, perms)[0]
 
 
+def head_case_of(BnA, form):
+    """head_case of a shape of the head suite: at the LARGE_SHAPES with LARGE_PERMS and not kept (one test reads each)."""
+    return head_case.__wrapped__(*BnA, form, LARGE_PERMS) if BnA in LARGE_SHAPES else head_case(*BnA, form)
+
+
 def stats_out_of_bounds(got, ref, e_stats, what=""):
     """n and the two counts' means (done, greedy: exact in float64) exactly; the others by yardstick_util.scalar_bound."""
     exact = [name for i, name in ((0, "n"), (5, "done"), (7, "greedy")) if got[i] != ref[i]]
     return exact + Y.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, what)
 
 
-def guarded_head(inp, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, fill=7.0, td=True):
+def guarded_head(inp, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, fill=7.0, td=True, keep=None):
     """learner.dqn_head on `inp` with every input, output and the workspace between guard slabs (guarded) and every output float starting
-    as `fill` -> (the binding's result: the `out` tensors themselves, the strays).  offpolicy_util.guarded_head for this head's outputs."""
+    as `fill` -> (the binding's result: the `out` tensors themselves, the strays).  offpolicy_util.guarded_head for this head's outputs.
+    keep: a dict that receives the workspace (int64, every word -1 before the call) as [workgroups, 8] partial rows."""
     from deep_rl_battlespace_amd import learner as L
     from guard_util import Buffers
     mix, dbl, delta, w = form
@@ -288,13 +328,18 @@ def guarded_head(inp, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, fill=7.
                      out=out, workspace=ws)
     torch.cuda.synchronize()
     assert all(a is b for a, b in zip(res, out))
+    if keep is not None:
+        keep["workspace"] = ws.view(-1, 8)
     return res, G.stray()
 
 
 # ------------------------------------------------------------------------------------------------ a whole update
 TEAMS = ((1, 5), (2, 8), (3, 11), (16, 50))         # (nA, Do)
 B = 64
+B_SPLIT = SPLIT_SHAPES[0][0]                        # 171 rows of a 3v3 team: three tiles, the VDN rows 85 and 170 split (SPLIT_SHAPES)
 MIXES = ("independent", "vdn")
+# (team, mix, batch) of the whole-update cases against float64: every team with both mixes at B, and the 3v3 team above one tile
+STEP_CASES = tuple((t, m, B) for t in TEAMS for m in MIXES) + tuple((TEAMS[2], m, B_SPLIT) for m in MIXES)
 KW = dict(gamma=GAMMA, tau=0.05, lr=2e-3, max_grad_norm=0.5, q_scale=Q_SCALE, huber_delta=DELTA)
 # ddpg_util.STEP_KW's eps, for its reason: at eps = 1e-8 Adam's first step is lr sign(g) and a gradient error of float32's size moves a parameter by lr
 STEP_KW = dict(KW, betas=(0.9, 0.999), eps=1e-3)
@@ -307,8 +352,13 @@ CASE_SEED = 60
 STEP_SEEDS = {}
 
 
-def team_id(team, mix=None):
-    return "nA%d-Do%d" % team + ("" if mix is None else "-" + mix)
+def step_seed(team, mix, batch_size=B):
+    """STEP_SEEDS' entry of a case: under (team, mix) at B, under (team, mix, batch_size) elsewhere."""
+    return STEP_SEEDS.get((team, mix) if batch_size == B else (team, mix, batch_size), 0)
+
+
+def team_id(team, mix=None, batch_size=B):
+    return "nA%d-Do%d" % team + ("" if mix is None else "-" + mix) + ("" if batch_size == B else "-B%d" % batch_size)
 
 
 def make_qnet(nA, Do, seed=0):
@@ -320,13 +370,13 @@ def make_qnet(nA, Do, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
-def learner_case(team, seed=0):
-    """(qnet, ring rows (N = 4 B; the act rows are score rows), idx of the first batch) of a team.  Read-only."""
+def learner_case(team, seed=0, batch_size=B):
+    """(qnet, ring rows (N = 4 batch_size; the act rows are score rows), idx of the first batch) of a team.  Read-only."""
     nA, Do = team
     seed += CASE_SEED
     qnet = make_qnet(nA, Do, seed)
-    rows = D.ring_rows(4 * B, nA, Do, 4, seed)
-    idx = torch.randint(0, 4 * B, (B,), generator=torch.Generator().manual_seed(9500 + seed))
+    rows = D.ring_rows(4 * batch_size, nA, Do, 4, seed)
+    idx = torch.randint(0, 4 * batch_size, (batch_size,), generator=torch.Generator().manual_seed(9500 + seed))
     return qnet, rows, idx
 
 
@@ -379,13 +429,13 @@ def near_kink(qnet, batch, ref, mix, kw=None):
     return torch.from_numpy(near)
 
 
-def try_seed(team, mix, seed):
+def try_seed(team, mix, seed, batch_size=B):
     """(the case or None where it does not qualify, share of rows left out, zeroing rounds, the smallest arg-max margin over ALL rows)."""
-    qnet, rows, idx = learner_case(team, seed)
+    qnet, rows, idx = learner_case(team, seed, batch_size)
     g = torch.Generator().manual_seed(9700 + seed)
     target = D.perturbed(qnet, g)
     batch = tuple(r[idx] for r in rows)
-    w0 = torch.rand((B, team[0]), generator=g) + 0.5
+    w0 = torch.rand((batch_size, team[0]), generator=g) + 0.5
     ref, w, rounds = O.kink_fixed_point(w0, lambda w: update_reference(qnet, target, batch, w, torch.float64, mix),
                                         lambda ref: near_kink(qnet, batch, ref, mix))
     share = float((w == 0).any(1).double().mean())
@@ -398,17 +448,18 @@ def try_seed(team, mix, seed):
 
 
 @functools.lru_cache(maxsize=None)
-def stepped_case(team, mix):
+def stepped_case(team, mix, batch_size=B):
     """One update from learner_case's network with a target that is NOT the network (each parameter plus 0.05 randn), STEP_KW, double Q
     and Huber delta = 1, on the CPU -> a namespace of the starting state, the row weights after the kink filter, ref and yard
     (update_reference in float64 and float32), stats (ref64's) and e_stats (the float32 yardstick's own error over 9 row orders)."""
-    c = try_seed(team, mix, STEP_SEEDS.get((team, mix), 0))[0]
-    assert c is not None, (team, mix)
+    c = try_seed(team, mix, step_seed(team, mix, batch_size), batch_size)[0]
+    assert c is not None, (team, mix, batch_size)
+    c.B = batch_size
     kw = STEP_KW
     head = dict(gamma=kw["gamma"], q_scale=kw["q_scale"], delta=kw["huber_delta"], double=True, mix=mix)
     c.yard = update_reference(c.qnet, c.target, c.batch, c.w, torch.float32, mix)
     c.stats = ref64(c.ref["inp"], **head)["stats"]
-    c.e_stats = Y.own_error(lambda order: torch_head(c.yard["inp"], torch.float32, perm=order, **head), dict(stats=c.stats), B)[0]
+    c.e_stats = Y.own_error(lambda order: torch_head(c.yard["inp"], torch.float32, perm=order, **head), dict(stats=c.stats), batch_size)[0]
     return c
 
 
@@ -485,14 +536,14 @@ def step_arrays(x):
     return dict(p=AU.net_arrays(x.qnet), m=cut(x.adam.m), v=cut(x.adam.v), target=AU.net_arrays(x.target_qnet))
 
 
-def learner_and_hand(team, prioritized=False, rows=None, seed=0, **kw):
+def learner_and_hand(team, prioritized=False, rows=None, seed=0, batch_size=B, **kw):
     """(a DQNLearner, a Hand) of a team on two rings of the same rows and seed, each with its own copy of learner_case's network."""
     from deep_rl_battlespace_amd import learner as L
-    qnet, case_rows, _ = learner_case(team, seed)
+    qnet, case_rows, _ = learner_case(team, seed, batch_size)
     rows = case_rows if rows is None else rows
     kw = {**KW, **kw}
-    return (L.DQNLearner(O.ring(rows, B, prioritized=prioritized), O.gpu_copy(qnet), **kw),
-            Hand(O.ring(rows, B, prioritized=prioritized), O.gpu_copy(qnet), **kw))
+    return (L.DQNLearner(O.ring(rows, batch_size, prioritized=prioritized), O.gpu_copy(qnet), **kw),
+            Hand(O.ring(rows, batch_size, prioritized=prioritized), O.gpu_copy(qnet), **kw))
 
 
 # ------------------------------------------------------------------------------------------------ the bandit

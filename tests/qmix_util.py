@@ -9,6 +9,7 @@ offpolicy_util.py and yardstick_util.py:
   torch_mix, torch_loss, torch_head   the mix and the QMIX loss as a torch user writes them; autograd from the two networks' tanh rows:
                      in float64 the check of the restatement (g4 = d loss / d y4, gh = d loss / d hy), in float32 the statistics' yardstick
   head_inputs, corner_inputs, HEAD_SHAPES, FORMS   the head suite's inputs, the rows built to hit the contract's corners, its case table
+  LARGE_SHAPES, PLANS, LARGE_FORMS, MORE_FORMS, head_cases   the shapes at which a workgroup takes J = 2 or 3 tiles, with the plan each must get
   guarded_head, guarded_inputs   learner.qmix_head / qmix_inputs with every array between guard slabs
   TEAMS, FLOAT64_TEAMS, learner_case, update_reference, near_kink, try_seed, stepped_case   a whole update on the CPU in float64 (the
                      reference) and float32 (the yardstick): autograd through both StackedActors, offpolicy_util.first_step per network
@@ -46,6 +47,17 @@ MAX_AGENTS = 4
 HEAD_SHAPES = ((1, 1, 4), (5, 3, 8), (257, 2, 8), (300, 4, 16))
 # (double, huber delta, weighted)
 FORMS = tuple((dbl, delta, w) for dbl in (True, False) for delta in (0.0, DELTA) for w in (True, False))
+# The smallest shapes at which a workgroup takes J > 1 tiles (bsx_ddpg_shared.h: plan_of(B, 1), one thread per batch row: tiles of TILE
+# rows, at most MAX_BLOCKS workgroups), (B, nA, embed) -> (tiles, J, workgroups): J = 2 at every embed -- one live thread in the last
+# workgroup and one tile past `tiles` --, and J = 3, which tells blockIdx * J from a hard-coded 2.  The widest rows are (262145, 2, 16)'s:
+# Mh = 17 members, an hy of 71 MB.  LARGE_FORMS run at every large shape, MORE_FORMS as well at (262145, 3, 8): every template bit takes
+# both values
+TILE, MAX_BLOCKS = Q.TILE, Q.MAX_BLOCKS
+LARGE_SHAPES = ((262145, 1, 4), (262145, 3, 8), (262145, 2, 16), (524289, 1, 4))
+PLANS = {(262145, 1, 4): (1025, 2, 513), (262145, 3, 8): (1025, 2, 513), (262145, 2, 16): (1025, 2, 513), (524289, 1, 4): (2049, 3, 683)}
+LARGE_FORMS = ((True, DELTA, True), (False, 0.0, False))
+MORE_FORMS = {(262145, 3, 8): ((True, 0.0, False), (False, DELTA, True))}
+LARGE_PERMS = Q.LARGE_PERMS         # the yardstick's row orders beside the given one at the LARGE_SHAPES (8 elsewhere)
 OUTS = ("g4", "gh", "q", "td")
 argmax4, same_bits_or_nan = Q.argmax4, Q.same_bits_or_nan
 
@@ -57,6 +69,15 @@ def shape_id(s):
 def form_id(form):
     dbl, delta, w = form
     return "%s-%s-%s" % ("double" if dbl else "single", "huber" if delta else "mse", "weighted" if w else "plain")
+
+
+def head_cases():
+    """[(shape, form)] of the head suite: every form at HEAD_SHAPES, LARGE_FORMS and MORE_FORMS at LARGE_SHAPES."""
+    return [(s, f) for s in HEAD_SHAPES for f in FORMS] + [(s, f) for s in LARGE_SHAPES for f in LARGE_FORMS + MORE_FORMS.get(s, ())]
+
+
+def head_case_id(c):
+    return shape_id(c[0]) + "-" + form_id(c[1])
 
 
 def members(nA, embed):
@@ -361,15 +382,22 @@ def head_case(shape, form, perms=8):
     return inp, ref, Y.own_error(lambda order: torch_head(inp, torch.float32, embed, perm=order, **_kw(form)), ref, B, perms)[0]
 
 
+def head_case_of(shape, form):
+    """head_case of a shape of the head suite: at the LARGE_SHAPES with LARGE_PERMS and not kept (one test reads each; a case holds up
+    to 400 MB)."""
+    return head_case.__wrapped__(shape, form, LARGE_PERMS) if shape in LARGE_SHAPES else head_case(shape, form)
+
+
 def stats_out_of_bounds(got, ref, e_stats, what=""):
     """n and the mean of `over` (a count: exact in float64) exactly; the others by yardstick_util.scalar_bound."""
     exact = [name for i, name in ((0, "n"), (5, "done")) if got[i] != ref[i]]
     return exact + Y.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, what)
 
 
-def guarded_head(inp, embed, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, fill=7.0, td=True):
+def guarded_head(inp, embed, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, fill=7.0, td=True, keep=None):
     """learner.qmix_head on `inp` with every input, output and the workspace between guard slabs (guarded) and every output float starting
-    as `fill` -> (the binding's result: the `out` tensors themselves, the strays)."""
+    as `fill` -> (the binding's result: the `out` tensors themselves, the strays).  keep: a dict that receives the workspace (int64, every
+    word -1 before the call) as [workgroups, 8] partial rows."""
     from deep_rl_battlespace_amd import learner as L
     from guard_util import Buffers
     dbl, delta, w = form
@@ -385,6 +413,8 @@ def guarded_head(inp, embed, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, 
                       weight=dev["weight"] if w else None, out=out, workspace=ws)
     torch.cuda.synchronize()
     assert all(a is b for a, b in zip(res, out))
+    if keep is not None:
+        keep["workspace"] = ws.view(-1, 8)
     return res, G.stray()
 
 
@@ -429,12 +459,12 @@ def make_mixer(nA, Do, embed, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
-def learner_case(team, seed=0):
-    """(qnet, mixer, ring rows (N = 4 B; the act rows are score rows), idx of the first batch) of a team.  Read-only."""
+def learner_case(team, seed=0, batch_size=B):
+    """(qnet, mixer, ring rows (N = 4 batch_size; the act rows are score rows), idx of the first batch) of a team.  Read-only."""
     nA, Do, embed = team
     seed += CASE_SEED
-    rows = D.ring_rows(4 * B, nA, Do, 4, seed)
-    idx = torch.randint(0, 4 * B, (B,), generator=torch.Generator().manual_seed(9500 + seed))
+    rows = D.ring_rows(4 * batch_size, nA, Do, 4, seed)
+    idx = torch.randint(0, 4 * batch_size, (batch_size,), generator=torch.Generator().manual_seed(9500 + seed))
     return Q.make_qnet(nA, Do, seed), make_mixer(nA, Do, embed, seed), rows, idx
 
 
@@ -501,14 +531,14 @@ def near_kink(nets, batch, ref, embed, kw=None):
     return torch.from_numpy(np.repeat(near[:, None], nA, 1))
 
 
-def try_seed(team, seed):
+def try_seed(team, seed, batch_size=B):
     """(the case or None where it does not qualify, share of rows left out, zeroing rounds, the smallest arg-max margin over ALL rows)."""
     nA, Do, embed = team
-    qnet, mixer, rows, idx = learner_case(team, seed)
+    qnet, mixer, rows, idx = learner_case(team, seed, batch_size)
     g = torch.Generator().manual_seed(9700 + seed)
     nets = (qnet, mixer, D.perturbed(qnet, g), D.perturbed(mixer, g))
     batch = tuple(r[idx] for r in rows)
-    w0 = (torch.rand((B, 1), generator=g) + 0.5).expand(-1, nA).contiguous()
+    w0 = (torch.rand((batch_size, 1), generator=g) + 0.5).expand(-1, nA).contiguous()
     ref, w, rounds = O.kink_fixed_point(w0, lambda w: update_reference(nets, batch, w, torch.float64, embed),
                                         lambda ref: near_kink(nets, batch, ref, embed))
     share = float((w == 0).any(1).double().mean())
@@ -521,17 +551,19 @@ def try_seed(team, seed):
 
 
 @functools.lru_cache(maxsize=None)
-def stepped_case(team):
+def stepped_case(team, batch_size=B):
     """One update from learner_case's networks with targets that are NOT the networks (each parameter plus 0.05 randn), STEP_KW, double Q
     and Huber delta = 1, on the CPU -> a namespace of the starting state, the row weights after the kink filter, ref and yard
-    (update_reference in float64 and float32), stats (ref64's) and e_stats (the float32 yardstick's own error over 9 row orders)."""
-    c = try_seed(team, STEP_SEEDS.get(team, 0))[0]
-    assert c is not None, team
+    (update_reference in float64 and float32), stats (ref64's) and e_stats (the float32 yardstick's own error over 9 row orders).
+    STEP_SEEDS' entry is the team's at B, (team, batch_size)'s elsewhere."""
+    c = try_seed(team, STEP_SEEDS.get(team if batch_size == B else (team, batch_size), 0), batch_size)[0]
+    assert c is not None, (team, batch_size)
+    c.B = batch_size
     kw = STEP_KW
     head = dict(gamma=kw["gamma"], q_scale=kw["q_scale"], delta=kw["huber_delta"], double=True)
     c.yard = update_reference(c.nets, c.batch, c.w, torch.float32, c.embed)
     c.stats = ref64(c.ref["inp"], c.embed, **head)["stats"]
-    c.e_stats = Y.own_error(lambda order: torch_head(c.yard["inp"], torch.float32, c.embed, perm=order, **head), dict(stats=c.stats), B)[0]
+    c.e_stats = Y.own_error(lambda order: torch_head(c.yard["inp"], torch.float32, c.embed, perm=order, **head), dict(stats=c.stats), batch_size)[0]
     return c
 
 
@@ -619,14 +651,14 @@ def step_arrays(x, which):
     return dict(p=AU.net_arrays(net), m=cut(state.m), v=cut(state.v), target=AU.net_arrays(getattr(x, "target_" + which)))
 
 
-def learner_and_hand(team, prioritized=False, rows=None, seed=0, **kw):
+def learner_and_hand(team, prioritized=False, rows=None, seed=0, batch_size=B, **kw):
     """(a QMIXLearner, a Hand) of a team on two rings of the same rows and seed, each with its own copies of learner_case's networks."""
     from deep_rl_battlespace_amd import learner as L
-    qnet, mixer, case_rows, _ = learner_case(team, seed)
+    qnet, mixer, case_rows, _ = learner_case(team, seed, batch_size)
     rows = case_rows if rows is None else rows
     kw = {**KW, "embed": team[2], **kw}
-    return (L.QMIXLearner(O.ring(rows, B, prioritized=prioritized), O.gpu_copy(qnet), O.gpu_copy(mixer), **kw),
-            Hand(O.ring(rows, B, prioritized=prioritized), O.gpu_copy(qnet), O.gpu_copy(mixer), **kw))
+    return (L.QMIXLearner(O.ring(rows, batch_size, prioritized=prioritized), O.gpu_copy(qnet), O.gpu_copy(mixer), **kw),
+            Hand(O.ring(rows, batch_size, prioritized=prioritized), O.gpu_copy(qnet), O.gpu_copy(mixer), **kw))
 
 
 # ------------------------------------------------------------------------------------------------ the pay-off VDN cannot fit

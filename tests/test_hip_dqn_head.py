@@ -1,7 +1,9 @@
 """The DQN head on the MI355X (csrc/bsx_dqn_head.hip: learner.dqn_head): g4, q and td BIT FOR BIT against the header's contract restated
 in numpy float32 (tests/dqn_util.py: contract32 -- every operation is specified, so the bar is exact), on clean inputs and on rows built
 to hit the contract's corners, for both mixes, double Q on and off, Huber off and delta = 1, weighted and plain; the statistics within
-yardstick_util.scalar_bound of float64; between guard slabs; the same bits on every call; td=None accepted."""
+yardstick_util.scalar_bound of float64; between guard slabs; the same bits on every call; td=None accepted.  The same at the shapes where a
+VDN row lies across two tiles or workgroups and where a workgroup takes two or three tiles (dqn_util.SPLIT_SHAPES, LARGE_SHAPES), with
+every partial row of the workspace written; and a split row's threads read across the tile edge, and their own row only."""
 import numpy as np
 import pytest
 import torch
@@ -21,16 +23,19 @@ def _kw(form):
     return dict(delta=delta, double=dbl, mix=mix, weight=w)
 
 
-@pytest.mark.parametrize("form", Q.FORMS, ids=Q.form_id)
-@pytest.mark.parametrize("BnA", Q.HEAD_SHAPES, **SHAPE_IDS)
+@pytest.mark.parametrize("BnA,form", Q.head_cases(), ids=[Q.head_case_id(c) for c in Q.head_cases()])
 def test_the_heads_outputs_are_the_contracts_bits_and_its_statistics_float64s_between_guard_slabs(BnA, form):
-    """Clean inputs.  Two fills: an output float that keeps both was not written; the two calls leave the same bits."""
-    inp, ref, yard, e_stats = Q.head_case(*BnA, form)
+    """Clean inputs.  Two fills: an output float that keeps both was not written; the two calls leave the same bits.  Every partial row
+    of the workspace -- 513 or 683 of them at dqn_util.LARGE_SHAPES -- is written."""
+    inp, ref, yard, e_stats = Q.head_case_of(BnA, form)
     fills = []
     for fill in (7.0, -3.0):
-        res, stray = Q.guarded_head(inp, form, guarded=True, fill=fill)
+        kept = {}
+        res, stray = Q.guarded_head(inp, form, guarded=True, fill=fill, keep=kept)
         assert not stray, stray
         fills.append([t.clone() for t in res])
+        ws = kept["workspace"]
+        assert ws.shape[0] == Q.PLANS.get(BnA, (0, 0, ws.shape[0]))[2] and not bool((ws == -1).any())      # the -1 fill is gone from every row
     assert O.same_bits(*fills)
     want = Q.contract32(inp, **_kw(form))
     for k in OUTS:
@@ -44,8 +49,7 @@ def test_the_heads_outputs_are_the_contracts_bits_and_its_statistics_float64s_be
         assert all(np.array_equal(_bits(getattr(res, k)), np.repeat(_bits(getattr(res, k))[:, :1], BnA[1], 1)) for k in ("q", "td"))
 
 
-@pytest.mark.parametrize("form", Q.FORMS, ids=Q.form_id)
-@pytest.mark.parametrize("BnA", Q.HEAD_SHAPES, **SHAPE_IDS)
+@pytest.mark.parametrize("BnA,form", Q.head_cases(), ids=[Q.head_case_id(c) for c in Q.head_cases()])
 def test_on_the_corner_rows_the_heads_outputs_are_the_contracts_bits(BnA, form):
     """dqn_util.corner_inputs: ties in act, y_next and y_cur (the first maximum wins), a NaN in a score row (it counts as the maximum),
     done rows whose next values are NaN or infinite (they stay out), a NaN d under Huber, |d| exactly delta, VDN rows where one agent is
@@ -72,6 +76,49 @@ def test_on_the_corner_rows_the_heads_outputs_are_the_contracts_bits(BnA, form):
     if BnA[0] >= len(Q.CORNERS):
         st = res.stats.cpu().numpy()
         assert st[0] == BnA[0] * BnA[1] and np.isnan(st[1]) and np.isfinite(st[5:]).all()        # the NaN d reaches the loss, not the counts
+
+
+@pytest.mark.parametrize("BnA", (Q.SPLIT_SHAPES[0], Q.LARGE_SHAPES[0]), **SHAPE_IDS)
+def test_a_thread_of_a_split_vdn_row_reads_across_the_tile_edge_and_its_own_row_only(BnA):
+    """VDN, weighted, double Q, Huber, at (171, 3) -- three workgroups of one tile -- and (87382, 3) -- two tiles per workgroup.  Row 85
+    is elements 255 .. 257: its first in tile 0, the others in tile 1 (at the larger shape the same workgroup's second tile); row 170 is
+    510 .. 512 and lies across two workgroups at both shapes.  With NaN in every input of the rows that lie wholly in tile 0 (y_cur, rew,
+    weight) every other row keeps its bits, rows 85 and 86 included: a thread of tile 1 starts at its own row.  With NaN in ONE element
+    of a split row, an element of the LATER tile, q and td are NaN in all three columns of that row -- the column the earlier tile owns
+    included -- and every other row keeps its bits: a thread reads across the edge, and its own row only."""
+    B, nA = BnA
+    form = ("vdn", True, Q.DELTA, True)
+    inp = Q.head_inputs(B, nA)
+    split = Q.split_rows(B, nA)
+    assert nA == 3 and split[:2].tolist() == [85, 170] and (85 * nA) // Q.TILE == 0 and (85 * nA + 1) // Q.TILE == 1
+    assert (170 * nA + 1) // Q.TILE == 1 and (170 * nA + 2) // Q.TILE == 2
+    base, _ = Q.guarded_head(inp, form)
+    got = lambda res: {k: getattr(res, k).cpu().numpy() for k in OUTS}            # noqa: E731
+    want = got(base)
+    assert all(np.isfinite(v).all() for v in want.values())
+
+    def poisoned(rows, cols):
+        out = {k: v.clone() for k, v in inp.items()}
+        for k in ("y_cur", "rew", "weight"):
+            out[k][rows, cols] = O.NAN
+        return out
+
+    whole = torch.arange(85)                                                        # the rows that lie wholly in tile 0: elements 0 .. 254
+    res, stray = Q.guarded_head(poisoned(whole, slice(None)), form, guarded=True)
+    assert not stray, stray
+    for k, v in got(res).items():
+        assert np.array_equal(v[85:].view(np.int32), want[k][85:].view(np.int32)), k
+        assert np.isnan(v[:85]).reshape(85, -1).any(1).all(), k
+    for row, col in ((85, 1), (170, 2)):                                            # elements 256 and 512: the first of tiles 1 and 2
+        assert (row * nA + col) % Q.TILE == 0
+        res, stray = Q.guarded_head(poisoned(row, col), form, guarded=True)
+        assert not stray, stray
+        out = got(res)
+        others = np.arange(B) != row
+        for k in OUTS:
+            assert np.array_equal(out[k][others].view(np.int32), want[k][others].view(np.int32)), (k, row)
+        assert np.isnan(out["q"][row]).all() and np.isnan(out["td"][row]).all(), row
+        assert np.isnan(out["g4"][row]).sum() == nA and np.isnan(out["g4"][row]).any(-1).all(), row     # one column per agent, the earlier tile's too
 
 
 @pytest.mark.parametrize("form", (Q.FORMS[0], Q.FORMS[3], Q.FORMS[10], Q.FORMS[13]), ids=Q.form_id)

@@ -3,7 +3,8 @@ Hand), for both mixes, on a plain and on a prioritised ring; a whole update from
 float64, the float32 torch composition as the yardstick; a captured update runs nothing, replays the eager updates bit for bit -- a
 prioritised ring of 4 096 rows with its leaves, tree and max_priority included -- and allocates nothing; set_lr is seen by a replay;
 sync() after an outside edit; publish() writes only its rows; the constructor's refusals; and a bandit on which the learner must find
-the paying arm and end at its torch twin's loss."""
+the paying arm and end at its torch twin's loss.  The by-hand, float64 and capture tests also run the 3v3 team at B = 171, where the head
+has three tiles and VDN rows lie across two of them."""
 import numpy as np
 import pytest
 import torch
@@ -15,21 +16,22 @@ import yardstick_util as Y
 
 pytestmark = pytest.mark.gpu
 
-TEAM_IDS = dict(ids=lambda t: Q.team_id(t))
-# (team, mix, prioritised, double): every team with both mixes; single Q and the prioritised ring at the ends of the table
-HAND_CASES = [(t, m, False, True) for t in Q.TEAMS for m in Q.MIXES] + [(Q.TEAMS[1], "vdn", True, True), (Q.TEAMS[3], "independent", True, True),
-                                                                        (Q.TEAMS[1], "independent", False, False), (Q.TEAMS[2], "vdn", True, False)]
+# (team, mix, prioritised, double, batch): every team with both mixes; single Q and the prioritised ring at the ends of the table; the
+# 3v3 team at B = 171: three tiles in the head, the VDN rows 85 and 170 split between two of them (dqn_util.SPLIT_SHAPES)
+HAND_CASES = [(t, m, False, True, Q.B) for t in Q.TEAMS for m in Q.MIXES] + \
+    [(Q.TEAMS[1], "vdn", True, True, Q.B), (Q.TEAMS[3], "independent", True, True, Q.B), (Q.TEAMS[1], "independent", False, False, Q.B),
+     (Q.TEAMS[2], "vdn", True, False, Q.B), (Q.TEAMS[2], "vdn", True, True, Q.B_SPLIT), (Q.TEAMS[2], "independent", False, True, Q.B_SPLIT)]
 
 
 def _case_id(c):
-    team, mix, prio, dbl = c
-    return Q.team_id(team, mix) + ("-prioritised" if prio else "") + ("" if dbl else "-single")
+    team, mix, prio, dbl, batch = c
+    return Q.team_id(team, mix) + ("-prioritised" if prio else "") + ("" if dbl else "-single") + ("" if batch == Q.B else "-B%d" % batch)
 
 
 @pytest.mark.parametrize("case", HAND_CASES, ids=_case_id)
 def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(case):
-    team, mix, prio, dbl = case
-    learner, hand = Q.learner_and_hand(team, prio, mix=mix, double=dbl, updates=2)
+    team, mix, prio, dbl, batch = case
+    learner, hand = Q.learner_and_hand(team, prio, batch_size=batch, mix=mix, double=dbl, updates=2)
     start = Q.snapshot(learner)
     assert O.differing(start, Q.snapshot(hand)) == []
     for call in range(2):
@@ -37,7 +39,8 @@ def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(
         hand.update()
         a, b = Q.snapshot(learner), Q.snapshot(hand)
         assert O.differing(a, b) == [], (call, O.differing(a, b))
-        assert stats is learner.stats and stats.shape == (2, 8) and float(stats[1, 0]) == Q.B * team[0]
+        assert stats is learner.stats and stats.shape == (2, 8) and float(stats[1, 0]) == batch * team[0]
+        assert learner.td.shape == (batch, team[0])
         assert torch.equal(learner.td.view(torch.int32), hand.td.view(torch.int32)) and torch.equal(learner.q.view(torch.int32), hand.q.view(torch.int32))
     assert int(learner.step) == 4 == int(learner.buffer._draws) and torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
     moved = set(O.differing(start, a))
@@ -53,26 +56,25 @@ def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(
         assert not learner._y_on.any()                                              # without double Q the second online forward is skipped
 
 
-@pytest.mark.parametrize("mix", Q.MIXES)
-@pytest.mark.parametrize("team", Q.TEAMS, **TEAM_IDS)
-def test_a_whole_update_with_a_distinct_target_against_float64(team, mix):
+@pytest.mark.parametrize("team,mix,batch", Q.STEP_CASES, ids=[Q.team_id(*c) for c in Q.STEP_CASES])
+def test_a_whole_update_with_a_distinct_target_against_float64(team, mix, batch):
     """One whole update through the primitives (Hand.one, dqn_util.STEP_KW: double Q, Huber delta = 1) from a target network that is NOT
     the network, against dqn_util.stepped_case's float64 reference with the same computation in float32 on the CPU as the yardstick:
     the gradient row, the step and the Polyak target -- each pooled over its ten tensors, ddpg_util.check_step's bars: the project's
     (2, 4), no wider factor -- and the statistics.  Rows near a kink carry no weight (tests/test_dqn_cpu.py holds the case to its cap).
     BSX_DQN_RATIOS_OUT names a file the measured ratios are appended to (profiles/dqn_float64.json keeps them)."""
     from deep_rl_battlespace_amd import learner as L
-    c = Q.stepped_case(team, mix)
+    c = Q.stepped_case(team, mix, batch)
     assert c.share <= Q.KINK_CAP
     kw = {k: v for k, v in Q.STEP_KW.items()}
-    hand = Q.Hand(O.ring(c.rows, Q.B), O.gpu_copy(c.qnet), mix=mix, double=True, updates=1, **kw)
+    hand = Q.Hand(O.ring(c.rows, batch), O.gpu_copy(c.qnet), mix=mix, double=True, updates=1, **kw)
     with torch.no_grad():
         for p in D.PARAMS:
             getattr(hand.target_qnet, p).copy_(getattr(c.target, p))
         hand.target_qnet.pack(out=hand._blob_tq)
     row = hand.one(*O.sample_is(hand, c.idx, c.batch), 0, weight=c.w.cuda())
     torch.cuda.synchronize()
-    sid, rec = Q.team_id(team, mix), {}
+    sid, rec = Q.team_id(team, mix, batch), {}
     print("DQN", sid)
     got = O.grad_arrays(row, 4)
     tens = lambda g: {"g": [g[p] for p in D.PARAMS]}                                # noqa: E731
@@ -92,14 +94,16 @@ def _prio_rows(N=4096, team=Q.TEAMS[1]):
     return D.ring_rows(N, team[0], team[1], 4, 77)
 
 
-@pytest.mark.parametrize("mix,prio", [("independent", False), ("vdn", False), ("independent", True), ("vdn", True)],
-                         ids=["independent", "vdn", "independent-prioritised-4096", "vdn-prioritised-4096"])
-def test_a_captured_update_runs_nothing_replays_the_eager_updates_bit_for_bit_and_allocates_nothing(mix, prio):
+@pytest.mark.parametrize("mix,prio,team,batch", [("independent", False, Q.TEAMS[1], Q.B), ("vdn", False, Q.TEAMS[1], Q.B),
+                                                 ("independent", True, Q.TEAMS[1], Q.B), ("vdn", True, Q.TEAMS[1], Q.B),
+                                                 ("vdn", True, Q.TEAMS[2], Q.B_SPLIT)],
+                         ids=["independent", "vdn", "independent-prioritised-4096", "vdn-prioritised-4096", "vdn-prioritised-4096-nA3-B171"])
+def test_a_captured_update_runs_nothing_replays_the_eager_updates_bit_for_bit_and_allocates_nothing(mix, prio, team, batch):
     """Four replays against four eager calls: parameters, targets, moments, blobs, statistics, the draw counter and, on the prioritised
-    ring of 4 096 rows, leaves, tree and max_priority, exact after every one; capture() undoes its warm-up."""
-    team = Q.TEAMS[1]
-    rows = _prio_rows() if prio else None
-    (captured, _), (eager, _) = (Q.learner_and_hand(team, prio, rows=rows, mix=mix, updates=2) for _ in range(2))
+    ring of 4 096 rows, leaves, tree and max_priority, exact after every one; capture() undoes its warm-up.  The last case is the 3v3
+    team at B = 171: a head of three tiles with split VDN rows inside the graph."""
+    rows = _prio_rows(team=team) if prio else None
+    (captured, _), (eager, _) = (Q.learner_and_hand(team, prio, rows=rows, batch_size=batch, mix=mix, updates=2) for _ in range(2))
     state = [t.detach().clone() for t in captured._state()]
     O.capture_runs_nothing(captured, Q.snapshot)
     assert all(torch.equal(a.view(torch.uint8), b.detach().view(torch.uint8)) for a, b in zip(state, captured._state()))

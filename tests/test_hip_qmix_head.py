@@ -2,7 +2,8 @@
 contract restated in numpy float32 (tests/qmix_util.py: contract32 -- every operation is specified, so the bar is exact), on clean inputs
 and on rows built to hit the contract's corners, for every embed, double Q on and off, Huber off and delta = 1, weighted and plain; the
 statistics within yardstick_util.scalar_bound of float64; between guard slabs; the same bits on every call; td=None accepted;
-qmix_inputs as bit copies."""
+qmix_inputs as bit copies.  The same at the shapes where a workgroup takes two or three tiles (qmix_util.LARGE_SHAPES), at every embed,
+with every partial row of the workspace written."""
 import numpy as np
 import pytest
 import torch
@@ -13,20 +14,22 @@ import qmix_util as X
 pytestmark = pytest.mark.gpu
 
 _bits = O.bits
-SHAPE_IDS = dict(ids=X.shape_id)
 
 
-@pytest.mark.parametrize("form", X.FORMS, ids=X.form_id)
-@pytest.mark.parametrize("shape", X.HEAD_SHAPES, **SHAPE_IDS)
+@pytest.mark.parametrize("shape,form", X.head_cases(), ids=[X.head_case_id(c) for c in X.head_cases()])
 def test_the_heads_outputs_are_the_contracts_bits_and_its_statistics_float64s_between_guard_slabs(shape, form):
-    """Clean inputs.  Two fills: an output float that keeps both was not written; the two calls leave the same bits."""
+    """Clean inputs.  Two fills: an output float that keeps both was not written; the two calls leave the same bits.  Every partial row
+    of the workspace -- 513 or 683 of them at qmix_util.LARGE_SHAPES -- is written."""
     B, nA, embed = shape
-    inp, ref, e_stats = X.head_case(shape, form)
+    inp, ref, e_stats = X.head_case_of(shape, form)
     fills = []
     for fill in (7.0, -3.0):
-        res, stray = X.guarded_head(inp, embed, form, guarded=True, fill=fill)
+        kept = {}
+        res, stray = X.guarded_head(inp, embed, form, guarded=True, fill=fill, keep=kept)
         assert not stray, stray
         fills.append([t.clone() for t in res])
+        ws = kept["workspace"]
+        assert ws.shape[0] == X.PLANS.get(shape, (0, 0, ws.shape[0]))[2] and not bool((ws == -1).any())    # the -1 fill is gone from every row
     assert O.same_bits(*fills)
     want = X.contract32(inp, embed, **X._kw(form))
     for k in X.OUTS:
@@ -40,8 +43,7 @@ def test_the_heads_outputs_are_the_contracts_bits_and_its_statistics_float64s_be
     assert all(np.array_equal(_bits(getattr(res, k)), np.repeat(_bits(getattr(res, k))[:, :1], nA, 1)) for k in ("q", "td"))
 
 
-@pytest.mark.parametrize("form", X.FORMS, ids=X.form_id)
-@pytest.mark.parametrize("shape", X.HEAD_SHAPES, **SHAPE_IDS)
+@pytest.mark.parametrize("shape,form", X.head_cases(), ids=[X.head_case_id(c) for c in X.head_cases()])
 def test_on_the_corner_rows_the_heads_outputs_are_the_contracts_bits(shape, form):
     """qmix_util.corner_inputs: ties and a NaN in act, a finished team whose next rows are NaN or infinite (they stay out), ONE plane
     finished, |d| exactly delta, pre exactly 0 and far below 0 (inputs beyond [-1, 1]), hypernet values +0 and -0, a NaN d under Huber,

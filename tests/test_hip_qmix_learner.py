@@ -1,6 +1,7 @@
 """QMIXLearner on the MI355X: an update is, bit for bit, the sequence of the public primitives written out by hand (tests/qmix_util.py:
-Hand) at every team up to (4, 14, embed 16), on a plain and on a prioritised ring; a whole update from target networks that are not the
-networks against float64, the float32 torch composition as the yardstick, pooled per network; a captured update runs nothing, replays
+Hand) at every team up to (4, 14, embed 16), on a plain and on a prioritised ring, and at B = 257 and 300, two tiles in the head; a
+whole update from target networks that are not the networks against float64, the float32 torch composition as the yardstick, pooled per
+network; a captured update runs nothing, replays
 the eager updates bit for bit -- a prioritised ring of 4 096 rows with its leaves, tree and max_priority included -- and allocates
 nothing; set_lr is seen by a replay; sync() re-packs four blobs; publish() writes the Q network alone; and the one-step game an additive
 mix cannot fit, which the learner must fit below half the additive floor and as well as its torch twin."""
@@ -19,20 +20,21 @@ import yardstick_util as Y
 pytestmark = pytest.mark.gpu
 
 TEAM_IDS = dict(ids=X.team_id)
-# (team, prioritised, double): every team; single Q and the prioritised ring at the ends of the table
-HAND_CASES = [(t, False, True) for t in X.TEAMS] + [(X.TEAMS[1], True, True), (X.TEAMS[3], True, True), (X.TEAMS[1], False, False),
-                                                    (X.TEAMS[2], True, False)]
+# (team, prioritised, double, batch): every team; single Q and the prioritised ring at the ends of the table; two tiles in the head
+# inside a whole update at B = 257 and B = 300, the second at the widest mixer
+HAND_CASES = [(t, False, True, X.B) for t in X.TEAMS] + [(X.TEAMS[1], True, True, X.B), (X.TEAMS[3], True, True, X.B), (X.TEAMS[1], False, False, X.B),
+                                                         (X.TEAMS[2], True, False, X.B), (X.TEAMS[2], True, True, 257), (X.TEAMS[3], False, True, 300)]
 
 
 def _case_id(c):
-    team, prio, dbl = c
-    return X.team_id(team) + ("-prioritised" if prio else "") + ("" if dbl else "-single")
+    team, prio, dbl, batch = c
+    return X.team_id(team) + ("-prioritised" if prio else "") + ("" if dbl else "-single") + ("" if batch == X.B else "-B%d" % batch)
 
 
 @pytest.mark.parametrize("case", HAND_CASES, ids=_case_id)
 def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(case):
-    team, prio, dbl = case
-    learner, hand = X.learner_and_hand(team, prio, double=dbl, updates=2)
+    team, prio, dbl, batch = case
+    learner, hand = X.learner_and_hand(team, prio, batch_size=batch, double=dbl, updates=2)
     start = X.snapshot(learner)
     assert O.differing(start, X.snapshot(hand)) == []
     for call in range(2):
@@ -40,7 +42,7 @@ def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(
         hand.update()
         a, b = X.snapshot(learner), X.snapshot(hand)
         assert O.differing(a, b) == [], (call, O.differing(a, b))
-        assert stats is learner.stats and stats.shape == (2, 8) and float(stats[1, 0]) == X.B
+        assert stats is learner.stats and stats.shape == (2, 8) and float(stats[1, 0]) == batch
         assert torch.equal(learner.td.view(torch.int32), hand.td.view(torch.int32)) and torch.equal(learner.q.view(torch.int32), hand.q.view(torch.int32))
     assert int(learner.step) == 4 == int(learner.step_mixer) == int(learner.buffer._draws) and torch.equal(learner.buffer.last_idx, hand.buffer.last_idx)
     moved = set(O.differing(start, a))
@@ -54,7 +56,7 @@ def test_an_update_is_the_by_hand_sequence_of_the_public_primitives_bit_for_bit(
     assert [float(x) for x in learner.step_stats[:, 0]] == [3.0, 4.0] == [float(x) for x in learner.step_stats_mixer[:, 0]]
     assert 0.0 <= float(learner.stats[1, 5]) < 1.0 and 0.0 <= float(learner.stats[1, 7]) <= 1.0
     assert torch.equal(learner.td, learner.td[:, :1].expand_as(learner.td)) and torch.equal(learner.q, learner.q[:, :1].expand_as(learner.q))
-    assert learner.members == X.members(team[0], team[2]) == learner.mixer.n_actors and learner._x_cur.shape == (X.B, learner.members, team[0] * team[1])
+    assert learner.members == X.members(team[0], team[2]) == learner.mixer.n_actors and learner._x_cur.shape == (batch, learner.members, team[0] * team[1])
     if not dbl:
         assert not learner._y_on.any()                                              # without double Q the second online forward is skipped
 

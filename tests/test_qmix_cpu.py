@@ -91,6 +91,31 @@ def test_members_and_the_workspace():
     assert lib.bsx_qmix_head_workspace_bytes(10, 2, None) == ARG
 
 
+def test_the_large_head_shapes_get_the_plans_they_are_chosen_for():
+    """qmix_util.PLANS on host arithmetic alone: per shape the workspace holds one partial row of 64 bytes per workgroup and a workgroup
+    takes J = ceil(tiles / workgroups) tiles of 256 batch rows; J = 2 runs at every embed and J = 3 once; one live thread in the last
+    tile; the forms give every template bit both values; the widest hy is the issue's 71 MB."""
+    from deep_rl_battlespace_amd import learner
+    assert set(X.PLANS) == set(X.LARGE_SHAPES) and not set(X.PLANS) & set(X.HEAD_SHAPES)
+    for (B, nA, embed), (tiles, J, groups) in X.PLANS.items():
+        nbytes = learner.qmix_head_workspace_bytes(B, nA)
+        assert nbytes % 64 == 0 and nbytes // 64 == groups, (B, nA, embed)
+        assert tiles == -(-B // X.TILE) and -(-tiles // groups) == J == -(-tiles // X.MAX_BLOCKS), (B, nA, embed)
+        assert B - (tiles - 1) * X.TILE == 1 and groups * J >= tiles
+        print("B%d-nA%d-E%d: %d tiles, J = %d, %d workgroups, Mh = %d" % (B, nA, embed, tiles, J, groups, X.members(nA, embed)))
+    assert {s[2] for s in X.LARGE_SHAPES if X.PLANS[s][1] == 2} == set(X.EMBEDS) and sorted({p[1] for p in X.PLANS.values()}) == [2, 3]
+    assert all(-(-s[0] // X.TILE) <= X.MAX_BLOCKS for s in X.HEAD_SHAPES)           # what the older shapes never reach: J = 1
+    assert [X.members(*s[1:]) for s in X.LARGE_SHAPES] == [4, 11, 17, 4]
+    assert max(s[0] * X.members(*s[1:]) * 16 for s in X.LARGE_SHAPES) == 262145 * 17 * 16 < 72e6
+    for shape in X.LARGE_SHAPES:
+        forms = X.LARGE_FORMS + X.MORE_FORMS.get(shape, ())
+        assert set(forms) <= set(X.FORMS) and len(set(forms)) == len(forms)
+        for bit in range(3):
+            assert len({bool(f[bit]) for f in forms}) == 2, (shape, bit)
+    assert set(X.MORE_FORMS) == {(262145, 3, 8)} and len({f for f in X.LARGE_FORMS + X.MORE_FORMS[(262145, 3, 8)]}) == 4
+    assert len(X.head_cases()) == len({X.head_case_id(c) for c in X.head_cases()}) == 4 * 8 + 4 * 2 + 2
+
+
 def test_the_entries_refuse_what_the_header_documents_before_any_launch_in_its_order():
     """Fake addresses only: every call is refused before anything reaches HIP."""
     L = _L()

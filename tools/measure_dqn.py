@@ -16,7 +16,7 @@ ring, blocks and statistics); medians, ranges and spreads per way.  The launches
 here: the figures are what the profile records.
 
 profiles/dqn_float64.json: what tests/test_dqn_cpu.py and test_hip_dqn_learner.py read beside their code:
-  stepped   the whole-update cases (dqn_util.stepped_case), all on the CPU: per (team, mix) the seed -- the first from 0 at which the
+  stepped   the whole-update cases (dqn_util.STEP_CASES, stepped_case), all on the CPU: per (team, mix, batch) the seed -- the first from 0 at which the
             float64 reference alone qualifies --, every seed tried, the share of rows the kink filter leaves out, its zeroing rounds and
             the smallest arg-max margin.  --ratios: a file of JSON lines the GPU test appended under BSX_DQN_RATIOS_OUT, kept as "kernel"
   bandit    the learning check's configuration and what its torch composition reaches at the candidates 100 .. 400 on the CPU: the
@@ -41,18 +41,17 @@ def float64_profile(argv):
     import offpolicy_util as O
     old = json.load(open(Q.PROFILE)) if os.path.exists(Q.PROFILE) else {}
     cases = {}
-    for team in Q.TEAMS:
-        for mix in Q.MIXES:
-            tried, seed = [], 0
-            while True:
-                c, share, rounds, low = Q.try_seed(team, mix, seed)
-                tried.append([seed, c is not None, round(100 * share, 2), rounds, float("%.3e" % low)])
-                if c is not None:
-                    break
-                seed += 1
-            assert seed == Q.STEP_SEEDS.get((team, mix), 0), (team, mix, seed)
-            cases[Q.team_id(team, mix)] = dict(seed=seed, left_out_percent=round(100 * c.share, 2), zeroing_rounds=c.rounds,
-                                               smallest_argmax_margin=float("%.3e" % c.margin), seeds_tried=tried)
+    for team, mix, batch in Q.STEP_CASES:
+        tried, seed = [], 0
+        while True:
+            c, share, rounds, low = Q.try_seed(team, mix, seed, batch)
+            tried.append([seed, c is not None, round(100 * share, 2), rounds, float("%.3e" % low)])
+            if c is not None:
+                break
+            seed += 1
+        assert seed == Q.step_seed(team, mix, batch), (team, mix, batch, seed)
+        cases[Q.team_id(team, mix, batch)] = dict(seed=seed, left_out_percent=round(100 * c.share, 2), zeroing_rounds=c.rounds,
+                                                  smallest_argmax_margin=float("%.3e" % c.margin), seeds_tried=tried)
     stepped = dict(what="tests/dqn_util.py stepped_case: one whole DQN update (double Q, Huber delta = 1, q_scale = 4) from a target network "
                         "that is not the network, eps = 1e-3, float64 on the CPU; the float32 yardstick is the same in float32",
                    seeds="per (team, mix) the first seed from 0 at which, on the float64 reference alone, the kink filter closes within 4 "
