@@ -23,6 +23,8 @@ ACT_I32, ACT_LOGITS_F32 = 0, 1
 ACT_F32, ACT_F64, ACT_F32X4 = 0, 1, 2
 PRIO_FANOUT, PRIO_ONE, PRIO_SALT = 64, 65536, 0x3C6EF372
 SAC_SALT = 0x60000000
+EPS_SALT = 0x20000000
+EPS_LINEAR, EPS_EXP = 0, 1
 QMIX_MAX_AGENTS, QMIX_EMBEDS = 4, (4, 8, 16)
 WINNER_NAMES = ("none", "red", "blue", "tie")
 
@@ -41,7 +43,7 @@ class BsxActorNoise(ctypes.Structure):
                 ("ou_sigma", ctypes.c_float), ("ou_mu", ctypes.c_float), ("ou_state", ctypes.c_void_p),
                 ("env_done", ctypes.c_void_p), ("z_inject", ctypes.c_void_p), ("ou_keep", ctypes.c_int),
                 ("sample_mode", ctypes.c_int), ("temperature", ctypes.c_float), ("logp", ctypes.c_void_p), ("u_inject", ctypes.c_void_p),
-                ("value_weights", ctypes.c_void_p), ("value", ctypes.c_void_p)]
+                ("value_weights", ctypes.c_void_p), ("value", ctypes.c_void_p), ("epsilon", ctypes.c_void_p), ("explored", ctypes.c_void_p)]
 
 
 class BsxGaussianHead(ctypes.Structure):
@@ -184,6 +186,7 @@ SIGNATURES = {
                                   c_void_p, c_int64, c_void_p]),
     "bsx_actor_forward_gaussian": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(BsxActorNoise),
                                            ctypes.POINTER(BsxGaussianHead), c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
+    "bsx_epsilon_advance": (c_int, [c_void_p, c_int, c_void_p, c_int64, ctypes.c_double, ctypes.c_double, c_int64, c_int, c_void_p]),
     "bsx_actor_grad_floats": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "bsx_actor_grad_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_actor_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -68,6 +68,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_dqn_head.hip"), ["-ffp-contract=off"]),
            # the QMIX head: the monotone mix, its TD target and both networks' grad_out, every operation rounded on its own (tests/qmix_util.py)
            (os.path.join(CSRC, "bsx_qmix_head.hip"), ["-ffp-contract=off"]),
+           # the epsilon-greedy schedule: binary64, every operation rounded on its own, as tests/epsilon_util.py restates the linear kind
+           (os.path.join(CSRC, "bsx_explore.hip"), ["-ffp-contract=off"]),
            # the keyed row permutation and the minibatch gather: integer arithmetic and bit copies
            (os.path.join(CSRC, "bsx_shuffle.hip"), [])]
 

@@ -88,10 +88,13 @@ static int actor_forward(const float* weights, const float* obs, float* scores, 
         if (nz.gaussian_std > 0.f || nz.ou_scale > 0.f || nz.sample_mode != 0 || nz.u_inject || nz.logp) return BSX_E_ARG;
         if (!aligned(head->log_std, 4) || (head->logp && !aligned(head->logp, 4))) return BSX_E_ALIGN;
     }
+    // epsilon-greedy replaces the exploration noise and both stochastic heads; the record of its draws needs it
+    if (nz.epsilon ? (nz.gaussian_std > 0.f || nz.ou_scale > 0.f || nz.sample_mode != 0 || gauss) : nz.explored != nullptr) return BSX_E_ARG;
     if (nz.ou_scale > 0.f && (!nz.ou_state || !aligned(nz.ou_state, 16))) return nz.ou_state ? BSX_E_ALIGN : BSX_E_ARG;
     if (nz.z_inject && !aligned(nz.z_inject, 16)) return BSX_E_ALIGN;
     if (nz.sample_mode != 0 && (nz.sample_mode != 1 || !(nz.temperature > 0.f))) return BSX_E_ARG;
-    if ((nz.u_inject && !aligned(nz.u_inject, 16)) || (nz.logp && !aligned(nz.logp, 4)) || (nz.value_weights && !aligned(nz.value_weights, 16))) return BSX_E_ALIGN;
+    if ((nz.u_inject && !aligned(nz.u_inject, 16)) || (nz.logp && !aligned(nz.logp, 4)) || (nz.value_weights && !aligned(nz.value_weights, 16)) ||
+        (nz.epsilon && !aligned(nz.epsilon, 4))) return BSX_E_ALIGN;
     if (nz.value_weights && (!nz.value || !aligned(nz.value, 4))) return nz.value ? BSX_E_ALIGN : BSX_E_ARG;
     if (env_offset < 0) return BSX_E_ARG;
     const int A = 2 * n, D = 3 * n + 2;

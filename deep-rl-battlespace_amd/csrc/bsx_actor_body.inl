@@ -123,7 +123,7 @@
         r4 = finish_row<true>(r4, b3, p.nz, p.seed, seq, row, uint64_t(p.env_offset) * uint64_t(p.A) + row, false, e < p.E, row,
                               gh.log_std + 3 * a, gh.logp);
     else
-        r4 = finish_row(r4, b3, p.nz, p.seed, seq, row, uint64_t(p.env_offset) * uint64_t(p.A) + row, game_over, e < p.E, row);
+        r4 = finish_row(r4, b3, p.nz, p.seed, seq, row, uint64_t(p.env_offset) * uint64_t(p.A) + row, game_over, e < p.E, row, nullptr, nullptr, a);
     if (e < p.E) reinterpret_cast<float4*>(p.scores)[row] = r4;
     if (p.nz.value_weights) {
         // ---- the value head: a second MLP of the same shape on the same rows, in the same precision mode (per-tile code of

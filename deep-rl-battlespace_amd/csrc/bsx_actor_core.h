@@ -112,6 +112,8 @@ __device__ inline float4 uniforms4(uint64_t seed, uint64_t seq, uint64_t grow, u
 // OU increment), 0x80000000 (the white term beside OU), 0x40000000 (the categorical head's uniforms).
 constexpr uint32_t GAUSS_SALT = 0xC0000000u;
 constexpr float HALF_LOG_2PI = 0.91893853320467274f;   // log(2 pi) / 2
+// The salt of the epsilon-greedy uniforms (nz.epsilon), distinct from the four above.
+constexpr uint32_t EPS_SALT = 0x20000000u;
 
 // tanh of the head sums + bias, exploration noise, clamp (maddpg/networks.py:85, maddpg/agent.py:30-31) for ONE row.
 // `row` indexes this launch's arrays (OU state, injected normals); `grow` = the job-wide row (env_offset + e)*A + a keys the
@@ -125,10 +127,16 @@ constexpr float HALF_LOG_2PI = 0.91893853320467274f;   // log(2 pi) / 2
 // row's plane's three values, read here, late), a = mu + sigma * z with z = columns 0..2 of the injected normals or of normals4 under
 // GAUSS_SALT; the row goes out UNCLIPPED with column 3 = 0, and log N(a; mu, sigma) summed over the three columns goes to logp[orow]
 // (nullable).  No tanh-squash correction: the clip to [-1, 1] belongs to the env's step (battle_env.py:295-297), not to the policy.
-template <bool GAUSS = false, class NZ>   // NZ: BsxActorNoise, in whatever address space the caller holds it (the fused kernels read it from the kernarg segment)
+// Epsilon-greedy (nz.epsilon non-null; discrete rows only, excludes the noise terms and the categorical head -- the launchers see to it):
+// u = uniforms4 under EPS_SALT (or the injected row); the row of plane `plane` explores iff u.x < epsilon[plane] -- u lies strictly inside
+// (0, 1), so epsilon <= 0 never explores, epsilon >= 1 always does, and a NaN compares false: greedy.  The random action is
+// int(u.y * 4.0f) = the top two bits of the 23-bit code, exact; an exploring row goes out as the +-1 row that bsx_instinct.h's
+// one_hot_scores writes for that action (the step's argmax4 plays it, the DQN / QMIX heads replay it), a greedy row as it stands.
+// explored[orow] (nullable) = 1 / 0 for every stored row.  The Philox block is drawn only when epsilon is set.
+template <bool GAUSS = false, bool EPS = true, class NZ>   // EPS = false: a continuous-action caller, the epsilon branch compiled out.  NZ: BsxActorNoise, in whatever address space the caller holds it (the fused kernels read it from the kernarg segment)
 __device__ inline float4 finish_row(float4 r4, const float4 b3, const NZ& nz, uint64_t seed, uint64_t seq,
                                     size_t row, uint64_t grow, bool game_over, bool store, size_t orow,
-                                    const float* log_std = nullptr, float* logp = nullptr) {
+                                    const float* log_std = nullptr, float* logp = nullptr, int plane = 0) {
     // No implicit contraction in here: the stand-alone actor kernel and the fused rollout must produce the same bits, and which
     // multiply the back end would fuse into which add depends on the code around the call.  Every fused operation is spelled out.
 #pragma clang fp contract(off)
@@ -178,6 +186,15 @@ __device__ inline float4 finish_row(float4 r4, const float4 b3, const NZ& nz, ui
         if (store && nz.logp) nz.logp[orow] = za - lse;
         (void)am;
         r4 = pr;
+    }
+    if constexpr (EPS) if (nz.epsilon) {
+        const float4 u = nz.u_inject ? reinterpret_cast<const float4*>(nz.u_inject)[row] : uniforms4(seed, seq, grow, EPS_SALT);
+        const bool explore = u.x < nz.epsilon[plane];
+        if (explore) {
+            const int ra = int(u.y * 4.0f);
+            r4 = make_float4(ra == 0 ? 1.f : -1.f, ra == 1 ? 1.f : -1.f, ra == 2 ? 1.f : -1.f, ra == 3 ? 1.f : -1.f);
+        }
+        if (store && nz.explored) nz.explored[orow] = explore ? 1 : 0;
     }
     return r4;
 }

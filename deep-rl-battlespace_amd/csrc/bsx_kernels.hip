@@ -428,10 +428,12 @@ int rollout(void* state, int64_t E, int n, int T, const float* weights, int prec
         if (nz.gaussian_std > 0.f || nz.ou_scale > 0.f || nz.sample_mode != 0 || nz.u_inject || nz.logp) return BSX_E_ARG;
         if (!aligned(head->log_std, 4) || (head->logp && !aligned(head->logp, 4))) return BSX_E_ALIGN;
     }
+    // epsilon-greedy belongs to discrete actions and replaces the exploration noise and both stochastic heads; the record of its draws needs it
+    if (nz.epsilon ? (nz.gaussian_std > 0.f || nz.ou_scale > 0.f || nz.sample_mode != 0 || CONT || gauss) : nz.explored != nullptr) return BSX_E_ARG;
     if (nz.ou_scale > 0.f && (!nz.ou_state || !aligned(nz.ou_state, 16))) return nz.ou_state ? BSX_E_ALIGN : BSX_E_ARG;
     if (nz.z_inject || nz.u_inject) return BSX_E_ARG;    // injected draws are per call: bsx_actor_forward only
     if (nz.sample_mode != 0 && (nz.sample_mode != 1 || !(nz.temperature > 0.f) || CONT)) return BSX_E_ARG;   // a categorical head belongs to discrete actions
-    if ((nz.logp && !aligned(nz.logp, 4)) || (nz.value_weights && !aligned(nz.value_weights, 16))) return BSX_E_ALIGN;
+    if ((nz.logp && !aligned(nz.logp, 4)) || (nz.value_weights && !aligned(nz.value_weights, 16)) || (nz.epsilon && !aligned(nz.epsilon, 4))) return BSX_E_ALIGN;
     if (nz.value_weights && (n != 1 || !nz.value || !aligned(nz.value, 4))) return BSX_E_ARG;          // the value head rides in the 1v1 kernel only
     if (!family_claim(state, CONT)) return BSX_E_FAMILY;
     const int64_t EA = E * 2 * n, D = 3 * n + 2;

@@ -60,12 +60,12 @@
                 r4 = bsx_actor::finish_row<true>(r4, b3, p.nz, p.aseed, aseq, row, uint64_t(p.env_offset) * uint64_t(A) + row, false, row_ok,
                                                  size_t(tk) * size_t(E_) * size_t(A) + row, p.gh.log_std + 3 * mine_c, p.gh.logp);
             } else {
-                r4 = bsx_actor::finish_row(r4, b3, p.nz, p.aseed, aseq, row, uint64_t(p.env_offset) * uint64_t(A) + row, game_over, row_ok,
-                                           size_t(tk) * size_t(E_) * size_t(A) + row);
+                r4 = bsx_actor::finish_row<false, false>(r4, b3, p.nz, p.aseed, aseq, row, uint64_t(p.env_offset) * uint64_t(A) + row, game_over, row_ok,
+                                                         size_t(tk) * size_t(E_) * size_t(A) + row);
             }
         } else {
             r4 = bsx_actor::finish_row(r4, b3, p.nz, p.aseed, aseq, row, uint64_t(p.env_offset) * uint64_t(A) + row, game_over, row_ok,
-                                       size_t(tk) * size_t(E_) * size_t(A) + row);
+                                       size_t(tk) * size_t(E_) * size_t(A) + row, nullptr, nullptr, mine_c);
         }
         if constexpr (N == 1) {
             if (p.nz.value_weights) {

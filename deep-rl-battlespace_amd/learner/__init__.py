@@ -12,6 +12,7 @@
               the rollout plays (csrc/bsx_dqn_head.hip)
   qmix.py     QMIX for the discrete game: the monotone mixing head between the Q network and a hypernetwork the fused MLP kernels already take,
               and QMIXLearner (csrc/bsx_qmix_head.hip)
+              (both learn from what a PolicyRollout(epsilon=...) plays: annealed epsilon-greedy is the rollout's, rollout.EpsilonSchedule)
   _common.py  what more than one of them uses: the hyper-parameter ranges, the stream, the capture of an update as one graph
 
 A PPO minibatch:  [minibatch_gather] -> bsx_actor_forward with the value head -> ppo_head -> bsx_mlp_grad of the actor, of the critic -> adam_step.

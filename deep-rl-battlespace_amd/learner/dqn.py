@@ -81,8 +81,10 @@ class DQNLearner(_RingLearner):
     The Q network is the network the rollout plays and Q_i(o, a) = q_scale * tanh-row[i][a]: bsx_mlp_forward is the rollout's float32
     kernel and the step kernel takes its arg-max over the same tanh row, so the learner's greedy action and the published rollout's
     action are the same bits, ties and saturation included.  Q is bounded by q_scale: choose q_scale >= r_max / (1 - gamma); a target
-    beyond q_scale cannot be reached (the tanh saturates and the gradient fades).  Exploration is the rollout's: noise_std, ou_scale, or
-    sample="categorical" with a temperature on the PolicyRollout that plays the published network; there is no epsilon-greedy path.
+    beyond q_scale cannot be reached (the tanh saturates and the gradient fades).  The behaviour policy is the rollout's: the
+    algorithm's own is annealed epsilon-greedy, PolicyRollout(epsilon=EpsilonSchedule(start, end, steps)) on the rollout that plays the
+    published network (a random row goes out one-hot, and the head replays it like any other); noise_std, ou_scale or
+    sample="categorical" with a temperature remain.
 
     One update, on the current stream, with cached buffers and no host synchronisation:
        1. buffer.sample()                                          the batch, drawn on the device

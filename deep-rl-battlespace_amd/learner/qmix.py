@@ -146,7 +146,8 @@ class QMIXLearner(_RingLearner):
     The Q network is DQNLearner's: Q_i(o, a) = q_scale * tanh-row[i][a], the learner's greedy action and the published rollout's action
     the same bits.  The mixer is a StackedActor(Mh, nA Do, 4), Mh = qmix_members(nA, embed) (one is made if none is given): its tanh
     rows are the mix's weights in tanh units, so |Q_tot| <= q_scale (1 + embed); choose q_scale >= r_max / (1 - gamma) as for DQN.
-    Execution stays decentralised: publish() copies the Q network alone.  Limits: nA <= 4, nA Do <= 64 (4v4: 56), embed 4, 8 or 16.
+    Execution stays decentralised: publish() copies the Q network alone.  The behaviour policy is the rollout's, as for DQN:
+    PolicyRollout(epsilon=EpsilonSchedule(start, end, steps)) is the paper's annealed epsilon-greedy.  Limits: nA <= 4, nA Do <= 64 (4v4: 56), embed 4, 8 or 16.
 
     One update, on the current stream, with cached buffers and no host synchronisation:
        1. buffer.sample()                                          the batch, drawn on the device

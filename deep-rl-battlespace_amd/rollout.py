@@ -158,17 +158,40 @@ class FusedActor:
     def refresh(self):
         self.actor.pack(out=self.weights)
 
-    def noise_struct(self, E, noise_std=0.0, ou=None, z=None, sample=None, value=None):
+    def noise_struct(self, E, noise_std=0.0, ou=None, z=None, sample=None, value=None, epsilon=None):
         """BsxActorNoise for E games (None = nothing to say); validates the OU state tensor.  z: optional float32 [E, A, 4] standard
         normals to use instead of the in-kernel draws (parity runs against the reference's np.random.randn values).
         sample: dict(temperature[, logp, u]) -- categorical policy head: the action is drawn from softmax(scores / temperature)
         (Gumbel-max; the score rows that go out are the perturbed ones), `logp` a float32 tensor ([E, A], or [T, E, A] for a one-launch
         rollout) that receives the drawn action's log-probability, `u` float32 [E, A, 4] uniforms to use instead of the draws (tests).
         value: dict(weights, out) -- a value head: `weights` the packed blob of a StackedActor with ONE output per agent, `out` a
-        float32 tensor ([E, A] / [T, E, A]) that receives V(obs)."""
-        if not (noise_std > 0.0 or ou is not None or sample is not None or value is not None):
+        float32 tensor ([E, A] / [T, E, A]) that receives V(obs).
+        epsilon: dict(value[, explored, u]) -- epsilon-greedy exploration (discrete actors; excludes noise_std, ou and sample): `value` a
+        contiguous float32 [A] device tensor, the per-plane exploration rates, read by the kernel at every launch (kept by reference: an
+        in-place update is seen by the next replay of a captured graph); `explored` a uint8 tensor ([E, A], or [T, E, A] for a one-launch
+        rollout) that receives 1 where the played action was the random one; `u` float32 [E, A, 4] uniforms to use instead of the draws
+        (tests)."""
+        if not (noise_std > 0.0 or ou is not None or sample is not None or value is not None or epsilon is not None):
             return None
         nz = _lib.BsxActorNoise(float(noise_std), 0.0, 0.15, 0.2, 0.0, None, None, None, 0, 0, 0.0, None, None, None, None)
+        if epsilon is not None:
+            if self.actor.n_actions != 4:
+                raise ValueError("epsilon-greedy exploration needs a discrete-action actor (4 action scores)")
+            if noise_std > 0.0 or ou is not None or sample is not None:
+                raise ValueError("epsilon-greedy exploration excludes exploration noise (noise_std, ou) and the categorical head (sample)")
+            ev, ex, u = epsilon["value"], epsilon.get("explored"), epsilon.get("u")
+            if (not isinstance(ev, torch.Tensor) or ev.dtype != torch.float32 or not ev.is_contiguous() or tuple(ev.shape) != (2 * self.n,)
+                    or ev.device != self.weights.device):
+                raise ValueError("epsilon['value'] must be a contiguous float32 [A] tensor on the actor's device")
+            nz.epsilon = ev.data_ptr()
+            if ex is not None:
+                if ex.dtype != torch.uint8 or not ex.is_contiguous() or tuple(ex.shape[-2:]) != (E, 2 * self.n):
+                    raise ValueError("epsilon['explored'] must be a contiguous uint8 [.., E, A] tensor")
+                nz.explored = ex.data_ptr()
+            if u is not None:
+                if u.dtype != torch.float32 or tuple(u.shape) != (E, 2 * self.n, 4) or not u.is_contiguous():
+                    raise ValueError("epsilon['u'] must be a contiguous float32 [E, A, 4] tensor")
+                nz.u_inject = u.data_ptr()
         if sample is not None:
             nz.sample_mode, nz.temperature = 1, float(sample.get("temperature", 1.0))
             if not nz.temperature > 0.0:
@@ -223,7 +246,7 @@ class FusedActor:
         return _lib.BsxGaussianHead(ls.data_ptr(), lp.data_ptr() if lp is not None else None)
 
     def forward_into(self, obs, scores, noise_std=0.0, seq=None, seq_base=None, ou=None, z=None, sample=None, value=None, games=None,
-                     gaussian=None):
+                     gaussian=None, epsilon=None):
         """obs f32 [E, A, D] (contiguous) -> scores f32 [E, A, 4] (contiguous, 16-byte aligned), on the current stream.
         noise_std: Gaussian exploration noise.  ou: optional dict(scale, state[, theta, sigma, mu, env_done]) for the
         reference's Ornstein-Uhlenbeck noise (utils/noise.py): `state` is a float32 [E, A, 4] tensor updated in place,
@@ -232,21 +255,25 @@ class FusedActor:
         games: (first, count) = evaluate only that range of the games (every tensor still the full one; the noise is keyed by the
         global row, so the draws are those of the full call).
         gaussian: dict(log_std[, logp]) -- the Gaussian policy head (head_struct; continuous actors): `scores` receives the unclipped draws
-        a = mu + exp(log_std) * z, column 3 = 0; `z` (if given) supplies the normals of columns 0..2 instead of the in-kernel draws."""
+        a = mu + exp(log_std) * z, column 3 = 0; `z` (if given) supplies the normals of columns 0..2 instead of the in-kernel draws.
+        epsilon: dict(value[, explored, u]) -- epsilon-greedy exploration (noise_struct; discrete actors): a row explores with probability
+        value[a] and then goes out as the one-hot row of a uniformly drawn action; `explored` records which rows did."""
         off = self.env_offset
         if games is not None:
             sl = slice(int(games[0]), int(games[0]) + int(games[1]))
             cut = lambda d, keys: None if d is None else dict(d, **{k: d[k][sl] for k in keys if d.get(k) is not None})   # noqa: E731
             obs, scores, z = obs[sl], scores[sl], (z[sl] if z is not None else None)
             ou, sample, value = cut(ou, ("state", "env_done")), cut(sample, ("logp", "u")), cut(value, ("out",))
-            gaussian = cut(gaussian, ("logp",))
+            gaussian, epsilon = cut(gaussian, ("logp",)), cut(epsilon, ("explored", "u"))
             off += int(games[0])
         E = obs.shape[0]
         if seq is None:
             self.seq += 1
             seq = self.seq
+        if gaussian is not None and epsilon is not None:
+            raise ValueError("epsilon-greedy exploration is for discrete actions: the Gaussian policy head excludes it")
         head = self.head_struct(E, gaussian, noise_std, ou, sample) if gaussian is not None else None
-        nz = self.noise_struct(E, noise_std, ou, z, sample, value)
+        nz = self.noise_struct(E, noise_std, ou, z, sample, value, epsilon)
         if head is not None and nz is None and z is not None:       # the head's injected normals with no other noise field
             if z.dtype != torch.float32 or tuple(z.shape) != (E, 2 * self.n, 4) or not z.is_contiguous():
                 raise ValueError("z must be a contiguous float32 [E, A, 4] tensor")
@@ -284,6 +311,56 @@ def gaussian_log_prob(actor, log_std, obs, actions, fused=False):
     return logp, entropy
 
 
+class EpsilonSchedule:
+    """The annealed exploration rate of an epsilon-greedy behaviour policy (DQN, VDN, QMIX), kept on the device:
+
+        sched = EpsilonSchedule(1.0, 0.05, steps=50_000)                  # linear from 1.0 to 0.05 over 50 000 ticks
+        ro = PolicyRollout(env, actor, T=32, epsilon=sched)               # ro.epsilon is sched.value
+
+    `value` (float32 [A], every plane the same rate; created by PolicyRollout, or by bind()) is what the actor kernels read; `count`
+    (int64 [1]) is how far the schedule has moved.  advance(by) is one small kernel, bsx_epsilon_advance, with no host synchronisation:
+    count += by, then value = end + (start - end) * max(0, 1 - count / steps) (kind="linear") or end + (start - end) * exp(-count / steps)
+    (kind="exponential"), in float64, rounded once to float32.  PolicyRollout calls advance(T) (unit="ticks"; unit="rollouts": advance(1))
+    at the end of every run, inside the captured graph, so the rate a run plays with is the one set by the runs before it and replays
+    anneal with no host work.  reset(count) re-seeds it."""
+
+    KINDS = {"linear": _lib.EPS_LINEAR, "exponential": _lib.EPS_EXP}
+
+    def __init__(self, start, end, steps, kind="linear", unit="ticks"):
+        self.start, self.end, self.steps = float(start), float(end), int(steps)
+        if not (0.0 <= self.start <= 1.0 and 0.0 <= self.end <= 1.0):
+            raise ValueError("start and end must lie in [0, 1]")
+        if self.steps < 1:
+            raise ValueError("steps must be >= 1")
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {sorted(self.KINDS)}")
+        if unit not in ("ticks", "rollouts"):
+            raise ValueError("unit must be 'ticks' or 'rollouts'")
+        self.kind, self.unit = kind, unit
+        self.value, self.count = None, None
+
+    def bind(self, n_planes, device):
+        """Create `value` float32 [n_planes] and `count` on `device`, at count 0 (a schedule belongs to one rollout)."""
+        if self.value is not None:
+            raise ValueError("this EpsilonSchedule is already bound to a rollout")
+        self._lib = _lib.load()
+        self.value = torch.zeros(int(n_planes), dtype=torch.float32, device=device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=device)
+        return self.reset(0)
+
+    def advance(self, by=1):
+        """count += by and `value` rewritten from the new count, on the current stream (capturable)."""
+        _lib.check(self._lib.bsx_epsilon_advance(self.value.data_ptr(), self.value.numel(), self.count.data_ptr(), int(by), self.start, self.end,
+                                                 self.steps, self.KINDS[self.kind], torch.cuda.current_stream(self.value.device).cuda_stream),
+                   "bsx_epsilon_advance")
+        return self
+
+    def reset(self, count=0):
+        """Set the counter (in place: a captured graph goes on from there) and `value` to the schedule's rate at it."""
+        self.count.fill_(int(count))
+        return self.advance(0)
+
+
 class PolicyRollout:
     """T ticks of (actor -> step) for all games, captured once into a HIP graph and replayed.
 
@@ -306,6 +383,13 @@ class PolicyRollout:
     clips them to [-1, 1], as the reference's does), logp[t] = Normal(mu, sigma).log_prob(a).sum(-1) -- gaussian_log_prob() is its learner
     side.  Rows a scripted opponent plays carry logp 0.
 
+    Value-based learners (learner.DQNLearner, learner.QMIXLearner; a discrete env): epsilon= a float, a float32 [A] device tensor (kept by
+    reference) or an EpsilonSchedule makes the behaviour policy epsilon-greedy: with probability epsilon[a] a plane's row goes out as the
+    one-hot row of a uniformly drawn action, otherwise as the actor's.  ro.epsilon is the tensor the kernels read at every launch -- writing
+    it in place changes the next run() or replay with no re-capture --, ro.explored[t] (bool [E, A]) says which rows were random; a
+    scripted opponent's rows never are.  An EpsilonSchedule is advanced by T inside the run, where the noise keys move.  It replaces
+    noise_std, ou_scale and sample=.
+
     The env must be batched, rng='philox', discrete or continuous (4 or 3 actor outputs); auto_reset is recommended (finished games
     re-spawn in place).  Without auto_reset a finished game stays inert until the host re-spawns it between two runs:
     `ro.run(); env.reset(mask=finished); ro.start()` -- start() takes the observations, env_done and (with gae=) the done flags of every game
@@ -316,7 +400,8 @@ class PolicyRollout:
     kernel and restarted per game; then clamp(-1, 1) as maddpg/agent.py:31 does."""
 
     def __init__(self, env, actor, T, noise_std=0.0, fused=True, seed=0, opponent=None, ou_scale=0.0, one_launch=False,
-                 precision="f32", ou_restart=True, sample=None, temperature=1.0, value_actor=None, chains="auto", gae=None, log_std=None):
+                 precision="f32", ou_restart=True, sample=None, temperature=1.0, value_actor=None, chains="auto", gae=None, log_std=None,
+                 epsilon=None):
         """actor: a StackedActor.  fused=True evaluates it with the hand-written HIP kernel (FusedActor), False with
         torch ops (the fp32 reference of the same op).  opponent: an `instinct.Team` that plays its team's planes
         instead of the actor (the reference's training setup, main.py:119-122: learned red vs scripted blue): its
@@ -401,6 +486,26 @@ class PolicyRollout:
         self.log_std = log_std
         self.logp = torch.zeros((T, E, A), dtype=torch.float32, device=dev) if sample is not None else None
         self._sample = dict(temperature=float(temperature)) if sample == "categorical" else None
+        # epsilon=: epsilon-greedy exploration in the row finish of every fused discrete form (csrc/bsx_actor_core.h); the rates live in a
+        # device tensor that each launch reads, so a schedule -- or the caller -- moves them under a captured graph
+        self.epsilon, self.explored, self._explored, self._eps_schedule = None, None, None, None
+        if epsilon is not None:
+            if not fused or self.continuous:
+                raise ValueError("epsilon-greedy exploration needs the fused actor and a discrete env")
+            if sample is not None or self.noise_std > 0.0 or ou_scale > 0.0:
+                raise ValueError("epsilon-greedy exploration excludes sample=, noise_std and ou_scale")
+            if isinstance(epsilon, EpsilonSchedule):
+                self._eps_schedule = epsilon.bind(A, dev)
+                self.epsilon = epsilon.value
+            elif isinstance(epsilon, torch.Tensor):
+                if (epsilon.dtype != torch.float32 or not epsilon.is_contiguous() or tuple(epsilon.shape) != (A,)
+                        or epsilon.device != torch.device(dev)):
+                    raise ValueError("epsilon must be a float, an EpsilonSchedule or a contiguous float32 [A] tensor on the env's device")
+                self.epsilon = epsilon
+            else:
+                self.epsilon = torch.full((A,), float(epsilon), dtype=torch.float32, device=dev)
+            self._explored = torch.zeros((T, E, A), dtype=torch.uint8, device=dev)
+            self.explored = self._explored.view(torch.bool)
         self.value, self._value_w = None, None
         if value_actor is not None:
             if value_actor.n_actions != 1 or value_actor.n_actors != A or value_actor.obs_len != D:
@@ -466,8 +571,9 @@ class PolicyRollout:
             sample = dict(self._sample, logp=self.logp[t]) if self._sample is not None else None
             value = dict(weights=self._value_w, out=self.value[t]) if self._value_w is not None else None
             gaussian = dict(self._gauss, logp=self.logp[t]) if self._gauss is not None else None
+            epsilon = dict(value=self.epsilon, explored=self._explored[t]) if self.epsilon is not None else None
             self.fused.forward_into(self.obs[t], self.scores[t], self.noise_std, seq=t, seq_base=self._seq_base, ou=ou, sample=sample, value=value,
-                                    games=games, gaussian=gaussian)
+                                    games=games, gaussian=gaussian, epsilon=epsilon)
             if self._act64 is not None:
                 cols = slice(self.opponent._cols[0], self.opponent._cols[-1] + 1)   # a team's planes are adjacent columns (a slice: nothing is uploaded while capturing)
                 self._act64.copy_(self.scores[t][..., :3])
@@ -482,6 +588,8 @@ class PolicyRollout:
                 return
             if self.opponent is not None:
                 self.opponent.write_actions(out=self.scores[t], obs=self.obs[t])
+                if self.epsilon is not None:                                     # the actor's draws on the scripted rows were not played
+                    self._explored[t][:, self.opponent._cols[0]:self.opponent._cols[-1] + 1] = 0
             self.env._launch(self.scores[t].data_ptr(), self._kind, False, None,
                              self.obs[t + 1].data_ptr(), self.rew[t].data_ptr(), self._done[t].data_ptr(),
                              env_done_ptr=self.env_done[t + 1].data_ptr(), games=games)
@@ -534,7 +642,8 @@ class PolicyRollout:
         if self.one_launch:
             sample = dict(self._sample, logp=self.logp) if self._sample is not None else None
             value = dict(weights=self._value_w, out=self.value) if self._value_w is not None else None
-            nz = self.fused.noise_struct(self.env.n_envs, self.noise_std, self.ou, sample=sample, value=value)
+            epsilon = dict(value=self.epsilon, explored=self._explored) if self.epsilon is not None else None
+            nz = self.fused.noise_struct(self.env.n_envs, self.noise_std, self.ou, sample=sample, value=value, epsilon=epsilon)
             head = (self.fused.head_struct(self.env.n_envs, dict(self._gauss, logp=self.logp)) if self._gauss is not None else None)
             self.env._launch_rollout(self.T, self.fused.weights.data_ptr(), self.fused.precision,
                                      -1 if self.opponent is None else self.opponent.team, self.obs.data_ptr(), self.scores.data_ptr(),
@@ -557,6 +666,8 @@ class PolicyRollout:
             # env.reset(mask=...) seeds the carry with 0 for the re-spawned games and with the run's last flags for every other game
             self.env._done.copy_(self._done_prev)
         self._seq_base.add_(self.T)                    # fresh exploration-noise keys for the next run
+        if self._eps_schedule is not None:             # ... and the next run's exploration rate, on device
+            self._eps_schedule.advance(self.T if self._eps_schedule.unit == "ticks" else 1)
 
     def _advantages(self):
         """V(obs[T]) into last_value, then GAE over this run's records.  The value pass draws nothing (no noise, no sample, no OU state)

@@ -225,6 +225,19 @@ typedef struct BsxActorNoise {
                                  (head column 0 = the value, columns 1-3 zero); evaluated in the call's `precision` mode on the rows the actor reads */
     float* value;             /* float32 [E*A] (bsx_rollout_*: [T][E*A]), required with value_weights: V(obs) = head + bias, no tanh.
                                  bsx_rollout_* take a value head for n = 1 only (the per-tick form for any n). */
+    /* ---- epsilon-greedy exploration of a value-based learner's behaviour policy (DQN / VDN / QMIX), discrete actions only.  With
+     * `epsilon` set, every row an actor plays draws u = four uniforms (23 bits: (code + 0.5) * 2^-23, strictly inside (0, 1)) from Philox
+     * keyed like every other actor draw -- (seed, seq + *seq_base, job-wide row (env_offset + e)*A + a) -- under a salt of its own,
+     * 0x20000000 (u_inject replaces them, bsx_actor_forward only).  The row explores iff u.x < epsilon[a], a = the row's plane: epsilon <= 0
+     * never explores, epsilon >= 1 always does, a NaN compares false and stays greedy.  The random action is int(u.y * 4.0f) (exact: the
+     * top two bits of the code), and the exploring row is written as that action's one-hot +-1 row, as bsx_instinct_discrete writes the
+     * scripted opponent's: the step's arg-max plays it and bsx_dqn_head / bsx_qmix_head replay it.  A greedy row goes out as it does
+     * without epsilon, bit for bit.  Rows of a scripted team are not the actor's: neither their scores nor their `explored` are touched.
+     * epsilon excludes gaussian_std > 0, ou_scale > 0, sample_mode != 0, a continuous env and the Gaussian head (BSX_E_ARG); `explored`
+     * without `epsilon` is BSX_E_ARG; a misaligned `epsilon` BSX_E_ALIGN.  Both null: nothing changes. */
+    const float* epsilon;     /* nullable float32 [A], 4-byte aligned, device: per-plane exploration rate, read by every launch
+                                 (a captured graph sees in-place updates); constant across the T ticks of one bsx_rollout_* launch */
+    uint8_t* explored;        /* nullable uint8 [E*A] (bsx_rollout_*: [T][E*A]): 1 where the played action was the random one */
 } BsxActorNoise;
 /* precision of the 64 x 64 layer: exact float32 (an fmaf chain, bit for bit), or both operands split in two bf16 terms and
  * three bf16 matrix products accumulated in float32 (16x the matrix rate; loses about 20x float32's own rounding error on a head sum:
@@ -260,6 +273,17 @@ typedef struct BsxGaussianHead {
 int bsx_actor_forward_gaussian(const float* weights, const float* obs, float* scores, int64_t E, int n, int precision,
                                const BsxActorNoise* noise, const BsxGaussianHead* head, uint64_t seed, uint64_t seq,
                                const uint64_t* seq_base, int64_t env_offset, void* stream);
+
+/* The annealing schedule of BsxActorNoise.epsilon, on device: one small launch, no host synchronisation (capturable).
+ *   *count += by;  c = the NEW count;
+ *   kind 0 (linear):       eps = end + (start - end) * max(0, 1 - c / steps)
+ *   kind 1 (exponential):  eps = end + (start - end) * exp(-c / steps)
+ * in binary64, every operation rounded on its own, then rounded once to float32 and written to epsilon[0 .. A-1].
+ *   epsilon float32 [A] (4-byte aligned), count int64 (8-byte aligned), both on device.
+ * BSX_E_ARG: a null pointer, A < 1, steps < 1, an unknown kind, start or end outside [0, 1] (a NaN included); BSX_E_ALIGN. */
+#define BSX_EPS_LINEAR 0
+#define BSX_EPS_EXP 1
+int bsx_epsilon_advance(float* epsilon, int A, int64_t* count, int64_t by, double start, double end, int64_t steps, int kind, void* stream);
 
 /* The caller's rollout loop -- `for t in range(T): actions = actor(obs) (+ noise, clamp); obs, rew, done = step(actions)`
  * (main.py:177-181 with maddpg/agent.py:25-33) -- in ONE launch: T x (bsx_actor_forward -> bsx_step_discrete with
