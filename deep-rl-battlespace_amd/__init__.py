@@ -16,7 +16,9 @@ Only what the hot path needs lives here:
   advantage.py   GAE advantages / returns / per-agent mask of a rollout on device, for on-policy learners (csrc/bsx_advantage.hip)
   learner/       the on-device learners, one module per kernel family:
     mlp.py       the actor / value MLP as one fused forward and one fused backward for on-device learners (csrc/bsx_actor_grad.hip)
-    ppo.py       the PPO loss head between them and the minibatch update over a rollout's records, PPOLearner (csrc/bsx_ppo_head.hip)
+    ppo.py       the PPO loss head between them and the minibatch update over a rollout's records, PPOLearner (csrc/bsx_ppo_head.hip);
+                 joint_obs, the input rows of a centralised critic on the team's joint observation, which PPOLearner trains on a
+                 PolicyRollout(central_critic=): MAPPO (csrc/bsx_ppo_central.hip)
     adam.py      the fused clip + Adam + pack step that makes a whole update one graph, and its tied form for agents that share one
                  policy per team, and the same step for a network of any width with Polyak target networks kept in the same pass
                  (csrc/bsx_adam_step.hip)
@@ -44,6 +46,7 @@ from .learner import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGra
                       sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)
 from .learner import DQN_STATS, DQNLearner, DqnHead, dqn_head, dqn_head_workspace_bytes  # noqa: F401
 from .learner import QMIX_STATS, QMIXLearner, QmixHead, qmix_head, qmix_head_workspace_bytes, qmix_inputs, qmix_members  # noqa: F401
+from .learner import joint_obs, joint_width  # noqa: F401
 from .envs.battle_env import parallel_env  # noqa: F401
 from .replay import NStepAppender, PrioritizedReplayBuffer  # noqa: F401
 
@@ -53,4 +56,4 @@ __all__ = ["AdamState", "DDPGLearner", "Minibatch", "NStepAppender", "PPOLearner
            "SACLearner", "SAC_PI_STATS", "SAC_STATS", "SacHead", "SacPolicyGrad", "sac_head", "sac_head_workspace_bytes", "sac_policy_grad",
            "sac_policy_grad_workspace_bytes", "sac_policy_seed", "sac_sample_actions", "DQNLearner", "DQN_STATS", "DqnHead", "dqn_head",
            "dqn_head_workspace_bytes", "QMIXLearner", "QMIX_STATS", "QmixHead", "qmix_head", "qmix_head_workspace_bytes", "qmix_inputs",
-           "qmix_members"]
+           "qmix_members", "joint_obs", "joint_width"]

@@ -216,6 +216,7 @@ SIGNATURES = {
     "bsx_ppo_head_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_ppo_head": (c_int, [ctypes.POINTER(BsxPpoIo), c_int64, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                              ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "bsx_ppo_joint_obs": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "bsx_adam_step_workspace_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "bsx_adam_step": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_void_p, c_void_p, c_void_p]),
     "bsx_adam_step_shared": (c_int, [ctypes.POINTER(BsxAdamIo), c_int, c_int, c_void_p, c_void_p, c_void_p]),

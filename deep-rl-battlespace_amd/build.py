@@ -56,6 +56,8 @@ SOURCES = [(os.path.join(CSRC, "bsx_kernels.hip"), STEP_FLAGS),
            (os.path.join(CSRC, "bsx_advantage.hip"), ["-ffp-contract=off"]),
            # the PPO loss head: float32 element-wise terms held to a float64 reference, not to bits: contraction allowed
            (os.path.join(CSRC, "bsx_ppo_head.hip"), []),
+           # the centralised critic's input rows from the observation records: bit copies
+           (os.path.join(CSRC, "bsx_ppo_central.hip"), []),
            # the optimiser step (clip + Adam + pack): float32 element-wise, held to a float64 reference; the blob it packs is bit copies
            (os.path.join(CSRC, "bsx_adam_step.hip"), []),
            # between the MLP calls of a DDPG update: bit copies, and a TD head whose one multiply-add is an explicit fmaf

@@ -3,7 +3,8 @@
   mlp.py      the actor / value / Q MLP as ONE fused forward and ONE fused backward, its cached buffers and its one check (csrc/bsx_actor_grad.hip)
   adam.py     clip + Adam + pack as two launches: the actors' step, its tied form, the free-width form with Polyak targets (csrc/bsx_adam_step.hip)
   shuffle.py  a keyed row permutation and the gather of a shuffled minibatch (csrc/bsx_shuffle.hip)
-  ppo.py      the PPO loss head and PPOLearner, the update of a rollout's two networks (csrc/bsx_ppo_head.hip)
+  ppo.py      the PPO loss head and PPOLearner, the update of a rollout's two networks (csrc/bsx_ppo_head.hip); joint_obs, the input rows of
+              a centralised critic (MAPPO: csrc/bsx_ppo_central.hip), which PPOLearner trains on a PolicyRollout(central_critic=)
   ddpg.py     the critic join, TD head and action gradient, and DDPGLearner, the MADDPG update of a team from its ring (csrc/bsx_ddpg_head.hip)
   td3.py      target policy smoothing, the TD head of two critics, the second critic TD3Learner and SACLearner share, and TD3Learner: twin critics,
               a delayed actor and target step (csrc/bsx_td3_head.hip)
@@ -16,6 +17,8 @@
   _common.py  what more than one of them uses: the hyper-parameter ranges, the stream, the capture of an update as one graph
 
 A PPO minibatch:  [minibatch_gather] -> bsx_actor_forward with the value head -> ppo_head -> bsx_mlp_grad of the actor, of the critic -> adam_step.
+  central critic: [minibatch_gather] -> bsx_actor_forward, no value head -> joint_obs -> bsx_mlp_forward of the critic (raw = v) -> ppo_head ->
+                  bsx_mlp_grad of the actor on obs, of the critic on the joined rows -> adam_step of the actor, mlp_adam_step of the critic.
 A DDPG update:    buffer.sample -> ddpg_inputs -> target actor, ddpg_put_actions -> target critic, critic -> td_head -> bsx_mlp_grad, mlp_adam_step of the
                   critic -> actor, ddpg_put_actions -> bsx_mlp_grad of the critic for grad_x, ddpg_action_grad -> bsx_mlp_grad, mlp_adam_step of the actor.
 A TD3 update:     as DDPG's, with td3_smooth_actions in place of the first ddpg_put_actions, both target critics and both critics -> td3_head ->
@@ -39,7 +42,7 @@ from .adam import (ADAM_STATS, HYPER, AdamState, adam_hyper, adam_step, adam_ste
                    mlp_adam_step_workspace_bytes, share_group, tie_)
 from .ddpg import MAX_OBS, TD_STATS, DDPGLearner, TdHead, ddpg_action_grad, ddpg_inputs, ddpg_put_actions, td_head, td_head_workspace_bytes  # noqa: F401
 from .mlp import H, PARAMS, blob_floats, categorical_log_prob, fused_apply, fused_grad, fused_mlp, grad_floats, mlp_grad, split_grad  # noqa: F401
-from .ppo import KINDS, STATS, PPOLearner, PpoHead, ppo_head, ppo_head_workspace_bytes  # noqa: F401
+from .ppo import KINDS, STATS, PPOLearner, PpoHead, joint_obs, joint_width, ppo_head, ppo_head_workspace_bytes  # noqa: F401
 from .td3 import TD3_STATS, TD3Learner, Td3Head, td3_head, td3_head_workspace_bytes, td3_smooth_actions  # noqa: F401
 from .sac import (SAC_PI_STATS, SAC_STATS, SACLearner, SacHead, SacPolicyGrad, sac_head, sac_head_workspace_bytes, sac_policy_grad,  # noqa: F401
                   sac_policy_grad_workspace_bytes, sac_policy_seed, sac_sample_actions)

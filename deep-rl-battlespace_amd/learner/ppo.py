@@ -1,7 +1,9 @@
 """The PPO update on device (csrc/bsx_ppo_head.hip): the loss head between the fused forward and backward, and the learner around it.
 
   ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, ...)      from the forward's outputs and a rollout's records to both grad_out tensors, one pass
-  PPOLearner(rollout, ...)                                      the PPO update of a PolicyRollout's networks; device_step=True, capture(): one graph
+  joint_width(n, Do), joint_obs(obs)                            a centralised critic's input width and rows: own observation first, then the team-mates'
+  PPOLearner(rollout, ...)                                      the PPO update of a PolicyRollout's networks; device_step=True, capture(): one graph;
+                                                                on a PolicyRollout(central_critic=) it is MAPPO's: a critic on the team's joint observation
 """
 from collections import namedtuple
 from functools import partial
@@ -11,8 +13,9 @@ import torch
 from .. import _lib
 from .._args import _F32, _FLAG, _need, _workspace
 from ._common import _POSITIVE, _capture, _f32, _hyper, _stream
-from .adam import AdamState, adam_hyper, adam_step, adam_step_workspace_bytes, is_tied, share_group, tie_
-from .mlp import PARAMS, _actor_forward, _buffers, _check_mlp, _mlp_grad, split_grad
+from .adam import (AdamState, adam_hyper, adam_step, adam_step_workspace_bytes, is_tied, mlp_adam_step, mlp_adam_step_workspace_bytes, share_group,
+                   tie_)
+from .mlp import PARAMS, _actor_forward, _buffers, _check_mlp, _mlp_forward, _mlp_grad, split_grad
 from .shuffle import Minibatch, _word, minibatch_gather
 
 PpoHead = namedtuple("PpoHead", "g_pi g_v g_log_std stats")
@@ -86,6 +89,48 @@ def ppo_head(kind, y, v, rec, logp_old, adv, ret, mask, *, clip, c_v, c_e, tempe
     return PpoHead(g_pi, g_v, g_ls if k == 1 else None, stats)
 
 
+JOINT_MAX_N = 4
+
+
+def joint_width(n, Do=None):
+    """n * Do: the inputs of a centralised critic of a team of n planes (1 .. 4) whose observations have Do floats (None: the env's
+    3n + 2) -- 5, 16, 33 and 56 for 1v1 ... 4v4.  ValueError for another n, or a width the fused MLP kernels do not take (5v5: 85)."""
+    n = int(n)
+    Do = 3 * n + 2 if Do is None else int(Do)
+    if not 1 <= n <= JOINT_MAX_N or Do < 1:
+        raise ValueError(f"a central critic joins the observations of a team of 1 .. {JOINT_MAX_N} planes, each of at least one float: got "
+                         f"n = {n} and Do = {Do} ({n} x {Do} = {n * Do} inputs; the fused MLP kernels take at most {_lib.MLP_MAX_D})")
+    if n * Do > _lib.MLP_MAX_D:
+        raise ValueError(f"a central critic of a team of {n} planes reads {n} x {Do} = {n * Do} inputs: the fused MLP kernels take at most "
+                         f"{_lib.MLP_MAX_D}")
+    return n * Do
+
+
+def joint_obs(obs, *, out=None):
+    """The input rows of a centralised critic from observation records, in one launch (csrc/bsx_ppo_central.hip, `bsx_ppo_joint_obs`;
+    the contract is written out in include/battlespace_hip.h) -> x float32 [..., A, n Do].  obs float32 [..., A, Do], contiguous, on the
+    GPU, A = 2n planes in two teams of n adjacent columns, 1 <= n <= 4 and n Do <= 64; leading axes are flattened.  Row (.., i) of x is
+    plane i's own observation followed by its team-mates' in ascending plane index, as bit copies; nothing is masked.  out: the tensor
+    to write into (nothing is allocated then: a captured graph)."""
+    if not isinstance(obs, torch.Tensor) or obs.dim() < 2:
+        raise ValueError("obs must be a float32 [..., A, Do] tensor")
+    if obs.device.type != "cuda":
+        raise ValueError(f"joint_obs runs on the GPU: obs is on {obs.device}")
+    dev, (A, Do) = obs.device, obs.shape[-2:]
+    if A < 2 or A % 2:
+        raise ValueError(f"obs has shape {tuple(obs.shape)}: an even number of planes A = 2n is needed")
+    width = joint_width(A // 2, Do)
+    lead = tuple(obs.shape[:-2])
+    need = partial(_need, dev=dev, anchor="obs")
+    need(obs, "obs", (*lead, A, Do), _F32)
+    if out is None:
+        out = torch.empty((*lead, A, width), dtype=torch.float32, device=dev)
+    need(out, "out", (*lead, A, width), _F32)
+    if obs.numel():
+        _lib.check(_lib.load().bsx_ppo_joint_obs(obs.data_ptr(), obs.numel() // (A * Do), A, Do, out.data_ptr(), _stream(dev)), "bsx_ppo_joint_obs")
+    return out
+
+
 class PPOLearner:
     """The PPO update of a PolicyRollout's two networks, on device:
 
@@ -146,17 +191,28 @@ class PPOLearner:
     opponent share="all" is a ValueError (the scripted team's parameters are left alone); share="team" trains the learned team's one
     policy and keeps every bit of the scripted team's.  share=None (the default) is the unshared update, bit for bit.
 
-    rollout: a PolicyRollout with sample="categorical" or "gaussian", a value_actor and gae= (ValueError otherwise).  vclip: clip the
+    A centralised critic (MAPPO): on a PolicyRollout(central_critic=net) `critic` is that net, a StackedActor(A, joint_width(n), 1), and
+    `critic_input` is "central" ("own" otherwise).  A minibatch is then six calls: the actor's forward WITHOUT a value head, joint_obs of
+    the minibatch's observation rows into a cached [R, A, n D] buffer, bsx_mlp_forward of the critic on it (its raw column is v),
+    ppo_head, bsx_mlp_grad of the actor on obs and of the critic on the joined rows.  The two networks no longer share a shape and are
+    stepped one after the other, each clipped by its OWN gradient norm: device_step=True is adam_step of the actor (and log_std) into
+    step_count / step_stats, then mlp_adam_step of the critic into critic_step_count / critic_step_stats, both with group=; they read
+    ONE `hyper` tensor unless lr_critic= gives the critic a second one (`hyper_critic`; set_lr(lr, critic=)).  device_step=False clips
+    the actor's parameters (with log_std) and the critic's separately and steps one torch optimiser (lr_critic: a parameter group).
+    vclip, both kinds, shuffle=True, share= (is_tied is asked of the central critic too) and a scripted opponent are as above.
+
+    rollout: a PolicyRollout with sample="categorical" or "gaussian", a value_actor or a central_critic, and gae= (ValueError otherwise).  vclip: clip the
     value loss around the rollout's recorded values.  optimizer: any torch optimiser over the parameters, instead of Adam(lr, betas, eps)
     (a ValueError with device_step=True)."""
 
     def __init__(self, rollout, *, clip=0.2, c_v=0.5, c_e=0.01, vclip=None, epochs=4, minibatches=4, lr=3e-4, max_grad_norm=None, optimizer=None,
-                 device_step=False, betas=(0.9, 0.999), eps=1e-8, shuffle=False, shuffle_seed=None, share=None):
+                 device_step=False, betas=(0.9, 0.999), eps=1e-8, shuffle=False, shuffle_seed=None, share=None, lr_critic=None):
         ro = rollout
         if getattr(ro, "_sample", None) is None and getattr(ro, "_gauss", None) is None:
             raise ValueError("PPOLearner needs a PolicyRollout with sample='categorical' or 'gaussian' (it reads the recorded logp)")
-        if getattr(ro, "_value_w", None) is None or getattr(ro, "_gae", None) is None:
-            raise ValueError("PPOLearner needs a PolicyRollout with a value_actor and gae= (it reads value, adv, ret and mask)")
+        self.central = getattr(ro, "_central_w", None) is not None
+        if (getattr(ro, "_value_w", None) is None and not self.central) or getattr(ro, "_gae", None) is None:
+            raise ValueError("PPOLearner needs a PolicyRollout with a value_actor or a central_critic, and gae= (it reads value, adv, ret and mask)")
         epochs, minibatches = int(epochs), int(minibatches)
         if epochs < 1 or minibatches < 1 or ro.T % minibatches:
             raise ValueError(f"epochs >= 1 and a minibatches >= 1 that divides T = {ro.T} are needed (a minibatch is a range of whole ticks)")
@@ -166,7 +222,11 @@ class PPOLearner:
             raise ValueError("shuffle_seed belongs to shuffle=True")
         self.shuffle = shuffle
         self.shuffle_seed = (int(ro.fused.seed) & ((1 << 64) - 1) if shuffle_seed is None else _word(shuffle_seed, "shuffle_seed")) if shuffle else None
-        self.rollout, self.actor, self.critic = ro, ro.actor, ro.value_actor
+        self.rollout, self.actor, self.critic = ro, ro.actor, ro.central_critic if self.central else ro.value_actor
+        self.critic_input = "central" if self.central else "own"
+        self._ro_blob_v = ro._central_w if self.central else ro._value_w                # the critic's blob the rollout reads
+        if lr_critic is not None and (not self.central or optimizer is not None):
+            raise ValueError("lr_critic is for a central critic, which is stepped on its own (and not with an optimizer= of the caller's)")
         self.kind = "gaussian" if ro._gauss is not None else "categorical"
         self.temperature = ro._sample["temperature"] if self.kind == "categorical" else 1.0
         self.log_std = ro.log_std if self.kind == "gaussian" else None
@@ -175,21 +235,26 @@ class PPOLearner:
         self.epochs, self.minibatches = epochs, minibatches
         self.max_grad_norm = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)   # (no clipping is None here)
         _check_mlp(self.actor, ro.obs[:1], True, "fused_apply", obs_shaped=True)     # the observation check, under fused_apply's name
-        _check_mlp(self.critic, ro.obs[:1], True, "fused_apply", obs_shaped=True)
         A = self.actor.n_actors
+        if self.central:
+            _check_mlp(self.critic, ro._central_x[:1], False, "fused_mlp")
+        else:
+            _check_mlp(self.critic, ro.obs[:1], True, "fused_apply", obs_shaped=True)
         self.group = share_group(share, A // 2)
         if self.group > 1:
             if getattr(ro, "opponent", None) is not None and self.group == A:
                 raise ValueError("a rollout with a scripted opponent cannot share one policy across both teams (share='all'): the scripted "
                                  "team's parameters are left alone; use share='team'")
-            for name, x in (("actor", self.actor), ("value_actor", self.critic), ("log_std", self.log_std)):
+            critic_name, critic_blob = ("central_critic", "ro._central_w") if self.central else ("value_actor", "ro._value_w")
+            for name, x in (("actor", self.actor), (critic_name, self.critic), ("log_std", self.log_std)):
                 if x is not None and not is_tied(x, self.group):
                     raise ValueError(f"share={share!r} needs networks that are already shared: the rollout's {name} differs inside a group of "
-                                     f"{self.group} agents.  Tie actor, value_actor and log_std with learner.tie_(x, {self.group}) before "
+                                     f"{self.group} agents.  Tie actor, {critic_name} and log_std with learner.tie_(x, {self.group}) before "
                                      "building the PolicyRollout, or tie them and re-pack with ro.fused.refresh() and "
-                                     "critic.pack(out=ro._value_w)")
-        self.params = ([getattr(self.actor, k) for k in PARAMS] + [getattr(self.critic, k) for k in PARAMS]
-                       + ([self.log_std] if self.log_std is not None else []))
+                                     f"critic.pack(out={critic_blob})")
+        self._params_a = [getattr(self.actor, k) for k in PARAMS] + ([self.log_std] if self.log_std is not None else [])
+        self._params_v = [getattr(self.critic, k) for k in PARAMS]
+        self.params = self._params_a[:len(PARAMS)] + self._params_v + self._params_a[len(PARAMS):]
         dev = ro.obs.device
         self.device_step, self._graph = bool(device_step), None
         if self.device_step:
@@ -201,11 +266,19 @@ class PPOLearner:
             self.adam_a, self.adam_v = AdamState(self.actor), AdamState(self.critic)
             self.adam_ls = AdamState(self.log_std) if self.log_std is not None else None
             self.step_stats = torch.zeros((epochs * minibatches, 4), dtype=torch.float64, device=dev)
-            self._adam_ws = _workspace(None, adam_step_workspace_bytes(self.actor.n_actors // 2, 2), dev)
-            self._blob_a, self._blob_v = ro.fused.weights, ro._value_w       # the step packs into the blobs the rollout plays from
+            self._adam_ws = _workspace(None, adam_step_workspace_bytes(A // 2, 1 if self.central else 2), dev)
+            self._blob_a, self._blob_v = ro.fused.weights, self._ro_blob_v   # the step packs into the blobs the rollout plays from
+            if self.central:                 # the critic is stepped on its own (mlp_adam_step: its width is not the actor's), with its own norm
+                self.hyper_critic = self.hyper if lr_critic is None else adam_hyper(lr_critic, betas, eps, self.max_grad_norm, dev)
+                self.critic_step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+                self.critic_step_stats = torch.zeros((epochs * minibatches, 4), dtype=torch.float64, device=dev)
+                self._adam_ws_v = _workspace(None, mlp_adam_step_workspace_bytes(A, 1), dev)
         else:
-            self.optimizer = optimizer if optimizer is not None else torch.optim.Adam(self.params, lr=lr, betas=betas, eps=eps)
-            self._blob_a, self._blob_v = torch.empty_like(ro.fused.weights), torch.empty_like(ro._value_w)
+            if optimizer is None:
+                groups = self.params if lr_critic is None else [dict(params=self._params_a), dict(params=self._params_v, lr=_hyper("lr", lr_critic))]
+                optimizer = torch.optim.Adam(groups, lr=lr, betas=betas, eps=eps)
+            self.optimizer = optimizer
+            self._blob_a, self._blob_v = torch.empty_like(ro.fused.weights), torch.empty_like(self._ro_blob_v)
         self._by_rows = {}
         self.stats = torch.zeros((epochs * minibatches, 8), dtype=torch.float64, device=dev)
         if shuffle:
@@ -223,6 +296,7 @@ class PPOLearner:
             A, dev = self.actor.n_actors, self.rollout.obs.device
             f = _f32(torch.empty, dev)
             self._by_rows[R] = dict(y=f(R, A, 4), v=f(R, A), g_pi=f(R, A, 4), g_v=f(R, A, 4),
+                                    x=f(R, A, self.critic.obs_len) if self.central else None, y_v=f(R, A, 4) if self.central else None,
                                     g_ls=f(A, 3) if self.kind == "gaussian" else None,
                                     stats=torch.empty(8, dtype=torch.float64, device=dev),
                                     ws=_workspace(None, ppo_head_workspace_bytes(R, A), dev))
@@ -265,21 +339,28 @@ class PPOLearner:
         return self._gathered
 
     def _grads(self, mb, pack, stats):
-        """The five calls of a minibatch on its records `mb` (a Minibatch of R contiguous rows: views of a tick range, or gathered)."""
+        """The five calls of a minibatch on its records `mb` (a Minibatch of R contiguous rows: views of a tick range, or gathered); six
+        with a central critic, whose forward is a call of its own on the join of the same rows."""
         lib, obs = _lib.load(), mb.obs
         (R, A, D), dev = obs.shape, obs.device
         b = self._head_buffers(R)
         if pack:
             self.actor.pack(out=self._blob_a)
             self.critic.pack(out=self._blob_v)
-        _actor_forward(lib, self._blob_a, obs, b["y"], self._blob_v, b["v"])
+        if self.central:             # the actor without a value head; the critic on the join of the same rows, its raw column the value
+            _actor_forward(lib, self._blob_a, obs, b["y"])
+            x = joint_obs(obs, out=b["x"])
+            _mlp_forward(lib, self._blob_v, x, b["y_v"], raw=b["v"])
+        else:
+            x = obs
+            _actor_forward(lib, self._blob_a, obs, b["y"], self._blob_v, b["v"])
         head = ppo_head(self.kind, b["y"], b["v"], mb.rec, mb.logp, mb.adv, mb.ret, mb.mask,
                         clip=self.clip, c_v=self.c_v, c_e=self.c_e, temperature=self.temperature, log_std=self.log_std,
                         v_old=mb.value, vclip=self.vclip,
                         out=(b["g_pi"], b["g_v"], b["g_ls"], b["stats"] if stats is None else stats), workspace=b["ws"])
         # the head's outputs ARE bsx_mlp_grad's grad_out (four columns, the unused ones +0): mlp_grad's call without its padded copy
         row_a = _mlp_grad(lib, _buffers(self.actor).get(R, A, D, dev), self._blob_a, obs, head.g_pi, True)
-        row_v = _mlp_grad(lib, _buffers(self.critic).get(R, A, D, dev), self._blob_v, obs, head.g_v, False)
+        row_v = _mlp_grad(lib, _buffers(self.critic).get(R, A, x.shape[2], dev), self._blob_v, x, head.g_v, False)
         return row_a, row_v, head.g_log_std, head.stats
 
     def install(self, row_a, row_v, g_log_std):
@@ -335,12 +416,16 @@ class PPOLearner:
             row_a, row_v, g_ls, stats = self._step_grads(i)
             self.install(row_a, row_v, g_ls)
             if self.max_grad_norm is not None:
-                torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+                if self.central:                       # each network's own norm, as MAPPO clips them
+                    torch.nn.utils.clip_grad_norm_(self._params_a, self.max_grad_norm)
+                    torch.nn.utils.clip_grad_norm_(self._params_v, self.max_grad_norm)
+                else:
+                    torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
             self.optimizer.step()
             self._tie_params()
             self.stats[i].copy_(stats)
         ro.fused.refresh()
-        self.critic.pack(out=ro._value_w)
+        self.critic.pack(out=self._ro_blob_v)
         if self.shuffle:
             self.shuffle_base.add_(self.epochs)
         return self.stats
@@ -356,9 +441,14 @@ class PPOLearner:
         ls = self.log_std
         for i in range(self.epochs * self.minibatches):
             row_a, row_v, g_ls, _ = self._step_grads(i, pack=False, stats=self.stats[i])
-            adam_step([self.actor, self.critic], [row_a, row_v], [self.adam_a, self.adam_v], [self._blob_a, self._blob_v], self.hyper,
+            both = not self.central
+            adam_step([self.actor, self.critic] if both else [self.actor], [row_a, row_v] if both else [row_a],
+                      [self.adam_a, self.adam_v] if both else [self.adam_a], [self._blob_a, self._blob_v] if both else [self._blob_a], self.hyper,
                       self.step_count, log_std=ls, g_log_std=g_ls if ls is not None else None, log_std_state=self.adam_ls,
                       stats=self.step_stats[i], workspace=self._adam_ws, group=self.group)
+            if self.central:
+                mlp_adam_step([self.critic], [row_v], [self.adam_v], [self._blob_v], self.hyper_critic, self.critic_step_count,
+                              stats=self.critic_step_stats[i], workspace=self._adam_ws_v, group=self.group)
         if self.shuffle:
             self.shuffle_base.add_(self.epochs)                  # on the stream, inside a captured update: the next one draws afresh
 
@@ -366,13 +456,19 @@ class PPOLearner:
         """Every tensor an update writes that outlives it."""
         return (list(self.params) + [self.adam_a.m, self.adam_a.v, self.adam_v.m, self.adam_v.v, self.step_count, self._blob_a, self._blob_v,
                                      self.stats, self.step_stats] + ([self.adam_ls.m, self.adam_ls.v] if self.adam_ls is not None else [])
-                + ([self.shuffle_base, self.minibatch_idx] if self.shuffle else []))
+                + ([self.shuffle_base, self.minibatch_idx] if self.shuffle else [])
+                + ([self.critic_step_count, self.critic_step_stats] if self.central else []))
 
-    def set_lr(self, lr):
+    def set_lr(self, lr, critic=None):
         """The learning rate of the steps from now on, written to `hyper` on the device (a fill on the current stream: no host
-        synchronisation); a captured update reads it at every replay."""
+        synchronisation); a captured update reads it at every replay.  A central critic reads the same tensor, so it follows; built
+        with lr_critic= it has a `hyper_critic` of its own, which critic= sets."""
         self._need_device_step("set_lr")
+        if critic is not None and (not self.central or self.hyper_critic is self.hyper):
+            raise ValueError("set_lr(critic=) needs a central critic built with lr_critic= (one rate tensor is shared otherwise)")
         self.hyper[0].fill_(_hyper("lr", lr))
+        if critic is not None:
+            self.hyper_critic[0].fill_(_hyper("lr", critic))
 
     def sync(self):
         """Re-pack both blobs from the parameters, once: for a caller who has edited the parameters from outside (loaded a checkpoint)."""

@@ -397,11 +397,22 @@ class PolicyRollout:
     re-spawned that way (to mu = 0.0; every other row keeps its bits), since no tick of the next run finds them finished.
     Exploration noise on the score vectors is Gaussian (noise_std) and/or the reference's Ornstein-Uhlenbeck process
     (ou_scale = main.py's curr_noise; utils/noise.py), whose state is one more [E, A, 4] tensor updated inside the actor
-    kernel and restarted per game; then clamp(-1, 1) as maddpg/agent.py:31 does."""
+    kernel and restarted per game; then clamp(-1, 1) as maddpg/agent.py:31 does.
+
+    A centralised critic (MAPPO): central_critic= a StackedActor(A, learner.joint_width(n), 1) in place of value_actor (the two exclude
+    each other; fused actor, 1v1 ... 4v4).  Row (e, i) of its input is plane i's own observation followed by its team-mates'
+    (learner.joint_obs); it is never played, so no tick evaluates a value head and the one-launch form takes it at every size it has.
+    After the ticks, one forward over rows 0 .. T of obs writes value [T, E, A] and last_value [E, A] -- views of ONE [T + 1, E, A] tensor
+    --, in chunks of central_chunk whole ticks through one cached input buffer; central_chunk=None takes the most ticks whose input rows
+    stay under 32 MiB (_CENTRAL_BYTES: a chunk is written by the join and read back by the forward at once, and at that size it is still
+    in the last-level cache), at least one.  gae=, adv, ret, mask, adv_stats and a scripted opponent's flags are what they are with a
+    value_actor.  learner.PPOLearner trains both networks from such a rollout."""
+
+    _CENTRAL_BYTES = 32 << 20
 
     def __init__(self, env, actor, T, noise_std=0.0, fused=True, seed=0, opponent=None, ou_scale=0.0, one_launch=False,
                  precision="f32", ou_restart=True, sample=None, temperature=1.0, value_actor=None, chains="auto", gae=None, log_std=None,
-                 epsilon=None):
+                 epsilon=None, central_critic=None, central_chunk=None):
         """actor: a StackedActor.  fused=True evaluates it with the hand-written HIP kernel (FusedActor), False with
         torch ops (the fp32 reference of the same op).  opponent: an `instinct.Team` that plays its team's planes
         instead of the actor (the reference's training setup, main.py:119-122: learned red vs scripted blue): its
@@ -471,6 +482,25 @@ class PolicyRollout:
             raise ValueError("the categorical head needs the fused actor and a discrete env")
         if value_actor is not None and not fused:
             raise ValueError("the value head needs the fused actor")
+        # central_critic (MAPPO): a value function on what the whole team sees -- a StackedActor(A, n D, 1) on learner.joint_obs' rows --,
+        # used for training only and never played: the actor kernels carry NO value head (so the one-launch form takes it at 1v1 ... 4v4),
+        # and value / last_value are one bsx_mlp_forward over the records after the ticks (_advantages), in chunks of central_chunk ticks
+        # through ONE cached input buffer.  central_chunk=None: the most ticks whose input rows stay under _CENTRAL_BYTES.
+        self.central_critic, self._central_w = None, None
+        if central_critic is not None:
+            if value_actor is not None:
+                raise ValueError("central_critic excludes value_actor: a rollout records one value function")
+            if not fused:
+                raise ValueError("the central critic needs the fused actor")
+            from .learner import joint_width
+            width = joint_width(env.n_agents, env.obs_size)
+            if central_critic.n_actions != 1 or central_critic.n_actors != env._A or central_critic.obs_len != width:
+                raise ValueError(f"central_critic must be a StackedActor(n_actors={env._A}, obs_len={width}, n_actions=1): every plane's "
+                                 "value head on its team's joint observation (learner.joint_width)")
+            if central_chunk is not None and (isinstance(central_chunk, bool) or not isinstance(central_chunk, int) or central_chunk < 1):
+                raise ValueError(f"central_chunk must be None or a number of ticks >= 1, got {central_chunk!r}")
+        elif central_chunk is not None:
+            raise ValueError("central_chunk belongs to central_critic")
         self._gauss = None
         if sample == "gaussian":
             if not fused or not self.continuous:
@@ -514,14 +544,24 @@ class PolicyRollout:
                 raise ValueError("the one-launch rollout takes a value head at 1v1 only (use the graph form)")
             self.value_actor, self._value_w = value_actor, value_actor.pack()
             self.value = torch.zeros((T, E, A), dtype=torch.float32, device=dev)
+        if central_critic is not None:
+            # value and last_value are views of ONE [T + 1, E, A] tensor: the critic's forward over rows 0 .. T of obs writes it whole
+            self.central_critic, self._central_w = central_critic, central_critic.pack()
+            self._values = torch.zeros((T + 1, E, A), dtype=torch.float32, device=dev)
+            self.value, self.last_value = self._values[:T], self._values[T]
+            per_tick = E * A * width * 4
+            chunk = max(1, self._CENTRAL_BYTES // per_tick) if central_chunk is None else central_chunk
+            self.central_chunk = min(chunk, T + 1)
+            self._central_x = torch.empty((self.central_chunk, E, A, width), dtype=torch.float32, device=dev)
+            self._central_y = torch.empty((self.central_chunk, E, A, 4), dtype=torch.float32, device=dev)     # the forward's tanh rows (not read)
         # gae=dict(gamma, lam[, normalize]): an on-policy learner's inputs, computed in the same graph after the ticks (advantage.gae):
         # last_value = V(obs[T]) by one value-only pass of the fused actor, then adv / ret / mask [T, E, A] and, with normalize, adv_stats
         # = (n, mean, std).  _done_prev carries the agents' done flags from one run to the next (start() seeds it from the env, which
         # every run hands its last flags).
         self._gae = None
         if gae is not None:
-            if value_actor is None:
-                raise ValueError("gae= needs a value_actor (the bootstrap value V(obs[T]) and value[t] come from it)")
+            if value_actor is None and central_critic is None:
+                raise ValueError("gae= needs a value_actor or a central_critic (the bootstrap value V(obs[T]) and value[t] come from it)")
             from . import advantage
             self._gae = dict(gamma=float(gae["gamma"]), lam=float(gae["lam"]), normalize=bool(gae.get("normalize", False)))
             advantage.check_rates(self._gae["gamma"], self._gae["lam"])
@@ -529,10 +569,11 @@ class PolicyRollout:
             self.ret = torch.zeros((T, E, A), dtype=torch.float32, device=dev)
             self._mask = torch.zeros((T, E, A), dtype=torch.uint8, device=dev)
             self.mask = self._mask.view(torch.bool)
-            self.last_value = torch.zeros((E, A), dtype=torch.float32, device=dev)
             self.adv_stats = torch.zeros(3, dtype=torch.float64, device=dev)
             self._done_prev = torch.zeros((E, A), dtype=torch.uint8, device=dev)
-            self._lv_scores = torch.zeros((E, A, 4), dtype=torch.float32, device=dev)      # the actor half of the value pass (not read)
+            if central_critic is None:
+                self.last_value = torch.zeros((E, A), dtype=torch.float32, device=dev)
+                self._lv_scores = torch.zeros((E, A, 4), dtype=torch.float32, device=dev)  # the actor half of the value pass (not read)
             self._gae_ws = (torch.empty(advantage.workspace_bytes(E, A, T), dtype=torch.uint8, device=dev)
                             if self._gae["normalize"] else None)
             # a scripted opponent's planes are not the actor's decisions: GAE takes the learned team's flags (advantage.gae(agents=)) --
@@ -660,6 +701,8 @@ class PolicyRollout:
                     self._tick(t, games)
             self.env.fork_join(ranges, ticks, self._side)
             self.env._env_done.copy_(self.env_done[self.T])        # the per-tick launches wrote their flags into the record
+        if self._gae is None and self._central_w is not None:
+            self._central_values()                     # (with gae=, _advantages runs it)
         if self._gae is not None:
             self._advantages()
             # no tick writes the env's own done flags (they go into the record): hand it the last tick's, so that a start() after
@@ -673,11 +716,26 @@ class PolicyRollout:
         """V(obs[T]) into last_value, then GAE over this run's records.  The value pass draws nothing (no noise, no sample, no OU state)
         and takes an explicit sequence number: the actor's `seq`, `_seq_base` and every noise state stay as the ticks left them."""
         from . import advantage
-        self.fused.forward_into(self.obs[self.T], self._lv_scores, 0.0, seq=0, value=dict(weights=self._value_w, out=self.last_value))
+        if self._central_w is not None:
+            self._central_values()
+        else:
+            self.fused.forward_into(self.obs[self.T], self._lv_scores, 0.0, seq=0, value=dict(weights=self._value_w, out=self.last_value))
         g = self._gae
         advantage.gae(self.rew, self.value, self.last_value, self._done, self.env_done, self._done_prev, g["gamma"], g["lam"],
                       normalize=g["normalize"], out=(self.adv, self.ret, self._mask), stats=self.adv_stats, workspace=self._gae_ws,
                       agents=self._gae_agents)
+
+    def _central_values(self):
+        """The central critic on rows 0 .. T of obs -> value and last_value (one [T + 1, E, A] tensor), in chunks of central_chunk whole
+        ticks: bsx_ppo_joint_obs into the one cached input buffer (a prefix view for a shorter last chunk), then bsx_mlp_forward, whose
+        `raw` column -- head column 0 before tanh -- is written straight into the chunk's rows of the value tensor.  A forward row
+        depends on its own input row alone, so the chunking does not show in the values.  Launches only: capturable."""
+        from .learner import _mlp_forward, joint_obs
+        lib, (E, A) = _lib.load(), self._values.shape[1:]
+        for t0 in range(0, self.T + 1, self.central_chunk):
+            t1 = min(t0 + self.central_chunk, self.T + 1)
+            x = joint_obs(self.obs[t0:t1], out=self._central_x[:t1 - t0])
+            _mlp_forward(lib, self._central_w, x.view(-1, A, x.shape[-1]), self._central_y[:t1 - t0].view(-1, A, 4), raw=self._values[t0:t1].view(-1, A))
 
     def run(self):
         """T ticks (asynchronous).  Afterwards obs[0..T], scores, rew, done hold this rollout's transitions."""

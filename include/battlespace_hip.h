@@ -708,6 +708,24 @@ int bsx_ppo_head_workspace_bytes(int64_t R, int A, size_t* bytes);
 int bsx_ppo_head(const BsxPpoIo* io, int64_t R, int A, int kind, float temperature, float clip, float vclip, float c_v, float c_e,
                  void* workspace, double* stats, void* stream);
 
+/* ---- the input rows of a centralised PPO critic (MAPPO, Yu et al. 2022) (deep-rl-battlespace_amd/learner/ppo.py: joint_width,
+ * joint_obs, PPOLearner on a PolicyRollout(central_critic=); csrc/bsx_ppo_central.hip).  The critic is a network the fused MLP kernels
+ * already take, a StackedActor(A, n Do, 1) evaluated after the ticks on the records (bsx_mlp_forward's `raw` column is the value), so the
+ * actor kernels carry no value head; what it reads is built here.
+ * obs [R][A][Do], A = 2n planes in two blocks of n adjacent columns (a team: the layout of share_group("team", n) and of the scripted
+ * opponent's columns); x [R][A][n Do] (out).  Row (r, i) of x is plane i's agent-specific joint observation, n slots of Do floats:
+ *     slot 0             obs[r][i]
+ *     slot s, 1 .. n-1   obs[r][j], j the s-th plane of i's team in ascending plane index with i itself skipped:
+ *                        j = team n + (s <= k ? s - 1 : s)   for i = team n + k
+ * Own-first is what lets one critic shared by a team tell its members apart.  Every float is a bit copy (NaN payloads and -0 survive);
+ * the rows of dead team-mates are copied as recorded -- nothing is masked here, the mask is GAE's.  Indexing is 64-bit throughout.
+ * ONE launch whose grid is a function of (R, A, Do) and x's alignment alone, plain vector loads and stores, every obs row read once; no
+ * host synchronisation: capturable in a HIP graph.  x must not overlap obs.  R = 0 is a no-op that succeeds (after the checks).
+ * Refusals, before the launch, in this order: BSX_E_ARG for a null obs or x; R < 0 or R > BSX_MAX_E; A odd or A / 2 outside 1 .. 4;
+ * Do < 1 or (A / 2) Do > BSX_MLP_MAX_D.  Then BSX_E_ALIGN for obs or x off a 4-byte boundary (x on a 16-byte boundary, as every
+ * allocation is, takes the widest stores). */
+int bsx_ppo_joint_obs(const float* obs, int64_t R, int A, int Do, float* x, void* stream);
+
 /* ---- the optimiser step (deep-rl-battlespace_amd/learner.py: adam_step, PPOLearner(device_step=True); csrc/bsx_adam_step.hip): torch's
  * clip_grad_norm_(params, max_grad_norm) followed by Adam.step() (no weight decay, no amsgrad) over one or two StackedActor networks and,
  * optionally, the Gaussian head's log_std -- from the gradient rows bsx_actor_grad writes to updated parameters, Adam moments and the packed
