@@ -11,7 +11,6 @@
 #include <stdint.h>
 
 #include "battlespace_hip.h"
-#include "bsx_argmax4.h"
 #include "bsx_args.h"
 #include "bsx_block_sum.h"
 
@@ -27,11 +26,6 @@ constexpr int64_t COPY_MAX_BLOCKS = 65536;     // the copy kernels stride over t
 constexpr int MAX_DO = 3 * BSX_MAX_N + 2;      // an observation row of the widest team
 
 typedef float F4 __attribute__((ext_vector_type(4)));
-
-// a row of four scores as the discrete heads (bsx_dqn_head.hip, bsx_qmix_head.hip) read it: the step kernels' choice, and column a of a
-// row by selects -- a dynamically indexed vector would live in scratch memory
-__device__ __forceinline__ int argmax_row(const F4 v) { return bsxk::argmax4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ float pick(const F4 v, int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : (a == 2 ? v[2] : v[3])); }
 
 struct Shape {                                 // a checked (B, nA, Do, k, central)
     int64_t B;
@@ -109,13 +103,29 @@ struct HeadView {                              // the pass's view of a head kern
     double* part;                              // workspace: [blocks][STAT_COLS] partial rows
 };
 
+// The end of every head kernel, the discrete heads' (bsx_q_head.h) included: a thread's NS float64 sums are added across the workgroup
+// in a fixed order (bsx_block_sum.h) and stored as the workgroup's partial row, 0 | the NS sums | 0 up to STAT_COLS
+template <int NS>
+__device__ __forceinline__ void store_partial_row(const double (&acc)[NS], double* part) {
+    __shared__ double s_w[NS][WAVES];
+    const int tid = threadIdx.x;
+    double sum[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
+    if (tid < STAT_COLS) {
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
+        part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
+    }
+}
+
 // One thread per element and tile of 256, J consecutive tiles per workgroup; the float32 terms of the statistics are added in float64 per
-// thread, then across the workgroup in a fixed order (bsx_block_sum.h), and stored as the workgroup's partial row.  WEIGHT 1: weight is given
+// thread, then across the workgroup and stored (store_partial_row).  WEIGHT 1: weight is given
 template <HeadKind KIND, int WEIGHT>
 __device__ __forceinline__ void td_head_pass(const HeadView& p) {
     constexpr bool TWIN = KIND != HEAD_ONE, SOFT = KIND == HEAD_SOFT;
     constexpr int NS = TWIN ? 7 : 6;           // a partial row: 0 | w (d1^2 + d2^2) | q1 | y | |d1| | done | w | |q1 - q2| (0 with one critic)
-    __shared__ double s_w[NS][WAVES];
     const int tid = threadIdx.x;
     double acc[NS] = {};
     F4* gq14 = reinterpret_cast<F4*>(p.g_q1);
@@ -152,15 +162,7 @@ __device__ __forceinline__ void td_head_pass(const HeadView& p) {
         acc[5] += double(w);
         if constexpr (TWIN) acc[6] += double(fabsf(q - q2));
     }
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
-    if (tid < STAT_COLS) {
-        double t = 0.0;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
-        p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
-    }
+    store_partial_row(acc, p.part);
 }
 
 // Q = 1024 / 8 threads per column; thread (q, c) adds the partial rows q, q + Q, .. in order; then 16 threads per column add every

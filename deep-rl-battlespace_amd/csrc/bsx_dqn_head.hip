@@ -6,7 +6,8 @@
 // rows, the TD target, its clipped error into column a of g4, the statistics.  mix = 1 (VDN): Q and the target are sums over the row's
 // agents in agent order; every thread of a row adds them itself (nA <= 16 rows of 16 bytes, served from cache), so a row may lie across
 // two tiles or workgroups and there is nothing to exchange.
-// It is built on bsx_ddpg_shared.h: the TD heads' plan, per-workgroup sums, merge kernel and entry helpers.  Built with -ffp-contract=off:
+// It is built on bsx_q_head.h, what the two discrete heads share (the tail from the TD target down among it), itself on
+// bsx_ddpg_shared.h: the TD heads' plan, per-workgroup sums, merge kernel and entry helpers.  Built with -ffp-contract=off:
 // every operation is one float32 rounding and the one multiply-add is an explicit fmaf (tests/dqn_util.py restates it in numpy).  Every
 // index is 64-bit.  No floating-point atomics, no flags or spins; the grid is a function of (B, nA) alone.
 
@@ -14,19 +15,12 @@
 #include <stdint.h>
 
 #include "battlespace_hip.h"
-#include "bsx_argmax4.h"
 #include "bsx_args.h"
-#include "bsx_ddpg_shared.h"
+#include "bsx_q_head.h"
 
 namespace {
 
-struct HeadArgs {
-    BsxDqnIo io;
-    int64_t M, tiles;
-    int J, nA;
-    float gamma, q_scale, delta, s2;           // delta: huber_delta (0: none); s2 = float(2.0 / B)
-    double* part;                              // workspace: [blocks][STAT_COLS] partial rows
-};
+typedef QHeadArgs<BsxDqnIo> HeadArgs;
 
 struct Elem {                                  // what element (b, i) contributes on its own
     float qc, qn;
@@ -53,10 +47,8 @@ __device__ __forceinline__ Elem elem_of(const HeadArgs& p, int64_t i) {
 template <int FORM>
 __global__ __launch_bounds__(TPB) void bsx_dqn_head_kernel(const HeadArgs p) {
     constexpr int WEIGHT = FORM & 1, DOUBLE = (FORM >> 1) & 1, MIX = (FORM >> 2) & 1;
-    constexpr int NS = 7;                      // a partial row: 0 | w l(d) | Q | y | |d| | done | w | greedy
-    __shared__ double s_w[NS][WAVES];
     const int tid = threadIdx.x;
-    double acc[NS] = {};
+    double acc[Q_NS] = {};
     F4* g4 = reinterpret_cast<F4*>(p.io.g4);
     const int64_t tile0 = int64_t(blockIdx.x) * p.J;
     for (int j = 0; j < p.J; ++j) {
@@ -77,37 +69,14 @@ __global__ __launch_bounds__(TPB) void bsx_dqn_head_kernel(const HeadArgs p) {
             }
         }
         const float w = WEIGHT ? p.io.weight[wi] : 1.0f;
-        const float y = fmaf(p.gamma, N, R);
-        const float d = Q - y, ad = fabsf(d);
-        const bool huber = p.delta > 0.0f;
-        const float c = (huber && d == d) ? fminf(fmaxf(d, -p.delta), p.delta) : d;       // a NaN stays a NaN
-        const float g = ((w * c) * p.s2) * p.q_scale;
-        F4 row = F4(0.0f);
-        row[0] = e.a == 0 ? g : 0.0f;
-        row[1] = e.a == 1 ? g : 0.0f;
-        row[2] = e.a == 2 ? g : 0.0f;
-        row[3] = e.a == 3 ? g : 0.0f;
-        g4[i] = row;
+        const QTail t = q_tail(p, Q, q_target(p, N, R), w);
+        g4[i] = one_hot(e.a, t.g);
         p.io.q[i] = Q;
-        if (p.io.td) p.io.td[i] = y;
-        const float loss = (!huber || ad <= p.delta) ? (w * d) * d : w * (p.delta * (2.0f * ad - p.delta));
-        acc[0] += double(loss);
-        acc[1] += double(Q);
-        acc[2] += double(y);
-        acc[3] += double(ad);
-        acc[4] += e.over ? 1.0 : 0.0;
-        acc[5] += double(w);
+        if (p.io.td) p.io.td[i] = t.y;
+        q_sums(p, t, Q, w, e.over, acc);
         acc[6] += e.greedy ? 1.0 : 0.0;
     }
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
-    if (tid < STAT_COLS) {
-        double t = 0.0;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
-        p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
-    }
+    store_partial_row(acc, p.part);
 }
 
 typedef void (*HeadKernel)(HeadArgs);
@@ -124,13 +93,8 @@ int bsx_dqn_head(const BsxDqnIo* io, int64_t B, int nA, float gamma, float q_sca
                  double* stats, void* stream) {
     if (!io || !io->y_cur || !io->y_next_target || !io->act || !io->rew || !io->done || !io->g4 || !io->q) return BSX_E_ARG;
     if (!head_ranges(gamma, B, nA, workspace, stats)) return BSX_E_ARG;
-    if (!(q_scale > 0.0f) || !(huber_delta >= 0.0f)) return BSX_E_ARG;                     // NaN too
-    if ((double_q != 0 && double_q != 1) || (mix != 0 && mix != 1)) return BSX_E_ARG;
-    if (double_q && !io->y_next_online) return BSX_E_ARG;
-    if (!aligned(io->y_cur, 16) || !aligned(io->y_next_online, 16) || !aligned(io->y_next_target, 16) || !aligned(io->act, 16) ||
-        !aligned(io->g4, 16))
-        return BSX_E_ALIGN;
-    if (!aligned(io->rew, 4) || !aligned(io->weight, 4) || !aligned(io->q, 4) || !aligned(io->td, 4)) return BSX_E_ALIGN;
+    if (mix != 0 && mix != 1) return BSX_E_ARG;
+    if (const int e = q_head_refusal(io, q_scale, huber_delta, double_q)) return e;
     const HeadArgs a{*io, 0, 0, 0, nA, gamma, q_scale, huber_delta, float(2.0 / double(B)), nullptr};
     const int form = (double_q << 1) | (mix << 2);
     return launch_head<true, HeadArgs>(KERNELS[form | 1], KERNELS[form], io->weight != nullptr, a, B, nA, workspace, stats, stream);

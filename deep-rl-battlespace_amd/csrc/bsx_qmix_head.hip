@@ -6,6 +6,7 @@
 // E = 4 m.  This pass lies between the four forwards and the two bsx_mlp_grad(squash = 1) calls: per batch row the mix of the replayed
 // actions' values on the online rows, the mix of the greedy next actions' values on the target rows, the TD target, and BOTH grad_out
 // tensors -- g4 for the Q network, gh for the mixer -- with the statistics.
+// The readers of a score row, the tail from the TD target down and the entry's common part are bsx_q_head.h's, the DQN head's own.
 // One thread per batch row on the TD heads' plan (bsx_ddpg_shared.h: plan_of(B, 1)), sums and merge.  pre, h and the slopes live in
 // registers under compile-time indices: the agent loop is unrolled to QMIX_MAX_AGENTS with a guard, and the agents' W1 rows are read a
 // second time (from cache) for the gradients instead of being kept.  Built with -ffp-contract=off: every operation is one float32
@@ -16,9 +17,8 @@
 #include <stdint.h>
 
 #include "battlespace_hip.h"
-#include "bsx_argmax4.h"
 #include "bsx_args.h"
-#include "bsx_ddpg_shared.h"
+#include "bsx_q_head.h"
 
 namespace {
 
@@ -28,13 +28,7 @@ inline bool qmix_embed(int embed) { return embed == 4 || embed == 8 || embed == 
 inline bool qmix_team(int nA) { return nA >= 1 && nA <= QMIX_MAX_AGENTS; }
 inline int members_of(int nA, int embed) { return nA * (embed / 4) + 2 * (embed / 4) + 1; }
 
-struct HeadArgs {
-    BsxQmixIo io;
-    int64_t M, tiles;                          // M = B: one thread per batch row
-    int J, nA;
-    float gamma, q_scale, delta, s2;           // delta: huber_delta (0: none); s2 = float(2.0 / B)
-    double* part;                              // workspace: [blocks][STAT_COLS] partial rows
-};
+typedef QHeadArgs<BsxQmixIo> HeadArgs;         // M = B: one thread per batch row
 
 __device__ __forceinline__ float sgn(float t) { return float(t > 0.0f) - float(t < 0.0f); }
 
@@ -84,10 +78,8 @@ __device__ __forceinline__ float mix_of(const F4* hy, int nA, const float (&u)[Q
 template <int FORM>
 __global__ __launch_bounds__(TPB) void bsx_qmix_head_kernel(const HeadArgs p) {
     constexpr int WEIGHT = FORM & 1, DOUBLE = (FORM >> 1) & 1, E = 4 << (FORM >> 2), m = E / 4;
-    constexpr int NS = 7;                      // a partial row: 0 | w l(d) | Q_tot | y | |d| | over | w | greedy share
-    __shared__ double s_w[NS][WAVES];
     const int tid = threadIdx.x, nA = p.nA, Mh = nA * m + 2 * m + 1;
-    double acc[NS] = {};
+    double acc[Q_NS] = {};                     // Q: Q_tot; done: the whole team over; greedy: the row's share
     const F4* yc4 = reinterpret_cast<const F4*>(p.io.y_cur);
     const F4* yt4 = reinterpret_cast<const F4*>(p.io.y_next_target);
     const F4* yo4 = reinterpret_cast<const F4*>(DOUBLE ? p.io.y_next_online : p.io.y_next_target);
@@ -117,7 +109,7 @@ __global__ __launch_bounds__(TPB) void bsx_qmix_head_kernel(const HeadArgs p) {
         }
         const float tot_n = mix_of<E>(reinterpret_cast<const F4*>(p.io.hy_next_target) + h0, nA, u, h, sl);
         const float N = over ? 0.0f : p.q_scale * tot_n;
-        const float y = fmaf(p.gamma, N, R);
+        const float y = q_target(p, N, R);
         // the mix of the replayed actions' values on the online mixer's rows
         int greedy = 0;
 #pragma unroll
@@ -133,10 +125,8 @@ __global__ __launch_bounds__(TPB) void bsx_qmix_head_kernel(const HeadArgs p) {
         const float tot = mix_of<E>(hy, nA, u, h, sl);
         const float Q = p.q_scale * tot;
         const float w = WEIGHT ? p.io.weight[r0] : 1.0f;
-        const float d = Q - y, ad = fabsf(d);
-        const bool huber = p.delta > 0.0f;
-        const float c = (huber && d == d) ? fminf(fmaxf(d, -p.delta), p.delta) : d;       // a NaN stays a NaN
-        const float G = ((w * c) * p.s2) * p.q_scale;
+        const QTail t = q_tail(p, Q, y, w);
+        const float G = t.g;
         // ws_e = w2_e * slope_e into sl[]; the rows of b1 and w2, then b2's
 #pragma unroll
         for (int j = 0; j < m; ++j) {
@@ -172,35 +162,15 @@ __global__ __launch_bounds__(TPB) void bsx_qmix_head_kernel(const HeadArgs p) {
                     }
                     gh[h0 + i * m + j] = gw1;
                 }
-                const float g = G * S;
-                F4 row = F4(0.0f);
-                row[0] = a[i] == 0 ? g : 0.0f;
-                row[1] = a[i] == 1 ? g : 0.0f;
-                row[2] = a[i] == 2 ? g : 0.0f;
-                row[3] = a[i] == 3 ? g : 0.0f;
-                g4[r0 + i] = row;
+                g4[r0 + i] = one_hot(a[i], G * S);
                 p.io.q[r0 + i] = Q;
                 if (p.io.td) p.io.td[r0 + i] = y;
             }
         }
-        const float loss = (!huber || ad <= p.delta) ? (w * d) * d : w * (p.delta * (2.0f * ad - p.delta));
-        acc[0] += double(loss);
-        acc[1] += double(Q);
-        acc[2] += double(y);
-        acc[3] += double(ad);
-        acc[4] += over ? 1.0 : 0.0;
-        acc[5] += double(w);
+        q_sums(p, t, Q, w, over, acc);
         acc[6] += double(greedy) / double(nA);
     }
-    double sum[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) sum[c] = block_sum<double, WAVES>(acc[c], s_w[c]);
-    if (tid < STAT_COLS) {
-        double t = 0.0;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) t = tid == c + 1 ? sum[c] : t;
-        p.part[int64_t(blockIdx.x) * STAT_COLS + tid] = t;
-    }
+    store_partial_row(acc, p.part);
 }
 
 typedef void (*HeadKernel)(HeadArgs);
@@ -252,13 +222,8 @@ int bsx_qmix_head(const BsxQmixIo* io, int64_t B, int nA, int embed, float gamma
         !io->gh || !io->q)
         return BSX_E_ARG;
     if (!head_ranges(gamma, B, 1, workspace, stats) || !qmix_team(nA) || !qmix_embed(embed)) return BSX_E_ARG;
-    if (!(q_scale > 0.0f) || !(huber_delta >= 0.0f)) return BSX_E_ARG;                     // NaN too
-    if (double_q != 0 && double_q != 1) return BSX_E_ARG;
-    if (double_q && !io->y_next_online) return BSX_E_ARG;
-    if (!aligned(io->y_cur, 16) || !aligned(io->y_next_online, 16) || !aligned(io->y_next_target, 16) || !aligned(io->hy_cur, 16) ||
-        !aligned(io->hy_next_target, 16) || !aligned(io->act, 16) || !aligned(io->g4, 16) || !aligned(io->gh, 16))
-        return BSX_E_ALIGN;
-    if (!aligned(io->rew, 4) || !aligned(io->weight, 4) || !aligned(io->q, 4) || !aligned(io->td, 4)) return BSX_E_ALIGN;
+    if (const int e = q_head_refusal(io, q_scale, huber_delta, double_q)) return e;
+    if (!aligned(io->hy_cur, 16) || !aligned(io->hy_next_target, 16) || !aligned(io->gh, 16)) return BSX_E_ALIGN;
     const HeadArgs a{*io, 0, 0, 0, nA, gamma, q_scale, huber_delta, float(2.0 / double(B)), nullptr};
     const int form = (double_q << 1) | ((embed == 4 ? 0 : (embed == 8 ? 1 : 2)) << 2);
     return launch_head<true, HeadArgs>(KERNELS[form | 1], KERNELS[form], io->weight != nullptr, a, B, 1, workspace, stats, stream);

@@ -36,6 +36,15 @@ def _critic_width(nA, Do, k, central):
     return Dc
 
 
+def _stacked_shape(net, name, want, context=""):
+    """The refusal of a learner's network that is not a StackedActor of the shape `want` = (n_actors, obs_len, n_actions); context:
+    what beside the buffer fixes that shape, as the message's clause (" and critic_input='central'")."""
+    have = tuple(getattr(net, a, None) for a in ("n_actors", "obs_len", "n_actions"))
+    if not _is_stacked(net) or have != want:
+        raise ValueError(f"{name} must be a StackedActor{want} for this buffer{context}, got "
+                         f"{'StackedActor' + str(have) if None not in have else type(net).__name__}")
+
+
 def _batch_rows(x, name):
     if not isinstance(x, torch.Tensor) or x.dim() != 3:
         raise ValueError(f"{name} must be a float32 [B, nA, columns] tensor")
@@ -186,9 +195,20 @@ def td_head(q, q_next, rew, done, gamma, *, weight=None, out=None, workspace=Non
 
 class _RingLearner:
     """What the learners that update networks from a device ring share, and no learner on its own: DDPGLearner (with TD3Learner and
-    SACLearner under it), dqn.DQNLearner and qmix.QMIXLearner.  A subclass sets `buffer`, `B`, `nA`, `Do`, `k`, `updates`, `stats`, `_graph = None`, `critics`
-    (the list of its critics' records; empty without one) and `_actor_net`, the record of the network a rollout plays; it writes
-    `_update(u)` and `_state()`."""
+    SACLearner under it), dqn.DQNLearner and qmix.QMIXLearner.  A subclass calls `_ring` first and sets `B`, `nA`, `Do`, `k`, `stats`, `critics`
+    (the list of its critics' records; empty without one), `_actor_net`, the record of the network a rollout plays, `_adam_ws` and
+    `_steps`, the (step counter, step statistics) pairs of its optimiser steps; it writes `_update(u)`."""
+
+    def _ring(self, buffer, gamma, updates, max_grad_norm):
+        """The refusals every ring learner starts with -> max_grad_norm as adam_hyper takes it; sets `buffer`, `gamma`, `updates`,
+        `_prioritized` and `_graph`."""
+        if not isinstance(buffer, DeviceReplayBuffer):
+            raise ValueError(f"{type(self).__name__} needs a DeviceReplayBuffer (it samples on the device)")
+        self.buffer, self.gamma, self.updates = buffer, _hyper("gamma", gamma), int(updates)
+        if self.updates < 1:
+            raise ValueError(f"updates must be >= 1, got {updates!r}")
+        self._prioritized, self._graph = isinstance(buffer, PrioritizedReplayBuffer), None
+        return None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)
 
     def _net(self, net, D, critic=False, gx=False, members=None):
         """A network as the learner holds it -> _Net: with a deep copy as its target, both packed blobs, its AdamState and MLP buffers;
@@ -213,6 +233,16 @@ class _RingLearner:
         """Of every network: its blobs and moments, then its parameters and its target's."""
         return ([t for n in self._nets() for t in (n.blob, n.target_blob, n.adam.m, n.adam.v)]
                 + [getattr(net, p) for n in self._nets() for net in (n.net, n.target) for p in PARAMS])
+
+    def _adam_one(self, n, row, hyper, step, stats):
+        """ONE mlp_adam_step of the network of record n, on its gradient row, with its Polyak target and both blobs."""
+        mlp_adam_step([n.net], [row], [n.adam], [n.blob], hyper, step, targets=[n.target], target_blobs=[n.target_blob], stats=stats,
+                      workspace=self._adam_ws)
+
+    def _state(self):
+        """Every tensor an update writes that outlives it."""
+        return ([self.buffer._draws] + [s for s, _ in self._steps] + [self.stats] + [t for _, t in self._steps] + self._net_state()
+                + ([self.buffer._leaves, self.buffer.tree, self.buffer.max_priority] if self._prioritized else []))
 
     def _run(self):
         for u in range(self.updates):
@@ -305,27 +335,18 @@ class DDPGLearner(_RingLearner):
 
     def __init__(self, buffer, actor, critic=None, *, critic_input="central", gamma=0.95, tau=0.01, lr_actor=1e-3, lr_critic=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=1):
-        if not isinstance(buffer, DeviceReplayBuffer):
-            raise ValueError(f"{type(self).__name__} needs a DeviceReplayBuffer (it samples on the device)")
+        mgn = self._ring(buffer, gamma, updates, max_grad_norm)
         if critic_input not in ("central", "own"):
             raise ValueError(f"critic_input must be 'central' or 'own', got {critic_input!r}")
-        self.buffer, self.central = buffer, critic_input == "central"
+        self.central = critic_input == "central"
         nA, Do, k, B = buffer.n_agents, buffer.actor_states.shape[2], buffer.n_actions, buffer.batch_size
         dev = buffer.actor_states.device
         Dc = _critic_width(nA, Do, k, self.central)
         self.nA, self.Do, self.k, self.B, self.Dc = nA, Do, k, B, Dc
-        self.gamma = _hyper("gamma", gamma)
-        self.updates = int(updates)
-        if self.updates < 1:
-            raise ValueError(f"updates must be >= 1, got {updates!r}")
-        mgn = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)
         if critic is None:
             critic = StackedActor(nA, Dc, 1, device=dev)
-        for net, name, want in ((actor, "actor", (nA, Do, k)), (critic, "critic", (nA, Dc, 1))):
-            have = tuple(getattr(net, a, None) for a in ("n_actors", "obs_len", "n_actions"))
-            if not _is_stacked(net) or have != want:
-                raise ValueError(f"{name} must be a StackedActor{want} for this buffer and critic_input={critic_input!r}, got "
-                                 f"{'StackedActor' + str(have) if None not in have else type(net).__name__}")
+        _stacked_shape(actor, "actor", (nA, Do, k), f" and critic_input={critic_input!r}")
+        _stacked_shape(critic, "critic", (nA, Dc, 1), f" and critic_input={critic_input!r}")
         f = _f32(torch.zeros, dev)                               # zero-filled: what no kernel of an update writes stays +0
         self._x_cur, self._x_next, self._x_pi = f(B, nA, Dc), f(B, nA, Dc), f(B, nA, Dc)
         _check_mlp(actor, buffer._b_obs, True, type(self).__name__)
@@ -338,12 +359,11 @@ class DDPGLearner(_RingLearner):
         self.step_actor, self.step_critic = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
         self.stats = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
         self.step_stats_actor, self.step_stats_critic = (torch.zeros((self.updates, 4), dtype=torch.float64, device=dev) for _ in range(2))
+        self._steps = [(self.step_actor, self.step_stats_actor), (self.step_critic, self.step_stats_critic)]
         self._y4, self._yq4, self._g_pi, self._g_a4 = (f(B, nA, 4) for _ in range(4))
         self.td = f(B, nA)
         self._head_ws = _workspace(None, td_head_workspace_bytes(B, nA), dev)        # (the three heads share one plan: one size)
         self._adam_ws = _workspace(None, mlp_adam_step_workspace_bytes(nA, 1), dev)
-        self._prioritized = isinstance(buffer, PrioritizedReplayBuffer)
-        self._graph = None
 
     def _update(self, u):
         """Update u of a call: the steps of the class's docstring, each a method of its own that a subclass overrides singly."""
@@ -394,14 +414,7 @@ class DDPGLearner(_RingLearner):
         _mlp_grad(lib, c.buf, c.blob, self._x_pi, self._g_pi, False, c.buf["gx"])
         ddpg_action_grad(c.buf["gx"], Do, k, central=central, out=self._g_a4)
         row_a = _mlp_grad(lib, self._buf_a, self._blob_a, obs, self._g_a4, True)
-        mlp_adam_step([self.actor], [row_a], [self.adam_actor], [self._blob_a], self.hyper_actor, self.step_actor,
-                      targets=[self.target_actor], target_blobs=[self._blob_ta], stats=self.step_stats_actor[u], workspace=self._adam_ws)
-
-    def _state(self):
-        """Every tensor an update writes that outlives it."""
-        return ([self.buffer._draws, self.step_actor, self.step_critic, self.stats, self.step_stats_actor, self.step_stats_critic]
-                + self._net_state()
-                + ([self.buffer._leaves, self.buffer.tree, self.buffer.max_priority] if self._prioritized else []))
+        self._adam_one(self._actor_net, row_a, self.hyper_actor, self.step_actor, self.step_stats_actor[u])
 
     def set_lr(self, actor=None, critic=None):
         """The learning rates of the steps from now on, written to the hyper rows on the device (fills on the current stream: no host

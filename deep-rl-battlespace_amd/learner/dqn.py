@@ -2,6 +2,7 @@
 
   dqn_head                              the (double) Q-learning target, independent or VDN-mixed, and the network's grad_out, in one pass
   DQNLearner(buffer, qnet, ...)         independent DQN or VDN of a team from its DeviceReplayBuffer; capture() makes it one graph
+  _QLearner                             what DQNLearner and qmix.QMIXLearner share: the Q network's half of the constructor and of an update
 
 The Q network of a team is the network its rollout plays, a StackedActor(nA, Do, 4), with Q_i(o, a) = q_scale * y4[i][a] on the
 tanh-squashed row of bsx_mlp_forward: the learner's greedy action and the action a published rollout plays are the same bits.  The
@@ -13,11 +14,10 @@ import torch
 
 from .. import _lib
 from .._args import _workspace
-from ..replay import DeviceReplayBuffer, PrioritizedReplayBuffer
 from ._common import _POSITIVE, _WEIGHT, _f32, _hyper, _ptr, _stream
-from .adam import adam_hyper, mlp_adam_step, mlp_adam_step_workspace_bytes
-from .ddpg import _head_args, _RingLearner
-from .mlp import _check_mlp, _is_stacked, _mlp_forward, _mlp_grad
+from .adam import adam_hyper, mlp_adam_step_workspace_bytes
+from .ddpg import _head_args, _RingLearner, _stacked_shape
+from .mlp import _check_mlp, _mlp_forward, _mlp_grad
 
 DqnHead = namedtuple("DqnHead", "g4 q td stats")
 DQN_STATS = ("n", "loss", "q", "target", "abs_td", "done", "weight", "greedy")
@@ -66,7 +66,66 @@ def dqn_head(y_cur, y_next_target, act, rew, done, gamma, *, q_scale, y_next_onl
     return DqnHead(g4, q, td, stats)
 
 
-class DQNLearner(_RingLearner):
+class _QLearner(_RingLearner):
+    """What DQNLearner and qmix.QMIXLearner share, and no learner on its own.  The constructor in its two halves, between which a
+    subclass refuses the shapes of its networks (every shape refusal comes before the first look at a network's tensors): `_q_args`, the
+    refusals and hypers that need no network, and `_q_state`, the Q network a rollout plays as the record `_actor_net` with its public
+    aliases, ONE hyper row, the Q network's step counter and statistics and the head's row buffers.  Of an update: the three forwards of
+    the Q network and what follows the head up to the Q network's gradient; and set_lr.  A subclass adds its head's workspace
+    `_head_ws` (and, with more networks, their records to `critics` and their pairs to `_steps`) and writes `_update(u)`."""
+
+    def _q_args(self, buffer, *, double, q_scale, huber_delta, gamma, updates, max_grad_norm):
+        """-> max_grad_norm as adam_hyper takes it; sets the hypers and `nA`, `Do`, `k`, `B`."""
+        mgn = self._ring(buffer, gamma, updates, max_grad_norm)
+        self.double = bool(double)
+        self.q_scale, self.huber_delta = _hyper("q_scale", q_scale, _POSITIVE), _hyper("huber_delta", huber_delta, _WEIGHT)
+        if buffer.n_actions != 4:
+            raise ValueError(f"{type(self).__name__} learns the discrete game: the ring must keep the four action scores (n_actions == 4), "
+                             f"got {buffer.n_actions}")
+        self.nA, self.Do, self.k, self.B = buffer.n_agents, buffer.actor_states.shape[2], 4, buffer.batch_size
+        return mgn
+
+    def _q_state(self, qnet, mgn, *, tau, lr, betas, eps):
+        """qnet: of the shape the subclass has checked (_stacked_shape)."""
+        buffer, nA, Do, B = self.buffer, self.nA, self.Do, self.B
+        dev = buffer.actor_states.device
+        _check_mlp(qnet, buffer._b_obs, True, type(self).__name__)
+        self.critics = []
+        self._actor_net = self._net(qnet, Do)
+        self.qnet, self.target_qnet, self._blob_q, self._blob_tq, self.adam, self._buf_q = self._actor_net[:6]
+        self.hyper = adam_hyper(lr, betas, eps, mgn, dev, tau)
+        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.stats = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
+        self.step_stats = torch.zeros((self.updates, 4), dtype=torch.float64, device=dev)
+        self._steps = [(self.step, self.step_stats)]
+        f = _f32(torch.zeros, dev)
+        self._y_cur, self._y_on, self._y_tg, self._g4 = (f(B, nA, 4) for _ in range(4))
+        self.q, self.td = f(B, nA), f(B, nA)
+        self._adam_ws = _workspace(None, mlp_adam_step_workspace_bytes(nA, 1), dev)
+
+    def _q_forwards(self):
+        """After the draw: the online network on obs -> y_cur, double=True: on obs_next -> y_next_online (double=False: no launch), the
+        target network on obs_next -> y_next_target.  -> (the library, y_next_online or None: what the head takes, the batch's weight or None)"""
+        lib, buf = _lib.load(), self.buffer
+        _mlp_forward(lib, self._blob_q, buf._b_obs, self._y_cur)
+        if self.double:
+            _mlp_forward(lib, self._blob_q, buf._b_obs_, self._y_on)
+        _mlp_forward(lib, self._blob_tq, buf._b_obs_, self._y_tg)
+        return lib, self._y_on if self.double else None, buf.weights if self._prioritized else None
+
+    def _after_head(self, lib):
+        """After the head: a prioritised ring's new priorities from (q, y), then the Q network's gradient from g4 -> its row."""
+        if self._prioritized:
+            self.buffer.update_priorities(self.q, self.td)
+        return _mlp_grad(lib, self._buf_q, self._blob_q, self.buffer._b_obs, self._g4, True)
+
+    def set_lr(self, lr):
+        """The learning rate of the steps from now on -- of every network the learner steps --, written to the hyper row on the device (a
+        fill on the current stream: no host synchronisation); a captured update reads it at every replay."""
+        self.hyper[0].fill_(_hyper("lr", lr))
+
+
+class DQNLearner(_QLearner):
     """Q-learning of a team for the discrete game from its replay ring, on device: independent DQN per agent (Mnih et al. 2015) or the
     value-decomposition mix of the team (mix="vdn"; Sunehag et al. 2018), double Q (van Hasselt et al. 2016), a soft target network, Adam.
 
@@ -108,66 +167,17 @@ class DQNLearner(_RingLearner):
 
     def __init__(self, buffer, qnet, *, mix="independent", double=True, q_scale, huber_delta=0.0, gamma=0.95, tau=0.01, lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=1):
-        if not isinstance(buffer, DeviceReplayBuffer):
-            raise ValueError(f"{type(self).__name__} needs a DeviceReplayBuffer (it samples on the device)")
         self.mix, self._mix = mix, _mix(mix)
-        self.double = bool(double)
-        self.q_scale, self.huber_delta = _hyper("q_scale", q_scale, _POSITIVE), _hyper("huber_delta", huber_delta, _WEIGHT)
-        self.gamma = _hyper("gamma", gamma)
-        self.updates = int(updates)
-        if self.updates < 1:
-            raise ValueError(f"updates must be >= 1, got {updates!r}")
-        mgn = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)
-        if buffer.n_actions != 4:
-            raise ValueError(f"{type(self).__name__} learns the discrete game: the ring must keep the four action scores (n_actions == 4), "
-                             f"got {buffer.n_actions}")
-        self.buffer = buffer
-        nA, Do, B = buffer.n_agents, buffer.actor_states.shape[2], buffer.batch_size
-        dev = buffer.actor_states.device
-        self.nA, self.Do, self.k, self.B = nA, Do, 4, B
-        have = tuple(getattr(qnet, a, None) for a in ("n_actors", "obs_len", "n_actions"))
-        if not _is_stacked(qnet) or have != (nA, Do, 4):
-            raise ValueError(f"qnet must be a StackedActor{(nA, Do, 4)} for this buffer, got "
-                             f"{'StackedActor' + str(have) if None not in have else type(qnet).__name__}")
-        _check_mlp(qnet, buffer._b_obs, True, type(self).__name__)
-        self.critics = []
-        self._actor_net = self._net(qnet, Do)
-        self.qnet, self.target_qnet, self._blob_q, self._blob_tq, self.adam, self._buf_q = self._actor_net[:6]
-        self.hyper = adam_hyper(lr, betas, eps, mgn, dev, tau)
-        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.stats = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
-        self.step_stats = torch.zeros((self.updates, 4), dtype=torch.float64, device=dev)
-        f = _f32(torch.zeros, dev)
-        self._y_cur, self._y_on, self._y_tg, self._g4 = (f(B, nA, 4) for _ in range(4))
-        self.q, self.td = f(B, nA), f(B, nA)
-        self._head_ws = _workspace(None, dqn_head_workspace_bytes(B, nA), dev)
-        self._adam_ws = _workspace(None, mlp_adam_step_workspace_bytes(nA, 1), dev)
-        self._prioritized = isinstance(buffer, PrioritizedReplayBuffer)
-        self._graph = None
+        mgn = self._q_args(buffer, double=double, q_scale=q_scale, huber_delta=huber_delta, gamma=gamma, updates=updates, max_grad_norm=max_grad_norm)
+        _stacked_shape(qnet, "qnet", (self.nA, self.Do, 4))
+        self._q_state(qnet, mgn, tau=tau, lr=lr, betas=betas, eps=eps)
+        self._head_ws = _workspace(None, dqn_head_workspace_bytes(self.B, self.nA), self.hyper.device)
 
     def _update(self, u):
         """Update u of a call: the steps of the class's docstring."""
-        lib, buf = _lib.load(), self.buffer
+        buf = self.buffer
         buf.sample()
-        _mlp_forward(lib, self._blob_q, buf._b_obs, self._y_cur)
-        if self.double:
-            _mlp_forward(lib, self._blob_q, buf._b_obs_, self._y_on)
-        _mlp_forward(lib, self._blob_tq, buf._b_obs_, self._y_tg)
-        dqn_head(self._y_cur, self._y_tg, buf._b_act, buf._b_rew, buf._b_done, self.gamma, q_scale=self.q_scale,
-                 y_next_online=self._y_on if self.double else None, mix=self.mix, huber_delta=self.huber_delta,
-                 weight=buf.weights if self._prioritized else None, out=(self._g4, self.q, self.td, self.stats[u]), workspace=self._head_ws)
-        if self._prioritized:
-            buf.update_priorities(self.q, self.td)
-        row = _mlp_grad(lib, self._buf_q, self._blob_q, buf._b_obs, self._g4, True)
-        mlp_adam_step([self.qnet], [row], [self.adam], [self._blob_q], self.hyper, self.step, targets=[self.target_qnet],
-                      target_blobs=[self._blob_tq], stats=self.step_stats[u], workspace=self._adam_ws)
-
-    def _state(self):
-        """Every tensor an update writes that outlives it."""
-        return ([self.buffer._draws, self.step, self.stats, self.step_stats] + self._net_state()
-                + ([self.buffer._leaves, self.buffer.tree, self.buffer.max_priority] if self._prioritized else []))
-
-    def set_lr(self, lr):
-        """The learning rate of the steps from now on, written to the hyper row on the device (a fill on the current stream: no host
-        synchronisation); a captured update reads it at every replay."""
-        self.hyper[0].fill_(_hyper("lr", lr))
+        lib, y_on, weight = self._q_forwards()
+        dqn_head(self._y_cur, self._y_tg, buf._b_act, buf._b_rew, buf._b_done, self.gamma, q_scale=self.q_scale, y_next_online=y_on, mix=self.mix,
+                 huber_delta=self.huber_delta, weight=weight, out=(self._g4, self.q, self.td, self.stats[u]), workspace=self._head_ws)
+        self._adam_one(self._actor_net, self._after_head(lib), self.hyper, self.step, self.step_stats[u])

@@ -9,7 +9,8 @@ and the learner around it.
 The Q network is dqn.py's: the StackedActor(nA, Do, 4) the rollout plays, Q_i(o, a) = q_scale * tanh row.  The mixer is a
 StackedActor(Mh, nA Do, 4) whose tanh rows on the team's joint observation are the weights of the monotone mix (the hypernetwork of
 Rashid et al. 2018), so its forward, backward, Adam step, Polyak target and packed blobs are the fused MLP kernels' own.  The ring, the
-networks' records, capture(), sync() and publish() are ddpg.py's (_RingLearner); qmix_head's argument check is its _head_args.
+networks' records, capture(), sync() and publish() are ddpg.py's (_RingLearner), the Q network's half of the constructor and of an
+update dqn.py's (_QLearner); qmix_head's argument check is ddpg.py's _head_args.
 """
 from collections import namedtuple
 from functools import partial
@@ -18,12 +19,12 @@ import torch
 
 from .. import _lib
 from .._args import _F32, _need, _workspace
-from ..replay import DeviceReplayBuffer, PrioritizedReplayBuffer
 from ..rollout import StackedActor
 from ._common import _POSITIVE, _WEIGHT, _f32, _hyper, _ptr, _stream
-from .adam import adam_hyper, mlp_adam_step, mlp_adam_step_workspace_bytes
-from .ddpg import _head_args, _RingLearner
-from .mlp import _check_mlp, _is_stacked, _mlp_forward, _mlp_grad
+from .adam import mlp_adam_step_workspace_bytes
+from .ddpg import _head_args, _stacked_shape
+from .dqn import _QLearner
+from .mlp import _check_mlp, _mlp_forward, _mlp_grad
 
 QmixHead = namedtuple("QmixHead", "g4 gh q td stats")
 QMIX_STATS = ("n", "loss", "q_tot", "target", "abs_td", "done", "weight", "greedy")
@@ -129,7 +130,7 @@ def qmix_head(y_cur, y_next_target, hy_cur, hy_next_target, act, rew, done, gamm
     return QmixHead(g4, gh, q, td, stats)
 
 
-class QMIXLearner(_RingLearner):
+class QMIXLearner(_QLearner):
     """QMIX of a team for the discrete game from its replay ring, on device (Rashid et al. 2018): per-plane Q networks, a monotone
     mixing network whose weights a hypernetwork makes from the team's joint observation, double Q, soft target networks, Adam.  What
     DQNLearner(mix="vdn") cannot represent -- a team value that is not a sum of per-plane terms: a base that falls to combined fire, a
@@ -173,83 +174,41 @@ class QMIXLearner(_RingLearner):
 
     def __init__(self, buffer, qnet, mixer=None, *, embed=8, double=True, q_scale, huber_delta=0.0, gamma=0.95, tau=0.01, lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, updates=1):
-        if not isinstance(buffer, DeviceReplayBuffer):
-            raise ValueError(f"{type(self).__name__} needs a DeviceReplayBuffer (it samples on the device)")
-        self.double = bool(double)
-        self.q_scale, self.huber_delta = _hyper("q_scale", q_scale, _POSITIVE), _hyper("huber_delta", huber_delta, _WEIGHT)
-        self.gamma = _hyper("gamma", gamma)
-        self.updates = int(updates)
-        if self.updates < 1:
-            raise ValueError(f"updates must be >= 1, got {updates!r}")
-        mgn = None if max_grad_norm is None else _hyper("max_grad_norm", max_grad_norm, _POSITIVE)
-        if buffer.n_actions != 4:
-            raise ValueError(f"{type(self).__name__} learns the discrete game: the ring must keep the four action scores (n_actions == 4), "
-                             f"got {buffer.n_actions}")
-        self.buffer = buffer
-        nA, Do, B = buffer.n_agents, buffer.actor_states.shape[2], buffer.batch_size
-        dev = buffer.actor_states.device
+        mgn = self._q_args(buffer, double=double, q_scale=q_scale, huber_delta=huber_delta, gamma=gamma, updates=updates, max_grad_norm=max_grad_norm)
+        nA, Do, B, dev = self.nA, self.Do, self.B, buffer.actor_states.device
         Mh = qmix_members(nA, embed)                                # refuses the embed, then the team
         S = _joint_width(nA, Do)
-        self.nA, self.Do, self.k, self.B, self.embed, self.members, self.S = nA, Do, 4, B, int(embed), Mh, S
+        self.embed, self.members, self.S = int(embed), Mh, S
         if mixer is None:
             mixer = StackedActor(Mh, S, 4, device=dev)
-        for net, name, want in ((qnet, "qnet", (nA, Do, 4)), (mixer, "mixer", (Mh, S, 4))):
-            have = tuple(getattr(net, a, None) for a in ("n_actors", "obs_len", "n_actions"))
-            if not _is_stacked(net) or have != want:
-                raise ValueError(f"{name} must be a StackedActor{want} for this buffer and embed={int(embed)}, got "
-                                 f"{'StackedActor' + str(have) if None not in have else type(net).__name__}")
+        _stacked_shape(qnet, "qnet", (nA, Do, 4), f" and embed={int(embed)}")
+        _stacked_shape(mixer, "mixer", (Mh, S, 4), f" and embed={int(embed)}")
+        self._q_state(qnet, mgn, tau=tau, lr=lr, betas=betas, eps=eps)
         f = _f32(torch.zeros, dev)
         self._x_cur, self._x_next = f(B, Mh, S), f(B, Mh, S)
-        _check_mlp(qnet, buffer._b_obs, True, type(self).__name__)
         _check_mlp(mixer, self._x_cur, True, type(self).__name__)
-        self.critics = []
-        self._actor_net = self._net(qnet, Do)
         self._mixer_net = self._net(mixer, S, members=Mh)
         self.critics.append(self._mixer_net)                        # the second network sync() and the state list run over
-        self.qnet, self.target_qnet, self._blob_q, self._blob_tq, self.adam, self._buf_q = self._actor_net[:6]
         self.mixer, self.target_mixer, self._blob_m, self._blob_tm, self.adam_mixer, self._buf_m = self._mixer_net[:6]
-        self.hyper = adam_hyper(lr, betas, eps, mgn, dev, tau)
-        self.step, self.step_mixer = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
-        self.stats = torch.zeros((self.updates, 8), dtype=torch.float64, device=dev)
-        self.step_stats, self.step_stats_mixer = (torch.zeros((self.updates, 4), dtype=torch.float64, device=dev) for _ in range(2))
-        self._y_cur, self._y_on, self._y_tg, self._g4 = (f(B, nA, 4) for _ in range(4))
+        self.step_mixer = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.step_stats_mixer = torch.zeros((self.updates, 4), dtype=torch.float64, device=dev)
+        self._steps.append((self.step_mixer, self.step_stats_mixer))
         self._hy_cur, self._hy_tg, self._gh = (f(B, Mh, 4) for _ in range(3))
-        self.q, self.td = f(B, nA), f(B, nA)
         self._head_ws = _workspace(None, qmix_head_workspace_bytes(B, nA), dev)
         self._adam_ws = _workspace(None, max(mlp_adam_step_workspace_bytes(nA, 1), mlp_adam_step_workspace_bytes(Mh, 1)), dev)
-        self._prioritized = isinstance(buffer, PrioritizedReplayBuffer)
-        self._graph = None
 
     def _update(self, u):
         """Update u of a call: the steps of the class's docstring."""
-        lib, buf = _lib.load(), self.buffer
+        buf = self.buffer
         buf.sample()
-        _mlp_forward(lib, self._blob_q, buf._b_obs, self._y_cur)
-        if self.double:
-            _mlp_forward(lib, self._blob_q, buf._b_obs_, self._y_on)
-        _mlp_forward(lib, self._blob_tq, buf._b_obs_, self._y_tg)
+        lib, y_on, weight = self._q_forwards()
         qmix_inputs(buf._b_obs, buf._b_obs_, self.members, out=(self._x_cur, self._x_next))
         _mlp_forward(lib, self._blob_m, self._x_cur, self._hy_cur)
         _mlp_forward(lib, self._blob_tm, self._x_next, self._hy_tg)
         qmix_head(self._y_cur, self._y_tg, self._hy_cur, self._hy_tg, buf._b_act, buf._b_rew, buf._b_done, self.gamma, embed=self.embed,
-                  q_scale=self.q_scale, y_next_online=self._y_on if self.double else None, huber_delta=self.huber_delta,
-                  weight=buf.weights if self._prioritized else None, out=(self._g4, self._gh, self.q, self.td, self.stats[u]),
-                  workspace=self._head_ws)
-        if self._prioritized:
-            buf.update_priorities(self.q, self.td)
-        row_q = _mlp_grad(lib, self._buf_q, self._blob_q, buf._b_obs, self._g4, True)
+                  q_scale=self.q_scale, y_next_online=y_on, huber_delta=self.huber_delta, weight=weight,
+                  out=(self._g4, self._gh, self.q, self.td, self.stats[u]), workspace=self._head_ws)
+        row_q = self._after_head(lib)
         row_m = _mlp_grad(lib, self._buf_m, self._blob_m, self._x_cur, self._gh, True)
-        mlp_adam_step([self.qnet], [row_q], [self.adam], [self._blob_q], self.hyper, self.step, targets=[self.target_qnet],
-                      target_blobs=[self._blob_tq], stats=self.step_stats[u], workspace=self._adam_ws)
-        mlp_adam_step([self.mixer], [row_m], [self.adam_mixer], [self._blob_m], self.hyper, self.step_mixer, targets=[self.target_mixer],
-                      target_blobs=[self._blob_tm], stats=self.step_stats_mixer[u], workspace=self._adam_ws)
-
-    def _state(self):
-        """Every tensor an update writes that outlives it."""
-        return ([self.buffer._draws, self.step, self.step_mixer, self.stats, self.step_stats, self.step_stats_mixer] + self._net_state()
-                + ([self.buffer._leaves, self.buffer.tree, self.buffer.max_priority] if self._prioritized else []))
-
-    def set_lr(self, lr):
-        """The learning rate of both networks' steps from now on, written to the hyper row on the device (a fill on the current stream:
-        no host synchronisation); a captured update reads it at every replay."""
-        self.hyper[0].fill_(_hyper("lr", lr))
+        self._adam_one(self._actor_net, row_q, self.hyper, self.step, self.step_stats[u])
+        self._adam_one(self._mixer_net, row_m, self.hyper, self.step_mixer, self.step_stats_mixer[u])

@@ -17,7 +17,7 @@ from .._args import _F32, _need, _workspace
 from ..rollout import StackedActor
 from ._common import _U64, _WEIGHT, _hyper, _int64_word, _ptr, _stream
 from .adam import mlp_adam_step_workspace_bytes
-from .ddpg import DDPGLearner, _batch_rows, _critic_width, _head_args
+from .ddpg import DDPGLearner, _batch_rows, _critic_width, _head_args, _stacked_shape
 from .mlp import _check_mlp, _mlp_forward
 
 Td3Head = namedtuple("Td3Head", "g_q1 g_q2 g_pi td stats")
@@ -92,10 +92,7 @@ class _TwinCriticLearner(DDPGLearner):
         nA, Dc, dev = self.nA, self.Dc, self._x_cur.device
         if critic2 is None:
             critic2 = StackedActor(nA, Dc, 1, device=dev)
-        have = tuple(getattr(critic2, a, None) for a in ("n_actors", "obs_len", "n_actions"))
-        if have != (nA, Dc, 1):
-            raise ValueError(f"critic2 must be a StackedActor{(nA, Dc, 1)} for this buffer and critic_input={critic_input!r}, got "
-                             f"{'StackedActor' + str(have) if None not in have else type(critic2).__name__}")
+        _stacked_shape(critic2, "critic2", (nA, Dc, 1), f" and critic_input={critic_input!r}")
         _check_mlp(critic2, self._x_cur, False, type(self).__name__)
         self.critic2, self.target_critic2, self._blob_c2, self._blob_tc2, self.adam_critic2 = self._net(critic2, Dc, critic=True, gx=gx2)[:5]
         self._noise_draws = torch.zeros(1, dtype=torch.int64, device=dev)

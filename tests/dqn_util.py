@@ -34,6 +34,7 @@ import actor_grad_util as U
 import ddpg_util as D
 import mlp_grad_util as M
 import offpolicy_util as O
+import qlearn_util as QL
 import yardstick_util as Y
 
 PARAMS = U.PARAMS
@@ -106,7 +107,7 @@ def contract32(inp, gamma=GAMMA, q_scale=Q_SCALE, delta=0.0, double=True, mix="i
     f = {k: v.numpy() for k, v in inp.items()}
     f32 = np.float32
     B, nA = f["rew"].shape
-    qs, dl, s2 = f32(q_scale), f32(delta), f32(2.0 / B)
+    qs = f32(q_scale)
     with np.errstate(all="ignore"):
         a = argmax4(f["act"])
         an = argmax4(f["y_next_online"] if double else f["y_next_target"])
@@ -122,11 +123,7 @@ def contract32(inp, gamma=GAMMA, q_scale=Q_SCALE, delta=0.0, double=True, mix="i
         else:
             Q, N, R = qc, qn, rew
             w = f["weight"] if weight else np.ones((B, nA), f32)
-        w = w.astype(f32)
-        y = _fmaf32(gamma, N, R)
-        d = (Q - y).astype(f32)
-        c = np.where((dl > 0) & (d == d), np.minimum(np.maximum(d, -dl), dl), d).astype(f32) if delta > 0 else d
-        g = (((w * c).astype(f32) * s2).astype(f32) * qs).astype(f32)
+        y, g = QL.tail32(_fmaf32, Q, N, R, w.astype(f32), gamma, q_scale, delta, B)
     g4 = np.zeros((B, nA, 4), f32)
     np.put_along_axis(g4, a[..., None], g[..., None], -1)
     return dict(g4=g4, q=Q.astype(f32), td=y)
@@ -148,15 +145,10 @@ def ref64(inp, gamma=GAMMA, q_scale=Q_SCALE, delta=0.0, double=True, mix="indepe
         if mix == "vdn":
             Q, N, R = (np.repeat(x.sum(1, keepdims=True), nA, 1) for x in (qc, qn, f["rew"]))
             w = np.repeat(w[:, :1], nA, 1)
-        y = gamma * N + R
-        d = Q - y
-        c = np.clip(d, -delta, delta) if delta > 0 else d
-        loss = np.where(np.abs(d) <= delta, d * d, delta * (2 * np.abs(d) - delta)) if delta > 0 else d * d
+        y, d, loss, g = QL.tail64(Q, N, R, w, gamma, q_scale, delta, B)
         g4 = np.zeros((B, nA, 4))
-        np.put_along_axis(g4, a[..., None], (w * c * (2.0 / B) * q_scale)[..., None], -1)
-        n = float(B * nA)
-        stats = np.array([n, (w * loss).sum() / n, Q.sum() / n, y.sum() / n, np.abs(d).sum() / n, over.sum() / n, w.sum() / n,
-                          (a == argmax4(f["y_cur"])).sum() / n])
+        np.put_along_axis(g4, a[..., None], g[..., None], -1)
+        stats = QL.stats64(float(B * nA), w, loss, Q, y, d, over, a == argmax4(f["y_cur"]))
     return dict(g4=g4, q=Q, td=y, stats=stats)
 
 
@@ -173,11 +165,7 @@ def torch_loss(y_cur, y_on, y_tg, act, rew, done, w, dtype, gamma, q_scale, delt
         y = R + float(np.float32(gamma)) * N
     if mix == "vdn":
         Q = Q.sum(1, keepdim=True)
-    if delta > 0:
-        el = 2.0 * delta * torch.nn.functional.smooth_l1_loss(Q, y, reduction="none", beta=delta)
-    else:
-        el = torch.nn.functional.mse_loss(Q, y, reduction="none")
-    el = w * el
+    el = w * QL.element_loss(Q, y, delta)
     nA = act.shape[1]
     full = lambda x: x.expand(-1, nA)                                               # noqa: E731
     return el.mean(0).sum(), full(Q), full(y), full(el), full(w)
@@ -306,31 +294,20 @@ def head_case_of(BnA, form):
 
 def stats_out_of_bounds(got, ref, e_stats, what=""):
     """n and the two counts' means (done, greedy: exact in float64) exactly; the others by yardstick_util.scalar_bound."""
-    exact = [name for i, name in ((0, "n"), (5, "done"), (7, "greedy")) if got[i] != ref[i]]
-    return exact + Y.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, what)
+    return QL.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, ((0, "n"), (5, "done"), (7, "greedy")), what)
 
 
 def guarded_head(inp, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, fill=7.0, td=True, keep=None):
-    """learner.dqn_head on `inp` with every input, output and the workspace between guard slabs (guarded) and every output float starting
-    as `fill` -> (the binding's result: the `out` tensors themselves, the strays).  offpolicy_util.guarded_head for this head's outputs.
-    keep: a dict that receives the workspace (int64, every word -1 before the call) as [workgroups, 8] partial rows."""
+    """learner.dqn_head between guard slabs: qlearn_util.guarded_head (its arguments) for this head's outputs and binding."""
     from deep_rl_battlespace_amd import learner as L
-    from guard_util import Buffers
     mix, dbl, delta, w = form
     B, nA = inp["rew"].shape
-    G = Buffers(guarded)
-    dev = O.put(G, inp)
-    out = (G("g4", (B, nA, 4), torch.float32, init=fill), G("q", (B, nA), torch.float32, init=fill),
-           G("td", (B, nA), torch.float32, init=fill) if td else None, G("stats", (8,), torch.float64, init=fill))
-    ws = G("workspace", (L.dqn_head_workspace_bytes(B, nA) // 8,), torch.int64, init=-1)
-    res = L.dqn_head(dev["y_cur"], dev["y_next_target"], dev["act"], dev["rew"], dev["done"], gamma, q_scale=q_scale,
-                     y_next_online=dev["y_next_online"] if dbl else None, mix=mix, huber_delta=delta, weight=dev["weight"] if w else None,
-                     out=out, workspace=ws)
-    torch.cuda.synchronize()
-    assert all(a is b for a, b in zip(res, out))
-    if keep is not None:
-        keep["workspace"] = ws.view(-1, 8)
-    return res, G.stray()
+
+    def call(dev, out, ws):
+        return L.dqn_head(dev["y_cur"], dev["y_next_target"], dev["act"], dev["rew"], dev["done"], gamma, q_scale=q_scale,
+                          y_next_online=dev["y_next_online"] if dbl else None, mix=mix, huber_delta=delta, weight=dev["weight"] if w else None,
+                          out=out, workspace=ws)
+    return QL.guarded_head(inp, (("g4", (B, nA, 4)), ("q", (B, nA))), L.dqn_head_workspace_bytes(B, nA), call, guarded, fill, td, keep)
 
 
 # ------------------------------------------------------------------------------------------------ a whole update
@@ -464,58 +441,22 @@ def stepped_case(team, mix, batch_size=B):
 
 
 # ------------------------------------------------------------------------------------------------ one update by hand
-STATE = ("_blob_q", "_blob_tq", "step", "stats", "step_stats")
+snapshot, step_arrays = QL.snapshot, QL.step_arrays     # of the one network "qnet": the defaults
 
 
-def snapshot(x):
-    """{name: bits} of everything an update of x (a DQNLearner or a Hand) writes that outlives it: the blobs, the step word, the
-    statistics, the network, its target and moments, the ring's draw counter and, of a prioritised ring, leaves, tree and max_priority."""
-    torch.cuda.synchronize()
-    out = {k: getattr(x, k).detach().clone() for k in STATE}
-    out["draws"] = x.buffer._draws.clone()
-    for name in ("qnet", "target_qnet"):
-        for p in PARAMS:
-            out[f"{name}.{p}"] = getattr(getattr(x, name), p).detach().clone()
-    out["adam.m"], out["adam.v"] = x.adam.m.clone(), x.adam.v.clone()
-    if hasattr(x.buffer, "tree"):
-        out.update(leaves=x.buffer._leaves.clone(), tree=x.buffer.tree.clone(), max_priority=x.buffer.max_priority.clone())
-    return {k: (v.view(torch.int32) if v.dtype == torch.float32 else v.view(torch.int64) if v.dtype == torch.float64 else v) for k, v in out.items()}
+class Hand(QL.Hand):
+    """What a DQNLearner holds, under the same names (qlearn_util.Hand), and its update written out with the public primitives alone:
+    the ring's sample(), bsx_mlp_forward (offpolicy_util.Hand.forward), dqn_head, update_priorities, mlp_grad, mlp_adam_step."""
 
-
-class Hand:
-    """What a DQNLearner holds, under the same names, and its update written out with the public primitives alone: the ring's sample(),
-    bsx_mlp_forward (offpolicy_util.Hand.forward), dqn_head, update_priorities, mlp_grad, mlp_adam_step."""
-
-    def __init__(self, buffer, qnet, mix="independent", double=True, q_scale=Q_SCALE, huber_delta=0.0, gamma=GAMMA, tau=0.01, lr=1e-3,
-                 max_grad_norm=None, updates=1, betas=(0.9, 0.999), eps=1e-8):
-        from deep_rl_battlespace_amd import learner as L
-        self.buffer, self.mix, self.double, self.q_scale, self.huber_delta, self.gamma, self.updates = buffer, mix, double, q_scale, huber_delta, gamma, updates
-        self.prioritized = hasattr(buffer, "tree")
-        self.qnet = self.actor = qnet                                               # (actor: what offpolicy_loop_util.twin_publish copies)
-        self.target_qnet = copy.deepcopy(qnet)
-        self.target_qnet.__dict__.pop("_bsx_mlp_buffers", None)
-        self._blob_q, self._blob_tq, self.adam = qnet.pack(), self.target_qnet.pack(), L.AdamState(qnet)
-        dev = qnet.w1.device
-        self.hyper = L.adam_hyper(lr, betas, eps, max_grad_norm, dev, tau)
-        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.stats = torch.zeros((updates, 8), dtype=torch.float64, device=dev)
-        self.step_stats = torch.zeros((updates, 4), dtype=torch.float64, device=dev)
-        self.q = self.td = None
-
-    def update(self):
-        for u in range(self.updates):
-            self.one(*O.batch_of(self.buffer.sample()), u, weight=self.buffer.weights if self.prioritized else None)
-        return self.stats
-
-    forward = O.Hand.forward
+    def __init__(self, buffer, qnet, mix="independent", q_scale=Q_SCALE, gamma=GAMMA, **kw):
+        super().__init__(buffer, dict(qnet=qnet), q_scale=q_scale, gamma=gamma, **kw)
+        self.mix = mix
 
     def one(self, obs, act, rew, obs_next, done, u, weight=None, adam=True):
         """The seven steps on a batch -> the network's gradient row (a copy of mlp_grad's cached row)."""
         from deep_rl_battlespace_amd import learner as L
         obs, act, obs_next = obs.contiguous(), act.contiguous(), obs_next.contiguous()
-        y_cur = self.forward(self._blob_q, obs)
-        y_on = self.forward(self._blob_q, obs_next) if self.double else None
-        y_tg = self.forward(self._blob_tq, obs_next)
+        y_cur, y_on, y_tg = self.q_rows(obs, obs_next)
         head = L.dqn_head(y_cur, y_tg, act, rew, done, self.gamma, q_scale=self.q_scale, y_next_online=y_on, mix=self.mix,
                           huber_delta=self.huber_delta, weight=weight)
         self.stats[u].copy_(head.stats)
@@ -527,13 +468,6 @@ class Hand:
             L.mlp_adam_step([self.qnet], [row], [self.adam], [self._blob_q], self.hyper, self.step, targets=[self.target_qnet],
                             target_blobs=[self._blob_tq], stats=self.step_stats[u])
         return row
-
-
-def step_arrays(x):
-    """dict(p, m, v, target) of lists of ten numpy arrays: x's network, its moments and its target (offpolicy_util.step_arrays' form)."""
-    import adam_util as AU
-    cut = lambda row: AU.row_to_tensors(row.detach().cpu().numpy(), 4)              # noqa: E731
-    return dict(p=AU.net_arrays(x.qnet), m=cut(x.adam.m), v=cut(x.adam.v), target=AU.net_arrays(x.target_qnet))
 
 
 def learner_and_hand(team, prioritized=False, rows=None, seed=0, batch_size=B, **kw):

@@ -32,6 +32,7 @@ import ddpg_util as D
 import dqn_util as Q
 import mlp_grad_util as M
 import offpolicy_util as O
+import qlearn_util as QL
 import yardstick_util as Y
 
 PARAMS = U.PARAMS
@@ -138,7 +139,7 @@ def contract32(inp, embed, gamma=GAMMA, q_scale=Q_SCALE, delta=0.0, double=True,
     f32 = np.float32
     B, nA = f["rew"].shape
     m = embed // 4
-    qs, dl, s2 = f32(q_scale), f32(delta), f32(2.0 / B)
+    qs = f32(q_scale)
     with np.errstate(all="ignore"):
         a = argmax4(f["act"])
         an = argmax4(f["y_next_online"] if double else f["y_next_target"])
@@ -149,14 +150,11 @@ def contract32(inp, embed, gamma=GAMMA, q_scale=Q_SCALE, delta=0.0, double=True,
         R = f["rew"][:, 0].astype(f32).copy()
         for i in range(1, nA):
             R = (R + f["rew"][:, i]).astype(f32)
-        y = fmaf32(np.full(B, gamma, f32), N, R)
         u = Q._take(f["y_cur"], a).astype(f32)
         tot, h, sl = mix32(u, f["hy_cur"], embed)
         Qt = (qs * tot).astype(f32)
         w = f["weight"][:, 0].astype(f32) if weight else np.ones(B, f32)
-        d = (Qt - y).astype(f32)
-        c = np.where(d == d, np.minimum(np.maximum(d, -dl), dl), d).astype(f32) if delta > 0 else d
-        G = (((w * c).astype(f32) * s2).astype(f32) * qs).astype(f32)
+        y, G = QL.tail32(fmaf32, Qt, N, R, w, gamma, q_scale, delta, B)
         t1, _, t2, _ = split(f["hy_cur"], nA, embed)
         W1 = np.abs(t1)
         ws = (np.abs(t2) * sl).astype(f32)
@@ -201,15 +199,11 @@ def ref64(inp, embed, gamma=GAMMA, q_scale=Q_SCALE, delta=0.0, double=True, weig
         over = fin.all(1)
         un = np.where(fin, 0.0, Q._take(f["y_next_target"], an))
         N = np.where(over, 0.0, q_scale * mix64(un, f["hy_next_target"], embed)[0])
-        y = gamma * N + f["rew"].sum(1)
         u = Q._take(f["y_cur"], a)
         tot, h, sl = mix64(u, f["hy_cur"], embed)
         Qt = q_scale * tot
         w = f["weight"][:, 0] if weight else np.ones(B)
-        d = Qt - y
-        c = np.clip(d, -delta, delta) if delta > 0 else d
-        loss = np.where(np.abs(d) <= delta, d * d, delta * (2 * np.abs(d) - delta)) if delta > 0 else d * d
-        G = w * c * (2.0 / B) * q_scale
+        y, d, loss, G = QL.tail64(Qt, N, f["rew"].sum(1), w, gamma, q_scale, delta, B)
         t1, _, t2, _ = split(f["hy_cur"], nA, embed)
         ws = np.abs(t2) * sl
         g4 = np.zeros((B, nA, 4))
@@ -220,9 +214,7 @@ def ref64(inp, embed, gamma=GAMMA, q_scale=Q_SCALE, delta=0.0, double=True, weig
         gh[:, k:k + m] = (G[:, None] * ws).reshape(B, m, 4)
         gh[:, k + m:k + 2 * m] = (G[:, None] * h * np.sign(t2)).reshape(B, m, 4)
         gh[:, k + 2 * m, 0] = G
-        greedy = (a == argmax4(f["y_cur"])).mean(1)
-        n = float(B)
-        stats = np.array([n, (w * loss).sum() / n, Qt.sum() / n, y.sum() / n, np.abs(d).sum() / n, over.sum() / n, w.sum() / n, greedy.sum() / n])
+        stats = QL.stats64(float(B), w, loss, Qt, y, d, over, (a == argmax4(f["y_cur"])).mean(1))
     rep = lambda x: np.repeat(x[:, None], nA, 1)                                    # noqa: E731
     return dict(g4=g4, gh=gh, q=rep(Qt), td=rep(y), stats=stats)
 
@@ -250,11 +242,7 @@ def torch_loss(y_cur, hy_cur, y_on, y_tg, hy_tg, act, rew, done, w, dtype, gamma
         un = torch.where(done != 0, torch.zeros((), dtype=dtype), nxt)
         N = torch.where((done != 0).all(1), torch.zeros((), dtype=dtype), q_scale * torch_mix(un, hy_tg, embed))
         y = rew.sum(1) + float(np.float32(gamma)) * N
-    if delta > 0:
-        el = 2.0 * delta * torch.nn.functional.smooth_l1_loss(Qt, y, reduction="none", beta=delta)
-    else:
-        el = torch.nn.functional.mse_loss(Qt, y, reduction="none")
-    el = w * el
+    el = w * QL.element_loss(Qt, y, delta)
     return el.mean(), Qt, y, el, w
 
 
@@ -390,32 +378,22 @@ def head_case_of(shape, form):
 
 def stats_out_of_bounds(got, ref, e_stats, what=""):
     """n and the mean of `over` (a count: exact in float64) exactly; the others by yardstick_util.scalar_bound."""
-    exact = [name for i, name in ((0, "n"), (5, "done")) if got[i] != ref[i]]
-    return exact + Y.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, what)
+    return QL.stats_out_of_bounds(got, ref, e_stats, STAT_NAMES, ((0, "n"), (5, "done")), what)
 
 
 def guarded_head(inp, embed, form, gamma=GAMMA, q_scale=Q_SCALE, guarded=False, fill=7.0, td=True, keep=None):
-    """learner.qmix_head on `inp` with every input, output and the workspace between guard slabs (guarded) and every output float starting
-    as `fill` -> (the binding's result: the `out` tensors themselves, the strays).  keep: a dict that receives the workspace (int64, every
-    word -1 before the call) as [workgroups, 8] partial rows."""
+    """learner.qmix_head between guard slabs: qlearn_util.guarded_head (its arguments) for this head's outputs and binding."""
     from deep_rl_battlespace_amd import learner as L
-    from guard_util import Buffers
     dbl, delta, w = form
     B, nA = inp["rew"].shape
     Mh = members(nA, embed)
-    G = Buffers(guarded)
-    dev = O.put(G, inp)
-    out = (G("g4", (B, nA, 4), torch.float32, init=fill), G("gh", (B, Mh, 4), torch.float32, init=fill), G("q", (B, nA), torch.float32, init=fill),
-           G("td", (B, nA), torch.float32, init=fill) if td else None, G("stats", (8,), torch.float64, init=fill))
-    ws = G("workspace", (L.qmix_head_workspace_bytes(B, nA) // 8,), torch.int64, init=-1)
-    res = L.qmix_head(dev["y_cur"], dev["y_next_target"], dev["hy_cur"], dev["hy_next_target"], dev["act"], dev["rew"], dev["done"], gamma,
-                      embed=embed, q_scale=q_scale, y_next_online=dev["y_next_online"] if dbl else None, huber_delta=delta,
-                      weight=dev["weight"] if w else None, out=out, workspace=ws)
-    torch.cuda.synchronize()
-    assert all(a is b for a, b in zip(res, out))
-    if keep is not None:
-        keep["workspace"] = ws.view(-1, 8)
-    return res, G.stray()
+
+    def call(dev, out, ws):
+        return L.qmix_head(dev["y_cur"], dev["y_next_target"], dev["hy_cur"], dev["hy_next_target"], dev["act"], dev["rew"], dev["done"], gamma,
+                           embed=embed, q_scale=q_scale, y_next_online=dev["y_next_online"] if dbl else None, huber_delta=delta,
+                           weight=dev["weight"] if w else None, out=out, workspace=ws)
+    return QL.guarded_head(inp, (("g4", (B, nA, 4)), ("gh", (B, Mh, 4)), ("q", (B, nA))), L.qmix_head_workspace_bytes(B, nA), call, guarded, fill,
+                           td, keep)
 
 
 def guarded_inputs(obs, obs_next, Mh, fill=7.0):
@@ -568,63 +546,27 @@ def stepped_case(team, batch_size=B):
 
 
 # ------------------------------------------------------------------------------------------------ one update by hand
-STATE = ("_blob_q", "_blob_tq", "_blob_m", "_blob_tm", "step", "step_mixer", "stats", "step_stats", "step_stats_mixer")
-NETS = ("qnet", "target_qnet", "mixer", "target_mixer")
+NETS = ("qnet", "mixer")
 
 
 def snapshot(x):
-    """{name: bits} of everything an update of x (a QMIXLearner or a Hand) writes that outlives it."""
-    torch.cuda.synchronize()
-    out = {k: getattr(x, k).detach().clone() for k in STATE}
-    out["draws"] = x.buffer._draws.clone()
-    for name in NETS:
-        for p in PARAMS:
-            out[f"{name}.{p}"] = getattr(getattr(x, name), p).detach().clone()
-    for name in ("adam", "adam_mixer"):
-        out[name + ".m"], out[name + ".v"] = getattr(x, name).m.clone(), getattr(x, name).v.clone()
-    if hasattr(x.buffer, "tree"):
-        out.update(leaves=x.buffer._leaves.clone(), tree=x.buffer.tree.clone(), max_priority=x.buffer.max_priority.clone())
-    return {k: (v.view(torch.int32) if v.dtype == torch.float32 else v.view(torch.int64) if v.dtype == torch.float64 else v) for k, v in out.items()}
+    """{name: bits} of everything an update of x (a QMIXLearner or a Hand) writes that outlives it: qlearn_util.snapshot of both networks."""
+    return QL.snapshot(x, NETS)
 
 
-class Hand:
-    """What a QMIXLearner holds, under the same names, and its update written out with the public primitives alone: the ring's sample(),
-    bsx_mlp_forward (offpolicy_util.Hand.forward), qmix_inputs, qmix_head, update_priorities, mlp_grad, mlp_adam_step."""
+class Hand(QL.Hand):
+    """What a QMIXLearner holds, under the same names (qlearn_util.Hand), and its update written out with the public primitives alone:
+    the ring's sample(), bsx_mlp_forward (offpolicy_util.Hand.forward), qmix_inputs, qmix_head, update_priorities, mlp_grad, mlp_adam_step."""
 
-    def __init__(self, buffer, qnet, mixer, embed=8, double=True, q_scale=Q_SCALE, huber_delta=0.0, gamma=GAMMA, tau=0.01, lr=1e-3,
-                 max_grad_norm=None, updates=1, betas=(0.9, 0.999), eps=1e-8):
-        from deep_rl_battlespace_amd import learner as L
-        self.buffer, self.embed, self.double, self.q_scale, self.huber_delta, self.gamma, self.updates = buffer, embed, double, q_scale, huber_delta, gamma, updates
-        self.prioritized = hasattr(buffer, "tree")
-        self.qnet = self.actor = qnet                                               # (actor: what offpolicy_loop_util.twin_publish copies)
-        self.mixer = mixer
-        for name, net in (("qnet", qnet), ("mixer", mixer)):
-            t = copy.deepcopy(net)
-            t.__dict__.pop("_bsx_mlp_buffers", None)
-            setattr(self, "target_" + name, t)
-        self._blob_q, self._blob_tq, self.adam = qnet.pack(), self.target_qnet.pack(), L.AdamState(qnet)
-        self._blob_m, self._blob_tm, self.adam_mixer = mixer.pack(), self.target_mixer.pack(), L.AdamState(mixer)
-        dev = qnet.w1.device
-        self.hyper = L.adam_hyper(lr, betas, eps, max_grad_norm, dev, tau)
-        self.step, self.step_mixer = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
-        self.stats = torch.zeros((updates, 8), dtype=torch.float64, device=dev)
-        self.step_stats, self.step_stats_mixer = (torch.zeros((updates, 4), dtype=torch.float64, device=dev) for _ in range(2))
-        self.q = self.td = None
-
-    def update(self):
-        for u in range(self.updates):
-            self.one(*O.batch_of(self.buffer.sample()), u, weight=self.buffer.weights if self.prioritized else None)
-        return self.stats
-
-    forward = O.Hand.forward
+    def __init__(self, buffer, qnet, mixer, embed=8, q_scale=Q_SCALE, gamma=GAMMA, **kw):
+        super().__init__(buffer, dict(qnet=qnet, mixer=mixer), q_scale=q_scale, gamma=gamma, **kw)
+        self.embed = embed
 
     def one(self, obs, act, rew, obs_next, done, u, weight=None, adam=True):
         """The twelve steps on a batch -> (the Q network's gradient row, the mixer's): copies of mlp_grad's cached rows."""
         from deep_rl_battlespace_amd import learner as L
         obs, act, obs_next = obs.contiguous(), act.contiguous(), obs_next.contiguous()
-        y_cur = self.forward(self._blob_q, obs)
-        y_on = self.forward(self._blob_q, obs_next) if self.double else None
-        y_tg = self.forward(self._blob_tq, obs_next)
+        y_cur, y_on, y_tg = self.q_rows(obs, obs_next)
         x_cur, x_next = L.qmix_inputs(obs, obs_next, self.mixer.n_actors)
         hy_cur, hy_tg = self.forward(self._blob_m, x_cur), self.forward(self._blob_tm, x_next)
         head = L.qmix_head(y_cur, y_tg, hy_cur, hy_tg, act, rew, done, self.gamma, embed=self.embed, q_scale=self.q_scale, y_next_online=y_on,
@@ -643,12 +585,7 @@ class Hand:
         return row_q, row_m
 
 
-def step_arrays(x, which):
-    """dict(p, m, v, target) of lists of ten numpy arrays: x's network `which` ("qnet" / "mixer"), its moments and its target."""
-    import adam_util as AU
-    net, state = getattr(x, which), getattr(x, "adam" if which == "qnet" else "adam_mixer")
-    cut = lambda row: AU.row_to_tensors(row.detach().cpu().numpy(), 4)              # noqa: E731
-    return dict(p=AU.net_arrays(net), m=cut(state.m), v=cut(state.v), target=AU.net_arrays(getattr(x, "target_" + which)))
+step_arrays = QL.step_arrays                        # (x, which): "qnet" or "mixer"
 
 
 def learner_and_hand(team, prioritized=False, rows=None, seed=0, batch_size=B, **kw):

@@ -55,12 +55,14 @@ def test_header_library_and_binding_agree_on_the_new_entries_and_the_abi_stays()
     doc = pkg.DQNLearner.__doc__
     assert "q_scale >= r_max / (1 - gamma)" in doc and "cannot be reached" in doc and "bootstrap_gamma" in doc and "epsilon-greedy" in doc
     assert "A DQN update:" in pkg.learner.__doc__
-    # argmax4 is stated once, and both the step kernels and the head include that statement
+    # argmax4 is stated once, and both the step kernels and the head include that statement: the head through bsx_q_head.h, the
+    # discrete heads' shared header
     csrc = os.path.join(ROOT, "deep-rl-battlespace_amd", "csrc")
     defs = [f for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".inl")) and re.search(r"\bint argmax4\(", open(os.path.join(csrc, f)).read())]
     assert defs == ["bsx_argmax4.h"]
-    for f in ("bsx_step_kernel.h", "bsx_dqn_head.hip"):
+    for f in ("bsx_step_kernel.h", "bsx_q_head.h"):
         assert '#include "bsx_argmax4.h"' in open(os.path.join(csrc, f)).read(), f
+    assert '#include "bsx_q_head.h"' in open(os.path.join(csrc, "bsx_dqn_head.hip")).read()
 
 
 def test_the_workspace_is_bsx_td_heads():

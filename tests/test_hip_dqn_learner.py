@@ -12,6 +12,7 @@ import torch
 import ddpg_util as D
 import dqn_util as Q
 import offpolicy_util as O
+import qlearn_util as QL
 import yardstick_util as Y
 
 pytestmark = pytest.mark.gpu
@@ -104,75 +105,17 @@ def test_a_captured_update_runs_nothing_replays_the_eager_updates_bit_for_bit_an
     team at B = 171: a head of three tiles with split VDN rows inside the graph."""
     rows = _prio_rows(team=team) if prio else None
     (captured, _), (eager, _) = (Q.learner_and_hand(team, prio, rows=rows, batch_size=batch, mix=mix, updates=2) for _ in range(2))
-    state = [t.detach().clone() for t in captured._state()]
-    O.capture_runs_nothing(captured, Q.snapshot)
-    assert all(torch.equal(a.view(torch.uint8), b.detach().view(torch.uint8)) for a, b in zip(state, captured._state()))
-    assert any(t is captured.buffer._draws for t in captured._state()) and len(state) == len(eager._state())
-    assert not prio or all(any(t is x for t in captured._state()) for x in (captured.buffer.tree, captured.buffer._leaves, captured.buffer.max_priority))
-    draws = []
-
-    def each(u):
-        draws.append(captured.buffer.last_idx.clone())
-        assert torch.equal(captured.td.view(torch.int32), eager.td.view(torch.int32))
-        if prio:
-            tree = captured.buffer.tree.clone()
-            captured.buffer.rebuild_tree()
-            torch.cuda.synchronize()
-            assert torch.equal(tree, captured.buffer.tree), u                        # the tree is exact after every replay
-    O.replays_the_eager_updates(captured, eager, Q.snapshot, 4, each)
-    assert not torch.equal(draws[0], draws[1]) and int(captured.buffer._draws) == 8 == int(captured.step)
-    O.allocates_nothing(captured)
+    QL.captured_update(captured, eager, prio)
 
 
 def test_set_lr_is_seen_by_a_replay_and_sync_repacks_after_an_outside_edit():
-    team = Q.TEAMS[1]
-    (a, _), (b, _) = (Q.learner_and_hand(team, mix="vdn") for _ in range(2))
-    a.capture(), b.capture()
-    a.update(), b.update()
-    assert O.differing(Q.snapshot(a), Q.snapshot(b)) == []
-    a.set_lr(0.0)
-    before = Q.snapshot(a)
-    a.update(), b.update()
-    after = Q.snapshot(a)
-    assert all(torch.equal(before[f"qnet.{p}"], after[f"qnet.{p}"]) for p in D.PARAMS) and torch.equal(before["_blob_q"], after["_blob_q"])
-    assert not torch.equal(before["adam.m"], after["adam.m"]) and int(a.step) == 2                # the step ran, with a rate of 0
-    assert not torch.equal(after["qnet.w1"], Q.snapshot(b)["qnet.w1"])
-    with pytest.raises(ValueError, match="lr"):
-        a.set_lr(-1.0)
-    # an outside edit: the blobs are stale until sync()
-    with torch.no_grad():
-        a.qnet.w3.mul_(0.5)
-        a.target_qnet.b3.add_(0.25)
-    assert not torch.equal(a.qnet.pack().view(torch.int32), a._blob_q.view(torch.int32))
-    a.sync()
-    for net, blob in ((a.qnet, a._blob_q), (a.target_qnet, a._blob_tq)):
-        assert torch.equal(net.pack().view(torch.int32), blob.view(torch.int32))
+    (a, _), (b, _) = (Q.learner_and_hand(Q.TEAMS[1], mix="vdn") for _ in range(2))
+    QL.set_lr_and_sync(a, b)
 
 
 def test_publish_writes_only_its_rows_of_the_rollouts_blob():
-    import offpolicy_loop_util as LU
-    n = 2
-    env, ro = LU.rollout(n, 16, 4, False, True, 7)
-    torch.manual_seed(5)
     from deep_rl_battlespace_amd import learner as L
-    from deep_rl_battlespace_amd.rollout import StackedActor
-    qnet = StackedActor(n, env.obs_size, 4, device="cuda")
-    rows = D.ring_rows(4 * Q.B, n, env.obs_size, 4, 3)
-    learner = L.DQNLearner(O.ring(rows, Q.B), qnet, **Q.KW)
-    learner.update()
-    for cols in (range(n), range(n, 2 * n)):
-        w0 = ro.fused.weights.clone()
-        p0 = {p: getattr(ro.actor, p).detach().clone() for p in D.PARAMS}
-        learner.publish(ro, cols)
-        torch.cuda.synchronize()
-        mine, other = list(cols), [c for c in range(2 * n) if c not in cols]
-        assert torch.equal(ro.fused.weights[mine].view(torch.int32), learner._blob_q.view(torch.int32))
-        assert torch.equal(ro.fused.weights[other].view(torch.int32), w0[other].view(torch.int32))
-        for p in D.PARAMS:
-            assert torch.equal(getattr(ro.actor, p)[mine], getattr(learner.qnet, p)) and torch.equal(getattr(ro.actor, p)[other], p0[p][other]), p
-    for bad in (range(1, 2), [0, 2], range(3, 5)):
-        with pytest.raises(ValueError, match="contiguous range"):
-            learner.publish(ro, bad)
+    QL.publish_rows(lambda ring, qnet: L.DQNLearner(ring, qnet, **Q.KW), Q.B)
 
 
 def test_the_constructor_refuses_what_it_cannot_learn_from():

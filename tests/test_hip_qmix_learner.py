@@ -14,6 +14,7 @@ import torch
 
 import ddpg_util as D
 import offpolicy_util as O
+import qlearn_util as QL
 import qmix_util as X
 import yardstick_util as Y
 
@@ -103,81 +104,18 @@ def test_a_captured_update_runs_nothing_replays_the_eager_updates_bit_for_bit_an
     team = X.TEAMS[1]
     rows = D.ring_rows(4096, team[0], team[1], 4, 77) if prio else None
     (captured, _), (eager, _) = (X.learner_and_hand(team, prio, rows=rows, updates=2) for _ in range(2))
-    state = [t.detach().clone() for t in captured._state()]
-    O.capture_runs_nothing(captured, X.snapshot)
-    assert all(torch.equal(a.view(torch.uint8), b.detach().view(torch.uint8)) for a, b in zip(state, captured._state()))
-    assert any(t is captured.buffer._draws for t in captured._state()) and len(state) == len(eager._state())
-    assert all(any(t is x for t in captured._state()) for x in (captured._blob_m, captured._blob_tm, captured.adam_mixer.m, captured.step_mixer))
-    assert not prio or all(any(t is x for t in captured._state()) for x in (captured.buffer.tree, captured.buffer._leaves, captured.buffer.max_priority))
-    draws = []
-
-    def each(u):
-        draws.append(captured.buffer.last_idx.clone())
-        assert torch.equal(captured.td.view(torch.int32), eager.td.view(torch.int32))
-        if prio:
-            tree = captured.buffer.tree.clone()
-            captured.buffer.rebuild_tree()
-            torch.cuda.synchronize()
-            assert torch.equal(tree, captured.buffer.tree), u                        # the tree is exact after every replay
-    O.replays_the_eager_updates(captured, eager, X.snapshot, 4, each)
-    assert not torch.equal(draws[0], draws[1]) and int(captured.buffer._draws) == 8 == int(captured.step) == int(captured.step_mixer)
-    O.allocates_nothing(captured)
+    QL.captured_update(captured, eager, prio, X.NETS)
 
 
 def test_set_lr_is_seen_by_a_replay_and_sync_repacks_four_blobs_after_an_outside_edit():
-    team = X.TEAMS[1]
-    (a, _), (b, _) = (X.learner_and_hand(team) for _ in range(2))
-    a.capture(), b.capture()
-    a.update(), b.update()
-    assert O.differing(X.snapshot(a), X.snapshot(b)) == []
-    a.set_lr(0.0)
-    before = X.snapshot(a)
-    a.update(), b.update()
-    after = X.snapshot(a)
-    for net, blob in (("qnet", "_blob_q"), ("mixer", "_blob_m")):
-        assert all(torch.equal(before[f"{net}.{p}"], after[f"{net}.{p}"]) for p in D.PARAMS) and torch.equal(before[blob], after[blob])
-    assert not torch.equal(before["adam.m"], after["adam.m"]) and not torch.equal(before["adam_mixer.m"], after["adam_mixer.m"])
-    assert int(a.step) == 2 == int(a.step_mixer)                                                   # the steps ran, with a rate of 0
-    assert not torch.equal(after["qnet.w1"], X.snapshot(b)["qnet.w1"]) and not torch.equal(after["mixer.w1"], X.snapshot(b)["mixer.w1"])
-    with pytest.raises(ValueError, match="lr"):
-        a.set_lr(-1.0)
-    # an outside edit: the blobs are stale until sync()
-    with torch.no_grad():
-        a.qnet.w3.mul_(0.5)
-        a.target_qnet.b3.add_(0.25)
-        a.mixer.w3.mul_(0.5)
-        a.target_mixer.b3.add_(0.25)
-    pairs = ((a.qnet, a._blob_q), (a.target_qnet, a._blob_tq), (a.mixer, a._blob_m), (a.target_mixer, a._blob_tm))
-    assert all(not torch.equal(net.pack().view(torch.int32), blob.view(torch.int32)) for net, blob in pairs)
-    a.sync()
-    assert all(torch.equal(net.pack().view(torch.int32), blob.view(torch.int32)) for net, blob in pairs)
+    (a, _), (b, _) = (X.learner_and_hand(X.TEAMS[1]) for _ in range(2))
+    QL.set_lr_and_sync(a, b, X.NETS)
 
 
 def test_publish_writes_only_the_q_networks_rows_of_the_rollouts_blob():
-    import offpolicy_loop_util as LU
-    n = 2
-    env, ro = LU.rollout(n, 16, 4, False, True, 7)
-    torch.manual_seed(5)
     from deep_rl_battlespace_amd import learner as L
-    from deep_rl_battlespace_amd.rollout import StackedActor
-    qnet = StackedActor(n, env.obs_size, 4, device="cuda")
-    rows = D.ring_rows(4 * X.B, n, env.obs_size, 4, 3)
-    learner = L.QMIXLearner(O.ring(rows, X.B), qnet, **X.KW)            # the mixer is made: embed 8
-    assert learner.mixer.n_actors == 9 and learner.mixer.obs_len == n * env.obs_size and learner._actor_net.net is qnet
-    learner.update()
-    for cols in (range(n), range(n, 2 * n)):
-        w0 = ro.fused.weights.clone()
-        p0 = {p: getattr(ro.actor, p).detach().clone() for p in D.PARAMS}
-        learner.publish(ro, cols)
-        torch.cuda.synchronize()
-        mine, other = list(cols), [c for c in range(2 * n) if c not in cols]
-        assert torch.equal(ro.fused.weights[mine].view(torch.int32), learner._blob_q.view(torch.int32))
-        assert torch.equal(ro.fused.weights[other].view(torch.int32), w0[other].view(torch.int32))
-        for p in D.PARAMS:
-            assert torch.equal(getattr(ro.actor, p)[mine], getattr(learner.qnet, p)) and torch.equal(getattr(ro.actor, p)[other], p0[p][other]), p
-    for bad in (range(1, 2), [0, 2], range(3, 5)):
-        with pytest.raises(ValueError, match="contiguous range"):
-            learner.publish(ro, bad)
+    learner = QL.publish_rows(lambda ring, qnet: L.QMIXLearner(ring, qnet, **X.KW), X.B)    # the mixer is made: embed 8
+    assert learner.mixer.n_actors == 9 and learner.mixer.obs_len == 2 * learner.Do
 
 
 def test_the_constructor_refuses_what_it_cannot_learn_from():
