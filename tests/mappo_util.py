@@ -9,9 +9,16 @@ share:
   six_calls        one central minibatch from the raw calls; by_hand, the device update written out with them
   minibatch_float  a central minibatch in torch on the CPU, float64 (the restatement) or float32 (the yardstick): the two networks'
                    forwards, ppo_head_util's reference / torch_loss between them, the chain rule back through both networks
-  first_step_meets_the_bars   ppo_learner_util's test of the first optimiser step, for two networks stepped and clipped on their own
+  first_step_meets_the_bars   ppo_learner_util's test of the first optimiser step, for two networks stepped and clipped on their own;
+                   group_sums, the tied step's gradient in its float64 reference: every group's sum at each of its members
+  critic_values    the critic on join(ro.obs), all T + 1 ticks, in torch on the CPU: float64 (what the recorded values are held to) or
+                   float32 (the yardstick); value_yardstick_spread, how far the yardstick's own error moves when the join's columns and
+                   w1's rows are permuted alike; PROFILE (profiles/mappo_wide.json), value_factors and append_ratios, what is recorded
 
 Nothing here imports the native library at module level."""
+import json
+import os
+
 import numpy as np
 import torch
 
@@ -24,6 +31,7 @@ import yardstick_util as Y
 from ppo_learner_util import KW, STEPS, TAU
 
 PARAMS = L.PARAMS
+PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mappo_wide.json")
 
 
 def join(obs):
@@ -220,6 +228,17 @@ def kept_rows(ro, kind, t0=0, t1=None):
 
 
 # ---------------------------------------------------------------------------------------------------- the first step
+def group_sums(xs, g):
+    """xs: arrays [A, ...] -> float64 copies with every group's sum (g adjacent agents) at each of its members: the tied step's
+    gradient, one per group."""
+    out = []
+    for x in xs:
+        x = np.asarray(x, np.float64)
+        s = x.reshape(x.shape[0] // g, g, *x.shape[1:]).sum(1, keepdims=True)
+        out.append(np.broadcast_to(s, (x.shape[0] // g, g, *x.shape[1:])).reshape(x.shape).copy())
+    return out
+
+
 def first_step_meets_the_bars(ro, kw, g=1, norm_rtol=1e-10):
     """ppo_learner_util.first_step_meets_the_bars for a central critic: one optimiser step from one start state on the same gradient
     rows -- PPOLearner's default path (install, clip_grad_norm_ once per network, torch Adam) and its device path (adam_step of the
@@ -242,20 +261,12 @@ def first_step_meets_the_bars(ro, kw, g=1, norm_rtol=1e-10):
         torch.cuda.synchronize()
         return [AU.net_arrays(ro.actor) + ([ro.log_std.detach().cpu().numpy().copy()] if gauss else []), AU.net_arrays(ro.central_critic)]
 
-    def summed(xs):
-        """every group's float64 sum at each of its members (the tied step: one gradient per group)"""
-        out = []
-        for x in xs:
-            x = np.asarray(x, np.float64)
-            s = x.reshape(x.shape[0] // g, g, *x.shape[1:]).sum(1, keepdims=True)
-            out.append(np.broadcast_to(s, (x.shape[0] // g, g, *x.shape[1:])).reshape(x.shape).copy())
-        return out
     p0 = arrays()
     grads = [AU.row_to_tensors(rows[0].cpu().numpy(), ro.actor.n_actions) + ([rows[2].cpu().numpy()] if gauss else []),
              AU.row_to_tensors(rows[1].cpu().numpy(), 1)]
     ref = []
     for p, gr in zip(p0, grads):
-        gs = summed(gr)
+        gs = group_sums(gr, g)
         zeros = [np.zeros_like(x, dtype=np.float64) for x in p]
         norm = float(np.sqrt(sum(float((x[::g] ** 2).sum()) for x in gs)))          # a group counts once in the norm: the leaders' sums
         coef = min(1.0, hp["max_grad_norm"] / (norm + 1e-6))
@@ -292,3 +303,51 @@ def first_step_meets_the_bars(ro, kw, g=1, norm_rtol=1e-10):
         pmv = lambda p, m, v: dict(p=lead(p), m=lead(m), v=lead(v))     # noqa: E731
         AU.check_step(pmv(got[i], got_m[i], got_v[i]), pmv(*ref[i][:3]), pmv(tor[i], tor_m[i], tor_v[i]), f"net{i}", names=("p", "m", "v"))
     return figures
+
+
+# ---------------------------------------------------------------------------------------------------- the recorded values
+# the recorded values against float64: (kind, n, one_launch) at VALUE_E games (ragged against a wave) -- every join width, 5, 16, 33, 56
+VALUE_E = 33
+VALUE_CASES = {
+    "categorical-n1": ("categorical", 1, False),
+    "gaussian-n2": ("gaussian", 2, False),
+    "categorical-n3": ("categorical", 3, False),
+    "gaussian-n4": ("gaussian", 4, False),
+    "categorical-n4-one_launch": ("categorical", 4, True),
+}
+
+
+def critic_values(ro, dtype, perm=None):
+    """The critic of a central rollout on join(ro.obs), all T + 1 ticks, in torch on the CPU in `dtype` (StackedActor's own forward,
+    the raw head) -> float64 array [T + 1, E, A].  perm: a permutation of the join's columns, applied to the columns of x and to the rows
+    of w1 alike -- the same function of the same inputs, every sum of the first layer taken in another order."""
+    T1, E, A, _ = ro.obs.shape
+    x = torch.from_numpy(join(ro.obs.detach().cpu().numpy())).view(T1 * E, A, -1)
+    c = R.to(ro.central_critic, "cpu", dtype)
+    with torch.no_grad():
+        if perm is not None:
+            perm = torch.as_tensor(perm)
+            x = x[..., perm].contiguous()
+            c.w1.copy_(c.w1[:, perm, :].clone())
+        return c(x.to(dtype), squash=False)[..., 0].double().numpy().reshape(T1, E, A)
+
+
+def value_yardstick_spread(ro, ref, yard, perms=8):
+    """(max ratio, mean ratio): how far max and mean |yard - ref| of the float32 yardstick move over `perms` seeded column permutations
+    of critic_values (actor_grad_util.spread: the larger of p / base and base / p).  No kernel output enters."""
+    W = ro.central_critic.obs_len
+    others = ({"v": critic_values(ro, torch.float32, torch.randperm(W, generator=torch.Generator().manual_seed(4100 + p)))} for p in range(perms))
+    return G.spread({"v": ref}, {"v": yard}, others, ("v",))["v"]
+
+
+def value_factors(case, profile=None):
+    """(fm, fx) of a case of the recorded-values test: the exception profiles/mappo_wide.json records for it, else yardstick_util.FACTORS."""
+    return Y.factor_of(Y.recorded(PROFILE if profile is None else profile, "exceptions", case))("values")
+
+
+def append_ratios(case, ratios, spread):
+    """Appends a case's measured ratios and yardstick spread to the file BSX_MAPPO_RATIOS_OUT names, if it names one."""
+    path = os.environ.get("BSX_MAPPO_RATIOS_OUT")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps({"case": case, "ratios": [round(float(r), 4) for r in ratios], "yardstick_spread_max_mean": [round(float(s), 4) for s in spread]}) + "\n")

@@ -1,9 +1,11 @@
 """learner.PPOLearner on a PolicyRollout(central_critic=) -- MAPPO's update -- on the MI355X: a minibatch is the six calls made by hand,
 bit for bit; its gradient rows and the first optimiser step meet the float64 yardstick's bars (tests/mappo_util.py builds the
 restatement on ppo_head_util's and adam_util's references; the bars are actor_grad_util.check's and adam_util.check_step's); the
-captured update is the eager one and allocates nothing; actor and critic are clipped by their own norms; shared teams stay identical;
-a scripted team keeps every bit; shuffled minibatches; the next run's values come from the stepped critic.  T = 8; 1v1, 2v2, 3v3; 96
-and 33 games; both kinds."""
+captured update is the eager one and allocates nothing; actor and critic are clipped by their own norms; a tied team's first step
+meets the same bars against the float64 sum of its members' rows (groups of 2, 3 and 4) and shared teams stay identical; a scripted
+team keeps every bit (categorical 2v2 blue, gaussian 3v3 red); shuffled minibatches; the next run's values come from the stepped
+critic, behind the per-tick graph and behind the one-launch rollout.  T = 8; 1v1, 2v2, 3v3, 4v4 (the critic's widest input: 56
+floats on 8 planes); 96 and 33 games; both kinds."""
 import numpy as np
 import pytest
 import torch
@@ -17,7 +19,8 @@ from ppo_learner_util import HEAD_KW, KW, STEPS
 pytestmark = pytest.mark.gpu
 
 # (kind, n, E): every team size, both game counts and both kinds
-SHAPES = (("gaussian", 1, 96), ("categorical", 1, 33), ("categorical", 2, 96), ("gaussian", 2, 33), ("gaussian", 3, 96), ("categorical", 3, 33))
+SHAPES = (("gaussian", 1, 96), ("categorical", 1, 33), ("categorical", 2, 96), ("gaussian", 2, 33), ("gaussian", 3, 96), ("categorical", 3, 33),
+          ("categorical", 4, 96), ("gaussian", 4, 33))
 IDS = ["%s-n%d-E%d" % s for s in SHAPES]
 
 
@@ -78,7 +81,7 @@ def test_the_gradient_rows_of_a_minibatch_meet_the_bars_against_the_float64_rest
         assert err <= Y.scalar_bound(ref["g_log_std"], e_ls)
 
 
-@pytest.mark.parametrize("kind,n,E", (SHAPES[0], SHAPES[2], SHAPES[5]), ids=(IDS[0], IDS[2], IDS[5]))
+@pytest.mark.parametrize("kind,n,E", (SHAPES[0], SHAPES[2], SHAPES[5], SHAPES[7]), ids=(IDS[0], IDS[2], IDS[5], IDS[7]))
 def test_the_first_step_meets_the_bars_and_each_network_is_clipped_by_its_own_norm(kind, n, E):
     ro = M.central_rollout(kind, n=n, E=E)
     # a max_grad_norm small enough that both networks clip: each coefficient follows from its own norm
@@ -86,8 +89,26 @@ def test_the_first_step_meets_the_bars_and_each_network_is_clipped_by_its_own_no
     assert coef_a < 1.0 and coef_v < 1.0 and norm_a != norm_v and abs(coef_a * (norm_a + 1e-6) - coef_v * (norm_v + 1e-6)) < 1e-9
 
 
+# (kind, n, E, max_grad_norm): groups of 2, 3 (odd) and 4 with both networks clipping; a group of 4 with log_std tied too, at the suite's 0.5
+TIED = (("categorical", 2, 96, 0.01), ("gaussian", 3, 33, 0.01), ("categorical", 4, 96, 0.01), ("gaussian", 4, 33, 0.5))
+
+
+@pytest.mark.parametrize("kind,n,E,max_grad_norm", TIED, ids=["%s-g%d-E%d-clip%g" % c for c in TIED])
+def test_a_tied_teams_first_step_meets_the_bars_against_the_float64_sum_of_its_members_rows(kind, n, E, max_grad_norm):
+    """share="team" on a central critic, device and torch paths: the reference steps every group with the float64 sum of its members'
+    gradient rows and counts it once in the norm, so a step that dropped a member's row or summed the wrong planes moves the leaders
+    off it by a whole row, not by rounding.  The device adds a group's rows in float32 (as the torch path's install does), so the
+    recorded norm is held to the float64 one to 1e-6, the shared PPO test's allowance: g - 1 roundings of 2^-24 per element at most."""
+    ro = M.central_rollout(kind, n=n, E=E, group=n)
+    figures = M.first_step_meets_the_bars(ro, dict(share="team", max_grad_norm=max_grad_norm), g=n, norm_rtol=1e-6)
+    (norm_a, coef_a), (norm_v, coef_v) = figures.values()
+    assert norm_a > 0 and norm_v > 0 and norm_a != norm_v
+    if max_grad_norm == 0.01:                        # both networks clip: each coefficient follows from its own norm
+        assert coef_a < 1.0 and coef_v < 1.0 and abs(coef_a * (norm_a + 1e-6) - coef_v * (norm_v + 1e-6)) < 1e-9
+
+
 # ---------------------------------------------------------------------------------------------------- the device update
-@pytest.mark.parametrize("kind,n,E", (SHAPES[0], SHAPES[2], SHAPES[3], SHAPES[5]), ids=(IDS[0], IDS[2], IDS[3], IDS[5]))
+@pytest.mark.parametrize("kind,n,E", (SHAPES[0], SHAPES[2], SHAPES[3], SHAPES[5], SHAPES[6]), ids=(IDS[0], IDS[2], IDS[3], IDS[5], IDS[6]))
 def test_the_device_update_is_the_sequence_by_hand_captured_is_eager_and_nothing_is_allocated(kind, n, E):
     from deep_rl_battlespace_amd.learner import PPOLearner
     ro = M.central_rollout(kind, n=n, E=E)
@@ -161,9 +182,8 @@ def test_lr_critic_gives_the_critic_a_rate_of_its_own_on_both_paths():
 # ---------------------------------------------------------------------------------------------------- sharing, scripted opponent
 @pytest.mark.parametrize("device_step", [True, False])
 @pytest.mark.parametrize("kind", ["gaussian", "categorical"])
-def test_a_shared_team_stays_identical_over_two_updates_on_both_paths(kind, device_step):
+def test_a_shared_team_stays_identical_over_two_updates_on_both_paths(kind, device_step, n=2):
     from deep_rl_battlespace_amd.learner import PPOLearner, tie_
-    n = 2
     ro = M.central_rollout(kind, n=n, E=96, group=n)
     learner = PPOLearner(ro, share="team", device_step=device_step, **KW)
     assert learner.group == n
@@ -186,11 +206,18 @@ def test_a_shared_team_stays_identical_over_two_updates_on_both_paths(kind, devi
 
 
 @pytest.mark.parametrize("device_step", [True, False])
-def test_a_scripted_team_keeps_every_bit_and_the_learned_team_moves(device_step):
+@pytest.mark.parametrize("kind,n", [("categorical", 3), ("gaussian", 4)], ids=["categorical-n3", "gaussian-n4"])
+def test_a_shared_team_of_three_and_of_four_stays_identical_over_two_updates_on_both_paths(kind, n, device_step):
+    """The cheap check at the wider groups (an odd one, and the largest a tied step sums); that the members are RIGHT is the tied first
+    step's test above."""
+    test_a_shared_team_stays_identical_over_two_updates_on_both_paths(kind, device_step, n)
+
+
+@pytest.mark.parametrize("device_step", [True, False])
+def test_a_scripted_team_keeps_every_bit_and_the_learned_team_moves(device_step, kind="categorical", n=2, opponent="blue"):
     from deep_rl_battlespace_amd.learner import PPOLearner
-    n = 2
-    ro = M.central_rollout("categorical", n=n, E=96, opponent="blue")
-    scripted, learned = L.scripted_columns(n, "blue")
+    ro = M.central_rollout(kind, n=n, E=96, opponent=opponent)
+    scripted, learned = L.scripted_columns(n, opponent)
     learner = PPOLearner(ro, device_step=device_step, **KW)
     if device_step:
         lv = M.learner_view(learner)
@@ -208,8 +235,39 @@ def test_a_scripted_team_keeps_every_bit_and_the_learned_team_moves(device_step)
     assert L.blobs_are_packs(M.view(ro))
 
 
+@pytest.mark.parametrize("device_step", [True, False])
+def test_a_scripted_red_team_keeps_every_bit_at_3v3_under_the_gaussian_head(device_step):
+    """The other team, the other head (log_std rows and their moments have an agent axis too) and an odd team: blue learns."""
+    test_a_scripted_team_keeps_every_bit_and_the_learned_team_moves(device_step, "gaussian", 3, "red")
+
+
+# ---------------------------------------------------------------------------------------------------- behind the one-launch rollout
+@pytest.mark.parametrize("kind,n,E", (SHAPES[2], SHAPES[7]), ids=(IDS[2], IDS[7]))
+def test_behind_a_one_launch_rollout_a_minibatch_is_the_six_calls_and_the_next_runs_values_come_from_the_stepped_critic(kind, n, E):
+    """The form a central critic opens beyond 1v1: the ticks are one kernel, the critic's pass follows it inside the same captured run."""
+    from deep_rl_battlespace_amd.learner import PPOLearner
+    ro = M.central_rollout(kind, n=n, E=E, one_launch=True)
+    rv = M.view(ro)
+    assert ro.one_launch and ro.graph is not None and ro._value_w is None
+    learner = PPOLearner(ro, device_step=True, **KW)
+    got = [x.clone() if x is not None else None for x in learner.minibatch_grads(0, ro.T)]
+    want = M.six_calls(ro, kind, M.minibatch_of(ro, clone=True), ro.actor.pack(), ro.central_critic.pack(), HEAD_KW)
+    torch.cuda.synchronize()
+    assert _same(got, want) and float(got[3][0]) == float(ro.mask.sum()) > 0 and float(got[1].abs().max()) > 0
+    assert learner.capture() is learner
+    for update in range(2):
+        before = L.keep(rv)
+        learner.update()
+        ro.run()
+        torch.cuda.synchronize()
+        assert not torch.equal(L.keep(rv)[10], before[10]), update                    # the critic moved
+        assert torch.equal(_bits(ro._values), _bits(M.central_values(ro, ro.central_critic.pack()))), update
+        assert L.blobs_are_packs(rv), update
+    assert int(learner.step_count) == 2 * STEPS and int(learner.critic_step_count) == 2 * STEPS
+
+
 # ---------------------------------------------------------------------------------------------------- shuffle
-@pytest.mark.parametrize("kind,n,E", (SHAPES[1], SHAPES[4]), ids=(IDS[1], IDS[4]))
+@pytest.mark.parametrize("kind,n,E", (SHAPES[1], SHAPES[4], SHAPES[7]), ids=(IDS[1], IDS[4], IDS[7]))
 def test_shuffled_minibatches_with_vclip_are_the_six_calls_on_the_gathered_rows(kind, n, E):
     from deep_rl_battlespace_amd.learner import Minibatch, PPOLearner
     ro = M.central_rollout(kind, n=n, E=E)

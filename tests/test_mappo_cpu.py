@@ -2,7 +2,10 @@
 the numpy restatement of the join (tests/mappo_util.py), which the GPU is held to bit for bit, puts a plane's own observation first
 and its team-mates after it in ascending order; the widths and their refusals; the new entry point is declared, bound, exported and
 refuses bad sizes before any launch (fake addresses only: no call here reaches a kernel); PolicyRollout validates the new keyword on a
-stub env."""
+stub env; what the GPU suites' float64 references rest on -- the tied step's group sums on a row made by hand, the critic on the join
+against the network written out in numpy, a column permutation as the same function -- and profiles/mappo_wide.json against the rule
+that alone may widen a factor."""
+import json
 import os
 import re
 import types
@@ -124,3 +127,70 @@ def test_policy_rollout_validates_the_central_critic_before_any_gpu_call():
     # without the keyword nothing of it exists
     ro = PolicyRollout(env, actor, 4, value_actor=own, **kw)
     assert ro._central_w is None and ro.central_critic is None and not hasattr(ro, "_values")
+
+
+def test_the_tied_references_group_sums_put_every_groups_sum_at_each_of_its_members():
+    # four agents in two groups of two, a row of three floats each, by hand; float32 in, float64 out, the input untouched
+    row = np.array([[1, 2, 3], [10, 20, 30], [0.5, -1, 4], [0.25, 1, -4]], np.float32)
+    kept = row.copy()
+    (s,) = M.group_sums([row], 2)
+    assert s.dtype == np.float64 and s.tolist() == [[11, 22, 33], [11, 22, 33], [0.75, 0, 0], [0.75, 0, 0]] and (row == kept).all()
+    # the sum is taken in float64: 1 + 2^-30 + 2^-30 survives, as it would not in float32
+    tiny = np.array([[1.0], [2.0 ** -30], [2.0 ** -30]], np.float32)
+    assert M.group_sums([tiny], 3)[0].tolist() == [[1.0 + 2.0 ** -29]] * 3
+    # trailing axes of any depth (a w1 of [A, D, 64]), groups of 3 and 4 never mix, g = 1 is the rows themselves
+    rng = np.random.default_rng(0)
+    for A, g in ((6, 3), (8, 4), (8, 2), (6, 1)):
+        w, b = rng.standard_normal((A, 5, 7)).astype(np.float32), rng.standard_normal((A, 3)).astype(np.float32)
+        sw, sb = M.group_sums([w, b], g)
+        assert sw.shape == w.shape and sb.shape == b.shape
+        for a in range(A):
+            lo = a // g * g
+            assert np.array_equal(sw[a], w[lo:lo + g].astype(np.float64).sum(0)) and np.array_equal(sb[a], b[lo:lo + g].astype(np.float64).sum(0))
+
+
+def _recorded_stub(n, E=7, T=3, seed=5):
+    """What critic_values reads of a rollout: obs [T + 1, E, A, Do] and a central critic at trained weight scale, on the CPU."""
+    from deep_rl_battlespace_amd.learner import joint_width
+    from deep_rl_battlespace_amd.rollout import StackedActor
+    torch.manual_seed(seed)
+    critic = StackedActor(2 * n, joint_width(n), 1)
+    with torch.no_grad():
+        critic.w3.mul_(100.0)
+    obs = torch.rand((T + 1, E, 2 * n, 3 * n + 2), generator=torch.Generator().manual_seed(seed)) * 2 - 1
+    return types.SimpleNamespace(obs=obs, central_critic=critic)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 4])
+def test_critic_values_is_the_critic_on_the_join_and_a_column_permutation_is_the_same_function(n):
+    ro = _recorded_stub(n)
+    T1, E, A, Do = ro.obs.shape
+    ref, yard = M.critic_values(ro, torch.float64), M.critic_values(ro, torch.float32)
+    assert ref.shape == yard.shape == (T1, E, A) and ref.dtype == yard.dtype == np.float64
+    # row by row against the network written out in numpy float64 on the join of that row alone
+    c = {k: getattr(ro.central_critic, k).detach().double().numpy() for k in M.PARAMS}
+    ln = lambda x, g, h: (x - x.mean()) / np.sqrt(x.var() + 1e-5) * g + h     # noqa: E731
+    for t, e, a in ((0, 0, 0), (T1 - 1, E - 1, A - 1), (1, 3, n)):
+        x = M.join(ro.obs[t, e].double().numpy())[a]
+        h = np.maximum(ln(x @ c["w1"][a] + c["b1"][a, 0], c["g1"][a, 0], c["h1"][a, 0]), 0)
+        h = np.maximum(ln(h @ c["w2"][a] + c["b2"][a, 0], c["g2"][a, 0], c["h2"][a, 0]), 0)
+        assert abs(float(h @ c["w3"][a][:, 0] + c["b3"][a, 0, 0]) - ref[t, e, a]) <= 1e-12 * max(1.0, abs(ref[t, e, a]))
+    # permuted alike, float64 agrees to its own rounding and float32 stays a float32 evaluation; the critic itself is left alone
+    w1 = ro.central_critic.w1.detach().clone()
+    perm = torch.randperm(ro.central_critic.obs_len, generator=torch.Generator().manual_seed(1))
+    assert np.abs(M.critic_values(ro, torch.float64, perm) - ref).max() <= 1e-12 * np.abs(ref).max()
+    e0, e1 = np.abs(yard - ref).max(), np.abs(M.critic_values(ro, torch.float32, perm) - ref).max()
+    assert 0 < e1 < 8 * e0 and e0 < 8 * e1 and e0 < 1e-4 * np.abs(ref).max() and torch.equal(ro.central_critic.w1, w1)
+    spread = M.value_yardstick_spread(ro, ref, yard)
+    assert len(spread) == 2 and all(1.0 <= s < 8.0 for s in spread), spread
+
+
+def test_the_profile_records_every_value_case_and_widens_a_factor_only_by_the_rule_on_the_yardsticks_own_spread():
+    import yardstick_util as Y
+    prof = json.load(open(M.PROFILE))
+    assert set(prof["values"]) == set(M.VALUE_CASES) and tuple(prof["factors"]) == Y.FACTORS
+    spreads = {case: {"values": rec["yardstick_spread_max_mean"]} for case, rec in prof["values"].items()}
+    assert prof["exceptions"] == Y.exceptions_from(spreads)
+    for case, rec in prof["values"].items():
+        assert Y.within(rec["ratios_mean_max"], M.value_factors(case)), case
+    assert M.value_factors("no such case") == Y.FACTORS
